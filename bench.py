@@ -13,7 +13,8 @@ target (on CPU the reference's autocast / GradScaler are off, train_m
 float32 MFMA; bf16 = a BUILDER-CHOSEN reduced-precision mode (bfloat16 activations in HBM and bf16 MFMA operands,
 float32 accumulation / BatchNorm / loss / optimiser).  It is NOT the reference's arithmetic: on a GPU the reference
 autocasts to float16 with a GradScaler and clips the still-scaled gradients.  At N = 1 the default U-Net line also
-carries the bf16 measurement of the same step as the companion object "bfloat16".
+carries the bf16 measurement of the same step as the companion object "bfloat16".  --dump-outputs DIR also writes the
+loss and model state of the last timed step as .npy files, so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -451,9 +452,47 @@ def read_launch_csv(path):
     return rows
 
 
+DUMP_BUDGET_BYTES = 64_000_000        # --dump-outputs: all files together stay under this
+
+
+def step_outputs(losses, models):
+    """What a caller of the timed step holds after its last step: the loss(es) it returned and the state it updated in place
+    (parameters and BatchNorm statistics of every model), as float64 / float32 host arrays keyed by name."""
+    out = {k: np.asarray(float(v), np.float64) for k, v in losses.items()}
+    for prefix, m in models:
+        for k, v in m.state_dict().items():
+            v = np.asarray(v)
+            out[prefix + k] = v.astype(np.float64) if v.dtype.kind in "iu" else v.astype(np.float32, copy=False)
+    return out
+
+
+def dump_outputs(outputs, out_dir, budget=DUMP_BUDGET_BYTES):
+    """Write every array as `out_dir/<name>.npy`.  If they would take more than `budget` bytes in all, every array of more
+    than 2^16 elements is cut to a fixed sample of its flattened elements, the same in every run: sorted indices drawn
+    without replacement by a generator seeded with the CRC-32 of the name, as many as the budget leaves room for."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    budget -= 256 * len(outputs)                                     # .npy headers
+    big = {k for k, v in outputs.items() if v.size > 1 << 16}
+    small_bytes = sum(v.nbytes for k, v in outputs.items() if k not in big)
+    big_bytes = sum(outputs[k].nbytes for k in big)
+    keep = 1.0 if small_bytes + big_bytes <= budget else max(0.0, budget - small_bytes) / big_bytes
+    total, sampled = 0, 0
+    for k, v in outputs.items():
+        if k in big and keep < 1.0:
+            n = int(v.size * keep)
+            idx = np.sort(np.random.default_rng(zlib.crc32(k.encode())).choice(v.size, n, replace=False))
+            v, sampled = v.reshape(-1)[idx], sampled + 1
+        path = os.path.join(out_dir, k + ".npy")
+        np.save(path, v)
+        total += os.path.getsize(path)
+    log(f"dumped {len(outputs)} arrays ({sampled} sampled, {total / 1e6:.1f} MB) to {out_dir}")
+
+
 def measure(model, ctx, D, d_x, d_y, hp, args, dtype, rank, launch_csv=None):
     """W untimed + K timed steps of `model` in arithmetic `dtype` (barrier + synchronize on both sides, max over
-    ranks), then the per-family HIP-event profile on separate steps."""
+    ranks), then the per-family HIP-event profile on separate steps.  With --dump-outputs, rank 0 also returns what the
+    last timed step computed (`step_outputs`), read before the sustained sample and the profile steps train on."""
     import tempfile
     B, S = args.batch, args.size
     model.set_compute_dtype(MODE_BY_DTYPE[dtype])
@@ -480,6 +519,7 @@ def measure(model, ctx, D, d_x, d_y, hp, args, dtype, rank, launch_csv=None):
     loss, _ = model.last_loss()
     if not np.isfinite(loss):
         raise SystemExit(f"non-finite loss {loss}")
+    outputs = step_outputs({"loss": loss}, [("", model)]) if args.dump_outputs and rank == 0 else None
     # ---- sustained sample: the contract's K steps are a fraction of a second on a power-bound kernel mix; the same step for
     # about two more seconds, in windows of 20 steps (a synchronisation between windows), shows the clock the chip settles at
     sustained = None
@@ -524,7 +564,8 @@ def measure(model, ctx, D, d_x, d_y, hp, args, dtype, rank, launch_csv=None):
                 fam_ov = ctx.profile_report()
         ctx.set_overlap(not os.environ.get("RFI_NO_OVERLAP") == "1")
     D.barrier()
-    return {"wall": wall, "ev_ms": ev_ms, "loss": float(loss), "fam": fam, "fam_ov": fam_ov, "launches": launches, "sustained": sustained}
+    return {"wall": wall, "ev_ms": ev_ms, "loss": float(loss), "fam": fam, "fam_ov": fam_ov, "launches": launches, "sustained": sustained,
+            "outputs": outputs}
 
 
 def synthetic_instances(batch, size, seed, per_image=3):
@@ -607,6 +648,9 @@ def run_maskrcnn(args, ctx, D, rank, local_rank, world, n_ranks_seen):
     log(f"[{args.dtype}] timed region done: {wall * 1e3 / args.steps:.1f} ms/step")
     if not np.isfinite(losses["loss"]):
         raise SystemExit(f"non-finite loss {losses}")
+    outputs = None
+    if args.dump_outputs and rank == 0:
+        outputs = step_outputs(losses, [(f"{n}.", m) for n, m in zip(("backbone", "rpn", "box", "mask"), det.models())])
     fam, launches, host_ms = {}, [], None
     if args.profile_steps > 0:
         import tempfile
@@ -662,6 +706,8 @@ def run_maskrcnn(args, ctx, D, rank, local_rank, world, n_ranks_seen):
     if world == 1 and not args.no_cpu_baseline:
         log("cpu baseline ...")
         out["cpu_baseline"] = cpu_baseline_maskrcnn(S, B)
+    if outputs is not None:
+        dump_outputs(outputs, args.dump_outputs)
     print(json.dumps(out), flush=True)
     beat("done")
     D.shutdown()
@@ -708,9 +754,16 @@ def main():
     ap.add_argument("--no-bf16-line", "--no-float32-line", dest="no_companion", action="store_true",
                     help="skip the bfloat16 measurement the default N = 1 U-Net line carries next to the float32 one")
     ap.add_argument("--launch-csv", default=None, help="write the per-launch HIP-event profile here")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last of them computed (the loss and the updated model state; "
+                         "with the bfloat16 companion line its step too, as bfloat16.*) as DIR/<name>.npy in float32 / "
+                         "float64, at most 64 MB in all (a fixed, seeded sample of larger arrays beyond that); the inputs "
+                         "and initial weights are seeded, so two builds run with the same arguments can be compared")
     ap.add_argument("--dry-run", action="store_true",
                     help="control plane only (rendezvous, barrier, max-over-ranks, one JSON line); no GPU work")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and not os.environ.get("RFI_BENCH_WORKER"):
         raise SystemExit(Supervisor(args.gpus, sys.argv[1:]).run())
@@ -864,6 +917,11 @@ def main():
     if world == 1 and not args.no_cpu_baseline:
         log("cpu baseline ...")
         out["cpu_baseline"] = cpu_baseline(args.workload, args.features, S, B)
+    if res["outputs"] is not None:
+        outputs = dict(res["outputs"])
+        if second is not None:            # the bfloat16 companion line's step: same names under "bfloat16."
+            outputs.update(("bfloat16." + k, v) for k, v in second["outputs"].items())
+        dump_outputs(outputs, args.dump_outputs)
     print(json.dumps(out), flush=True)
     beat("done")
     D.shutdown()

@@ -67,9 +67,13 @@ def init_gradient_exchange(ctx, rank: int, world: int):
 
 
 def barrier():
+    """A barrier on the control plane that never touches the GPU: an all-reduce of one host integer over gloo.
+    (`torch.distributed.barrier` asks torch for the machine's accelerator first, which initialises the HIP runtime and
+    opens the GPU in every rank -- also in a process that does no GPU work, such as bench.py --dry-run.)"""
+    import torch
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized():
-        dist.barrier()
+        dist.all_reduce(torch.zeros(1, dtype=torch.int64), op=dist.ReduceOp.SUM)
 
 
 def shutdown():
@@ -78,7 +82,7 @@ def shutdown():
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized():
         try:
-            dist.barrier()
+            barrier()
         finally:
             dist.destroy_process_group()
 

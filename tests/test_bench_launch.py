@@ -146,3 +146,37 @@ def test_bench_supervisor_attempt_limit_runs_from_the_end_of_the_imports():
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1 and json.loads(lines[0])["fallback"] == "unbucketed", r.stdout
     assert "after the imports" in r.stderr and "attempt 1 (bucketed exchange) failed" in r.stderr, r.stderr[-1500:]
+
+
+def test_bench_rejects_a_step_count_below_one():
+    """--steps sets the number of timed steps; zero of them is an error up front, not a division by zero after the loop."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--steps", "0"], env=_clean_env(),
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr, r.stderr[-1500:]
+
+
+def test_bench_dump_outputs_stays_within_its_budget_with_a_fixed_sample(tmp_path):
+    """--dump-outputs: every array becomes <name>.npy; over the byte budget the large arrays are cut to a sample of their
+    elements that is the same in every run, small arrays and scalars stay whole."""
+    import numpy as np
+
+    import bench
+    rng = np.random.default_rng(0)
+    outputs = {"loss": np.asarray(0.5, np.float64), "enc.weight": rng.standard_normal(1_000_000).astype(np.float32),
+               "enc.bias": rng.standard_normal(64).astype(np.float32)}
+    full = tmp_path / "full"
+    bench.dump_outputs(outputs, str(full))
+    for k, v in outputs.items():
+        np.testing.assert_array_equal(np.load(full / f"{k}.npy"), v)
+    runs = []
+    for name in ("a", "b"):
+        bench.dump_outputs(outputs, str(tmp_path / name), budget=1_000_000)
+        assert sum(f.stat().st_size for f in (tmp_path / name).iterdir()) <= 1_000_000
+        runs.append({k: np.load(tmp_path / name / f"{k}.npy") for k in outputs})
+    w = runs[0]["enc.weight"]
+    assert 0 < w.size < outputs["enc.weight"].size and w.dtype == np.float32
+    assert np.isin(w, outputs["enc.weight"]).all()
+    for k in outputs:
+        np.testing.assert_array_equal(runs[0][k], runs[1][k])
+    np.testing.assert_array_equal(runs[0]["enc.bias"], outputs["enc.bias"])
+    assert float(runs[0]["loss"]) == 0.5

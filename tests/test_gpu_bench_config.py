@@ -147,3 +147,34 @@ def test_bench_configuration_masks_agree_across_modes():
     assert (a != b).mean() <= 1e-4
     if (a | b).mean() > 0.01:
         assert metrics_ref.evaluate_segmentation(a, b)["iou"] >= 1 - 1e-3
+
+
+def test_bench_dump_outputs_is_the_state_after_its_timed_steps(tmp_path):
+    """bench.py --dump-outputs writes what its timed path computed in the last timed step: the loss and the model state after
+    W + K steps, for the float32 line and its bfloat16 companion -- bit for bit what the same steps on the same seeded
+    inputs give through the model API (the sustained sample and the profile steps that follow do not leak into it)."""
+    import os
+    import subprocess
+    import sys
+
+    from rfi_toolbox_amd._lib import Hyper
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    b, s, f, warmup, steps = 4, 128, 32, 2, 3            # the benched patch and width, fewer patches
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--batch", str(b), "--size", str(s),
+                        "--features", str(f), "--warmup", str(warmup), "--steps", str(steps), "--sustain-steps", "20",
+                        "--profile-steps", "1", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d_x, d_y = make_training_patches_device(b, s, seed=1234, device=0)
+    hp = Hyper(1e-4, 0.9, 0.999, 1e-8, 1e-5, 1.0)
+    for mode, prefix in (("float32", ""), ("bfloat16", "bfloat16.")):
+        torch.manual_seed(1234)
+        m = UNet(3, 1, f, device=0).train().set_compute_dtype(mode)
+        for _ in range(warmup + steps):
+            m.train_step_async(d_x.ptr, d_y.ptr, b, s, s, hp)
+        loss, _ = m.last_loss()
+        assert float(np.load(tmp_path / f"{prefix}loss.npy")) == loss
+        for k, v in m.state_dict().items():
+            got = np.load(tmp_path / f"{prefix}{k}.npy")
+            assert got.dtype in (np.float32, np.float64), (k, got.dtype)
+            np.testing.assert_array_equal(got, v.numpy(), err_msg=prefix + k)
