@@ -430,7 +430,8 @@ size_t rfi_op_rpn_loss_ws_bytes(void);
  * rpn_loss_devcount: rfi_op_rpn_loss_dev with the normaliser read from device memory (the sampler's count).
  * fastrcnn_loss_dev: rfi_op_fastrcnn_loss leaving (classification, box) in loss2_dev; workspace as rpn_loss_dev.
  * anchor_match_batched_ws: rfi_op_anchor_match_batched with a caller-held workspace of images x gt_max floats.
- * segsort_u64: n_segs segments of `stride` (a power of two <= 8192) 64-bit keys, each sorted ascending in place.
+ * segsort_u64: n_segs segments of `stride` (a power of two, 2 .. 65536) 64-bit keys, each sorted ascending in place (up to
+ *   8192 keys: one launch sorting in LDS; longer segments: a multi-pass bitonic sort through global memory).
  * sample_keys: labels [images][n] (1 positive, 0 negative) -> keys [images][stride] = class << 48 | r << 16 | i with
  *   r = Philox4x32-10(counter (i, image, stream0 + class, step), key seed).x; rows >= count[image] (null: n) get ~0.
  * rpn_sample_apply: from the SORTED keys, `batch` anchors per image (at most max_pos positive, smallest keys first) keep their

@@ -6,7 +6,8 @@
 // package's conventions; oracle/mask_rcnn_ref.py restates them in NumPy -- parity unpinned by the reference.
 //
 // Everything here is small integer / box work on a few thousand elements per image: one workgroup per image (or per
-// (image, level) set), 64-bit keys sorted in LDS by a bitonic network, results written in a fixed order -- no atomics on
+// (image, level) set), 64-bit keys sorted in LDS by a bitonic network (segments over 8192 keys -- images over 128 px -- by the
+// same network in several passes through global memory), results written in a fixed order -- no atomics on
 // floats, no data-dependent launch geometry, nothing read back by the host.
 //
 // Random choices: element i of image b draws r = Philox4x32-10(counter (i, b, stream, step), key = seed).x and a class
@@ -68,6 +69,50 @@ __global__ __launch_bounds__(1024) void segsort_kernel(u64* __restrict__ keys, i
     for (int i = threadIdx.x; i < stride; i += blockDim.x) s_keys[i] = seg[i];
     bitonic_sort(s_keys, stride);
     for (int i = threadIdx.x; i < stride; i += blockDim.x) seg[i] = s_keys[i];
+}
+
+// ---------------------------------------------------------------- segmented sort of segments longer than LDS holds
+// The same bitonic network as bitonic_sort over a whole segment of `stride` keys (a power of two, 16384 .. 65536), cut into
+// launches: LDS passes over chunks of kChunk keys do every step j < kChunk, one global compare-exchange launch does each step
+// j >= kChunk.  The direction of a pair comes from its index in the SEGMENT (not in the chunk).
+constexpr int kChunk = 8192;
+
+// k_merge == 0: stages k = 2 .. kChunk of the network (chunk c of a segment ends up ascending for even c, descending for
+// odd c); k_merge > kChunk: the steps j = kChunk / 2 .. 1 of stage k_merge
+__global__ __launch_bounds__(1024) void segsort_chunk_kernel(u64* __restrict__ keys, int stride, int k_merge) {
+    extern __shared__ u64 s_keys[];
+    const size_t off = (size_t)blockIdx.x * kChunk;
+    const int base = (int)(off & (size_t)(stride - 1));                       // index of the chunk's first key in its segment
+    u64* c = keys + off;
+    for (int i = threadIdx.x; i < kChunk; i += blockDim.x) s_keys[i] = c[i];
+    const int k_lo = k_merge ? k_merge : 2, k_hi = k_merge ? k_merge : kChunk;
+    for (int k = k_lo; k <= k_hi; k <<= 1)
+        for (int j = min(k, kChunk) >> 1; j > 0; j >>= 1) {
+            __syncthreads();
+            for (int t = threadIdx.x; t < (kChunk >> 1); t += blockDim.x) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+                const int p = i | j;
+                const bool up = ((base + i) & k) == 0;
+                const u64 a = s_keys[i], b = s_keys[p];
+                if ((a > b) == up) { s_keys[i] = b; s_keys[p] = a; }
+            }
+        }
+    __syncthreads();
+    for (int i = threadIdx.x; i < kChunk; i += blockDim.x) c[i] = s_keys[i];
+}
+
+// one step (k, j >= kChunk) of the network over every segment: pair t of a segment compares keys i and i | j
+__global__ __launch_bounds__(kB) void segsort_step_kernel(u64* __restrict__ keys, int stride, int k, int j, long long pairs) {
+    const int half = stride >> 1;
+    for (long long g = (long long)blockIdx.x * kB + threadIdx.x; g < pairs; g += (long long)gridDim.x * kB) {
+        const int t = (int)(g % half);
+        u64* s = keys + (size_t)(g / half) * stride;
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+        const int p = i | j;
+        const bool up = (i & k) == 0;
+        const u64 a = s[i], b = s[p];
+        if ((a > b) == up) { s[i] = b; s[p] = a; }
+    }
 }
 
 // ---------------------------------------------------------------- sampler keys: class << 48 | random << 16 | index
@@ -326,7 +371,25 @@ int pow2_at_least(int n) {
 
 // ======================================================================================== launch wrappers
 void launch_segsort_u64(rfi_ctx* ctx, unsigned long long* keys, int n_segs, int stride) {
-    RFI_REQUIRE(n_segs > 0 && stride >= 2 && stride <= 8192 && (stride & (stride - 1)) == 0, "segsort: segments of 2 .. 8192 keys, a power of two");
+    RFI_REQUIRE(n_segs > 0 && stride >= 2 && stride <= 65536 && (stride & (stride - 1)) == 0, "segsort: segments of 2 .. 65536 keys, a power of two");
+    if (stride > kChunk) {
+        // log2(stride / kChunk) stages past the chunk sort, each: its global steps j = k / 2 .. kChunk, then one LDS pass
+        ProfScope ps(ctx, FAM_ELEMWISE, 0, (double)n_segs * stride * 16 * 8);
+        const unsigned chunks = (unsigned)((long long)n_segs * stride / kChunk);
+        const long long pairs = (long long)n_segs * (stride >> 1);
+        const unsigned grid = (unsigned)std::min<long long>(cdiv(pairs, kB), 4096);
+        hipLaunchKernelGGL(segsort_chunk_kernel, dim3(chunks), dim3(1024), (size_t)kChunk * 8, ctx->stream, keys, stride, 0);
+        check_launch("segsort_chunk");
+        for (int k = 2 * kChunk; k <= stride; k <<= 1) {
+            for (int j = k >> 1; j >= kChunk; j >>= 1) {
+                hipLaunchKernelGGL(segsort_step_kernel, dim3(grid), dim3(kB), 0, ctx->stream, keys, stride, k, j, pairs);
+                check_launch("segsort_step");
+            }
+            hipLaunchKernelGGL(segsort_chunk_kernel, dim3(chunks), dim3(1024), (size_t)kChunk * 8, ctx->stream, keys, stride, k);
+            check_launch("segsort_chunk");
+        }
+        return;
+    }
     ProfScope ps(ctx, FAM_ELEMWISE, 0, (double)n_segs * stride * 16);
     const int threads = stride >= 2048 ? 1024 : (stride >= 512 ? 256 : 64);      // (a compare-exchange pair per thread and stage)
     hipLaunchKernelGGL(segsort_kernel, dim3(n_segs), dim3(threads), (size_t)stride * 8, ctx->stream, keys, stride);

@@ -35,6 +35,7 @@ from .mask_head import MaskHead
 from .rpn_head import RPNHead
 
 _STRIDES = (4, 8, 16, 32, 64)
+_MAX_ANCHORS = 65536                  # rfi_op_sample_keys: the anchor index is 16 bits of the sampler's key
 
 
 def _level_anchors(h, w, stride, size):
@@ -112,6 +113,18 @@ class MaskRCNN:
         return [_level_anchors(h // s, w // s, s, 2.0 * s) for s in _STRIDES]
 
     @staticmethod
+    def _check_size(h, w, train):
+        """The image sizes the detector supports, checked before anything is allocated or launched: H and W positive
+        multiples of 64 (the backbone's five stride-2 stages and P6), and for ``train_step`` at most 65,536 anchors per image
+        (the samplers pack an anchor's index into 16 bits of a sort key): 384 x 384 is the largest square size."""
+        if h <= 0 or w <= 0 or h % 64 or w % 64:
+            raise ValueError(f"MaskRCNN: H and W must be positive multiples of 64, got {h} x {w}")
+        if train:
+            a = 4 * sum((h // s) * (w // s) for s in _STRIDES)
+            if a > _MAX_ANCHORS:
+                raise ValueError(f"MaskRCNN.train_step: at most {_MAX_ANCHORS} anchors per image, {h} x {w} has {a}")
+
+    @staticmethod
     def _level_thresholds(size):
         half = np.float32(size) / np.float32(2.0)
         return tuple(float(np.float32(c * half) * np.float32(c * half)) for c in (0.5, 1.0, 2.0))
@@ -179,6 +192,7 @@ class MaskRCNN:
     def predict(self, images):
         x = np.ascontiguousarray(np.asarray(images, np.float32))
         n, h, w, _ = x.shape
+        self._check_size(h, w, False)
         for m in (self.rpn, self.box, self.mask):
             m.eval()
         feats = self.backbone.forward_features(x)
@@ -228,6 +242,7 @@ class MaskRCNN:
         b = getattr(self, "_buf", None)
         if getattr(self, "_buf_key", None) == key and b.gcap >= gmax:
             return b
+        self._check_size(h, w, True)
         ctx, F = self.backbone.ctx, self.F
         b = type("Buffers", (), {})()
         b.gcap = max(8, 2 * gmax)

@@ -20,16 +20,84 @@ def _P(d):
 
 
 def test_segmented_sort_of_u64_keys():
+    """One LDS launch up to 8192 keys per segment; 16384 .. 65536 (images over 128 px) the multi-pass path."""
     from rfi_toolbox_amd._lib import check, lib
     ctx = _ctx()
     rng = np.random.default_rng(0)
-    for segs, stride in ((3, 2), (5, 64), (7, 1024), (4, 8192)):
+    for segs, stride in ((3, 2), (5, 64), (7, 1024), (4, 8192), (3, 16384), (4, 32768), (3, 65536)):
         k = rng.integers(0, 2 ** 63, (segs, stride), dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, (segs, stride), dtype=np.uint64)
         k[0, : stride // 2] = np.uint64(0xFFFFFFFFFFFFFFFF)                      # padding keys and ties
         k[-1, :] = k[-1, 0]
         d = ctx.to_device(k)
         check(lib.rfi_op_segsort_u64(ctx.handle, _P(d), segs, stride))
         assert np.array_equal(d.numpy(), np.sort(k, axis=1)), (segs, stride)
+
+
+def test_segmented_sort_of_ordered_segments_past_lds():
+    """Already ascending and descending segments (a wrong merge direction leaves them unsorted or reversed), runs of equal
+    keys crossing the 8192-key chunks, keys with the top bit set (unsigned order) -- next to segments that must stay apart."""
+    from rfi_toolbox_amd._lib import check, lib
+    ctx = _ctx()
+    rng = np.random.default_rng(5)
+    for stride in (16384, 32768, 65536):
+        r = np.sort(rng.integers(0, 2 ** 64 - 1, stride, dtype=np.uint64, endpoint=True))
+        k = np.stack([r, r[::-1], np.repeat(r[:: 64], 64)[::-1], r[rng.permutation(stride)],
+                      np.concatenate([r[stride // 2:], r[: stride // 2]])])             # two ascending halves swapped
+        d = ctx.to_device(np.ascontiguousarray(k))
+        check(lib.rfi_op_segsort_u64(ctx.handle, _P(d), len(k), stride))
+        got = d.numpy()
+        assert np.array_equal(got, np.sort(k, axis=1)), stride
+        assert np.array_equal(got[0], r) and np.array_equal(got[1], r)
+
+
+def _rpn_sample(ctx, labels, targets, off, stride, seed, step, batch, max_pos):
+    """sample_keys -> segsort_u64 -> rpn_sample_apply over len(off) - 1 levels; (labels, targets) per image as the device left
+    them, the sampled count, and the labels the counter-based oracle keeps."""
+    from oracle.mask_rcnn_ref import sample_order
+    from rfi_toolbox_amd._lib import check, lib
+    B, n, L = labels.shape[0], int(off[-1]), len(off) - 1
+    dl, dt = ctx.to_device(labels), ctx.to_device(targets)
+    keys, cnt = ctx.empty((B, stride), np.uint64), ctx.to_device(np.zeros(4, np.int32))
+    lev_l = [ctx.empty((B * int(off[l + 1] - off[l]),), np.int8) for l in range(L)]
+    lev_t = [ctx.empty((B * int(off[l + 1] - off[l]), 4), np.float32) for l in range(L)]
+    check(lib.rfi_op_sample_keys(ctx.handle, _P(dl), B, n, None, seed, step, 0, _P(keys), stride))
+    check(lib.rfi_op_segsort_u64(ctx.handle, _P(keys), B, stride))
+    pl, pt = (C.c_void_p * L)(*[a.ptr for a in lev_l]), (C.c_void_p * L)(*[a.ptr for a in lev_t])
+    check(lib.rfi_op_rpn_sample_apply(ctx.handle, _P(keys), B, n, stride, batch, max_pos, _P(dl), _P(dt), L, off.ctypes.data_as(C.c_void_p),
+                                      pl, pt, _P(cnt)))
+    got = np.concatenate([a.numpy().reshape(B, -1) for a in lev_l], 1)
+    got_t = np.concatenate([a.numpy().reshape(B, -1, 4) for a in lev_t], 1)
+    want = labels.copy()
+    for i in range(B):
+        pos, neg = np.flatnonzero(labels[i] == 1), np.flatnonzero(labels[i] == 0)
+        npos = min(len(pos), max_pos)
+        want[i, sample_order(pos, i, 0, seed, step)[npos:]] = -1
+        want[i, sample_order(neg, i, 1, seed, step)[batch - npos:]] = -1
+    return got, got_t, int(cnt.numpy()[0]), want
+
+
+@pytest.mark.parametrize("size", [256, 384])
+def test_rpn_sampler_at_large_image_anchor_counts(size):
+    """The anchors of a size x size image over five levels (256: 21,824 anchors, stride 32768; 384: 49,104, stride 65536 --
+    indices past 2^15 in the key's 16-bit field), positives and negatives spread over every level."""
+    ctx = _ctx()
+    rng = np.random.default_rng(6)
+    off = np.concatenate([[0], np.cumsum([4 * (size // s) ** 2 for s in (4, 8, 16, 32, 64)])]).astype(np.int32)
+    n, B = int(off[-1]), 3
+    stride = 1 << (n - 1).bit_length()
+    labels = rng.choice([-1, 0, 1], size=(B, n), p=[0.3, 0.69, 0.01]).astype(np.int8)
+    labels[1] = np.where(rng.random(n) < 0.5, 1, 0)                              # more positives than the cap
+    labels[2, : n - 100] = -1                                                    # candidates only at the end (level 4)
+    targets = rng.standard_normal((B, n, 4)).astype(np.float32)
+    seed, step, batch, max_pos = (123 << 32) | 17, 3, 256, 128
+    got, got_t, cnt, want = _rpn_sample(ctx, labels, targets, off, stride, seed, step, batch, max_pos)
+    assert np.array_equal(got, want)
+    assert np.array_equal(got_t, targets)
+    assert cnt == int((want >= 0).sum())
+    assert (want[1] == 1).sum() == max_pos and (want >= 0).sum(1)[0] == batch and (want[2] >= 0).sum() == (labels[2] >= 0).sum() <= 100
+    assert (np.flatnonzero(want[0] >= 0) >= off[1]).any()                       # sampled anchors beyond level 0 ...
+    if size == 384:
+        assert (np.flatnonzero(want[1] >= 0) >= 1 << 15).any()                  # ... and past index 32767
 
 
 def test_rpn_sampler_against_the_counter_based_oracle():
@@ -127,6 +195,52 @@ def test_topk_decode_and_post_nms_selection():
         want = np.concatenate([gb[i].reshape(-1, 4)[sel], gt[i, :gcnt[i]]])
         assert gpc[i] == len(want)
         assert np.array_equal(gp[i, :len(want)], want), i
+
+
+def test_topk_decode_of_a_level_past_lds():
+    """Level 0 of a 256 x 256 image: 64 x 64 pixels x 4 anchors = 16,384 keys (the multi-pass sort).  Image 0: a tie of 5,000
+    scores above every other, spread over the whole level (the K best are its lowest indices); image 1: 0.0 and -0.0 tied at
+    the top (they compare equal: index order), the rest negative; image 2: plain random with a collapsing box."""
+    from oracle import detection_ref
+    from rfi_toolbox_amd._lib import check, lib
+    from rfi_toolbox_amd.models.mask_rcnn import _level_anchors, _topk_desc_stable
+    ctx = _ctx()
+    rng = np.random.default_rng(7)
+    B, K, A, hl, st, size = 3, 200, 4, 64, 4, 256.0
+    P_ = hl * hl
+    head = rng.standard_normal((B, P_, 5 * A)).astype(np.float32)
+    head[:, :, A:] *= 0.5
+    sc = head[:, :, :A].reshape(B, -1)                                           # (a copy: written back below)
+    sc[0, rng.choice(P_ * A, 5000, replace=False)] = 6.0
+    sc[1] = -np.abs(sc[1]) - 1.0
+    zeros = rng.choice(P_ * A, 300, replace=False)
+    sc[1, zeros] = np.where(np.arange(300) % 2 == 0, np.float32(-0.0), np.float32(0.0))
+    head[:, :, :A] = sc.reshape(B, P_, A)
+    j = int(np.argsort(-sc[2], kind="stable")[3])
+    head[2, j // A, A + 4 * (j % A) + 2] = -30.0                                 # the fourth best box collapses (width under min_size)
+    anchors = _level_anchors(hl, hl, st, 2.0 * st)
+    stride = P_ * A
+    dh, da, keys = ctx.to_device(head), ctx.to_device(anchors), ctx.empty((B, stride), np.uint64)
+    boxes = ctx.to_device(np.full((B, 1, K, 4), np.nan, np.float32))
+    scores, counts = ctx.to_device(np.full((B, 1, K), np.nan, np.float32)), ctx.empty((B, 1), np.int32)
+    check(lib.rfi_op_topk_keys(ctx.handle, _P(dh), B, P_, A, _P(keys), stride))
+    check(lib.rfi_op_segsort_u64(ctx.handle, _P(keys), B, stride))
+    check(lib.rfi_op_topk_decode(ctx.handle, _P(keys), B, stride, P_, A, K, _P(dh), _P(da), size, size, 1e-2, _P(boxes), _P(scores),
+                                 _P(counts), 1, 0))
+    sc, dl = head[:, :, :A].reshape(B, -1), head[:, :, A:].reshape(B, -1, 4)
+    top = _topk_desc_stable(sc, K)
+    assert np.array_equal(top[0], np.sort(np.flatnonzero(sc[0] == 6.0))[:K]) and np.array_equal(top[1], np.sort(zeros)[:K])
+    gb, gs, gc = boxes.numpy()[:, 0], scores.numpy()[:, 0], counts.numpy()[:, 0]
+    for i in range(B):
+        bx = detection_ref.decode_boxes(anchors[top[i]], dl[i, top[i]], image_size=(256, 256))
+        ok = ((bx[:, 2] - bx[:, 0]) >= 1e-2) & ((bx[:, 3] - bx[:, 1]) >= 1e-2)
+        first = np.argsort(~ok, kind="stable")
+        c = int(ok.sum())
+        assert gc[i] == c and (i != 2 or not ok[3]), i
+        want_s = sc[i, top[i]][first][:c]
+        assert np.array_equal(gs[i, :c], want_s) and np.isneginf(gs[i, c:]).all(), i
+        assert np.array_equal(np.signbit(gs[i, :c]), np.signbit(want_s)), i                # the score itself, not only its value
+        np.testing.assert_allclose(gb[i, :c], bx[first][:c], rtol=0, atol=2e-3)
 
 
 def test_roi_sampler_compaction_and_levels():

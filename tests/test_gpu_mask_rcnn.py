@@ -10,15 +10,19 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-def _batch(rng, n=2, size=128):
-    x = rng.standard_normal((n, size, size, 3)).astype(np.float32) * 0.1
+def _batch(rng, n=2, size=128, box_scale=1.0):
+    """n images of size (an int: square, or (H, W)) with two box instances each, placed anywhere in the image; box sides
+    20 .. 60 px at 128, scaled with the image and by box_scale (> 1: RoIs on the upper pyramid levels too)."""
+    H, W = (size, size) if np.isscalar(size) else size
+    x = rng.standard_normal((n, H, W, 3)).astype(np.float32) * 0.1
     targets = []
     for i in range(n):
         boxes, masks = [], []
         for _ in range(2):
             w, h = rng.integers(20, 60, 2)
-            x1, y1 = rng.integers(0, size - w), rng.integers(0, size - h)
-            m = np.zeros((size, size), np.uint8)
+            w, h = int(w * box_scale * W) // 128, int(h * box_scale * H) // 128
+            x1, y1 = rng.integers(0, W - w), rng.integers(0, H - h)
+            m = np.zeros((H, W), np.uint8)
             m[y1:y1 + h, x1:x1 + w] = 1
             x[i, y1:y1 + h, x1:x1 + w] += 2.0
             boxes.append([x1, y1, x1 + w, y1 + h]); masks.append(m)
@@ -77,8 +81,13 @@ def _states(det):
     return {"backbone": det.backbone.state_dict(), "rpn": det.rpn.state_dict(), "box": det.box.state_dict(), "mask": det.mask.state_dict()}
 
 
-@pytest.mark.parametrize("widths", [(16, 64, 128), (64, 256, 1024)], ids=["reduced", "resnet50_fpn256"])
-def test_assembled_step_against_the_oracle(widths):
+# 128 x 128 at both widths (the benched size: 5,456 anchors, every sort in one LDS launch); 256 x 256 (21,824 anchors: the
+# anchor keys in segments of 32768, level 0's top-k in 16384), 128 x 384 (16,368: non-square, 16384) and 384 x 384 (49,104:
+# 65536, the largest size train_step accepts) through the multi-pass sort
+@pytest.mark.parametrize("widths, size, box_scale", [((16, 64, 128), 128, 1.0), ((64, 256, 1024), 128, 1.0), ((16, 64, 128), 256, 1.6),
+                                                     ((16, 64, 128), (128, 384), 1.6), ((16, 64, 128), 384, 1.6)],
+                         ids=["reduced", "resnet50_fpn256", "reduced_256", "reduced_128x384", "reduced_384"])
+def test_assembled_step_against_the_oracle(widths, size, box_scale):
     import torch
     from oracle.mask_rcnn_ref import MaskRCNNRef
     from rfi_toolbox_amd.models import MaskRCNN
@@ -86,7 +95,7 @@ def test_assembled_step_against_the_oracle(widths):
     det = MaskRCNN(2, 3, *widths, seed=7)
     det.keep_trace = True
     ref = MaskRCNNRef(2, 3, *widths).load(_states(det))
-    x, targets = _batch(np.random.default_rng(1))
+    x, targets = _batch(np.random.default_rng(1), size=size, box_scale=box_scale)
     got = det.train_step(x, targets, lr=0.0, weight_decay=0.0, max_grad_norm=1e9)        # (lr 0: the weights stay what the oracle holds)
     tr = det.last_trace
     # continuous quantities, on the decisions the device step took
@@ -109,6 +118,43 @@ def test_assembled_step_against_the_oracle(widths):
     np.testing.assert_allclose(ftr["roi_targets"], tr["roi_targets"], rtol=1e-4, atol=1e-5)
     for k in free:
         assert abs(got[k] - free[k]) <= 5e-4 * max(1.0, abs(free[k])), (k, got[k], free[k])
+    assert all(np.isfinite(v) for v in got.values())
+    if size != 128:                          # the larger images' RoIs: beyond the first 128 px and above pyramid level 0
+        assert tr["rois"][:, 3:].max() > 128 and (tr["roi_levels"] > 0).any()
+
+
+def test_train_step_and_predict_refuse_unsupported_sizes_before_any_work():
+    """On the device: a step at 448 x 448 (66,836 anchors) stops with the ValueError before anything is allocated, and the
+    detector still trains at a supported size afterwards."""
+    import torch
+    from rfi_toolbox_amd.models import MaskRCNN
+    torch.manual_seed(3)
+    det = MaskRCNN(2, 3, 16, 64, 128, seed=7)
+    x, targets = _batch(np.random.default_rng(1), n=1, size=448)
+    with pytest.raises(ValueError, match="65536 anchors"):
+        det.train_step(x, targets, lr=0.0)
+    assert getattr(det, "_buf", None) is None
+    with pytest.raises(ValueError, match="multiples of 64"):
+        det.predict(np.zeros((1, 128, 96, 3), np.float32))
+    x, targets = _batch(np.random.default_rng(1), n=1)
+    assert np.isfinite(det.train_step(x, targets, lr=0.0)["loss"])
+
+
+def test_predict_at_256():
+    import torch
+    from rfi_toolbox_amd.models import MaskRCNN
+    torch.manual_seed(3)
+    det = MaskRCNN(2, 3, 16, 64, 128, seed=7)
+    det.score_thresh = 0.0                   # (untrained: keep every box, so the mask branch and the pasting run)
+    x, _ = _batch(np.random.default_rng(2), size=256, box_scale=1.6)
+    out = det.predict(x)
+    assert len(out) == 2
+    for o in out:
+        k = len(o["boxes"])
+        assert 0 < k <= det.max_det and o["boxes"].shape == (k, 4) and o["scores"].shape == (k,) and o["labels"].shape == (k,)
+        assert o["masks"].shape == (k, 256, 256) and o["masks"].dtype == bool and o["rfi_mask"].shape == (256, 256)
+        assert (o["boxes"] >= 0).all() and (o["boxes"] <= 256).all()
+        assert (o["boxes"][:, 2] >= o["boxes"][:, 0]).all() and (o["boxes"][:, 3] >= o["boxes"][:, 1]).all()
 
 
 def test_batched_matcher_and_nms_match_the_per_image_oracle():
@@ -175,12 +221,21 @@ def test_assembled_step_is_bitwise_reproducible():
     """No float atomics anywhere in the step (the RoIAlign gradient is a gather, every reduction has a fixed order): the
     same weights, batch and sampler seed give bit-identical losses and gradient norms, with the weight-gradient kernels of
     four models sharing the side stream, the slab workspace and the event rings."""
+    _check_bitwise_reproducible(128, 1.0)
+
+
+def test_assembled_step_is_bitwise_reproducible_at_256():
+    """The same at 256 x 256: the multi-pass sorts of the anchor and top-k keys included."""
+    _check_bitwise_reproducible(256, 1.6)
+
+
+def _check_bitwise_reproducible(size, box_scale):
     import torch
     from rfi_toolbox_amd.models import MaskRCNN
     torch.manual_seed(3)
     det = MaskRCNN(2, 3, 16, 64, 128, seed=7)
     det.keep_trace = True
-    x, targets = _batch(np.random.default_rng(1), n=4)
+    x, targets = _batch(np.random.default_rng(1), n=4, size=size, box_scale=box_scale)
     watch = [e[0] for e in det.backbone._entries if e[0].endswith("weight") and ("conv" in e[0] or "downsample.0" in e[0] or "blocks" in e[0])][::5]
     runs = []
     for _ in range(4):
@@ -188,9 +243,10 @@ def test_assembled_step_is_bitwise_reproducible():
         losses = det.train_step(x, targets, lr=0.0, weight_decay=0.0, max_grad_norm=1e9)
         # (the backbone's weight gradients run on the side stream next to its main chain: whole tensors, not only their norm)
         grads = {k: det.backbone.grad(k).copy() for k in watch}
-        runs.append((losses, dict(det.last_trace["grad_norms"]), det.last_trace["rois"].copy(), grads))
-    for losses, norms, rois, grads in runs[1:]:
+        runs.append((losses, dict(det.last_trace["grad_norms"]), det.last_trace["rois"].copy(), grads, det.last_trace["rpn_labels"].copy()))
+    for losses, norms, rois, grads, rpn_labels in runs[1:]:
         assert losses == runs[0][0] and norms == runs[0][1] and np.array_equal(rois, runs[0][2])
+        assert np.array_equal(rpn_labels, runs[0][4])
         assert all(np.array_equal(grads[k], runs[0][3][k]) for k in watch)
 
 
