@@ -44,7 +44,6 @@ struct PConvDev {
     int nkc, ncb;                    // K chunks (all segments), 32-channel output blocks
     unsigned x_zero[2];              // byte offset of >= 64 zero bytes inside each segment's allocation
     unsigned wb_zero;                // ... and inside the filter allocation
-    int diag;                        // RFI_PCONV_DIAG: 1 skip the MFMA phase, 2 skip the DMA (timing experiments only)
     unsigned long long* stamps;      // RFI_DIAG_STAMPS build: per-wave phase cycle sums
 };
 
@@ -307,7 +306,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void pconv_kernel(PConvDev d) {
             // (every tile of the model shapes) run a copy of the loop WITHOUT bounds tests, and the statistics are accumulated
             // whether or not the launch wants them: the loop is straight-line code -- with a branch per quarter (full tile?
             // statistics? backward sums?) the compiler waited for every LDS operation at each join and copied the statistics
-            // registers at every merge; skipping the epilogue altogether (RFI_PCONV_DIAG=4) showed it to be 24 % (512-channel
+            // registers at every merge; skipping the epilogue altogether (a timing experiment) showed it to be 24 % (512-channel
             // layers) to 42 % (64-channel layers at 1024 x 1024) of the kernel
             constexpr int NQ = NTL * MT * 4;
             const int pl = lane >> 3, g4 = (lane & 7) * 4;
@@ -336,10 +335,6 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void pconv_kernel(PConvDev d) {
                         const unsigned w1 = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{v[2], v[3]}, bf16x2));
                         v = f32x4{__builtin_bit_cast(float, w0 << 16), __builtin_bit_cast(float, w0 & 0xffff0000u),
                                   __builtin_bit_cast(float, w1 << 16), __builtin_bit_cast(float, w1 & 0xffff0000u)};
-#ifdef RFI_DIAG_STAMPS
-                        if (d.diag & 8) asm volatile("" :: "v"(w0), "v"(w1));      // (timing experiment: the epilogue without its stores)
-                        else
-#endif
                         if constexpr (OM == 2) *reinterpret_cast<u32x2*>(a.y16 + off) = u32x2{w0, w1};
                     }
                     if constexpr (OM != 2) *reinterpret_cast<f32x4*>(a.y + off) = v;
@@ -435,7 +430,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void pconv_kernel(PConvDev d) {
         float* s_ep = reinterpret_cast<float*>(smem + wave * C::EPI_WAVE_BYTES);
 #pragma unroll
         for (int g = 0; g < G; ++g)
-            if (g0 + g < my_tiles && !(d.diag & 4)) {
+            if (g0 + g < my_tiles) {
                 if (vec_out) epilogue(tl[g], acc[g], s_ep, std::true_type{});
                 else if constexpr (OM == 0) epilogue(tl[g], acc[g], s_ep, std::false_type{});
             }
@@ -478,19 +473,11 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void pconv_kernel(PConvDev d) {
                         RFI_T(t0);
                         if (!last) {
                             issue_A(wrap ? tl[0] : tl[G > 1 ? g + 1 < G ? g + 1 : 0 : 0], wrap ? kc + 1 : kc, (item + 1) & 1);
-#ifdef RFI_DIAG_STAMPS
-                            if (wrap && !(d.diag & 2)) issue_B(kc + 1, (kc + 1) & 1);      // (timing experiment: no filter DMA after the first chunk)
-#else
                             if (wrap) issue_B(kc + 1, (kc + 1) & 1);
-#endif
                         }
                         RFI_T(t1);
                         if (last) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef RFI_DIAG_STAMPS
-                        else if (wrap && !(d.diag & 2)) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(C::A_ITEMS + C::B_ITEMS) : "memory");
-#else
                         else if (wrap) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(C::A_ITEMS + C::B_ITEMS) : "memory");
-#endif
                         else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(C::A_ITEMS) : "memory");
                         RFI_T(t2);
                         __builtin_amdgcn_s_barrier();                       // every wave's pieces of THIS item have landed
@@ -574,46 +561,42 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void pconv_kernel(PConvDev d) {
             for (int g = 0; g < G; ++g) {
                 if (g < gcount) {
                     RFI_T(t0);
-                    if (!(d.diag & 2) || (g0 == 0 && kc == 0 && g == 0)) {
-                        issue_A(tl[g], kc);
-                        if (g == 0) issue_B(kc);     // the filter tile of the chunk serves every tile of the group
-                    }
+                    issue_A(tl[g], kc);
+                    if (g == 0) issue_B(kc);         // the filter tile of the chunk serves every tile of the group
                     RFI_T(t1);
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     RFI_T(t2);
                     __syncthreads();                 // s_waitcnt vmcnt(0) + barrier: every wave's pieces have landed
                     RFI_T(t3);
-                    if (!(d.diag & 1)) {
-                        // software pipeline over the taps: the fragments of tap t+1 are read from LDS BEFORE the MFMAs
-                        // of tap t are issued, so their LDS latency hides under those MFMAs (hipcc otherwise sinks every
-                        // ds_read to just before its first use and the matrix pipe idles for one LDS round trip per
-                        // fragment: measured 66 % duty in this phase).  The fences pin "reads of t+1, then MFMAs of t".
-                        bf16x8 afr[2][MT][P], bfr[2][NTL][P];
-                        auto load_frags = [&](int tap, bf16x8 (&af)[MT][P], bf16x8 (&bf)[NTL][P]) {
-                            const int tr = tap / R, ts = tap % R;
+                    // software pipeline over the taps: the fragments of tap t+1 are read from LDS BEFORE the MFMAs
+                    // of tap t are issued, so their LDS latency hides under those MFMAs (hipcc otherwise sinks every
+                    // ds_read to just before its first use and the matrix pipe idles for one LDS round trip per
+                    // fragment: measured 66 % duty in this phase).  The fences pin "reads of t+1, then MFMAs of t".
+                    bf16x8 afr[2][MT][P], bfr[2][NTL][P];
+                    auto load_frags = [&](int tap, bf16x8 (&af)[MT][P], bf16x8 (&bf)[NTL][P]) {
+                        const int tr = tap / R, ts = tap % R;
+#pragma unroll
+                        for (int nt = 0; nt < NTL; ++nt)
+#pragma unroll
+                            for (int p = 0; p < P; ++p)
+                                bf[nt][p] = *reinterpret_cast<const bf16x8*>(sB + b_base + ((tap * C::NCBL + nt) * P + p) * 1024);
+#pragma unroll
+                        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                            for (int p = 0; p < P; ++p)
+                                af[mt][p] = *reinterpret_cast<const bf16x8*>(sA + a_base[mt] + (tr * C::HW + ts) * C::ROWB + p * 32);
+                    };
+                    load_frags(0, afr[0], bfr[0]);
+#pragma unroll
+                    for (int tap = 0; tap < C::NTAP; ++tap) {
+                        if (tap + 1 < C::NTAP) load_frags(tap + 1, afr[(tap + 1) & 1], bfr[(tap + 1) & 1]);
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
                             for (int nt = 0; nt < NTL; ++nt)
-#pragma unroll
-                                for (int p = 0; p < P; ++p)
-                                    bf[nt][p] = *reinterpret_cast<const bf16x8*>(sB + b_base + ((tap * C::NCBL + nt) * P + p) * 1024);
-#pragma unroll
-                            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                                for (int p = 0; p < P; ++p)
-                                    af[mt][p] = *reinterpret_cast<const bf16x8*>(sA + a_base[mt] + (tr * C::HW + ts) * C::ROWB + p * 32);
-                        };
-                        load_frags(0, afr[0], bfr[0]);
-#pragma unroll
-                        for (int tap = 0; tap < C::NTAP; ++tap) {
-                            if (tap + 1 < C::NTAP) load_frags(tap + 1, afr[(tap + 1) & 1], bfr[(tap + 1) & 1]);
-                            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                                for (int nt = 0; nt < NTL; ++nt)
-                                    acc[g][mt][nt] = mma<P>(afr[tap & 1][mt], bfr[tap & 1][nt], acc[g][mt][nt]);
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
+                                acc[g][mt][nt] = mma<P>(afr[tap & 1][mt], bfr[tap & 1][nt], acc[g][mt][nt]);
+                        __builtin_amdgcn_sched_barrier(0);
                     }
                     RFI_T(t4);
                     __syncthreads();                 // every wave is done reading the halo tile (and, after the last tile
@@ -663,9 +646,8 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void pconv_kernel(PConvDev d) {
 
 template <int R, int S, int TH, int TW, int WM, int WN, int MT, int NTL, int P, int G, int PAD = 1, bool BWD = false, int OM = -1, bool DB = false>
 void launch_cfg(rfi_ctx* ctx, PConvDev& d) {
-    if constexpr (OM >= 0 && !DB && P == 1 && R == 3 && S == 1) {      // double-buffered staging from 3 K chunks (bf16 flow; RFI_PCONV_DB=0: off)
-        static const int db = getenv("RFI_PCONV_DB") ? atoi(getenv("RFI_PCONV_DB")) : 3;
-        if (db > 0 && d.nkc >= db) return launch_cfg<R, S, TH, TW, WM, WN, MT, NTL, P, G, PAD, BWD, OM, true>(ctx, d);
+    if constexpr (OM >= 0 && !DB && P == 1 && R == 3 && S == 1) {      // double-buffered staging from 3 K chunks (bf16 flow)
+        if (d.nkc >= 3) return launch_cfg<R, S, TH, TW, WM, WN, MT, NTL, P, G, PAD, BWD, OM, true>(ctx, d);
     }
     if constexpr (OM < 0) {                           // pick the epilogue variant of this launch
         const int om = d.a.y16 ? 2 : d.a.round_y ? 1 : 0;
@@ -768,11 +750,9 @@ template <int P>
 void dispatch(rfi_ctx* ctx, PConvDev& d) {
     const PConvArgs& a = d.a;
     // bf16 flow, 64 output channels and more: 2 x 2 blocks per wave on ONE tile per group (a third fewer LDS bytes per MFMA
-    // than 2 x 1 blocks on two tiles; pays only together with the double-buffered staging: -0.9 % step time;
-    // RFI_PCONV_NT2=0 for A/B runs)
-    static const int wide = getenv("RFI_PCONV_NT2") ? atoi(getenv("RFI_PCONV_NT2")) : 1;
+    // than 2 x 1 blocks on two tiles; pays only together with the double-buffered staging: -0.9 % step time)
     if constexpr (P == 1) {
-        if (wide && a.Cout >= 64 * wide) {
+        if (a.Cout >= 64) {
             if (a.W >= 32) return launch_cfg<3, 1, 8, 32, 4, 1, 2, 2, P, 1, 1>(ctx, d);
             if (a.W >= 16) return launch_cfg<3, 1, 16, 16, 4, 1, 2, 2, P, 1, 1>(ctx, d);
         }
@@ -808,8 +788,6 @@ void launch_pconv(rfi_ctx* ctx, PConvArgs& a) {
     const int64_t wbytes = (int64_t)wb_elems(a.R * a.R, a.Cout, 16 * a.x[0].nchunks, a.nseg > 1 ? 16 * a.x[1].nchunks : 0, a.P) * 2;
     RFI_REQUIRE(wbytes + 64 < ((int64_t)1 << 32), "pconv: filter tensor too large");
     d.wb_zero = (unsigned)wbytes;                      // ... and so is every wB tensor
-    static const int diag = getenv("RFI_PCONV_DIAG") ? atoi(getenv("RFI_PCONV_DIAG")) : 0;
-    d.diag = diag;
     d.stamps = nullptr;
     RFI_REQUIRE((int64_t)a.N * a.Hout * a.Wout * a.y_pstride < (int64_t)1 << 31, "pconv: output too large for 32-bit offsets");
     const double flops = a.algo_flops >= 0 ? a.algo_flops : 2.0 * a.N * a.H * a.W * (double)a.Cout * (a.R * a.R) * 16.0 * d.nkc;

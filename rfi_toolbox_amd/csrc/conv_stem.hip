@@ -168,7 +168,7 @@ __global__ __launch_bounds__(256) void conv_stem_kernel(StemDev d) {
 bool conv_stem_eligible(const ConvArgs& a) {
     if (!(a.R == 3 && a.S == 1 && a.pad == 1 && a.zgroups == 1 && a.Cin == 4 && a.x.pstride == 4 && (a.Cout == 32 || a.Cout == 64))) return false;
     if (a.Hin != a.H || a.Win != a.W || a.Hout != a.H || a.Wout != a.W || a.osy != 1 || a.osx != 1 || a.ooy || a.oox) return false;
-    if (a.xf.scale || a.fold || a.y16 || a.bwd_y) return false;
+    if (a.xf.scale || a.fold || a.y16) return false;
     if ((reinterpret_cast<uintptr_t>(a.x.p) | reinterpret_cast<uintptr_t>(a.w)) & 15) return false;
     return (int64_t)a.N * a.H * a.W * std::max<int64_t>(a.y.pstride, 4) * 4 < ((int64_t)1 << 40);
 }

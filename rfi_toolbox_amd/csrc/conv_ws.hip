@@ -47,8 +47,6 @@ struct WsDev {
     int y_ps;
     double* stats;                    // [gridDim.x][Cout][2] fp64 (sum y, sum y^2) records, or null
     int wide_epi;                     // 64-channel blocks: 16-byte output stores through an LDS transpose (y_ps % 4 == 0, 16-byte aligned y)
-    int diag;                         // RFI_WS_DIAG (timing experiments, wrong results): 1 no halo loads after the first, 2 no filter DMA, 4 no MFMAs
-    int prio;                         // RFI_WS_PRIO (tuning): 0 none, 1 consumers at priority 2, 2 producers at priority 1
     unsigned long long* stamps;       // RFI_DIAG_STAMPS build: per-wave cycle sums
 };
 
@@ -219,7 +217,6 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(WsDev d) {
                 }
             }
         };
-        if (d.prio == 2) __builtin_amdgcn_s_setprio(1);
         // load cursor: item (lk, lch)
         int lk = 0, lch = 0;
         Tile lt = tile_of(0);
@@ -235,7 +232,7 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(WsDev d) {
                 WS_ACC(2, t0, t1);
                 if constexpr (ADB) write_all((q + 1) & 1);         // the consumers left this buffer an item ago
                 __builtin_amdgcn_sched_barrier(0);
-                if (!(d.diag & 2)) issue_B(lch, (q + 1) & 1);      // its buffer was last read for item q - 1
+                issue_B(lch, (q + 1) & 1);                         // its buffer was last read for item q - 1
                 __builtin_amdgcn_sched_barrier(0);
                 if (q + 2 < nitems) {
                     if (++lch == nkc) {
@@ -245,7 +242,7 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(WsDev d) {
                         setup_halo(lt);
                     }
                 }
-                if (!(d.diag & 1)) issue_loads(lch * 16);          // (the very last item is re-read once: harmless)
+                issue_loads(lch * 16);                             // (the very last item is re-read once: harmless)
                 __builtin_amdgcn_sched_barrier(0);
                 // the DMA pieces were issued BEFORE the halo loads: all but the youngest HALO_ITEMS operations done = every
                 // piece has landed
@@ -268,7 +265,6 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(WsDev d) {
         }
     } else {
         // =============================================================== consumers
-        if (d.prio == 1) __builtin_amdgcn_s_setprio(2);
         const int cw = wave, li = lane & 31, lh = lane >> 5;
         int a_base[2];
 #pragma unroll
@@ -442,18 +438,14 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(WsDev d) {
                     pend = false;
                 }
             }
-            if (d.diag & 4) {
-                if constexpr (!ADB) wg_barrier();
+            if (pend) {                                  // (pend implies chunk 0 of the next tile)
+                run_item(std::true_type{}, std::true_type{}, sA, sB);
+                epi_finish();
+                pend = false;
+            } else if (cch == 0) {
+                run_item(std::false_type{}, std::true_type{}, sA, sB);
             } else {
-                if (pend) {                              // (pend implies chunk 0 of the next tile)
-                    run_item(std::true_type{}, std::true_type{}, sA, sB);
-                    epi_finish();
-                    pend = false;
-                } else if (cch == 0) {
-                    run_item(std::false_type{}, std::true_type{}, sA, sB);
-                } else {
-                    run_item(std::false_type{}, std::false_type{}, sA, sB);
-                }
+                run_item(std::false_type{}, std::false_type{}, sA, sB);
             }
             WS_T(t1);
             if (++cch == nkc) {                          // the tile is complete
@@ -656,7 +648,7 @@ bool conv_ws_eligible(const ConvArgs& a) {
     if (!(a.R == 3 && a.S == 1 && a.pad == 1 && a.zgroups == 1 && a.fold == 0)) return false;
     if (a.Hin != a.H || a.Win != a.W || a.Hout != a.H || a.Wout != a.W) return false;
     if (a.osy != 1 || a.osx != 1 || a.ooy != 0 || a.oox != 0) return false;
-    if (a.y16 || a.bwd_y || a.W < 8 || a.H < 8) return false;
+    if (a.y16 || a.W < 8 || a.H < 8) return false;
     if (a.Cin % 16 != 0 || a.x.pstride % 4 != 0 || (reinterpret_cast<uintptr_t>(a.x.p) & 15)) return false;
     if (a.xf.scale && ((reinterpret_cast<uintptr_t>(a.xf.scale) & 15) || (reinterpret_cast<uintptr_t>(a.xf.shift) & 15))) return false;
     // 32-bit byte offsets with 2^31 as the "reads zero" offset of the buffer loads; 32-bit element offsets of the output
@@ -682,12 +674,7 @@ void launch_conv_ws(rfi_ctx* ctx, ConvArgs& a, const bf16_t* wB, int P) {
     d.y = a.y.p; d.y_ps = a.y.pstride;
     d.stats = nullptr;
     d.stamps = nullptr;
-    static const int prio = getenv("RFI_WS_PRIO") ? atoi(getenv("RFI_WS_PRIO")) : 0;
-    d.prio = prio;
-    static const int diag = getenv("RFI_WS_DIAG") ? atoi(getenv("RFI_WS_DIAG")) : 0;
-    d.diag = diag;
-    static const bool no_wide = getenv("RFI_WS_NARROW_EPI") != nullptr;          // A/B runs: dword stores from the accumulators
-    d.wide_epi = !no_wide && a.y.pstride % 4 == 0 && (reinterpret_cast<uintptr_t>(a.y.p) & 15) == 0;
+    d.wide_epi = a.y.pstride % 4 == 0 && (reinterpret_cast<uintptr_t>(a.y.p) & 15) == 0;
     const double flops = a.algo_flops >= 0 ? a.algo_flops : 2.0 * a.N * a.H * a.W * (double)a.Cout * 9 * a.Cin;
     std::string label;
     if (ctx->profiling)
@@ -695,14 +682,13 @@ void launch_conv_ws(rfi_ctx* ctx, ConvArgs& a, const bf16_t* wB, int P) {
                 std::to_string(a.Cin) + "->" + std::to_string(a.Cout) + (a.xf.scale ? " xf" : "") + (P == 3 ? " 3xbf16" : " bf16");
     const double bytes = 4.0 * ((double)a.N * a.H * a.W * a.Cin + 9.0 * a.Cin * a.Cout) + 4.0 * a.N * a.H * a.W * a.Cout;
     ProfScope ps(ctx, FAM_CONV_MFMA, flops, bytes, label);
-    static const int ntl_max = getenv("RFI_WS_NTL") ? atoi(getenv("RFI_WS_NTL")) : 4;          // A/B runs
     const int xf = !a.xf.scale ? 0 : (a.xf.relu == 1 || (a.xf.relu == 2 && a.xf.slope == 0.0f)) ? 1 : 2;
     // wider channel blocks cut the producers' work per MFMA (64 channels for the split arithmetic; 128 where one MFMA
     // stands for a block product); they are used where the grid still covers the chip (tiles x blocks >= ~256 workgroups)
     const int64_t tiles = (a.W >= 16 ? (int64_t)a.N : cdiv(a.N, 4)) * cdiv(a.H, a.W >= 32 ? 8 : a.W >= 16 ? 16 : 8) * cdiv(a.W, a.W >= 32 ? 32 : a.W >= 16 ? 16 : 8);
     int ntl = 1;
-    if (a.Cout > 32 && ntl_max >= 2 && tiles * cdiv(d.ncb, 2) >= 224) ntl = 2;
-    if (P == 1 && a.Cout > 64 && ntl_max >= 4 && tiles * cdiv(d.ncb, 4) >= 224) ntl = 4;
+    if (a.Cout > 32 && tiles * cdiv(d.ncb, 2) >= 224) ntl = 2;
+    if (P == 1 && a.Cout > 64 && tiles * cdiv(d.ncb, 4) >= 224) ntl = 4;
     if (P == 3) {
         if (ntl == 2) dispatch_xf<2, 3>(ctx, a, d, xf);
         else dispatch_xf<1, 3>(ctx, a, d, xf);

@@ -1468,8 +1468,7 @@ void launch_bn_bwd_reduce(rfi_ctx* ctx, YRef da, YRef y, int64_t M, int C,
                           const float* invstd, float* partial_ws, float* c1, float* c2,
                           float* dgamma, float* dbeta, float slope) {
     ChanGeom g = geom_rows(M, C);
-    static const bool no16 = getenv("RFI_NO_BN16") != nullptr;          // A/B runs: the generic kernels for bfloat16 tensors too
-    const bool fast16 = !no16 && da.bf16 && y.bf16 && C % 8 == 0 && da.stride(C) == C && y.stride(C) % 8 == 0 &&
+    const bool fast16 = da.bf16 && y.bf16 && C % 8 == 0 && da.stride(C) == C && y.stride(C) % 8 == 0 &&
                         !((reinterpret_cast<uintptr_t>(da.p) | reinterpret_cast<uintptr_t>(y.p) | reinterpret_cast<uintptr_t>(scale) |
                            reinterpret_cast<uintptr_t>(shift) | reinterpret_cast<uintptr_t>(mean) | reinterpret_cast<uintptr_t>(invstd)) & 15);
     if (fast16) {
@@ -1508,8 +1507,7 @@ void launch_bn_bwd_apply(rfi_ctx* ctx, YRef da_inout, YRef y, int64_t M, int C,
                          int64_t planes_pstride, int planes_P, hipEvent_t done, bool finish_dbias, const float* head_dl,
                          const float* head_w) {
     ChanGeom g = geom_rows(M, C);
-    static const bool no16 = getenv("RFI_NO_BN16") != nullptr;
-    const bool fast16 = !no16 && da_inout.bf16 && y.bf16 && planes_out && planes_P == 1 && !head_dl && C % 8 == 0 && da_inout.stride(C) == C &&
+    const bool fast16 = da_inout.bf16 && y.bf16 && planes_out && planes_P == 1 && !head_dl && C % 8 == 0 && da_inout.stride(C) == C &&
                         y.stride(C) % 8 == 0 && planes_pstride % 8 == 0 &&
                         !((reinterpret_cast<uintptr_t>(da_inout.p) | reinterpret_cast<uintptr_t>(y.p) | reinterpret_cast<uintptr_t>(planes_out) |
                            reinterpret_cast<uintptr_t>(scale) | reinterpret_cast<uintptr_t>(shift) | reinterpret_cast<uintptr_t>(mean) |

@@ -329,8 +329,7 @@ void launch_gw(rfi_ctx* ctx, GwDev& d) {
     using C = GwCfg<NB, PWV>;
     const int ntiles = (int)cdiv(d.M, TM);
     const int ycols = (int)cdiv(d.ncb, NB);
-    static const int wgs = getenv("RFI_GW_WGS") ? atoi(getenv("RFI_GW_WGS")) : 256;
-    const int gmax = std::max(8, wgs / ycols);
+    const int gmax = std::max(8, 256 / ycols);
     const int tx = (int)cdiv(ntiles, 8);
     const int per = (int)cdiv(tx, std::max(1, gmax / 8));
     int GX = 8 * (int)cdiv(tx, per);
@@ -354,7 +353,7 @@ bool gemm_ws_eligible(const ConvArgs& a) {
                          a.Hout == a.H && a.Wout == a.W && a.osy == 1 && a.osx == 1 && a.ooy == 0 && a.oox == 0;
     const bool one = a.R == 1 && a.S == 1 && a.pad == 0 && a.zgroups == 1 && a.Hin == a.H && a.Win == a.W && a.Hout == a.H &&
                      a.Wout == a.W && a.osy == 1 && a.osx == 1 && a.ooy == 0 && a.oox == 0;
-    if (!(fwd_t || dgrad_t || one) || a.fold || a.y16 || a.bwd_y || a.stats) return false;
+    if (!(fwd_t || dgrad_t || one) || a.fold || a.y16 || a.stats) return false;
     if (a.Cin % 16 != 0 || a.x.pstride % 4 != 0 || (reinterpret_cast<uintptr_t>(a.x.p) & 15)) return false;
     if (a.xf.scale && ((reinterpret_cast<uintptr_t>(a.xf.scale) & 15) || (reinterpret_cast<uintptr_t>(a.xf.shift) & 15))) return false;
     if ((int64_t)a.N * a.Hin * a.Win * a.x.pstride * 4 >= (int64_t)1 << 31 || (int64_t)a.N * a.Hout * a.Wout * a.y.pstride >= (int64_t)1 << 31) return false;
@@ -391,7 +390,6 @@ void launch_gemm_ws(rfi_ctx* ctx, ConvArgs& a, const bf16_t* wB3) {
     const int xf = !a.xf.scale ? 0 : (a.xf.relu == 1 || (a.xf.relu == 2 && a.xf.slope == 0.0f)) ? 1 : 2;
     // 8 blocks per workgroup where the grid still covers the chip, else 4 (2 for a 64-channel output)
     const bool wide = d.ncb > 4 && cdiv(d.M, TM) * cdiv(d.ncb, 8) >= 192;
-    static const bool pwv8 = !(getenv("RFI_GW_PWV") && atoi(getenv("RFI_GW_PWV")) == 4);      // (A/B: RFI_GW_PWV=4)
     // (measured and not kept: 64-channel column groups with eight producer waves where 128-channel ones leave half the CUs
     // without a workgroup -- the 8 x 8 maps: the kernel alone 59 -> 53 us, the step +0.7 %: the idle CUs are where the side
     // stream's weight gradient runs)
@@ -403,14 +401,10 @@ void launch_gemm_ws(rfi_ctx* ctx, ConvArgs& a, const bf16_t* wB3) {
         if (xf == 0) launch_gw<2, 0>(ctx, d);
         else if (xf == 1) launch_gw<2, 1>(ctx, d);
         else launch_gw<2, 2>(ctx, d);
-    } else if (pwv8) {
+    } else {
         if (xf == 0) launch_gw<4, 0, 8>(ctx, d);
         else if (xf == 1) launch_gw<4, 1, 8>(ctx, d);
         else launch_gw<4, 2, 8>(ctx, d);
-    } else {
-        if (xf == 0) launch_gw<4, 0>(ctx, d);
-        else if (xf == 1) launch_gw<4, 1>(ctx, d);
-        else launch_gw<4, 2>(ctx, d);
     }
 }
 

@@ -75,13 +75,6 @@ struct ConvArgs {
     // launcher honoured it (else the caller records an event as usual)
     hipEvent_t done = nullptr;
     bool done_used = false;
-    // with `stats`: the output is dA, the gradient w.r.t. the ACTIVATED output of a Conv+BN layer whose raw output
-    // is bwd_y (same shape as the output).  The records then hold the BatchNorm-BACKWARD sums (sum dz, sum dz * xhat;
-    // dz = dA * act'(y*scale+shift), xhat = (y - mean) * invstd) instead of (sum y, sum y^2): bn_bwd_reduce's pass
-    // over dA and Y disappears (launch_bn_bwd_finalize_records finishes them).
-    const float* bwd_y = nullptr;
-    const float *bwd_scale = nullptr, *bwd_shift = nullptr, *bwd_mean = nullptr, *bwd_invstd = nullptr;
-    float bwd_slope = 0.0f;
 #ifdef RFI_DIAG_STAMPS
     unsigned long long* stamps = nullptr;   // diagnostic build only: per-workgroup phase cycle sums
 #endif
@@ -99,7 +92,6 @@ bool gemm_ws_eligible(const ConvArgs& a);        // gemm_ws.hip: transposed conv
 void launch_gemm_ws(rfi_ctx* ctx, ConvArgs& a, const unsigned short* wB3);
 
 bool conv_mfma_eligible(const ConvArgs& a);
-bool bf16_k16();           // RFI_BF16_K16=1: the float32-tensor bf16 mode runs the K = 16 MFMA on the split path's data flow (conv_mfma.hip)
 // filters [taps][Cout][Cin] -> [taps][Cout][ceil(Cin/16)][h16 | m16 | l16] bf16 records (24 floats each)
 size_t weights_x3_floats(int taps, int Cout, int Cin);
 void launch_weights_to_x3(rfi_ctx* ctx, const float* w, int taps, int Cout, int Cin, float* out);
@@ -178,7 +170,7 @@ void launch_bn_bwd_reduce(rfi_ctx* ctx, YRef da, YRef y, int64_t M, int C,
                           const float* invstd, float* partial_ws, float* c1, float* c2,
                           float* dgamma, float* dbeta, float slope = 0.0f);
 size_t bn_bwd_ws_floats(int64_t M, int C);
-// the same finish when the partial sums came out of the producing conv kernel's epilogue (ConvArgs::bwd_y)
+// the same finish when the partial sums came out of the pass that produced dA (launch_pool_bwd_merge_sums, launch_head_bwd)
 void launch_bn_bwd_finalize_records(rfi_ctx* ctx, const float* partial_ws, int records, int64_t M, int C, float* c1,
                                     float* c2, float* dgamma, float* dbeta);
 // backward, pass 2 (in place on da): dy = gamma*invstd * (dz - c1 - xhat*c2); also per-channel

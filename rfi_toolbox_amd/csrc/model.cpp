@@ -60,17 +60,10 @@ rfi_model::~rfi_model() {
     if (d_scalars) ctx->release(d_scalars);
     if (wd_ready) (void)hipEventDestroy(wd_ready);
     if (lazy_ev) (void)hipEventDestroy(lazy_ev);
-    for (hipEvent_t e : skip_done) if (e) (void)hipEventDestroy(e);
 }
 
 // ------------------------------------------------------------------------------------ build
 void rfi_model::build() {
-    if (const char* e = getenv("RFI_COMPUTE")) {      // arithmetic of new models: f32 (default) | f32mfma | bf16
-        compute_bf16 = std::string(e) == "bf16" || std::string(e) == "bf16regs";
-        compute_x3 = std::string(e) == "f32" || std::string(e) == "f32x3" || std::string(e) == "f32planes";
-        planesP = std::string(e) == "bf16" ? 1 : (std::string(e) == "f32planes" ? 3 : 0);
-    }
-    if (const char* e = getenv("RFI_BN_FUSE")) fuse_bn_bwd = e[0] == '1';
     if (arch != 0 && !(arch == 2 && planesP == 1 && feat % 16 == 0)) planesP = 0;     // the plane data flow: the plain U-Net; the
                                                                                       // ResNet-encoder U-Net's bfloat16 flow
     if (arch == 1) return build_cnn3();
@@ -460,12 +453,11 @@ void rfi_model::refresh_dgrad_weights() {
     }
     // Split rebuild (plain U-Net, float32 tensors, overlap on): the forward pass needs the forward-direction copies only, so
     // the dgrad layout and its B-operand images are rebuilt on the SIDE stream (idle during the forward pass) under the first
-    // convs; backward() waits for them (wait_wd).  RFI_NO_WD_SIDE=1: everything on the main stream, as before
-    static const bool no_wd_side = getenv("RFI_NO_WD_SIDE") != nullptr;
+    // convs; backward() waits for them (wait_wd)
     // (the plane flows: the forward pass reads the forward-direction images only, nothing but the input-gradient kernels reads
     // the dgrad layouts -- unless pre-split records of them are in use)
     const bool split_planes = planesP && wb_pool && wb_n_fwd > 0 && !use_w3() && training;
-    const bool split = !no_wd_side && ctx->overlap && !ctx->profiling && ctx->stream == ctx->main_stream &&
+    const bool split = ctx->overlap && !ctx->profiling && ctx->stream == ctx->main_stream &&
                        (split_planes || (arch == 0 && !planesP && ws_need() != 0 && ws_pool && ws_P == ws_need() && ws_n_fwd > 0 &&
                                          (!use_w3() || (x3_descs && !x3_reads_wd && x3_for_ws_P == ws_P))));
     if (split) {
@@ -494,7 +486,6 @@ void rfi_model::refresh_dgrad_weights() {
         }
         // layers whose filters the wave-specialised kernels read (ws_by_w) need no records: launch_conv drops
         // ConvArgs::w3 for them, and a shape those kernels decline (maps under 8 x 8) gets a temporary split copy
-        static const bool all_x3 = getenv("RFI_NO_WS") != nullptr || getenv("RFI_NO_GW") != nullptr;     // A/B runs
         if (x3_descs && (x3_for_ws_P != ws_P || x3_for_shape != pH * 65536 + pW)) {
             ctx->release(x3_descs);
             x3_descs = nullptr;
@@ -503,7 +494,7 @@ void rfi_model::refresh_dgrad_weights() {
             x3_for_ws_P = ws_P;
             x3_bytes = 0;
             std::vector<X3Desc> h;
-            x3_skips_ws_layers = !all_x3 && ws_P == 3 && arch == 0;
+            x3_skips_ws_layers = ws_P == 3 && arch == 0;
             x3_reads_wd = false;
             x3_skipped.clear();
             // a layer is left out only if the wave-specialised kernels cannot decline it at the prepared shape: its maps are at
@@ -635,7 +626,7 @@ namespace {
 
 struct Shape { int N, H, W; };
 
-void run_conv_bn(rfi_model* m, ConvBN& c, View in, InXform xf, Shape s, float* Y, bool train, hipEvent_t coeffs_done = nullptr) {
+void run_conv_bn(rfi_model* m, ConvBN& c, View in, InXform xf, Shape s, float* Y, bool train) {
     ConvArgs a;
     a.x = in;
     a.N = s.N; a.H = s.H; a.W = s.W; a.Hin = s.H; a.Win = s.W;
@@ -662,12 +653,11 @@ void run_conv_bn(rfi_model* m, ConvBN& c, View in, InXform xf, Shape s, float* Y
         if (a.stats_records == 0) launch_bn_stats(m->ctx, Y, M, c.cout, ws);   // direct-kernel fallback
         launch_bn_finalize(m->ctx, ws, M, c.cout, m->params + c.g_off, m->params + c.be_off,
                            c.running_mean(), c.running_var(), c.ema_repeats, c.mean(), c.invstd(),
-                           c.scale(), c.shift(), nullptr, a.stats_records, coeffs_done);
+                           c.scale(), c.shift(), nullptr, a.stats_records);
         c.nbt += c.ema_repeats;
     } else {
         launch_bn_eval_coeffs(m->ctx, c.cout, m->params + c.g_off, m->params + c.be_off, c.running_mean(),
                               c.running_var(), c.scale(), c.shift());
-        if (coeffs_done) RFI_CHECK_HIP(hipEventRecord(coeffs_done, m->ctx->stream));
     }
 }
 
@@ -700,28 +690,12 @@ void rfi_model::forward(const float* x_dev, int n, int h, int w, bool train_mode
         ConvBN& c2 = convs[2 * (l - 1) + 1];
         run_conv_bn(this, c1, cur, InXform{}, s, buf(encY1[l]), train_mode);
         if (l == 1) side_rebuild_wd();
-        // The pooled tensor feeds the next conv at once; the skip (the activated output in the decoder's concat buffer) is not
-        // read before the decoder.  RFI_POOL_SPLIT=1: the main stream writes the pooled tensor only (a quarter of the bytes)
-        // and the skip is written on the side stream under the next level's matrix-bound convs.  OFF by default: measured
-        // 6.69 against 6.64 ms per step (round 4, two interleaved pairs) -- the second read of Y and the skip write next to
-        // the convs cost them more than the 45 us the main stream saves
-        static const bool no_split = getenv("RFI_POOL_SPLIT") == nullptr;
-        const bool split_pool = !no_split && train_mode && ctx->overlap && ctx->stream == ctx->main_stream && !(s.H & 1) && !(s.W & 1);      // (training passes: the backward pass's side_join recycles the events)
-        const hipEvent_t coeffs = split_pool ? next_fork_event() : nullptr;
-        run_conv_bn(this, c2, View{buf(encY1[l]), c1.cout}, bn_xf(c1), s, buf(encY2[l]), train_mode, coeffs);
-        const MutView skip{buf(concat[l]) + c2.cout, 2 * c2.cout};
-        if (split_pool && coeffs) {
-            launch_bn_relu_pool(ctx, buf(encY2[l]), s.N, s.H, s.W, c2.cout, c2.scale(), c2.shift(), MutView{}, buf(pool[l]), act_slope);
-            if ((int)skip_done.size() <= l) skip_done.resize(l + 1, nullptr);
-            if (!skip_done[l]) RFI_CHECK_HIP(hipEventCreateWithFlags(&skip_done[l], hipEventDisableTiming));
-            side_begin_after(coeffs);             // (the side stream waits for c2's scale / shift only)
-            struct Back { rfi_ctx* c; ~Back() { c->stream = c->main_stream; } } back{ctx};
-            launch_bn_relu_pool(ctx, buf(encY2[l]), s.N, s.H, s.W, c2.cout, c2.scale(), c2.shift(), skip, nullptr, act_slope);
-            RFI_CHECK_HIP(hipEventRecord(skip_done[l], ctx->side_stream));
-            skip_pending |= 1u << l;
-        } else {
-            launch_bn_relu_pool(ctx, buf(encY2[l]), s.N, s.H, s.W, c2.cout, c2.scale(), c2.shift(), skip, buf(pool[l]), act_slope);
-        }
+        run_conv_bn(this, c2, View{buf(encY1[l]), c1.cout}, bn_xf(c1), s, buf(encY2[l]), train_mode);
+        // one pass writes the pooled tensor and the skip (the activated output in the decoder's concat buffer).  Writing the
+        // skip on the side stream under the next level's convs measured slower: 6.69 against 6.64 ms per step (round 4) --
+        // the second read of Y and the skip write next to the convs cost them more than the 45 us the main stream saves
+        launch_bn_relu_pool(ctx, buf(encY2[l]), s.N, s.H, s.W, c2.cout, c2.scale(), c2.shift(),
+                            MutView{buf(concat[l]) + c2.cout, 2 * c2.cout}, buf(pool[l]), act_slope);
         cur = View{buf(pool[l]), c2.cout};
     }
     {
@@ -757,10 +731,6 @@ void rfi_model::forward(const float* x_dev, int n, int h, int w, bool train_mode
         launch_conv(ctx, a);
         ConvBN& c1 = convs[IB + 2 + 2 * k];
         ConvBN& c2 = convs[IB + 2 + 2 * k + 1];
-        if (skip_pending & (1u << l)) {           // the skip half of concat[l] was written on the side stream
-            RFI_CHECK_HIP(hipStreamWaitEvent(ctx->main_stream, skip_done[l], 0));
-            skip_pending &= ~(1u << l);
-        }
         run_conv_bn(this, c1, View{buf(concat[l]), 2 * u.cout}, InXform{}, s, buf(decY1[l]), train_mode);
         run_conv_bn(this, c2, View{buf(decY1[l]), c1.cout}, bn_xf(c1), s, buf(decY2[l]), train_mode);
         prevY = buf(decY2[l]);
@@ -800,7 +770,7 @@ void rfi_model::side_begin() {
     ctx->stream = ctx->side_stream;
 }
 hipEvent_t rfi_model::next_fork_event() {
-    static const bool off = getenv("RFI_NO_STOP_EVENTS") != nullptr;        // A/B runs: event-record packets as before
+    static const bool off = getenv("RFI_NO_STOP_EVENTS") != nullptr;        // (bench.py's fallback: event-record packets instead)
     if (!ctx->overlap || off) return nullptr;
     if (ctx->fork_ring_used == ctx->fork_ring.size()) {
         hipEvent_t e;
@@ -825,8 +795,7 @@ void rfi_model::side_end() {
     ++side_seq;
 }
 void rfi_model::side_join_lazy() {
-    static const bool off = getenv("RFI_NO_LAZY_JOIN") != nullptr;          // A/B runs: join at the end of the pass
-    if (off || (exchange_in_backward && ctx->exchange_active())) return side_join();      // (a bucket may leave right behind this pass)
+    if (exchange_in_backward && ctx->exchange_active()) return side_join();      // (a bucket may leave right behind this pass)
     if (!ctx->overlap || side_seq == 0) return;
     if (!lazy_ev) RFI_CHECK_HIP(hipEventCreateWithFlags(&lazy_ev, hipEventDisableTiming));
     RFI_CHECK_HIP(hipEventRecord(lazy_ev, ctx->side_stream));
@@ -915,11 +884,10 @@ struct SideScope {
 // given dA (grad w.r.t. the ACTIVATED output of conv c, overwritten with dY), produce dW/db/dgamma/
 // dbeta into the grad buffer and, if dx != null, the gradient w.r.t. the conv's (activated) input.
 // `have_records` > 0: the BatchNorm-backward sums of this layer already sit in the workspace (the kernel that
-// produced dA folded them into its epilogue).  `next` / `next_Y`: the Conv+BN layer whose activated output dx is
-// the gradient of (null: none); returns the number of records the dgrad left for it (0: none).
-int backward_conv_bn(rfi_model* m, ConvBN& c, float* dA, const float* Y, View in, InXform in_xf,
-                     Shape s, float* dx, int have_records, ConvBN* next, const float* next_Y,
-                     const float* head_dl = nullptr, const float* head_w = nullptr) {
+// produced dA folded them into its own pass).
+void backward_conv_bn(rfi_model* m, ConvBN& c, float* dA, const float* Y, View in, InXform in_xf,
+                      Shape s, float* dx, int have_records,
+                      const float* head_dl = nullptr, const float* head_w = nullptr) {
     rfi_ctx* ctx = m->ctx;
     const int64_t M = (int64_t)s.N * s.H * s.W;
     float* ws = m->buf(m->ws_red);
@@ -929,14 +897,12 @@ int backward_conv_bn(rfi_model* m, ConvBN& c, float* dA, const float* Y, View in
     else
         launch_bn_bwd_reduce(ctx, dA, Y, M, c.cout, c.scale(), c.shift(), c.mean(), c.invstd(), ws, c.c1(),
                              c.c2(), m->grads + c.g_off, m->grads + c.be_off, m->act_slope);
-    // RFI_WGRAD_LATE=1 (default): the weight gradient is enqueued BEHIND the input-gradient conv of the same layer (the side
-    // stream waits for it): two matrix-core kernels sharing the chip finish no sooner than one after the other, but a
-    // weight gradient that runs next to the following layer's BatchNorm-backward passes (memory-bound) hides them
-    static const bool late = !(getenv("RFI_WGRAD_LATE") && atoi(getenv("RFI_WGRAD_LATE")) == 0);
-    // a kernel that carries a completion signal leaves a ~5 us bubble behind it on its stream: only the kernel the side stream
-    // actually waits for gets one (RFI_ALL_STOP_EVENTS=1: every bn_bwd_apply too, as in round 3)
-    static const bool all_stop = getenv("RFI_ALL_STOP_EVENTS") != nullptr;
-    const hipEvent_t dy_done = (all_stop || !late || !dx) ? m->next_fork_event() : nullptr;      // completes with the kernel that writes dY (over dA)
+    // the weight gradient is enqueued BEHIND the input-gradient conv of the same layer (the side stream waits for it): two
+    // matrix-core kernels sharing the chip finish no sooner than one after the other, but a weight gradient that runs next
+    // to the following layer's BatchNorm-backward passes (memory-bound) hides them.
+    // A kernel that carries a completion signal leaves a ~5 us bubble behind it on its stream: only the kernel the side stream
+    // actually waits for gets one
+    const hipEvent_t dy_done = dx ? nullptr : m->next_fork_event();      // completes with the kernel that writes dY (over dA)
     // (dbias_deferred: the partial sums of the conv-bias gradient stay in the layer's own region; backward() finishes every
     // layer's in one launch at the end of the pass)
     launch_bn_bwd_apply(ctx, dA, Y, M, c.cout, c.scale(), c.shift(), c.mean(), c.invstd(),
@@ -957,71 +923,36 @@ int backward_conv_bn(rfi_model* m, ConvBN& c, float* dA, const float* Y, View in
     wa.slab_floats = m->bufs[m->ws_slab].n;
     wa.bf16 = m->compute_bf16;
     wa.bf16x3 = m->compute_x3;
-    const int ci = (int)(&c - m->convs.data());
-    if (!late || !dx) m->wgrad_on_side(ci, wa, dy_done);
-    int records = 0;
-    if (dx) {
-        ConvArgs a;
-        a.x = View{dA, c.cout};
-        a.N = s.N; a.H = s.H; a.W = s.W; a.Hin = s.H; a.Win = s.W;
-        a.Cin = c.cout; a.Cout = c.cin;     // dx exists only for layers whose cin == cin_p
-        a.w = c.wd;
-        a.w3 = m->use_w3() ? c.wd3 : nullptr;
-        m->ws_set(a);
-        a.bias = nullptr;
-        a.y = MutView{dx, c.cin};
-        a.Hout = s.H; a.Wout = s.W;
-        a.R = 3; a.S = 1; a.pad = 1;
-        a.bf16 = m->compute_bf16;
-        a.bf16x3 = m->compute_x3;
-        if (next && m->fuse_bn_bwd) {       // dx is next's dA: fold its BatchNorm-backward sums into this epilogue
-            a.stats = reinterpret_cast<double*>(ws);
-            a.stats_max_records = (int)(bn_stats_ws_floats(next->cout) / ((size_t)next->cout * 4));
-            a.bwd_y = next_Y;
-            a.bwd_scale = next->scale(); a.bwd_shift = next->shift();
-            a.bwd_mean = next->mean(); a.bwd_invstd = next->invstd();
-            a.bwd_slope = m->act_slope;
-        }
-        if (late) a.done = m->next_fork_event();      // the weight gradient starts when this kernel completes
-        launch_conv(ctx, a);
-        records = a.stats_records;
-        if (late) m->wgrad_on_side(ci, wa, a.done_used ? a.done : nullptr, !a.done_used);
+    if (!dx) {
+        m->wgrad_on_side(wa, dy_done);
+        return;
     }
-    return records;
+    ConvArgs a;
+    a.x = View{dA, c.cout};
+    a.N = s.N; a.H = s.H; a.W = s.W; a.Hin = s.H; a.Win = s.W;
+    a.Cin = c.cout; a.Cout = c.cin;     // dx exists only for layers whose cin == cin_p
+    a.w = c.wd;
+    a.w3 = m->use_w3() ? c.wd3 : nullptr;
+    m->ws_set(a);
+    a.bias = nullptr;
+    a.y = MutView{dx, c.cin};
+    a.Hout = s.H; a.Wout = s.W;
+    a.R = 3; a.S = 1; a.pad = 1;
+    a.bf16 = m->compute_bf16;
+    a.bf16x3 = m->compute_x3;
+    a.done = m->next_fork_event();      // the weight gradient starts when this kernel completes
+    launch_conv(ctx, a);
+    m->wgrad_on_side(wa, a.done_used ? a.done : nullptr, !a.done_used);
 }
 
 }  // namespace
 
 // A layer's weight gradient has no consumer before the optimiser: it is a FILLER for the stretches in which the main stream
-// runs memory-bound BatchNorm-backward kernels.  By default it is enqueued on the side stream when its layer is done; the
-// defer map (RFI_WGRAD_DEFER="9>2,4>1": the weight gradient of convs[9] goes behind that of convs[2], ...; ">-1": the end of
-// the pass) moves weight gradients of deep layers -- whose own BatchNorm chains are short, so that they only queue behind
-// matrix-bound kernels -- to the shallow levels, whose BatchNorm chains outlast their own weight gradients.  Everything a
-// weight-gradient kernel reads stays untouched until side_join, so the order is free.  Not with a gradient exchange: the
-// buckets leave in layer order.
-void rfi_model::wgrad_on_side(int ci, const rfi::WgradArgs& wa, hipEvent_t after, bool after_everything) {
-    auto issue = [&](const rfi::WgradArgs& w, hipEvent_t ev, bool all) {
-        SideScope side(this, all ? nullptr : ev);      // (no event: the side stream waits for everything enqueued on main so far)
-        launch_wgrad(ctx, w);
-        side.end();
-    };
-    const int to = (ci >= 0 && ci < (int)defer_to.size() && !ctx->exchange_active() && ctx->overlap) ? defer_to[ci] : -2;
-    if (to != -2) deferred.push_back(DeferredWgrad{wa, after_everything ? nullptr : after, to});
-    else issue(wa, after, after_everything);
-    for (size_t i = 0; i < deferred.size();) {    // whatever was parked behind this layer's weight gradient
-        if (deferred[i].to == ci && to == -2) {
-            issue(deferred[i].a, deferred[i].after, false);
-            deferred.erase(deferred.begin() + i);
-        } else ++i;
-    }
-}
-void rfi_model::flush_deferred_wgrads() {
-    for (auto& d : deferred) {
-        SideScope side(this, d.after);
-        launch_wgrad(ctx, d.a);
-        side.end();
-    }
-    deferred.clear();
+// runs memory-bound BatchNorm-backward kernels: it is enqueued on the side stream when its layer is done
+void rfi_model::wgrad_on_side(const rfi::WgradArgs& wa, hipEvent_t after, bool after_everything) {
+    SideScope side(this, after_everything ? nullptr : after);      // (no event: the side stream waits for everything enqueued on main so far)
+    launch_wgrad(ctx, wa);
+    side.end();
 }
 
 void rfi_model::backward(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w) {
@@ -1051,23 +982,8 @@ void rfi_model::backward(const float* x_dev, const uint8_t* labels_dev, int n, i
     refresh_dgrad_weights();
     wait_wd();                        // (the input-gradient-direction filter copies were rebuilt on the side stream)
     if (planesP) return backward_planes(x_dev, labels_dev, n, h, w);
-    static const int bound_env = getenv("RFI_SIDE_BOUND") ? atoi(getenv("RFI_SIDE_BOUND")) : 0;
-    side_bound = arch == 0 ? bound_env : 2;       // (the ResNet-style encoder double-buffers by block parity: bound 2)
-    deferred.clear();
-    if (defer_to.empty()) {                       // parsed once per model
-        defer_to.assign(convs.size(), -2);
-        const char* e = getenv("RFI_WGRAD_DEFER");
-        if (arch == 0 && e) {
-            int a = 0, b = 0, nread = 0;
-            while (*e && sscanf(e, "%d>%d%n", &a, &b, &nread) == 2) {
-                if (a >= 0 && a < (int)convs.size() && b >= -1 && b < (int)convs.size()) defer_to[a] = b;
-                e += nread;
-                if (*e == ',') ++e;
-            }
-        }
-    }
-    static const bool no_defer = getenv("RFI_NO_DEFER_DBIAS") != nullptr;
-    dbias_deferred = arch == 0 && dbias_pool && !no_defer && !ctx->exchange_active();
+    side_bound = arch == 0 ? 0 : 2;               // (the ResNet-style encoder double-buffers by block parity: bound 2)
+    dbias_deferred = arch == 0 && dbias_pool && !ctx->exchange_active();
     // loss -> dlogits -> head
     if (loss_kind == 1)
         launch_focal_bwd(ctx, buf(head_sigmoid ? probs : logits), labels_dev, M1, focal_alpha, focal_gamma, buf(dlogits));
@@ -1078,8 +994,7 @@ void rfi_model::backward(const float* x_dev, const uint8_t* labels_dev, int n, i
     // a one-channel head sends d[pixel] * w[channel] down: where its BatchNorm-backward sums come out of launch_head_bwd's own
     // pass the gradient tensor is never written -- bn_bwd_apply recomputes it from the logit gradients (268 MB of HBM traffic
     // less at batch 64 x 128^2 x 32, in the one stretch of the step where no matrix-core kernel can run)
-    static const bool no_head_fuse = getenv("RFI_NO_HEAD_FUSE") != nullptr;
-    bool head_skip = out_ch == 1 && !no_head_fuse;
+    bool head_skip = out_ch == 1;
     {
         ConvBN& last = convs[IB + 2 + 2 * (D - 1) + 1];
         // (head partials behind the region where the next layer expects its BatchNorm-backward records)
@@ -1091,7 +1006,6 @@ void rfi_model::backward(const float* x_dev, const uint8_t* labels_dev, int n, i
                                        buf(ws_red), nullptr, &head_skip, !hdefer);
     }
     // decoders, shallow to deep
-    int pending_records = head_records;   // BatchNorm-backward records a producing kernel left for the next layer
     for (int l = 1; l <= D; ++l) {
         const int k = D - l;
         Shape s{n, h >> (l - 1), w >> (l - 1)};
@@ -1101,12 +1015,11 @@ void rfi_model::backward(const float* x_dev, const uint8_t* labels_dev, int n, i
         UpConv& u = ups[k];
         // conv2: input = act(decY1) ; conv1: input = concat (materialised)
         const bool from_head = l == 1 && head_skip;
-        int rec = backward_conv_bn(this, c2, buf(gA[l]), buf(decY2[l]), View{buf(decY1[l]), c1.cout}, bn_xf(c1), s,
-                                   buf(gB[l]), pending_records, &c1, buf(decY1[l]), from_head ? buf(dlogits) : nullptr,
-                                   from_head ? params + head_w_off : nullptr);
+        backward_conv_bn(this, c2, buf(gA[l]), buf(decY2[l]), View{buf(decY1[l]), c1.cout}, bn_xf(c1), s,
+                         buf(gB[l]), l == 1 ? head_records : 0, from_head ? buf(dlogits) : nullptr,
+                         from_head ? params + head_w_off : nullptr);
         backward_conv_bn(this, c1, buf(gB[l]), buf(decY1[l]), View{buf(concat[l]), 2 * u.cout}, InXform{}, s,
-                         buf(dconcat[l]), rec, nullptr, nullptr);
-        pending_records = 0;
+                         buf(dconcat[l]), 0);
         // up-conv: dUp = dconcat[..., 0:C]
         const float* prevY = (l == D) ? buf(bottY2) : buf(decY2[l + 1]);
         ConvBN& prevBN = (l == D) ? convs[IB + 1] : convs[IB + 2 + 2 * (k - 1) + 1];
@@ -1149,16 +1062,7 @@ void rfi_model::backward(const float* x_dev, const uint8_t* labels_dev, int n, i
         a.R = 2; a.S = 2; a.pad = 0;
         a.bf16 = compute_bf16;
         a.bf16x3 = compute_x3;
-        if (fuse_bn_bwd) {                  // dprev is prevBN's dA: its BatchNorm-backward sums come out of this epilogue
-            a.stats = reinterpret_cast<double*>(buf(ws_red));
-            a.stats_max_records = (int)(bn_stats_ws_floats(prevBN.cout) / ((size_t)prevBN.cout * 4));
-            a.bwd_y = prevY;
-            a.bwd_scale = prevBN.scale(); a.bwd_shift = prevBN.shift();
-            a.bwd_mean = prevBN.mean(); a.bwd_invstd = prevBN.invstd();
-            a.bwd_slope = act_slope;
-        }
         launch_conv(ctx, a);
-        pending_records = a.stats_records;
         // gradients of decoder level l (and, for l = 1, of the head) are complete: exchange them now
         bucket_ready(u.w_off, l == 1 ? n_flat : ups[k + 1].w_off);
     }
@@ -1167,20 +1071,17 @@ void rfi_model::backward(const float* x_dev, const uint8_t* labels_dev, int n, i
         Shape s{n, h >> D, w >> D};
         ConvBN& c1 = convs[IB];
         ConvBN& c2 = convs[IB + 1];
-        int rec = backward_conv_bn(this, c2, buf(gBottA), buf(bottY2), View{buf(bottY1), c1.cout}, bn_xf(c1), s,
-                                   buf(gBottB), pending_records, &c1, buf(bottY1));
-        backward_conv_bn(this, c1, buf(gBottB), buf(bottY1), View{buf(pool[D]), c1.cin}, InXform{}, s,
-                         buf(dpool[D]), rec, nullptr, nullptr);
+        backward_conv_bn(this, c2, buf(gBottA), buf(bottY2), View{buf(bottY1), c1.cout}, bn_xf(c1), s, buf(gBottB), 0);
+        backward_conv_bn(this, c1, buf(gBottB), buf(bottY1), View{buf(pool[D]), c1.cin}, InXform{}, s, buf(dpool[D]), 0);
         bucket_ready(c1.w_off, ups[0].w_off);
     }
     if (arch == 2) {                  // ResNet-style encoder (model_resnet.cpp)
         backward_resnet_encoder(x_dev, n, h, w);
-        flush_deferred_wgrads();
         side_join();
         return;
     }
     // encoders, deep to shallow.  They write their own gradient tensors (not the decoder's of the same level), so nothing
-    // the weight-gradient kernels read is rewritten before side_join(): no run-ahead bound (RFI_SIDE_BOUND restores one)
+    // the weight-gradient kernels read is rewritten before side_join(): no run-ahead bound
     for (int l = D; l >= 1; --l) {
         Shape s{n, h >> (l - 1), w >> (l - 1)};
         ConvBN& c1 = convs[2 * (l - 1)];
@@ -1195,15 +1096,13 @@ void rfi_model::backward(const float* x_dev, const uint8_t* labels_dev, int n, i
         if (!have)
             launch_pool_bwd_merge(ctx, buf(encY2[l]), s.N, s.H, s.W, c2.cout, c2.scale(), c2.shift(),
                                   View{buf(dconcat[l]) + c2.cout, 2 * c2.cout}, buf(dpool[l]), buf(gA[l]), act_slope);
-        int rec = backward_conv_bn(this, c2, buf(gA[l]), buf(encY2[l]), View{buf(encY1[l]), c1.cout}, bn_xf(c1), s,
-                                   buf(gB[l]), have, &c1, buf(encY1[l]));
+        backward_conv_bn(this, c2, buf(gA[l]), buf(encY2[l]), View{buf(encY1[l]), c1.cout}, bn_xf(c1), s, buf(gB[l]), have);
         View in = (l == 1) ? (c1.cin_p == in_ch ? View{x_dev, in_ch} : View{buf(x_pad), c1.cin_p})
                            : View{buf(pool[l - 1]), c1.cin};
         backward_conv_bn(this, c1, buf(gB[l]), buf(encY1[l]), in, InXform{}, s,
-                         (l == 1) ? nullptr : buf(dpool[l - 1]), rec, nullptr, nullptr);
+                         (l == 1) ? nullptr : buf(dpool[l - 1]), 0);
         bucket_ready(c1.w_off, convs[l == D ? IB : 2 * l].w_off);       // convs[2 l] = first conv of the next level / the bottleneck
     }
-    flush_deferred_wgrads();
     if (dbias_deferred) launch_finish_channel_sums_batched(ctx, static_cast<const FinishSumDesc*>(dbias_descs), dbias_n, dbias_max_c);
     side_join();
     side_bound = 2;

@@ -103,9 +103,7 @@ struct rfi_model {
     float act_slope = 0.0f;           // 0: ReLU; > 0: LeakyReLU(negative_slope) (UNetDifferentActivation)
     bool compute_bf16 = false;        // conv / wgrad MFMAs on bf16-rounded operands (fp32 storage + accumulate)
     bool compute_x3 = true;           // DEFAULT: float32 contractions by 3 x bf16 pieces (float32-level accuracy)
-    bool use_w3() const { return compute_x3 || (compute_bf16 && rfi::bf16_k16()); }   // who reads the pre-split filter records
-    bool fuse_bn_bwd = false;         // BatchNorm-backward sums folded into the epilogue of the kernel producing dA (RFI_BN_FUSE=1: on;
-                                      // measured neutral: -0.31 ms of BatchNorm passes, +0.18 ms of conv epilogues)
+    bool use_w3() const { return compute_x3; }   // who reads the pre-split filter records
     int loss_kind = 0;                // 0: BCE-with-logits + dice (the reference's, train_model.py:120-128); 1: focal
     float focal_alpha = 0.25f, focal_gamma = 2.0f;
     bool head_sigmoid = false;        // UNetOverfit: forward returns sigmoid(logits); the loss sees that too
@@ -130,7 +128,7 @@ struct rfi_model {
     double ws_bytes = 0;
     std::unordered_map<const float*, const rfi::bf16_t*> ws_by_w;    // float32 filter pointer (ConvArgs::w) -> the same filters for conv_ws / gemm_ws
     int ws_P = 0;                     // planes of the copies in ws_pool: 3 (float32 by 3 x bf16), 1 (bf16 operands), 0 (none built)
-    int ws_need() const { return planesP ? 0 : compute_x3 ? 3 : (compute_bf16 && !rfi::bf16_k16()) ? 1 : 0; }
+    int ws_need() const { return planesP ? 0 : compute_x3 ? 3 : compute_bf16 ? 1 : 0; }
     // the copy of filter `w` for the wave-specialised kernels in the current arithmetic (null: none)
     void ws_set(rfi::ConvArgs& a) const {
         auto it = ws_by_w.find(a.w);
@@ -151,8 +149,6 @@ struct rfi_model {
     // stream runs the forward pass; the backward pass waits for wd_ready
     hipEvent_t wd_ready = nullptr;
     bool wd_pending = false;
-    std::vector<hipEvent_t> skip_done;      // per encoder level: the skip half of concat[l] is written (side stream, forward pass)
-    unsigned skip_pending = 0;              // levels whose skip write the main stream has not waited for yet
     bool wd_side_todo = false;        // the side half of a split rebuild has not been enqueued yet
     void side_rebuild_wd();
     bool x3_reads_wd = false;         // the batched 3 x bf16 record rebuild reads dgrad-layout filters
@@ -241,8 +237,7 @@ struct rfi_model {
     // the 1x1 head as a GEMM on the matrix cores (conv kernels forward / input gradient, weight-gradient kernel) instead of the
     // per-pixel VALU kernels written for one output channel: where it has enough outputs (the RPN head's 5 A = 20)
     bool head_on_mfma() const {
-        static const bool off = getenv("RFI_HEAD_VALU") != nullptr;       // A/B runs
-        return !off && (arch == 3 || arch == 4) && out_ch >= 8 && out_ch % 4 == 0 && in_ch % 4 == 0 && (compute_x3 || compute_bf16);
+        return (arch == 3 || arch == 4) && out_ch >= 8 && out_ch % 4 == 0 && in_ch % 4 == 0 && (compute_x3 || compute_bf16);
     }
     void build_mask();
     void prepare_mask(int n, int h, int w);
@@ -338,12 +333,7 @@ struct rfi_model {
     bool lazy_pending = false;
     void side_join_lazy();
     void join_pending_side();
-    // weight gradients parked for a later point of the backward pass (model.cpp, wgrad_on_side)
-    struct DeferredWgrad { rfi::WgradArgs a; hipEvent_t after; int to; };
-    std::vector<DeferredWgrad> deferred;
-    std::vector<int> defer_to;        // per conv: -2 at once; k >= 0: behind convs[k]'s weight gradient; -1: at the end of the pass
-    void wgrad_on_side(int ci, const rfi::WgradArgs& wa, hipEvent_t after, bool after_everything = false);
-    void flush_deferred_wgrads();
+    void wgrad_on_side(const rfi::WgradArgs& wa, hipEvent_t after, bool after_everything = false);
     // bucketed gradient exchange (common.hpp): grads[lo, hi) are final once everything enqueued so far on the main
     // and side streams has run -> all-reduce them on the communication stream; exchange_join: main waits for all
     bool exchange_in_backward = false;   // set by the full-step entry points only (the split API exchanges explicitly)

@@ -408,9 +408,7 @@ void rfi_model::forward_backbone(const float* x_dev, int n, int h, int w) {
 // dP2..dP6 sit in fdP[0..3] / fdP6 (rfi_backbone_backward copies them there)
 void rfi_model::backward_backbone(const float* x_dev, int n, int h, int w) {
     refresh_dgrad_weights();
-    static const int bound_env = getenv("RFI_BB_SIDE_BOUND") ? atoi(getenv("RFI_BB_SIDE_BOUND")) : 2;     // (1..5: A/B runs; measured 31.8 / 32.2 / 32.9 ms per
-                                                                                                    // step of the detector at bound 2 / bound 5 / no side stream)
-    side_bound = std::min(5, std::max(1, bound_env));
+    side_bound = 2;                   // (measured 31.8 / 32.2 / 32.9 ms per step of the detector at bound 2 / bound 5 / no side stream)
     const int F = out_ch;
     int last[4], bi = -1;
     for (int s = 0; s < 4; ++s) { bi += kBlocksPerStage[s]; last[s] = bi; }

@@ -66,8 +66,7 @@ void rfi_model::prepare_planes(int n, int h, int w) {
     }
     const int64_t Mb = (int64_t)n * (h >> D) * (w >> D);
     for (int i : {pA1b, pdYbottA, pdYbottB}) pl[i].ensure(ctx, Mb, feat << D, P);
-    static const bool no_y16 = getenv("RFI_NO_Y16") != nullptr;                 // A/B runs: float32 conv outputs
-    y16_flow = P == 1 && feat % 4 == 0 && (!no_y16 || rs);
+    y16_flow = P == 1 && feat % 4 == 0;
     if (y16_flow) {
         if (yB1 < 0) {
             auto mk1 = [&](std::vector<int>& v) { v.assign(D + 1, -1); for (int l = 1; l <= D; ++l) { pl.emplace_back(); v[l] = (int)pl.size() - 1; } };
@@ -83,8 +82,7 @@ void rfi_model::prepare_planes(int n, int h, int w) {
         pl[yB1].ensure(ctx, Mb, feat << D, 1);
         pl[yD2top].ensure(ctx, M1, feat, 1);
     }
-    static const bool no_g16 = getenv("RFI_NO_G16") != nullptr;                 // A/B runs: float32 gradient tensors
-    g16_flow = y16_flow && feat % 16 == 0 && (!no_g16 || rs);
+    g16_flow = y16_flow && feat % 16 == 0;
     if (g16_flow) {
         if (g16BottB < 0) {
             auto mk1 = [&](std::vector<int>& v) { v.assign(D + 1, -1); for (int l = 1; l <= D; ++l) { pl.emplace_back(); v[l] = (int)pl.size() - 1; } };
@@ -99,8 +97,7 @@ void rfi_model::prepare_planes(int n, int h, int w) {
         }
         pl[g16BottB].ensure(ctx, Mb, feat << D, 1);
     }
-    static const bool no_ctp = getenv("RFI_NO_CONVT_PLANES") != nullptr;        // A/B runs: the round-1 transposed-conv kernels
-    convt_planes = g16_flow && feat % 32 == 0 && !no_ctp;
+    convt_planes = g16_flow && feat % 32 == 0;
     if (convt_planes) {
         if (yB2 < 0) {
             auto mk1 = [&](std::vector<int>& v) { v.assign(D + 1, -1); for (int l = 1; l <= D; ++l) { pl.emplace_back(); v[l] = (int)pl.size() - 1; } };
@@ -572,8 +569,7 @@ int backward_pconv_bn(rfi_model* m, ConvBN& c, YRef dA, YRef Y, const PlaneSeg* 
         else { a.y = dx.f; a.y_pstride = c.cin; }
         a.Hout = s.H; a.Wout = s.W;
         a.algo_flops = 2.0 * s.N * s.H * s.W * 9.0 * c.cin * c.cout;
-        static const bool no_fuse = getenv("RFI_NO_BN_FUSE") != nullptr;     // A/B runs: separate bn_bwd_reduce
-        if (next && next_Y.bf16 && !no_fuse) {
+        if (next && next_Y.bf16) {
             a.stats = reinterpret_cast<double*>(ws);          // (this layer's dy sums have been finished out of it)
             a.stats_max_records = (int)(bn_stats_ws_floats(next->cout) / ((size_t)next->cout * 4));
             a.bwd_y16 = static_cast<const bf16_t*>(next_Y.p);
@@ -677,15 +673,13 @@ void rfi_model::backward_planes(const float* x_dev, const uint8_t* labels_dev, i
     const int D = depth, IB = i_bott;
     // every layer owns its dY plane tensor and the other side-stream inputs (forward planes, dconcat, raw conv outputs)
     // are not rewritten before side_join(): the main stream never has to wait for a weight gradient inside the pass
-    static const int bound_env = getenv("RFI_SIDE_BOUND") ? atoi(getenv("RFI_SIDE_BOUND")) : 0;
-    side_bound = bound_env;
+    side_bound = 0;
     // a raw conv output of the forward pass: bfloat16 tensor pl[hi] in the bf16 flow, else float32 bufs[fi]
     auto yr = [&](int fi, int hi) { return (y16_flow && hi >= 0) ? YRef(pl[hi].p, pl[hi].pstride) : YRef(buf(fi)); };
     // a gradient tensor an input-gradient conv writes: bfloat16 tensor pl[hi] in the bf16 flow, else float32 bufs[fi]
     auto gt = [&](int fi, int hi) { return hi >= 0 ? GT(pl[hi]) : GT(buf(fi)); };
     const int64_t M1 = (int64_t)n * h * w;
-    static const bool no_defer = getenv("RFI_NO_DEFER_DBIAS") != nullptr;
-    dbias_deferred = dbias_pool && !no_defer && !ctx->exchange_active();    // (bias gradients must be final before their bucket leaves)
+    dbias_deferred = dbias_pool && !ctx->exchange_active();    // (bias gradients must be final before their bucket leaves)
     if (loss_kind == 1)
         launch_focal_bwd(ctx, buf(head_sigmoid ? probs : logits), labels_dev, M1, focal_alpha, focal_gamma, buf(dlogits));
     else

@@ -479,22 +479,19 @@ void launch_wgrad(rfi_ctx* ctx, const WgradArgs& a_in, int impl) {
         launch_wgrad_direct(ctx, a);
         return;
     }
-    static const bool no_ws = getenv("RFI_NO_WGRAD_WS") != nullptr;       // A/B runs: round 2's kernels
-    static const bool no_stem = getenv("RFI_NO_STEM") != nullptr;
-    if (!no_ws && !no_stem && a.bf16x3 && wgrad_stem_eligible(a)) {
+    if (a.bf16x3 && wgrad_stem_eligible(a)) {
         launch_wgrad_stem(ctx, a);    // Cx = 4: (tap, channel) packed into the GEMM's N (wgrad_stem.hip)
         return;
     }
-    if (!no_ws && (a.bf16x3 || a.bf16) && wgrad_ws_eligible(a) && (wgrad_split_eligible(a) || (a.R == 2 && a.S == 2))) {
+    if ((a.bf16x3 || a.bf16) && wgrad_ws_eligible(a) && (wgrad_split_eligible(a) || (a.R == 2 && a.S == 2))) {
         launch_wgrad_ws(ctx, a);      // (its slab plan -- 256 workgroups -- fits inside wgrad_split's, which sized the workspace)
         return;
     }
-    static const bool old_x3 = getenv("RFI_OLD_WGRAD") != nullptr;       // round 1's split-per-fragment kernel (A/B runs)
     // R = 2 / S = 1 and R = 1 (ResNet-style encoder) exist only in the split-at-staging kernel (P = 1: bf16 mode)
     const bool only_split = (a.R == 2 && a.S == 1) || a.R == 1;
     if (only_split) RFI_REQUIRE((a.bf16 || a.bf16x3) && wgrad_split_eligible(a),
                                 "wgrad: 2x2 stride-1 and 1x1 weight gradients need the bf16 or 3 x bf16 arithmetic and 4-channel alignment");
-    if (((a.bf16x3 && !old_x3) || only_split) && wgrad_split_eligible(a)) {
+    if ((a.bf16x3 || only_split) && wgrad_split_eligible(a)) {
         launch_wgrad_split(ctx, a);
         return;
     }

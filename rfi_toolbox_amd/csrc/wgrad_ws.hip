@@ -61,7 +61,7 @@ struct WWCfg {
     static_assert(BLOCKS == 1 || BLOCKS == 2 || BLOCKS == 4, "1, 2 or 4 channel blocks");
     static_assert(BM % 16 == 0 && KS % WP == 0 && TW % 4 == 0, "tile must split into k-steps of 16 pixels");
     static_assert(NPT % YQ == 0 && NPT % XQ == 0, "a producer thread keeps one channel group for all its items");
-    static_assert(PWV == 4 || PWV == 8 || PWV == 12, "4 consumer waves + 4, 8 or 12 producer waves");
+    static_assert(PWV == 4 || PWV == 8, "4 consumer waves + 4 or 8 producer waves");
     static_assert(ST == 1 || (ST == 2 && R == 2), "stride 2: the transposed conv's 2x2 taps");
     static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 };
@@ -433,10 +433,9 @@ struct Plan { int nsplit; int64_t slab_stride; };
 
 template <int R, int BYB, int BXB, int TH, int TW>
 Plan plan_cfg(const WgradArgs& a) {
-    static const int wgs = getenv("RFI_WGRAD_WS_WGS") ? atoi(getenv("RFI_WGRAD_WS_WGS")) : 256;    // one workgroup per CU
     const int ntiles = a.N * (int)cdiv(a.H, TH) * (int)cdiv(a.W, TW);
     const int chunks = (int)cdiv(a.Cy, 32 * BYB) * (int)cdiv(a.Cx, 32 * BXB);
-    int nsplit = (int)cdiv(wgs, chunks);
+    int nsplit = (int)cdiv(256, chunks);             // one workgroup per CU
     if (nsplit > ntiles) nsplit = ntiles;
     if (nsplit < 1) nsplit = 1;
     return Plan{nsplit, (int64_t)R * R * a.tap_stride};
@@ -509,14 +508,14 @@ void select(rfi_ctx* ctx, const WgradArgs& a) {
     } while (0)
     if constexpr (R == 1) {
         // one tap: producer-bound (header) -- eight producer waves where both operands have 64-channel tiles
-        static const int pwv = getenv("RFI_WGRAD_PWV") ? atoi(getenv("RFI_WGRAD_PWV")) : 8;
-        if (y2 && x2 && pwv == 8) {
+        if (y2 && x2) {
             if (p1) launch_cfg<1, 2, 2, 8, 8, 1, 2, 1, 8>(ctx, a);
             else launch_cfg<1, 2, 2, 8, 8, 3, 2, 1, 8>(ctx, a);
             return;
         }
+    } else {
+        if (y2 && x2) RFI_WW(2, 2, 8, 8);
     }
-    if (y2 && x2) RFI_WW(2, 2, 8, 8);
     if (y2) RFI_WW(2, 1, 8, 8);
     if (x2) RFI_WW(1, 2, 8, 8);
     if (a.W >= 16) RFI_WW(1, 1, 8, 16);
@@ -529,13 +528,10 @@ void select(rfi_ctx* ctx, const WgradArgs& a) {
 void select_t2(rfi_ctx* ctx, const WgradArgs& a, Plan* plan_only) {
     const bool p1 = a.bf16 && !a.bf16x3;
     const bool y2 = a.Cy > 32, x2 = a.Cx > 32;
-    static const int pwv = getenv("RFI_WGRAD_T2_PWV") ? atoi(getenv("RFI_WGRAD_T2_PWV")) : 8;     // (A/B: 4, 8 or 12 producer waves)
 #define RFI_WT(BYB_, BXB_, TH_, TW_)                                                       \
     do {                                                                                   \
         if (plan_only) { *plan_only = plan_cfg<2, BYB_, BXB_, TH_, TW_>(a); return; }      \
         if (p1) launch_cfg<2, BYB_, BXB_, TH_, TW_, 1, 2, 2, 8>(ctx, a);                   \
-        else if (pwv == 12) launch_cfg<2, BYB_, BXB_, TH_, TW_, 3, 2, 2, 12>(ctx, a);      \
-        else if (pwv == 4) launch_cfg<2, BYB_, BXB_, TH_, TW_, 3, 2, 2, 4>(ctx, a);        \
         else launch_cfg<2, BYB_, BXB_, TH_, TW_, 3, 2, 2, 8>(ctx, a);                      \
         return;                                                                            \
     } while (0)
@@ -556,8 +552,7 @@ bool wgrad_ws_eligible(const WgradArgs& a) {
     if ((int64_t)a.N * a.Hx * a.Wx * a.xop.pstride * 4 >= 0x7f000000ll || (int64_t)a.N * a.H * a.W * a.yop.pstride * 4 >= 0x7f000000ll) return false;
     if (((int64_t)a.Wx + 1) * a.xop.pstride * 4 >= (1 << 24)) return false;
     if (a.R == 2 && a.S == 2 && a.pad == 0) {             // the transposed conv's weight gradient (select_t2)
-        static const bool no_t2 = getenv("RFI_NO_WGRAD_T2") != nullptr;
-        return !no_t2 && a.Hx == 2 * a.H && a.Wx == 2 * a.W;
+        return a.Hx == 2 * a.H && a.Wx == 2 * a.W;
     }
     if (a.S != 1) return false;
     return (a.R == 3 && a.pad == 1) || (a.R == 2 && a.pad == 1) || (a.R == 1 && a.pad == 0);

@@ -23,8 +23,6 @@ from __future__ import annotations
 import ctypes as C
 import math
 
-import os
-
 import numpy as np
 
 from .._lib import DEVICE, HOST, check, lib
@@ -82,8 +80,6 @@ def _paste(prob, box, h, w):
     out[iy1:iy2, ix1:ix2] = v > 0.5
     return out
 
-
-_RPN_ALL_LATE = os.environ.get("RFI_RPN_ALL_LATE") is not None     # A/B runs: every level's RPN training pass behind the proposals
 
 class MaskRCNN:
     def __init__(self, num_classes=2, in_channels=3, base_width=64, fpn_channels=256, representation_size=1024, *, device=None,
@@ -362,7 +358,7 @@ class MaskRCNN:
         for lvl in (0, 1, 2, 3, 4):
             _, hl, wl, _ = b.shapes[lvl]
             check(lib.rfi_model_forward_nhwc(self.rpn._h, P(b.feats[lvl]), DEVICE, n, hl, wl, P(b.rpn_out[lvl]), DEVICE))
-            if lvl == 0 and not _RPN_ALL_LATE:
+            if lvl == 0:
                 rpn_backward(0)
         # ---- proposals: top pre_nms per level -> decode + clip -> per-level NMS -> best post_nms + ground truth
         K = self.pre_nms
@@ -387,7 +383,7 @@ class MaskRCNN:
                                      P(b.roi_lvl), P(b.img_start), P(b.rois_m), P(b.rois_g), P(b.lvl_m), P(b.fg_start), P(b.counts)))
         check(lib.rfi_readback_begin(H, P(b.counts), 8))         # (R, Rf) come down while the RPN head's backward passes run
         # ---- the rest of the RPN head's own training work (level 4 first: its forward pass was the last one above)
-        for lvl in ((4, 0, 1, 2, 3) if _RPN_ALL_LATE else (4, 1, 2, 3)):
+        for lvl in (4, 1, 2, 3):
             _, hl, wl, _ = b.shapes[lvl]
             if lvl != 4:
                 check(lib.rfi_model_forward_nhwc(self.rpn._h, P(b.feats[lvl]), DEVICE, n, hl, wl, P(b.rpn_out[lvl]), DEVICE))

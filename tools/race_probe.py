@@ -5,8 +5,7 @@ share CUs, so any data race or co-residency hazard shows up here as a flicker; t
 v_cvt_f64_f32 hazard of DESIGN.md was found (lanes 48-63 of the BatchNorm-backward sums of pool_bwd_merge, next to a
 weight-gradient kernel).
 
-    python tools/race_probe.py [bfloat16|float32] [repetitions] [comm_emulate world]
-    RFI_SIDE_BOUND=2 ...      # bound the main stream's run-ahead over the side stream as the float32 path does"""
+    python tools/race_probe.py [bfloat16|float32] [repetitions] [comm_emulate world]"""
 import os
 import sys
 
