@@ -336,6 +336,26 @@ int rfi_confusion_counts(rfi_ctx* ctx, const void* pred, int pred_dtype, int pre
 int rfi_threshold_logits(rfi_ctx* ctx, const float* logits_dev, int64_t count, float threshold,
                          uint8_t* mask_dev);
 
+/* ---- flagging-quality statistics: the reductions of evaluation/statistics.py:10-229 over a whole array.
+ *      data: `count` elements of dtype RFI_C128 / RFI_C64 / RFI_F64 / RFI_F32 (complex: |z| by NumPy's rule
+ *      L * sqrt(fma(S/L, S/L, 1)), L = max(|re|,|im|), S = min, in the input's precision); flags: `count` bytes of
+ *      flags_dtype RFI_U8 (non-zero == flagged) or NULL (nothing flagged).  `want` is a bit set of RFI_FS_ALL (the
+ *      statistics of every element -> all_out), RFI_FS_CLEAN (of the unflagged elements -> clean_out) and
+ *      RFI_FS_MEDIANS (also median and MAD).  Medians, MAD and max are exact and, like mean and std, in float32
+ *      for float32 / complex64 input (float32 values returned as doubles); mean and std are two-pass fp64 sums.
+ *      Any NaN among a view's values makes its mean, std, median, MAD and max NaN (np.median, not nanmedian);
+ *      an empty view has count 0 and NaN statistics.  One call, one device synchronisation, bitwise reproducible;
+ *      with no flag set the unflagged view is bit-identical to the all view. ---- */
+typedef struct rfi_flag_stats {
+    int64_t count;       /* elements in the view */
+    int64_t flagged;     /* flagged elements of the whole input */
+    double mean, std, median, mad, max;
+} rfi_flag_stats;
+enum { RFI_FS_ALL = 1, RFI_FS_CLEAN = 2, RFI_FS_MEDIANS = 4 };
+int rfi_flag_statistics(rfi_ctx* ctx, const void* data, int data_mem, int dtype, int64_t count,
+                        const void* flags, int flags_mem, int flags_dtype, int want,
+                        rfi_flag_stats* all_out, rfi_flag_stats* clean_out);
+
 /* ---- kernel-level entry points (device pointers only).  Used by the parity tests to
  *      check each HIP kernel against the oracle in isolation.  impl: 0 auto, 1 direct VALU,
  *      2 MFMA implicit GEMM in native float32 (v_mfma_f32_32x32x2_f32), 3 MFMA implicit GEMM with bfloat16

@@ -19,6 +19,14 @@ U8, FLOAT32 = 0, 1
 IMPL_AUTO, IMPL_DIRECT, IMPL_MFMA, IMPL_MFMA_BF16, IMPL_MFMA_BF16X3, IMPL_PLANES_X3, IMPL_PLANES_BF16, IMPL_WS_X3, IMPL_WS_BF16 = 0, 1, 2, 3, 4, 5, 6, 7, 8
 
 
+FS_ALL, FS_CLEAN, FS_MEDIANS = 1, 2, 4
+
+
+class FlagStats(C.Structure):
+    _fields_ = [("count", C.c_int64), ("flagged", C.c_int64), ("mean", C.c_double), ("std", C.c_double),
+                ("median", C.c_double), ("mad", C.c_double), ("max", C.c_double)]
+
+
 class Hyper(C.Structure):
     _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
                 ("weight_decay", C.c_double), ("max_grad_norm", C.c_double)]
@@ -152,6 +160,7 @@ _PROTOS = {
     "rfi_preprocess_gather": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _i]),
     "rfi_confusion_counts": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i64, _pi64, _pi64, _pi64]),
     "rfi_threshold_logits": (_i, [_vp, _vp, _i64, _f, _vp]),
+    "rfi_flag_statistics": (_i, [_vp, _vp, _i, _i, _i64, _vp, _i, _i, _i, C.POINTER(FlagStats), C.POINTER(FlagStats)]),
     "rfi_op_conv3x3": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     "rfi_op_conv1x1": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     "rfi_op_conv_s2": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),

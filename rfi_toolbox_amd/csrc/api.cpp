@@ -1496,6 +1496,44 @@ int rfi_confusion_counts(rfi_ctx* ctx, const void* pred, int pred_dtype, int pre
         if (tt_) ctx->release(tt_);
     });
 }
+int rfi_flag_statistics(rfi_ctx* ctx, const void* data, int data_mem, int dtype, int64_t count, const void* flags,
+                        int flags_mem, int flags_dtype, int want, rfi_flag_stats* all_out, rfi_flag_stats* clean_out) {
+    return guarded([&] {
+        RFI_REQUIRE(ctx, "flag_statistics: null context");
+        RFI_REQUIRE(dtype >= RFI_C128 && dtype <= RFI_F32, "flag_statistics: dtype must be complex128, complex64, float64 or float32");
+        RFI_REQUIRE(count >= 0 && (count == 0 || data), "flag_statistics: bad data");
+        RFI_REQUIRE(!flags || flags_dtype == RFI_U8, "flag_statistics: flags must be uint8 (non-zero == flagged)");
+        RFI_REQUIRE(data_mem == RFI_HOST || data_mem == RFI_DEVICE, "flag_statistics: bad data memory kind");
+        RFI_REQUIRE(!flags || flags_mem == RFI_HOST || flags_mem == RFI_DEVICE, "flag_statistics: bad flags memory kind");
+        RFI_REQUIRE((want & ~(RFI_FS_ALL | RFI_FS_CLEAN | RFI_FS_MEDIANS)) == 0 && (want & (RFI_FS_ALL | RFI_FS_CLEAN)),
+                    "flag_statistics: want must select the all and/or the unflagged view");
+        RFI_REQUIRE((!(want & RFI_FS_ALL) || all_out) && (!(want & RFI_FS_CLEAN) || clean_out), "flag_statistics: null output");
+        const double qnan = std::nan("");
+        rfi_flag_stats res[2];
+        for (auto& r : res) r = rfi_flag_stats{0, 0, qnan, qnan, qnan, qnan, qnan};
+        if (count > 0) {
+            ctx->activate();
+            const size_t esz = dtype == RFI_C128 ? 16 : (dtype == RFI_F32 ? 4 : 8);
+            const bool cplx = dtype == RFI_C128 || dtype == RFI_C64;
+            // without flags the unflagged view IS the all view: compute it once
+            const int views = flags ? (want & (RFI_FS_ALL | RFI_FS_CLEAN)) : RFI_FS_ALL;
+            Staged in(ctx, data, data_mem, (size_t)count * esz);
+            Staged fl(ctx, flags, flags_mem, flags ? (size_t)count : 0);
+            // workspace and |z| buffer in the context's scratch (kept between calls: no allocation per call)
+            const size_t wsb = (flag_stats_ws_bytes() + 255) / 256 * 256;
+            char* ws = static_cast<char*>(ctx->get_scratch(wsb + (cplx ? (size_t)count * (esz / 2) : 0)));
+            void* mag = cplx ? ws + wsb : nullptr;
+            auto* dout = reinterpret_cast<rfi_flag_stats*>(ws + flag_stats_ws_bytes() - sizeof(res));
+            launch_flag_stats(ctx, in.dev, dtype, count, static_cast<const uint8_t*>(fl.dev), views,
+                              (want & RFI_FS_MEDIANS) != 0, ws, mag, dout);
+            RFI_CHECK_HIP(hipMemcpyAsync(res, dout, sizeof(res), hipMemcpyDeviceToHost, ctx->stream));
+            RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+            if (!flags) res[1] = res[0];
+        }
+        if (want & RFI_FS_ALL) *all_out = res[0];
+        if (want & RFI_FS_CLEAN) *clean_out = res[1];
+    });
+}
 int rfi_threshold_logits(rfi_ctx* ctx, const float* logits_dev, int64_t count, float threshold,
                          uint8_t* mask_dev) {
     return guarded([&] {

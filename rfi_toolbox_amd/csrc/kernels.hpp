@@ -318,6 +318,12 @@ void launch_confusion(rfi_ctx* ctx, const void* pred, int pred_dtype, const void
                       int truth_dtype, int64_t count, unsigned long long* counts3);
 void launch_threshold(rfi_ctx* ctx, const float* logits, int64_t count, float threshold,
                       uint8_t* mask);
+// whole-array flagging statistics (flag_stats.hip): src is `n` elements of dtype RFI_C128/C64/F64/F32 on the device,
+// flags n bytes (non-zero == flagged) or nullptr; views bit 0 all elements, bit 1 unflagged elements; ws holds
+// flag_stats_ws_bytes(); mag holds n input-precision floats (complex input only); out_dev[2] receives the views
+size_t flag_stats_ws_bytes();
+void launch_flag_stats(rfi_ctx* ctx, const void* src, int dtype, int64_t n, const uint8_t* flags, int views,
+                       bool medians, void* ws, void* mag, rfi_flag_stats* out_dev);
 
 // x[i] *= f  (the emulated gradient exchange of the single-GPU tests, rfi_comm_emulate)
 void launch_scale_inplace(rfi_ctx* ctx, float* x, int64_t n, float f);
