@@ -356,6 +356,87 @@ int rfi_flag_statistics(rfi_ctx* ctx, const void* data, int data_mem, int dtype,
                         const void* flags, int flags_mem, int flags_dtype, int want,
                         rfi_flag_stats* all_out, rfi_flag_stats* clean_out);
 
+/* ---- RFISimulator on device: the 4-polarisation coherent-phase waterfalls and full-truth masks of
+ *      rfi_toolbox/core/simulator.py:147-237 (generate_rfi) and :137-145 (generate_clean_data), n_samples at once.
+ *      Physics and order of addition are the reference's, in fp64; the random stream is Philox4x32-10
+ *      (10 rounds, multipliers 0xD2511F53 / 0xCD9E8D57, key bumps 0x9E3779B9 / 0xBB67AE85), key (seed lo, seed hi),
+ *      counter (c0 position, c1 event, c2 stream, c3 global sample index = first_sample + s).  A draw depends
+ *      on nothing else, so results do not depend on the launch geometry or on how samples are split into calls.
+ *
+ *      Word -> value mappings (a, b, w: 32-bit words):
+ *        u53(a, b)      = ((a >> 5) * 2^26 + (b >> 6)) * 2^-53          in [0, 1) (NumPy's random_sample rule)
+ *        uniform(lo,hi) = lo + (hi - lo) * u53                           (NumPy's order of operations)
+ *        randint(lo,hi) = lo + ((uint64) w * (hi - lo)) >> 32            in [lo, hi)
+ *        sign(w)        = w >> 31 ? -1.0 : +1.0
+ *        power(w)       = power_range[((uint64) w * n_power) >> 32]
+ *        normals        = Box-Muller: r = sqrt(-2 ln((a + 1) 2^-32)), th = 2 pi b 2^-32 -> (r cos th, r sin th)
+ *
+ *      Event table (drawn on device into events_dev, RFI_SIM_SLOTS(T, F) records per sample, in this order):
+ *        slot 0                header: i0 = number of broadband chunks (2 or 3), v0 = baseline_frac
+ *        slots 1..3            broadband chunks (only the first i0 are used)
+ *        NN = int(F * 0.05)    narrowband channels;  NB = int(T * 0.1) burst rows
+ *        5 linear sweeps, then 5 quadratic sweeps.
+ *      Event e of category k draws 20 words w0..w19 = Philox(c0 = j, c1 = e, c2 = k, c3 = sample), j = 0..4 in turn
+ *      (k: 0 header, 1 broadband, 2 narrowband, 3 burst, 4 linear, 5 quadratic):
+ *        header      baseline_frac = u53(w0, w1) (unless given), chunks = 2 + randint(0, 2) of w2
+ *        broadband   i0 start = randint(0, max(1, F - 101)) of w0, i1 width = randint(50, min(150, F - 1 - start))
+ *                    of w1, i2 drifting = u53(w4, w5) < drift_prob;           phase extent (width, T)
+ *        narrowband  i0 channel = randint(0, F) of w0, i1 drifting (w4, w5), i2 power index of w1, v0 its power;
+ *                    phase extent (1, T)
+ *        burst       i0 row = randint(0, T) of w0, i2 power index of w1, v0 its power; phase extent (F, 1), fixed
+ *        linear      i0 start_t = randint(0, T/2) of w0, i1 start_f = randint(0, F/2) of w1, i2 drifting (w4, w5),
+ *                    v0 slope = uniform(-2, 2) of (w16, w17);                 phase extent (1, T/2)
+ *        quadratic   i0 start_t = randint(0, T/4) of w0, i1 start_f = randint(0, F/4) of w1, i2 direction =
+ *                    sign(w2), drifting;                                      phase extent (1, T/4)
+ *      Phase parameters of _draw_event_phase (simulator.py:69-90), extent (w, nt), bl = baseline_frac:
+ *        r0 = (uniform(0.5, 1 + bl max_time_fringes) of (w8, w9) / nt) sign(w10)
+ *        s0 = (uniform(0.5, 1 + bl max_freq_fringes) of (w12, w13) / w) sign(w11)
+ *        phi0 = uniform(0, 2 pi) of (w14, w15)
+ *        sdot = drifting ? ((uniform(0.5, 1 + bl max_freq_fringes) of (w6, w7) / w) sign(w3) - s0) / nt : 0
+ *
+ *      Per-pixel and per-point draws (position, event, stream):
+ *        (t F + f, 0, 8)  -> normals RR (re, im), RL (re, im);  (t F + f, 1, 8) -> LR, LL
+ *        (t F + f, b, 9)  -> broadband chunk b: modulation uniform(0.5, 2) of (w0, w1), power of w2
+ *        (t, k, 10)       -> narrowband k: modulation of (w0, w1);   (f, k, 11) -> burst k: modulation of (w0, w1)
+ *        (i, k, 12)       -> linear sweep k, point i: power of w0;    (t, k, 13) -> quadratic sweep k, point t
+ *        (t F + f, 0, 14) -> cross-hand factors uniform(0, 1): RL of (w0, w1), LR of (w2, w3)
+ *
+ *      Per pixel, one gather in the reference's order: RR = noise + broadband (chunk order) + narrowband + bursts
+ *      + linear sweeps + quadratic sweeps; LL the same without the quadratic sweeps; RL/LR = noise + factor RR.
+ *      Mask: broadband / narrowband / burst pixels with |field| > detect_floor, sweep points with
+ *      amp > detect_floor.  gibbs_ringing convolves broadband rows with gibbs_kernel (np.convolve 'same', zero
+ *      outside the chunk) and spreads narrowband / burst lines to +-8 channels / rows (kernel cut at the edges);
+ *      it never changes the mask.  No atomics: every run is bitwise reproducible.
+ *
+ *      Sizes: T >= 4, F >= 52 (the reference's randint bounds; clean: T, F >= 1), T F < 2^32, first_sample + n_samples <= 2^32,
+ *      1 <= n_power <= 1024.  Outputs (device memory, written in full):
+ *        out_layout RFI_SIM_C128 / RFI_SIM_C64: (n, 4, T, F) complex in the order RR, RL, LR, LL;
+ *        RFI_SIM_NCHW: (n, 8, T, F) float32, channels RR.re RR.im RL.re RL.im LR.re LR.im LL.re LL.im;
+ *        RFI_SIM_NHWC: (n, T, F, 8) float32, the same channels last.  Float outputs are the fp64 values rounded
+ *        once.  mask_dev: (n, T, F) uint8.  events_dev: n RFI_SIM_SLOTS(T, F) records (may be NULL when clean);
+ *      baseline_frac_dev: n doubles, each sample's baseline_frac (may be NULL).
+ *      clean != 0 is generate_clean_data: noise only, an empty mask, no event table; any T, F >= 1.  power_range_dev and
+ *      events_dev are device pointers.  Stream-ordered on the context's stream; no synchronisation. ---- */
+typedef struct rfi_sim_event {
+    int32_t i0, i1, i2, i3;
+    double s0, sdot, r0, phi0;   /* phase parameters (header: unused) */
+    double v0, v1;               /* v0: power (narrowband, burst), slope (linear), baseline_frac (header) */
+} rfi_sim_event;
+typedef struct rfi_sim_params {
+    int32_t time_bins, freq_bins;
+    int32_t n_power;             /* entries of power_range_dev */
+    int32_t gibbs_ringing;
+    int32_t clean;
+    int32_t fixed_baseline;      /* 1: every sample uses baseline_frac; 0: drawn per sample */
+    double baseline_frac, detect_floor, drift_prob, max_time_fringes, max_freq_fringes;
+    double gibbs_kernel[17];     /* _make_gibbs_kernel(8, 2.0), used when gibbs_ringing */
+} rfi_sim_params;
+enum { RFI_SIM_C128 = 0, RFI_SIM_C64 = 1, RFI_SIM_NCHW = 2, RFI_SIM_NHWC = 3 };
+#define RFI_SIM_SLOTS(T, F) (14 + (int)((double)(F) * 0.05) + (int)((double)(T) * 0.1))
+int rfi_simulate_rfi(rfi_ctx* ctx, uint64_t seed, uint64_t first_sample, int n_samples, const rfi_sim_params* params,
+                     const double* power_range_dev, int out_layout, void* out_dev, uint8_t* mask_dev,
+                     rfi_sim_event* events_dev, double* baseline_frac_dev);
+
 /* ---- kernel-level entry points (device pointers only).  Used by the parity tests to
  *      check each HIP kernel against the oracle in isolation.  impl: 0 auto, 1 direct VALU,
  *      2 MFMA implicit GEMM in native float32 (v_mfma_f32_32x32x2_f32), 3 MFMA implicit GEMM with bfloat16

@@ -27,6 +27,16 @@ class FlagStats(C.Structure):
                 ("median", C.c_double), ("mad", C.c_double), ("max", C.c_double)]
 
 
+SIM_C128, SIM_C64, SIM_NCHW, SIM_NHWC = 0, 1, 2, 3
+
+
+class SimParams(C.Structure):
+    _fields_ = [("time_bins", C.c_int32), ("freq_bins", C.c_int32), ("n_power", C.c_int32), ("gibbs_ringing", C.c_int32),
+                ("clean", C.c_int32), ("fixed_baseline", C.c_int32), ("baseline_frac", C.c_double),
+                ("detect_floor", C.c_double), ("drift_prob", C.c_double), ("max_time_fringes", C.c_double),
+                ("max_freq_fringes", C.c_double), ("gibbs_kernel", C.c_double * 17)]
+
+
 class Hyper(C.Structure):
     _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
                 ("weight_decay", C.c_double), ("max_grad_norm", C.c_double)]
@@ -160,6 +170,7 @@ _PROTOS = {
     "rfi_preprocess_gather": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _i]),
     "rfi_confusion_counts": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i64, _pi64, _pi64, _pi64]),
     "rfi_threshold_logits": (_i, [_vp, _vp, _i64, _f, _vp]),
+    "rfi_simulate_rfi": (_i, [_vp, C.c_uint64, C.c_uint64, _i, C.POINTER(SimParams), _vp, _i, _vp, _vp, _vp, _vp]),
     "rfi_flag_statistics": (_i, [_vp, _vp, _i, _i, _i64, _vp, _i, _i, _i, C.POINTER(FlagStats), C.POINTER(FlagStats)]),
     "rfi_op_conv3x3": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     "rfi_op_conv1x1": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),

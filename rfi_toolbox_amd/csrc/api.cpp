@@ -1534,6 +1534,28 @@ int rfi_flag_statistics(rfi_ctx* ctx, const void* data, int data_mem, int dtype,
         if (want & RFI_FS_CLEAN) *clean_out = res[1];
     });
 }
+int rfi_simulate_rfi(rfi_ctx* ctx, uint64_t seed, uint64_t first_sample, int n_samples, const rfi_sim_params* params,
+                     const double* power_range_dev, int out_layout, void* out_dev, uint8_t* mask_dev,
+                     rfi_sim_event* events_dev, double* baseline_frac_dev) {
+    return guarded([&] {
+        RFI_REQUIRE(ctx && params, "simulate_rfi: null argument");
+        const rfi_sim_params& p = *params;
+        const int64_t T = p.time_bins, F = p.freq_bins;
+        RFI_REQUIRE(p.clean ? (T >= 1 && F >= 1) : (T >= 4 && F >= 52),
+                    "simulate_rfi: needs time_bins >= 4 and freq_bins >= 52 (the reference's randint bounds)");
+        RFI_REQUIRE(T * F < ((int64_t)1 << 32), "simulate_rfi: time_bins * freq_bins must stay below 2^32");
+        RFI_REQUIRE(n_samples >= 0, "simulate_rfi: negative sample count");
+        RFI_REQUIRE(first_sample + (uint64_t)n_samples <= ((uint64_t)1 << 32), "simulate_rfi: sample counter past 2^32");
+        RFI_REQUIRE(n_samples * T * ((F + 255) / 256) < ((int64_t)1 << 31), "simulate_rfi: batch too large for one launch");
+        RFI_REQUIRE(p.n_power >= 1 && p.n_power <= 1024, "simulate_rfi: power_range must have 1..1024 entries");
+        RFI_REQUIRE(out_layout >= RFI_SIM_C128 && out_layout <= RFI_SIM_NHWC, "simulate_rfi: bad out_layout");
+        RFI_REQUIRE(out_dev && mask_dev && power_range_dev && (p.clean || events_dev), "simulate_rfi: null buffer");
+        if (n_samples == 0) return;
+        ctx->activate();
+        launch_rfi_sim(ctx, seed, (unsigned)first_sample, n_samples, p, power_range_dev, out_layout, out_dev, mask_dev,
+                       events_dev, baseline_frac_dev);
+    });
+}
 int rfi_threshold_logits(rfi_ctx* ctx, const float* logits_dev, int64_t count, float threshold,
                          uint8_t* mask_dev) {
     return guarded([&] {

@@ -324,6 +324,11 @@ void launch_threshold(rfi_ctx* ctx, const float* logits, int64_t count, float th
 size_t flag_stats_ws_bytes();
 void launch_flag_stats(rfi_ctx* ctx, const void* src, int dtype, int64_t n, const uint8_t* flags, int views,
                        bool medians, void* ws, void* mag, rfi_flag_stats* out_dev);
+// RFISimulator waterfalls (rfi_sim.hip): draws the event table into `events` (unless p.clean), then one gather per
+// pixel into `out` (layout RFI_SIM_*) and `mask`; sizes are checked by rfi_simulate_rfi
+void launch_rfi_sim(rfi_ctx* ctx, unsigned long long seed, unsigned first_sample, int n_samples,
+                    const rfi_sim_params& p, const double* power_dev, int layout, void* out, uint8_t* mask,
+                    rfi_sim_event* events, double* baseline_out);
 
 // x[i] *= f  (the emulated gradient exchange of the single-GPU tests, rfi_comm_emulate)
 void launch_scale_inplace(rfi_ctx* ctx, float* x, int64_t n, float f);

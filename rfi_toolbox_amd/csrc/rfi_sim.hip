@@ -1,0 +1,407 @@
+// RFISimulator on device (rfi_toolbox/core/simulator.py:137-237): four-polarisation waterfalls with coherent
+// per-event phase and full-truth masks down to a detectability floor, n samples per call, straight into HBM.
+//
+// Two launches.  rfisim_events_kernel draws every event's parameters (one thread per event slot) from
+// Philox4x32-10 into a fixed-layout table (include/rfi_hip.h: rfi_sim_event and the word -> value mappings).
+// rfisim_pixels_kernel then makes one gather per pixel: a workgroup owns a 256-column segment of one row, reads
+// the sample's event table with scalar loads and adds, in fp64 and in the reference's order, noise + broadband +
+// narrowband + bursts + linear sweeps (+ quadratic sweeps for RR), then RL/LR = noise + factor * RR.  A sweep
+// is found per pixel in O(1): one sweep visits distinct rows, so the row gives the point index.  Every per-pixel
+// and per-point value is keyed by (position, event, stream, global sample), so the result depends neither on
+// the launch geometry nor on how the samples are split into calls.  No atomics: runs are bitwise reproducible.
+//
+// Gibbs ringing: a broadband pixel is a 17-tap convolution of its chunk's row.  Each field value costs a Philox
+// block and an fp64 sincos, so recomputing it per tap would cost 17x; instead the workgroup stages the row
+// segment of each chunk, with an 8-column halo on either side, in LDS (<= 3 chunks x 272 x 16 B) and every lane
+// sums its 17 taps from there.  Narrowband / burst lines are one value per (event, row) or (event, column) and
+// are evaluated by the lanes that need them.
+#include "kernels.hpp"
+
+namespace rfi {
+namespace {
+
+constexpr int kChunk = 256;          // columns per workgroup (= threads)
+constexpr int kHalo = 8;             // Gibbs kernel half-width (n_side of _make_gibbs_kernel)
+constexpr double kTwoPi = 6.283185307179586;     // 2 * np.pi
+
+enum { S_HEADER = 0, S_BROAD = 1, S_NARROW = 2, S_BURST = 3, S_LINEAR = 4, S_QUAD = 5,
+       S_NOISE = 8, S_BROAD_PX = 9, S_NARROW_PT = 10, S_BURST_PT = 11, S_LINEAR_PT = 12, S_QUAD_PT = 13,
+       S_CROSS = 14 };
+
+struct U4 { unsigned x, y, z, w; };
+
+__device__ __forceinline__ U4 philox4x32_10(U4 c, unsigned k0, unsigned k1) {
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c.x;
+        const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c.z;
+        const U4 n{(unsigned)(p1 >> 32) ^ c.y ^ k0, (unsigned)p1, (unsigned)(p0 >> 32) ^ c.w ^ k1, (unsigned)p0};
+        c = n;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return c;
+}
+
+struct SimDev {
+    unsigned k0, k1, first;          // key; global index of sample 0 (first + n <= 2^32)
+    int n, T, F, NN, NB, slots, n_power, clean, fixed_bl, layout;
+    double bl, floor, drift_prob, mtf, mff;
+    double gk[17];
+    const double* power;
+    rfi_sim_event* ev;
+    double* bl_out;
+    void* out;
+    uint8_t* mask;
+};
+
+__device__ __forceinline__ U4 draw(const SimDev& d, unsigned pos, unsigned event, unsigned stream, unsigned sample) {
+    return philox4x32_10(U4{pos, event, stream, sample}, d.k0, d.k1);
+}
+// NumPy's random_sample from two words, and uniform(lo, hi) = lo + (hi - lo) * u
+__device__ __forceinline__ double u53(unsigned a, unsigned b) {
+    return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) / 9007199254740992.0;
+}
+__device__ __forceinline__ double uniform(double lo, double hi, unsigned a, unsigned b) { return lo + (hi - lo) * u53(a, b); }
+__device__ __forceinline__ int randint(int lo, int hi, unsigned w) {
+    return lo + (int)(((unsigned long long)w * (unsigned long long)(hi - lo)) >> 32);
+}
+__device__ __forceinline__ double sgn(unsigned w) { return (w >> 31) ? -1.0 : 1.0; }
+__device__ __forceinline__ int power_index(unsigned w, int n) { return (int)(((unsigned long long)w * (unsigned)n) >> 32); }
+__device__ __forceinline__ void normal2(unsigned a, unsigned b, double& n0, double& n1) {
+    const double r = sqrt(-2.0 * log(((double)a + 1.0) * (1.0 / 4294967296.0)));
+    double s, c;
+    sincos(kTwoPi * ((double)b * (1.0 / 4294967296.0)), &s, &c);
+    n0 = r * c;
+    n1 = r * s;
+}
+
+// _draw_event_phase (simulator.py:69-90) for an event of extent (width channels, ntimes rows)
+__device__ void draw_phase(const SimDev& d, const unsigned* w, int width, int ntimes, bool drifting, double bl,
+                           rfi_sim_event& e) {
+    const double wd = (double)(width > 1 ? width : 1), nt = (double)(ntimes > 1 ? ntimes : 1);
+    const double n_ft = uniform(0.5, 1.0 + bl * d.mtf, w[8], w[9]);
+    e.r0 = (n_ft / nt) * sgn(w[10]);
+    const double n_ff = uniform(0.5, 1.0 + bl * d.mff, w[12], w[13]);
+    e.s0 = (n_ff / wd) * sgn(w[11]);
+    e.phi0 = uniform(0.0, kTwoPi, w[14], w[15]);
+    if (drifting) {
+        const double s_end = (uniform(0.5, 1.0 + bl * d.mff, w[6], w[7]) / wd) * sgn(w[3]);
+        e.sdot = (s_end - e.s0) / nt;
+    } else {
+        e.sdot = 0.0;
+    }
+}
+
+__global__ void rfisim_events_kernel(SimDev d) {
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (int64_t)d.n * d.slots) return;
+    const int s = (int)(gid / d.slots), slot = (int)(gid % d.slots);
+    const unsigned sample = d.first + (unsigned)s;
+    const int T = d.T, F = d.F;
+    const U4 h = draw(d, 0, 0, S_HEADER, sample);
+    const double bl = d.fixed_bl ? d.bl : u53(h.x, h.y);
+    rfi_sim_event e{};
+    int cat, k;
+    if (slot == 0) { cat = S_HEADER; k = 0; }
+    else if (slot < 4) { cat = S_BROAD; k = slot - 1; }
+    else if (slot < 4 + d.NN) { cat = S_NARROW; k = slot - 4; }
+    else if (slot < 4 + d.NN + d.NB) { cat = S_BURST; k = slot - 4 - d.NN; }
+    else if (slot < 9 + d.NN + d.NB) { cat = S_LINEAR; k = slot - 4 - d.NN - d.NB; }
+    else { cat = S_QUAD; k = slot - 9 - d.NN - d.NB; }
+    unsigned w[20];
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+        const U4 r = draw(d, (unsigned)j, (unsigned)k, (unsigned)cat, sample);
+        w[4 * j] = r.x; w[4 * j + 1] = r.y; w[4 * j + 2] = r.z; w[4 * j + 3] = r.w;
+    }
+    switch (cat) {
+    case S_HEADER:
+        e.i0 = 2 + randint(0, 2, h.z);
+        e.v0 = bl;
+        if (d.bl_out) d.bl_out[s] = bl;
+        break;
+    case S_BROAD: {                  // simulator.py:163-168
+        const int max_width = F - 1;
+        e.i0 = randint(0, max(1, max_width - 100), w[0]);
+        e.i1 = randint(50, min(150, max_width - e.i0), w[1]);
+        e.i2 = u53(w[4], w[5]) < d.drift_prob;
+        draw_phase(d, w, e.i1, T, e.i2 != 0, bl, e);
+        break;
+    }
+    case S_NARROW:                   // :179-183
+        e.i0 = randint(0, F, w[0]);
+        e.i2 = power_index(w[1], d.n_power);
+        e.v0 = d.power[e.i2];
+        e.i1 = u53(w[4], w[5]) < d.drift_prob;
+        draw_phase(d, w, 1, T, e.i1 != 0, bl, e);
+        break;
+    case S_BURST:                    // :193-196
+        e.i0 = randint(0, T, w[0]);
+        e.i2 = power_index(w[1], d.n_power);
+        e.v0 = d.power[e.i2];
+        draw_phase(d, w, F, 1, false, bl, e);
+        break;
+    case S_LINEAR:                   // :201-206
+        e.i0 = randint(0, T / 2, w[0]);
+        e.i1 = randint(0, F / 2, w[1]);
+        e.v0 = uniform(-2.0, 2.0, w[16], w[17]);
+        e.i2 = u53(w[4], w[5]) < d.drift_prob;
+        draw_phase(d, w, 1, T / 2, e.i2 != 0, bl, e);
+        break;
+    default:                         // S_QUAD, :218-222
+        e.i0 = randint(0, T / 4, w[0]);
+        e.i1 = randint(0, F / 4, w[1]);
+        e.i2 = (int)sgn(w[2]);
+        draw_phase(d, w, 1, T / 4, true, bl, e);
+        break;
+    }
+    d.ev[gid] = e;
+}
+
+// _phase_grid (:92-95) at (t, n)
+__device__ __forceinline__ double phase(const rfi_sim_event& e, int t, int n) {
+    return kTwoPi * ((e.s0 + e.sdot * (double)t) * (double)n + e.r0 * (double)t) + e.phi0;
+}
+// amp * exp(1j * phase): NumPy's complex product with a real amplitude is (amp cos, amp sin)
+__device__ __forceinline__ double2 field(double amp, double ph) {
+    double s, c;
+    sincos(ph, &s, &c);
+    return make_double2(amp * c, amp * s);
+}
+__device__ __forceinline__ double2 broadband_field(const SimDev& d, const rfi_sim_event& e, int b, int t, int f,
+                                                   unsigned sample) {
+    const U4 r = draw(d, (unsigned)t * (unsigned)d.F + (unsigned)f, (unsigned)b, S_BROAD_PX, sample);
+    const double mod = uniform(0.5, 2.0, r.x, r.y);
+    return field(mod * d.power[power_index(r.z, d.n_power)], phase(e, t, f));
+}
+__device__ __forceinline__ void add(double2& acc, double2 v) {
+    acc.x = acc.x + v.x;
+    acc.y = acc.y + v.y;
+}
+
+template <bool RING>
+__global__ __launch_bounds__(kChunk) void rfisim_pixels_kernel(SimDev d) {
+    const int nchunk = (d.F + kChunk - 1) / kChunk;
+    const int64_t bid = blockIdx.x;
+    const int chunk = (int)(bid % nchunk);
+    const int64_t row = bid / nchunk;
+    const int t = (int)(row % d.T), s = (int)(row / d.T);
+    const int T = d.T, F = d.F, f0 = chunk * kChunk, f = f0 + (int)threadIdx.x;
+    const bool active = f < F;
+    const unsigned sample = d.first + (unsigned)s;
+    const unsigned pix = (unsigned)t * (unsigned)F + (unsigned)(active ? f : 0);
+
+    double2 rr, rl, lr, ll;
+    {
+        const U4 a = draw(d, pix, 0, S_NOISE, sample), b = draw(d, pix, 1, S_NOISE, sample);
+        normal2(a.x, a.y, rr.x, rr.y);
+        normal2(a.z, a.w, rl.x, rl.y);
+        normal2(b.x, b.y, lr.x, lr.y);
+        normal2(b.z, b.w, ll.x, ll.y);
+    }
+    bool m = false;
+    if (!d.clean) {
+        const rfi_sim_event* __restrict__ E = d.ev + (int64_t)s * d.slots;
+        const int nbb = E[0].i0;
+        const double floor = d.floor;
+        // broadband chunks, in event order (:162-176)
+        if (RING) {
+            __shared__ double2 seg[3][kChunk + 2 * kHalo];
+            for (int b = 0; b < nbb; ++b) {
+                const rfi_sim_event e = E[1 + b];
+                const int lo = max(e.i0, f0 - kHalo), hi = min(e.i0 + e.i1, f0 + kChunk + kHalo);
+                for (int c = lo + (int)threadIdx.x; c < hi; c += kChunk)
+                    seg[b][c - (f0 - kHalo)] = broadband_field(d, e, b, t, c, sample);
+            }
+            __syncthreads();
+            for (int b = 0; b < nbb; ++b) {
+                const int c0 = E[1 + b].i0, c1 = c0 + E[1 + b].i1;
+                if (active && f >= c0 && f < c1) {
+                    const double2 own = seg[b][f - f0 + kHalo];
+                    m = m || hypot(own.x, own.y) > floor;
+                    // np.convolve(row, k, 'same'): out[f] = sum_c row[c] k[f - c + 8], zeros outside the chunk
+                    double2 acc = make_double2(0.0, 0.0);
+                    const int lo = max(c0, f - kHalo), hi = min(c1 - 1, f + kHalo);
+                    for (int c = lo; c <= hi; ++c) {
+                        const double2 v = seg[b][c - f0 + kHalo];
+                        const double k = d.gk[f - c + kHalo];
+                        acc.x = acc.x + v.x * k;
+                        acc.y = acc.y + v.y * k;
+                    }
+                    add(rr, acc);
+                    add(ll, acc);
+                }
+            }
+        } else {
+            for (int b = 0; b < nbb; ++b) {
+                const rfi_sim_event e = E[1 + b];
+                if (active && f >= e.i0 && f < e.i0 + e.i1) {
+                    const double2 v = broadband_field(d, e, b, t, f, sample);
+                    m = m || hypot(v.x, v.y) > floor;
+                    add(rr, v);
+                    add(ll, v);
+                }
+            }
+        }
+        // narrowband channels (:178-188): the line value at row t, deposited on its channel or spread +-8 channels
+        // (the channels / rows are fetched 64 at a time, one per lane, and broadcast with readlane: a dependent
+        // scalar load per event would put one memory latency per event on every wave)
+        const int lane = (int)(threadIdx.x & 63);
+        for (int base = 0; base < d.NN; base += 64) {
+            const int mine = base + lane < d.NN ? E[4 + base + lane].i0 : 0;
+            const int cnt = min(64, d.NN - base);
+            for (int j = 0; j < cnt; ++j) {
+                const int k = base + j;
+                const int df = f - __builtin_amdgcn_readlane(mine, j);
+                if (active && (RING ? (df >= -kHalo && df <= kHalo) : df == 0)) {
+                    const rfi_sim_event e = E[4 + k];
+                    const U4 r = draw(d, (unsigned)t, (unsigned)k, S_NARROW_PT, sample);
+                    const double2 v = field(uniform(0.5, 2.0, r.x, r.y) * e.v0, phase(e, t, e.i0));
+                    if (df == 0) m = m || hypot(v.x, v.y) > floor;
+                    const double2 c = RING ? make_double2(v.x * d.gk[df + kHalo], v.y * d.gk[df + kHalo]) : v;
+                    add(rr, c);
+                    add(ll, c);
+                }
+            }
+        }
+        // burst rows (:190-199)
+        for (int base = 0; base < d.NB; base += 64) {
+            const int mine = base + lane < d.NB ? E[4 + d.NN + base + lane].i0 : 0;
+            const int cnt = min(64, d.NB - base);
+            for (int j = 0; j < cnt; ++j) {
+                const int k = base + j;
+                const int dt = t - __builtin_amdgcn_readlane(mine, j);
+                if (active && (RING ? (dt >= -kHalo && dt <= kHalo) : dt == 0)) {
+                    const rfi_sim_event e = E[4 + d.NN + k];
+                    const U4 r = draw(d, (unsigned)f, (unsigned)k, S_BURST_PT, sample);
+                    const double2 v = field(uniform(0.5, 2.0, r.x, r.y) * e.v0, phase(e, e.i0, f));
+                    if (dt == 0) m = m || hypot(v.x, v.y) > floor;
+                    const double2 c = RING ? make_double2(d.gk[dt + kHalo] * v.x, d.gk[dt + kHalo] * v.y) : v;
+                    add(rr, c);
+                    add(ll, c);
+                }
+            }
+        }
+        // linear sweeps (:201-214): point i = t - start_t, channel int(start_f + slope i) % F
+        for (int k = 0; k < 5; ++k) {
+            const rfi_sim_event e = E[4 + d.NN + d.NB + k];
+            const int i = (t - e.i0 + T) % T;
+            if (i < T / 2) {
+                const long long q = (long long)((double)e.i1 + e.v0 * (double)i);   // int(): toward zero
+                int fi = (int)(q % F);
+                if (fi < 0) fi += F;                                              // Python's % F
+                if (active && f == fi) {
+                    const double amp = d.power[power_index(draw(d, (unsigned)i, (unsigned)k, S_LINEAR_PT, sample).x,
+                                                           d.n_power)];
+                    const double2 v = field(amp, phase(e, t, fi));
+                    add(rr, v);
+                    add(ll, v);
+                    m = m || amp > floor;
+                }
+            }
+        }
+        // quadratic sweeps, RR only (:216-228): channel (start_f + (direction t^2) // 100) % F, floor division
+        for (int k = 0; k < 5; ++k) {
+            const rfi_sim_event e = E[9 + d.NN + d.NB + k];
+            const int tt = (t - e.i0 + T) % T;
+            if (tt < T / 4) {
+                const long long num = (long long)e.i2 * (long long)tt * (long long)tt;
+                const long long fl = num >= 0 ? num / 100 : -((-num + 99) / 100);
+                int fi = (int)(((long long)e.i1 + fl) % F);
+                if (fi < 0) fi += F;
+                if (active && f == fi) {
+                    const double amp = d.power[power_index(draw(d, (unsigned)tt, (unsigned)k, S_QUAD_PT, sample).x,
+                                                           d.n_power)];
+                    add(rr, field(amp, phase(e, t, fi)));
+                    m = m || amp > floor;
+                }
+            }
+        }
+        // cross hands (:231-235)
+        const U4 x = draw(d, pix, 0, S_CROSS, sample);
+        const double frl = u53(x.x, x.y), flr = u53(x.z, x.w);
+        rl.x = rl.x + frl * rr.x;
+        rl.y = rl.y + frl * rr.y;
+        lr.x = lr.x + flr * rr.x;
+        lr.y = lr.y + flr * rr.y;
+    }
+    if (!active) return;
+    const int64_t plane = (int64_t)T * F, px = (int64_t)t * F + f;
+    d.mask[(int64_t)s * plane + px] = m ? 1 : 0;
+    switch (d.layout) {
+    case RFI_SIM_C128: {
+        double2* o = reinterpret_cast<double2*>(d.out) + (int64_t)s * 4 * plane + px;
+        o[0] = rr; o[plane] = rl; o[2 * plane] = lr; o[3 * plane] = ll;
+        break;
+    }
+    case RFI_SIM_C64: {
+        float2* o = reinterpret_cast<float2*>(d.out) + (int64_t)s * 4 * plane + px;
+        o[0] = make_float2((float)rr.x, (float)rr.y);
+        o[plane] = make_float2((float)rl.x, (float)rl.y);
+        o[2 * plane] = make_float2((float)lr.x, (float)lr.y);
+        o[3 * plane] = make_float2((float)ll.x, (float)ll.y);
+        break;
+    }
+    case RFI_SIM_NCHW: {
+        float* o = reinterpret_cast<float*>(d.out) + (int64_t)s * 8 * plane + px;
+        o[0] = (float)rr.x; o[plane] = (float)rr.y; o[2 * plane] = (float)rl.x; o[3 * plane] = (float)rl.y;
+        o[4 * plane] = (float)lr.x; o[5 * plane] = (float)lr.y; o[6 * plane] = (float)ll.x; o[7 * plane] = (float)ll.y;
+        break;
+    }
+    default: {                       // RFI_SIM_NHWC: two 16-byte stores per pixel
+        float4* o = reinterpret_cast<float4*>(d.out) + ((int64_t)s * plane + px) * 2;
+        o[0] = make_float4((float)rr.x, (float)rr.y, (float)rl.x, (float)rl.y);
+        o[1] = make_float4((float)lr.x, (float)lr.y, (float)ll.x, (float)ll.y);
+        break;
+    }
+    }
+}
+
+}  // namespace
+
+void launch_rfi_sim(rfi_ctx* ctx, unsigned long long seed, unsigned first_sample, int n_samples,
+                    const rfi_sim_params& p, const double* power_dev, int layout, void* out, uint8_t* mask,
+                    rfi_sim_event* events, double* baseline_out) {
+    SimDev d{};
+    d.k0 = (unsigned)seed;
+    d.k1 = (unsigned)(seed >> 32);
+    d.first = first_sample;
+    d.n = n_samples;
+    d.T = p.time_bins;
+    d.F = p.freq_bins;
+    d.NN = (int)((double)p.freq_bins * 0.05);
+    d.NB = (int)((double)p.time_bins * 0.1);
+    d.slots = RFI_SIM_SLOTS(p.time_bins, p.freq_bins);
+    d.n_power = p.n_power;
+    d.clean = p.clean ? 1 : 0;
+    d.fixed_bl = p.fixed_baseline ? 1 : 0;
+    d.layout = layout;
+    d.bl = p.baseline_frac;
+    d.floor = p.detect_floor;
+    d.drift_prob = p.drift_prob;
+    d.mtf = p.max_time_fringes;
+    d.mff = p.max_freq_fringes;
+    for (int i = 0; i < 17; ++i) d.gk[i] = p.gibbs_kernel[i];
+    d.power = power_dev;
+    d.ev = events;
+    d.bl_out = baseline_out;
+    d.out = out;
+    d.mask = mask;
+    const int64_t px = (int64_t)n_samples * d.T * d.F;
+    const int esz = layout == RFI_SIM_C128 ? 64 : 32;
+    ProfScope ps(ctx, FAM_PREPROCESS, 0, (double)px * (esz + 1));
+    if (!d.clean) {
+        const int64_t nt = (int64_t)n_samples * d.slots;
+        hipLaunchKernelGGL(rfisim_events_kernel, dim3((unsigned)cdiv(nt, 256)), dim3(256), 0, ctx->stream, d);
+        check_launch("rfisim_events");
+    }
+    const int64_t blocks = (int64_t)n_samples * d.T * cdiv(d.F, kChunk);
+    if (p.gibbs_ringing && !d.clean)
+        hipLaunchKernelGGL(rfisim_pixels_kernel<true>, dim3((unsigned)blocks), dim3(kChunk), 0, ctx->stream, d);
+    else
+        hipLaunchKernelGGL(rfisim_pixels_kernel<false>, dim3((unsigned)blocks), dim3(kChunk), 0, ctx->stream, d);
+    check_launch("rfisim_pixels");
+}
+
+}  // namespace rfi
