@@ -70,6 +70,35 @@ static const char* kFamilyNames[FAM_COUNT] = {"conv_igemm_mfma", "wgrad_igemm_mf
                                               "batchnorm", "elementwise", "slab_reduce", "optimizer",
                                               "preprocess", "metrics", "comm"};
 
+namespace {
+
+// build the model `make` returns; if that throws, the model is deleted without the destructor's frees (everything it
+// allocated is tracked by ctx)
+template <class Make>
+int create_model(const char* fn, rfi_ctx* ctx, rfi_model** out, Make make) {
+    return guarded([&] {
+        RFI_REQUIRE(ctx && out, std::string(fn) + ": null argument");
+        rfi_model* m = make();
+        m->ctx = ctx;
+        try {
+            m->build();
+        } catch (...) {
+            m->ctx = nullptr;
+            delete m;
+            throw;
+        }
+        *out = m;
+    });
+}
+
+// the plain U-Net (models/unet.py), or null
+UNetModel* plain_unet(rfi_model* m) {
+    auto* u = dynamic_cast<UNetModel*>(m);
+    return u && !u->resnet_encoder ? u : nullptr;
+}
+
+}  // namespace
+
 extern "C" {
 
 int rfi_abi_version(void) { return RFI_HIP_ABI_VERSION; }
@@ -264,152 +293,42 @@ int rfi_profile_get(rfi_ctx* ctx, int family, int64_t* launches, double* total_m
 // ------------------------------------------------------------------------------------ model
 int rfi_unet_create(rfi_ctx* ctx, int in_channels, int out_channels, int init_features, int depth,
                     rfi_model** out) {
-    return guarded([&] {
-        RFI_REQUIRE(ctx && out, "rfi_unet_create: null argument");
-        auto* m = new rfi_model();
-        m->ctx = ctx;
-        m->in_ch = in_channels;
-        m->out_ch = out_channels;
-        m->feat = init_features;
-        m->depth = depth;
-        try {
-            m->build();
-        } catch (...) {
-            m->ctx = nullptr;   // nothing to free through the dtor path that is not tracked by ctx
-            delete m;
-            throw;
-        }
-        *out = m;
-    });
+    return create_model("rfi_unet_create", ctx, out,
+                        [&] { return new UNetModel(in_channels, out_channels, init_features, depth, false); });
 }
 int rfi_cnn3_create(rfi_ctx* ctx, int in_channels, int out_channels, int width, rfi_model** out) {
-    return guarded([&] {
-        RFI_REQUIRE(ctx && out, "rfi_cnn3_create: null argument");
-        auto* m = new rfi_model();
-        m->ctx = ctx;
-        m->arch = 1;
-        m->in_ch = in_channels;
-        m->out_ch = out_channels;
-        m->feat = width;
-        m->depth = 0;
-        try {
-            m->build();
-        } catch (...) {
-            m->ctx = nullptr;
-            delete m;
-            throw;
-        }
-        *out = m;
-    });
+    return create_model("rfi_cnn3_create", ctx, out, [&] { return new Cnn3Model(in_channels, out_channels, width); });
 }
 int rfi_unet_resnet_create(rfi_ctx* ctx, int in_channels, int out_channels, int init_features, rfi_model** out) {
-    return guarded([&] {
-        RFI_REQUIRE(ctx && out, "rfi_unet_resnet_create: null argument");
-        auto* m = new rfi_model();
-        m->ctx = ctx;
-        m->arch = 2;
-        m->in_ch = in_channels;
-        m->out_ch = out_channels;
-        m->feat = init_features;
-        m->depth = 4;
-        try {
-            m->build();
-        } catch (...) {
-            m->ctx = nullptr;
-            delete m;
-            throw;
-        }
-        *out = m;
-    });
+    return create_model("rfi_unet_resnet_create", ctx, out,
+                        [&] { return new UNetModel(in_channels, out_channels, init_features, 4, true); });
 }
 int rfi_mask_head_create(rfi_ctx* ctx, int in_channels, int conv_layers, int out_channels, rfi_model** out) {
-    return guarded([&] {
-        RFI_REQUIRE(ctx && out, "rfi_mask_head_create: null argument");
-        auto* m = new rfi_model();
-        m->ctx = ctx;
-        m->arch = 3;
-        m->in_ch = in_channels;
-        m->out_ch = out_channels;
-        m->feat = in_channels;
-        m->depth = conv_layers;
-        try {
-            m->build();
-        } catch (...) {
-            m->ctx = nullptr;
-            delete m;
-            throw;
-        }
-        *out = m;
-    });
+    return create_model("rfi_mask_head_create", ctx, out,
+                        [&] { return new ConvHeadModel(in_channels, conv_layers, out_channels, true); });
 }
 int rfi_box_head_create(rfi_ctx* ctx, int in_features, int hidden, int fc_layers, int num_outputs, rfi_model** out) {
-    return guarded([&] {
-        RFI_REQUIRE(ctx && out, "rfi_box_head_create: null argument");
-        auto* m = new rfi_model();
-        m->ctx = ctx;
-        m->arch = 6;
-        m->in_ch = in_features;
-        m->feat = hidden;
-        m->depth = fc_layers;
-        m->out_ch = num_outputs;
-        try {
-            m->build();
-        } catch (...) {
-            m->ctx = nullptr;
-            delete m;
-            throw;
-        }
-        *out = m;
-    });
+    return create_model("rfi_box_head_create", ctx, out,
+                        [&] { return new BoxHeadModel(in_features, hidden, fc_layers, num_outputs); });
 }
 int rfi_resnet50_fpn_create(rfi_ctx* ctx, int in_channels, int base_width, int fpn_channels, rfi_model** out) {
-    return guarded([&] {
-        RFI_REQUIRE(ctx && out, "rfi_resnet50_fpn_create: null argument");
-        auto* m = new rfi_model();
-        m->ctx = ctx;
-        m->arch = 5;
-        m->in_ch = in_channels;
-        m->feat = base_width;
-        m->out_ch = fpn_channels;
-        try {
-            m->build();
-        } catch (...) {
-            m->ctx = nullptr;
-            delete m;
-            throw;
-        }
-        *out = m;
-    });
+    return create_model("rfi_resnet50_fpn_create", ctx, out,
+                        [&] { return new BackboneModel(in_channels, base_width, fpn_channels); });
 }
 int rfi_rpn_head_create(rfi_ctx* ctx, int in_channels, int conv_layers, int anchors_per_pixel, rfi_model** out) {
-    return guarded([&] {
-        RFI_REQUIRE(ctx && out, "rfi_rpn_head_create: null argument");
+    return create_model("rfi_rpn_head_create", ctx, out, [&] {
         RFI_REQUIRE(anchors_per_pixel > 0 && anchors_per_pixel % 4 == 0, "RPNHead: anchors per pixel must be a positive multiple of 4");
-        auto* m = new rfi_model();
-        m->ctx = ctx;
-        m->arch = 4;
-        m->in_ch = in_channels;
-        m->out_ch = 5 * anchors_per_pixel;
-        m->feat = in_channels;
-        m->depth = conv_layers;
-        try {
-            m->build();
-        } catch (...) {
-            m->ctx = nullptr;
-            delete m;
-            throw;
-        }
-        *out = m;
+        return new ConvHeadModel(in_channels, conv_layers, 5 * anchors_per_pixel, false);
     });
 }
 int rfi_model_input_grad(rfi_model* m, float* dx, int dx_mem) {
     return guarded([&] {
-        RFI_REQUIRE(m->arch == 3 || m->arch == 4 || m->arch == 6, "input_grad: only the mask head computes the gradient w.r.t. its input");
+        RFI_REQUIRE(m->gx >= 0, "input_grad: only the mask head computes the gradient w.r.t. its input");
         RFI_REQUIRE(m->pN > 0 && dx, "input_grad: no backward pass has run");
         m->ctx->activate();
         const size_t cnt = (size_t)m->pN * m->pH * m->pW * m->in_ch;
-        if (dx_mem == RFI_DEVICE) launch_copy_d2d(m->ctx, dx, m->buf(m->mkGx), cnt * sizeof(float));
-        else RFI_CHECK_HIP(hipMemcpyAsync(dx, m->buf(m->mkGx), cnt * sizeof(float), hipMemcpyDeviceToHost, m->ctx->stream));
+        if (dx_mem == RFI_DEVICE) launch_copy_d2d(m->ctx, dx, m->buf(m->gx), cnt * sizeof(float));
+        else RFI_CHECK_HIP(hipMemcpyAsync(dx, m->buf(m->gx), cnt * sizeof(float), hipMemcpyDeviceToHost, m->ctx->stream));
         if (dx_mem != RFI_DEVICE || getenv("RFI_SYNC_ALWAYS")) RFI_CHECK_HIP(hipStreamSynchronize(m->ctx->stream));   // (sync_if_host below)
     });
 }
@@ -581,7 +500,7 @@ int rfi_model_load_entry(rfi_model* m, const char* name, const void* host, size_
             ConvBN& c = m->convs[e.layer];
             float* dst = e.kind == 3 ? c.running_mean() : (e.kind == 4 ? c.running_var() : (e.kind == 8 ? c.mean() : c.invstd()));
             upload(m, dst, src, (size_t)c.cout);
-            m->frozen_dirty = true;
+            if (auto* b = dynamic_cast<BackboneModel*>(m)) b->frozen_dirty = true;
             return;
         }
         std::vector<float> tmp;
@@ -662,9 +581,10 @@ int rfi_model_set_training(rfi_model* m, int training) {
 }
 int rfi_model_set_activation(rfi_model* m, float negative_slope) {
     return guarded([&] {
-        RFI_REQUIRE(m->arch == 0, "set_activation: U-Net models only");
+        UNetModel* u = plain_unet(m);
+        RFI_REQUIRE(u, "set_activation: U-Net models only");
         RFI_REQUIRE(negative_slope >= 0.0f && negative_slope < 1.0f, "set_activation: negative_slope must be in [0, 1)");
-        m->act_slope = negative_slope;
+        u->act_slope = negative_slope;
     });
 }
 int rfi_model_set_compute_dtype(rfi_model* m, int dtype) {
@@ -673,11 +593,7 @@ int rfi_model_set_compute_dtype(rfi_model* m, int dtype) {
                     "set_compute_dtype: 0 native float32 MFMA, 1 bfloat16 (bf16 activations in HBM, plane kernels), "
                     "2 float32 by 3 x bfloat16 splitting in registers (default), 3 the same arithmetic on pre-split "
                     "plane tensors, 4 bfloat16 operands rounded in registers (float32 storage)");
-        m->compute_bf16 = dtype == 1 || dtype == 4;
-        m->compute_x3 = dtype == 2 || dtype == 3;
-        if (m->arch == 0) m->set_planes(dtype == 1 ? 1 : (dtype == 3 ? 3 : 0));
-        // the ResNet-encoder U-Net has the bfloat16 flow only, for widths in whole 16-channel chunks (else: dtype 4's kernels)
-        if (m->arch == 2) m->set_planes(dtype == 1 && m->feat % 16 == 0 ? 1 : 0);
+        m->set_compute_dtype(dtype);
     });
 }
 int rfi_model_set_loss(rfi_model* m, int kind, float alpha, float gamma) {
@@ -691,7 +607,7 @@ int rfi_model_set_loss(rfi_model* m, int kind, float alpha, float gamma) {
 }
 int rfi_model_set_head_sigmoid(rfi_model* m, int enabled) {
     return guarded([&] {
-        RFI_REQUIRE(m->arch == 0, "set_head_sigmoid: U-Net models only");
+        RFI_REQUIRE(plain_unet(m), "set_head_sigmoid: U-Net models only");
         m->head_sigmoid = enabled != 0;
     });
 }
@@ -852,7 +768,7 @@ int rfi_train_step_async(rfi_model* m, const float* x_dev, const uint8_t* labels
 int rfi_model_backward_dlogits(rfi_model* m, const float* x, int x_mem, const float* dlogits, int dlogits_mem, int n, int h,
                                int w) {
     return guarded([&] {
-        RFI_REQUIRE(m->arch == 3 || m->arch == 4 || m->arch == 6, "backward_dlogits: mask / RPN / box heads only");
+        RFI_REQUIRE(m->gx >= 0, "backward_dlogits: mask / RPN / box heads only");
         RFI_REQUIRE(m->pN == n && m->pH == h && m->pW == w, "backward_dlogits: run the forward pass on this input first");
         m->ctx->activate();
         const float* xd = stage_input(m, x, x_mem, n, h, w, false);
@@ -867,7 +783,8 @@ int rfi_model_backward_dlogits(rfi_model* m, const float* x, int x_mem, const fl
 }
 int rfi_backbone_forward(rfi_model* m, const float* x, int x_mem, int n, int h, int w, float* const feats[5], int feats_mem) {
     return guarded([&] {
-        RFI_REQUIRE(m->arch == 5 && feats, "backbone_forward: ResNet-50-FPN models only");
+        auto* b = dynamic_cast<BackboneModel*>(m);
+        RFI_REQUIRE(b && feats, "backbone_forward: ResNet-50-FPN models only");
         m->ctx->activate();
         m->prepare(n, h, w);
         const float* xd = stage_input(m, x, x_mem, n, h, w, false);
@@ -876,7 +793,7 @@ int rfi_backbone_forward(rfi_model* m, const float* x, int x_mem, int n, int h, 
             if (!feats[i]) continue;
             const int lvl = i + 2;
             const size_t cnt = (size_t)n * (h >> lvl) * (w >> lvl) * m->out_ch;
-            copy_on_stream(m->ctx, feats[i], m->buf(i < 4 ? m->fP[i] : m->fP6), cnt * sizeof(float),
+            copy_on_stream(m->ctx, feats[i], m->buf(i < 4 ? b->fP[i] : b->fP6), cnt * sizeof(float),
                            feats_mem == RFI_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost);
         }
         sync_if_host(m, x_mem, feats_mem);
@@ -884,14 +801,15 @@ int rfi_backbone_forward(rfi_model* m, const float* x, int x_mem, int n, int h, 
 }
 int rfi_backbone_backward(rfi_model* m, const float* x, int x_mem, int n, int h, int w, const float* const dfeats[5], int dfeats_mem) {
     return guarded([&] {
-        RFI_REQUIRE(m->arch == 5 && dfeats, "backbone_backward: ResNet-50-FPN models only");
+        auto* b = dynamic_cast<BackboneModel*>(m);
+        RFI_REQUIRE(b && dfeats, "backbone_backward: ResNet-50-FPN models only");
         RFI_REQUIRE(m->pN == n && m->pH == h && m->pW == w, "backbone_backward: run the forward pass on this input first");
         m->ctx->activate();
         const float* xd = stage_input(m, x, x_mem, n, h, w, false);
         for (int i = 0; i < 5; ++i) {
             const int lvl = i + 2;
             const size_t cnt = (size_t)n * (h >> lvl) * (w >> lvl) * m->out_ch;
-            float* dst = m->buf(i < 4 ? m->fdP[i] : m->fdP6);
+            float* dst = m->buf(i < 4 ? b->fdP[i] : b->fdP6);
             if (dfeats[i])
                 copy_on_stream(m->ctx, dst, dfeats[i], cnt * sizeof(float),
                                dfeats_mem == RFI_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice);
@@ -988,54 +906,15 @@ int rfi_model_debug_tensor(rfi_model* m, const char* name, float* host, size_t h
         }
         const float* src = nullptr;
         size_t n = 0;
-        const int D = m->depth;
-        RFI_REQUIRE(m->arch == 0 || base == "logits" || base == "dlogits" || base == "chan" ||
-                        (m->arch == 2 && base != "encY1" && base != "encY2" && base != "pool" && base != "dpool"),
-                    "debug_tensor: this model exposes only logits / dlogits / chan (and the decoder tensors of the ResNet-encoder U-Net)");
-        RFI_REQUIRE(!(m->y16_flow && m->planesP == 1 && (base == "encY1" || base == "encY2" || base == "decY1" || base == "bottY1" ||
-                                                        (base == "decY2" && idx == 1))),
-                    "debug_tensor: this conv output is stored as bfloat16 in the bfloat16 compute mode");
-        RFI_REQUIRE(!(m->g16_flow && m->planesP == 1 && (base == "gB" || base == "dpool" || base == "gBottB" || base == "gA")),
-                    "debug_tensor: this gradient tensor is stored as bfloat16 in the bfloat16 compute mode");
-        RFI_REQUIRE(!(m->convt_planes && m->planesP == 1 && (base == "decY2" || base == "bottY2" || base == "gBottA")),
-                    "debug_tensor: with the transposed convs on the plane kernels this tensor is stored as bfloat16");
-        auto level = [&](const std::vector<int>& v, size_t chmul) {
-            RFI_REQUIRE(idx >= 1 && idx <= D, "debug_tensor: level out of range");
-            const size_t M = (size_t)m->pN * (m->pH >> (idx - 1)) * (m->pW >> (idx - 1));
-            src = m->buf(v[idx]);
-            n = M * ((size_t)m->feat << (idx - 1)) * chmul;
-        };
-        const size_t Mb = (size_t)m->pN * (m->pH >> D) * (m->pW >> D), Cb = (size_t)m->feat << D;
         const size_t M1 = (size_t)m->pN * m->pH * m->pW * m->out_scale * m->out_scale;     // pixels of the OUTPUT map
-        if (base == "encY1") level(m->encY1, 1);
-        else if (base == "encY2") level(m->encY2, 1);
-        else if (base == "decY1") level(m->decY1, 1);
-        else if (base == "decY2") level(m->decY2, 1);
-        else if (base == "gA") level(!m->planesP && m->arch == 0 ? m->gAe : m->gA, 1);     // (as left by the encoder phase)
-        else if (base == "gB") level(!m->planesP && m->arch == 0 ? m->gBe : m->gB, 1);
-        else if (base == "concat") level(m->concat, 2);
-        else if (base == "dconcat") {
-            level(m->dconcat, 2);
-            if (m->convt_planes && m->planesP == 1 && host) {      // stored as bfloat16: its values as float32 (tools/race_probe.py watches it)
-                const PlaneBuf& g = m->pl[m->g16cat[idx]];
-                launch_planes_to_f32(m->ctx, g.p, g.pstride, (int64_t)(n / ((size_t)2 * (m->feat << (idx - 1)))), 2 * (m->feat << (idx - 1)), 1,
-                                     m->buf(m->dconcat[idx]), 2 * (m->feat << (idx - 1)));
-            }
-        }
-        else if (base == "pool") { level(m->pool, 1); n /= 4; }
-        else if (base == "dpool") { level(m->dpool, 1); n /= 4; }
-        else if (base == "bottY1") { src = m->buf(m->bottY1); n = Mb * Cb; }
-        else if (base == "bottY2") { src = m->buf(m->bottY2); n = Mb * Cb; }
-        else if (base == "gBottA") { src = m->buf(m->gBottA); n = Mb * Cb; }
-        else if (base == "gBottB") { src = m->buf(m->gBottB); n = Mb * Cb; }
-        else if (base == "logits") { src = m->buf(m->logits); n = M1 * m->out_ch; }
+        if (base == "logits") { src = m->buf(m->logits); n = M1 * m->out_ch; }
         else if (base == "dlogits") { src = m->buf(m->dlogits); n = M1 * m->out_ch; }
         else if (base == "chan") {
             RFI_REQUIRE(idx >= 0 && idx < (int)m->convs.size(), "debug_tensor: conv index out of range");
             src = m->convs[idx].chan;
             n = (size_t)8 * m->convs[idx].cout;
         } else {
-            throw Error("debug_tensor: unknown tensor " + s);
+            m->debug_tensor(s, base, idx, host != nullptr, src, n);     // (the U-Net's tensors)
         }
         if (n_floats) *n_floats = (int64_t)n;
         if (host) {
@@ -1047,52 +926,10 @@ int rfi_model_debug_tensor(rfi_model* m, const char* name, float* host, size_t h
 
 int rfi_model_algorithmic_flops(rfi_model* m, int n, int h, int w, double* fwd, double* step) {
     return guarded([&] {
-        // 2*M*K*N over every conv / convT / head, each layer evaluated once
-        double f = 0, stem = 0;
-        const int D = m->depth;
-        if (m->arch == 6) {
-            for (auto& c : m->convs) f += 2.0 * n * c.cin * c.cout;
-            f += 2.0 * n * (double)m->feat * m->out_ch;
-            if (fwd) *fwd = f;
-            if (step) *step = 3.0 * f;
-            return;
-        }
-        if (m->arch == 5) {             // every conv once at its output resolution (the stem's 7x7 has stride 2)
-            for (auto& c : m->convs) f += 2.0 * n * (double)(h >> c.level) * (w >> c.level) * c.R * c.R * c.cin * c.cout;
-            if (fwd) *fwd = f;
-            if (step) *step = 3.0 * f - 2.0 * n * (double)(h >> 1) * (w >> 1) * 49.0 * m->convs[0].cin * m->convs[0].cout;
-            return;
-        }
-        if (m->arch == 3 || m->arch == 4) {   // mask / RPN head: L 3x3 convs, (the transposed conv,) the 1x1 head
-            const double M = (double)n * h * w, C = m->in_ch, s2 = (double)m->out_scale * m->out_scale;
-            f = m->depth * 2.0 * M * 9.0 * C * C + (m->arch == 3 ? 2.0 * M * 4.0 * C * C : 0.0) + 2.0 * s2 * M * C * m->out_ch;
-            if (fwd) *fwd = f;
-            if (step) *step = 3.0 * f;  // the input gradient is computed too (it feeds the RoIAlign adjoint)
-            return;
-        }
-        if (m->arch == 1) {             // 3-layer CNN: two 3x3 convs at full resolution + the 1x1 head
-            const double M = (double)n * h * w;
-            stem = 2.0 * M * 9.0 * m->convs[0].cin * m->convs[0].cout;
-            f = stem + 2.0 * M * 9.0 * m->convs[1].cin * m->convs[1].cout + 2.0 * M * (double)m->feat * m->out_ch;
-            if (fwd) *fwd = f;
-            if (step) *step = 3.0 * f - stem;
-            return;
-        }
-        for (size_t ci = 0; ci < m->convs.size(); ++ci) {
-            const int lvl = m->convs[ci].level, R = m->convs[ci].R;       // M = OUTPUT pixels (stride-2 convs included)
-            const double M = (double)n * (h >> (lvl - 1)) * (w >> (lvl - 1));
-            const double fl = 2.0 * M * R * R * m->convs[ci].cin * m->convs[ci].cout;
-            f += fl;
-            if (ci == 0) stem = fl;
-        }
-        for (int k = 0; k < D; ++k) {
-            const int l = D - k;
-            const double M = (double)n * (h >> l) * (w >> l);
-            f += 2.0 * M * 4.0 * m->ups[k].cin * m->ups[k].cout;
-        }
-        f += 2.0 * n * h * w * (double)m->feat * m->out_ch;
+        double f = 0, st = 0;
+        m->algorithmic_flops(n, h, w, f, st);
         if (fwd) *fwd = f;
-        if (step) *step = 3.0 * f - stem;     // fwd + dgrad + wgrad, no dgrad for the first layer
+        if (step) *step = st;
     });
 }
 

@@ -45,14 +45,9 @@ rfi_model::~rfi_model() {
     if (!ctx) return;
     ctx->activate();
     for (auto& b : bufs) b.free();
-    for (auto& b : pl) b.free();
-    if (wb_pool) ctx->release(wb_pool);
-    if (wb_descs) ctx->release(wb_descs);
     if (ws_pool) ctx->release(ws_pool);
-    if (dbias_pool) ctx->release(dbias_pool);
-    if (dbias_descs) ctx->release(dbias_descs);
     if (ws_descs) ctx->release(ws_descs);
-    for (float* p : {params, grads, adam_m, adam_v, chan_pool, wd_pool, w3_pool, rs_wpool, rs_cls_pool, grad_acc})   // (rs_wpool: arch 2 and 5)
+    for (float* p : {params, grads, adam_m, adam_v, chan_pool, wd_pool, w3_pool, grad_acc})
         if (p) ctx->release(p);
     if (relayout_descs) ctx->release(relayout_descs);
     if (x3_descs) ctx->release(x3_descs);
@@ -62,15 +57,17 @@ rfi_model::~rfi_model() {
     if (lazy_ev) (void)hipEventDestroy(lazy_ev);
 }
 
+UNetModel::~UNetModel() {
+    if (!ctx) return;
+    ctx->activate();
+    for (auto& b : pl) b.free();
+    for (void* p : {(void*)wb_pool, wb_descs, (void*)dbias_pool, dbias_descs, (void*)rs_wpool, (void*)rs_cls_pool})
+        if (p) ctx->release(p);
+}
+
 // ------------------------------------------------------------------------------------ build
-void rfi_model::build() {
-    if (arch != 0 && !(arch == 2 && planesP == 1 && feat % 16 == 0)) planesP = 0;     // the plane data flow: the plain U-Net; the
-                                                                                      // ResNet-encoder U-Net's bfloat16 flow
-    if (arch == 1) return build_cnn3();
-    if (arch == 3 || arch == 4) return build_mask();
-    if (arch == 5) return build_backbone();
-    if (arch == 6) return build_mlp();
-    if (arch == 2) return build_resnet();
+void UNetModel::build() {
+    if (resnet_encoder) return build_resnet();
     RFI_REQUIRE(in_ch > 0 && out_ch > 0 && feat > 0, "UNet: channel counts must be positive");
     RFI_REQUIRE(depth >= 1 && depth <= 6, "UNet: depth must be in [1,6]");
     const int D = depth;
@@ -176,20 +173,7 @@ void rfi_model::build() {
     }
 
     // ---- device state
-    ctx->activate();
-    const size_t bytes = n_flat * sizeof(float);
-    params = static_cast<float*>(ctx->alloc(bytes));
-    grads = static_cast<float*>(ctx->alloc(bytes));
-    adam_m = static_cast<float*>(ctx->alloc(bytes));
-    adam_v = static_cast<float*>(ctx->alloc(bytes));
-    chan_pool = static_cast<float*>(ctx->alloc(chan_floats * sizeof(float)));
-    wd_pool = static_cast<float*>(ctx->alloc(wd_floats * sizeof(float)));
-    d_sums = static_cast<double*>(ctx->alloc(8 * sizeof(double)));
-    d_scalars = static_cast<float*>(ctx->alloc(8 * sizeof(float)));
-    for (float* p : {params, grads, adam_m, adam_v}) RFI_CHECK_HIP(hipMemsetAsync(p, 0, bytes, ctx->stream));
-    RFI_CHECK_HIP(hipMemsetAsync(chan_pool, 0, chan_floats * sizeof(float), ctx->stream));
-    RFI_CHECK_HIP(hipMemsetAsync(d_sums, 0, 8 * sizeof(double), ctx->stream));
-    RFI_CHECK_HIP(hipMemsetAsync(d_scalars, 0, 8 * sizeof(float), ctx->stream));
+    alloc_state(chan_floats, wd_floats);
     size_t co = 0, wo = 0;
     size_t conv_i = 0;
     // wd_pool sub-allocation must follow the same order as the sizing above
@@ -212,7 +196,7 @@ void rfi_model::build() {
     reset_channel_state();
 }
 
-void rfi_model::set_planes(int P) {
+void UNetModel::set_planes(int P) {
     if (P == planesP) return;
     ctx->activate();
     RFI_CHECK_HIP(hipStreamSynchronize(ctx->main_stream));
@@ -223,6 +207,25 @@ void rfi_model::set_planes(int P) {
     planesP = P;
     wd_dirty = true;
     pN = 0;                                       // (prepare() again: the two flows of the ResNet-encoder model own different tensors)
+}
+
+// device state of a freshly built parameter table: the flat buffers (zeroed), the per-channel state and dgrad-layout pools
+// (the caller sub-allocates them), the loss scalars
+void rfi_model::alloc_state(size_t chan_floats, size_t wd_floats) {
+    ctx->activate();
+    const size_t bytes = n_flat * sizeof(float);
+    params = static_cast<float*>(ctx->alloc(bytes));
+    grads = static_cast<float*>(ctx->alloc(bytes));
+    adam_m = static_cast<float*>(ctx->alloc(bytes));
+    adam_v = static_cast<float*>(ctx->alloc(bytes));
+    chan_pool = static_cast<float*>(ctx->alloc(chan_floats * sizeof(float)));
+    wd_pool = static_cast<float*>(ctx->alloc(wd_floats * sizeof(float)));
+    d_sums = static_cast<double*>(ctx->alloc(8 * sizeof(double)));
+    d_scalars = static_cast<float*>(ctx->alloc(8 * sizeof(float)));
+    for (float* p : {params, grads, adam_m, adam_v}) RFI_CHECK_HIP(hipMemsetAsync(p, 0, bytes, ctx->stream));
+    RFI_CHECK_HIP(hipMemsetAsync(chan_pool, 0, chan_floats * sizeof(float), ctx->stream));
+    RFI_CHECK_HIP(hipMemsetAsync(d_sums, 0, 8 * sizeof(double), ctx->stream));
+    RFI_CHECK_HIP(hipMemsetAsync(d_scalars, 0, 8 * sizeof(float), ctx->stream));
 }
 
 void rfi_model::reset_channel_state() {
@@ -258,10 +261,10 @@ void rfi_model::prepare(int n, int h, int w) {
         ctx->bucket_ev_used = 0;
         pend_lo = pend_hi = 0;
     }
-    if (arch == 1) return prepare_cnn3(n, h, w);
-    if (arch == 3 || arch == 4) return prepare_mask(n, h, w);
-    if (arch == 5) return prepare_backbone(n, h, w);
-    if (arch == 6) return prepare_mlp(n, h, w);
+    prepare_shape(n, h, w);
+}
+
+void UNetModel::prepare_shape(int n, int h, int w) {
     const int div = 1 << depth;
     RFI_REQUIRE(h % div == 0 && w % div == 0,
                 "forward: H and W must be multiples of 2^depth (" + std::to_string(div) +
@@ -285,11 +288,11 @@ void rfi_model::prepare(int n, int h, int w) {
         const size_t M = (size_t)n * (h >> (l - 1)) * (w >> (l - 1));
         const size_t C = (size_t)feat << (l - 1);
         for (int i : {decY1[l], decY2[l], gA[l], gB[l]}) bufs[i].ensure(ctx, M * C);
-        if (!planesP && arch == 0) for (int i : {gAe[l], gBe[l]}) bufs[i].ensure(ctx, M * C);   // (the encoder phase's own gradient tensors)
-        if (arch != 2) for (int i : {encY1[l], encY2[l]}) bufs[i].ensure(ctx, M * C);     // (arch 2: its own tensors, prepare_resnet)
+        if (!planesP && !resnet_encoder) for (int i : {gAe[l], gBe[l]}) bufs[i].ensure(ctx, M * C);   // (the encoder phase's own gradient tensors)
+        if (!resnet_encoder) for (int i : {encY1[l], encY2[l]}) bufs[i].ensure(ctx, M * C);     // (ResNet encoder: its own tensors, prepare_resnet)
         bufs[concat[l]].ensure(ctx, M * 2 * C);
         bufs[dconcat[l]].ensure(ctx, M * 2 * C);
-        if (arch != 2 || l == D) {
+        if (!resnet_encoder || l == D) {
             bufs[pool[l]].ensure(ctx, M / 4 * C);
             bufs[dpool[l]].ensure(ctx, M / 4 * C);
         }
@@ -349,7 +352,7 @@ void rfi_model::prepare(int n, int h, int w) {
     bufs[ws_slab].ensure(ctx, slab_need + 16);
     // per-layer regions for the partial sums of the conv-bias gradients + the table of the batched finisher
     // (the plane flows too: the plain U-Net's and the ResNet-encoder model's, whose encoder convs have no bias)
-    if (arch == 0 || (arch == 2 && planesP)) {
+    if (!resnet_encoder || planesP) {
         if (dbias_pool) { ctx->release(dbias_pool); dbias_pool = nullptr; }
         if (dbias_descs) { ctx->release(dbias_descs); dbias_descs = nullptr; }
         size_t need = 0;
@@ -402,7 +405,7 @@ void rfi_model::prepare(int n, int h, int w) {
         RFI_CHECK_HIP(hipMemcpyAsync(dbias_descs, hd.data(), hd.size() * sizeof(FinishSumDesc), hipMemcpyHostToDevice, ctx->stream));
         RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));     // hd goes out of scope
     }
-    if (arch == 2 && !planesP) prepare_resnet(n, h, w);
+    if (resnet_encoder && !planesP) prepare_resnet(n, h, w);
     pN = n; pH = h; pW = w;
 }
 
@@ -425,7 +428,7 @@ void rfi_model::side_rebuild_wd() {
     struct Back { rfi_ctx* c; ~Back() { c->stream = c->main_stream; } } back{ctx};
     launch_weight_to_dgrad_batched(ctx, static_cast<const RelayoutDesc*>(relayout_descs), relayout_n, params,
                                    wd_pool, relayout_bytes, relayout_tiles);
-    if (planesP) refresh_plane_weights(2);
+    if (planesP) refresh_model_weights(2);
     else refresh_ws_weights(ws_need(), 2);
     RFI_CHECK_HIP(hipEventRecord(wd_ready, ctx->side_stream));
     wd_pending = true;
@@ -451,15 +454,10 @@ void rfi_model::refresh_dgrad_weights() {
                                      hipMemcpyHostToDevice, ctx->stream));
         RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));     // h goes out of scope
     }
-    // Split rebuild (plain U-Net, float32 tensors, overlap on): the forward pass needs the forward-direction copies only, so
-    // the dgrad layout and its B-operand images are rebuilt on the SIDE stream (idle during the forward pass) under the first
-    // convs; backward() waits for them (wait_wd)
-    // (the plane flows: the forward pass reads the forward-direction images only, nothing but the input-gradient kernels reads
-    // the dgrad layouts -- unless pre-split records of them are in use)
-    const bool split_planes = planesP && wb_pool && wb_n_fwd > 0 && !use_w3() && training;
-    const bool split = ctx->overlap && !ctx->profiling && ctx->stream == ctx->main_stream &&
-                       (split_planes || (arch == 0 && !planesP && ws_need() != 0 && ws_pool && ws_P == ws_need() && ws_n_fwd > 0 &&
-                                         (!use_w3() || (x3_descs && !x3_reads_wd && x3_for_ws_P == ws_P))));
+    // Split rebuild (wd_split_ok): the forward pass needs the forward-direction copies only, so the dgrad layout and its
+    // B-operand images are rebuilt on the SIDE stream (idle during the forward pass) under the first convs; backward() waits
+    // for them (wait_wd)
+    const bool split = ctx->overlap && !ctx->profiling && ctx->stream == ctx->main_stream && wd_split_ok();
     if (split) {
         wd_side_todo = true;                      // (forward() starts it behind the first conv: side_rebuild_wd)
     } else {
@@ -494,7 +492,7 @@ void rfi_model::refresh_dgrad_weights() {
             x3_for_ws_P = ws_P;
             x3_bytes = 0;
             std::vector<X3Desc> h;
-            x3_skips_ws_layers = ws_P == 3 && arch == 0;
+            const bool skip_ws = x3_skips_ws_layers && ws_P == 3;
             x3_reads_wd = false;
             x3_skipped.clear();
             // a layer is left out only if the wave-specialised kernels cannot decline it at the prepared shape: its maps are at
@@ -502,7 +500,7 @@ void rfi_model::refresh_dgrad_weights() {
             // synchronise the stream inside launch_conv.  (pH == 0: nothing prepared yet, keep everything)
             auto add = [&](const float* src, float* dst, int taps, int cout, int cin, int level = 0) {
                 const bool small_map = pH == 0 || (level > 0 && ((pH >> (level - 1)) < 8 || (pW >> (level - 1)) < 8));
-                if (x3_skips_ws_layers && ws_by_w.count(src) && !small_map) { x3_skipped.insert(src); return; }
+                if (skip_ws && ws_by_w.count(src) && !small_map) { x3_skipped.insert(src); return; }
                 if (src < params || src >= params + n_flat) x3_reads_wd = true;
                 h.push_back(X3Desc{src, dst, (int64_t)taps * cout, cin, (cin + 15) / 16});
                 x3_bytes += (double)taps * cout * cin * 4 + (double)weights_x3_floats(taps, cout, cin) * 4;
@@ -524,9 +522,22 @@ void rfi_model::refresh_dgrad_weights() {
         if (x3_n) launch_weights_to_x3_batched(ctx, static_cast<const X3Desc*>(x3_descs), x3_n, x3_bytes);
         x3_fresh = true;
     }
-    if (arch == 2 && !planesP) refresh_resnet_weights();   // 2x2 forms of the stride-2 filters
-    if (planesP) refresh_plane_weights(split ? 1 : 0);     // B-operand-order filters of the plane kernels
+    refresh_model_weights(split ? 1 : 0);
     wd_dirty = false;
+}
+
+// plain U-Net, float32 tensors: when the wave-specialised copies of both directions are in use (and the pre-split records
+// do not read the dgrad layouts).  The plane flows: the forward pass reads the forward-direction images only, nothing but
+// the input-gradient kernels reads the dgrad layouts -- unless pre-split records of them are in use
+bool UNetModel::wd_split_ok() const {
+    if (planesP) return wb_pool && wb_n_fwd > 0 && !use_w3() && training;
+    return !resnet_encoder && ws_need() != 0 && ws_pool && ws_P == ws_need() && ws_n_fwd > 0 &&
+           (!use_w3() || (x3_descs && !x3_reads_wd && x3_for_ws_P == ws_P));
+}
+
+void UNetModel::refresh_model_weights(int which) {
+    if (planesP) refresh_plane_weights(which);                   // B-operand-order filters of the plane kernels
+    else if (resnet_encoder) refresh_resnet_weights();           // 2x2 forms of the stride-2 filters
 }
 
 // filters of every 3x3 stride-1 layer in MFMA B-operand order with three planes (conv_ws.hip), both directions, rebuilt
@@ -676,14 +687,14 @@ rfi::View rfi_model::network_input(const float* x_dev, int n, int h, int w) {
 void rfi_model::forward(const float* x_dev, int n, int h, int w, bool train_mode) {
     prepare(n, h, w);
     refresh_dgrad_weights();          // derived filter copies (dgrad layout, 3 x bf16 records) follow the parameters
-    if (arch == 1) return forward_cnn3(x_dev, n, h, w);
-    if (arch == 3 || arch == 4) return forward_mask(x_dev, n, h, w);
-    if (arch == 5) return forward_backbone(x_dev, n, h, w);
-    if (arch == 6) return forward_mlp(x_dev, n);
+    forward_pass(x_dev, n, h, w, train_mode);
+}
+
+void UNetModel::forward_pass(const float* x_dev, int n, int h, int w, bool train_mode) {
     if (planesP) return forward_planes(x_dev, n, h, w, train_mode);
     const int D = depth, IB = i_bott;
     View cur = network_input(x_dev, n, h, w);
-    if (arch == 2) cur = forward_resnet_encoder(cur, n, h, w, train_mode);
+    if (resnet_encoder) cur = forward_resnet_encoder(cur, n, h, w, train_mode);
     else for (int l = 1; l <= D; ++l) {
         Shape s{n, h >> (l - 1), w >> (l - 1)};
         ConvBN& c1 = convs[2 * (l - 1)];
@@ -885,7 +896,7 @@ struct SideScope {
 // dbeta into the grad buffer and, if dx != null, the gradient w.r.t. the conv's (activated) input.
 // `have_records` > 0: the BatchNorm-backward sums of this layer already sit in the workspace (the kernel that
 // produced dA folded them into its own pass).
-void backward_conv_bn(rfi_model* m, ConvBN& c, float* dA, const float* Y, View in, InXform in_xf,
+void backward_conv_bn(UNetModel* m, ConvBN& c, float* dA, const float* Y, View in, InXform in_xf,
                       Shape s, float* dx, int have_records,
                       const float* head_dl = nullptr, const float* head_w = nullptr) {
     rfi_ctx* ctx = m->ctx;
@@ -957,33 +968,17 @@ void rfi_model::wgrad_on_side(const rfi::WgradArgs& wa, hipEvent_t after, bool a
 
 void rfi_model::backward(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w) {
     join_pending_side();
-    if (arch == 6) {
-        backward_mlp(x_dev, n);
-        bucket_ready(0, n_flat);
-        return;
-    }
-    if (arch == 5) {
-        backward_backbone(x_dev, n, h, w);
-        bucket_ready(0, n_flat);
-        return;
-    }
-    if (arch == 3 || arch == 4) {
-        backward_mask(x_dev, labels_dev, n, h, w);
-        bucket_ready(0, n_flat);
-        return;
-    }
-    if (arch == 1) {
-        backward_cnn3(x_dev, labels_dev, n, h, w);
-        bucket_ready(0, n_flat);                  // three layers: one bucket
-        return;
-    }
+    backward_pass(x_dev, labels_dev, n, h, w);
+}
+
+void UNetModel::backward_pass(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w) {
     const int D = depth, IB = i_bott;
     const int64_t M1 = (int64_t)n * h * w;
     refresh_dgrad_weights();
     wait_wd();                        // (the input-gradient-direction filter copies were rebuilt on the side stream)
     if (planesP) return backward_planes(x_dev, labels_dev, n, h, w);
-    side_bound = arch == 0 ? 0 : 2;               // (the ResNet-style encoder double-buffers by block parity: bound 2)
-    dbias_deferred = arch == 0 && dbias_pool && !ctx->exchange_active();
+    side_bound = resnet_encoder ? 2 : 0;          // (the ResNet-style encoder double-buffers by block parity: bound 2)
+    dbias_deferred = !resnet_encoder && dbias_pool && !ctx->exchange_active();
     // loss -> dlogits -> head
     if (loss_kind == 1)
         launch_focal_bwd(ctx, buf(head_sigmoid ? probs : logits), labels_dev, M1, focal_alpha, focal_gamma, buf(dlogits));
@@ -1075,7 +1070,7 @@ void rfi_model::backward(const float* x_dev, const uint8_t* labels_dev, int n, i
         backward_conv_bn(this, c1, buf(gBottB), buf(bottY1), View{buf(pool[D]), c1.cin}, InXform{}, s, buf(dpool[D]), 0);
         bucket_ready(c1.w_off, ups[0].w_off);
     }
-    if (arch == 2) {                  // ResNet-style encoder (model_resnet.cpp)
+    if (resnet_encoder) {             // ResNet-style encoder (model_resnet.cpp)
         backward_resnet_encoder(x_dev, n, h, w);
         side_join();
         return;
@@ -1127,4 +1122,80 @@ void rfi_model::apply(const rfi_hyper& hp, float grad_scale) {
     launch_adam(ctx, a);
     wd_dirty = true;
     x3_fresh = false;
+}
+
+// ------------------------------------------------------------------------------------ entry-point hooks
+void rfi_model::set_compute_dtype(int dtype) {
+    compute_bf16 = dtype == 1 || dtype == 4;
+    compute_x3 = dtype == 2 || dtype == 3;
+}
+void UNetModel::set_compute_dtype(int dtype) {
+    rfi_model::set_compute_dtype(dtype);
+    // the ResNet-encoder U-Net has the bfloat16 flow only, for widths in whole 16-channel chunks (else: dtype 4's kernels)
+    if (resnet_encoder) set_planes(dtype == 1 && feat % 16 == 0 ? 1 : 0);
+    else set_planes(dtype == 1 ? 1 : (dtype == 3 ? 3 : 0));
+}
+
+void rfi_model::debug_tensor(const std::string&, const std::string&, int, bool, const float*&, size_t&) {
+    throw Error("debug_tensor: this model exposes only logits / dlogits / chan (and the decoder tensors of the ResNet-encoder U-Net)");
+}
+void UNetModel::debug_tensor(const std::string& name, const std::string& base, int idx, bool to_host, const float*& src, size_t& n) {
+    if (resnet_encoder && (base == "encY1" || base == "encY2" || base == "pool" || base == "dpool"))
+        return rfi_model::debug_tensor(name, base, idx, to_host, src, n);
+    RFI_REQUIRE(!(y16_flow && planesP == 1 && (base == "encY1" || base == "encY2" || base == "decY1" || base == "bottY1" ||
+                                               (base == "decY2" && idx == 1))),
+                "debug_tensor: this conv output is stored as bfloat16 in the bfloat16 compute mode");
+    RFI_REQUIRE(!(g16_flow && planesP == 1 && (base == "gB" || base == "dpool" || base == "gBottB" || base == "gA")),
+                "debug_tensor: this gradient tensor is stored as bfloat16 in the bfloat16 compute mode");
+    RFI_REQUIRE(!(convt_planes && planesP == 1 && (base == "decY2" || base == "bottY2" || base == "gBottA")),
+                "debug_tensor: with the transposed convs on the plane kernels this tensor is stored as bfloat16");
+    const int D = depth;
+    auto level = [&](const std::vector<int>& v, size_t chmul) {
+        RFI_REQUIRE(idx >= 1 && idx <= D, "debug_tensor: level out of range");
+        const size_t M = (size_t)pN * (pH >> (idx - 1)) * (pW >> (idx - 1));
+        src = buf(v[idx]);
+        n = M * ((size_t)feat << (idx - 1)) * chmul;
+    };
+    const size_t Mb = (size_t)pN * (pH >> D) * (pW >> D), Cb = (size_t)feat << D;
+    if (base == "encY1") level(encY1, 1);
+    else if (base == "encY2") level(encY2, 1);
+    else if (base == "decY1") level(decY1, 1);
+    else if (base == "decY2") level(decY2, 1);
+    else if (base == "gA") level(!planesP && !resnet_encoder ? gAe : gA, 1);     // (as left by the encoder phase)
+    else if (base == "gB") level(!planesP && !resnet_encoder ? gBe : gB, 1);
+    else if (base == "concat") level(concat, 2);
+    else if (base == "dconcat") {
+        level(dconcat, 2);
+        if (convt_planes && planesP == 1 && to_host) {      // stored as bfloat16: its values as float32 (tools/race_probe.py watches it)
+            const PlaneBuf& g = pl[g16cat[idx]];
+            launch_planes_to_f32(ctx, g.p, g.pstride, (int64_t)(n / ((size_t)2 * (feat << (idx - 1)))), 2 * (feat << (idx - 1)), 1,
+                                 buf(dconcat[idx]), 2 * (feat << (idx - 1)));
+        }
+    }
+    else if (base == "pool") { level(pool, 1); n /= 4; }
+    else if (base == "dpool") { level(dpool, 1); n /= 4; }
+    else if (base == "bottY1") { src = buf(bottY1); n = Mb * Cb; }
+    else if (base == "bottY2") { src = buf(bottY2); n = Mb * Cb; }
+    else if (base == "gBottA") { src = buf(gBottA); n = Mb * Cb; }
+    else if (base == "gBottB") { src = buf(gBottB); n = Mb * Cb; }
+    else throw Error("debug_tensor: unknown tensor " + name);
+}
+
+void UNetModel::algorithmic_flops(int n, int h, int w, double& fwd, double& step) const {
+    double f = 0, stem = 0;
+    for (size_t ci = 0; ci < convs.size(); ++ci) {
+        const int lvl = convs[ci].level, R = convs[ci].R;       // M = OUTPUT pixels (stride-2 convs included)
+        const double M = (double)n * (h >> (lvl - 1)) * (w >> (lvl - 1));
+        const double fl = 2.0 * M * R * R * convs[ci].cin * convs[ci].cout;
+        f += fl;
+        if (ci == 0) stem = fl;
+    }
+    for (int k = 0; k < depth; ++k) {
+        const int l = depth - k;
+        const double M = (double)n * (h >> l) * (w >> l);
+        f += 2.0 * M * 4.0 * ups[k].cin * ups[k].cout;
+    }
+    f += 2.0 * n * h * w * (double)feat * out_ch;
+    fwd = f;
+    step = 3.0 * f - stem;     // fwd + dgrad + wgrad, no dgrad for the first layer
 }

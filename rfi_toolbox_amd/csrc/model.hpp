@@ -1,4 +1,4 @@
-// U-Net graph of rfi_toolbox/models/unet.py on top of the HIP kernels (host orchestration).
+// The networks of the library (one class per network) on top of the HIP kernels (host orchestration).
 #pragma once
 #include "planes.hpp"
 
@@ -29,7 +29,7 @@ struct ConvBN {
     int cin = 0, cout = 0;
     int cin_p = 0;                      // cin rounded up to a multiple of 4 (library layout; zero padded)
     size_t w_off = 0, b_off = 0, g_off = 0, be_off = 0;   // offsets into the flat param/grad buffers
-    size_t dbias_rec_off = 0;           // this layer's region of rfi_model::dbias_pool (floats)
+    size_t dbias_rec_off = 0;           // this layer's region of UNetModel::dbias_pool (floats)
     int ema_repeats = 1;
     int level = 1;                      // resolution level of the OUTPUT: H >> (level - 1)
     int R = 3, stride = 1;              // ResNet-style encoder: 3x3 stride 1 / 2, or the 1x1 stride-2 projection (R = 1)
@@ -64,7 +64,7 @@ struct UpConv {
     std::string name;                   // "decoder4.up"
     int cin = 0, cout = 0;
     size_t w_off = 0, b_off = 0;        // forward layout [4][cout][cin]
-    size_t dbias_rec_off = 0;           // this layer's region of rfi_model::dbias_pool (floats)
+    size_t dbias_rec_off = 0;           // this layer's region of UNetModel::dbias_pool (floats)
     float* wd = nullptr;                // dgrad layout [4][cin][cout]
     float* w3 = nullptr;                // 3 x bf16 records of both layouts
     float* wd3 = nullptr;
@@ -90,27 +90,27 @@ struct Entry {
 
 }  // namespace rfi
 
+// What every network shares: shape, compute mode, loss, the parameter table with its flat buffers and derived filter
+// copies, the buffers of the prepared shape, the side-stream / bucketed-exchange machinery and the optimiser step.  One
+// derived class per network (below) builds its layers and runs its passes through the virtual hooks.
 struct rfi_model {
     rfi_ctx* ctx = nullptr;
     int in_ch = 0, out_ch = 0, feat = 0, depth = 0;
-    int arch = 0;                     // 0: U-Net (models/unet.py), 1: 3-layer CNN (depth == 0),
-                                      // 2: U-Net with a ResNet-18-style encoder (model_resnet.cpp),
-                                      // 3: Mask R-CNN's per-RoI mask head (model_mask.cpp; depth = conv layers),
-                                      // 4: RPN head (the same stack without the transposed conv),
-                                      // 5: ResNet-50-FPN backbone, frozen BatchNorm (model_backbone.cpp), 6: FC box head (model_mlp.cpp)
-    int i_bott = 0;                   // index of the bottleneck's first conv in `convs` (decoder convs follow it)
+    int out_scale = 1;                // output map / input map in each direction (the mask head's transposed conv: 2)
     bool training = true;
-    float act_slope = 0.0f;           // 0: ReLU; > 0: LeakyReLU(negative_slope) (UNetDifferentActivation)
     bool compute_bf16 = false;        // conv / wgrad MFMAs on bf16-rounded operands (fp32 storage + accumulate)
     bool compute_x3 = true;           // DEFAULT: float32 contractions by 3 x bf16 pieces (float32-level accuracy)
     bool use_w3() const { return compute_x3; }   // who reads the pre-split filter records
+    // plane data flow (model_planes.cpp; set by the U-Net family only): 0 off (round-1 kernels on float32 tensors), 1 bf16
+    // activations (the bfloat16 compute mode), 3 float32 as three bf16 pieces
+    int planesP = 0;
     int loss_kind = 0;                // 0: BCE-with-logits + dice (the reference's, train_model.py:120-128); 1: focal
     float focal_alpha = 0.25f, focal_gamma = 2.0f;
     bool head_sigmoid = false;        // UNetOverfit: forward returns sigmoid(logits); the loss sees that too
     int probs = -1;                   // buffer index of sigmoid(logits) when head_sigmoid
 
-    std::vector<rfi::ConvBN> convs;   // enc1.c1, enc1.c2, ..., encD.c2, bott.c1, bott.c2, decD.c1, decD.c2, ..., dec1.c2
-    std::vector<rfi::UpConv> ups;     // decD.up ... dec1.up   (index 0 = deepest)
+    std::vector<rfi::ConvBN> convs;   // the network's conv-like layers in forward order
+    std::vector<rfi::UpConv> ups;     // its transposed convs
     size_t head_w_off = 0, head_b_off = 0;
     std::vector<rfi::Entry> entries;
     std::unordered_map<std::string, int> entry_index;
@@ -137,10 +137,10 @@ struct rfi_model {
         a.wB1 = ws_P == 1 ? p : nullptr;
         if (a.wB3 && x3_skipped.count(a.w)) a.w3 = nullptr;   // (no pre-split records are kept for this layer)
     }
-    // the plain U-Net keeps no pre-split (3 x bf16) filter records for the layers the wave-specialised kernels cover: at its
-    // shapes they never decline.  The other models (detector backbone on 4 x 4 maps, heads) keep every record up to date, so a
-    // declined shape runs the round-2 kernel on valid records instead of a temporary copy (an allocation + a stream
-    // synchronisation per launch)
+    // set by the plain U-Net: it keeps no pre-split (3 x bf16) filter records for the layers the wave-specialised kernels
+    // cover, since at its shapes they never decline.  The other models (detector backbone on 4 x 4 maps, heads) keep every
+    // record up to date, so a declined shape runs the round-2 kernel on valid records instead of a temporary copy (an
+    // allocation + a stream synchronisation per launch)
     bool x3_skips_ws_layers = false;
     int ws_n_fwd = 0;                 // the first ws_n_fwd descriptors build the forward-direction copies (sources in `params`)
     double ws_bytes_fwd = 0;
@@ -153,15 +153,6 @@ struct rfi_model {
     void side_rebuild_wd();
     bool x3_reads_wd = false;         // the batched 3 x bf16 record rebuild reads dgrad-layout filters
     void wait_wd();
-    // conv-bias gradients of the float32 U-Net path: bn_bwd_apply leaves its per-block partial sums in a per-layer region of
-    // dbias_pool; ONE batched launch at the end of the backward pass finishes them all (single-GPU steps: with a gradient
-    // exchange the buckets need every gradient of a layer when the layer is done)
-    float* dbias_pool = nullptr;
-    void* dbias_descs = nullptr;
-    int dbias_n = 0, dbias_max_c = 0;
-    bool dbias_deferred = false;
-    size_t head_rec_off = 0;            // the head's region of dbias_pool (its dw / db partials)
-    bool head_fin_deferred = false;
     void* x3_descs = nullptr;         // device table of the batched rebuild
     int x3_n = 0;
     int x3_for_ws_P = -1;             // the ws_P the record list was built for (layers with ws copies are left out)
@@ -180,69 +171,101 @@ struct rfi_model {
     int pN = 0, pH = 0, pW = 0;
     std::vector<rfi::DevBuf> bufs;
     // indices into bufs
-    std::vector<int> encY1, encY2, concat, pool, decY1, decY2, gA, gB, dconcat, dpool;
-    std::vector<int> gAe, gBe;        // float32 U-Net path: the encoder phase's gradient tensors (gA / gB are the decoder's)
-    int bottY1 = -1, bottY2 = -1, gBottA = -1, gBottB = -1, logits = -1, dlogits = -1;
+    int logits = -1, dlogits = -1;
     int x_stage = -1, x_stage2 = -1, x_pad = -1, out_stage = -1, ws_red = -1, ws_slab = -1, lab_stage = -1;
+    int gx = -1;                      // the gradient w.r.t. the input (the detector's heads; -1: the model computes none)
+    bool ext_dlogits = false;         // backward from caller-provided dlogits (rfi_model_backward_dlogits)
     double* d_sums = nullptr;         // [0..3] loss sums, [4] grad sumsq
     float* d_scalars = nullptr;       // [0] loss, [1] grad norm
     float last_loss = 0, last_norm = 0;
 
-    void build();
-    void prepare(int n, int h, int w);
-    // 3-layer CNN (model_cnn.cpp)
-    int cY1 = -1, cY2 = -1, cG1 = -1, cG2 = -1;
-    void build_cnn3();
-    void prepare_cnn3(int n, int h, int w);
-    void forward_cnn3(const float* x_dev, int n, int h, int w);
-    void backward_cnn3(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w);
+    rfi_model(int in, int out, int f, int d) : in_ch(in), out_ch(out), feat(f), depth(d) {}
+    virtual ~rfi_model();
+    virtual void build() = 0;                          // layers, parameter table, device state
+    void prepare(int n, int h, int w);                 // (rejoins the streams, then prepare_shape)
+    virtual void prepare_shape(int n, int h, int w) = 0;
+    void forward(const float* x_dev, int n, int h, int w, bool train_mode);    // (prepare + derived filters, then forward_pass)
+    virtual void forward_pass(const float* x_dev, int n, int h, int w, bool train_mode) = 0;
+    void loss_forward(const uint8_t* labels_dev, int n, int h, int w);
+    void backward(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w);    // (then backward_pass)
+    virtual void backward_pass(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w) = 0;
+    void apply(const rfi_hyper& hp, float grad_scale);
+    virtual void algorithmic_flops(int n, int h, int w, double& fwd, double& step) const = 0;   // 2*M*K*N per layer
+    virtual void set_compute_dtype(int dtype);        // rfi_model_set_compute_dtype's codes
+    // rfi_model_debug_tensor for names other than logits / dlogits / chan: `n` floats at `src`
+    virtual void debug_tensor(const std::string& name, const std::string& base, int idx, bool to_host, const float*& src, size_t& n);
+
+    void alloc_state(size_t chan_floats, size_t wd_floats);    // (build(): flat buffers, pools, loss scalars)
     void reset_channel_state();       // running stats 0/1, BN-less layers: scale 1, shift 0
     float* buf(int i) { return bufs[i].p; }
     int new_buf() { bufs.emplace_back(); return (int)bufs.size() - 1; }
+    rfi::View network_input(const float* x_dev, int n, int h, int w);
+    void refresh_dgrad_weights();
+    // U-Net family hooks of refresh_dgrad_weights: may the input-gradient-direction copies be rebuilt on the side stream, and
+    // the model's own derived filters (which: as refresh_ws_weights)
+    virtual bool wd_split_ok() const { return false; }
+    virtual void refresh_model_weights(int which) {}
 
-    // ---- fully connected box head (model_mlp.cpp; arch 6): depth FC + ReLU layers in_ch -> feat -> feat, head feat -> out_ch
-    void build_mlp();
-    void prepare_mlp(int n, int h, int w);
-    void forward_mlp(const float* x_dev, int n);
-    void backward_mlp(const float* x_dev, int n);
+    // backward-pass overlap: wgrad launches go to the context's side stream (see model.cpp)
+    int side_seq = 0;
+    int side_bound = 2;               // main may run this many side launches ahead (0: no bound -- nothing the side work reads is rewritten before side_join)
+    void side_begin();                // side stream waits for everything enqueued on the main stream so far
+    hipEvent_t next_fork_event();     // a fresh event for launch_*(..., done) (null: overlap off)
+    void side_begin_after(hipEvent_t producer_done);   // side stream waits for that producer kernel only (null: as side_begin)
+    void side_end();                  // marks the side launch; bounds the main stream's run-ahead
+    void side_join();                 // main stream waits for all side work
+    // a head model inside a larger step (the detector's box / mask heads): nothing the caller does next needs this model's WEIGHT
+    // gradients, so the pass ends without waiting for them; whoever touches the gradients, the buffers or the weights next
+    // (apply, all-reduce, accumulate, store_grad, the next forward / backward pass) joins first
+    hipEvent_t lazy_ev = nullptr;
+    bool lazy_pending = false;
+    void side_join_lazy();
+    void join_pending_side();
+    void wgrad_on_side(const rfi::WgradArgs& wa, hipEvent_t after, bool after_everything = false);
+    // bucketed gradient exchange (common.hpp): grads[lo, hi) are final once everything enqueued so far on the main
+    // and side streams has run -> all-reduce them on the communication stream; exchange_join: main waits for all
+    bool exchange_in_backward = false;   // set by the full-step entry points only (the split API exchanges explicitly)
+    void bucket_ready(size_t lo, size_t hi);
+    size_t pend_lo = 0, pend_hi = 0;  // finished but not yet exchanged range (small buckets wait for their neighbours)
+    void flush_bucket();
+    void exchange_join();
+};
 
-    // ---- ResNet-50-FPN backbone with frozen BatchNorm (model_backbone.cpp; arch 5): feat = base width (64), out_ch = FPN channels
-    struct BBlock {
-        int stage = 0, stride = 1, cin = 0, width = 0, cout = 0, lvl_in = 2, lvl = 2;      // resolution H >> lvl
-        int c1 = -1, c2 = -1, c3 = -1, cd = -1;                                           // convs indices (cd: projection shortcut)
-        int Y1 = -1, Y2 = -1, Y3 = -1, Yd = -1, A = -1, xs1 = -1, xsA = -1;               // bufs indices
-        float *sc4 = nullptr, *sh4 = nullptr;             // conv1's affine coefficients tiled x 4 (space-to-depth input of a stride-2 conv2)
-    };
-    std::vector<BBlock> bb;
-    int fpn_inner[4] = {-1, -1, -1, -1}, fpn_layer[4] = {-1, -1, -1, -1};
-    int bY0 = -1, bP0 = -1, bArg = -1, bdW = -1, bS = -1, bCol = -1, bWp = -1, fP6 = -1, fdP6 = -1;
-    int stem_kp() const { return (49 * in_ch + 15) / 16 * 16; }      // K of the K-packed 7x7 stem
-    int fL[4] = {-1, -1, -1, -1}, fM[4] = {-1, -1, -1, -1}, fP[4] = {-1, -1, -1, -1}, fdM[4] = {-1, -1, -1, -1}, fdP[4] = {-1, -1, -1, -1};
-    float* bb_stem_w3 = nullptr;      // 3 x bf16 records of the K-packed stem filters (rebuilt with them every step)
-    int bG[6] = {-1, -1, -1, -1, -1, -1};
-    int bT[4][3] = {{-1, -1, -1}, {-1, -1, -1}, {-1, -1, -1}, {-1, -1, -1}};   // dY3 / dY2 / dY1 / dYd of a Bottleneck, by block index mod 3: what the side stream's weight gradients read
-    bool frozen_dirty = true;         // frozen BatchNorm buffers changed: scale / shift must be recomputed
-    void build_backbone();
-    void prepare_backbone(int n, int h, int w);
-    void refresh_backbone();
-    void forward_backbone(const float* x_dev, int n, int h, int w);
-    void backward_backbone(const float* x_dev, int n, int h, int w);
-
-    // ---- per-RoI mask head (model_mask.cpp; arch 3): depth conv3x3+ReLU layers, a transposed conv + ReLU, a 1x1 head.
-    // The output map is out_scale (= 2) times the input map in each direction
-    int out_scale = 1;
-    bool ext_dlogits = false;         // backward from caller-provided dlogits (rfi_model_backward_dlogits)
-    std::vector<int> mkY, mkG;
-    int mkU = -1, mkGU = -1, mkGx = -1, head_wd = -1, head_w3 = -1, head_wd3 = -1;
-    // the 1x1 head as a GEMM on the matrix cores (conv kernels forward / input gradient, weight-gradient kernel) instead of the
-    // per-pixel VALU kernels written for one output channel: where it has enough outputs (the RPN head's 5 A = 20)
-    bool head_on_mfma() const {
-        return (arch == 3 || arch == 4) && out_ch >= 8 && out_ch % 4 == 0 && in_ch % 4 == 0 && (compute_x3 || compute_bf16);
+// U-Net (models/unet.py; model.cpp) and, with resnet_encoder, the U-Net with a ResNet-18-style encoder (SURVEY 8a A10;
+// model_resnet.cpp).  Both share the decoder, the head, the loss and the plane data flow (model_planes.cpp)
+struct UNetModel : rfi_model {
+    const bool resnet_encoder;
+    UNetModel(int in, int out, int f, int d, bool resnet) : rfi_model(in, out, f, d), resnet_encoder(resnet) {
+        x3_skips_ws_layers = !resnet;
     }
-    void build_mask();
-    void prepare_mask(int n, int h, int w);
-    void forward_mask(const float* x_dev, int n, int h, int w);
-    void backward_mask(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w);
+    ~UNetModel() override;
+    void build() override;
+    void prepare_shape(int n, int h, int w) override;
+    void forward_pass(const float* x_dev, int n, int h, int w, bool train_mode) override;
+    void backward_pass(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w) override;
+    void algorithmic_flops(int n, int h, int w, double& fwd, double& step) const override;
+    void set_compute_dtype(int dtype) override;
+    void debug_tensor(const std::string& name, const std::string& base, int idx, bool to_host, const float*& src, size_t& n) override;
+    bool wd_split_ok() const override;
+    void refresh_model_weights(int which) override;
+
+    int i_bott = 0;                   // index of the bottleneck's first conv in `convs` (decoder convs follow it)
+    float act_slope = 0.0f;           // 0: ReLU; > 0: LeakyReLU(negative_slope) (UNetDifferentActivation)
+    // BN-apply + activation of layer c as a load transform for its consumers (slope 0 = ReLU)
+    rfi::InXform bn_xf(const rfi::ConvBN& c) const { return rfi::act_xform(c.scale(), c.shift(), act_slope); }
+    // convs: enc1.c1, enc1.c2, ..., encD.c2, bott.c1, bott.c2, decD.c1, decD.c2, ..., dec1.c2; ups: decD.up ... dec1.up
+    std::vector<int> encY1, encY2, concat, pool, decY1, decY2, gA, gB, dconcat, dpool;
+    std::vector<int> gAe, gBe;        // float32 U-Net path: the encoder phase's gradient tensors (gA / gB are the decoder's)
+    int bottY1 = -1, bottY2 = -1, gBottA = -1, gBottB = -1;
+    // conv-bias gradients of the float32 U-Net path: bn_bwd_apply leaves its per-block partial sums in a per-layer region of
+    // dbias_pool; ONE batched launch at the end of the backward pass finishes them all (single-GPU steps: with a gradient
+    // exchange the buckets need every gradient of a layer when the layer is done)
+    float* dbias_pool = nullptr;
+    void* dbias_descs = nullptr;
+    int dbias_n = 0, dbias_max_c = 0;
+    bool dbias_deferred = false;
+    size_t head_rec_off = 0;            // the head's region of dbias_pool (its dw / db partials)
+    bool head_fin_deferred = false;
 
     // ---- ResNet-18-style encoder (model_resnet.cpp): stem + 4 stages of 2 BasicBlocks
     struct ResBlock {
@@ -262,9 +285,7 @@ struct rfi_model {
     rfi::View forward_resnet_encoder(rfi::View x, int n, int h, int w, bool train_mode);
     void backward_resnet_encoder(const float* x_dev, int n, int h, int w);
 
-    // ---- plane data flow (model_planes.cpp): planesP = 0 off (round-1 kernels on float32 tensors), 1 bf16
-    // activations (the bfloat16 compute mode), 3 float32 as three bf16 pieces
-    int planesP = 0;
+    // ---- plane data flow (model_planes.cpp; planesP in the base)
     std::vector<rfi::PlaneBuf> pl;
     std::vector<int> pA1e, pSkip, pPool, pUp, pA1d, pdYa, pdYb, pdYaE, pdYbE, upf;
     int pXin = -1, pA1b = -1, pdYbottA = -1, pdYbottB = -1;
@@ -280,7 +301,7 @@ struct rfi_model {
     bool g16_flow = false;
     std::vector<int> g16A, g16B, g16pool;       // g16A: dA of the second convs where an elementwise kernel produces it (head, max-pool backward)
     int g16BottB = -1;
-    // ResNet-style encoder on the bf16 flow (arch 2, feat % 16 == 0; model_planes.cpp): indices into pl.  Every block owns its
+    // ResNet-style encoder on the bf16 flow (feat % 16 == 0; model_planes.cpp): indices into pl.  Every block owns its
     // raw conv outputs, its activation planes and its dY planes (the side stream's weight gradients read them until side_join)
     struct ResPlanes {
         int Y1 = -1, Y2 = -1, Yd = -1, A1 = -1, A = -1, dY1 = -1, dY2 = -1, dYd = -1;
@@ -291,7 +312,7 @@ struct rfi_model {
     int rpStemY = -1, rpA0 = -1, rpdY0 = -1, rp_dA1 = -1, rp_dX = -1;
     int rp_dz[2] = {-1, -1};
     float* rs_cls_pool = nullptr;
-    bool resnet_planes() const { return arch == 2 && planesP == 1; }
+    bool resnet_planes() const { return resnet_encoder && planesP == 1; }
     void forward_resnet_planes(rfi::PlaneSeg& cur, int n, int h, int w, bool train_mode);
     void backward_resnet_planes(int n, int h, int w);
     // transposed convs on the plane kernels (bfloat16 flow, init_features % 32 == 0): the DoubleConv outputs they read are bfloat16
@@ -317,37 +338,76 @@ struct rfi_model {
     void refresh_plane_weights(int which = 0);       // 0 everything; 1 forward-direction images; 2 input-gradient direction (+ class tables)
     void forward_planes(const float* x_dev, int n, int h, int w, bool train_mode);
     void backward_planes(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w);
+};
 
-    // backward-pass overlap: wgrad launches go to the context's side stream (see model.cpp)
-    int side_seq = 0;
-    int side_bound = 2;               // main may run this many side launches ahead (0: no bound -- nothing the side work reads is rewritten before side_join)
-    void side_begin();                // side stream waits for everything enqueued on the main stream so far
-    hipEvent_t next_fork_event();     // a fresh event for launch_*(..., done) (null: overlap off)
-    void side_begin_after(hipEvent_t producer_done);   // side stream waits for that producer kernel only (null: as side_begin)
-    void side_end();                  // marks the side launch; bounds the main stream's run-ahead
-    void side_join();                 // main stream waits for all side work
-    // a head model inside a larger step (the detector's box / mask heads): nothing the caller does next needs this model's WEIGHT
-    // gradients, so the pass ends without waiting for them; whoever touches the gradients, the buffers or the weights next
-    // (apply, all-reduce, accumulate, store_grad, the next forward / backward pass) joins first
-    hipEvent_t lazy_ev = nullptr;
-    bool lazy_pending = false;
-    void side_join_lazy();
-    void join_pending_side();
-    void wgrad_on_side(const rfi::WgradArgs& wa, hipEvent_t after, bool after_everything = false);
-    // bucketed gradient exchange (common.hpp): grads[lo, hi) are final once everything enqueued so far on the main
-    // and side streams has run -> all-reduce them on the communication stream; exchange_join: main waits for all
-    bool exchange_in_backward = false;   // set by the full-step entry points only (the split API exchanges explicitly)
-    void bucket_ready(size_t lo, size_t hi);
-    size_t pend_lo = 0, pend_hi = 0;  // finished but not yet exchanged range (small buckets wait for their neighbours)
-    void flush_bucket();
-    void exchange_join();
-    // BN-apply + activation of layer c as a load transform for its consumers (slope 0 = ReLU)
-    rfi::InXform bn_xf(const rfi::ConvBN& c) const { return rfi::act_xform(c.scale(), c.shift(), act_slope); }
-    void refresh_dgrad_weights();
-    rfi::View network_input(const float* x_dev, int n, int h, int w);
-    void forward(const float* x_dev, int n, int h, int w, bool train_mode);
-    void loss_forward(const uint8_t* labels_dev, int n, int h, int w);
-    void backward(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w);
-    void apply(const rfi_hyper& hp, float grad_scale);
-    ~rfi_model();
+// 3-layer CNN (model_cnn.cpp)
+struct Cnn3Model : rfi_model {
+    Cnn3Model(int in, int out, int width) : rfi_model(in, out, width, 0) {}
+    void build() override;
+    void prepare_shape(int n, int h, int w) override;
+    void forward_pass(const float* x_dev, int n, int h, int w, bool train_mode) override;
+    void backward_pass(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w) override;
+    void algorithmic_flops(int n, int h, int w, double& fwd, double& step) const override;
+    int cY1 = -1, cY2 = -1, cG1 = -1, cG2 = -1;
+};
+
+// Mask R-CNN's per-RoI mask head (model_mask.cpp; depth = conv layers): depth conv3x3+ReLU layers, a
+// transposed conv + ReLU, a 1x1 head, the output map twice the input map in each direction.  Without `upsample`: the RPN
+// head (the same stack without the transposed conv)
+struct ConvHeadModel : rfi_model {
+    const bool upsample;
+    ConvHeadModel(int in, int layers, int out, bool up) : rfi_model(in, out, in, layers), upsample(up) { gx = new_buf(); }
+    void build() override;
+    void prepare_shape(int n, int h, int w) override;
+    void forward_pass(const float* x_dev, int n, int h, int w, bool train_mode) override;
+    void backward_pass(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w) override;
+    void algorithmic_flops(int n, int h, int w, double& fwd, double& step) const override;
+    std::vector<int> mkY, mkG;
+    int mkU = -1, mkGU = -1, head_wd = -1, head_w3 = -1, head_wd3 = -1;
+    // the 1x1 head as a GEMM on the matrix cores (conv kernels forward / input gradient, weight-gradient kernel) instead of the
+    // per-pixel VALU kernels written for one output channel: where it has enough outputs (the RPN head's 5 A = 20)
+    bool head_on_mfma() const { return out_ch >= 8 && out_ch % 4 == 0 && in_ch % 4 == 0 && (compute_x3 || compute_bf16); }
+    float* head_in() { return upsample ? buf(mkU) : buf(mkY[depth - 1]); }     // what the 1x1 head reads ...
+    float* head_din() { return upsample ? buf(mkGU) : buf(mkG[depth - 1]); }   // ... and the gradient it sends down
+};
+
+// ResNet-50-FPN backbone with frozen BatchNorm (model_backbone.cpp): feat = base width (64), out_ch = FPN channels
+struct BackboneModel : rfi_model {
+    BackboneModel(int in, int base_width, int fpn_ch) : rfi_model(in, fpn_ch, base_width, 0) {}
+    ~BackboneModel() override;
+    void build() override;
+    void prepare_shape(int n, int h, int w) override;
+    void forward_pass(const float* x_dev, int n, int h, int w, bool train_mode) override;
+    void backward_pass(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w) override;
+    void algorithmic_flops(int n, int h, int w, double& fwd, double& step) const override;
+    struct BBlock {
+        int stage = 0, stride = 1, cin = 0, width = 0, cout = 0, lvl_in = 2, lvl = 2;      // resolution H >> lvl
+        int c1 = -1, c2 = -1, c3 = -1, cd = -1;                                           // convs indices (cd: projection shortcut)
+        int Y1 = -1, Y2 = -1, Y3 = -1, Yd = -1, A = -1, xs1 = -1, xsA = -1;               // bufs indices
+        float *sc4 = nullptr, *sh4 = nullptr;             // conv1's affine coefficients tiled x 4 (space-to-depth input of a stride-2 conv2)
+    };
+    std::vector<BBlock> bb;
+    int fpn_inner[4] = {-1, -1, -1, -1}, fpn_layer[4] = {-1, -1, -1, -1};
+    int bY0 = -1, bP0 = -1, bArg = -1, bdW = -1, bS = -1, bCol = -1, bWp = -1, fP6 = -1, fdP6 = -1;
+    int stem_kp() const { return (49 * in_ch + 15) / 16 * 16; }      // K of the K-packed 7x7 stem
+    int fL[4] = {-1, -1, -1, -1}, fM[4] = {-1, -1, -1, -1}, fP[4] = {-1, -1, -1, -1}, fdM[4] = {-1, -1, -1, -1}, fdP[4] = {-1, -1, -1, -1};
+    float* rs_wpool = nullptr;        // derived filters of the stride-2 convs, the stem's records, identity scale / shift
+    float* rs_ones = nullptr;
+    float* rs_zeros = nullptr;
+    float* bb_stem_w3 = nullptr;      // 3 x bf16 records of the K-packed stem filters (rebuilt with them every step)
+    int bG[6] = {-1, -1, -1, -1, -1, -1};
+    int bT[4][3] = {{-1, -1, -1}, {-1, -1, -1}, {-1, -1, -1}, {-1, -1, -1}};   // dY3 / dY2 / dY1 / dYd of a Bottleneck, by block index mod 3: what the side stream's weight gradients read
+    bool frozen_dirty = true;         // frozen BatchNorm buffers changed: scale / shift must be recomputed
+    void refresh_backbone();
+};
+
+// fully connected box head (model_mlp.cpp): depth FC + ReLU layers in_ch -> feat -> feat, head feat -> out_ch
+struct BoxHeadModel : rfi_model {
+    BoxHeadModel(int in, int hidden, int layers, int out) : rfi_model(in, out, hidden, layers) { gx = new_buf(); }
+    void build() override;
+    void prepare_shape(int n, int h, int w) override;
+    void forward_pass(const float* x_dev, int n, int h, int w, bool train_mode) override;
+    void backward_pass(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w) override;
+    void algorithmic_flops(int n, int h, int w, double& fwd, double& step) const override;
+    std::vector<int> fcY, fcG;        // raw outputs of the FC layers and their gradients
 };

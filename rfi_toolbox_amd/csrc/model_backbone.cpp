@@ -1,4 +1,4 @@
-// ResNet-50-FPN backbone of the Mask R-CNN path (BASELINE.json configs[3]; arch 5).  NOT in the
+// ResNet-50-FPN backbone of the Mask R-CNN path (BASELINE.json configs[3]).  NOT in the
 // reference (no detector there) and torchvision is absent: builder-defined as the published networks (He et al. 2016,
 // ResNet-50 with the stride on the 3x3 conv of a Bottleneck; Lin et al. 2017, FPN) with the layer names and the frozen
 // BatchNorm of the usual detection backbone; oracle/backbone_ref.py holds it as plain torch.nn modules.
@@ -28,7 +28,7 @@ namespace {
 const int kBlocksPerStage[4] = {3, 4, 6, 3};
 }
 
-void rfi_model::build_backbone() {
+void BackboneModel::build() {
     RFI_REQUIRE(in_ch > 0 && feat > 0 && feat % 4 == 0 && out_ch > 0 && out_ch % 4 == 0,
                 "ResNet50FPN: base width and FPN channels must be positive multiples of 4");
     depth = 4;
@@ -106,19 +106,7 @@ void rfi_model::build_backbone() {
         }
     }
 
-    ctx->activate();
-    const size_t bytes = n_flat * sizeof(float);
-    params = static_cast<float*>(ctx->alloc(bytes));
-    grads = static_cast<float*>(ctx->alloc(bytes));
-    adam_m = static_cast<float*>(ctx->alloc(bytes));
-    adam_v = static_cast<float*>(ctx->alloc(bytes));
-    chan_pool = static_cast<float*>(ctx->alloc(chan_floats * sizeof(float)));
-    wd_pool = static_cast<float*>(ctx->alloc(wd_floats * sizeof(float)));
-    d_sums = static_cast<double*>(ctx->alloc(8 * sizeof(double)));
-    d_scalars = static_cast<float*>(ctx->alloc(8 * sizeof(float)));
-    for (float* p : {params, grads, adam_m, adam_v}) RFI_CHECK_HIP(hipMemsetAsync(p, 0, bytes, ctx->stream));
-    RFI_CHECK_HIP(hipMemsetAsync(d_sums, 0, 8 * sizeof(double), ctx->stream));
-    RFI_CHECK_HIP(hipMemsetAsync(d_scalars, 0, 8 * sizeof(float), ctx->stream));
+    alloc_state(chan_floats, wd_floats);
     size_t co = 0, wo = 0;
     for (auto& c : convs) {
         c.chan = chan_pool + co; co += align4((size_t)8 * c.cout);
@@ -169,7 +157,7 @@ void rfi_model::build_backbone() {
     frozen_dirty = true;
 }
 
-void rfi_model::prepare_backbone(int n, int h, int w) {
+void BackboneModel::prepare_shape(int n, int h, int w) {
     RFI_REQUIRE(h % 64 == 0 && w % 64 == 0, "ResNet50FPN: H and W must be multiples of 64");
     if (n == pN && h == pH && w == pW && !bufs.empty()) return;
     ctx->activate();
@@ -249,7 +237,7 @@ void rfi_model::prepare_backbone(int n, int h, int w) {
 }
 
 // frozen BatchNorm coefficients and the derived filter copies the batched relayout does not cover
-void rfi_model::refresh_backbone() {
+void BackboneModel::refresh_backbone() {
     if (frozen_dirty) {
         for (auto& c : convs)
             if (c.has_bn) launch_bn_eval_coeffs(ctx, c.cout, c.mean(), c.invstd(), c.running_mean(), c.running_var(), c.scale(), c.shift());
@@ -337,7 +325,7 @@ void wgrad(rfi_model* m, View x, InXform xf_x, const float* dY, int cy, int cx, 
     launch_wgrad(m->ctx, wa);
 }
 // dA (gradient w.r.t. act(Y * scale + shift), or w.r.t. the affine output when slope = 1) -> dY in place: dA * scale * act'
-void affine_bwd(rfi_model* m, const ConvBN& c, float* dA, const float* Y, int64_t M, float slope) {
+void affine_bwd(BackboneModel* m, const ConvBN& c, float* dA, const float* Y, int64_t M, float slope) {
     launch_bn_bwd_apply(m->ctx, dA, Y, M, c.cout, c.scale(), c.shift(), m->rs_zeros, m->rs_ones, c.scale(), m->rs_zeros, m->rs_zeros,
                         m->buf(m->ws_red), nullptr, slope);
 }
@@ -345,7 +333,7 @@ InXform act_of(const ConvBN& c) { return InXform{c.scale(), c.shift(), 1, 0.0f};
 
 }  // namespace
 
-void rfi_model::forward_backbone(const float* x_dev, int n, int h, int w) {
+void BackboneModel::forward_pass(const float* x_dev, int n, int h, int w, bool) {
     refresh_dgrad_weights();
     refresh_backbone();
     {   // stem: 7x7 / 2 as a GEMM on its K-packed input (K = 49 C padded to a multiple of 16), then max-pool of the activated output
@@ -406,7 +394,7 @@ void rfi_model::forward_backbone(const float* x_dev, int n, int h, int w) {
 }
 
 // dP2..dP6 sit in fdP[0..3] / fdP6 (rfi_backbone_backward copies them there)
-void rfi_model::backward_backbone(const float* x_dev, int n, int h, int w) {
+void BackboneModel::backward_pass(const float* x_dev, const uint8_t*, int n, int h, int w) {
     refresh_dgrad_weights();
     side_bound = 2;                   // (measured 31.8 / 32.2 / 32.9 ms per step of the detector at bound 2 / bound 5 / no side stream)
     const int F = out_ch;
@@ -520,4 +508,19 @@ void rfi_model::backward_backbone(const float* x_dev, int n, int h, int w) {
         }
     }
     side_join();
+    bucket_ready(0, n_flat);
+}
+
+BackboneModel::~BackboneModel() {
+    if (!ctx) return;
+    ctx->activate();
+    if (rs_wpool) ctx->release(rs_wpool);
+}
+
+// every conv once at its output resolution (the stem's 7x7 has stride 2)
+void BackboneModel::algorithmic_flops(int n, int h, int w, double& fwd, double& step) const {
+    double f = 0;
+    for (auto& c : convs) f += 2.0 * n * (double)(h >> c.level) * (w >> c.level) * c.R * c.R * c.cin * c.cout;
+    fwd = f;
+    step = 3.0 * f - 2.0 * n * (double)(h >> 1) * (w >> 1) * 49.0 * convs[0].cin * convs[0].cout;
 }

@@ -14,7 +14,7 @@ using namespace rfi;
 
 static size_t align4(size_t v) { return (v + 3) & ~size_t(3); }
 
-void rfi_model::build_cnn3() {
+void Cnn3Model::build() {
     RFI_REQUIRE(in_ch > 0 && out_ch > 0 && feat > 0, "SimpleCNN: channel counts must be positive");
     RFI_REQUIRE(feat % 4 == 0, "SimpleCNN: width must be a multiple of 4 (16-byte NHWC pixels)");
     convs.clear();
@@ -66,19 +66,7 @@ void rfi_model::build_cnn3() {
         push(e);
     }
 
-    ctx->activate();
-    const size_t bytes = n_flat * sizeof(float);
-    params = static_cast<float*>(ctx->alloc(bytes));
-    grads = static_cast<float*>(ctx->alloc(bytes));
-    adam_m = static_cast<float*>(ctx->alloc(bytes));
-    adam_v = static_cast<float*>(ctx->alloc(bytes));
-    chan_pool = static_cast<float*>(ctx->alloc(chan_floats * sizeof(float)));
-    wd_pool = static_cast<float*>(ctx->alloc(wd_floats * sizeof(float)));
-    d_sums = static_cast<double*>(ctx->alloc(8 * sizeof(double)));
-    d_scalars = static_cast<float*>(ctx->alloc(8 * sizeof(float)));
-    for (float* p : {params, grads, adam_m, adam_v}) RFI_CHECK_HIP(hipMemsetAsync(p, 0, bytes, ctx->stream));
-    RFI_CHECK_HIP(hipMemsetAsync(d_sums, 0, 8 * sizeof(double), ctx->stream));
-    RFI_CHECK_HIP(hipMemsetAsync(d_scalars, 0, 8 * sizeof(float), ctx->stream));
+    alloc_state(chan_floats, wd_floats);
     size_t co = 0, wo = 0;
     for (auto& c : convs) {
         c.chan = chan_pool + co; co += align4((size_t)8 * c.cout);
@@ -90,7 +78,7 @@ void rfi_model::build_cnn3() {
     reset_channel_state();
 }
 
-void rfi_model::prepare_cnn3(int n, int h, int w) {
+void Cnn3Model::prepare_shape(int n, int h, int w) {
     if (n == pN && h == pH && w == pW && !bufs.empty()) return;
     ctx->activate();
     if (bufs.empty()) {
@@ -150,7 +138,7 @@ InXform relu_xf(const ConvBN& c) { return InXform{c.scale(), c.shift(), 1}; }
 
 }  // namespace
 
-void rfi_model::forward_cnn3(const float* x_dev, int n, int h, int w) {
+void Cnn3Model::forward_pass(const float* x_dev, int n, int h, int w, bool) {
     refresh_dgrad_weights();
     ConvBN& c1 = convs[0];
     ConvBN& c2 = convs[1];
@@ -173,7 +161,7 @@ void rfi_model::forward_cnn3(const float* x_dev, int n, int h, int w) {
                     params + head_b_off, out_ch, buf(logits));
 }
 
-void rfi_model::backward_cnn3(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w) {
+void Cnn3Model::backward_pass(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w) {
     ConvBN& c1 = convs[0];
     ConvBN& c2 = convs[1];
     const int64_t M = (int64_t)n * h * w;
@@ -217,4 +205,13 @@ void rfi_model::backward_cnn3(const float* x_dev, const uint8_t* labels_dev, int
     View x = c1.cin_p == in_ch ? View{x_dev, in_ch} : View{buf(x_pad), c1.cin_p};
     conv_backward(c1, buf(cG1), buf(cY1), x, InXform{}, nullptr);
     side_join();
+    bucket_ready(0, n_flat);                  // three layers: one bucket
+}
+
+// two 3x3 convs at full resolution + the 1x1 head
+void Cnn3Model::algorithmic_flops(int n, int h, int w, double& fwd, double& step) const {
+    const double M = (double)n * h * w;
+    const double stem = 2.0 * M * 9.0 * convs[0].cin * convs[0].cout;
+    fwd = stem + 2.0 * M * 9.0 * convs[1].cin * convs[1].cout + 2.0 * M * (double)feat * out_ch;
+    step = 3.0 * fwd - stem;
 }

@@ -12,7 +12,7 @@
 // raw conv outputs are kept; ReLU is applied by the consumers' loads, as in model_cnn.cpp.  rfi_model_input_grad returns
 // the gradient w.r.t. x, which rfi_op_roi_align_backward scatters back into the feature map.
 //
-// arch 4, the RPN head (Ren et al. 2015), is the same stack without the transposed conv: Conv3x3(C -> C) + ReLU, then ONE
+// Without `upsample` it is the RPN head (Ren et al. 2015), is the same stack without the transposed conv: Conv3x3(C -> C) + ReLU, then ONE
 // 1x1 conv with 5 A outputs per pixel = A objectness logits followed by A x 4 box deltas (cls_logits and bbox_pred of the
 // usual implementation stacked; models/rpn_head.py splits them at the state_dict boundary).  Its loss needs per-anchor
 // targets, so it lives outside the model: rfi_op_rpn_loss produces d(loss)/d(head output) and
@@ -25,10 +25,10 @@ using namespace rfi;
 
 static size_t align4(size_t v) { return (v + 3) & ~size_t(3); }
 
-void rfi_model::build_mask() {
+void ConvHeadModel::build() {
     RFI_REQUIRE(in_ch > 0 && in_ch % 4 == 0, "MaskHead: in_channels must be a positive multiple of 4 (16-byte NHWC pixels)");
     RFI_REQUIRE(out_ch > 0 && depth >= 1 && depth <= 8, "MaskHead: out_channels > 0, 1..8 conv layers");
-    const bool up = arch == 3;
+    const bool up = upsample;
     feat = in_ch;
     out_scale = up ? 2 : 1;
     loss_kind = 1;                // sigmoid focal loss with gamma = 0 and no alpha = plain mean BCE-with-logits
@@ -99,19 +99,7 @@ void rfi_model::build_mask() {
         push(e);
     }
 
-    ctx->activate();
-    const size_t bytes = n_flat * sizeof(float);
-    params = static_cast<float*>(ctx->alloc(bytes));
-    grads = static_cast<float*>(ctx->alloc(bytes));
-    adam_m = static_cast<float*>(ctx->alloc(bytes));
-    adam_v = static_cast<float*>(ctx->alloc(bytes));
-    chan_pool = static_cast<float*>(ctx->alloc(chan_floats * sizeof(float)));
-    wd_pool = static_cast<float*>(ctx->alloc(wd_floats * sizeof(float)));
-    d_sums = static_cast<double*>(ctx->alloc(8 * sizeof(double)));
-    d_scalars = static_cast<float*>(ctx->alloc(8 * sizeof(float)));
-    for (float* p : {params, grads, adam_m, adam_v}) RFI_CHECK_HIP(hipMemsetAsync(p, 0, bytes, ctx->stream));
-    RFI_CHECK_HIP(hipMemsetAsync(d_sums, 0, 8 * sizeof(double), ctx->stream));
-    RFI_CHECK_HIP(hipMemsetAsync(d_scalars, 0, 8 * sizeof(float), ctx->stream));
+    alloc_state(chan_floats, wd_floats);
     size_t co = 0, wo = 0;
     for (auto& c : convs) {
         c.chan = chan_pool + co; co += align4((size_t)8 * c.cout);
@@ -124,23 +112,23 @@ void rfi_model::build_mask() {
     reset_channel_state();
 }
 
-void rfi_model::prepare_mask(int n, int h, int w) {
+void ConvHeadModel::prepare_shape(int n, int h, int w) {
     if (n == pN && h == pH && w == pW && !bufs.empty()) return;
     ctx->activate();
     const int L = depth, C = in_ch;
-    if (bufs.empty()) {
+    if (mkY.empty()) {
         mkY.assign(L, -1); mkG.assign(L, -1);
         for (int i = 0; i < L; ++i) { mkY[i] = new_buf(); mkG[i] = new_buf(); }
-        mkU = new_buf(); mkGU = new_buf(); mkGx = new_buf();
+        mkU = new_buf(); mkGU = new_buf();
         logits = new_buf(); dlogits = new_buf(); head_wd = new_buf(); head_w3 = new_buf(); head_wd3 = new_buf();
         x_stage = new_buf(); x_stage2 = new_buf(); x_pad = new_buf(); out_stage = new_buf();
         ws_red = new_buf(); ws_slab = new_buf(); lab_stage = new_buf();
     }
     const size_t M = (size_t)n * h * w, M4 = (size_t)out_scale * out_scale * M;
     for (int i = 0; i < L; ++i) { bufs[mkY[i]].ensure(ctx, M * C); bufs[mkG[i]].ensure(ctx, M * C); }
-    bufs[mkU].ensure(ctx, arch == 3 ? M4 * C : 16);
-    bufs[mkGU].ensure(ctx, arch == 3 ? M4 * C : 16);
-    bufs[mkGx].ensure(ctx, M * C);
+    bufs[mkU].ensure(ctx, upsample ? M4 * C : 16);
+    bufs[mkGU].ensure(ctx, upsample ? M4 * C : 16);
+    bufs[gx].ensure(ctx, M * C);
     bufs[logits].ensure(ctx, M4 * out_ch);
     bufs[dlogits].ensure(ctx, M4 * out_ch);
     bufs[x_stage].ensure(ctx, M * C);
@@ -214,7 +202,7 @@ ConvArgs conv3x3_args(rfi_model* m, View in, InXform xf, const float* w, const f
 
 }  // namespace
 
-void rfi_model::forward_mask(const float* x_dev, int n, int h, int w) {
+void ConvHeadModel::forward_pass(const float* x_dev, int n, int h, int w, bool) {
     refresh_dgrad_weights();
     const int L = depth, C = in_ch;
     const int64_t M4 = (int64_t)out_scale * out_scale * n * h * w;
@@ -224,7 +212,7 @@ void rfi_model::forward_mask(const float* x_dev, int n, int h, int w) {
                                   params + c.w_off, c.w3, params + c.b_off, buf(mkY[i]), C, n, h, w);
         launch_conv(ctx, a);
     }
-    if (arch == 3) {
+    if (upsample) {
         UpConv& u = ups[0];
         ConvArgs a;
         a.x = View{buf(mkY[L - 1]), C};
@@ -247,7 +235,7 @@ void rfi_model::forward_mask(const float* x_dev, int n, int h, int w) {
     const ConvBN& cl = convs[L - 1];                  // (its scale = 1 / shift = 0 vectors serve the ReLU of U as well)
     if (head_on_mfma()) {             // a wide 1x1 head (the RPN's 5 A outputs) is a GEMM: the conv kernels, not the per-pixel VALU kernel
         ConvArgs a;
-        a.x = View{arch == 3 ? buf(mkU) : buf(mkY[L - 1]), C};
+        a.x = View{head_in(), C};
         a.N = n; a.H = out_scale * h; a.W = out_scale * w; a.Hin = a.H; a.Win = a.W;
         a.Cin = C; a.Cout = out_ch;
         a.w = params + head_w_off;
@@ -265,11 +253,11 @@ void rfi_model::forward_mask(const float* x_dev, int n, int h, int w) {
         launch_conv(ctx, a);
         return;
     }
-    launch_head_fwd(ctx, arch == 3 ? buf(mkU) : buf(mkY[L - 1]), M4, C, cl.scale(), cl.shift(), params + head_w_off, params + head_b_off,
+    launch_head_fwd(ctx, head_in(), M4, C, cl.scale(), cl.shift(), params + head_w_off, params + head_b_off,
                     out_ch, buf(logits));
 }
 
-void rfi_model::backward_mask(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w) {
+void ConvHeadModel::backward_pass(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w) {
     const int L = depth, C = in_ch;
     const int64_t M = (int64_t)n * h * w, M4 = (int64_t)out_scale * out_scale * M;
     refresh_dgrad_weights();
@@ -280,8 +268,8 @@ void rfi_model::backward_mask(const float* x_dev, const uint8_t* labels_dev, int
     const ConvBN& cl = convs[L - 1];
     if (head_on_mfma()) {
         // da = dlogits . W (a 1x1 conv with the transposed filter), dW = dlogits^T . act (the 1x1 weight gradient), db = column sums
-        float* const hin = arch == 3 ? buf(mkU) : buf(mkY[L - 1]);
-        float* const da = arch == 3 ? buf(mkGU) : buf(mkG[L - 1]);
+        float* const hin = head_in();
+        float* const da = head_din();
         launch_weight_to_dgrad(ctx, params + head_w_off, 1, out_ch, C, 0, buf(head_wd));
         ConvArgs a;
         a.x = View{buf(dlogits), out_ch};
@@ -317,10 +305,10 @@ void rfi_model::backward_mask(const float* x_dev, const uint8_t* labels_dev, int
         launch_wgrad(ctx, wa);
         side_end();
     } else
-    launch_head_bwd(ctx, arch == 3 ? buf(mkU) : buf(mkY[L - 1]), M4, C, cl.scale(), cl.shift(), params + head_w_off, out_ch, buf(dlogits),
-                    arch == 3 ? buf(mkGU) : buf(mkG[L - 1]), buf(ws_red), grads + head_w_off, grads + head_b_off);
+    launch_head_bwd(ctx, head_in(), M4, C, cl.scale(), cl.shift(), params + head_w_off, out_ch, buf(dlogits), head_din(), buf(ws_red),
+                    grads + head_w_off, grads + head_b_off);
     // transposed conv: dU = dUa * (U > 0); bias, weight and input gradients
-    if (arch == 3) {
+    if (upsample) {
     UpConv& u = ups[0];
     launch_relu_bwd(ctx, buf(mkGU), buf(mkU), M4 * C);
     launch_channel_sum(ctx, View{buf(mkGU), C}, M4, C, buf(ws_red), grads + u.b_off);
@@ -379,8 +367,16 @@ void rfi_model::backward_mask(const float* x_dev, const uint8_t* labels_dev, int
         side_begin();
         launch_wgrad(ctx, wa);
         side_end();
-        ConvArgs a = conv3x3_args(this, View{dA, C}, InXform{}, c.wd, c.wd3, nullptr, i == 0 ? buf(mkGx) : buf(mkG[i - 1]), C, n, h, w);
+        ConvArgs a = conv3x3_args(this, View{dA, C}, InXform{}, c.wd, c.wd3, nullptr, i == 0 ? buf(gx) : buf(mkG[i - 1]), C, n, h, w);
         launch_conv(ctx, a);
     }
     side_join_lazy();                 // (a head inside the detector's step: the caller goes on with the input gradient)
+    bucket_ready(0, n_flat);
+}
+
+// L 3x3 convs, (the transposed conv,) the 1x1 head
+void ConvHeadModel::algorithmic_flops(int n, int h, int w, double& fwd, double& step) const {
+    const double M = (double)n * h * w, C = in_ch, s2 = (double)out_scale * out_scale;
+    fwd = depth * 2.0 * M * 9.0 * C * C + (upsample ? 2.0 * M * 4.0 * C * C : 0.0) + 2.0 * s2 * M * C * out_ch;
+    step = 3.0 * fwd;                 // the input gradient is computed too (it feeds the RoIAlign adjoint)
 }

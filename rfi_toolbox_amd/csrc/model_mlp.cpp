@@ -1,4 +1,4 @@
-// The box head of Faster / Mask R-CNN (BASELINE.json configs[3]; arch 6) as a stack of fully
+// The box head of Faster / Mask R-CNN (BASELINE.json configs[3]) as a stack of fully
 // connected layers on the matrix cores.  NOT in the reference (no detector there) and torchvision is absent:
 // builder-defined as the published head (Girshick 2015 / Lin et al. 2017: two FC layers of 1024 units + ReLU on the
 // flattened 7 x 7 x 256 RoI features, then the class scores and the per-class box deltas; torchvision's TwoMLPHead +
@@ -18,7 +18,7 @@ using namespace rfi;
 
 static size_t align4(size_t v) { return (v + 3) & ~size_t(3); }
 
-void rfi_model::build_mlp() {
+void BoxHeadModel::build() {
     RFI_REQUIRE(in_ch > 0 && in_ch % 4 == 0 && feat > 0 && feat % 4 == 0 && out_ch > 0 && depth >= 1 && depth <= 8,
                 "BoxHead: in_features and hidden width must be positive multiples of 4, 1..8 layers");
     const int L = depth;
@@ -68,19 +68,7 @@ void rfi_model::build_mlp() {
         e.name = "head.bias"; e.ndim = 1; e.dims[0] = out_ch; e.kind = 2; e.which = 4;
         push(e);
     }
-    ctx->activate();
-    const size_t bytes = n_flat * sizeof(float);
-    params = static_cast<float*>(ctx->alloc(bytes));
-    grads = static_cast<float*>(ctx->alloc(bytes));
-    adam_m = static_cast<float*>(ctx->alloc(bytes));
-    adam_v = static_cast<float*>(ctx->alloc(bytes));
-    chan_pool = static_cast<float*>(ctx->alloc(chan_floats * sizeof(float)));
-    wd_pool = static_cast<float*>(ctx->alloc(wd_floats * sizeof(float)));
-    d_sums = static_cast<double*>(ctx->alloc(8 * sizeof(double)));
-    d_scalars = static_cast<float*>(ctx->alloc(8 * sizeof(float)));
-    for (float* p : {params, grads, adam_m, adam_v}) RFI_CHECK_HIP(hipMemsetAsync(p, 0, bytes, ctx->stream));
-    RFI_CHECK_HIP(hipMemsetAsync(d_sums, 0, 8 * sizeof(double), ctx->stream));
-    RFI_CHECK_HIP(hipMemsetAsync(d_scalars, 0, 8 * sizeof(float), ctx->stream));
+    alloc_state(chan_floats, wd_floats);
     size_t co = 0, wo = 0;
     for (auto& c : convs) {
         c.chan = chan_pool + co; co += align4((size_t)8 * c.cout);
@@ -99,22 +87,21 @@ Lay layout_of(int rows) { return rows % 32 == 0 ? Lay{1, rows / 32, 32} : Lay{ro
 InXform relu_of(const ConvBN& c) { return InXform{c.scale(), c.shift(), 1}; }
 }  // namespace
 
-void rfi_model::prepare_mlp(int n, int h, int w) {
+void BoxHeadModel::prepare_shape(int n, int h, int w) {
     RFI_REQUIRE(h == 1 && w == 1, "BoxHead: the input is [R, in_features] (n = R, h = w = 1)");
     if (n == pN && !bufs.empty()) return;
     ctx->activate();
     const int L = depth;
-    if (bufs.empty()) {
-        mkY.assign(L, -1); mkG.assign(L, -1);
-        for (int i = 0; i < L; ++i) { mkY[i] = new_buf(); mkG[i] = new_buf(); }
-        mkGx = new_buf();
+    if (fcY.empty()) {
+        fcY.assign(L, -1); fcG.assign(L, -1);
+        for (int i = 0; i < L; ++i) { fcY[i] = new_buf(); fcG[i] = new_buf(); }
         logits = new_buf(); dlogits = new_buf();
         x_stage = new_buf(); x_stage2 = new_buf(); x_pad = new_buf(); out_stage = new_buf();
         ws_red = new_buf(); ws_slab = new_buf(); lab_stage = new_buf();
     }
     const size_t M = (size_t)n;
-    for (int i = 0; i < L; ++i) { bufs[mkY[i]].ensure(ctx, M * feat); bufs[mkG[i]].ensure(ctx, M * feat); }
-    bufs[mkGx].ensure(ctx, M * in_ch);
+    for (int i = 0; i < L; ++i) { bufs[fcY[i]].ensure(ctx, M * feat); bufs[fcG[i]].ensure(ctx, M * feat); }
+    bufs[gx].ensure(ctx, M * in_ch);
     bufs[logits].ensure(ctx, M * out_ch);
     bufs[dlogits].ensure(ctx, M * out_ch);
     bufs[x_stage].ensure(ctx, M * in_ch);
@@ -141,21 +128,21 @@ void rfi_model::prepare_mlp(int n, int h, int w) {
     pN = n; pH = 1; pW = 1;
 }
 
-void rfi_model::forward_mlp(const float* x_dev, int n) {
+void BoxHeadModel::forward_pass(const float* x_dev, int n, int, int, bool) {
     refresh_dgrad_weights();
     const int L = depth;
     const Lay s = layout_of(n);
     for (int i = 0; i < L; ++i) {
         ConvBN& c = convs[i];
         ConvArgs a;
-        a.x = i == 0 ? View{x_dev, in_ch} : View{buf(mkY[i - 1]), feat};
+        a.x = i == 0 ? View{x_dev, in_ch} : View{buf(fcY[i - 1]), feat};
         a.N = s.N; a.H = s.H; a.W = s.W; a.Hin = s.H; a.Win = s.W;
         a.Cin = c.cin; a.Cout = c.cout;
         a.w = params + c.w_off;
         a.w3 = use_w3() ? c.w3 : nullptr;
         ws_set(a);
         a.bias = params + c.b_off;
-        a.y = MutView{buf(mkY[i]), c.cout};
+        a.y = MutView{buf(fcY[i]), c.cout};
         a.Hout = s.H; a.Wout = s.W;
         a.R = 1; a.S = 1; a.pad = 0;
         if (i > 0) a.xf = relu_of(convs[i - 1]);
@@ -164,11 +151,11 @@ void rfi_model::forward_mlp(const float* x_dev, int n) {
         launch_conv(ctx, a);
     }
     const ConvBN& cl = convs[L - 1];
-    launch_head_fwd(ctx, buf(mkY[L - 1]), n, feat, cl.scale(), cl.shift(), params + head_w_off, params + head_b_off, out_ch, buf(logits));
+    launch_head_fwd(ctx, buf(fcY[L - 1]), n, feat, cl.scale(), cl.shift(), params + head_w_off, params + head_b_off, out_ch, buf(logits));
 }
 
 // dlogits are the caller's (rfi_model_backward_dlogits): this head has no loss of its own
-void rfi_model::backward_mlp(const float* x_dev, int n) {
+void BoxHeadModel::backward_pass(const float* x_dev, const uint8_t*, int n, int, int) {
     RFI_REQUIRE(ext_dlogits, "BoxHead: the loss lives outside the model (rfi_op_fastrcnn_loss + rfi_model_backward_dlogits)");
     side_bound = 0;
     const int L = depth;
@@ -176,15 +163,15 @@ void rfi_model::backward_mlp(const float* x_dev, int n) {
     const int64_t M = n;
     refresh_dgrad_weights();
     const ConvBN& cl = convs[L - 1];
-    launch_head_bwd(ctx, buf(mkY[L - 1]), M, feat, cl.scale(), cl.shift(), params + head_w_off, out_ch, buf(dlogits), buf(mkG[L - 1]),
+    launch_head_bwd(ctx, buf(fcY[L - 1]), M, feat, cl.scale(), cl.shift(), params + head_w_off, out_ch, buf(dlogits), buf(fcG[L - 1]),
                     buf(ws_red), grads + head_w_off, grads + head_b_off);
     for (int i = L - 1; i >= 0; --i) {
         ConvBN& c = convs[i];
-        float* dA = buf(mkG[i]);
-        launch_relu_bwd(ctx, dA, buf(mkY[i]), M * c.cout);
+        float* dA = buf(fcG[i]);
+        launch_relu_bwd(ctx, dA, buf(fcY[i]), M * c.cout);
         launch_channel_sum(ctx, View{dA, c.cout}, M, c.cout, buf(ws_red), grads + c.b_off);
         WgradArgs wa;
-        wa.xop = i == 0 ? View{x_dev, in_ch} : View{buf(mkY[i - 1]), feat};
+        wa.xop = i == 0 ? View{x_dev, in_ch} : View{buf(fcY[i - 1]), feat};
         if (i > 0) wa.xf_x = relu_of(convs[i - 1]);
         wa.yop = View{dA, c.cout};
         wa.N = s.N; wa.H = s.H; wa.W = s.W; wa.Hx = s.H; wa.Wx = s.W;
@@ -197,7 +184,7 @@ void rfi_model::backward_mlp(const float* x_dev, int n) {
         wa.slab_floats = bufs[ws_slab].n;
         wa.bf16 = compute_bf16;
         wa.bf16x3 = compute_x3;
-        {   // side stream: every layer owns its gradient tensor mkG[i], nothing the weight gradient reads is rewritten in this pass
+        {   // side stream: every layer owns its gradient tensor fcG[i], nothing the weight gradient reads is rewritten in this pass
             struct Back { rfi_ctx* c; ~Back() { c->stream = c->main_stream; } } back{ctx};
             side_begin();
             launch_wgrad(ctx, wa);
@@ -210,7 +197,7 @@ void rfi_model::backward_mlp(const float* x_dev, int n) {
         a.w = c.wd;
         a.w3 = use_w3() ? c.wd3 : nullptr;
         ws_set(a);
-        a.y = MutView{i == 0 ? buf(mkGx) : buf(mkG[i - 1]), c.cin};
+        a.y = MutView{i == 0 ? buf(gx) : buf(fcG[i - 1]), c.cin};
         a.Hout = s.H; a.Wout = s.W;
         a.R = 1; a.S = 1; a.pad = 0;
         a.bf16 = compute_bf16;
@@ -218,4 +205,13 @@ void rfi_model::backward_mlp(const float* x_dev, int n) {
         launch_conv(ctx, a);
     }
     side_join_lazy();                 // (the caller goes on with the input gradient; the weight gradients are needed at the optimiser step)
+    bucket_ready(0, n_flat);
+}
+
+void BoxHeadModel::algorithmic_flops(int n, int, int, double& fwd, double& step) const {
+    double f = 0;
+    for (auto& c : convs) f += 2.0 * n * c.cin * c.cout;
+    f += 2.0 * n * (double)feat * out_ch;
+    fwd = f;
+    step = 3.0 * f;
 }

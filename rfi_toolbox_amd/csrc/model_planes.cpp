@@ -43,9 +43,9 @@ void PlaneBuf::free() {
 
 }  // namespace rfi
 
-void rfi_model::prepare_planes(int n, int h, int w) {
+void UNetModel::prepare_planes(int n, int h, int w) {
     const int P = planesP, D = depth, IB = i_bott;
-    const bool rs = arch == 2;                     // ResNet-style encoder: its own tensors instead of the U-Net encoder's
+    const bool rs = resnet_encoder;                    // ResNet-style encoder: its own tensors instead of the U-Net encoder's
     if (pl.empty()) {
         auto mk = [&](std::vector<int>& v) { v.assign(D + 1, -1); for (int l = 1; l <= D; ++l) { pl.emplace_back(); v[l] = (int)pl.size() - 1; } };
         mk(pA1e); mk(pSkip); mk(pPool); mk(pUp); mk(pA1d); mk(pdYa); mk(pdYb); mk(pdYaE); mk(pdYbE);
@@ -177,11 +177,11 @@ void rfi_model::prepare_planes(int n, int h, int w) {
 
 // filters of every 3x3 layer in MFMA B-operand order, both directions, rebuilt with the dgrad layouts after each
 // optimiser step by ONE batched launch
-void rfi_model::refresh_plane_weights(int which) {
+void UNetModel::refresh_plane_weights(int which) {
     const int P = planesP, IB = i_bott;
     auto two_seg = [&](size_t ci) { return (int)ci >= IB + 2 && (((int)ci - (IB + 2)) & 1) == 0; };      // decoder conv1: [up | skip]
     auto has_wBd = [&](const ConvBN& c) { return c.R == 3 && c.stride == 1; };      // (the other shapes' input gradients: class tables)
-    if (arch == 2 && rpb.empty()) rpb.assign(blocks.size(), ResPlanes());
+    if (resnet_encoder && rpb.empty()) rpb.assign(blocks.size(), ResPlanes());
     if (!wb_pool) {
         // the table: every forward-direction image first (what the forward pass reads), then the input-gradient direction
         // (dgrad layouts, parity-class tables) -- the second half can be rebuilt on the side stream under the forward pass
@@ -288,7 +288,7 @@ struct YT {
 };
 
 // (s: the OUTPUT grid; a stride-2 layer reads an input of twice that size)
-void run_pconv_bn(rfi_model* m, ConvBN& c, const PlaneSeg* in, int nseg, Shape s, YT Yt, bool train) {
+void run_pconv_bn(UNetModel* m, ConvBN& c, const PlaneSeg* in, int nseg, Shape s, YT Yt, bool train) {
     float* Y = Yt.f;
     PConvArgs a;
     a.x[0] = in[0];
@@ -324,7 +324,7 @@ void run_pconv_bn(rfi_model* m, ConvBN& c, const PlaneSeg* in, int nseg, Shape s
 }
 
 // Conv3x3+BN+act twice: Y1 = conv(in) ; A1 = planes(act(BN(Y1))) ; Y2 = conv(A1)
-void double_conv(rfi_model* m, ConvBN& c1, ConvBN& c2, const PlaneSeg* in, int nseg, Shape s, YT Y1, PlaneBuf& A1,
+void double_conv(UNetModel* m, ConvBN& c1, ConvBN& c2, const PlaneSeg* in, int nseg, Shape s, YT Y1, PlaneBuf& A1,
                  YT Y2, bool train) {
     run_pconv_bn(m, c1, in, nseg, s, Y1, train);
     const int64_t M = (int64_t)s.N * s.H * s.W;
@@ -340,7 +340,7 @@ void double_conv(rfi_model* m, ConvBN& c1, ConvBN& c2, const PlaneSeg* in, int n
 // (statistics from the conv epilogues), activations as the operands of the next contraction.  Stride-2 layers read the
 // full-resolution planes directly (the LDS halo tile has the stride): no space-to-depth copy.  A stage's output IS the
 // decoder's skip tensor.  cur <- the pooled output of the last stage.
-void rfi_model::forward_resnet_planes(PlaneSeg& cur, int n, int h, int w, bool train) {
+void UNetModel::forward_resnet_planes(PlaneSeg& cur, int n, int h, int w, bool train) {
     const int D = depth;
     {
         ConvBN& c = convs[0];
@@ -382,7 +382,7 @@ void rfi_model::forward_resnet_planes(PlaneSeg& cur, int n, int h, int w, bool t
     cur = seg_of(pl[pPool[D]]);
 }
 
-void rfi_model::forward_planes(const float* x_dev, int n, int h, int w, bool train_mode) {
+void UNetModel::forward_planes(const float* x_dev, int n, int h, int w, bool train_mode) {
     const int D = depth, P = planesP;
     prepare_planes(n, h, w);
     launch_act_split(ctx, View{x_dev, in_ch}, (int64_t)n * h * w, in_ch, InXform{}, P, pl[pXin].p, pl[pXin].pstride);
@@ -390,7 +390,7 @@ void rfi_model::forward_planes(const float* x_dev, int n, int h, int w, bool tra
     const int IB = i_bott;
     // a raw conv output: the bfloat16 tensor pl[hi] when the bf16 flow is on (hi >= 0), else the float32 tensor bufs[fi]
     auto yt = [&](int fi, int hi) { YT y; if (y16_flow && hi >= 0) y.h = &pl[hi]; else y.f = buf(fi); return y; };
-    if (arch == 2) forward_resnet_planes(cur, n, h, w, train_mode);
+    if (resnet_encoder) forward_resnet_planes(cur, n, h, w, train_mode);
     else for (int l = 1; l <= D; ++l) {
         Shape s{n, h >> (l - 1), w >> (l - 1)};
         ConvBN& c1 = convs[2 * (l - 1)];
@@ -515,7 +515,7 @@ struct GT {
 // own -- a residual branch, whose masked gradient dA already is dz).  Layers with a stride or other taps (ResNet-style
 // encoder): s is the OUTPUT grid, `in` the input of stride times that size, dx must be null (the caller runs the input
 // gradient by parity classes).
-int backward_pconv_bn(rfi_model* m, ConvBN& c, YRef dA, YRef Y, const PlaneSeg* in, int nseg, Shape s,
+int backward_pconv_bn(UNetModel* m, ConvBN& c, YRef dA, YRef Y, const PlaneSeg* in, int nseg, Shape s,
                       GT dx, PlaneBuf& dYp, int have_records = 0, ConvBN* next = nullptr, YRef next_Y = YRef((const float*)nullptr),
                       const float* slope_override = nullptr) {
     rfi_ctx* ctx = m->ctx;
@@ -595,7 +595,7 @@ int backward_pconv_bn(rfi_model* m, ConvBN& c, YRef dA, YRef Y, const PlaneSeg* 
 //   stride-2 block  projection: BNd backward of the same dz -> dYd planes, its weight gradient; the input gradient of conv1 AND
 //                   of the projection as four 2x2 contractions, one per parity class of the input pixel, written with output
 //                   stride 2 (class 0 takes the projection as a second K segment): no zero-stuffed tensor, no scatter pass
-void rfi_model::backward_resnet_planes(int n, int h, int w) {
+void UNetModel::backward_resnet_planes(int n, int h, int w) {
     const int D = depth;
     const float one = 1.0f;
     // gradient w.r.t. the last stage's output: skip gradient + max-pool routing of dpool (-> rp_dX, as "dX from above")
@@ -668,7 +668,7 @@ void rfi_model::backward_resnet_planes(int n, int h, int w) {
     }
 }
 
-void rfi_model::backward_planes(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w) {
+void UNetModel::backward_planes(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w) {
     (void)x_dev;
     const int D = depth, IB = i_bott;
     // every layer owns its dY plane tensor and the other side-stream inputs (forward planes, dconcat, raw conv outputs)
@@ -813,7 +813,7 @@ void rfi_model::backward_planes(const float* x_dev, const uint8_t* labels_dev, i
                           gt(dpool[D], g16_flow ? g16pool[D] : -1), pl[pdYbottB], rec1);
         bucket_ready(convs[IB].w_off, ups[0].w_off);
     }
-    if (arch == 2) backward_resnet_planes(n, h, w);
+    if (resnet_encoder) backward_resnet_planes(n, h, w);
     else for (int l = D; l >= 1; --l) {           // encoders, deep to shallow
         Shape s{n, h >> (l - 1), w >> (l - 1)};
         ConvBN& c1 = convs[2 * (l - 1)];

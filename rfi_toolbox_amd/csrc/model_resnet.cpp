@@ -23,7 +23,7 @@ using namespace rfi;
 
 static size_t align4(size_t v) { return (v + 3) & ~size_t(3); }
 
-void rfi_model::build_resnet() {
+void UNetModel::build_resnet() {
     RFI_REQUIRE(in_ch > 0 && out_ch > 0 && feat > 0 && feat % 4 == 0, "UNetResNet18: init_features must be a positive multiple of 4");
     depth = 4;
     const int D = depth;
@@ -131,20 +131,7 @@ void rfi_model::build_resnet() {
     }
 
     // ---- device state
-    ctx->activate();
-    const size_t bytes = n_flat * sizeof(float);
-    params = static_cast<float*>(ctx->alloc(bytes));
-    grads = static_cast<float*>(ctx->alloc(bytes));
-    adam_m = static_cast<float*>(ctx->alloc(bytes));
-    adam_v = static_cast<float*>(ctx->alloc(bytes));
-    chan_pool = static_cast<float*>(ctx->alloc(chan_floats * sizeof(float)));
-    wd_pool = static_cast<float*>(ctx->alloc(wd_floats * sizeof(float)));
-    d_sums = static_cast<double*>(ctx->alloc(8 * sizeof(double)));
-    d_scalars = static_cast<float*>(ctx->alloc(8 * sizeof(float)));
-    for (float* p : {params, grads, adam_m, adam_v}) RFI_CHECK_HIP(hipMemsetAsync(p, 0, bytes, ctx->stream));
-    RFI_CHECK_HIP(hipMemsetAsync(chan_pool, 0, chan_floats * sizeof(float), ctx->stream));
-    RFI_CHECK_HIP(hipMemsetAsync(d_sums, 0, 8 * sizeof(double), ctx->stream));
-    RFI_CHECK_HIP(hipMemsetAsync(d_scalars, 0, 8 * sizeof(float), ctx->stream));
+    alloc_state(chan_floats, wd_floats);
     size_t co = 0, wo = 0;
     for (int ci = 0; ci < i_bott + 2; ++ci) {
         ConvBN& c = convs[ci];
@@ -188,7 +175,7 @@ void rfi_model::build_resnet() {
     reset_channel_state();
 }
 
-void rfi_model::prepare_resnet(int n, int h, int w) {
+void UNetModel::prepare_resnet(int n, int h, int w) {
     if (rs_stemY < 0) {
         rs_stemY = new_buf(); rs_a0 = new_buf(); rs_g0 = new_buf(); rs_g1 = new_buf();
         rs_dX = new_buf(); rs_dS = new_buf(); rs_dW = new_buf(); rs_dzd = new_buf();
@@ -218,7 +205,7 @@ void rfi_model::prepare_resnet(int n, int h, int w) {
 
 // the 2x2 forms of the stride-2 filters (forward and input-gradient layouts); every other derived copy comes from
 // the batched relayout of model.cpp
-void rfi_model::refresh_resnet_weights() {
+void UNetModel::refresh_resnet_weights() {
     for (int ci = 0; ci < i_bott; ++ci) {
         ConvBN& c = convs[ci];
         if (c.stride != 2 || c.R != 3) continue;
@@ -323,7 +310,7 @@ void dgrad(rfi_model* m, const float* dY, int cy, const float* wd, const float* 
 }  // namespace
 
 // -> the pooled output of layer 4 (input of the bottleneck); skip l is written into concat[l][..., C:2C]
-View rfi_model::forward_resnet_encoder(View x, int n, int h, int w, bool train) {
+View UNetModel::forward_resnet_encoder(View x, int n, int h, int w, bool train) {
     const int D = depth;
     {                                             // stem: a0 = relu(BN(conv3x3(x)))
         ConvBN& c = convs[0];
@@ -371,7 +358,7 @@ View rfi_model::forward_resnet_encoder(View x, int n, int h, int w, bool train) 
     return View{buf(pool[D]), lb.cout};
 }
 
-void rfi_model::backward_resnet_encoder(const float* x_dev, int n, int h, int w) {
+void UNetModel::backward_resnet_encoder(const float* x_dev, int n, int h, int w) {
     const int D = depth;
     // gradient w.r.t. the last stage's output: skip gradient + max-pool routing of dpool
     float* gout = buf(rs_g0);
