@@ -336,6 +336,43 @@ int rfi_confusion_counts(rfi_ctx* ctx, const void* pred, int pred_dtype, int pre
 int rfi_threshold_logits(rfi_ctx* ctx, const float* logits_dev, int64_t count, float threshold,
                          uint8_t* mask_dev);
 
+/* ---- whole-observation prediction: the inverse of the inference-mode tiling of Preprocessor.create_dataset
+ *      (preprocessing/preprocessor.py:281,317-351 keeps `original_shapes` for it; nothing in the reference inverts it).
+ *      Tiling of an n_planes x C x T stack by `rfi_tiling`:
+ *        views 1, 2 or 4 select views {0}, {0,1}, {0,1,2,3} (rfi_patch_src's meanings);
+ *        tile origins along an axis of length L: 0 when L <= ps, else 0, s, 2s, ..., k*s with k = ceil((L-ps)/s);
+ *        edge RFI_EDGE_PAD: the last tile may run past the edge (zero padding; s == ps is the reference's tiling),
+ *        edge RFI_EDGE_SHIFT: the last origin is L-ps instead, so no tile holds padding;
+ *        patch order: plane-major, then view, then tile row, then tile column (row-major in view coordinates).
+ *      Stitch: per waterfall pixel, every (view, tile) that covers it is visited in ascending view, tile row, tile
+ *      column order; each visit reads p = 1.0f / (1.0f + expf(-x)) (kind RFI_VALUES_LOGITS) or x itself
+ *      (RFI_VALUES_PROBS); combine RFI_COMBINE_MEAN: float32 running sum in that order / float32 count,
+ *      RFI_COMBINE_MAX: the maximum.  flag = combined > threshold.  Padding never reaches the output.  Gather form,
+ *      no atomics: bitwise reproducible. ---- */
+typedef struct rfi_tiling {
+    int32_t ps, stride, edge, views;
+} rfi_tiling;
+enum { RFI_EDGE_PAD = 0, RFI_EDGE_SHIFT = 1 };
+enum { RFI_COMBINE_MEAN = 0, RFI_COMBINE_MAX = 1 };
+enum { RFI_VALUES_LOGITS = 0, RFI_VALUES_PROBS = 1 };
+/* host only: the number of patches one C x T plane is cut into */
+int rfi_tiling_count(int c, int t, const rfi_tiling* tiling, int64_t* patches_per_plane);
+/* values: n_planes x patches_per_plane patches of ps x ps float32 in the order above; flags: n_planes x C x T uint8;
+ * prob (optional, NULL = none): n_planes x C x T float32 combined values.  Returns when the outputs are in place. */
+int rfi_stitch_patches(rfi_ctx* ctx, const float* values, int values_mem, int kind, int n_planes, int c, int t,
+                       const rfi_tiling* tiling, int combine, float threshold, uint8_t* flags, int flags_mem,
+                       float* prob, int prob_mem);
+/* the whole pipeline on a model with 3 input channels and 1 output channel: planes (n_planes x C x T, RFI_C128 or
+ * RFI_C64, host or device) are streamed through in chunks of whole planes -- upload, gather + channel extraction
+ * (rfi_preprocess_gather's kernels), EVAL-mode forward in sub-batches of `batch` patches (BatchNorm on the running
+ * statistics whatever the model's mode; running buffers untouched), stitch of the model's output (logits, or the
+ * probabilities of a sigmoid-head model: never sigmoided twice), download.  Device workspace is bounded by one chunk
+ * (at most 1 GiB, held in the context's grow-only scratch for later calls); a single plane too large for it is an
+ * error.  Returns when the outputs are in place. */
+int rfi_model_predict_flags(rfi_model* m, const void* planes, int planes_mem, int dtype, int n_planes, int c, int t,
+                            const rfi_tiling* tiling, int batch, int combine, float threshold, uint8_t* flags,
+                            int flags_mem, float* prob, int prob_mem);
+
 /* ---- flagging-quality statistics: the reductions of evaluation/statistics.py:10-229 over a whole array.
  *      data: `count` elements of dtype RFI_C128 / RFI_C64 / RFI_F64 / RFI_F32 (complex: |z| by NumPy's rule
  *      L * sqrt(fma(S/L, S/L, 1)), L = max(|re|,|im|), S = min, in the input's precision); flags: `count` bytes of

@@ -37,6 +37,15 @@ class SimParams(C.Structure):
                 ("max_freq_fringes", C.c_double), ("gibbs_kernel", C.c_double * 17)]
 
 
+EDGE_PAD, EDGE_SHIFT = 0, 1
+COMBINE_MEAN, COMBINE_MAX = 0, 1
+VALUES_LOGITS, VALUES_PROBS = 0, 1
+
+
+class Tiling(C.Structure):
+    _fields_ = [("ps", C.c_int32), ("stride", C.c_int32), ("edge", C.c_int32), ("views", C.c_int32)]
+
+
 class Hyper(C.Structure):
     _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
                 ("weight_decay", C.c_double), ("max_grad_norm", C.c_double)]
@@ -170,6 +179,9 @@ _PROTOS = {
     "rfi_preprocess_gather": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _i]),
     "rfi_confusion_counts": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i64, _pi64, _pi64, _pi64]),
     "rfi_threshold_logits": (_i, [_vp, _vp, _i64, _f, _vp]),
+    "rfi_tiling_count": (_i, [_i, _i, C.POINTER(Tiling), _pi64]),
+    "rfi_stitch_patches": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(Tiling), _i, _f, _vp, _i, _vp, _i]),
+    "rfi_model_predict_flags": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(Tiling), _i, _i, _f, _vp, _i, _vp, _i]),
     "rfi_simulate_rfi": (_i, [_vp, C.c_uint64, C.c_uint64, _i, C.POINTER(SimParams), _vp, _i, _vp, _vp, _vp, _vp]),
     "rfi_flag_statistics": (_i, [_vp, _vp, _i, _i, _i64, _vp, _i, _i, _i, C.POINTER(FlagStats), C.POINTER(FlagStats)]),
     "rfi_op_conv3x3": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),

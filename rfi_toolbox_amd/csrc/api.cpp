@@ -1401,6 +1401,212 @@ int rfi_threshold_logits(rfi_ctx* ctx, const float* logits_dev, int64_t count, f
     });
 }
 
+// ------------------------------------------------------------------------------------ whole-observation prediction
+namespace {
+// workspace of rfi_model_predict_flags that grows with the chunk (patch outputs, staged planes and outputs, the table)
+constexpr size_t kPredictBudget = size_t(1) << 30;
+
+// a temporary HIP stream / events, and a stream swap for profiled launches on another stream
+struct TmpStream {
+    hipStream_t s = nullptr;
+    TmpStream() { RFI_CHECK_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
+    ~TmpStream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
+};
+struct TmpEvents {
+    std::vector<hipEvent_t> e;
+    explicit TmpEvents(int n) : e((size_t)n, nullptr) {
+        for (auto& x : e) RFI_CHECK_HIP(hipEventCreateWithFlags(&x, hipEventDisableTiming));
+    }
+    ~TmpEvents() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
+};
+struct OnStream {
+    rfi_ctx* c; hipStream_t old;
+    OnStream(rfi_ctx* ctx, hipStream_t s) : c(ctx), old(ctx->stream) { c->stream = s; }
+    ~OnStream() { c->stream = old; }
+};
+}  // namespace
+
+int rfi_tiling_count(int c, int t, const rfi_tiling* tiling, int64_t* patches_per_plane) {
+    return guarded([&] {
+        RFI_REQUIRE(tiling && patches_per_plane, "tiling_count: null argument");
+        RFI_REQUIRE(c > 0 && t > 0, "tiling_count: empty plane");
+        check_tiling(*tiling);
+        *patches_per_plane = tiling_patches_per_plane(c, t, *tiling);
+    });
+}
+
+int rfi_stitch_patches(rfi_ctx* ctx, const float* values, int values_mem, int kind, int n_planes, int c, int t,
+                       const rfi_tiling* tiling, int combine, float threshold, uint8_t* flags, int flags_mem,
+                       float* prob, int prob_mem) {
+    return guarded([&] {
+        RFI_REQUIRE(ctx && values && flags && tiling, "stitch_patches: null argument");
+        RFI_REQUIRE(n_planes >= 0 && c > 0 && t > 0, "stitch_patches: bad shape");
+        check_tiling(*tiling);
+        if (n_planes == 0) return;
+        ctx->activate();
+        const int64_t ppp = tiling_patches_per_plane(c, t, *tiling);
+        const size_t px = (size_t)n_planes * c * t;
+        Staged v(ctx, values, values_mem, (size_t)n_planes * ppp * tiling->ps * tiling->ps * sizeof(float));
+        void* df = flags_mem == RFI_HOST ? ctx->alloc(px) : flags;
+        void* dp = prob && prob_mem == RFI_HOST ? ctx->alloc(px * sizeof(float)) : prob;
+        struct Free {
+            rfi_ctx* c; void* a; void* b;
+            ~Free() { (void)hipStreamSynchronize(c->stream); try { if (a) c->release(a); if (b) c->release(b); } catch (...) {} }
+        } fr{ctx, df != flags ? df : nullptr, dp != prob ? dp : nullptr};
+        launch_stitch(ctx, static_cast<const float*>(v.dev), kind, n_planes, c, t, *tiling, combine, threshold,
+                      static_cast<uint8_t*>(df), static_cast<float*>(dp));
+        if (df != flags) RFI_CHECK_HIP(hipMemcpyAsync(flags, df, px, hipMemcpyDeviceToHost, ctx->stream));
+        if (dp != prob) RFI_CHECK_HIP(hipMemcpyAsync(prob, dp, px * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    });
+}
+
+// Chunks of k whole planes.  Per chunk: gather + channel extraction of `nb` patches at a time into one image batch,
+// eval forward of that batch (always nb samples: one prepared shape; the slots past the chunk's last patch hold zeros or
+// the previous batch's images and their outputs are dropped -- eval mode is independent per sample), its output copied
+// into the chunk's patch-output buffer, then one stitch.  Host input is uploaded on a second stream into two alternating
+// slots, the next chunk's upload next to the current chunk's compute; host outputs are staged the same way and copied
+// back on that stream while the next chunk computes.
+int rfi_model_predict_flags(rfi_model* m, const void* planes, int planes_mem, int dtype, int n_planes, int c, int t,
+                            const rfi_tiling* tiling, int batch, int combine, float threshold, uint8_t* flags,
+                            int flags_mem, float* prob, int prob_mem) {
+    return guarded([&] {
+        RFI_REQUIRE(m && planes && flags && tiling, "predict_flags: null argument");
+        RFI_REQUIRE(dtype == RFI_C128 || dtype == RFI_C64,
+                    "predict_flags: planes must be complex128 or complex64 (real input: Preprocessor + rfi_stitch_patches)");
+        RFI_REQUIRE(n_planes >= 0 && c > 0 && t > 0 && batch > 0, "predict_flags: bad shape or batch");
+        RFI_REQUIRE(m->in_ch == 3 && m->out_ch == 1 && m->out_scale == 1,
+                    "predict_flags: needs a model with 3 input channels, 1 output channel and an output map the size of its input");
+        RFI_REQUIRE(combine == RFI_COMBINE_MEAN || combine == RFI_COMBINE_MAX, "predict_flags: combine must be mean (0) or max (1)");
+        check_tiling(*tiling);
+        if (n_planes == 0) return;
+        rfi_ctx* ctx = m->ctx;
+        ctx->activate();
+        const int ps = tiling->ps;
+        const int64_t ppp = tiling_patches_per_plane(c, t, *tiling);
+        const size_t esz = dtype == RFI_C128 ? 16 : 8;
+        const size_t plane_px = (size_t)c * t, plane_bytes = plane_px * esz, patch_px = (size_t)ps * ps;
+        const bool host_in = planes_mem == RFI_HOST, host_fl = flags_mem == RFI_HOST, host_pr = prob && prob_mem == RFI_HOST;
+        const size_t out_px_bytes = (host_fl ? 1 : 0) + (host_pr ? 4 : 0);
+        const size_t per_plane = (size_t)ppp * (patch_px * sizeof(float) + sizeof(rfi_patch_src)) +
+                                 (host_in ? 2 * plane_bytes : 0) + 2 * plane_px * out_px_bytes;
+        RFI_REQUIRE(per_plane <= kPredictBudget,
+                    "predict_flags: one " + std::to_string(c) + " x " + std::to_string(t) + " plane needs " +
+                        std::to_string(per_plane >> 20) + " MiB of workspace at this tiling (" + std::to_string(ppp) +
+                        " patches of " + std::to_string(ps) + "^2), over the budget of " +
+                        std::to_string(kPredictBudget >> 20) + " MiB; planes are not split: use a larger stride, fewer views "
+                        "or smaller planes");
+        // planes per chunk: at least ~4 batches of patches, no more than the budget holds; among up to 4x that, the one
+        // whose last batch wastes the smallest share of slots
+        const int kmax = (int)std::min<size_t>((size_t)n_planes, kPredictBudget / per_plane);
+        const int k0 = (int)std::min<int64_t>(kmax, std::max<int64_t>(1, cdiv(4 * (int64_t)batch, ppp)));
+        int k = k0;
+        double best = 2.0;
+        for (int kk = k0; kk <= std::min(kmax, 4 * k0); ++kk) {
+            const int64_t np = (int64_t)kk * ppp, nbk = std::min<int64_t>(batch, np);
+            const double waste = (double)(cdiv(np, nbk) * nbk - np) / (double)np;
+            if (waste < best - 1e-12) { best = waste; k = kk; }
+        }
+        const int64_t chunk_patches = (int64_t)k * ppp;
+        const int nb = (int)std::min<int64_t>(batch, chunk_patches);
+        const int nchunks = (int)cdiv(n_planes, k);
+        const int kind = m->head_sigmoid ? RFI_VALUES_PROBS : RFI_VALUES_LOGITS;
+
+        // the chunk's patch table (plane indices local to the chunk; the same for every chunk, a prefix for the last)
+        std::vector<rfi_patch_src> table((size_t)chunk_patches);
+        {
+            const int nC = (int)(tiling_patches_per_plane(c, 1, rfi_tiling{ps, tiling->stride, tiling->edge, 1}));
+            const int nT = (int)(tiling_patches_per_plane(1, t, rfi_tiling{ps, tiling->stride, tiling->edge, 1}));
+            auto origin = [&](int i, int n, int L) {
+                return (tiling->edge == RFI_EDGE_SHIFT && i == n - 1 && L > ps) ? L - ps : i * tiling->stride;
+            };
+            size_t e = 0;
+            for (int p = 0; p < k; ++p)
+                for (int v = 0; v < tiling->views; ++v) {
+                    const bool tr = v >= 2;
+                    const int nr = tr ? nT : nC, nc = tr ? nC : nT, Hv = tr ? t : c, Wv = tr ? c : t;
+                    for (int i = 0; i < nr; ++i)
+                        for (int j = 0; j < nc; ++j) table[e++] = rfi_patch_src{p, v, origin(i, nr, Hv), origin(j, nc, Wv)};
+                }
+        }
+
+        // one grow-only scratch region: [table | min/max words | images | patch outputs | 2 plane slots | 2 output slots]
+        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+        const size_t b_table = al(table.size() * sizeof(rfi_patch_src)), b_mm = al((size_t)nb * 4 * sizeof(unsigned long long));
+        const size_t b_img = al((size_t)nb * patch_px * 3 * sizeof(float)), b_out = al((size_t)chunk_patches * patch_px * sizeof(float));
+        const size_t b_in = host_in ? al((size_t)k * plane_bytes) : 0;
+        const size_t b_fl = host_fl ? al((size_t)k * plane_px) : 0, b_pr = host_pr ? al((size_t)k * plane_px * sizeof(float)) : 0;
+        char* base = static_cast<char*>(ctx->get_scratch(b_table + b_mm + b_img + b_out + 2 * (b_in + b_fl + b_pr)));
+        auto* d_table = reinterpret_cast<rfi_patch_src*>(base);
+        float* d_mm = reinterpret_cast<float*>(base + b_table);
+        float* d_img = reinterpret_cast<float*>(base + b_table + b_mm);
+        float* d_out = reinterpret_cast<float*>(base + b_table + b_mm + b_img);
+        char* slots = base + b_table + b_mm + b_img + b_out;
+        auto in_slot = [&](int s) { return slots + s * b_in; };
+        auto fl_slot = [&](int s) { return reinterpret_cast<uint8_t*>(slots + 2 * b_in + s * b_fl); };
+        auto pr_slot = [&](int s) { return reinterpret_cast<float*>(slots + 2 * (b_in + b_fl) + s * b_pr); };
+        RFI_CHECK_HIP(hipMemcpyAsync(d_table, table.data(), table.size() * sizeof(rfi_patch_src), hipMemcpyHostToDevice,
+                                     ctx->stream));
+        RFI_CHECK_HIP(hipMemsetAsync(d_img, 0, b_img, ctx->stream));
+
+        TmpStream cs;
+        TmpEvents ev(8);          // [0,1] upload done, [2,3] slot read by the gathers, [4,5] outputs ready, [6,7] outputs copied
+        struct Drain {            // every exit (an exception included) leaves both streams idle
+            rfi_ctx* c; hipStream_t s;
+            ~Drain() { (void)hipStreamSynchronize(s); (void)hipStreamSynchronize(c->stream); }
+        } drain{ctx, cs.s};
+        const char* src = static_cast<const char*>(planes);
+        auto planes_in = [&](int ci) { return std::min(k, n_planes - ci * k); };
+        auto upload = [&](int ci) {
+            const int s = ci & 1;
+            if (ci >= 2) RFI_CHECK_HIP(hipStreamWaitEvent(cs.s, ev.e[2 + s], 0));
+            OnStream on(ctx, cs.s);
+            ProfScope pf(ctx, FAM_PREPROCESS, 0, (double)planes_in(ci) * plane_bytes, "predict_upload");
+            RFI_CHECK_HIP(hipMemcpyAsync(in_slot(s), src + (size_t)ci * k * plane_bytes, (size_t)planes_in(ci) * plane_bytes,
+                                         hipMemcpyHostToDevice, cs.s));
+            RFI_CHECK_HIP(hipEventRecord(ev.e[s], cs.s));
+        };
+        auto download = [&](int ci) {
+            const int s = ci & 1;
+            const size_t px = (size_t)planes_in(ci) * plane_px, off = (size_t)ci * k * plane_px;
+            RFI_CHECK_HIP(hipStreamWaitEvent(cs.s, ev.e[4 + s], 0));
+            OnStream on(ctx, cs.s);
+            ProfScope pf(ctx, FAM_PREPROCESS, 0, (double)px * out_px_bytes, "predict_download");
+            if (host_fl) RFI_CHECK_HIP(hipMemcpyAsync(flags + off, fl_slot(s), px, hipMemcpyDeviceToHost, cs.s));
+            if (host_pr) RFI_CHECK_HIP(hipMemcpyAsync(prob + off, pr_slot(s), px * sizeof(float), hipMemcpyDeviceToHost, cs.s));
+            RFI_CHECK_HIP(hipEventRecord(ev.e[6 + s], cs.s));
+        };
+        auto compute = [&](int ci) {
+            const int s = ci & 1, np = planes_in(ci);
+            const int64_t npatch = (int64_t)np * ppp;
+            const void* pl = host_in ? static_cast<const void*>(in_slot(s)) : static_cast<const void*>(src + (size_t)ci * k * plane_bytes);
+            if (host_in) RFI_CHECK_HIP(hipStreamWaitEvent(ctx->stream, ev.e[s], 0));
+            if ((host_fl || host_pr) && ci >= 2) RFI_CHECK_HIP(hipStreamWaitEvent(ctx->stream, ev.e[6 + s], 0));
+            for (int64_t p0 = 0; p0 < npatch; p0 += nb) {
+                const int nv = (int)std::min<int64_t>(nb, npatch - p0);
+                launch_preprocess(ctx, pl, dtype, nv, ps, ps, d_mm, d_img, d_table + p0, c, t);
+                if (p0 + nb >= npatch) RFI_CHECK_HIP(hipEventRecord(ev.e[2 + s], ctx->stream));
+                m->forward(d_img, nb, ps, ps, false);
+                launch_copy_d2d(ctx, d_out + p0 * patch_px, m->buf(m->head_sigmoid ? m->probs : m->logits),
+                                (size_t)nv * patch_px * sizeof(float));
+            }
+            const size_t off = (size_t)ci * k * plane_px;
+            launch_stitch(ctx, d_out, kind, np, c, t, *tiling, combine, threshold, host_fl ? fl_slot(s) : flags + off,
+                          prob ? (host_pr ? pr_slot(s) : prob + off) : nullptr);
+            RFI_CHECK_HIP(hipEventRecord(ev.e[4 + s], ctx->stream));
+        };
+        if (host_in) upload(0);
+        for (int ci = 0; ci < nchunks; ++ci) {
+            compute(ci);
+            if (ci > 0 && (host_fl || host_pr)) download(ci - 1);
+            if (host_in && ci + 1 < nchunks) upload(ci + 1);
+        }
+        if (host_fl || host_pr) download(nchunks - 1);
+        RFI_CHECK_HIP(hipStreamSynchronize(cs.s));
+        RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    });
+}
+
 // ------------------------------------------------------------------------------------ kernel-level ops
 namespace {
 struct Scratch {

@@ -318,6 +318,12 @@ void launch_confusion(rfi_ctx* ctx, const void* pred, int pred_dtype, const void
                       int truth_dtype, int64_t count, unsigned long long* counts3);
 void launch_threshold(rfi_ctx* ctx, const float* logits, int64_t count, float threshold,
                       uint8_t* mask);
+// inverse of the inference tiling (stitch.hip): patch values (n_planes x tiling_patches_per_plane x ps x ps) -> flags
+// (and prob when non-null), n_planes x C x T; semantics in include/rfi_hip.h (rfi_stitch_patches)
+int64_t tiling_patches_per_plane(int C, int T, const rfi_tiling& tiling);
+void check_tiling(const rfi_tiling& tiling);
+void launch_stitch(rfi_ctx* ctx, const float* values, int kind, int n_planes, int C, int T, const rfi_tiling& tiling,
+                   int combine, float threshold, uint8_t* flags, float* prob);
 // whole-array flagging statistics (flag_stats.hip): src is `n` elements of dtype RFI_C128/C64/F64/F32 on the device,
 // flags n bytes (non-zero == flagged) or nullptr; views bit 0 all elements, bit 1 unflagged elements; ws holds
 // flag_stats_ws_bytes(); mag holds n input-precision floats (complex input only); out_dev[2] receives the views

@@ -144,6 +144,7 @@ class Preprocessor:
             self.data = data[np.newaxis, ...]
         else:
             raise ValueError(f"Data must be 3D or 4D, got shape {data.shape}")
+        self._input_shape = data.shape
         self.flags = flags
         self.patches = None
         self.patch_flags = None
@@ -234,6 +235,8 @@ class Preprocessor:
         rot = augmentation_rotations if (enable_augmentation and augmentation_rotations > 1) else 1
         have_flags = use_custom_flags and self.flags is not None
         self._table = None
+        self._last_request = {"inference_mode": bool(inference_mode), "rot": rot, "patch_size": patch_size,
+                              "num_patches": num_patches}       # what reconstruct_flags inverts
         if on_device_tiling and have_flags and np.iscomplexobj(self.data):
             metadata = {"patch_size": patch_size, "stretch": stretch, "flag_sigma": flag_sigma,
                         "normalize_before_stretch": normalize_before_stretch,
@@ -298,6 +301,80 @@ class Preprocessor:
                     "original_shapes": getattr(self, "original_shapes", None)}
         self.dataset = TorchDataset(torch.from_numpy(images), torch.from_numpy(labels), metadata)
         return self.dataset
+
+    # ---- the inverse of the inference-mode tiling (librfi_hip.so rfi_stitch_patches)
+    def reconstruct_flags(self, predictions, threshold=0.5, combine="mean", logits=False):
+        """Flags of the input data's shape from per-patch predictions of the last
+        ``create_dataset(inference_mode=True, ...)`` call (the reconstruction the reference keeps
+        ``original_shapes`` for, preprocessor.py:317-351), made by any model.
+
+        ``predictions``: ``(N, ps, ps)``, ``(N, ps, ps, 1)`` or ``(N, 1, ps, ps)`` in dataset order, NumPy or torch;
+        probabilities, or logits with ``logits=True`` (read as ``sigmoid``).  Every pixel combines the patches that
+        cover it -- one per view -- by float32 ``"mean"`` or ``"max"`` and is flagged when that is ``> threshold``."""
+        from ..inference import _COMBINE
+        from .._lib import EDGE_PAD, VALUES_LOGITS, VALUES_PROBS, Tiling
+
+        req = getattr(self, "_last_request", None)
+        if req is None or not req["inference_mode"]:
+            raise ValueError("reconstruct_flags inverts create_dataset(inference_mode=True, ...); the last dataset was "
+                             + ("not made" if req is None else "made in training mode (filtered and shuffled patches)"))
+        if combine not in _COMBINE:
+            raise ValueError(f"combine must be 'mean' or 'max', got {combine!r}")
+        pred = predictions.detach().cpu().numpy() if isinstance(predictions, torch.Tensor) else np.asarray(predictions)
+        pred = np.asarray(pred, dtype=np.float32)
+        if pred.ndim == 4 and pred.shape[-1] == 1:
+            pred = pred[..., 0]
+        elif pred.ndim == 4 and pred.shape[1] == 1:
+            pred = pred[:, 0]
+        if pred.ndim != 3:
+            raise ValueError(f"predictions must be (N, ps, ps), (N, ps, ps, 1) or (N, 1, ps, ps), got {np.shape(predictions)}")
+        B, P, Cn, Tn = self.data.shape
+        ps, rot = int(req["patch_size"]), req["rot"]
+        views = 1 if rot < 2 else (2 if rot < 4 else 4)
+        whole = Cn <= ps and Tn <= ps
+        n_full = B * P * views * (1 if whole else -(-Cn // ps) * -(-Tn // ps))
+        if req["num_patches"] and req["num_patches"] < n_full:
+            raise ValueError(f"the dataset was truncated to num_patches={req['num_patches']} of {n_full} patches; "
+                             "every patch is needed to reconstruct the flags")
+        if len(pred) != n_full:
+            raise ValueError(f"expected {n_full} patch predictions in dataset order, got {len(pred)}")
+        if whole:           # whole, unpadded waterfalls (preprocessor.py:340-347): the inverse views on the host
+            if pred.shape[1:] != (Cn, Tn) or (views == 4 and Cn != Tn):
+                raise ValueError(f"expected whole {Cn} x {Tn} waterfalls as patches, got {pred.shape[1:]}")
+            out = self._reconstruct_whole(pred.reshape(B * P, views, *pred.shape[1:]), combine, logits)
+            flags = out > np.float32(threshold)
+        else:
+            if pred.shape[1:] != (ps, ps):
+                raise ValueError(f"expected {ps} x {ps} patches, got {pred.shape[1:]}")
+            pred = np.ascontiguousarray(pred)
+            flags = np.empty((B * P, Cn, Tn), dtype=np.uint8)
+            ctx = Context.get(self._device)
+            check(lib.rfi_stitch_patches(ctx.handle, pred.ctypes.data_as(C.c_void_p), HOST,
+                                         VALUES_LOGITS if logits else VALUES_PROBS, B * P, Cn, Tn,
+                                         C.byref(Tiling(ps, ps, EDGE_PAD, views)), _COMBINE[combine], float(threshold),
+                                         flags.ctypes.data_as(C.c_void_p), HOST, None, HOST))
+            flags = flags.view(bool)
+        return flags.reshape(self._input_shape)
+
+    @staticmethod
+    def _reconstruct_whole(pred, combine, logits):
+        """(planes, views, h, w) whole-view predictions -> (planes, C, T) combined float32 values."""
+        one = np.float32(1.0)
+        acc = cnt = None
+        for v in range(pred.shape[1]):
+            p = pred[:, v].astype(np.float32)
+            if logits:
+                p = one / (one + np.exp(-p))
+            # back to plane coordinates: views 0 plane, 1 plane[::-1,:], 2 plane.T, 3 plane.T[::-1,:]
+            p = p if v == 0 else (p[:, ::-1, :] if v == 1 else (np.swapaxes(p, 1, 2) if v == 2 else np.swapaxes(p[:, ::-1, :], 1, 2)))
+            if acc is None:
+                acc, cnt = p.copy(), 1
+            elif combine == "mean":
+                acc += p
+                cnt += 1
+            else:
+                acc = np.where(p > acc, p, acc)
+        return acc / np.float32(cnt) if combine == "mean" else acc
 
     # ---- order-statistic branches on the GPU (librfi_hip.so rfi_preprocess_real / rfi_mad_flags)
     def _real_on_device(self, patches, stretch, before, after, sigma):

@@ -188,7 +188,8 @@ def as_pointer(x, dtype, ctx: Context):
             raise TypeError(f"device array has dtype {x.dtype}, expected {np.dtype(dtype)}")
         return x.ptr, DEVICE, x
     if is_torch(x):
-        tdt = {np.dtype(np.float32): torch.float32, np.dtype(np.uint8): torch.uint8}[np.dtype(dtype)]
+        tdt = {np.dtype(np.float32): torch.float32, np.dtype(np.uint8): torch.uint8,
+               np.dtype(np.complex64): torch.complex64, np.dtype(np.complex128): torch.complex128}[np.dtype(dtype)]
         if x.is_cuda:
             if x.device.index not in (None, ctx.device_index):
                 raise RuntimeError(f"tensor is on {x.device}, context on GPU {ctx.device_index}")
