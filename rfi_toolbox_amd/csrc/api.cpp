@@ -3,7 +3,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <random>
 
 #include "model.hpp"
 
@@ -341,125 +340,10 @@ int rfi_model_destroy(rfi_model* m) {
     });
 }
 
-namespace {
-
-// reference layout <-> library layout for one entry; host staging vectors
-// cin_p >= cin: library rows are zero-padded to cin_p input channels
-void to_lib_conv(const float* oihw, int cout, int cin, int R, std::vector<float>& out, int cin_p = -1) {
-    if (cin_p < 0) cin_p = cin;
-    out.assign((size_t)R * R * cout * cin_p, 0.0f);
-    for (int co = 0; co < cout; ++co)
-        for (int ci = 0; ci < cin; ++ci)
-            for (int t = 0; t < R * R; ++t)
-                out[((size_t)t * cout + co) * cin_p + ci] = oihw[((size_t)co * cin + ci) * R * R + t];
-}
-void from_lib_conv(const float* lib, int cout, int cin, int R, float* oihw, int cin_p = -1) {
-    if (cin_p < 0) cin_p = cin;
-    for (int co = 0; co < cout; ++co)
-        for (int ci = 0; ci < cin; ++ci)
-            for (int t = 0; t < R * R; ++t)
-                oihw[((size_t)co * cin + ci) * R * R + t] = lib[((size_t)t * cout + co) * cin_p + ci];
-}
-// ConvTranspose2d weight is [cin][cout][2][2]
-void to_lib_convt(const float* iohw, int cin, int cout, std::vector<float>& out) {
-    out.resize((size_t)4 * cout * cin);
-    for (int ci = 0; ci < cin; ++ci)
-        for (int co = 0; co < cout; ++co)
-            for (int t = 0; t < 4; ++t)
-                out[((size_t)t * cout + co) * cin + ci] = iohw[((size_t)ci * cout + co) * 4 + t];
-}
-void from_lib_convt(const float* lib, int cin, int cout, float* iohw) {
-    for (int ci = 0; ci < cin; ++ci)
-        for (int co = 0; co < cout; ++co)
-            for (int t = 0; t < 4; ++t)
-                iohw[((size_t)ci * cout + co) * 4 + t] = lib[((size_t)t * cout + co) * cin + ci];
-}
-
-// where a float entry lives inside a flat buffer (params / grads / adam m / adam v)
-size_t flat_offset(const rfi_model* m, const Entry& e) {
-    switch (e.kind) {
-        case 0: case 7: return m->convs[e.layer].w_off;
-        case 1: return m->ups[e.layer].w_off;
-        case 6: return m->head_w_off;
-        case 2:
-            switch (e.which) {
-                case 0: return m->convs[e.layer].b_off;
-                case 1: return m->convs[e.layer].g_off;
-                case 2: return m->convs[e.layer].be_off;
-                case 3: return m->ups[e.layer].b_off;
-                default: return m->head_b_off;
-            }
-        default: throw Error("entry " + e.name + " is not a parameter");
-    }
-}
-
-void upload(rfi_model* m, float* dst, const float* src, size_t n) {
-    RFI_CHECK_HIP(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyHostToDevice, m->ctx->stream));
-    RFI_CHECK_HIP(hipStreamSynchronize(m->ctx->stream));
-}
-void download(rfi_model* m, float* dst, const float* src, size_t n) {
-    RFI_CHECK_HIP(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToHost, m->ctx->stream));
-    RFI_CHECK_HIP(hipStreamSynchronize(m->ctx->stream));
-}
-
-const Entry& find_entry(rfi_model* m, const char* name) {
-    RFI_REQUIRE(name, "null entry name");
-    auto it = m->entry_index.find(name);
-    RFI_REQUIRE(it != m->entry_index.end(), std::string("unexpected key in state_dict: ") + name);
-    return m->entries[it->second];
-}
-
-void store_from_flat(rfi_model* m, const float* flat, const Entry& e, void* host, size_t bytes) {
-    RFI_REQUIRE(bytes == (size_t)e.numel() * sizeof(float),
-                "size mismatch for " + e.name + ": expected " + std::to_string(e.numel() * 4) + " bytes, got " +
-                    std::to_string(bytes));
-    const size_t off = flat_offset(m, e);
-    const int cin_p = e.kind == 0 ? m->convs[e.layer].cin_p : 0;
-    std::vector<float> tmp(e.kind == 0 ? (size_t)e.dims[2] * e.dims[3] * e.dims[0] * cin_p : (size_t)e.numel());
-    download(m, tmp.data(), flat + off, tmp.size());
-    float* out = static_cast<float*>(host);
-    if (e.kind == 0) from_lib_conv(tmp.data(), (int)e.dims[0], (int)e.dims[1], (int)e.dims[2], out, cin_p);
-    else if (e.kind == 1) from_lib_convt(tmp.data(), (int)e.dims[0], (int)e.dims[1], out);
-    else std::memcpy(out, tmp.data(), bytes);
-}
-
-}  // namespace
-
 int rfi_model_init(rfi_model* m, uint64_t seed) {
     return guarded([&] {
         m->ctx->activate();
-        std::mt19937_64 rng(seed);
-        std::vector<float> flat(m->n_flat, 0.0f);
-        auto uni = [&](float bound) {
-            return (float)((std::generate_canonical<double, 53>(rng) * 2.0 - 1.0) * bound);
-        };
-        float last_bound = 0;
-        for (const Entry& e : m->entries) {
-            if (e.kind == 0 || e.kind == 1 || e.kind == 6 || e.kind == 7) {
-                // kaiming_uniform(a=sqrt(5)) == U(+-1/sqrt(fan_in)), fan_in = dims[1]*kh*kw
-                const double fan_in = (double)e.dims[1] * e.dims[2] * e.dims[3];
-                last_bound = (float)(1.0 / std::sqrt(fan_in));
-                float* w = flat.data() + flat_offset(m, e);
-                if (e.kind == 0) {                      // [tap][cout][cin_p], padded channels stay 0
-                    const int cin_p = m->convs[e.layer].cin_p, cin = (int)e.dims[1];
-                    for (int64_t r = 0; r < e.dims[2] * e.dims[3] * e.dims[0]; ++r)
-                        for (int ci = 0; ci < cin; ++ci) w[r * cin_p + ci] = uni(last_bound);
-                } else {
-                    for (int64_t i = 0; i < e.numel(); ++i) w[i] = uni(last_bound);   // layout-agnostic iid
-                }
-            } else if (e.kind == 2) {
-                float* v = flat.data() + flat_offset(m, e);
-                for (int64_t i = 0; i < e.numel(); ++i)
-                    v[i] = (e.which == 1) ? 1.0f : (e.which == 2 ? 0.0f : uni(last_bound));
-            }
-        }
-        upload(m, m->params, flat.data(), m->n_flat);
-        m->reset_channel_state();
-        RFI_CHECK_HIP(hipMemsetAsync(m->adam_m, 0, m->n_flat * sizeof(float), m->ctx->stream));
-        RFI_CHECK_HIP(hipMemsetAsync(m->adam_v, 0, m->n_flat * sizeof(float), m->ctx->stream));
-        m->adam_step = 0;
-        m->wd_dirty = true;
-        m->x3_fresh = false;
+        m->init_params(seed);
     });
 }
 
@@ -475,8 +359,8 @@ int rfi_model_entry_info(rfi_model* m, int index, const char** name, int* ndim, 
         if (ndim) *ndim = e.ndim;
         if (dims)
             for (int i = 0; i < 4; ++i) dims[i] = i < e.ndim ? e.dims[i] : 1;
-        if (is_int64) *is_int64 = e.kind == 5;
-        if (is_parameter) *is_parameter = (e.kind == 0 || e.kind == 1 || e.kind == 2 || e.kind == 6 || e.kind == 7);
+        if (is_int64) *is_int64 = e.kind == EntryKind::NumBatchesTracked;
+        if (is_parameter) *is_parameter = rfi::is_parameter(e.kind);
     });
 }
 int rfi_model_param_count(rfi_model* m, int64_t* n) {
@@ -486,87 +370,37 @@ int rfi_model_param_count(rfi_model* m, int64_t* n) {
 int rfi_model_load_entry(rfi_model* m, const char* name, const void* host, size_t bytes) {
     return guarded([&] {
         m->ctx->activate();
-        const Entry& e = find_entry(m, name);
-        if (e.kind == 5) {
-            RFI_REQUIRE(bytes == sizeof(int64_t), "size mismatch for " + e.name);
-            m->convs[e.layer].nbt = *static_cast<const int64_t*>(host);
-            return;
-        }
-        RFI_REQUIRE(bytes == (size_t)e.numel() * sizeof(float),
-                    "size mismatch for " + e.name + ": expected " + std::to_string(e.numel() * 4) +
-                        " bytes, got " + std::to_string(bytes));
-        const float* src = static_cast<const float*>(host);
-        if (e.kind == 3 || e.kind == 4 || e.kind == 8 || e.kind == 9) {     // (8 / 9: frozen BatchNorm weight / bias)
-            ConvBN& c = m->convs[e.layer];
-            float* dst = e.kind == 3 ? c.running_mean() : (e.kind == 4 ? c.running_var() : (e.kind == 8 ? c.mean() : c.invstd()));
-            upload(m, dst, src, (size_t)c.cout);
-            if (auto* b = dynamic_cast<BackboneModel*>(m)) b->frozen_dirty = true;
-            return;
-        }
-        std::vector<float> tmp;
-        if (e.kind == 0) to_lib_conv(src, (int)e.dims[0], (int)e.dims[1], (int)e.dims[2], tmp, m->convs[e.layer].cin_p);
-        else if (e.kind == 1) to_lib_convt(src, (int)e.dims[0], (int)e.dims[1], tmp);
-        else tmp.assign(src, src + e.numel());
-        upload(m, m->params + flat_offset(m, e), tmp.data(), tmp.size());
-        m->wd_dirty = true;
-        m->x3_fresh = false;
+        m->load_entry(m->entry(name), host, bytes);
     });
 }
-
 int rfi_model_store_entry(rfi_model* m, const char* name, void* host, size_t bytes) {
     return guarded([&] {
         m->ctx->activate();
-        const Entry& e = find_entry(m, name);
-        if (e.kind == 5) {
-            RFI_REQUIRE(bytes == sizeof(int64_t), "size mismatch for " + e.name);
-            *static_cast<int64_t*>(host) = m->convs[e.layer].nbt;
-            return;
-        }
-        if (e.kind == 3 || e.kind == 4 || e.kind == 8 || e.kind == 9) {
-            RFI_REQUIRE(bytes == (size_t)e.numel() * sizeof(float), "size mismatch for " + e.name);
-            ConvBN& c = m->convs[e.layer];
-            const float* srcd = e.kind == 3 ? c.running_mean() : (e.kind == 4 ? c.running_var() : (e.kind == 8 ? c.mean() : c.invstd()));
-            download(m, static_cast<float*>(host), srcd, (size_t)c.cout);
-            return;
-        }
-        store_from_flat(m, m->params, e, host, bytes);
+        m->store_entry(m->entry(name), host, bytes);
     });
 }
-
 int rfi_model_store_grad(rfi_model* m, const char* name, void* host, size_t bytes) {
     return guarded([&] {
         m->ctx->activate();
         m->join_pending_side();
-        store_from_flat(m, m->grads, find_entry(m, name), host, bytes);
+        m->store_flat(m->grads, m->entry(name), host, bytes);
     });
 }
 int rfi_model_store_adam(rfi_model* m, const char* name, void* host_m, void* host_v, size_t bytes,
                          int64_t* step) {
     return guarded([&] {
         m->ctx->activate();
-        const Entry& e = find_entry(m, name);
-        if (host_m) store_from_flat(m, m->adam_m, e, host_m, bytes);
-        if (host_v) store_from_flat(m, m->adam_v, e, host_v, bytes);
+        const Entry& e = m->entry(name);
+        if (host_m) m->store_flat(m->adam_m, e, host_m, bytes);
+        if (host_v) m->store_flat(m->adam_v, e, host_v, bytes);
         if (step) *step = m->adam_step;
     });
 }
-
 int rfi_model_load_adam(rfi_model* m, const char* name, const void* host_m, const void* host_v,
                         size_t bytes) {
     return guarded([&] {
         m->ctx->activate();
-        const Entry& e = find_entry(m, name);
-        RFI_REQUIRE(bytes == (size_t)e.numel() * sizeof(float), "size mismatch for " + e.name);
-        const size_t off = flat_offset(m, e);
-        for (int which = 0; which < 2; ++which) {
-            const float* src = static_cast<const float*>(which ? host_v : host_m);
-            if (!src) continue;
-            std::vector<float> tmp;
-            if (e.kind == 0) to_lib_conv(src, (int)e.dims[0], (int)e.dims[1], (int)e.dims[2], tmp, m->convs[e.layer].cin_p);
-            else if (e.kind == 1) to_lib_convt(src, (int)e.dims[0], (int)e.dims[1], tmp);
-            else tmp.assign(src, src + e.numel());
-            upload(m, (which ? m->adam_v : m->adam_m) + off, tmp.data(), tmp.size());
-        }
+        m->load_adam(m->entry(name), host_m, host_v, bytes);
     });
 }
 int rfi_model_set_adam_step(rfi_model* m, int64_t step) {
@@ -919,7 +753,8 @@ int rfi_model_debug_tensor(rfi_model* m, const char* name, float* host, size_t h
         if (n_floats) *n_floats = (int64_t)n;
         if (host) {
             RFI_REQUIRE(host_floats >= n, "debug_tensor: host buffer too small");
-            download(m, host, src, n);
+            RFI_CHECK_HIP(hipMemcpyAsync(host, src, n * sizeof(float), hipMemcpyDeviceToHost, m->ctx->stream));
+            RFI_CHECK_HIP(hipStreamSynchronize(m->ctx->stream));
         }
     });
 }

@@ -39,8 +39,6 @@ void DevBuf::free() {
 
 }  // namespace rfi
 
-static size_t align4(size_t v) { return (v + 3) & ~size_t(3); }
-
 rfi_model::~rfi_model() {
     if (!ctx) return;
     ctx->activate();
@@ -71,11 +69,8 @@ void UNetModel::build() {
     RFI_REQUIRE(in_ch > 0 && out_ch > 0 && feat > 0, "UNet: channel counts must be positive");
     RFI_REQUIRE(depth >= 1 && depth <= 6, "UNet: depth must be in [1,6]");
     const int D = depth;
-    convs.clear();
-    ups.clear();
-    size_t off = 0, chan_floats = 0, wd_floats = 0;
     i_bott = 2 * D;
-    auto add_conv = [&](const std::string& prefix, int conv_idx, int bn_idx, int cin, int cout, int ema, int lvl) {
+    auto add = [&](const std::string& prefix, int conv_idx, int bn_idx, int cin, int cout, int ema, int lvl) {
         ConvBN c;
         c.conv_name = prefix + "." + std::to_string(conv_idx);
         c.bn_name = prefix + "." + std::to_string(bn_idx);
@@ -86,114 +81,30 @@ void UNetModel::build() {
         c.cout = cout;
         c.ema_repeats = ema;
         c.level = lvl;
-        c.w_off = off; off = align4(off + (size_t)9 * c.cin_p * cout);
-        c.b_off = off; off = align4(off + cout);
-        c.g_off = off; off = align4(off + cout);
-        c.be_off = off; off = align4(off + cout);
-        chan_floats += align4((size_t)8 * cout);
-        wd_floats += align4((size_t)9 * c.cin_p * cout);
-        convs.push_back(c);
+        add_conv(c);
     };
     int cin = in_ch;
     for (int l = 1; l <= D; ++l) {
         const int cout = feat << (l - 1);
         const std::string p = "encoder" + std::to_string(l) + ".conv.conv";
-        add_conv(p, 0, 1, cin, cout, 2, l);
-        add_conv(p, 3, 4, cout, cout, 2, l);
+        add(p, 0, 1, cin, cout, 2, l);
+        add(p, 3, 4, cout, cout, 2, l);
         cin = cout;
     }
-    add_conv("bottleneck.conv", 0, 1, cin, cin * 2, 1, D + 1);
-    add_conv("bottleneck.conv", 3, 4, cin * 2, cin * 2, 1, D + 1);
+    add("bottleneck.conv", 0, 1, cin, cin * 2, 1, D + 1);
+    add("bottleneck.conv", 3, 4, cin * 2, cin * 2, 1, D + 1);
     cin *= 2;
-    // decoder parameters come in forward order: up, conv1, conv2 per level; to keep `convs`
-    // contiguous the up-convs get their offsets here and the convs right after
+    // decoder parameters come in forward order: up, conv1, conv2 per level
     for (int l = D; l >= 1; --l) {
         const int cout = feat << (l - 1);
-        UpConv u;
-        u.name = "decoder" + std::to_string(l) + ".up";
-        u.cin = cin;
-        u.cout = cout;
-        u.w_off = off; off = align4(off + (size_t)4 * cin * cout);
-        u.b_off = off; off = align4(off + cout);
-        wd_floats += align4((size_t)4 * cin * cout);
-        ups.push_back(u);
+        add_up("decoder" + std::to_string(l) + ".up", cin, cout);
         const std::string p = "decoder" + std::to_string(l) + ".conv.conv";
-        add_conv(p, 0, 1, cin, cout, 1, l);
-        add_conv(p, 3, 4, cout, cout, 1, l);
+        add(p, 0, 1, cin, cout, 1, l);
+        add(p, 3, 4, cout, cout, 1, l);
         cin = cout;
     }
-    head_w_off = off; off = align4(off + (size_t)out_ch * feat);
-    head_b_off = off; off = align4(off + out_ch);
-    n_flat = off;
-
-    // ---- state_dict entry table in the reference's order
-    entries.clear();
-    entry_index.clear();
-    n_params = 0;
-    auto push = [&](Entry e) {
-        entry_index[e.name] = (int)entries.size();
-        if (e.kind == 0 || e.kind == 1 || e.kind == 2 || e.kind == 6) n_params += e.numel();
-        entries.push_back(e);
-    };
-    auto push_conv_entries = [&](int ci) {
-        const ConvBN& c = convs[ci];
-        Entry e;
-        e.layer = ci;
-        e.name = c.conv_name + ".weight"; e.ndim = 4; e.dims[0] = c.cout; e.dims[1] = c.cin; e.dims[2] = 3; e.dims[3] = 3; e.kind = 0; push(e);
-        e = Entry(); e.layer = ci;
-        e.name = c.conv_name + ".bias"; e.ndim = 1; e.dims[0] = c.cout; e.kind = 2; e.which = 0; push(e);
-        e.name = c.bn_name + ".weight"; e.which = 1; push(e);
-        e.name = c.bn_name + ".bias"; e.which = 2; push(e);
-        e.name = c.bn_name + ".running_mean"; e.kind = 3; push(e);
-        e.name = c.bn_name + ".running_var"; e.kind = 4; push(e);
-        e.name = c.bn_name + ".num_batches_tracked"; e.kind = 5; e.ndim = 0; e.dims[0] = 0; push(e);
-    };
-    for (int l = 1; l <= D; ++l) {
-        push_conv_entries(2 * (l - 1));
-        push_conv_entries(2 * (l - 1) + 1);
-    }
-    push_conv_entries(2 * D);
-    push_conv_entries(2 * D + 1);
-    for (int l = D; l >= 1; --l) {
-        const int k = D - l;
-        const UpConv& u = ups[k];
-        Entry e;
-        e.layer = k;
-        e.name = u.name + ".weight"; e.ndim = 4; e.dims[0] = u.cin; e.dims[1] = u.cout; e.dims[2] = 2; e.dims[3] = 2; e.kind = 1; push(e);
-        e = Entry(); e.layer = k;
-        e.name = u.name + ".bias"; e.ndim = 1; e.dims[0] = u.cout; e.kind = 2; e.which = 3; push(e);
-        push_conv_entries(2 * D + 2 + 2 * k);
-        push_conv_entries(2 * D + 2 + 2 * k + 1);
-    }
-    {
-        Entry e;
-        e.name = "final_conv.weight"; e.ndim = 4; e.dims[0] = out_ch; e.dims[1] = feat; e.dims[2] = 1; e.dims[3] = 1; e.kind = 6; push(e);
-        e = Entry();
-        e.name = "final_conv.bias"; e.ndim = 1; e.dims[0] = out_ch; e.kind = 2; e.which = 4; push(e);
-    }
-
-    // ---- device state
-    alloc_state(chan_floats, wd_floats);
-    size_t co = 0, wo = 0;
-    size_t conv_i = 0;
-    // wd_pool sub-allocation must follow the same order as the sizing above
-    for (int l = 1; l <= 2 * D + 2; ++l) {   // encoder + bottleneck convs
-        ConvBN& c = convs[conv_i++];
-        c.chan = chan_pool + co; co += align4((size_t)8 * c.cout);
-        c.wd = wd_pool + wo; wo += align4((size_t)9 * c.cin_p * c.cout);
-    }
-    for (int k = 0; k < D; ++k) {
-        ups[k].wd = wd_pool + wo; wo += align4((size_t)4 * ups[k].cin * ups[k].cout);
-        for (int j = 0; j < 2; ++j) {
-            ConvBN& c = convs[conv_i++];
-            c.chan = chan_pool + co; co += align4((size_t)8 * c.cout);
-            c.wd = wd_pool + wo; wo += align4((size_t)9 * c.cin_p * c.cout);
-        }
-    }
-    adam_step = 0;
-    wd_dirty = true;
-    x3_fresh = false;
-    reset_channel_state();
+    add_head("final_conv", feat);
+    alloc_state();
 }
 
 void UNetModel::set_planes(int P) {
@@ -207,38 +118,6 @@ void UNetModel::set_planes(int P) {
     planesP = P;
     wd_dirty = true;
     pN = 0;                                       // (prepare() again: the two flows of the ResNet-encoder model own different tensors)
-}
-
-// device state of a freshly built parameter table: the flat buffers (zeroed), the per-channel state and dgrad-layout pools
-// (the caller sub-allocates them), the loss scalars
-void rfi_model::alloc_state(size_t chan_floats, size_t wd_floats) {
-    ctx->activate();
-    const size_t bytes = n_flat * sizeof(float);
-    params = static_cast<float*>(ctx->alloc(bytes));
-    grads = static_cast<float*>(ctx->alloc(bytes));
-    adam_m = static_cast<float*>(ctx->alloc(bytes));
-    adam_v = static_cast<float*>(ctx->alloc(bytes));
-    chan_pool = static_cast<float*>(ctx->alloc(chan_floats * sizeof(float)));
-    wd_pool = static_cast<float*>(ctx->alloc(wd_floats * sizeof(float)));
-    d_sums = static_cast<double*>(ctx->alloc(8 * sizeof(double)));
-    d_scalars = static_cast<float*>(ctx->alloc(8 * sizeof(float)));
-    for (float* p : {params, grads, adam_m, adam_v}) RFI_CHECK_HIP(hipMemsetAsync(p, 0, bytes, ctx->stream));
-    RFI_CHECK_HIP(hipMemsetAsync(chan_pool, 0, chan_floats * sizeof(float), ctx->stream));
-    RFI_CHECK_HIP(hipMemsetAsync(d_sums, 0, 8 * sizeof(double), ctx->stream));
-    RFI_CHECK_HIP(hipMemsetAsync(d_scalars, 0, 8 * sizeof(float), ctx->stream));
-}
-
-void rfi_model::reset_channel_state() {
-    for (auto& c : convs) {
-        std::vector<float> ch((size_t)8 * c.cout, 0.0f);
-        for (int i = 0; i < c.cout; ++i) ch[c.cout + i] = 1.0f;                          // running_var = 1
-        if (!c.has_bn)
-            for (int i = 0; i < c.cout; ++i) ch[(size_t)4 * c.cout + i] = 1.0f;          // scale = 1, shift = 0
-        RFI_CHECK_HIP(hipMemcpyAsync(c.chan, ch.data(), ch.size() * sizeof(float), hipMemcpyHostToDevice,
-                                     ctx->stream));
-        RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-        c.nbt = 0;
-    }
 }
 
 // ------------------------------------------------------------------------------------ prepare

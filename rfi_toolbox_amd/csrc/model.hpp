@@ -39,6 +39,8 @@ struct ConvBN {
     float* ws2d3 = nullptr;             // ... and the 3 x bf16 records of both (a launch without them splits a temporary copy
     float* wds2d3 = nullptr;            // and drains the stream to free it: six stalls per step)
     bool has_bn = true;                 // false: Conv+bias -> ReLU (SimpleCNN); scale=1, shift=0 stay fixed
+    bool frozen_bn = false;             // (with has_bn) BatchNorm frozen to its buffers (the backbone): no trainable affine
+    size_t chan_off = 0, wd_off = 0;    // this layer's regions of chan_pool / wd_pool (floats)
     int64_t nbt = 0;                    // num_batches_tracked (host side)
     // device per-channel state: [running_mean | running_var | mean | invstd | scale | shift | c1 | c2]
     float* chan = nullptr;
@@ -50,6 +52,9 @@ struct ConvBN {
     float* shift() const { return chan + 5 * cout; }
     float* c1() const { return chan + 6 * cout; }
     float* c2() const { return chan + 7 * cout; }
+    // a frozen BatchNorm computes no batch statistics: its weight and bias live in the mean / invstd slots
+    float* frozen_weight() const { return mean(); }
+    float* frozen_bias() const { return invstd(); }
     float* wd = nullptr;                // dgrad-layout copy of the weight [9][cin_p][cout]
     float* w3 = nullptr;                // 3 x bf16 records of the forward layout (launch_weights_to_x3)
     float* wd3 = nullptr;               // ... and of the dgrad layout
@@ -65,6 +70,7 @@ struct UpConv {
     int cin = 0, cout = 0;
     size_t w_off = 0, b_off = 0;        // forward layout [4][cout][cin]
     size_t dbias_rec_off = 0;           // this layer's region of UNetModel::dbias_pool (floats)
+    size_t wd_off = 0;                  // ... and of wd_pool
     float* wd = nullptr;                // dgrad layout [4][cin][cout]
     float* w3 = nullptr;                // 3 x bf16 records of both layouts
     float* wd3 = nullptr;
@@ -72,21 +78,40 @@ struct UpConv {
     bf16_t* wBd = nullptr;              // ... and the 2x2 stride-2 contraction of the input gradient
 };
 
+// what a state_dict entry is, which decides where it lives and in what layout
+enum class EntryKind {
+    ConvWeight,      // OIHW <-> the flat buffers' [tap][cout][cin_p] (padded channels stay 0)
+    ConvTWeight,     // IOHW <-> [tap][cout][cin]
+    LinearWeight,    // the head's and the 1x1 convs' [cout][cin][1][1]: the library's [1 tap][cout][cin] as is
+    Bias, BnWeight, BnBias,                                  // flat vectors
+    RunningMean, RunningVar, FrozenBnWeight, FrozenBnBias,   // per-channel state of convs[layer]
+    NumBatchesTracked,                                       // host int64 of convs[layer]
+};
+// parameters live in the flat buffers (trained, counted by num_parameters); the other kinds are buffers
+inline bool is_parameter(EntryKind k) { return k <= EntryKind::BnBias; }
+
 struct Entry {
     std::string name;
+    EntryKind kind = EntryKind::Bias;
     int ndim = 0;
     int64_t dims[4] = {0, 0, 0, 0};
-    int kind = 0;        // 0 conv weight (OIHW), 1 convT weight (IOHW), 2 vector param, 3 running_mean,
-                         // 4 running_var, 5 num_batches_tracked, 6 final weight, 8 / 9 frozen BatchNorm weight / bias (buffers), 7 1x1 conv weight of convs[layer]
-                         // ([cout][cin][1][1] is the library's [1 tap][cout][cin] as is)
-    int layer = -1;      // index into convs / ups; -1 for the head
-    int which = 0;       // vector param: 0 conv bias, 1 bn gamma, 2 bn beta, 3 up bias, 4 head bias
+    int layer = -1;      // index into convs (ConvWeight, per-channel and host entries)
+    size_t off = 0;      // parameters: offset into the flat buffers
     int64_t numel() const {
         int64_t n = 1;
         for (int i = 0; i < ndim; ++i) n *= dims[i];
         return n;
     }
 };
+
+inline size_t align4(size_t v) { return (v + 3) & ~size_t(3); }
+
+// reference layout <-> library layout of a conv / transposed-conv weight (model_params.cpp); cin_p >= cin: library rows
+// are zero-padded to cin_p input channels
+void to_lib_conv(const float* oihw, int cout, int cin, int R, std::vector<float>& out, int cin_p = -1);
+void from_lib_conv(const float* lib, int cout, int cin, int R, float* oihw, int cin_p = -1);
+void to_lib_convt(const float* iohw, int cin, int cout, std::vector<float>& out);     // ConvTranspose2d weight [cin][cout][2][2]
+void from_lib_convt(const float* lib, int cin, int cout, float* iohw);
 
 }  // namespace rfi
 
@@ -195,8 +220,20 @@ struct rfi_model {
     // rfi_model_debug_tensor for names other than logits / dlogits / chan: `n` floats at `src`
     virtual void debug_tensor(const std::string& name, const std::string& base, int idx, bool to_host, const float*& src, size_t& n);
 
-    void alloc_state(size_t chan_floats, size_t wd_floats);    // (build(): flat buffers, pools, loss scalars)
+    // ---- the parameter table (model_params.cpp).  build() registers the layers in the order of the flat buffers, which
+    // is also the state_dict's: each gets its align4'd flat slots, its regions of chan_pool / wd_pool and its entries
+    size_t chan_floats = 0, wd_floats = 0;
+    int add_conv(rfi::ConvBN c);      // (names, shape and flags set) slots w, b, and g, be for a trainable BatchNorm; -> convs index
+    void add_up(const std::string& name, int cin, int cout);   // transposed conv: w, b
+    void add_head(const std::string& name, int cin);           // the final 1x1 conv (out_ch outputs): w, b
+    void alloc_state();               // (end of build()) flat buffers, pools and the layers' pointers into them, loss scalars
     void reset_channel_state();       // running stats 0/1, BN-less layers: scale 1, shift 0
+    const rfi::Entry& entry(const char* name) const;
+    void init_params(uint64_t seed);  // rfi_model_init
+    void load_entry(const rfi::Entry& e, const void* host, size_t bytes);
+    void store_entry(const rfi::Entry& e, void* host, size_t bytes);
+    void store_flat(const float* flat, const rfi::Entry& e, void* host, size_t bytes);   // a parameter's slot of params / grads / adam_m / adam_v
+    void load_adam(const rfi::Entry& e, const void* host_m, const void* host_v, size_t bytes);
     float* buf(int i) { return bufs[i].p; }
     int new_buf() { bufs.emplace_back(); return (int)bufs.size() - 1; }
     rfi::View network_input(const float* x_dev, int n, int h, int w);

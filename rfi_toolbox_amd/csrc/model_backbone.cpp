@@ -22,8 +22,6 @@
 
 using namespace rfi;
 
-static size_t align4(size_t v) { return (v + 3) & ~size_t(3); }
-
 namespace {
 const int kBlocksPerStage[4] = {3, 4, 6, 3};
 }
@@ -33,10 +31,7 @@ void BackboneModel::build() {
                 "ResNet50FPN: base width and FPN channels must be positive multiples of 4");
     depth = 4;
     const int w0 = feat, F = out_ch;
-    convs.clear();
-    ups.clear();
     bb.clear();
-    size_t off = 0, chan_floats = 0, wd_floats = 0;
     auto add = [&](const std::string& cname, const std::string& bname, int cin, int cout, int R, int stride, int lvl, bool bn,
                    bool bias) {
         ConvBN c;
@@ -45,14 +40,8 @@ void BackboneModel::build() {
         c.cin = c.cin_p = cin;
         c.cout = cout;
         c.R = R; c.stride = stride; c.level = lvl;
-        c.has_bn = bn; c.has_bias = bias;
-        c.w_off = off; off = align4(off + (size_t)R * R * cin * cout);
-        c.b_off = off; off = align4(off + cout);
-        c.g_off = c.be_off = 0;
-        chan_floats += align4((size_t)8 * cout);
-        wd_floats += align4((size_t)R * R * cin * cout);
-        convs.push_back(c);
-        return (int)convs.size() - 1;
+        c.has_bn = bn; c.frozen_bn = true; c.has_bias = bias;
+        return add_conv(c);
     };
     add("body.conv1", "body.bn1", in_ch, w0, 7, 2, 1, true, false);          // level = log2 of the OUTPUT stride
     int cin = w0;
@@ -78,40 +67,9 @@ void BackboneModel::build() {
         fpn_inner[i] = add("fpn.inner_blocks." + std::to_string(i) + ".0", "", 4 * (w0 << i), F, 1, 1, i + 2, false, true);
     for (int i = 0; i < 4; ++i)
         fpn_layer[i] = add("fpn.layer_blocks." + std::to_string(i) + ".0", "", F, F, 3, 1, i + 2, false, true);
-    head_w_off = head_b_off = off;
-    n_flat = off;
+    head_w_off = head_b_off = n_flat;     // (no head)
+    alloc_state();
 
-    entries.clear();
-    entry_index.clear();
-    n_params = 0;
-    auto push = [&](Entry e, bool param) {
-        entry_index[e.name] = (int)entries.size();
-        if (param) n_params += e.numel();
-        entries.push_back(e);
-    };
-    for (int ci = 0; ci < (int)convs.size(); ++ci) {
-        const ConvBN& c = convs[ci];
-        Entry e;
-        e.layer = ci;
-        e.name = c.conv_name + ".weight"; e.ndim = 4; e.dims[0] = c.cout; e.dims[1] = c.cin; e.dims[2] = c.R; e.dims[3] = c.R;
-        e.kind = c.R == 1 ? 7 : 0;
-        push(e, true);
-        e = Entry(); e.layer = ci; e.ndim = 1; e.dims[0] = c.cout;
-        if (c.has_bias) { e.name = c.conv_name + ".bias"; e.kind = 2; e.which = 0; push(e, true); }
-        if (c.has_bn) {          // frozen: buffers, not parameters (kinds 8 / 9 / 3 / 4 live in the per-channel state)
-            e.name = c.bn_name + ".weight"; e.kind = 8; push(e, false);
-            e.name = c.bn_name + ".bias"; e.kind = 9; push(e, false);
-            e.name = c.bn_name + ".running_mean"; e.kind = 3; push(e, false);
-            e.name = c.bn_name + ".running_var"; e.kind = 4; push(e, false);
-        }
-    }
-
-    alloc_state(chan_floats, wd_floats);
-    size_t co = 0, wo = 0;
-    for (auto& c : convs) {
-        c.chan = chan_pool + co; co += align4((size_t)8 * c.cout);
-        c.wd = wd_pool + wo; wo += align4((size_t)c.R * c.R * c.cin * c.cout);
-    }
     // 2x2 forms of the stride-2 3x3 filters, 4x tiled affine coefficients of their inputs, identity vectors
     const size_t cmax = (size_t)32 * w0;
     size_t need = 2 * cmax + 16;
@@ -143,15 +101,11 @@ void BackboneModel::build() {
         RFI_CHECK_HIP(hipMemcpyAsync(rs_ones, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
         RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     }
-    adam_step = 0;
-    wd_dirty = true;
-    x3_fresh = false;
-    reset_channel_state();            // running stats 0 / 1; BN-less layers: scale 1, shift 0
     for (auto& c : convs)             // frozen gamma = 1, beta = 0 until loaded (slots 2 and 3 of the per-channel state)
         if (c.has_bn) {
             std::vector<float> g((size_t)2 * c.cout, 0.0f);
             for (int i = 0; i < c.cout; ++i) g[i] = 1.0f;
-            RFI_CHECK_HIP(hipMemcpyAsync(c.mean(), g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+            RFI_CHECK_HIP(hipMemcpyAsync(c.frozen_weight(), g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
             RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
         }
     frozen_dirty = true;
@@ -240,7 +194,7 @@ void BackboneModel::prepare_shape(int n, int h, int w) {
 void BackboneModel::refresh_backbone() {
     if (frozen_dirty) {
         for (auto& c : convs)
-            if (c.has_bn) launch_bn_eval_coeffs(ctx, c.cout, c.mean(), c.invstd(), c.running_mean(), c.running_var(), c.scale(), c.shift());
+            if (c.has_bn) launch_bn_eval_coeffs(ctx, c.cout, c.frozen_weight(), c.frozen_bias(), c.running_mean(), c.running_var(), c.scale(), c.shift());
         for (auto& k : bb)
             if (k.stride == 2) {                  // the 2x2 conv reads the space-to-depth of conv1's RAW output: coefficients x 4
                 const ConvBN& c1 = convs[k.c1];

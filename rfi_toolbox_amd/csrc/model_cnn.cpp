@@ -12,14 +12,9 @@
 
 using namespace rfi;
 
-static size_t align4(size_t v) { return (v + 3) & ~size_t(3); }
-
 void Cnn3Model::build() {
     RFI_REQUIRE(in_ch > 0 && out_ch > 0 && feat > 0, "SimpleCNN: channel counts must be positive");
     RFI_REQUIRE(feat % 4 == 0, "SimpleCNN: width must be a multiple of 4 (16-byte NHWC pixels)");
-    convs.clear();
-    ups.clear();
-    size_t off = 0, chan_floats = 0, wd_floats = 0;
     const char* names[2] = {"encoder.0", "encoder.2"};
     for (int i = 0; i < 2; ++i) {
         ConvBN c;
@@ -28,54 +23,10 @@ void Cnn3Model::build() {
         c.cin = i == 0 ? in_ch : feat;
         c.cin_p = i == 0 ? (int)align4((size_t)in_ch) : feat;
         c.cout = feat;
-        c.w_off = off; off = align4(off + (size_t)9 * c.cin_p * c.cout);
-        c.b_off = off; off = align4(off + c.cout);
-        c.g_off = c.be_off = 0;
-        chan_floats += align4((size_t)8 * c.cout);
-        wd_floats += align4((size_t)9 * c.cin_p * c.cout);
-        convs.push_back(c);
+        add_conv(c);
     }
-    head_w_off = off; off = align4(off + (size_t)out_ch * feat);
-    head_b_off = off; off = align4(off + out_ch);
-    n_flat = off;
-
-    entries.clear();
-    entry_index.clear();
-    n_params = 0;
-    auto push = [&](Entry e) {
-        entry_index[e.name] = (int)entries.size();
-        n_params += e.numel();
-        entries.push_back(e);
-    };
-    for (int i = 0; i < 2; ++i) {
-        Entry e;
-        e.layer = i;
-        e.name = convs[i].conv_name + ".weight"; e.ndim = 4;
-        e.dims[0] = convs[i].cout; e.dims[1] = convs[i].cin; e.dims[2] = 3; e.dims[3] = 3; e.kind = 0;
-        push(e);
-        e = Entry(); e.layer = i;
-        e.name = convs[i].conv_name + ".bias"; e.ndim = 1; e.dims[0] = convs[i].cout; e.kind = 2; e.which = 0;
-        push(e);
-    }
-    {
-        Entry e;
-        e.name = "decoder.0.weight"; e.ndim = 4; e.dims[0] = out_ch; e.dims[1] = feat; e.dims[2] = 1; e.dims[3] = 1; e.kind = 6;
-        push(e);
-        e = Entry();
-        e.name = "decoder.0.bias"; e.ndim = 1; e.dims[0] = out_ch; e.kind = 2; e.which = 4;
-        push(e);
-    }
-
-    alloc_state(chan_floats, wd_floats);
-    size_t co = 0, wo = 0;
-    for (auto& c : convs) {
-        c.chan = chan_pool + co; co += align4((size_t)8 * c.cout);
-        c.wd = wd_pool + wo; wo += align4((size_t)9 * c.cin_p * c.cout);
-    }
-    adam_step = 0;
-    wd_dirty = true;
-        x3_fresh = false;
-    reset_channel_state();
+    add_head("decoder.0", feat);
+    alloc_state();
 }
 
 void Cnn3Model::prepare_shape(int n, int h, int w) {

@@ -23,8 +23,6 @@
 
 using namespace rfi;
 
-static size_t align4(size_t v) { return (v + 3) & ~size_t(3); }
-
 void ConvHeadModel::build() {
     RFI_REQUIRE(in_ch > 0 && in_ch % 4 == 0, "MaskHead: in_channels must be a positive multiple of 4 (16-byte NHWC pixels)");
     RFI_REQUIRE(out_ch > 0 && depth >= 1 && depth <= 8, "MaskHead: out_channels > 0, 1..8 conv layers");
@@ -35,81 +33,16 @@ void ConvHeadModel::build() {
     focal_alpha = -1.0f;
     focal_gamma = 0.0f;
     const int L = depth, C = in_ch;
-    convs.clear();
-    ups.clear();
-    size_t off = 0, chan_floats = 0, wd_floats = 0;
     for (int i = 0; i < L; ++i) {
         ConvBN c;
         c.conv_name = up ? "mask_fcn" + std::to_string(i + 1) : "conv." + std::to_string(i) + ".0";
         c.has_bn = false;
         c.cin = c.cin_p = c.cout = C;
-        c.w_off = off; off = align4(off + (size_t)9 * C * C);
-        c.b_off = off; off = align4(off + C);
-        c.g_off = c.be_off = 0;
-        chan_floats += align4((size_t)8 * C);
-        wd_floats += align4((size_t)9 * C * C);
-        convs.push_back(c);
+        add_conv(c);
     }
-    if (up) {
-        UpConv u;
-        u.name = "conv5_mask";
-        u.cin = u.cout = C;
-        u.w_off = off; off = align4(off + (size_t)4 * C * C);
-        u.b_off = off; off = align4(off + C);
-        wd_floats += align4((size_t)4 * C * C);
-        ups.push_back(u);
-    }
-    head_w_off = off; off = align4(off + (size_t)out_ch * C);
-    head_b_off = off; off = align4(off + out_ch);
-    n_flat = off;
-
-    entries.clear();
-    entry_index.clear();
-    n_params = 0;
-    auto push = [&](Entry e) {
-        entry_index[e.name] = (int)entries.size();
-        n_params += e.numel();
-        entries.push_back(e);
-    };
-    for (int i = 0; i < L; ++i) {
-        Entry e;
-        e.layer = i;
-        e.name = convs[i].conv_name + ".weight"; e.ndim = 4; e.dims[0] = C; e.dims[1] = C; e.dims[2] = 3; e.dims[3] = 3; e.kind = 0;
-        push(e);
-        e = Entry(); e.layer = i;
-        e.name = convs[i].conv_name + ".bias"; e.ndim = 1; e.dims[0] = C; e.kind = 2; e.which = 0;
-        push(e);
-    }
-    if (up) {
-        Entry e;
-        e.layer = 0;
-        e.name = "conv5_mask.weight"; e.ndim = 4; e.dims[0] = C; e.dims[1] = C; e.dims[2] = 2; e.dims[3] = 2; e.kind = 1;
-        push(e);
-        e = Entry(); e.layer = 0;
-        e.name = "conv5_mask.bias"; e.ndim = 1; e.dims[0] = C; e.kind = 2; e.which = 3;
-        push(e);
-    }
-    {
-        const std::string hn = up ? "mask_fcn_logits" : "head";
-        Entry e;
-        e.name = hn + ".weight"; e.ndim = 4; e.dims[0] = out_ch; e.dims[1] = C; e.dims[2] = 1; e.dims[3] = 1; e.kind = 6;
-        push(e);
-        e = Entry();
-        e.name = hn + ".bias"; e.ndim = 1; e.dims[0] = out_ch; e.kind = 2; e.which = 4;
-        push(e);
-    }
-
-    alloc_state(chan_floats, wd_floats);
-    size_t co = 0, wo = 0;
-    for (auto& c : convs) {
-        c.chan = chan_pool + co; co += align4((size_t)8 * c.cout);
-        c.wd = wd_pool + wo; wo += align4((size_t)9 * c.cin_p * c.cout);
-    }
-    if (up) ups[0].wd = wd_pool + wo;
-    adam_step = 0;
-    wd_dirty = true;
-    x3_fresh = false;
-    reset_channel_state();
+    if (up) add_up("conv5_mask", C, C);
+    add_head(up ? "mask_fcn_logits" : "head", C);
+    alloc_state();
 }
 
 void ConvHeadModel::prepare_shape(int n, int h, int w) {

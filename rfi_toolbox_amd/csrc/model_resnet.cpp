@@ -21,16 +21,11 @@
 
 using namespace rfi;
 
-static size_t align4(size_t v) { return (v + 3) & ~size_t(3); }
-
 void UNetModel::build_resnet() {
     RFI_REQUIRE(in_ch > 0 && out_ch > 0 && feat > 0 && feat % 4 == 0, "UNetResNet18: init_features must be a positive multiple of 4");
     depth = 4;
     const int D = depth;
-    convs.clear();
-    ups.clear();
     blocks.clear();
-    size_t off = 0, chan_floats = 0, wd_floats = 0;
     auto add = [&](const std::string& cname, const std::string& bname, int cin, int cout, int R, int stride, int lvl, bool bias) {
         ConvBN c;
         c.conv_name = cname;
@@ -39,15 +34,7 @@ void UNetModel::build_resnet() {
         c.cin_p = convs.empty() ? (int)align4((size_t)cin) : cin;
         c.cout = cout;
         c.R = R; c.stride = stride; c.level = lvl; c.has_bias = bias;
-        c.ema_repeats = 1;
-        c.w_off = off; off = align4(off + (size_t)R * R * c.cin_p * cout);
-        c.b_off = off; off = align4(off + cout);
-        c.g_off = off; off = align4(off + cout);
-        c.be_off = off; off = align4(off + cout);
-        chan_floats += align4((size_t)8 * cout);
-        wd_floats += align4((size_t)R * R * c.cin_p * cout);
-        convs.push_back(c);
-        return (int)convs.size() - 1;
+        return add_conv(c);
     };
     add("stem.0", "stem.1", in_ch, feat, 3, 1, 1, false);
     int cin = feat;
@@ -71,81 +58,15 @@ void UNetModel::build_resnet() {
     cin *= 2;
     for (int l = D; l >= 1; --l) {
         const int cout = feat << (l - 1);
-        UpConv u;
-        u.name = "decoder" + std::to_string(l) + ".up";
-        u.cin = cin;
-        u.cout = cout;
-        u.w_off = off; off = align4(off + (size_t)4 * cin * cout);
-        u.b_off = off; off = align4(off + cout);
-        wd_floats += align4((size_t)4 * cin * cout);
-        ups.push_back(u);
+        add_up("decoder" + std::to_string(l) + ".up", cin, cout);
         const std::string p = "decoder" + std::to_string(l) + ".conv.conv";
         add(p + ".0", p + ".1", cin, cout, 3, 1, l, true);
         add(p + ".3", p + ".4", cout, cout, 3, 1, l, true);
         cin = cout;
     }
-    head_w_off = off; off = align4(off + (size_t)out_ch * feat);
-    head_b_off = off; off = align4(off + out_ch);
-    n_flat = off;
+    add_head("final_conv", feat);
+    alloc_state();
 
-    // ---- state_dict entries in the oracle module's order
-    entries.clear();
-    entry_index.clear();
-    n_params = 0;
-    auto push = [&](Entry e) {
-        entry_index[e.name] = (int)entries.size();
-        if (e.kind == 0 || e.kind == 1 || e.kind == 2 || e.kind == 6 || e.kind == 7) n_params += e.numel();
-        entries.push_back(e);
-    };
-    auto push_conv = [&](int ci) {
-        const ConvBN& c = convs[ci];
-        Entry e;
-        e.layer = ci;
-        e.name = c.conv_name + ".weight"; e.ndim = 4; e.dims[0] = c.cout; e.dims[1] = c.cin; e.dims[2] = c.R; e.dims[3] = c.R;
-        e.kind = c.R == 1 ? 7 : 0;
-        push(e);
-        e = Entry(); e.layer = ci; e.ndim = 1; e.dims[0] = c.cout; e.kind = 2;
-        if (c.has_bias) { e.name = c.conv_name + ".bias"; e.which = 0; push(e); }
-        e.name = c.bn_name + ".weight"; e.which = 1; push(e);
-        e.name = c.bn_name + ".bias"; e.which = 2; push(e);
-        e.name = c.bn_name + ".running_mean"; e.kind = 3; push(e);
-        e.name = c.bn_name + ".running_var"; e.kind = 4; push(e);
-        e.name = c.bn_name + ".num_batches_tracked"; e.kind = 5; e.ndim = 0; e.dims[0] = 0; push(e);
-    };
-    for (int ci = 0; ci < i_bott + 2; ++ci) push_conv(ci);
-    for (int k = 0; k < D; ++k) {
-        const UpConv& u = ups[k];
-        Entry e;
-        e.layer = k;
-        e.name = u.name + ".weight"; e.ndim = 4; e.dims[0] = u.cin; e.dims[1] = u.cout; e.dims[2] = 2; e.dims[3] = 2; e.kind = 1; push(e);
-        e = Entry(); e.layer = k;
-        e.name = u.name + ".bias"; e.ndim = 1; e.dims[0] = u.cout; e.kind = 2; e.which = 3; push(e);
-        push_conv(i_bott + 2 + 2 * k);
-        push_conv(i_bott + 2 + 2 * k + 1);
-    }
-    {
-        Entry e;
-        e.name = "final_conv.weight"; e.ndim = 4; e.dims[0] = out_ch; e.dims[1] = feat; e.dims[2] = 1; e.dims[3] = 1; e.kind = 6; push(e);
-        e = Entry();
-        e.name = "final_conv.bias"; e.ndim = 1; e.dims[0] = out_ch; e.kind = 2; e.which = 4; push(e);
-    }
-
-    // ---- device state
-    alloc_state(chan_floats, wd_floats);
-    size_t co = 0, wo = 0;
-    for (int ci = 0; ci < i_bott + 2; ++ci) {
-        ConvBN& c = convs[ci];
-        c.chan = chan_pool + co; co += align4((size_t)8 * c.cout);
-        c.wd = wd_pool + wo; wo += align4((size_t)c.R * c.R * c.cin_p * c.cout);
-    }
-    for (int k = 0; k < D; ++k) {
-        ups[k].wd = wd_pool + wo; wo += align4((size_t)4 * ups[k].cin * ups[k].cout);
-        for (int jj = 0; jj < 2; ++jj) {
-            ConvBN& c = convs[i_bott + 2 + 2 * k + jj];
-            c.chan = chan_pool + co; co += align4((size_t)8 * c.cout);
-            c.wd = wd_pool + wo; wo += align4((size_t)9 * c.cin_p * c.cout);
-        }
-    }
     // derived filters of the stride-2 convs (2x2 form + its dgrad layout) and identity scale / shift vectors
     size_t wneed = 0;
     for (auto& c : convs)
@@ -169,10 +90,6 @@ void UNetModel::build_resnet() {
         RFI_CHECK_HIP(hipMemcpyAsync(rs_ones, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
         RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     }
-    adam_step = 0;
-    wd_dirty = true;
-    x3_fresh = false;
-    reset_channel_state();
 }
 
 void UNetModel::prepare_resnet(int n, int h, int w) {
