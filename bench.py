@@ -13,8 +13,13 @@ target (on CPU the reference's autocast / GradScaler are off, train_m
 float32 MFMA; bf16 = a BUILDER-CHOSEN reduced-precision mode (bfloat16 activations in HBM and bf16 MFMA operands,
 float32 accumulation / BatchNorm / loss / optimiser).  It is NOT the reference's arithmetic: on a GPU the reference
 autocasts to float16 with a GradScaler and clips the still-scaled gradients.  At N = 1 the default U-Net line also
-carries the bf16 measurement of the same step as the companion object "bfloat16".  --dump-outputs DIR also writes the
-loss and model state of the last timed step as .npy files, so that two builds can be compared output for output.
+carries the bf16 measurement of the same step as the companion object "bfloat16" under --full.  --dump-outputs DIR also
+writes the loss and model state of the last timed step as .npy files, so that two builds can be compared output for output.
+
+A plain run sets up, warms up, times the K steps, writes its outputs (--dump-outputs) and prints the line.  Everything
+else the benchmark measures is behind --full: the sustained sample after the timed region, the per-kernel-family profile
+steps and the roofline computed from them, the bfloat16 companion line and the CPU baselines.  --sustain-steps,
+--profile-steps and --launch-csv still ask for their own measurement in a plain run.
 """
 import argparse
 import json
@@ -677,12 +682,7 @@ def run_maskrcnn(args, ctx, D, rank, local_rank, world, n_ranks_seen):
         beat("done")
         D.shutdown()
         return
-    P = max(args.profile_steps, 1)
     ms_per_step = wall * 1e3 / args.steps
-    peak = PEAK_BY_DTYPE[args.dtype]
-    roof, _ = roofline_of(launches, fam, P, args.dtype, "maskrcnn", peak)
-    kernel_ms = sum(f["ms"] for f in fam.values()) / P
-    step_flops = sum(f["flops"] for f in fam.values()) / P
     out = {"metric": "training patches/sec (128x128x3)", "value": round(world * B * args.steps / wall, 2), "unit": "patches/s",
            "n_gpus": world, "n_ranks_seen": n_ranks_seen, "fallback": os.environ.get("RFI_BENCH_FALLBACK"), "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16" if args.dtype.startswith("bf16") else "f32",
@@ -693,17 +693,23 @@ def run_maskrcnn(args, ctx, D, rank, local_rank, world, n_ranks_seen):
                                   "builder-defined detector, SURVEY 8a A11)",
                       "arithmetic": ARITHMETIC[args.dtype], "global_batch": B * world, "patch": [S, S, 3], "parallelism": f"dp{world}",
                       "params": int(sum(m.num_parameters() for m in det.models()))},
-           "roofline": roof,
-           "step": {"algorithmic_gflop_per_patch": round(step_flops / B / 1e9, 3),
-                    "tflops_whole_step": round(step_flops / (ms_per_step * 1e-3) / 1e12, 3),
-                    "kernel_ms_per_step_serial": round(kernel_ms, 3),
-                    "host_bookkeeping_ms_per_step": round(max(ms_per_step - kernel_ms, 0.0), 3),
-                    "note": "the box bookkeeping between the stages (top-k, samplers, proposal selection, RoI lists) runs on the "
-                            "device; host_bookkeeping = max(0, ms_per_step - kernel_ms_per_step_serial), where the serial sum "
-                            "counts the side-stream weight gradients one after the other",
-                    "final_losses": {k: round(float(v), 5) for k, v in losses.items()}},
-           "families": per_family(fam, P)}
-    if world == 1 and not args.no_cpu_baseline:
+           "step": {"final_losses": {k: round(float(v), 5) for k, v in losses.items()}}}
+    if args.profile_steps > 0:
+        P = args.profile_steps
+        roof, _ = roofline_of(launches, fam, P, args.dtype, "maskrcnn", PEAK_BY_DTYPE[args.dtype])
+        kernel_ms = sum(f["ms"] for f in fam.values()) / P
+        step_flops = sum(f["flops"] for f in fam.values()) / P
+        out["roofline"] = roof
+        out["step"] = {"algorithmic_gflop_per_patch": round(step_flops / B / 1e9, 3),
+                       "tflops_whole_step": round(step_flops / (ms_per_step * 1e-3) / 1e12, 3),
+                       "kernel_ms_per_step_serial": round(kernel_ms, 3),
+                       "host_bookkeeping_ms_per_step": round(max(ms_per_step - kernel_ms, 0.0), 3),
+                       "note": "the box bookkeeping between the stages (top-k, samplers, proposal selection, RoI lists) runs on "
+                               "the device; host_bookkeeping = max(0, ms_per_step - kernel_ms_per_step_serial), where the serial "
+                               "sum counts the side-stream weight gradients one after the other",
+                       **out["step"]}
+        out["families"] = per_family(fam, P)
+    if world == 1 and args.full and not args.no_cpu_baseline:
         log("cpu baseline ...")
         out["cpu_baseline"] = cpu_baseline_maskrcnn(S, B)
     if outputs is not None:
@@ -747,16 +753,22 @@ def main():
                          "precision, not the reference's arithmetic; f32mfma: native float32 MFMA; "
                          "f32planes: the f32 arithmetic on pre-split plane tensors; bf16regs: bf16 operands rounded in "
                          "registers, float32 storage (round 1's bf16 mode)")
-    ap.add_argument("--profile-steps", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything, not just the headline: the sustained sample, the per-kernel-family profile and "
+                         "roofline, the bfloat16 companion line of the default N = 1 U-Net run and the CPU baselines")
+    ap.add_argument("--profile-steps", type=int, default=None,
+                    help="steps of each per-kernel-family profile pass (default: 3 with --full, 0 otherwise)")
     ap.add_argument("--sustain-steps", type=int, default=None,
-                    help="steps of the sustained sample run after the timed region (default: 300 for the 128x128 workloads, 0 otherwise)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="steps of the sustained sample run after the timed region (default with --full: 300 for the 128x128 "
+                         "workloads, 0 otherwise; 0 without --full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-bf16-line", "--no-float32-line", dest="no_companion", action="store_true",
-                    help="skip the bfloat16 measurement the default N = 1 U-Net line carries next to the float32 one")
-    ap.add_argument("--launch-csv", default=None, help="write the per-launch HIP-event profile here")
+                    help="with --full: skip the bfloat16 measurement the default N = 1 U-Net line carries next to the float32 one")
+    ap.add_argument("--launch-csv", default=None, help="write the per-launch HIP-event profile here (needs the profile steps)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last of them computed (the loss and the updated model state; "
-                         "with the bfloat16 companion line its step too, as bfloat16.*) as DIR/<name>.npy in float32 / "
+                         "for the default N = 1 U-Net run the bfloat16 companion's step too, as bfloat16.*, whose steps then "
+                         "run also without --full) as DIR/<name>.npy in float32 / "
                          "float64, at most 64 MB in all (a fixed, seeded sample of larger arrays beyond that); the inputs "
                          "and initial weights are seeded, so two builds run with the same arguments can be compared")
     ap.add_argument("--dry-run", action="store_true",
@@ -764,6 +776,10 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.profile_steps is None:
+        args.profile_steps = 3 if args.full else 0
+    if args.launch_csv and args.profile_steps < 1:
+        ap.error("--launch-csv needs the profile steps: add --full or --profile-steps N")
 
     if args.gpus > 1 and not os.environ.get("RFI_BENCH_WORKER"):
         raise SystemExit(Supervisor(args.gpus, sys.argv[1:]).run())
@@ -780,7 +796,7 @@ def main():
     if args.features is None:
         args.features = 64 if args.workload in ("cnn3", "resnet", "resnet1024") else 32
     if args.sustain_steps is None:
-        args.sustain_steps = 300 if args.workload in ("unet", "cnn3") else 0
+        args.sustain_steps = 300 if args.full and args.workload in ("unet", "cnn3") else 0
     default_dtype = args.dtype is None
     if default_dtype:
         args.dtype = "bf16" if args.workload in ("unet1024", "resnet1024") else "f32"    # (configs[2] names bf16)
@@ -846,7 +862,8 @@ def main():
 
     res = measure(model, ctx, D, d_x, d_y, hp, args, args.dtype, rank, args.launch_csv)
     second = None
-    if world == 1 and default_dtype and args.workload == "unet" and not args.no_companion:
+    # the bfloat16 companion is measured under --full; a plain run with --dump-outputs runs its steps for the dump alone
+    if world == 1 and default_dtype and args.workload == "unet" and not args.no_companion and (args.full or args.dump_outputs):
         del model
         model2 = build_model()                    # the same step from the same initial weights in the bf16 mode
         second = measure(model2, ctx, D, d_x, d_y, hp, args, "bf16", rank)
@@ -868,18 +885,20 @@ def main():
     def line_of(r, dtype):
         ms_per_step = r["wall"] * 1e3 / args.steps
         peak = PEAK_BY_DTYPE[dtype]
-        roof, _ = roofline_of(r["launches"], r["fam"], max(args.profile_steps, 1), dtype, args.workload, peak)
         step_tflops = step_flops / (ms_per_step * 1e-3) / 1e12
-        return {"value": round(world * B * args.steps / r["wall"], 2), "ms_per_step": round(ms_per_step, 4),
+        line = {"value": round(world * B * args.steps / r["wall"], 2), "ms_per_step": round(ms_per_step, 4),
                 "dtype": "bf16" if dtype.startswith("bf16") else "f32", "arithmetic": ARITHMETIC[dtype],
-                "roofline": roof,
-                "sustained": r["sustained"],
                 "step": {"algorithmic_gflop_per_patch": round(step_flops / B / 1e9, 3),
                          "tflops_whole_step": round(step_tflops, 3),
                          "frac_of_instruction_peak": round(step_tflops / peak, 4),
-                         "hip_event_ms_per_step": round(r["ev_ms"] / args.steps, 4), "final_loss": round(r["loss"], 6)},
-                "families": per_family(r["fam"], max(args.profile_steps, 1)),
-                "families_overlapped": per_family(r["fam_ov"], max(args.profile_steps, 1))}
+                         "hip_event_ms_per_step": round(r["ev_ms"] / args.steps, 4), "final_loss": round(r["loss"], 6)}}
+        if r["sustained"] is not None:
+            line["sustained"] = r["sustained"]
+        if args.profile_steps > 0:
+            line["roofline"], _ = roofline_of(r["launches"], r["fam"], args.profile_steps, dtype, args.workload, peak)
+            line["families"] = per_family(r["fam"], args.profile_steps)
+            line["families_overlapped"] = per_family(r["fam_ov"], args.profile_steps)
+        return line
 
     main_line = line_of(res, args.dtype)
     out = {
@@ -903,18 +922,14 @@ def main():
                    "arithmetic": main_line["arithmetic"],
                    "global_batch": B * world, "patch": [S, S, 3], "parallelism": f"dp{world}",
                    "params": n_params},
-        "roofline": main_line["roofline"],
-        "sustained": main_line["sustained"],
-        "step": main_line["step"],
-        "families": main_line["families"],
-        "families_overlapped": main_line["families_overlapped"],
     }
-    if second is not None:
+    out.update((k, main_line[k]) for k in ("roofline", "sustained", "step", "families", "families_overlapped") if k in main_line)
+    if second is not None and args.full:
         out["bfloat16"] = line_of(second, "bf16")
         out["bfloat16"]["note"] = ("the same step, same inputs and initial weights, with --dtype bf16: a builder-chosen "
                                    "reduced-precision mode (bf16 storage and MFMA operands), NOT the reference's arithmetic and "
                                    "not the parity target; the top-level line is the float32 one")
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         log("cpu baseline ...")
         out["cpu_baseline"] = cpu_baseline(args.workload, args.features, S, B)
     if res["outputs"] is not None:

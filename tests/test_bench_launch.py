@@ -155,6 +155,17 @@ def test_bench_rejects_a_step_count_below_one():
     assert r.returncode == 2 and "--steps must be at least 1" in r.stderr, r.stderr[-1500:]
 
 
+def test_bench_rejects_a_launch_csv_without_profile_steps(tmp_path):
+    """A plain run has no profile steps: asking it for their per-launch CSV is an error up front, not a missing file."""
+    csv = tmp_path / "launches.csv"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--launch-csv", str(csv)],
+                       env=_clean_env(), capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--launch-csv needs the profile steps" in r.stderr, r.stderr[-1500:]
+    assert not csv.exists()
+    out = _run(args=("--full", "--launch-csv", str(csv)))          # --full brings the profile steps (dry run: none taken)
+    assert out["dry_run"] is True
+
+
 def test_bench_dump_outputs_stays_within_its_budget_with_a_fixed_sample(tmp_path):
     """--dump-outputs: every array becomes <name>.npy; over the byte budget the large arrays are cut to a sample of their
     elements that is the same in every run, small arrays and scalars stay whole."""

@@ -178,3 +178,32 @@ def test_bench_dump_outputs_is_the_state_after_its_timed_steps(tmp_path):
             got = np.load(tmp_path / f"{prefix}{k}.npy")
             assert got.dtype in (np.float32, np.float64), (k, got.dtype)
             np.testing.assert_array_equal(got, v.numpy(), err_msg=prefix + k)
+
+
+def test_bench_plain_line_is_the_headline_and_full_adds_the_rest():
+    """A plain bench.py run times its steps and prints the headline alone; --full adds the sustained sample, the profile
+    (roofline, kernel families) and the bfloat16 companion line to the same headline fields."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--batch", "4", "--warmup", "2", "--steps", "3"]
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--sustain-steps", "20", "--profile-steps", "1"])):
+        r = subprocess.run(base + extra, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(out) == 1, r.stdout
+        lines[name] = json.loads(out[0])
+    for d in lines.values():
+        assert d["metric"] == "training patches/sec (128x128x3)" and d["unit"] == "patches/s" and d["higher_is_better"] is True
+        assert d["dtype"] == "f32" and d["steps"] == 3 and d["warmup"] == 2
+        assert d["value"] > 0 and abs(d["value"] - 4 * 1e3 / d["ms_per_step"]) <= 1e-3 * d["value"]
+        assert np.isfinite(d["step"]["final_loss"])
+    plain, full = lines["plain"], lines["full"]
+    assert not {"sustained", "roofline", "families", "families_overlapped", "bfloat16", "cpu_baseline"} & set(plain)
+    assert full["sustained"]["steps"] == 20 and "roofline" in full and full["families"] and full["families_overlapped"]
+    assert full["bfloat16"]["dtype"] == "bf16" and "roofline" in full["bfloat16"] and full["bfloat16"]["families"]
+    assert plain["step"]["final_loss"] == full["step"]["final_loss"]      # the same K timed steps from the same seeds

@@ -4,7 +4,7 @@ O=$R/gpurun_out/r4m
 mkdir -p $O
 export TMPDIR=/tmp
 cd /tmp
-B="python3 $R/bench.py"
+B="python3 $R/bench.py --full"
 T="timeout -k 10"
 $T 400 $B --workload maskrcnn > $O/bench_maskrcnn.json 2> $O/bench.err
 $T 300 $B --workload resnet1024 --no-cpu-baseline > $O/bench_resnet1024.json 2>> $O/bench.err

@@ -16,7 +16,7 @@ O=$R/gpurun_out/$TAG
 mkdir -p "$O"
 export TMPDIR=/tmp
 cd /tmp
-B="python3 $R/bench.py"
+B="python3 $R/bench.py --full"
 T="timeout -k 10"
 P="--no-cpu-baseline --profile-steps 0 --steps 10 --warmup 3"
 Q="--no-cpu-baseline --profile-steps 0 --steps 5 --warmup 2"
