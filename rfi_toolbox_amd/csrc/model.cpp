@@ -303,8 +303,9 @@ void rfi_model::side_rebuild_wd() {
     if (!wd_side_todo) return;
     wd_side_todo = false;
     if (!wd_ready) RFI_CHECK_HIP(hipEventCreateWithFlags(&wd_ready, hipEventDisableTiming));
-    side_begin();                                 // the side stream waits for everything on main so far (the optimiser step)
-    struct Back { rfi_ctx* c; ~Back() { c->stream = c->main_stream; } } back{ctx};
+    // the side stream waits for everything on main so far (the optimiser step); no end(): wd_ready marks this work, and the
+    // scope puts the context's stream back
+    SideScope side(this);
     launch_weight_to_dgrad_batched(ctx, static_cast<const RelayoutDesc*>(relayout_descs), relayout_n, params,
                                    wd_pool, relayout_bytes, relayout_tiles);
     if (planesP) refresh_model_weights(2);
@@ -421,7 +422,7 @@ void UNetModel::refresh_model_weights(int which) {
 
 // filters of every 3x3 stride-1 layer in MFMA B-operand order with three planes (conv_ws.hip), both directions, rebuilt
 // with the other derived copies after each optimiser step by ONE batched launch.  Callers find them by the layer's
-// float32 filter pointer (ws_set(ConvArgs) looks up ConvArgs::w), which every model's conv helper already passes around
+// float32 filter pointer (set_filters -> ws_set looks up ConvArgs::w)
 void rfi_model::refresh_ws_weights(int P, int which) {
     if (P != ws_P) {                  // another arithmetic: its copies have another size
         if (ws_pool) { ctx->release(ws_pool); ws_pool = nullptr; }
@@ -511,48 +512,102 @@ void rfi_model::refresh_ws_weights(int P, int which) {
     if (which == 2 && ws_n > ws_n_fwd) launch_weights_to_wb(ctx, descs + ws_n_fwd, ws_n - ws_n_fwd, ws_bytes - ws_bytes_fwd);
 }
 
-// ------------------------------------------------------------------------------------ forward
-namespace {
-
-struct Shape { int N, H, W; };
-
-void run_conv_bn(rfi_model* m, ConvBN& c, View in, InXform xf, Shape s, float* Y, bool train) {
+// ------------------------------------------------------------------------------------ shared launches
+ConvArgs rfi_model::conv_same(View x, InXform xf, Shape s, int R, int pad, int cin, int cout, const float* w, const float* w3,
+                              const float* bias, float* y) const {
     ConvArgs a;
-    a.x = in;
+    a.x = x;
     a.N = s.N; a.H = s.H; a.W = s.W; a.Hin = s.H; a.Win = s.W;
-    a.Cin = c.cin_p; a.Cout = c.cout;
-    a.w = m->params + c.w_off;
-    a.w3 = m->use_w3() ? c.w3 : nullptr;
-    m->ws_set(a);
-    a.bias = m->params + c.b_off;
-    a.y = MutView{Y, c.cout};
+    a.Cin = cin; a.Cout = cout;
+    set_filters(a, w, w3);            // (null w3: the kernel launcher splits a temporary copy)
+    a.bias = bias;
+    a.y = MutView{y, cout};
     a.Hout = s.H; a.Wout = s.W;
-    a.R = 3; a.S = 1; a.pad = 1;
+    a.R = R; a.S = 1; a.pad = pad;
     a.xf = xf;
-    a.algo_flops = 2.0 * s.N * s.H * s.W * 9.0 * c.cin * c.cout;
-    float* ws = m->buf(m->ws_red);
+    return a;
+}
+
+WgradArgs rfi_model::wgrad_same(View x, InXform xf_x, const float* dy, Shape s, int R, int pad, int cin, int cout,
+                                float* dw) const {
+    WgradArgs wa;
+    wa.xop = x;
+    wa.yop = View{dy, cout};
+    wa.xf_x = xf_x;
+    wa.N = s.N; wa.H = s.H; wa.W = s.W; wa.Hx = s.H; wa.Wx = s.W;
+    wa.Cx = cin; wa.Cy = cout;
+    wa.R = R; wa.S = 1; wa.pad = pad;
+    wa.dw = dw;
+    wa.tap_stride = (int64_t)cin * cout;
+    wa.sy = cin; wa.sx = 1;
+    set_wgrad(wa);
+    return wa;
+}
+
+void rfi_model::conv_bn(ConvBN& c, View in, InXform xf, Shape s, const float* w, const float* w3, int R, int pad, int cin,
+                        float* Y, bool train, double flops) {
+    ConvArgs a = conv_same(in, xf, s, R, pad, cin, c.cout, w, w3, c.has_bias ? params + c.b_off : nullptr, Y);
+    a.algo_flops = flops;
+    float* ws = buf(ws_red);
     if (train) {            // batch statistics come out of the conv epilogue (no second pass over Y)
         a.stats = reinterpret_cast<double*>(ws);
         a.stats_max_records = (int)(bn_stats_ws_floats(c.cout) / ((size_t)c.cout * 4));
     }
-    a.bf16 = m->compute_bf16;
-    a.bf16x3 = m->compute_x3;
-    launch_conv(m->ctx, a);
+    launch_conv(ctx, a);
     const int64_t M = (int64_t)s.N * s.H * s.W;
     if (train) {
-        if (a.stats_records == 0) launch_bn_stats(m->ctx, Y, M, c.cout, ws);   // direct-kernel fallback
-        launch_bn_finalize(m->ctx, ws, M, c.cout, m->params + c.g_off, m->params + c.be_off,
-                           c.running_mean(), c.running_var(), c.ema_repeats, c.mean(), c.invstd(),
-                           c.scale(), c.shift(), nullptr, a.stats_records);
+        if (a.stats_records == 0) launch_bn_stats(ctx, Y, M, c.cout, ws);   // direct-kernel fallback
+        launch_bn_finalize(ctx, ws, M, c.cout, params + c.g_off, params + c.be_off, c.running_mean(), c.running_var(),
+                           c.ema_repeats, c.mean(), c.invstd(), c.scale(), c.shift(), nullptr, a.stats_records);
         c.nbt += c.ema_repeats;
     } else {
-        launch_bn_eval_coeffs(m->ctx, c.cout, m->params + c.g_off, m->params + c.be_off, c.running_mean(),
-                              c.running_var(), c.scale(), c.shift());
+        launch_bn_eval_coeffs(ctx, c.cout, params + c.g_off, params + c.be_off, c.running_mean(), c.running_var(),
+                              c.scale(), c.shift());
     }
 }
 
+// ConvTranspose2d(k2, s2) forward: ONE 1x1 launch over the input grid whose four filter groups (zgroups) land on the four
+// pixels of each 2 x 2 output block
+ConvArgs rfi_model::convt_args(const UpConv& u, View x, InXform xf, Shape s) const {
+    ConvArgs a;
+    a.x = x;
+    a.N = s.N; a.H = s.H; a.W = s.W; a.Hin = s.H; a.Win = s.W;
+    a.Cin = u.cin; a.Cout = u.cout;
+    set_filters(a, params + u.w_off, u.w3);
+    a.bias = params + u.b_off;
+    a.Hout = 2 * s.H; a.Wout = 2 * s.W;
+    a.osy = 2; a.osx = 2;
+    a.R = 1; a.S = 1; a.pad = 0;
+    a.zgroups = 4;
+    a.xf = xf;
+    return a;
+}
 
-}  // namespace
+void rfi_model::convt_backward(const UpConv& u, View dup, View x, InXform xf, Shape s, float* dx) {
+    WgradArgs wa;
+    wa.xop = dup;
+    wa.yop = x;
+    wa.xf_y = xf;
+    wa.N = s.N; wa.H = s.H; wa.W = s.W; wa.Hx = 2 * s.H; wa.Wx = 2 * s.W;
+    wa.Cx = u.cout; wa.Cy = u.cin;
+    wa.R = 2; wa.S = 2; wa.pad = 0;
+    wa.dw = grads + u.w_off;
+    wa.tap_stride = (int64_t)u.cin * u.cout;
+    wa.sy = 1; wa.sx = u.cin;          // -> [tap][cout][cin]
+    set_wgrad(wa);
+    wgrad_on_side(wa, nullptr);
+    ConvArgs a;
+    a.x = dup;
+    a.N = s.N; a.H = s.H; a.W = s.W; a.Hin = 2 * s.H; a.Win = 2 * s.W;
+    a.Cin = u.cout; a.Cout = u.cin;
+    set_filters(a, u.wd, u.wd3);
+    a.y = MutView{dx, u.cin};
+    a.Hout = s.H; a.Wout = s.W;
+    a.R = 2; a.S = 2; a.pad = 0;
+    launch_conv(ctx, a);
+}
+
+// ------------------------------------------------------------------------------------ forward
 
 // the first conv sees the input with its channels zero-padded to a multiple of 4 (16-byte pixels),
 // so the 3-channel stem runs on the same MFMA kernels as every other layer
@@ -572,15 +627,18 @@ void rfi_model::forward(const float* x_dev, int n, int h, int w, bool train_mode
 void UNetModel::forward_pass(const float* x_dev, int n, int h, int w, bool train_mode) {
     if (planesP) return forward_planes(x_dev, n, h, w, train_mode);
     const int D = depth, IB = i_bott;
+    auto run_conv_bn = [&](ConvBN& c, View in, InXform xf, Shape s, float* Y) {
+        conv_bn(c, in, xf, s, params + c.w_off, c.w3, 3, 1, c.cin_p, Y, train_mode, 2.0 * s.N * s.H * s.W * 9.0 * c.cin * c.cout);
+    };
     View cur = network_input(x_dev, n, h, w);
     if (resnet_encoder) cur = forward_resnet_encoder(cur, n, h, w, train_mode);
     else for (int l = 1; l <= D; ++l) {
         Shape s{n, h >> (l - 1), w >> (l - 1)};
         ConvBN& c1 = convs[2 * (l - 1)];
         ConvBN& c2 = convs[2 * (l - 1) + 1];
-        run_conv_bn(this, c1, cur, InXform{}, s, buf(encY1[l]), train_mode);
+        run_conv_bn(c1, cur, InXform{}, s, buf(encY1[l]));
         if (l == 1) side_rebuild_wd();
-        run_conv_bn(this, c2, View{buf(encY1[l]), c1.cout}, bn_xf(c1), s, buf(encY2[l]), train_mode);
+        run_conv_bn(c2, View{buf(encY1[l]), c1.cout}, bn_xf(c1), s, buf(encY2[l]));
         // one pass writes the pooled tensor and the skip (the activated output in the decoder's concat buffer).  Writing the
         // skip on the side stream under the next level's convs measured slower: 6.69 against 6.64 ms per step (round 4) --
         // the second read of Y and the skip write next to the convs cost them more than the 45 us the main stream saves
@@ -592,8 +650,8 @@ void UNetModel::forward_pass(const float* x_dev, int n, int h, int w, bool train
         Shape s{n, h >> D, w >> D};
         ConvBN& c1 = convs[IB];
         ConvBN& c2 = convs[IB + 1];
-        run_conv_bn(this, c1, cur, InXform{}, s, buf(bottY1), train_mode);
-        run_conv_bn(this, c2, View{buf(bottY1), c1.cout}, bn_xf(c1), s, buf(bottY2), train_mode);
+        run_conv_bn(c1, cur, InXform{}, s, buf(bottY1));
+        run_conv_bn(c2, View{buf(bottY1), c1.cout}, bn_xf(c1), s, buf(bottY2));
     }
     const float* prevY = buf(bottY2);
     ConvBN* prevBN = &convs[IB + 1];
@@ -602,27 +660,13 @@ void UNetModel::forward_pass(const float* x_dev, int n, int h, int w, bool train
         UpConv& u = ups[k];
         Shape sin{n, h >> l, w >> l};
         Shape s{n, h >> (l - 1), w >> (l - 1)};
-        ConvArgs a;
-        a.x = View{prevY, u.cin};
-        a.N = sin.N; a.H = sin.H; a.W = sin.W; a.Hin = sin.H; a.Win = sin.W;
-        a.Cin = u.cin; a.Cout = u.cout;
-        a.w = params + u.w_off;
-        a.w3 = use_w3() ? u.w3 : nullptr;
-        ws_set(a);
-        a.bias = params + u.b_off;
+        ConvArgs a = convt_args(u, View{prevY, u.cin}, bn_xf(*prevBN), sin);
         a.y = MutView{buf(concat[l]), 2 * u.cout};
-        a.Hout = s.H; a.Wout = s.W;
-        a.osy = 2; a.osx = 2;
-        a.R = 1; a.S = 1; a.pad = 0;
-        a.zgroups = 4;
-        a.xf = bn_xf(*prevBN);
-        a.bf16 = compute_bf16;
-        a.bf16x3 = compute_x3;
         launch_conv(ctx, a);
         ConvBN& c1 = convs[IB + 2 + 2 * k];
         ConvBN& c2 = convs[IB + 2 + 2 * k + 1];
-        run_conv_bn(this, c1, View{buf(concat[l]), 2 * u.cout}, InXform{}, s, buf(decY1[l]), train_mode);
-        run_conv_bn(this, c2, View{buf(decY1[l]), c1.cout}, bn_xf(c1), s, buf(decY2[l]), train_mode);
+        run_conv_bn(c1, View{buf(concat[l]), 2 * u.cout}, InXform{}, s, buf(decY1[l]));
+        run_conv_bn(c2, View{buf(decY1[l]), c1.cout}, bn_xf(c1), s, buf(decY2[l]));
         prevY = buf(decY2[l]);
         prevBN = &c2;
     }
@@ -762,15 +806,6 @@ void rfi_model::exchange_join() {
 
 namespace {
 
-// launches inside a SideScope go to the side stream; if one throws, the context's stream is put back
-struct SideScope {
-    rfi_model* m;
-    bool ended = false;
-    explicit SideScope(rfi_model* model, hipEvent_t after = nullptr) : m(model) { m->side_begin_after(after); }
-    void end() { m->side_end(); ended = true; }
-    ~SideScope() { if (!ended) m->ctx->stream = m->ctx->main_stream; }
-};
-
 // given dA (grad w.r.t. the ACTIVATED output of conv c, overwritten with dY), produce dW/db/dgamma/
 // dbeta into the grad buffer and, if dx != null, the gradient w.r.t. the conv's (activated) input.
 // `have_records` > 0: the BatchNorm-backward sums of this layer already sit in the workspace (the kernel that
@@ -798,38 +833,14 @@ void backward_conv_bn(UNetModel* m, ConvBN& c, float* dA, const float* Y, View i
     launch_bn_bwd_apply(ctx, dA, Y, M, c.cout, c.scale(), c.shift(), c.mean(), c.invstd(),
                         m->params + c.g_off, c.c1(), c.c2(), m->dbias_deferred ? m->dbias_pool + c.dbias_rec_off : ws,
                         m->grads + c.b_off, m->act_slope, nullptr, 0, 0, dy_done, !m->dbias_deferred, head_dl, head_w);
-    WgradArgs wa;
-    wa.xop = in;
-    wa.yop = View{dA, c.cout};
-    wa.xf_x = in_xf;
-    wa.N = s.N; wa.H = s.H; wa.W = s.W; wa.Hx = s.H; wa.Wx = s.W;
-    wa.Cx = c.cin_p; wa.Cy = c.cout;
-    wa.R = 3; wa.S = 1; wa.pad = 1;
-    wa.dw = m->grads + c.w_off;
-    wa.tap_stride = (int64_t)c.cin_p * c.cout;
-    wa.sy = c.cin_p; wa.sx = 1;
+    WgradArgs wa = m->wgrad_same(in, in_xf, dA, s, 3, 1, c.cin_p, c.cout, m->grads + c.w_off);
     wa.algo_flops = 2.0 * s.N * s.H * s.W * 9.0 * c.cin * c.cout;
-    wa.slab = m->buf(m->ws_slab);
-    wa.slab_floats = m->bufs[m->ws_slab].n;
-    wa.bf16 = m->compute_bf16;
-    wa.bf16x3 = m->compute_x3;
     if (!dx) {
         m->wgrad_on_side(wa, dy_done);
         return;
     }
-    ConvArgs a;
-    a.x = View{dA, c.cout};
-    a.N = s.N; a.H = s.H; a.W = s.W; a.Hin = s.H; a.Win = s.W;
-    a.Cin = c.cout; a.Cout = c.cin;     // dx exists only for layers whose cin == cin_p
-    a.w = c.wd;
-    a.w3 = m->use_w3() ? c.wd3 : nullptr;
-    m->ws_set(a);
-    a.bias = nullptr;
-    a.y = MutView{dx, c.cin};
-    a.Hout = s.H; a.Wout = s.W;
-    a.R = 3; a.S = 1; a.pad = 1;
-    a.bf16 = m->compute_bf16;
-    a.bf16x3 = m->compute_x3;
+    // (dx exists only for layers whose cin == cin_p)
+    ConvArgs a = m->conv_same(View{dA, c.cout}, InXform{}, s, 3, 1, c.cout, c.cin, c.wd, c.wd3, nullptr, dx);
     a.done = m->next_fork_event();      // the weight gradient starts when this kernel completes
     launch_conv(ctx, a);
     m->wgrad_on_side(wa, a.done_used ? a.done : nullptr, !a.done_used);
@@ -903,40 +914,7 @@ void UNetModel::backward_pass(const float* x_dev, const uint8_t* labels_dev, int
             launch_channel_sum(ctx, dUp, (int64_t)s.N * s.H * s.W, u.cout, defer ? dbias_pool + u.dbias_rec_off : buf(ws_red),
                                grads + u.b_off, !defer);
         }
-        WgradArgs wa;
-        wa.xop = dUp;
-        wa.yop = View{prevY, u.cin};
-        wa.xf_y = bn_xf(prevBN);
-        wa.N = sin.N; wa.H = sin.H; wa.W = sin.W; wa.Hx = s.H; wa.Wx = s.W;
-        wa.Cx = u.cout; wa.Cy = u.cin;
-        wa.R = 2; wa.S = 2; wa.pad = 0;
-        wa.dw = grads + u.w_off;
-        wa.tap_stride = (int64_t)u.cin * u.cout;
-        wa.sy = 1; wa.sx = u.cin;          // -> [tap][cout][cin]
-        wa.slab = buf(ws_slab);
-        wa.slab_floats = bufs[ws_slab].n;
-        wa.bf16 = compute_bf16;
-        wa.bf16x3 = compute_x3;
-        {
-            SideScope side(this);
-            launch_wgrad(ctx, wa);
-            side.end();
-        }
-        ConvArgs a;
-        a.x = dUp;
-        a.N = sin.N; a.H = sin.H; a.W = sin.W; a.Hin = s.H; a.Win = s.W;
-        a.Cin = u.cout; a.Cout = u.cin;
-        a.w = u.wd;
-        a.w3 = use_w3() ? u.wd3 : nullptr;
-        ws_set(a);
-        a.bias = nullptr;
-        float* dprev = (l == D) ? buf(gBottA) : buf(gA[l + 1]);
-        a.y = MutView{dprev, u.cin};
-        a.Hout = sin.H; a.Wout = sin.W;
-        a.R = 2; a.S = 2; a.pad = 0;
-        a.bf16 = compute_bf16;
-        a.bf16x3 = compute_x3;
-        launch_conv(ctx, a);
+        convt_backward(u, dUp, View{prevY, u.cin}, bn_xf(prevBN), sin, (l == D) ? buf(gBottA) : buf(gA[l + 1]));
         // gradients of decoder level l (and, for l = 1, of the head) are complete: exchange them now
         bucket_ready(u.w_off, l == 1 ? n_flat : ups[k + 1].w_off);
     }
@@ -1005,8 +983,7 @@ void rfi_model::apply(const rfi_hyper& hp, float grad_scale) {
 
 // ------------------------------------------------------------------------------------ entry-point hooks
 void rfi_model::set_compute_dtype(int dtype) {
-    compute_bf16 = dtype == 1 || dtype == 4;
-    compute_x3 = dtype == 2 || dtype == 3;
+    arith = dtype == 1 || dtype == 4 ? Arith::BF16 : dtype == 2 || dtype == 3 ? Arith::X3 : Arith::F32;
 }
 void UNetModel::set_compute_dtype(int dtype) {
     rfi_model::set_compute_dtype(dtype);

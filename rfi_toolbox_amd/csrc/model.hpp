@@ -106,6 +106,12 @@ struct Entry {
 
 inline size_t align4(size_t v) { return (v + 3) & ~size_t(3); }
 
+struct Shape { int N, H, W; };
+
+// BatchNorm-apply + activation of layer c as a load transform for its consumers (slope 0 = ReLU; a layer without
+// BatchNorm keeps scale 1, shift 0)
+inline InXform act_of(const ConvBN& c, float slope = 0.0f) { return act_xform(c.scale(), c.shift(), slope); }
+
 // reference layout <-> library layout of a conv / transposed-conv weight (model_params.cpp); cin_p >= cin: library rows
 // are zero-padded to cin_p input channels
 void to_lib_conv(const float* oihw, int cout, int cin, int R, std::vector<float>& out, int cin_p = -1);
@@ -123,9 +129,11 @@ struct rfi_model {
     int in_ch = 0, out_ch = 0, feat = 0, depth = 0;
     int out_scale = 1;                // output map / input map in each direction (the mask head's transposed conv: 2)
     bool training = true;
-    bool compute_bf16 = false;        // conv / wgrad MFMAs on bf16-rounded operands (fp32 storage + accumulate)
-    bool compute_x3 = true;           // DEFAULT: float32 contractions by 3 x bf16 pieces (float32-level accuracy)
-    bool use_w3() const { return compute_x3; }   // who reads the pre-split filter records
+    // the arithmetic of the conv / wgrad MFMAs (float32 storage + accumulate): native float32, bf16-rounded operands, or
+    // float32 operands as three bf16 pieces (DEFAULT: float32-level accuracy)
+    enum class Arith { F32, BF16, X3 };
+    Arith arith = Arith::X3;
+    bool use_w3() const { return arith == Arith::X3; }   // who reads the pre-split filter records
     // plane data flow (model_planes.cpp; set by the U-Net family only): 0 off (round-1 kernels on float32 tensors), 1 bf16
     // activations (the bfloat16 compute mode), 3 float32 as three bf16 pieces
     int planesP = 0;
@@ -153,7 +161,7 @@ struct rfi_model {
     double ws_bytes = 0;
     std::unordered_map<const float*, const rfi::bf16_t*> ws_by_w;    // float32 filter pointer (ConvArgs::w) -> the same filters for conv_ws / gemm_ws
     int ws_P = 0;                     // planes of the copies in ws_pool: 3 (float32 by 3 x bf16), 1 (bf16 operands), 0 (none built)
-    int ws_need() const { return planesP ? 0 : compute_x3 ? 3 : compute_bf16 ? 1 : 0; }
+    int ws_need() const { return planesP ? 0 : arith == Arith::X3 ? 3 : arith == Arith::BF16 ? 1 : 0; }
     // the copy of filter `w` for the wave-specialised kernels in the current arithmetic (null: none)
     void ws_set(rfi::ConvArgs& a) const {
         auto it = ws_by_w.find(a.w);
@@ -161,6 +169,22 @@ struct rfi_model {
         a.wB3 = ws_P == 3 ? p : nullptr;
         a.wB1 = ws_P == 1 ? p : nullptr;
         if (a.wB3 && x3_skipped.count(a.w)) a.w3 = nullptr;   // (no pre-split records are kept for this layer)
+    }
+    // The one place that maps `arith` onto a launch: its filters w (with their pre-split records w3, read in the 3 x bf16
+    // arithmetic only, and the wave-specialised copy) and the MFMA mode ...
+    void set_filters(rfi::ConvArgs& a, const float* w, const float* w3) const {
+        a.w = w;
+        a.w3 = use_w3() ? w3 : nullptr;
+        ws_set(a);                    // (after w and w3: it looks up w and may clear w3)
+        a.bf16 = arith == Arith::BF16;
+        a.bf16x3 = arith == Arith::X3;
+    }
+    // ... and a weight gradient's slab workspace and MFMA mode
+    void set_wgrad(rfi::WgradArgs& wa) const {
+        wa.slab = bufs[ws_slab].p;
+        wa.slab_floats = bufs[ws_slab].n;
+        wa.bf16 = arith == Arith::BF16;
+        wa.bf16x3 = arith == Arith::X3;
     }
     // set by the plain U-Net: it keeps no pre-split (3 x bf16) filter records for the layers the wave-specialised kernels
     // cover, since at its shapes they never decline.  The other models (detector backbone on 4 x 4 maps, heads) keep every
@@ -243,6 +267,22 @@ struct rfi_model {
     virtual bool wd_split_ok() const { return false; }
     virtual void refresh_model_weights(int which) {}
 
+    // ---- launches on float32 tensors the networks share (model.cpp); algo_flops, stats and done stay the caller's
+    // a stride-1 conv whose output grid is its input's (s): R x R taps, `pad`, filters w [tap][cout][cin], output [M][cout]
+    rfi::ConvArgs conv_same(rfi::View x, rfi::InXform xf, rfi::Shape s, int R, int pad, int cin, int cout, const float* w,
+                            const float* w3, const float* bias, float* y) const;
+    // its weight gradient from dy ([M][cout]) into dw [tap][cout][cin]
+    rfi::WgradArgs wgrad_same(rfi::View x, rfi::InXform xf_x, const float* dy, rfi::Shape s, int R, int pad, int cin, int cout,
+                              float* dw) const;
+    // conv_same into Y with the BatchNorm statistics of layer c from its epilogue + finalize (train), or its eval coefficients
+    void conv_bn(rfi::ConvBN& c, rfi::View in, rfi::InXform xf, rfi::Shape s, const float* w, const float* w3, int R, int pad,
+                 int cin, float* Y, bool train, double flops);
+    // ConvTranspose2d(k2, s2) over the input grid s: the forward launch but its output (y / y16: the caller's) ...
+    rfi::ConvArgs convt_args(const rfi::UpConv& u, rfi::View x, rfi::InXform xf, rfi::Shape s) const;
+    // ... and its backward pass from dup (the gradient w.r.t. its output): the weight gradient on the side stream, then the
+    // input gradient into dx [M][u.cin].  (The bias gradient is the caller's.)
+    void convt_backward(const rfi::UpConv& u, rfi::View dup, rfi::View x, rfi::InXform xf, rfi::Shape s, float* dx);
+
     // backward-pass overlap: wgrad launches go to the context's side stream (see model.cpp)
     int side_seq = 0;
     int side_bound = 2;               // main may run this many side launches ahead (0: no bound -- nothing the side work reads is rewritten before side_join)
@@ -268,6 +308,18 @@ struct rfi_model {
     void exchange_join();
 };
 
+namespace rfi {
+// launches inside a SideScope go to the side stream (behind `after`, or behind everything enqueued on the main stream so
+// far); end() marks the side launch.  Left without end() (a throw) the context's stream is put back
+struct SideScope {
+    rfi_model* m;
+    bool ended = false;
+    explicit SideScope(rfi_model* model, hipEvent_t after = nullptr) : m(model) { m->side_begin_after(after); }
+    void end() { m->side_end(); ended = true; }
+    ~SideScope() { if (!ended) m->ctx->stream = m->ctx->main_stream; }
+};
+}  // namespace rfi
+
 // U-Net (models/unet.py; model.cpp) and, with resnet_encoder, the U-Net with a ResNet-18-style encoder (SURVEY 8a A10;
 // model_resnet.cpp).  Both share the decoder, the head, the loss and the plane data flow (model_planes.cpp)
 struct UNetModel : rfi_model {
@@ -289,7 +341,7 @@ struct UNetModel : rfi_model {
     int i_bott = 0;                   // index of the bottleneck's first conv in `convs` (decoder convs follow it)
     float act_slope = 0.0f;           // 0: ReLU; > 0: LeakyReLU(negative_slope) (UNetDifferentActivation)
     // BN-apply + activation of layer c as a load transform for its consumers (slope 0 = ReLU)
-    rfi::InXform bn_xf(const rfi::ConvBN& c) const { return rfi::act_xform(c.scale(), c.shift(), act_slope); }
+    rfi::InXform bn_xf(const rfi::ConvBN& c) const { return rfi::act_of(c, act_slope); }
     // convs: enc1.c1, enc1.c2, ..., encD.c2, bott.c1, bott.c2, decD.c1, decD.c2, ..., dec1.c2; ups: decD.up ... dec1.up
     std::vector<int> encY1, encY2, concat, pool, decY1, decY2, gA, gB, dconcat, dpool;
     std::vector<int> gAe, gBe;        // float32 U-Net path: the encoder phase's gradient tensors (gA / gB are the decoder's)
@@ -403,7 +455,7 @@ struct ConvHeadModel : rfi_model {
     int mkU = -1, mkGU = -1, head_wd = -1, head_w3 = -1, head_wd3 = -1;
     // the 1x1 head as a GEMM on the matrix cores (conv kernels forward / input gradient, weight-gradient kernel) instead of the
     // per-pixel VALU kernels written for one output channel: where it has enough outputs (the RPN head's 5 A = 20)
-    bool head_on_mfma() const { return out_ch >= 8 && out_ch % 4 == 0 && in_ch % 4 == 0 && (compute_x3 || compute_bf16); }
+    bool head_on_mfma() const { return out_ch >= 8 && out_ch % 4 == 0 && in_ch % 4 == 0 && arith != Arith::F32; }
     float* head_in() { return upsample ? buf(mkU) : buf(mkY[depth - 1]); }     // what the 1x1 head reads ...
     float* head_din() { return upsample ? buf(mkGU) : buf(mkG[depth - 1]); }   // ... and the gradient it sends down
 };

@@ -219,71 +219,27 @@ void BackboneModel::refresh_backbone() {
 
 namespace {
 
-struct Sh { int N, H, W; };
-
-void conv(rfi_model* m, View in, InXform xf, Sh s, int Hin, int Win, const float* w, const float* w3, const float* bias, int cin,
-          int cout, int R, int S, int pad, float* Y) {
-    // a 1x1 conv does not see the image structure: on small maps (W < 32) run it on the same pixels laid out as one
-    // [M / 32] x 32 image, so that the 32-pixel-wide tiles of the kernels are full instead of mostly padding
+// a 1x1 conv does not see the image structure: on small maps (W < 32) run it on the same pixels laid out as one
+// [M / 32] x 32 image, so that the 32-pixel-wide tiles of the kernels are full instead of mostly padding
+Shape flat_1x1(Shape s, int R) {
     const int64_t M = (int64_t)s.N * s.H * s.W;
-    if (R == 1 && S == 1 && Hin == s.H && Win == s.W && s.W < 32 && M % 32 == 0) {
-        s = Sh{1, (int)(M / 32), 32};
-        Hin = s.H; Win = s.W;
-    }
-    ConvArgs a;
-    a.x = in;
-    a.N = s.N; a.H = s.H; a.W = s.W; a.Hin = Hin; a.Win = Win;
-    a.Cin = cin; a.Cout = cout;
-    a.w = w;
-    a.w3 = m->use_w3() ? w3 : nullptr;
-    m->ws_set(a);
-    a.bias = bias;
-    a.y = MutView{Y, cout};
-    a.Hout = s.H; a.Wout = s.W;
-    a.R = R; a.S = S; a.pad = pad;
-    a.xf = xf;
-    a.bf16 = m->compute_bf16;
-    a.bf16x3 = m->compute_x3;
+    return R == 1 && s.W < 32 && M % 32 == 0 ? Shape{1, (int)(M / 32), 32} : s;
+}
+// every conv of the backbone is stride 1 on its own output grid s (stride 2: the 2x2 form on the space-to-depth input)
+void conv(rfi_model* m, View in, InXform xf, Shape s, const float* w, const float* w3, const float* bias, int cin, int cout, int R,
+          int pad, float* Y) {
+    ConvArgs a = m->conv_same(in, xf, flat_1x1(s, R), R, pad, cin, cout, w, w3, bias, Y);
     launch_conv(m->ctx, a);
 }
-// RAII: launches between construction and end() go to the side stream (model.cpp, side_begin / side_end)
-struct SideScopeB {
-    rfi_model* m;
-    bool ended = false;
-    explicit SideScopeB(rfi_model* model) : m(model) { m->side_begin(); }
-    void end() { m->side_end(); ended = true; }
-    ~SideScopeB() { if (!ended) m->ctx->stream = m->ctx->main_stream; }
-};
-
 // (the caller decides the stream: backward_backbone puts the weight gradients on the side stream)
-void wgrad(rfi_model* m, View x, InXform xf_x, const float* dY, int cy, int cx, Sh s, int Hx, int Wx, int R, int S, int pad, float* dw) {
-    const int64_t M = (int64_t)s.N * s.H * s.W;
-    if (R == 1 && S == 1 && Hx == s.H && Wx == s.W && s.W < 32 && M % 32 == 0) {       // (as in conv())
-        s = Sh{1, (int)(M / 32), 32};
-        Hx = s.H; Wx = s.W;
-    }
-    WgradArgs wa;
-    wa.xop = x;
-    wa.yop = View{dY, cy};
-    wa.xf_x = xf_x;
-    wa.N = s.N; wa.H = s.H; wa.W = s.W; wa.Hx = Hx; wa.Wx = Wx;
-    wa.Cx = cx; wa.Cy = cy;
-    wa.R = R; wa.S = S; wa.pad = pad;
-    wa.dw = dw;
-    wa.tap_stride = (int64_t)cx * cy;
-    wa.sy = cx; wa.sx = 1;
-    wa.slab = m->buf(m->ws_slab);
-    wa.slab_floats = m->bufs[m->ws_slab].n;
-    wa.bf16 = m->compute_bf16;
-    wa.bf16x3 = m->compute_x3;
-    launch_wgrad(m->ctx, wa);
+WgradArgs wgrad(const rfi_model* m, View x, InXform xf_x, const float* dY, int cy, int cx, Shape s, int R, int pad, float* dw) {
+    return m->wgrad_same(x, xf_x, dY, flat_1x1(s, R), R, pad, cx, cy, dw);
 }
 // dA (gradient w.r.t. act(Y * scale + shift), or w.r.t. the affine output when slope = 1) -> dY in place: dA * scale * act'
 void affine_bwd(BackboneModel* m, const ConvBN& c, float* dA, const float* Y, int64_t M, float slope) {
     launch_bn_bwd_apply(m->ctx, dA, Y, M, c.cout, c.scale(), c.shift(), m->rs_zeros, m->rs_ones, c.scale(), m->rs_zeros, m->rs_zeros,
                         m->buf(m->ws_red), nullptr, slope);
 }
-InXform act_of(const ConvBN& c) { return InXform{c.scale(), c.shift(), 1, 0.0f}; }
 
 }  // namespace
 
@@ -296,32 +252,30 @@ void BackboneModel::forward_pass(const float* x_dev, int n, int h, int w, bool) 
         launch_im2col(ctx, x_dev, n, h, w, in_ch, 7, 2, 3, h / 2, w / 2, Kp, buf(bCol));
         launch_w_pack(ctx, params + c.w_off, 49, c.cout, in_ch, Kp, buf(bWp), true);
         if (use_w3()) launch_weights_to_x3(ctx, buf(bWp), 1, c.cout, Kp, bb_stem_w3);
-        conv(this, View{buf(bCol), Kp}, InXform{}, Sh{n, h / 2, w / 2}, h / 2, w / 2, buf(bWp), bb_stem_w3, nullptr, Kp, c.cout, 1, 1, 0, buf(bY0));
+        conv(this, View{buf(bCol), Kp}, InXform{}, Shape{n, h / 2, w / 2}, buf(bWp), bb_stem_w3, nullptr, Kp, c.cout, 1, 0, buf(bY0));
         launch_maxpool3_fwd(ctx, buf(bY0), n, h / 2, w / 2, c.cout, c.scale(), c.shift(), buf(bP0), reinterpret_cast<unsigned*>(buf(bArg)));
     }
     const float* a_in = buf(bP0);
     for (auto& k : bb) {
         ConvBN &c1 = convs[k.c1], &c2 = convs[k.c2], &c3 = convs[k.c3];
-        const Sh si{n, h >> k.lvl_in, w >> k.lvl_in}, so{n, h >> k.lvl, w >> k.lvl};
-        conv(this, View{a_in, k.cin}, InXform{}, si, si.H, si.W, params + c1.w_off, c1.w3, nullptr, k.cin, k.width, 1, 1, 0, buf(k.Y1));
+        const Shape si{n, h >> k.lvl_in, w >> k.lvl_in}, so{n, h >> k.lvl, w >> k.lvl};
+        conv(this, View{a_in, k.cin}, InXform{}, si, params + c1.w_off, c1.w3, nullptr, k.cin, k.width, 1, 0, buf(k.Y1));
         if (k.stride == 2) {
             launch_s2d(ctx, buf(k.Y1), n, si.H, si.W, k.width, buf(k.xs1));
-            conv(this, View{buf(k.xs1), 4 * k.width}, InXform{k.sc4, k.sh4, 1, 0.0f}, so, so.H, so.W, c2.ws2d, c2.ws2d3, nullptr, 4 * k.width,
-                 k.width, 2, 1, 1, buf(k.Y2));
+            conv(this, View{buf(k.xs1), 4 * k.width}, InXform{k.sc4, k.sh4, 1, 0.0f}, so, c2.ws2d, c2.ws2d3, nullptr, 4 * k.width,
+                 k.width, 2, 1, buf(k.Y2));
         } else {
-            conv(this, View{buf(k.Y1), k.width}, act_of(c1), so, so.H, so.W, params + c2.w_off, c2.w3, nullptr, k.width, k.width, 3, 1, 1,
-                 buf(k.Y2));
+            conv(this, View{buf(k.Y1), k.width}, act_of(c1), so, params + c2.w_off, c2.w3, nullptr, k.width, k.width, 3, 1, buf(k.Y2));
         }
-        conv(this, View{buf(k.Y2), k.width}, act_of(c2), so, so.H, so.W, params + c3.w_off, c3.w3, nullptr, k.width, k.cout, 1, 1, 0, buf(k.Y3));
+        conv(this, View{buf(k.Y2), k.width}, act_of(c2), so, params + c3.w_off, c3.w3, nullptr, k.width, k.cout, 1, 0, buf(k.Y3));
         const int64_t M = (int64_t)so.N * so.H * so.W;
         if (k.cd >= 0) {
             ConvBN& cd = convs[k.cd];
             if (k.stride == 2) {
                 launch_s2d(ctx, a_in, n, si.H, si.W, k.cin, buf(k.xsA));
-                conv(this, View{buf(k.xsA), 4 * k.cin}, InXform{}, so, so.H, so.W, params + cd.w_off, cd.w3, nullptr, k.cin, k.cout, 1, 1, 0,
-                     buf(k.Yd));
+                conv(this, View{buf(k.xsA), 4 * k.cin}, InXform{}, so, params + cd.w_off, cd.w3, nullptr, k.cin, k.cout, 1, 0, buf(k.Yd));
             } else {
-                conv(this, View{a_in, k.cin}, InXform{}, so, so.H, so.W, params + cd.w_off, cd.w3, nullptr, k.cin, k.cout, 1, 1, 0, buf(k.Yd));
+                conv(this, View{a_in, k.cin}, InXform{}, so, params + cd.w_off, cd.w3, nullptr, k.cin, k.cout, 1, 0, buf(k.Yd));
             }
             launch_bn_add_relu(ctx, buf(k.Y3), c3.scale(), c3.shift(), buf(k.Yd), cd.scale(), cd.shift(), M, k.cout,
                                MutView{buf(k.A), k.cout}, MutView{});
@@ -336,13 +290,13 @@ void BackboneModel::forward_pass(const float* x_dev, int n, int h, int w, bool) 
     for (int s = 0; s < 4; ++s) { bi += kBlocksPerStage[s]; last[s] = bi; }
     for (int i = 3; i >= 0; --i) {
         const BBlock& k = bb[last[i]];
-        const Sh s{n, h >> (i + 2), w >> (i + 2)};
+        const Shape s{n, h >> (i + 2), w >> (i + 2)};
         ConvBN& ci = convs[fpn_inner[i]];
-        conv(this, View{buf(k.A), k.cout}, InXform{}, s, s.H, s.W, params + ci.w_off, ci.w3, params + ci.b_off, k.cout, F, 1, 1, 0, buf(fL[i]));
+        conv(this, View{buf(k.A), k.cout}, InXform{}, s, params + ci.w_off, ci.w3, params + ci.b_off, k.cout, F, 1, 0, buf(fL[i]));
         if (i == 3) launch_copy_d2d(ctx, buf(fM[i]), buf(fL[i]), (size_t)s.N * s.H * s.W * F * sizeof(float));
         else launch_fpn_merge_fwd(ctx, buf(fL[i]), buf(fM[i + 1]), s.N, s.H, s.W, F, buf(fM[i]));
         ConvBN& cl = convs[fpn_layer[i]];
-        conv(this, View{buf(fM[i]), F}, InXform{}, s, s.H, s.W, params + cl.w_off, cl.w3, params + cl.b_off, F, F, 3, 1, 1, buf(fP[i]));
+        conv(this, View{buf(fM[i]), F}, InXform{}, s, params + cl.w_off, cl.w3, params + cl.b_off, F, F, 3, 1, buf(fP[i]));
     }
     launch_subsample2(ctx, buf(fP[3]), n, h >> 5, w >> 5, F, buf(fP6));
 }
@@ -359,12 +313,12 @@ void BackboneModel::backward_pass(const float* x_dev, const uint8_t*, int n, int
     launch_subsample2_bwd_add(ctx, buf(fdP6), n, h >> 5, w >> 5, F, buf(fdP[3]));
     float* dC[4] = {buf(bG[2]), buf(bG[3]), buf(bG[4]), buf(bG[5])};
     for (int i = 0; i < 4; ++i) {                   // fine to coarse: dM_i needs dM_{i-1}
-        const Sh s{n, h >> (i + 2), w >> (i + 2)};
+        const Shape s{n, h >> (i + 2), w >> (i + 2)};
         const int64_t M = (int64_t)s.N * s.H * s.W;
         ConvBN& cl = convs[fpn_layer[i]];
         launch_channel_sum(ctx, View{buf(fdP[i]), F}, M, F, ws, grads + cl.b_off);
-        { SideScopeB side(this); wgrad(this, View{buf(fM[i]), F}, InXform{}, buf(fdP[i]), F, F, s, s.H, s.W, 3, 1, 1, grads + cl.w_off); side.end(); }
-        conv(this, View{buf(fdP[i]), F}, InXform{}, s, s.H, s.W, cl.wd, cl.wd3, nullptr, F, F, 3, 1, 1, buf(fdM[i]));
+        wgrad_on_side(wgrad(this, View{buf(fM[i]), F}, InXform{}, buf(fdP[i]), F, F, s, 3, 1, grads + cl.w_off), nullptr);
+        conv(this, View{buf(fdP[i]), F}, InXform{}, s, cl.wd, cl.wd3, nullptr, F, F, 3, 1, buf(fdM[i]));
         if (i > 0) {                                // + the share of M_{i-1} = L_{i-1} + up(M_i)
             launch_fpn_merge_bwd_top(ctx, buf(fdM[i - 1]), n, h >> (i + 1), w >> (i + 1), F, buf(bG[0]));
             launch_add_inplace(ctx, buf(fdM[i]), buf(bG[0]), M * F);
@@ -372,8 +326,8 @@ void BackboneModel::backward_pass(const float* x_dev, const uint8_t*, int n, int
         const BBlock& k = bb[last[i]];
         ConvBN& ci = convs[fpn_inner[i]];
         launch_channel_sum(ctx, View{buf(fdM[i]), F}, M, F, ws, grads + ci.b_off);
-        { SideScopeB side(this); wgrad(this, View{buf(k.A), k.cout}, InXform{}, buf(fdM[i]), F, k.cout, s, s.H, s.W, 1, 1, 0, grads + ci.w_off); side.end(); }
-        conv(this, View{buf(fdM[i]), F}, InXform{}, s, s.H, s.W, ci.wd, ci.wd3, nullptr, F, k.cout, 1, 1, 0, dC[i]);
+        wgrad_on_side(wgrad(this, View{buf(k.A), k.cout}, InXform{}, buf(fdM[i]), F, k.cout, s, 1, 0, grads + ci.w_off), nullptr);
+        conv(this, View{buf(fdM[i]), F}, InXform{}, s, ci.wd, ci.wd3, nullptr, F, k.cout, 1, 0, dC[i]);
     }
     // ---- body, last block first.  gout: gradient w.r.t. the block output A
     float* gout = buf(bG[0]);
@@ -385,7 +339,7 @@ void BackboneModel::backward_pass(const float* x_dev, const uint8_t*, int n, int
     for (int b = (int)bb.size() - 1; b >= 0; --b) {
         BBlock& k = bb[b];
         ConvBN &c1 = convs[k.c1], &c2 = convs[k.c2], &c3 = convs[k.c3];
-        const Sh si{n, h >> k.lvl_in, w >> k.lvl_in}, so{n, h >> k.lvl, w >> k.lvl};
+        const Shape si{n, h >> k.lvl_in, w >> k.lvl_in}, so{n, h >> k.lvl, w >> k.lvl};
         const int64_t Mo = (int64_t)so.N * so.H * so.W, Mi = (int64_t)si.N * si.H * si.W;
         const float* a_in = b == 0 ? buf(bP0) : buf(bb[b - 1].A);
         // The weight gradients run on the side stream next to this chain (its masks, affine backward passes, space-to-depth
@@ -401,41 +355,41 @@ void BackboneModel::backward_pass(const float* x_dev, const uint8_t*, int n, int
         // dz = gout * [A > 0] -> dY3 = dz * scale3
         launch_relu_mask(ctx, View{gout, k.cout}, View{}, View{buf(k.A), k.cout}, View{}, Mo, k.cout, t3);
         affine_bwd(this, c3, t3, buf(k.Y3), Mo, 1.0f);
-        { SideScopeB side(this); wgrad(this, View{buf(k.Y2), k.width}, act_of(c2), t3, k.cout, k.width, so, so.H, so.W, 1, 1, 0, grads + c3.w_off); side.end(); }
-        conv(this, View{t3, k.cout}, InXform{}, so, so.H, so.W, c3.wd, c3.wd3, nullptr, k.cout, k.width, 1, 1, 0, dA2);
+        wgrad_on_side(wgrad(this, View{buf(k.Y2), k.width}, act_of(c2), t3, k.cout, k.width, so, 1, 0, grads + c3.w_off), nullptr);
+        conv(this, View{t3, k.cout}, InXform{}, so, c3.wd, c3.wd3, nullptr, k.cout, k.width, 1, 0, dA2);
         affine_bwd(this, c2, dA2, buf(k.Y2), Mo, 0.0f);                   // -> dY2
         if (k.stride == 2) {
             {
-                SideScopeB side(this);              // (the 2x2-form gradient goes back to the 3x3 layout behind its slab reduction)
-                wgrad(this, View{buf(k.xs1), 4 * k.width}, InXform{k.sc4, k.sh4, 1, 0.0f}, dA2, k.width, 4 * k.width, so, so.H, so.W, 2, 1, 1,
-                      buf(bdW));
+                SideScope side(this);               // (the 2x2-form gradient goes back to the 3x3 layout behind its slab reduction)
+                launch_wgrad(ctx, wgrad(this, View{buf(k.xs1), 4 * k.width}, InXform{k.sc4, k.sh4, 1, 0.0f}, dA2, k.width, 4 * k.width,
+                                        so, 2, 1, buf(bdW)));
                 launch_w_s2d(ctx, grads + c2.w_off, c2.cout, c2.cin, buf(bdW), false);
                 side.end();
             }
             float* dXs = buf(bS);                   // scratch [Mo][4 width]
-            conv(this, View{dA2, k.width}, InXform{}, so, so.H, so.W, c2.wds2d, c2.wds2d3, nullptr, k.width, 4 * k.width, 2, 1, 0, dXs);
+            conv(this, View{dA2, k.width}, InXform{}, so, c2.wds2d, c2.wds2d3, nullptr, k.width, 4 * k.width, 2, 0, dXs);
             launch_d2s_add(ctx, dXs, nullptr, View{}, n, si.H, si.W, k.width, dA1);
         } else {
-            { SideScopeB side(this); wgrad(this, View{buf(k.Y1), k.width}, act_of(c1), dA2, k.width, k.width, so, so.H, so.W, 3, 1, 1, grads + c2.w_off); side.end(); }
-            conv(this, View{dA2, k.width}, InXform{}, so, so.H, so.W, c2.wd, c2.wd3, nullptr, k.width, k.width, 3, 1, 1, dA1);
+            wgrad_on_side(wgrad(this, View{buf(k.Y1), k.width}, act_of(c1), dA2, k.width, k.width, so, 3, 1, grads + c2.w_off), nullptr);
+            conv(this, View{dA2, k.width}, InXform{}, so, c2.wd, c2.wd3, nullptr, k.width, k.width, 3, 1, dA1);
         }
         affine_bwd(this, c1, dA1, buf(k.Y1), Mi, 0.0f);                   // -> dY1
-        { SideScopeB side(this); wgrad(this, View{a_in, k.cin}, InXform{}, dA1, k.width, k.cin, si, si.H, si.W, 1, 1, 0, grads + c1.w_off); side.end(); }
+        wgrad_on_side(wgrad(this, View{a_in, k.cin}, InXform{}, dA1, k.width, k.cin, si, 1, 0, grads + c1.w_off), nullptr);
         float* dX = gother;                                               // [Mi][cin]
-        conv(this, View{dA1, k.width}, InXform{}, si, si.H, si.W, c1.wd, c1.wd3, nullptr, k.width, k.cin, 1, 1, 0, dX);
+        conv(this, View{dA1, k.width}, InXform{}, si, c1.wd, c1.wd3, nullptr, k.width, k.cin, 1, 0, dX);
         if (k.cd >= 0) {
             ConvBN& cd = convs[k.cd];
             launch_relu_mask(ctx, View{gout, k.cout}, View{}, View{buf(k.A), k.cout}, View{}, Mo, k.cout, td);
             affine_bwd(this, cd, td, buf(k.Yd), Mo, 1.0f);                // -> dYd
             if (k.stride == 2) {
-                { SideScopeB side(this); wgrad(this, View{buf(k.xsA), 4 * k.cin}, InXform{}, td, k.cout, k.cin, so, so.H, so.W, 1, 1, 0, grads + cd.w_off); side.end(); }
+                wgrad_on_side(wgrad(this, View{buf(k.xsA), 4 * k.cin}, InXform{}, td, k.cout, k.cin, so, 1, 0, grads + cd.w_off), nullptr);
                 float* dS = buf(bS);
-                conv(this, View{td, k.cout}, InXform{}, so, so.H, so.W, cd.wd, cd.wd3, nullptr, k.cout, k.cin, 1, 1, 0, dS);
+                conv(this, View{td, k.cout}, InXform{}, so, cd.wd, cd.wd3, nullptr, k.cout, k.cin, 1, 0, dS);
                 launch_subsample2_bwd_add(ctx, dS, n, si.H, si.W, k.cin, dX);      // the projection saw x[:, ::2, ::2]
             } else {
-                { SideScopeB side(this); wgrad(this, View{a_in, k.cin}, InXform{}, td, k.cout, k.cin, so, so.H, so.W, 1, 1, 0, grads + cd.w_off); side.end(); }
+                wgrad_on_side(wgrad(this, View{a_in, k.cin}, InXform{}, td, k.cout, k.cin, so, 1, 0, grads + cd.w_off), nullptr);
                 float* dS = buf(bS);
-                conv(this, View{td, k.cout}, InXform{}, so, so.H, so.W, cd.wd, cd.wd3, nullptr, k.cout, k.cin, 1, 1, 0, dS);
+                conv(this, View{td, k.cout}, InXform{}, so, cd.wd, cd.wd3, nullptr, k.cout, k.cin, 1, 0, dS);
                 launch_add_inplace(ctx, dX, dS, Mi * k.cin);
             }
         } else {                                    // identity shortcut: + gout * [A > 0]
@@ -455,8 +409,8 @@ void BackboneModel::backward_pass(const float* x_dev, const uint8_t*, int n, int
         (void)x_dev;                                  // (its K-packed copy from the forward pass is the operand)
         const int Kp = stem_kp();
         {
-            SideScopeB side(this);
-            wgrad(this, View{buf(bCol), Kp}, InXform{}, dA0, c.cout, Kp, Sh{n, H2, W2}, H2, W2, 1, 1, 0, buf(bWp));
+            SideScope side(this);
+            launch_wgrad(ctx, wgrad(this, View{buf(bCol), Kp}, InXform{}, dA0, c.cout, Kp, Shape{n, H2, W2}, 1, 0, buf(bWp)));
             launch_w_pack(ctx, grads + c.w_off, 49, c.cout, in_ch, Kp, buf(bWp), false);
             side.end();
         }

@@ -67,46 +67,18 @@ void Cnn3Model::prepare_shape(int n, int h, int w) {
     pN = n; pH = h; pW = w;
 }
 
-namespace {
-
-ConvArgs conv3x3(const ConvBN& c, View in, InXform xf, const float* w, const float* bias, float* y, int cin_gemm,
-                 int cout_gemm, int n, int h, int wd) {
-    ConvArgs a;
-    a.x = in;
-    a.N = n; a.H = h; a.W = wd; a.Hin = h; a.Win = wd;
-    a.Cin = cin_gemm; a.Cout = cout_gemm;
-    a.w = w;
-    a.bias = bias;
-    a.y = MutView{y, cout_gemm};
-    a.Hout = h; a.Wout = wd;
-    a.R = 3; a.S = 1; a.pad = 1;
-    a.xf = xf;
-    a.algo_flops = 2.0 * n * h * wd * 9.0 * c.cin * c.cout;
-    return a;
-}
-
-InXform relu_xf(const ConvBN& c) { return InXform{c.scale(), c.shift(), 1}; }
-
-}  // namespace
-
 void Cnn3Model::forward_pass(const float* x_dev, int n, int h, int w, bool) {
     refresh_dgrad_weights();
     ConvBN& c1 = convs[0];
     ConvBN& c2 = convs[1];
+    const Shape s{n, h, w};
     View x = network_input(x_dev, n, h, w);
-    ConvArgs a1 = conv3x3(c1, x, InXform{}, params + c1.w_off, params + c1.b_off, buf(cY1), c1.cin_p, c1.cout,
-                          n, h, w);
-    a1.w3 = use_w3() ? c1.w3 : nullptr;
-    ws_set(a1);
-    a1.bf16 = compute_bf16;
-    a1.bf16x3 = compute_x3;
+    ConvArgs a1 = conv_same(x, InXform{}, s, 3, 1, c1.cin_p, c1.cout, params + c1.w_off, c1.w3, params + c1.b_off, buf(cY1));
+    a1.algo_flops = 2.0 * n * h * w * 9.0 * c1.cin * c1.cout;
     launch_conv(ctx, a1);
-    ConvArgs a2 = conv3x3(c2, View{buf(cY1), c1.cout}, relu_xf(c1), params + c2.w_off, params + c2.b_off,
-                          buf(cY2), c2.cin_p, c2.cout, n, h, w);
-    a2.w3 = use_w3() ? c2.w3 : nullptr;
-    ws_set(a2);
-    a2.bf16 = compute_bf16;
-    a2.bf16x3 = compute_x3;
+    ConvArgs a2 = conv_same(View{buf(cY1), c1.cout}, act_of(c1), s, 3, 1, c2.cin_p, c2.cout, params + c2.w_off, c2.w3,
+                            params + c2.b_off, buf(cY2));
+    a2.algo_flops = 2.0 * n * h * w * 9.0 * c2.cin * c2.cout;
     launch_conv(ctx, a2);
     launch_head_fwd(ctx, buf(cY2), (int64_t)n * h * w, feat, c2.scale(), c2.shift(), params + head_w_off,
                     params + head_b_off, out_ch, buf(logits));
@@ -116,6 +88,7 @@ void Cnn3Model::backward_pass(const float* x_dev, const uint8_t* labels_dev, int
     ConvBN& c1 = convs[0];
     ConvBN& c2 = convs[1];
     const int64_t M = (int64_t)n * h * w;
+    const Shape s{n, h, w};
     refresh_dgrad_weights();
     if (loss_kind == 1) launch_focal_bwd(ctx, buf(logits), labels_dev, M, focal_alpha, focal_gamma, buf(dlogits));
     else launch_loss_bwd(ctx, buf(logits), labels_dev, M, d_sums, buf(dlogits));
@@ -125,34 +98,16 @@ void Cnn3Model::backward_pass(const float* x_dev, const uint8_t* labels_dev, int
     auto conv_backward = [&](ConvBN& c, float* dA, const float* Y, View in, InXform in_xf, float* dx) {
         launch_relu_bwd(ctx, dA, Y, M * c.cout);                       // dA -> dY
         launch_channel_sum(ctx, View{dA, c.cout}, M, c.cout, buf(ws_red), grads + c.b_off);
-        WgradArgs wa;
-        wa.xop = in;
-        wa.yop = View{dA, c.cout};
-        wa.xf_x = in_xf;
-        wa.N = n; wa.H = h; wa.W = w; wa.Hx = h; wa.Wx = w;
-        wa.Cx = c.cin_p; wa.Cy = c.cout;
-        wa.R = 3; wa.S = 1; wa.pad = 1;
-        wa.dw = grads + c.w_off;
-        wa.tap_stride = (int64_t)c.cin_p * c.cout;
-        wa.sy = c.cin_p; wa.sx = 1;
+        WgradArgs wa = wgrad_same(in, in_xf, dA, s, 3, 1, c.cin_p, c.cout, grads + c.w_off);
         wa.algo_flops = 2.0 * M * 9.0 * c.cin * c.cout;
-        wa.slab = buf(ws_slab);
-        wa.slab_floats = bufs[ws_slab].n;
-        side_begin();                      // wgrad on the side stream, next to the dgrad / ReLU chain
-        wa.bf16 = compute_bf16;
-    wa.bf16x3 = compute_x3;
-        launch_wgrad(ctx, wa);
-        side_end();
+        wgrad_on_side(wa, nullptr);                // wgrad on the side stream, next to the dgrad / ReLU chain
         if (dx) {
-            ConvArgs a = conv3x3(c, View{dA, c.cout}, InXform{}, c.wd, nullptr, dx, c.cout, c.cin, n, h, w);
-            a.w3 = use_w3() ? c.wd3 : nullptr;
-            ws_set(a);
-            a.bf16 = compute_bf16;
-    a.bf16x3 = compute_x3;
+            ConvArgs a = conv_same(View{dA, c.cout}, InXform{}, s, 3, 1, c.cout, c.cin, c.wd, c.wd3, nullptr, dx);
+            a.algo_flops = 2.0 * n * h * w * 9.0 * c.cin * c.cout;
             launch_conv(ctx, a);
         }
     };
-    conv_backward(c2, buf(cG2), buf(cY2), View{buf(cY1), c1.cout}, relu_xf(c1), buf(cG1));
+    conv_backward(c2, buf(cG2), buf(cY2), View{buf(cY1), c1.cout}, act_of(c1), buf(cG1));
     View x = c1.cin_p == in_ch ? View{x_dev, in_ch} : View{buf(x_pad), c1.cin_p};
     conv_backward(c1, buf(cG1), buf(cY1), x, InXform{}, nullptr);
     side_join();

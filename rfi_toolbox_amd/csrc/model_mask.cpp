@@ -110,79 +110,27 @@ void ConvHeadModel::prepare_shape(int n, int h, int w) {
     pN = n; pH = h; pW = w;
 }
 
-namespace {
-
-InXform relu_of(const ConvBN& c) { return InXform{c.scale(), c.shift(), 1}; }     // scale 1, shift 0 (reset_channel_state)
-
-ConvArgs conv3x3_args(rfi_model* m, View in, InXform xf, const float* w, const float* w3, const float* bias, float* y, int C,
-                      int n, int h, int wd) {
-    ConvArgs a;
-    a.x = in;
-    a.N = n; a.H = h; a.W = wd; a.Hin = h; a.Win = wd;
-    a.Cin = C; a.Cout = C;
-    a.w = w;
-    a.w3 = m->use_w3() ? w3 : nullptr;
-    m->ws_set(a);
-    a.bias = bias;
-    a.y = MutView{y, C};
-    a.Hout = h; a.Wout = wd;
-    a.R = 3; a.S = 1; a.pad = 1;
-    a.xf = xf;
-    a.bf16 = m->compute_bf16;
-    a.bf16x3 = m->compute_x3;
-    return a;
-}
-
-}  // namespace
-
 void ConvHeadModel::forward_pass(const float* x_dev, int n, int h, int w, bool) {
     refresh_dgrad_weights();
     const int L = depth, C = in_ch;
     const int64_t M4 = (int64_t)out_scale * out_scale * n * h * w;
     for (int i = 0; i < L; ++i) {
         ConvBN& c = convs[i];
-        ConvArgs a = conv3x3_args(this, i == 0 ? View{x_dev, C} : View{buf(mkY[i - 1]), C}, i == 0 ? InXform{} : relu_of(convs[i - 1]),
-                                  params + c.w_off, c.w3, params + c.b_off, buf(mkY[i]), C, n, h, w);
+        ConvArgs a = conv_same(i == 0 ? View{x_dev, C} : View{buf(mkY[i - 1]), C}, i == 0 ? InXform{} : act_of(convs[i - 1]),
+                               Shape{n, h, w}, 3, 1, C, C, params + c.w_off, c.w3, params + c.b_off, buf(mkY[i]));
         launch_conv(ctx, a);
     }
     if (upsample) {
-        UpConv& u = ups[0];
-        ConvArgs a;
-        a.x = View{buf(mkY[L - 1]), C};
-        a.N = n; a.H = h; a.W = w; a.Hin = h; a.Win = w;
-        a.Cin = C; a.Cout = C;
-        a.w = params + u.w_off;
-        a.w3 = use_w3() ? u.w3 : nullptr;
-        ws_set(a);
-        a.bias = params + u.b_off;
+        ConvArgs a = convt_args(ups[0], View{buf(mkY[L - 1]), C}, act_of(convs[L - 1]), Shape{n, h, w});
         a.y = MutView{buf(mkU), C};
-        a.Hout = 2 * h; a.Wout = 2 * w;
-        a.osy = 2; a.osx = 2;
-        a.R = 1; a.S = 1; a.pad = 0;
-        a.zgroups = 4;
-        a.xf = relu_of(convs[L - 1]);
-        a.bf16 = compute_bf16;
-        a.bf16x3 = compute_x3;
         launch_conv(ctx, a);
     }
     const ConvBN& cl = convs[L - 1];                  // (its scale = 1 / shift = 0 vectors serve the ReLU of U as well)
     if (head_on_mfma()) {             // a wide 1x1 head (the RPN's 5 A outputs) is a GEMM: the conv kernels, not the per-pixel VALU kernel
-        ConvArgs a;
-        a.x = View{head_in(), C};
-        a.N = n; a.H = out_scale * h; a.W = out_scale * w; a.Hin = a.H; a.Win = a.W;
-        a.Cin = C; a.Cout = out_ch;
-        a.w = params + head_w_off;
-        if (use_w3()) {               // the pre-split records of this small filter are rebuilt per pass (one 5-us launch, no allocation)
-            launch_weights_to_x3(ctx, a.w, 1, out_ch, C, buf(head_w3));
-            a.w3 = buf(head_w3);
-        }
-        a.bias = params + head_b_off;
-        a.y = MutView{buf(logits), out_ch};
-        a.Hout = a.H; a.Wout = a.W;
-        a.R = 1; a.S = 1; a.pad = 0;
-        a.xf = relu_of(cl);
-        a.bf16 = compute_bf16;
-        a.bf16x3 = compute_x3;
+        // the pre-split records of this small filter are rebuilt per pass (one 5-us launch, no allocation)
+        if (use_w3()) launch_weights_to_x3(ctx, params + head_w_off, 1, out_ch, C, buf(head_w3));
+        ConvArgs a = conv_same(View{head_in(), C}, act_of(cl), Shape{n, out_scale * h, out_scale * w}, 1, 0, C, out_ch,
+                               params + head_w_off, buf(head_w3), params + head_b_off, buf(logits));
         launch_conv(ctx, a);
         return;
     }
@@ -193,6 +141,7 @@ void ConvHeadModel::forward_pass(const float* x_dev, int n, int h, int w, bool) 
 void ConvHeadModel::backward_pass(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w) {
     const int L = depth, C = in_ch;
     const int64_t M = (int64_t)n * h * w, M4 = (int64_t)out_scale * out_scale * M;
+    const Shape s{n, h, w}, s4{n, out_scale * h, out_scale * w};
     refresh_dgrad_weights();
     if (!ext_dlogits) {               // (rfi_model_backward_dlogits: the caller's loss kernel has filled dlogits)
         if (loss_kind == 1) launch_focal_bwd(ctx, buf(logits), labels_dev, M4 * out_ch, focal_alpha, focal_gamma, buf(dlogits));
@@ -201,106 +150,31 @@ void ConvHeadModel::backward_pass(const float* x_dev, const uint8_t* labels_dev,
     const ConvBN& cl = convs[L - 1];
     if (head_on_mfma()) {
         // da = dlogits . W (a 1x1 conv with the transposed filter), dW = dlogits^T . act (the 1x1 weight gradient), db = column sums
-        float* const hin = head_in();
-        float* const da = head_din();
         launch_weight_to_dgrad(ctx, params + head_w_off, 1, out_ch, C, 0, buf(head_wd));
-        ConvArgs a;
-        a.x = View{buf(dlogits), out_ch};
-        a.N = n; a.H = out_scale * h; a.W = out_scale * w; a.Hin = a.H; a.Win = a.W;
-        a.Cin = out_ch; a.Cout = C;
-        a.w = buf(head_wd);
-        if (use_w3()) {
-            launch_weights_to_x3(ctx, a.w, 1, C, out_ch, buf(head_wd3));
-            a.w3 = buf(head_wd3);
-        }
-        a.y = MutView{da, C};
-        a.Hout = a.H; a.Wout = a.W;
-        a.R = 1; a.S = 1; a.pad = 0;
-        a.bf16 = compute_bf16;
-        a.bf16x3 = compute_x3;
+        if (use_w3()) launch_weights_to_x3(ctx, buf(head_wd), 1, C, out_ch, buf(head_wd3));
+        ConvArgs a = conv_same(View{buf(dlogits), out_ch}, InXform{}, s4, 1, 0, out_ch, C, buf(head_wd), buf(head_wd3), nullptr,
+                               head_din());
         launch_conv(ctx, a);
         launch_channel_sum(ctx, View{buf(dlogits), out_ch}, M4, out_ch, buf(ws_red), grads + head_b_off);
-        WgradArgs wa;
-        wa.xop = View{hin, C};
-        wa.xf_x = relu_of(cl);
-        wa.yop = View{buf(dlogits), out_ch};
-        wa.N = n; wa.H = out_scale * h; wa.W = out_scale * w; wa.Hx = wa.H; wa.Wx = wa.W;
-        wa.Cx = C; wa.Cy = out_ch;
-        wa.R = 1; wa.S = 1; wa.pad = 0;
-        wa.dw = grads + head_w_off;
-        wa.tap_stride = (int64_t)C * out_ch;
-        wa.sy = C; wa.sx = 1;
-        wa.slab = buf(ws_slab);
-        wa.slab_floats = bufs[ws_slab].n;
-        wa.bf16 = compute_bf16;
-        wa.bf16x3 = compute_x3;
-        side_begin();
-        launch_wgrad(ctx, wa);
-        side_end();
+        wgrad_on_side(wgrad_same(View{head_in(), C}, act_of(cl), buf(dlogits), s4, 1, 0, C, out_ch, grads + head_w_off), nullptr);
     } else
     launch_head_bwd(ctx, head_in(), M4, C, cl.scale(), cl.shift(), params + head_w_off, out_ch, buf(dlogits), head_din(), buf(ws_red),
                     grads + head_w_off, grads + head_b_off);
     // transposed conv: dU = dUa * (U > 0); bias, weight and input gradients
     if (upsample) {
-    UpConv& u = ups[0];
-    launch_relu_bwd(ctx, buf(mkGU), buf(mkU), M4 * C);
-    launch_channel_sum(ctx, View{buf(mkGU), C}, M4, C, buf(ws_red), grads + u.b_off);
-    {
-        WgradArgs wa;
-        wa.xop = View{buf(mkGU), C};
-        wa.yop = View{buf(mkY[L - 1]), C};
-        wa.xf_y = relu_of(convs[L - 1]);
-        wa.N = n; wa.H = h; wa.W = w; wa.Hx = 2 * h; wa.Wx = 2 * w;
-        wa.Cx = C; wa.Cy = C;
-        wa.R = 2; wa.S = 2; wa.pad = 0;
-        wa.dw = grads + u.w_off;
-        wa.tap_stride = (int64_t)C * C;
-        wa.sy = 1; wa.sx = C;                         // -> [tap][cout][cin]
-        wa.slab = buf(ws_slab);
-        wa.slab_floats = bufs[ws_slab].n;
-        wa.bf16 = compute_bf16;
-        wa.bf16x3 = compute_x3;
-        side_begin();
-        launch_wgrad(ctx, wa);
-        side_end();
-        ConvArgs a;
-        a.x = View{buf(mkGU), C};
-        a.N = n; a.H = h; a.W = w; a.Hin = 2 * h; a.Win = 2 * w;
-        a.Cin = C; a.Cout = C;
-        a.w = u.wd;
-        a.w3 = use_w3() ? u.wd3 : nullptr;
-        ws_set(a);
-        a.y = MutView{buf(mkG[L - 1]), C};
-        a.Hout = h; a.Wout = w;
-        a.R = 2; a.S = 2; a.pad = 0;
-        a.bf16 = compute_bf16;
-        a.bf16x3 = compute_x3;
-        launch_conv(ctx, a);
-    }
+        const UpConv& u = ups[0];
+        launch_relu_bwd(ctx, buf(mkGU), buf(mkU), M4 * C);
+        launch_channel_sum(ctx, View{buf(mkGU), C}, M4, C, buf(ws_red), grads + u.b_off);
+        convt_backward(u, View{buf(mkGU), C}, View{buf(mkY[L - 1]), C}, act_of(convs[L - 1]), s, buf(mkG[L - 1]));
     }
     for (int i = L - 1; i >= 0; --i) {
         ConvBN& c = convs[i];
         float* dA = buf(mkG[i]);
         launch_relu_bwd(ctx, dA, buf(mkY[i]), M * C);                       // dA -> dY
         launch_channel_sum(ctx, View{dA, C}, M, C, buf(ws_red), grads + c.b_off);
-        WgradArgs wa;
-        wa.xop = i == 0 ? View{x_dev, C} : View{buf(mkY[i - 1]), C};
-        if (i > 0) wa.xf_x = relu_of(convs[i - 1]);
-        wa.yop = View{dA, C};
-        wa.N = n; wa.H = h; wa.W = w; wa.Hx = h; wa.Wx = w;
-        wa.Cx = C; wa.Cy = C;
-        wa.R = 3; wa.S = 1; wa.pad = 1;
-        wa.dw = grads + c.w_off;
-        wa.tap_stride = (int64_t)C * C;
-        wa.sy = C; wa.sx = 1;
-        wa.slab = buf(ws_slab);
-        wa.slab_floats = bufs[ws_slab].n;
-        wa.bf16 = compute_bf16;
-        wa.bf16x3 = compute_x3;
-        side_begin();
-        launch_wgrad(ctx, wa);
-        side_end();
-        ConvArgs a = conv3x3_args(this, View{dA, C}, InXform{}, c.wd, c.wd3, nullptr, i == 0 ? buf(gx) : buf(mkG[i - 1]), C, n, h, w);
+        wgrad_on_side(wgrad_same(i == 0 ? View{x_dev, C} : View{buf(mkY[i - 1]), C}, i == 0 ? InXform{} : act_of(convs[i - 1]), dA, s,
+                                 3, 1, C, C, grads + c.w_off), nullptr);
+        ConvArgs a = conv_same(View{dA, C}, InXform{}, s, 3, 1, C, C, c.wd, c.wd3, nullptr, i == 0 ? buf(gx) : buf(mkG[i - 1]));
         launch_conv(ctx, a);
     }
     side_join_lazy();                 // (a head inside the detector's step: the caller goes on with the input gradient)

@@ -34,10 +34,8 @@ void BoxHeadModel::build() {
 }
 
 namespace {
-struct Lay { int N, H, W; };
 // R rows as an image: [R / 32] x 32 when possible (full 32-wide tiles), else R x 1 x 1
-Lay layout_of(int rows) { return rows % 32 == 0 ? Lay{1, rows / 32, 32} : Lay{rows, 1, 1}; }
-InXform relu_of(const ConvBN& c) { return InXform{c.scale(), c.shift(), 1}; }
+Shape layout_of(int rows) { return rows % 32 == 0 ? Shape{1, rows / 32, 32} : Shape{rows, 1, 1}; }
 }  // namespace
 
 void BoxHeadModel::prepare_shape(int n, int h, int w) {
@@ -66,7 +64,7 @@ void BoxHeadModel::prepare_shape(int n, int h, int w) {
                                 sumsq_ws_doubles((int64_t)n_flat) * 2});
     bufs[ws_red].ensure(ctx, red_need + 16);
     size_t slab_need = 0;
-    const Lay s = layout_of(n);
+    const Shape s = layout_of(n);
     for (auto& c : convs) {
         WgradArgs a;
         a.N = s.N; a.H = s.H; a.W = s.W; a.Hx = s.H; a.Wx = s.W;
@@ -84,23 +82,11 @@ void BoxHeadModel::prepare_shape(int n, int h, int w) {
 void BoxHeadModel::forward_pass(const float* x_dev, int n, int, int, bool) {
     refresh_dgrad_weights();
     const int L = depth;
-    const Lay s = layout_of(n);
+    const Shape s = layout_of(n);
     for (int i = 0; i < L; ++i) {
         ConvBN& c = convs[i];
-        ConvArgs a;
-        a.x = i == 0 ? View{x_dev, in_ch} : View{buf(fcY[i - 1]), feat};
-        a.N = s.N; a.H = s.H; a.W = s.W; a.Hin = s.H; a.Win = s.W;
-        a.Cin = c.cin; a.Cout = c.cout;
-        a.w = params + c.w_off;
-        a.w3 = use_w3() ? c.w3 : nullptr;
-        ws_set(a);
-        a.bias = params + c.b_off;
-        a.y = MutView{buf(fcY[i]), c.cout};
-        a.Hout = s.H; a.Wout = s.W;
-        a.R = 1; a.S = 1; a.pad = 0;
-        if (i > 0) a.xf = relu_of(convs[i - 1]);
-        a.bf16 = compute_bf16;
-        a.bf16x3 = compute_x3;
+        ConvArgs a = conv_same(i == 0 ? View{x_dev, in_ch} : View{buf(fcY[i - 1]), feat}, i == 0 ? InXform{} : act_of(convs[i - 1]), s,
+                               1, 0, c.cin, c.cout, params + c.w_off, c.w3, params + c.b_off, buf(fcY[i]));
         launch_conv(ctx, a);
     }
     const ConvBN& cl = convs[L - 1];
@@ -112,7 +98,7 @@ void BoxHeadModel::backward_pass(const float* x_dev, const uint8_t*, int n, int,
     RFI_REQUIRE(ext_dlogits, "BoxHead: the loss lives outside the model (rfi_op_fastrcnn_loss + rfi_model_backward_dlogits)");
     side_bound = 0;
     const int L = depth;
-    const Lay s = layout_of(n);
+    const Shape s = layout_of(n);
     const int64_t M = n;
     refresh_dgrad_weights();
     const ConvBN& cl = convs[L - 1];
@@ -123,38 +109,11 @@ void BoxHeadModel::backward_pass(const float* x_dev, const uint8_t*, int n, int,
         float* dA = buf(fcG[i]);
         launch_relu_bwd(ctx, dA, buf(fcY[i]), M * c.cout);
         launch_channel_sum(ctx, View{dA, c.cout}, M, c.cout, buf(ws_red), grads + c.b_off);
-        WgradArgs wa;
-        wa.xop = i == 0 ? View{x_dev, in_ch} : View{buf(fcY[i - 1]), feat};
-        if (i > 0) wa.xf_x = relu_of(convs[i - 1]);
-        wa.yop = View{dA, c.cout};
-        wa.N = s.N; wa.H = s.H; wa.W = s.W; wa.Hx = s.H; wa.Wx = s.W;
-        wa.Cx = c.cin; wa.Cy = c.cout;
-        wa.R = 1; wa.S = 1; wa.pad = 0;
-        wa.dw = grads + c.w_off;
-        wa.tap_stride = (int64_t)c.cin * c.cout;
-        wa.sy = c.cin; wa.sx = 1;
-        wa.slab = buf(ws_slab);
-        wa.slab_floats = bufs[ws_slab].n;
-        wa.bf16 = compute_bf16;
-        wa.bf16x3 = compute_x3;
-        {   // side stream: every layer owns its gradient tensor fcG[i], nothing the weight gradient reads is rewritten in this pass
-            struct Back { rfi_ctx* c; ~Back() { c->stream = c->main_stream; } } back{ctx};
-            side_begin();
-            launch_wgrad(ctx, wa);
-            side_end();
-        }
-        ConvArgs a;
-        a.x = View{dA, c.cout};
-        a.N = s.N; a.H = s.H; a.W = s.W; a.Hin = s.H; a.Win = s.W;
-        a.Cin = c.cout; a.Cout = c.cin;
-        a.w = c.wd;
-        a.w3 = use_w3() ? c.wd3 : nullptr;
-        ws_set(a);
-        a.y = MutView{i == 0 ? buf(gx) : buf(fcG[i - 1]), c.cin};
-        a.Hout = s.H; a.Wout = s.W;
-        a.R = 1; a.S = 1; a.pad = 0;
-        a.bf16 = compute_bf16;
-        a.bf16x3 = compute_x3;
+        // side stream: every layer owns its gradient tensor fcG[i], nothing the weight gradient reads is rewritten in this pass
+        wgrad_on_side(wgrad_same(i == 0 ? View{x_dev, in_ch} : View{buf(fcY[i - 1]), feat}, i == 0 ? InXform{} : act_of(convs[i - 1]),
+                                 dA, s, 1, 0, c.cin, c.cout, grads + c.w_off), nullptr);
+        ConvArgs a = conv_same(View{dA, c.cout}, InXform{}, s, 1, 0, c.cout, c.cin, c.wd, c.wd3, nullptr,
+                               i == 0 ? buf(gx) : buf(fcG[i - 1]));
         launch_conv(ctx, a);
     }
     side_join_lazy();                 // (the caller goes on with the input gradient; the weight gradients are needed at the optimiser step)

@@ -276,8 +276,6 @@ void UNetModel::refresh_plane_weights(int which) {
 
 namespace {
 
-struct Shape { int N, H, W; };
-
 PlaneSeg seg_of(const PlaneBuf& b) { return PlaneSeg{b.p, b.pstride, b.nchunks}; }
 
 // where a raw conv output lives: a float32 tensor (values rounded to bf16 when the bf16 flow is on) or a bfloat16 one
@@ -443,20 +441,9 @@ void UNetModel::forward_planes(const float* x_dev, int n, int h, int w, bool tra
             prevBN = &c2;
             continue;
         }
-        ConvArgs a;                               // ConvTranspose2d(k2,s2): the round-1 kernel, float32 tensors
-        a.x = View{prevY, u.cin};
-        a.N = sin.N; a.H = sin.H; a.W = sin.W; a.Hin = sin.H; a.Win = sin.W;
-        a.Cin = u.cin; a.Cout = u.cout;
-        a.w = params + u.w_off;
-        a.w3 = use_w3() ? u.w3 : nullptr;
-        a.bias = params + u.b_off;
-        a.Hout = s.H; a.Wout = s.W;
-        a.osy = 2; a.osx = 2;
-        a.R = 1; a.S = 1; a.pad = 0;
-        a.zgroups = 4;
-        a.xf = bn_xf(*prevBN);
-        a.bf16 = compute_bf16;
-        a.bf16x3 = compute_x3;
+        // ConvTranspose2d(k2,s2): the round-1 kernel, float32 tensors (with a plane flow on, ws_need() == 0: no wave-specialised
+        // copy exists for set_filters to find)
+        ConvArgs a = convt_args(u, View{prevY, u.cin}, bn_xf(*prevBN), sin);
         // bf16 data flow with whole 16-channel chunks: the kernel writes the up-conv output as the bf16 operand of the
         // decoder's first conv directly; otherwise float32 + one conversion pass (which also zero-fills chunk padding)
         const bool direct = P == 1 && u.cout % 16 == 0 && conv_mfma_eligible(a) && pl[pUp[l]].pstride % 4 == 0;
@@ -486,14 +473,6 @@ void UNetModel::forward_planes(const float* x_dev, int n, int h, int w, bool tra
 }
 
 namespace {
-
-struct SideScopeP {
-    rfi_model* m;
-    bool ended = false;
-    explicit SideScopeP(rfi_model* model, hipEvent_t after = nullptr) : m(model) { m->side_begin_after(after); }
-    void end() { m->side_end(); ended = true; }
-    ~SideScopeP() { if (!ended) m->ctx->stream = m->ctx->main_stream; }
-};
 
 // dA: gradient w.r.t. the ACTIVATED output of conv c (float32, left untouched).  Writes dW / db / dgamma / dbeta
 // and, if dx != null, the gradient w.r.t. the conv's input (float32 raw, `cin` channels per pixel).
@@ -554,7 +533,7 @@ int backward_pconv_bn(UNetModel* m, ConvBN& c, YRef dA, YRef Y, const PlaneSeg* 
     wa.slab = m->buf(m->ws_slab);
     wa.slab_floats = m->bufs[m->ws_slab].n;
     {
-        SideScopeP side(m, dy_done);
+        SideScope side(m, dy_done);
         launch_pwgrad(ctx, wa);
         side.end();
     }
@@ -733,7 +712,7 @@ void UNetModel::backward_planes(const float* x_dev, const uint8_t* labels_dev, i
             wa.slab = buf(ws_slab);
             wa.slab_floats = bufs[ws_slab].n;
             {
-                SideScopeP side(this);
+                SideScope side(this);
                 launch_pwgrad(ctx, wa);
                 side.end();
             }
@@ -769,38 +748,7 @@ void UNetModel::backward_planes(const float* x_dev, const uint8_t* labels_dev, i
             launch_channel_sum(ctx, dUp, (int64_t)s.N * s.H * s.W, u.cout, udefer ? dbias_pool + u.dbias_rec_off : buf(ws_red), grads + u.b_off,
                                !udefer);
         }
-        WgradArgs wa;
-        wa.xop = dUp;
-        wa.yop = View{prevY, u.cin};
-        wa.xf_y = bn_xf(prevBN);
-        wa.N = sin.N; wa.H = sin.H; wa.W = sin.W; wa.Hx = s.H; wa.Wx = s.W;
-        wa.Cx = u.cout; wa.Cy = u.cin;
-        wa.R = 2; wa.S = 2; wa.pad = 0;
-        wa.dw = grads + u.w_off;
-        wa.tap_stride = (int64_t)u.cin * u.cout;
-        wa.sy = 1; wa.sx = u.cin;
-        wa.slab = buf(ws_slab);
-        wa.slab_floats = bufs[ws_slab].n;
-        wa.bf16 = compute_bf16;
-        wa.bf16x3 = compute_x3;
-        {
-            SideScopeP side(this);
-            launch_wgrad(ctx, wa);
-            side.end();
-        }
-        ConvArgs a;
-        a.x = dUp;
-        a.N = sin.N; a.H = sin.H; a.W = sin.W; a.Hin = s.H; a.Win = s.W;
-        a.Cin = u.cout; a.Cout = u.cin;
-        a.w = u.wd;
-        a.w3 = use_w3() ? u.wd3 : nullptr;
-        float* dprev = (l == D) ? buf(gBottA) : buf(gA[l + 1]);
-        a.y = MutView{dprev, u.cin};
-        a.Hout = sin.H; a.Wout = sin.W;
-        a.R = 2; a.S = 2; a.pad = 0;
-        a.bf16 = compute_bf16;
-        a.bf16x3 = compute_x3;
-        launch_conv(ctx, a);
+        convt_backward(u, dUp, View{prevY, u.cin}, bn_xf(prevBN), sin, (l == D) ? buf(gBottA) : buf(gA[l + 1]));
         bucket_ready(u.w_off, l == 1 ? n_flat : ups[k + 1].w_off);      // decoder level l (+ head) is complete
     }
     {                                             // bottleneck

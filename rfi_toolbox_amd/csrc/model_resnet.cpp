@@ -135,104 +135,13 @@ void UNetModel::refresh_resnet_weights() {
     }
 }
 
-namespace {
-
-struct Shape { int N, H, W; };
-
-// generic conv + BatchNorm statistics on float32 tensors (round-1 kernels): R x R, stride 1, `pad`
-void conv_bn(rfi_model* m, ConvBN& c, View in, InXform xf, Shape s, const float* w, const float* w3, int taps_R, int pad,
-             int cin, float* Y, bool train, double flops) {
-    ConvArgs a;
-    a.x = in;
-    a.N = s.N; a.H = s.H; a.W = s.W; a.Hin = s.H; a.Win = s.W;
-    a.Cin = cin; a.Cout = c.cout;
-    a.w = w;
-    a.w3 = m->use_w3() ? w3 : nullptr;            // null: the kernel launcher splits a temporary copy
-    m->ws_set(a);
-    a.bias = c.has_bias ? m->params + c.b_off : nullptr;
-    a.y = MutView{Y, c.cout};
-    a.Hout = s.H; a.Wout = s.W;
-    a.R = taps_R; a.S = 1; a.pad = pad;
-    a.xf = xf;
-    a.algo_flops = flops;
-    float* ws = m->buf(m->ws_red);
-    if (train) {
-        a.stats = reinterpret_cast<double*>(ws);
-        a.stats_max_records = (int)(bn_stats_ws_floats(c.cout) / ((size_t)c.cout * 4));
-    }
-    a.bf16 = m->compute_bf16;
-    a.bf16x3 = m->compute_x3;
-    launch_conv(m->ctx, a);
-    const int64_t M = (int64_t)s.N * s.H * s.W;
-    if (train) {
-        if (a.stats_records == 0) launch_bn_stats(m->ctx, Y, M, c.cout, ws);
-        launch_bn_finalize(m->ctx, ws, M, c.cout, m->params + c.g_off, m->params + c.be_off, c.running_mean(), c.running_var(),
-                           c.ema_repeats, c.mean(), c.invstd(), c.scale(), c.shift(), nullptr, a.stats_records);
-        c.nbt += c.ema_repeats;
-    } else {
-        launch_bn_eval_coeffs(m->ctx, c.cout, m->params + c.g_off, m->params + c.be_off, c.running_mean(), c.running_var(),
-                              c.scale(), c.shift());
-    }
-}
-
-struct SideScopeR {
-    rfi_model* m;
-    bool ended = false;
-    explicit SideScopeR(rfi_model* model) : m(model) { m->side_begin(); }
-    void end() { m->side_end(); ended = true; }
-    ~SideScopeR() { if (!ended) m->ctx->stream = m->ctx->main_stream; }
-};
-
-// dW of a conv (R x R stride 1 `pad`) into `dw` ([taps][cout][cx]) on the side stream
-void wgrad(rfi_model* m, View x, InXform xf_x, const float* dY, int cy, int cx, Shape s, int R, int pad, float* dw, double flops) {
-    WgradArgs wa;
-    wa.xop = x;
-    wa.yop = View{dY, cy};
-    wa.xf_x = xf_x;
-    wa.N = s.N; wa.H = s.H; wa.W = s.W; wa.Hx = s.H; wa.Wx = s.W;
-    wa.Cx = cx; wa.Cy = cy;
-    wa.R = R; wa.S = 1; wa.pad = pad;
-    wa.dw = dw;
-    wa.tap_stride = (int64_t)cx * cy;
-    wa.sy = cx; wa.sx = 1;
-    wa.algo_flops = flops;
-    wa.slab = m->buf(m->ws_slab);
-    wa.slab_floats = m->bufs[m->ws_slab].n;
-    wa.bf16 = m->compute_bf16;
-    wa.bf16x3 = m->compute_x3;
-    SideScopeR side(m);
-    launch_wgrad(m->ctx, wa);
-    side.end();
-}
-
-// dX = conv(dY, dgrad-layout filters): R x R stride 1 `pad` (pad of the GRADIENT conv)
-void dgrad(rfi_model* m, const float* dY, int cy, const float* wd, const float* wd3, int cx, Shape s, int R, int pad, float* dx,
-           double flops) {
-    ConvArgs a;
-    a.x = View{dY, cy};
-    a.N = s.N; a.H = s.H; a.W = s.W; a.Hin = s.H; a.Win = s.W;
-    a.Cin = cy; a.Cout = cx;
-    a.w = wd;
-    a.w3 = m->use_w3() ? wd3 : nullptr;
-    m->ws_set(a);
-    a.y = MutView{dx, cx};
-    a.Hout = s.H; a.Wout = s.W;
-    a.R = R; a.S = 1; a.pad = pad;
-    a.algo_flops = flops;
-    a.bf16 = m->compute_bf16;
-    a.bf16x3 = m->compute_x3;
-    launch_conv(m->ctx, a);
-}
-
-}  // namespace
-
 // -> the pooled output of layer 4 (input of the bottleneck); skip l is written into concat[l][..., C:2C]
 View UNetModel::forward_resnet_encoder(View x, int n, int h, int w, bool train) {
     const int D = depth;
     {                                             // stem: a0 = relu(BN(conv3x3(x)))
         ConvBN& c = convs[0];
         Shape s{n, h, w};
-        conv_bn(this, c, x, InXform{}, s, params + c.w_off, c.w3, 3, 1, c.cin_p, buf(rs_stemY), train, 2.0 * n * h * w * 9.0 * c.cin * c.cout);
+        conv_bn(c, x, InXform{}, s, params + c.w_off, c.w3, 3, 1, c.cin_p, buf(rs_stemY), train, 2.0 * n * h * w * 9.0 * c.cin * c.cout);
         launch_bn_add_relu(ctx, buf(rs_stemY), c.scale(), c.shift(), nullptr, nullptr, nullptr, (int64_t)n * h * w, c.cout,
                            MutView{buf(rs_a0), c.cout}, MutView{});
     }
@@ -246,14 +155,14 @@ View UNetModel::forward_resnet_encoder(View x, int n, int h, int w, bool train) 
         const double f1 = 2.0 * M * 9.0 * b.cin * b.cout, f2 = 2.0 * M * 9.0 * b.cout * b.cout;
         if (b.stride == 2) {
             launch_s2d(ctx, a_in, n, s.H * 2, s.W * 2, b.cin, buf(b.xs));
-            conv_bn(this, c1, View{buf(b.xs), 4 * b.cin}, InXform{}, s, c1.ws2d, c1.ws2d3, 2, 1, 4 * b.cin, buf(b.Y1), train, f1);
+            conv_bn(c1, View{buf(b.xs), 4 * b.cin}, InXform{}, s, c1.ws2d, c1.ws2d3, 2, 1, 4 * b.cin, buf(b.Y1), train, f1);
             ConvBN& cd = convs[b.cd];             // projection: 1x1 on the (0, 0) slice of the space-to-depth input
-            conv_bn(this, cd, View{buf(b.xs), 4 * b.cin}, InXform{}, s, params + cd.w_off, cd.w3, 1, 0, b.cin, buf(b.Yd), train,
+            conv_bn(cd, View{buf(b.xs), 4 * b.cin}, InXform{}, s, params + cd.w_off, cd.w3, 1, 0, b.cin, buf(b.Yd), train,
                     2.0 * M * b.cin * b.cout);
         } else {
-            conv_bn(this, c1, View{a_in, b.cin}, InXform{}, s, params + c1.w_off, c1.w3, 3, 1, b.cin, buf(b.Y1), train, f1);
+            conv_bn(c1, View{a_in, b.cin}, InXform{}, s, params + c1.w_off, c1.w3, 3, 1, b.cin, buf(b.Y1), train, f1);
         }
-        conv_bn(this, c2, View{buf(b.Y1), b.cout}, bn_xf(c1), s, params + c2.w_off, c2.w3, 3, 1, b.cout, buf(b.Y2), train, f2);
+        conv_bn(c2, View{buf(b.Y1), b.cout}, bn_xf(c1), s, params + c2.w_off, c2.w3, 3, 1, b.cout, buf(b.Y2), train, f2);
         // a_out = relu(BN2(Y2) + shortcut); the stage output also goes into the decoder's concat buffer (the skip)
         const bool last = (bi & 1) == 1;
         MutView skip = last ? MutView{buf(concat[b.level]) + b.cout, 2 * b.cout} : MutView{};
@@ -277,6 +186,19 @@ View UNetModel::forward_resnet_encoder(View x, int n, int h, int w, bool train) 
 
 void UNetModel::backward_resnet_encoder(const float* x_dev, int n, int h, int w) {
     const int D = depth;
+    // dW of a conv (R x R stride 1 `pad`) into `dw` ([taps][cy][cx]) on the side stream
+    auto wgrad = [&](View x, InXform xf_x, const float* dY, int cy, int cx, Shape s, int R, int pad, float* dw, double flops) {
+        WgradArgs wa = wgrad_same(x, xf_x, dY, s, R, pad, cx, cy, dw);
+        wa.algo_flops = flops;
+        wgrad_on_side(wa, nullptr);
+    };
+    // dX = conv(dY, dgrad-layout filters): R x R stride 1 `pad` (pad of the GRADIENT conv)
+    auto dgrad = [&](const float* dY, int cy, const float* wd, const float* wd3, int cx, Shape s, int R, int pad, float* dx,
+                     double flops) {
+        ConvArgs a = conv_same(View{dY, cy}, InXform{}, s, R, pad, cy, cx, wd, wd3, nullptr, dx);
+        a.algo_flops = flops;
+        launch_conv(ctx, a);
+    };
     // gradient w.r.t. the last stage's output: skip gradient + max-pool routing of dpool
     float* gout = buf(rs_g0);
     float* gother = buf(rs_g1);
@@ -303,9 +225,9 @@ void UNetModel::backward_resnet_encoder(const float* x_dev, int n, int h, int w)
                              grads + c2.g_off, grads + c2.be_off, 1.0f);
         launch_bn_bwd_apply(ctx, dz, buf(b.Y2), M, b.cout, c2.scale(), c2.shift(), c2.mean(), c2.invstd(), params + c2.g_off,
                             c2.c1(), c2.c2(), ws, nullptr, 1.0f);                 // dz <- dY2
-        wgrad(this, View{buf(b.Y1), b.cout}, bn_xf(c1), dz, b.cout, b.cout, s, 3, 1, grads + c2.w_off, f2);
+        wgrad(View{buf(b.Y1), b.cout}, bn_xf(c1), dz, b.cout, b.cout, s, 3, 1, grads + c2.w_off, f2);
         float* dA1 = buf(rs_dA1[bi & 1]);
-        dgrad(this, dz, b.cout, c2.wd, c2.wd3, b.cout, s, 3, 1, dA1, f2);
+        dgrad(dz, b.cout, c2.wd, c2.wd3, b.cout, s, 3, 1, dA1, f2);
         launch_bn_bwd_reduce(ctx, dA1, buf(b.Y1), M, b.cout, c1.scale(), c1.shift(), c1.mean(), c1.invstd(), ws, c1.c1(), c1.c2(),
                              grads + c1.g_off, grads + c1.be_off, act_slope);
         launch_bn_bwd_apply(ctx, dA1, buf(b.Y1), M, b.cout, c1.scale(), c1.shift(), c1.mean(), c1.invstd(), params + c1.g_off,
@@ -313,13 +235,13 @@ void UNetModel::backward_resnet_encoder(const float* x_dev, int n, int h, int w)
         float* dX = buf(rs_dX);
         if (b.stride == 2) {
             // conv1 in its 2x2 form on the space-to-depth input: weight gradient in that layout, then back to 3x3
-            wgrad(this, View{buf(b.xs), 4 * b.cin}, InXform{}, dA1, b.cout, 4 * b.cin, s, 2, 1, buf(rs_dW), f1);
+            wgrad(View{buf(b.xs), 4 * b.cin}, InXform{}, dA1, b.cout, 4 * b.cin, s, 2, 1, buf(rs_dW), f1);
             {
-                SideScopeR side(this);            // (after the slab reduction of that wgrad, same stream)
+                SideScope side(this);             // (after the slab reduction of that wgrad, same stream)
                 launch_w_s2d(ctx, grads + c1.w_off, b.cout, b.cin, buf(rs_dW), false);
                 side.end();
             }
-            dgrad(this, dA1, b.cout, c1.wds2d, c1.wds2d3, 4 * b.cin, s, 2, 0, dX, f1);             // [M][4 cin]
+            dgrad(dA1, b.cout, c1.wds2d, c1.wds2d3, 4 * b.cin, s, 2, 0, dX, f1);             // [M][4 cin]
             // ---- projection branch: BNd on the same dz (recomputed: the first copy now holds dY2), 1x1 conv
             ConvBN& cd = convs[b.cd];
             dz = buf(rs_dzd);
@@ -328,14 +250,14 @@ void UNetModel::backward_resnet_encoder(const float* x_dev, int n, int h, int w)
                                  grads + cd.g_off, grads + cd.be_off, 1.0f);
             launch_bn_bwd_apply(ctx, dz, buf(b.Yd), M, b.cout, cd.scale(), cd.shift(), cd.mean(), cd.invstd(), params + cd.g_off,
                                 cd.c1(), cd.c2(), ws, nullptr, 1.0f);             // dz <- dYd
-            wgrad(this, View{buf(b.xs), 4 * b.cin}, InXform{}, dz, b.cout, b.cin, s, 1, 0, grads + cd.w_off, 2.0 * M * b.cin * b.cout);
+            wgrad(View{buf(b.xs), 4 * b.cin}, InXform{}, dz, b.cout, b.cin, s, 1, 0, grads + cd.w_off, 2.0 * M * b.cin * b.cout);
             float* dS = buf(rs_dS);
-            dgrad(this, dz, b.cout, cd.wd, cd.wd3, b.cin, s, 1, 0, dS, 2.0 * M * b.cin * b.cout);   // [M][cin]
+            dgrad(dz, b.cout, cd.wd, cd.wd3, b.cin, s, 1, 0, dS, 2.0 * M * b.cin * b.cout);   // [M][cin]
             // back to full resolution, + the skip gradient of the previous stage (its output is this block's input)
             launch_d2s_add(ctx, dX, dS, View{buf(dconcat[b.level - 1]) + b.cin, 2 * b.cin}, n, s.H * 2, s.W * 2, b.cin, gother);
         } else {
-            wgrad(this, View{a_in, b.cin}, InXform{}, dA1, b.cout, b.cin, s, 3, 1, grads + c1.w_off, f1);
-            dgrad(this, dA1, b.cout, c1.wd, c1.wd3, b.cin, s, 3, 1, dX, f1);
+            wgrad(View{a_in, b.cin}, InXform{}, dA1, b.cout, b.cin, s, 3, 1, grads + c1.w_off, f1);
+            dgrad(dA1, b.cout, c1.wd, c1.wd3, b.cin, s, 3, 1, dX, f1);
             // identity shortcut: gin = dX + gout * (a_out > 0)
             launch_relu_mask(ctx, View{gout, b.cout}, View{}, View{buf(b.A), b.cout}, View{dX, b.cin}, M, b.cout, gother);
         }
@@ -352,7 +274,7 @@ void UNetModel::backward_resnet_encoder(const float* x_dev, int n, int h, int w)
         launch_bn_bwd_apply(ctx, gout, buf(rs_stemY), M, c.cout, c.scale(), c.shift(), c.mean(), c.invstd(), params + c.g_off,
                             c.c1(), c.c2(), ws, nullptr, act_slope);
         View in = c.cin_p == in_ch ? View{x_dev, in_ch} : View{buf(x_pad), c.cin_p};
-        wgrad(this, in, InXform{}, gout, c.cout, c.cin_p, s, 3, 1, grads + c.w_off, 2.0 * M * 9.0 * c.cin * c.cout);
+        wgrad(in, InXform{}, gout, c.cout, c.cin_p, s, 3, 1, grads + c.w_off, 2.0 * M * 9.0 * c.cin * c.cout);
         bucket_ready(0, convs[blocks[0].c1].w_off);
     }
 }
