@@ -50,6 +50,8 @@ int rfi_ctx_synchronize(rfi_ctx* ctx);
 /* the hipStream_t every kernel of this ctx is launched on (for event timing / interop) */
 int rfi_ctx_stream(rfi_ctx* ctx, void** hip_stream);
 int rfi_ctx_device_name(rfi_ctx* ctx, char* buf, size_t buflen);
+/* the device allocations the ctx holds now (rfi_malloc, models, scratch): their number and bytes (host only) */
+int rfi_ctx_allocations(rfi_ctx* ctx, int64_t* count, uint64_t* bytes);
 
 /* device memory owned by the ctx (freed at rfi_ctx_destroy if still live) */
 int rfi_malloc(rfi_ctx* ctx, size_t bytes, void** dptr);

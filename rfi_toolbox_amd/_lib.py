@@ -76,6 +76,7 @@ _PROTOS = {
     "rfi_ctx_set_overlap": (_i, [_vp, _i]),
     "rfi_ctx_stream": (_i, [_vp, _pvp]),
     "rfi_ctx_device_name": (_i, [_vp, _cp, _sz]),
+    "rfi_ctx_allocations": (_i, [_vp, _pi64, C.POINTER(C.c_uint64)]),
     "rfi_malloc": (_i, [_vp, _sz, _pvp]),
     "rfi_free": (_i, [_vp, _vp]),
     "rfi_memcpy": (_i, [_vp, _vp, _i, _vp, _i, _sz]),

@@ -31,6 +31,12 @@ void rfi_ctx::release(void* p) {
     allocs.erase(it);
     RFI_CHECK_HIP(hipFree(p));
 }
+void* rfi_ctx::upload_table(const void* host, size_t bytes) {
+    void* d = alloc(bytes);
+    if (bytes) RFI_CHECK_HIP(hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, stream));
+    RFI_CHECK_HIP(hipStreamSynchronize(stream));
+    return d;
+}
 void* rfi_ctx::get_scratch(size_t bytes) {
     if (bytes > scratch_bytes) {
         if (scratch) {
@@ -95,6 +101,26 @@ UNetModel* plain_unet(rfi_model* m) {
     auto* u = dynamic_cast<UNetModel*>(m);
     return u && !u->resnet_encoder ? u : nullptr;
 }
+
+size_t dtype_bytes(int dtype) { return dtype == RFI_C128 ? 16 : (dtype == RFI_F32 ? 4 : 8); }
+
+// the two losses of rfi_op_rpn_loss / rfi_op_fastrcnn_loss: `launch(workspace, two-float device output)`, then read back
+template <class Launch>
+void read_losses(rfi_ctx* ctx, float* loss0, float* loss1, Launch launch) {
+    float h2[2];
+    CallScope sc(ctx);
+    launch(sc.temp<double>(rpn_loss_ws_doubles()), sc.out(h2, RFI_HOST, 2));
+    sc.finish();
+    if (loss0) *loss0 = h2[0];
+    if (loss1) *loss1 = h2[1];
+}
+
+// launches on another stream for the life of the scope (profiled launches read ctx->stream)
+struct OnStream {
+    rfi_ctx* c; hipStream_t old;
+    OnStream(rfi_ctx* ctx, hipStream_t s) : c(ctx), old(ctx->stream) { c->stream = s; }
+    ~OnStream() { c->stream = old; }
+};
 
 }  // namespace
 
@@ -193,6 +219,16 @@ int rfi_ctx_device_name(rfi_ctx* ctx, char* buf, size_t buflen) {
         std::string s = std::string(ctx->prop.name) + " " + ctx->prop.gcnArchName + " CUs=" +
                         std::to_string(ctx->prop.multiProcessorCount);
         std::snprintf(buf, buflen, "%s", s.c_str());
+    });
+}
+
+int rfi_ctx_allocations(rfi_ctx* ctx, int64_t* count, uint64_t* bytes) {
+    return guarded([&] {
+        RFI_REQUIRE(ctx && count && bytes, "rfi_ctx_allocations: null argument");
+        uint64_t b = 0;
+        for (const auto& kv : ctx->allocs) b += kv.second;
+        *count = (int64_t)ctx->allocs.size();
+        *bytes = b;
     });
 }
 
@@ -865,9 +901,7 @@ int rfi_comm_emulate(rfi_ctx* ctx, int world) {
 namespace rfi {
 // one bucket of the gradient exchange, on the context's communication stream (the caller orders it by events)
 void comm_bucket_allreduce(rfi_ctx* ctx, float* dptr, int64_t count) {
-    hipStream_t keep = ctx->stream;
-    ctx->stream = ctx->comm_stream;
-    struct Restore { rfi_ctx* c; hipStream_t s; ~Restore() { c->stream = s; } } restore{ctx, keep};
+    OnStream on(ctx, ctx->comm_stream);
     if (ctx->comm_emulate > 1) {
         launch_scale_inplace(ctx, dptr, count, (float)ctx->comm_emulate);
         return;
@@ -899,49 +933,16 @@ int rfi_preprocess_patches(rfi_ctx* ctx, const void* patches, int patches_mem, i
         if (n == 0) return;
         ctx->activate();
         const size_t px = (size_t)n * ps_h * ps_w;
-        const size_t esz = dtype == RFI_C128 ? 16 : (dtype == RFI_F32 ? 4 : 8);
-        void* din = const_cast<void*>(patches);
-        float* dout = out_nhwc;
-        void *tmp_in = nullptr, *tmp_out = nullptr;
-        if (patches_mem == RFI_HOST) {
-            tmp_in = ctx->alloc(px * esz);
-            RFI_CHECK_HIP(hipMemcpyAsync(tmp_in, patches, px * esz, hipMemcpyHostToDevice, ctx->stream));
-            din = tmp_in;
-        }
-        if (out_mem == RFI_HOST) {
-            tmp_out = ctx->alloc(px * 3 * sizeof(float));
-            dout = static_cast<float*>(tmp_out);
-        }
+        CallScope sc(ctx);                  // (holds nothing with device pointers only: the call stays asynchronous)
+        const void* din = sc.in(patches, patches_mem, px * dtype_bytes(dtype));
+        float* dout = sc.out(out_nhwc, out_mem, px * 3);
         void* mm = ctx->get_scratch((size_t)n * 4 * sizeof(unsigned long long));
         launch_preprocess(ctx, din, dtype, n, ps_h, ps_w, static_cast<float*>(mm), dout);
-        if (out_mem == RFI_HOST)
-            RFI_CHECK_HIP(hipMemcpyAsync(out_nhwc, dout, px * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        if (tmp_in || tmp_out) {            // device-to-device calls stay asynchronous on the ctx stream
-            RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-            if (tmp_in) ctx->release(tmp_in);
-            if (tmp_out) ctx->release(tmp_out);
-        }
+        sc.finish();
     });
 }
 
 namespace {
-// device copy of `bytes` host bytes (or the pointer itself when already on the device)
-struct Staged {
-    rfi_ctx* ctx; void* dev; bool owned;
-    Staged(rfi_ctx* c, const void* p, int mem, size_t bytes) : ctx(c), dev(const_cast<void*>(p)), owned(false) {
-        if (mem == RFI_HOST && p && bytes) {
-            dev = ctx->alloc(bytes);
-            owned = true;
-            RFI_CHECK_HIP(hipMemcpyAsync(dev, p, bytes, hipMemcpyHostToDevice, ctx->stream));
-        }
-    }
-    ~Staged() {
-        if (owned) {
-            (void)hipStreamSynchronize(ctx->stream);
-            try { ctx->release(dev); } catch (...) {}
-        }
-    }
-};
 void check_table(const rfi_patch_src* t, int n, int n_planes, int c, int tt, int ps) {
     RFI_REQUIRE(n_planes > 0 && c > 0 && tt > 0 && ps > 0, "preprocess_gather: bad shape");
     RFI_REQUIRE((int64_t)n_planes * c * tt < ((int64_t)1 << 40), "preprocess_gather: waterfall too large");
@@ -960,15 +961,12 @@ int rfi_patch_any_flag(rfi_ctx* ctx, const uint8_t* flags, int flags_mem, int n_
         if (n == 0) return;
         check_table(table_host, n, n_planes, c, t, ps);
         ctx->activate();
-        Staged fl(ctx, flags, flags_mem, (size_t)n_planes * c * t);
-        Staged tb(ctx, table_host, RFI_HOST, (size_t)n * sizeof(rfi_patch_src));
-        unsigned* d_any = static_cast<unsigned*>(ctx->alloc((size_t)n * sizeof(unsigned)));
-        launch_patch_any_flag(ctx, static_cast<const uint8_t*>(fl.dev), static_cast<const rfi_patch_src*>(tb.dev), c, t,
-                              n, ps, d_any);
         std::vector<unsigned> h((size_t)n);
-        RFI_CHECK_HIP(hipMemcpyAsync(h.data(), d_any, (size_t)n * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-        RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-        ctx->release(d_any);
+        CallScope sc(ctx);
+        const uint8_t* fl = sc.in(flags, flags_mem, (size_t)n_planes * c * t);
+        const rfi_patch_src* tb = sc.in(table_host, RFI_HOST, (size_t)n);
+        launch_patch_any_flag(ctx, fl, tb, c, t, n, ps, sc.out(h.data(), RFI_HOST, (size_t)n));
+        sc.finish();
         for (int i = 0; i < n; ++i) any_out_host[i] = h[(size_t)i] ? 1 : 0;
     });
 }
@@ -983,26 +981,17 @@ int rfi_preprocess_gather(rfi_ctx* ctx, const void* planes, int planes_mem, int 
         if (n == 0) return;
         check_table(table_host, n, n_planes, c, t, ps);
         ctx->activate();
-        const size_t esz = dtype == RFI_C128 ? 16 : (dtype == RFI_F32 ? 4 : 8);
-        const size_t px = (size_t)n * ps * ps;
-        Staged pl(ctx, planes, planes_mem, (size_t)n_planes * c * t * esz);
-        Staged fl(ctx, flags, flags_mem, (size_t)n_planes * c * t);
-        Staged tb(ctx, table_host, RFI_HOST, (size_t)n * sizeof(rfi_patch_src));
-        float* dout = out_nhwc;
-        uint8_t* dlab = out_labels;
-        void *tmp_out = nullptr, *tmp_lab = nullptr;
-        if (out_mem == RFI_HOST) dout = static_cast<float*>(tmp_out = ctx->alloc(px * 3 * sizeof(float)));
-        if (out_labels && labels_mem == RFI_HOST) dlab = static_cast<uint8_t*>(tmp_lab = ctx->alloc(px));
+        const size_t px = (size_t)n * ps * ps, plane_px = (size_t)n_planes * c * t;
+        CallScope sc(ctx);
+        const void* pl = sc.in(planes, planes_mem, plane_px * dtype_bytes(dtype));
+        const uint8_t* fl = sc.in(flags, flags_mem, plane_px);
+        const rfi_patch_src* tb = sc.in(table_host, RFI_HOST, (size_t)n);
+        float* dout = sc.out(out_nhwc, out_mem, px * 3);
+        uint8_t* dlab = sc.out(out_labels, labels_mem, px);
         void* mm = ctx->get_scratch((size_t)n * 4 * sizeof(unsigned long long));
-        const auto* table_dev = static_cast<const rfi_patch_src*>(tb.dev);
-        launch_preprocess(ctx, pl.dev, dtype, n, ps, ps, static_cast<float*>(mm), dout, table_dev, c, t);
-        if (out_labels) launch_gather_labels(ctx, static_cast<const uint8_t*>(fl.dev), table_dev, c, t, n, ps, dlab);
-        if (tmp_out)
-            RFI_CHECK_HIP(hipMemcpyAsync(out_nhwc, dout, px * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        if (tmp_lab) RFI_CHECK_HIP(hipMemcpyAsync(out_labels, dlab, px, hipMemcpyDeviceToHost, ctx->stream));
-        RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));     // the staged table dies with this call
-        if (tmp_out) ctx->release(tmp_out);
-        if (tmp_lab) ctx->release(tmp_lab);
+        launch_preprocess(ctx, pl, dtype, n, ps, ps, static_cast<float*>(mm), dout, tb, c, t);
+        if (out_labels) launch_gather_labels(ctx, fl, tb, c, t, n, ps, dlab);
+        sc.finish();
     });
 }
 
@@ -1028,13 +1017,14 @@ int rfi_preprocess_real(rfi_ctx* ctx, const void* patches, int patches_mem, int 
         if (n == 0) return;
         ctx->activate();
         const int per = ps_h * ps_w;
-        const size_t px = (size_t)n * per, esz = dtype == RFI_F64 ? 8 : 4;
-        Staged in(ctx, patches, patches_mem, px * esz);
-        double* w = static_cast<double*>(ctx->alloc(px * sizeof(double)));
-        double* stat = static_cast<double*>(ctx->alloc((size_t)n * 2 * sizeof(double) + (size_t)n * sizeof(int)));
+        const size_t px = (size_t)n * per;
+        CallScope sc(ctx);
+        const void* in = sc.in(patches, patches_mem, px * dtype_bytes(dtype));
+        double* w = sc.temp<double>(px);
+        double* stat = static_cast<double*>(sc.temp<void>((size_t)n * 2 * sizeof(double) + (size_t)n * sizeof(int)));
         double *d_med = stat, *d_mad = stat + n;
         int* d_cnt = reinterpret_cast<int*>(stat + 2 * (size_t)n);
-        launch_to_abs_f64(ctx, in.dev, dtype, (int64_t)px, w);            // real dtypes: widening copy
+        launch_to_abs_f64(ctx, in, dtype, (int64_t)px, w);            // real dtypes: widening copy
         auto normalise = [&] {
             launch_patch_median(ctx, w, n, per, false, nullptr, false, d_med, nullptr, f32);
             launch_scale_by_median(ctx, w, n, per, d_med, f32);
@@ -1046,32 +1036,21 @@ int rfi_preprocess_real(rfi_ctx* ctx, const void* patches, int patches_mem, int 
             launch_replace_inf(ctx, w, n, per, d_mad, d_cnt);
         }
         if (normalize_after) normalise();
-        float* dout = out_nhwc;
-        uint8_t* dfl = flags_out;
-        void *tmp_out = nullptr, *tmp_fl = nullptr;
-        if (out_mem == RFI_HOST) dout = static_cast<float*>(tmp_out = ctx->alloc(px * 3 * sizeof(float)));
-        if (flags_out && flags_mem == RFI_HOST) dfl = static_cast<uint8_t*>(tmp_fl = ctx->alloc(px));
+        float* dout = sc.out(out_nhwc, out_mem, px * 3);
+        uint8_t* dfl = sc.out(flags_out, flags_mem, px);
         if (flags_out) {
             median_and_mad(ctx, w, n, per, false, d_med, d_mad, nullptr, f32);
             launch_mad_flags(ctx, w, n, per, d_med, d_mad, flag_sigma, dfl, f32);
         }
         void* mm = ctx->get_scratch((size_t)n * 4 * sizeof(unsigned long long));
-        float* w32 = nullptr;
         if (f32) {                                  // the channel kernels' float32 form on the float32 values
-            w32 = static_cast<float*>(ctx->alloc(px * sizeof(float)));
+            float* w32 = sc.temp<float>(px);
             launch_narrow_f32(ctx, w, (int64_t)px, w32);
             launch_preprocess(ctx, w32, RFI_F32, n, ps_h, ps_w, static_cast<float*>(mm), dout);
         } else {
             launch_preprocess(ctx, w, RFI_F64, n, ps_h, ps_w, static_cast<float*>(mm), dout);
         }
-        if (tmp_out) RFI_CHECK_HIP(hipMemcpyAsync(out_nhwc, dout, px * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        if (tmp_fl) RFI_CHECK_HIP(hipMemcpyAsync(flags_out, dfl, px, hipMemcpyDeviceToHost, ctx->stream));
-        RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-        ctx->release(w);
-        ctx->release(stat);
-        if (w32) ctx->release(w32);
-        if (tmp_out) ctx->release(tmp_out);
-        if (tmp_fl) ctx->release(tmp_fl);
+        sc.finish();
     });
 }
 
@@ -1083,21 +1062,16 @@ int rfi_mad_flags(rfi_ctx* ctx, const void* patches, int patches_mem, int dtype,
         if (n == 0) return;
         ctx->activate();
         const int per = ps_h * ps_w;
-        const size_t px = (size_t)n * per, esz = dtype == RFI_C128 ? 16 : (dtype == RFI_F32 ? 4 : 8);
-        Staged in(ctx, patches, patches_mem, px * esz);
-        double* w = static_cast<double*>(ctx->alloc(px * sizeof(double)));
-        double* stat = static_cast<double*>(ctx->alloc((size_t)n * 2 * sizeof(double)));
-        uint8_t* dfl = flags_out;
-        void* tmp_fl = nullptr;
-        if (flags_mem == RFI_HOST) dfl = static_cast<uint8_t*>(tmp_fl = ctx->alloc(px));
-        launch_to_abs_f64(ctx, in.dev, dtype, (int64_t)px, w);
+        const size_t px = (size_t)n * per;
+        CallScope sc(ctx);
+        const void* in = sc.in(patches, patches_mem, px * dtype_bytes(dtype));
+        double* w = sc.temp<double>(px);
+        double* stat = sc.temp<double>((size_t)n * 2);
+        uint8_t* dfl = sc.out(flags_out, flags_mem, px);
+        launch_to_abs_f64(ctx, in, dtype, (int64_t)px, w);
         median_and_mad(ctx, w, n, per, false, stat, stat + n, nullptr);
         launch_mad_flags(ctx, w, n, per, stat, stat + n, flag_sigma, dfl);
-        if (tmp_fl) RFI_CHECK_HIP(hipMemcpyAsync(flags_out, dfl, px, hipMemcpyDeviceToHost, ctx->stream));
-        RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-        ctx->release(w);
-        ctx->release(stat);
-        if (tmp_fl) ctx->release(tmp_fl);
+        sc.finish();
     });
 }
 
@@ -1116,22 +1090,15 @@ int rfi_generate_waterfalls(rfi_ctx* ctx, uint64_t seed, int n_samples, int n_po
         for (int s = 0; s < n_samples; ++s)
             RFI_REQUIRE(event_offsets_host[s] <= event_offsets_host[s + 1], "generate_waterfalls: offsets must ascend");
         ctx->activate();
-        const size_t px = (size_t)n_samples * n_pol * c * t, esz = out_dtype == RFI_C128 ? 16 : 8;
-        Staged ev(ctx, events_host, RFI_HOST, (size_t)std::max(n_events, 1) * sizeof(rfi_event));
-        Staged of(ctx, event_offsets_host, RFI_HOST, (size_t)(n_samples + 1) * sizeof(int32_t));
-        void* dpl = planes_out;
-        uint8_t* dfl = flags_out;
-        void *tmp_p = nullptr, *tmp_f = nullptr;
-        if (planes_mem == RFI_HOST) dpl = tmp_p = ctx->alloc(px * esz);
-        if (flags_mem == RFI_HOST) dfl = static_cast<uint8_t*>(tmp_f = ctx->alloc(px));
-        launch_synth(ctx, seed, n_samples, n_pol, c, t, noise_mjy, bandpass, bandpass_order, pol_corr,
-                     static_cast<const rfi_event*>(n_events ? ev.dev : nullptr), static_cast<const int*>(of.dev),
-                     out_dtype, dpl, dfl);
-        if (tmp_p) RFI_CHECK_HIP(hipMemcpyAsync(planes_out, dpl, px * esz, hipMemcpyDeviceToHost, ctx->stream));
-        if (tmp_f) RFI_CHECK_HIP(hipMemcpyAsync(flags_out, dfl, px, hipMemcpyDeviceToHost, ctx->stream));
-        RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-        if (tmp_p) ctx->release(tmp_p);
-        if (tmp_f) ctx->release(tmp_f);
+        const size_t px = (size_t)n_samples * n_pol * c * t;
+        CallScope sc(ctx);
+        const rfi_event* ev = sc.in(events_host, RFI_HOST, (size_t)std::max(n_events, 1));
+        const int32_t* of = sc.in(event_offsets_host, RFI_HOST, (size_t)(n_samples + 1));
+        void* dpl = sc.out(planes_out, planes_mem, px * dtype_bytes(out_dtype));
+        uint8_t* dfl = sc.out(flags_out, flags_mem, px);
+        launch_synth(ctx, seed, n_samples, n_pol, c, t, noise_mjy, bandpass, bandpass_order, pol_corr, n_events ? ev : nullptr,
+                     of, out_dtype, dpl, dfl);
+        sc.finish();
     });
 }
 
@@ -1143,29 +1110,13 @@ int rfi_confusion_counts(rfi_ctx* ctx, const void* pred, int pred_dtype, int pre
         RFI_REQUIRE((pred_dtype == RFI_U8 || pred_dtype == RFI_FLOAT32) &&
                         (truth_dtype == RFI_U8 || truth_dtype == RFI_FLOAT32), "confusion: dtype must be u8 or f32");
         ctx->activate();
-        const void *dp = pred, *dt = truth;
-        void *tp_ = nullptr, *tt_ = nullptr;
-        if (pred_mem == RFI_HOST && count) {
-            const size_t b = (size_t)count * (pred_dtype ? 4 : 1);
-            tp_ = ctx->alloc(b);
-            RFI_CHECK_HIP(hipMemcpyAsync(tp_, pred, b, hipMemcpyHostToDevice, ctx->stream));
-            dp = tp_;
-        }
-        if (truth_mem == RFI_HOST && count) {
-            const size_t b = (size_t)count * (truth_dtype ? 4 : 1);
-            tt_ = ctx->alloc(b);
-            RFI_CHECK_HIP(hipMemcpyAsync(tt_, truth, b, hipMemcpyHostToDevice, ctx->stream));
-            dt = tt_;
-        }
-        auto* d3 = static_cast<unsigned long long*>(ctx->alloc(3 * sizeof(unsigned long long)));
-        launch_confusion(ctx, dp, pred_dtype, dt, truth_dtype, count, d3);
         unsigned long long h3[3];
-        RFI_CHECK_HIP(hipMemcpyAsync(h3, d3, sizeof(h3), hipMemcpyDeviceToHost, ctx->stream));
-        RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+        CallScope sc(ctx);
+        const void* dp = sc.in(pred, pred_mem, (size_t)count * (pred_dtype ? 4 : 1));
+        const void* dt = sc.in(truth, truth_mem, (size_t)count * (truth_dtype ? 4 : 1));
+        launch_confusion(ctx, dp, pred_dtype, dt, truth_dtype, count, sc.out(h3, RFI_HOST, 3));
+        sc.finish();
         *tp = (int64_t)h3[0]; *fp = (int64_t)h3[1]; *fn = (int64_t)h3[2];
-        ctx->release(d3);
-        if (tp_) ctx->release(tp_);
-        if (tt_) ctx->release(tt_);
     });
 }
 int rfi_flag_statistics(rfi_ctx* ctx, const void* data, int data_mem, int dtype, int64_t count, const void* flags,
@@ -1185,21 +1136,22 @@ int rfi_flag_statistics(rfi_ctx* ctx, const void* data, int data_mem, int dtype,
         for (auto& r : res) r = rfi_flag_stats{0, 0, qnan, qnan, qnan, qnan, qnan};
         if (count > 0) {
             ctx->activate();
-            const size_t esz = dtype == RFI_C128 ? 16 : (dtype == RFI_F32 ? 4 : 8);
+            const size_t esz = dtype_bytes(dtype);
             const bool cplx = dtype == RFI_C128 || dtype == RFI_C64;
             // without flags the unflagged view IS the all view: compute it once
             const int views = flags ? (want & (RFI_FS_ALL | RFI_FS_CLEAN)) : RFI_FS_ALL;
-            Staged in(ctx, data, data_mem, (size_t)count * esz);
-            Staged fl(ctx, flags, flags_mem, flags ? (size_t)count : 0);
+            CallScope sc(ctx);
+            const void* in = sc.in(data, data_mem, (size_t)count * esz);
+            const void* fl = sc.in(flags, flags_mem, flags ? (size_t)count : 0);
             // workspace and |z| buffer in the context's scratch (kept between calls: no allocation per call)
             const size_t wsb = (flag_stats_ws_bytes() + 255) / 256 * 256;
             char* ws = static_cast<char*>(ctx->get_scratch(wsb + (cplx ? (size_t)count * (esz / 2) : 0)));
             void* mag = cplx ? ws + wsb : nullptr;
             auto* dout = reinterpret_cast<rfi_flag_stats*>(ws + flag_stats_ws_bytes() - sizeof(res));
-            launch_flag_stats(ctx, in.dev, dtype, count, static_cast<const uint8_t*>(fl.dev), views,
-                              (want & RFI_FS_MEDIANS) != 0, ws, mag, dout);
+            launch_flag_stats(ctx, in, dtype, count, static_cast<const uint8_t*>(fl), views, (want & RFI_FS_MEDIANS) != 0, ws,
+                              mag, dout);
             RFI_CHECK_HIP(hipMemcpyAsync(res, dout, sizeof(res), hipMemcpyDeviceToHost, ctx->stream));
-            RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+            RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));     // (the result lies in the scratch: also with device inputs)
             if (!flags) res[1] = res[0];
         }
         if (want & RFI_FS_ALL) *all_out = res[0];
@@ -1241,7 +1193,7 @@ namespace {
 // workspace of rfi_model_predict_flags that grows with the chunk (patch outputs, staged planes and outputs, the table)
 constexpr size_t kPredictBudget = size_t(1) << 30;
 
-// a temporary HIP stream / events, and a stream swap for profiled launches on another stream
+// a temporary HIP stream / events
 struct TmpStream {
     hipStream_t s = nullptr;
     TmpStream() { RFI_CHECK_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
@@ -1253,11 +1205,6 @@ struct TmpEvents {
         for (auto& x : e) RFI_CHECK_HIP(hipEventCreateWithFlags(&x, hipEventDisableTiming));
     }
     ~TmpEvents() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
-};
-struct OnStream {
-    rfi_ctx* c; hipStream_t old;
-    OnStream(rfi_ctx* ctx, hipStream_t s) : c(ctx), old(ctx->stream) { c->stream = s; }
-    ~OnStream() { c->stream = old; }
 };
 }  // namespace
 
@@ -1281,18 +1228,13 @@ int rfi_stitch_patches(rfi_ctx* ctx, const float* values, int values_mem, int ki
         ctx->activate();
         const int64_t ppp = tiling_patches_per_plane(c, t, *tiling);
         const size_t px = (size_t)n_planes * c * t;
-        Staged v(ctx, values, values_mem, (size_t)n_planes * ppp * tiling->ps * tiling->ps * sizeof(float));
-        void* df = flags_mem == RFI_HOST ? ctx->alloc(px) : flags;
-        void* dp = prob && prob_mem == RFI_HOST ? ctx->alloc(px * sizeof(float)) : prob;
-        struct Free {
-            rfi_ctx* c; void* a; void* b;
-            ~Free() { (void)hipStreamSynchronize(c->stream); try { if (a) c->release(a); if (b) c->release(b); } catch (...) {} }
-        } fr{ctx, df != flags ? df : nullptr, dp != prob ? dp : nullptr};
-        launch_stitch(ctx, static_cast<const float*>(v.dev), kind, n_planes, c, t, *tiling, combine, threshold,
-                      static_cast<uint8_t*>(df), static_cast<float*>(dp));
-        if (df != flags) RFI_CHECK_HIP(hipMemcpyAsync(flags, df, px, hipMemcpyDeviceToHost, ctx->stream));
-        if (dp != prob) RFI_CHECK_HIP(hipMemcpyAsync(prob, dp, px * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+        CallScope sc(ctx);
+        const float* v = sc.in(values, values_mem, (size_t)n_planes * ppp * tiling->ps * tiling->ps);
+        uint8_t* df = sc.out(flags, flags_mem, px);
+        float* dp = sc.out(prob, prob_mem, px);
+        launch_stitch(ctx, v, kind, n_planes, c, t, *tiling, combine, threshold, df, dp);
+        sc.finish();
+        RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));     // (with device pointers only too)
     });
 }
 
@@ -1319,7 +1261,7 @@ int rfi_model_predict_flags(rfi_model* m, const void* planes, int planes_mem, in
         ctx->activate();
         const int ps = tiling->ps;
         const int64_t ppp = tiling_patches_per_plane(c, t, *tiling);
-        const size_t esz = dtype == RFI_C128 ? 16 : 8;
+        const size_t esz = dtype_bytes(dtype);
         const size_t plane_px = (size_t)c * t, plane_bytes = plane_px * esz, patch_px = (size_t)ps * ps;
         const bool host_in = planes_mem == RFI_HOST, host_fl = flags_mem == RFI_HOST, host_pr = prob && prob_mem == RFI_HOST;
         const size_t out_px_bytes = (host_fl ? 1 : 0) + (host_pr ? 4 : 0);
@@ -1444,21 +1386,7 @@ int rfi_model_predict_flags(rfi_model* m, const void* planes, int planes_mem, in
 
 // ------------------------------------------------------------------------------------ kernel-level ops
 namespace {
-struct Scratch {
-    rfi_ctx* c;
-    std::vector<void*> v;
-    explicit Scratch(rfi_ctx* ctx) : c(ctx) {}
-    float* get(size_t floats) {
-        void* p = c->alloc(floats * sizeof(float));
-        v.push_back(p);
-        return static_cast<float*>(p);
-    }
-    ~Scratch() {
-        hipStreamSynchronize(c->stream);
-        for (void* p : v) c->release(p);
-    }
-};
-float* upload_lib_weight(rfi_ctx* ctx, Scratch& s, const float* dev_ref, size_t numel, bool convt,
+float* upload_lib_weight(rfi_ctx* ctx, CallScope& s, const float* dev_ref, size_t numel, bool convt,
                          int d0, int d1, int R) {
     // dev_ref holds the reference layout ON DEVICE; bounce through the host to convert
     std::vector<float> h(numel), lib;
@@ -1466,10 +1394,21 @@ float* upload_lib_weight(rfi_ctx* ctx, Scratch& s, const float* dev_ref, size_t 
     RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     if (convt) to_lib_convt(h.data(), d0, d1, lib);
     else to_lib_conv(h.data(), d0, d1, R, lib);
-    float* d = s.get(numel);
+    float* d = s.temp<float>(numel);
     RFI_CHECK_HIP(hipMemcpyAsync(d, lib.data(), numel * 4, hipMemcpyHostToDevice, ctx->stream));
     RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     return d;
+}
+// the reverse: a library-layout weight gradient on the device (3x3 conv [9][d0 = cout][d1 = cin], convT [4][cout][cin]
+// as d0 = cin, d1 = cout) to the reference layout at the caller's device pointer
+void store_ref_wgrad(rfi_ctx* ctx, const float* lib_dev, size_t numel, bool convt, int d0, int d1, float* dst_ref) {
+    std::vector<float> lib(numel), ref(numel);
+    RFI_CHECK_HIP(hipMemcpyAsync(lib.data(), lib_dev, numel * 4, hipMemcpyDeviceToHost, ctx->stream));
+    RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    if (convt) from_lib_convt(lib.data(), d0, d1, ref.data());
+    else from_lib_conv(lib.data(), d0, d1, 3, ref.data());
+    RFI_CHECK_HIP(hipMemcpyAsync(dst_ref, ref.data(), numel * 4, hipMemcpyHostToDevice, ctx->stream));
+    RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
 }
 
 // ---- the stride-2 layers on the plane kernels (bfloat16 flow of the ResNet-encoder model; impl 6): temporary plane copies
@@ -1479,23 +1418,23 @@ struct PlaneTmp {                 // a zero-tailed bf16 tensor [pixels][chunks *
     int nchunks = 0;
     PlaneSeg seg() const { return PlaneSeg{p, ps, nchunks}; }
 };
-PlaneTmp plane_tmp(rfi_ctx* ctx, Scratch& s, int64_t pixels, int C) {
+PlaneTmp plane_tmp(rfi_ctx* ctx, CallScope& s, int64_t pixels, int C) {
     PlaneTmp t;
     t.nchunks = plane_chunks(C);
     t.ps = (int64_t)t.nchunks * 16;
     const size_t bytes = (size_t)pixels * t.ps * 2 + 64;
-    t.p = reinterpret_cast<bf16_t*>(s.get((bytes + 3) / 4));
+    t.p = reinterpret_cast<bf16_t*>(s.temp<float>((bytes + 3) / 4));
     RFI_CHECK_HIP(hipMemsetAsync(t.p, 0, bytes, ctx->stream));
     return t;
 }
-PlaneTmp planes_of(rfi_ctx* ctx, Scratch& s, const float* x, int64_t pixels, int C) {
+PlaneTmp planes_of(rfi_ctx* ctx, CallScope& s, const float* x, int64_t pixels, int C) {
     PlaneTmp t = plane_tmp(ctx, s, pixels, C);
     launch_act_split(ctx, View{x, C}, pixels, C, InXform{}, 1, t.p, t.ps);
     return t;
 }
-bf16_t* wb_of(rfi_ctx* ctx, Scratch& s, const float* src, int taps, int Cout, int Cin, int seg0, int seg1) {
+bf16_t* wb_of(rfi_ctx* ctx, CallScope& s, const float* src, int taps, int Cout, int Cin, int seg0, int seg1) {
     const size_t e = wb_elems(taps, Cout, seg0, seg1, 1);
-    bf16_t* wb = reinterpret_cast<bf16_t*>(s.get((e * 2 + 64 + 3) / 4));
+    bf16_t* wb = reinterpret_cast<bf16_t*>(s.temp<float>((e * 2 + 64 + 3) / 4));
     RFI_CHECK_HIP(hipMemsetAsync(wb, 0, e * 2 + 64, ctx->stream));
     launch_weights_to_wb_one(ctx, WBDesc{src, wb, taps, Cout, Cin, {seg0, seg1}, 1});
     return wb;
@@ -1507,7 +1446,7 @@ int rfi_op_conv3x3(rfi_ctx* ctx, int impl, const float* x, int n, int h, int w, 
                    const float* in_shift, int in_relu, float* y) {
     return guarded([&] {
         ctx->activate();
-        Scratch s(ctx);
+        CallScope s(ctx);
         ConvArgs a;
         a.x = View{x, cin};
         a.N = n; a.H = h; a.W = w; a.Hin = h; a.Win = w; a.Cin = cin; a.Cout = cout;
@@ -1523,7 +1462,7 @@ int rfi_op_conv1x1(rfi_ctx* ctx, int impl, const float* x, int n, int h, int w, 
                    int cout, const float* in_scale, const float* in_shift, int in_relu, float* y) {
     return guarded([&] {
         ctx->activate();
-        Scratch s(ctx);
+        CallScope s(ctx);
         ConvArgs a;
         a.x = View{x, cin};
         a.N = n; a.H = h; a.W = w; a.Hin = h; a.Win = w; a.Cin = cin; a.Cout = cout;
@@ -1540,9 +1479,9 @@ int rfi_op_conv3x3_dgrad(rfi_ctx* ctx, int impl, const float* dy, int n, int h, 
                          const float* w_oihw, int cin, float* dx) {
     return guarded([&] {
         ctx->activate();
-        Scratch s(ctx);
+        CallScope s(ctx);
         float* wf = upload_lib_weight(ctx, s, w_oihw, (size_t)9 * cin * cout, false, cout, cin, 3);
-        float* wd = s.get((size_t)9 * cin * cout);
+        float* wd = s.temp<float>((size_t)9 * cin * cout);
         launch_weight_to_dgrad(ctx, wf, 9, cout, cin, 1, wd);
         ConvArgs a;
         a.x = View{dy, cout};
@@ -1558,7 +1497,7 @@ int rfi_op_conv3x3_wgrad(rfi_ctx* ctx, int impl, const float* x, const float* dy
                          float* dw_oihw) {
     return guarded([&] {
         ctx->activate();
-        Scratch s(ctx);
+        CallScope s(ctx);
         WgradArgs a;
         a.xop = View{x, cin};
         a.yop = View{dy, cout};
@@ -1567,16 +1506,11 @@ int rfi_op_conv3x3_wgrad(rfi_ctx* ctx, int impl, const float* x, const float* dy
         a.tap_stride = (int64_t)cin * cout;
         a.sy = cin; a.sx = 1;
         const size_t numel = (size_t)9 * cin * cout;
-        a.dw = s.get(numel);
+        a.dw = s.temp<float>(numel);
         a.slab_floats = wgrad_slab_floats(a, impl);
-        a.slab = s.get(a.slab_floats);
+        a.slab = s.temp<float>(a.slab_floats);
         launch_wgrad(ctx, a, impl);
-        std::vector<float> lib(numel), ref(numel);
-        RFI_CHECK_HIP(hipMemcpyAsync(lib.data(), a.dw, numel * 4, hipMemcpyDeviceToHost, ctx->stream));
-        RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-        from_lib_conv(lib.data(), cout, cin, 3, ref.data());
-        RFI_CHECK_HIP(hipMemcpyAsync(dw_oihw, ref.data(), numel * 4, hipMemcpyHostToDevice, ctx->stream));
-        RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+        store_ref_wgrad(ctx, a.dw, numel, false, cout, cin, dw_oihw);
     });
 }
 // ---- stride-2 convolutions of the ResNet-style encoder (model_resnet.cpp): 3x3 / pad 1 as a 2x2 convolution on the
@@ -1586,7 +1520,7 @@ int rfi_op_conv_s2(rfi_ctx* ctx, int impl, int ksize, const float* x, int n, int
     return guarded([&] {
         RFI_REQUIRE(ksize == 3 || ksize == 1, "conv_s2: kernel size 3 or 1");
         ctx->activate();
-        Scratch s(ctx);
+        CallScope s(ctx);
         if (impl == IMPL_PLANES_BF16) {           // the strided contraction on the full-resolution planes, bfloat16 output
             RFI_REQUIRE(cout % 4 == 0, "conv_s2 on planes: cout % 4 == 0");
             const int64_t Mo = (int64_t)n * (h / 2) * (w / 2);
@@ -1604,7 +1538,7 @@ int rfi_op_conv_s2(rfi_ctx* ctx, int impl, int ksize, const float* x, int n, int
             launch_planes_to_f32(ctx, yp.p, yp.ps, Mo, cout, 1, y, cout);
             return;
         }
-        float* xs = s.get((size_t)n * h * w * cin);
+        float* xs = s.temp<float>((size_t)n * h * w * cin);
         launch_s2d(ctx, x, n, h, w, cin, xs);
         ConvArgs a;
         a.N = n; a.H = h / 2; a.W = w / 2; a.Hin = h / 2; a.Win = w / 2; a.Cout = cout;
@@ -1614,7 +1548,7 @@ int rfi_op_conv_s2(rfi_ctx* ctx, int impl, int ksize, const float* x, int n, int
         a.S = 1;
         if (ksize == 3) {
             float* w3 = upload_lib_weight(ctx, s, w_oihw, (size_t)9 * cin * cout, false, cout, cin, 3);
-            float* w2 = s.get((size_t)16 * cin * cout);
+            float* w2 = s.temp<float>((size_t)16 * cin * cout);
             launch_w_s2d(ctx, w3, cout, cin, w2, true);
             a.w = w2; a.Cin = 4 * cin; a.R = 2; a.pad = 1;
         } else {
@@ -1628,13 +1562,13 @@ int rfi_op_conv_s2_dgrad(rfi_ctx* ctx, int impl, int ksize, const float* dy, int
     return guarded([&] {
         RFI_REQUIRE(ksize == 3 || ksize == 1, "conv_s2_dgrad: kernel size 3 or 1");
         ctx->activate();
-        Scratch s(ctx);
+        CallScope s(ctx);
         if (impl == IMPL_PLANES_BF16) {           // four 2x2 contractions of dY, one per parity class of the input pixel
             RFI_REQUIRE(cin % 4 == 0, "conv_s2_dgrad on planes: cin % 4 == 0");
             const int64_t Mo = (int64_t)n * (h / 2) * (w / 2), Mi = (int64_t)n * h * w;
             const PlaneTmp dyp = planes_of(ctx, s, dy, Mo, cout);
             const float* w3 = ksize == 3 ? upload_lib_weight(ctx, s, w_oihw, (size_t)9 * cin * cout, false, cout, cin, 3) : nullptr;
-            float* cls = s.get(s2_class_floats(cout, cin));
+            float* cls = s.temp<float>(s2_class_floats(cout, cin));
             launch_w_s2_classes(ctx, w3, ksize == 1 ? w_oihw : nullptr, cout, cin, cls);     // (a 1x1 layer: the second K segment of class 0)
             PlaneTmp dxp = plane_tmp(ctx, s, Mi, cin);
             bf16_t* dx16 = dxp.p;                 // dense [Mi][cin] bfloat16 (cin % 16 != 0: rows of cin elements inside the allocation)
@@ -1659,21 +1593,21 @@ int rfi_op_conv_s2_dgrad(rfi_ctx* ctx, int impl, int ksize, const float* dy, int
         a.x = View{dy, cout};
         a.Hout = h / 2; a.Wout = w / 2;
         a.S = 1;
-        float* dxp = s.get((size_t)n * h * w * cin);
+        float* dxp = s.temp<float>((size_t)n * h * w * cin);
         float* ds = nullptr;
         if (ksize == 3) {
             float* w3 = upload_lib_weight(ctx, s, w_oihw, (size_t)9 * cin * cout, false, cout, cin, 3);
-            float* w2 = s.get((size_t)16 * cin * cout);
-            float* wd = s.get((size_t)16 * cin * cout);
+            float* w2 = s.temp<float>((size_t)16 * cin * cout);
+            float* wd = s.temp<float>((size_t)16 * cin * cout);
             launch_w_s2d(ctx, w3, cout, cin, w2, true);
             launch_weight_to_dgrad(ctx, w2, 4, cout, 4 * cin, 1, wd);
             a.w = wd; a.Cout = 4 * cin; a.R = 2; a.pad = 0;
             a.y = MutView{dxp, 4 * cin};
         } else {
-            float* wd = s.get((size_t)cin * cout);
+            float* wd = s.temp<float>((size_t)cin * cout);
             launch_weight_to_dgrad(ctx, w_oihw, 1, cout, cin, 0, wd);
             RFI_CHECK_HIP(hipMemsetAsync(dxp, 0, (size_t)n * h * w * cin * sizeof(float), ctx->stream));
-            ds = s.get((size_t)n * (h / 2) * (w / 2) * cin);
+            ds = s.temp<float>((size_t)n * (h / 2) * (w / 2) * cin);
             a.w = wd; a.Cout = cin; a.R = 1; a.pad = 0;
             a.y = MutView{ds, cin};
         }
@@ -1686,7 +1620,7 @@ int rfi_op_conv_s2_wgrad(rfi_ctx* ctx, int impl, int ksize, const float* x, cons
     return guarded([&] {
         RFI_REQUIRE(ksize == 3 || ksize == 1, "conv_s2_wgrad: kernel size 3 or 1");
         ctx->activate();
-        Scratch s(ctx);
+        CallScope s(ctx);
         if (impl == IMPL_PLANES_BF16) {           // the strided weight gradient on the full-resolution planes
             const PlaneTmp xp = planes_of(ctx, s, x, (int64_t)n * h * w, cin);
             const PlaneTmp dyp = planes_of(ctx, s, dy, (int64_t)n * (h / 2) * (w / 2), cout);
@@ -1697,23 +1631,18 @@ int rfi_op_conv_s2_wgrad(rfi_ctx* ctx, int impl, int ksize, const float* x, cons
             a.R = ksize; a.S = 2; a.pad = ksize == 3 ? 1 : 0;
             a.tap_stride = (int64_t)cin * cout; a.sy = cin; a.sx = 1;
             const size_t numel = (size_t)ksize * ksize * cin * cout;
-            a.dw = s.get(numel);
+            a.dw = s.temp<float>(numel);
             a.slab_floats = pwgrad_slab_floats(a);
-            a.slab = s.get(a.slab_floats);
+            a.slab = s.temp<float>(a.slab_floats);
             launch_pwgrad(ctx, a);
             if (ksize == 1) {
                 RFI_CHECK_HIP(hipMemcpyAsync(dw_oihw, a.dw, numel * 4, hipMemcpyDeviceToDevice, ctx->stream));
                 return;
             }
-            std::vector<float> lib(numel), ref(numel);
-            RFI_CHECK_HIP(hipMemcpyAsync(lib.data(), a.dw, numel * 4, hipMemcpyDeviceToHost, ctx->stream));
-            RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-            from_lib_conv(lib.data(), cout, cin, 3, ref.data());
-            RFI_CHECK_HIP(hipMemcpyAsync(dw_oihw, ref.data(), numel * 4, hipMemcpyHostToDevice, ctx->stream));
-            RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+            store_ref_wgrad(ctx, a.dw, numel, false, cout, cin, dw_oihw);
             return;
         }
-        float* xs = s.get((size_t)n * h * w * cin);
+        float* xs = s.temp<float>((size_t)n * h * w * cin);
         launch_s2d(ctx, x, n, h, w, cin, xs);
         WgradArgs a;
         a.xop = View{xs, 4 * cin};
@@ -1725,30 +1654,25 @@ int rfi_op_conv_s2_wgrad(rfi_ctx* ctx, int impl, int ksize, const float* x, cons
         a.tap_stride = (int64_t)a.Cx * cout;
         a.sy = a.Cx;
         const size_t numel = (size_t)a.R * a.R * a.Cx * cout;
-        a.dw = s.get(numel);
+        a.dw = s.temp<float>(numel);
         a.slab_floats = wgrad_slab_floats(a, impl);
-        a.slab = s.get(a.slab_floats);
+        a.slab = s.temp<float>(a.slab_floats);
         launch_wgrad(ctx, a, impl);
         if (ksize == 1) {
             RFI_CHECK_HIP(hipMemcpyAsync(dw_oihw, a.dw, numel * 4, hipMemcpyDeviceToDevice, ctx->stream));
             return;
         }
         const size_t n3 = (size_t)9 * cin * cout;
-        float* w3 = s.get(n3);
+        float* w3 = s.temp<float>(n3);
         launch_w_s2d(ctx, w3, cout, cin, a.dw, false);
-        std::vector<float> lib(n3), ref(n3);
-        RFI_CHECK_HIP(hipMemcpyAsync(lib.data(), w3, n3 * 4, hipMemcpyDeviceToHost, ctx->stream));
-        RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-        from_lib_conv(lib.data(), cout, cin, 3, ref.data());
-        RFI_CHECK_HIP(hipMemcpyAsync(dw_oihw, ref.data(), n3 * 4, hipMemcpyHostToDevice, ctx->stream));
-        RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+        store_ref_wgrad(ctx, w3, n3, false, cout, cin, dw_oihw);
     });
 }
 int rfi_op_convt2x2(rfi_ctx* ctx, int impl, const float* x, int n, int h, int w, int cin,
                     const float* w_iohw, const float* bias, int cout, float* y) {
     return guarded([&] {
         ctx->activate();
-        Scratch s(ctx);
+        CallScope s(ctx);
         if (impl == IMPL_PLANES_BF16) {           // ONE 1x1 contraction on planes: the four taps are 4 cout output channels
             RFI_REQUIRE(cout % 32 == 0, "convt2x2 on planes: cout % 32 == 0");
             const int64_t Mi = (int64_t)n * h * w;
@@ -1784,9 +1708,9 @@ int rfi_op_convt2x2_dgrad(rfi_ctx* ctx, int impl, const float* dy, int n, int h,
                           const float* w_iohw, int cin, float* dx) {
     return guarded([&] {
         ctx->activate();
-        Scratch s(ctx);
+        CallScope s(ctx);
         float* wf = upload_lib_weight(ctx, s, w_iohw, (size_t)4 * cin * cout, true, cin, cout, 2);
-        float* wd = s.get((size_t)4 * cin * cout);
+        float* wd = s.temp<float>((size_t)4 * cin * cout);
         launch_weight_to_dgrad(ctx, wf, 4, cout, cin, 0, wd);
         if (impl == IMPL_PLANES_BF16) {           // a 2x2 stride-2 contraction of dy on planes, bfloat16 out
             RFI_REQUIRE(cin % 4 == 0, "convt2x2_dgrad on planes: cin % 4 == 0");
@@ -1818,7 +1742,7 @@ int rfi_op_convt2x2_wgrad(rfi_ctx* ctx, int impl, const float* x, const float* d
                           int cin, int cout, float* dw_iohw) {
     return guarded([&] {
         ctx->activate();
-        Scratch s(ctx);
+        CallScope s(ctx);
         WgradArgs a;
         a.xop = View{dy, cout};
         a.yop = View{x, cin};
@@ -1827,7 +1751,7 @@ int rfi_op_convt2x2_wgrad(rfi_ctx* ctx, int impl, const float* x, const float* d
         a.tap_stride = (int64_t)cin * cout;
         a.sy = 1; a.sx = cin;
         const size_t numel = (size_t)4 * cin * cout;
-        a.dw = s.get(numel);
+        a.dw = s.temp<float>(numel);
         if (impl == IMPL_PLANES_BF16) {           // the 2x2 stride-2 weight gradient on planes (Xop = the output gradient)
             const PlaneTmp dyp = planes_of(ctx, s, dy, (int64_t)4 * n * h * w, cout);
             const PlaneTmp xp = planes_of(ctx, s, x, (int64_t)n * h * w, cin);
@@ -1838,19 +1762,14 @@ int rfi_op_convt2x2_wgrad(rfi_ctx* ctx, int impl, const float* x, const float* d
             pa.R = 2; pa.S = 2; pa.pad = 0;
             pa.dw = a.dw; pa.tap_stride = a.tap_stride; pa.sy = 1; pa.sx = cin;
             pa.slab_floats = pwgrad_slab_floats(pa);
-            pa.slab = s.get(pa.slab_floats);
+            pa.slab = s.temp<float>(pa.slab_floats);
             launch_pwgrad(ctx, pa);
         } else {
-        a.slab_floats = wgrad_slab_floats(a, impl);
-        a.slab = s.get(a.slab_floats);
-        launch_wgrad(ctx, a, impl);
+            a.slab_floats = wgrad_slab_floats(a, impl);
+            a.slab = s.temp<float>(a.slab_floats);
+            launch_wgrad(ctx, a, impl);
         }
-        std::vector<float> lib(numel), ref(numel);
-        RFI_CHECK_HIP(hipMemcpyAsync(lib.data(), a.dw, numel * 4, hipMemcpyDeviceToHost, ctx->stream));
-        RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-        from_lib_convt(lib.data(), cin, cout, ref.data());
-        RFI_CHECK_HIP(hipMemcpyAsync(dw_iohw, ref.data(), numel * 4, hipMemcpyHostToDevice, ctx->stream));
-        RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+        store_ref_wgrad(ctx, a.dw, numel, true, cin, cout, dw_iohw);
     });
 }
 int rfi_op_roi_align(rfi_ctx* ctx, const float* x, int n, int h, int w, int c, const float* rois, int r,
@@ -1898,23 +1817,17 @@ int rfi_op_fastrcnn_loss(rfi_ctx* ctx, const float* head, int64_t rois, int num_
                          float beta, float* dhead, float* loss_classifier, float* loss_box_reg) {
     return guarded([&] {
         ctx->activate();
-        double* ws = static_cast<double*>(ctx->alloc(rpn_loss_ws_doubles() * 8 + 16));
-        struct Free { rfi_ctx* c; void* p; ~Free() { try { c->release(p); } catch (...) {} } } fr{ctx, ws};
-        float* out2 = reinterpret_cast<float*>(ws + rpn_loss_ws_doubles());
-        launch_fastrcnn_loss(ctx, head, rois, num_classes, labels, targets, beta, dhead, ws, out2);
-        float h2[2];
-        RFI_CHECK_HIP(hipMemcpyAsync(h2, out2, sizeof(h2), hipMemcpyDeviceToHost, ctx->stream));
-        RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-        if (loss_classifier) *loss_classifier = h2[0];
-        if (loss_box_reg) *loss_box_reg = h2[1];
+        read_losses(ctx, loss_classifier, loss_box_reg, [&](double* ws, float* out2) {
+            launch_fastrcnn_loss(ctx, head, rois, num_classes, labels, targets, beta, dhead, ws, out2);
+        });
     });
 }
 int rfi_op_anchor_match(rfi_ctx* ctx, const float* anchors, int64_t n, const float* gt_boxes, int n_gt, float fg_iou, float bg_iou,
                         int allow_low_quality, int8_t* labels, int32_t* matched, float* targets) {
     return guarded([&] {
         ctx->activate();
-        float* ws = static_cast<float*>(ctx->alloc((size_t)(n_gt > 0 ? n_gt : 1) * sizeof(float)));
-        struct Free { rfi_ctx* c; void* p; ~Free() { (void)hipStreamSynchronize(c->stream); try { c->release(p); } catch (...) {} } } fr{ctx, ws};
+        CallScope sc(ctx);
+        float* ws = sc.temp<float>((size_t)(n_gt > 0 ? n_gt : 1));
         launch_anchor_match(ctx, anchors, n, gt_boxes, n_gt, fg_iou, bg_iou, allow_low_quality != 0, ws,
                             reinterpret_cast<signed char*>(labels), matched, targets);
     });
@@ -1925,12 +1838,10 @@ int rfi_op_nms(rfi_ctx* ctx, const float* boxes_sorted, int n, float iou_thresho
         ctx->activate();
         if (n <= 0) { *n_keep = 0; return; }
         const int words = (n + 63) / 64;
-        auto* mask = static_cast<unsigned long long*>(ctx->alloc((size_t)n * words * 8));
-        struct Free { rfi_ctx* c; void* p; ~Free() { try { c->release(p); } catch (...) {} } } fr{ctx, mask};
-        launch_nms_mask(ctx, boxes_sorted, n, iou_threshold, mask);
         std::vector<unsigned long long> h((size_t)n * words), removed(words, 0ull);
-        RFI_CHECK_HIP(hipMemcpyAsync(h.data(), mask, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-        RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+        CallScope sc(ctx);
+        launch_nms_mask(ctx, boxes_sorted, n, iou_threshold, sc.out(h.data(), RFI_HOST, h.size()));
+        sc.finish();
         int k = 0;                                   // greedy scan in score order: keep i unless a kept box suppressed it
         for (int i = 0; i < n; ++i) {
             if (removed[i / 64] >> (i % 64) & 1ull) continue;
@@ -1946,11 +1857,11 @@ int rfi_op_anchor_match_batched(rfi_ctx* ctx, const float* anchors, int64_t n, i
                                 int allow_low_quality, int8_t* labels, int32_t* matched, float* targets) {
     return guarded([&] {
         ctx->activate();
-        float* best = static_cast<float*>(ctx->alloc((size_t)images * gt_max * 4 + 16));
-        struct Free { rfi_ctx* c; void* p; ~Free() { try { c->release(p); } catch (...) {} } } fr{ctx, best};
+        CallScope sc(ctx);
+        float* best = sc.temp<float>((size_t)images * gt_max + 4);
         launch_anchor_match_batched(ctx, anchors, n, anchor_stride, anchor_count, gt_boxes, images, gt_max, gt_count, fg_iou, bg_iou,
                                     allow_low_quality != 0, best, reinterpret_cast<signed char*>(labels), matched, targets);
-        RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));       // (the workspace is released on return)
+        sc.finish();
     });
 }
 int rfi_op_nms_batched(rfi_ctx* ctx, const float* boxes_sorted, const int32_t* count, int sets, int k, float iou_threshold, uint8_t* keep) {
@@ -1964,16 +1875,10 @@ int rfi_op_rpn_loss(rfi_ctx* ctx, const float* head, int64_t pixels, int anchors
                     float* loss_box) {
     return guarded([&] {
         ctx->activate();
-        double* ws = static_cast<double*>(ctx->alloc(rpn_loss_ws_doubles() * 8 + 16));
-        struct Free { rfi_ctx* c; void* p; ~Free() { try { c->release(p); } catch (...) {} } } fr{ctx, ws};
-        float* out2 = reinterpret_cast<float*>(ws + rpn_loss_ws_doubles());
-        launch_rpn_loss(ctx, head, pixels, anchors_per_pixel, reinterpret_cast<const signed char*>(labels), targets, num_sampled, beta,
-                        dhead, ws, out2);
-        float h2[2];
-        RFI_CHECK_HIP(hipMemcpyAsync(h2, out2, sizeof(h2), hipMemcpyDeviceToHost, ctx->stream));
-        RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-        if (loss_objectness) *loss_objectness = h2[0];
-        if (loss_box) *loss_box = h2[1];
+        read_losses(ctx, loss_objectness, loss_box, [&](double* ws, float* out2) {
+            launch_rpn_loss(ctx, head, pixels, anchors_per_pixel, reinterpret_cast<const signed char*>(labels), targets, num_sampled,
+                            beta, dhead, ws, out2);
+        });
     });
 }
 int rfi_op_rpn_loss_dev(rfi_ctx* ctx, const float* head, int64_t pixels, int anchors_per_pixel, const int8_t* labels,
@@ -2104,9 +2009,9 @@ int rfi_op_bn_backward16(rfi_ctx* ctx, const uint16_t* da, const uint16_t* y, in
     return guarded([&] {
         ctx->activate();
         RFI_REQUIRE(m > 0 && c > 0 && c % 16 == 0, "bn_backward16: channels in whole 16-channel chunks");
-        Scratch s(ctx);
-        float* ws = s.get(std::max(bn_bwd_ws_floats(m, c), channel_sum_ws_floats(m, c)) + 16);
-        float* c12 = s.get((size_t)2 * c);
+        CallScope s(ctx);
+        float* ws = s.temp<float>(std::max(bn_bwd_ws_floats(m, c), channel_sum_ws_floats(m, c)) + 16);
+        float* c12 = s.temp<float>((size_t)2 * c);
         launch_bn_bwd_reduce(ctx, YRef(da, (int64_t)c), YRef(y, (int64_t)c), m, c, scale, shift, mean, invstd, ws, c12, c12 + c, dgamma, dbeta, slope);
         launch_bn_bwd_apply(ctx, YRef(da, (int64_t)c), YRef(y, (int64_t)c), m, c, scale, shift, mean, invstd, gamma, c12, c12 + c, ws, dbias, slope, dy,
                             (int64_t)c, 1);
@@ -2165,9 +2070,9 @@ int rfi_op_fpn_merge_backward(rfi_ctx* ctx, const float* dout, int n, int h, int
 int rfi_op_bn_stats(rfi_ctx* ctx, const float* y, int64_t m, int c, float* mean, float* var_biased) {
     return guarded([&] {
         ctx->activate();
-        Scratch s(ctx);
-        float* ws = s.get(bn_stats_ws_floats(c));
-        float* tmp = s.get((size_t)6 * c);
+        CallScope s(ctx);
+        float* ws = s.temp<float>(bn_stats_ws_floats(c));
+        float* tmp = s.temp<float>((size_t)6 * c);
         std::vector<float> ones((size_t)c, 1.0f), zeros((size_t)c, 0.0f);
         RFI_CHECK_HIP(hipMemcpyAsync(tmp, ones.data(), c * 4, hipMemcpyHostToDevice, ctx->stream));
         RFI_CHECK_HIP(hipMemcpyAsync(tmp + c, zeros.data(), c * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -2196,11 +2101,11 @@ int rfi_op_bn_relu_backward(rfi_ctx* ctx, const float* y, int64_t m, int c, cons
                             const float* beta, float* da_inout, float* dgamma, float* dbeta, float* dbias) {
     return guarded([&] {
         ctx->activate();
-        Scratch s(ctx);
+        CallScope s(ctx);
         size_t wsf = bn_stats_ws_floats(c);
         if (bn_bwd_ws_floats(m, c) > wsf) wsf = bn_bwd_ws_floats(m, c);
-        float* ws = s.get(wsf);
-        float* t = s.get((size_t)6 * c);     // mean | invstd | scale | shift | c1 | c2
+        float* ws = s.temp<float>(wsf);
+        float* t = s.temp<float>((size_t)6 * c);     // mean | invstd | scale | shift | c1 | c2
         launch_bn_stats(ctx, y, m, c, ws);
         launch_bn_finalize(ctx, ws, m, c, gamma, beta, nullptr, nullptr, 0, t, t + c, t + 2 * c, t + 3 * c,
                            nullptr);

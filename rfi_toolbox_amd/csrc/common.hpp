@@ -8,6 +8,7 @@
 #include <mutex>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <unordered_set>
 #include <vector>
@@ -134,6 +135,8 @@ struct rfi_ctx {
 
     void* alloc(size_t bytes);
     void release(void* p);
+    // a persistent device copy of a host table the caller is about to drop (waits for it; the caller releases it)
+    void* upload_table(const void* host, size_t bytes);
     void activate() const;   // hipSetDevice
     hipEvent_t get_event();
     void drain_profile();
@@ -165,6 +168,56 @@ struct ProfScope {
             c->fam[fam].launches += 1;
             c->pending.push_back({a, b, fam, fl, by, std::move(label)});
         }
+    }
+};
+
+// Device memory one call needs for itself -- workspace, device copies of host inputs, device stand-ins for host
+// outputs -- all used on the stream current when the scope opens.  finish() enqueues the copies back to the host
+// outputs and, if the scope holds anything, waits for that stream (errors reported): the host outputs are then
+// written.  The destructor runs on every exit, a throw included: it waits for that stream if the scope holds
+// anything, releases everything, and never throws.  Counts are in elements (of `void`: bytes).
+struct CallScope {
+    explicit CallScope(rfi_ctx* ctx) : c(ctx), stream(ctx->stream) {}
+    CallScope(const CallScope&) = delete;
+    CallScope& operator=(const CallScope&) = delete;
+    template <class T> T* temp(size_t count) { return static_cast<T*>(take(count * size_of<T>())); }
+    // p itself if it is not a host pointer, null or count 0; else a device copy
+    template <class T> const T* in(const T* p, int mem, size_t count) {
+        if (mem != RFI_HOST || !p || !count) return p;
+        T* d = temp<T>(count);
+        RFI_CHECK_HIP(hipMemcpyAsync(d, p, count * size_of<T>(), hipMemcpyHostToDevice, stream));
+        return d;
+    }
+    // p itself if it is not a host pointer (or null); else a device buffer that finish() copies to p
+    template <class T> T* out(T* p, int mem, size_t count) {
+        if (mem != RFI_HOST || !p) return p;
+        T* d = temp<T>(count);
+        back.push_back(Back{p, d, count * size_of<T>()});
+        return d;
+    }
+    void finish() {
+        for (const Back& b : back) RFI_CHECK_HIP(hipMemcpyAsync(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost, stream));
+        back.clear();
+        if (!held.empty()) RFI_CHECK_HIP(hipStreamSynchronize(stream));
+    }
+    ~CallScope() {
+        if (held.empty()) return;
+        (void)hipStreamSynchronize(stream);
+        for (void* p : held) try { c->release(p); } catch (...) {}
+    }
+
+   private:
+    struct Back { void* host; const void* dev; size_t bytes; };
+    rfi_ctx* c;
+    hipStream_t stream;
+    std::vector<void*> held;
+    std::vector<Back> back;
+    template <class T> static constexpr size_t size_of() { return sizeof(std::conditional_t<std::is_void<T>::value, char, T>); }
+    void* take(size_t bytes) {
+        held.reserve(held.size() + 1);          // (so that push_back cannot throw with the allocation in hand)
+        void* p = c->alloc(bytes);
+        held.push_back(p);
+        return p;
     }
 };
 

@@ -752,12 +752,8 @@ void launch_conv(rfi_ctx* ctx, ConvArgs& a, int impl) {
         // conv_ws: [9][Cout][Cin]; gemm_ws: the transposed conv forward as ONE tap of 4 Cout channels, its input gradient
         // as four taps, a 1x1 conv as one tap
         const int taps = gw ? (a.R == 2 ? 4 : 1) : 9, cout = gw && a.zgroups == 4 ? 4 * a.Cout : a.Cout;
-        const size_t we = wb_elems(taps, cout, a.Cin, 0, P);
-        bf16_t* wb = static_cast<bf16_t*>(ctx->alloc(we * 2 + 64));
-        struct Free {
-            rfi_ctx* c; void* p;
-            ~Free() { (void)hipStreamSynchronize(c->stream); try { c->release(p); } catch (...) {} }
-        } fr{ctx, wb};
+        CallScope sc(ctx);
+        bf16_t* wb = sc.temp<bf16_t>(wb_elems(taps, cout, a.Cin, 0, P) + 32);
         launch_weights_to_wb_one(ctx, WBDesc{a.w, wb, taps, cout, a.Cin, {a.Cin, 0}, P});
         if (gw) launch_gemm_ws(ctx, a, wb);
         else launch_conv_ws(ctx, a, wb, P);
@@ -800,24 +796,16 @@ void launch_conv(rfi_ctx* ctx, ConvArgs& a, int impl) {
         return;
     }
     // 3 x bf16: the filters are read pre-split (ConvArgs::w3); callers that only have float32 weights (the
-    // kernel-level API) get a temporary split copy
-    float* tmp_w3 = nullptr;
+    // kernel-level API) get a temporary split copy, and their ConvArgs::w3 is null again on return
+    CallScope sc(ctx);
+    struct ClearW3 { ConvArgs* a; ~ClearW3() { if (a) a->w3 = nullptr; } } clear_w3{nullptr};
     if (a.bf16x3 && !a.w3) {
         const int taps = a.R * a.R * a.zgroups;
-        tmp_w3 = static_cast<float*>(ctx->alloc(weights_x3_floats(taps, a.Cout, a.Cin) * sizeof(float)));
-        launch_weights_to_x3(ctx, a.w, taps, a.Cout, a.Cin, tmp_w3);
-        a.w3 = tmp_w3;
+        float* w3 = sc.temp<float>(weights_x3_floats(taps, a.Cout, a.Cin));
+        launch_weights_to_x3(ctx, a.w, taps, a.Cout, a.Cin, w3);
+        a.w3 = w3;
+        clear_w3.a = &a;
     }
-    struct FreeTmp {
-        rfi_ctx* c; float* p; ConvArgs& a;
-        ~FreeTmp() {
-            if (p) {
-                (void)hipStreamSynchronize(c->stream);
-                try { c->release(p); } catch (...) {}
-                a.w3 = nullptr;
-            }
-        }
-    } free_tmp{ctx, tmp_w3, a};
     const double flops = a.algo_flops >= 0 ? a.algo_flops
                                            : 2.0 * a.N * a.H * a.W * (double)a.Cout * a.R * a.R * a.Cin * a.zgroups;
     std::string label;

@@ -817,12 +817,9 @@ void launch_pconv_from_f32(rfi_ctx* ctx, ConvArgs& c, int P) {
     RFI_REQUIRE(c.R == 3 && c.S == 1 && c.pad == 1 && c.zgroups == 1, "pconv bridge: 3x3 stride-1 only");
     const int64_t pix = (int64_t)c.N * c.Hin * c.Win;
     const size_t xe = plane_elems(pix, c.Cin, P), we = wb_elems(9, c.Cout, c.Cin, 0, P);
-    bf16_t* xp = static_cast<bf16_t*>(ctx->alloc(xe * 2 + 64));
-    bf16_t* wb = static_cast<bf16_t*>(ctx->alloc(we * 2 + 64));
-    struct Free {
-        rfi_ctx* c; void* a; void* b;
-        ~Free() { (void)hipStreamSynchronize(c->stream); try { c->release(a); c->release(b); } catch (...) {} }
-    } fr{ctx, xp, wb};
+    CallScope sc(ctx);
+    bf16_t* xp = sc.temp<bf16_t>(xe + 32);
+    bf16_t* wb = sc.temp<bf16_t>(we + 32);
     RFI_CHECK_HIP(hipMemsetAsync(reinterpret_cast<char*>(xp) + xe * 2, 0, 64, ctx->stream));
     RFI_CHECK_HIP(hipMemsetAsync(reinterpret_cast<char*>(wb) + we * 2, 0, 64, ctx->stream));
     const int64_t ps = (int64_t)plane_chunks(c.Cin) * P * 16;

@@ -280,9 +280,7 @@ void UNetModel::prepare_shape(int n, int h, int w) {
             dbias_max_c = std::max(dbias_max_c, out_ch * feat);
         }
         dbias_n = (int)hd.size();
-        dbias_descs = ctx->alloc(hd.size() * sizeof(FinishSumDesc));
-        RFI_CHECK_HIP(hipMemcpyAsync(dbias_descs, hd.data(), hd.size() * sizeof(FinishSumDesc), hipMemcpyHostToDevice, ctx->stream));
-        RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));     // hd goes out of scope
+        dbias_descs = ctx->upload_table(hd.data(), hd.size() * sizeof(FinishSumDesc));
     }
     if (resnet_encoder && !planesP) prepare_resnet(n, h, w);
     pN = n; pH = h; pW = w;
@@ -329,10 +327,7 @@ void rfi_model::refresh_dgrad_weights() {
         }
         relayout_n = (int)h.size();
         relayout_tiles = relayout_assign_tiles(h.data(), relayout_n);
-        relayout_descs = ctx->alloc(h.size() * sizeof(RelayoutDesc));
-        RFI_CHECK_HIP(hipMemcpyAsync(relayout_descs, h.data(), h.size() * sizeof(RelayoutDesc),
-                                     hipMemcpyHostToDevice, ctx->stream));
-        RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));     // h goes out of scope
+        relayout_descs = ctx->upload_table(h.data(), h.size() * sizeof(RelayoutDesc));
     }
     // Split rebuild (wd_split_ok): the forward pass needs the forward-direction copies only, so the dgrad layout and its
     // B-operand images are rebuilt on the SIDE stream (idle during the forward pass) under the first convs; backward() waits
@@ -395,9 +390,7 @@ void rfi_model::refresh_dgrad_weights() {
             }
             x3_for_shape = pH * 65536 + pW;
             x3_n = (int)h.size();
-            x3_descs = ctx->alloc((h.size() + 1) * sizeof(X3Desc));
-            if (x3_n) RFI_CHECK_HIP(hipMemcpyAsync(x3_descs, h.data(), h.size() * sizeof(X3Desc), hipMemcpyHostToDevice, ctx->stream));
-            RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));     // h goes out of scope
+            x3_descs = ctx->upload_table(h.data(), h.size() * sizeof(X3Desc));
         }
         if (x3_n) launch_weights_to_x3_batched(ctx, static_cast<const X3Desc*>(x3_descs), x3_n, x3_bytes);
         x3_fresh = true;
@@ -502,9 +495,7 @@ void rfi_model::refresh_ws_weights(int P, int which) {
         ws_bytes += ws_bytes_fwd;
         hd.insert(hd.end(), hdg.begin(), hdg.end());
         ws_n = (int)hd.size();
-        ws_descs = ctx->alloc(hd.size() * sizeof(WBDesc));
-        RFI_CHECK_HIP(hipMemcpyAsync(ws_descs, hd.data(), hd.size() * sizeof(WBDesc), hipMemcpyHostToDevice, ctx->stream));
-        RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));     // hd goes out of scope
+        ws_descs = ctx->upload_table(hd.data(), hd.size() * sizeof(WBDesc));
     }
     const WBDesc* descs = static_cast<const WBDesc*>(ws_descs);
     if (which == 0 && ws_n) launch_weights_to_wb(ctx, descs, ws_n, ws_bytes);

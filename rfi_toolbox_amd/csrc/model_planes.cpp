@@ -258,9 +258,7 @@ void UNetModel::refresh_plane_weights(int which) {
             }
         }
         wb_n = (int)hd.size();
-        wb_descs = ctx->alloc(hd.size() * sizeof(WBDesc));
-        RFI_CHECK_HIP(hipMemcpyAsync(wb_descs, hd.data(), hd.size() * sizeof(WBDesc), hipMemcpyHostToDevice, ctx->stream));
-        RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));     // hd goes out of scope
+        wb_descs = ctx->upload_table(hd.data(), hd.size() * sizeof(WBDesc));
     }
     const WBDesc* descs = static_cast<const WBDesc*>(wb_descs);
     if (which != 2) launch_weights_to_wb(ctx, descs, wb_n_fwd, wb_bytes_fwd);

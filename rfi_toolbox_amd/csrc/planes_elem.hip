@@ -416,11 +416,9 @@ void launch_weights_to_wb(rfi_ctx* ctx, const WBDesc* descs_dev, int n, double t
     check_launch("weights_to_wb");
 }
 void launch_weights_to_wb_one(rfi_ctx* ctx, const WBDesc& d) {
-    WBDesc* dev = static_cast<WBDesc*>(ctx->alloc(sizeof(WBDesc)));
-    RFI_CHECK_HIP(hipMemcpyAsync(dev, &d, sizeof(WBDesc), hipMemcpyHostToDevice, ctx->stream));
-    launch_weights_to_wb(ctx, dev, 1, 0);
-    RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));         // &d is the caller's stack; dev is freed here
-    ctx->release(dev);
+    CallScope sc(ctx);
+    launch_weights_to_wb(ctx, sc.in(&d, RFI_HOST, 1), 1, 0);
+    sc.finish();                                              // &d is the caller's stack
 }
 
 }  // namespace rfi

@@ -432,12 +432,9 @@ void launch_pwgrad_from_f32(rfi_ctx* ctx, const WgradArgs& w, int P) {
     RFI_REQUIRE(w.R == 3 && w.S == 1 && w.pad == 1, "pwgrad bridge: 3x3 stride-1 only");
     const int64_t xpix = (int64_t)w.N * w.Hx * w.Wx, ypix = (int64_t)w.N * w.H * w.W;
     const size_t xe = plane_elems(xpix, w.Cx, P), ye = plane_elems(ypix, w.Cy, P);
-    bf16_t* xp = static_cast<bf16_t*>(ctx->alloc(xe * 2 + 64));
-    bf16_t* yp = static_cast<bf16_t*>(ctx->alloc(ye * 2 + 64));
-    struct Free {
-        rfi_ctx* c; void* a; void* b;
-        ~Free() { (void)hipStreamSynchronize(c->stream); try { c->release(a); c->release(b); } catch (...) {} }
-    } fr{ctx, xp, yp};
+    CallScope sc(ctx);
+    bf16_t* xp = sc.temp<bf16_t>(xe + 32);
+    bf16_t* yp = sc.temp<bf16_t>(ye + 32);
     RFI_CHECK_HIP(hipMemsetAsync(reinterpret_cast<char*>(xp) + xe * 2, 0, 64, ctx->stream));
     RFI_CHECK_HIP(hipMemsetAsync(reinterpret_cast<char*>(yp) + ye * 2, 0, 64, ctx->stream));
     const int64_t xs = (int64_t)plane_chunks(w.Cx) * P * 16, ys = (int64_t)plane_chunks(w.Cy) * P * 16;

@@ -187,3 +187,43 @@ def test_mad_flags_of_complex_input_on_device(dtype):
     assert b.labels.numpy().any()
     np.testing.assert_array_equal(a.labels.numpy(), b.labels.numpy())
     np.testing.assert_allclose(a.images.numpy(), b.images.numpy(), rtol=0, atol=2e-6)
+
+
+def test_failed_preprocess_calls_release_their_device_temporaries():
+    """A call that stages host data and then fails on an argument check leaves no device memory behind: the context's
+    allocation count is what the valid calls (and the grow-only scratch they made) left, and the context stays usable."""
+    import ctypes as C
+
+    from rfi_toolbox_amd import runtime
+    from rfi_toolbox_amd._lib import F64, HOST, lib
+
+    ctx = runtime.Context(0)          # a context of its own: arrays of other tests freed meanwhile cannot move the count
+    try:
+        def ptr(a):
+            return a.ctypes.data_as(C.c_void_p)
+
+        def calls(pixels):
+            """rfi_preprocess_patches and rfi_preprocess_real on one float64 host row -> (rc, last error) of each"""
+            x = np.random.default_rng(pixels).random((1, 1, pixels))
+            out = np.empty((1, 1, pixels, 3), np.float32)
+            rc = lib.rfi_preprocess_patches(ctx.handle, ptr(x), HOST, F64, 1, 1, pixels, ptr(out), HOST)
+            res = [(rc, lib.rfi_last_error().decode())]
+            rc = lib.rfi_preprocess_real(ctx.handle, ptr(x), HOST, F64, 1, 1, pixels, 0, 0, 0, 3.0, ptr(out), HOST,
+                                         None, HOST)
+            res.append((rc, lib.rfi_last_error().decode()))
+            return res
+
+        def allocations():
+            n, b = C.c_int64(), C.c_uint64()
+            assert lib.rfi_ctx_allocations(ctx.handle, C.byref(n), C.byref(b)) == 0
+            return n.value, b.value
+
+        assert [rc for rc, _ in calls(4096)] == [0, 0]
+        before = allocations()
+        for rc, err in calls(4097):       # 64-bit rows longer than 4,096 pixels: refused after the host data is staged
+            assert rc == 1 and "patch rows this long" in err, err
+        assert allocations() == before
+        assert [rc for rc, _ in calls(4096)] == [0, 0]
+        assert allocations() == before
+    finally:
+        lib.rfi_ctx_destroy(ctx.handle)
