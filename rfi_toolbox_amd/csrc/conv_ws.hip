@@ -675,20 +675,21 @@ void launch_conv_ws(rfi_ctx* ctx, ConvArgs& a, const bf16_t* wB, int P) {
     d.stats = nullptr;
     d.stamps = nullptr;
     d.wide_epi = a.y.pstride % 4 == 0 && (reinterpret_cast<uintptr_t>(a.y.p) & 15) == 0;
-    const double flops = a.algo_flops >= 0 ? a.algo_flops : 2.0 * a.N * a.H * a.W * (double)a.Cout * 9 * a.Cin;
-    std::string label;
-    if (ctx->profiling)
-        label = "conv_ws N" + std::to_string(a.N) + " " + std::to_string(a.H) + "x" + std::to_string(a.W) + " " +
-                std::to_string(a.Cin) + "->" + std::to_string(a.Cout) + (a.xf.scale ? " xf" : "") + (P == 3 ? " 3xbf16" : " bf16");
-    const double bytes = 4.0 * ((double)a.N * a.H * a.W * a.Cin + 9.0 * a.Cin * a.Cout) + 4.0 * a.N * a.H * a.W * a.Cout;
-    ProfScope ps(ctx, FAM_CONV_MFMA, flops, bytes, label);
-    const int xf = !a.xf.scale ? 0 : (a.xf.relu == 1 || (a.xf.relu == 2 && a.xf.slope == 0.0f)) ? 1 : 2;
     // wider channel blocks cut the producers' work per MFMA (64 channels for the split arithmetic; 128 where one MFMA
     // stands for a block product); they are used where the grid still covers the chip (tiles x blocks >= ~256 workgroups)
     const int64_t tiles = (a.W >= 16 ? (int64_t)a.N : cdiv(a.N, 4)) * cdiv(a.H, a.W >= 32 ? 8 : a.W >= 16 ? 16 : 8) * cdiv(a.W, a.W >= 32 ? 32 : a.W >= 16 ? 16 : 8);
     int ntl = 1;
     if (a.Cout > 32 && tiles * cdiv(d.ncb, 2) >= 224) ntl = 2;
     if (P == 1 && a.Cout > 64 && tiles * cdiv(d.ncb, 4) >= 224) ntl = 4;
+    const double flops = a.algo_flops >= 0 ? a.algo_flops : 2.0 * a.N * a.H * a.W * (double)a.Cout * 9 * a.Cin;
+    std::string label;
+    if (ctx->profiling)
+        label = "conv_ws N" + std::to_string(a.N) + " " + std::to_string(a.H) + "x" + std::to_string(a.W) + " " +
+                std::to_string(a.Cin) + "->" + std::to_string(a.Cout) + (a.xf.scale ? " xf" : "") + (P == 3 ? " 3xbf16" : " bf16") +
+                (a.W >= 32 ? " t8x32" : a.W >= 16 ? " t16x16" : " t4x8x8") + " ntl" + std::to_string(ntl);      // (the tile family of dispatch_ws)
+    const double bytes = 4.0 * ((double)a.N * a.H * a.W * a.Cin + 9.0 * a.Cin * a.Cout) + 4.0 * a.N * a.H * a.W * a.Cout;
+    ProfScope ps(ctx, FAM_CONV_MFMA, flops, bytes, label);
+    const int xf = !a.xf.scale ? 0 : (a.xf.relu == 1 || (a.xf.relu == 2 && a.xf.slope == 0.0f)) ? 1 : 2;
     if (P == 3) {
         if (ntl == 2) dispatch_xf<2, 3>(ctx, a, d, xf);
         else dispatch_xf<1, 3>(ctx, a, d, xf);

@@ -380,16 +380,16 @@ void launch_gemm_ws(rfi_ctx* ctx, ConvArgs& a, const bf16_t* wB3) {
     d.bias = a.bias;
     d.y = a.y.p; d.y_ps = a.y.pstride;
     const double flops = a.algo_flops >= 0 ? a.algo_flops : 2.0 * d.M * (double)d.Ngemm * a.Cin * d.ntap;
+    // 8 blocks per workgroup where the grid still covers the chip, else 4 (2 for a 64-channel output)
+    const bool wide = d.ncb > 4 && cdiv(d.M, TM) * cdiv(d.ncb, 8) >= 192;
     std::string label;
     if (ctx->profiling)
         label = std::string("gemm_ws ") + (a.zgroups == 4 ? "convT" : a.R == 2 ? "convT-dgrad" : "1x1") + " N" + std::to_string(a.N) + " " +
                 std::to_string(a.H) + "x" + std::to_string(a.W) + " " + std::to_string(a.Cin) + "->" + std::to_string(a.Cout) +
-                (a.xf.scale ? " xf" : "") + " 3xbf16";
+                (a.xf.scale ? " xf" : "") + " 3xbf16" + (wide ? " nb8 wide" : d.ncb <= 2 ? " nb2" : " nb4");
     const double bytes = 4.0 * ((double)a.N * a.Hin * a.Win * a.Cin + (double)d.ntap * a.Cin * d.Ngemm) + 4.0 * d.M * (double)d.Ngemm;
     ProfScope ps(ctx, FAM_CONV_MFMA, flops, bytes, label);
     const int xf = !a.xf.scale ? 0 : (a.xf.relu == 1 || (a.xf.relu == 2 && a.xf.slope == 0.0f)) ? 1 : 2;
-    // 8 blocks per workgroup where the grid still covers the chip, else 4 (2 for a 64-channel output)
-    const bool wide = d.ncb > 4 && cdiv(d.M, TM) * cdiv(d.ncb, 8) >= 192;
     // (measured and not kept: 64-channel column groups with eight producer waves where 128-channel ones leave half the CUs
     // without a workgroup -- the 8 x 8 maps: the kernel alone 59 -> 53 us, the step +0.7 %: the idle CUs are where the side
     // stream's weight gradient runs)

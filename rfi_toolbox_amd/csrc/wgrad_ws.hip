@@ -461,7 +461,8 @@ void launch_cfg(rfi_ctx* ctx, const WgradArgs& a) {
         if (ctx->profiling)
             label = "wgrad_ws R" + std::to_string(R) + (ST == 2 ? "s2" : "") + " N" + std::to_string(a.N) + " " + std::to_string(a.H) + "x" +
                     std::to_string(a.W) + " cx" + std::to_string(a.Cx) + " cy" + std::to_string(a.Cy) + " split" +
-                    std::to_string(p.nsplit) + (P == 3 ? " 3xbf16" : " bf16");
+                    std::to_string(p.nsplit) + (P == 3 ? " 3xbf16" : " bf16") + " b" + std::to_string(BYB) + "x" + std::to_string(BXB) +
+                    " t" + std::to_string(TH) + "x" + std::to_string(TW) + " xm" + std::to_string(XM) + (PWV == 8 ? " pw8" : "");
         const double bytes = 4.0 * ((double)a.N * a.Hx * a.Wx * a.Cx + (double)a.N * a.H * a.W * a.Cy + (double)R * R * a.Cx * a.Cy);
         ProfScope ps(ctx, FAM_WGRAD_MFMA, flops, bytes, label);
 #ifdef RFI_DIAG_STAMPS

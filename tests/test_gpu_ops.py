@@ -17,7 +17,8 @@ TOL = 2e-5
 CONV_SHAPES = [
     (2, 16, 16, 3, 8), (1, 8, 8, 4, 4), (2, 32, 32, 32, 32), (2, 64, 64, 32, 64), (1, 16, 16, 64, 128),
     (2, 8, 8, 128, 64), (1, 24, 40, 16, 48), (3, 4, 4, 8, 16), (1, 128, 128, 32, 32), (1, 12, 20, 20, 36),
-    # the stem shapes (Cin = 4 = three channels padded, Cout 32 / 64): conv_stem.hip / wgrad_stem.hip, whole and ragged tiles
+    # the stem shapes (Cin = 4 = three channels padded, Cout 32 / 64): conv_stem.hip, whole and ragged tiles (the weight
+    # gradient of calls this small runs wgrad_ws; wgrad_stem.hip takes it from 64 pixel tiles on: test_gpu_x3_accuracy.py)
     (2, 16, 32, 4, 32), (1, 13, 37, 4, 32), (3, 8, 16, 4, 64), (1, 40, 24, 4, 64),
 ]
 
@@ -78,6 +79,9 @@ def test_conv3x3_dgrad_wgrad(shape):
 
 
 def test_conv3x3_wgrad_with_load_transform():
+    """IMPL_X3 runs the wave-specialised weight-gradient kernel here (wgrad_ws with the compile-time BatchNorm + ReLU load
+    transform: launch_wgrad takes it wherever the shape is eligible; there is no IMPL_WS route for weight gradients).
+    Every tile variant of it, in both transform forms: test_gpu_x3_accuracy.py."""
     n, h, w, cin, cout = 2, 16, 16, 32, 64
     g = torch.Generator().manual_seed(3)
     x = torch.randn(n, cin, h, w, generator=g)
@@ -163,9 +167,25 @@ def _unet_conv_shapes(f, n, size, depth=4):
     return sorted(set(out))
 
 
+def _layer_impls(cin, cout, h, w):
+    """0: the kernel-level default (native float32 MFMA; the direct kernel where Cin % 4 != 0); IMPL_X3: the same kernel in
+    the models' default arithmetic; IMPL_WS: the wave-specialised kernels the models launch at that shape (forward, and the
+    input gradient as a conv with the channels swapped; the weight gradient behind IMPL_X3 is wgrad_ws / wgrad_stem)."""
+    fwd, dgrad, wgrad = [0], [0], [0]
+    if cin % 4 == 0 and cout % 4 == 0:
+        fwd, dgrad, wgrad = fwd + [IMPL_X3], dgrad + [IMPL_X3], wgrad + [IMPL_X3]
+    if h >= 8 and w >= 8:
+        if cin % 16 == 0 or (cin == 4 and cout in (32, 64)):
+            fwd.append(IMPL_WS)
+        if cout % 16 == 0:
+            dgrad.append(IMPL_WS)
+    return fwd, dgrad, wgrad
+
+
 @pytest.mark.parametrize("shape", _unet_conv_shapes(16, 2, 64) + _unet_conv_shapes(8, 1, 32))
 def test_every_unet_layer_shape(shape):
-    """forward, dgrad and wgrad at exactly the shapes the model launches (auto implementation)."""
+    """forward, dgrad and wgrad at exactly the shapes the model launches: the auto implementation of the kernel-level ABI
+    (native float32), and the float32-by-3xbf16 kernels the models run by default (_layer_impls)."""
     n, h, w, cin, cout = shape
     g = torch.Generator().manual_seed(hash(shape) % 997)
     x = torch.randn(n, cin, h, w, generator=g, requires_grad=True)
@@ -177,15 +197,19 @@ def test_every_unet_layer_shape(shape):
     c = ctx()
     dx, dw, db, ddy = (c.to_device(nhwc(x.detach())), c.to_device(wt.detach().numpy()), c.to_device(b.numpy()),
                        c.to_device(nhwc(dy)))
-    out = c.empty((n, h, w, cout))
-    check(lib.rfi_op_conv3x3(c.handle, 0, P(dx), n, h, w, cin, P(dw), P(db), cout, None, None, 0, P(out)))
-    assert rel_err(out.numpy(), nhwc(y.detach())) <= TOL
-    gx = c.empty((n, h, w, cin))
-    check(lib.rfi_op_conv3x3_dgrad(c.handle, 0, P(ddy), n, h, w, cout, P(dw), cin, P(gx)))
-    assert rel_err(gx.numpy(), nhwc(x.grad)) <= TOL
-    gw = c.empty((cout, cin, 3, 3))
-    check(lib.rfi_op_conv3x3_wgrad(c.handle, 0, P(dx), P(ddy), n, h, w, cin, cout, None, None, 0, P(gw)))
-    assert rel_err(gw.numpy(), wt.grad.numpy()) <= 5e-5
+    fwd, dgrad, wgrad = _layer_impls(cin, cout, h, w)
+    for impl in fwd:
+        out = c.empty((n, h, w, cout))
+        check(lib.rfi_op_conv3x3(c.handle, impl, P(dx), n, h, w, cin, P(dw), P(db), cout, None, None, 0, P(out)))
+        assert rel_err(out.numpy(), nhwc(y.detach())) <= TOL, f"fwd impl={impl}"
+    for impl in dgrad:
+        gx = c.empty((n, h, w, cin))
+        check(lib.rfi_op_conv3x3_dgrad(c.handle, impl, P(ddy), n, h, w, cout, P(dw), cin, P(gx)))
+        assert rel_err(gx.numpy(), nhwc(x.grad)) <= TOL, f"dgrad impl={impl}"
+    for impl in wgrad:
+        gw = c.empty((cout, cin, 3, 3))
+        check(lib.rfi_op_conv3x3_wgrad(c.handle, impl, P(dx), P(ddy), n, h, w, cin, cout, None, None, 0, P(gw)))
+        assert rel_err(gw.numpy(), wt.grad.numpy()) <= 5e-5, f"wgrad impl={impl}"
 
 
 POOL_SHAPES = [(2, 32, 32, 32), (2, 64, 64, 16), (1, 8, 8, 128), (3, 4, 6, 5), (1, 16, 16, 64)]
@@ -266,7 +290,7 @@ def test_conv3x3_double_tile_kernels(shape):
     c = ctx()
     dx, dw, db, ddy = c.to_device(nhwc(x)), c.to_device(wt.numpy()), c.to_device(b.numpy()), c.to_device(nhwc(dy))
     dsc, dsh = c.to_device(sc.numpy()), c.to_device(sh.numpy())
-    for impl in (IMPL_MFMA, IMPL_X3, IMPL_PX3):
+    for impl in (IMPL_MFMA, IMPL_X3, IMPL_PX3, IMPL_WS):     # (IMPL_WS: conv_ws with 64-channel blocks, the benchmark's variant)
         out = c.empty((n, h, w, cout))
         check(lib.rfi_op_conv3x3(c.handle, impl, P(dx), n, h, w, cin, P(dw), P(db), cout, P(dsc), P(dsh), 1, P(out)))
         assert rel_err(out.numpy(), nhwc(y.detach())) <= TOL, f"fwd impl={impl}"
@@ -282,7 +306,7 @@ def _wide(shape, g, lo, hi):
     return (torch.randn(shape, generator=g).double() * torch.pow(torch.tensor(2.0, dtype=torch.float64), k)).float()
 
 
-@pytest.mark.parametrize("impl", [IMPL_MFMA, IMPL_X3, IMPL_PX3])
+@pytest.mark.parametrize("impl", [IMPL_MFMA, IMPL_X3, IMPL_PX3, IMPL_WS])
 def test_conv3x3_wide_dynamic_range_and_cancellation(impl):
     """The float32-by-3xbf16 arithmetic claims ONE float32 rounding per product (the three dropped piece
     products are <= 2^-24 |a b|), for any finite operands, not just randn.  Operands spanning 2^-60 .. 2^60
@@ -314,7 +338,7 @@ def test_conv3x3_wide_dynamic_range_and_cancellation(impl):
     assert (got[cancel].abs() <= 16 * 2.0 ** -24 * bound[cancel]).all()
 
 
-@pytest.mark.parametrize("impl", [IMPL_MFMA, IMPL_X3, IMPL_PX3])
+@pytest.mark.parametrize("impl", [IMPL_MFMA, IMPL_X3, IMPL_PX3, IMPL_WS])
 def test_conv3x3_non_finite_lanes(impl):
     """An inf and a NaN in the input: every output whose 3x3 window contains one of them must come out
     non-finite, every other output must be unaffected.  (The split path turns inf into NaN -- inf - inf in the
@@ -340,7 +364,7 @@ def test_conv3x3_non_finite_lanes(impl):
     assert rel_err(got[ok], nhwc(clean)[0][ok]) <= TOL
 
 
-@pytest.mark.parametrize("impl", [IMPL_MFMA, IMPL_X3, IMPL_PX3])
+@pytest.mark.parametrize("impl", [IMPL_MFMA, IMPL_X3, IMPL_PX3, IMPL_WS])
 def test_conv3x3_tiny_operands_underflow(impl):
     """Operands near the bottom of the float32 range: the low bf16 pieces underflow (bf16 shares float32's
     exponent range), which may cost relative accuracy only where the PRODUCTS are themselves subnormal; results
