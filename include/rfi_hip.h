@@ -476,6 +476,45 @@ int rfi_simulate_rfi(rfi_ctx* ctx, uint64_t seed, uint64_t first_sample, int n_s
                      const double* power_range_dev, int out_layout, void* out_dev, uint8_t* mask_dev,
                      rfi_sim_event* events_dev, double* baseline_frac_dev);
 
+/* ---- input normalisation of 8-channel data (datasets/rfi_mask_dataset.py:99-156, scripts/normalize_rfi_data.py).
+ *
+ *      rfi_norm_statistics: statistics of populations of real scalars held in device memory, dtype RFI_F64 or
+ *      RFI_F32 (complex data is passed as its interleaved real scalars: every statistic here is invariant under
+ *      permutation).  chunks / counts: `n_chunks` device pointers and their scalar counts (host arrays).
+ *        segment == 0   one population: the concatenation of all chunks (n_out must be 1);
+ *        segment  > 0   n_chunks must be 1; the chunk is cut into n_out = counts[0] / segment populations of
+ *                       `segment` consecutive scalars each, all handled by the same launches.
+ *      Per population (out, a host array of n_out records): count, the number of non-finite values, min, max, the fp64
+ *      mean and POPULATION variance (two-pass), and for the median, the 25 % and the 75 % quantile (q[0], q[1], q[2])
+ *      the two bracketing order statistics of NumPy's default linear method: virtual index v = q (count - 1) formed in
+ *      fp64 by rfi_norm_bracket, ranks floor(v) and min(floor(v) + 1, count - 1).  The interpolation between the
+ *      brackets is left to the caller; with quantiles == 0 the order statistics are not computed (q is NaN), which
+ *      leaves 2 reads of the data instead of 6 (float32: 3).  min, max and the order statistics are exact (radix selection); the sums are
+ *      taken over fixed 8192-scalar tiles of the population's index range and reduced in a fixed order, so every
+ *      result is bitwise reproducible and independent of how the population is split into chunks.  With
+ *      nonfinite != 0 the other fields are unspecified.  Populations: at most 4096, each non-empty.  Synchronises.
+ *
+ *      rfi_norm_apply: dst = float32((double(src) - centre) / scale), fp64 arithmetic on the exact source value,
+ *      rounded once; a pair with scale == 0 writes zeros (min-max normalisation of a constant population).  params_dev
+ *      NULL: the pair (centre, scale) for every sample; else a device array of n (centre, scale) pairs, one per
+ *      sample.  Source (device): dtype RFI_F64 / RFI_F32 in layout RFI_NORM_NCHW (n, 8, T, F) or RFI_NORM_NHWC
+ *      (n, T, F, 8); RFI_C128 / RFI_C64 (n, 4, T, F) in the order RR, RL, LR, LL (src_layout RFI_NORM_NCHW), giving
+ *      the channels RR.re RR.im RL.re ... LL.im.  Destination (device): float32 in RFI_NORM_NCHW or RFI_NORM_NHWC;
+ *      pixels = T F.  dst may equal src when both have the same dtype and layout, and must not overlap it otherwise.
+ *      Stream-ordered on the context's stream; no synchronisation. ---- */
+typedef struct rfi_norm_stats {
+    int64_t count, nonfinite;
+    double min, max, mean, var;
+    double q[3][2];      /* [median, 25 %, 75 %][lower, upper bracket] */
+} rfi_norm_stats;
+enum { RFI_NORM_NCHW = 0, RFI_NORM_NHWC = 1 };
+/* ranks[0], ranks[1] = the bracketing 0-based ranks of quantile q among count values; *frac = v - floor(v) */
+int rfi_norm_bracket(int64_t count, double q, int64_t* ranks, double* frac);
+int rfi_norm_statistics(rfi_ctx* ctx, const void* const* chunks, const int64_t* counts, int n_chunks, int dtype,
+                        int64_t segment, int quantiles, rfi_norm_stats* out, int n_out);
+int rfi_norm_apply(rfi_ctx* ctx, const void* src_dev, int dtype, int src_layout, int n, int64_t pixels, double centre,
+                   double scale, const double* params_dev, float* dst_dev, int dst_layout);
+
 /* ---- kernel-level entry points (device pointers only).  Used by the parity tests to
  *      check each HIP kernel against the oracle in isolation.  impl: 0 auto, 1 direct VALU,
  *      2 MFMA implicit GEMM in native float32 (v_mfma_f32_32x32x2_f32), 3 MFMA implicit GEMM with bfloat16

@@ -28,6 +28,12 @@ class FlagStats(C.Structure):
 
 
 SIM_C128, SIM_C64, SIM_NCHW, SIM_NHWC = 0, 1, 2, 3
+NORM_NCHW, NORM_NHWC = 0, 1
+
+
+class NormStats(C.Structure):
+    _fields_ = [("count", C.c_int64), ("nonfinite", C.c_int64), ("min", C.c_double), ("max", C.c_double),
+                ("mean", C.c_double), ("var", C.c_double), ("q", C.c_double * 2 * 3)]
 
 
 class SimParams(C.Structure):
@@ -185,6 +191,9 @@ _PROTOS = {
     "rfi_model_predict_flags": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(Tiling), _i, _i, _f, _vp, _i, _vp, _i]),
     "rfi_simulate_rfi": (_i, [_vp, C.c_uint64, C.c_uint64, _i, C.POINTER(SimParams), _vp, _i, _vp, _vp, _vp, _vp]),
     "rfi_flag_statistics": (_i, [_vp, _vp, _i, _i, _i64, _vp, _i, _i, _i, C.POINTER(FlagStats), C.POINTER(FlagStats)]),
+    "rfi_norm_bracket": (_i, [_i64, C.c_double, _pi64, _pd]),
+    "rfi_norm_statistics": (_i, [_vp, _pvp, _pi64, _i, _i, _i64, _i, C.POINTER(NormStats), _i]),
+    "rfi_norm_apply": (_i, [_vp, _vp, _i, _i, _i, _i64, C.c_double, C.c_double, _vp, _vp, _i]),
     "rfi_op_conv3x3": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     "rfi_op_conv1x1": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     "rfi_op_conv_s2": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),

@@ -1180,6 +1180,82 @@ int rfi_simulate_rfi(rfi_ctx* ctx, uint64_t seed, uint64_t first_sample, int n_s
                        events_dev, baseline_frac_dev);
     });
 }
+namespace {
+void norm_bracket(int64_t count, double q, int64_t* ranks, double* frac) {
+    const double v = q * (double)(count - 1), f = std::floor(v);
+    ranks[0] = (int64_t)f;
+    ranks[1] = std::min(ranks[0] + 1, count - 1);
+    if (frac) *frac = v - f;
+}
+}  // namespace
+int rfi_norm_bracket(int64_t count, double q, int64_t* ranks, double* frac) {
+    return guarded([&] {
+        RFI_REQUIRE(count >= 1 && q >= 0.0 && q <= 1.0 && ranks, "norm_bracket: needs count >= 1, 0 <= q <= 1 and ranks");
+        norm_bracket(count, q, ranks, frac);
+    });
+}
+int rfi_norm_statistics(rfi_ctx* ctx, const void* const* chunks, const int64_t* counts, int n_chunks, int dtype,
+                        int64_t segment, int quantiles, rfi_norm_stats* out, int n_out) {
+    return guarded([&] {
+        RFI_REQUIRE(ctx && chunks && counts && out, "norm_statistics: null argument");
+        RFI_REQUIRE(dtype == RFI_F64 || dtype == RFI_F32, "norm_statistics: dtype must be float64 or float32 (pass complex data as its real scalars)");
+        RFI_REQUIRE(n_chunks >= 1 && n_chunks <= 65536, "norm_statistics: needs 1 to 65536 chunks");
+        RFI_REQUIRE(segment >= 0, "norm_statistics: negative segment");
+        RFI_REQUIRE(segment == 0 || n_chunks == 1, "norm_statistics: the per-sample mode takes one chunk");
+        const size_t esz = dtype == RFI_F32 ? 4 : 8;
+        std::vector<norm_chunk> table((size_t)n_chunks + 1);
+        int64_t total = 0;
+        for (int i = 0; i < n_chunks; ++i) {
+            RFI_REQUIRE(counts[i] >= 0 && (counts[i] == 0 || chunks[i]), "norm_statistics: bad chunk");
+            RFI_REQUIRE(reinterpret_cast<uintptr_t>(chunks[i]) % esz == 0, "norm_statistics: misaligned chunk");
+            table[i] = norm_chunk{chunks[i], total};
+            total += counts[i];
+        }
+        table[n_chunks] = norm_chunk{nullptr, total};
+        RFI_REQUIRE(total >= 1, "norm_statistics: no data");
+        const int64_t seg = segment ? segment : total;
+        RFI_REQUIRE(total % seg == 0, "norm_statistics: the chunk is not a whole number of segments");
+        const int64_t pops = total / seg;
+        RFI_REQUIRE(pops <= 4096, "norm_statistics: at most 4096 populations per call");
+        RFI_REQUIRE(n_out == pops, "norm_statistics: n_out must be the number of populations");
+        int64_t ranks[6];
+        norm_bracket(seg, 0.5, ranks + 0, nullptr);
+        norm_bracket(seg, 0.25, ranks + 2, nullptr);
+        norm_bracket(seg, 0.75, ranks + 4, nullptr);
+        ctx->activate();
+        CallScope sc(ctx);
+        const norm_chunk* tb = sc.in(table.data(), RFI_HOST, table.size());
+        void* ws = sc.temp<void>(norm_stats_ws_bytes((int)pops, seg));
+        rfi_norm_stats* dout = sc.out(out, RFI_HOST, (size_t)pops);
+        launch_norm_stats(ctx, tb, n_chunks, dtype == RFI_F32, seg, (int)pops, quantiles != 0, ranks, ws, dout);
+        sc.finish();
+    });
+}
+int rfi_norm_apply(rfi_ctx* ctx, const void* src_dev, int dtype, int src_layout, int n, int64_t pixels, double centre,
+                   double scale, const double* params_dev, float* dst_dev, int dst_layout) {
+    return guarded([&] {
+        RFI_REQUIRE(ctx, "norm_apply: null context");
+        RFI_REQUIRE(dtype >= RFI_C128 && dtype <= RFI_F32, "norm_apply: dtype must be complex128, complex64, float64 or float32");
+        RFI_REQUIRE(src_layout == RFI_NORM_NCHW || src_layout == RFI_NORM_NHWC, "norm_apply: bad source layout");
+        RFI_REQUIRE(dst_layout == RFI_NORM_NCHW || dst_layout == RFI_NORM_NHWC, "norm_apply: bad destination layout");
+        const bool cplx = dtype == RFI_C128 || dtype == RFI_C64;
+        RFI_REQUIRE(!cplx || src_layout == RFI_NORM_NCHW, "norm_apply: complex input is (n, 4, T, F)");
+        RFI_REQUIRE(n >= 0 && pixels >= 1 && (double)n * (double)pixels < 549755813888.0, "norm_apply: bad sizes");
+        if (n == 0) return;
+        RFI_REQUIRE(src_dev && dst_dev, "norm_apply: null buffer");
+        RFI_REQUIRE(reinterpret_cast<uintptr_t>(src_dev) % 16 == 0 && reinterpret_cast<uintptr_t>(dst_dev) % 16 == 0,
+                    "norm_apply: buffers must be 16-byte aligned");
+        const size_t sbytes = (size_t)n * (size_t)pixels * 8 * (dtype == RFI_C64 || dtype == RFI_F32 ? 4 : 8);
+        const size_t dbytes = (size_t)n * (size_t)pixels * 8 * 4;
+        const char *s0 = static_cast<const char*>(src_dev), *d0 = reinterpret_cast<const char*>(dst_dev);
+        const bool same = s0 == d0 && dtype == RFI_F32 && src_layout == dst_layout;
+        RFI_REQUIRE(same || s0 + sbytes <= d0 || d0 + dbytes <= s0,
+                    "norm_apply: source and destination overlap (in place needs the same dtype and layout)");
+        ctx->activate();
+        launch_norm_apply(ctx, src_dev, dtype, src_layout == RFI_NORM_NHWC, n, pixels, centre, scale, params_dev, dst_dev,
+                          dst_layout == RFI_NORM_NHWC);
+    });
+}
 int rfi_threshold_logits(rfi_ctx* ctx, const float* logits_dev, int64_t count, float threshold,
                          uint8_t* mask_dev) {
     return guarded([&] {

@@ -1,0 +1,459 @@
+// Input normalisation of 8-channel RFI data (rfi_toolbox/datasets/rfi_mask_dataset.py:99-156 and
+// scripts/normalize_rfi_data.py::normalize_array): the statistics of whole populations of real scalars, and the
+// streaming transform dst = (src - centre) / scale with the layout conversion fused.
+//
+// Statistics.  A population is `seg` consecutive scalars of the concatenation of the call's chunks (dataset mode:
+// one population, every chunk; per-sample mode: one chunk cut into equal segments).  Per population: min, max,
+// the number of non-finite values, fp64 mean and population variance, and six order statistics (the two brackets
+// of the median, the 25 % and the 75 % quantile; the ranks come from the host).
+//
+//   pass 0     sums, min / max, non-finite count, histogram of the first radix digit
+//   control    one workgroup per population: fixed-order reduction of the partial sums; picks each rank's digit
+//   pass 1     squared deviations about the mean + the second digit, for all six ranks of all populations at once
+//   pass 2..   one digit each (3 passes in all for float32, 6 for float64); not run when no quantile is wanted
+//
+// Order statistics are exact: radix selection on the order-preserving integer image of T, kDigit bits at a time
+// (as flag_stats.hip).  Sums are per SUM TILE: 8192 consecutive scalars of the population, owned by one wave, lane l
+// adding its elements l, l + 64, ... in order, then a fixed xor butterfly; the tile sums are then added by one
+// workgroup in a fixed order.  A tile is a range of population indices, not of memory: a tile that straddles two chunks is read
+// from both, so every result is independent of the chunking and of the launch geometry, bit for bit.  Histogram
+// counts are integers (LDS atomics, then one global integer atomic per non-zero bin); nothing is a floating-point
+// atomic.
+//
+// Apply.  A lane owns one pixel: it reads the pixel's 8 scalars (8 planes, 4 complex planes, or 8 contiguous),
+// forms (double(x) - centre) / scale in fp64, rounds once to float32 and writes 8 planes or 32 contiguous bytes.
+#include "kernels.hpp"
+
+namespace rfi {
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kWaves = kBlock / 64;
+constexpr int kDigit = 11, kBins = 1 << kDigit;
+constexpr int kSlots = 6;                        // slot 2 q + j: q 0 median / 1 25 % / 2 75 %; j 0 lower, 1 upper bracket
+constexpr int kUnroll = 8;
+constexpr int kWaveTile = 64 * kUnroll;          // scalars a wave loads at a time
+constexpr int kSuper = 16;                       // wave tiles per partial sum
+constexpr int kSumTile = kWaveTile * kSuper;     // scalars per partial sum
+constexpr int kMaxBlocks = 2048;                 // 8 workgroups per CU on 256 CUs
+
+typedef unsigned long long u64;
+
+__device__ __forceinline__ unsigned okey(float f) {
+    const unsigned u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ u64 okey(double f) {
+    const u64 u = (u64)__double_as_longlong(f);
+    return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ __forceinline__ float unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+__device__ __forceinline__ double unkey(u64 k) {
+    return __longlong_as_double((long long)((k & 0x8000000000000000ull) ? (k & 0x7fffffffffffffffull) : ~k));
+}
+template <typename T> struct KeyOf;
+template <> struct KeyOf<float> { typedef unsigned K; static constexpr int bits = 32; };
+template <> struct KeyOf<double> { typedef u64 K; static constexpr int bits = 64; };
+
+template <typename T> __host__ __device__ constexpr int npass() { return (KeyOf<T>::bits + kDigit - 1) / kDigit; }
+template <typename T> __device__ __forceinline__ int digit_shift(int p) {
+    const int s = KeyOf<T>::bits - kDigit * (p + 1);
+    return s > 0 ? s : 0;
+}
+
+struct NsState {                                 // one per population (zeroed by the host before pass 0)
+    u64 nminkey, maxkey, nonfinite;              // nminkey: max of ~key, so that zero is the identity of both
+    double mean, var;
+    u64 prefix[kSlots], rank[kSlots];
+    int alias[kSlots];                           // slot whose histogram this slot reads (equal prefixes share one)
+};
+struct NsArgs {
+    const norm_chunk* chunks;                    // n_chunks + 1 entries; the last one holds the total
+    int n_chunks;
+    int pops;
+    int last_pass;                               // the pass after which the record is written (1 without quantiles)
+    int64_t seg;                                 // scalars per population
+    int64_t wtiles;                              // sum tiles per population
+    u64 rank[kSlots];
+    double* partial;                             // [pops][wtiles]
+    u64* ghist;                                  // [pops][kSlots][kBins]
+    NsState* st;
+    rfi_norm_stats* out;
+};
+
+__device__ __forceinline__ double wave_sum(double v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ double wave_min(double v) {
+    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ u64 wave_usum(u64 v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// the `len` scalars from index g0 of the concatenation, lane l taking l, l + 64, ...; lanes past `len` get 0
+template <typename T>
+__device__ __forceinline__ void load_tile(const NsArgs& a, int64_t g0, int len, int lane, T (&x)[kUnroll]) {
+    int c = 0;
+    if (a.n_chunks > 1) {                        // last chunk starting at or before g0 (wave-uniform)
+        int lo = 0, hi = a.n_chunks - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (a.chunks[mid].start <= g0) lo = mid; else hi = mid - 1;
+        }
+        c = lo;
+    }
+    if (g0 + len <= a.chunks[c + 1].start) {     // the whole tile lies in chunk c
+        const T* p = static_cast<const T*>(a.chunks[c].ptr) + (g0 - a.chunks[c].start);
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const int i = lane + 64 * u;
+            x[u] = i < len ? p[i] : (T)0;
+        }
+    } else {                                     // the tile straddles chunks: each element finds its own
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const int i = lane + 64 * u;
+            x[u] = (T)0;
+            if (i < len) {
+                const int64_t g = g0 + i;
+                while (c + 1 < a.n_chunks && g >= a.chunks[c + 1].start) ++c;
+                x[u] = static_cast<const T*>(a.chunks[c].ptr)[g - a.chunks[c].start];
+            }
+        }
+    }
+}
+
+// MODE 0: sums, extrema, non-finite count, first digit (one histogram).  MODE 1: squared deviations + a digit.
+// MODE 2: a digit only.  grid (blocks, pops); every wave walks wave tiles of its population.
+template <typename T, int MODE>
+__global__ __launch_bounds__(kBlock) void ns_pass_kernel(NsArgs a, int pass) {
+    typedef typename KeyOf<T>::K K;
+    constexpr int NS = MODE == 0 ? 1 : kSlots;
+    __shared__ unsigned lh[NS][kBins];
+    const int pop = blockIdx.y;
+    NsState* st = a.st + pop;
+    bool built[NS];
+    K prefix[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        built[s] = MODE == 0 || st->alias[s] == s;
+        prefix[s] = MODE == 0 ? (K)0 : (K)st->prefix[s];
+    }
+    const int hi = KeyOf<T>::bits - kDigit * pass, sh = digit_shift<T>(pass);
+    const K mask = pass == 0 ? (K)0 : (K)(~(K)0 << hi);
+    const unsigned dmask = (1u << (hi - sh)) - 1u;
+    const double mean = MODE == 1 ? st->mean : 0.0;
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+        if (built[s])
+            for (int b = threadIdx.x; b < kBins; b += kBlock) lh[s][b] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    T mn = (T)INFINITY, mx = (T)-INFINITY;
+    u64 nf = 0;
+    for (int64_t wt = (int64_t)blockIdx.x * kWaves + w; wt < a.wtiles; wt += (int64_t)gridDim.x * kWaves) {
+        double s = 0.0;
+        for (int j = 0; j < kSuper; ++j) {
+            const int64_t off = wt * kSumTile + (int64_t)j * kWaveTile;
+            const int64_t left = a.seg - off;
+            if (left <= 0) break;
+            const int len = left < kWaveTile ? (int)left : kWaveTile;
+            T x[kUnroll];
+            load_tile<T>(a, (int64_t)pop * a.seg + off, len, lane, x);
+#pragma unroll
+            for (int u = 0; u < kUnroll; ++u) {
+                const bool ok = lane + 64 * u < len;
+                if (MODE == 0) {
+                    s += (double)x[u];
+                    if (ok) {
+                        if (x[u] < mn) mn = x[u];
+                        if (x[u] > mx) mx = x[u];
+                        nf += isfinite(x[u]) ? 0 : 1;
+                    }
+                } else if (MODE == 1) {
+                    const double d = ok ? (double)x[u] - mean : 0.0;
+                    s += d * d;
+                }
+                if (ok) {
+                    const K k = okey(x[u]);
+#pragma unroll
+                    for (int q = 0; q < NS; ++q)
+                        if (built[q] && (k & mask) == prefix[q]) atomicAdd(&lh[q][(unsigned)(k >> sh) & dmask], 1u);
+                }
+            }
+        }
+        if (MODE != 2) {
+            s = wave_sum(s);
+            if (lane == 0) a.partial[(int64_t)pop * a.wtiles + wt] = s;
+        }
+    }
+    if (MODE == 0) {
+        const double lo = wave_min((double)mn), up = wave_max((double)mx);
+        nf = wave_usum(nf);
+        if (lane == 0) {
+            if (lo <= up) {                      // (false for a wave that saw nothing, or nothing but NaN)
+                atomicMax(&st->nminkey, ~okey(lo));
+                atomicMax(&st->maxkey, okey(up));
+            }
+            if (nf) atomicAdd(&st->nonfinite, nf);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        if (!built[s]) continue;
+        u64* g = a.ghist + ((size_t)pop * kSlots + s) * kBins;
+        for (int b = threadIdx.x; b < kBins; b += kBlock) {
+            const unsigned c = lh[s][b];
+            if (c) atomicAdd(&g[b], (u64)c);
+        }
+    }
+}
+
+// sum of the population's tile sums in a fixed order: thread t adds tiles t, t + kBlock, ...; then a fixed tree
+__device__ double reduce_partials(const double* p, int64_t n) {
+    __shared__ double sh[kBlock];
+    double r = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += kBlock) r += p[i];
+    sh[threadIdx.x] = r;
+    __syncthreads();
+    for (int o = kBlock / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+        __syncthreads();
+    }
+    const double out = sh[0];
+    __syncthreads();
+    return out;
+}
+
+// digit of the bin holding 0-based rank `rank` of histogram h; *below = count in the bins before it
+__device__ void find_digit(const u64* h, u64 rank, int* digit, u64* below) {
+    constexpr int per = kBins / kBlock;
+    __shared__ u64 part[kBlock];
+    u64 loc[per], sum = 0;
+#pragma unroll
+    for (int k = 0; k < per; ++k) {
+        loc[k] = h[threadIdx.x * per + k];
+        sum += loc[k];
+    }
+    part[threadIdx.x] = sum;
+    if (threadIdx.x == 0) { *digit = 0; *below = 0; }
+    __syncthreads();
+    for (int o = 1; o < kBlock; o <<= 1) {                   // inclusive scan
+        const u64 add = (int)threadIdx.x >= o ? part[threadIdx.x - o] : 0;
+        __syncthreads();
+        part[threadIdx.x] += add;
+        __syncthreads();
+    }
+    const u64 incl = part[threadIdx.x], excl = incl - sum;
+    if (rank >= excl && rank < incl) {
+        u64 c = excl;
+#pragma unroll
+        for (int k = 0; k < per; ++k) {
+            if (rank >= c && rank < c + loc[k]) {
+                *digit = threadIdx.x * per + k;
+                *below = c;
+            }
+            c += loc[k];
+        }
+    }
+    __syncthreads();
+}
+
+// one workgroup per population, after pass `pass`: sums -> mean (pass 0) / variance (pass 1); every rank's digit;
+// the histograms are cleared for the next pass; the last pass writes the record
+template <typename T>
+__global__ __launch_bounds__(kBlock) void ns_control_kernel(NsArgs a, int pass) {
+    typedef typename KeyOf<T>::K K;
+    __shared__ int s_digit, s_alias[kSlots];
+    __shared__ u64 s_below, s_rank[kSlots];
+    const int pop = blockIdx.x;
+    NsState* st = a.st + pop;                                // written by thread 0 only; the others read LDS copies
+    if (pass <= 1) {
+        const double r = reduce_partials(a.partial + (int64_t)pop * a.wtiles, a.wtiles);
+        if (threadIdx.x == 0) {
+            if (pass == 0) st->mean = r / (double)a.seg;
+            else st->var = r / (double)a.seg;
+        }
+    }
+    if (threadIdx.x == 0)
+        for (int s = 0; s < kSlots; ++s) {
+            s_alias[s] = pass == 0 ? 0 : st->alias[s];
+            s_rank[s] = pass == 0 ? a.rank[s] : st->rank[s];
+        }
+    __syncthreads();
+    const int sh = digit_shift<T>(pass);
+    u64* gh = a.ghist + (size_t)pop * kSlots * kBins;
+    for (int s = 0; s < kSlots; ++s) {
+        find_digit(gh + (size_t)s_alias[s] * kBins, s_rank[s], &s_digit, &s_below);
+        if (threadIdx.x == 0) {
+            st->prefix[s] = (pass == 0 ? 0 : st->prefix[s]) | ((u64)s_digit << sh);
+            st->rank[s] = s_rank[s] - s_below;
+        }
+        __syncthreads();
+    }
+    for (int b = threadIdx.x; b < kSlots * kBins; b += kBlock) gh[b] = 0;
+    if (threadIdx.x == 0) {
+        for (int s = 0; s < kSlots; ++s) {
+            int al = s;
+            for (int r = s - 1; r >= 0; --r)
+                if (st->prefix[r] == st->prefix[s]) al = r;
+            st->alias[s] = al;
+        }
+        if (pass == a.last_pass) {
+            rfi_norm_stats o;
+            o.count = a.seg;
+            o.nonfinite = (int64_t)st->nonfinite;
+            o.min = unkey(~st->nminkey);
+            o.max = unkey(st->maxkey);
+            o.mean = st->mean;
+            o.var = st->var;
+            const bool have = a.last_pass == npass<T>() - 1;
+            for (int s = 0; s < kSlots; ++s)
+                o.q[s >> 1][s & 1] = have ? (double)unkey((K)st->prefix[s]) : __longlong_as_double(0x7ff8000000000000ll);
+            a.out[pop] = o;
+        }
+    }
+}
+
+template <typename T>
+void run_stats(rfi_ctx* ctx, const NsArgs& a) {
+    const int64_t groups = cdiv(a.wtiles, kWaves);            // a workgroup's four waves take four sum tiles at a time
+    const int64_t cap = std::max<int64_t>(1, kMaxBlocks / a.pops);
+    const dim3 g((unsigned)std::min(groups, cap), (unsigned)a.pops), b(kBlock);
+    hipLaunchKernelGGL((ns_pass_kernel<T, 0>), g, b, 0, ctx->stream, a, 0);
+    check_launch("norm_stats_pass0");
+    hipLaunchKernelGGL(ns_control_kernel<T>, dim3(a.pops), b, 0, ctx->stream, a, 0);
+    hipLaunchKernelGGL((ns_pass_kernel<T, 1>), g, b, 0, ctx->stream, a, 1);
+    hipLaunchKernelGGL(ns_control_kernel<T>, dim3(a.pops), b, 0, ctx->stream, a, 1);
+    for (int p = 2; p <= a.last_pass; ++p) {
+        hipLaunchKernelGGL((ns_pass_kernel<T, 2>), g, b, 0, ctx->stream, a, p);
+        hipLaunchKernelGGL(ns_control_kernel<T>, dim3(a.pops), b, 0, ctx->stream, a, p);
+    }
+    check_launch("norm_stats");
+}
+
+constexpr size_t up256(size_t b) { return (b + 255) / 256 * 256; }
+size_t hist_bytes(int pops) { return up256((size_t)pops * kSlots * kBins * sizeof(u64)); }
+size_t state_bytes(int pops) { return up256((size_t)pops * sizeof(NsState)); }
+size_t partial_bytes(int pops, int64_t seg) { return up256((size_t)pops * (size_t)cdiv(seg, kSumTile) * sizeof(double)); }
+
+// ---------------------------------------------------------------- apply
+enum { SRC_PLANAR = 0, SRC_COMPLEX = 1, SRC_NHWC = 2 };
+
+template <typename S> struct alignas(2 * sizeof(S)) Pair { S x, y; };
+template <typename S> struct alignas(16) Quad;                // 16 bytes of S
+template <> struct alignas(16) Quad<float> { float v[4]; };
+template <> struct alignas(16) Quad<double> { double v[2]; };
+
+// src and dst may be the same buffer (same dtype and layout only): a lane reads its pixel's 8 values before it
+// writes the same 8 places, so neither pointer is __restrict__
+template <typename S, int SRC, bool DNHWC>
+__global__ __launch_bounds__(kBlock) void ns_apply_kernel(const S* src, float* dst, int64_t total, int64_t px, double centre,
+                                                          double scale, const double* params) {
+    const int64_t gid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (gid >= total) return;
+    const int64_t n = gid / px, p = gid - n * px;
+    if (params) {
+        centre = params[2 * n];
+        scale = params[2 * n + 1];
+    }
+    S v[8];
+    if constexpr (SRC == SRC_PLANAR) {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) v[c] = src[(n * 8 + c) * px + p];
+    } else if constexpr (SRC == SRC_COMPLEX) {
+        const Pair<S>* q = reinterpret_cast<const Pair<S>*>(src);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const Pair<S> z = q[(n * 4 + c) * px + p];
+            v[2 * c] = z.x;
+            v[2 * c + 1] = z.y;
+        }
+    } else {
+        constexpr int per = 16 / sizeof(S);
+        const Quad<S>* q = reinterpret_cast<const Quad<S>*>(src + gid * 8);
+#pragma unroll
+        for (int c = 0; c < 8 / per; ++c) {
+            const Quad<S> z = q[c];
+#pragma unroll
+            for (int k = 0; k < per; ++k) v[c * per + k] = z.v[k];
+        }
+    }
+    float o[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) o[c] = scale == 0.0 ? 0.0f : (float)(((double)v[c] - centre) / scale);
+    if constexpr (DNHWC) {
+        Quad<float>* q = reinterpret_cast<Quad<float>*>(dst + gid * 8);
+        q[0] = Quad<float>{{o[0], o[1], o[2], o[3]}};
+        q[1] = Quad<float>{{o[4], o[5], o[6], o[7]}};
+    } else {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) dst[(n * 8 + c) * px + p] = o[c];
+    }
+}
+
+template <typename S, int SRC>
+void run_apply(rfi_ctx* ctx, const void* src, float* dst, int64_t total, int64_t px, double centre, double scale,
+               const double* params, bool dnhwc) {
+    const dim3 g((unsigned)cdiv(total, kBlock)), b(kBlock);
+    if (dnhwc)
+        hipLaunchKernelGGL((ns_apply_kernel<S, SRC, true>), g, b, 0, ctx->stream, static_cast<const S*>(src), dst, total, px,
+                           centre, scale, params);
+    else
+        hipLaunchKernelGGL((ns_apply_kernel<S, SRC, false>), g, b, 0, ctx->stream, static_cast<const S*>(src), dst, total, px,
+                           centre, scale, params);
+    check_launch("norm_apply");
+}
+
+}  // namespace
+
+size_t norm_stats_ws_bytes(int pops, int64_t seg) { return hist_bytes(pops) + state_bytes(pops) + partial_bytes(pops, seg); }
+
+int norm_stats_passes(bool f32, bool quantiles) { return !quantiles ? 2 : (f32 ? npass<float>() : npass<double>()); }
+
+void launch_norm_stats(rfi_ctx* ctx, const norm_chunk* chunks_dev, int n_chunks, bool f32, int64_t seg, int pops,
+                       bool quantiles, const int64_t* ranks6, void* ws, rfi_norm_stats* out_dev) {
+    const int np = norm_stats_passes(f32, quantiles);
+    ProfScope ps(ctx, FAM_PREPROCESS, 0, (double)np * (double)pops * (double)seg * (f32 ? 4 : 8));
+    NsArgs a;
+    a.chunks = chunks_dev;
+    a.n_chunks = n_chunks;
+    a.pops = pops;
+    a.last_pass = np - 1;
+    a.seg = seg;
+    a.wtiles = cdiv(seg, kSumTile);
+    for (int s = 0; s < kSlots; ++s) a.rank[s] = (u64)ranks6[s];
+    char* w = static_cast<char*>(ws);
+    a.ghist = reinterpret_cast<u64*>(w);
+    a.st = reinterpret_cast<NsState*>(w + hist_bytes(pops));
+    a.partial = reinterpret_cast<double*>(w + hist_bytes(pops) + state_bytes(pops));
+    a.out = out_dev;
+    RFI_CHECK_HIP(hipMemsetAsync(ws, 0, hist_bytes(pops) + state_bytes(pops), ctx->stream));
+    if (f32) run_stats<float>(ctx, a);
+    else run_stats<double>(ctx, a);
+}
+
+void launch_norm_apply(rfi_ctx* ctx, const void* src, int dtype, bool src_nhwc, int n, int64_t px, double centre, double scale,
+                       const double* params_dev, float* dst, bool dst_nhwc) {
+    const int64_t total = (int64_t)n * px;
+    const bool f32 = dtype == RFI_C64 || dtype == RFI_F32;
+    ProfScope ps(ctx, FAM_PREPROCESS, 0, (double)total * 8 * ((f32 ? 4 : 8) + 4));
+    if (dtype == RFI_C128) run_apply<double, SRC_COMPLEX>(ctx, src, dst, total, px, centre, scale, params_dev, dst_nhwc);
+    else if (dtype == RFI_C64) run_apply<float, SRC_COMPLEX>(ctx, src, dst, total, px, centre, scale, params_dev, dst_nhwc);
+    else if (dtype == RFI_F64 && src_nhwc) run_apply<double, SRC_NHWC>(ctx, src, dst, total, px, centre, scale, params_dev, dst_nhwc);
+    else if (dtype == RFI_F64) run_apply<double, SRC_PLANAR>(ctx, src, dst, total, px, centre, scale, params_dev, dst_nhwc);
+    else if (src_nhwc) run_apply<float, SRC_NHWC>(ctx, src, dst, total, px, centre, scale, params_dev, dst_nhwc);
+    else run_apply<float, SRC_PLANAR>(ctx, src, dst, total, px, centre, scale, params_dev, dst_nhwc);
+}
+
+}  // namespace rfi

@@ -330,6 +330,21 @@ void launch_stitch(rfi_ctx* ctx, const float* values, int kind, int n_planes, in
 size_t flag_stats_ws_bytes();
 void launch_flag_stats(rfi_ctx* ctx, const void* src, int dtype, int64_t n, const uint8_t* flags, int views,
                        bool medians, void* ws, void* mag, rfi_flag_stats* out_dev);
+// input normalisation (dataset_norm.hip).  Statistics of `pops` populations of `seg` consecutive scalars (float32 when
+// f32, else float64) of the concatenation of the chunks; chunks_dev has n_chunks + 1 entries ascending in `start`, the
+// last one holding the total; ranks6: 0-based ranks of the slots (median lo, hi; 25 % lo, hi; 75 % lo, hi), each
+// < seg (the order statistics are only found with `quantiles`); ws holds norm_stats_ws_bytes(pops, seg);
+// out_dev[pops].  norm_stats_passes: reads of the source per call.
+struct norm_chunk { const void* ptr; int64_t start; };
+size_t norm_stats_ws_bytes(int pops, int64_t seg);
+int norm_stats_passes(bool f32, bool quantiles);
+void launch_norm_stats(rfi_ctx* ctx, const norm_chunk* chunks_dev, int n_chunks, bool f32, int64_t seg, int pops,
+                       bool quantiles, const int64_t* ranks6, void* ws, rfi_norm_stats* out_dev);
+// dst = float32((double(src) - centre) / scale) over n samples of px pixels x 8 channels; params_dev: n (centre, scale)
+// pairs replacing the scalars; scale == 0 writes zeros.  Complex dtypes are (n, 4, px); real ones (n, 8, px) or, with
+// src_nhwc, (n, px, 8); dst (n, 8, px) or (n, px, 8)
+void launch_norm_apply(rfi_ctx* ctx, const void* src, int dtype, bool src_nhwc, int n, int64_t px, double centre, double scale,
+                       const double* params_dev, float* dst, bool dst_nhwc);
 // RFISimulator waterfalls (rfi_sim.hip): draws the event table into `events` (unless p.clean), then one gather per
 // pixel into `out` (layout RFI_SIM_*) and `mask`; sizes are checked by rfi_simulate_rfi
 void launch_rfi_sim(rfi_ctx* ctx, unsigned long long seed, unsigned first_sample, int n_samples,
