@@ -100,7 +100,7 @@ int rfi_unet_resnet_create(rfi_ctx* ctx, int in_channels, int out_channels, int 
  * [R, 2h, 2w] uint8 and the loss is the mean BCE-with-logits over them (K = 1; rfi_model_set_loss(m, 1, alpha, gamma)
  * switches to a focal loss).  Entries: mask_fcn{1..L}.weight/bias, conv5_mask.weight/bias, mask_fcn_logits.weight/bias.
  * Every rfi_model_* / rfi_train_* call applies with n = R; rfi_model_input_grad returns the gradient w.r.t. the input
- * features of the last backward pass ([R, h, w, C]) for rfi_op_roi_align_backward. */
+ * features of the last backward pass ([R, h, w, C]) for rfi_op_roi_align_backward / rfi_op_roi_align_ml_backward. */
 int rfi_mask_head_create(rfi_ctx* ctx, int in_channels, int conv_layers, int out_channels, rfi_model** out);
 int rfi_model_input_grad(rfi_model* m, float* dx, int dx_mem);
 /* The RPN head (Faster R-CNN; SURVEY 8a A11, not in the reference): conv_layers x [Conv3x3(C->C, p1)+bias -> ReLU] -> ONE
@@ -130,8 +130,11 @@ int rfi_rpn_head_create(rfi_ctx* ctx, int in_channels, int conv_layers, int anch
 int rfi_box_head_create(rfi_ctx* ctx, int in_features, int hidden, int fc_layers, int num_outputs, rfi_model** out);
 /* x += y on the device (n % 4 == 0): sums the feature-map gradients of several branches */
 int rfi_op_add_inplace(rfi_ctx* ctx, float* x, const float* y, int64_t n);
+/* fastrcnn_loss: head, labels, targets, dhead (the gradient of classification + box w.r.t. the head output) and
+ * loss2_dev[0..1] = (classification, box) all live on the device; workspace: rfi_op_rpn_loss_ws_bytes() bytes of device
+ * memory the caller keeps until the stream has passed.  Does not allocate or synchronise. */
 int rfi_op_fastrcnn_loss(rfi_ctx* ctx, const float* head, int64_t rois, int num_classes, const int32_t* labels, const float* targets,
-                         float beta, float* dhead, float* loss_classifier, float* loss_box_reg);
+                         float beta, float* dhead, void* workspace, float* loss2_dev);
 int rfi_resnet50_fpn_create(rfi_ctx* ctx, int in_channels, int base_width, int fpn_channels, rfi_model** out);
 int rfi_backbone_forward(rfi_model* m, const float* x, int x_mem, int n, int h, int w, float* const feats[5], int feats_mem);
 int rfi_backbone_backward(rfi_model* m, const float* x, int x_mem, int n, int h, int w, const float* const dfeats[5],
@@ -555,13 +558,11 @@ int rfi_op_convt2x2_wgrad(rfi_ctx* ctx, int impl, const float* x, const float* d
  * al. 2017): out = lateral + nearest-neighbour 2x upsampling of top [n][ceil(h/2)][ceil(w/2)][c].  Device pointers. */
 int rfi_op_roi_align(rfi_ctx* ctx, const float* x, int n, int h, int w, int c, const float* rois, int r,
                      float spatial_scale, int ph, int pw, int sampling_ratio, int aligned, float* out);
-int rfi_op_roi_align_backward(rfi_ctx* ctx, const float* dout, int n, int h, int w, int c, const float* rois,
-                              int r, float spatial_scale, int ph, int pw, int sampling_ratio, int aligned,
-                              float* dx);
-/* roi_align_backward_sorted: the same gradient by gather -- RoIs sorted by batch index (ascending); every element of dx is
- * WRITTEN (no prior zeroing, no accumulation), no float atomics: bit-reproducible.  Device pointers. */
-int rfi_op_roi_align_backward_sorted(rfi_ctx* ctx, const float* dout, int n, int h, int w, int c, const float* rois_sorted, int r,
-                                     float spatial_scale, int ph, int pw, int sampling_ratio, int aligned, float* dx);
+/* roi_align_backward: the gradient w.r.t. the feature map, by gather.  Contract: the RoIs are sorted by batch index
+ * (ascending), c % 4 == 0, and every element of dx [n][h][w][c] is WRITTEN exactly once (no prior zeroing, no accumulation).
+ * No float atomics: bit-reproducible.  Device pointers; does not allocate or synchronise. */
+int rfi_op_roi_align_backward(rfi_ctx* ctx, const float* dout, int n, int h, int w, int c, const float* rois_sorted, int r,
+                              float spatial_scale, int ph, int pw, int sampling_ratio, int aligned, float* dx);
 /* mask_targets: the training targets of the mask branch -- RoIAlign (rules above, scale 1, not aligned) of one-channel
  * uint8 instance masks [g][h][w], thresholded at 0.5: rois[r] = (instance index, x1, y1, x2, y2) -> out uint8 [r][ph][pw].
  * Device pointers. */
@@ -573,42 +574,36 @@ int rfi_op_mask_targets(rfi_ctx* ctx, const uint8_t* masks, int g, int h, int w,
  *   clipped to [0, clip_w] x [0, clip_h] when clip_w > 0.
  * nms: boxes sorted by descending score -> indices kept by greedy suppression at IoU > iou_threshold (host array of n ints).
  * rpn_loss: head output [pixels][5 A] (A objectness logits, then A x 4 deltas), labels int8 [pixels A] in {1, 0, -1 =
- *   not sampled}, regression targets [pixels A][4]; objectness = sum BCE over sampled / num_sampled, box = sum smooth-L1
- *   (beta) over positives / num_sampled; dhead = gradient of (objectness + box) w.r.t. the head output. */
+ *   not sampled}, regression targets [pixels A][4]; with count = max(*num_sampled_dev, 1), an int32 on the device (the
+ *   sampler's count): objectness = sum BCE over sampled / count, box = sum smooth-L1 (beta) over positives / count; dhead =
+ *   gradient of (objectness + box) w.r.t. the head output; loss2_dev[0..1] = (objectness, box) on the device.  Workspace:
+ *   rfi_op_rpn_loss_ws_bytes() bytes of device memory the caller keeps until the stream has passed.  Does not allocate or
+ *   synchronise. */
 int rfi_op_box_decode(rfi_ctx* ctx, const float* anchors, int64_t n_anchors, const float* deltas, int64_t n, float clip_h,
                       float clip_w, float* boxes);
-/* anchor_match: the Matcher + BoxCoder.encode of RPN training on device -- per anchor the first-argmax ground truth,
- *   label 1 (IoU >= fg_iou, or, with allow_low_quality, the anchor attains some ground truth's best IoU), 0 (IoU < bg_iou),
- *   -1 (between); matched[n] = ground-truth index for labels 1 (else -1); targets[n][4] (may be null) = encoded deltas of the
- *   positives, zeros elsewhere.  The random 256-anchor sampling that follows stays on the host. */
-int rfi_op_anchor_match(rfi_ctx* ctx, const float* anchors, int64_t n, const float* gt_boxes, int n_gt, float fg_iou, float bg_iou,
-                        int allow_low_quality, int8_t* labels, int32_t* matched, float* targets);
 int rfi_op_nms(rfi_ctx* ctx, const float* boxes_sorted, int n, float iou_threshold, int32_t* keep_host, int* n_keep);
 /* Batched forms -- one launch for every image of a batch, all tensors device pointers.
- * anchor_match_batched: anchors shared by the images (anchor_stride 0: [n][4]) or per image (anchor_stride = n:
- *   [images][n][4] with anchor_count[b] valid rows -- the proposals of the RoI stage; null: all n); gt_boxes
- *   [images][gt_max][4] with gt_count[b] valid rows; labels / matched [images][n], targets [images][n][4] (may be null).  A row
- *   beyond anchor_count[b] gets label -2.
+ * anchor_match_batched: the Matcher + BoxCoder.encode of RPN / RoI training -- per anchor the first-argmax ground truth,
+ *   label 1 (IoU >= fg_iou, or, with allow_low_quality, the anchor attains some ground truth's best IoU), 0 (IoU < bg_iou, or
+ *   gt_count[b] == 0), -1 (between); matched = ground-truth index for labels 1 (else -1); targets (may be null) = encoded
+ *   deltas of the positives, zeros elsewhere.  Anchors shared by the images (anchor_stride 0: [n][4]) or per image
+ *   (anchor_stride = n: [images][n][4] with anchor_count[b] valid rows -- the proposals of the RoI stage; null: all n);
+ *   gt_boxes [images][gt_max][4] (gt_max >= 1) with gt_count[b] valid rows; labels / matched [images][n], targets
+ *   [images][n][4].  A row beyond anchor_count[b] gets label -2.  best_ws: a workspace of images x gt_max floats on the
+ *   device that the caller keeps until the stream has passed.  Does not allocate or synchronise.
  * nms_batched: `sets` independent sets of at most k <= 256 boxes, each sorted by descending score ([sets][k][4], count[s]
  *   valid rows) -> keep uint8 [sets][k] (1 kept, 0 suppressed or beyond count). */
 int rfi_op_anchor_match_batched(rfi_ctx* ctx, const float* anchors, int64_t n, int64_t anchor_stride, const int32_t* anchor_count,
                                 const float* gt_boxes, int images, int gt_max, const int32_t* gt_count, float fg_iou, float bg_iou,
-                                int allow_low_quality, int8_t* labels, int32_t* matched, float* targets);
+                                int allow_low_quality, float* best_ws, int8_t* labels, int32_t* matched, float* targets);
 int rfi_op_nms_batched(rfi_ctx* ctx, const float* boxes_sorted, const int32_t* count, int sets, int k, float iou_threshold, uint8_t* keep);
 int rfi_op_rpn_loss(rfi_ctx* ctx, const float* head, int64_t pixels, int anchors_per_pixel, const int8_t* labels,
-                    const float* targets, int64_t num_sampled, float beta, float* dhead, float* loss_objectness,
-                    float* loss_box);
-/* rpn_loss_dev: rpn_loss without the host round trip -- the two loss scalars land in loss2_dev[0..1] (device), nothing
- * synchronises; workspace: rfi_op_rpn_loss_ws_bytes() bytes of device memory the caller keeps until the stream has passed. */
-int rfi_op_rpn_loss_dev(rfi_ctx* ctx, const float* head, int64_t pixels, int anchors_per_pixel, const int8_t* labels,
-                        const float* targets, int64_t num_sampled, float beta, float* dhead, void* workspace, float* loss2_dev);
+                    const float* targets, const int32_t* num_sampled_dev, float beta, float* dhead, void* workspace,
+                    float* loss2_dev);
 size_t rfi_op_rpn_loss_ws_bytes(void);
 /* ---- The detector's box bookkeeping on the device (csrc/detect_sample.hip): the work rfi_toolbox_amd.models.MaskRCNN did in
  * NumPy between the GPU stages (the reference has no detector, so no reference interface is replaced: SURVEY 8a A11).  All
  * pointers are device pointers unless named *_host; nothing here synchronises or allocates.
- * rpn_loss_devcount: rfi_op_rpn_loss_dev with the normaliser read from device memory (the sampler's count).
- * fastrcnn_loss_dev: rfi_op_fastrcnn_loss leaving (classification, box) in loss2_dev; workspace as rpn_loss_dev.
- * anchor_match_batched_ws: rfi_op_anchor_match_batched with a caller-held workspace of images x gt_max floats.
  * segsort_u64: n_segs segments of `stride` (a power of two, 2 .. 65536) 64-bit keys, each sorted ascending in place (up to
  *   8192 keys: one launch sorting in LDS; longer segments: a multi-pass bitonic sort through global memory).
  * sample_keys: labels [images][n] (1 positive, 0 negative) -> keys [images][stride] = class << 48 | r << 16 | i with
@@ -629,14 +624,6 @@ size_t rfi_op_rpn_loss_ws_bytes(void);
  * roi_align_ml / _backward: RoIAlign where RoI r uses map level[r] of four ([n][h0 >> k][w0 >> k][c], scale scale0 / 2^k; host
  *   arrays of device pointers); the row count is read from count_dev, max_rois sizes the launch; backward ADDS into dmaps.
  * readback_begin / _end: a copy of <= 2048 bytes to the host that waits for the work enqueued BEFORE begin only. */
-int rfi_op_rpn_loss_devcount(rfi_ctx* ctx, const float* head, int64_t pixels, int anchors_per_pixel, const int8_t* labels,
-                             const float* targets, const int32_t* num_sampled_dev, float beta, float* dhead, void* workspace,
-                             float* loss2_dev);
-int rfi_op_fastrcnn_loss_dev(rfi_ctx* ctx, const float* head, int64_t rois, int num_classes, const int32_t* labels, const float* targets,
-                             float beta, float* dhead, void* workspace, float* loss2_dev);
-int rfi_op_anchor_match_batched_ws(rfi_ctx* ctx, const float* anchors, int64_t n, int64_t anchor_stride, const int32_t* anchor_count,
-                                   const float* gt_boxes, int images, int gt_max, const int32_t* gt_count, float fg_iou, float bg_iou,
-                                   int allow_low_quality, float* best_ws, int8_t* labels, int32_t* matched, float* targets);
 int rfi_op_segsort_u64(rfi_ctx* ctx, uint64_t* keys, int n_segs, int stride);
 int rfi_op_sample_keys(rfi_ctx* ctx, const int8_t* labels, int images, int n, const int32_t* count, uint64_t seed, uint32_t step,
                        uint32_t stream0, uint64_t* keys, int stride);

@@ -103,7 +103,6 @@ _PROTOS = {
     "rfi_rpn_head_create": (_i, [_vp, _i, _i, _i, _pvp]),
     "rfi_box_head_create": (_i, [_vp, _i, _i, _i, _i, _pvp]),
     "rfi_op_add_inplace": (_i, [_vp, _vp, _vp, _i64]),
-    "rfi_op_fastrcnn_loss": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _f, _vp, _pf, _pf]),
     "rfi_resnet50_fpn_create": (_i, [_vp, _i, _i, _i, _pvp]),
     "rfi_backbone_forward": (_i, [_vp, _vp, _i, _i, _i, _i, _pvp, _i]),
     "rfi_backbone_backward": (_i, [_vp, _vp, _i, _i, _i, _i, _pvp, _i]),
@@ -144,19 +143,15 @@ _PROTOS = {
     "rfi_comm_emulate": (_i, [_vp, _i]),
     "rfi_op_roi_align": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _f, _i, _i, _i, _i, _vp]),
     "rfi_op_mask_targets": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp]),
-    "rfi_op_anchor_match_batched": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i, _i, _vp, _f, _f, _i, _vp, _vp, _vp]),
     "rfi_op_nms_batched": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp]),
-    "rfi_op_roi_align_backward_sorted": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _f, _i, _i, _i, _i, _vp]),
     "rfi_op_roi_align_backward": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _f, _i, _i, _i, _i, _vp]),
     "rfi_op_fpn_merge": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "rfi_op_box_decode": (_i, [_vp, _vp, _i64, _vp, _i64, _f, _f, _vp]),
     "rfi_op_nms": (_i, [_vp, _vp, _i, _f, _vp, _pi]),
-    "rfi_op_anchor_match": (_i, [_vp, _vp, _i64, _vp, _i, _f, _f, _i, _vp, _vp, _vp]),
-    "rfi_op_rpn_loss_dev": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _i64, _f, _vp, _vp, _vp]),
     "rfi_op_rpn_loss_ws_bytes": (_sz, []),
-    "rfi_op_rpn_loss_devcount": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
-    "rfi_op_fastrcnn_loss_dev": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _f, _vp, _vp, _vp]),
-    "rfi_op_anchor_match_batched_ws": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i, _i, _vp, _f, _f, _i, _vp, _vp, _vp, _vp]),
+    "rfi_op_rpn_loss": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
+    "rfi_op_fastrcnn_loss": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _f, _vp, _vp, _vp]),
+    "rfi_op_anchor_match_batched": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i, _i, _vp, _f, _f, _i, _vp, _vp, _vp, _vp]),
     "rfi_op_segsort_u64": (_i, [_vp, _vp, _i, _i]),
     "rfi_op_sample_keys": (_i, [_vp, _vp, _i, _i, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _i]),
     "rfi_op_rpn_sample_apply": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
@@ -173,7 +168,6 @@ _PROTOS = {
     "rfi_op_bn_backward16": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
     "rfi_readback_begin": (_i, [_vp, _vp, _sz]),
     "rfi_readback_end": (_i, [_vp, _vp, _sz]),
-    "rfi_op_rpn_loss": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _i64, _f, _vp, _pf, _pf]),
     "rfi_op_fpn_merge_backward": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "rfi_comm_allreduce_sum_f32": (_i, [_vp, _vp, _i64]),
     "rfi_model_allreduce_grads": (_i, [_vp]),

@@ -112,80 +112,9 @@ __global__ __launch_bounds__(256) void mask_targets_kernel(const unsigned char* 
     }
 }
 
-// backward: scatter dout / count through the same bilinear weights (float atomics: the sum over overlapping
-// RoIs is order dependent in the last bits, like the published implementations)
-__global__ __launch_bounds__(256) void roi_align_bwd_kernel(const float* __restrict__ dout, int N, int H, int W, int C,
-                                                           const float* __restrict__ rois, int R, float scale, int PH, int PW,
-                                                           int sr, int aligned, float* __restrict__ dx) {
-    const int64_t total = (int64_t)R * PH * PW * C;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int c = (int)(i % C);
-        int64_t t = i / C;
-        const int pw = (int)(t % PW); t /= PW;
-        const int ph = (int)(t % PH);
-        const int r = (int)(t / PH);
-        const RoiGeom g = roi_geom(rois, r, scale, PH, PW, sr, aligned != 0);
-        if (g.n < 0 || g.n >= N) continue;
-        const float gv = dout[i] / (float)(g.gh * g.gw > 0 ? g.gh * g.gw : 1);
-        float* db = dx + (int64_t)g.n * H * W * C + c;
-        if (g.gh <= 2 && g.gw <= 2) {
-            // the usual 2 x 2 samples of a bin: where the bin is about a pixel wide or less they share corner pixels, so their
-            // contributions are summed per pixel of a 3 x 3 window first (static indices only: everything stays in
-            // registers) -- 4 to 9 atomics per bin instead of 16
-            Bilin bs[4];
-            int ymin = H, xmin = W, ymax = -1, xmax = -1;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int iy = k >> 1, ix = k & 1;
-                const float yy = g.y1 + ph * g.bh + (iy + 0.5f) * g.bh / g.gh;
-                const float xx = g.x1 + pw * g.bw + (ix + 0.5f) * g.bw / g.gw;
-                bs[k] = bilin(yy, xx, H, W);
-                if (iy >= g.gh || ix >= g.gw) bs[k].ok = false;
-                if (bs[k].ok) {
-                    ymin = min(ymin, bs[k].y0); ymax = max(ymax, bs[k].y1);
-                    xmin = min(xmin, bs[k].x0); xmax = max(xmax, bs[k].x1);
-                } else {
-                    bs[k].w00 = bs[k].w01 = bs[k].w10 = bs[k].w11 = 0.0f;
-                }
-            }
-            if (ymax < 0) continue;                      // no sample inside the map
-            if (ymax - ymin <= 2 && xmax - xmin <= 2) {
-#pragma unroll
-                for (int wy = 0; wy < 3; ++wy)
-#pragma unroll
-                    for (int wx = 0; wx < 3; ++wx) {
-                        const int py = ymin + wy, px = xmin + wx;
-                        float v = 0.0f;
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            v += (bs[k].y0 == py && bs[k].x0 == px) ? bs[k].w00 : 0.0f;
-                            v += (bs[k].y0 == py && bs[k].x1 == px && bs[k].x1 != bs[k].x0) ? bs[k].w01 : 0.0f;
-                            v += (bs[k].y1 == py && bs[k].x0 == px && bs[k].y1 != bs[k].y0) ? bs[k].w10 : 0.0f;
-                            v += (bs[k].y1 == py && bs[k].x1 == px && bs[k].x1 != bs[k].x0 && bs[k].y1 != bs[k].y0) ? bs[k].w11 : 0.0f;
-                        }
-                        if (v != 0.0f && py <= ymax && px <= xmax) atomicAdd(db + ((int64_t)py * W + px) * C, gv * v);
-                    }
-                continue;
-            }
-        }
-        for (int iy = 0; iy < g.gh; ++iy) {
-            const float yy = g.y1 + ph * g.bh + (iy + 0.5f) * g.bh / g.gh;
-            for (int ix = 0; ix < g.gw; ++ix) {
-                const float xx = g.x1 + pw * g.bw + (ix + 0.5f) * g.bw / g.gw;
-                const Bilin b = bilin(yy, xx, H, W);
-                if (!b.ok) continue;
-                atomicAdd(db + ((int64_t)b.y0 * W + b.x0) * C, gv * b.w00);
-                atomicAdd(db + ((int64_t)b.y0 * W + b.x1) * C, gv * b.w01);
-                atomicAdd(db + ((int64_t)b.y1 * W + b.x0) * C, gv * b.w10);
-                atomicAdd(db + ((int64_t)b.y1 * W + b.x1) * C, gv * b.w11);
-            }
-        }
-    }
-}
-
-// ---- the same gradient by GATHER: one thread per (image, feature pixel, 4 channels) sums what every RoI of its image sends to
-// that pixel, in RoI order -- no atomics (the scatter form is bound by float atomics of overlapping RoIs contending in
-// L2: 5.5 ms of the Mask R-CNN step), every pixel written exactly once (no memset), bit-reproducible.  Needs the RoIs
+// backward by GATHER: one thread per (image, feature pixel, 4 channels) sums what every RoI of its image sends to that
+// pixel, in RoI order -- no atomics (a scatter form is bound by float atomics of overlapping RoIs contending in L2: it
+// took 5.5 ms of the Mask R-CNN step), every pixel written exactly once (no memset), bit-reproducible.  Needs the RoIs
 // sorted by image index (ascending).  The bilinear weight is separable, w(py, px) = wy * wx with the per-axis rule of
 // bilin(); per bin the weights of its samples are summed first, so a (pixel, RoI) pair costs one 16-byte load of dout per
 // bin within a pixel's reach.
@@ -452,9 +381,9 @@ void launch_roi_align_fwd(rfi_ctx* ctx, const float* x, int N, int H, int W, int
                        rois, R, scale, PH, PW, sampling_ratio, aligned ? 1 : 0, out);
     check_launch("roi_align_fwd");
 }
-void launch_roi_align_bwd_sorted(rfi_ctx* ctx, const float* dout, int N, int H, int W, int C, const float* rois, int R, float scale,
-                                 int PH, int PW, int sr, bool aligned, float* dx) {
-    RFI_REQUIRE(C % 4 == 0 && N > 0 && H > 0 && W > 0 && PH > 0 && PW > 0 && R >= 0, "roi_align_backward_sorted: C % 4 == 0 and positive sizes");
+void launch_roi_align_bwd(rfi_ctx* ctx, const float* dout, int N, int H, int W, int C, const float* rois, int R, float scale,
+                          int PH, int PW, int sr, bool aligned, float* dx) {
+    RFI_REQUIRE(C % 4 == 0 && N > 0 && H > 0 && W > 0 && PH > 0 && PW > 0 && R >= 0, "roi_align_backward: C % 4 == 0 and positive sizes");
     ProfScope ps(ctx, FAM_ELEMWISE, 0, (double)R * PH * PW * C * 4 * 4 + (double)N * H * W * C * 4);
     const int64_t items = (int64_t)H * W * (C / 4);
     int bx = (int)std::min<int64_t>(cdiv(items, 256), 4096);
@@ -470,16 +399,6 @@ void launch_mask_targets(rfi_ctx* ctx, const unsigned char* masks, int G, int H,
     hipLaunchKernelGGL(mask_targets_kernel, dim3(grid_of((int64_t)R * PH * PW)), dim3(256), 0, ctx->stream, masks, G, H, W, rois, R,
                        PH, PW, sr, out);
     check_launch("mask_targets");
-}
-void launch_roi_align_bwd(rfi_ctx* ctx, const float* dout, int N, int H, int W, int C, const float* rois, int R, float scale,
-                          int PH, int PW, int sampling_ratio, bool aligned, float* dx) {
-    RFI_REQUIRE(N > 0 && H > 0 && W > 0 && PH > 0 && PW > 0, "roi_align: positive sizes");
-    RFI_CHECK_HIP(hipMemsetAsync(dx, 0, (size_t)N * H * W * C * sizeof(float), ctx->stream));
-    if (R == 0) return;
-    ProfScope ps(ctx, FAM_ELEMWISE, 0, (double)R * PH * PW * C * 4 * 5);
-    hipLaunchKernelGGL(roi_align_bwd_kernel, dim3(grid_of((int64_t)R * PH * PW * C)), dim3(256), 0, ctx->stream, dout, N, H, W, C,
-                       rois, R, scale, PH, PW, sampling_ratio, aligned ? 1 : 0, dx);
-    check_launch("roi_align_bwd");
 }
 static MlMaps ml_maps(const float* const* x, float* const* dx, int H0, int W0, float scale0) {
     MlMaps m{};

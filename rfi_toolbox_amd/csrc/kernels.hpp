@@ -357,17 +357,19 @@ void launch_scale_inplace(rfi_ctx* ctx, float* x, int64_t n, float f);
 // RoIAlign over an NHWC feature map; rois = R x (batch index, x1, y1, x2, y2) float32 in image coordinates
 void launch_roi_align_fwd(rfi_ctx* ctx, const float* x, int N, int H, int W, int C, const float* rois, int R, float scale,
                           int PH, int PW, int sampling_ratio, bool aligned, float* out);      // out [R][PH][PW][C]
-// gather form of the RoIAlign gradient: RoIs sorted by image index; writes EVERY element of dx (no accumulation, no atomics)
-void launch_roi_align_bwd_sorted(rfi_ctx* ctx, const float* dout, int N, int H, int W, int C, const float* rois, int R, float scale,
-                                 int PH, int PW, int sr, bool aligned, float* dx);
+// the RoIAlign gradient by gather: RoIs sorted by image index, C % 4 == 0; writes EVERY element of dx [N][H][W][C] once (no
+// prior zeroing, no accumulation, no atomics)
+void launch_roi_align_bwd(rfi_ctx* ctx, const float* dout, int N, int H, int W, int C, const float* rois, int R, float scale,
+                          int PH, int PW, int sr, bool aligned, float* dx);
 void launch_mask_targets(rfi_ctx* ctx, const unsigned char* masks, int G, int H, int W, const float* rois, int R, int PH, int PW,
                          int sr, unsigned char* out);
+// anchors vs the ground-truth boxes of every image (device pointers): labels int8 (1 / 0 / -1; -2 beyond anchor_count[b]),
+// matched ground-truth index (labels 1, else -1) and, if targets != null, the encoded regression targets; best_ws: B x Gmax
+// floats of scratch
 void launch_anchor_match_batched(rfi_ctx* ctx, const float* anchors, int64_t n, int64_t anchor_stride, const int* anchor_count,
                                  const float* gt, int B, int Gmax, const int* gt_count, float hi, float lo, bool low_quality,
                                  float* best_ws, signed char* labels, int* matched, float* targets);
 void launch_nms_batched(rfi_ctx* ctx, const float* boxes, const int* count, int B, int K, float thr, unsigned char* keep);
-void launch_roi_align_bwd(rfi_ctx* ctx, const float* dout, int N, int H, int W, int C, const float* rois, int R, float scale,
-                          int PH, int PW, int sampling_ratio, bool aligned, float* dx);       // dx [N][H][W][C], zeroed here
 // FPN top-down merge: out = lateral + nearest 2x upsampling of top ([N][ceil(H/2)][ceil(W/2)][C])
 void launch_fpn_merge_fwd(rfi_ctx* ctx, const float* lateral, const float* top, int N, int H, int W, int C, float* out);
 void launch_fpn_merge_bwd_top(rfi_ctx* ctx, const float* dout, int N, int H, int W, int C, float* dtop);
@@ -377,22 +379,17 @@ void launch_fpn_merge_bwd_top(rfi_ctx* ctx, const float* dout, int N, int H, int
 // when clip_w > 0; anchors [n_anchors][4] repeat over the n = k * n_anchors delta rows
 void launch_box_decode(rfi_ctx* ctx, const float* anchors, int64_t n_anchors, const float* deltas, int64_t n, float clip_h,
                        float clip_w, float* out);
-// anchors vs G ground-truth boxes (device pointers): labels int8 (1 / 0 / -1), matched ground-truth index (labels 1, else
-// -1) and, if targets != null, the encoded regression targets [n][4]; best_ws: G floats of scratch
-void launch_anchor_match(rfi_ctx* ctx, const float* anchors, int64_t n, const float* gt, int G, float hi, float lo, bool low_quality,
-                         float* best_ws, signed char* labels, int* matched, float* targets);
 // suppression bit matrix [n][ceil(n / 64)] of boxes sorted by descending score (bit j of row i: j > i and IoU > thr)
 void launch_nms_mask(rfi_ctx* ctx, const float* boxes, int n, float thr, unsigned long long* mask);
-// RPN loss on a head output [P][5 A]: BCE on the sampled anchors + smooth L1 on the positives, both / num_sampled;
-// writes the gradient w.r.t. the head output and the two loss terms (device floats)
+// RPN loss on a head output [P][5 A]: BCE on the sampled anchors + smooth L1 on the positives, both / max(*num_sampled_dev, 1)
+// (the normaliser is read from the device); writes the gradient w.r.t. the head output and the two loss terms (device floats)
 size_t rpn_loss_ws_doubles();
+void launch_rpn_loss(rfi_ctx* ctx, const float* head, int64_t P, int A, const signed char* labels, const float* targets,
+                     const int* num_sampled_dev, float beta, float* dhead, double* partial_ws, float* loss2_dev);
 // Fast R-CNN loss on the box head's output [R][5 K1]: mean cross-entropy + smooth L1 of the ground-truth class's deltas over the
 // foreground RoIs / R; labels int32 in [0, K1) (0 = background); writes the gradient and the two terms (partial_ws as rpn_loss)
 void launch_fastrcnn_loss(rfi_ctx* ctx, const float* head, int64_t R, int K1, const int* labels, const float* targets, float beta,
                           float* dhead, double* partial_ws, float* loss2_dev);
-void launch_rpn_loss(rfi_ctx* ctx, const float* head, int64_t P, int A, const signed char* labels, const float* targets,
-                     int64_t num_sampled, float beta, float* dhead, double* partial_ws, float* loss2_dev,
-                     const int* num_sampled_dev = nullptr);      // num_sampled_dev != null: the normaliser is read from the device
 
 // ---------------------------------------------------------------- the detector's box bookkeeping on the device (detect_sample.hip)
 // keys: 64-bit, one segment of `stride` (a power of two <= 8192) keys per workgroup, sorted ascending in place

@@ -10,7 +10,7 @@
 //
 // oracle/mask_head_ref.py holds the same layers as plain torch.nn modules (parity unpinned by the reference).  Only the
 // raw conv outputs are kept; ReLU is applied by the consumers' loads, as in model_cnn.cpp.  rfi_model_input_grad returns
-// the gradient w.r.t. x, which rfi_op_roi_align_backward scatters back into the feature map.
+// the gradient w.r.t. x, which rfi_op_roi_align_backward / rfi_op_roi_align_ml_backward gather back into the feature map.
 //
 // Without `upsample` it is the RPN head (Ren et al. 2015), is the same stack without the transposed conv: Conv3x3(C -> C) + ReLU, then ONE
 // 1x1 conv with 5 A outputs per pixel = A objectness logits followed by A x 4 box deltas (cls_logits and bbox_pred of the

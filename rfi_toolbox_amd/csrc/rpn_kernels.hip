@@ -57,13 +57,14 @@ __global__ __launch_bounds__(64) void nms_mask_kernel(const float* __restrict__ 
 
 // RPN loss over the head output [P][5 A] (A objectness logits, then A x 4 box deltas per pixel): labels [P A] in
 // {1 positive, 0 negative, -1 not sampled}, targets [P A][4].  Writes d(loss)/d(head output) and fp64 partials
-// [block][2] = (sum BCE over sampled, sum smooth-L1 over positives), both terms scaled by inv_count.
+// [block][2] = (sum BCE over sampled, sum smooth-L1 over positives); the gradient is scaled by 1 / max(*count_dev, 1), the
+// normaliser the sampler left on the device.
 __global__ __launch_bounds__(kB) void rpn_loss_kernel(const float* __restrict__ head, int64_t P, int A,
                                                      const signed char* __restrict__ labels, const float* __restrict__ targets,
-                                                     float inv_count, const int* __restrict__ count_dev, float beta,
+                                                     const int* __restrict__ count_dev, float beta,
                                                      float* __restrict__ dhead, double* __restrict__ partial) {
     __shared__ double red[2][kB];
-    if (count_dev) inv_count = 1.0f / (float)max(*count_dev, 1);         // the normaliser lives on the device (the sampler's count)
+    const float inv_count = 1.0f / (float)max(*count_dev, 1);
     double s_obj = 0.0, s_box = 0.0;
     const int64_t total = P * A;
     const int ps = 5 * A;
@@ -172,60 +173,9 @@ __device__ __forceinline__ float iou_of(const float4 a, const float4 b) {
     const float inter = iw * ih;
     return inter / ((a.z - a.x) * (a.w - a.y) + (b.z - b.x) * (b.w - b.y) - inter);
 }
-// best[g] = max over anchors of IoU(gt g, anchor): one block per ground-truth box
-__global__ __launch_bounds__(kB) void gt_best_iou_kernel(const float* __restrict__ anchors, int64_t n, const float* __restrict__ gt,
-                                                        float* __restrict__ best) {
-    __shared__ float red[kB];
-    const float4 g = *reinterpret_cast<const float4*>(gt + (int64_t)blockIdx.x * 4);
-    float m = 0.0f;
-    for (int64_t i = threadIdx.x; i < n; i += kB) m = fmaxf(m, iou_of(g, *reinterpret_cast<const float4*>(anchors + i * 4)));
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int o = kB / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + o]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) best[blockIdx.x] = red[0];
-}
-// per anchor: matched ground truth = first argmax of the IoU; label 1 (IoU >= hi, or -- low-quality rule -- the anchor
-// attains some ground truth's best IoU), 0 (IoU < lo), -1 (between); matched index kept for labels 1 only (else -1)
-__global__ __launch_bounds__(kB) void anchor_match_kernel(const float* __restrict__ anchors, int64_t n, const float* __restrict__ gt,
-                                                         int G, const float* __restrict__ best, float hi, float lo, int low_quality,
-                                                         signed char* __restrict__ labels, int* __restrict__ matched) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float4 a = *reinterpret_cast<const float4*>(anchors + i * 4);
-        float mv = -1.0f;
-        int mi = -1;
-        bool lq = false;
-        for (int g = 0; g < G; ++g) {
-            const float v = iou_of(*reinterpret_cast<const float4*>(gt + (int64_t)g * 4), a);
-            if (v > mv) { mv = v; mi = g; }
-            lq = lq || (low_quality && v == best[g] && v > 0.0f);
-        }
-        int lab = G == 0 ? 0 : (mv >= hi ? 1 : (mv < lo ? 0 : -1));
-        if (lq) lab = 1;
-        labels[i] = (signed char)lab;
-        matched[i] = lab == 1 ? mi : -1;
-    }
-}
-// regression targets of the positive anchors: encode(gt[matched], anchor) with weights 1; zeros elsewhere
-__global__ __launch_bounds__(kB) void box_encode_kernel(const float* __restrict__ anchors, int64_t n, const float* __restrict__ gt,
-                                                       const int* __restrict__ matched, float* __restrict__ targets) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-        const int m = matched[i];
-        if (m >= 0) {
-            const float4 a = *reinterpret_cast<const float4*>(anchors + i * 4), g = *reinterpret_cast<const float4*>(gt + (int64_t)m * 4);
-            const float aw = a.z - a.x, ah = a.w - a.y, gw = g.z - g.x, gh = g.w - g.y;
-            t = make_float4(((g.x + 0.5f * gw) - (a.x + 0.5f * aw)) / aw, ((g.y + 0.5f * gh) - (a.y + 0.5f * ah)) / ah, logf(gw / aw),
-                            logf(gh / ah));
-        }
-        *reinterpret_cast<float4*>(targets + i * 4) = t;
-    }
-}
-
-// ---- batched forms (one launch for every image of a batch): blockIdx.y = image.  Anchors are shared (stride 0) or per
-// image ([B][n][4], `acount[b]` of them valid: the proposals of the RoI stage); ground truth [B][Gmax][4] with gcount[b]
+// One launch for every image of a batch: blockIdx.y = image.  Anchors are shared (stride 0) or per image ([B][n][4],
+// `acount[b]` of them valid: the proposals of the RoI stage); ground truth [B][Gmax][4] with gcount[b].
+// best[b][g] = max over anchors of IoU(gt g, anchor): one block per ground-truth box
 __global__ __launch_bounds__(kB) void gt_best_iou_batched_kernel(const float* __restrict__ anchors, int64_t n, int64_t astride,
                                                                 const int* __restrict__ acount, const float* __restrict__ gt, int Gmax,
                                                                 const int* __restrict__ gcount, float* __restrict__ best) {
@@ -245,7 +195,10 @@ __global__ __launch_bounds__(kB) void gt_best_iou_batched_kernel(const float* __
     }
     if (threadIdx.x == 0) best[(int64_t)b * Gmax + g] = red[0];
 }
-// labels as anchor_match_kernel; an entry beyond acount[b] gets label -2 (not a box), matched -1, zero targets
+// per anchor: matched ground truth = first argmax of the IoU; label 1 (IoU >= hi, or -- low-quality rule -- the anchor
+// attains some ground truth's best IoU), 0 (IoU < lo), -1 (between); matched index kept for labels 1 only (else -1);
+// regression targets of the positives: encode(gt[matched], anchor) with weights 1, zeros elsewhere.  An entry beyond
+// acount[b] gets label -2 (not a box), matched -1, zero targets
 __global__ __launch_bounds__(kB) void anchor_match_batched_kernel(const float* __restrict__ anchors, int64_t n, int64_t astride,
                                                                  const int* __restrict__ acount, const float* __restrict__ gt, int Gmax,
                                                                  const int* __restrict__ gcount, const float* __restrict__ best, float hi,
@@ -351,27 +304,6 @@ void launch_nms_batched(rfi_ctx* ctx, const float* boxes, const int* count, int 
     check_launch("nms_batched");
 }
 
-void launch_anchor_match(rfi_ctx* ctx, const float* anchors, int64_t n, const float* gt, int G, float hi, float lo, bool low_quality,
-                         float* best_ws, signed char* labels, int* matched, float* targets) {
-    RFI_REQUIRE(n > 0 && G >= 0, "anchor_match: empty anchors");
-    RFI_REQUIRE(!((reinterpret_cast<uintptr_t>(anchors) | reinterpret_cast<uintptr_t>(gt) | reinterpret_cast<uintptr_t>(targets)) & 15),
-                "anchor_match: 16-byte aligned boxes");
-    ProfScope ps(ctx, FAM_ELEMWISE, 0, (double)n * (16.0 * (G > 0 ? 2 : 1) + 21));
-    if (G > 0) {
-        hipLaunchKernelGGL(gt_best_iou_kernel, dim3(G), dim3(kB), 0, ctx->stream, anchors, n, gt, best_ws);
-        check_launch("gt_best_iou");
-    }
-    int64_t b = cdiv(n, kB);
-    if (b > 4096) b = 4096;
-    hipLaunchKernelGGL(anchor_match_kernel, dim3((unsigned)b), dim3(kB), 0, ctx->stream, anchors, n, gt, G, best_ws, hi, lo,
-                       low_quality ? 1 : 0, labels, matched);
-    check_launch("anchor_match");
-    if (targets) {
-        hipLaunchKernelGGL(box_encode_kernel, dim3((unsigned)b), dim3(kB), 0, ctx->stream, anchors, n, gt, matched, targets);
-        check_launch("box_encode");
-    }
-}
-
 void launch_fastrcnn_loss(rfi_ctx* ctx, const float* head, int64_t R, int K1, const int* labels, const float* targets, float beta,
                           float* dhead, double* partial_ws, float* loss2_dev) {
     RFI_REQUIRE(R > 0 && K1 >= 2, "fastrcnn_loss: R > 0 and at least background + one class");
@@ -408,19 +340,17 @@ void launch_nms_mask(rfi_ctx* ctx, const float* boxes, int n, float thr, unsigne
 }
 size_t rpn_loss_ws_doubles() { return 2 * 1024; }
 void launch_rpn_loss(rfi_ctx* ctx, const float* head, int64_t P, int A, const signed char* labels, const float* targets,
-                     int64_t num_sampled, float beta, float* dhead, double* partial_ws, float* loss2_dev, const int* num_sampled_dev) {
+                     const int* num_sampled_dev, float beta, float* dhead, double* partial_ws, float* loss2_dev) {
     RFI_REQUIRE(P > 0 && A > 0 && A % 4 == 0, "rpn_loss: P > 0 and anchors per pixel a multiple of 4 (16-byte aligned delta groups)");
     RFI_REQUIRE(!((reinterpret_cast<uintptr_t>(head) | reinterpret_cast<uintptr_t>(targets) | reinterpret_cast<uintptr_t>(dhead)) & 15),
                 "rpn_loss: 16-byte aligned tensors");
-    const float inv = num_sampled > 0 ? 1.0f / (float)num_sampled : 0.0f;
     int64_t blocks = cdiv(P * A, kB);
     if (blocks > 1024) blocks = 1024;
     ProfScope ps(ctx, FAM_ELEMWISE, 0, (double)P * A * (5 * 8 + 17));
-    hipLaunchKernelGGL(rpn_loss_kernel, dim3((unsigned)blocks), dim3(kB), 0, ctx->stream, head, P, A, labels, targets, inv, num_sampled_dev,
-                       beta, dhead, partial_ws);
+    hipLaunchKernelGGL(rpn_loss_kernel, dim3((unsigned)blocks), dim3(kB), 0, ctx->stream, head, P, A, labels, targets, num_sampled_dev, beta,
+                       dhead, partial_ws);
     check_launch("rpn_loss");
-    hipLaunchKernelGGL(rpn_loss_finish_kernel, dim3(1), dim3(64), 0, ctx->stream, partial_ws, (int)blocks, (double)inv, loss2_dev,
-                       num_sampled_dev);
+    hipLaunchKernelGGL(rpn_loss_finish_kernel, dim3(1), dim3(64), 0, ctx->stream, partial_ws, (int)blocks, 0.0, loss2_dev, num_sampled_dev);
     check_launch("rpn_loss_finish");
 }
 

@@ -33,8 +33,13 @@ def roi_align(x, rois, spatial_scale=1.0, output_size=(7, 7), sampling_ratio=2, 
 
 
 def roi_align_backward(dout, input_shape, rois, spatial_scale=1.0, sampling_ratio=2, aligned=False, device=None, to_host=True):
+    """dout (R, PH, PW, C); rois (R, 5) in any order -> d(x) (N, H, W, C).  The kernel gathers per image from RoIs sorted by
+    batch index: the RoIs are stable-sorted on the host and dout is permuted the same way before the call."""
     ctx = Context.get(device)
-    dd, dr = _dev(ctx, dout), _dev(ctx, np.asarray(rois, np.float32).reshape(-1, 5))
+    rois = np.asarray(rois, np.float32).reshape(-1, 5)
+    order = np.argsort(rois[:, 0], kind="stable")
+    dout = dout.numpy() if isinstance(dout, DeviceArray) else np.asarray(dout, np.float32)
+    dd, dr = ctx.to_device(dout[order]), ctx.to_device(rois[order])
     n, h, w, c = input_shape
     r, ph, pw, _ = dd.shape
     dx = ctx.empty((n, h, w, c), np.float32)
@@ -115,26 +120,20 @@ def rpn_loss(head, labels, targets, anchors_per_pixel, beta=1.0 / 9, device=None
     dl = ctx.to_device(lab)
     dt = _dev(ctx, np.asarray(targets, np.float32).reshape(-1, 4))
     dg = ctx.empty(dh.shape, np.float32)
-    lo, lb = C.c_float(), C.c_float()
-    check(lib.rfi_op_rpn_loss(ctx.handle, _p(dh), dh.shape[0], a, _p(dl), _p(dt),
-                              int((lab >= 0).sum()) if num_sampled is None else int(num_sampled), float(beta), _p(dg),
-                              C.byref(lo), C.byref(lb)))
-    return lo.value, lb.value, dg.numpy()
+    count = ctx.to_device(np.asarray([(lab >= 0).sum() if num_sampled is None else num_sampled], np.int32))
+    ws, loss2 = ctx.empty((int(lib.rfi_op_rpn_loss_ws_bytes()),), np.uint8), ctx.empty((2,), np.float32)
+    check(lib.rfi_op_rpn_loss(ctx.handle, _p(dh), dh.shape[0], a, _p(dl), _p(dt), _p(count), float(beta), _p(dg), _p(ws), _p(loss2)))
+    ctx.synchronize()
+    lo, lb = loss2.numpy()
+    return float(lo), float(lb), dg.numpy()
 
 
 def anchor_match(anchors, gt_boxes, fg_iou=0.7, bg_iou=0.3, allow_low_quality=True, device=None):
     """RPN training targets of one image: anchors (n, 4) vs ground truth (g, 4) -> labels int8 (n,) in {1, 0, -1}, matched
     ground-truth index int32 (n,) (-1 unless positive), regression targets float32 (n, 4) (zeros unless positive)."""
-    ctx = Context.get(device)
-    da = _dev(ctx, np.asarray(anchors, np.float32).reshape(-1, 4))
-    g = np.asarray(gt_boxes, np.float32).reshape(-1, 4)
-    dg = ctx.to_device(np.ascontiguousarray(g if len(g) else np.zeros((1, 4), np.float32)))
-    n = da.shape[0]
-    labels, matched, targets = ctx.empty((n,), np.int8), ctx.empty((n,), np.int32), ctx.empty((n, 4), np.float32)
-    check(lib.rfi_op_anchor_match(ctx.handle, _p(da), n, _p(dg), len(g), float(fg_iou), float(bg_iou), 1 if allow_low_quality else 0,
-                                  _p(labels), _p(matched), _p(targets)))
-    ctx.synchronize()
-    return labels.numpy(), matched.numpy(), targets.numpy()
+    labels, matched, targets = anchor_match_batched(np.asarray(anchors, np.float32).reshape(-1, 4), [gt_boxes], fg_iou, bg_iou,
+                                                    allow_low_quality, device=device)
+    return labels[0], matched[0], targets[0]
 
 
 def fastrcnn_loss(head, labels, targets, beta=1.0 / 9, device=None):
@@ -149,9 +148,11 @@ def fastrcnn_loss(head, labels, targets, beta=1.0 / 9, device=None):
         raise ValueError("labels must be one class index in [0, K1) per RoI")
     dl, dt = ctx.to_device(lab), _dev(ctx, np.asarray(targets, np.float32).reshape(r, 4))
     dg = ctx.empty((r, 5 * k1), np.float32)
-    lc, lb = C.c_float(), C.c_float()
-    check(lib.rfi_op_fastrcnn_loss(ctx.handle, _p(dh), r, k1, _p(dl), _p(dt), float(beta), _p(dg), C.byref(lc), C.byref(lb)))
-    return lc.value, lb.value, dg.numpy()
+    ws, loss2 = ctx.empty((int(lib.rfi_op_rpn_loss_ws_bytes()),), np.uint8), ctx.empty((2,), np.float32)
+    check(lib.rfi_op_fastrcnn_loss(ctx.handle, _p(dh), r, k1, _p(dl), _p(dt), float(beta), _p(dg), _p(ws), _p(loss2)))
+    ctx.synchronize()
+    lc, lb = loss2.numpy()
+    return float(lc), float(lb), dg.numpy()
 
 
 # ---------------------------------------------------------------- batched forms: one launch for a whole batch of images
@@ -180,9 +181,11 @@ def anchor_match_batched(anchors, gt_list, fg_iou=0.7, bg_iou=0.3, allow_low_qua
     da, dg, dgc = ctx.to_device(a), ctx.to_device(gt), ctx.to_device(gc)
     dac = None if anchor_counts is None else ctx.to_device(np.ascontiguousarray(np.asarray(anchor_counts, np.int32)))
     labels, matched, targets = ctx.empty((B, n), np.int8), ctx.empty((B, n), np.int32), ctx.empty((B, n, 4), np.float32)
+    best_ws = ctx.empty((B, gt.shape[1]), np.float32)
     check(lib.rfi_op_anchor_match_batched(ctx.handle, _p(da), n, 0 if shared else n, None if dac is None else _p(dac), _p(dg), B,
                                           gt.shape[1], _p(dgc), float(fg_iou), float(bg_iou), 1 if allow_low_quality else 0,
-                                          _p(labels), _p(matched), _p(targets)))
+                                          _p(best_ws), _p(labels), _p(matched), _p(targets)))
+    ctx.synchronize()
     return labels.numpy(), matched.numpy(), targets.numpy()
 
 

@@ -12,7 +12,7 @@ published head (He et al. 2017, fig. 4 right; the layer names are those of torch
 on RoIAlign-ed features ``(R, 14, 14, C)`` (``detection_ops.roi_align``) -> logits ``(R, 28, 28, num_classes)``; the
 training step is the U-Net's (clip + Adam) with the mean binary cross-entropy over every RoI pixel as the loss
 (``num_classes == 1``: one foreground class, RFI).  ``input_grad()`` returns the gradient w.r.t. the RoI features of
-the last backward pass, which ``detection_ops.roi_align_backward`` scatters into the feature map.
+the last backward pass, which ``detection_ops.roi_align_backward`` gathers into the feature map.
 oracle/mask_head_ref.py holds the same layers as plain ``torch.nn`` modules (parity unpinned by the reference).
 """
 from __future__ import annotations

@@ -143,12 +143,6 @@ class MaskRCNN:
                 res[idx] = ops.roi_align(feats[k], rois[idx], 1.0 / _STRIDES[k], (out, out), 2, False)
         return res, lv
 
-    def _roi_align_backward(self, dres, feats_shapes, rois, lv, dfe):
-        for k in range(4):
-            idx = np.flatnonzero(lv == k)
-            if len(idx):
-                dfe[k] += ops.roi_align_backward(dres[idx], feats_shapes[k], rois[idx], 1.0 / _STRIDES[k], 2, False)
-
     def _proposals(self, rpn_out, anchors, n, h, w, extra=None):
         """Per image: top ``pre_nms`` boxes per level by objectness, decoded and clipped, per-level NMS, the ``post_nms``
         best overall (+ ``extra`` boxes: the ground truth during training).  One decode launch per level and ONE NMS
@@ -332,7 +326,7 @@ class MaskRCNN:
         seed, step = self.seed & 0xFFFFFFFFFFFFFFFF, self.sample_step & 0xFFFFFFFF
         self.sample_step += 1
         # ---- RPN targets: matcher (IoU 0.7 / 0.3, low-quality matches) + sampler (256 per image, at most half positive)
-        check(lib.rfi_op_anchor_match_batched_ws(H, P(b.anchors), b.A, 0, None, P(b.gt), n, G, P(b.gt_count), 0.7, 0.3, 1, P(b.best_ws),
+        check(lib.rfi_op_anchor_match_batched(H, P(b.anchors), b.A, 0, None, P(b.gt), n, G, P(b.gt_count), 0.7, 0.3, 1, P(b.best_ws),
                                                  P(b.m_lab), P(b.m_idx), P(b.m_tgt)))
         check(lib.rfi_op_sample_keys(H, P(b.m_lab), n, b.A, None, seed, step, 0, P(b.keys_a), b.stride_a))
         check(lib.rfi_op_segsort_u64(H, P(b.keys_a), n, b.stride_a))
@@ -345,7 +339,7 @@ class MaskRCNN:
             """Loss (global normaliser on the device) and backward pass of the shared head at one level; its activations of this
             level must be the ones the head holds."""
             _, hl, wl, _ = b.shapes[lvl]
-            check(lib.rfi_op_rpn_loss_devcount(H, P(b.rpn_out[lvl]), n * hl * wl, 4, P(b.rpn_lab[lvl]), P(b.rpn_tgt[lvl]), P(b.n_sampled),
+            check(lib.rfi_op_rpn_loss(H, P(b.rpn_out[lvl]), n * hl * wl, 4, P(b.rpn_lab[lvl]), P(b.rpn_tgt[lvl]), P(b.n_sampled),
                                                1.0 / 9, P(b.rpn_dout[lvl]), P(b.rpn_ws[lvl]), C.c_void_p(b.rpn_loss2.ptr + 8 * lvl)))
             check(lib.rfi_model_backward_dlogits(self.rpn._h, P(b.feats[lvl]), DEVICE, P(b.rpn_dout[lvl]), DEVICE, n, hl, wl))
             self.rpn.accumulate_gradients("add")
@@ -373,7 +367,7 @@ class MaskRCNN:
         check(lib.rfi_op_proposals_select(H, P(b.cand_boxes), P(b.cand_scores), P(b.keep), n, 5, K, self.post_nms, P(b.gt), G,
                                           P(b.gt_count), b.pmax, P(b.props), P(b.pcount)))
         # ---- RoI targets: matcher at 0.5, sampler (128 per image, at most a quarter foreground), compact lists + levels
-        check(lib.rfi_op_anchor_match_batched_ws(H, P(b.props), b.pmax, b.pmax, P(b.pcount), P(b.gt), n, G, P(b.gt_count), 0.5, 0.5, 0,
+        check(lib.rfi_op_anchor_match_batched(H, P(b.props), b.pmax, b.pmax, P(b.pcount), P(b.gt), n, G, P(b.gt_count), 0.5, 0.5, 0,
                                                  P(b.best_ws), P(b.r_lab), P(b.r_idx), P(b.r_tgt)))
         check(lib.rfi_op_roi_sample(H, P(b.r_lab), P(b.pcount), n, b.pmax, self.roi_batch, self.roi_batch // 4, seed, step, 2, P(b.sel),
                                     P(b.nsel), P(b.npos)))
@@ -398,7 +392,7 @@ class MaskRCNN:
         if R:
             check(lib.rfi_op_roi_align_ml(H, b.pf4, n, h0, w0, F, 0.25, P(b.rois), P(b.roi_lvl), P(b.counts), R, 7, 7, 2, P(b.roi7)))
             check(lib.rfi_model_forward_nhwc(self.box._h, P(b.roi7), DEVICE, R, 1, 1, P(b.box_out), DEVICE))
-            check(lib.rfi_op_fastrcnn_loss_dev(H, P(b.box_out), R, k1, P(b.box_lab), P(b.box_tgt), 1.0 / 9, P(b.box_dout), P(b.box_ws),
+            check(lib.rfi_op_fastrcnn_loss(H, P(b.box_out), R, k1, P(b.box_lab), P(b.box_tgt), 1.0 / 9, P(b.box_dout), P(b.box_ws),
                                                P(b.box_loss2)))
             check(lib.rfi_model_backward_dlogits(self.box._h, P(b.roi7), DEVICE, P(b.box_dout), DEVICE, R, 1, 1))
             check(lib.rfi_model_input_grad(self.box._h, P(b.roi7_grad), DEVICE))
