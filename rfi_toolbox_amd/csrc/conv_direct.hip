@@ -8,7 +8,16 @@ namespace {
 
 constexpr int kBlock = 256;
 
+// BF16 (the bf16 compute modes): both operands of every product are rounded to bfloat16 (RNE) and accumulated in float32,
+// as the MFMA kernels of those modes do -- a layer the matrix cores do not take runs the same arithmetic as its neighbours
+template <bool BF16>
+__device__ __forceinline__ float operand(float v) {
+    if constexpr (BF16) return (float)(__bf16)v;
+    return v;
+}
+
 // thread = (output pixel, cout); cout fastest so that stores and weight reads coalesce
+template <bool BF16>
 __global__ void conv_direct_kernel(ConvArgs a) {
     const int z = blockIdx.y;
     const float* __restrict__ w = a.w + (size_t)z * a.Cout * a.Cin * (a.zgroups > 1 ? 1 : 0);
@@ -35,10 +44,10 @@ __global__ void conv_direct_kernel(ConvArgs a) {
                 for (int ci = 0; ci < a.Cin; ++ci) {
                     float v = xp[ci] * a.xf.scale[ci] + a.xf.shift[ci];
                     if (a.xf.relu) v = v > 0.0f ? v : v * a.xf.slope;
-                    acc = fmaf(v, wp[ci], acc);
+                    acc = fmaf(operand<BF16>(v), operand<BF16>(wp[ci]), acc);
                 }
             } else {
-                for (int ci = 0; ci < a.Cin; ++ci) acc = fmaf(xp[ci], wp[ci], acc);
+                for (int ci = 0; ci < a.Cin; ++ci) acc = fmaf(operand<BF16>(xp[ci]), operand<BF16>(wp[ci]), acc);
             }
         }
         const int64_t opix = ((int64_t)n * a.Hout + (oy * a.osy + ooy)) * a.Wout + (ox * a.osx + oox);
@@ -48,6 +57,7 @@ __global__ void conv_direct_kernel(ConvArgs a) {
 
 // thread = one dW element, ordered (tap, cx, cy) with cy fastest; grid.y = pixel split.
 // slab[split][tap][cx][cy] partial sums, reduced afterwards.
+template <bool BF16>
 __global__ void wgrad_direct_kernel(WgradArgs a, int64_t pix_per_split, int64_t nout) {
     const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (o >= nout) return;
@@ -80,7 +90,7 @@ __global__ void wgrad_direct_kernel(WgradArgs a, int64_t pix_per_split, int64_t 
                 yv = yv * sys + syh;
                 if (a.xf_y.relu) yv = yv > 0.0f ? yv : yv * a.xf_y.slope;
             }
-            acc = fmaf(xv, yv, acc);
+            acc = fmaf(operand<BF16>(xv), operand<BF16>(yv), acc);
         }
         if (++x == a.W) {
             x = 0;
@@ -114,8 +124,8 @@ void launch_conv_direct(rfi_ctx* ctx, const ConvArgs& a) {
     if (blocks > 65536) blocks = 65536;
     const double flops = 2.0 * total * a.R * a.R * a.Cin * a.zgroups;
     ProfScope ps(ctx, FAM_CONV_DIRECT, flops, 0);
-    hipLaunchKernelGGL(conv_direct_kernel, dim3((unsigned)blocks, a.zgroups), dim3(kBlock), 0,
-                       ctx->stream, a);
+    if (a.bf16) hipLaunchKernelGGL(conv_direct_kernel<true>, dim3((unsigned)blocks, a.zgroups), dim3(kBlock), 0, ctx->stream, a);
+    else hipLaunchKernelGGL(conv_direct_kernel<false>, dim3((unsigned)blocks, a.zgroups), dim3(kBlock), 0, ctx->stream, a);
     check_launch("conv_direct");
 }
 
@@ -144,8 +154,9 @@ void launch_wgrad_direct(rfi_ctx* ctx, const WgradArgs& a) {
     const int64_t pps = cdiv(M, nsplit);
     {
         ProfScope ps(ctx, FAM_CONV_DIRECT, 2.0 * M * nout, 0);
-        hipLaunchKernelGGL(wgrad_direct_kernel, dim3((unsigned)cdiv(nout, kBlock), nsplit), dim3(kBlock),
-                           0, ctx->stream, a, pps, nout);
+        const dim3 grid((unsigned)cdiv(nout, kBlock), nsplit);
+        if (a.bf16) hipLaunchKernelGGL(wgrad_direct_kernel<true>, grid, dim3(kBlock), 0, ctx->stream, a, pps, nout);
+        else hipLaunchKernelGGL(wgrad_direct_kernel<false>, grid, dim3(kBlock), 0, ctx->stream, a, pps, nout);
         check_launch("wgrad_direct");
     }
     {

@@ -61,7 +61,7 @@ struct ConvArgs {
                                       // Cout = 4 * fold, output channel co belongs to phase z = co / fold, channel co % fold
     InXform xf;
     double algo_flops = -1;           // algorithmic FLOPs for the profile (default: from the shape)
-    bool bf16 = false;                // MFMA kernels: operands rounded to bf16 in registers, fp32 accumulate
+    bool bf16 = false;                // MFMA and direct kernels: operands rounded to bf16 in registers, fp32 accumulate
     bool bf16x3 = false;              // MFMA kernels: float32 operands split into 3 bf16 pieces, 6 bf16 MFMAs per K=16
     int planes = 0;                   // 1 / 3: run on the plane kernels through temporary plane copies (IMPL_PLANES_*)
     // optional: per-channel (sum, sumsq) of the OUTPUT in the epilogue (BatchNorm statistics).  in: stats
@@ -120,7 +120,7 @@ struct WgradArgs {
     float* slab = nullptr;            // workspace for split partials
     size_t slab_floats = 0;
     double algo_flops = -1;
-    bool bf16 = false;                // MFMA kernel: operands rounded to bf16 in registers, fp32 accumulate
+    bool bf16 = false;                // MFMA and direct kernels: operands rounded to bf16 in registers, fp32 accumulate
     bool bf16x3 = false;              // MFMA kernel: float32 emulated by 3 x bf16 pieces
     int planes = 0;                   // 1 / 3: plane kernel through temporary plane copies (IMPL_PLANES_*)
 };
