@@ -649,6 +649,36 @@ int rfi_op_roi_align_ml(rfi_ctx* ctx, const float* const* maps_host, int n, int 
 int rfi_op_roi_align_ml_backward(rfi_ctx* ctx, float* const* dmaps_host, int n, int h0, int w0, int c, float scale0, const float* dout,
                                  const float* rois, const int32_t* level, const int32_t* img_start, int max_rois, int ph, int pw,
                                  int sampling_ratio);
+/* ---- Detector inference on the device (csrc/detect_infer.hip): what rfi_toolbox_amd.models.MaskRCNN.predict does in NumPy
+ * behind the box head and the mask head; MaskRCNN.detect chains these with the entry points above.  All pointers are device
+ * pointers; nothing here synchronises or allocates.  Box tensors are 16-byte aligned.
+ * detect_candidates: head [images pmax][5 k1] (k1 class logits, then k1 x 4 deltas; row b pmax + r = proposal r of image b),
+ *   props [images][pmax][4] with pcount[b] valid rows, pmax <= 256.  Per image and foreground class c = 1 .. k1 - 1:
+ *   prob = softmax(logits)[c] in float32, class c's deltas decoded against the proposal (weights 1, dw / dh <= log(1000/16))
+ *   and clipped to [0, clip_w] x [0, clip_h]; rows with prob > score_thresh and both sides >= min_size, sorted by descending
+ *   prob (ties: ascending proposal index) -> set b (k1 - 1) + c - 1 of boxes [sets][pmax][4], scores [sets][pmax] (-inf behind
+ *   the count), counts [sets]: the input form of rfi_op_nms_batched.
+ * detect_select: from the candidate sets ([images][classes][k], classes <= 32 sets of k <= 256) and the NMS keep bytes, per
+ *   image the max_det best kept boxes (descending score, ties class-major, then by position in the class's set) ->
+ *   det_boxes [images][max_det][4] (zero padded), det_scores, det_labels (int32, 1-based class; 0 padding), det_count
+ *   [images], and the mask branch's RoI list rois [images max_det][5] (image, x1, y1, x2, y2; padding rows: a zero box of their
+ *   own image) with level = [area >= t1] + [area >= t2] + [area >= t3].
+ * rois_from_boxes: props [images][pmax][4] + pcount -> rois [images pmax][5] + level at a fixed stride of pmax rows per image
+ *   (rows beyond pcount[b]: a zero box of image b, whatever props holds there).
+ * mask_paste: logits [images max_det][28][28] -> p = sigmoid, bilinear sample at (px + 0.5 - x1) / max(x2 - x1, 1e-6) * 28 - 0.5
+ *   (indices clamped to [0, 27], fractions to [0, 1]) for the pixels of [max(floor(x1), 0), min(ceil(x2), w)) x [.. y ..),
+ *   mask = v > 0.5, 0 elsewhere and for slots >= det_count[b]; rfi_mask [images][h][w] = OR over the image's instances;
+ *   masks [images][max_det][h][w] is written unless null.  max_det <= 256, w % 4 == 0, masks 4-byte aligned. */
+int rfi_op_detect_candidates(rfi_ctx* ctx, const float* head, const float* props, const int32_t* pcount, int images, int pmax, int k1,
+                             float clip_h, float clip_w, float score_thresh, float min_size, float* boxes, float* scores,
+                             int32_t* counts);
+int rfi_op_detect_select(rfi_ctx* ctx, const float* boxes, const float* scores, const uint8_t* keep, int images, int classes, int k,
+                         int max_det, float t1, float t2, float t3, float* det_boxes, float* det_scores, int32_t* det_labels,
+                         int32_t* det_count, float* rois, int32_t* level);
+int rfi_op_rois_from_boxes(rfi_ctx* ctx, const float* props, const int32_t* pcount, int images, int pmax, float t1, float t2, float t3,
+                           float* rois, int32_t* level);
+int rfi_op_mask_paste(rfi_ctx* ctx, const float* logits, const float* det_boxes, const int32_t* det_count, int images, int max_det, int h,
+                      int w, uint8_t* rfi_mask, uint8_t* masks);
 /* ---- elementwise kernels of the bfloat16 data flow (ResNet-style encoder, BatchNorm backward), for the kernel-level parity
  *      tests.  bfloat16 tensors are dense [m][c] arrays of uint16 bit patterns, c % 8 == 0, 16-byte aligned.  No counterpart
  *      in the reference (its tensors are float32): these are the builder's reduced-precision storage forms of

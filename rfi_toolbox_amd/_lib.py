@@ -163,6 +163,10 @@ _PROTOS = {
                                 _vp, _vp, _vp, _vp, _vp]),
     "rfi_op_roi_align_ml": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "rfi_op_roi_align_ml_backward": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
+    "rfi_op_detect_candidates": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp]),
+    "rfi_op_detect_select": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rfi_op_rois_from_boxes": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp]),
+    "rfi_op_mask_paste": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "rfi_op_bn_add_relu16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _vp]),
     "rfi_op_relu_mask_sum16": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i, _vp]),
     "rfi_op_bn_backward16": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),

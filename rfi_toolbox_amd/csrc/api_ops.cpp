@@ -552,6 +552,43 @@ int rfi_op_roi_compact(rfi_ctx* ctx, const int32_t* sel, const int32_t* nsel, co
                            cls, tgt, gt, level, img_start, rois_fg, rois_gt, level_fg, fg_start, counts);
     });
 }
+// ---- detector inference on the device (detect_infer.hip): nothing here synchronises or allocates
+int rfi_op_detect_candidates(rfi_ctx* ctx, const float* head, const float* props, const int32_t* pcount, int images, int pmax, int k1,
+                             float clip_h, float clip_w, float score_thresh, float min_size, float* boxes, float* scores,
+                             int32_t* counts) {
+    return guarded([&] {
+        ctx->activate();
+        RFI_REQUIRE(head && props && pcount && boxes && scores && counts, "detect_candidates: null tensor");
+        launch_detect_candidates(ctx, head, props, pcount, images, pmax, k1, clip_h, clip_w, score_thresh, min_size, boxes, scores, counts);
+    });
+}
+int rfi_op_detect_select(rfi_ctx* ctx, const float* boxes, const float* scores, const uint8_t* keep, int images, int classes, int k,
+                         int max_det, float t1, float t2, float t3, float* det_boxes, float* det_scores, int32_t* det_labels,
+                         int32_t* det_count, float* rois, int32_t* level) {
+    return guarded([&] {
+        ctx->activate();
+        RFI_REQUIRE(boxes && scores && keep && det_boxes && det_scores && det_labels && det_count && rois && level,
+                    "detect_select: null tensor");
+        launch_detect_select(ctx, boxes, scores, keep, images, classes, k, max_det, t1, t2, t3, det_boxes, det_scores, det_labels,
+                             det_count, rois, level);
+    });
+}
+int rfi_op_rois_from_boxes(rfi_ctx* ctx, const float* props, const int32_t* pcount, int images, int pmax, float t1, float t2, float t3,
+                           float* rois, int32_t* level) {
+    return guarded([&] {
+        ctx->activate();
+        RFI_REQUIRE(props && pcount && rois && level, "rois_from_boxes: null tensor");
+        launch_rois_from_boxes(ctx, props, pcount, images, pmax, t1, t2, t3, rois, level);
+    });
+}
+int rfi_op_mask_paste(rfi_ctx* ctx, const float* logits, const float* det_boxes, const int32_t* det_count, int images, int max_det, int h,
+                      int w, uint8_t* rfi_mask, uint8_t* masks) {
+    return guarded([&] {
+        ctx->activate();
+        RFI_REQUIRE(logits && det_boxes && det_count && rfi_mask, "mask_paste: null tensor");
+        launch_mask_paste(ctx, logits, det_boxes, det_count, images, max_det, h, w, rfi_mask, masks);
+    });
+}
 int rfi_op_bn_add_relu16(rfi_ctx* ctx, const uint16_t* y, const float* scale, const float* shift, const uint16_t* s, const float* s_scale,
                          const float* s_shift, int64_t m, int c, uint16_t* out) {
     return guarded([&] {

@@ -14,12 +14,12 @@
 // keeps its elements of SMALLEST (r, i) -- a function of (seed, step, image, element) only, which the oracle evaluates with
 // the same generator (oracle/synth_ref.philox4x32_10).
 #include "kernels.hpp"
+#include "detect_sort.hpp"
 
 namespace rfi {
 namespace {
 
 constexpr int kB = 256;
-typedef unsigned long long u64;
 
 struct U4 { unsigned x, y, z, w; };
 __device__ __forceinline__ U4 philox4x32_10(U4 c, unsigned k0, unsigned k1) {
@@ -35,27 +35,6 @@ __device__ __forceinline__ U4 philox4x32_10(U4 c, unsigned k0, unsigned k1) {
     return c;
 }
 
-// ascending bitonic sort of s[0 .. n) in LDS, n a power of two; every thread of the block takes part
-__device__ void bitonic_sort(u64* s, int n) {
-    for (int k = 2; k <= n; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            __syncthreads();
-            for (int t = threadIdx.x; t < (n >> 1); t += blockDim.x) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                const int p = i | j;
-                const bool up = (i & k) == 0;
-                const u64 a = s[i], b = s[p];
-                if ((a > b) == up) { s[i] = b; s[p] = a; }
-            }
-        }
-    __syncthreads();
-}
-
-// order-preserving image of a float32 for DESCENDING order: smaller key = larger score; -0.0 and 0.0 tie
-__device__ __forceinline__ unsigned desc_key(float s) {
-    const unsigned bits = __float_as_uint((-s) + 0.0f);
-    return (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);
-}
 __device__ __forceinline__ int lower_bound(const u64* s, int n, u64 v) {      // first index with s[i] >= v
     int a = 0, b = n;
     while (a < b) { const int m = (a + b) >> 1; if (s[m] < v) a = m + 1; else b = m; }
@@ -359,12 +338,6 @@ __global__ __launch_bounds__(kB) void roi_compact_kernel(const int* __restrict__
             o.level_fg[f] = lvl;
         }
     }
-}
-
-int pow2_at_least(int n) {
-    int p = 2;
-    while (p < n) p <<= 1;
-    return p;
 }
 
 }  // namespace

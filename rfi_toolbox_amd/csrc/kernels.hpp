@@ -430,6 +430,25 @@ void launch_roi_align_ml_fwd(rfi_ctx* ctx, const float* const* maps, int N, int 
 void launch_roi_align_ml_bwd(rfi_ctx* ctx, float* const* dmaps, int N, int H0, int W0, int C, float scale0, const float* dout,
                              const float* rois, const int* level, const int* img_start, int max_rois, int PH, int PW, int sr);
 
+// ---------------------------------------------------------------- detector inference on the device (detect_infer.hip)
+// per (image, foreground class): softmax probability, the class's deltas decoded against the proposals and clipped, rows with
+// prob > score_thresh and sides >= min_size sorted by descending probability -> boxes [B (K1 - 1)][Pmax][4], scores (-inf
+// behind the count), counts; head [B Pmax][5 K1], Pmax <= 256
+void launch_detect_candidates(rfi_ctx* ctx, const float* head, const float* props, const int* pcount, int B, int Pmax, int K1, float clip_h,
+                              float clip_w, float score_thresh, float min_size, float* boxes, float* scores, int* counts);
+// per image: the max_det best kept candidates of its `classes` sets of K (descending score, ties class-major) -> detections
+// (zero padded), their count, the mask branch's RoI rows [B max_det][5] and pyramid levels
+void launch_detect_select(rfi_ctx* ctx, const float* boxes, const float* scores, const unsigned char* keep, int B, int classes, int K,
+                          int max_det, float t1, float t2, float t3, float* det_boxes, float* det_scores, int* det_labels, int* det_count,
+                          float* rois, int* level);
+// props [B][Pmax][4] + pcount -> rois [B Pmax][5] + level (rows beyond pcount[b]: a zero box of image b)
+void launch_rois_from_boxes(rfi_ctx* ctx, const float* props, const int* pcount, int B, int Pmax, float t1, float t2, float t3, float* rois,
+                            int* level);
+// 28 x 28 mask logits [B max_det][28][28] pasted into their boxes: rfi_mask [B][H][W] = union, masks (may be null)
+// [B][max_det][H][W]; W % 4 == 0
+void launch_mask_paste(rfi_ctx* ctx, const float* logits, const float* det_boxes, const int* det_count, int B, int max_det, int H, int W,
+                       unsigned char* rfi_mask, unsigned char* masks);
+
 // ---------------------------------------------------------------- ResNet-style encoder pieces (resnet_kernels.hip)
 void launch_s2d(rfi_ctx* ctx, const float* x, int N, int H, int W, int C, float* out);          // [N,H,W,C] -> [N,H/2,W/2,4C]
 void launch_d2s_add(rfi_ctx* ctx, const float* dxp, const float* ds, View extra, int N, int H, int W, int C, float* out);

@@ -10,13 +10,16 @@ draws Philox4x32-10(counter (i, b, stream, step), key seed) and a class keeps it
 objectness scores, decode + clip, per-level NMS, the post-NMS selection, matching, the compact RoI lists and their pyramid
 levels, multi-level RoIAlign both ways in one launch each.  What crosses PCIe inside a step: the ground-truth boxes going up,
 two integers (RoI and foreground counts, read back under the RPN head's backward pass) and the loss scalars coming down.
-``predict`` is the plain host-array form.  Conventions where implementations differ: box-coder weights 1 in both stages,
+``detect`` is inference in the same manner (``csrc/detect_infer.hip``: per-class candidates, selection of the detections, mask
+paste with the union): images go up, detections and masks come down, nothing is read back in between.  ``predict`` is the
+plain host-array form of the same computation.  Conventions where implementations differ: box-coder weights 1 in both stages,
 four anchors per pixel (aspect ratios 0.5, 1, 2 and a 1.5x square), level assignment
 ``k = clip(floor(4 + log2(sqrt(area) / (image_size / 2))), 2, 5)`` evaluated as three area comparisons.
 
     det = MaskRCNN(num_classes=2)
     losses = det.train_step(images_nhwc, [{"boxes": (g, 4), "labels": (g,), "masks": (g, H, W)}, ...])
-    out = det.predict(images_nhwc)          # per image: boxes, scores, labels, masks (full-size bool), rfi_mask (union)
+    out = det.detect(images_nhwc)           # per image: boxes, scores, labels, masks (full-size bool), rfi_mask (union)
+    out = det.predict(images_nhwc)          # the same through host arrays
 """
 from __future__ import annotations
 
@@ -180,6 +183,8 @@ class MaskRCNN:
 
     # ---- inference
     def predict(self, images):
+        """The plain host-array form: every stage's tensors pass through NumPy.  ``detect`` is the device form (same
+        results, nothing leaves HBM between the stages); this one takes any size ``_check_size`` accepts."""
         x = np.ascontiguousarray(np.asarray(images, np.float32))
         n, h, w, _ = x.shape
         self._check_size(h, w, False)
@@ -225,6 +230,154 @@ class MaskRCNN:
             out.append({"boxes": boxes, "scores": scores, "labels": labels, "masks": masks,
                         "rfi_mask": masks.any(0) if len(masks) else np.zeros((h, w), bool)})
         return out
+
+    # ---- inference on the device: nothing is read back between the image upload and the result download
+    def _check_detect(self, n, h, w):
+        """What ``detect`` supports, checked before anything is allocated or launched."""
+        self._check_size(h, w, False)
+        if n < 1:
+            raise ValueError("MaskRCNN.detect: at least one image")
+        if (h // 4) * (w // 4) * 4 > _MAX_ANCHORS:
+            raise ValueError(f"MaskRCNN.detect: at most {_MAX_ANCHORS} anchors on the finest level (512 x 512), {h} x {w} has "
+                             f"{(h // 4) * (w // 4) * 4}; use predict for larger images")
+        if not (1 <= self.pre_nms <= 256 and 1 <= self.post_nms <= 256):
+            raise ValueError(f"MaskRCNN.detect: pre_nms and post_nms in 1 .. 256, got {self.pre_nms}, {self.post_nms}")
+        if not 1 <= self.max_det <= self.post_nms:
+            raise ValueError(f"MaskRCNN.detect: 1 <= max_det <= post_nms, got {self.max_det} (post_nms {self.post_nms})")
+        if not 2 <= self.num_classes <= 33:
+            raise ValueError(f"MaskRCNN.detect: 2 .. 33 classes (background included), got {self.num_classes}")
+
+    def _detect_buffers(self, n, h, w):
+        key = (n, h, w, self.pre_nms, self.post_nms, self.max_det)
+        d = getattr(self, "_dbuf", None)
+        if getattr(self, "_dbuf_key", None) == key:
+            return d
+        self._check_detect(n, h, w)
+        ctx, F, k1 = self.backbone.ctx, self.F, self.num_classes
+        K, P, D = self.pre_nms, self.post_nms, self.max_det
+        d = type("DetectBuffers", (), {})()
+        d.x = None                                   # the upload buffer: made on the first host-array call
+        d.shapes = [(n, h // s, w // s, F) for s in _STRIDES]
+        d.feats = [ctx.empty(sh, np.float32) for sh in d.shapes]
+        d.pf = (C.c_void_p * 5)(*[f.ptr for f in d.feats])
+        d.pf4 = (C.c_void_p * 4)(*[f.ptr for f in d.feats[:4]])
+        d.rpn_out = [ctx.empty((sh[0], sh[1], sh[2], 20), np.float32) for sh in d.shapes]
+        anchors = self._anchors(h, w)
+        d.aoff = np.concatenate([[0], np.cumsum([len(a) for a in anchors])]).astype(np.int64)
+        d.anchors = ctx.to_device(np.concatenate(anchors).astype(np.float32))
+        d.stride_l = [max(2, 1 << max(1, int(len(a) - 1).bit_length())) for a in anchors]
+        d.keys_l = [ctx.empty((n, st), np.uint64) for st in d.stride_l]
+        d.cand_boxes, d.cand_scores = ctx.empty((n, 5, K, 4), np.float32), ctx.empty((n, 5, K), np.float32)
+        d.cand_counts, d.keep = ctx.empty((n, 5), np.int32), ctx.empty((n, 5, K), np.uint8)
+        d.no_gt, d.no_gt_count = ctx.empty((n, 1, 4), np.float32), ctx.empty((n,), np.int32)     # proposals_select's (empty) ground truth
+        d.no_gt.zero_(); d.no_gt_count.zero_()
+        d.props, d.pcount = ctx.empty((n, P, 4), np.float32), ctx.empty((n,), np.int32)
+        d.rois, d.roi_lvl = ctx.empty((n * P, 5), np.float32), ctx.empty((n * P,), np.int32)
+        d.rows = ctx.to_device(np.asarray([n * P, n * D], np.int32))                           # roi_align_ml's row counts
+        d.roi7 = ctx.empty((n * P, 7, 7, F), np.float32)
+        d.box_out = ctx.empty((n * P, 5 * k1), np.float32)
+        d.cls_boxes, d.cls_scores = ctx.empty((n, k1 - 1, P, 4), np.float32), ctx.empty((n, k1 - 1, P), np.float32)
+        d.cls_counts, d.cls_keep = ctx.empty((n, k1 - 1), np.int32), ctx.empty((n, k1 - 1, P), np.uint8)
+        d.boxes, d.scores = ctx.empty((n, D, 4), np.float32), ctx.empty((n, D), np.float32)
+        d.labels, d.counts = ctx.empty((n, D), np.int32), ctx.empty((n,), np.int32)
+        d.rois_m, d.lvl_m = ctx.empty((n * D, 5), np.float32), ctx.empty((n * D,), np.int32)
+        d.roi14 = ctx.empty((n * D, 14, 14, F), np.float32)
+        d.mask_out = ctx.empty((n * D, 28, 28), np.float32)
+        d.rfi_mask = ctx.empty((n, h, w), np.uint8)
+        d.masks = None                               # (n, max_det, H, W): made on the first call that asks for instance masks
+        self._dbuf_key, self._dbuf = key, d
+        return d
+
+    def detect(self, images, instance_masks=True, out="host"):
+        """``predict`` with every stage on device pointers (``csrc/detect_infer.hip`` and the entry points of ``train_step``):
+        backbone, RPN head, per-level top-k / decode / NMS, proposal selection, RoIAlign, box head, per-class candidates /
+        NMS / selection, RoIAlign, mask head, paste.  Every launch size follows from (n, H, W, post_nms, max_det,
+        num_classes): nothing is read back between the image upload and the result download.
+
+        ``images``: NumPy (n, H, W, C) or a float32 NHWC ``DeviceArray`` (used in place).  H and W multiples of 64 up to 512 x 512,
+        ``pre_nms`` and ``post_nms`` <= 256, ``max_det`` <= ``post_nms`` (``ValueError`` otherwise; ``predict`` has no such limits).
+        ``out="host"``: ``predict``'s list of dicts; ``out="device"``: one dict of ``DeviceArray``s -- boxes (n, max_det, 4), scores,
+        labels (int32), counts (n,), rfi_mask (n, H, W) uint8, masks (n, max_det, H, W) uint8 -- zero behind ``counts`` and valid
+        until the next ``detect`` at this shape.  ``instance_masks=False``: no ``masks`` (neither written nor downloaded), only
+        the union ``rfi_mask``."""
+        from ..runtime import DeviceArray
+        if out not in ("host", "device"):
+            raise ValueError(f"MaskRCNN.detect: out must be 'host' or 'device', got {out!r}")
+        dev_in = isinstance(images, DeviceArray)
+        if dev_in and images.dtype != np.float32:
+            raise ValueError("MaskRCNN.detect: a DeviceArray input must be float32 NHWC")
+        x = images if dev_in else np.ascontiguousarray(np.asarray(images, np.float32))
+        if len(x.shape) != 4:
+            raise ValueError(f"MaskRCNN.detect: images must be (n, H, W, C), got {tuple(x.shape)}")
+        n, h, w, c = x.shape
+        if c != self.backbone.in_channels:
+            raise ValueError(f"MaskRCNN.detect: expected {self.backbone.in_channels} input channels, got {c}")
+        d = self._detect_buffers(n, h, w)
+        ctx, F, k1 = self.backbone.ctx, self.F, self.num_classes
+        K, Pn, D = self.pre_nms, self.post_nms, self.max_det
+        H = ctx.handle
+        P = lambda a: C.c_void_p(a.ptr)  # noqa: E731
+        for m in (self.rpn, self.box, self.mask):
+            m.eval()
+        if dev_in:
+            x_in = x
+        else:
+            if d.x is None:
+                d.x = ctx.empty((n, h, w, c), np.float32)
+            d.x.copy_from(x)
+            x_in = d.x
+        if instance_masks and d.masks is None:
+            d.masks = ctx.empty((n, D, h, w), np.uint8)
+        # ---- backbone, RPN head and the K best anchors of every level
+        check(lib.rfi_backbone_forward(self.backbone._h, P(x_in), DEVICE, n, h, w, d.pf, DEVICE))
+        for lvl in range(5):
+            _, hl, wl, _ = d.shapes[lvl]
+            check(lib.rfi_model_forward_nhwc(self.rpn._h, P(d.feats[lvl]), DEVICE, n, hl, wl, P(d.rpn_out[lvl]), DEVICE))
+            check(lib.rfi_op_topk_keys(H, P(d.rpn_out[lvl]), n, hl * wl, 4, P(d.keys_l[lvl]), d.stride_l[lvl]))
+            check(lib.rfi_op_segsort_u64(H, P(d.keys_l[lvl]), n, d.stride_l[lvl]))
+            check(lib.rfi_op_topk_decode(H, P(d.keys_l[lvl]), n, d.stride_l[lvl], hl * wl, 4, K, P(d.rpn_out[lvl]),
+                                         C.c_void_p(d.anchors.ptr + int(d.aoff[lvl]) * 16), float(h), float(w), 1e-2, P(d.cand_boxes),
+                                         P(d.cand_scores), P(d.cand_counts), 5, lvl))
+        # ---- proposals: per-level NMS, the post_nms best of an image (no ground truth appended)
+        check(lib.rfi_op_nms_batched(H, P(d.cand_boxes), P(d.cand_counts), n * 5, K, float(self.rpn_nms), P(d.keep)))
+        check(lib.rfi_op_proposals_select(H, P(d.cand_boxes), P(d.cand_scores), P(d.keep), n, 5, K, Pn, P(d.no_gt), 1, P(d.no_gt_count),
+                                          Pn, P(d.props), P(d.pcount)))
+        # ---- box head on post_nms rows per image (rows behind an image's count: a zero box, dropped by detect_candidates)
+        t1, t2, t3 = self._level_thresholds(max(h, w))
+        h0, w0 = h // 4, w // 4
+        check(lib.rfi_op_rois_from_boxes(H, P(d.props), P(d.pcount), n, Pn, t1, t2, t3, P(d.rois), P(d.roi_lvl)))
+        check(lib.rfi_op_roi_align_ml(H, d.pf4, n, h0, w0, F, 0.25, P(d.rois), P(d.roi_lvl), P(d.rows), n * Pn, 7, 7, 2, P(d.roi7)))
+        check(lib.rfi_model_forward_nhwc(self.box._h, P(d.roi7), DEVICE, n * Pn, 1, 1, P(d.box_out), DEVICE))
+        # ---- detections: per-class candidates, per-class NMS, the max_det best of an image
+        check(lib.rfi_op_detect_candidates(H, P(d.box_out), P(d.props), P(d.pcount), n, Pn, k1, float(h), float(w), float(self.score_thresh),
+                                           1e-2, P(d.cls_boxes), P(d.cls_scores), P(d.cls_counts)))
+        check(lib.rfi_op_nms_batched(H, P(d.cls_boxes), P(d.cls_counts), n * (k1 - 1), Pn, float(self.det_nms), P(d.cls_keep)))
+        check(lib.rfi_op_detect_select(H, P(d.cls_boxes), P(d.cls_scores), P(d.cls_keep), n, k1 - 1, Pn, D, t1, t2, t3, P(d.boxes),
+                                       P(d.scores), P(d.labels), P(d.counts), P(d.rois_m), P(d.lvl_m)))
+        # ---- mask branch on max_det rows per image, pasted into the image plane with the union in the same pass
+        check(lib.rfi_op_roi_align_ml(H, d.pf4, n, h0, w0, F, 0.25, P(d.rois_m), P(d.lvl_m), C.c_void_p(d.rows.ptr + 4), n * D, 14, 14, 2,
+                                      P(d.roi14)))
+        check(lib.rfi_model_forward_nhwc(self.mask._h, P(d.roi14), DEVICE, n * D, 14, 14, P(d.mask_out), DEVICE))
+        check(lib.rfi_op_mask_paste(H, P(d.mask_out), P(d.boxes), P(d.counts), n, D, h, w, P(d.rfi_mask),
+                                    P(d.masks) if instance_masks else None))
+        if out == "device":
+            res = {"boxes": d.boxes, "scores": d.scores, "labels": d.labels, "counts": d.counts, "rfi_mask": d.rfi_mask}
+            if instance_masks:
+                res["masks"] = d.masks
+            return res
+        # ---- down: the detections and the masks
+        cnt, boxes, scores, labels = d.counts.numpy(), d.boxes.numpy(), d.scores.numpy(), d.labels.numpy()
+        rfi = d.rfi_mask.numpy().astype(bool)
+        masks = d.masks.numpy() if instance_masks else None
+        res = []
+        for i in range(n):
+            k = int(cnt[i])
+            o = {"boxes": boxes[i, :k].copy(), "scores": scores[i, :k].copy(), "labels": labels[i, :k].astype(np.int64)}
+            if instance_masks:
+                o["masks"] = masks[i, :k].astype(bool)
+            o["rfi_mask"] = rfi[i]
+            res.append(o)
+        return res
 
     # ---- one optimisation step: everything between the input batch and the loss scalars happens in HBM
     def _buffers(self, n, h, w, gmax):

@@ -3,7 +3,9 @@
 well ``predict`` recovers them: best box IoU per ground-truth region and the IoU of the union mask.  A functional
 demonstration (the pieces are parity-tested one by one), not a benchmark.
 
-    python tools/demo_mask_rcnn.py [--steps 200] [--dtype float32|bfloat16]"""
+    python tools/demo_mask_rcnn.py [--steps 200] [--dtype float32|bfloat16] [--detect]
+
+``--detect`` runs ``MaskRCNN.detect`` (inference on the device) too and prints whether both forms agree."""
 import argparse
 import os
 import sys
@@ -40,6 +42,7 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--dtype", default="float32")
     ap.add_argument("--images", type=int, default=4)
+    ap.add_argument("--detect", action="store_true", help="run MaskRCNN.detect too and compare it with predict")
     a = ap.parse_args()
     import torch
     from rfi_toolbox_amd.models import MaskRCNN
@@ -59,6 +62,17 @@ def main():
         gm = t["masks"].any(0)
         mi = (gm & o["rfi_mask"]).sum() / max((gm | o["rfi_mask"]).sum(), 1)
         print(f"image {i}: {len(o['boxes'])} detections, best box IoU per region {[round(float(b), 3) for b in best]}, union-mask IoU {mi:.3f}")
+    if a.detect:
+        dev = det.detect(x)
+        same = all(len(d["boxes"]) == len(o["boxes"]) and np.array_equal(d["labels"], o["labels"]) for d, o in zip(dev, out))
+        if same:
+            db = max((float(np.abs(d["boxes"] - o["boxes"]).max()) for d, o in zip(dev, out) if len(o["boxes"])), default=0.0)
+            ds = max((float(np.abs(d["scores"] - o["scores"]).max()) for d, o in zip(dev, out) if len(o["boxes"])), default=0.0)
+            px = sum(int((d["rfi_mask"] != o["rfi_mask"]).sum()) for d, o in zip(dev, out))
+            print(f"detect agrees with predict: same detections and labels, max |d box| {db:.2e} px, max |d score| {ds:.2e}, "
+                  f"{px} union-mask pixels differ")
+        else:
+            print("detect DISAGREES with predict:", [(len(d["boxes"]), len(o["boxes"])) for d, o in zip(dev, out)])
 
 
 if __name__ == "__main__":
