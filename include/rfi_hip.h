@@ -518,6 +518,37 @@ int rfi_norm_statistics(rfi_ctx* ctx, const void* const* chunks, const int64_t* 
 int rfi_norm_apply(rfi_ctx* ctx, const void* src_dev, int dtype, int src_layout, int n, int64_t pixels, double centre,
                    double scale, const double* params_dev, float* dst_dev, int dst_layout);
 
+/* ---- training augmentation (scripts/train_model.py:44-53,70-75, --augment): HorizontalFlip, VerticalFlip, Rotate and
+ *      ShiftScaleRotate of a batch and its masks, as flips and ONE resampling through the composed affine transform.
+ *      Distribution-level parity: the reference resamples once per transform with its library's own random stream.
+ *
+ *      x (n, h, w, c) float32 NHWC, 1 <= c <= 16; y (n, h, w) bytes; the outputs have the same shapes in separate
+ *      buffers (a gather is never in place).  Sample i of call number `call` draws u[0..11] from three Philox4x32-10
+ *      blocks k = 0, 1, 2 with counter (i, call_lo, call_hi, k) and key (seed_lo, seed_hi), the words in order,
+ *      u = (word + 0.5) 2^-32 in fp64.  Gates: hflip u0 < p_hflip, vflip u1 < p_vflip, rotate u2 < p_rotate,
+ *      shift-scale-rotate u3 < p_ssr.  theta1 = (2 u4 - 1) rotate_limit_deg, theta2 = (2 u5 - 1) ssr_rotate_limit_deg,
+ *      s = 1 + (2 u6 - 1) scale_limit, dx = (2 u7 - 1) shift_limit w, dy = (2 u8 - 1) shift_limit h.  About the centre
+ *      c = ((w - 1) / 2, (h - 1) / 2) the forward map of pixel coordinates is M = SSR R(theta1) Fv Fh,
+ *      SSR = [s cos -s sin dx; s sin s cos dy], gated-off factors the identity; output pixel (xo, yo) reads the source
+ *      position M^-1 ((xo, yo) - c) + c, all in fp64.  Image: bilinear over floor and floor + 1, each index reflected
+ *      on its own (reflect-101: period 2 (N - 1), the edge pixel not repeated), weights and sum in fp64, one rounding
+ *      to float32.  Mask: the byte at (floor(sx + 0.5), floor(sy + 0.5)), reflected the same way.  A sample with the
+ *      rotate and ssr gates both off is a copy with the flips applied, bit for bit (non-finite values included).
+ *      No atomics: the output is a function of the arguments alone.
+ *
+ *      rfi_augment_params (host only, no context): gates[n][4] = (hflip, vflip, rotate, ssr) and inv[n][6] = the
+ *      row-major 2 x 3 map from an output pixel to its source position, from the same function the kernel evaluates.
+ *      rfi_augment_batch: x, y host or device (x_mem, y_mem), x_out, y_out device; one launch on the context's stream,
+ *      no synchronisation when the inputs are device-resident.  Probabilities in [0, 1], limits >= 0, scale_limit < 1,
+ *      h w <= 2^30; with c % 4 == 0 the float buffers must be 16-byte aligned.  n == 0 is a no-op. ---- */
+typedef struct rfi_augment_config {
+    uint64_t seed;
+    float p_hflip, p_vflip, p_rotate, rotate_limit_deg, p_ssr, shift_limit, scale_limit, ssr_rotate_limit_deg;
+} rfi_augment_config;
+int rfi_augment_params(const rfi_augment_config* cfg, uint64_t call, int n, int h, int w, int32_t* gates, double* inv);
+int rfi_augment_batch(rfi_ctx* ctx, const float* x, int x_mem, const uint8_t* y, int y_mem, int n, int h, int w, int c,
+                      const rfi_augment_config* cfg, uint64_t call, float* x_out, uint8_t* y_out);
+
 /* ---- kernel-level entry points (device pointers only).  Used by the parity tests to
  *      check each HIP kernel against the oracle in isolation.  impl: 0 auto, 1 direct VALU,
  *      2 MFMA implicit GEMM in native float32 (v_mfma_f32_32x32x2_f32), 3 MFMA implicit GEMM with bfloat16

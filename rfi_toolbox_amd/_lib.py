@@ -36,6 +36,12 @@ class NormStats(C.Structure):
                 ("mean", C.c_double), ("var", C.c_double), ("q", C.c_double * 2 * 3)]
 
 
+class AugmentConfig(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("p_hflip", C.c_float), ("p_vflip", C.c_float), ("p_rotate", C.c_float),
+                ("rotate_limit_deg", C.c_float), ("p_ssr", C.c_float), ("shift_limit", C.c_float),
+                ("scale_limit", C.c_float), ("ssr_rotate_limit_deg", C.c_float)]
+
+
 class SimParams(C.Structure):
     _fields_ = [("time_bins", C.c_int32), ("freq_bins", C.c_int32), ("n_power", C.c_int32), ("gibbs_ringing", C.c_int32),
                 ("clean", C.c_int32), ("fixed_baseline", C.c_int32), ("baseline_frac", C.c_double),
@@ -192,6 +198,8 @@ _PROTOS = {
     "rfi_norm_bracket": (_i, [_i64, C.c_double, _pi64, _pd]),
     "rfi_norm_statistics": (_i, [_vp, _pvp, _pi64, _i, _i, _i64, _i, C.POINTER(NormStats), _i]),
     "rfi_norm_apply": (_i, [_vp, _vp, _i, _i, _i, _i64, C.c_double, C.c_double, _vp, _vp, _i]),
+    "rfi_augment_params": (_i, [C.POINTER(AugmentConfig), C.c_uint64, _i, _i, _i, C.POINTER(C.c_int32), _pd]),
+    "rfi_augment_batch": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, C.POINTER(AugmentConfig), C.c_uint64, _vp, _vp]),
     "rfi_op_conv3x3": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     "rfi_op_conv1x1": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     "rfi_op_conv_s2": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),

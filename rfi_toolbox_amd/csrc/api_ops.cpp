@@ -657,6 +657,49 @@ int rfi_readback_end(rfi_ctx* ctx, void* dst_host, size_t bytes) {
         ctx->readback_bytes = 0;
     });
 }
+// ---- training augmentation (augment.hip)
+static void check_augment_config(const rfi_augment_config* cfg, int n, int h, int w) {
+    RFI_REQUIRE(cfg, "augment: null config");
+    for (float p : {cfg->p_hflip, cfg->p_vflip, cfg->p_rotate, cfg->p_ssr})
+        RFI_REQUIRE(p >= 0.0f && p <= 1.0f, "augment: probabilities must be in [0, 1]");
+    for (float l : {cfg->rotate_limit_deg, cfg->shift_limit, cfg->scale_limit, cfg->ssr_rotate_limit_deg})
+        RFI_REQUIRE(l >= 0.0f && l <= 3.0e38f, "augment: limits must be finite and >= 0");
+    RFI_REQUIRE(cfg->scale_limit < 1.0f, "augment: scale_limit must be < 1");
+    RFI_REQUIRE(n >= 0 && h >= 1 && w >= 1 && (int64_t)h * w <= (int64_t(1) << 30), "augment: needs n >= 0, h, w >= 1 and h w <= 2^30");
+}
+int rfi_augment_params(const rfi_augment_config* cfg, uint64_t call, int n, int h, int w, int32_t* gates, double* inv) {
+    return guarded([&] {
+        check_augment_config(cfg, n, h, w);
+        if (n == 0) return;
+        RFI_REQUIRE(gates && inv, "augment_params: null output");
+        augment_params_host(*cfg, call, n, h, w, gates, inv);
+    });
+}
+int rfi_augment_batch(rfi_ctx* ctx, const float* x, int x_mem, const uint8_t* y, int y_mem, int n, int h, int w, int c,
+                      const rfi_augment_config* cfg, uint64_t call, float* x_out, uint8_t* y_out) {
+    return guarded([&] {
+        RFI_REQUIRE(ctx, "augment_batch: null context");
+        check_augment_config(cfg, n, h, w);
+        RFI_REQUIRE(c >= 1 && c <= 16, "augment_batch: 1 <= c <= 16");
+        if (n == 0) return;
+        const int64_t px = (int64_t)n * h * w;
+        RFI_REQUIRE(cdiv((int64_t)h * w, 256) * n <= 0x7fffffff, "augment_batch: batch too large for one launch");
+        RFI_REQUIRE(x && y && x_out && y_out, "augment_batch: null buffer");
+        const char *xi = reinterpret_cast<const char*>(x), *xo = reinterpret_cast<const char*>(x_out);
+        const char *yi = reinterpret_cast<const char*>(y), *yo = reinterpret_cast<const char*>(y_out);
+        RFI_REQUIRE(x_mem == RFI_HOST || xi + px * c * 4 <= xo || xo + px * c * 4 <= xi, "augment_batch: x and x_out overlap");
+        RFI_REQUIRE(y_mem == RFI_HOST || yi + px <= yo || yo + px <= yi, "augment_batch: y and y_out overlap");
+        ctx->activate();
+        CallScope sc(ctx);
+        const float* dx = sc.in(x, x_mem, (size_t)px * c);
+        const uint8_t* dy = sc.in(y, y_mem, (size_t)px);
+        const uintptr_t al = c % 4 == 0 ? 16 : 4;
+        RFI_REQUIRE(reinterpret_cast<uintptr_t>(dx) % al == 0 && reinterpret_cast<uintptr_t>(x_out) % al == 0,
+                    "augment_batch: float buffers must be 4-byte aligned (16-byte when c % 4 == 0)");
+        launch_augment(ctx, dx, dy, n, h, w, c, *cfg, call, x_out, y_out);
+        sc.finish();
+    });
+}
 int rfi_op_fpn_merge(rfi_ctx* ctx, const float* lateral, const float* top, int n, int h, int w, int c, float* out) {
     return guarded([&] {
         ctx->activate();

@@ -345,6 +345,12 @@ void launch_norm_stats(rfi_ctx* ctx, const norm_chunk* chunks_dev, int n_chunks,
 // src_nhwc, (n, px, 8); dst (n, 8, px) or (n, px, 8)
 void launch_norm_apply(rfi_ctx* ctx, const void* src, int dtype, bool src_nhwc, int n, int64_t px, double centre, double scale,
                        const double* params_dev, float* dst, bool dst_nhwc);
+// training augmentation (augment.hip): flips and one composed affine warp of x [n][h][w][c] float32 and y [n][h][w] bytes
+// into x_out / y_out (never in place); the transform of sample i is drawn in the kernel from (cfg, call, i).
+// augment_params_host evaluates the same draw on the host: gates [n][4], inv [n][6].  Semantics in include/rfi_hip.h.
+void augment_params_host(const rfi_augment_config& cfg, uint64_t call, int n, int h, int w, int32_t* gates, double* inv);
+void launch_augment(rfi_ctx* ctx, const float* x, const uint8_t* y, int n, int h, int w, int c, const rfi_augment_config& cfg,
+                    uint64_t call, float* x_out, uint8_t* y_out);
 // RFISimulator waterfalls (rfi_sim.hip): draws the event table into `events` (unless p.clean), then one gather per
 // pixel into `out` (layout RFI_SIM_*) and `mask`; sizes are checked by rfi_simulate_rfi
 void launch_rfi_sim(rfi_ctx* ctx, unsigned long long seed, unsigned first_sample, int n_samples,

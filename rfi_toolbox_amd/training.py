@@ -9,17 +9,24 @@
 * ``evaluate_rfi_model`` -- scripts/evaluate_model.py:18-58: eval mode, per batch
   ``sigmoid > 0.5`` -> ``evaluate_segmentation``, then the MEAN OF THE PER-BATCH metrics
   (:54-56; not the metric of the pooled counts).
+* ``Augmenter`` -- train_model.py:44-53,70-75 (``--augment``): HorizontalFlip, VerticalFlip, Rotate(15) and
+  ShiftScaleRotate(0.05, 0.05, 10), each with p = 0.5, of a batch and its masks on the device
+  (``rfi_augment_batch``).  Distribution-level parity: the same family of transforms with this project's own
+  Philox stream, the data resampled ONCE through the composed transform (the reference interpolates per transform).
 Data are TorchDataset-like (``.images`` NHWC float32, ``.labels`` uint8) or (images, labels) pairs.
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 import os
 
 import numpy as np
 import torch
 
+from ._lib import AugmentConfig, check, lib
 from .evaluation.metrics import _dice, _f1, _iou, _precision, _recall
+from .runtime import Context, as_pointer, is_torch
 
 
 def _pair(ds):
@@ -70,9 +77,91 @@ def load_checkpoint(path, model, load_optimizer=True):
     return ck
 
 
+class Augmenter:
+    """The reference's training augmentation on the device.  ``aug(images, labels, call)`` warps a batch (n, H, W, C)
+    float32 and its masks (n, H, W) uint8 into two new ``DeviceArray``s; sample i of call number ``call`` draws its
+    transform from (seed, call, i) alone (semantics: include/rfi_hip.h), so equal arguments give equal bits."""
+
+    _PROBS = ("p_hflip", "p_vflip", "p_rotate", "p_ssr")
+    _LIMITS = ("rotate_limit", "shift_limit", "scale_limit", "ssr_rotate_limit")
+
+    def __init__(self, seed=0, p_hflip=0.5, p_vflip=0.5, p_rotate=0.5, rotate_limit=15, p_ssr=0.5, shift_limit=0.05,
+                 scale_limit=0.05, ssr_rotate_limit=10, device=None):
+        if not isinstance(seed, (int, np.integer)) or isinstance(seed, bool) or not 0 <= seed < 2 ** 64:
+            raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
+        self.seed = int(seed)
+        given = dict(p_hflip=p_hflip, p_vflip=p_vflip, p_rotate=p_rotate, rotate_limit=rotate_limit, p_ssr=p_ssr,
+                     shift_limit=shift_limit, scale_limit=scale_limit, ssr_rotate_limit=ssr_rotate_limit)
+        for k, v in given.items():
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
+                raise ValueError(f"{k} must be a finite number, got {v!r}")
+            if k in self._PROBS and not 0.0 <= v <= 1.0:
+                raise ValueError(f"{k} must be in [0, 1], got {v!r}")
+            if k in self._LIMITS and v < 0:
+                raise ValueError(f"{k} must be >= 0, got {v!r}")
+            setattr(self, k, float(v))
+        if np.float32(self.scale_limit) >= 1:
+            raise ValueError(f"scale_limit must be < 1, got {scale_limit!r}")
+        self.device = device
+
+    def _config(self):
+        return AugmentConfig(self.seed, self.p_hflip, self.p_vflip, self.p_rotate, self.rotate_limit, self.p_ssr,
+                             self.shift_limit, self.scale_limit, self.ssr_rotate_limit)
+
+    @staticmethod
+    def _call(call):
+        if not isinstance(call, (int, np.integer)) or isinstance(call, bool) or not 0 <= call < 2 ** 64:
+            raise ValueError(f"call must be an integer in [0, 2^64), got {call!r}")
+        return int(call)
+
+    def params(self, n, h, w, call=0):
+        """(gates (n, 4) int32 = hflip, vflip, rotate, ssr; inv (n, 6) float64 = the row-major 2 x 3 map from an output
+        pixel to its source position) of the samples of call ``call``: the host evaluation of what the kernel draws."""
+        call = self._call(call)
+        if n < 0 or h < 1 or w < 1:
+            raise ValueError(f"needs n >= 0 and h, w >= 1, got {(n, h, w)}")
+        gates, inv = np.zeros((n, 4), np.int32), np.zeros((n, 6), np.float64)
+        cfg = self._config()
+        check(lib.rfi_augment_params(C.byref(cfg), call, n, h, w, gates.ctypes.data_as(C.POINTER(C.c_int32)),
+                                     inv.ctypes.data_as(C.POINTER(C.c_double))))
+        return gates, inv
+
+    def __call__(self, images, labels, call=0):
+        call = self._call(call)
+        shape, lshape = tuple(images.shape), tuple(labels.shape)
+        if len(shape) != 4 or not 1 <= shape[3] <= 16 or shape[1] < 1 or shape[2] < 1:
+            raise ValueError(f"images must be (n, H, W, C) with 1 <= C <= 16, got shape {shape}")
+        if lshape != shape[:3]:
+            raise ValueError(f"labels shape {lshape} does not match images {shape}")
+        n, h, w, c = shape
+        ctx = Context.get(self.device)
+        xp, xm, k1 = as_pointer(images, np.float32, ctx)
+        yp, ym, k2 = as_pointer(labels, np.uint8, ctx)
+        x_out, y_out = ctx.empty(shape, np.float32), ctx.empty(lshape, np.uint8)
+        cfg = self._config()
+        check(lib.rfi_augment_batch(ctx.handle, C.c_void_p(xp), xm, C.c_void_p(yp), ym, n, h, w, c, C.byref(cfg), call,
+                                    C.c_void_p(x_out.ptr), C.c_void_p(y_out.ptr)))
+        if any(is_torch(v) and v.is_cuda for v in (images, labels)):
+            ctx.synchronize()                 # before torch's allocator may hand the (possibly temporary) tensors out again
+        del k1, k2
+        return x_out, y_out
+
+    def state_dict(self):
+        """plain numbers (for a checkpoint's ``args``)"""
+        return {"seed": self.seed, **{k: getattr(self, k) for k in self._PROBS + self._LIMITS}}
+
+    @classmethod
+    def from_state_dict(cls, state, device=None):
+        return cls(device=device, **state)
+
+
 def train_rfi_model(model, train_data, val_data=None, num_epochs=50, batch_size=4, lr=1e-4,
-                    weight_decay=1e-5, checkpoint_dir=None, resume_from=None, args=None, log=print):
-    """Returns the history [{epoch, train_loss, val_loss}].  Defaults = train_model.py:86-95."""
+                    weight_decay=1e-5, checkpoint_dir=None, resume_from=None, args=None, log=print,
+                    augment=False, augment_seed=0):
+    """Returns the history [{epoch, train_loss, val_loss}].  Defaults = train_model.py:86-95.  augment=True
+    (train_model.py --augment): training batch b of epoch e (both 0-based, e counted from 0 also when resuming) goes
+    through ``Augmenter(seed=augment_seed)(x, y, call=(e << 32) | b)`` on the device; validation data never does."""
+    aug = Augmenter(seed=augment_seed, device=getattr(getattr(model, "ctx", None), "device_index", None)) if augment else None
     tr_x, tr_y = _pair(train_data)
     start_epoch = 0
     if resume_from:
@@ -82,7 +171,11 @@ def train_rfi_model(model, train_data, val_data=None, num_epochs=50, batch_size=
     for epoch in range(start_epoch, num_epochs):
         model.train()
         order = torch.randperm(len(tr_x)).numpy()            # DataLoader(shuffle=True), train_model.py:106
-        losses = [model.train_step(tr_x[sel], tr_y[sel], **hyper) for sel in _batches(len(tr_x), batch_size, order)]
+        if aug is None:
+            losses = [model.train_step(tr_x[sel], tr_y[sel], **hyper) for sel in _batches(len(tr_x), batch_size, order)]
+        else:
+            losses = [model.train_step(*aug(tr_x[sel], tr_y[sel], call=(epoch << 32) | b), **hyper)
+                      for b, sel in enumerate(_batches(len(tr_x), batch_size, order))]
         rec = {"epoch": epoch + 1, "train_loss": float(np.mean(losses)), "val_loss": None}
         if val_data is not None:
             va_x, va_y = _pair(val_data)
