@@ -549,6 +549,72 @@ int rfi_augment_params(const rfi_augment_config* cfg, uint64_t call, int n, int 
 int rfi_augment_batch(rfi_ctx* ctx, const float* x, int x_mem, const uint8_t* y, int y_mem, int n, int h, int w, int c,
                       const rfi_augment_config* cfg, uint64_t call, float* x_out, uint8_t* y_out);
 
+/* ---- statistical baseline flagger: SumThreshold with a masked smooth background fit and the scale-invariant-rank (SIR)
+ *      operator (Offringa et al. 2010, MNRAS 405, 155; Offringa, van de Gronde & Roerdink 2012, A&A 539, A95).  The reference
+ *      takes its statistical flaggers from CASA and has no code for this: the semantics below are this project's own, and
+ *      tests/sumthreshold_ref.py restates them in NumPy; the library equals it bit for bit (it is built with
+ *      -ffp-contract=off, so the operations below are the operations executed).
+ *
+ *      Planes are (n_planes, C, T) with time contiguous; axis 1 = time, 0 = frequency.  Flags are bytes, non-zero == flagged.
+ *
+ *      Per plane: X float32 = |z| for complex input (the rule of rfi_flag_statistics, in the input's precision, then rounded
+ *      to float32), float64 input rounded to float32.  F = prior | ~isfinite(X); non-finite X are then 0.  B = 0 (float32).
+ *      For it = 0 .. iterations - 1:
+ *        1  R = X - B in float32.
+ *        2  med, mad = NumPy's float32 median of the unflagged R and float32 median of |R - med| (what rfi_flag_statistics
+ *           returns with RFI_FS_CLEAN | RFI_FS_MEDIANS).  No unflagged sample, or mad == 0: the plane is finished and goes to
+ *           SIR.
+ *        3  sigma = 1.4826 * (double) mad.
+ *        4  ladder, in double: s = base_sensitivity * 2^(iterations - 1 - it) (repeated doubling); p_0 = 1, p_k = p_{k-1} * rho;
+ *           chi_k = ((s * chi_1) * sigma) / p_k, k = 0 .. levels - 1.
+ *        5  for each k, M = 2^k: F = pass(R, med, F, M, chi_k, time), then F = pass(R, med, F, M, chi_k, frequency).
+ *        6  if it < iterations - 1: B = smooth(X, F).
+ *      pass (snapshot semantics: reads F_in, writes F_out; skipped when M exceeds the line length): level 0 is
+ *        d_i = unflagged_i ? (double) R_i - (double) med : 0.0, n_i = unflagged_i; level j is d_j(i) = d_{j-1}(i) +
+ *        d_{j-1}(i + 2^(j-1)), likewise n (a balanced tree).  Window i, wholly inside the line, hits iff n >= 1 and
+ *        fabs(d) > (double) n * chi.  F_out = F_in | the M samples of every hitting window.
+ *      smooth: u = 1.0 for unflagged samples, else 0.0; x = u * (double) X.  N1(c, t) = sum over d = -Ht .. Ht ascending of
+ *        w_t[d + Ht] * x(c, t + d), taps outside the plane skipped, each product rounded, then added, from 0.0 in double;
+ *        D1 the same over u.  The same along frequency on N1 and D1 with w_f gives N2, D2.  B = D2 > 0 ? (float)(N2 / D2) : 0.
+ *        The weight tables cross this interface as data: no exponential is evaluated in the library.
+ *      SIR, after the last iteration, along time and then along frequency on the result: q = floor(eta * 1024 + 0.5) is formed
+ *        by the caller; q == 0 skips it.  Sample k of a line ends flagged iff some a <= k <= b has
+ *        1024 * #flagged[a..b] >= (1024 - q) * (b - a + 1): with P the int32 prefix sums of (flagged ? q : q - 1024), iff
+ *        max_{j > k} P_j >= min_{j <= k} P_j.
+ *      No float atomics; every output is a function of the arguments alone.
+ *
+ *      rfi_sumthreshold_ladder (host only, no context): chi_out[levels] of `iteration` for a given sigma, by the inline
+ *        function the device evaluates.
+ *      rfi_sumthreshold_pass: values float32, flags_in / flags_out bytes, host or device; window a power of two in 1 .. 128;
+ *        threshold_host / center_host: one double per plane.  A window longer than the line copies the flags.
+ *      rfi_masked_smooth: values float32, flags bytes -> out float32; weights_*_host: 2 half + 1 doubles each.
+ *      rfi_sir_operator: 0 <= q <= 1023.
+ *      rfi_sumthreshold_flag: data of dtype RFI_C128 / C64 / F64 / F32, prior flags optional (NULL).  Planes are processed in
+ *        chunks whose workspace (26 bytes per sample, plus staging for host buffers) stays within the context's 1 GiB
+ *        grow-only scratch; a single plane too large for it is an error.  Between the upload and the download nothing is read
+ *        back: medians, MADs and thresholds stay in device memory.  With device-resident data, prior and flags_out the call
+ *        only enqueues work on the context's stream.
+ *      Sizes: 1 <= C, T <= 2^20; 1 <= iterations; 1 <= levels <= 8; rho > 1; half widths >= 0. ---- */
+typedef struct rfi_sumthreshold_config {
+    int32_t iterations, levels;
+    double base_sensitivity, chi_1, rho;
+    int32_t half_t, half_f;     /* half widths of the smoothing tables (time, frequency) */
+    int32_t sir_q;              /* floor(eta * 1024 + 0.5), 0 .. 1023 */
+    int32_t pad_;
+} rfi_sumthreshold_config;
+int rfi_sumthreshold_ladder(const rfi_sumthreshold_config* cfg, double sigma, int iteration, double* chi_out);
+int rfi_sumthreshold_pass(rfi_ctx* ctx, const float* values, int values_mem, const uint8_t* flags_in, int flags_mem, int n_planes,
+                          int c, int t, int window, int axis, const double* threshold_host, const double* center_host,
+                          uint8_t* flags_out, int out_mem);
+int rfi_masked_smooth(rfi_ctx* ctx, const float* values, int values_mem, const uint8_t* flags, int flags_mem, int n_planes, int c,
+                      int t, const double* weights_t_host, int half_t, const double* weights_f_host, int half_f, float* out,
+                      int out_mem);
+int rfi_sir_operator(rfi_ctx* ctx, const uint8_t* flags_in, int flags_mem, int n_planes, int c, int t, int axis, int q,
+                     uint8_t* flags_out, int out_mem);
+int rfi_sumthreshold_flag(rfi_ctx* ctx, const void* data, int data_mem, int dtype, const uint8_t* prior, int prior_mem, int n_planes,
+                          int c, int t, const rfi_sumthreshold_config* cfg, const double* weights_t_host,
+                          const double* weights_f_host, uint8_t* flags_out, int out_mem);
+
 /* ---- kernel-level entry points (device pointers only).  Used by the parity tests to
  *      check each HIP kernel against the oracle in isolation.  impl: 0 auto, 1 direct VALU,
  *      2 MFMA implicit GEMM in native float32 (v_mfma_f32_32x32x2_f32), 3 MFMA implicit GEMM with bfloat16

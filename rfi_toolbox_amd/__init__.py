@@ -12,6 +12,6 @@ __version__ = "0.1.0"
 def __getattr__(name):
     import importlib
     if name in ("models", "evaluation", "preprocessing", "datasets", "training", "distributed", "runtime",
-                "data_generation", "core", "inference"):
+                "data_generation", "core", "inference", "flagging"):
         return importlib.import_module(f"{__name__}.{name}")
     raise AttributeError(name)

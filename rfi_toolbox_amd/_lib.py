@@ -42,6 +42,11 @@ class AugmentConfig(C.Structure):
                 ("scale_limit", C.c_float), ("ssr_rotate_limit_deg", C.c_float)]
 
 
+class SumThresholdConfig(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("levels", C.c_int32), ("base_sensitivity", C.c_double), ("chi_1", C.c_double),
+                ("rho", C.c_double), ("half_t", C.c_int32), ("half_f", C.c_int32), ("sir_q", C.c_int32), ("pad_", C.c_int32)]
+
+
 class SimParams(C.Structure):
     _fields_ = [("time_bins", C.c_int32), ("freq_bins", C.c_int32), ("n_power", C.c_int32), ("gibbs_ringing", C.c_int32),
                 ("clean", C.c_int32), ("fixed_baseline", C.c_int32), ("baseline_frac", C.c_double),
@@ -200,6 +205,11 @@ _PROTOS = {
     "rfi_norm_apply": (_i, [_vp, _vp, _i, _i, _i, _i64, C.c_double, C.c_double, _vp, _vp, _i]),
     "rfi_augment_params": (_i, [C.POINTER(AugmentConfig), C.c_uint64, _i, _i, _i, C.POINTER(C.c_int32), _pd]),
     "rfi_augment_batch": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, C.POINTER(AugmentConfig), C.c_uint64, _vp, _vp]),
+    "rfi_sumthreshold_ladder": (_i, [C.POINTER(SumThresholdConfig), C.c_double, _i, _pd]),
+    "rfi_sumthreshold_pass": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _pd, _pd, _vp, _i]),
+    "rfi_masked_smooth": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _pd, _i, _pd, _i, _vp, _i]),
+    "rfi_sir_operator": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i]),
+    "rfi_sumthreshold_flag": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _i, C.POINTER(SumThresholdConfig), _pd, _pd, _vp, _i]),
     "rfi_op_conv3x3": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     "rfi_op_conv1x1": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     "rfi_op_conv_s2": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),

@@ -700,6 +700,181 @@ int rfi_augment_batch(rfi_ctx* ctx, const float* x, int x_mem, const uint8_t* y,
         sc.finish();
     });
 }
+// ---- statistical baseline flagger (sumthreshold.hip)
+namespace {
+constexpr size_t kFlagBudget = size_t(1) << 30;      // workspace of one chunk of rfi_sumthreshold_flag
+
+void check_st_planes(const char* who, int n_planes, int c, int t) {
+    RFI_REQUIRE(n_planes >= 0 && c >= 1 && t >= 1 && c <= (1 << 20) && t <= (1 << 20),
+                std::string(who) + ": needs n_planes >= 0 and 1 <= C, T <= 2^20");
+    RFI_REQUIRE((double)n_planes * c * t <= 4.0e9, std::string(who) + ": stack too large for one call");
+}
+void check_st_config(const rfi_sumthreshold_config* cfg) {
+    RFI_REQUIRE(cfg, "sumthreshold: null config");
+    RFI_REQUIRE(cfg->iterations >= 1 && cfg->iterations <= 64, "sumthreshold: iterations must be in 1 .. 64");
+    RFI_REQUIRE(cfg->levels >= 1 && cfg->levels <= 8, "sumthreshold: levels must be in 1 .. 8");
+    RFI_REQUIRE(cfg->rho > 1.0 && cfg->rho <= 1.0e6, "sumthreshold: rho must be > 1");
+    RFI_REQUIRE(cfg->base_sensitivity > 0.0 && cfg->chi_1 > 0.0, "sumthreshold: base_sensitivity and chi_1 must be > 0");
+    RFI_REQUIRE(cfg->half_t >= 0 && cfg->half_f >= 0 && cfg->half_t <= (1 << 20) && cfg->half_f <= (1 << 20),
+                "sumthreshold: half widths must be in 0 .. 2^20");
+    RFI_REQUIRE(cfg->sir_q >= 0 && cfg->sir_q <= 1023, "sumthreshold: sir_q must be in 0 .. 1023");
+}
+bool mem_ok(int mem) { return mem == RFI_HOST || mem == RFI_DEVICE; }
+}  // namespace
+
+int rfi_sumthreshold_ladder(const rfi_sumthreshold_config* cfg, double sigma, int iteration, double* chi_out) {
+    return guarded([&] {
+        check_st_config(cfg);
+        RFI_REQUIRE(chi_out, "sumthreshold_ladder: null output");
+        RFI_REQUIRE(iteration >= 0 && iteration < cfg->iterations, "sumthreshold_ladder: iteration out of range");
+        sumthreshold_ladder_host(*cfg, sigma, iteration, chi_out);
+    });
+}
+int rfi_sumthreshold_pass(rfi_ctx* ctx, const float* values, int values_mem, const uint8_t* flags_in, int flags_mem, int n_planes,
+                          int c, int t, int window, int axis, const double* threshold_host, const double* center_host,
+                          uint8_t* flags_out, int out_mem) {
+    return guarded([&] {
+        RFI_REQUIRE(ctx, "sumthreshold_pass: null context");
+        check_st_planes("sumthreshold_pass", n_planes, c, t);
+        RFI_REQUIRE(window >= 1 && window <= st_max_window() && (window & (window - 1)) == 0,
+                    "sumthreshold_pass: window must be a power of two in 1 .. 128");
+        RFI_REQUIRE(axis == 0 || axis == 1, "sumthreshold_pass: axis must be 0 (frequency) or 1 (time)");
+        RFI_REQUIRE(mem_ok(values_mem) && mem_ok(flags_mem) && mem_ok(out_mem), "sumthreshold_pass: bad memory kind");
+        if (n_planes == 0) return;
+        RFI_REQUIRE(values && flags_in && flags_out && threshold_host && center_host, "sumthreshold_pass: null argument");
+        ctx->activate();
+        const size_t n = (size_t)n_planes * c * t;
+        CallScope sc(ctx);
+        const float* x = sc.in(values, values_mem, n);
+        const uint8_t* fi = sc.in(flags_in, flags_mem, n);
+        uint8_t* fo = sc.out(flags_out, out_mem, n);
+        RFI_REQUIRE(fi != fo, "sumthreshold_pass: flags_in and flags_out must be different buffers");
+        if (window > (axis == 1 ? t : c)) {
+            RFI_CHECK_HIP(hipMemcpyAsync(fo, fi, n, hipMemcpyDeviceToDevice, ctx->stream));
+        } else {
+            const double* th = sc.in(threshold_host, RFI_HOST, (size_t)n_planes);
+            const double* ce = sc.in(center_host, RFI_HOST, (size_t)n_planes);
+            launch_st_pass(ctx, x, nullptr, fi, fo, n_planes, c, t, window, axis, ce, th, 1, nullptr, 0);
+        }
+        sc.finish();
+    });
+}
+int rfi_masked_smooth(rfi_ctx* ctx, const float* values, int values_mem, const uint8_t* flags, int flags_mem, int n_planes, int c,
+                      int t, const double* weights_t_host, int half_t, const double* weights_f_host, int half_f, float* out,
+                      int out_mem) {
+    return guarded([&] {
+        RFI_REQUIRE(ctx, "masked_smooth: null context");
+        check_st_planes("masked_smooth", n_planes, c, t);
+        RFI_REQUIRE(half_t >= 0 && half_f >= 0 && half_t <= (1 << 20) && half_f <= (1 << 20), "masked_smooth: half widths must be in 0 .. 2^20");
+        RFI_REQUIRE(mem_ok(values_mem) && mem_ok(flags_mem) && mem_ok(out_mem), "masked_smooth: bad memory kind");
+        if (n_planes == 0) return;
+        RFI_REQUIRE(values && flags && out && weights_t_host && weights_f_host, "masked_smooth: null argument");
+        ctx->activate();
+        const size_t n = (size_t)n_planes * c * t;
+        CallScope sc(ctx);
+        const float* x = sc.in(values, values_mem, n);
+        const uint8_t* f = sc.in(flags, flags_mem, n);
+        float* b = sc.out(out, out_mem, n);
+        const double* wt = sc.in(weights_t_host, RFI_HOST, (size_t)2 * half_t + 1);
+        const double* wf = sc.in(weights_f_host, RFI_HOST, (size_t)2 * half_f + 1);
+        launch_st_smooth(ctx, x, f, n_planes, c, t, wt, half_t, wf, half_f, sc.temp<double>(2 * n), b);
+        sc.finish();
+    });
+}
+int rfi_sir_operator(rfi_ctx* ctx, const uint8_t* flags_in, int flags_mem, int n_planes, int c, int t, int axis, int q,
+                     uint8_t* flags_out, int out_mem) {
+    return guarded([&] {
+        RFI_REQUIRE(ctx, "sir_operator: null context");
+        check_st_planes("sir_operator", n_planes, c, t);
+        RFI_REQUIRE(axis == 0 || axis == 1, "sir_operator: axis must be 0 (frequency) or 1 (time)");
+        RFI_REQUIRE(q >= 0 && q <= 1023, "sir_operator: q must be in 0 .. 1023");
+        RFI_REQUIRE(mem_ok(flags_mem) && mem_ok(out_mem), "sir_operator: bad memory kind");
+        if (n_planes == 0) return;
+        RFI_REQUIRE(flags_in && flags_out, "sir_operator: null argument");
+        ctx->activate();
+        const size_t n = (size_t)n_planes * c * t;
+        CallScope sc(ctx);
+        const uint8_t* fi = sc.in(flags_in, flags_mem, n);
+        uint8_t* fo = sc.out(flags_out, out_mem, n);
+        if (q == 0) {
+            if (fi != fo) RFI_CHECK_HIP(hipMemcpyAsync(fo, fi, n, hipMemcpyDeviceToDevice, ctx->stream));
+        } else {
+            launch_st_sir(ctx, fi, fo, n_planes, c, t, axis, q, sc.temp<int>(n));
+        }
+        sc.finish();
+    });
+}
+// Chunks of k whole planes in the context's scratch: [weights | state | X | B | Fa | Fb | N1 D1 | staged data | staged prior].
+// Host data and prior are uploaded per chunk and the chunk's flags copied back, all on the context's stream; device
+// buffers are used in place.
+int rfi_sumthreshold_flag(rfi_ctx* ctx, const void* data, int data_mem, int dtype, const uint8_t* prior, int prior_mem, int n_planes,
+                          int c, int t, const rfi_sumthreshold_config* cfg, const double* weights_t_host,
+                          const double* weights_f_host, uint8_t* flags_out, int out_mem) {
+    return guarded([&] {
+        RFI_REQUIRE(ctx, "sumthreshold_flag: null context");
+        RFI_REQUIRE(dtype >= RFI_C128 && dtype <= RFI_F32, "sumthreshold_flag: dtype must be complex128, complex64, float64 or float32");
+        check_st_planes("sumthreshold_flag", n_planes, c, t);
+        check_st_config(cfg);
+        RFI_REQUIRE(mem_ok(data_mem) && (!prior || mem_ok(prior_mem)) && mem_ok(out_mem), "sumthreshold_flag: bad memory kind");
+        if (n_planes == 0) return;
+        RFI_REQUIRE(data && flags_out && weights_t_host && weights_f_host, "sumthreshold_flag: null argument");
+        ctx->activate();
+        const size_t esz = dtype == RFI_C128 ? 16 : (dtype == RFI_F32 ? 4 : 8);
+        const size_t px = (size_t)c * t;
+        const bool host_in = data_mem == RFI_HOST, host_pr = prior && prior_mem == RFI_HOST, host_out = out_mem == RFI_HOST;
+        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+        const size_t nwt = (size_t)2 * cfg->half_t + 1, nwf = (size_t)2 * cfg->half_f + 1;
+        const size_t b_w = al(nwt * 8) + al(nwf * 8);
+        const size_t per_plane = px * (26 + (host_in ? esz : 0) + (host_pr ? 1 : 0)) + st_state_bytes(1);
+        const size_t slack = 8 * 256;                                      // the alignment of the eight regions
+        RFI_REQUIRE(b_w + slack + per_plane <= kFlagBudget,
+                    "sumthreshold_flag: one " + std::to_string(c) + " x " + std::to_string(t) + " plane needs " +
+                        std::to_string(per_plane >> 20) + " MiB of workspace, over the budget of " +
+                        std::to_string(kFlagBudget >> 20) + " MiB; planes are not split");
+        const int k = (int)std::min<size_t>((size_t)n_planes, (kFlagBudget - b_w - slack) / per_plane);
+        const size_t kn = (size_t)k * px;
+        const size_t b_state = al(st_state_bytes(k)), b_x = al(kn * 4), b_f = al(kn), b_nd = al(kn * 16);
+        const size_t b_in = host_in ? al(kn * esz) : 0, b_pr = host_pr ? al(kn) : 0;
+        char* base = static_cast<char*>(ctx->get_scratch(b_w + b_state + 2 * b_x + 2 * b_f + b_nd + b_in + b_pr));
+        double* d_wt = reinterpret_cast<double*>(base);
+        double* d_wf = reinterpret_cast<double*>(base + al(nwt * 8));
+        char* p = base + b_w;
+        void* d_state = p; p += b_state;
+        float* d_x = reinterpret_cast<float*>(p); p += b_x;
+        float* d_b = reinterpret_cast<float*>(p); p += b_x;
+        uint8_t* d_fa = reinterpret_cast<uint8_t*>(p); p += b_f;
+        uint8_t* d_fb = reinterpret_cast<uint8_t*>(p); p += b_f;
+        double* d_nd = reinterpret_cast<double*>(p); p += b_nd;
+        char* d_in = p; p += b_in;
+        uint8_t* d_pr = reinterpret_cast<uint8_t*>(p);
+        RFI_CHECK_HIP(hipMemcpyAsync(d_wt, weights_t_host, nwt * 8, hipMemcpyHostToDevice, ctx->stream));
+        RFI_CHECK_HIP(hipMemcpyAsync(d_wf, weights_f_host, nwf * 8, hipMemcpyHostToDevice, ctx->stream));
+        struct Drain {            // a failure part way leaves no work in flight on buffers the caller owns
+            rfi_ctx* c; bool armed;
+            ~Drain() { if (armed) (void)hipStreamSynchronize(c->stream); }
+        } drain{ctx, true};
+        const char* src = static_cast<const char*>(data);
+        for (int p0 = 0; p0 < n_planes; p0 += k) {
+            const int np = std::min(k, n_planes - p0);
+            const size_t off = (size_t)p0 * px, cn = (size_t)np * px;
+            const void* in = src + off * esz;
+            const uint8_t* pr = prior ? prior + off : nullptr;
+            if (host_in) {
+                RFI_CHECK_HIP(hipMemcpyAsync(d_in, in, cn * esz, hipMemcpyHostToDevice, ctx->stream));
+                in = d_in;
+            }
+            if (host_pr) {
+                RFI_CHECK_HIP(hipMemcpyAsync(d_pr, pr, cn, hipMemcpyHostToDevice, ctx->stream));
+                pr = d_pr;
+            }
+            uint8_t* out = host_out ? d_fa : flags_out + off;
+            launch_sumthreshold_flag(ctx, in, dtype, pr, np, c, t, *cfg, d_wt, d_wf, d_x, d_b, d_fa, d_fb, d_nd, d_state, out);
+            if (host_out) RFI_CHECK_HIP(hipMemcpyAsync(flags_out + off, out, cn, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        if (host_in || host_pr || host_out) RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+        drain.armed = false;
+    });
+}
 int rfi_op_fpn_merge(rfi_ctx* ctx, const float* lateral, const float* top, int n, int h, int w, int c, float* out) {
     return guarded([&] {
         ctx->activate();

@@ -351,6 +351,26 @@ void launch_norm_apply(rfi_ctx* ctx, const void* src, int dtype, bool src_nhwc, 
 void augment_params_host(const rfi_augment_config& cfg, uint64_t call, int n, int h, int w, int32_t* gates, double* inv);
 void launch_augment(rfi_ctx* ctx, const float* x, const uint8_t* y, int n, int h, int w, int c, const rfi_augment_config& cfg,
                     uint64_t call, float* x_out, uint8_t* y_out);
+// SumThreshold baseline flagger (sumthreshold.hip; semantics in include/rfi_hip.h, "statistical baseline flagger").  Planes are
+// (planes, C, T), time contiguous; X / B float32, flags bytes; axis 1 = time, 0 = frequency.
+//   st_pass: F_out = F_in | hits of window M (a power of two, 1 .. st_max_window(), no longer than the line); center / chi: one
+//            device double per plane, `pstride` doubles apart; done (optional): one int per plane, `dstride` ints apart, non-zero
+//            = leave the plane alone; B (optional) is subtracted from X in float32 first
+//   st_smooth: wt / wf device tables of 2 h + 1 doubles; nd: workspace of 2 n doubles (n = planes C T)
+//   st_sir: q = 1 .. 1023; ws: n ints; F_in may equal F_out
+//   sumthreshold_flag: the whole pipeline; X, B n floats, Fa, Fb n bytes, nd 2 n doubles, state st_state_bytes(planes); the
+//            flags end in `out` (n bytes).  Nothing is read back.
+void sumthreshold_ladder_host(const rfi_sumthreshold_config& cfg, double sigma, int iteration, double* chi);
+size_t st_state_bytes(int planes);
+int st_max_window();
+void launch_st_pass(rfi_ctx* ctx, const float* X, const float* B, const uint8_t* Fin, uint8_t* Fout, int planes, int C, int T, int M,
+                    int axis, const double* center, const double* chi, int pstride, const int* done, int dstride);
+void launch_st_smooth(rfi_ctx* ctx, const float* X, const uint8_t* F, int planes, int C, int T, const double* wt, int ht,
+                      const double* wf, int hf, double* nd, float* B);
+void launch_st_sir(rfi_ctx* ctx, const uint8_t* Fin, uint8_t* Fout, int planes, int C, int T, int axis, int q, int* ws);
+void launch_sumthreshold_flag(rfi_ctx* ctx, const void* src, int dtype, const uint8_t* prior, int planes, int C, int T,
+                              const rfi_sumthreshold_config& cfg, const double* wt, const double* wf, float* X, float* B, uint8_t* Fa,
+                              uint8_t* Fb, double* nd, void* state, uint8_t* out);
 // RFISimulator waterfalls (rfi_sim.hip): draws the event table into `events` (unless p.clean), then one gather per
 // pixel into `out` (layout RFI_SIM_*) and `mask`; sizes are checked by rfi_simulate_rfi
 void launch_rfi_sim(rfi_ctx* ctx, unsigned long long seed, unsigned first_sample, int n_samples,

@@ -1,0 +1,304 @@
+"""A statistical baseline flagger on the GPU: SumThreshold with a masked smooth background fit and the
+scale-invariant-rank (SIR) operator -- the core of the strategy observatories run today (Offringa et al. 2010, MNRAS
+405, 155; Offringa, van de Gronde & Roerdink 2012, A&A 539, A95).  It is what a learned model is compared against:
+
+    flags = sumthreshold_flags(vis)                      # vis (B, P, C, T) complex -> bool flags of vis.shape
+
+The reference toolbox takes its statistical flaggers from CASA and has no code for this; the arithmetic is this
+project's own and is pinned, operation by operation, in include/rfi_hip.h ("statistical baseline flagger").  Per
+(C, T) plane: the magnitude as float32; then ``iterations`` rounds of [median and MAD of the residual over the
+unflagged samples -> a ladder of ``levels`` thresholds chi_k = s chi_1 sigma / rho^k for window lengths 2^k -> one
+SumThreshold pass along time and one along frequency per window length -> a new background from a masked Gaussian
+smooth of the unflagged data], the sensitivity s halving its factor every round down to ``base_sensitivity``; then the
+SIR operator with aggressiveness ``sir_eta`` along time and along frequency.  Everything between the upload and the
+download happens on the device (csrc/sumthreshold.hip); there is no CPU path.
+
+A Gaussian smooth cannot follow a bandpass that falls off steeply (the simulator's t^8 band edges): about a quarter of
+such a plane gets flagged.  Divide the bandpass out first, as an observatory pipeline does.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from ._lib import C64, C128, DEVICE, F32, F64, HOST, SumThresholdConfig, check, lib
+from .runtime import Context, DeviceArray, is_torch, torch
+
+_CODES = {np.dtype(np.complex128): C128, np.dtype(np.complex64): C64, np.dtype(np.float64): F64, np.dtype(np.float32): F32}
+MAX_AXIS = 1 << 20
+MAX_WINDOW = 128
+
+
+def gaussian_weights(sigma, half) -> np.ndarray:
+    """The weight table of one smoothing direction, 2 half + 1 float64 values (the one place it is computed)."""
+    sigma, half = float(sigma), int(half)
+    return np.exp(-np.arange(-half, half + 1)**2 / (2 * sigma * sigma))
+
+
+def sir_q(eta) -> int:
+    """The integer the SIR operator works with: floor(eta 1024 + 0.5)."""
+    return int(np.floor(np.float64(eta) * 1024.0 + 0.5))
+
+
+# ---------------------------------------------------------------------------------------------- argument plumbing
+def _np_dtype(x):
+    if isinstance(x, DeviceArray):
+        return x.dtype
+    if is_torch(x):
+        return {torch.complex128: np.complex128, torch.complex64: np.complex64, torch.float64: np.float64,
+                torch.float32: np.float32, torch.uint8: np.uint8, torch.bool: np.bool_}.get(x.dtype)
+    return np.asarray(x).dtype
+
+
+def _shape(x):
+    return tuple(int(s) for s in (x.shape if isinstance(x, DeviceArray) or is_torch(x) else np.asarray(x).shape))
+
+
+def _check_planes(name, x):
+    shape = _shape(x)
+    if len(shape) < 2:
+        raise ValueError(f"{name} must have shape (..., C, T) with ndim >= 2, got shape {shape}")
+    if not 1 <= shape[-2] <= MAX_AXIS or not 1 <= shape[-1] <= MAX_AXIS:
+        raise ValueError(f"{name}: C and T must be in 1 .. 2^20, got {shape[-2]} x {shape[-1]}")
+    return shape
+
+
+def _check_flags(flags, shape):
+    if _shape(flags) != shape:
+        raise ValueError(f"flags have shape {_shape(flags)}, the data {shape}")
+    dt = _np_dtype(flags)
+    if dt is None or np.dtype(dt) not in (np.dtype(np.bool_), np.dtype(np.uint8)):
+        raise ValueError(f"flags must be bool or uint8, got {dt}")
+
+
+def _pointer(x, dtype, ctx):
+    """-> (ptr, mem, keepalive) of x as contiguous `dtype` (bool is passed as its bytes)."""
+    dtype = np.dtype(dtype)
+    if isinstance(x, DeviceArray):
+        if x.ctx is not ctx:
+            raise ValueError("device array belongs to another context")
+        return x.ptr, DEVICE, x
+    if is_torch(x):
+        t = x.detach()
+        if t.dtype == torch.bool:
+            t = t.to(torch.uint8)
+        t = t.contiguous()
+        if t.is_cuda:
+            if t.device.index not in (None, ctx.device_index):
+                raise ValueError(f"tensor is on {t.device}, the context on GPU {ctx.device_index}")
+            torch.cuda.current_stream(t.device).synchronize()        # hand over to the context's stream
+            return t.data_ptr(), DEVICE, t
+        x = t.numpy()
+    a = np.ascontiguousarray(np.asarray(x))
+    if a.dtype == np.bool_:
+        a = a.view(np.uint8)
+    a = np.ascontiguousarray(a, dtype=dtype)
+    return a.ctypes.data, HOST, a
+
+
+def _on_device(*xs):
+    return any(isinstance(x, DeviceArray) or (is_torch(x) and x.is_cuda) for x in xs if x is not None)
+
+
+def _context(device, *xs):
+    for x in xs:
+        if isinstance(x, DeviceArray):
+            return x.ctx
+    for x in xs:
+        if is_torch(x) and x.is_cuda and device is None:
+            return Context.get(x.device.index or 0)
+    return Context.get(device)
+
+
+def _axis(axis, ndim):
+    if axis in (-1, ndim - 1):
+        return 1
+    if axis in (-2, ndim - 2):
+        return 0
+    raise ValueError(f"axis must name the time axis (-1) or the frequency axis (-2), got {axis!r}")
+
+
+def _real_values(name, values):
+    dt = _np_dtype(values)
+    if dt is None or np.dtype(dt) not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError(f"{name} must be float32 or float64, got {dt}")
+    if isinstance(values, DeviceArray) and values.dtype != np.float32:
+        raise ValueError(f"a device array of {name} must be float32")
+    if is_torch(values):
+        return values.to(torch.float32)
+    return values if isinstance(values, DeviceArray) else np.asarray(values, dtype=np.float32)
+
+
+def _doubles(a):
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    return a, a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+# ---------------------------------------------------------------------------------------------- the three stages
+def sumthreshold_pass(values, flags, window, threshold, center=0.0, axis=-1, device=None) -> np.ndarray:
+    """One SumThreshold pass: ``flags | (the samples of every window of `window` consecutive samples along `axis`
+    whose unflagged values v - center sum to more than threshold times their number in absolute value)``.
+
+    ``values`` (..., C, T) real, ``flags`` of the same shape; ``window`` a power of two up to 128 (a window longer than
+    the line changes nothing); ``threshold`` and ``center`` scalars or one value per plane.  Returns NumPy bool.
+    """
+    shape = _check_planes("values", values)
+    values = _real_values("values", values)
+    _check_flags(flags, shape)
+    if not isinstance(window, (int, np.integer)) or not 1 <= window <= MAX_WINDOW or window & (window - 1):
+        raise ValueError(f"window must be a power of two in 1 .. {MAX_WINDOW}, got {window!r}")
+    ax = _axis(axis, len(shape))
+    planes = int(np.prod(shape[:-2], dtype=np.int64))
+    try:
+        th = np.broadcast_to(np.asarray(threshold, np.float64).reshape(-1), (planes,))
+        ce = np.broadcast_to(np.asarray(center, np.float64).reshape(-1), (planes,))
+    except ValueError:
+        raise ValueError(f"threshold and center must be scalars or hold one value per plane ({planes})") from None
+    out = np.empty(shape, np.uint8)
+    if out.size:
+        ctx = _context(device, values, flags)
+        vp, vm, k1 = _pointer(values, np.float32, ctx)
+        fp, fm, k2 = _pointer(flags, np.uint8, ctx)
+        th, thp = _doubles(th)
+        ce, cep = _doubles(ce)
+        check(lib.rfi_sumthreshold_pass(ctx.handle, C.c_void_p(vp), vm, C.c_void_p(fp), fm, planes, shape[-2], shape[-1],
+                                        int(window), ax, thp, cep, C.c_void_p(out.ctypes.data), HOST))
+        del k1, k2
+    return out.view(bool)
+
+
+def masked_gaussian_smooth(values, flags, weights_t, weights_f, device=None) -> np.ndarray:
+    """The background fit: per sample the weighted mean of the unflagged samples around it, separable, time direction
+    first; 0 where no unflagged sample lies under the window.  ``weights_t`` / ``weights_f``: tables of odd length
+    (``gaussian_weights``).  Returns NumPy float32."""
+    shape = _check_planes("values", values)
+    values = _real_values("values", values)
+    _check_flags(flags, shape)
+    wt, wf = np.asarray(weights_t, np.float64), np.asarray(weights_f, np.float64)
+    for name, w in (("weights_t", wt), ("weights_f", wf)):
+        if w.ndim != 1 or w.size % 2 != 1:
+            raise ValueError(f"{name} must be a 1-d table of odd length, got shape {w.shape}")
+    planes = int(np.prod(shape[:-2], dtype=np.int64))
+    out = np.empty(shape, np.float32)
+    if out.size:
+        ctx = _context(device, values, flags)
+        vp, vm, k1 = _pointer(values, np.float32, ctx)
+        fp, fm, k2 = _pointer(flags, np.uint8, ctx)
+        wt, wtp = _doubles(wt)
+        wf, wfp = _doubles(wf)
+        check(lib.rfi_masked_smooth(ctx.handle, C.c_void_p(vp), vm, C.c_void_p(fp), fm, planes, shape[-2], shape[-1],
+                                    wtp, wt.size // 2, wfp, wf.size // 2, C.c_void_p(out.ctypes.data), HOST))
+        del k1, k2
+    return out
+
+
+def sir_operator(flags, eta, axis=-1, device=None) -> np.ndarray:
+    """The scale-invariant rank operator along one axis: a sample ends flagged when it lies in an interval of which
+    at least a share 1 - eta is flagged (eta rounded to a multiple of 1/1024).  Returns NumPy bool."""
+    shape = _check_planes("flags", flags)
+    _check_flags(flags, shape)
+    if not 0.0 <= float(eta) < 1.0:
+        raise ValueError(f"eta must be in [0, 1), got {eta!r}")
+    ax = _axis(axis, len(shape))
+    planes = int(np.prod(shape[:-2], dtype=np.int64))
+    out = np.empty(shape, np.uint8)
+    if out.size:
+        ctx = _context(device, flags)
+        fp, fm, keep = _pointer(flags, np.uint8, ctx)
+        check(lib.rfi_sir_operator(ctx.handle, C.c_void_p(fp), fm, planes, shape[-2], shape[-1], ax, min(sir_q(eta), 1023),
+                                   C.c_void_p(out.ctypes.data), HOST))
+        del keep
+    return out.view(bool)
+
+
+# ---------------------------------------------------------------------------------------------- the pipeline
+def make_config(iterations=3, levels=7, base_sensitivity=1.0, chi_1=6.0, rho=1.5, smooth_sigma=(2.5, 5.0),
+                smooth_half=(10, 15), sir_eta=0.2):
+    """-> (SumThresholdConfig, weights_t, weights_f) after the argument checks (no device call)."""
+    if not isinstance(iterations, (int, np.integer)) or iterations < 1:
+        raise ValueError(f"iterations must be an integer >= 1, got {iterations!r}")
+    if iterations > 64:
+        raise ValueError(f"iterations must be at most 64, got {iterations!r}")
+    if not isinstance(levels, (int, np.integer)) or not 1 <= levels <= 8:
+        raise ValueError(f"levels must be an integer in 1 .. 8, got {levels!r}")
+    if not float(rho) > 1.0:
+        raise ValueError(f"rho must be > 1, got {rho!r}")
+    if not float(base_sensitivity) > 0.0 or not float(chi_1) > 0.0:
+        raise ValueError("base_sensitivity and chi_1 must be > 0")
+    try:
+        (st, sf), (ht, hf) = smooth_sigma, smooth_half
+    except (TypeError, ValueError):
+        raise ValueError("smooth_sigma and smooth_half must be (time, frequency) pairs") from None
+    if not (float(st) > 0.0 and float(sf) > 0.0):
+        raise ValueError(f"smooth_sigma must be > 0 in both directions, got {smooth_sigma!r}")
+    if not all(isinstance(h, (int, np.integer)) and 0 <= h <= MAX_AXIS for h in (ht, hf)):
+        raise ValueError(f"smooth_half must hold integers in 0 .. 2^20, got {smooth_half!r}")
+    if not 0.0 <= float(sir_eta) < 1.0:
+        raise ValueError(f"sir_eta must be in [0, 1), got {sir_eta!r}")
+    cfg = SumThresholdConfig(int(iterations), int(levels), float(base_sensitivity), float(chi_1), float(rho), int(ht), int(hf),
+                             min(sir_q(sir_eta), 1023), 0)
+    return cfg, gaussian_weights(st, ht), gaussian_weights(sf, hf)
+
+
+def threshold_ladder(sigma, iteration, **config) -> np.ndarray:
+    """chi_k, k = 0 .. levels - 1, of one iteration for a noise estimate ``sigma`` (``rfi_sumthreshold_ladder``: the
+    function the device evaluates; host only)."""
+    cfg, _, _ = make_config(**config)
+    out = np.empty(cfg.levels, np.float64)
+    check(lib.rfi_sumthreshold_ladder(C.byref(cfg), float(sigma), int(iteration), out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
+def sumthreshold_flags(data, flags=None, iterations=3, levels=7, base_sensitivity=1.0, chi_1=6.0, rho=1.5,
+                       smooth_sigma=(2.5, 5.0), smooth_half=(10, 15), sir_eta=0.2, out="host", device=None):
+    """Flags of a whole observation from the SumThreshold baseline strategy (module docstring).
+
+    ``data``: ``(..., C, T)``, every leading axis a batch of independent planes; complex64 / complex128 visibilities
+    (their magnitude is flagged) or float32 / float64 magnitudes; a NumPy array, a torch CPU or CUDA tensor, or a
+    ``DeviceArray``.  ``flags``: optional prior flags of the same shape, bool or uint8 (non-zero == flagged); they
+    count as flagged throughout and stay set.  ``smooth_sigma`` / ``smooth_half``: (time, frequency) pairs.
+
+    ``out="host"`` returns bool flags of ``data``'s shape, like ``predict_flags`` (a CUDA tensor for CUDA input, else
+    NumPy); ``out="device"`` returns a uint8 ``DeviceArray`` and, with device-resident inputs, only enqueues work.
+    """
+    shape = _check_planes("data", data)
+    dt = _np_dtype(data)
+    if dt is None or np.dtype(dt) not in _CODES:
+        raise ValueError(f"data must be complex64, complex128, float32 or float64, got {dt}")
+    dt = np.dtype(dt)
+    if flags is not None:
+        _check_flags(flags, shape)
+    if out not in ("host", "device"):
+        raise ValueError(f"out must be 'host' or 'device', got {out!r}")
+    cfg, wt, wf = make_config(iterations, levels, base_sensitivity, chi_1, rho, smooth_sigma, smooth_half, sir_eta)
+    planes = int(np.prod(shape[:-2], dtype=np.int64))
+
+    ctx = _context(device, data, flags)
+    dp, dm, k1 = _pointer(data, dt, ctx)
+    fp, fm, k2 = _pointer(flags, np.uint8, ctx) if flags is not None else (None, HOST, None)
+    cuda_in = is_torch(data) and data.is_cuda
+    if out == "device":
+        res = ctx.empty(shape, np.uint8)
+        rp, rm = res.ptr, DEVICE
+    elif cuda_in:
+        res = torch.empty(shape, dtype=torch.uint8, device=data.device)
+        torch.cuda.current_stream(data.device).synchronize()        # (the output's memory may have just been freed)
+        rp, rm = res.data_ptr(), DEVICE
+    else:
+        res = np.empty(shape, np.uint8)
+        rp, rm = res.ctypes.data, HOST
+    if planes:
+        _, wtp = _doubles(wt)
+        _, wfp = _doubles(wf)
+        check(lib.rfi_sumthreshold_flag(ctx.handle, C.c_void_p(dp), dm, _CODES[dt], C.c_void_p(fp) if fp else None, fm, planes,
+                                        shape[-2], shape[-1], C.byref(cfg), wtp, wfp, C.c_void_p(rp), rm))
+    if out == "device":
+        res._keep = (k1, k2)             # the inputs may still be read by work in flight: they live as long as the result
+        return res
+    if cuda_in:
+        ctx.synchronize()
+        del k1, k2
+        return res.view(torch.bool)
+    del k1, k2
+    return res.view(bool)
