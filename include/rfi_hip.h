@@ -615,6 +615,74 @@ int rfi_sumthreshold_flag(rfi_ctx* ctx, const void* data, int data_mem, int dtyp
                           int c, int t, const rfi_sumthreshold_config* cfg, const double* weights_t_host,
                           const double* weights_f_host, uint8_t* flags_out, int out_mem);
 
+/* ---- CASA-style baseline flaggers: TFCrop, RFlag and the flag extension (the `tfcrop`, `rflag` and `extend` modes of CASA's
+ *      flagdata, which the reference toolbox calls and has no code for).  The semantics below are this project's own,
+ *      tests/casa_flaggers_ref.py restates them in NumPy and the library equals it bit for bit.  Planes are (n_planes, C, T)
+ *      with time contiguous; flags are bytes, non-zero == flagged.  Every plane is cut along time into chunks of `ntime`
+ *      samples (the last may be shorter); the unit of work is (plane, chunk) and nothing crosses a chunk boundary.  All sums
+ *      below run sequentially in ascending index from 0.0 in double, a sample outside the mask adding +0.0.
+ *
+ *      Robust fit of a line y_0 .. y_{L-1} (float32) with mask u: w = u; for j = 0 .. 4:
+ *        1  shape "line": one piece of degree 1; shape "poly": that at j = 0, then min(2 j + 1, maxnpieces) pieces of degree 3.
+ *           Piece p of n covers samples floor(p L / n) .. floor((p + 1) L / n) - 1 (possibly none).
+ *        2  per piece of m samples: x_i = (double)(2 i - (m - 1)) / (double)(m - 1) (0 for m = 1), x2 = x x, x3 = x2 x, x4 = x2 x2,
+ *           x5 = x4 x, x6 = x3 x3; S_q = sum_w x^q (q = 0 .. 6), B_q = sum_w x^q (double) y (q = 0 .. 3), k = #w.  d = min(degree,
+ *           k - 1).  The normal equations A_rs = S_{r+s}, b_r = B_r (r, s <= d) are padded to 4 x 4 with identity rows (b = 0).
+ *           Elimination without pivoting: for p = 0 .. 3, r = p + 1 .. 3: f = A_rp / A_pp; A_rs = A_rs - f A_ps (s = p + 1 .. 3);
+ *           b_r = b_r - f b_p.  Back substitution for r = 3 .. 0: s = b_r; s = s - A_rt c_t (t = r + 1 .. 3 ascending); c_r = s / A_rr.
+ *           fit_i = ((c_3 x + c_2) x + c_1) x + c_0; r_i = (double) y_i - fit_i.
+ *        3  over the w-samples of the whole line: n, s1 = sum r, s2 = sum r r; mean = s1 / n; var = s2 / n - mean mean;
+ *           sigma = sqrt(var > 0 ? var : 0), 0 for n = 0.  Unless sigma > 0 the iteration ends here with w as it is.
+ *        4  w = w & (fabs(r) <= cutoff sigma).
+ *      The line's new flags are u & ~w.
+ *
+ *      TFCrop: X, F as for the SumThreshold flagger (|z| by the same rule, float32; F = prior | ~isfinite(X); non-finite X <- 0).
+ *        Per chunk: m_c = (float)(sum over the unflagged t of (double) X / count), channels without a sample masked; the robust
+ *        fit of m along frequency (freqfit, freqcutoff) gives b_c = the fit of its last iteration that ran (its flags are
+ *        dropped); Y = (float)((double) X / b_c) where b_c > 0 and finite, else X.  Time stage: the robust fit of every channel
+ *        Y[c, :] (timefit, timecutoff) with u = ~F; frequency stage: of every time sample Y[:, t] (freqfit, freqcutoff).
+ *        flagdimension orders them (freqtime: time stage first); a stage sees the flags of the one before.
+ *      RFlag (complex input only, all in double): F = prior | a non-finite part; non-finite z <- 0.  Both analyses read this F.
+ *        Time, per channel of a chunk: over the unflagged samples of t - h .. t + h inside the chunk (h = winsize / 2), n >= 2:
+ *        means m = sum / n per part, v = sum (re - m_re)^2 / n + sum (im - m_im)^2 / n, rms_t = sqrt(v > 0 ? v : 0).  Over the
+ *        rms_t that exist: med = NumPy's median (the mean (a + b) / 2 of the two middle order statistics), dev = median of
+ *        |rms_t - med|; (c, t) is flagged iff rms_t exists and rms_t > timedevscale (med + dev); timedev replaces med + dev.
+ *        Spectral, per time sample: the same means and d_t = sqrt(v) across the unflagged channels (n >= 2); one threshold per
+ *        chunk, freqdevscale (median + MAD of the d_t that exist), freqdev replacing median + MAD; an unflagged (c, t) whose d_t
+ *        exists is flagged iff sqrt((re - a_re)^2 + (im - a_im)^2) > threshold.  A line without a value has threshold
+ *        scale * inf.  The result is pinned for data whose variances stay finite.
+ *      Extend, per chunk, each step on a snapshot of the one before: growaround (more than 4 of the 8 neighbours inside the
+ *        chunk flagged); growtime ((double)(100 count) > growtime (double) n flags the channel for the chunk); growfreq (the same
+ *        per time sample across the channels); flagneartime; flagnearfreq.
+ *
+ *      Planes are processed in groups whose workspace stays within the context's 1 GiB scratch (tfcrop 35, rflag 26, extend 2
+ *      bytes per sample, a little per plane, plus staging for host buffers); a single plane too large for it is an error.
+ *      Nothing is read back between the upload and the download; with device-resident buffers a call only enqueues work.
+ *      timedev_host: NULL or n_planes * C doubles; freqdev_host: NULL or n_planes doubles.
+ *      Sizes: 1 <= C, T <= 2^20; 1 <= ntime; 1 <= maxnpieces; winsize odd >= 1; cutoffs and scales >= 0; 0 <= grow* <= 100. ---- */
+enum { RFI_TFCROP_FREQTIME = 0, RFI_TFCROP_TIMEFREQ = 1, RFI_TFCROP_TIME = 2, RFI_TFCROP_FREQ = 3 };
+typedef struct rfi_tfcrop_config {
+    int32_t ntime;              /* a value >= T means the whole axis */
+    int32_t timefit, freqfit;   /* 0 "line", 1 "poly" */
+    int32_t maxnpieces, flagdimension, pad_;
+    double timecutoff, freqcutoff;
+} rfi_tfcrop_config;
+typedef struct rfi_rflag_config {
+    int32_t ntime, winsize;
+    double timedevscale, freqdevscale;
+} rfi_rflag_config;
+typedef struct rfi_extend_config {
+    int32_t ntime, growaround, flagneartime, flagnearfreq;
+    double growtime, growfreq;
+} rfi_extend_config;
+int rfi_tfcrop_flag(rfi_ctx* ctx, const void* data, int data_mem, int dtype, const uint8_t* prior, int prior_mem, int n_planes, int c,
+                    int t, const rfi_tfcrop_config* cfg, uint8_t* flags_out, int out_mem);
+int rfi_rflag_flag(rfi_ctx* ctx, const void* data, int data_mem, int dtype, const uint8_t* prior, int prior_mem, int n_planes, int c,
+                   int t, const rfi_rflag_config* cfg, const double* timedev_host, const double* freqdev_host, uint8_t* flags_out,
+                   int out_mem);
+int rfi_extend_flags(rfi_ctx* ctx, const uint8_t* flags_in, int flags_mem, int n_planes, int c, int t, const rfi_extend_config* cfg,
+                     uint8_t* flags_out, int out_mem);
+
 /* ---- kernel-level entry points (device pointers only).  Used by the parity tests to
  *      check each HIP kernel against the oracle in isolation.  impl: 0 auto, 1 direct VALU,
  *      2 MFMA implicit GEMM in native float32 (v_mfma_f32_32x32x2_f32), 3 MFMA implicit GEMM with bfloat16

@@ -47,6 +47,20 @@ class SumThresholdConfig(C.Structure):
                 ("rho", C.c_double), ("half_t", C.c_int32), ("half_f", C.c_int32), ("sir_q", C.c_int32), ("pad_", C.c_int32)]
 
 
+class TfcropConfig(C.Structure):
+    _fields_ = [("ntime", C.c_int32), ("timefit", C.c_int32), ("freqfit", C.c_int32), ("maxnpieces", C.c_int32),
+                ("flagdimension", C.c_int32), ("pad_", C.c_int32), ("timecutoff", C.c_double), ("freqcutoff", C.c_double)]
+
+
+class RflagConfig(C.Structure):
+    _fields_ = [("ntime", C.c_int32), ("winsize", C.c_int32), ("timedevscale", C.c_double), ("freqdevscale", C.c_double)]
+
+
+class ExtendConfig(C.Structure):
+    _fields_ = [("ntime", C.c_int32), ("growaround", C.c_int32), ("flagneartime", C.c_int32), ("flagnearfreq", C.c_int32),
+                ("growtime", C.c_double), ("growfreq", C.c_double)]
+
+
 class SimParams(C.Structure):
     _fields_ = [("time_bins", C.c_int32), ("freq_bins", C.c_int32), ("n_power", C.c_int32), ("gibbs_ringing", C.c_int32),
                 ("clean", C.c_int32), ("fixed_baseline", C.c_int32), ("baseline_frac", C.c_double),
@@ -210,6 +224,9 @@ _PROTOS = {
     "rfi_masked_smooth": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _pd, _i, _pd, _i, _vp, _i]),
     "rfi_sir_operator": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i]),
     "rfi_sumthreshold_flag": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _i, C.POINTER(SumThresholdConfig), _pd, _pd, _vp, _i]),
+    "rfi_tfcrop_flag": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _i, C.POINTER(TfcropConfig), _vp, _i]),
+    "rfi_rflag_flag": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _i, C.POINTER(RflagConfig), _pd, _pd, _vp, _i]),
+    "rfi_extend_flags": (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(ExtendConfig), _vp, _i]),
     "rfi_op_conv3x3": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     "rfi_op_conv1x1": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     "rfi_op_conv_s2": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),

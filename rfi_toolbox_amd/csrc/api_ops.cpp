@@ -1,5 +1,6 @@
 // extern "C" surface of librfi_hip.so, continued: the kernel-level ops (declared in include/rfi_hip.h).
 #include <algorithm>
+#include <functional>
 
 #include "model.hpp"
 
@@ -873,6 +874,144 @@ int rfi_sumthreshold_flag(rfi_ctx* ctx, const void* data, int data_mem, int dtyp
         }
         if (host_in || host_pr || host_out) RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
         drain.armed = false;
+    });
+}
+// ---- CASA-style baseline flaggers (casa_flaggers.hip)
+namespace {
+// Groups of k whole planes in the context's scratch: [workspace of the launch | staged data | staged prior | staged extras].
+// Host buffers are uploaded per group and the group's flags copied out, all on the context's stream; device buffers are
+// used in place.  ws(k): workspace bytes of k planes (at most k ws(1)); extra_doubles: per-plane doubles of up to two optional
+// host arrays (timedev, freqdev) that travel with the group; run(in, prior, first plane, planes, ws, extras) -> the flags.
+using GroupWs = std::function<size_t(int)>;
+using GroupRun = std::function<const uint8_t*(const void*, const uint8_t*, int, void*, const double* const*)>;
+void flag_in_groups(rfi_ctx* ctx, const std::string& who, const void* data, int data_mem, size_t esz, const uint8_t* prior, int prior_mem,
+                    int n_planes, size_t px, const double* const extra_host[2], const size_t extra_doubles[2], uint8_t* flags_out,
+                    int out_mem, const GroupWs& ws, const GroupRun& run) {
+    const bool host_in = data_mem == RFI_HOST, host_pr = prior && prior_mem == RFI_HOST, host_out = out_mem == RFI_HOST;
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    size_t ex[2];
+    for (int e = 0; e < 2; ++e) ex[e] = extra_host[e] ? extra_doubles[e] * 8 : 0;
+    const size_t per_plane = ws(1) + (host_in ? al(px * esz) : 0) + (host_pr ? al(px) : 0) + al(ex[0]) + al(ex[1]);
+    RFI_REQUIRE(per_plane <= kFlagBudget, who + ": one plane needs " + std::to_string(per_plane >> 20) +
+                                              " MiB of workspace, over the budget of " + std::to_string(kFlagBudget >> 20) +
+                                              " MiB; planes are not split");
+    const int k = (int)std::min<size_t>((size_t)n_planes, kFlagBudget / per_plane);
+    const size_t kn = (size_t)k * px;
+    const size_t b_ws = al(ws(k)), b_in = host_in ? al(kn * esz) : 0, b_pr = host_pr ? al(kn) : 0;
+    const size_t b_e0 = al(ex[0] * k), b_e1 = al(ex[1] * k);
+    char* base = static_cast<char*>(ctx->get_scratch(b_ws + b_in + b_pr + b_e0 + b_e1));
+    char* d_in = base + b_ws;
+    uint8_t* d_pr = reinterpret_cast<uint8_t*>(d_in + b_in);
+    double* d_ex[2] = {reinterpret_cast<double*>(d_in + b_in + b_pr), reinterpret_cast<double*>(d_in + b_in + b_pr + b_e0)};
+    struct Drain {            // a failure part way leaves no work in flight on buffers the caller owns
+        rfi_ctx* c; bool armed;
+        ~Drain() { if (armed) (void)hipStreamSynchronize(c->stream); }
+    } drain{ctx, true};
+    const char* src = static_cast<const char*>(data);
+    for (int p0 = 0; p0 < n_planes; p0 += k) {
+        const int np = std::min(k, n_planes - p0);
+        const size_t off = (size_t)p0 * px, cn = (size_t)np * px;
+        const void* in = src + off * esz;
+        const uint8_t* pr = prior ? prior + off : nullptr;
+        if (host_in) {
+            RFI_CHECK_HIP(hipMemcpyAsync(d_in, in, cn * esz, hipMemcpyHostToDevice, ctx->stream));
+            in = d_in;
+        }
+        if (host_pr) {
+            RFI_CHECK_HIP(hipMemcpyAsync(d_pr, pr, cn, hipMemcpyHostToDevice, ctx->stream));
+            pr = d_pr;
+        }
+        const double* extras[2] = {nullptr, nullptr};
+        for (int e = 0; e < 2; ++e)
+            if (extra_host[e]) {
+                RFI_CHECK_HIP(hipMemcpyAsync(d_ex[e], extra_host[e] + (size_t)p0 * extra_doubles[e], (size_t)np * ex[e],
+                                             hipMemcpyHostToDevice, ctx->stream));
+                extras[e] = d_ex[e];
+            }
+        const uint8_t* res = run(in, pr, np, static_cast<void*>(base), extras);
+        RFI_CHECK_HIP(hipMemcpyAsync(flags_out + off, res, cn, host_out ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    if (host_in || host_pr || host_out || extra_host[0] || extra_host[1]) RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    drain.armed = false;
+}
+const double* const kNoExtras[2] = {nullptr, nullptr};
+const size_t kNoExtraSizes[2] = {0, 0};
+bool in_range(double v, double lo, double hi) { return v >= lo && v <= hi; }      // (false for NaN)
+}  // namespace
+
+int rfi_tfcrop_flag(rfi_ctx* ctx, const void* data, int data_mem, int dtype, const uint8_t* prior, int prior_mem, int n_planes, int c,
+                    int t, const rfi_tfcrop_config* cfg, uint8_t* flags_out, int out_mem) {
+    return guarded([&] {
+        RFI_REQUIRE(ctx, "tfcrop_flag: null context");
+        RFI_REQUIRE(dtype >= RFI_C128 && dtype <= RFI_F32, "tfcrop_flag: dtype must be complex128, complex64, float64 or float32");
+        check_st_planes("tfcrop_flag", n_planes, c, t);
+        RFI_REQUIRE(cfg, "tfcrop_flag: null config");
+        RFI_REQUIRE(cfg->ntime >= 1, "tfcrop_flag: ntime must be >= 1");
+        RFI_REQUIRE((cfg->timefit == 0 || cfg->timefit == 1) && (cfg->freqfit == 0 || cfg->freqfit == 1),
+                    "tfcrop_flag: timefit and freqfit must be 0 (line) or 1 (poly)");
+        RFI_REQUIRE(cfg->maxnpieces >= 1, "tfcrop_flag: maxnpieces must be >= 1");
+        RFI_REQUIRE(cfg->flagdimension >= RFI_TFCROP_FREQTIME && cfg->flagdimension <= RFI_TFCROP_FREQ, "tfcrop_flag: bad flagdimension");
+        RFI_REQUIRE(in_range(cfg->timecutoff, 0.0, 1.0e300) && in_range(cfg->freqcutoff, 0.0, 1.0e300), "tfcrop_flag: cutoffs must be >= 0");
+        RFI_REQUIRE(mem_ok(data_mem) && (!prior || mem_ok(prior_mem)) && mem_ok(out_mem), "tfcrop_flag: bad memory kind");
+        if (n_planes == 0) return;
+        RFI_REQUIRE(data && flags_out, "tfcrop_flag: null argument");
+        ctx->activate();
+        rfi_tfcrop_config cf = *cfg;
+        cf.ntime = std::min(cf.ntime, t);
+        const size_t esz = dtype == RFI_C128 ? 16 : (dtype == RFI_F32 ? 4 : 8);
+        flag_in_groups(ctx, "tfcrop_flag", data, data_mem, esz, prior, prior_mem, n_planes, (size_t)c * t, kNoExtras, kNoExtraSizes, flags_out,
+                       out_mem, [&](int k) { return tfcrop_ws_bytes(k, c, t, cf.ntime); },
+                       [&](const void* in, const uint8_t* pr, int np, void* ws, const double* const*) {
+                           return launch_tfcrop_flag(ctx, in, dtype, pr, np, c, t, cf, ws);
+                       });
+    });
+}
+int rfi_rflag_flag(rfi_ctx* ctx, const void* data, int data_mem, int dtype, const uint8_t* prior, int prior_mem, int n_planes, int c,
+                   int t, const rfi_rflag_config* cfg, const double* timedev_host, const double* freqdev_host, uint8_t* flags_out,
+                   int out_mem) {
+    return guarded([&] {
+        RFI_REQUIRE(ctx, "rflag_flag: null context");
+        RFI_REQUIRE(dtype == RFI_C128 || dtype == RFI_C64, "rflag_flag: dtype must be complex128 or complex64");
+        check_st_planes("rflag_flag", n_planes, c, t);
+        RFI_REQUIRE(cfg, "rflag_flag: null config");
+        RFI_REQUIRE(cfg->ntime >= 1, "rflag_flag: ntime must be >= 1");
+        RFI_REQUIRE(cfg->winsize >= 1 && cfg->winsize % 2 == 1, "rflag_flag: winsize must be odd and >= 1");
+        RFI_REQUIRE(in_range(cfg->timedevscale, 0.0, 1.0e300) && in_range(cfg->freqdevscale, 0.0, 1.0e300), "rflag_flag: scales must be >= 0");
+        RFI_REQUIRE(mem_ok(data_mem) && (!prior || mem_ok(prior_mem)) && mem_ok(out_mem), "rflag_flag: bad memory kind");
+        if (n_planes == 0) return;
+        RFI_REQUIRE(data && flags_out, "rflag_flag: null argument");
+        ctx->activate();
+        rfi_rflag_config cf = *cfg;
+        cf.ntime = std::min(cf.ntime, t);
+        const double* const extras[2] = {timedev_host, freqdev_host};
+        const size_t sizes[2] = {(size_t)c, 1};
+        flag_in_groups(ctx, "rflag_flag", data, data_mem, dtype == RFI_C128 ? 16 : 8, prior, prior_mem, n_planes, (size_t)c * t, extras, sizes,
+                       flags_out, out_mem, [&](int k) { return rflag_ws_bytes(k, c, t, cf.ntime); },
+                       [&](const void* in, const uint8_t* pr, int np, void* ws, const double* const* ex) {
+                           return launch_rflag_flag(ctx, in, dtype, pr, np, c, t, cf, ex[0], ex[1], ws);
+                       });
+    });
+}
+int rfi_extend_flags(rfi_ctx* ctx, const uint8_t* flags_in, int flags_mem, int n_planes, int c, int t, const rfi_extend_config* cfg,
+                     uint8_t* flags_out, int out_mem) {
+    return guarded([&] {
+        RFI_REQUIRE(ctx, "extend_flags: null context");
+        check_st_planes("extend_flags", n_planes, c, t);
+        RFI_REQUIRE(cfg, "extend_flags: null config");
+        RFI_REQUIRE(cfg->ntime >= 1, "extend_flags: ntime must be >= 1");
+        RFI_REQUIRE(in_range(cfg->growtime, 0.0, 100.0) && in_range(cfg->growfreq, 0.0, 100.0),
+                    "extend_flags: growtime and growfreq must be in 0 .. 100");
+        RFI_REQUIRE(mem_ok(flags_mem) && mem_ok(out_mem), "extend_flags: bad memory kind");
+        if (n_planes == 0) return;
+        RFI_REQUIRE(flags_in && flags_out, "extend_flags: null argument");
+        ctx->activate();
+        rfi_extend_config cf = *cfg;
+        cf.ntime = std::min(cf.ntime, t);
+        flag_in_groups(ctx, "extend_flags", flags_in, flags_mem, 1, nullptr, RFI_HOST, n_planes, (size_t)c * t, kNoExtras, kNoExtraSizes,
+                       flags_out, out_mem, [&](int k) { return extend_ws_bytes(k, c, t); },
+                       [&](const void* in, const uint8_t*, int np, void* ws, const double* const*) {
+                           return launch_extend_flags(ctx, static_cast<const uint8_t*>(in), np, c, t, cf, ws);
+                       });
     });
 }
 int rfi_op_fpn_merge(rfi_ctx* ctx, const float* lateral, const float* top, int n, int h, int w, int c, float* out) {

@@ -371,6 +371,18 @@ void launch_st_sir(rfi_ctx* ctx, const uint8_t* Fin, uint8_t* Fout, int planes, 
 void launch_sumthreshold_flag(rfi_ctx* ctx, const void* src, int dtype, const uint8_t* prior, int planes, int C, int T,
                               const rfi_sumthreshold_config& cfg, const double* wt, const double* wf, float* X, float* B, uint8_t* Fa,
                               uint8_t* Fb, double* nd, void* state, uint8_t* out);
+// CASA-style baseline flaggers (casa_flaggers.hip; semantics in include/rfi_hip.h, "CASA-style baseline flaggers").  Each launch
+// works on `planes` device-resident planes inside a workspace of *_ws_bytes and returns the buffer inside it that holds the
+// flags (0 / 1 bytes); cfg.ntime is in 1 .. T.  timedev (planes C doubles) / freqdev (planes doubles): device pointers or null.
+void launch_st_prepare(rfi_ctx* ctx, const void* src, int dtype, const uint8_t* prior, int64_t n, float* X, uint8_t* F);
+size_t tfcrop_ws_bytes(int planes, int C, int T, int ntime);
+uint8_t* launch_tfcrop_flag(rfi_ctx* ctx, const void* src, int dtype, const uint8_t* prior, int planes, int C, int T,
+                            const rfi_tfcrop_config& cfg, void* ws);
+size_t rflag_ws_bytes(int planes, int C, int T, int ntime);
+uint8_t* launch_rflag_flag(rfi_ctx* ctx, const void* src, int dtype, const uint8_t* prior, int planes, int C, int T,
+                           const rfi_rflag_config& cfg, const double* timedev, const double* freqdev, void* ws);
+size_t extend_ws_bytes(int planes, int C, int T);
+uint8_t* launch_extend_flags(rfi_ctx* ctx, const uint8_t* Fin, int planes, int C, int T, const rfi_extend_config& cfg, void* ws);
 // RFISimulator waterfalls (rfi_sim.hip): draws the event table into `events` (unless p.clean), then one gather per
 // pixel into `out` (layout RFI_SIM_*) and `mask`; sizes are checked by rfi_simulate_rfi
 void launch_rfi_sim(rfi_ctx* ctx, unsigned long long seed, unsigned first_sample, int n_samples,

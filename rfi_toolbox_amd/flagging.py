@@ -15,6 +15,11 @@ download happens on the device (csrc/sumthreshold.hip); there is no CPU path.
 
 A Gaussian smooth cannot follow a bandpass that falls off steeply (the simulator's t^8 band edges): about a quarter of
 such a plane gets flagged.  Divide the bandpass out first, as an observatory pipeline does.
+
+The other statistical flaggers the reference names are here as well, in the style of CASA's flagdata modes and per
+chunk of ``ntime`` time samples: ``tfcrop_flags`` (robust piecewise-polynomial fits along time and frequency after the
+bandpass is divided out), ``rflag_flags`` (sliding-window rms along time and deviation from the mean spectrum, exact
+medians) and ``extend_flags`` (csrc/casa_flaggers.hip; header section "CASA-style baseline flaggers").
 """
 from __future__ import annotations
 
@@ -22,7 +27,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import C64, C128, DEVICE, F32, F64, HOST, SumThresholdConfig, check, lib
+from ._lib import C64, C128, DEVICE, ExtendConfig, F32, F64, HOST, RflagConfig, SumThresholdConfig, TfcropConfig, check, lib
 from .runtime import Context, DeviceArray, is_torch, torch
 
 _CODES = {np.dtype(np.complex128): C128, np.dtype(np.complex64): C64, np.dtype(np.float64): F64, np.dtype(np.float32): F32}
@@ -302,3 +307,164 @@ def sumthreshold_flags(data, flags=None, iterations=3, levels=7, base_sensitivit
         return res.view(torch.bool)
     del k1, k2
     return res.view(bool)
+
+
+# ---------------------------------------------------------------------------------------------- CASA-style flaggers
+_FITS = {"line": 0, "poly": 1}
+_DIMENSIONS = {"freqtime": 0, "timefreq": 1, "time": 2, "freq": 3}
+_INT_MAX = (1 << 31) - 1
+
+
+def _ntime(ntime):
+    """None (the whole axis) or an integer >= 1 -> the int32 the library takes."""
+    if ntime is None:
+        return _INT_MAX
+    if isinstance(ntime, (bool, np.bool_)) or not isinstance(ntime, (int, np.integer)) or ntime < 1:
+        raise ValueError(f"ntime must be None or an integer >= 1, got {ntime!r}")
+    return int(min(ntime, _INT_MAX))
+
+
+def _non_negative(name, v):
+    v = float(v)
+    if not 0.0 <= v < float("inf"):
+        raise ValueError(f"{name} must be finite and >= 0, got {v!r}")
+    return v
+
+
+def _per_plane(name, v, planes, per, forms):
+    """None or float64 (planes * per,) from a scalar, one value per plane or (planes, per) values."""
+    if v is None:
+        return None
+    a = np.asarray(v, np.float64)
+    if a.size == 1:
+        return np.full(planes * per, a.reshape(()), np.float64)
+    if a.size == planes * per and (per == 1 or a.ndim >= 2 or planes == 1):
+        return np.ascontiguousarray(a.reshape(planes * per))
+    if a.size == planes:
+        return np.ascontiguousarray(np.repeat(a.reshape(planes), per))
+    raise ValueError(f"{name} must be {forms}, got shape {a.shape}")
+
+
+def _run_flagger(call, data, dt, flags, shape, out, device):
+    """The shared tail of the three flaggers: pointers, the result buffer of `out`, then call(ctx, data pointer and
+    memory kind, prior pointer and kind, planes, result pointer and kind)."""
+    planes = int(np.prod(shape[:-2], dtype=np.int64))
+    ctx = _context(device, data, flags)
+    dp, dm, k1 = _pointer(data, dt, ctx)
+    fp, fm, k2 = _pointer(flags, np.uint8, ctx) if flags is not None else (None, HOST, None)
+    cuda_in = is_torch(data) and data.is_cuda
+    if out == "device":
+        res = ctx.empty(shape, np.uint8)
+        rp, rm = res.ptr, DEVICE
+    elif cuda_in:
+        res = torch.empty(shape, dtype=torch.uint8, device=data.device)
+        torch.cuda.current_stream(data.device).synchronize()        # (the output's memory may have just been freed)
+        rp, rm = res.data_ptr(), DEVICE
+    else:
+        res = np.empty(shape, np.uint8)
+        rp, rm = res.ctypes.data, HOST
+    if planes:
+        check(call(ctx, C.c_void_p(dp), dm, C.c_void_p(fp) if fp else None, fm, planes, C.c_void_p(rp), rm))
+    if out == "device":
+        res._keep = (k1, k2)             # the inputs may still be read by work in flight: they live as long as the result
+        return res
+    if cuda_in:
+        ctx.synchronize()
+        del k1, k2
+        return res.view(torch.bool)
+    del k1, k2
+    return res.view(bool)
+
+
+def _check_data(data, flags, out, codes):
+    shape = _check_planes("data", data)
+    dt = _np_dtype(data)
+    if dt is None or np.dtype(dt) not in codes:
+        raise ValueError(f"data must be one of {', '.join(str(c) for c in codes)}, got {dt}")
+    if flags is not None:
+        _check_flags(flags, shape)
+    if out not in ("host", "device"):
+        raise ValueError(f"out must be 'host' or 'device', got {out!r}")
+    return shape, np.dtype(dt)
+
+
+def tfcrop_flags(data, flags=None, ntime=None, timecutoff=4.0, freqcutoff=3.0, timefit="line", freqfit="poly", maxnpieces=7,
+                 flagdimension="freqtime", out="host", device=None):
+    """Flags from a TFCrop-style flagger (CASA flagdata ``mode="tfcrop"``): robust fits along time and frequency.
+
+    ``data``, ``flags``, ``out`` and ``device`` as for ``sumthreshold_flags`` (complex input is flagged on its
+    magnitude).  Every plane is cut along time into chunks of ``ntime`` samples (None: the whole axis), and nothing
+    crosses a chunk boundary.  Per chunk the mean bandpass over the unflagged samples is fitted robustly along frequency
+    and divided out; then every channel is fitted along time (``timefit``, ``timecutoff``) and every time sample along
+    frequency (``freqfit``, ``freqcutoff``) in the order ``flagdimension`` ("freqtime": time first, "timefreq", "time",
+    "freq").  A fit is "line" or "poly" (a line, then up to ``maxnpieces`` cubic pieces), iterated five times, each time
+    rejecting the samples further than cutoff standard deviations of the residuals from it.  The arithmetic is pinned in
+    include/rfi_hip.h ("CASA-style baseline flaggers") and is this project's own: results agree with CASA in kind, not
+    bit for bit.  CASA's ``usewindowstats`` / ``halfwin`` are not built.  There is no CPU path."""
+    shape, dt = _check_data(data, flags, out, _CODES)
+    for name, v in (("timefit", timefit), ("freqfit", freqfit)):
+        if v not in _FITS:
+            raise ValueError(f"{name} must be 'line' or 'poly', got {v!r}")
+    if flagdimension not in _DIMENSIONS:
+        raise ValueError(f"flagdimension must be one of {', '.join(_DIMENSIONS)}, got {flagdimension!r}")
+    if isinstance(maxnpieces, (bool, np.bool_)) or not isinstance(maxnpieces, (int, np.integer)) or maxnpieces < 1:
+        raise ValueError(f"maxnpieces must be an integer >= 1, got {maxnpieces!r}")
+    cfg = TfcropConfig(_ntime(ntime), _FITS[timefit], _FITS[freqfit], int(min(maxnpieces, _INT_MAX)), _DIMENSIONS[flagdimension], 0,
+                       _non_negative("timecutoff", timecutoff), _non_negative("freqcutoff", freqcutoff))
+
+    def call(ctx, dp, dm, fp, fm, planes, rp, rm):
+        return lib.rfi_tfcrop_flag(ctx.handle, dp, dm, _CODES[dt], fp, fm, planes, shape[-2], shape[-1], C.byref(cfg), rp, rm)
+    return _run_flagger(call, data, dt, flags, shape, out, device)
+
+
+def rflag_flags(data, flags=None, ntime=None, winsize=3, timedevscale=5.0, freqdevscale=5.0, timedev=None, freqdev=None,
+                out="host", device=None):
+    """Flags from an RFlag-style flagger (CASA flagdata ``mode="rflag"``), on the real and imaginary parts of complex
+    visibilities (real input raises ``ValueError``).
+
+    Per chunk of ``ntime`` samples (None: the whole axis).  Time analysis: per channel the rms of the unflagged samples
+    in a sliding window of ``winsize`` (odd) samples; a sample is flagged when the rms of its window exceeds
+    ``timedevscale`` times (median + median absolute deviation of the channel's rms values).  Spectral analysis: per time
+    sample the deviation of every channel from the mean over the unflagged channels; a sample is flagged when it exceeds
+    ``freqdevscale`` times (median + MAD over the chunk of the per-sample rms deviations).  Both read the same input
+    flags and their results are ORed.  ``timedev`` replaces median + MAD of the time analysis (a scalar, one value per
+    plane or ``(planes, C)`` values), ``freqdev`` that of the spectral analysis (a scalar or one value per plane).
+    Medians are exact.  Unlike CASA, no polynomial is fitted to the per-channel thresholds across a spectral window.
+    ``data``, ``flags``, ``out`` and ``device`` as for ``sumthreshold_flags``.  There is no CPU path."""
+    codes = {k: v for k, v in _CODES.items() if k.kind == "c"}
+    shape, dt = _check_data(data, flags, out, codes)
+    if isinstance(winsize, (bool, np.bool_)) or not isinstance(winsize, (int, np.integer)) or winsize < 1 or winsize % 2 == 0:
+        raise ValueError(f"winsize must be an odd integer >= 1, got {winsize!r}")
+    planes = int(np.prod(shape[:-2], dtype=np.int64))
+    cfg = RflagConfig(_ntime(ntime), int(min(winsize, _INT_MAX)), _non_negative("timedevscale", timedevscale),
+                      _non_negative("freqdevscale", freqdevscale))
+    td = _per_plane("timedev", timedev, planes, shape[-2], "a scalar, one value per plane or (planes, C) values")
+    fd = _per_plane("freqdev", freqdev, planes, 1, "a scalar or one value per plane")
+    tdp = td.ctypes.data_as(C.POINTER(C.c_double)) if td is not None else None
+    fdp = fd.ctypes.data_as(C.POINTER(C.c_double)) if fd is not None else None
+
+    def call(ctx, dp, dm, fp, fm, planes, rp, rm):
+        return lib.rfi_rflag_flag(ctx.handle, dp, dm, _CODES[dt], fp, fm, planes, shape[-2], shape[-1], C.byref(cfg), tdp, fdp, rp, rm)
+    return _run_flagger(call, data, dt, flags, shape, out, device)
+
+
+def extend_flags(flags, ntime=None, growtime=50.0, growfreq=50.0, growaround=False, flagneartime=False, flagnearfreq=False,
+                 out="host", device=None):
+    """CASA flagdata ``mode="extend"`` on ``(..., C, T)`` bool or uint8 flags, per chunk of ``ntime`` samples and in this
+    order, each step on the result of the one before: ``growaround`` (a sample with more than 4 of its 8 neighbours
+    flagged), ``growtime`` (a channel flagged for more than that many per cent of the chunk is flagged for all of it; 100
+    switches it off), ``growfreq`` (the same per time sample across the channels), ``flagneartime`` and ``flagnearfreq``
+    (the samples one step from a flagged one).  ``out`` and ``device`` as for ``sumthreshold_flags``."""
+    shape = _check_planes("flags", flags)
+    _check_flags(flags, shape)
+    if out not in ("host", "device"):
+        raise ValueError(f"out must be 'host' or 'device', got {out!r}")
+    for name, v in (("growtime", growtime), ("growfreq", growfreq)):
+        if not 0.0 <= float(v) <= 100.0:
+            raise ValueError(f"{name} must be in 0 .. 100, got {v!r}")
+    cfg = ExtendConfig(_ntime(ntime), int(bool(growaround)), int(bool(flagneartime)), int(bool(flagnearfreq)), float(growtime),
+                       float(growfreq))
+
+    def call(ctx, dp, dm, fp, fm, planes, rp, rm):
+        return lib.rfi_extend_flags(ctx.handle, dp, dm, planes, shape[-2], shape[-1], C.byref(cfg), rp, rm)
+    return _run_flagger(call, flags, np.uint8, None, shape, out, device)

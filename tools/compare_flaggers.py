@@ -1,0 +1,91 @@
+#!/usr/bin/env python3
+"""Compare the statistical flaggers with each other and, given a checkpoint, with a learned one -- the comparison the
+toolbox exists for ("established statistical methods (TFCROP, RFLAG, AOFlagger)" against a segmentation model).
+
+    python tools/compare_flaggers.py [--source simulator|synthetic] [--samples 8] [--size 256] [--seed 0] [--ntime N]
+                                     [--checkpoint unet.pt --width 16]
+
+Planes come from ``RFISimulator.generate_batch`` (default) or from ``oracle/synth_ref.generate`` with a fixed event list on
+96 x 160 planes.  Every flagger runs on the device: ``sumthreshold_flags``, ``tfcrop_flags`` and ``rflag_flags``,
+the last two also followed by ``extend_flags`` as CASA users run them, and with ``--checkpoint`` ``predict_flags`` of a
+``UNet(3, 1, --width)``.  One table: ``evaluate_segmentation`` against the truth mask and ``compute_ffi`` per flagger."""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+EVENTS = [[(0, 20, 21, 0, 160, 5.0), (0, 0, 96, 40, 42, 3.0), (1, 10, 80, 4, 1, 2.0)], [(0, 5, 7, 0, 160, 1.0), (0, 50, 51, 100, 108, 0.8)]]
+
+
+def parse(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--source", choices=("simulator", "synthetic"), default="simulator")
+    ap.add_argument("--samples", type=int, default=8)
+    ap.add_argument("--size", type=int, default=256, help="channels and time samples of a plane")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--ntime", type=int, default=None, help="time samples per chunk of tfcrop / rflag / extend (default: all)")
+    ap.add_argument("--checkpoint", default=None, help="a checkpoint of UNet(3, 1, --width): adds predict_flags to the table")
+    ap.add_argument("--width", type=int, default=16)
+    ap.add_argument("--patch-size", type=int, default=128)
+    return ap.parse_args(argv)
+
+
+def planes_and_truth(args):
+    """-> (data (n, P, C, T) complex64, truth (n, P, C, T) uint8) as NumPy arrays, time contiguous."""
+    if args.source == "synthetic":                                      # fixed 96 x 160 planes, two polarisations
+        from oracle import synth_ref
+        events = [EVENTS[i % len(EVENTS)] for i in range(args.samples)]
+        planes, truth = synth_ref.generate(args.seed, events, 2, 96, 160, noise=0.1, use_bandpass=False)
+        return planes.astype(np.complex64), truth
+    from rfi_toolbox_amd.core.simulator import RFISimulator
+    batch = RFISimulator(args.size, args.size, seed=args.seed).generate_batch(args.samples)
+    data = np.ascontiguousarray(batch.data.numpy().swapaxes(-1, -2))    # the simulator's planes are (time, frequency)
+    mask = np.ascontiguousarray(batch.mask.numpy().swapaxes(-1, -2))
+    return data, np.ascontiguousarray(np.repeat(mask[:, None], 4, axis=1))     # one truth mask for a sample's four planes
+
+
+def flaggers(args):
+    from rfi_toolbox_amd import flagging as fl
+    ext = dict(ntime=args.ntime, growaround=True, flagneartime=True, flagnearfreq=True, out="device")
+    table = [("sumthreshold", lambda d: fl.sumthreshold_flags(d, out="device")),
+             ("tfcrop", lambda d: fl.tfcrop_flags(d, ntime=args.ntime, out="device")),
+             ("tfcrop+extend", lambda d: fl.extend_flags(fl.tfcrop_flags(d, ntime=args.ntime, out="device"), **ext)),
+             ("rflag", lambda d: fl.rflag_flags(d, ntime=args.ntime, out="device")),
+             ("rflag+extend", lambda d: fl.extend_flags(fl.rflag_flags(d, ntime=args.ntime, out="device"), **ext))]
+    if args.checkpoint:
+        from rfi_toolbox_amd.inference import predict_flags
+        from rfi_toolbox_amd.models import UNet
+        from rfi_toolbox_amd.training import load_checkpoint
+        model = UNet(3, 1, args.width, device="cuda:0")
+        load_checkpoint(args.checkpoint, model, load_optimizer=False)
+
+        def learned(d):
+            return predict_flags(model, d, patch_size=args.patch_size).view(np.uint8)
+        table.append(("predict_flags", learned))
+    return table
+
+
+def main(argv=None):
+    args = parse(argv)
+    from rfi_toolbox_amd.evaluation.metrics import evaluate_segmentation
+    from rfi_toolbox_amd.evaluation.statistics import compute_ffi
+    data, truth = planes_and_truth(args)
+    rows = []
+    for name, run in flaggers(args):
+        flags = run(data)
+        seg = evaluate_segmentation(flags, truth)
+        ffi = compute_ffi(data, flags)
+        rows.append((name, seg, ffi))
+    print(f"{'flagger':<15}{'iou':>8}{'precision':>11}{'recall':>8}{'f1':>8}{'ffi':>8}{'flagged':>9}")
+    for name, seg, ffi in rows:
+        print(f"{name:<15}{seg['iou']:>8.4f}{seg['precision']:>11.4f}{seg['recall']:>8.4f}{seg['f1']:>8.4f}{ffi['ffi']:>8.4f}"
+              f"{ffi['flagged_fraction']:>9.4f}")
+    return rows
+
+
+if __name__ == "__main__":
+    main()
