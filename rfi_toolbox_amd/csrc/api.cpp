@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "launch_common.hpp"
 #include "model.hpp"
 
 using namespace rfi;
@@ -101,8 +102,6 @@ UNetModel* plain_unet(rfi_model* m) {
     auto* u = dynamic_cast<UNetModel*>(m);
     return u && !u->resnet_encoder ? u : nullptr;
 }
-
-size_t dtype_bytes(int dtype) { return dtype == RFI_C128 ? 16 : (dtype == RFI_F32 ? 4 : 8); }
 
 // launches on another stream for the life of the scope (profiled launches read ctx->stream)
 struct OnStream {
@@ -1373,7 +1372,6 @@ int rfi_model_predict_flags(rfi_model* m, const void* planes, int planes_mem, in
         }
 
         // one grow-only scratch region: [table | min/max words | images | patch outputs | 2 plane slots | 2 output slots]
-        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
         const size_t b_table = al(table.size() * sizeof(rfi_patch_src)), b_mm = al((size_t)nb * 4 * sizeof(unsigned long long));
         const size_t b_img = al((size_t)nb * patch_px * 3 * sizeof(float)), b_out = al((size_t)chunk_patches * patch_px * sizeof(float));
         const size_t b_in = host_in ? al((size_t)k * plane_bytes) : 0;
@@ -1393,10 +1391,7 @@ int rfi_model_predict_flags(rfi_model* m, const void* planes, int planes_mem, in
 
         TmpStream cs;
         TmpEvents ev(8);          // [0,1] upload done, [2,3] slot read by the gathers, [4,5] outputs ready, [6,7] outputs copied
-        struct Drain {            // every exit (an exception included) leaves both streams idle
-            rfi_ctx* c; hipStream_t s;
-            ~Drain() { (void)hipStreamSynchronize(s); (void)hipStreamSynchronize(c->stream); }
-        } drain{ctx, cs.s};
+        Drain drain{ctx, cs.s};   // every exit (an exception included) leaves both streams idle
         const char* src = static_cast<const char*>(planes);
         auto planes_in = [&](int ci) { return std::min(k, n_planes - ci * k); };
         auto upload = [&](int ci) {

@@ -1,6 +1,5 @@
 // extern "C" surface of librfi_hip.so, continued: the kernel-level ops (declared in include/rfi_hip.h).
 #include <algorithm>
-#include <functional>
 
 #include "model.hpp"
 
@@ -699,319 +698,6 @@ int rfi_augment_batch(rfi_ctx* ctx, const float* x, int x_mem, const uint8_t* y,
                     "augment_batch: float buffers must be 4-byte aligned (16-byte when c % 4 == 0)");
         launch_augment(ctx, dx, dy, n, h, w, c, *cfg, call, x_out, y_out);
         sc.finish();
-    });
-}
-// ---- statistical baseline flagger (sumthreshold.hip)
-namespace {
-constexpr size_t kFlagBudget = size_t(1) << 30;      // workspace of one chunk of rfi_sumthreshold_flag
-
-void check_st_planes(const char* who, int n_planes, int c, int t) {
-    RFI_REQUIRE(n_planes >= 0 && c >= 1 && t >= 1 && c <= (1 << 20) && t <= (1 << 20),
-                std::string(who) + ": needs n_planes >= 0 and 1 <= C, T <= 2^20");
-    RFI_REQUIRE((double)n_planes * c * t <= 4.0e9, std::string(who) + ": stack too large for one call");
-}
-void check_st_config(const rfi_sumthreshold_config* cfg) {
-    RFI_REQUIRE(cfg, "sumthreshold: null config");
-    RFI_REQUIRE(cfg->iterations >= 1 && cfg->iterations <= 64, "sumthreshold: iterations must be in 1 .. 64");
-    RFI_REQUIRE(cfg->levels >= 1 && cfg->levels <= 8, "sumthreshold: levels must be in 1 .. 8");
-    RFI_REQUIRE(cfg->rho > 1.0 && cfg->rho <= 1.0e6, "sumthreshold: rho must be > 1");
-    RFI_REQUIRE(cfg->base_sensitivity > 0.0 && cfg->chi_1 > 0.0, "sumthreshold: base_sensitivity and chi_1 must be > 0");
-    RFI_REQUIRE(cfg->half_t >= 0 && cfg->half_f >= 0 && cfg->half_t <= (1 << 20) && cfg->half_f <= (1 << 20),
-                "sumthreshold: half widths must be in 0 .. 2^20");
-    RFI_REQUIRE(cfg->sir_q >= 0 && cfg->sir_q <= 1023, "sumthreshold: sir_q must be in 0 .. 1023");
-}
-bool mem_ok(int mem) { return mem == RFI_HOST || mem == RFI_DEVICE; }
-}  // namespace
-
-int rfi_sumthreshold_ladder(const rfi_sumthreshold_config* cfg, double sigma, int iteration, double* chi_out) {
-    return guarded([&] {
-        check_st_config(cfg);
-        RFI_REQUIRE(chi_out, "sumthreshold_ladder: null output");
-        RFI_REQUIRE(iteration >= 0 && iteration < cfg->iterations, "sumthreshold_ladder: iteration out of range");
-        sumthreshold_ladder_host(*cfg, sigma, iteration, chi_out);
-    });
-}
-int rfi_sumthreshold_pass(rfi_ctx* ctx, const float* values, int values_mem, const uint8_t* flags_in, int flags_mem, int n_planes,
-                          int c, int t, int window, int axis, const double* threshold_host, const double* center_host,
-                          uint8_t* flags_out, int out_mem) {
-    return guarded([&] {
-        RFI_REQUIRE(ctx, "sumthreshold_pass: null context");
-        check_st_planes("sumthreshold_pass", n_planes, c, t);
-        RFI_REQUIRE(window >= 1 && window <= st_max_window() && (window & (window - 1)) == 0,
-                    "sumthreshold_pass: window must be a power of two in 1 .. 128");
-        RFI_REQUIRE(axis == 0 || axis == 1, "sumthreshold_pass: axis must be 0 (frequency) or 1 (time)");
-        RFI_REQUIRE(mem_ok(values_mem) && mem_ok(flags_mem) && mem_ok(out_mem), "sumthreshold_pass: bad memory kind");
-        if (n_planes == 0) return;
-        RFI_REQUIRE(values && flags_in && flags_out && threshold_host && center_host, "sumthreshold_pass: null argument");
-        ctx->activate();
-        const size_t n = (size_t)n_planes * c * t;
-        CallScope sc(ctx);
-        const float* x = sc.in(values, values_mem, n);
-        const uint8_t* fi = sc.in(flags_in, flags_mem, n);
-        uint8_t* fo = sc.out(flags_out, out_mem, n);
-        RFI_REQUIRE(fi != fo, "sumthreshold_pass: flags_in and flags_out must be different buffers");
-        if (window > (axis == 1 ? t : c)) {
-            RFI_CHECK_HIP(hipMemcpyAsync(fo, fi, n, hipMemcpyDeviceToDevice, ctx->stream));
-        } else {
-            const double* th = sc.in(threshold_host, RFI_HOST, (size_t)n_planes);
-            const double* ce = sc.in(center_host, RFI_HOST, (size_t)n_planes);
-            launch_st_pass(ctx, x, nullptr, fi, fo, n_planes, c, t, window, axis, ce, th, 1, nullptr, 0);
-        }
-        sc.finish();
-    });
-}
-int rfi_masked_smooth(rfi_ctx* ctx, const float* values, int values_mem, const uint8_t* flags, int flags_mem, int n_planes, int c,
-                      int t, const double* weights_t_host, int half_t, const double* weights_f_host, int half_f, float* out,
-                      int out_mem) {
-    return guarded([&] {
-        RFI_REQUIRE(ctx, "masked_smooth: null context");
-        check_st_planes("masked_smooth", n_planes, c, t);
-        RFI_REQUIRE(half_t >= 0 && half_f >= 0 && half_t <= (1 << 20) && half_f <= (1 << 20), "masked_smooth: half widths must be in 0 .. 2^20");
-        RFI_REQUIRE(mem_ok(values_mem) && mem_ok(flags_mem) && mem_ok(out_mem), "masked_smooth: bad memory kind");
-        if (n_planes == 0) return;
-        RFI_REQUIRE(values && flags && out && weights_t_host && weights_f_host, "masked_smooth: null argument");
-        ctx->activate();
-        const size_t n = (size_t)n_planes * c * t;
-        CallScope sc(ctx);
-        const float* x = sc.in(values, values_mem, n);
-        const uint8_t* f = sc.in(flags, flags_mem, n);
-        float* b = sc.out(out, out_mem, n);
-        const double* wt = sc.in(weights_t_host, RFI_HOST, (size_t)2 * half_t + 1);
-        const double* wf = sc.in(weights_f_host, RFI_HOST, (size_t)2 * half_f + 1);
-        launch_st_smooth(ctx, x, f, n_planes, c, t, wt, half_t, wf, half_f, sc.temp<double>(2 * n), b);
-        sc.finish();
-    });
-}
-int rfi_sir_operator(rfi_ctx* ctx, const uint8_t* flags_in, int flags_mem, int n_planes, int c, int t, int axis, int q,
-                     uint8_t* flags_out, int out_mem) {
-    return guarded([&] {
-        RFI_REQUIRE(ctx, "sir_operator: null context");
-        check_st_planes("sir_operator", n_planes, c, t);
-        RFI_REQUIRE(axis == 0 || axis == 1, "sir_operator: axis must be 0 (frequency) or 1 (time)");
-        RFI_REQUIRE(q >= 0 && q <= 1023, "sir_operator: q must be in 0 .. 1023");
-        RFI_REQUIRE(mem_ok(flags_mem) && mem_ok(out_mem), "sir_operator: bad memory kind");
-        if (n_planes == 0) return;
-        RFI_REQUIRE(flags_in && flags_out, "sir_operator: null argument");
-        ctx->activate();
-        const size_t n = (size_t)n_planes * c * t;
-        CallScope sc(ctx);
-        const uint8_t* fi = sc.in(flags_in, flags_mem, n);
-        uint8_t* fo = sc.out(flags_out, out_mem, n);
-        if (q == 0) {
-            if (fi != fo) RFI_CHECK_HIP(hipMemcpyAsync(fo, fi, n, hipMemcpyDeviceToDevice, ctx->stream));
-        } else {
-            launch_st_sir(ctx, fi, fo, n_planes, c, t, axis, q, sc.temp<int>(n));
-        }
-        sc.finish();
-    });
-}
-// Chunks of k whole planes in the context's scratch: [weights | state | X | B | Fa | Fb | N1 D1 | staged data | staged prior].
-// Host data and prior are uploaded per chunk and the chunk's flags copied back, all on the context's stream; device
-// buffers are used in place.
-int rfi_sumthreshold_flag(rfi_ctx* ctx, const void* data, int data_mem, int dtype, const uint8_t* prior, int prior_mem, int n_planes,
-                          int c, int t, const rfi_sumthreshold_config* cfg, const double* weights_t_host,
-                          const double* weights_f_host, uint8_t* flags_out, int out_mem) {
-    return guarded([&] {
-        RFI_REQUIRE(ctx, "sumthreshold_flag: null context");
-        RFI_REQUIRE(dtype >= RFI_C128 && dtype <= RFI_F32, "sumthreshold_flag: dtype must be complex128, complex64, float64 or float32");
-        check_st_planes("sumthreshold_flag", n_planes, c, t);
-        check_st_config(cfg);
-        RFI_REQUIRE(mem_ok(data_mem) && (!prior || mem_ok(prior_mem)) && mem_ok(out_mem), "sumthreshold_flag: bad memory kind");
-        if (n_planes == 0) return;
-        RFI_REQUIRE(data && flags_out && weights_t_host && weights_f_host, "sumthreshold_flag: null argument");
-        ctx->activate();
-        const size_t esz = dtype == RFI_C128 ? 16 : (dtype == RFI_F32 ? 4 : 8);
-        const size_t px = (size_t)c * t;
-        const bool host_in = data_mem == RFI_HOST, host_pr = prior && prior_mem == RFI_HOST, host_out = out_mem == RFI_HOST;
-        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-        const size_t nwt = (size_t)2 * cfg->half_t + 1, nwf = (size_t)2 * cfg->half_f + 1;
-        const size_t b_w = al(nwt * 8) + al(nwf * 8);
-        const size_t per_plane = px * (26 + (host_in ? esz : 0) + (host_pr ? 1 : 0)) + st_state_bytes(1);
-        const size_t slack = 8 * 256;                                      // the alignment of the eight regions
-        RFI_REQUIRE(b_w + slack + per_plane <= kFlagBudget,
-                    "sumthreshold_flag: one " + std::to_string(c) + " x " + std::to_string(t) + " plane needs " +
-                        std::to_string(per_plane >> 20) + " MiB of workspace, over the budget of " +
-                        std::to_string(kFlagBudget >> 20) + " MiB; planes are not split");
-        const int k = (int)std::min<size_t>((size_t)n_planes, (kFlagBudget - b_w - slack) / per_plane);
-        const size_t kn = (size_t)k * px;
-        const size_t b_state = al(st_state_bytes(k)), b_x = al(kn * 4), b_f = al(kn), b_nd = al(kn * 16);
-        const size_t b_in = host_in ? al(kn * esz) : 0, b_pr = host_pr ? al(kn) : 0;
-        char* base = static_cast<char*>(ctx->get_scratch(b_w + b_state + 2 * b_x + 2 * b_f + b_nd + b_in + b_pr));
-        double* d_wt = reinterpret_cast<double*>(base);
-        double* d_wf = reinterpret_cast<double*>(base + al(nwt * 8));
-        char* p = base + b_w;
-        void* d_state = p; p += b_state;
-        float* d_x = reinterpret_cast<float*>(p); p += b_x;
-        float* d_b = reinterpret_cast<float*>(p); p += b_x;
-        uint8_t* d_fa = reinterpret_cast<uint8_t*>(p); p += b_f;
-        uint8_t* d_fb = reinterpret_cast<uint8_t*>(p); p += b_f;
-        double* d_nd = reinterpret_cast<double*>(p); p += b_nd;
-        char* d_in = p; p += b_in;
-        uint8_t* d_pr = reinterpret_cast<uint8_t*>(p);
-        RFI_CHECK_HIP(hipMemcpyAsync(d_wt, weights_t_host, nwt * 8, hipMemcpyHostToDevice, ctx->stream));
-        RFI_CHECK_HIP(hipMemcpyAsync(d_wf, weights_f_host, nwf * 8, hipMemcpyHostToDevice, ctx->stream));
-        struct Drain {            // a failure part way leaves no work in flight on buffers the caller owns
-            rfi_ctx* c; bool armed;
-            ~Drain() { if (armed) (void)hipStreamSynchronize(c->stream); }
-        } drain{ctx, true};
-        const char* src = static_cast<const char*>(data);
-        for (int p0 = 0; p0 < n_planes; p0 += k) {
-            const int np = std::min(k, n_planes - p0);
-            const size_t off = (size_t)p0 * px, cn = (size_t)np * px;
-            const void* in = src + off * esz;
-            const uint8_t* pr = prior ? prior + off : nullptr;
-            if (host_in) {
-                RFI_CHECK_HIP(hipMemcpyAsync(d_in, in, cn * esz, hipMemcpyHostToDevice, ctx->stream));
-                in = d_in;
-            }
-            if (host_pr) {
-                RFI_CHECK_HIP(hipMemcpyAsync(d_pr, pr, cn, hipMemcpyHostToDevice, ctx->stream));
-                pr = d_pr;
-            }
-            uint8_t* out = host_out ? d_fa : flags_out + off;
-            launch_sumthreshold_flag(ctx, in, dtype, pr, np, c, t, *cfg, d_wt, d_wf, d_x, d_b, d_fa, d_fb, d_nd, d_state, out);
-            if (host_out) RFI_CHECK_HIP(hipMemcpyAsync(flags_out + off, out, cn, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        if (host_in || host_pr || host_out) RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-        drain.armed = false;
-    });
-}
-// ---- CASA-style baseline flaggers (casa_flaggers.hip)
-namespace {
-// Groups of k whole planes in the context's scratch: [workspace of the launch | staged data | staged prior | staged extras].
-// Host buffers are uploaded per group and the group's flags copied out, all on the context's stream; device buffers are
-// used in place.  ws(k): workspace bytes of k planes (at most k ws(1)); extra_doubles: per-plane doubles of up to two optional
-// host arrays (timedev, freqdev) that travel with the group; run(in, prior, first plane, planes, ws, extras) -> the flags.
-using GroupWs = std::function<size_t(int)>;
-using GroupRun = std::function<const uint8_t*(const void*, const uint8_t*, int, void*, const double* const*)>;
-void flag_in_groups(rfi_ctx* ctx, const std::string& who, const void* data, int data_mem, size_t esz, const uint8_t* prior, int prior_mem,
-                    int n_planes, size_t px, const double* const extra_host[2], const size_t extra_doubles[2], uint8_t* flags_out,
-                    int out_mem, const GroupWs& ws, const GroupRun& run) {
-    const bool host_in = data_mem == RFI_HOST, host_pr = prior && prior_mem == RFI_HOST, host_out = out_mem == RFI_HOST;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    size_t ex[2];
-    for (int e = 0; e < 2; ++e) ex[e] = extra_host[e] ? extra_doubles[e] * 8 : 0;
-    const size_t per_plane = ws(1) + (host_in ? al(px * esz) : 0) + (host_pr ? al(px) : 0) + al(ex[0]) + al(ex[1]);
-    RFI_REQUIRE(per_plane <= kFlagBudget, who + ": one plane needs " + std::to_string(per_plane >> 20) +
-                                              " MiB of workspace, over the budget of " + std::to_string(kFlagBudget >> 20) +
-                                              " MiB; planes are not split");
-    const int k = (int)std::min<size_t>((size_t)n_planes, kFlagBudget / per_plane);
-    const size_t kn = (size_t)k * px;
-    const size_t b_ws = al(ws(k)), b_in = host_in ? al(kn * esz) : 0, b_pr = host_pr ? al(kn) : 0;
-    const size_t b_e0 = al(ex[0] * k), b_e1 = al(ex[1] * k);
-    char* base = static_cast<char*>(ctx->get_scratch(b_ws + b_in + b_pr + b_e0 + b_e1));
-    char* d_in = base + b_ws;
-    uint8_t* d_pr = reinterpret_cast<uint8_t*>(d_in + b_in);
-    double* d_ex[2] = {reinterpret_cast<double*>(d_in + b_in + b_pr), reinterpret_cast<double*>(d_in + b_in + b_pr + b_e0)};
-    struct Drain {            // a failure part way leaves no work in flight on buffers the caller owns
-        rfi_ctx* c; bool armed;
-        ~Drain() { if (armed) (void)hipStreamSynchronize(c->stream); }
-    } drain{ctx, true};
-    const char* src = static_cast<const char*>(data);
-    for (int p0 = 0; p0 < n_planes; p0 += k) {
-        const int np = std::min(k, n_planes - p0);
-        const size_t off = (size_t)p0 * px, cn = (size_t)np * px;
-        const void* in = src + off * esz;
-        const uint8_t* pr = prior ? prior + off : nullptr;
-        if (host_in) {
-            RFI_CHECK_HIP(hipMemcpyAsync(d_in, in, cn * esz, hipMemcpyHostToDevice, ctx->stream));
-            in = d_in;
-        }
-        if (host_pr) {
-            RFI_CHECK_HIP(hipMemcpyAsync(d_pr, pr, cn, hipMemcpyHostToDevice, ctx->stream));
-            pr = d_pr;
-        }
-        const double* extras[2] = {nullptr, nullptr};
-        for (int e = 0; e < 2; ++e)
-            if (extra_host[e]) {
-                RFI_CHECK_HIP(hipMemcpyAsync(d_ex[e], extra_host[e] + (size_t)p0 * extra_doubles[e], (size_t)np * ex[e],
-                                             hipMemcpyHostToDevice, ctx->stream));
-                extras[e] = d_ex[e];
-            }
-        const uint8_t* res = run(in, pr, np, static_cast<void*>(base), extras);
-        RFI_CHECK_HIP(hipMemcpyAsync(flags_out + off, res, cn, host_out ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    if (host_in || host_pr || host_out || extra_host[0] || extra_host[1]) RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    drain.armed = false;
-}
-const double* const kNoExtras[2] = {nullptr, nullptr};
-const size_t kNoExtraSizes[2] = {0, 0};
-bool in_range(double v, double lo, double hi) { return v >= lo && v <= hi; }      // (false for NaN)
-}  // namespace
-
-int rfi_tfcrop_flag(rfi_ctx* ctx, const void* data, int data_mem, int dtype, const uint8_t* prior, int prior_mem, int n_planes, int c,
-                    int t, const rfi_tfcrop_config* cfg, uint8_t* flags_out, int out_mem) {
-    return guarded([&] {
-        RFI_REQUIRE(ctx, "tfcrop_flag: null context");
-        RFI_REQUIRE(dtype >= RFI_C128 && dtype <= RFI_F32, "tfcrop_flag: dtype must be complex128, complex64, float64 or float32");
-        check_st_planes("tfcrop_flag", n_planes, c, t);
-        RFI_REQUIRE(cfg, "tfcrop_flag: null config");
-        RFI_REQUIRE(cfg->ntime >= 1, "tfcrop_flag: ntime must be >= 1");
-        RFI_REQUIRE((cfg->timefit == 0 || cfg->timefit == 1) && (cfg->freqfit == 0 || cfg->freqfit == 1),
-                    "tfcrop_flag: timefit and freqfit must be 0 (line) or 1 (poly)");
-        RFI_REQUIRE(cfg->maxnpieces >= 1, "tfcrop_flag: maxnpieces must be >= 1");
-        RFI_REQUIRE(cfg->flagdimension >= RFI_TFCROP_FREQTIME && cfg->flagdimension <= RFI_TFCROP_FREQ, "tfcrop_flag: bad flagdimension");
-        RFI_REQUIRE(in_range(cfg->timecutoff, 0.0, 1.0e300) && in_range(cfg->freqcutoff, 0.0, 1.0e300), "tfcrop_flag: cutoffs must be >= 0");
-        RFI_REQUIRE(mem_ok(data_mem) && (!prior || mem_ok(prior_mem)) && mem_ok(out_mem), "tfcrop_flag: bad memory kind");
-        if (n_planes == 0) return;
-        RFI_REQUIRE(data && flags_out, "tfcrop_flag: null argument");
-        ctx->activate();
-        rfi_tfcrop_config cf = *cfg;
-        cf.ntime = std::min(cf.ntime, t);
-        const size_t esz = dtype == RFI_C128 ? 16 : (dtype == RFI_F32 ? 4 : 8);
-        flag_in_groups(ctx, "tfcrop_flag", data, data_mem, esz, prior, prior_mem, n_planes, (size_t)c * t, kNoExtras, kNoExtraSizes, flags_out,
-                       out_mem, [&](int k) { return tfcrop_ws_bytes(k, c, t, cf.ntime); },
-                       [&](const void* in, const uint8_t* pr, int np, void* ws, const double* const*) {
-                           return launch_tfcrop_flag(ctx, in, dtype, pr, np, c, t, cf, ws);
-                       });
-    });
-}
-int rfi_rflag_flag(rfi_ctx* ctx, const void* data, int data_mem, int dtype, const uint8_t* prior, int prior_mem, int n_planes, int c,
-                   int t, const rfi_rflag_config* cfg, const double* timedev_host, const double* freqdev_host, uint8_t* flags_out,
-                   int out_mem) {
-    return guarded([&] {
-        RFI_REQUIRE(ctx, "rflag_flag: null context");
-        RFI_REQUIRE(dtype == RFI_C128 || dtype == RFI_C64, "rflag_flag: dtype must be complex128 or complex64");
-        check_st_planes("rflag_flag", n_planes, c, t);
-        RFI_REQUIRE(cfg, "rflag_flag: null config");
-        RFI_REQUIRE(cfg->ntime >= 1, "rflag_flag: ntime must be >= 1");
-        RFI_REQUIRE(cfg->winsize >= 1 && cfg->winsize % 2 == 1, "rflag_flag: winsize must be odd and >= 1");
-        RFI_REQUIRE(in_range(cfg->timedevscale, 0.0, 1.0e300) && in_range(cfg->freqdevscale, 0.0, 1.0e300), "rflag_flag: scales must be >= 0");
-        RFI_REQUIRE(mem_ok(data_mem) && (!prior || mem_ok(prior_mem)) && mem_ok(out_mem), "rflag_flag: bad memory kind");
-        if (n_planes == 0) return;
-        RFI_REQUIRE(data && flags_out, "rflag_flag: null argument");
-        ctx->activate();
-        rfi_rflag_config cf = *cfg;
-        cf.ntime = std::min(cf.ntime, t);
-        const double* const extras[2] = {timedev_host, freqdev_host};
-        const size_t sizes[2] = {(size_t)c, 1};
-        flag_in_groups(ctx, "rflag_flag", data, data_mem, dtype == RFI_C128 ? 16 : 8, prior, prior_mem, n_planes, (size_t)c * t, extras, sizes,
-                       flags_out, out_mem, [&](int k) { return rflag_ws_bytes(k, c, t, cf.ntime); },
-                       [&](const void* in, const uint8_t* pr, int np, void* ws, const double* const* ex) {
-                           return launch_rflag_flag(ctx, in, dtype, pr, np, c, t, cf, ex[0], ex[1], ws);
-                       });
-    });
-}
-int rfi_extend_flags(rfi_ctx* ctx, const uint8_t* flags_in, int flags_mem, int n_planes, int c, int t, const rfi_extend_config* cfg,
-                     uint8_t* flags_out, int out_mem) {
-    return guarded([&] {
-        RFI_REQUIRE(ctx, "extend_flags: null context");
-        check_st_planes("extend_flags", n_planes, c, t);
-        RFI_REQUIRE(cfg, "extend_flags: null config");
-        RFI_REQUIRE(cfg->ntime >= 1, "extend_flags: ntime must be >= 1");
-        RFI_REQUIRE(in_range(cfg->growtime, 0.0, 100.0) && in_range(cfg->growfreq, 0.0, 100.0),
-                    "extend_flags: growtime and growfreq must be in 0 .. 100");
-        RFI_REQUIRE(mem_ok(flags_mem) && mem_ok(out_mem), "extend_flags: bad memory kind");
-        if (n_planes == 0) return;
-        RFI_REQUIRE(flags_in && flags_out, "extend_flags: null argument");
-        ctx->activate();
-        rfi_extend_config cf = *cfg;
-        cf.ntime = std::min(cf.ntime, t);
-        flag_in_groups(ctx, "extend_flags", flags_in, flags_mem, 1, nullptr, RFI_HOST, n_planes, (size_t)c * t, kNoExtras, kNoExtraSizes,
-                       flags_out, out_mem, [&](int k) { return extend_ws_bytes(k, c, t); },
-                       [&](const void* in, const uint8_t*, int np, void* ws, const double* const*) {
-                           return launch_extend_flags(ctx, static_cast<const uint8_t*>(in), np, c, t, cf, ws);
-                       });
     });
 }
 int rfi_op_fpn_merge(rfi_ctx* ctx, const float* lateral, const float* top, int n, int h, int w, int c, float* out) {

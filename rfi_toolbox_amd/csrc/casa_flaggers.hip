@@ -20,6 +20,7 @@
 #include <utility>
 
 #include "kernels.hpp"
+#include "launch_common.hpp"
 #include "select_common.hpp"
 
 namespace rfi {
@@ -29,12 +30,6 @@ constexpr int kBlock = 256;
 constexpr int kLane = 64;                   // fit and selection kernels: one wave per workgroup
 constexpr int kTile = 32;                   // transpose tile
 constexpr int kFitIterations = 5;
-
-unsigned grid_of(int64_t blocks, const char* what) {
-    RFI_REQUIRE(blocks >= 1 && blocks <= 0x7fffffff, std::string(what) + ": too many workgroups for one launch");
-    return (unsigned)blocks;
-}
-size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // ---- (planes, R, S) -> (planes, S, R)
 template <typename T>
@@ -439,15 +434,6 @@ __global__ __launch_bounds__(kBlock) void ex_near_kernel(const uint8_t* __restri
     }
     Fout[i] = f ? 1 : 0;
 }
-
-struct Carve {                                              // consecutive 256-byte aligned regions of one workspace
-    char* p;
-    template <typename T> T* take(size_t count) {
-        T* r = reinterpret_cast<T*>(p);
-        p += al(count * sizeof(T));
-        return r;
-    }
-};
 
 }  // namespace
 

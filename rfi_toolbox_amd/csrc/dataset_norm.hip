@@ -23,6 +23,7 @@
 // Apply.  A lane owns one pixel: it reads the pixel's 8 scalars (8 planes, 4 complex planes, or 8 contiguous),
 // forms (double(x) - centre) / scale in fp64, rounds once to float32 and writes 8 planes or 32 contiguous bytes.
 #include "kernels.hpp"
+#include "select_common.hpp"
 
 namespace rfi {
 namespace {
@@ -37,20 +38,6 @@ constexpr int kSuper = 16;                       // wave tiles per partial sum
 constexpr int kSumTile = kWaveTile * kSuper;     // scalars per partial sum
 constexpr int kMaxBlocks = 2048;                 // 8 workgroups per CU on 256 CUs
 
-typedef unsigned long long u64;
-
-__device__ __forceinline__ unsigned okey(float f) {
-    const unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ u64 okey(double f) {
-    const u64 u = (u64)__double_as_longlong(f);
-    return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ float unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-__device__ __forceinline__ double unkey(u64 k) {
-    return __longlong_as_double((long long)((k & 0x8000000000000000ull) ? (k & 0x7fffffffffffffffull) : ~k));
-}
 template <typename T> struct KeyOf;
 template <> struct KeyOf<float> { typedef unsigned K; static constexpr int bits = 32; };
 template <> struct KeyOf<double> { typedef u64 K; static constexpr int bits = 64; };

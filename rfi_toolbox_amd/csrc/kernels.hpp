@@ -358,8 +358,8 @@ void launch_augment(rfi_ctx* ctx, const float* x, const uint8_t* y, int n, int h
 //            = leave the plane alone; B (optional) is subtracted from X in float32 first
 //   st_smooth: wt / wf device tables of 2 h + 1 doubles; nd: workspace of 2 n doubles (n = planes C T)
 //   st_sir: q = 1 .. 1023; ws: n ints; F_in may equal F_out
-//   sumthreshold_flag: the whole pipeline; X, B n floats, Fa, Fb n bytes, nd 2 n doubles, state st_state_bytes(planes); the
-//            flags end in `out` (n bytes).  Nothing is read back.
+//   sumthreshold_flag: the whole pipeline, by the workspace convention of the flaggers below; wt / wf as for st_smooth.  The
+//            flags end in `dst` (device memory) or, when dst is null, inside ws; returns where.  Nothing is read back.
 void sumthreshold_ladder_host(const rfi_sumthreshold_config& cfg, double sigma, int iteration, double* chi);
 size_t st_state_bytes(int planes);
 int st_max_window();
@@ -368,12 +368,14 @@ void launch_st_pass(rfi_ctx* ctx, const float* X, const float* B, const uint8_t*
 void launch_st_smooth(rfi_ctx* ctx, const float* X, const uint8_t* F, int planes, int C, int T, const double* wt, int ht,
                       const double* wf, int hf, double* nd, float* B);
 void launch_st_sir(rfi_ctx* ctx, const uint8_t* Fin, uint8_t* Fout, int planes, int C, int T, int axis, int q, int* ws);
-void launch_sumthreshold_flag(rfi_ctx* ctx, const void* src, int dtype, const uint8_t* prior, int planes, int C, int T,
-                              const rfi_sumthreshold_config& cfg, const double* wt, const double* wf, float* X, float* B, uint8_t* Fa,
-                              uint8_t* Fb, double* nd, void* state, uint8_t* out);
-// CASA-style baseline flaggers (casa_flaggers.hip; semantics in include/rfi_hip.h, "CASA-style baseline flaggers").  Each launch
-// works on `planes` device-resident planes inside a workspace of *_ws_bytes and returns the buffer inside it that holds the
-// flags (0 / 1 bytes); cfg.ntime is in 1 .. T.  timedev (planes C doubles) / freqdev (planes doubles): device pointers or null.
+size_t sumthreshold_ws_bytes(int planes, int C, int T);
+uint8_t* launch_sumthreshold_flag(rfi_ctx* ctx, const void* src, int dtype, const uint8_t* prior, int planes, int C, int T,
+                                  const rfi_sumthreshold_config& cfg, const double* wt, const double* wf, void* ws, uint8_t* dst);
+// CASA-style baseline flaggers (casa_flaggers.hip; semantics in include/rfi_hip.h, "CASA-style baseline flaggers").  The
+// workspace convention of every baseline flagger: a launch works on `planes` device-resident planes inside one workspace `ws`
+// of *_ws_bytes(planes, ...) bytes (at most planes times the bytes of one plane), carves it with Carve (launch_common.hpp)
+// and returns the buffer that holds the flags (0 / 1 bytes).  cfg.ntime is in 1 .. T.  timedev (planes C doubles) / freqdev
+// (planes doubles): device pointers or null.
 void launch_st_prepare(rfi_ctx* ctx, const void* src, int dtype, const uint8_t* prior, int64_t n, float* X, uint8_t* F);
 size_t tfcrop_ws_bytes(int planes, int C, int T, int ntime);
 uint8_t* launch_tfcrop_flag(rfi_ctx* ctx, const void* src, int dtype, const uint8_t* prior, int planes, int C, int T,

@@ -1,5 +1,5 @@
-// Device helpers shared by the exact order-statistic kernels (flag_stats.hip, sumthreshold.hip): the order-preserving
-// integer image of a float for radix selection, and |z| as NumPy computes it.
+// Device helpers shared by the exact order-statistic kernels (flag_stats.hip, dataset_norm.hip, sumthreshold.hip,
+// casa_flaggers.hip): the order-preserving integer image of a float for radix selection, and |z| as NumPy computes it.
 #pragma once
 #include <hip/hip_runtime.h>
 

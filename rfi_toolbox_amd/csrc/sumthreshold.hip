@@ -22,6 +22,7 @@
 #include <utility>
 
 #include "kernels.hpp"
+#include "launch_common.hpp"
 #include "select_common.hpp"
 
 namespace rfi {
@@ -386,11 +387,6 @@ __global__ __launch_bounds__(kBlock) void st_sir_kernel(const uint8_t* Fin, uint
     }
 }
 
-unsigned grid_of(int64_t blocks, const char* what) {
-    RFI_REQUIRE(blocks >= 1 && blocks <= 0x7fffffff, std::string(what) + ": too many workgroups for one launch");
-    return (unsigned)blocks;
-}
-
 unsigned* hist_of(void* state, int planes) { return reinterpret_cast<unsigned*>(static_cast<StPlane*>(state) + planes); }
 
 }  // namespace
@@ -403,8 +399,7 @@ size_t st_state_bytes(int planes) { return (size_t)planes * (sizeof(StPlane) + 2
 int st_max_window() { return kMaxWindow; }
 
 void launch_st_prepare(rfi_ctx* ctx, const void* src, int dtype, const uint8_t* prior, int64_t n, float* X, uint8_t* F) {
-    const size_t esz = dtype == RFI_C128 ? 16 : (dtype == RFI_F32 ? 4 : 8);
-    ProfScope ps(ctx, FAM_METRICS, 0, (double)n * (esz + (prior ? 1 : 0) + 5), "st_prepare");
+    ProfScope ps(ctx, FAM_METRICS, 0, (double)n * (dtype_bytes(dtype) + (prior ? 1 : 0) + 5), "st_prepare");
     const dim3 g(grid_of(cdiv(n, kBlock), "sumthreshold prepare")), b(kBlock);
     switch (dtype) {
         case RFI_C128: hipLaunchKernelGGL(st_prepare_kernel<RFI_C128>, g, b, 0, ctx->stream, src, prior, n, X, F); break;
@@ -474,12 +469,22 @@ void launch_st_sir(rfi_ctx* ctx, const uint8_t* Fin, uint8_t* Fout, int planes, 
     check_launch("st_sir");
 }
 
-// the whole pipeline on `planes` device-resident planes.  X, B: n floats; Fa, Fb: n bytes; nd: 2 n doubles; state:
-// st_state_bytes(planes); wt / wf: device weight tables.  The flags end in `out` (n bytes; may be Fa or Fb).
-void launch_sumthreshold_flag(rfi_ctx* ctx, const void* src, int dtype, const uint8_t* prior, int planes, int C, int T,
-                              const rfi_sumthreshold_config& cfg, const double* wt, const double* wf, float* X, float* B, uint8_t* Fa,
-                              uint8_t* Fb, double* nd, void* state, uint8_t* out) {
+// the whole pipeline on `planes` device-resident planes.  Workspace: the state records, X and B floats, Fa and Fb bytes and
+// the (N1, D1) doubles of n = planes C T samples; wt / wf: device weight tables.  The flags end in `dst` (n bytes of device
+// memory), or in a buffer inside ws when dst is null; returns where.
+size_t sumthreshold_ws_bytes(int planes, int C, int T) {
+    const size_t n = (size_t)planes * C * T;
+    return al(st_state_bytes(planes)) + 2 * al(n * 4) + 2 * al(n) + al(n * 16);
+}
+uint8_t* launch_sumthreshold_flag(rfi_ctx* ctx, const void* src, int dtype, const uint8_t* prior, int planes, int C, int T,
+                                  const rfi_sumthreshold_config& cfg, const double* wt, const double* wf, void* ws, uint8_t* dst) {
     const int64_t px = (int64_t)C * T, n = planes * px;
+    Carve cv{static_cast<char*>(ws)};
+    void* state = cv.take<char>(st_state_bytes(planes));
+    float *X = cv.take<float>(n), *B = cv.take<float>(n);
+    uint8_t *Fa = cv.take<uint8_t>(n), *Fb = cv.take<uint8_t>(n);
+    double* nd = cv.take<double>(2 * n);
+    uint8_t* out = dst ? dst : Fa;
     RFI_CHECK_HIP(hipMemsetAsync(state, 0, st_state_bytes(planes), ctx->stream));
     RFI_CHECK_HIP(hipMemsetAsync(B, 0, (size_t)n * sizeof(float), ctx->stream));
     launch_st_prepare(ctx, src, dtype, prior, n, X, Fa);
@@ -505,6 +510,7 @@ void launch_sumthreshold_flag(rfi_ctx* ctx, const void* src, int dtype, const ui
     } else if (out != cur) {
         RFI_CHECK_HIP(hipMemcpyAsync(out, cur, (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
     }
+    return out;
 }
 
 }  // namespace rfi

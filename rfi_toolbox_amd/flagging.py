@@ -61,12 +61,13 @@ def _shape(x):
 
 
 def _check_planes(name, x):
+    """-> (shape, number of planes) of a (..., C, T) stack."""
     shape = _shape(x)
     if len(shape) < 2:
         raise ValueError(f"{name} must have shape (..., C, T) with ndim >= 2, got shape {shape}")
     if not 1 <= shape[-2] <= MAX_AXIS or not 1 <= shape[-1] <= MAX_AXIS:
         raise ValueError(f"{name}: C and T must be in 1 .. 2^20, got {shape[-2]} x {shape[-1]}")
-    return shape
+    return shape, int(np.prod(shape[:-2], dtype=np.int64))
 
 
 def _check_flags(flags, shape):
@@ -140,6 +141,61 @@ def _doubles(a):
     return a, a.ctypes.data_as(C.POINTER(C.c_double))
 
 
+def _run_stage(fn, inputs, shape, planes, args, result_dtype, device):
+    """The shared tail of the three stage functions: fn(context, pointer and memory kind of every (array, dtype) of
+    `inputs`, planes, C, T, *args, result pointer, HOST) into a new NumPy array of `shape`."""
+    out = np.empty(shape, result_dtype)
+    if planes:
+        ctx = _context(device, *(x for x, _ in inputs))
+        held = [_pointer(x, dt, ctx) for x, dt in inputs]
+        check(fn(ctx.handle, *(a for p, mem, _ in held for a in (C.c_void_p(p), mem)), planes, shape[-2], shape[-1], *args,
+                 C.c_void_p(out.ctypes.data), HOST))
+    return out
+
+
+def _check_data(data, flags, out, codes):
+    """-> (shape, number of planes, dtype) after the checks the flaggers share (`flags` may be None)."""
+    shape, planes = _check_planes("data", data)
+    dt = _np_dtype(data)
+    if dt is None or np.dtype(dt) not in codes:
+        raise ValueError(f"data must be one of {', '.join(str(c) for c in codes)}, got {dt}")
+    if flags is not None:
+        _check_flags(flags, shape)
+    if out not in ("host", "device"):
+        raise ValueError(f"out must be 'host' or 'device', got {out!r}")
+    return shape, planes, np.dtype(dt)
+
+
+def _run_flagger(call, data, dt, flags, shape, planes, out, device):
+    """The shared tail of the four flaggers: pointers, the result buffer of `out`, then call(ctx, data pointer and
+    memory kind, prior pointer and kind, result pointer and kind)."""
+    ctx = _context(device, data, flags)
+    dp, dm, k1 = _pointer(data, dt, ctx)
+    fp, fm, k2 = _pointer(flags, np.uint8, ctx) if flags is not None else (None, HOST, None)
+    cuda_in = is_torch(data) and data.is_cuda
+    if out == "device":
+        res = ctx.empty(shape, np.uint8)
+        rp, rm = res.ptr, DEVICE
+    elif cuda_in:
+        res = torch.empty(shape, dtype=torch.uint8, device=data.device)
+        torch.cuda.current_stream(data.device).synchronize()        # (the output's memory may have just been freed)
+        rp, rm = res.data_ptr(), DEVICE
+    else:
+        res = np.empty(shape, np.uint8)
+        rp, rm = res.ctypes.data, HOST
+    if planes:
+        check(call(ctx, C.c_void_p(dp), dm, C.c_void_p(fp) if fp else None, fm, C.c_void_p(rp), rm))
+    if out == "device":
+        res._keep = (k1, k2)             # the inputs may still be read by work in flight: they live as long as the result
+        return res
+    if cuda_in:
+        ctx.synchronize()
+        del k1, k2
+        return res.view(torch.bool)
+    del k1, k2
+    return res.view(bool)
+
+
 # ---------------------------------------------------------------------------------------------- the three stages
 def sumthreshold_pass(values, flags, window, threshold, center=0.0, axis=-1, device=None) -> np.ndarray:
     """One SumThreshold pass: ``flags | (the samples of every window of `window` consecutive samples along `axis`
@@ -148,73 +204,50 @@ def sumthreshold_pass(values, flags, window, threshold, center=0.0, axis=-1, dev
     ``values`` (..., C, T) real, ``flags`` of the same shape; ``window`` a power of two up to 128 (a window longer than
     the line changes nothing); ``threshold`` and ``center`` scalars or one value per plane.  Returns NumPy bool.
     """
-    shape = _check_planes("values", values)
+    shape, planes = _check_planes("values", values)
     values = _real_values("values", values)
     _check_flags(flags, shape)
     if not isinstance(window, (int, np.integer)) or not 1 <= window <= MAX_WINDOW or window & (window - 1):
         raise ValueError(f"window must be a power of two in 1 .. {MAX_WINDOW}, got {window!r}")
     ax = _axis(axis, len(shape))
-    planes = int(np.prod(shape[:-2], dtype=np.int64))
     try:
         th = np.broadcast_to(np.asarray(threshold, np.float64).reshape(-1), (planes,))
         ce = np.broadcast_to(np.asarray(center, np.float64).reshape(-1), (planes,))
     except ValueError:
         raise ValueError(f"threshold and center must be scalars or hold one value per plane ({planes})") from None
-    out = np.empty(shape, np.uint8)
-    if out.size:
-        ctx = _context(device, values, flags)
-        vp, vm, k1 = _pointer(values, np.float32, ctx)
-        fp, fm, k2 = _pointer(flags, np.uint8, ctx)
-        th, thp = _doubles(th)
-        ce, cep = _doubles(ce)
-        check(lib.rfi_sumthreshold_pass(ctx.handle, C.c_void_p(vp), vm, C.c_void_p(fp), fm, planes, shape[-2], shape[-1],
-                                        int(window), ax, thp, cep, C.c_void_p(out.ctypes.data), HOST))
-        del k1, k2
-    return out.view(bool)
+    th, thp = _doubles(th)
+    ce, cep = _doubles(ce)
+    return _run_stage(lib.rfi_sumthreshold_pass, [(values, np.float32), (flags, np.uint8)], shape, planes,
+                      (int(window), ax, thp, cep), np.uint8, device).view(bool)
 
 
 def masked_gaussian_smooth(values, flags, weights_t, weights_f, device=None) -> np.ndarray:
     """The background fit: per sample the weighted mean of the unflagged samples around it, separable, time direction
     first; 0 where no unflagged sample lies under the window.  ``weights_t`` / ``weights_f``: tables of odd length
     (``gaussian_weights``).  Returns NumPy float32."""
-    shape = _check_planes("values", values)
+    shape, planes = _check_planes("values", values)
     values = _real_values("values", values)
     _check_flags(flags, shape)
     wt, wf = np.asarray(weights_t, np.float64), np.asarray(weights_f, np.float64)
     for name, w in (("weights_t", wt), ("weights_f", wf)):
         if w.ndim != 1 or w.size % 2 != 1:
             raise ValueError(f"{name} must be a 1-d table of odd length, got shape {w.shape}")
-    planes = int(np.prod(shape[:-2], dtype=np.int64))
-    out = np.empty(shape, np.float32)
-    if out.size:
-        ctx = _context(device, values, flags)
-        vp, vm, k1 = _pointer(values, np.float32, ctx)
-        fp, fm, k2 = _pointer(flags, np.uint8, ctx)
-        wt, wtp = _doubles(wt)
-        wf, wfp = _doubles(wf)
-        check(lib.rfi_masked_smooth(ctx.handle, C.c_void_p(vp), vm, C.c_void_p(fp), fm, planes, shape[-2], shape[-1],
-                                    wtp, wt.size // 2, wfp, wf.size // 2, C.c_void_p(out.ctypes.data), HOST))
-        del k1, k2
-    return out
+    wt, wtp = _doubles(wt)
+    wf, wfp = _doubles(wf)
+    return _run_stage(lib.rfi_masked_smooth, [(values, np.float32), (flags, np.uint8)], shape, planes,
+                      (wtp, wt.size // 2, wfp, wf.size // 2), np.float32, device)
 
 
 def sir_operator(flags, eta, axis=-1, device=None) -> np.ndarray:
     """The scale-invariant rank operator along one axis: a sample ends flagged when it lies in an interval of which
     at least a share 1 - eta is flagged (eta rounded to a multiple of 1/1024).  Returns NumPy bool."""
-    shape = _check_planes("flags", flags)
+    shape, planes = _check_planes("flags", flags)
     _check_flags(flags, shape)
     if not 0.0 <= float(eta) < 1.0:
         raise ValueError(f"eta must be in [0, 1), got {eta!r}")
     ax = _axis(axis, len(shape))
-    planes = int(np.prod(shape[:-2], dtype=np.int64))
-    out = np.empty(shape, np.uint8)
-    if out.size:
-        ctx = _context(device, flags)
-        fp, fm, keep = _pointer(flags, np.uint8, ctx)
-        check(lib.rfi_sir_operator(ctx.handle, C.c_void_p(fp), fm, planes, shape[-2], shape[-1], ax, min(sir_q(eta), 1023),
-                                   C.c_void_p(out.ctypes.data), HOST))
-        del keep
-    return out.view(bool)
+    return _run_stage(lib.rfi_sir_operator, [(flags, np.uint8)], shape, planes, (ax, min(sir_q(eta), 1023)), np.uint8,
+                      device).view(bool)
 
 
 # ---------------------------------------------------------------------------------------------- the pipeline
@@ -267,46 +300,15 @@ def sumthreshold_flags(data, flags=None, iterations=3, levels=7, base_sensitivit
     ``out="host"`` returns bool flags of ``data``'s shape, like ``predict_flags`` (a CUDA tensor for CUDA input, else
     NumPy); ``out="device"`` returns a uint8 ``DeviceArray`` and, with device-resident inputs, only enqueues work.
     """
-    shape = _check_planes("data", data)
-    dt = _np_dtype(data)
-    if dt is None or np.dtype(dt) not in _CODES:
-        raise ValueError(f"data must be complex64, complex128, float32 or float64, got {dt}")
-    dt = np.dtype(dt)
-    if flags is not None:
-        _check_flags(flags, shape)
-    if out not in ("host", "device"):
-        raise ValueError(f"out must be 'host' or 'device', got {out!r}")
+    shape, planes, dt = _check_data(data, flags, out, _CODES)
     cfg, wt, wf = make_config(iterations, levels, base_sensitivity, chi_1, rho, smooth_sigma, smooth_half, sir_eta)
-    planes = int(np.prod(shape[:-2], dtype=np.int64))
+    wt, wtp = _doubles(wt)
+    wf, wfp = _doubles(wf)
 
-    ctx = _context(device, data, flags)
-    dp, dm, k1 = _pointer(data, dt, ctx)
-    fp, fm, k2 = _pointer(flags, np.uint8, ctx) if flags is not None else (None, HOST, None)
-    cuda_in = is_torch(data) and data.is_cuda
-    if out == "device":
-        res = ctx.empty(shape, np.uint8)
-        rp, rm = res.ptr, DEVICE
-    elif cuda_in:
-        res = torch.empty(shape, dtype=torch.uint8, device=data.device)
-        torch.cuda.current_stream(data.device).synchronize()        # (the output's memory may have just been freed)
-        rp, rm = res.data_ptr(), DEVICE
-    else:
-        res = np.empty(shape, np.uint8)
-        rp, rm = res.ctypes.data, HOST
-    if planes:
-        _, wtp = _doubles(wt)
-        _, wfp = _doubles(wf)
-        check(lib.rfi_sumthreshold_flag(ctx.handle, C.c_void_p(dp), dm, _CODES[dt], C.c_void_p(fp) if fp else None, fm, planes,
-                                        shape[-2], shape[-1], C.byref(cfg), wtp, wfp, C.c_void_p(rp), rm))
-    if out == "device":
-        res._keep = (k1, k2)             # the inputs may still be read by work in flight: they live as long as the result
-        return res
-    if cuda_in:
-        ctx.synchronize()
-        del k1, k2
-        return res.view(torch.bool)
-    del k1, k2
-    return res.view(bool)
+    def call(ctx, dp, dm, fp, fm, rp, rm):
+        return lib.rfi_sumthreshold_flag(ctx.handle, dp, dm, _CODES[dt], fp, fm, planes, shape[-2], shape[-1], C.byref(cfg), wtp, wfp,
+                                         rp, rm)
+    return _run_flagger(call, data, dt, flags, shape, planes, out, device)
 
 
 # ---------------------------------------------------------------------------------------------- CASA-style flaggers
@@ -345,49 +347,6 @@ def _per_plane(name, v, planes, per, forms):
     raise ValueError(f"{name} must be {forms}, got shape {a.shape}")
 
 
-def _run_flagger(call, data, dt, flags, shape, out, device):
-    """The shared tail of the three flaggers: pointers, the result buffer of `out`, then call(ctx, data pointer and
-    memory kind, prior pointer and kind, planes, result pointer and kind)."""
-    planes = int(np.prod(shape[:-2], dtype=np.int64))
-    ctx = _context(device, data, flags)
-    dp, dm, k1 = _pointer(data, dt, ctx)
-    fp, fm, k2 = _pointer(flags, np.uint8, ctx) if flags is not None else (None, HOST, None)
-    cuda_in = is_torch(data) and data.is_cuda
-    if out == "device":
-        res = ctx.empty(shape, np.uint8)
-        rp, rm = res.ptr, DEVICE
-    elif cuda_in:
-        res = torch.empty(shape, dtype=torch.uint8, device=data.device)
-        torch.cuda.current_stream(data.device).synchronize()        # (the output's memory may have just been freed)
-        rp, rm = res.data_ptr(), DEVICE
-    else:
-        res = np.empty(shape, np.uint8)
-        rp, rm = res.ctypes.data, HOST
-    if planes:
-        check(call(ctx, C.c_void_p(dp), dm, C.c_void_p(fp) if fp else None, fm, planes, C.c_void_p(rp), rm))
-    if out == "device":
-        res._keep = (k1, k2)             # the inputs may still be read by work in flight: they live as long as the result
-        return res
-    if cuda_in:
-        ctx.synchronize()
-        del k1, k2
-        return res.view(torch.bool)
-    del k1, k2
-    return res.view(bool)
-
-
-def _check_data(data, flags, out, codes):
-    shape = _check_planes("data", data)
-    dt = _np_dtype(data)
-    if dt is None or np.dtype(dt) not in codes:
-        raise ValueError(f"data must be one of {', '.join(str(c) for c in codes)}, got {dt}")
-    if flags is not None:
-        _check_flags(flags, shape)
-    if out not in ("host", "device"):
-        raise ValueError(f"out must be 'host' or 'device', got {out!r}")
-    return shape, np.dtype(dt)
-
-
 def tfcrop_flags(data, flags=None, ntime=None, timecutoff=4.0, freqcutoff=3.0, timefit="line", freqfit="poly", maxnpieces=7,
                  flagdimension="freqtime", out="host", device=None):
     """Flags from a TFCrop-style flagger (CASA flagdata ``mode="tfcrop"``): robust fits along time and frequency.
@@ -401,7 +360,7 @@ def tfcrop_flags(data, flags=None, ntime=None, timecutoff=4.0, freqcutoff=3.0, t
     rejecting the samples further than cutoff standard deviations of the residuals from it.  The arithmetic is pinned in
     include/rfi_hip.h ("CASA-style baseline flaggers") and is this project's own: results agree with CASA in kind, not
     bit for bit.  CASA's ``usewindowstats`` / ``halfwin`` are not built.  There is no CPU path."""
-    shape, dt = _check_data(data, flags, out, _CODES)
+    shape, planes, dt = _check_data(data, flags, out, _CODES)
     for name, v in (("timefit", timefit), ("freqfit", freqfit)):
         if v not in _FITS:
             raise ValueError(f"{name} must be 'line' or 'poly', got {v!r}")
@@ -412,9 +371,9 @@ def tfcrop_flags(data, flags=None, ntime=None, timecutoff=4.0, freqcutoff=3.0, t
     cfg = TfcropConfig(_ntime(ntime), _FITS[timefit], _FITS[freqfit], int(min(maxnpieces, _INT_MAX)), _DIMENSIONS[flagdimension], 0,
                        _non_negative("timecutoff", timecutoff), _non_negative("freqcutoff", freqcutoff))
 
-    def call(ctx, dp, dm, fp, fm, planes, rp, rm):
+    def call(ctx, dp, dm, fp, fm, rp, rm):
         return lib.rfi_tfcrop_flag(ctx.handle, dp, dm, _CODES[dt], fp, fm, planes, shape[-2], shape[-1], C.byref(cfg), rp, rm)
-    return _run_flagger(call, data, dt, flags, shape, out, device)
+    return _run_flagger(call, data, dt, flags, shape, planes, out, device)
 
 
 def rflag_flags(data, flags=None, ntime=None, winsize=3, timedevscale=5.0, freqdevscale=5.0, timedev=None, freqdev=None,
@@ -432,10 +391,9 @@ def rflag_flags(data, flags=None, ntime=None, winsize=3, timedevscale=5.0, freqd
     Medians are exact.  Unlike CASA, no polynomial is fitted to the per-channel thresholds across a spectral window.
     ``data``, ``flags``, ``out`` and ``device`` as for ``sumthreshold_flags``.  There is no CPU path."""
     codes = {k: v for k, v in _CODES.items() if k.kind == "c"}
-    shape, dt = _check_data(data, flags, out, codes)
+    shape, planes, dt = _check_data(data, flags, out, codes)
     if isinstance(winsize, (bool, np.bool_)) or not isinstance(winsize, (int, np.integer)) or winsize < 1 or winsize % 2 == 0:
         raise ValueError(f"winsize must be an odd integer >= 1, got {winsize!r}")
-    planes = int(np.prod(shape[:-2], dtype=np.int64))
     cfg = RflagConfig(_ntime(ntime), int(min(winsize, _INT_MAX)), _non_negative("timedevscale", timedevscale),
                       _non_negative("freqdevscale", freqdevscale))
     td = _per_plane("timedev", timedev, planes, shape[-2], "a scalar, one value per plane or (planes, C) values")
@@ -443,9 +401,9 @@ def rflag_flags(data, flags=None, ntime=None, winsize=3, timedevscale=5.0, freqd
     tdp = td.ctypes.data_as(C.POINTER(C.c_double)) if td is not None else None
     fdp = fd.ctypes.data_as(C.POINTER(C.c_double)) if fd is not None else None
 
-    def call(ctx, dp, dm, fp, fm, planes, rp, rm):
+    def call(ctx, dp, dm, fp, fm, rp, rm):
         return lib.rfi_rflag_flag(ctx.handle, dp, dm, _CODES[dt], fp, fm, planes, shape[-2], shape[-1], C.byref(cfg), tdp, fdp, rp, rm)
-    return _run_flagger(call, data, dt, flags, shape, out, device)
+    return _run_flagger(call, data, dt, flags, shape, planes, out, device)
 
 
 def extend_flags(flags, ntime=None, growtime=50.0, growfreq=50.0, growaround=False, flagneartime=False, flagnearfreq=False,
@@ -455,7 +413,7 @@ def extend_flags(flags, ntime=None, growtime=50.0, growfreq=50.0, growaround=Fal
     flagged), ``growtime`` (a channel flagged for more than that many per cent of the chunk is flagged for all of it; 100
     switches it off), ``growfreq`` (the same per time sample across the channels), ``flagneartime`` and ``flagnearfreq``
     (the samples one step from a flagged one).  ``out`` and ``device`` as for ``sumthreshold_flags``."""
-    shape = _check_planes("flags", flags)
+    shape, planes = _check_planes("flags", flags)
     _check_flags(flags, shape)
     if out not in ("host", "device"):
         raise ValueError(f"out must be 'host' or 'device', got {out!r}")
@@ -465,6 +423,6 @@ def extend_flags(flags, ntime=None, growtime=50.0, growfreq=50.0, growaround=Fal
     cfg = ExtendConfig(_ntime(ntime), int(bool(growaround)), int(bool(flagneartime)), int(bool(flagnearfreq)), float(growtime),
                        float(growfreq))
 
-    def call(ctx, dp, dm, fp, fm, planes, rp, rm):
+    def call(ctx, dp, dm, fp, fm, rp, rm):
         return lib.rfi_extend_flags(ctx.handle, dp, dm, planes, shape[-2], shape[-1], C.byref(cfg), rp, rm)
-    return _run_flagger(call, flags, np.uint8, None, shape, out, device)
+    return _run_flagger(call, flags, np.uint8, None, shape, planes, out, device)

@@ -234,3 +234,35 @@ def test_pipeline_device_input_and_reproducibility(fl, stack, expected):
     t = torch.from_numpy(c64).cuda()
     got = fl.sumthreshold_flags(t, flags=torch.from_numpy(prior).cuda())
     assert got.is_cuda and got.dtype == torch.bool and np.array_equal(got.cpu().numpy(), host)
+
+
+# ---------------------------------------------------------------------------------------------- the plane-group driver
+def test_stack_across_a_group_boundary(fl):
+    """The driver that carries a stack through the context's scratch, with more than one group: 2 planes of 4096 x 8192
+    float32.  One plane needs 26 bytes of workspace per sample (832 MiB) and up to 5 more with host data and prior flags
+    staged (992 MiB), plus the state record, the weight tables and the alignment of the regions (well under 1 MiB): one plane
+    fits the 1 GiB budget and two do not, so the call takes two groups of one plane and the second starts at plane 1.  The
+    reference is the single-group path (each plane flagged on its own), which the tests above pin to the NumPy oracle; no
+    oracle runs at this size."""
+    import torch
+    C, T = 4096, 8192
+    assert 31 * C * T + (1 << 20) <= 1 << 30 < 2 * 26 * C * T
+    gen = torch.Generator(device="cuda").manual_seed(20)
+    x = 1.0 + 0.1 * torch.randn((2, C, T), generator=gen, device="cuda", dtype=torch.float32)
+    x[0, 100] += 2.0                                       # a few strong lines, other ones in each plane
+    x[0, :, 5000:5003] += 2.0
+    x[1, 3000:3002] += 2.0
+    x[1, :, 77] += 2.0
+    cfg = dict(iterations=1, levels=1, sir_eta=0.2)
+    host = x.cpu().numpy()
+    modes = {"cuda tensor -> host": (x, "host", lambda r: r.cpu().numpy()),
+             "cuda tensor -> device": (x, "device", lambda r: r.numpy().view(bool)),
+             "numpy (staged)": (host, "host", lambda r: r)}
+    for name, (data, out, to_numpy) in modes.items():
+        stacked = to_numpy(fl.sumthreshold_flags(data, out=out, **cfg))
+        assert stacked.dtype == bool and stacked.shape == (2, C, T), name
+        for i in range(2):
+            alone = to_numpy(fl.sumthreshold_flags(data[i], out=out, **cfg))
+            assert np.array_equal(stacked[i], alone), (name, i, int((stacked[i] != alone).sum()))
+        assert stacked[0, 100].all() and stacked[1, 3000].all() and not stacked.all(), name
+        assert not np.array_equal(stacked[0], stacked[1]), name      # (so equality above tells plane 1 from plane 0 flagged twice)
