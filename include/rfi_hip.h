@@ -246,6 +246,11 @@ int rfi_model_algorithmic_flops(rfi_model* m, int n, int h, int w, double* fwd, 
  * "encY1.<l>" "encY2.<l>" "decY1.<l>" "decY2.<l>" "concat.<l>" "pool.<l>" "bottY1" "bottY2" "logits"
  * "dlogits" "gA.<l>" "gB.<l>" "dconcat.<l>" "dpool.<l>" "gBottA" "gBottB" (raw NHWC fp32), and
  * "chan.<conv index>" = [running_mean|running_var|mean|invstd|scale|shift|c1|c2] x Cout.
+ * ResNet-50-FPN backbone (conv indices in state_dict order of the conv weights): "conv.<i>" raw
+ * output of conv i before its frozen BatchNorm, on its own output grid (0: the stem at H/2; FPN
+ * inner / layer blocks: the lateral / the pyramid level), "pool" the pooled stem, "block.<b>" the
+ * output of Bottleneck b (0..15), "merged.<i>" the top-down merged map of FPN level i (0..3),
+ * "dmerged.<i>" its gradient (valid after a backward pass); all NHWC fp32.
  * host == NULL only reports the element count. */
 int rfi_model_debug_tensor(rfi_model* m, const char* name, float* host, size_t host_floats,
                            int64_t* n_floats);

@@ -984,7 +984,8 @@ void UNetModel::set_compute_dtype(int dtype) {
 }
 
 void rfi_model::debug_tensor(const std::string&, const std::string&, int, bool, const float*&, size_t&) {
-    throw Error("debug_tensor: this model exposes only logits / dlogits / chan (and the decoder tensors of the ResNet-encoder U-Net)");
+    throw Error("debug_tensor: this model exposes only logits / dlogits / chan (the U-Net and the ResNet-50-FPN backbone expose their "
+                "own tensors, the ResNet-encoder U-Net its decoder's: see rfi_hip.h)");
 }
 void UNetModel::debug_tensor(const std::string& name, const std::string& base, int idx, bool to_host, const float*& src, size_t& n) {
     if (resnet_encoder && (base == "encY1" || base == "encY2" || base == "pool" || base == "dpool"))

@@ -469,6 +469,7 @@ struct BackboneModel : rfi_model {
     void forward_pass(const float* x_dev, int n, int h, int w, bool train_mode) override;
     void backward_pass(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w) override;
     void algorithmic_flops(int n, int h, int w, double& fwd, double& step) const override;
+    void debug_tensor(const std::string& name, const std::string& base, int idx, bool to_host, const float*& src, size_t& n) override;
     struct BBlock {
         int stage = 0, stride = 1, cin = 0, width = 0, cout = 0, lvl_in = 2, lvl = 2;      // resolution H >> lvl
         int c1 = -1, c2 = -1, c3 = -1, cd = -1;                                           // convs indices (cd: projection shortcut)

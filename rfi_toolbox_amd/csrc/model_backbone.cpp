@@ -419,6 +419,42 @@ void BackboneModel::backward_pass(const float* x_dev, const uint8_t*, int n, int
     bucket_ready(0, n_flat);
 }
 
+// conv.<i>: raw (pre-BatchNorm) output of convs[i] on its own output grid; pool: the pooled stem; block.<b>: output of
+// Bottleneck b; merged.<i> / dmerged.<i>: the top-down merged map of FPN level i and its gradient (after a backward pass)
+void BackboneModel::debug_tensor(const std::string& name, const std::string& base, int idx, bool, const float*& src, size_t& n) {
+    auto px = [&](int lvl) { return (size_t)pN * (pH >> lvl) * (pW >> lvl); };
+    if (base == "conv") {
+        RFI_REQUIRE(idx >= 0 && idx < (int)convs.size(), "debug_tensor: conv index out of range");
+        int b = idx == 0 ? bY0 : -1;
+        for (auto& k : bb) {
+            if (idx == k.c1) b = k.Y1;
+            else if (idx == k.c2) b = k.Y2;
+            else if (idx == k.c3) b = k.Y3;
+            else if (idx == k.cd) b = k.Yd;
+        }
+        for (int i = 0; i < 4; ++i) {
+            if (idx == fpn_inner[i]) b = fL[i];
+            else if (idx == fpn_layer[i]) b = fP[i];
+        }
+        RFI_REQUIRE(b >= 0, "debug_tensor: conv index out of range");
+        src = buf(b);
+        n = px(convs[idx].level) * convs[idx].cout;
+    } else if (name == "pool") {
+        src = buf(bP0);
+        n = px(2) * feat;
+    } else if (base == "block") {
+        RFI_REQUIRE(idx >= 0 && idx < (int)bb.size(), "debug_tensor: block index out of range");
+        src = buf(bb[idx].A);
+        n = px(bb[idx].lvl) * bb[idx].cout;
+    } else if (base == "merged" || base == "dmerged") {
+        RFI_REQUIRE(idx >= 0 && idx < 4, "debug_tensor: FPN level out of range");
+        src = buf(base == "merged" ? fM[idx] : fdM[idx]);
+        n = px(idx + 2) * out_ch;
+    } else {
+        throw Error("debug_tensor: unknown tensor " + name);
+    }
+}
+
 BackboneModel::~BackboneModel() {
     if (!ctx) return;
     ctx->activate();

@@ -1,31 +1,56 @@
 """-m gpu: the ResNet-50-FPN backbone of the Mask R-CNN path (BASELINE.json configs[3]) on MI355X
-against oracle/backbone_ref.py (plain torch.nn modules; parity unpinned by the reference, which has no detector): the five
-pyramid levels of the forward pass and every parameter gradient of the backward pass from given d(loss)/d(P_i)."""
-from collections import OrderedDict
+against oracle/backbone_ref.py (plain torch.nn modules; parity unpinned by the reference, which has no detector), layer
+by layer at float32 rounding level: every conv output, the pooled stem, every Bottleneck output, the merged FPN maps and
+the five pyramid levels of the forward pass; every parameter gradient and the gradients of the merged maps of the backward
+pass from given d(loss)/d(P_i).
 
+The yardstick is the float32 oracle's own error against the float64 oracle, both run with every ReLU replaced by the mask
+the DEVICE's forward tensors give (tests/backbone_cases.py): with the masks fixed the backward pass is one linear map and
+no ReLU input within rounding of 0 can take another branch than the oracle's, so no bound has to survive that event.
+What is left to the inputs is asserted: no ReLU input the device itself could decide either way, no max-pool window with
+two candidates within rounding (B.masks_from_tensors).
+
+K_F, K_G: the worst ratios measured on the MI355X over all cases, times 2 (seed-to-seed spread), rounded up to a power of
+two.  Measured (fwd = worst e_hip / e_ref over the tensors, grad = worst rel_hip / rel_ref over the gradients):
+
+    case                  fwd                  grad
+    c3_w8_2x64x64         2.60  (conv.48)      1.98  (body.layer2.2.conv1.weight)
+    c3_w8_1x64x128        2.43  (conv.29)      3.16  (fpn.inner_blocks.2.0.bias)
+    c3_w8_1x128x64        3.17  (conv.29)      2.76  (fpn.inner_blocks.3.0.bias)
+    c1_w8_3x64x64         1.69  (conv.35)      4.25  (body.layer1.1.conv1.weight)
+    c8_w4_2x64x64         1.75  (conv.44)      1.97  (body.layer2.3.conv1.weight)
+    c3_w16_2x128x128      3.25  (conv.29)      3.39  (body.layer2.1.conv1.weight)
+    c3_w64_1x128x128      7.57  (conv.48)     13.61  (fpn.inner_blocks.2.0.bias)
+    mfma_c3_w8_2x64x64    2.44  (conv.48)      1.99  (body.layer3.5.conv1.weight)
+    worst                 7.57 -> K_F = 16    13.61 -> K_G = 32
+
+(median gradient ratio 1.0 .. 1.3 at the small widths, 5.6 at the real widths, whose contractions are up to 2304 products long:
+the 3 x bf16 kernels carry up to 16 units of 2^-24 per product, tests/test_gpu_x3_accuracy.py.)  Every case had no undecided
+element and no undecided window at its first seed.
+
+The bfloat16 compute mode has no case here.  Measured at (3, 8, 16, 2, 64, 64) against the float64 oracle whose Conv2d
+inputs and weights are rounded to bfloat16 (masks from the device), as ratios to the float32 oracle's distance from it:
+forward worst 1.03 (conv.42), median 0.40, where 0.5 per tensor was asked; gradients worst 2.38 (body.layer3.2.conv1.weight),
+median 0.86, where 1.1 and 0.8 were asked.  That emulation is not the kernels' arithmetic: they round the dY operand of
+both backward contractions too, and in the forward pass the float32 CPU run of the very same emulation is at 0.94 (conv.40),
+median 0.35 -- one activation that rounds to the other bfloat16 neighbour moves a width-8 output by as much as all the
+operand rounding together, so no float32 implementation stays under 0.5 per tensor through 50 layers.
+"""
 import numpy as np
 import pytest
 import torch
 
+import backbone_cases as B
 from oracle import backbone_ref as bref
-from oracle import unet_ref
 from rfi_toolbox_amd.models import ResNet50FPN
+from rfi_toolbox_amd.runtime import Context
 
 pytestmark = pytest.mark.gpu
 
+K_F = 16
+K_G = 32
 
-def _state(w, f, seed):
-    """Default conv init with non-trivial frozen BatchNorm buffers (every term of the affine matters)."""
-    st = bref.init_state(3, w, f, seed=seed)
-    g = torch.Generator().manual_seed(seed + 1)
-    for k in st:
-        if k.endswith("running_mean"):
-            st[k] = 0.1 * torch.randn(st[k].shape, generator=g)
-        elif k.endswith("running_var"):
-            st[k] = 0.5 + torch.rand(st[k].shape, generator=g)
-        elif ".bn" in k or "downsample.1" in k:
-            st[k] = (1 + 0.2 * torch.randn(st[k].shape, generator=g)) if k.endswith("weight") else 0.1 * torch.randn(st[k].shape, generator=g)
-    return st
+SMALL = B.BY_ID["c3_w8_2x64x64"]
 
 
 def test_state_dict_and_default_init():
@@ -36,7 +61,7 @@ def test_state_dict_and_default_init():
     assert list(sd.keys()) == list(want.keys())
     for k in want:
         assert torch.equal(sd[k], want[k]), k
-    st = _state(8, 16, 4)
+    st = B._state(3, 8, 16, 4)
     m.load_state_dict(st)
     back = m.state_dict()
     for k, v in st.items():
@@ -49,43 +74,40 @@ def test_state_dict_and_default_init():
         ResNet50FPN(3, 6, 16)
 
 
-@pytest.mark.parametrize("mode,w,f,n,s", [("float32", 8, 16, 2, 64), ("float32_mfma", 8, 16, 2, 64), ("float32", 16, 32, 2, 128),
-                                           ("float32", 64, 256, 1, 128)])
-def test_features_and_gradients_vs_oracle(mode, w, f, n, s):
-    st = _state(w, f, 11)
-    g = torch.Generator().manual_seed(12)
-    x = torch.randn(n, s, s, 3, generator=g)
-    mod = bref.ResNet50FPN(3, w, f)
-    mod.load_state_dict(st)
-    xo = unet_ref.nhwc_to_nchw(x)
-    feats = mod(xo)
-    dfe = [torch.randn(t.shape, generator=g) / t[0].numel() ** 0.5 for t in feats]
-    params = [p for p in mod.parameters()]
-    names = [k for k, _ in mod.named_parameters()]
-    grads = torch.autograd.grad(sum((t * d).sum() for t, d in zip(feats, dfe)), params)
-    mod64 = bref.ResNet50FPN(3, w, f).double()
-    mod64.load_state_dict(OrderedDict((k, v.double()) for k, v in st.items()))
-    feats64 = mod64(xo.double())
-    grads64 = torch.autograd.grad(sum((t * d.double()).sum() for t, d in zip(feats64, dfe)), list(mod64.parameters()))
+def _device_run(c):
+    """Forward + backward of case c on the device -> (model, inputs, masks, forward tensors, gradients)."""
+    st, x, dfe = B.case_inputs(c)
+    names = B.conv_names(st)
+    m = ResNet50FPN(c.cin, c.w, c.f).load_state_dict(st).set_compute_dtype(c.mode)
+    feats = m.forward_features(x.numpy())
+    dm = B.masks_from_device(m, names, c.n, c.h, c.wd)           # (from the forward tensors, before any backward pass)
+    t = {f"feat.{i}": a for i, a in enumerate(feats)}
+    for k in [f"conv.{i}" for i in range(len(names))] + ["pool"] + [f"block.{b}" for b in range(16)] + [f"merged.{i}" for i in range(4)]:
+        t[k] = m.debug_tensor(k)
+    m.backward(x.numpy(), [d.numpy() for d in dfe])
+    g = {k: m.grad(k) for k, v in st.items() if "bn" not in k and "downsample.1" not in k}
+    for i in range(4):
+        g[f"dmerged.{i}"] = m.debug_tensor(f"dmerged.{i}")
+    return m, (st, x, dfe), dm, t, g
 
-    m = ResNet50FPN(3, w, f).load_state_dict(st).set_compute_dtype(mode)
-    got = m.forward_features(x.numpy())
-    for i, (a, b) in enumerate(zip(got, feats)):
-        b = b.detach().permute(0, 2, 3, 1).numpy()
-        assert a.shape == b.shape
-        assert np.abs(a - b).max() <= 5e-5 * max(1.0, np.abs(b).max()), i
-    m.backward(x.numpy(), [d.permute(0, 2, 3, 1).numpy() for d in dfe])
-    worst = []
-    for k, g32, g64 in zip(names, grads, grads64):
-        w64 = g64.numpy().ravel()
-        nrm = np.linalg.norm(w64) + 1e-30
-        rel_ref = np.linalg.norm(g32.numpy().ravel() - w64) / nrm
-        rel_hip = np.linalg.norm(m.grad(k).ravel() - w64) / nrm
-        worst.append((rel_hip, k, rel_ref))
-        # a ReLU input within rounding of 0 takes the other branch than the oracle's and moves every gradient computed
-        # after it by one element's share (see tests/test_gpu_resnet_unet.py): 2e-2 bounds that, the median pins the rest
-        assert rel_hip <= max(4 * rel_ref, 2e-2), (k, rel_hip, rel_ref)
-    assert np.median([t[0] for t in worst]) <= 5e-3, sorted(worst)[-3:]
+
+def _assert_decided(c, dm):
+    assert dm.undecided == 0, f"{c.id}: {dm.undecided} ReLU inputs the device could decide either way -- pick another seed"
+    assert dm.undecided_windows == 0, f"{c.id}: {dm.undecided_windows} max-pool windows with two candidates within rounding -- pick another seed"
+
+
+@pytest.mark.parametrize("c", B.CASES, ids=lambda c: c.id)
+def test_features_and_gradients_vs_oracle(c):
+    m, (st, x, dfe), dm, t, g = _device_run(c)
+    m64 = B.run_oracle(st, x, dfe, torch.float64, masks=dm.masks)
+    m32 = B.run_oracle(st, x, dfe, torch.float32, masks=dm.masks)
+    assert set(t) == set(m64.tensors) and set(g) == set(m64.grads)
+    rf, kf = B.check_forward(t, m32.tensors, m64.tensors)
+    rg, kg = B.check_gradients(g, m32.grads, m64.grads)
+    print(f"BACKBONE {c.id} fwd={rf:.2f} ({kf}) grad={rg:.2f} ({kg}) undecided={dm.undecided}+{dm.undecided_windows}")
+    _assert_decided(c, dm)
+    B.check_forward(t, m32.tensors, m64.tensors, bound=K_F)
+    B.check_gradients(g, m32.grads, m64.grads, bound=K_G)
     # frozen BatchNorm: buffers unchanged by a step, parameters move
     before = m.state_dict()
     m.apply_gradients(lr=1e-3, weight_decay=0.0)
@@ -93,3 +115,119 @@ def test_features_and_gradients_vs_oracle(mode, w, f, n, s):
     for k in before:
         same = torch.equal(before[k], after[k])
         assert same == (".bn" in k or "downsample.1" in k), k
+
+
+# ------------------------------------------------------------------------------------------------------ behaviour
+def _params(st):
+    return [k for k in st if "bn" not in k and "downsample.1" not in k]
+
+
+def _grads(m, st):
+    return {k: m.grad(k).copy() for k in _params(st)}
+
+
+def _same(a, b):
+    return [k for k in a if not np.array_equal(a[k], b[k])]
+
+
+@pytest.mark.parametrize("c,reps", [(SMALL, 20), (B.Case("c3_w16_4x128x128", "float32", 3, 16, 32, 4, 128, 128, 11), 20)],
+                         ids=lambda v: getattr(v, "id", None))
+def test_overlap_and_repetition_are_bitwise_neutral(c, reps):
+    """The weight gradients on the side stream read dY3 / dY2 / dY1 / dYd buffers that block b - 3 rewrites (by block index
+    mod 3, run-ahead bound 2): serial execution and every repetition give the same bits."""
+    st, x, dfe = B.case_inputs(c)
+    x, dfe = x.numpy(), [d.numpy() for d in dfe]
+    m = ResNet50FPN(c.cin, c.w, c.f).load_state_dict(st)
+    ctx = Context.get(0)
+    try:
+        ctx.set_overlap(False)
+        f0 = m.forward_features(x)
+        m.backward(x, dfe)
+        g0 = _grads(m, st)
+        ctx.set_overlap(True)
+        for r in range(reps):
+            f = m.forward_features(x)
+            m.backward(x, dfe)
+            assert all(np.array_equal(a, b) for a, b in zip(f, f0)), r
+            assert not _same(g0, _grads(m, st)), (r, _same(g0, _grads(m, st))[:3])
+    finally:
+        ctx.set_overlap(True)
+
+
+def test_none_gradients_are_zero_gradients():
+    c = SMALL
+    st, x, dfe = B.case_inputs(c)
+    x, dfe = x.numpy(), [d.numpy() for d in dfe]
+    m = ResNet50FPN(c.cin, c.w, c.f).load_state_dict(st)
+    m.forward_features(x)
+    m.backward(x, dfe)                                  # (every gradient buffer holds something else first)
+    zeros = [np.zeros_like(d) for d in dfe]
+    m.backward(x, [dfe[0], zeros[1], zeros[2], zeros[3], dfe[4]])
+    want = _grads(m, st)
+    m.backward(x, dfe)
+    m.backward(x, [dfe[0], None, None, None, dfe[4]])
+    got = _grads(m, st)
+    assert not _same(want, got), _same(want, got)[:3]
+    for i in (1, 2):                                    # nothing reaches the output convs of levels 1 and 2 ...
+        for s in ("weight", "bias"):
+            assert not got[f"fpn.layer_blocks.{i}.0.{s}"].any(), (i, s)
+    for i in (0, 3):                                    # ... dP2 reaches level 0's and dP6 (through P5[:, ::2, ::2]) level 3's
+        for s in ("weight", "bias"):
+            assert got[f"fpn.layer_blocks.{i}.0.{s}"].any(), (i, s)
+    assert got["body.conv1.weight"].any()
+    m.backward(x, [dfe[0], None, None, None, None])
+    got = _grads(m, st)
+    for i in (1, 2, 3):
+        for s in ("weight", "bias"):
+            assert not got[f"fpn.layer_blocks.{i}.0.{s}"].any(), (i, s)
+    m.backward(x, [None] * 5)
+    got = _grads(m, st)
+    assert not [k for k, v in got.items() if v.any()]
+
+
+def test_shape_changes_on_one_model():
+    c = SMALL
+    st, xa, da = B.case_inputs(c)
+    _, xb, db = B.inputs(c.cin, c.w, c.f, 1, 128, 64, c.seed + 7)
+    xa, da, xb, db = xa.numpy(), [d.numpy() for d in da], xb.numpy(), [d.numpy() for d in db]
+
+    def step(m, x, d):
+        f = m.forward_features(x)
+        m.backward(x, d)
+        return f, _grads(m, st)
+    m = ResNet50FPN(c.cin, c.w, c.f).load_state_dict(st)
+    f1, g1 = step(m, xa, da)
+    f2, g2 = step(m, xb, db)                            # the buffers grow ...
+    f3, g3 = step(m, xa, da)                            # ... and are used at the smaller shape again
+    fresh = ResNet50FPN(c.cin, c.w, c.f).load_state_dict(st)
+    ff, gf = step(fresh, xb, db)
+    assert all(np.array_equal(a, b) for a, b in zip(f1, f3)) and not _same(g1, g3), _same(g1, g3)[:3]
+    assert all(np.array_equal(a, b) for a, b in zip(f2, ff)) and not _same(g2, gf), _same(g2, gf)[:3]
+
+
+def test_errors_raised():
+    c = SMALL
+    st, x, dfe = B.case_inputs(c)
+    x, dfe = x.numpy(), [d.numpy() for d in dfe]
+    m = ResNet50FPN(c.cin, c.w, c.f).load_state_dict(st)
+    with pytest.raises(RuntimeError):
+        m.debug_tensor("conv.0")                        # no prepared shape yet
+    with pytest.raises(RuntimeError):
+        m.backward(x, dfe)                              # no forward pass at all
+    m.forward_features(x)
+    xb = np.zeros((1, 128, 64, c.cin), np.float32)
+    with pytest.raises(RuntimeError):
+        m.backward(xb, [np.zeros(s, np.float32) for s in m._shapes(1, 128, 64)])      # none on that shape
+    with pytest.raises(ValueError):
+        m.forward_features(np.zeros((1, 64, 64, c.cin + 1), np.float32))
+    for h, w in ((96, 64), (64, 96), (32, 64)):
+        with pytest.raises(RuntimeError):
+            m.forward_features(np.zeros((1, h, w, c.cin), np.float32))
+    m.forward_features(x)
+    n_conv = len(B.conv_names(st))
+    for name in ("conv.%d" % n_conv, "conv.-1", "chan.%d" % n_conv, "block.16", "block.-1", "merged.4", "dmerged.4", "pool.0", "encY1.1",
+                 "nothing"):
+        with pytest.raises(RuntimeError):
+            m.debug_tensor(name)
+    assert m.debug_tensor("conv.%d" % (n_conv - 1)).size == c.n * (c.h >> 5) * (c.wd >> 5) * c.f
+    assert m.debug_tensor("pool").size == c.n * (c.h >> 2) * (c.wd >> 2) * c.w
