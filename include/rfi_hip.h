@@ -260,6 +260,11 @@ int rfi_model_debug_tensor(rfi_model* m, const char* name, float* host, size_t h
 int rfi_model_eval_batch(rfi_model* m, const float* x_nhwc, int x_mem, const uint8_t* labels,
                          int labels_mem, int n, int h, int w, float threshold, int64_t* tp,
                          int64_t* fp, int64_t* fn);
+/* rfi_model_eval_batch for n_thresholds cuts from ONE forward pass: forward in the current mode, then
+ * rfi_threshold_sweep's kernel with kind LOGITS on what eval_batch thresholds (logits, or the probabilities of a
+ * sigmoid-head model: sigmoid of the model's output, as evaluate_model.py:44 does), one group.  counts: K x 3. */
+int rfi_model_eval_sweep(rfi_model* m, const float* x_nhwc, int x_mem, const uint8_t* labels, int labels_mem,
+                         int n, int h, int w, const float* thresholds_host, int n_thresholds, int64_t* counts_host);
 
 /* ---- data-parallel gradient exchange (new; the reference has no multi-GPU path) -------
  * RCCL over xGMI: ncclAllReduce(sum) of the flat gradient buffer on the ctx stream.
@@ -345,6 +350,21 @@ int rfi_confusion_counts(rfi_ctx* ctx, const void* pred, int pred_dtype, int pre
 /* sigmoid(logit) > threshold on device (evaluate_model.py:44-47), u8 out */
 int rfi_threshold_logits(rfi_ctx* ctx, const float* logits_dev, int64_t count, float threshold,
                          uint8_t* mask_dev);
+/* counts[g][k] = (tp, fp, fn) of "p > thresholds[k]" against truth over group g, for every k at once.
+ * p = scores[i] (RFI_VALUES_PROBS) or 1.0f / (1.0f + expf(-scores[i])) (RFI_VALUES_LOGITS: the expression
+ * of rfi_threshold_logits and rfi_stitch_patches).  truth: RFI_U8 or RFI_FLOAT32, non-zero == positive
+ * (rfi_confusion_counts' rule).  A NaN score is flagged at no threshold.  thresholds: host, float32, finite,
+ * strictly increasing, 1 <= n_thresholds <= 1024.  Groups: count / group_elems contiguous runs of group_elems
+ * elements (count % group_elems == 0, at most 65535 groups; group_elems == count: one group).  Device pointers
+ * need only their element's alignment (a slice of a larger array is fine).
+ * counts_host: n_groups x n_thresholds x 3 int64.  One call, one synchronisation.
+ * Arithmetic: an element's bin is b = the number of thresholds strictly below p (binary search; NaN gives bin 0);
+ * each element adds 1 to hist[2*b + positive] on the device (integer adds, so the result is exact and independent of
+ * their order); then tp[k] = sum over b > k of hist[b][1], fp[k] = sum over b > k of hist[b][0], fn[k] = P - tp[k]
+ * with P the number of positives (these K + 1 suffix sums run on the host). */
+int rfi_threshold_sweep(rfi_ctx* ctx, const float* scores, int scores_mem, int kind, const void* truth, int truth_dtype,
+                        int truth_mem, int64_t count, int64_t group_elems, const float* thresholds_host,
+                        int n_thresholds, int64_t* counts_host);
 
 /* ---- whole-observation prediction: the inverse of the inference-mode tiling of Preprocessor.create_dataset
  *      (preprocessing/preprocessor.py:281,317-351 keeps `original_shapes` for it; nothing in the reference inverts it).

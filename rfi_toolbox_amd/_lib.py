@@ -160,6 +160,7 @@ _PROTOS = {
     "rfi_model_load_adam": (_i, [_vp, _cp, _vp, _vp, _sz]),
     "rfi_model_set_adam_step": (_i, [_vp, _i64]),
     "rfi_model_eval_batch": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _f, _pi64, _pi64, _pi64]),
+    "rfi_model_eval_sweep": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "rfi_model_algorithmic_flops": (_i, [_vp, _i, _i, _i, _pd, _pd]),
     "rfi_model_debug_tensor": (_i, [_vp, _cp, _vp, _sz, _pi64]),
     "rfi_comm_unique_id": (_i, [_vp]),
@@ -209,6 +210,7 @@ _PROTOS = {
     "rfi_preprocess_gather": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _i]),
     "rfi_confusion_counts": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i64, _pi64, _pi64, _pi64]),
     "rfi_threshold_logits": (_i, [_vp, _vp, _i64, _f, _vp]),
+    "rfi_threshold_sweep": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i64, _i64, _vp, _i, _vp]),
     "rfi_tiling_count": (_i, [_i, _i, C.POINTER(Tiling), _pi64]),
     "rfi_stitch_patches": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(Tiling), _i, _f, _vp, _i, _vp, _i]),
     "rfi_model_predict_flags": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(Tiling), _i, _i, _f, _vp, _i, _vp, _i]),

@@ -723,6 +723,29 @@ int rfi_model_eval_batch(rfi_model* m, const float* x, int x_mem, const uint8_t*
     });
 }
 
+int rfi_model_eval_sweep(rfi_model* m, const float* x, int x_mem, const uint8_t* labels, int labels_mem, int n, int h,
+                         int w, const float* thresholds_host, int n_thresholds, int64_t* counts_host) {
+    return guarded([&] {
+        RFI_REQUIRE(m->out_ch == 1, "eval_sweep: defined for out_channels == 1");
+        RFI_REQUIRE(thresholds_host && counts_host, "eval_sweep: null argument");
+        check_sweep_thresholds(thresholds_host, n_thresholds);
+        m->ctx->activate();
+        m->prepare(n, h, w);
+        const float* xd = stage_input(m, x, x_mem, n, h, w, false);
+        const uint8_t* yd = stage_labels(m, labels, labels_mem, n, h, w);
+        m->forward(xd, n, h, w, m->training);
+        const int64_t cnt = (int64_t)n * h * w * m->out_scale * m->out_scale;
+        std::vector<unsigned long long> hist(2 * ((size_t)n_thresholds + 1));
+        CallScope sc(m->ctx);
+        const float* dthr = sc.in(thresholds_host, RFI_HOST, (size_t)n_thresholds);
+        // what eval_batch thresholds: sigmoid of the model's output, whatever the model returns (evaluate_model.py:44-47)
+        launch_threshold_sweep(m->ctx, m->buf(m->head_sigmoid ? m->probs : m->logits), RFI_VALUES_LOGITS, yd, RFI_U8, 1, cnt,
+                               dthr, n_thresholds, sc.out(hist.data(), RFI_HOST, hist.size()));
+        sc.finish();
+        threshold_sweep_counts(hist.data(), 1, n_thresholds, counts_host);
+    });
+}
+
 int rfi_model_grad_accumulate(rfi_model* m, int phase) {
     return guarded([&] {
         RFI_REQUIRE(phase >= 0 && phase <= 2, "grad_accumulate: phase 0 (begin), 1 (add the current gradients), 2 (end: sum -> gradients)");

@@ -657,6 +657,32 @@ int rfi_readback_end(rfi_ctx* ctx, void* dst_host, size_t bytes) {
         ctx->readback_bytes = 0;
     });
 }
+// ---- confusion counts at every threshold from one pass (threshold_sweep.hip)
+int rfi_threshold_sweep(rfi_ctx* ctx, const float* scores, int scores_mem, int kind, const void* truth, int truth_dtype,
+                        int truth_mem, int64_t count, int64_t group_elems, const float* thresholds_host, int n_thresholds,
+                        int64_t* counts_host) {
+    return guarded([&] {
+        RFI_REQUIRE(ctx && scores && truth && thresholds_host && counts_host, "threshold_sweep: null argument");
+        check_sweep_thresholds(thresholds_host, n_thresholds);
+        RFI_REQUIRE(kind == RFI_VALUES_LOGITS || kind == RFI_VALUES_PROBS, "threshold_sweep: kind must be logits or probabilities");
+        RFI_REQUIRE(truth_dtype == RFI_U8 || truth_dtype == RFI_FLOAT32, "threshold_sweep: truth must be u8 or f32");
+        RFI_REQUIRE((scores_mem == RFI_HOST || scores_mem == RFI_DEVICE) && (truth_mem == RFI_HOST || truth_mem == RFI_DEVICE),
+                    "threshold_sweep: bad memory kind");
+        RFI_REQUIRE(count >= 1 && group_elems >= 1 && count % group_elems == 0 && count / group_elems <= 65535,
+                    "threshold_sweep: count must be a positive multiple of group_elems, at most 65535 groups");
+        const int64_t n_groups = count / group_elems;
+        std::vector<unsigned long long> hist((size_t)n_groups * 2 * ((size_t)n_thresholds + 1));
+        ctx->activate();
+        CallScope sc(ctx);
+        const float* ds = sc.in(scores, scores_mem, (size_t)count);
+        const void* dt = sc.in(truth, truth_mem, (size_t)count * (truth_dtype == RFI_U8 ? 1 : 4));
+        const float* dthr = sc.in(thresholds_host, RFI_HOST, (size_t)n_thresholds);
+        launch_threshold_sweep(ctx, ds, kind, dt, truth_dtype, n_groups, group_elems, dthr, n_thresholds,
+                               sc.out(hist.data(), RFI_HOST, hist.size()));
+        sc.finish();
+        threshold_sweep_counts(hist.data(), n_groups, n_thresholds, counts_host);
+    });
+}
 // ---- training augmentation (augment.hip)
 static void check_augment_config(const rfi_augment_config* cfg, int n, int h, int w) {
     RFI_REQUIRE(cfg, "augment: null config");

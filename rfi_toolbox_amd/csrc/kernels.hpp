@@ -318,6 +318,14 @@ void launch_confusion(rfi_ctx* ctx, const void* pred, int pred_dtype, const void
                       int truth_dtype, int64_t count, unsigned long long* counts3);
 void launch_threshold(rfi_ctx* ctx, const float* logits, int64_t count, float threshold,
                       uint8_t* mask);
+// confusion counts at every threshold in one pass (threshold_sweep.hip).  hist: n_groups x (K + 1) bins x {negative,
+// positive} 64-bit words on the device (zeroed here); thr_dev: K strictly increasing thresholds on the device;
+// threshold_sweep_counts turns a host copy of hist into counts[g][k] = (tp, fp, fn); arithmetic in include/rfi_hip.h
+void launch_threshold_sweep(rfi_ctx* ctx, const float* scores, int kind, const void* truth, int truth_dtype,
+                            int64_t n_groups, int64_t group_elems, const float* thr_dev, int K,
+                            unsigned long long* hist);
+void check_sweep_thresholds(const float* thr_host, int K);       // 1 .. 1024 finite, strictly increasing, or throws
+void threshold_sweep_counts(const unsigned long long* hist, int64_t n_groups, int K, int64_t* counts);
 // inverse of the inference tiling (stitch.hip): patch values (n_planes x tiling_patches_per_plane x ps x ps) -> flags
 // (and prob when non-null), n_planes x C x T; semantics in include/rfi_hip.h (rfi_stitch_patches)
 int64_t tiling_patches_per_plane(int C, int T, const rfi_tiling& tiling);

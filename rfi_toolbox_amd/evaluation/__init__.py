@@ -2,9 +2,11 @@
 flagging-quality statistics (evaluation/statistics.py:10-229)."""
 from .metrics import (compute_dice, compute_f1, compute_iou, compute_precision, compute_recall,
                       confusion_counts, evaluate_segmentation)
+from .sweep import ThresholdSweep, default_thresholds, sweep_from_counts, threshold_sweep
 from .statistics import (compute_calcquality, compute_ffi, compute_statistics, flag_statistics,
                          print_statistics_comparison)
 
 __all__ = ["compute_iou", "compute_precision", "compute_recall", "compute_f1", "compute_dice",
            "evaluate_segmentation", "confusion_counts", "compute_statistics", "compute_ffi", "compute_calcquality",
-           "print_statistics_comparison", "flag_statistics"]
+           "print_statistics_comparison", "flag_statistics", "threshold_sweep", "ThresholdSweep", "sweep_from_counts",
+           "default_thresholds"]

@@ -416,6 +416,22 @@ class HipSegmenter:
         del keep
         return tp.value, fp.value, fn.value
 
+    def eval_sweep(self, data, mask, thresholds):
+        """int64 (K, 3): ``eval_batch(data, mask, t)`` for every ``t`` of ``thresholds`` from ONE forward pass (more than
+        1024 distinct thresholds: one pass per 1024).  Rows follow the caller's order, duplicates included."""
+        from ..evaluation.sweep import MAX_THRESHOLDS, prepare_thresholds
+        thr, uniq, inverse = prepare_thresholds(thresholds)
+        n, h, w, xp, xm, yp, ym, keep = self._xy(data, mask, True)
+        counts = np.empty((uniq.size, 3), np.int64)
+        for k0 in range(0, uniq.size, MAX_THRESHOLDS):
+            chunk = np.ascontiguousarray(uniq[k0:k0 + MAX_THRESHOLDS])
+            out = np.empty((chunk.size, 3), np.int64)
+            check(lib.rfi_model_eval_sweep(self._h, C.c_void_p(xp), xm, C.c_void_p(yp), ym, n, h, w,
+                                           chunk.ctypes.data_as(C.c_void_p), chunk.size, out.ctypes.data_as(C.c_void_p)))
+            counts[k0:k0 + chunk.size] = out
+        del keep
+        return counts[inverse]
+
     def algorithmic_flops(self, n, h, w):
         f, s = C.c_double(), C.c_double()
         check(lib.rfi_model_algorithmic_flops(self._h, n, h, w, C.byref(f), C.byref(s)))

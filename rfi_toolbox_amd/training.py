@@ -59,6 +59,38 @@ def evaluate_rfi_model(model, dataset, batch_size=4, threshold=0.5):
     return {k: float(np.mean([m[k] for m in per_batch])) for k in per_batch[0]}
 
 
+def sweep_rfi_model(model, dataset, batch_size=4, thresholds=None):
+    """``evaluate_rfi_model`` at every threshold from one forward pass per batch.  Returns a dict: ``thresholds``
+    (float32, the caller's order; None: 0.01 ... 0.99), ``mean_per_batch`` metric -> (K,) under the reference's rule
+    (the mean of the per-batch metrics, evaluate_model.py:54-56 -- at a threshold of the sweep it equals
+    ``evaluate_rfi_model(..., threshold=t)``), ``pooled`` the ``ThresholdSweep`` of all batches' counts together,
+    ``best`` metric -> (threshold, value) under the per-batch rule, ties to the lowest threshold."""
+    from .evaluation.sweep import prepare_thresholds, sweep_from_counts
+    thr = prepare_thresholds(thresholds)[0]
+    images, labels = _pair(dataset)
+    was_training = model.training
+    model.eval()
+    counts = []
+    try:
+        for sel in _batches(len(images), batch_size):
+            counts.append(model.eval_sweep(images[sel], labels[sel], thr))
+    finally:
+        model.train(was_training)
+    if not counts:
+        raise ValueError("empty dataset")
+    rules = {"iou": _iou, "precision": _precision, "recall": _recall, "f1": _f1, "dice": _dice}
+    mean = {name: np.array([float(np.mean([f(*(int(v) for v in c[k])) for c in counts])) for k in range(thr.size)])
+            for name, f in rules.items()}
+    order = np.argsort(thr, kind="stable")
+    best = {}
+    for name, curve in mean.items():
+        at = order[int(np.argmax(curve[order]))]
+        best[name] = (float(thr[at]), float(curve[at]))
+    counts = np.stack(counts)
+    pooled = sweep_from_counts(thr, counts.sum(axis=0), int(np.prod(np.shape(labels), dtype=np.int64)))
+    return {"thresholds": thr, "mean_per_batch": mean, "pooled": pooled, "best": best}
+
+
 def save_checkpoint(path, model, epoch=None, loss=None, args=None, optimizer_hyper=None):
     """The dict train_model.py:177-183 writes (or :190-193 when epoch is None)."""
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)

@@ -3,12 +3,15 @@
 toolbox exists for ("established statistical methods (TFCROP, RFLAG, AOFlagger)" against a segmentation model).
 
     python tools/compare_flaggers.py [--source simulator|synthetic] [--samples 8] [--size 256] [--seed 0] [--ntime N]
-                                     [--checkpoint unet.pt --width 16]
+                                     [--checkpoint unet.pt --width 16 [--sweep]]
 
 Planes come from ``RFISimulator.generate_batch`` (default) or from ``oracle/synth_ref.generate`` with a fixed event list on
 96 x 160 planes.  Every flagger runs on the device: ``sumthreshold_flags``, ``tfcrop_flags`` and ``rflag_flags``,
 the last two also followed by ``extend_flags`` as CASA users run them, and with ``--checkpoint`` ``predict_flags`` of a
-``UNet(3, 1, --width)``.  One table: ``evaluate_segmentation`` against the truth mask and ``compute_ffi`` per flagger."""
+``UNet(3, 1, --width)``.  One table: ``evaluate_segmentation`` against the truth mask and ``compute_ffi`` per flagger.
+``--sweep`` adds the row ``unet@best-f1``: the same model cut where its f1 is highest instead of at 0.5, the cut found by
+one ``threshold_sweep`` over the probabilities ``predict_flags`` leaves on the device.  That cut is chosen on the very
+planes it is scored on, so the row is the model's ceiling on these planes, not a held-out figure."""
 import argparse
 import os
 import sys
@@ -31,7 +34,11 @@ def parse(argv=None):
     ap.add_argument("--checkpoint", default=None, help="a checkpoint of UNet(3, 1, --width): adds predict_flags to the table")
     ap.add_argument("--width", type=int, default=16)
     ap.add_argument("--patch-size", type=int, default=128)
-    return ap.parse_args(argv)
+    ap.add_argument("--sweep", action="store_true", help="with --checkpoint: add the model at its best-f1 threshold on these planes")
+    args = ap.parse_args(argv)
+    if args.sweep and not args.checkpoint:
+        ap.error("--sweep needs --checkpoint")
+    return args
 
 
 def planes_and_truth(args):
@@ -48,7 +55,8 @@ def planes_and_truth(args):
     return data, np.ascontiguousarray(np.repeat(mask[:, None], 4, axis=1))     # one truth mask for a sample's four planes
 
 
-def flaggers(args):
+def flaggers(args, truth, chosen):
+    """[(name, planes -> flags)]; the --sweep row leaves its cut and the f1 the sweep found in ``chosen``"""
     from rfi_toolbox_amd import flagging as fl
     ext = dict(ntime=args.ntime, growaround=True, flagneartime=True, flagnearfreq=True, out="device")
     table = [("sumthreshold", lambda d: fl.sumthreshold_flags(d, out="device")),
@@ -66,6 +74,16 @@ def flaggers(args):
         def learned(d):
             return predict_flags(model, d, patch_size=args.patch_size).view(np.uint8)
         table.append(("predict_flags", learned))
+        if args.sweep:
+            import torch
+            from rfi_toolbox_amd.evaluation import threshold_sweep
+
+            def learned_at_best_cut(d):
+                _, prob = predict_flags(model, torch.from_numpy(d).cuda(), patch_size=args.patch_size, return_probabilities=True)
+                chosen["threshold"], chosen["f1"] = threshold_sweep(prob, truth).best("f1")
+                cut = torch.tensor(chosen["threshold"], dtype=torch.float32, device=prob.device)
+                return (prob > cut).to(torch.uint8).cpu().numpy()
+            table.append(("unet@best-f1", learned_at_best_cut))
     return table
 
 
@@ -74,8 +92,8 @@ def main(argv=None):
     from rfi_toolbox_amd.evaluation.metrics import evaluate_segmentation
     from rfi_toolbox_amd.evaluation.statistics import compute_ffi
     data, truth = planes_and_truth(args)
-    rows = []
-    for name, run in flaggers(args):
+    rows, chosen = [], {}
+    for name, run in flaggers(args, truth, chosen):
         flags = run(data)
         seg = evaluate_segmentation(flags, truth)
         ffi = compute_ffi(data, flags)
@@ -84,6 +102,9 @@ def main(argv=None):
     for name, seg, ffi in rows:
         print(f"{name:<15}{seg['iou']:>8.4f}{seg['precision']:>11.4f}{seg['recall']:>8.4f}{seg['f1']:>8.4f}{ffi['ffi']:>8.4f}"
               f"{ffi['flagged_fraction']:>9.4f}")
+    if chosen:
+        print(f"unet@best-f1: threshold {chosen['threshold']:.2f} (f1 {chosen['f1']:.4f}), the best of 0.01 ... 0.99 ON THE PLANES "
+              "SCORED ABOVE -- chosen and scored on the same data, so an upper bound for this model, not a validation result")
     return rows
 
 
