@@ -708,6 +708,54 @@ int rfi_rflag_flag(rfi_ctx* ctx, const void* data, int data_mem, int dtype, cons
 int rfi_extend_flags(rfi_ctx* ctx, const uint8_t* flags_in, int flags_mem, int n_planes, int c, int t, const rfi_extend_config* cfg,
                      uint8_t* flags_out, int out_mem);
 
+/* ---- connected components: labelling of binary planes, the component table, despeckling and the detector's instance
+ *      targets (csrc/components.hip; rfi_toolbox_amd/components.py).  Not in the reference; the labelling equals
+ *      scipy.ndimage.label bit for bit and tests/components_ref.py restates the rest in NumPy.  All integer work: results are
+ *      exact and do not depend on launch geometry or on the order of atomics.
+ *
+ *      Input: n planes [n][H][W] of RFI_U8 or RFI_FLOAT32; any non-zero element is foreground (rfi_confusion_counts' rule;
+ *      NaN is non-zero).  Planes are independent: the last row of plane i and the first row of plane i + 1 are not
+ *      neighbours.  connectivity 4 (edge neighbours) or 8 (edge and corner neighbours).  H, W >= 1, H W <= 2^30, n <= 65535.
+ *
+ *      Labels: int32 [n][H][W], 0 for background; the components of a plane are numbered 1 .. K by the smallest linear index
+ *      y W + x each one contains -- scipy.ndimage.label(mask != 0, generate_binary_structure(2, 1 | 2)).  n_components[i] = K.
+ *      Table: with comp_base[i] = the exclusive prefix sum of n_components (the caller's; `total` = its sum, < 2^31),
+ *      component l of plane i has slot comp_base[i] + l - 1: area int32 [total]; box int32 [total][4] = (xmin, ymin, xmax,
+ *      ymax), inclusive.
+ *      Despeckle (components_keep): out uint8 [n][H][W] = foreground AND area of its component >= min_area.
+ *      Instances, per plane: a component survives when area >= min_area, xmax - xmin + 1 >= min_side and ymax - ymin + 1 >=
+ *      min_side.  The G = max_instances (1 .. 256) survivors of largest area are kept, ties to the smaller label, and written
+ *      in descending area, ties ascending label, whether or not anything was cut: boxes float32 [n][G][4] = (xmin, ymin,
+ *      xmax + 1, ymax + 1) (the half-open boxes of the detector's targets), labels int32 [n][G] = 1, component int32 [n][G] =
+ *      the label the slot came from; rows >= count[i] are zero.  count [n]; n_survivors [n] (> count: the plane was cut);
+ *      base [n] = the exclusive prefix sum of count.  instance_masks: masks uint8 [sum of count][H][W],
+ *      masks[base[i] + j] = (labels_i == component[i][j]).
+ *
+ *      Method: label equivalence with union-find -- a pixel starts as its own parent, a union is atomicMin on the larger
+ *      root, judged by the value the atomic returned; tiles of 32 x 64 pixels in LDS, unions across the tile borders, then
+ *      flatten / count roots / scan / rank / renumber in launches of their own.  components_limits gives the tile's height and
+ *      width and the pixels of one root count (where the code's paths change).  The selection orders keys
+ *      (~area << 32 | label); with more than G survivors the G-th key is found by a radix select first.
+ *
+ *      Every pointer is a device pointer; nothing here allocates or synchronises.  workspace: rfi_components_ws_bytes(n, h, w)
+ *      bytes (0 for sizes out of range), 256-byte aligned, kept until the stream has passed; box and boxes 16-byte aligned.
+ *      copy_rows: `rows` rows of width_bytes from src (rows src_pitch bytes apart) to dst (dst_pitch), device to device on
+ *      the context's stream: how instance targets of stride G reach the detector's buffers of another stride. ---- */
+int rfi_components_limits(int32_t* tile_h, int32_t* tile_w, int32_t* scan_block);      /* host only */
+size_t rfi_components_ws_bytes(int n, int h, int w);                                    /* host only */
+int rfi_op_label_components(rfi_ctx* ctx, const void* masks, int dtype, int n, int h, int w, int connectivity, void* workspace,
+                            int32_t* labels, int32_t* n_components);
+int rfi_op_component_table(rfi_ctx* ctx, const int32_t* labels, int n, int h, int w, const int32_t* comp_base, int64_t total,
+                           int32_t* area, int32_t* box);
+int rfi_op_components_keep(rfi_ctx* ctx, const int32_t* labels, int n, int h, int w, const int32_t* comp_base, const int32_t* area,
+                           int min_area, uint8_t* out);
+int rfi_op_instances_select(rfi_ctx* ctx, const int32_t* n_components, const int32_t* comp_base, const int32_t* area, const int32_t* box,
+                            int n, int min_area, int min_side, int max_instances, float* boxes, int32_t* labels, int32_t* count,
+                            int32_t* n_survivors, int32_t* base, int32_t* component);
+int rfi_op_instance_masks(rfi_ctx* ctx, const int32_t* labels, int n, int h, int w, const int32_t* component, const int32_t* count,
+                          const int32_t* base, int max_instances, uint8_t* masks);
+int rfi_op_copy_rows(rfi_ctx* ctx, const void* src, size_t src_pitch, void* dst, size_t dst_pitch, size_t width_bytes, size_t rows);
+
 /* ---- kernel-level entry points (device pointers only).  Used by the parity tests to
  *      check each HIP kernel against the oracle in isolation.  impl: 0 auto, 1 direct VALU,
  *      2 MFMA implicit GEMM in native float32 (v_mfma_f32_32x32x2_f32), 3 MFMA implicit GEMM with bfloat16

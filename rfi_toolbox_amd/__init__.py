@@ -12,6 +12,8 @@ __version__ = "0.1.0"
 def __getattr__(name):
     import importlib
     if name in ("models", "evaluation", "preprocessing", "datasets", "training", "distributed", "runtime",
-                "data_generation", "core", "inference", "flagging"):
+                "data_generation", "core", "inference", "flagging", "components"):
         return importlib.import_module(f"{__name__}.{name}")
+    if name in ("label_components", "component_table", "remove_small_components", "instances_from_masks", "InstanceTargets"):
+        return getattr(importlib.import_module(f"{__name__}.components"), name)
     raise AttributeError(name)

@@ -229,6 +229,14 @@ _PROTOS = {
     "rfi_tfcrop_flag": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _i, C.POINTER(TfcropConfig), _vp, _i]),
     "rfi_rflag_flag": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _i, C.POINTER(RflagConfig), _pd, _pd, _vp, _i]),
     "rfi_extend_flags": (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(ExtendConfig), _vp, _i]),
+    "rfi_components_limits": (_i, [C.POINTER(C.c_int32)] * 3),
+    "rfi_components_ws_bytes": (_sz, [_i, _i, _i]),
+    "rfi_op_label_components": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "rfi_op_component_table": (_i, [_vp, _vp, _i, _i, _i, _vp, _i64, _vp, _vp]),
+    "rfi_op_components_keep": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp]),
+    "rfi_op_instances_select": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "rfi_op_instance_masks": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
+    "rfi_op_copy_rows": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz]),
     "rfi_op_conv3x3": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     "rfi_op_conv1x1": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     "rfi_op_conv_s2": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),

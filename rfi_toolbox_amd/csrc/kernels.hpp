@@ -393,6 +393,20 @@ uint8_t* launch_rflag_flag(rfi_ctx* ctx, const void* src, int dtype, const uint8
                            const rfi_rflag_config& cfg, const double* timedev, const double* freqdev, void* ws);
 size_t extend_ws_bytes(int planes, int C, int T);
 uint8_t* launch_extend_flags(rfi_ctx* ctx, const uint8_t* Fin, int planes, int C, int T, const rfi_extend_config& cfg, void* ws);
+// connected components (components.hip; semantics in include/rfi_hip.h, "connected components").  Device pointers; nothing
+// here allocates or synchronises.  ws holds components_ws_bytes(n, h, w); masks dtype RFI_U8 or RFI_FLOAT32.
+void components_limits(int* tile_h, int* tile_w, int* scan_block);
+size_t components_ws_bytes(int n, int h, int w);
+void launch_label_components(rfi_ctx* ctx, const void* masks, int dtype, int n, int h, int w, int connectivity, void* ws, int* labels,
+                             int* n_components);
+void launch_component_table(rfi_ctx* ctx, const int* labels, int n, int h, int w, const int* comp_base, int64_t total, int* area, int* box);
+void launch_components_keep(rfi_ctx* ctx, const int* labels, int n, int h, int w, const int* comp_base, const int* area, int min_area,
+                            uint8_t* out);
+void launch_instances_select(rfi_ctx* ctx, const int* n_components, const int* comp_base, const int* area, const int* box, int n,
+                             int min_area, int min_side, int max_instances, float* boxes, int* cls, int* count, int* n_survivors, int* base,
+                             int* component);
+void launch_instance_masks(rfi_ctx* ctx, const int* labels, int n, int h, int w, const int* component, const int* count, const int* base,
+                           int max_instances, uint8_t* masks);
 // RFISimulator waterfalls (rfi_sim.hip): draws the event table into `events` (unless p.clean), then one gather per
 // pixel into `out` (layout RFI_SIM_*) and `mask`; sizes are checked by rfi_simulate_rfi
 void launch_rfi_sim(rfi_ctx* ctx, unsigned long long seed, unsigned first_sample, int n_samples,

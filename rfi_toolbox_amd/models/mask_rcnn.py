@@ -448,18 +448,34 @@ class MaskRCNN:
     def train_step(self, images, targets, lr=1e-4, weight_decay=1e-5, max_grad_norm=1.0, masks_resident=False):
         """One training step.  masks_resident=True: the caller promises that `targets` (the SAME list object as in the
         previous step) still holds the same instance masks, so the copy already in HBM is used; otherwise the masks are
-        uploaded every step (a list refilled in place must not train the mask branch on last step's masks)."""
+        uploaded every step (a list refilled in place must not train the mask branch on last step's masks).
+
+        ``targets`` may also be the ``InstanceTargets`` of ``instances_from_masks`` (made with instance masks, on this
+        detector's GPU, for planes of the images' size): its boxes, labels, counts and instance masks are used where they are,
+        in HBM -- nothing is assembled on the host, no mask is uploaded, ``masks_resident`` is ignored -- and the step equals
+        the one on ``targets.to_list()`` bit for bit."""
+        from ..components import InstanceTargets
         from ..runtime import DeviceArray
         dev_in = isinstance(images, DeviceArray)                 # images already in HBM (float32 NHWC): no copy
         x = images if dev_in else np.ascontiguousarray(np.asarray(images, np.float32))
         n, h, w, _ = x.shape
+        inst = targets if isinstance(targets, InstanceTargets) else None
+        if inst is not None:
+            if len(inst) != n or inst.shape != (h, w):
+                raise ValueError(f"MaskRCNN.train_step: targets of {len(inst)} planes of {inst.shape[0]} x {inst.shape[1]} for "
+                                 f"{n} images of {h} x {w}")
+            if inst.masks is None or not isinstance(inst.boxes, DeviceArray) or inst.boxes.ctx is not self.backbone.ctx:
+                raise ValueError("MaskRCNN.train_step: InstanceTargets must hold instance masks and live on the detector's GPU")
         ctx, F, k1 = self.backbone.ctx, self.F, self.num_classes
         H = ctx.handle
         P = lambda d: C.c_void_p(d.ptr)  # noqa: E731
         for m in (self.rpn, self.box, self.mask):
             m.train()
-        gts = [np.asarray(t["boxes"], np.float32).reshape(-1, 4) for t in targets]
-        gcount = np.asarray([len(g) for g in gts], np.int32)
+        if inst is not None:
+            gcount = inst.count_host
+        else:
+            gts = [np.asarray(t["boxes"], np.float32).reshape(-1, 4) for t in targets]
+            gcount = np.asarray([len(g) for g in gts], np.int32)
         b = self._buffers(n, h, w, int(gcount.max()) if n else 0)
         if dev_in:
             b.x_in = x
@@ -467,14 +483,23 @@ class MaskRCNN:
             b.x.copy_from(x)
             b.x_in = b.x
         G = b.gcap
-        # ---- up: the ground truth (boxes, class labels, counts) -- a few hundred bytes per image
-        gt = np.zeros((n, G, 4), np.float32)
-        gl = np.zeros((n, G), np.int32)
-        for i, (g, t) in enumerate(zip(gts, targets)):
-            gt[i, :len(g)] = g
-            gl[i, :len(g)] = np.asarray(t["labels"], np.int32).reshape(-1)
         gbase = np.concatenate([[0], np.cumsum(gcount)]).astype(np.int32)
-        b.gt.copy_from(gt); b.gt_labels.copy_from(gl); b.gt_count.copy_from(gcount); b.gt_base.copy_from(gbase[:n])
+        if inst is not None:
+            # ---- the ground truth is in HBM already: its rows of max_instances slots go into the buffers' rows of G (zero behind)
+            gi = min(G, inst.boxes.shape[1])                     # (every count is <= both)
+            b.gt.zero_(); b.gt_labels.zero_()
+            check(lib.rfi_op_copy_rows(H, P(inst.boxes), inst.boxes.shape[1] * 16, P(b.gt), G * 16, gi * 16, n))
+            check(lib.rfi_op_copy_rows(H, P(inst.labels), inst.labels.shape[1] * 4, P(b.gt_labels), G * 4, gi * 4, n))
+            check(lib.rfi_op_copy_rows(H, P(inst.count), 4 * n, P(b.gt_count), 4 * n, 4 * n, 1))
+            check(lib.rfi_op_copy_rows(H, P(inst.base), 4 * n, P(b.gt_base), 4 * n, 4 * n, 1))
+        else:
+            # ---- up: the ground truth (boxes, class labels, counts) -- a few hundred bytes per image
+            gt = np.zeros((n, G, 4), np.float32)
+            gl = np.zeros((n, G), np.int32)
+            for i, (g, t) in enumerate(zip(gts, targets)):
+                gt[i, :len(g)] = g
+                gl[i, :len(g)] = np.asarray(t["labels"], np.int32).reshape(-1)
+            b.gt.copy_from(gt); b.gt_labels.copy_from(gl); b.gt_count.copy_from(gcount); b.gt_base.copy_from(gbase[:n])
         b.n_sampled.zero_()
         seed, step = self.seed & 0xFFFFFFFFFFFFFFFF, self.sample_step & 0xFFFFFFFF
         self.sample_step += 1
@@ -553,14 +578,18 @@ class MaskRCNN:
                                                    7, 7, 2))
         # ---- mask branch on the foreground RoIs: targets = the matched ground-truth mask, RoIAligned to 28 x 28 at 0.5
         if Rf:
-            if b.masks is None or b.masks_n < gbase[-1]:
-                b.masks, b.masks_n, b.masks_of = ctx.empty((int(gbase[-1]), h, w), np.uint8), int(gbase[-1]), None
-            if not (masks_resident and b.masks_of is targets):   # (resident only on the caller's word AND for the same list object)
-                self._upload(b.masks, np.concatenate([np.asarray(t["masks"], np.uint8).reshape(-1, h, w) for t in targets]))
-                b.masks_of = targets
+            if inst is not None:
+                gt_masks = inst.masks                            # (sum of count, h, w) in HBM
+            else:
+                if b.masks is None or b.masks_n < gbase[-1]:
+                    b.masks, b.masks_n, b.masks_of = ctx.empty((int(gbase[-1]), h, w), np.uint8), int(gbase[-1]), None
+                if not (masks_resident and b.masks_of is targets):   # (resident only on the caller's word AND for the same list object)
+                    self._upload(b.masks, np.concatenate([np.asarray(t["masks"], np.uint8).reshape(-1, h, w) for t in targets]))
+                    b.masks_of = targets
+                gt_masks = b.masks
             check(lib.rfi_op_roi_align_ml(H, b.pf4, n, h0, w0, F, 0.25, P(b.rois_m), P(b.lvl_m), C.c_void_p(b.counts.ptr + 4), Rf, 14, 14, 2,
                                           P(b.roi14)))
-            check(lib.rfi_op_mask_targets(H, P(b.masks), int(gbase[-1]), h, w, P(b.rois_g), Rf, 28, 28, 2, P(b.mask_t)))
+            check(lib.rfi_op_mask_targets(H, P(gt_masks), int(gbase[-1]), h, w, P(b.rois_g), Rf, 28, 28, 2, P(b.mask_t)))
             check(lib.rfi_train_forward_backward(self.mask._h, P(b.roi14), DEVICE, P(b.mask_t), DEVICE, Rf, 14, 14, None))
             check(lib.rfi_model_input_grad(self.mask._h, P(b.roi14_grad), DEVICE))
             check(lib.rfi_op_roi_align_ml_backward(H, b.pdf4, n, h0, w0, F, 0.25, P(b.roi14_grad), P(b.rois_m), P(b.lvl_m), P(b.fg_start), Rf,

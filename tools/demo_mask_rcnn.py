@@ -3,9 +3,10 @@
 well ``predict`` recovers them: best box IoU per ground-truth region and the IoU of the union mask.  A functional
 demonstration (the pieces are parity-tested one by one), not a benchmark.
 
-    python tools/demo_mask_rcnn.py [--steps 200] [--dtype float32|bfloat16] [--detect]
+    python tools/demo_mask_rcnn.py [--steps 200] [--dtype float32|bfloat16] [--detect] [--from-masks]
 
-``--detect`` runs ``MaskRCNN.detect`` (inference on the device) too and prints whether both forms agree."""
+``--from-masks`` trains on instance targets that ``instances_from_masks`` builds on the GPU from ONE binary mask per image
+(the union of its rectangles: two that touch become one instance) instead of the per-rectangle targets.  ``--detect`` runs ``MaskRCNN.detect`` (inference on the device) too and prints whether both forms agree."""
 import argparse
 import os
 import sys
@@ -43,15 +44,22 @@ def main():
     ap.add_argument("--dtype", default="float32")
     ap.add_argument("--images", type=int, default=4)
     ap.add_argument("--detect", action="store_true", help="run MaskRCNN.detect too and compare it with predict")
+    ap.add_argument("--from-masks", action="store_true", help="build the targets from each image's binary mask by instances_from_masks")
     a = ap.parse_args()
     import torch
     from rfi_toolbox_amd.models import MaskRCNN
     torch.manual_seed(0)
     det = MaskRCNN(2, 3, 16, 64, 128, seed=0).set_compute_dtype(a.dtype)
     x, targets = batch(np.random.default_rng(1), a.images, 128)
+    step_targets = targets
+    if a.from_masks:
+        from rfi_toolbox_amd.components import instances_from_masks
+        step_targets = instances_from_masks(np.stack([t["masks"].any(0) for t in targets]))
+        targets = step_targets.to_list()                # (what the report below compares against)
+        print(f"instances per image from the binary masks: {step_targets.count_host.tolist()}")
     t0 = time.time()
     for s in range(a.steps):
-        l = det.train_step(x, targets, lr=2e-3, weight_decay=0.0, max_grad_norm=10.0)
+        l = det.train_step(x, step_targets, lr=2e-3, weight_decay=0.0, max_grad_norm=10.0)
         if s % 20 == 0 or s == a.steps - 1:
             print(f"step {s:4d}  " + "  ".join(f"{k[5:] or 'total'} {v:.4f}" for k, v in l.items()), flush=True)
     print(f"{a.steps} steps in {time.time() - t0:.1f} s")
