@@ -10,12 +10,17 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RFI_HIP_LIB") or os.path.join(_HERE, "librfi_hip.so")     # (override: A/B runs of two builds)
 
 HOST, DEVICE = 0, 1
 C128, C64, F64, F32 = 0, 1, 2, 3
 U8, FLOAT32 = 0, 1
+VALUE_CODES = {np.dtype(np.complex128): C128, np.dtype(np.complex64): C64, np.dtype(np.float64): F64, np.dtype(np.float32): F32}
+COMPLEX_CODES = {d: c for d, c in VALUE_CODES.items() if d.kind == "c"}
+MASK_CODES = {np.dtype(np.uint8): U8, np.dtype(np.float32): FLOAT32}
 IMPL_AUTO, IMPL_DIRECT, IMPL_MFMA, IMPL_MFMA_BF16, IMPL_MFMA_BF16X3, IMPL_PLANES_X3, IMPL_PLANES_BF16, IMPL_WS_X3, IMPL_WS_BF16 = 0, 1, 2, 3, 4, 5, 6, 7, 8
 
 

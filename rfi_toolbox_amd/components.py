@@ -22,8 +22,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import DEVICE, FLOAT32, HOST, U8, check, lib
-from .runtime import Context, DeviceArray, is_torch, torch
+from ._lib import DEVICE, HOST, MASK_CODES, check, lib
+from .runtime import DeviceArray, P, check_out, context_for, describe, is_torch, operand, torch
 
 MAX_PLANE = 1 << 30
 MAX_PLANES = 65535
@@ -39,15 +39,11 @@ def limits():
 
 
 # ---------------------------------------------------------------------------------------------- argument plumbing
-def _shape(x):
-    return tuple(int(s) for s in (x.shape if isinstance(x, DeviceArray) or is_torch(x) else np.asarray(x).shape))
-
-
 def _check_masks(name, masks, connectivity):
     """-> (shape, n, H, W) after the checks every function starts with (no device call)."""
     if connectivity not in (4, 8) or isinstance(connectivity, (bool, np.bool_)):
         raise ValueError(f"connectivity must be 4 or 8, got {connectivity!r}")
-    shape = _shape(masks)
+    shape, dt, _, owner = describe(masks)
     if len(shape) < 2:
         raise ValueError(f"{name} must have shape (..., H, W) with ndim >= 2, got shape {shape}")
     h, w = shape[-2:]
@@ -56,56 +52,15 @@ def _check_masks(name, masks, connectivity):
     n = int(np.prod(shape[:-2], dtype=np.int64))
     if n > MAX_PLANES:
         raise ValueError(f"{name}: at most {MAX_PLANES} planes in one call, got {n}")
-    if isinstance(masks, DeviceArray) and masks.dtype not in (np.dtype(np.uint8), np.dtype(np.bool_), np.dtype(np.float32)):
-        raise ValueError(f"a device array of {name} must be uint8, bool or float32, got {masks.dtype}")
+    if owner is not None and dt not in (np.dtype(np.uint8), np.dtype(np.bool_), np.dtype(np.float32)):
+        raise ValueError(f"a device array of {name} must be uint8, bool or float32, got {dt}")
     return shape, n, h, w
-
-
-def _check_out(out):
-    if out not in ("host", "device"):
-        raise ValueError(f"out must be 'host' or 'device', got {out!r}")
 
 
 def _positive(name, v):
     if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 1:
         raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
     return int(min(v, (1 << 31) - 1))
-
-
-def _context(device, x):
-    if isinstance(x, DeviceArray):
-        return x.ctx
-    if is_torch(x) and x.is_cuda and device is None:
-        return Context.get(x.device.index or 0)
-    return Context.get(device)
-
-
-def _device_masks(masks, ctx):
-    """-> (pointer, dtype code, keepalive) of the masks in HBM as uint8 or float32 (other dtypes: ``!= 0`` as uint8)."""
-    if isinstance(masks, DeviceArray):
-        if masks.ctx is not ctx:
-            raise ValueError("device array belongs to another context")
-        return masks.ptr, FLOAT32 if masks.dtype == np.float32 else U8, masks
-    if is_torch(masks):
-        t = masks.detach()
-        if t.is_cuda:
-            if t.device.index not in (None, ctx.device_index):
-                raise ValueError(f"tensor is on {t.device}, the context on GPU {ctx.device_index}")
-            if t.dtype == torch.bool:
-                t = t.to(torch.uint8)
-            elif t.dtype not in (torch.uint8, torch.float32):
-                t = (t != 0).to(torch.uint8)
-            t = t.contiguous()
-            torch.cuda.current_stream(t.device).synchronize()        # hand over to the context's stream
-            return t.data_ptr(), FLOAT32 if t.dtype == torch.float32 else U8, t
-        masks = t.numpy()
-    a = np.asarray(masks)
-    if a.dtype == np.bool_:
-        a = a.view(np.uint8)
-    elif a.dtype not in (np.dtype(np.uint8), np.dtype(np.float32)):
-        a = (a != 0).view(np.uint8)
-    d = ctx.to_device(a)
-    return d.ptr, FLOAT32 if a.dtype == np.float32 else U8, d
 
 
 def _read_ints(ctx, dev, count):
@@ -133,9 +88,10 @@ class _Labelled:
     (``labels``, when the labels are the result) or in the context's scratch."""
 
     def __init__(self, masks, n, h, w, connectivity, device, own_labels=False):
-        self.ctx, self.n, self.h, self.w = _context(device, masks), n, h, w
+        self.ctx, self.n, self.h, self.w = context_for(device, masks), n, h, w
         ctx = self.ctx
-        ptr, code, self._input = _device_masks(masks, ctx)
+        m = operand(masks, ctx, (np.uint8, np.float32), "nonzero", to_device=True)      # (the kernel reads HBM only)
+        ptr, code, self._input = m.ptr, MASK_CODES[m.dtype], m.keep
         ws_bytes, lab_bytes = int(lib.rfi_components_ws_bytes(n, h, w)), (4 * n * h * w + 255) & ~255
         self.n_components = ctx.empty((n,), np.int32)
         if own_labels:
@@ -169,9 +125,9 @@ def label_components(masks, connectivity=8, out="host", device=None):
     leading shape -- ``scipy.ndimage.label(mask != 0, generate_binary_structure(2, 1 if connectivity == 4 else 2))`` of every
     plane.  ``out="host"``: NumPy arrays; ``out="device"``: two ``DeviceArray``s, and nothing is read back."""
     shape, n, h, w = _check_masks("masks", masks, connectivity)
-    _check_out(out)
+    check_out(out)
     if n == 0:
-        ctx = _context(device, masks) if out == "device" else None
+        ctx = context_for(device, masks) if out == "device" else None
         return (ctx.empty(shape, np.int32), ctx.empty(shape[:-2], np.int32)) if ctx else (np.zeros(shape, np.int32),
                                                                                           np.zeros(shape[:-2], np.int32))
     lab = _Labelled(masks, n, h, w, connectivity, device, own_labels=out == "device")
@@ -205,7 +161,7 @@ def remove_small_components(flags, min_area, connectivity=8, out="host", device=
     (it sizes the area table); with a device-resident input nothing else crosses PCIe."""
     shape, n, h, w = _check_masks("flags", flags, connectivity)
     min_area = _positive("min_area", min_area)
-    _check_out(out)
+    check_out(out)
     ctx = None
     if n:
         lab = _Labelled(flags, n, h, w, connectivity, device)
@@ -216,11 +172,11 @@ def remove_small_components(flags, min_area, connectivity=8, out="host", device=
                                          C.c_void_p(lab.area.ptr), min_area, C.c_void_p(res.ptr)))
         res._keep = lab
     if out == "device":
-        return res if n else _context(device, flags).empty(shape, np.uint8)
+        return res if n else context_for(device, flags).empty(shape, np.uint8)
     host = res.numpy() if n else np.zeros(shape, np.uint8)
     if is_torch(flags):
         return torch.from_numpy(host).to(device=flags.device, dtype=flags.dtype)
-    dt = flags.dtype if isinstance(flags, DeviceArray) else np.asarray(flags).dtype
+    dt = describe(flags)[1]
     return host.view(np.bool_) if dt == np.bool_ else host.astype(dt, copy=False)
 
 
@@ -290,7 +246,6 @@ def instances_from_masks(masks, connectivity=8, min_area=1, min_side=1, max_inst
     k_host = lab.table()
     boxes, labels, component = ctx.empty((n, G, 4), np.float32), ctx.empty((n, G), np.int32), ctx.empty((n, G), np.int32)
     count, surv, base = ctx.empty((n,), np.int32), ctx.empty((n,), np.int32), ctx.empty((n,), np.int32)
-    P = lambda d: C.c_void_p(d.ptr)  # noqa: E731
     check(lib.rfi_op_instances_select(ctx.handle, P(lab.n_components), P(lab.comp_base), P(lab.area), P(lab.box), n, min_area, min_side, G,
                                       P(boxes), P(labels), P(count), P(surv), P(base), P(component)))
     count_host, surv_host = _read_ints(ctx, count, n), _read_ints(ctx, surv, n)

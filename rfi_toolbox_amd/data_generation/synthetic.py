@@ -95,7 +95,7 @@ class SyntheticWaterfalls:
     def sample_device(self, n_samples, device=None, dtype=np.complex128, seed=None):
         """n_samples waterfalls generated IN HBM -> (planes DeviceArray (n, npol, nc, nt) complex,
         flags DeviceArray uint8 same shape, events per sample).  Only the event table crosses PCIe."""
-        from .._lib import C128, C64, DEVICE, HOST, check, lib
+        from .._lib import COMPLEX_CODES, DEVICE, HOST, check, lib
         from ..runtime import Context
         ctx = Context.get(device)
         events = [self.draw_events() for _ in range(n_samples)]
@@ -109,7 +109,7 @@ class SyntheticWaterfalls:
                 flat[k] = (kind, r0, r1, c0, c1, 0, amp)
                 k += 1
             offs[i + 1] = k
-        code = {np.dtype(np.complex128): C128, np.dtype(np.complex64): C64}[np.dtype(dtype)]
+        code = COMPLEX_CODES[np.dtype(dtype)]
         shape = (n_samples, self.npol, self.nc, self.nt)
         planes, flags = ctx.empty(shape, dtype), ctx.empty(shape, np.uint8)
         if seed is None:
@@ -186,7 +186,7 @@ def make_training_patches_device(n_patches, size=128, seed=0, device=None, count
     tiling / blank-patch test / channels / labels by the gather kernels, results left on the device.
     -> (images DeviceArray (n, size, size, 3) float32, labels DeviceArray (n, size, size) uint8).
     Only event tables and 16-byte patch-table entries cross PCIe."""
-    from .._lib import C128, C64
+    from .._lib import COMPLEX_CODES
     from ..preprocessing.preprocessor import gather_patches, select_patches
     from ..runtime import Context
     ctx = Context.get(device)
@@ -194,7 +194,7 @@ def make_training_patches_device(n_patches, size=128, seed=0, device=None, count
         scale = (size * size) / (1024.0 * 1024.0)
         counts = {k: max(1, int(round(v * scale * 4))) for k, v in YAML_4K_COUNTS.items()}
     gen = SyntheticWaterfalls(size, size, 1, counts=counts, seed=seed)
-    code = {np.dtype(np.complex128): C128, np.dtype(np.complex64): C64}[np.dtype(dtype)]
+    code = COMPLEX_CODES[np.dtype(dtype)]
     images, labels = ctx.empty((n_patches, size, size, 3), np.float32), ctx.empty((n_patches, size, size), np.uint8)
     state = np.random.get_state()
     np.random.seed(seed)

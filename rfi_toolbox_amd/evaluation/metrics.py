@@ -8,47 +8,20 @@ import ctypes as C
 
 import numpy as np
 
-from .._lib import DEVICE, FLOAT32, HOST, U8, check, lib
-from ..runtime import Context, DeviceArray, is_torch
-
-
-def _operand(a, ctx):
-    """-> (ptr, dtype_code, mem, count, keepalive)"""
-    if isinstance(a, DeviceArray):
-        code = {np.dtype(np.uint8): U8, np.dtype(np.float32): FLOAT32}[a.dtype]
-        return a.ptr, code, DEVICE, int(np.prod(a.shape, dtype=np.int64)), a
-    if is_torch(a):
-        import torch
-        t = a.detach()
-        if t.dtype == torch.bool:
-            t = t.to(torch.uint8)
-        if t.dtype not in (torch.uint8, torch.float32):
-            t = (t != 0).to(torch.uint8)
-        t = t.contiguous()
-        if t.is_cuda:
-            torch.cuda.current_stream(t.device).synchronize()
-            return t.data_ptr(), (U8 if t.dtype == torch.uint8 else FLOAT32), DEVICE, t.numel(), t
-        a = t.numpy()
-    a = np.asarray(a)
-    if a.dtype == np.bool_:
-        a = a.view(np.uint8) if a.flags.c_contiguous else a.astype(np.uint8)
-    elif a.dtype not in (np.uint8, np.float32):
-        a = (a != 0).astype(np.uint8)
-    a = np.ascontiguousarray(a)
-    return a.ctypes.data, (U8 if a.dtype == np.uint8 else FLOAT32), HOST, a.size, a
+from .._lib import MASK_CODES, check, lib
+from ..runtime import context_for, describe, operand
 
 
 def confusion_counts(pred, true, device=None):
     """(tp, fp, fn) as Python ints."""
-    ctx = Context.get(device)
-    pp, pd, pm, pn, k1 = _operand(pred, ctx)
-    tp_, td, tm, tn, k2 = _operand(true, ctx)
+    pn, tn = (int(np.prod(describe(a)[0], dtype=np.int64)) for a in (pred, true))
     if pn != tn:
         raise ValueError(f"pred has {pn} elements, true has {tn}")
+    ctx = context_for(device, pred, true)
+    p, t = (operand(a, ctx, (np.uint8, np.float32), "nonzero") for a in (pred, true))
     tp, fp, fn = C.c_int64(), C.c_int64(), C.c_int64()
-    check(lib.rfi_confusion_counts(ctx.handle, C.c_void_p(pp), pd, pm, C.c_void_p(tp_), td, tm, pn,
-                                   C.byref(tp), C.byref(fp), C.byref(fn)))
-    del k1, k2
+    check(lib.rfi_confusion_counts(ctx.handle, C.c_void_p(p.ptr), MASK_CODES[p.dtype], p.mem, C.c_void_p(t.ptr), MASK_CODES[t.dtype],
+                                   t.mem, pn, C.byref(tp), C.byref(fp), C.byref(fn)))
     return tp.value, fp.value, fn.value
 
 

@@ -18,8 +18,8 @@ from collections import namedtuple
 
 import numpy as np
 
-from .._lib import C64, C128, DEVICE, F32, F64, FS_ALL, FS_CLEAN, FS_MEDIANS, HOST, U8, FlagStats as _Raw, check, lib
-from ..runtime import Context, DeviceArray, is_torch
+from .._lib import C64, F32, FS_ALL, FS_CLEAN, FS_MEDIANS, HOST, U8, VALUE_CODES, FlagStats as _Raw, check, lib
+from ..runtime import Context, context_for, describe, operand  # noqa: F401  (Context: the tests patch it through this module)
 
 __all__ = ["FlagStats", "flag_statistics", "compute_mad", "compute_statistics", "compute_ffi", "compute_calcquality",
            "print_statistics_comparison"]
@@ -29,79 +29,27 @@ FlagStats.__doc__ = """Statistics of one view.  count: elements in the view; fla
 input; size: elements of the input; mean, std, median, mad, max: Python floats (NaN for an empty view, for a view
 holding a NaN, and for median/mad when not requested); float32: True for float32 / complex64 input."""
 
-_CODES = {np.dtype(np.complex128): C128, np.dtype(np.complex64): C64, np.dtype(np.float64): F64,
-          np.dtype(np.float32): F32}
-
-
-def _numpy_data(a):
-    a = np.asarray(a)
-    if a.dtype.kind in "biu":               # NumPy's median / mean of bool and integer arrays work in float64
-        a = a.astype(np.float64)
-    if a.dtype not in _CODES:
-        raise TypeError(f"data must be complex128, complex64, float64, float32, bool or integer, not {a.dtype}")
-    a = np.ascontiguousarray(a)
-    return a.ctypes.data, _CODES[a.dtype], HOST, a.size, a, None
-
-
-def _data_operand(a):
-    """-> (ptr, dtype code, mem, count, keepalive, cuda device index or None)"""
-    if isinstance(a, DeviceArray):
-        if a.dtype not in _CODES:
-            return _numpy_data(a.numpy())
-        return a.ptr, _CODES[a.dtype], DEVICE, int(np.prod(a.shape, dtype=np.int64)), a, a.ctx.device_index
-    if is_torch(a):
-        import torch
-        t = a.detach()
-        if t.dtype == torch.bool or not (t.is_floating_point() or t.is_complex()):
-            t = t.to(torch.float64)
-        codes = {torch.complex128: C128, torch.complex64: C64, torch.float64: F64, torch.float32: F32}
-        if t.dtype not in codes:
-            raise TypeError(f"data must be complex128, complex64, float64, float32, bool or integer, not {t.dtype}")
-        t = t.contiguous()
-        if t.is_cuda:
-            torch.cuda.current_stream(t.device).synchronize()
-            return t.data_ptr(), codes[t.dtype], DEVICE, t.numel(), t, t.device.index
-        return _numpy_data(t.numpy())
-    return _numpy_data(a)
-
-
-def _flags_operand(f):
-    """-> (ptr, mem, count, keepalive); non-zero == flagged"""
-    if isinstance(f, DeviceArray):
-        if f.dtype not in (np.dtype(np.uint8), np.dtype(np.bool_)):
-            raise TypeError(f"flags must be bool or uint8, not {f.dtype}")
-        return f.ptr, DEVICE, int(np.prod(f.shape, dtype=np.int64)), f
-    if is_torch(f):
-        import torch
-        t = f.detach()
-        if t.dtype not in (torch.bool, torch.uint8):
-            raise TypeError(f"flags must be bool or uint8, not {t.dtype}")
-        t = t.contiguous()
-        if t.dtype == torch.bool:
-            t = t.view(torch.uint8)
-        if t.is_cuda:
-            torch.cuda.current_stream(t.device).synchronize()
-            return t.data_ptr(), DEVICE, t.numel(), t
-        f = t.numpy()
-    f = np.asarray(f)
-    if f.dtype not in (np.dtype(np.uint8), np.dtype(np.bool_)):
-        raise TypeError(f"flags must be bool or uint8, not {f.dtype}")
-    f = np.ascontiguousarray(f).view(np.uint8)
-    return f.ctypes.data, HOST, f.size, f
-
-
 def _stats(data, flags, want, medians, device):
-    dp, code, dm, n, k1, dev = _data_operand(data)
-    fp, fm, k2 = None, HOST, None
+    shape, dt, _, owner = describe(data)
+    if dt is None or not (dt in VALUE_CODES or dt.kind in "biu"):
+        raise TypeError(f"data must be complex128, complex64, float64, float32, bool or integer, not {dt}")
+    n = int(np.prod(shape, dtype=np.int64))
     if flags is not None:
-        fp, fm, fn, k2 = _flags_operand(flags)
+        fshape, fdt = describe(flags)[:2]
+        if fdt is None or fdt not in (np.dtype(np.uint8), np.dtype(np.bool_)):
+            raise TypeError(f"flags must be bool or uint8, not {fdt}")
+        fn = int(np.prod(fshape, dtype=np.int64))
         if fn != n:
             raise ValueError(f"flags has {fn} elements, data has {n}")
-    ctx = Context.get(device if device is not None else dev)
+    if owner is not None and dt not in VALUE_CODES:
+        data = data.numpy()                      # (nothing widens a device array in place: bool and integers come down)
+    ctx = context_for(device, data, flags)
+    d = operand(data, ctx, tuple(VALUE_CODES), "widen")   # NumPy's median / mean of bool and integer arrays work in float64
+    f = operand(flags, ctx, (np.uint8,)) if flags is not None else None
+    code = VALUE_CODES[d.dtype]
     a, c = _Raw(), _Raw()
-    check(lib.rfi_flag_statistics(ctx.handle, C.c_void_p(dp), dm, code, n, C.c_void_p(fp), fm, U8,
-                                  want | (FS_MEDIANS if medians else 0), C.byref(a), C.byref(c)))
-    del k1, k2
+    check(lib.rfi_flag_statistics(ctx.handle, C.c_void_p(d.ptr), d.mem, code, n, C.c_void_p(f.ptr) if f else None, f.mem if f else HOST,
+                                  U8, want | (FS_MEDIANS if medians else 0), C.byref(a), C.byref(c)))
     f32 = code in (C64, F32)
     return tuple(FlagStats(int(r.count), int(r.flagged), int(n), float(r.mean), float(r.std), float(r.median),
                            float(r.mad), float(r.max), f32) for r in (a, c))

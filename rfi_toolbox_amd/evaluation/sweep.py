@@ -11,9 +11,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from .._lib import DEVICE, HOST, VALUES_LOGITS, VALUES_PROBS, check, lib
-from ..runtime import Context, DeviceArray, is_torch
-from .metrics import _operand
+from .._lib import MASK_CODES, VALUES_LOGITS, VALUES_PROBS, check, lib
+from ..runtime import context_for, describe, operand
 
 METRICS = ("iou", "precision", "recall", "f1", "dice")
 MAX_THRESHOLDS = 1024          # per call of the library
@@ -38,29 +37,6 @@ def prepare_thresholds(thresholds):
         raise ValueError("thresholds must be finite (in float32)")
     uniq, inverse = np.unique(thr, return_inverse=True)
     return thr, np.ascontiguousarray(uniq), inverse.reshape(-1)
-
-
-def _score_operand(a):
-    """-> (ptr, mem, shape, keepalive) of a float32 score array"""
-    if isinstance(a, DeviceArray):
-        if a.dtype != np.dtype(np.float32):
-            raise ValueError(f"scores must be float32, got {a.dtype}")
-        return a.ptr, DEVICE, tuple(a.shape), a
-    if is_torch(a):
-        import torch
-        t = a.detach()
-        if not t.dtype.is_floating_point:
-            raise ValueError(f"scores must be float32, got {t.dtype}")
-        t = t.to(torch.float32).contiguous()
-        if t.is_cuda:
-            torch.cuda.current_stream(t.device).synchronize()
-            return t.data_ptr(), DEVICE, tuple(t.shape), t
-        a = t.numpy()
-    a = np.asarray(a)
-    if a.dtype.kind != "f":
-        raise ValueError(f"scores must be float32, got {a.dtype}")
-    a = np.ascontiguousarray(a, dtype=np.float32)
-    return a.ctypes.data, HOST, tuple(a.shape), a
 
 
 def _ratio(num, den, empty):
@@ -164,11 +140,13 @@ def threshold_sweep(scores, true, thresholds=None, *, kind="probabilities", per=
     if kind not in ("probabilities", "logits"):
         raise ValueError(f"kind must be 'probabilities' or 'logits', got {kind!r}")
     thr, uniq, inverse = prepare_thresholds(thresholds)
-    sp, sm, shape, k1 = _score_operand(scores)
-    tshape = tuple(true.shape) if hasattr(true, "shape") else np.shape(true)
-    if tuple(tshape) != shape:
-        raise ValueError(f"scores have shape {shape}, true has shape {tuple(tshape)}")
-    tp_, td, tm, tn, k2 = _operand(true, None)
+    shape, dt, _, owner = describe(scores)
+    floating = scores.dtype.is_floating_point if dt is None else dt.kind == "f"      # (None: a torch dtype NumPy lacks)
+    if not floating or (owner is not None and dt != np.float32):
+        raise ValueError(f"scores must be float32, got {scores.dtype if dt is None else dt}")
+    tshape = describe(true)[0]
+    if tshape != shape:
+        raise ValueError(f"scores have shape {shape}, true has shape {tshape}")
     if per is None:
         group_shape = ()
     else:
@@ -182,15 +160,16 @@ def threshold_sweep(scores, true, thresholds=None, *, kind="probabilities", per=
     counts = np.zeros((n_groups, uniq.size, 3), np.int64)
     group_elems = count // n_groups if n_groups else 0
     if count:
-        ctx = Context.get(device)
+        ctx = context_for(device, scores, true)
+        s = operand(scores, ctx, (np.float32,), "cast")
+        t = operand(true, ctx, (np.uint8, np.float32), "nonzero")
         kmax = max(1, min(MAX_THRESHOLDS, _HIST_SLOTS // (2 * n_groups) - 1))
         for k0 in range(0, uniq.size, kmax):
             chunk = np.ascontiguousarray(uniq[k0:k0 + kmax])
             out = np.empty((n_groups, chunk.size, 3), np.int64)
-            check(lib.rfi_threshold_sweep(ctx.handle, C.c_void_p(sp), sm, VALUES_LOGITS if kind == "logits" else VALUES_PROBS,
-                                          C.c_void_p(tp_), td, tm, count, group_elems, chunk.ctypes.data_as(C.c_void_p),
+            check(lib.rfi_threshold_sweep(ctx.handle, C.c_void_p(s.ptr), s.mem, VALUES_LOGITS if kind == "logits" else VALUES_PROBS,
+                                          C.c_void_p(t.ptr), MASK_CODES[t.dtype], t.mem, count, group_elems, chunk.ctypes.data_as(C.c_void_p),
                                           chunk.size, out.ctypes.data_as(C.c_void_p)))
             counts[:, k0:k0 + chunk.size] = out
-    del k1, k2
     counts = counts[:, inverse].reshape(group_shape + (thr.size, 3))
     return sweep_from_counts(thr, counts, np.full(group_shape, group_elems, np.int64))

@@ -27,10 +27,9 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import C64, C128, DEVICE, ExtendConfig, F32, F64, HOST, RflagConfig, SumThresholdConfig, TfcropConfig, check, lib
-from .runtime import Context, DeviceArray, is_torch, torch
+from ._lib import COMPLEX_CODES, HOST, VALUE_CODES as _CODES, ExtendConfig, RflagConfig, SumThresholdConfig, TfcropConfig, check, lib
+from .runtime import as_pointer, check_out, context_for, describe, is_torch, result_buffer, torch
 
-_CODES = {np.dtype(np.complex128): C128, np.dtype(np.complex64): C64, np.dtype(np.float64): F64, np.dtype(np.float32): F32}
 MAX_AXIS = 1 << 20
 MAX_WINDOW = 128
 
@@ -46,23 +45,10 @@ def sir_q(eta) -> int:
     return int(np.floor(np.float64(eta) * 1024.0 + 0.5))
 
 
-# ---------------------------------------------------------------------------------------------- argument plumbing
-def _np_dtype(x):
-    if isinstance(x, DeviceArray):
-        return x.dtype
-    if is_torch(x):
-        return {torch.complex128: np.complex128, torch.complex64: np.complex64, torch.float64: np.float64,
-                torch.float32: np.float32, torch.uint8: np.uint8, torch.bool: np.bool_}.get(x.dtype)
-    return np.asarray(x).dtype
-
-
-def _shape(x):
-    return tuple(int(s) for s in (x.shape if isinstance(x, DeviceArray) or is_torch(x) else np.asarray(x).shape))
-
-
+# ---------------------------------------------------------------------------------------------- argument checks
 def _check_planes(name, x):
     """-> (shape, number of planes) of a (..., C, T) stack."""
-    shape = _shape(x)
+    shape = describe(x)[0]
     if len(shape) < 2:
         raise ValueError(f"{name} must have shape (..., C, T) with ndim >= 2, got shape {shape}")
     if not 1 <= shape[-2] <= MAX_AXIS or not 1 <= shape[-1] <= MAX_AXIS:
@@ -71,50 +57,11 @@ def _check_planes(name, x):
 
 
 def _check_flags(flags, shape):
-    if _shape(flags) != shape:
-        raise ValueError(f"flags have shape {_shape(flags)}, the data {shape}")
-    dt = _np_dtype(flags)
-    if dt is None or np.dtype(dt) not in (np.dtype(np.bool_), np.dtype(np.uint8)):
+    fshape, dt = describe(flags)[:2]
+    if fshape != shape:
+        raise ValueError(f"flags have shape {fshape}, the data {shape}")
+    if dt is None or dt not in (np.dtype(np.bool_), np.dtype(np.uint8)):
         raise ValueError(f"flags must be bool or uint8, got {dt}")
-
-
-def _pointer(x, dtype, ctx):
-    """-> (ptr, mem, keepalive) of x as contiguous `dtype` (bool is passed as its bytes)."""
-    dtype = np.dtype(dtype)
-    if isinstance(x, DeviceArray):
-        if x.ctx is not ctx:
-            raise ValueError("device array belongs to another context")
-        return x.ptr, DEVICE, x
-    if is_torch(x):
-        t = x.detach()
-        if t.dtype == torch.bool:
-            t = t.to(torch.uint8)
-        t = t.contiguous()
-        if t.is_cuda:
-            if t.device.index not in (None, ctx.device_index):
-                raise ValueError(f"tensor is on {t.device}, the context on GPU {ctx.device_index}")
-            torch.cuda.current_stream(t.device).synchronize()        # hand over to the context's stream
-            return t.data_ptr(), DEVICE, t
-        x = t.numpy()
-    a = np.ascontiguousarray(np.asarray(x))
-    if a.dtype == np.bool_:
-        a = a.view(np.uint8)
-    a = np.ascontiguousarray(a, dtype=dtype)
-    return a.ctypes.data, HOST, a
-
-
-def _on_device(*xs):
-    return any(isinstance(x, DeviceArray) or (is_torch(x) and x.is_cuda) for x in xs if x is not None)
-
-
-def _context(device, *xs):
-    for x in xs:
-        if isinstance(x, DeviceArray):
-            return x.ctx
-    for x in xs:
-        if is_torch(x) and x.is_cuda and device is None:
-            return Context.get(x.device.index or 0)
-    return Context.get(device)
 
 
 def _axis(axis, ndim):
@@ -125,15 +72,12 @@ def _axis(axis, ndim):
     raise ValueError(f"axis must name the time axis (-1) or the frequency axis (-2), got {axis!r}")
 
 
-def _real_values(name, values):
-    dt = _np_dtype(values)
-    if dt is None or np.dtype(dt) not in (np.dtype(np.float32), np.dtype(np.float64)):
+def _check_real(name, values):
+    _, dt, _, owner = describe(values)
+    if dt is None or dt not in (np.dtype(np.float32), np.dtype(np.float64)):
         raise ValueError(f"{name} must be float32 or float64, got {dt}")
-    if isinstance(values, DeviceArray) and values.dtype != np.float32:
+    if owner is not None and dt != np.float32:
         raise ValueError(f"a device array of {name} must be float32")
-    if is_torch(values):
-        return values.to(torch.float32)
-    return values if isinstance(values, DeviceArray) else np.asarray(values, dtype=np.float32)
 
 
 def _doubles(a):
@@ -146,8 +90,8 @@ def _run_stage(fn, inputs, shape, planes, args, result_dtype, device):
     `inputs`, planes, C, T, *args, result pointer, HOST) into a new NumPy array of `shape`."""
     out = np.empty(shape, result_dtype)
     if planes:
-        ctx = _context(device, *(x for x, _ in inputs))
-        held = [_pointer(x, dt, ctx) for x, dt in inputs]
+        ctx = context_for(device, *(x for x, _ in inputs))
+        held = [as_pointer(x, dt, ctx) for x, dt in inputs]
         check(fn(ctx.handle, *(a for p, mem, _ in held for a in (C.c_void_p(p), mem)), planes, shape[-2], shape[-1], *args,
                  C.c_void_p(out.ctypes.data), HOST))
     return out
@@ -156,43 +100,30 @@ def _run_stage(fn, inputs, shape, planes, args, result_dtype, device):
 def _check_data(data, flags, out, codes):
     """-> (shape, number of planes, dtype) after the checks the flaggers share (`flags` may be None)."""
     shape, planes = _check_planes("data", data)
-    dt = _np_dtype(data)
-    if dt is None or np.dtype(dt) not in codes:
+    dt = describe(data)[1]
+    if dt is None or dt not in codes:
         raise ValueError(f"data must be one of {', '.join(str(c) for c in codes)}, got {dt}")
     if flags is not None:
         _check_flags(flags, shape)
-    if out not in ("host", "device"):
-        raise ValueError(f"out must be 'host' or 'device', got {out!r}")
-    return shape, planes, np.dtype(dt)
+    check_out(out)
+    return shape, planes, dt
 
 
 def _run_flagger(call, data, dt, flags, shape, planes, out, device):
     """The shared tail of the four flaggers: pointers, the result buffer of `out`, then call(ctx, data pointer and
     memory kind, prior pointer and kind, result pointer and kind)."""
-    ctx = _context(device, data, flags)
-    dp, dm, k1 = _pointer(data, dt, ctx)
-    fp, fm, k2 = _pointer(flags, np.uint8, ctx) if flags is not None else (None, HOST, None)
-    cuda_in = is_torch(data) and data.is_cuda
-    if out == "device":
-        res = ctx.empty(shape, np.uint8)
-        rp, rm = res.ptr, DEVICE
-    elif cuda_in:
-        res = torch.empty(shape, dtype=torch.uint8, device=data.device)
-        torch.cuda.current_stream(data.device).synchronize()        # (the output's memory may have just been freed)
-        rp, rm = res.data_ptr(), DEVICE
-    else:
-        res = np.empty(shape, np.uint8)
-        rp, rm = res.ctypes.data, HOST
+    ctx = context_for(device, data, flags)
+    dp, dm, k1 = as_pointer(data, dt, ctx)
+    fp, fm, k2 = as_pointer(flags, np.uint8, ctx) if flags is not None else (None, HOST, None)
+    res, rp, rm = result_buffer(ctx, shape, np.uint8, out, data)
     if planes:
         check(call(ctx, C.c_void_p(dp), dm, C.c_void_p(fp) if fp else None, fm, C.c_void_p(rp), rm))
     if out == "device":
         res._keep = (k1, k2)             # the inputs may still be read by work in flight: they live as long as the result
         return res
-    if cuda_in:
+    if is_torch(res):
         ctx.synchronize()
-        del k1, k2
         return res.view(torch.bool)
-    del k1, k2
     return res.view(bool)
 
 
@@ -205,7 +136,7 @@ def sumthreshold_pass(values, flags, window, threshold, center=0.0, axis=-1, dev
     the line changes nothing); ``threshold`` and ``center`` scalars or one value per plane.  Returns NumPy bool.
     """
     shape, planes = _check_planes("values", values)
-    values = _real_values("values", values)
+    _check_real("values", values)
     _check_flags(flags, shape)
     if not isinstance(window, (int, np.integer)) or not 1 <= window <= MAX_WINDOW or window & (window - 1):
         raise ValueError(f"window must be a power of two in 1 .. {MAX_WINDOW}, got {window!r}")
@@ -226,7 +157,7 @@ def masked_gaussian_smooth(values, flags, weights_t, weights_f, device=None) -> 
     first; 0 where no unflagged sample lies under the window.  ``weights_t`` / ``weights_f``: tables of odd length
     (``gaussian_weights``).  Returns NumPy float32."""
     shape, planes = _check_planes("values", values)
-    values = _real_values("values", values)
+    _check_real("values", values)
     _check_flags(flags, shape)
     wt, wf = np.asarray(weights_t, np.float64), np.asarray(weights_f, np.float64)
     for name, w in (("weights_t", wt), ("weights_f", wf)):
@@ -390,8 +321,7 @@ def rflag_flags(data, flags=None, ntime=None, winsize=3, timedevscale=5.0, freqd
     plane or ``(planes, C)`` values), ``freqdev`` that of the spectral analysis (a scalar or one value per plane).
     Medians are exact.  Unlike CASA, no polynomial is fitted to the per-channel thresholds across a spectral window.
     ``data``, ``flags``, ``out`` and ``device`` as for ``sumthreshold_flags``.  There is no CPU path."""
-    codes = {k: v for k, v in _CODES.items() if k.kind == "c"}
-    shape, planes, dt = _check_data(data, flags, out, codes)
+    shape, planes, dt = _check_data(data, flags, out, COMPLEX_CODES)
     if isinstance(winsize, (bool, np.bool_)) or not isinstance(winsize, (int, np.integer)) or winsize < 1 or winsize % 2 == 0:
         raise ValueError(f"winsize must be an odd integer >= 1, got {winsize!r}")
     cfg = RflagConfig(_ntime(ntime), int(min(winsize, _INT_MAX)), _non_negative("timedevscale", timedevscale),
@@ -415,8 +345,7 @@ def extend_flags(flags, ntime=None, growtime=50.0, growfreq=50.0, growaround=Fal
     (the samples one step from a flagged one).  ``out`` and ``device`` as for ``sumthreshold_flags``."""
     shape, planes = _check_planes("flags", flags)
     _check_flags(flags, shape)
-    if out not in ("host", "device"):
-        raise ValueError(f"out must be 'host' or 'device', got {out!r}")
+    check_out(out)
     for name, v in (("growtime", growtime), ("growfreq", growfreq)):
         if not 0.0 <= float(v) <= 100.0:
             raise ValueError(f"{name} must be in 0 .. 100, got {v!r}")

@@ -21,8 +21,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import C64, C128, COMBINE_MAX, COMBINE_MEAN, DEVICE, EDGE_PAD, EDGE_SHIFT, HOST, Tiling, check, lib
-from .runtime import as_pointer, is_torch, torch
+from ._lib import COMBINE_MAX, COMBINE_MEAN, COMPLEX_CODES, EDGE_PAD, EDGE_SHIFT, Tiling, check, lib
+from .runtime import as_pointer, describe, is_torch, result_buffer, torch
 
 _COMBINE = {"mean": COMBINE_MEAN, "max": COMBINE_MAX}
 _EDGE = {"pad": EDGE_PAD, "shift": EDGE_SHIFT}
@@ -75,14 +75,10 @@ def predict_flags(model, data, patch_size=128, stride=None, views=1, combine="me
     ps, s = check_tiling_args(patch_size, stride, views, combine, edge)
     if not isinstance(batch_size, (int, np.integer)) or batch_size <= 0:
         raise ValueError(f"batch_size must be a positive integer, got {batch_size!r}")
-    cuda_in = is_torch(data) and data.is_cuda
-    if is_torch(data):
-        complex_in, shape = data.is_complex(), tuple(data.shape)
-        dt = {torch.complex64: np.complex64, torch.complex128: np.complex128}.get(data.dtype, np.complex128)
-    else:
-        data = np.asarray(data)
-        complex_in, shape = np.iscomplexobj(data), data.shape
-        dt = data.dtype if data.dtype in (np.complex64, np.complex128) else np.complex128
+    shape, dt = describe(data)[:2]
+    complex_in = data.is_complex() if dt is None else dt.kind == "c"
+    if dt is None or dt not in COMPLEX_CODES:
+        dt = np.dtype(np.complex128)
     if not complex_in:
         raise ValueError("predict_flags takes complex visibilities; for real-valued input build the patches with "
                          "Preprocessor(data).create_dataset(..., inference_mode=True), run the model and put the "
@@ -99,22 +95,14 @@ def predict_flags(model, data, patch_size=128, stride=None, views=1, combine="me
         raise ValueError(f"patch_size {ps} is not a multiple of {f}, the downsampling factor of {type(model).__name__}")
     Cn, Tn = int(shape[-2]), int(shape[-1])
     n_planes = int(np.prod(shape[:-2], dtype=np.int64))
-    code = C64 if dt == np.complex64 else C128
     ctx = model.ctx
     ptr, mem, keep = as_pointer(data, dt, ctx)
-    if cuda_in:
-        flags = torch.empty(shape, dtype=torch.uint8, device=data.device)
-        prob = torch.empty(shape, dtype=torch.float32, device=data.device) if return_probabilities else None
-        torch.cuda.current_stream(data.device).synchronize()        # (the outputs' memory may have just been freed)
-        fp, pp, omem = flags.data_ptr(), (prob.data_ptr() if prob is not None else None), DEVICE
-    else:
-        flags = np.empty(shape, dtype=np.uint8)
-        prob = np.empty(shape, dtype=np.float32) if return_probabilities else None
-        fp, pp, omem = flags.ctypes.data, (prob.ctypes.data if prob is not None else None), HOST
+    flags, fp, omem = result_buffer(ctx, shape, np.uint8, "host", data)
+    prob, pp, _ = result_buffer(ctx, shape, np.float32, "host", data) if return_probabilities else (None, None, None)
     if n_planes and Cn and Tn:
-        check(lib.rfi_model_predict_flags(model._h, C.c_void_p(ptr), mem, code, n_planes, Cn, Tn,
+        check(lib.rfi_model_predict_flags(model._h, C.c_void_p(ptr), mem, COMPLEX_CODES[dt], n_planes, Cn, Tn,
                                           C.byref(Tiling(ps, s, _EDGE[edge], views)), int(batch_size), _COMBINE[combine],
                                           float(threshold), C.c_void_p(fp), omem, C.c_void_p(pp) if pp else None, omem))
     del keep
-    flags = flags.view(torch.bool) if cuda_in else flags.view(bool)
+    flags = flags.view(torch.bool) if is_torch(flags) else flags.view(bool)
     return (flags, prob) if return_probabilities else flags

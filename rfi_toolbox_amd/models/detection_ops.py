@@ -8,26 +8,23 @@ import ctypes as C
 import numpy as np
 
 from .._lib import check, lib
-from ..runtime import Context, DeviceArray
+from ..runtime import Context, DeviceArray, P, context_for, operand
 
 
 def _dev(ctx, a):
-    return a if isinstance(a, DeviceArray) else ctx.to_device(np.ascontiguousarray(a, np.float32))
-
-
-def _p(d):
-    return C.c_void_p(d.ptr)
+    """-> `a` as a float32 DeviceArray of `ctx` (host arrays are uploaded: the kernels read HBM only)."""
+    return operand(a, ctx, (np.float32,), "cast", to_device=True).keep
 
 
 def roi_align(x, rois, spatial_scale=1.0, output_size=(7, 7), sampling_ratio=2, aligned=False, device=None, to_host=True):
     """x (N, H, W, C) float32, C % 4 == 0; rois (R, 5) = (batch index, x1, y1, x2, y2) -> (R, PH, PW, C)."""
-    ctx = Context.get(device)
+    ctx = context_for(device, x)
     dx, dr = _dev(ctx, x), _dev(ctx, np.asarray(rois, np.float32).reshape(-1, 5))
     n, h, w, c = dx.shape
     ph, pw = output_size
     out = ctx.empty((dr.shape[0], ph, pw, c), np.float32)
-    check(lib.rfi_op_roi_align(ctx.handle, _p(dx), n, h, w, c, _p(dr), dr.shape[0], float(spatial_scale), ph, pw,
-                               int(sampling_ratio), 1 if aligned else 0, _p(out)))
+    check(lib.rfi_op_roi_align(ctx.handle, P(dx), n, h, w, c, P(dr), dr.shape[0], float(spatial_scale), ph, pw,
+                               int(sampling_ratio), 1 if aligned else 0, P(out)))
     ctx.synchronize()
     return out.numpy() if to_host else out
 
@@ -35,7 +32,7 @@ def roi_align(x, rois, spatial_scale=1.0, output_size=(7, 7), sampling_ratio=2, 
 def roi_align_backward(dout, input_shape, rois, spatial_scale=1.0, sampling_ratio=2, aligned=False, device=None, to_host=True):
     """dout (R, PH, PW, C); rois (R, 5) in any order -> d(x) (N, H, W, C).  The kernel gathers per image from RoIs sorted by
     batch index: the RoIs are stable-sorted on the host and dout is permuted the same way before the call."""
-    ctx = Context.get(device)
+    ctx = context_for(device, dout)
     rois = np.asarray(rois, np.float32).reshape(-1, 5)
     order = np.argsort(rois[:, 0], kind="stable")
     dout = dout.numpy() if isinstance(dout, DeviceArray) else np.asarray(dout, np.float32)
@@ -43,32 +40,32 @@ def roi_align_backward(dout, input_shape, rois, spatial_scale=1.0, sampling_rati
     n, h, w, c = input_shape
     r, ph, pw, _ = dd.shape
     dx = ctx.empty((n, h, w, c), np.float32)
-    check(lib.rfi_op_roi_align_backward(ctx.handle, _p(dd), n, h, w, c, _p(dr), r, float(spatial_scale), ph, pw,
-                                        int(sampling_ratio), 1 if aligned else 0, _p(dx)))
+    check(lib.rfi_op_roi_align_backward(ctx.handle, P(dd), n, h, w, c, P(dr), r, float(spatial_scale), ph, pw,
+                                        int(sampling_ratio), 1 if aligned else 0, P(dx)))
     ctx.synchronize()
     return dx.numpy() if to_host else dx
 
 
 def fpn_merge(lateral, top, device=None, to_host=True):
     """lateral (N, H, W, C) + nearest-neighbour 2x upsampling of top (N, ceil(H/2), ceil(W/2), C)."""
-    ctx = Context.get(device)
+    ctx = context_for(device, lateral, top)
     dl, dt = _dev(ctx, lateral), _dev(ctx, top)
     n, h, w, c = dl.shape
     if dt.shape != (n, (h + 1) // 2, (w + 1) // 2, c):
         raise ValueError(f"top must be {(n, (h + 1) // 2, (w + 1) // 2, c)}, got {dt.shape}")
     out = ctx.empty((n, h, w, c), np.float32)
-    check(lib.rfi_op_fpn_merge(ctx.handle, _p(dl), _p(dt), n, h, w, c, _p(out)))
+    check(lib.rfi_op_fpn_merge(ctx.handle, P(dl), P(dt), n, h, w, c, P(out)))
     ctx.synchronize()
     return out.numpy() if to_host else out
 
 
 def fpn_merge_backward(dout, device=None, to_host=True):
     """-> (d_lateral, d_top): d_lateral is dout itself, d_top sums each coarse pixel's 2x2 children."""
-    ctx = Context.get(device)
+    ctx = context_for(device, dout)
     dd = _dev(ctx, dout)
     n, h, w, c = dd.shape
     dtop = ctx.empty((n, (h + 1) // 2, (w + 1) // 2, c), np.float32)
-    check(lib.rfi_op_fpn_merge_backward(ctx.handle, _p(dd), n, h, w, c, _p(dtop)))
+    check(lib.rfi_op_fpn_merge_backward(ctx.handle, P(dd), n, h, w, c, P(dtop)))
     ctx.synchronize()
     return (dd.numpy(), dtop.numpy()) if to_host else (dd, dtop)
 
@@ -85,7 +82,7 @@ def decode_boxes(anchors, deltas, image_size=None, device=None):
         raise ValueError(f"{n} delta rows are not a multiple of {na} anchors")
     out = ctx.empty((n, 4), np.float32)
     h, w = (float(image_size[0]), float(image_size[1])) if image_size is not None else (0.0, 0.0)
-    check(lib.rfi_op_box_decode(ctx.handle, _p(da), na, _p(dd), n, h, w, _p(out)))
+    check(lib.rfi_op_box_decode(ctx.handle, P(da), na, P(dd), n, h, w, P(out)))
     ctx.synchronize()
     return out.numpy()
 
@@ -103,7 +100,7 @@ def nms(boxes, scores, iou_threshold, device=None):
     db = ctx.to_device(np.ascontiguousarray(boxes[order]))
     keep = np.empty(len(boxes), np.int32)
     nk = C.c_int()
-    check(lib.rfi_op_nms(ctx.handle, _p(db), len(boxes), float(iou_threshold), keep.ctypes.data_as(C.c_void_p), C.byref(nk)))
+    check(lib.rfi_op_nms(ctx.handle, P(db), len(boxes), float(iou_threshold), keep.ctypes.data_as(C.c_void_p), C.byref(nk)))
     return order[keep[:nk.value]]
 
 
@@ -122,7 +119,7 @@ def rpn_loss(head, labels, targets, anchors_per_pixel, beta=1.0 / 9, device=None
     dg = ctx.empty(dh.shape, np.float32)
     count = ctx.to_device(np.asarray([(lab >= 0).sum() if num_sampled is None else num_sampled], np.int32))
     ws, loss2 = ctx.empty((int(lib.rfi_op_rpn_loss_ws_bytes()),), np.uint8), ctx.empty((2,), np.float32)
-    check(lib.rfi_op_rpn_loss(ctx.handle, _p(dh), dh.shape[0], a, _p(dl), _p(dt), _p(count), float(beta), _p(dg), _p(ws), _p(loss2)))
+    check(lib.rfi_op_rpn_loss(ctx.handle, P(dh), dh.shape[0], a, P(dl), P(dt), P(count), float(beta), P(dg), P(ws), P(loss2)))
     ctx.synchronize()
     lo, lb = loss2.numpy()
     return float(lo), float(lb), dg.numpy()
@@ -149,7 +146,7 @@ def fastrcnn_loss(head, labels, targets, beta=1.0 / 9, device=None):
     dl, dt = ctx.to_device(lab), _dev(ctx, np.asarray(targets, np.float32).reshape(r, 4))
     dg = ctx.empty((r, 5 * k1), np.float32)
     ws, loss2 = ctx.empty((int(lib.rfi_op_rpn_loss_ws_bytes()),), np.uint8), ctx.empty((2,), np.float32)
-    check(lib.rfi_op_fastrcnn_loss(ctx.handle, _p(dh), r, k1, _p(dl), _p(dt), float(beta), _p(dg), _p(ws), _p(loss2)))
+    check(lib.rfi_op_fastrcnn_loss(ctx.handle, P(dh), r, k1, P(dl), P(dt), float(beta), P(dg), P(ws), P(loss2)))
     ctx.synchronize()
     lc, lb = loss2.numpy()
     return float(lc), float(lb), dg.numpy()
@@ -182,9 +179,9 @@ def anchor_match_batched(anchors, gt_list, fg_iou=0.7, bg_iou=0.3, allow_low_qua
     dac = None if anchor_counts is None else ctx.to_device(np.ascontiguousarray(np.asarray(anchor_counts, np.int32)))
     labels, matched, targets = ctx.empty((B, n), np.int8), ctx.empty((B, n), np.int32), ctx.empty((B, n, 4), np.float32)
     best_ws = ctx.empty((B, gt.shape[1]), np.float32)
-    check(lib.rfi_op_anchor_match_batched(ctx.handle, _p(da), n, 0 if shared else n, None if dac is None else _p(dac), _p(dg), B,
-                                          gt.shape[1], _p(dgc), float(fg_iou), float(bg_iou), 1 if allow_low_quality else 0,
-                                          _p(best_ws), _p(labels), _p(matched), _p(targets)))
+    check(lib.rfi_op_anchor_match_batched(ctx.handle, P(da), n, 0 if shared else n, None if dac is None else P(dac), P(dg), B,
+                                          gt.shape[1], P(dgc), float(fg_iou), float(bg_iou), 1 if allow_low_quality else 0,
+                                          P(best_ws), P(labels), P(matched), P(targets)))
     ctx.synchronize()
     return labels.numpy(), matched.numpy(), targets.numpy()
 
@@ -203,6 +200,6 @@ def nms_batched(boxes_sorted, counts, iou_threshold, device=None):
         return np.zeros(b.shape[:2], bool)
     db, dc = ctx.to_device(b), ctx.to_device(c)
     keep = ctx.empty(b.shape[:2], np.uint8)
-    check(lib.rfi_op_nms_batched(ctx.handle, _p(db), _p(dc), b.shape[0], b.shape[1], float(iou_threshold), _p(keep)))
+    check(lib.rfi_op_nms_batched(ctx.handle, P(db), P(dc), b.shape[0], b.shape[1], float(iou_threshold), P(keep)))
     ctx.synchronize()
     return keep.numpy().astype(bool)

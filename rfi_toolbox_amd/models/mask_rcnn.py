@@ -29,6 +29,7 @@ import math
 import numpy as np
 
 from .._lib import DEVICE, HOST, check, lib
+from ..runtime import P
 from . import detection_ops as ops
 from .backbone import ResNet50FPN
 from .box_head import BoxHead
@@ -316,7 +317,6 @@ class MaskRCNN:
         ctx, F, k1 = self.backbone.ctx, self.F, self.num_classes
         K, Pn, D = self.pre_nms, self.post_nms, self.max_det
         H = ctx.handle
-        P = lambda a: C.c_void_p(a.ptr)  # noqa: E731
         for m in (self.rpn, self.box, self.mask):
             m.eval()
         if dev_in:
@@ -468,7 +468,6 @@ class MaskRCNN:
                 raise ValueError("MaskRCNN.train_step: InstanceTargets must hold instance masks and live on the detector's GPU")
         ctx, F, k1 = self.backbone.ctx, self.F, self.num_classes
         H = ctx.handle
-        P = lambda d: C.c_void_p(d.ptr)  # noqa: E731
         for m in (self.rpn, self.box, self.mask):
             m.train()
         if inst is not None:

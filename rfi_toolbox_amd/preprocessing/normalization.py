@@ -139,19 +139,6 @@ class Normalizer:
         self.centres = self.scales = None          # per sample (scope "sample") or one entry (scope "dataset")
         self._params_dev = None
 
-    # ---- plumbing
-    def _context(self, x=None):
-        from ..runtime import Context, DeviceArray
-        if isinstance(x, DeviceArray) and self.device is None:
-            return x.ctx
-        return Context.get(self.device)
-
-    def _to_device(self, x):
-        from ..runtime import DeviceArray
-        if isinstance(x, DeviceArray):
-            return x
-        return self._context().to_device(np.asarray(x))
-
     @staticmethod
     def _as_list(x):
         return list(x) if isinstance(x, (list, tuple)) else [x]
@@ -160,7 +147,7 @@ class Normalizer:
         """The raw per-population statistics (list of dicts) of what ``fit`` would see; raises on non-finite input.
         quantiles=False skips the order statistics (``q`` is NaN): 2 reads of the data instead of 6."""
         from .._lib import F32, F64, NormStats, check, lib
-        from ..runtime import DeviceArray
+        from ..runtime import DeviceArray, context_for, operand
         xs = [x if isinstance(x, DeviceArray) else np.asarray(x) for x in self._as_list(x_or_list)]
         if not xs:
             raise ValueError("fit needs at least one array")
@@ -173,8 +160,8 @@ class Normalizer:
         if sum(d[0] for d in desc) == 0:
             raise ValueError("fit needs at least one sample")
         scalar = scalars.pop()
-        devs = [self._to_device(x) for x in xs]                      # kept alive until the call returns
-        ctx = self._context(devs[0])
+        ctx = context_for(self.device, *xs)
+        devs = [operand(x, ctx, tuple(_SCALAR), to_device=True) for x in xs]      # kept alive until the call returns
         counts = [d[0] * d[1] * 8 for d in desc]
         n = len(devs)
         ptrs = (C.c_void_p * n)(*[d.ptr for d in devs])
@@ -209,8 +196,8 @@ class Normalizer:
     def transform(self, x, out="nhwc", layout=None):
         """float32 (n, T, F, 8) for out="nhwc", (n, 8, T, F) for out="nchw": DeviceArray for DeviceArray input (stream-
         ordered, nothing synchronised), NumPy for NumPy input."""
-        from .._lib import C64, C128, F32, F64, NORM_NCHW, NORM_NHWC, check, lib
-        from ..runtime import DeviceArray
+        from .._lib import NORM_NCHW, NORM_NHWC, VALUE_CODES, check, lib
+        from ..runtime import DeviceArray, context_for, operand
         if out not in ("nhwc", "nchw"):
             raise ValueError(f"out must be 'nhwc' or 'nchw', got {out!r}")
         if not isinstance(x, DeviceArray):
@@ -221,17 +208,15 @@ class Normalizer:
         if self.scope == "sample" and len(self.centres) != n:
             raise ValueError(f"fitted on {len(self.centres)} samples, asked to transform {n}")
         on_device = isinstance(x, DeviceArray)
-        src = self._to_device(x)
-        ctx = self._context(src)
+        ctx = context_for(self.device, x)
+        src = operand(x, ctx, tuple(_SCALAR), to_device=True)
         dst = ctx.empty((n, T, F, 8) if out == "nhwc" else (n, 8, T, F), np.float32)
         params = None
         if self.scope == "sample":
             if self._params_dev is None or self._params_dev.ctx is not ctx:
                 self._params_dev = ctx.to_device(np.stack([self.centres, self.scales], axis=1).astype(np.float64))
             params = C.c_void_p(self._params_dev.ptr)
-        code = {np.dtype(np.complex128): C128, np.dtype(np.complex64): C64, np.dtype(np.float64): F64,
-                np.dtype(np.float32): F32}[np.dtype(src.dtype)]
-        check(lib.rfi_norm_apply(ctx.handle, C.c_void_p(src.ptr), code, NORM_NHWC if lay == "nhwc" else NORM_NCHW, n, px,
+        check(lib.rfi_norm_apply(ctx.handle, C.c_void_p(src.ptr), VALUE_CODES[src.dtype], NORM_NHWC if lay == "nhwc" else NORM_NCHW, n, px,
                                  self.centres[0], self.scales[0], params, C.c_void_p(dst.ptr),
                                  NORM_NHWC if out == "nhwc" else NORM_NCHW))
         if on_device:

@@ -24,9 +24,9 @@ import ctypes as C
 import numpy as np
 import torch
 
-from .._lib import C128, C64, DEVICE, F32, F64, HOST, check, lib
+from .._lib import C128, DEVICE, F32, F64, HOST, VALUE_CODES, check, lib
 from ..datasets.batched_dataset import TorchDataset
-from ..runtime import Context
+from ..runtime import Context, ptr_mem
 
 
 def patchify(array, patch_shape, step):
@@ -114,14 +114,6 @@ def select_patches(ctx, d_flags, n_planes, Cn, Tn, rot, ps, num_patches=None, in
 def gather_patches(ctx, d_planes, d_flags, code, n_planes, Cn, Tn, table, ps, images, labels):
     """Run the gather kernels for `table`; `images` / `labels` are NumPy arrays (host results) or
     DeviceArrays (results stay in HBM); labels may be None."""
-    from ..runtime import DeviceArray
-
-    def ptr_mem(a):
-        if a is None:
-            return None, HOST
-        if isinstance(a, DeviceArray):
-            return C.c_void_p(a.ptr), DEVICE
-        return a.ctypes.data_as(C.c_void_p), HOST
     ip, im = ptr_mem(images)
     lp, lm = ptr_mem(labels)
     if len(table):
@@ -154,8 +146,7 @@ class Preprocessor:
     # ---- device hot loop
     def _channels_on_device(self, patches):
         n, ph, pw = patches.shape
-        code = {np.dtype(np.complex128): C128, np.dtype(np.complex64): C64, np.dtype(np.float64): F64,
-                np.dtype(np.float32): F32}.get(patches.dtype)
+        code = VALUE_CODES.get(patches.dtype)
         if code is None:
             patches = patches.astype(np.complex128 if np.iscomplexobj(patches) else np.float64)
             code = C128 if np.iscomplexobj(patches) else F64
@@ -178,9 +169,9 @@ class Preprocessor:
         if ps_h != ps_w:
             return None
         ps = ps_h
-        code = {np.dtype(np.complex128): C128, np.dtype(np.complex64): C64}.get(data.dtype)
-        if code is None:
-            data, code = data.astype(np.complex128), C128
+        if data.dtype != np.complex64:
+            data = data.astype(np.complex128, copy=False)
+        code = VALUE_CODES[data.dtype]
         planes = np.ascontiguousarray(data.reshape(B * P, Cn, Tn))
         fl = np.asarray(self.flags)
         fl = fl[np.newaxis, ...] if fl.ndim == 3 else fl
@@ -393,8 +384,7 @@ class Preprocessor:
 
     def _mad_flags_on_device(self, patches, sigma):
         n, ph, pw = patches.shape
-        code = {np.dtype(np.complex128): C128, np.dtype(np.complex64): C64, np.dtype(np.float64): F64,
-                np.dtype(np.float32): F32}.get(patches.dtype)
+        code = VALUE_CODES.get(patches.dtype)
         if code is None:
             patches, code = patches.astype(np.complex128), C128
         patches = np.ascontiguousarray(patches)

@@ -3,8 +3,10 @@ and array plumbing between NumPy / torch and raw pointers.  No compute happens i
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import threading
+from collections import namedtuple
 
 import numpy as np
 
@@ -181,22 +183,138 @@ def is_torch(x) -> bool:
     return torch is not None and isinstance(x, torch.Tensor)
 
 
-def as_pointer(x, dtype, ctx: Context):
-    """-> (ptr, mem, keepalive).  Accepts DeviceArray, NumPy array, torch CPU / CUDA tensor."""
+# ---------------------------------------------------------------------------------------------- array arguments
+# Every public function takes NumPy arrays, torch CPU / CUDA tensors and DeviceArrays; what follows turns one into what
+# the C ABI wants and is the only place that does.
+_TORCH_NP = {} if torch is None else {
+    torch.bool: np.bool_, torch.uint8: np.uint8, torch.int8: np.int8, torch.int16: np.int16, torch.int32: np.int32,
+    torch.int64: np.int64, torch.float16: np.float16, torch.float32: np.float32, torch.float64: np.float64,
+    torch.complex64: np.complex64, torch.complex128: np.complex128}
+_TORCH_NP = {t: np.dtype(d) for t, d in _TORCH_NP.items()}
+_NP_TORCH = {d: t for t, d in _TORCH_NP.items()}
+_U8, _BOOL = np.dtype(np.uint8), np.dtype(np.bool_)
+
+Operand = namedtuple("Operand", "ptr mem dtype shape size keep")
+Operand.__doc__ = """An array argument as the C ABI takes it: pointer, HOST / DEVICE, the NumPy dtype behind the pointer,
+shape and element count of the caller's array, and what must stay referenced until the work that reads it is done."""
+
+
+def describe(x):
+    """-> (shape, NumPy dtype or None for a torch dtype NumPy lacks, GPU index or None, owning Context or None).
+    Nothing is copied, no device is touched and no context is made: argument checks build on this."""
     if isinstance(x, DeviceArray):
-        if x.dtype != np.dtype(dtype):
-            raise TypeError(f"device array has dtype {x.dtype}, expected {np.dtype(dtype)}")
-        return x.ptr, DEVICE, x
+        return x.shape, x.dtype, x.ctx.device_index, x.ctx
     if is_torch(x):
-        tdt = {np.dtype(np.float32): torch.float32, np.dtype(np.uint8): torch.uint8,
-               np.dtype(np.complex64): torch.complex64, np.dtype(np.complex128): torch.complex128}[np.dtype(dtype)]
-        if x.is_cuda:
-            if x.device.index not in (None, ctx.device_index):
-                raise RuntimeError(f"tensor is on {x.device}, context on GPU {ctx.device_index}")
-            t = x.detach().to(tdt).contiguous()
-            torch.cuda.current_stream(t.device).synchronize()     # hand over to the ctx stream
-            return t.data_ptr(), DEVICE, t
-        a = np.ascontiguousarray(x.detach().to(tdt).numpy())
-        return a.ctypes.data, HOST, a
-    a = np.ascontiguousarray(np.asarray(x), dtype=dtype)
-    return a.ctypes.data, HOST, a
+        return tuple(int(s) for s in x.shape), _TORCH_NP.get(x.dtype), (x.device.index or 0) if x.is_cuda else None, None
+    x = np.asarray(x)
+    return x.shape, x.dtype, None, None
+
+
+def context_for(device, *xs) -> Context:
+    """The context a call runs on: that of a DeviceArray among `xs`; else, when `device` is None, the GPU of a CUDA
+    tensor among them; else ``Context.get(device)``.  A `device` that names another context than the DeviceArray's is
+    refused here; every other input the choice contradicts is refused by ``operand``."""
+    for x in xs:
+        if isinstance(x, DeviceArray):
+            if device is not None and Context._cache.get((os.getpid(), _parse_device(device))) is not x.ctx:
+                raise ValueError(f"device array belongs to another context than that of device={device!r}")
+            return x.ctx
+    if device is None:
+        for x in xs:
+            if is_torch(x) and x.is_cuda:
+                return Context.get(x.device.index or 0)
+    return Context.get(device)
+
+
+def _convert(dt, accept, other, error):
+    """The dtype policy of ``operand``: -> (dtype the kernel gets, None | "view" | "cast" | "nonzero" to get there)."""
+    if dt is not None and dt in accept:          # (np.dtype(np.float64) == None holds: NumPy reads None as float64)
+        return dt, None
+    if dt is not None and dt == _BOOL and _U8 in accept:
+        return _U8, "view"
+    if other == "cast":
+        return accept[0], "cast"
+    if other == "nonzero":
+        return _U8, "nonzero"
+    if other == "widen" and dt is not None and dt.kind in "biu":
+        return np.dtype(np.float64), "cast"
+    raise error(dt) if error else TypeError(f"dtype {dt} is not accepted here ({', '.join(str(d) for d in accept)})")
+
+
+def operand(x, ctx, accept, other="reject", error=None, to_device=False) -> Operand:
+    """`x` (DeviceArray, NumPy array, torch CPU / CUDA tensor) as a contiguous array of one of the dtypes `accept`.
+
+    bool passes as its bytes where uint8 is accepted.  `other` says what becomes of every other dtype: "cast" to
+    ``accept[0]``, "nonzero" (``x != 0`` as uint8), "widen" (bool and integers to float64) or "reject"; what is not
+    covered raises ``error(dtype)``.  A DeviceArray is never converted.  Host data stays on the host and `ctx` is not
+    touched unless `to_device` uploads it (for kernels that read HBM only).  Refused with ValueError: a CUDA tensor on
+    another GPU than `ctx`'s, a DeviceArray of another context."""
+    accept = tuple(np.dtype(d) for d in accept)
+    if isinstance(x, DeviceArray):
+        dt = _U8 if x.dtype == _BOOL and _U8 in accept else x.dtype
+        if dt not in accept:
+            raise error(dt) if error else TypeError(f"device array has dtype {dt}, expected {' or '.join(str(a) for a in accept)}")
+        if x.ctx is not ctx:
+            raise ValueError("device array belongs to another context")
+        return Operand(x.ptr, DEVICE, dt, x.shape, math.prod(x.shape), x)
+    if is_torch(x):
+        t = x.detach()
+        dt, how = _convert(_TORCH_NP.get(t.dtype), accept, other, error)
+        if how is not None:
+            t = t.to(_NP_TORCH[dt]) if how == "cast" else (t if how == "view" else t != 0).view(torch.uint8)
+        t = t.contiguous()
+        if t.is_cuda:
+            if t.device.index not in (None, ctx.device_index):
+                raise ValueError(f"tensor is on {t.device}, the context on GPU {ctx.device_index}")
+            # torch's work on the tensor is queued on torch's stream, the kernel on the context's: wait for the first
+            torch.cuda.current_stream(t.device).synchronize()
+            return Operand(t.data_ptr(), DEVICE, dt, tuple(x.shape), t.numel(), t)
+        a = t.numpy()
+    else:
+        a = np.asarray(x)
+        dt, how = _convert(a.dtype, accept, other, error)
+        if how is not None:
+            a = a.astype(dt) if how == "cast" else (a if how == "view" else a != 0).view(np.uint8)
+    shape, a = a.shape, np.ascontiguousarray(a)            # (a 0-d array comes back 1-d: the shape is the caller's)
+    if to_device:
+        d = ctx.to_device(a)
+        return Operand(d.ptr, DEVICE, dt, shape, a.size, d)
+    return Operand(a.ctypes.data, HOST, dt, shape, a.size, a)
+
+
+def as_pointer(x, dtype, ctx: Context):
+    """-> (ptr, mem, keepalive) of `x` as contiguous `dtype`, cast where it is another."""
+    o = operand(x, ctx, (dtype,), "cast")
+    return o.ptr, o.mem, o.keep
+
+
+def check_out(out):
+    if out not in ("host", "device"):
+        raise ValueError(f"out must be 'host' or 'device', got {out!r}")
+
+
+def result_buffer(ctx, shape, dtype, out, like):
+    """-> (result, ptr, mem): a DeviceArray for ``out="device"``; else a torch tensor on `like`'s GPU when `like` is a
+    CUDA tensor, else a NumPy array."""
+    if out == "device":
+        res = ctx.empty(shape, dtype)
+        return res, res.ptr, DEVICE
+    if is_torch(like) and like.is_cuda:
+        res = torch.empty(shape, dtype=_NP_TORCH[np.dtype(dtype)], device=like.device)
+        # torch's allocator may hand out memory that work still queued on torch's stream uses: wait for it
+        torch.cuda.current_stream(like.device).synchronize()
+        return res, res.data_ptr(), DEVICE
+    res = np.empty(shape, dtype)
+    return res, res.ctypes.data, HOST
+
+
+def P(d):
+    """c_void_p of what holds a device pointer in ``.ptr`` (None stays None)."""
+    return None if d is None else C.c_void_p(d.ptr)
+
+
+def ptr_mem(a):
+    """-> (c_void_p or None, memory kind) of a DeviceArray, a NumPy array or None."""
+    if isinstance(a, DeviceArray):
+        return P(a), DEVICE
+    return (None if a is None else a.ctypes.data_as(C.c_void_p)), HOST

@@ -26,7 +26,7 @@ import torch
 
 from ._lib import AugmentConfig, check, lib
 from .evaluation.metrics import _dice, _f1, _iou, _precision, _recall
-from .runtime import Context, as_pointer, is_torch
+from .runtime import as_pointer, context_for, is_torch
 
 
 def _pair(ds):
@@ -166,15 +166,15 @@ class Augmenter:
         if lshape != shape[:3]:
             raise ValueError(f"labels shape {lshape} does not match images {shape}")
         n, h, w, c = shape
-        ctx = Context.get(self.device)
+        ctx = context_for(self.device, images, labels)
         xp, xm, k1 = as_pointer(images, np.float32, ctx)
         yp, ym, k2 = as_pointer(labels, np.uint8, ctx)
         x_out, y_out = ctx.empty(shape, np.float32), ctx.empty(lshape, np.uint8)
         cfg = self._config()
         check(lib.rfi_augment_batch(ctx.handle, C.c_void_p(xp), xm, C.c_void_p(yp), ym, n, h, w, c, C.byref(cfg), call,
                                     C.c_void_p(x_out.ptr), C.c_void_p(y_out.ptr)))
-        if any(is_torch(v) and v.is_cuda for v in (images, labels)):
-            ctx.synchronize()                 # before torch's allocator may hand the (possibly temporary) tensors out again
+        if any(is_torch(k) for k in (k1, k2)):
+            ctx.synchronize()                 # before torch's allocator may hand the (possibly temporary) CUDA tensors out again
         del k1, k2
         return x_out, y_out
 

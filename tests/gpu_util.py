@@ -1,19 +1,13 @@
 """Helpers shared by the -m gpu parity tests (call the HIP kernels through the C ABI)."""
-import ctypes as C
-
 import numpy as np
 import torch
 
 from rfi_toolbox_amd._lib import IMPL_AUTO, IMPL_DIRECT, IMPL_MFMA, check, lib  # noqa: F401
-from rfi_toolbox_amd.runtime import Context
+from rfi_toolbox_amd.runtime import Context, P  # noqa: F401
 
 
 def ctx():
     return Context.get(0)
-
-
-def P(d):
-    return C.c_void_p(d.ptr) if d is not None else None
 
 
 def nhwc(t):            # torch NCHW -> numpy NHWC
