@@ -398,6 +398,18 @@ def train_step(state, adam, x_nchw, y, lr=1e-4, betas=(0.9, 0.999), eps=1e-8,
     loss, logits, grads, bufs = loss_and_grads(state, x_nchw, y, training=True, tape=tape, forward_fn=forward_fn,
                                                loss_fn=loss_fn)
     total, coef = clip_coefficient(grads, clip)
+    adam_update(state, adam, grads, coef, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+    with torch.no_grad():
+        for k, v in bufs.items():
+            state[k] = v
+    return {"loss": float(loss), "grad_norm": float(total), "clip_coef": float(coef),
+            "logits": logits, "grads": grads}
+
+
+def adam_update(state, adam, grads, coef, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-5):
+    """The Adam half of ``train_step``: advance ``adam["step"]`` and update ``state`` / ``adam`` in place from the
+    gradients ``grads`` ({name: tensor}) scaled by the clip coefficient ``coef`` (a tensor or a float).  Runs in the
+    dtype of its tensors: float32 as the reference does, float64 as the yardstick of tests/loss_step_cases.py."""
     adam["step"] += 1
     t = adam["step"]
     b1, b2 = betas
@@ -414,10 +426,6 @@ def train_step(state, adam, x_nchw, y, lr=1e-4, betas=(0.9, 0.999), eps=1e-8,
             v = adam["v"][k].mul_(b2).addcmul_(g, g, value=1 - b2)
             denom = (v.sqrt() / math.sqrt(bc2)).add_(eps)
             state[k] = p.addcdiv(m, denom, value=-(lr / bc1))
-        for k, v in bufs.items():
-            state[k] = v
-    return {"loss": float(loss), "grad_norm": float(total), "clip_coef": float(coef),
-            "logits": logits, "grads": grads}
 
 
 # --------------------------------------------------------------------------

@@ -995,23 +995,30 @@ __global__ void focal_finish_kernel(const double* __restrict__ partial, int bloc
 // d FL / d x (closed form), times 1/N
 __global__ void focal_bwd_kernel(const float* __restrict__ logits, const uint8_t* __restrict__ labels, int64_t count,
                                  float alpha, float gamma, float* __restrict__ dlogits) {
-    const float invN = (float)(1.0 / (double)count);
+    const double n = (double)count;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) {
         const float x = logits[i];
         const bool pos = labels[i] != 0;
-        const float p = sigmoidf_(x);
+        // p and q = 1 - p from one exp, neither by subtraction from 1: with q = 1.0f - p the term gamma q softplus(x) of a
+        // background pixel is off by gamma x 2^-24 (q is 0 from x = 17 on, where the term is still 6e-7 at gamma = 0.5).
+        // The three library calls stay float32; the few products and sums around them are formed in double and rounded
+        // once, which keeps a pixel within about 2 x 2^-24 of the largest gradient
+        const float e = expf(-fabsf(x));
+        const double l1p = (double)log1pf(e);
+        const double big = 1.0 / (1.0 + (double)e), small = (double)e * big;      // sigmoid(|x|), sigmoid(-|x|)
+        const double p = x >= 0.0f ? big : small, q = x >= 0.0f ? small : big;
         // log p and log(1-p) without cancellation: -softplus(-x), -softplus(x)
-        const float sp_neg = fmaxf(-x, 0.0f) + log1pf(expf(-fabsf(x)));     // softplus(-x) = -log p
-        const float sp_pos = fmaxf(x, 0.0f) + log1pf(expf(-fabsf(x)));      // softplus(x)  = -log(1-p)
-        float g;
+        const double sp_neg = (double)fmaxf(-x, 0.0f) + l1p;     // softplus(-x) = -log p
+        const double sp_pos = (double)fmaxf(x, 0.0f) + l1p;      // softplus(x)  = -log(1-p)
+        double g;
         if (pos) {       // FL = -a (1-p)^g log p
-            const float a = alpha >= 0.0f ? alpha : 1.0f;
-            g = a * powf(1.0f - p, gamma) * (gamma * p * (-sp_neg) - (1.0f - p));
+            const double a = alpha >= 0.0f ? alpha : 1.0f;
+            g = a * (double)powf((float)q, gamma) * ((double)gamma * p * (-sp_neg) - q);
         } else {         // FL = -(1-a) p^g log(1-p)
-            const float a = alpha >= 0.0f ? 1.0f - alpha : 1.0f;
-            g = a * powf(p, gamma) * (p - gamma * (1.0f - p) * (-sp_pos));
+            const double a = alpha >= 0.0f ? 1.0 - (double)alpha : 1.0;
+            g = a * (double)powf((float)p, gamma) * (p + (double)gamma * q * sp_pos);
         }
-        dlogits[i] = g * invN;
+        dlogits[i] = (float)(g / n);
     }
 }
 
