@@ -16,4 +16,6 @@ def __getattr__(name):
         return importlib.import_module(f"{__name__}.{name}")
     if name in ("label_components", "component_table", "remove_small_components", "instances_from_masks", "InstanceTargets"):
         return getattr(importlib.import_module(f"{__name__}.components"), name)
+    if name in ("event_instances", "event_table", "EVENT_CLASSES"):
+        return getattr(importlib.import_module(f"{__name__}.core"), name)
     raise AttributeError(name)

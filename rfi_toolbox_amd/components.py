@@ -186,11 +186,13 @@ class InstanceTargets:
     ``n_survivors`` (n,) (> count: the plane had more than G instances and the smallest were cut), ``base`` (n,) (exclusive prefix
     sum of count), ``component`` (n, G) (the label of ``label_components`` each slot came from), ``masks`` uint8
     (sum of count, H, W) or None -- all ``DeviceArray``s -- plus the host copies ``count_host``, ``n_survivors_host`` and
-    ``n_components_host``.  Slots are in descending area, ties by ascending label."""
+    ``n_components_host``.  Slots are in descending area, ties by ascending label.  ``num_classes``: the classes the labels
+    need, background included (2 here; 6 for the emitter families of ``core.event_instances``)."""
 
     def __init__(self, shape, boxes, labels, count, n_survivors, base, component, masks, count_host, n_survivors_host,
-                 n_components_host):
+                 n_components_host, num_classes=2):
         self.shape = tuple(shape)                      # (H, W) of a plane
+        self.num_classes = int(num_classes)
         self.boxes, self.labels, self.count, self.n_survivors, self.base, self.component, self.masks = \
             boxes, labels, count, n_survivors, base, component, masks
         self.count_host, self.n_survivors_host, self.n_components_host = (np.asarray(a, np.int32) for a in
@@ -230,7 +232,8 @@ def instances_from_masks(masks, connectivity=8, min_area=1, min_side=1, max_inst
     per plane, the largest first (``InstanceTargets``).  ``instance_masks=False`` leaves ``masks`` out.
 
     On simulator masks expect one large instance plus specks: crossing narrow- and broadband lines merge into one
-    component.  The function is for labelled data whose emitters are separate."""
+    component.  The function is for labelled data whose emitters are separate; for the batches of ``RFISimulator``,
+    ``core.event_instances`` gives one instance per emitter."""
     shape, n, h, w = _check_masks("masks", masks, connectivity)
     min_area, min_side = _positive("min_area", min_area), _positive("min_side", min_side)
     if isinstance(max_instances, (bool, np.bool_)) or not isinstance(max_instances, (int, np.integer)) or \

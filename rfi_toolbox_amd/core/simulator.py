@@ -24,10 +24,23 @@ EVENT_DTYPE = np.dtype([("i0", "<i4"), ("i1", "<i4"), ("i2", "<i4"), ("i3", "<i4
                         ("r0", "<f8"), ("phi0", "<f8"), ("v0", "<f8"), ("v1", "<f8")])
 _LAYOUTS = {"complex128": 0, "complex64": 1, "nchw": 2, "nhwc": 3}
 
-SimBatch = namedtuple("SimBatch", ["data", "mask", "baseline_frac", "events"])
-SimBatch.__doc__ = """generate_batch's result, all in HBM: data DeviceArray (layout of ``out``), mask DeviceArray
-(n, T, F) uint8, baseline_frac DeviceArray (n,) float64 (None when clean), events DeviceArray
-(n, event_slots(T, F)) of EVENT_DTYPE (None when clean)."""
+SimOrigin = namedtuple("SimOrigin", ["seed", "first_sample", "T", "F", "params", "power"])
+SimOrigin.__doc__ = """What generated a SimBatch: the Philox key ``seed``, the global index ``first_sample`` of its sample 0,
+the plane size, the filled ``SimParams`` of the call (a snapshot: detect_floor, fringes, ...) and the device power table
+it drew from (held here, so it outlives a later change of ``power_range``)."""
+
+
+class SimBatch(namedtuple("SimBatch", ["data", "mask", "baseline_frac", "events"])):
+    """generate_batch's result, all in HBM: data DeviceArray (layout of ``out``), mask DeviceArray
+    (n, T, F) uint8, baseline_frac DeviceArray (n,) float64 (None when clean), events DeviceArray
+    (n, event_slots(T, F)) of EVENT_DTYPE (None when clean).  A 4-tuple of those; the attribute ``origin`` (SimOrigin,
+    not a field) carries what ``event_table`` / ``event_instances`` need to recompute each event's own pixels."""
+    origin = None
+
+    def __new__(cls, data, mask, baseline_frac, events, origin=None):
+        self = super().__new__(cls, data, mask, baseline_frac, events)
+        self.origin = origin
+        return self
 
 
 def event_slots(time_bins, freq_bins):
@@ -137,8 +150,9 @@ class RFISimulator:
                                    C.c_void_p(self._power_dev.ptr), _LAYOUTS[out], C.c_void_p(data.ptr),
                                    C.c_void_p(mask.ptr), C.c_void_p(events.ptr) if events is not None else None,
                                    C.c_void_p(bl.ptr) if bl is not None else None))
+        origin = SimOrigin(self.seed, self.sample_counter, T, F, p, self._power_dev)
         self.sample_counter += n
-        return SimBatch(data, mask, bl, events)
+        return SimBatch(data, mask, bl, events, origin)
 
     # ---- the reference's surface
     def generate_clean_data(self):

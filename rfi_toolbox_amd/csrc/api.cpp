@@ -1192,6 +1192,46 @@ int rfi_simulate_rfi(rfi_ctx* ctx, uint64_t seed, uint64_t first_sample, int n_s
     });
 }
 namespace {
+// the size limits rfi_simulate_rfi puts on a batch with events, for the entry points that recompute from its event table
+void require_sim_events_batch(const char* who, const rfi_sim_params& p, uint64_t first_sample, int n_samples) {
+    const std::string w(who);
+    const int64_t T = p.time_bins, F = p.freq_bins;
+    RFI_REQUIRE(!p.clean, w + ": a clean batch has no events");
+    RFI_REQUIRE(T >= 4 && F >= 52, w + ": needs time_bins >= 4 and freq_bins >= 52 (the reference's randint bounds)");
+    RFI_REQUIRE(T * F < ((int64_t)1 << 32), w + ": time_bins * freq_bins must stay below 2^32");
+    RFI_REQUIRE(n_samples >= 0, w + ": negative sample count");
+    RFI_REQUIRE(first_sample + (uint64_t)n_samples <= ((uint64_t)1 << 32), w + ": sample counter past 2^32");
+    RFI_REQUIRE(n_samples * T * ((F + 255) / 256) < ((int64_t)1 << 31), w + ": batch too large for one launch");
+    RFI_REQUIRE(p.n_power >= 1 && p.n_power <= 1024, w + ": power_range must have 1..1024 entries");
+}
+}  // namespace
+int rfi_sim_event_table(rfi_ctx* ctx, uint64_t seed, uint64_t first_sample, int n_samples, const rfi_sim_params* params,
+                        const double* power_range_dev, const rfi_sim_event* events_dev, int32_t* area, int32_t* box) {
+    return guarded([&] {
+        RFI_REQUIRE(ctx && params, "sim_event_table: null argument");
+        require_sim_events_batch("sim_event_table", *params, first_sample, n_samples);
+        RFI_REQUIRE(power_range_dev && events_dev && area && box, "sim_event_table: null buffer");
+        if (n_samples == 0) return;
+        ctx->activate();
+        launch_rfi_sim_event_table(ctx, seed, (unsigned)first_sample, n_samples, *params, power_range_dev, events_dev, area, box);
+    });
+}
+int rfi_sim_instances(rfi_ctx* ctx, uint64_t seed, uint64_t first_sample, int n_samples, const rfi_sim_params* params,
+                      const double* power_range_dev, const rfi_sim_event* events_dev, const int32_t* component, const int32_t* count,
+                      const int32_t* base, int max_instances, int class_mode, int32_t* labels, uint8_t* masks) {
+    return guarded([&] {
+        RFI_REQUIRE(ctx && params, "sim_instances: null argument");
+        require_sim_events_batch("sim_instances", *params, first_sample, n_samples);
+        RFI_REQUIRE(max_instances >= 1 && max_instances <= 256, "sim_instances: max_instances must be in 1 .. 256");
+        RFI_REQUIRE(class_mode == RFI_SIM_CLASS_SINGLE || class_mode == RFI_SIM_CLASS_FAMILY, "sim_instances: bad class_mode");
+        RFI_REQUIRE(power_range_dev && events_dev && component && count && base && labels, "sim_instances: null buffer");
+        if (n_samples == 0) return;
+        ctx->activate();
+        launch_rfi_sim_instances(ctx, seed, (unsigned)first_sample, n_samples, *params, power_range_dev, events_dev, component, count,
+                                 base, max_instances, class_mode, labels, masks);
+    });
+}
+namespace {
 void norm_bracket(int64_t count, double q, int64_t* ranks, double* frac) {
     const double v = q * (double)(count - 1), f = std::floor(v);
     ranks[0] = (int64_t)f;

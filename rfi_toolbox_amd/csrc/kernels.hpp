@@ -412,6 +412,13 @@ void launch_instance_masks(rfi_ctx* ctx, const int* labels, int n, int h, int w,
 void launch_rfi_sim(rfi_ctx* ctx, unsigned long long seed, unsigned first_sample, int n_samples,
                     const rfi_sim_params& p, const double* power_dev, int layout, void* out, uint8_t* mask,
                     rfi_sim_event* events, double* baseline_out);
+// per-event targets recomputed from the event table (rfi_sim.hip; include/rfi_hip.h, "per-emitter targets"): area and box of
+// every event slot; classes and instance masks of the slots rfi_op_instances_select kept.  Sizes are checked by the callers
+void launch_rfi_sim_event_table(rfi_ctx* ctx, unsigned long long seed, unsigned first_sample, int n_samples, const rfi_sim_params& p,
+                                const double* power_dev, const rfi_sim_event* events, int* area, int* box);
+void launch_rfi_sim_instances(rfi_ctx* ctx, unsigned long long seed, unsigned first_sample, int n_samples, const rfi_sim_params& p,
+                              const double* power_dev, const rfi_sim_event* events, const int* component, const int* count,
+                              const int* base, int max_instances, int class_mode, int* labels, uint8_t* masks);
 
 // x[i] *= f  (the emulated gradient exchange of the single-GPU tests, rfi_comm_emulate)
 void launch_scale_inplace(rfi_ctx* ctx, float* x, int64_t n, float f);

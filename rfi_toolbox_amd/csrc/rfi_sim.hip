@@ -15,6 +15,10 @@
 // segment of each chunk, with an 8-column halo on either side, in LDS (<= 3 chunks x 272 x 16 B) and every lane
 // sums its 17 taps from there.  Narrowband / burst lines are one value per (event, row) or (event, column) and
 // are evaluated by the lanes that need them.
+//
+// Per-emitter targets (below the pixel kernel): rfisim_event_table_kernel and rfisim_instance_masks_kernel recompute the
+// pixels each event ALONE flags from the event table, through the device functions the pixel kernel decides its mask
+// with -- one event is one instance of the detector's ground truth (include/rfi_hip.h, "per-emitter targets").
 #include "kernels.hpp"
 
 namespace rfi {
@@ -93,6 +97,17 @@ __device__ void draw_phase(const SimDev& d, const unsigned* w, int width, int nt
     }
 }
 
+// which event a table slot holds (the order of RFI_SIM_SLOTS): -> category S_HEADER .. S_QUAD, k = its index there
+__device__ __forceinline__ int slot_category(int slot, int NN, int NB, int& k) {
+    if (slot == 0) { k = 0; return S_HEADER; }
+    if (slot < 4) { k = slot - 1; return S_BROAD; }
+    if (slot < 4 + NN) { k = slot - 4; return S_NARROW; }
+    if (slot < 4 + NN + NB) { k = slot - 4 - NN; return S_BURST; }
+    if (slot < 9 + NN + NB) { k = slot - 4 - NN - NB; return S_LINEAR; }
+    k = slot - 9 - NN - NB;
+    return S_QUAD;
+}
+
 __global__ void rfisim_events_kernel(SimDev d) {
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= (int64_t)d.n * d.slots) return;
@@ -102,13 +117,8 @@ __global__ void rfisim_events_kernel(SimDev d) {
     const U4 h = draw(d, 0, 0, S_HEADER, sample);
     const double bl = d.fixed_bl ? d.bl : u53(h.x, h.y);
     rfi_sim_event e{};
-    int cat, k;
-    if (slot == 0) { cat = S_HEADER; k = 0; }
-    else if (slot < 4) { cat = S_BROAD; k = slot - 1; }
-    else if (slot < 4 + d.NN) { cat = S_NARROW; k = slot - 4; }
-    else if (slot < 4 + d.NN + d.NB) { cat = S_BURST; k = slot - 4 - d.NN; }
-    else if (slot < 9 + d.NN + d.NB) { cat = S_LINEAR; k = slot - 4 - d.NN - d.NB; }
-    else { cat = S_QUAD; k = slot - 9 - d.NN - d.NB; }
+    int k;
+    const int cat = slot_category(slot, d.NN, d.NB, k);
     unsigned w[20];
 #pragma unroll
     for (int j = 0; j < 5; ++j) {
@@ -175,6 +185,37 @@ __device__ __forceinline__ double2 broadband_field(const SimDev& d, const rfi_si
     const double mod = uniform(0.5, 2.0, r.x, r.y);
     return field(mod * d.power[power_index(r.z, d.n_power)], phase(e, t, f));
 }
+// What one event deposits and where: the pixel kernel and the per-event kernels below (table, instance masks) decide
+// "event e flags pixel (t, f)" through these and nothing else, so an event's own mask is the pixel kernel's term of it.
+__device__ __forceinline__ double2 narrowband_field(const SimDev& d, const rfi_sim_event& e, int k, int t, unsigned sample) {
+    const U4 r = draw(d, (unsigned)t, (unsigned)k, S_NARROW_PT, sample);
+    return field(uniform(0.5, 2.0, r.x, r.y) * e.v0, phase(e, t, e.i0));
+}
+__device__ __forceinline__ double2 burst_field(const SimDev& d, const rfi_sim_event& e, int k, int f, unsigned sample) {
+    const U4 r = draw(d, (unsigned)f, (unsigned)k, S_BURST_PT, sample);
+    return field(uniform(0.5, 2.0, r.x, r.y) * e.v0, phase(e, e.i0, f));
+}
+__device__ __forceinline__ bool detectable(double2 v, double floor) { return hypot(v.x, v.y) > floor; }
+// sweep point index of row t (a sweep visits distinct rows), < T/2 or T/4 on the sweep
+__device__ __forceinline__ int sweep_point(const rfi_sim_event& e, int t, int T) { return (t - e.i0 + T) % T; }
+// linear: channel int(start_f + slope i) % F
+__device__ __forceinline__ int linear_channel(const rfi_sim_event& e, int i, int F) {
+    const long long q = (long long)((double)e.i1 + e.v0 * (double)i);   // int(): toward zero
+    int fi = (int)(q % F);
+    if (fi < 0) fi += F;                                              // Python's % F
+    return fi;
+}
+// quadratic: channel (start_f + (direction t^2) // 100) % F, floor division
+__device__ __forceinline__ int quadratic_channel(const rfi_sim_event& e, int tt, int F) {
+    const long long num = (long long)e.i2 * (long long)tt * (long long)tt;
+    const long long fl = num >= 0 ? num / 100 : -((-num + 99) / 100);
+    int fi = (int)(((long long)e.i1 + fl) % F);
+    if (fi < 0) fi += F;
+    return fi;
+}
+__device__ __forceinline__ double sweep_amp(const SimDev& d, int point, int k, unsigned stream, unsigned sample) {
+    return d.power[power_index(draw(d, (unsigned)point, (unsigned)k, stream, sample).x, d.n_power)];
+}
 __device__ __forceinline__ void add(double2& acc, double2 v) {
     acc.x = acc.x + v.x;
     acc.y = acc.y + v.y;
@@ -219,7 +260,7 @@ __global__ __launch_bounds__(kChunk) void rfisim_pixels_kernel(SimDev d) {
                 const int c0 = E[1 + b].i0, c1 = c0 + E[1 + b].i1;
                 if (active && f >= c0 && f < c1) {
                     const double2 own = seg[b][f - f0 + kHalo];
-                    m = m || hypot(own.x, own.y) > floor;
+                    m = m || detectable(own, floor);
                     // np.convolve(row, k, 'same'): out[f] = sum_c row[c] k[f - c + 8], zeros outside the chunk
                     double2 acc = make_double2(0.0, 0.0);
                     const int lo = max(c0, f - kHalo), hi = min(c1 - 1, f + kHalo);
@@ -238,7 +279,7 @@ __global__ __launch_bounds__(kChunk) void rfisim_pixels_kernel(SimDev d) {
                 const rfi_sim_event e = E[1 + b];
                 if (active && f >= e.i0 && f < e.i0 + e.i1) {
                     const double2 v = broadband_field(d, e, b, t, f, sample);
-                    m = m || hypot(v.x, v.y) > floor;
+                    m = m || detectable(v, floor);
                     add(rr, v);
                     add(ll, v);
                 }
@@ -256,9 +297,8 @@ __global__ __launch_bounds__(kChunk) void rfisim_pixels_kernel(SimDev d) {
                 const int df = f - __builtin_amdgcn_readlane(mine, j);
                 if (active && (RING ? (df >= -kHalo && df <= kHalo) : df == 0)) {
                     const rfi_sim_event e = E[4 + k];
-                    const U4 r = draw(d, (unsigned)t, (unsigned)k, S_NARROW_PT, sample);
-                    const double2 v = field(uniform(0.5, 2.0, r.x, r.y) * e.v0, phase(e, t, e.i0));
-                    if (df == 0) m = m || hypot(v.x, v.y) > floor;
+                    const double2 v = narrowband_field(d, e, k, t, sample);
+                    if (df == 0) m = m || detectable(v, floor);
                     const double2 c = RING ? make_double2(v.x * d.gk[df + kHalo], v.y * d.gk[df + kHalo]) : v;
                     add(rr, c);
                     add(ll, c);
@@ -274,9 +314,8 @@ __global__ __launch_bounds__(kChunk) void rfisim_pixels_kernel(SimDev d) {
                 const int dt = t - __builtin_amdgcn_readlane(mine, j);
                 if (active && (RING ? (dt >= -kHalo && dt <= kHalo) : dt == 0)) {
                     const rfi_sim_event e = E[4 + d.NN + k];
-                    const U4 r = draw(d, (unsigned)f, (unsigned)k, S_BURST_PT, sample);
-                    const double2 v = field(uniform(0.5, 2.0, r.x, r.y) * e.v0, phase(e, e.i0, f));
-                    if (dt == 0) m = m || hypot(v.x, v.y) > floor;
+                    const double2 v = burst_field(d, e, k, f, sample);
+                    if (dt == 0) m = m || detectable(v, floor);
                     const double2 c = RING ? make_double2(d.gk[dt + kHalo] * v.x, d.gk[dt + kHalo] * v.y) : v;
                     add(rr, c);
                     add(ll, c);
@@ -286,14 +325,11 @@ __global__ __launch_bounds__(kChunk) void rfisim_pixels_kernel(SimDev d) {
         // linear sweeps (:201-214): point i = t - start_t, channel int(start_f + slope i) % F
         for (int k = 0; k < 5; ++k) {
             const rfi_sim_event e = E[4 + d.NN + d.NB + k];
-            const int i = (t - e.i0 + T) % T;
+            const int i = sweep_point(e, t, T);
             if (i < T / 2) {
-                const long long q = (long long)((double)e.i1 + e.v0 * (double)i);   // int(): toward zero
-                int fi = (int)(q % F);
-                if (fi < 0) fi += F;                                              // Python's % F
+                const int fi = linear_channel(e, i, F);
                 if (active && f == fi) {
-                    const double amp = d.power[power_index(draw(d, (unsigned)i, (unsigned)k, S_LINEAR_PT, sample).x,
-                                                           d.n_power)];
+                    const double amp = sweep_amp(d, i, k, S_LINEAR_PT, sample);
                     const double2 v = field(amp, phase(e, t, fi));
                     add(rr, v);
                     add(ll, v);
@@ -304,15 +340,11 @@ __global__ __launch_bounds__(kChunk) void rfisim_pixels_kernel(SimDev d) {
         // quadratic sweeps, RR only (:216-228): channel (start_f + (direction t^2) // 100) % F, floor division
         for (int k = 0; k < 5; ++k) {
             const rfi_sim_event e = E[9 + d.NN + d.NB + k];
-            const int tt = (t - e.i0 + T) % T;
+            const int tt = sweep_point(e, t, T);
             if (tt < T / 4) {
-                const long long num = (long long)e.i2 * (long long)tt * (long long)tt;
-                const long long fl = num >= 0 ? num / 100 : -((-num + 99) / 100);
-                int fi = (int)(((long long)e.i1 + fl) % F);
-                if (fi < 0) fi += F;
+                const int fi = quadratic_channel(e, tt, F);
                 if (active && f == fi) {
-                    const double amp = d.power[power_index(draw(d, (unsigned)tt, (unsigned)k, S_QUAD_PT, sample).x,
-                                                           d.n_power)];
+                    const double amp = sweep_amp(d, tt, k, S_QUAD_PT, sample);
                     add(rr, field(amp, phase(e, t, fi)));
                     m = m || amp > floor;
                 }
@@ -358,11 +390,201 @@ __global__ __launch_bounds__(kChunk) void rfisim_pixels_kernel(SimDev d) {
     }
 }
 
-}  // namespace
+// ---------------------------------------------------------------- per-event targets: table, classes, instance masks
+// One event is one instance.  Every pixel an event flags is recomputed from (seed, sample, event, position) with the
+// device functions above, so nothing here reads the mask or the waterfalls, and nothing depends on the launch geometry.
+constexpr int kTableBlock = 1024;    // threads of one (sample, slot) workgroup of the table kernel
+constexpr int kRun = 16;             // bytes of an instance mask one thread owns: one 16-byte store
 
-void launch_rfi_sim(rfi_ctx* ctx, unsigned long long seed, unsigned first_sample, int n_samples,
-                    const rfi_sim_params& p, const double* power_dev, int layout, void* out, uint8_t* mask,
-                    rfi_sim_event* events, double* baseline_out) {
+// pixels an event may flag: broadband width x T, narrowband T, burst F, linear T/2 points, quadratic T/4 points
+__device__ __forceinline__ int64_t event_support(const SimDev& d, const rfi_sim_event& e, int cat) {
+    switch (cat) {
+    case S_BROAD: return (int64_t)e.i1 * d.T;
+    case S_NARROW: return d.T;
+    case S_BURST: return d.F;
+    case S_LINEAR: return d.T / 2;
+    case S_QUAD: return d.T / 4;
+    default: return 0;
+    }
+}
+// item `it` of the support -> its pixel (t, f) and whether the event flags it
+__device__ __forceinline__ bool event_item(const SimDev& d, const rfi_sim_event& e, int cat, int k, int64_t it, unsigned sample,
+                                           int& t, int& f) {
+    switch (cat) {
+    case S_BROAD:
+        t = (int)(it / e.i1);
+        f = e.i0 + (int)(it % e.i1);
+        return detectable(broadband_field(d, e, k, t, f, sample), d.floor);
+    case S_NARROW:
+        t = (int)it;
+        f = e.i0;
+        return detectable(narrowband_field(d, e, k, t, sample), d.floor);
+    case S_BURST:
+        t = e.i0;
+        f = (int)it;
+        return detectable(burst_field(d, e, k, f, sample), d.floor);
+    case S_LINEAR:
+        t = (e.i0 + (int)it) % d.T;                    // sweep_point(e, t, T) == it
+        f = linear_channel(e, (int)it, d.F);
+        return sweep_amp(d, (int)it, k, S_LINEAR_PT, sample) > d.floor;
+    default:                                           // S_QUAD
+        t = (e.i0 + (int)it) % d.T;
+        f = quadratic_channel(e, (int)it, d.F);
+        return sweep_amp(d, (int)it, k, S_QUAD_PT, sample) > d.floor;
+    }
+}
+// the event's flags on columns [fa, fb) of row t (fb - fa <= kRun): bit j = pixel (t, fa + j).  Only a broadband interior
+// and the one column / row / point of a line event evaluate a draw.
+__device__ __forceinline__ unsigned event_row_bits(const SimDev& d, const rfi_sim_event& e, int cat, int k, int t, int fa, int fb,
+                                                   unsigned sample) {
+    unsigned bits = 0;
+    switch (cat) {
+    case S_BROAD:
+        for (int f = max(fa, e.i0), hi = min(fb, e.i0 + e.i1); f < hi; ++f)
+            bits |= (unsigned)detectable(broadband_field(d, e, k, t, f, sample), d.floor) << (f - fa);
+        break;
+    case S_NARROW:
+        if (e.i0 >= fa && e.i0 < fb) bits = (unsigned)detectable(narrowband_field(d, e, k, t, sample), d.floor) << (e.i0 - fa);
+        break;
+    case S_BURST:
+        if (t == e.i0)
+            for (int f = fa; f < fb; ++f) bits |= (unsigned)detectable(burst_field(d, e, k, f, sample), d.floor) << (f - fa);
+        break;
+    case S_LINEAR: {
+        const int i = sweep_point(e, t, d.T);
+        if (i < d.T / 2) {
+            const int fi = linear_channel(e, i, d.F);
+            if (fi >= fa && fi < fb) bits = (unsigned)(sweep_amp(d, i, k, S_LINEAR_PT, sample) > d.floor) << (fi - fa);
+        }
+        break;
+    }
+    case S_QUAD: {
+        const int tt = sweep_point(e, t, d.T);
+        if (tt < d.T / 4) {
+            const int fi = quadratic_channel(e, tt, d.F);
+            if (fi >= fa && fi < fb) bits = (unsigned)(sweep_amp(d, tt, k, S_QUAD_PT, sample) > d.floor) << (fi - fa);
+        }
+        break;
+    }
+    default: break;
+    }
+    return bits;
+}
+// the record of slot `slot` of sample s when it is a live event: a slot out of 1 .. slots - 1 and a broadband chunk the
+// header does not use are no event
+__device__ __forceinline__ bool live_event(const SimDev& d, int s, int slot, rfi_sim_event& e, int& cat, int& k) {
+    if (slot < 1 || slot >= d.slots) return false;
+    const rfi_sim_event* __restrict__ E = d.ev + (int64_t)s * d.slots;
+    cat = slot_category(slot, d.NN, d.NB, k);
+    if (cat == S_BROAD && k >= E[0].i0) return false;
+    e = E[slot];
+    return true;
+}
+
+// area and inclusive box of every event: one workgroup per (sample, slot 1 .. slots - 1); threads stride over the support,
+// then a wave reduction and a fixed-order reduction of the waves' partial results in LDS
+__global__ __launch_bounds__(kTableBlock) void rfisim_event_table_kernel(SimDev d, int* __restrict__ area, int* __restrict__ box) {
+    __shared__ int part[kTableBlock / 64][5];
+    const int S = d.slots - 1, s = (int)(blockIdx.x / S), slot = (int)(blockIdx.x % S) + 1;
+    const unsigned sample = d.first + (unsigned)s;
+    rfi_sim_event e;
+    int cat = S_HEADER, k = 0;
+    const bool live = live_event(d, s, slot, e, cat, k);
+    int cnt = 0, x0 = 0x7fffffff, y0 = 0x7fffffff, x1 = -1, y1 = -1;
+    if (live) {
+        const int64_t support = event_support(d, e, cat);
+        for (int64_t it = threadIdx.x; it < support; it += kTableBlock) {
+            int t, f;
+            if (event_item(d, e, cat, k, it, sample, t, f)) {
+                ++cnt;
+                x0 = min(x0, f); x1 = max(x1, f);
+                y0 = min(y0, t); y1 = max(y1, t);
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        cnt += __shfl_down(cnt, o);
+        x0 = min(x0, __shfl_down(x0, o)); y0 = min(y0, __shfl_down(y0, o));
+        x1 = max(x1, __shfl_down(x1, o)); y1 = max(y1, __shfl_down(y1, o));
+    }
+    const int wave = (int)(threadIdx.x >> 6);
+    if ((threadIdx.x & 63) == 0) {
+        part[wave][0] = cnt; part[wave][1] = x0; part[wave][2] = y0; part[wave][3] = x1; part[wave][4] = y1;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kTableBlock / 64; ++w) {
+            cnt += part[w][0];
+            x0 = min(x0, part[w][1]); y0 = min(y0, part[w][2]);
+            x1 = max(x1, part[w][3]); y1 = max(y1, part[w][4]);
+        }
+        const int64_t o = (int64_t)s * S + slot - 1;
+        area[o] = cnt;
+        reinterpret_cast<int4*>(box)[o] = cnt ? make_int4(x0, y0, x1, y1) : make_int4(0, 0, 0, 0);
+    }
+}
+
+// labels[i][j] = class of slot component[i][j], j < count[i]: 1, or the slot's category (1 broadband .. 5 quadratic)
+__global__ void rfisim_instance_labels_kernel(SimDev d, const int* __restrict__ component, const int* __restrict__ count, int G,
+                                              int family, int* __restrict__ labels) {
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (int64_t)d.n * G) return;
+    const int i = (int)(gid / G), j = (int)(gid % G);
+    if (j >= count[i]) return;
+    const int slot = component[gid];
+    int k, cls = 0;
+    if (slot >= 1 && slot < d.slots) cls = family ? slot_category(slot, d.NN, d.NB, k) : 1;
+    labels[gid] = cls;
+}
+
+// masks[base[i] + j] = the pixels event component[i][j] alone flags, j < count[i], as a gather: a thread owns the kRun
+// bytes of one 16-byte-aligned address range, works out the rows and columns they are, asks the event for its bits there
+// and stores them once -- 16 bytes at a time inside a plane, byte by byte where the range is cut by the plane's first or
+// last byte (planes are T F bytes apart, so all but the first may start unaligned; the neighbouring plane's thread
+// writes the other bytes of that range).  One range per thread on purpose: a range inside a broadband chunk is 16 draws
+// (Philox, fp64 sincos, hypot) one after the other, and a thread that walked eight ranges measured 2x slower.
+// blockIdx: (instance slot i G + j) x blocks_per_plane + block of the plane.
+__global__ __launch_bounds__(256) void rfisim_instance_masks_kernel(SimDev d, const int* __restrict__ component,
+                                                                    const int* __restrict__ count, const int* __restrict__ base, int G,
+                                                                    int blocks_per_plane, uint8_t* __restrict__ masks) {
+    const int64_t inst = blockIdx.x / blocks_per_plane;
+    const int i = (int)(inst / G), j = (int)(inst % G);
+    if (j >= count[i]) return;
+    const int64_t HW = (int64_t)d.T * d.F;
+    uint8_t* plane = masks + ((int64_t)base[i] + j) * HW;
+    const int head = (int)(reinterpret_cast<uintptr_t>(plane) & (kRun - 1));
+    const int64_t c = (int64_t)(blockIdx.x % blocks_per_plane) * 256 + threadIdx.x;
+    const int64_t r0 = c * kRun - head;                  // the range [r0, r0 + kRun) in the plane's pixel indices
+    const int64_t p0 = max(r0, (int64_t)0), p1 = min(r0 + kRun, HW);
+    if (p0 >= p1) return;
+    rfi_sim_event e;
+    int cat = S_HEADER, k = 0;
+    unsigned bits = 0;                                   // bit b = pixel r0 + b
+    if (live_event(d, i, component[(int64_t)i * G + j], e, cat, k)) {
+        const unsigned sample = d.first + (unsigned)i;
+        int t = (int)(p0 / d.F), f = (int)(p0 - (int64_t)t * d.F);
+        for (int64_t p = p0; p < p1; ++t, f = 0) {
+            const int fb = (int)min((int64_t)d.F, f + (p1 - p));
+            bits |= event_row_bits(d, e, cat, k, t, f, fb, sample) << (int)(p - r0);
+            p += fb - f;
+        }
+    }
+    if (p1 - p0 == kRun) {
+        unsigned w[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const unsigned nib = (bits >> (4 * q)) & 15u;
+            w[q] = (nib & 1u) | (nib & 2u) << 7 | (nib & 4u) << 14 | (nib & 8u) << 21;
+        }
+        *reinterpret_cast<uint4*>(plane + r0) = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {
+        for (int64_t p = p0; p < p1; ++p) plane[p] = (uint8_t)((bits >> (int)(p - r0)) & 1u);
+    }
+}
+
+SimDev sim_dev(unsigned long long seed, unsigned first_sample, int n_samples, const rfi_sim_params& p, const double* power_dev,
+               rfi_sim_event* events) {
     SimDev d{};
     d.k0 = (unsigned)seed;
     d.k1 = (unsigned)(seed >> 32);
@@ -376,7 +598,6 @@ void launch_rfi_sim(rfi_ctx* ctx, unsigned long long seed, unsigned first_sample
     d.n_power = p.n_power;
     d.clean = p.clean ? 1 : 0;
     d.fixed_bl = p.fixed_baseline ? 1 : 0;
-    d.layout = layout;
     d.bl = p.baseline_frac;
     d.floor = p.detect_floor;
     d.drift_prob = p.drift_prob;
@@ -385,6 +606,16 @@ void launch_rfi_sim(rfi_ctx* ctx, unsigned long long seed, unsigned first_sample
     for (int i = 0; i < 17; ++i) d.gk[i] = p.gibbs_kernel[i];
     d.power = power_dev;
     d.ev = events;
+    return d;
+}
+
+}  // namespace
+
+void launch_rfi_sim(rfi_ctx* ctx, unsigned long long seed, unsigned first_sample, int n_samples,
+                    const rfi_sim_params& p, const double* power_dev, int layout, void* out, uint8_t* mask,
+                    rfi_sim_event* events, double* baseline_out) {
+    SimDev d = sim_dev(seed, first_sample, n_samples, p, power_dev, events);
+    d.layout = layout;
     d.bl_out = baseline_out;
     d.out = out;
     d.mask = mask;
@@ -402,6 +633,34 @@ void launch_rfi_sim(rfi_ctx* ctx, unsigned long long seed, unsigned first_sample
     else
         hipLaunchKernelGGL(rfisim_pixels_kernel<false>, dim3((unsigned)blocks), dim3(kChunk), 0, ctx->stream, d);
     check_launch("rfisim_pixels");
+}
+
+void launch_rfi_sim_event_table(rfi_ctx* ctx, unsigned long long seed, unsigned first_sample, int n_samples, const rfi_sim_params& p,
+                                const double* power_dev, const rfi_sim_event* events, int* area, int* box) {
+    RFI_REQUIRE(reinterpret_cast<uintptr_t>(box) % 16 == 0, "sim_event_table: box must be 16-byte aligned");
+    const SimDev d = sim_dev(seed, first_sample, n_samples, p, power_dev, const_cast<rfi_sim_event*>(events));   // (read only here)
+    const int64_t blocks = (int64_t)n_samples * (d.slots - 1);
+    RFI_REQUIRE(blocks < ((int64_t)1 << 31), "sim_event_table: batch too large for one launch");
+    ProfScope ps(ctx, FAM_PREPROCESS);
+    hipLaunchKernelGGL(rfisim_event_table_kernel, dim3((unsigned)blocks), dim3(kTableBlock), 0, ctx->stream, d, area, box);
+    check_launch("rfisim_event_table");
+}
+
+void launch_rfi_sim_instances(rfi_ctx* ctx, unsigned long long seed, unsigned first_sample, int n_samples, const rfi_sim_params& p,
+                              const double* power_dev, const rfi_sim_event* events, const int* component, const int* count,
+                              const int* base, int max_instances, int class_mode, int* labels, uint8_t* masks) {
+    const SimDev d = sim_dev(seed, first_sample, n_samples, p, power_dev, const_cast<rfi_sim_event*>(events));   // (read only here)
+    const int64_t slots = (int64_t)n_samples * max_instances, HW = (int64_t)d.T * d.F;
+    const int64_t per_plane = cdiv(HW / kRun + 2, 256);          // ranges of a plane: at most HW / 16 whole ones and two cut ones
+    RFI_REQUIRE(slots * per_plane < ((int64_t)1 << 31), "sim_instances: batch too large for one launch");
+    ProfScope ps(ctx, FAM_PREPROCESS);
+    hipLaunchKernelGGL(rfisim_instance_labels_kernel, dim3((unsigned)cdiv(slots, 256)), dim3(256), 0, ctx->stream, d, component, count,
+                       max_instances, class_mode, labels);
+    check_launch("rfisim_instance_labels");
+    if (!masks) return;
+    hipLaunchKernelGGL(rfisim_instance_masks_kernel, dim3((unsigned)(slots * per_plane)), dim3(256), 0, ctx->stream, d, component, count,
+                       base, max_instances, (int)per_plane, masks);
+    check_launch("rfisim_instance_masks");
 }
 
 }  // namespace rfi

@@ -466,6 +466,9 @@ class MaskRCNN:
                                  f"{n} images of {h} x {w}")
             if inst.masks is None or not isinstance(inst.boxes, DeviceArray) or inst.boxes.ctx is not self.backbone.ctx:
                 raise ValueError("MaskRCNN.train_step: InstanceTargets must hold instance masks and live on the detector's GPU")
+            if inst.num_classes > self.num_classes:             # (a label past the box head's width would index out of range)
+                raise ValueError(f"MaskRCNN.train_step: targets with labels of {inst.num_classes} classes for a detector of "
+                                 f"{self.num_classes}")
         ctx, F, k1 = self.backbone.ctx, self.F, self.num_classes
         H = ctx.handle
         for m in (self.rpn, self.box, self.mask):

@@ -3,10 +3,12 @@
 well ``predict`` recovers them: best box IoU per ground-truth region and the IoU of the union mask.  A functional
 demonstration (the pieces are parity-tested one by one), not a benchmark.
 
-    python tools/demo_mask_rcnn.py [--steps 200] [--dtype float32|bfloat16] [--detect] [--from-masks]
+    python tools/demo_mask_rcnn.py [--steps 200] [--dtype float32|bfloat16] [--detect] [--from-masks | --from-simulator]
 
 ``--from-masks`` trains on instance targets that ``instances_from_masks`` builds on the GPU from ONE binary mask per image
-(the union of its rectangles: two that touch become one instance) instead of the per-rectangle targets.  ``--detect`` runs ``MaskRCNN.detect`` (inference on the device) too and prints whether both forms agree."""
+(the union of its rectangles: two that touch become one instance) instead of the per-rectangle targets.  ``--from-simulator`` trains a six-class detector on ``RFISimulator`` samples instead: 8-channel
+NHWC planes from ``generate_batch(out="nhwc")``, normalised per sample (``robust_scale``), with one instance per emitter and a class per
+emitter family from ``event_instances`` -- images, targets and instance masks never leave the GPU.  ``--detect`` runs ``MaskRCNN.detect`` (inference on the device) too and prints whether both forms agree."""
 import argparse
 import os
 import sys
@@ -45,13 +47,28 @@ def main():
     ap.add_argument("--images", type=int, default=4)
     ap.add_argument("--detect", action="store_true", help="run MaskRCNN.detect too and compare it with predict")
     ap.add_argument("--from-masks", action="store_true", help="build the targets from each image's binary mask by instances_from_masks")
+    ap.add_argument("--from-simulator", action="store_true",
+                    help="train on RFISimulator samples with one instance per emitter and a class per family (event_instances)")
     a = ap.parse_args()
+    if a.from_masks and a.from_simulator:
+        ap.error("--from-masks and --from-simulator exclude each other")
     import torch
     from rfi_toolbox_amd.models import MaskRCNN
     torch.manual_seed(0)
-    det = MaskRCNN(2, 3, 16, 64, 128, seed=0).set_compute_dtype(a.dtype)
-    x, targets = batch(np.random.default_rng(1), a.images, 128)
-    step_targets = targets
+    if a.from_simulator:
+        from rfi_toolbox_amd.core import EVENT_CLASSES, RFISimulator, event_instances
+        from rfi_toolbox_amd.preprocessing import Normalizer
+        det = MaskRCNN(len(EVENT_CLASSES), 8, 16, 64, 128, seed=0).set_compute_dtype(a.dtype)
+        sim_batch = RFISimulator(128, 128, seed=1).generate_batch(a.images, out="nhwc")
+        x = Normalizer("robust_scale", scope="sample").fit_transform(sim_batch.data, out="nhwc", layout="nhwc")
+        step_targets = event_instances(sim_batch, min_side=2, max_instances=16)      # (min_side=2: no one-pixel-wide lines)
+        targets = step_targets.to_list()
+        print(f"emitters per sample: {step_targets.count_host.tolist()} of {step_targets.n_survivors_host.tolist()} two pixels wide or more; "
+              f"families: {sorted({EVENT_CLASSES[c] for t in targets for c in t['labels']})}")
+    else:
+        det = MaskRCNN(2, 3, 16, 64, 128, seed=0).set_compute_dtype(a.dtype)
+        x, targets = batch(np.random.default_rng(1), a.images, 128)
+        step_targets = targets
     if a.from_masks:
         from rfi_toolbox_amd.components import instances_from_masks
         step_targets = instances_from_masks(np.stack([t["masks"].any(0) for t in targets]))
@@ -64,6 +81,8 @@ def main():
             print(f"step {s:4d}  " + "  ".join(f"{k[5:] or 'total'} {v:.4f}" for k, v in l.items()), flush=True)
     print(f"{a.steps} steps in {time.time() - t0:.1f} s")
     det.score_thresh = 0.5
+    if a.from_simulator:
+        x = x.numpy()                                   # (predict takes host images)
     out = det.predict(x)
     for i, (o, t) in enumerate(zip(out, targets)):
         best = [max((iou(g, b) for b in o["boxes"]), default=0.0) for g in t["boxes"]]
