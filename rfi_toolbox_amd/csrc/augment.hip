@@ -16,24 +16,13 @@
 // the values); every other one is a bilinear gather in fp64 rounded once to float32, the mask a nearest-neighbour
 // gather, both with reflect-101 borders.  No atomics: the output is a function of the arguments alone.
 #include "kernels.hpp"
+#include "philox.hpp"
 
 namespace rfi {
 namespace {
 
 constexpr int kBlock = 256;
 
-struct U4 { unsigned x, y, z, w; };
-__host__ __device__ inline U4 philox4x32_10(U4 c, unsigned k0, unsigned k1) {
-    for (int i = 0; i < 10; ++i) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c.x;
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c.z;
-        const U4 n{(unsigned)(p1 >> 32) ^ c.y ^ k0, (unsigned)p1, (unsigned)(p0 >> 32) ^ c.w ^ k1, (unsigned)p0};
-        c = n;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
 
 // gates (hflip, vflip, rotate, ssr) and inv = [L | c - L (c + t)], L = F R(-a1) R(-a2) / s: the inverse of
 // M = SSR R(a1) Fv Fh about the centre c = ((w - 1) / 2, (h - 1) / 2).  Gated-off factors enter as cos 1, sin 0, s 1,
@@ -42,7 +31,7 @@ __host__ __device__ inline void augment_draw(const rfi_augment_config& cfg, uint
                                              double* inv) {
     double u[12];
     for (int k = 0; k < 3; ++k) {
-        const U4 r = philox4x32_10(U4{(unsigned)i, (unsigned)call, (unsigned)(call >> 32), (unsigned)k}, (unsigned)cfg.seed,
+        const U4 r = philox4x32_10<false>(U4{(unsigned)i, (unsigned)call, (unsigned)(call >> 32), (unsigned)k}, (unsigned)cfg.seed,
                                    (unsigned)(cfg.seed >> 32));
         u[4 * k + 0] = ((double)r.x + 0.5) * 2.3283064365386963e-10;
         u[4 * k + 1] = ((double)r.y + 0.5) * 2.3283064365386963e-10;

@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "bf16_mma.hpp"
 #include "planes.hpp"
 
 namespace rfi {
@@ -29,61 +30,6 @@ namespace rfi {
 void launch_conv_direct(rfi_ctx* ctx, const ConvArgs& a);
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-// 4 floats (one lane's k-quad of a fragment) -> 4 bf16, round-to-nearest-even (2 x v_cvt_pk_bf16_f32)
-__device__ __forceinline__ s16x4 pack_bf16(f32x4 x) {
-    const f32x2 lo = {x.x, x.y}, hi = {x.z, x.w};
-    u32x2 r;
-    r.x = __builtin_bit_cast(unsigned, __builtin_convertvector(lo, bf16x2));
-    r.y = __builtin_bit_cast(unsigned, __builtin_convertvector(hi, bf16x2));
-    return __builtin_bit_cast(s16x4, r);
-}
-
-// ---- "3 x bf16" float32 emulation.  A float32 value is the exact sum of three bf16 pieces (8 + 8 + 8
-// significand bits): h = bf16(v), m = bf16(v - h), l = bf16(v - h - m).  A product a*b is then the sum of nine
-// piece products, each exact in the float32 accumulator; the three smallest (m*l, l*m, l*l <= 2^-24 |a b|) are
-// dropped, i.e. an error of the size of ONE float32 rounding per product.  Six v_mfma_f32_32x32x16_bf16
-// (32 cycles each, K = 16) replace eight v_mfma_f32_32x32x2_f32 (64 cycles each): 2.7x the matrix-pipe
-// throughput at float32-level accuracy (tools/mfma_rate.hip: 142 vs 2425 TFLOP/s raw).
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-struct Split3 { bf16x8 h, m, l; };
-__device__ __forceinline__ unsigned cvt_pair(float a, float b) {
-    const f32x2 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ void split_pair(float a, float b, unsigned& h, unsigned& m, unsigned& l) {
-    h = cvt_pair(a, b);
-    const float ra = a - __builtin_bit_cast(float, h << 16), rb = b - __builtin_bit_cast(float, h & 0xffff0000u);
-    m = cvt_pair(ra, rb);
-    const float sa = ra - __builtin_bit_cast(float, m << 16), sb = rb - __builtin_bit_cast(float, m & 0xffff0000u);
-    l = cvt_pair(sa, sb);
-}
-__device__ __forceinline__ Split3 split3(f32x4 x0, f32x4 x1) {      // 8 consecutive k of one lane
-    unsigned h[4], m[4], l[4];
-    split_pair(x0.x, x0.y, h[0], m[0], l[0]);
-    split_pair(x0.z, x0.w, h[1], m[1], l[1]);
-    split_pair(x1.x, x1.y, h[2], m[2], l[2]);
-    split_pair(x1.z, x1.w, h[3], m[3], l[3]);
-    const u32x4 H = {h[0], h[1], h[2], h[3]}, M = {m[0], m[1], m[2], m[3]}, L = {l[0], l[1], l[2], l[3]};
-    return Split3{__builtin_bit_cast(bf16x8, H), __builtin_bit_cast(bf16x8, M), __builtin_bit_cast(bf16x8, L)};
-}
-__device__ __forceinline__ f32x16 mfma_3xbf16(const Split3& a, const Split3& b, f32x16 acc) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.l, b.h, acc, 0, 0, 0);      // small terms first
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.m, b.m, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.l, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.m, b.h, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.m, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.h, acc, 0, 0, 0);
-    return acc;
-}
 
 constexpr int KC = 16;    // channels per K-chunk
 constexpr int KCP = 20;   // padded LDS row (floats)
@@ -118,7 +64,7 @@ struct Cfg {
 // BF: bf16 compute mode -- the SAME fp32 tiles in HBM and LDS; each lane's k-quad of an operand fragment is
 // rounded to bf16 in registers and ONE v_mfma_f32_32x32x8_bf16 (fp32 accumulate) replaces the four
 // fp32 32x32x2 MFMAs of that quad (identical k-to-lane mapping: lane half lh holds k = 4 lh .. 4 lh + 3).
-// PREC: 0 float32 MFMA, 1 bf16 (above), 2 float32 emulated by 3 x bf16 (Split3 above)
+// PREC: 0 float32 MFMA, 1 bf16 (above), 2 float32 emulated by 3 x bf16 (bf16_mma.hpp)
 template <int R, int S, int TH, int TW, int BN, int WM, int WN, int PREC>
 __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvArgs a) {
     using C = Cfg<R, S, TH, TW, BN, WM, WN, PREC>;
@@ -347,22 +293,21 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(ConvArgs a) {
 #pragma unroll
             for (int tap = 0; tap < C::NTAP; ++tap) {
                 const int tr = tap / R, ts = tap % R;
-                Split3 bs[C::NTL];
+                bf16x8 bs[C::NTL][3];
 #pragma unroll
                 for (int nt = 0; nt < C::NTL; ++nt) {
                     const float* bp = s_w + b_base[nt] + tap * BN * WROW3;        // planes h | m | l, 8 floats apart
-                    bs[nt] = Split3{__builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(bp)),
-                                    __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(bp + 8)),
-                                    __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(bp + 16))};
+#pragma unroll
+                    for (int p = 0; p < 3; ++p) bs[nt][p] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(bp + 8 * p));
                 }
 #pragma unroll
                 for (int mt = 0; mt < C::MT; ++mt) {
                     const float* ap = s_halo + a_base[mt] + (tr * C::HW + ts) * C::HROW;   // planes h | m | l, 8 floats apart
-                    const Split3 as{__builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(ap)),
-                                    __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(ap + 8)),
-                                    __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(ap + 16))};
+                    bf16x8 as[3];
 #pragma unroll
-                    for (int nt = 0; nt < C::NTL; ++nt) acc[mt][nt] = mfma_3xbf16(as, bs[nt], acc[mt][nt]);
+                    for (int p = 0; p < 3; ++p) as[p] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(ap + 8 * p));
+#pragma unroll
+                    for (int nt = 0; nt < C::NTL; ++nt) acc[mt][nt] = mma<3>(as, bs[nt], acc[mt][nt]);
                 }
             }
         } else {
@@ -651,47 +596,35 @@ size_t weights_x3_floats(int taps, int Cout, int Cin) {
     return (size_t)taps * Cout * ((Cin + KC - 1) / KC) * WROW3;
 }
 namespace {
-// w [taps][Cout][Cin] float32 -> records [taps][Cout][chunk][h16 | m16 | l16] bf16 (zero beyond Cin)
+// w [taps][Cout][Cin] float32 -> records [taps][Cout][chunk][h16 | m16 | l16] bf16 (zero beyond Cin); item i: 4 channels
+__device__ __forceinline__ void weights_to_x3_item(const float* __restrict__ w, int Cin, int nchunks, float* __restrict__ out, int64_t i) {
+    const int q = (int)(i & 3);
+    const int64_t rc = i >> 2;
+    const int chunk = (int)(rc % nchunks);
+    const int64_t row = rc / nchunks;
+    const int c = chunk * KC + q * 4;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (c < Cin) v = *reinterpret_cast<const f32x4*>(w + row * Cin + c);      // Cin % 4 == 0
+    unsigned h0, m0, l0, h1, m1, l1;
+    split_pair(v.x, v.y, h0, m0, l0);
+    split_pair(v.z, v.w, h1, m1, l1);
+    float* rec = out + rc * WROW3 + q * 2;
+    *reinterpret_cast<u32x2*>(rec) = u32x2{h0, h1};
+    *reinterpret_cast<u32x2*>(rec + 8) = u32x2{m0, m1};
+    *reinterpret_cast<u32x2*>(rec + 16) = u32x2{l0, l1};
+}
 __global__ void weights_to_x3_kernel(const float* __restrict__ w, int64_t rows, int Cin, int nchunks,
                                      float* __restrict__ out) {
     const int64_t total = rows * nchunks * 4;                    // one thread per 4 channels
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int q = (int)(i & 3);
-        const int64_t rc = i >> 2;
-        const int chunk = (int)(rc % nchunks);
-        const int64_t row = rc / nchunks;
-        const int c = chunk * KC + q * 4;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (c < Cin) v = *reinterpret_cast<const f32x4*>(w + row * Cin + c);      // Cin % 4 == 0
-        unsigned h0, m0, l0, h1, m1, l1;
-        split_pair(v.x, v.y, h0, m0, l0);
-        split_pair(v.z, v.w, h1, m1, l1);
-        float* rec = out + rc * WROW3 + q * 2;
-        *reinterpret_cast<u32x2*>(rec) = u32x2{h0, h1};
-        *reinterpret_cast<u32x2*>(rec + 8) = u32x2{m0, m1};
-        *reinterpret_cast<u32x2*>(rec + 16) = u32x2{l0, l1};
-    }
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x)
+        weights_to_x3_item(w, Cin, nchunks, out, i);
 }
 // the same for MANY filter tensors in one launch (all layers, both layouts, once per optimiser step)
 __global__ void weights_to_x3_batched_kernel(const X3Desc* __restrict__ descs) {
     const X3Desc d = descs[blockIdx.y];
     const int64_t total = d.rows * d.nchunks * 4;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int q = (int)(i & 3);
-        const int64_t rc = i >> 2;
-        const int chunk = (int)(rc % d.nchunks);
-        const int64_t row = rc / d.nchunks;
-        const int c = chunk * KC + q * 4;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (c < d.Cin) v = *reinterpret_cast<const f32x4*>(d.src + row * d.Cin + c);
-        unsigned h0, m0, l0, h1, m1, l1;
-        split_pair(v.x, v.y, h0, m0, l0);
-        split_pair(v.z, v.w, h1, m1, l1);
-        float* rec = d.dst + rc * WROW3 + q * 2;
-        *reinterpret_cast<u32x2*>(rec) = u32x2{h0, h1};
-        *reinterpret_cast<u32x2*>(rec + 8) = u32x2{m0, m1};
-        *reinterpret_cast<u32x2*>(rec + 16) = u32x2{l0, l1};
-    }
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x)
+        weights_to_x3_item(d.src, d.Cin, d.nchunks, d.dst, i);
 }
 }  // namespace
 void launch_weights_to_x3_batched(rfi_ctx* ctx, const X3Desc* descs_dev, int n, double total_bytes) {

@@ -27,17 +27,11 @@
 #include <type_traits>
 #include <vector>
 
+#include "bf16_mma.hpp"
 #include "planes.hpp"
 
 namespace rfi {
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
 
 struct PConvDev {
     PConvArgs a;
@@ -79,18 +73,6 @@ struct PCfg {
     static_assert(HW < 4096 && HH < 4096, "halo coordinates are packed in 12 bits");
     static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 };
-
-template <int P>
-__device__ __forceinline__ f32x16 mma(const bf16x8 (&a)[P], const bf16x8 (&b)[P], f32x16 acc) {
-    if constexpr (P == 3) {            // pieces: [0] = h, [1] = m, [2] = l; small terms first
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], acc, 0, 0, 0);
-    }
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc, 0, 0, 0);
-}
 
 // Two workgroups per CU alternate between their DMA wait and their MFMA phase (staging is single-buffered; the
 // other workgroup's MFMAs, LDS reads and output stores fill the wait).  A workgroup walks its tiles in GROUPS of
@@ -329,10 +311,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void pconv_kernel(PConvDev d) {
                 }
                 if (FULL || ok) {
                     if constexpr (OM >= 1) {            // the tensor holds bf16 values (RNE; NaN stays NaN): v_cvt_pk_bf16_f32
-                        typedef float f32x2 __attribute__((ext_vector_type(2)));
-                        typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-                        const unsigned w0 = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{v[0], v[1]}, bf16x2));
-                        const unsigned w1 = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{v[2], v[3]}, bf16x2));
+                        const unsigned w0 = cvt_pair(v[0], v[1]), w1 = cvt_pair(v[2], v[3]);
                         v = f32x4{__builtin_bit_cast(float, w0 << 16), __builtin_bit_cast(float, w0 & 0xffff0000u),
                                   __builtin_bit_cast(float, w1 << 16), __builtin_bit_cast(float, w1 & 0xffff0000u)};
                         if constexpr (OM == 2) *reinterpret_cast<u32x2*>(a.y16 + off) = u32x2{w0, w1};
@@ -449,7 +428,6 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void pconv_kernel(PConvDev d) {
 #endif
     if constexpr (DB) {
         static_assert(P == 1, "double-buffered staging: bf16 flow");
-        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
         constexpr int NRD = MT + NTL;                       // fragment reads per tap
         const unsigned lds0 = (unsigned)reinterpret_cast<uintptr_t>(smem);      // (low half of a flat LDS address = LDS offset)
         unsigned a_addr[MT];

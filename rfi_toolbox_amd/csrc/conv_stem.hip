@@ -117,7 +117,7 @@ __global__ __launch_bounds__(256) void conv_stem_kernel(StemDev d) {
                     af[p] = __builtin_bit_cast(bf16x8, u32x4{a0.x, a0.y, a1.x, a1.y});
                 }
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt) acc[nt] = mma3(af, bfr[nt][s], acc[nt]);
+                for (int nt = 0; nt < NT; ++nt) acc[nt] = mma<3>(af, bfr[nt][s], acc[nt]);
             }
             // epilogue: C row = pixel (reg & 3) + 8 (reg >> 2) + 4 kh of the block, column = channel li
             const int oy = oy0 + row;

@@ -1,5 +1,5 @@
 // Wave-specialised 3x3 / stride-1 / pad-1 convolution on float32 NHWC tensors in the float32-by-3xbf16 arithmetic
-// (six v_mfma_f32_32x32x16_bf16 per 32x32x16 block product, small terms first: planes.hpp, conv_mfma.hip).
+// (six v_mfma_f32_32x32x16_bf16 per 32x32x16 block product, small terms first: planes.hpp, bf16_mma.hpp).
 //
 //   y[n,oy,ox,co] = bias[co] + sum_{tap=(r,s)} sum_ci T(X)[n, oy+r-1, ox+s-1, ci] * W[tap][co][ci]
 //
@@ -391,7 +391,7 @@ __global__ __launch_bounds__(512) void conv_ws_kernel(WsDev d) {
                         if (FIRST && tap == 0)
 #pragma unroll
                             for (int r = 0; r < 16; ++r) c[r] = 0.0f;
-                        if constexpr (P == 3) acc[mt][nt] = mma3(afr[tap & 1][mt], bfr[tap & 1][nt], c);
+                        if constexpr (P == 3) acc[mt][nt] = mma<3>(afr[tap & 1][mt], bfr[tap & 1][nt], c);
                         else acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[tap & 1][mt][0], bfr[tap & 1][nt][0], c, 0, 0, 0);
                     }
                 if constexpr (PEND && DEFER) {

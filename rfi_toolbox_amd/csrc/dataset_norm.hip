@@ -68,23 +68,6 @@ struct NsArgs {
     rfi_norm_stats* out;
 };
 
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ double wave_min(double v) {
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ u64 wave_usum(u64 v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // the `len` scalars from index g0 of the concatenation, lane l taking l, l + 64, ...; lanes past `len` get 0
 template <typename T>
 __device__ __forceinline__ void load_tile(const NsArgs& a, int64_t g0, int len, int lane, T (&x)[kUnroll]) {

@@ -14,6 +14,7 @@
 // keeps its elements of SMALLEST (r, i) -- a function of (seed, step, image, element) only, which the oracle evaluates with
 // the same generator (oracle/synth_ref.philox4x32_10).
 #include "kernels.hpp"
+#include "philox.hpp"
 #include "detect_sort.hpp"
 
 namespace rfi {
@@ -21,19 +22,6 @@ namespace {
 
 constexpr int kB = 256;
 
-struct U4 { unsigned x, y, z, w; };
-__device__ __forceinline__ U4 philox4x32_10(U4 c, unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        const u64 p0 = (u64)0xD2511F53u * c.x;
-        const u64 p1 = (u64)0xCD9E8D57u * c.z;
-        const U4 n{(unsigned)(p1 >> 32) ^ c.y ^ k0, (unsigned)p1, (unsigned)(p0 >> 32) ^ c.w ^ k1, (unsigned)p0};
-        c = n;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
 
 __device__ __forceinline__ int lower_bound(const u64* s, int n, u64 v) {      // first index with s[i] >= v
     int a = 0, b = n;

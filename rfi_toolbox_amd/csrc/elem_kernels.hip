@@ -17,6 +17,7 @@ constexpr int kBlock = 256;
 constexpr int kFinCh = 2;                    // finishing kernels: channels per block ...
 constexpr int kFinLanes = kBlock / kFinCh;   // ... x record lanes
 
+// (not select_common.hpp's xor butterfly: __shfl_down sums in another order, i.e. other last bits; lane 0 holds the result)
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);

@@ -81,20 +81,6 @@ __device__ __forceinline__ u64* hist_of(const FsArgs& a, int sel, int pass, int 
     return a.ghist + ((size_t)(sel * kMaxPass + pass) * kSlots + slot) * kBins;
 }
 
-// fixed-order wave reduction (xor butterfly) and block reduction through LDS: deterministic
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ u64 wave_usum(u64 v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // reduce this thread's partials over the workgroup and store them as slab[blockIdx.x]
 __device__ void store_slab(Slab* slab, double s0, double s1, double m0, double m1, u64 n0, u64 n1, u64 fl) {
     __shared__ Slab ws[kWaves];

@@ -220,7 +220,7 @@ __global__ __launch_bounds__(256 + 64 * PWV) void gemm_ws_kernel(GwDev d) {
                 if (FIRST)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) c[r] = 0.0f;
-                acc[nb] = mma3(af, bf[nb & 1], c);
+                acc[nb] = mma<3>(af, bf[nb & 1], c);
 #pragma unroll
                 for (int i = 0; i < 6; ++i) {            // the next block's three reads between this block's six MFMAs
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);

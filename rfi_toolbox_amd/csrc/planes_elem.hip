@@ -1,28 +1,12 @@
 // Producers of the plane format (planes.hpp): activation split (with the producing layer's BatchNorm-apply +
 // activation folded in), filter re-layout into MFMA B-operand order, and the inverse (planes -> float32).
 // All HBM-bound elementwise kernels: 16-byte loads and stores, grid-stride.
+#include "bf16_mma.hpp"
 #include "planes.hpp"
 
 namespace rfi {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned cvt_pair(float a, float b) {       // RNE, v_cvt_pk_bf16_f32
-    const f32x2 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-// v = h + m + l exactly (three RNE bf16 pieces); the same sequence the round-1 kernels ran at staging time
-__device__ __forceinline__ void split_pair(float a, float b, unsigned& h, unsigned& m, unsigned& l) {
-    h = cvt_pair(a, b);
-    const float ra = a - __builtin_bit_cast(float, h << 16), rb = b - __builtin_bit_cast(float, h & 0xffff0000u);
-    m = cvt_pair(ra, rb);
-    const float sa = ra - __builtin_bit_cast(float, m << 16), sb = rb - __builtin_bit_cast(float, m & 0xffff0000u);
-    l = cvt_pair(sa, sb);
-}
 // 8 floats -> P pieces of 8 bf16 (16 bytes each)
 template <int P>
 __device__ __forceinline__ void split8(const float (&v)[8], u32x4 (&out)[3]) {

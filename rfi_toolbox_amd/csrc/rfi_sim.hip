@@ -20,6 +20,7 @@
 // pixels each event ALONE flags from the event table, through the device functions the pixel kernel decides its mask
 // with -- one event is one instance of the detector's ground truth (include/rfi_hip.h, "per-emitter targets").
 #include "kernels.hpp"
+#include "philox.hpp"
 
 namespace rfi {
 namespace {
@@ -32,20 +33,6 @@ enum { S_HEADER = 0, S_BROAD = 1, S_NARROW = 2, S_BURST = 3, S_LINEAR = 4, S_QUA
        S_NOISE = 8, S_BROAD_PX = 9, S_NARROW_PT = 10, S_BURST_PT = 11, S_LINEAR_PT = 12, S_QUAD_PT = 13,
        S_CROSS = 14 };
 
-struct U4 { unsigned x, y, z, w; };
-
-__device__ __forceinline__ U4 philox4x32_10(U4 c, unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c.x;
-        const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c.z;
-        const U4 n{(unsigned)(p1 >> 32) ^ c.y ^ k0, (unsigned)p1, (unsigned)(p0 >> 32) ^ c.w ^ k1, (unsigned)p0};
-        c = n;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
 
 struct SimDev {
     unsigned k0, k1, first;          // key; global index of sample 0 (first + n <= 2^32)

@@ -1,5 +1,6 @@
 // Device helpers shared by the exact order-statistic kernels (flag_stats.hip, dataset_norm.hip, sumthreshold.hip,
-// casa_flaggers.hip): the order-preserving integer image of a float for radix selection, and |z| as NumPy computes it.
+// casa_flaggers.hip): the order-preserving integer image of a float for radix selection, |z| as NumPy computes it, and
+// the fixed-order wave reductions.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -37,6 +38,24 @@ __device__ __forceinline__ T cabs_np(T re, T im) {
     if (L == (T)0) return (T)0;
     const T r = S / L;
     return L * sqrt_rn(fma_rn(r, r, (T)1));
+}
+
+// wave reductions in a fixed order (xor butterfly; every lane gets the result): the statistics are reproducible bit for bit
+__device__ __forceinline__ double wave_sum(double v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ double wave_min(double v) {
+    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ u64 wave_usum(u64 v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
 }
 
 }  // namespace rfi

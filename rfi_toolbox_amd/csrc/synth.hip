@@ -14,26 +14,13 @@
 // HBM-bound: 16 B (complex128) or 8 B (complex64) + 1 B mask written per pixel, nothing read but the
 // event table (scalar loads, shared by all lanes).
 #include "kernels.hpp"
+#include "philox.hpp"
 
 namespace rfi {
 namespace {
 
 constexpr int kBlock = 256;
 
-struct U4 { unsigned x, y, z, w; };
-
-__device__ __forceinline__ U4 philox4x32_10(U4 c, unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c.x;
-        const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c.z;
-        const U4 n{(unsigned)(p1 >> 32) ^ c.y ^ k0, (unsigned)p1, (unsigned)(p0 >> 32) ^ c.w ^ k1, (unsigned)p0};
-        c = n;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
 // (0, 1] and [0, 1) uniforms from 32 random bits
 __device__ __forceinline__ double u01_open0(unsigned u) { return ((double)u + 1.0) * (1.0 / 4294967296.0); }
 __device__ __forceinline__ double u01(unsigned u) { return (double)u * (1.0 / 4294967296.0); }

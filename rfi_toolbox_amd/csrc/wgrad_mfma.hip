@@ -12,6 +12,7 @@
 // blocks of a BY x BX channel tile or, when that tile is a single block, the tile's pixels.
 #include <algorithm>
 
+#include "bf16_mma.hpp"
 #include "planes.hpp"
 
 namespace rfi {
@@ -25,51 +26,15 @@ void launch_wgrad_split(rfi_ctx* ctx, const WgradArgs& a);
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-// float32 emulated by three bf16 pieces (see conv_mfma.hip): h = bf16(v), m = bf16(v - h), l = bf16(v - h - m)
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-struct Split3 { bf16x8 h, m, l; };
-__device__ __forceinline__ unsigned cvt_pair(float a, float b) {
-    const f32x2 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ void split_pair(float a, float b, unsigned& h, unsigned& m, unsigned& l) {
-    h = cvt_pair(a, b);
-    const float ra = a - __builtin_bit_cast(float, h << 16), rb = b - __builtin_bit_cast(float, h & 0xffff0000u);
-    m = cvt_pair(ra, rb);
-    const float sa = ra - __builtin_bit_cast(float, m << 16), sb = rb - __builtin_bit_cast(float, m & 0xffff0000u);
-    l = cvt_pair(sa, sb);
-}
-__device__ __forceinline__ Split3 split8(const float (&v)[8]) {
+// 8 floats -> the three bf16 pieces of the 3 x bf16 arithmetic (bf16_mma.hpp): [0] = h, [1] = m, [2] = l
+__device__ __forceinline__ void split8(const float (&v)[8], bf16x8 (&out)[3]) {
     unsigned h[4], m[4], l[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) split_pair(v[2 * i], v[2 * i + 1], h[i], m[i], l[i]);
     const u32x4 H = {h[0], h[1], h[2], h[3]}, M = {m[0], m[1], m[2], m[3]}, L = {l[0], l[1], l[2], l[3]};
-    return Split3{__builtin_bit_cast(bf16x8, H), __builtin_bit_cast(bf16x8, M), __builtin_bit_cast(bf16x8, L)};
-}
-__device__ __forceinline__ f32x16 mfma_3xbf16(const Split3& a, const Split3& b, f32x16 acc) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.l, b.h, acc, 0, 0, 0);      // small terms first
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.m, b.m, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.l, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.m, b.h, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.m, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h, b.h, acc, 0, 0, 0);
-    return acc;
-}
-
-__device__ __forceinline__ s16x4 pack_bf16(float a, float b, float c, float d) {   // RNE, 2 x v_cvt_pk_bf16_f32
-    const f32x2 lo = {a, b}, hi = {c, d};
-    u32x2 r;
-    r.x = __builtin_bit_cast(unsigned, __builtin_convertvector(lo, bf16x2));
-    r.y = __builtin_bit_cast(unsigned, __builtin_convertvector(hi, bf16x2));
-    return __builtin_bit_cast(s16x4, r);
+    out[0] = __builtin_bit_cast(bf16x8, H);
+    out[1] = __builtin_bit_cast(bf16x8, M);
+    out[2] = __builtin_bit_cast(bf16x8, L);
 }
 
 template <int R, int S, int BY, int BX, int TH, int TW>
@@ -242,14 +207,16 @@ __global__ __launch_bounds__(256) void wgrad_igemm_kernel(WgradDev d) {
                 float v[8];
 #pragma unroll
                 for (int t = 0; t < 8; ++t) v[t] = yr[(g * 16 + t) * C::BYP];
-                const Split3 a3 = split8(v);
+                bf16x8 a3[3], b3[3];
+                split8(v, a3);
                 const float* xr = xr0 + (g * 2 * S) * C::HW * C::BXP;
 #pragma unroll
                 for (int tap = 0; tap < C::NTAP; ++tap) {
                     const float* xp = xr + ((tap / R) * C::HW + (tap % R)) * C::BXP;
 #pragma unroll
                     for (int t = 0; t < 8; ++t) v[t] = xp[t * S * C::BXP];
-                    acc[tap] = mfma_3xbf16(a3, split8(v), acc[tap]);
+                    split8(v, b3);
+                    acc[tap] = mma<3>(a3, b3, acc[tap]);
                 }
             }
             __syncthreads();

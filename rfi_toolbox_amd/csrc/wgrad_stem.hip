@@ -21,9 +21,6 @@ namespace rfi {
 namespace {
 
 using namespace ws;
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
 struct WStemDev {
     const float* x;                   // [N][H][W][4]
     const float* dy;                  // [N][H][W][Cy]
@@ -34,12 +31,6 @@ struct WStemDev {
 constexpr int TH = 8, TW = 16, BM = TH * TW, HH = TH + 2, HW = TW + 2, HP = HH * HW;
 constexpr int ROW = 192;              // bytes per pixel of a 32-channel dA block image: 3 planes x 32 channels x 2 B
 constexpr int XPLANE = HP * 8;        // bytes of one X plane image: [halo pixel][4 bf16]
-
-__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* p0, const unsigned char* p1) {
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p0);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p1);
-    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
 
 template <int NT>
 __global__ __launch_bounds__(256) void wgrad_stem_kernel(WStemDev d) {
@@ -120,7 +111,7 @@ __global__ __launch_bounds__(256) void wgrad_stem_kernel(WStemDev d) {
 #pragma unroll
                 for (int p = 0; p < 3; ++p) af[p] = tr_frag(yimg + t0 * ROW + p * 64, yimg + t1 * ROW + p * 64);
 #pragma unroll
-                for (int cb = 0; cb < 2; ++cb) acc[nt][cb] = mma3(af, bf[cb], acc[nt][cb]);
+                for (int cb = 0; cb < 2; ++cb) acc[nt][cb] = mma<3>(af, bf[cb], acc[nt][cb]);
             }
         }
     }

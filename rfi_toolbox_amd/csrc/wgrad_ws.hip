@@ -28,9 +28,6 @@ namespace rfi {
 namespace {
 
 using namespace ws;
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
 struct WWsDev {
     WgradArgs a;
     int nsplit;
@@ -65,19 +62,6 @@ struct WWCfg {
     static_assert(ST == 1 || (ST == 2 && R == 2), "stride 2: the transposed conv's 2x2 taps");
     static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 };
-
-template <int P>
-__device__ __forceinline__ f32x16 mma(const bf16x8 (&a)[P], const bf16x8 (&b)[P], f32x16 acc) {
-    if constexpr (P == 3) return mma3(a, b, acc);
-    else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc, 0, 0, 0);
-}
-// one operand fragment: this lane's 8 pixels (k = 8 h + 0..7) of its channel, from two transposing reads of 4 pixel rows
-// each.  `p0` / `p1`: byte addresses of THIS lane's row of the two 4x16 blocks
-__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* p0, const unsigned char* p1) {
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p0);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p1);
-    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
 
 // barrier behind this wave's LDS writes (the producers have left by then: a terminated wave is not waited for)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
