@@ -317,7 +317,9 @@ int rfi_preprocess_gather(rfi_ctx* ctx, const void* planes, int planes_mem, int 
  *      (0 none, 1 SQRT, 2 LOG10; infinities <- MAD of the patch's finite values, :672-706), optional second
  *      normalise, then the 3-channel extraction of :608-644 + ImageNet normalisation -> out_nhwc; when
  *      flags_out != NULL also the MAD flags of the PROCESSED patches (:708-745, |x - med| > sigma * MAD).
- *      rfi_mad_flags: the same flags for any input dtype (complex: of |z|), nothing else. ---- */
+ *      rfi_mad_flags: the same flags for any input dtype (complex: of |z|), nothing else; complex64 / float32 input in
+ *      float32 arithmetic like rfi_preprocess_real, |z| of a complex64 rounded once as the C library's hypotf is.  Any n: stacks of
+ *      more than 65,535 patches are walked in chunks (here and in rfi_preprocess_patches / _gather). ---- */
 int rfi_preprocess_real(rfi_ctx* ctx, const void* patches, int patches_mem, int dtype, int n, int ps_h,
                         int ps_w, int stretch, int normalize_before, int normalize_after, double flag_sigma,
                         float* out_nhwc, int out_mem, uint8_t* flags_out, int flags_mem);
@@ -891,6 +893,14 @@ size_t rfi_op_rpn_loss_ws_bytes(void);
  * roi_align_ml / _backward: RoIAlign where RoI r uses map level[r] of four ([n][h0 >> k][w0 >> k][c], scale scale0 / 2^k; host
  *   arrays of device pointers); the row count is read from count_dev, max_rois sizes the launch; backward ADDS into dmaps.
  * readback_begin / _end: a copy of <= 2048 bytes to the host that waits for the work enqueued BEFORE begin only. */
+/* ---- per-patch order statistics on their own (csrc/order_stats.hip; rfi_preprocess_real and rfi_mad_flags build on them), for
+ *      the kernel-level parity tests.  v: n patches of `per` float64 values; device pointers throughout.
+ *      median[i] = the median (mean of the two middle values for an even count) of patch i's participating values: every
+ *      value that is not NaN (np.nanmedian) or, with finite_only, not NaN and not +-inf; absdev != 0: of |v - centre[i]|
+ *      instead.  NaN when nothing participates.  count (may be NULL): how many values took part.  f32 != 0: the doubles hold
+ *      float32 values and every arithmetic result is rounded to float32 (NumPy's float32 arithmetic on a float32 array). */
+int rfi_op_patch_median(rfi_ctx* ctx, const double* v, int n, int per, int absdev, const double* centre, int finite_only, int f32,
+                        double* median, int32_t* count);
 int rfi_op_segsort_u64(rfi_ctx* ctx, uint64_t* keys, int n_segs, int stride);
 int rfi_op_sample_keys(rfi_ctx* ctx, const int8_t* labels, int images, int n, const int32_t* count, uint64_t seed, uint32_t step,
                        uint32_t stream0, uint64_t* keys, int stride);

@@ -100,6 +100,27 @@ def channels_real(x):
     return np.stack([ch0, ch1, np.zeros_like(log_amp)], axis=-1)
 
 
+def channels(patches):
+    """(N,H,W) patches of any of the four input dtypes -> (N,H,W,3) float64 channels, the math in float64."""
+    p = np.asarray(patches)
+    return channels_complex(p.astype(np.complex128)) if np.iscomplexobj(p) else channels_real(p.astype(np.float64))
+
+
+def channels_f32(patches):
+    """The float32 restatement: the very expressions of channels_complex / channels_real on a complex64 / float32 stack,
+    where NumPy keeps every intermediate in float32 (Python-scalar constants do not widen an array)."""
+    p = np.asarray(patches)
+    assert p.dtype in (np.complex64, np.float32), p.dtype
+    ch = channels_complex(p) if np.iscomplexobj(p) else channels_real(p)
+    assert ch.dtype == np.float32, ch.dtype
+    return ch
+
+
+def images_of(ch):
+    """channels -> what create_dataset stores: the float32 cast, then the ImageNet normalisation in float32."""
+    return ((ch.astype(np.float32) - IMAGENET_MEAN) / IMAGENET_STD).astype(np.float32)
+
+
 def median_normalise(stack):
     med = np.nanmedian(stack.reshape(len(stack), -1), axis=1)
     scale = np.where(med > 0, med, 1.0)
@@ -183,5 +204,4 @@ def create_dataset(data, flags=None, patch_size=128, stretch_kind=None, flag_sig
         patches, pflags = patches[:num_patches], pflags[:num_patches]
 
     ch = channels_complex(patches) if np.iscomplexobj(patches) else channels_real(patches)
-    images = (ch.astype(np.float32) - IMAGENET_MEAN) / IMAGENET_STD
-    return images.astype(np.float32), np.asarray(pflags).astype(np.uint8)
+    return images_of(ch), np.asarray(pflags).astype(np.uint8)

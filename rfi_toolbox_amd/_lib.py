@@ -183,6 +183,7 @@ _PROTOS = {
     "rfi_op_rpn_loss": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
     "rfi_op_fastrcnn_loss": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _f, _vp, _vp, _vp]),
     "rfi_op_anchor_match_batched": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i, _i, _vp, _f, _f, _i, _vp, _vp, _vp, _vp]),
+    "rfi_op_patch_median": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
     "rfi_op_segsort_u64": (_i, [_vp, _vp, _i, _i]),
     "rfi_op_sample_keys": (_i, [_vp, _vp, _i, _i, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _i]),
     "rfi_op_rpn_sample_apply": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),

@@ -1079,9 +1079,11 @@ int rfi_mad_flags(rfi_ctx* ctx, const void* patches, int patches_mem, int dtype,
         double* w = sc.temp<double>(px);
         double* stat = sc.temp<double>((size_t)n * 2);
         uint8_t* dfl = sc.out(flags_out, flags_mem, px);
+        // complex64 / float32 input: NumPy keeps |z| and every step after it in float32 (rfi_preprocess_real's rule)
+        const bool f32 = dtype == RFI_C64 || dtype == RFI_F32;
         launch_to_abs_f64(ctx, in, dtype, (int64_t)px, w);
-        median_and_mad(ctx, w, n, per, false, stat, stat + n, nullptr);
-        launch_mad_flags(ctx, w, n, per, stat, stat + n, flag_sigma, dfl);
+        median_and_mad(ctx, w, n, per, false, stat, stat + n, nullptr, f32);
+        launch_mad_flags(ctx, w, n, per, stat, stat + n, flag_sigma, dfl, f32);
         sc.finish();
     });
 }

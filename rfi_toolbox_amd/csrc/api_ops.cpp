@@ -786,5 +786,17 @@ int rfi_op_bn_relu_backward(rfi_ctx* ctx, const float* y, int64_t m, int c, cons
                             ws, dbias);
     });
 }
+// ---- per-patch order statistics (order_stats.hip) on their own: what rfi_preprocess_real / rfi_mad_flags build on
+int rfi_op_patch_median(rfi_ctx* ctx, const double* v, int n, int per, int absdev, const double* centre, int finite_only, int f32,
+                        double* median, int32_t* count) {
+    return guarded([&] {
+        RFI_REQUIRE(n >= 0 && per >= 1, "patch_median: n >= 0 patches of per >= 1 values");
+        if (n == 0) return;
+        RFI_REQUIRE(v && median, "patch_median: null tensor");
+        RFI_REQUIRE(!absdev || centre, "patch_median: absolute deviations need the per-patch centres");
+        ctx->activate();
+        launch_patch_median(ctx, v, n, per, absdev != 0, absdev ? centre : nullptr, finite_only != 0, median, count, f32 != 0);
+    });
+}
 
 }  // extern "C"

@@ -290,6 +290,18 @@ struct AdamArgs {
 void launch_adam(rfi_ctx* ctx, const AdamArgs& a);
 
 // ---------------------------------------------------------------- preprocessing / metrics
+// The per-patch kernels carry the patch index in gridDim.y, which stops at 65,535: their launchers walk longer stacks in
+// chunks of this many patches, every per-patch pointer offset by the chunk's first patch.
+constexpr int kMaxGridY = 65535;
+#if defined(__HIPCC__)
+// |re + i im| of a complex64 as NumPy has it (the C library's hypotf): the root of the exact double sum of squares, rounded to
+// float32 once; |x| exactly when the other component is 0.  The device's own hypotf ends in the hardware's approximate square
+// root and can be an ulp off even there, which moves a median: the order statistics (to_abs_f64) use this one.  An infinite component gives infinity beside a NaN one.
+__device__ __forceinline__ float abs_c64(float re, float im) {
+    if (isinf(re) || isinf(im)) return INFINITY;
+    return (float)sqrt((double)re * (double)re + (double)im * (double)im);
+}
+#endif
 void launch_preprocess(rfi_ctx* ctx, const void* patches, int dtype, int n, int ph, int pw,
                        float* minmax_ws, float* out_nhwc, const rfi_patch_src* table_dev = nullptr, int C = 0,
                        int T = 0);

@@ -7,6 +7,8 @@
 // order-preserving 64-bit image of the doubles: 8 passes of 8 bits, a 256-bin LDS histogram per pass
 // over the elements that still match the prefix.  The patch (128 KiB at 128 x 128) stays in L2.
 // Everything here is byte-moving / integer work bound by L2 bandwidth; no MFMA.
+#include <algorithm>
+
 #include "kernels.hpp"
 
 namespace rfi {
@@ -103,7 +105,8 @@ __global__ void patch_median_kernel(const double* __restrict__ v, int per, int a
     }
     const double a = os_select(w, per, (n - 1) / 2, hist, &s_pref, &s_rank);
     const double b = (n & 1u) ? a : os_select(w, per, n / 2, hist, &s_pref, &s_rank);
-    if (threadIdx.x == 0) out[patch] = (n & 1u) ? a : (f32 ? r32(a + b) : (a + b)) / 2.0;     // np.mean of the two middle values
+    // np.mean of the two middle values; float32: the sum and the half are each rounded (the half of a subnormal is not exact)
+    if (threadIdx.x == 0) out[patch] = (n & 1u) ? a : (f32 ? r32(r32(a + b) / 2.0) : (a + b) / 2.0);
 }
 
 // v /= (med > 0 ? med : 1)   (_normalize, :646-670)
@@ -151,7 +154,7 @@ __global__ void to_abs_f64_kernel(const void* __restrict__ src, int dtype, int64
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         double r;
         if (dtype == RFI_C128) r = hypot(reinterpret_cast<const double*>(src)[2 * i], reinterpret_cast<const double*>(src)[2 * i + 1]);
-        else if (dtype == RFI_C64) r = (double)hypotf(reinterpret_cast<const float*>(src)[2 * i], reinterpret_cast<const float*>(src)[2 * i + 1]);
+        else if (dtype == RFI_C64) r = (double)abs_c64(reinterpret_cast<const float*>(src)[2 * i], reinterpret_cast<const float*>(src)[2 * i + 1]);
         else if (dtype == RFI_F64) r = reinterpret_cast<const double*>(src)[i];
         else r = (double)reinterpret_cast<const float*>(src)[i];
         dst[i] = r;
@@ -179,8 +182,11 @@ void launch_patch_median(rfi_ctx* ctx, const double* v, int n, int per, bool abs
 }
 void launch_scale_by_median(rfi_ctx* ctx, double* v, int n, int per, const double* med, bool f32) {
     ProfScope ps(ctx, FAM_PREPROCESS, 0, (double)n * per * 16);
-    hipLaunchKernelGGL(scale_by_median_kernel, dim3(grid1(per), n), dim3(kBlock), 0, ctx->stream, v, per, med, f32 ? 1 : 0);
-    check_launch("scale_by_median");
+    for (int n0 = 0; n0 < n; n0 += kMaxGridY) {
+        hipLaunchKernelGGL(scale_by_median_kernel, dim3(grid1(per), std::min(n - n0, kMaxGridY)), dim3(kBlock), 0, ctx->stream,
+                           v + (size_t)n0 * per, per, med + n0, f32 ? 1 : 0);
+        check_launch("scale_by_median");
+    }
 }
 void launch_stretch(rfi_ctx* ctx, double* v, int64_t total, int kind, bool f32) {
     ProfScope ps(ctx, FAM_PREPROCESS, 0, (double)total * 16);
@@ -189,15 +195,20 @@ void launch_stretch(rfi_ctx* ctx, double* v, int64_t total, int kind, bool f32) 
 }
 void launch_replace_inf(rfi_ctx* ctx, double* v, int n, int per, const double* mad, const int* nfinite) {
     ProfScope ps(ctx, FAM_PREPROCESS, 0, (double)n * per * 8);
-    hipLaunchKernelGGL(replace_inf_kernel, dim3(grid1(per), n), dim3(kBlock), 0, ctx->stream, v, per, mad, nfinite);
-    check_launch("replace_inf");
+    for (int n0 = 0; n0 < n; n0 += kMaxGridY) {
+        hipLaunchKernelGGL(replace_inf_kernel, dim3(grid1(per), std::min(n - n0, kMaxGridY)), dim3(kBlock), 0, ctx->stream,
+                           v + (size_t)n0 * per, per, mad + n0, nfinite + n0);
+        check_launch("replace_inf");
+    }
 }
 void launch_mad_flags(rfi_ctx* ctx, const double* v, int n, int per, const double* med, const double* mad,
                       double sigma, uint8_t* flags, bool f32) {
     ProfScope ps(ctx, FAM_PREPROCESS, 0, (double)n * per * 9);
-    hipLaunchKernelGGL(mad_flags_kernel, dim3(grid1(per), n), dim3(kBlock), 0, ctx->stream, v, per, med, mad, sigma,
-                       flags, f32 ? 1 : 0);
-    check_launch("mad_flags");
+    for (int n0 = 0; n0 < n; n0 += kMaxGridY) {
+        hipLaunchKernelGGL(mad_flags_kernel, dim3(grid1(per), std::min(n - n0, kMaxGridY)), dim3(kBlock), 0, ctx->stream,
+                           v + (size_t)n0 * per, per, med + n0, mad + n0, sigma, flags + (size_t)n0 * per, f32 ? 1 : 0);
+        check_launch("mad_flags");
+    }
 }
 void launch_to_abs_f64(rfi_ctx* ctx, const void* src, int dtype, int64_t total, double* dst) {
     ProfScope ps(ctx, FAM_PREPROCESS, 0, (double)total * 24);

@@ -3,6 +3,7 @@
 // [gradient magnitude of log-amplitude (per-patch min-max), log-amplitude, phase] -> float32 ->
 // ImageNet normalisation, written NHWC.  Math in fp64 for 64-bit inputs exactly as NumPy does it,
 // rounded to fp32 where the reference casts (.astype(np.float32), :376) and normalised in fp32 (:783).
+// 32-bit inputs: fp32 math, but for real input the log-amplitude is formed in fp64 (see pass 1).
 // Also the confusion counts of evaluation/metrics.py and the sigmoid threshold of evaluate_model.py.
 // Algorithmic traffic 16 B in + 12 B out (+1 B label on the host side) per pixel for complex128;
 // the per-patch min-max forces a second, 24 B/pixel pass over the output.
@@ -77,6 +78,13 @@ __device__ __forceinline__ double decd(unsigned long long u) {
 // per-patch extrema to mm (ordered-int atomics).  Real input: raw log-amp goes to channel 1's slot
 // and its extrema to mm as well.  Pass 2 rescales the slots with the extrema.  T = double for
 // 64-bit inputs (NumPy's precision), float for 32-bit inputs.
+// Real input, whose channel 1 is min-maxed per patch: the log-amp is formed in double whatever the input's
+// width, and what a float32 holds of it is la - la0, la0 = the log-amp of the patch's first pixel (0 when
+// that is not finite), which every block computes for itself.  |la - la0| <= the patch's span, so the
+// rounding moves the channel by <= 2^-24 whatever the contrast, where la itself would move it by
+// 2^-24 |la| / span (the reference min-maxes in the input's precision and casts afterwards).  That is
+// channel 1's slot, and for float32 input the LDS row as well (T = float), so its gradient and extrema are
+// those of la - la0.  Complex input (channel 1 has a fixed range) keeps T's own log-amp.
 
 template <typename T> struct LogAmp;
 template <> struct LogAmp<double> { static __device__ double f(double a) { return log10(a + 1e-10); } };
@@ -93,6 +101,15 @@ __global__ void prep_pass1_kernel(const void* __restrict__ src, int dtype, int p
     const bool is_complex = dtype == RFI_C128 || dtype == RFI_C64;
     rfi_patch_src ent{};
     if constexpr (GATHER) ent = gm.table[patch];
+    constexpr bool kWide = sizeof(T) == 8;
+    double la0 = 0.0;
+    if (!is_complex) {
+        T unused;
+        int64_t s0 = base;
+        if constexpr (GATHER) s0 = gather_index(gm, ent, 0, 0);
+        la0 = log10((double)load_amp<T>(src, dtype, s0, &unused) + 1e-10);
+        if (!isfinite(la0)) la0 = 0.0;
+    }
     // log-amp of [p0 - pw, p0 + NPB) ∩ [0, npix); channels 1/2 of the block's own pixels
     for (int k = threadIdx.x; k < pw + NPB; k += blockDim.x) {
         const int p = p0 - pw + k;
@@ -100,7 +117,16 @@ __global__ void prep_pass1_kernel(const void* __restrict__ src, int dtype, int p
         T phs;
         int64_t si = base + p;
         if constexpr (GATHER) si = gather_index(gm, ent, p / pw, p % pw);
-        const T la = LogAmp<T>::f(load_amp<T>(src, dtype, si, &phs));
+        const T amp = load_amp<T>(src, dtype, si, &phs);
+        T la;
+        float rel = 0.0f;                                           // real input: la - la0
+        if (is_complex) {
+            la = LogAmp<T>::f(amp);
+        } else {
+            const double lad = log10((double)amp + 1e-10);
+            rel = (float)(lad - la0);
+            la = kWide ? (T)lad : (T)rel;
+        }
         s_la[k] = la;
         if (p >= p0) {
             float* o = out + (base + p) * 3;
@@ -110,7 +136,7 @@ __global__ void prep_pass1_kernel(const void* __restrict__ src, int dtype, int p
                 o[1] = ((float)v - 0.456f) / 0.224f;
                 o[2] = ((float)((phs + (T)3.141592653589793) / (T)(2.0 * 3.141592653589793)) - 0.406f) / 0.225f;
             } else {
-                o[1] = (float)la;                                   // rescaled by pass 2
+                o[1] = rel;                                         // rescaled by pass 2
                 o[2] = (0.0f - 0.406f) / 0.225f;
             }
         }
@@ -127,7 +153,8 @@ __global__ void prep_pass1_kernel(const void* __restrict__ src, int dtype, int p
         const T g = sqrt(d0 * d0 + d1 * d1);
         out[(base + p) * 3] = (float)g;                             // rescaled by pass 2
         if (!isnan(g)) { gmin = g < gmin ? g : gmin; gmax = g > gmax ? g : gmax; }
-        if (!isnan(la)) { lmin = la < lmin ? la : lmin; lmax = la > lmax ? la : lmax; }
+        const T lr = kWide ? la - (T)la0 : la;
+        if (!isnan(lr)) { lmin = lr < lmin ? lr : lmin; lmax = lr > lmax ? lr : lmax; }
     }
     double e[4] = {(double)gmin, (double)gmax, (double)lmin, (double)lmax};
 #pragma unroll
@@ -243,6 +270,14 @@ void launch_preprocess(rfi_ctx* ctx, const void* patches, int dtype, int n, int 
     const bool wide = dtype == RFI_C128 || dtype == RFI_F64;
     const bool real_input = dtype == RFI_F64 || dtype == RFI_F32;
     unsigned long long* mm = reinterpret_cast<unsigned long long*>(minmax_ws);
+    if (n > kMaxGridY) {                      // chunks of the stack; the gather form reads the waterfall through its table
+        for (int n0 = 0; n0 < n; n0 += kMaxGridY) {
+            const char* src = reinterpret_cast<const char*>(patches) + (table_dev ? (size_t)0 : (size_t)n0 * per * (size_t)in_b);
+            launch_preprocess(ctx, src, dtype, std::min(n - n0, kMaxGridY), ph, pw, reinterpret_cast<float*>(mm + (size_t)n0 * 4),
+                              out_nhwc + (size_t)n0 * per * 3, table_dev ? table_dev + n0 : nullptr, C, T);
+        }
+        return;
+    }
     {
         ProfScope ps(ctx, FAM_PREPROCESS);
         hipLaunchKernelGGL(prep_init_mm64_kernel, dim3((int)cdiv(n, 256)), dim3(256), 0, ctx->stream, mm, n);
@@ -291,18 +326,22 @@ void launch_gather_labels(rfi_ctx* ctx, const uint8_t* flags, const rfi_patch_sr
                           int ps, uint8_t* out) {
     ProfScope ps_(ctx, FAM_PREPROCESS, 0, (double)n * ps * ps * 2);
     int bx = (int)cdiv((int64_t)ps * ps, kBlock * 4);
-    hipLaunchKernelGGL(gather_labels_kernel, dim3(bx, n), dim3(kBlock), 0, ctx->stream, flags, GatherMap{table_dev, C, T},
-                       ps, out);
-    check_launch("gather_labels");
+    for (int n0 = 0; n0 < n; n0 += kMaxGridY) {
+        hipLaunchKernelGGL(gather_labels_kernel, dim3(bx, std::min(n - n0, kMaxGridY)), dim3(kBlock), 0, ctx->stream, flags,
+                           GatherMap{table_dev + n0, C, T}, ps, out + (size_t)n0 * ps * ps);
+        check_launch("gather_labels");
+    }
 }
 void launch_patch_any_flag(rfi_ctx* ctx, const uint8_t* flags, const rfi_patch_src* table_dev, int C, int T, int n,
                            int ps, unsigned* any_out) {
     ProfScope ps_(ctx, FAM_PREPROCESS, 0, (double)n * ps * ps);
     RFI_CHECK_HIP(hipMemsetAsync(any_out, 0, (size_t)n * sizeof(unsigned), ctx->stream));
     int bx = (int)cdiv((int64_t)ps * ps, kBlock * 4);
-    hipLaunchKernelGGL(patch_any_flag_kernel, dim3(bx, n), dim3(kBlock), 0, ctx->stream, flags,
-                       GatherMap{table_dev, C, T}, ps, any_out);
-    check_launch("patch_any_flag");
+    for (int n0 = 0; n0 < n; n0 += kMaxGridY) {
+        hipLaunchKernelGGL(patch_any_flag_kernel, dim3(bx, std::min(n - n0, kMaxGridY)), dim3(kBlock), 0, ctx->stream, flags,
+                           GatherMap{table_dev + n0, C, T}, ps, any_out + n0);
+        check_launch("patch_any_flag");
+    }
 }
 
 void launch_confusion(rfi_ctx* ctx, const void* pred, int pred_dtype, const void* truth,

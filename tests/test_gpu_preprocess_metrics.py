@@ -72,8 +72,12 @@ def test_edge_patches_and_dtypes(golden_dir):
         np.testing.assert_allclose(got, (g[want].astype(np.float32) - mean) / std, rtol=0, atol=2e-6)
     z64 = g["d_z"].astype(np.complex64)                      # complex64 / float32 inputs: fp32 math
     got = p._channels_on_device(z64[None])[0]
-    want = preprocess_ref.channels_complex(z64.astype(np.complex128)[None])[0]
-    np.testing.assert_allclose(got, (want.astype(np.float32) - mean) / std, rtol=0, atol=5e-4)
+    want = preprocess_ref.images_of(preprocess_ref.channels(z64[None]))[0]
+    err_ref = np.abs(preprocess_ref.images_of(preprocess_ref.channels_f32(z64[None]))[0].astype(np.float64) - want).max(axis=(0, 1))
+    err = np.abs(got.astype(np.float64) - want).max(axis=(0, 1))
+    # what float32 arithmetic costs NumPy itself on this patch, times 4 for log10f / atan2f / hypotf, per channel; over the
+    # complex64 cases of test_gpu_preprocess_kernels.py an MI355X gave err_ref <= 9.5e-7 and a device error <= 1.2e-6
+    assert (err <= np.maximum(4.0 * err_ref, 2e-6)).all(), (err, err_ref)
     with pytest.raises(ValueError):
         Preprocessor(np.zeros((4, 4)))
     with pytest.raises(ValueError):
