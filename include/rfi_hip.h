@@ -787,6 +787,54 @@ int rfi_op_instance_masks(rfi_ctx* ctx, const int32_t* labels, int n, int h, int
                           const int32_t* base, int max_instances, uint8_t* masks);
 int rfi_op_copy_rows(rfi_ctx* ctx, const void* src, size_t src_pitch, void* dst, size_t dst_pitch, size_t width_bytes, size_t rows);
 
+/* ---- instance matching: scoring a detector's output against per-instance ground truth (csrc/instance_match.hip;
+ *      rfi_toolbox_amd/evaluation/detection.py).  Not in the reference; tests/instance_match_ref.py restates every rule in NumPy
+ *      and the results are equal bit for bit: integers, and float32 / float64 in the operation order pinned here.
+ *
+ *      An image i has det_count[i] detections in slots 0 .. D - 1 and gt_count[i] ground truths in slots 0 .. G - 1
+ *      (1 <= D, G <= 256, 1 <= n <= 65535; counts are cut to 0 .. D and 0 .. G).  Every output entry whose detection slot is
+ *      >= det_count[i] or whose ground-truth slot is >= gt_count[i] is 0 (IoU, intersection) or -1 (matches), and no kernel reads
+ *      a mask, box, score or label behind a count: those slots may hold anything.
+ *
+ *      pack_masks: masks uint8 [m][H][W], any non-zero byte foreground; H, W >= 1, H W <= 2^24, 1 <= m < 2^31; no alignment is
+ *      asked of `masks`.  With Wc = ceil(W / 64): bits uint64 [m][H][Wc], pixel (y, x) is bit x & 63 of word [y][x >> 6], the
+ *      bits of a row's last word beyond W are zero; area int32 [m] = the foreground pixels; extent int32 [m][4] = (first row,
+ *      first word column, last row + 1, last word column + 1) over the non-zero words, (0, 0, 0, 0) for an empty mask.
+ *
+ *      mask_iou: each side is (bits, area, extent) over `planes` packed planes plus count [n] and base [n]; slot s of image i is
+ *      plane base[i] + s (detections: base[i] = i D; targets: the exclusive prefix sum of count).  A plane index outside
+ *      0 .. planes - 1 counts as an empty mask of area 0; extents are cut to the plane.  inter int32 [n][D][G] = sum of
+ *      popcount(a & b) over the words inside both extents; union = area_d + area_g - inter in integers;
+ *      iou float32 [n][D][G] = (float)((double)inter / (double)union), 0 where union == 0.
+ *
+ *      box_iou: boxes float32 [n][D][4] and [n][G][4] = (x1, y1, x2, y2), all in float32 without contraction, in the order of
+ *      the detector's own IoU: iw = max(min(ax2, bx2) - max(ax1, bx1), 0), ih likewise from y, inter = iw * ih,
+ *      union = ((ax2 - ax1) * (ay2 - ay1) + (bx2 - bx1) * (by2 - by1)) - inter, iou = inter / union, 0 where union <= 0.
+ *
+ *      match_instances: COCO's evaluateImg without crowd or ignore regions, for T thresholds (`thresholds`: T float32 on the
+ *      HOST, 1 <= T <= 32, each finite and in (0, 1]) in one launch.  Per (image, threshold t): the detections are taken in
+ *      descending score, ties by ascending slot (the order is computed here, the input need not be sorted; -0 counts as +0);
+ *      each takes the still-unmatched ground truth of greatest iou among those with iou >= t, ties to the lowest slot, and,
+ *      with class_aware != 0, among those with gt_labels == its det_labels only; a detection with no such ground truth stays
+ *      unmatched.  det_match int32 [n][T][D] and gt_match int32 [n][T][G] hold the partner's slot or -1.
+ *
+ *      Method: a wave packs 64 bytes into one word with one ballot; the IoU runs one workgroup per (image, detection) with the
+ *      detection's extent window in LDS (up to 4096 words; read in place beyond), waves over ground truths, lanes over the
+ *      words of the shared window; matching is one wave per (image, threshold).
+ *
+ *      Every pointer but `thresholds` is a device pointer aligned to its element size; nothing here allocates or
+ *      synchronises. ---- */
+int rfi_op_pack_masks(rfi_ctx* ctx, const uint8_t* masks, int64_t m, int h, int w, uint64_t* bits, int32_t* area, int32_t* extent);
+int rfi_op_mask_iou(rfi_ctx* ctx, const uint64_t* det_bits, const int32_t* det_area, const int32_t* det_extent, const int32_t* det_count,
+                    const int32_t* det_base, int64_t det_planes, const uint64_t* gt_bits, const int32_t* gt_area, const int32_t* gt_extent,
+                    const int32_t* gt_count, const int32_t* gt_base, int64_t gt_planes, int n, int d, int g, int h, int w, int32_t* inter,
+                    float* iou);
+int rfi_op_box_iou(rfi_ctx* ctx, const float* det_boxes, const int32_t* det_count, const float* gt_boxes, const int32_t* gt_count, int n, int d,
+                   int g, float* iou);
+int rfi_op_match_instances(rfi_ctx* ctx, const float* iou, const float* scores, const int32_t* det_labels, const int32_t* det_count,
+                           const int32_t* gt_labels, const int32_t* gt_count, int n, int d, int g, const float* thresholds, int t,
+                           int class_aware, int32_t* det_match, int32_t* gt_match);
+
 /* ---- kernel-level entry points (device pointers only).  Used by the parity tests to
  *      check each HIP kernel against the oracle in isolation.  impl: 0 auto, 1 direct VALU,
  *      2 MFMA implicit GEMM in native float32 (v_mfma_f32_32x32x2_f32), 3 MFMA implicit GEMM with bfloat16

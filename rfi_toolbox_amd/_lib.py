@@ -245,6 +245,10 @@ _PROTOS = {
     "rfi_op_instances_select": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "rfi_op_instance_masks": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "rfi_op_copy_rows": (_i, [_vp, _vp, _sz, _vp, _sz, _sz, _sz]),
+    "rfi_op_pack_masks": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp]),
+    "rfi_op_mask_iou": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp, _vp]),
+    "rfi_op_box_iou": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "rfi_op_match_instances": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
     "rfi_op_conv3x3": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     "rfi_op_conv1x1": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     "rfi_op_conv_s2": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),

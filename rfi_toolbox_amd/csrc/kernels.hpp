@@ -419,6 +419,17 @@ void launch_instances_select(rfi_ctx* ctx, const int* n_components, const int* c
                              int* component);
 void launch_instance_masks(rfi_ctx* ctx, const int* labels, int n, int h, int w, const int* component, const int* count, const int* base,
                            int max_instances, uint8_t* masks);
+// instance matching (instance_match.hip; semantics in include/rfi_hip.h, "instance matching").  Device pointers except
+// `thresholds` (host, T floats); nothing here allocates or synchronises.  Sizes and alignment are checked here.
+void launch_pack_masks(rfi_ctx* ctx, const uint8_t* masks, int64_t m, int h, int w, uint64_t* bits, int* area, int* extent);
+void launch_mask_iou(rfi_ctx* ctx, const uint64_t* det_bits, const int* det_area, const int* det_extent, const int* det_count,
+                     const int* det_base, int64_t det_planes, const uint64_t* gt_bits, const int* gt_area, const int* gt_extent,
+                     const int* gt_count, const int* gt_base, int64_t gt_planes, int n, int D, int G, int h, int w, int* inter, float* iou);
+void launch_box_iou(rfi_ctx* ctx, const float* det_boxes, const int* det_count, const float* gt_boxes, const int* gt_count, int n, int D,
+                    int G, float* iou);
+void launch_match_instances(rfi_ctx* ctx, const float* iou, const float* scores, const int* det_labels, const int* det_count,
+                            const int* gt_labels, const int* gt_count, int n, int D, int G, const float* thresholds, int T, int class_aware,
+                            int* det_match, int* gt_match);
 // RFISimulator waterfalls (rfi_sim.hip): draws the event table into `events` (unless p.clean), then one gather per
 // pixel into `out` (layout RFI_SIM_*) and `mask`; sizes are checked by rfi_simulate_rfi
 void launch_rfi_sim(rfi_ctx* ctx, unsigned long long seed, unsigned first_sample, int n_samples,

@@ -57,5 +57,9 @@ __device__ __forceinline__ u64 wave_usum(u64 v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
 }
+__device__ __forceinline__ int wave_isum(int v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
 
 }  // namespace rfi

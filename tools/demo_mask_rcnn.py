@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Overfit the detector assembly (``MaskRCNN``) on a few synthetic patches with rectangular bright regions and report how
-well ``predict`` recovers them: best box IoU per ground-truth region and the IoU of the union mask.  A functional
+well ``predict`` recovers them: best box IoU per ground-truth region, the IoU of the union mask, and box and mask AP50 / AP /
+AR from ``evaluation.score_detections`` (per emitter family with ``--from-simulator``).  A functional
 demonstration (the pieces are parity-tested one by one), not a benchmark.
 
     python tools/demo_mask_rcnn.py [--steps 200] [--dtype float32|bfloat16] [--detect] [--from-masks | --from-simulator]
@@ -35,9 +36,16 @@ def batch(rng, n, size):
     return x, targets
 
 
-def iou(a, b):
-    ix = max(0.0, min(a[2], b[2]) - max(a[0], b[0])) * max(0.0, min(a[3], b[3]) - max(a[1], b[1]))
-    return ix / ((a[2] - a[0]) * (a[3] - a[1]) + (b[2] - b[0]) * (b[3] - b[1]) - ix)
+def report(title, detections, targets, num_classes, names):
+    """Box and mask AP of `detections` (the list of predict or the device dict of detect) against `targets`."""
+    from rfi_toolbox_amd.evaluation import score_detections
+    for kind in ("box", "mask"):
+        s = score_detections(detections, targets, num_classes=num_classes, kind=kind, class_names=names)
+        print(f"{title} {kind:4s} AP50 {s['AP50']:.3f}  AP {s['AP']:.3f}  AR {s['AR']:.3f}")
+        if num_classes > 2:
+            for name, c in s["per_class"].items():
+                if c["n_gt"] or c["n_det"]:
+                    print(f"    {name:16s} AP50 {c['AP50']:.3f}  AP {c['AP']:.3f}  AR {c['AR']:.3f}  ({c['n_gt']} emitters, {c['n_det']} detections)")
 
 
 def main():
@@ -84,12 +92,18 @@ def main():
     if a.from_simulator:
         x = x.numpy()                                   # (predict takes host images)
     out = det.predict(x)
+    from rfi_toolbox_amd.evaluation import match_instances
+    box_iou = match_instances(out, targets, kind="box", class_aware=False).numpy()["iou"]       # (n, D, G), zero behind the counts
     for i, (o, t) in enumerate(zip(out, targets)):
-        best = [max((iou(g, b) for b in o["boxes"]), default=0.0) for g in t["boxes"]]
+        best = box_iou[i, :, :len(t["boxes"])].max(axis=0, initial=0.0)
         gm = t["masks"].any(0)
         mi = (gm & o["rfi_mask"]).sum() / max((gm | o["rfi_mask"]).sum(), 1)
         print(f"image {i}: {len(o['boxes'])} detections, best box IoU per region {[round(float(b), 3) for b in best]}, union-mask IoU {mi:.3f}")
+    names = EVENT_CLASSES if a.from_simulator else ("background", "region")
+    report("predict:", out, step_targets if a.from_simulator or a.from_masks else targets, det.num_classes, names)
     if a.detect:
+        report("detect (device dict):", det.detect(x, out="device"), step_targets if a.from_simulator or a.from_masks else targets,
+               det.num_classes, names)
         dev = det.detect(x)
         same = all(len(d["boxes"]) == len(o["boxes"]) and np.array_equal(d["labels"], o["labels"]) for d, o in zip(dev, out))
         if same:
