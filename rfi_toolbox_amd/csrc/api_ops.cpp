@@ -60,6 +60,12 @@ bf16_t* wb_of(rfi_ctx* ctx, CallScope& s, const float* src, int taps, int Cout, 
     launch_weights_to_wb_one(ctx, WBDesc{src, wb, taps, Cout, Cin, {seg0, seg1}, 1});
     return wb;
 }
+// a weight gradient on a slab workspace of the call's own
+void wgrad_in_scope(rfi_ctx* ctx, CallScope& s, WgradArgs& a, int impl) {
+    a.slab_floats = wgrad_slab_floats(a, impl);
+    a.slab = s.temp<float>(a.slab_floats);
+    launch_wgrad(ctx, a, impl);
+}
 }  // namespace
 
 extern "C" {
@@ -130,9 +136,7 @@ int rfi_op_conv3x3_wgrad(rfi_ctx* ctx, int impl, const float* x, const float* dy
         a.sy = cin; a.sx = 1;
         const size_t numel = (size_t)9 * cin * cout;
         a.dw = s.temp<float>(numel);
-        a.slab_floats = wgrad_slab_floats(a, impl);
-        a.slab = s.temp<float>(a.slab_floats);
-        launch_wgrad(ctx, a, impl);
+        wgrad_in_scope(ctx, s, a, impl);
         store_ref_wgrad(ctx, a.dw, numel, false, cout, cin, dw_oihw);
     });
 }
@@ -278,9 +282,7 @@ int rfi_op_conv_s2_wgrad(rfi_ctx* ctx, int impl, int ksize, const float* x, cons
         a.sy = a.Cx;
         const size_t numel = (size_t)a.R * a.R * a.Cx * cout;
         a.dw = s.temp<float>(numel);
-        a.slab_floats = wgrad_slab_floats(a, impl);
-        a.slab = s.temp<float>(a.slab_floats);
-        launch_wgrad(ctx, a, impl);
+        wgrad_in_scope(ctx, s, a, impl);
         if (ksize == 1) {
             RFI_CHECK_HIP(hipMemcpyAsync(dw_oihw, a.dw, numel * 4, hipMemcpyDeviceToDevice, ctx->stream));
             return;
@@ -388,9 +390,7 @@ int rfi_op_convt2x2_wgrad(rfi_ctx* ctx, int impl, const float* x, const float* d
             pa.slab = s.temp<float>(pa.slab_floats);
             launch_pwgrad(ctx, pa);
         } else {
-            a.slab_floats = wgrad_slab_floats(a, impl);
-            a.slab = s.temp<float>(a.slab_floats);
-            launch_wgrad(ctx, a, impl);
+            wgrad_in_scope(ctx, s, a, impl);
         }
         store_ref_wgrad(ctx, a.dw, numel, true, cin, cout, dw_iohw);
     });

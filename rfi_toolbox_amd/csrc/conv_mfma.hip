@@ -27,8 +27,6 @@
 
 namespace rfi {
 
-void launch_conv_direct(rfi_ctx* ctx, const ConvArgs& a);
-
 namespace {
 
 constexpr int KC = 16;    // channels per K-chunk
@@ -655,90 +653,8 @@ bool conv_mfma_eligible(const ConvArgs& a) {
     return known;
 }
 
-void launch_conv(rfi_ctx* ctx, ConvArgs& a, int impl) {
-    if (impl == IMPL_PLANES_X3 || impl == IMPL_PLANES_BF16) {
-        RFI_REQUIRE(a.R == 3 && a.S == 1 && a.zgroups == 1, "conv: the plane kernels cover 3x3 stride-1 convolutions");
-        a.planes = impl == IMPL_PLANES_X3 ? 3 : 1;
-        impl = IMPL_MFMA;
-    }
-    if (impl == IMPL_MFMA_BF16) {
-        a.bf16 = true;
-        impl = IMPL_MFMA;
-    }
-    if (impl == IMPL_MFMA_BF16X3) {
-        a.bf16x3 = true;
-        a.wB3 = nullptr;                // (this implementation was asked for by name)
-        impl = IMPL_MFMA;
-    }
-    if (impl == IMPL_WS_X3 && conv_stem_eligible(a)) {       // kernel-level API / tests: the stem kernel by name
-        a.bf16x3 = true;
-        launch_conv_stem(ctx, a);
-        return;
-    }
-    if (impl == IMPL_WS_X3 || impl == IMPL_WS_BF16) {       // kernel-level API / tests: a temporary B-operand-order copy of the filters
-        const int P = impl == IMPL_WS_X3 ? 3 : 1;
-        const bool gw = !conv_ws_eligible(a) && gemm_ws_eligible(a);
-        RFI_REQUIRE(gw || conv_ws_eligible(a), "conv: shape not eligible for the wave-specialised kernels");
-        RFI_REQUIRE(!gw || P == 3, "conv: the wave-specialised GEMM kernel exists in the 3 x bf16 arithmetic only");
-        a.bf16x3 = P == 3;
-        a.bf16 = P == 1;
-        // conv_ws: [9][Cout][Cin]; gemm_ws: the transposed conv forward as ONE tap of 4 Cout channels, its input gradient
-        // as four taps, a 1x1 conv as one tap
-        const int taps = gw ? (a.R == 2 ? 4 : 1) : 9, cout = gw && a.zgroups == 4 ? 4 * a.Cout : a.Cout;
-        CallScope sc(ctx);
-        bf16_t* wb = sc.temp<bf16_t>(wb_elems(taps, cout, a.Cin, 0, P) + 32);
-        launch_weights_to_wb_one(ctx, WBDesc{a.w, wb, taps, cout, a.Cin, {a.Cin, 0}, P});
-        if (gw) launch_gemm_ws(ctx, a, wb);
-        else launch_conv_ws(ctx, a, wb, P);
-        return;
-    }
-    if (impl == IMPL_AUTO && a.bf16x3 && conv_stem_eligible(a)) {
-        launch_conv_stem(ctx, a);
-        return;
-    }
-    if (impl == IMPL_AUTO && a.bf16x3 && a.wB3 && conv_ws_eligible(a)) {
-        launch_conv_ws(ctx, a, a.wB3, 3);
-        return;
-    }
-    if (impl == IMPL_AUTO && a.bf16 && a.wB1 && conv_ws_eligible(a)) {
-        launch_conv_ws(ctx, a, a.wB1, 1);
-        return;
-    }
-    if (impl == IMPL_AUTO && a.bf16x3 && a.wB3 && gemm_ws_eligible(a)) {
-        launch_gemm_ws(ctx, a, a.wB3);
-        return;
-    }
-    // (a layer of the plain U-Net that carries a wave-specialised filter copy keeps no pre-split records up to date --
-    // rfi_model::ws_set clears ConvArgs::w3 for it -- so a shape those kernels declined runs below on a temporary split copy)
-    RFI_REQUIRE(a.N > 0 && a.H > 0 && a.W > 0 && a.Cin > 0 && a.Cout > 0, "conv: empty shape");
-    RFI_REQUIRE(a.x.pstride >= a.Cin && a.y.pstride >= a.Cout, "conv: pixel stride smaller than channels");
-    RFI_REQUIRE(a.zgroups == 1 || (a.zgroups == 4 && a.R == 1), "conv: zgroups only for convT forward");
-    RFI_REQUIRE((int64_t)a.N * a.Hin * a.Win * a.x.pstride < (int64_t)1 << 31 &&
-                    (int64_t)a.N * a.Hout * a.Wout * a.y.pstride < (int64_t)1 << 31 &&
-                    (int64_t)a.R * a.R * a.Cin * a.Cout * a.zgroups < (int64_t)1 << 31,
-                "conv: tensor too large for 32-bit element offsets");
-    if (a.planes) {                 // IMPL_PLANES_*: the plane kernels (conv_planes.hip) through temporary plane copies
-        launch_pconv_from_f32(ctx, a, a.planes);
-        return;
-    }
-    const bool ok = conv_mfma_eligible(a);
-    if (impl == IMPL_MFMA) RFI_REQUIRE(ok, "conv: shape/alignment not eligible for the MFMA kernel");
-    if (impl == IMPL_DIRECT || !ok) {
-        RFI_REQUIRE(!a.y16, "conv: bfloat16 output needs the MFMA kernel");
-        launch_conv_direct(ctx, a);
-        return;
-    }
-    // 3 x bf16: the filters are read pre-split (ConvArgs::w3); callers that only have float32 weights (the
-    // kernel-level API) get a temporary split copy, and their ConvArgs::w3 is null again on return
-    CallScope sc(ctx);
-    struct ClearW3 { ConvArgs* a; ~ClearW3() { if (a) a->w3 = nullptr; } } clear_w3{nullptr};
-    if (a.bf16x3 && !a.w3) {
-        const int taps = a.R * a.R * a.zgroups;
-        float* w3 = sc.temp<float>(weights_x3_floats(taps, a.Cout, a.Cin));
-        launch_weights_to_x3(ctx, a.w, taps, a.Cout, a.Cin, w3);
-        a.w3 = w3;
-        clear_w3.a = &a;
-    }
+// the MFMA kernel for an eligible, validated launch (launch_conv, dispatch.cpp); 3 x bf16: the filters are read pre-split (ConvArgs::w3)
+void launch_conv_mfma(rfi_ctx* ctx, ConvArgs& a) {
     const double flops = a.algo_flops >= 0 ? a.algo_flops
                                            : 2.0 * a.N * a.H * a.W * (double)a.Cout * a.R * a.R * a.Cin * a.zgroups;
     std::string label;

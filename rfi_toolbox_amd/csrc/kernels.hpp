@@ -80,27 +80,39 @@ struct ConvArgs {
 #endif
 };
 
-// 5 / 6: the plane kernels (planes.hpp) in the 3 x bf16 / bf16 arithmetic; callers holding float32 tensors get
-// temporary plane copies (kernel-level ABI, tests)
-// 7 / 8: the wave-specialised kernels (conv_ws.hip, gemm_ws.hip) in the 3 x bf16 / the bf16 arithmetic; callers without
-// ConvArgs::wB3 / wB1 get a temporary filter copy
+// The implementation codes of the kernel-level ABI.  5 / 6: the plane kernels (planes.hpp) in the 3 x bf16 / bf16 arithmetic;
+// callers holding float32 tensors get temporary plane copies.  7 / 8: the wave-specialised conv kernels (conv_stem.hip,
+// conv_ws.hip, gemm_ws.hip) in the 3 x bf16 / the bf16 arithmetic; callers without ConvArgs::wB3 / wB1 get a temporary
+// filter copy (a weight gradient takes 7 / 8 as IMPL_AUTO)
 enum ConvImpl { IMPL_AUTO = 0, IMPL_DIRECT = 1, IMPL_MFMA = 2, IMPL_MFMA_BF16 = 3, IMPL_MFMA_BF16X3 = 4,
                 IMPL_PLANES_X3 = 5, IMPL_PLANES_BF16 = 6, IMPL_WS_X3 = 7, IMPL_WS_BF16 = 8 };
+// ---- which kernel runs a launch (dispatch.cpp).  apply_impl writes an IMPL_* code into the descriptor's arithmetic flags;
+// choose_* read the descriptor and the *_eligible predicates only (no context, no launch, no allocation) and throw where an
+// implementation asked for by name does not fit.  launch_conv / launch_wgrad: apply_impl, choose, validate, launch
+enum class ConvKernel { Direct, Mfma, Stem, ConvWs, GemmWs, Planes };
+enum class WgradKernel { Direct, Mfma, Stem, Ws, Split, Planes };
+struct WgradArgs;
+void apply_impl(ConvArgs& a, int impl);
+void apply_impl(WgradArgs& a, int impl);
+ConvKernel choose_conv(const ConvArgs& a, int impl);
+WgradKernel choose_wgrad(const WgradArgs& a, int impl);
+void launch_conv(rfi_ctx* ctx, ConvArgs& a, int impl = IMPL_AUTO);
+// the kernels behind ConvKernel (the plane kernels' bridge: planes.hpp)
+void launch_conv_direct(rfi_ctx* ctx, const ConvArgs& a);
+bool conv_mfma_eligible(const ConvArgs& a);
+void launch_conv_mfma(rfi_ctx* ctx, ConvArgs& a);        // 3 x bf16: reads ConvArgs::w3
+// conv_stem.hip: the first 3x3 conv of a network (Cin = 4 padded, Cout 32 / 64) with K = (tap, channel) packed into three k-steps
+bool conv_stem_eligible(const ConvArgs& a);
+void launch_conv_stem(rfi_ctx* ctx, ConvArgs& a);
 bool conv_ws_eligible(const ConvArgs& a);
 void launch_conv_ws(rfi_ctx* ctx, ConvArgs& a, const unsigned short* wB, int P);
 bool gemm_ws_eligible(const ConvArgs& a);        // gemm_ws.hip: transposed conv (k2, s2) forward / input gradient, 1x1 convs
 void launch_gemm_ws(rfi_ctx* ctx, ConvArgs& a, const unsigned short* wB3);
-
-bool conv_mfma_eligible(const ConvArgs& a);
 // filters [taps][Cout][Cin] -> [taps][Cout][ceil(Cin/16)][h16 | m16 | l16] bf16 records (24 floats each)
 size_t weights_x3_floats(int taps, int Cout, int Cin);
 void launch_weights_to_x3(rfi_ctx* ctx, const float* w, int taps, int Cout, int Cin, float* out);
 struct X3Desc { const float* src; float* dst; int64_t rows; int Cin; int nchunks; };
 void launch_weights_to_x3_batched(rfi_ctx* ctx, const X3Desc* descs_dev, int n, double total_bytes);
-// conv_stem.hip: the first 3x3 conv of a network (Cin = 4 padded, Cout 32 / 64) with K = (tap, channel) packed into three k-steps
-bool conv_stem_eligible(const ConvArgs& a);
-void launch_conv_stem(rfi_ctx* ctx, ConvArgs& a);
-void launch_conv(rfi_ctx* ctx, ConvArgs& a, int impl = IMPL_AUTO);
 
 // ---------------------------------------------------------------- weight gradient
 //   dW[tap][cy][cx] = sum_{n,y,x} Yop[n,y,x,cy] * Xop[n, y*S + r - pad, x*S + s - pad, cx]
@@ -122,15 +134,27 @@ struct WgradArgs {
     double algo_flops = -1;
     bool bf16 = false;                // MFMA and direct kernels: operands rounded to bf16 in registers, fp32 accumulate
     bool bf16x3 = false;              // MFMA kernel: float32 emulated by 3 x bf16 pieces
-    int planes = 0;                   // 1 / 3: plane kernel through temporary plane copies (IMPL_PLANES_*)
 };
+void launch_wgrad(rfi_ctx* ctx, const WgradArgs& a, int impl = IMPL_AUTO);
+// the slab workspace launch_wgrad(a, impl) may need: the largest plan among the kernels that accept the shape, whatever the
+// arithmetic flags and the alignment of the data pointers at the launch (models size with null pointers)
 size_t wgrad_slab_floats(const WgradArgs& a, int impl);
+// the kernels behind WgradKernel.  *_slab_floats: the kernel's slab plan for a shape it accepts; the stem kernel sizes its
+// grid to the workspace it is given, and wgrad_stem_eligible holds only where that has room for 64 workgroups
+void launch_wgrad_direct(rfi_ctx* ctx, const WgradArgs& a);
+size_t wgrad_direct_slab_floats(const WgradArgs& a);
+bool wgrad_mfma_eligible(const WgradArgs& a);
+size_t wgrad_mfma_slab_floats(const WgradArgs& a);
+void launch_wgrad_mfma(rfi_ctx* ctx, const WgradArgs& a);
+// wgrad_split.hip: the bf16 / 3 x bf16 arithmetic with the operands split once at staging time
+bool wgrad_split_eligible(const WgradArgs& a);
+size_t wgrad_split_slab_floats(const WgradArgs& a);
+void launch_wgrad_split(rfi_ctx* ctx, const WgradArgs& a);
 bool wgrad_ws_eligible(const WgradArgs& a);      // wgrad_ws.hip: the wave-specialised kernel (float32 tensors, 3 x bf16 or bf16 operands)
+size_t wgrad_ws_slab_floats(const WgradArgs& a);
 void launch_wgrad_ws(rfi_ctx* ctx, const WgradArgs& a);
-size_t wgrad_ws_slab_floats(const WgradArgs& a);  // slab workspace of the shapes only wgrad_ws covers (R = 2 / stride 2), else 0
 bool wgrad_stem_eligible(const WgradArgs& a);    // wgrad_stem.hip: the first conv of a network (Cx = 4 padded, Cy 32 / 64)
 void launch_wgrad_stem(rfi_ctx* ctx, const WgradArgs& a);
-void launch_wgrad(rfi_ctx* ctx, const WgradArgs& a, int impl = IMPL_AUTO);
 
 // The raw output Y of a conv layer as the elementwise kernels read it: float32 [M][C] or, in the bf16 data flow
 // (planes.hpp, P = 1), bfloat16 [M][ps].  A `const float*` converts implicitly, so float32 call sites read as before.

@@ -161,7 +161,7 @@ void UNetModel::prepare_shape(int n, int h, int w) {
         x_stage = new_buf(); x_stage2 = new_buf(); x_pad = new_buf(); out_stage = new_buf();
         ws_red = new_buf(); ws_slab = new_buf(); lab_stage = new_buf();
     }
-    size_t slab_need = 0, red_need = 0;
+    size_t red_need = 0;
     auto upd_red = [&](size_t f) { if (f > red_need) red_need = f; };
     for (int l = 1; l <= D; ++l) {
         const size_t M = (size_t)n * (h >> (l - 1)) * (w >> (l - 1));
@@ -199,35 +199,16 @@ void UNetModel::prepare_shape(int n, int h, int w) {
     upd_red(loss_ws_doubles(M1) * 2);
     upd_red(sumsq_ws_doubles(n_flat) * 2);
     bufs[ws_red].ensure(ctx, red_need + 16);
-    // wgrad slabs: the largest need over all layers
-    auto conv_geom = [&](int ci, int& H, int& W) {         // spatial size of conv ci's output
-        H = h >> (convs[ci].level - 1);
-        W = w >> (convs[ci].level - 1);
-    };
-    for (size_t ci = 0; ci < convs.size(); ++ci) {
-        int H, W;
-        conv_geom((int)ci, H, W);
-        WgradArgs a;
-        a.N = n; a.H = H; a.W = W; a.Hx = H; a.Wx = W;
-        a.Cx = convs[ci].cin_p; a.Cy = convs[ci].cout;
-        a.R = 3; a.S = 1; a.pad = 1;
-        if (convs[ci].stride == 2) { a.Cx *= 4; a.R = 2; }            // its 2x2 form on the space-to-depth input
-        if (convs[ci].R == 1) { a.R = 1; a.pad = 0; }
-        a.xop.pstride = a.Cx; a.yop.pstride = a.Cy;
-        a.tap_stride = (int64_t)a.Cx * a.Cy;
-        a.bf16x3 = true;              // (the split-at-staging plan is the largest)
-        slab_need = std::max(slab_need, wgrad_slab_floats(a, IMPL_AUTO));
+    // wgrad slabs: the largest need over all layers, from the descriptors the backward passes build (model_resnet.cpp: a
+    // stride-2 3x3 conv runs as its 2x2 form on the space-to-depth input, the 1x1 projection on a channel slice of that input)
+    for (const ConvBN& c : convs) {
+        const Shape s{n, h >> (c.level - 1), w >> (c.level - 1)};
+        if (c.R == 1) need_slab(wgrad_same(View{nullptr, 4 * c.cin}, InXform{}, nullptr, s, 1, 0, c.cin, c.cout, nullptr));
+        else if (c.stride == 2) need_slab(wgrad_same(View{nullptr, 4 * c.cin}, InXform{}, nullptr, s, 2, 1, 4 * c.cin, c.cout, nullptr));
+        else need_slab(wgrad_same(View{nullptr, c.cin_p}, InXform{}, nullptr, s, 3, 1, c.cin_p, c.cout, nullptr));
     }
-    for (int k = 0; k < D; ++k) {
-        const int l = D - k;                       // decoder level; input at level l+1 resolution
-        WgradArgs a;
-        a.N = n; a.H = h >> l; a.W = w >> l; a.Hx = a.H * 2; a.Wx = a.W * 2;
-        a.Cx = ups[k].cout; a.Cy = ups[k].cin;
-        a.xop.pstride = 2 * ups[k].cout; a.yop.pstride = a.Cy;
-        a.R = 2; a.S = 2; a.pad = 0;
-        a.tap_stride = (int64_t)a.Cx * a.Cy;
-        slab_need = std::max(slab_need, wgrad_slab_floats(a, IMPL_AUTO));
-    }
+    for (int k = 0; k < D; ++k)                    // decoder level D - k: dUp is the first half of its concat gradient
+        need_slab(convt_wgrad_args(ups[k], View{nullptr, 2 * ups[k].cout}, View{nullptr, ups[k].cin}, InXform{}, Shape{n, h >> (D - k), w >> (D - k)}));
     bufs[ws_slab].ensure(ctx, slab_need + 16);
     // per-layer regions for the partial sums of the conv-bias gradients + the table of the batched finisher
     // (the plane flows too: the plain U-Net's and the ResNet-encoder model's, whose encoder convs have no bias)
@@ -236,12 +217,10 @@ void UNetModel::prepare_shape(int n, int h, int w) {
         if (dbias_descs) { ctx->release(dbias_descs); dbias_descs = nullptr; }
         size_t need = 0;
         std::vector<FinishSumDesc> hd;
-        for (size_t ci = 0; ci < convs.size(); ++ci) {
-            int H, W;
-            conv_geom((int)ci, H, W);
-            const int64_t M = (int64_t)n * H * W;
-            convs[ci].dbias_rec_off = need;
-            need += align4(channel_sum_ws_floats(M, convs[ci].cout)) + 4;
+        auto pixels = [&](const ConvBN& c) { return (int64_t)n * (h >> (c.level - 1)) * (w >> (c.level - 1)); };      // of its output
+        for (ConvBN& c : convs) {
+            c.dbias_rec_off = need;
+            need += align4(channel_sum_ws_floats(pixels(c), c.cout)) + 4;
         }
         for (int k = 0; k < depth; ++k) {               // the transposed convs' bias gradients (decoder level l = D - k)
             const int l = depth - k;
@@ -252,12 +231,9 @@ void UNetModel::prepare_shape(int n, int h, int w) {
         need += align4(head_bwd_ws_floats((int64_t)n * h * w, feat, out_ch)) + 4;
         dbias_pool = static_cast<float*>(ctx->alloc(need * sizeof(float)));
         dbias_max_c = 0;
-        for (size_t ci = 0; ci < convs.size(); ++ci) {
-            int H, W;
-            conv_geom((int)ci, H, W);
-            const ConvBN& c = convs[ci];
+        for (const ConvBN& c : convs) {
             if (!c.has_bias) continue;
-            hd.push_back(FinishSumDesc{reinterpret_cast<const double*>(dbias_pool + c.dbias_rec_off), bn_bwd_apply_records((int64_t)n * H * W, c.cout),
+            hd.push_back(FinishSumDesc{reinterpret_cast<const double*>(dbias_pool + c.dbias_rec_off), bn_bwd_apply_records(pixels(c), c.cout),
                                        (int64_t)c.cout, c.cout, grads + c.b_off});
             dbias_max_c = std::max(dbias_max_c, c.cout);
         }
@@ -574,7 +550,7 @@ ConvArgs rfi_model::convt_args(const UpConv& u, View x, InXform xf, Shape s) con
     return a;
 }
 
-void rfi_model::convt_backward(const UpConv& u, View dup, View x, InXform xf, Shape s, float* dx) {
+WgradArgs rfi_model::convt_wgrad_args(const UpConv& u, View dup, View x, InXform xf, Shape s) const {
     WgradArgs wa;
     wa.xop = dup;
     wa.yop = x;
@@ -586,7 +562,11 @@ void rfi_model::convt_backward(const UpConv& u, View dup, View x, InXform xf, Sh
     wa.tap_stride = (int64_t)u.cin * u.cout;
     wa.sy = 1; wa.sx = u.cin;          // -> [tap][cout][cin]
     set_wgrad(wa);
-    wgrad_on_side(wa, nullptr);
+    return wa;
+}
+
+void rfi_model::convt_backward(const UpConv& u, View dup, View x, InXform xf, Shape s, float* dx) {
+    wgrad_on_side(convt_wgrad_args(u, dup, x, xf, s), nullptr);
     ConvArgs a;
     a.x = dup;
     a.N = s.N; a.H = s.H; a.W = s.W; a.Hin = 2 * s.H; a.Win = 2 * s.W;

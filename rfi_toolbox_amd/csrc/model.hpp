@@ -186,6 +186,10 @@ struct rfi_model {
         wa.bf16 = arith == Arith::BF16;
         wa.bf16x3 = arith == Arith::X3;
     }
+    // prepare_shape: ws_slab (slab_need + 16 floats; grow-only, as the buffer) has to hold the slabs of weight gradient `wa` --
+    // the descriptor the backward pass will launch, from the same builder, with null data pointers
+    size_t slab_need = 0;
+    void need_slab(const rfi::WgradArgs& wa) { slab_need = std::max(slab_need, rfi::wgrad_slab_floats(wa, rfi::IMPL_AUTO)); }
     // set by the plain U-Net: it keeps no pre-split (3 x bf16) filter records for the layers the wave-specialised kernels
     // cover, since at its shapes they never decline.  The other models (detector backbone on 4 x 4 maps, heads) keep every
     // record up to date, so a declined shape runs the round-2 kernel on valid records instead of a temporary copy (an
@@ -279,8 +283,10 @@ struct rfi_model {
                  int cin, float* Y, bool train, double flops);
     // ConvTranspose2d(k2, s2) over the input grid s: the forward launch but its output (y / y16: the caller's) ...
     rfi::ConvArgs convt_args(const rfi::UpConv& u, rfi::View x, rfi::InXform xf, rfi::Shape s) const;
-    // ... and its backward pass from dup (the gradient w.r.t. its output): the weight gradient on the side stream, then the
-    // input gradient into dx [M][u.cin].  (The bias gradient is the caller's.)
+    // ... its weight gradient from dup (the gradient w.r.t. its output) ...
+    rfi::WgradArgs convt_wgrad_args(const rfi::UpConv& u, rfi::View dup, rfi::View x, rfi::InXform xf, rfi::Shape s) const;
+    // ... and its backward pass from dup: that weight gradient on the side stream, then the input gradient into dx [M][u.cin].
+    // (The bias gradient is the caller's.)
     void convt_backward(const rfi::UpConv& u, rfi::View dup, rfi::View x, rfi::InXform xf, rfi::Shape s, float* dx);
 
     // backward-pass overlap: wgrad launches go to the context's side stream (see model.cpp)

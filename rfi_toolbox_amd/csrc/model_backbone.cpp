@@ -111,6 +111,15 @@ void BackboneModel::build() {
     frozen_dirty = true;
 }
 
+namespace {
+// a 1x1 conv does not see the image structure: on small maps (W < 32) run it on the same pixels laid out as one
+// [M / 32] x 32 image, so that the 32-pixel-wide tiles of the kernels are full instead of mostly padding
+Shape flat_1x1(Shape s, int R) {
+    const int64_t M = (int64_t)s.N * s.H * s.W;
+    return R == 1 && s.W < 32 && M % 32 == 0 ? Shape{1, (int)(M / 32), 32} : s;
+}
+}  // namespace
+
 void BackboneModel::prepare_shape(int n, int h, int w) {
     RFI_REQUIRE(h % 64 == 0 && w % 64 == 0, "ResNet50FPN: H and W must be multiples of 64");
     if (n == pN && h == pH && w == pW && !bufs.empty()) return;
@@ -135,7 +144,7 @@ void BackboneModel::prepare_shape(int n, int h, int w) {
     bufs[bY0].ensure(ctx, px(1) * feat);
     bufs[bP0].ensure(ctx, px(2) * feat);
     bufs[bArg].ensure(ctx, px(2) * feat / 4 + 4);
-    size_t gmax = px(1) * feat, wmax = 16, slab_need = 0;
+    size_t gmax = px(1) * feat, wmax = 16;
     for (auto& k : bb) {
         bufs[k.Y1].ensure(ctx, px(k.lvl_in) * k.width);
         bufs[k.Y2].ensure(ctx, px(k.lvl) * k.width);
@@ -170,21 +179,15 @@ void BackboneModel::prepare_shape(int n, int h, int w) {
     red_need = std::max({red_need, bn_bwd_ws_floats((int64_t)px(1), cmax), channel_sum_ws_floats((int64_t)px(2), std::max(cmax, F))});
     bufs[ws_red].ensure(ctx, red_need + 16);
     for (auto& c : convs) {
-        WgradArgs a;
-        a.N = n; a.H = h >> c.level; a.W = w >> c.level; a.Hx = a.H; a.Wx = a.W;
-        a.Cx = c.cin; a.Cy = c.cout;
-        a.R = c.R; a.S = 1; a.pad = c.R / 2;
-        if (c.R == 3 && c.stride == 2) { a.Cx *= 4; a.R = 2; a.pad = 1; }
-        if (c.R == 7) { a.R = 1; a.pad = 0; a.Cx = stem_kp(); }          // the K-packed stem
-        a.xop.pstride = a.Cx; a.yop.pstride = a.Cy;
-        a.tap_stride = (int64_t)a.Cx * a.Cy;
-        a.bf16x3 = true;
-        slab_need = std::max(slab_need, wgrad_slab_floats(a, IMPL_AUTO));
-        const int64_t M = (int64_t)a.N * a.H * a.W;
-        if (a.R == 1 && a.W < 32 && M % 32 == 0) {      // the flattened layout wgrad() runs small 1x1 maps in
-            a.N = 1; a.H = a.Hx = (int)(M / 32); a.W = a.Wx = 32;
-            slab_need = std::max(slab_need, wgrad_slab_floats(a, IMPL_AUTO));
-        }
+        // in the form backward_pass launches it: a stride-2 3x3 conv as 2x2 on its space-to-depth input (of which a stride-2
+        // 1x1 projection reads a channel slice), the stem K-packed as a 1x1 conv
+        int R = c.R, pad = c.R / 2, cx = c.cin;
+        if (c.R == 3 && c.stride == 2) { R = 2; pad = 1; cx = 4 * c.cin; }
+        if (c.R == 7) { R = 1; pad = 0; cx = stem_kp(); }
+        const View x{nullptr, c.R == 1 && c.stride == 2 ? 4 * c.cin : cx};
+        const Shape s{n, h >> c.level, w >> c.level};
+        for (const Shape& l : {s, flat_1x1(s, R)})      // (a small 1x1 map in both layouts, as ever: ws_slab keeps its size)
+            need_slab(wgrad_same(x, InXform{}, nullptr, l, R, pad, cx, c.cout, nullptr));
     }
     bufs[ws_slab].ensure(ctx, slab_need + 16);
     pN = n; pH = h; pW = w;
@@ -219,12 +222,6 @@ void BackboneModel::refresh_backbone() {
 
 namespace {
 
-// a 1x1 conv does not see the image structure: on small maps (W < 32) run it on the same pixels laid out as one
-// [M / 32] x 32 image, so that the 32-pixel-wide tiles of the kernels are full instead of mostly padding
-Shape flat_1x1(Shape s, int R) {
-    const int64_t M = (int64_t)s.N * s.H * s.W;
-    return R == 1 && s.W < 32 && M % 32 == 0 ? Shape{1, (int)(M / 32), 32} : s;
-}
 // every conv of the backbone is stride 1 on its own output grid s (stride 2: the 2x2 form on the space-to-depth input)
 void conv(rfi_model* m, View in, InXform xf, Shape s, const float* w, const float* w3, const float* bias, int cin, int cout, int R,
           int pad, float* Y) {

@@ -47,22 +47,14 @@ void Cnn3Model::prepare_shape(int n, int h, int w) {
     bufs[x_pad].ensure(ctx, M1 * convs[0].cin_p);
     bufs[out_stage].ensure(ctx, M1 * out_ch);
     bufs[lab_stage].ensure(ctx, (M1 + 3) / 4 + 4);
-    size_t red_need = 0, slab_need = 0;
+    size_t red_need = 0;
     auto upd = [&](size_t f) { red_need = std::max(red_need, f); };
     upd(head_bwd_ws_floats((int64_t)M1, feat, out_ch));
     upd(channel_sum_ws_floats((int64_t)M1, feat));
     upd(loss_ws_doubles((int64_t)M1) * 2);
     upd(sumsq_ws_doubles((int64_t)n_flat) * 2);
     bufs[ws_red].ensure(ctx, red_need + 16);
-    for (auto& c : convs) {
-        WgradArgs a;
-        a.N = n; a.H = h; a.W = w; a.Hx = h; a.Wx = w;
-        a.Cx = c.cin_p; a.Cy = c.cout;
-        a.xop.pstride = a.Cx; a.yop.pstride = a.Cy;
-        a.R = 3; a.S = 1; a.pad = 1;
-        a.tap_stride = (int64_t)a.Cx * a.Cy;
-        slab_need = std::max(slab_need, wgrad_slab_floats(a, IMPL_AUTO));
-    }
+    for (auto& c : convs) need_slab(wgrad_same(View{nullptr, c.cin_p}, InXform{}, nullptr, Shape{n, h, w}, 3, 1, c.cin_p, c.cout, nullptr));
     bufs[ws_slab].ensure(ctx, slab_need + 16);
     pN = n; pH = h; pW = w;
 }

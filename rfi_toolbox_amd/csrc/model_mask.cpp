@@ -69,40 +69,20 @@ void ConvHeadModel::prepare_shape(int n, int h, int w) {
     bufs[x_pad].ensure(ctx, 16);
     bufs[out_stage].ensure(ctx, M4 * out_ch);
     bufs[lab_stage].ensure(ctx, (M4 + 3) / 4 + 4);
-    size_t red_need = 0, slab_need = 0;
+    size_t red_need = 0;
     auto upd = [&](size_t f) { red_need = std::max(red_need, f); };
     upd(head_bwd_ws_floats((int64_t)M4, C, out_ch));
     upd(channel_sum_ws_floats((int64_t)M4, C));
     upd(loss_ws_doubles((int64_t)M4) * 2);
     upd(sumsq_ws_doubles((int64_t)n_flat) * 2);
     bufs[ws_red].ensure(ctx, red_need + 16);
-    {
-        WgradArgs a;                                  // the 3x3 layers
-        a.N = n; a.H = h; a.W = w; a.Hx = h; a.Wx = w;
-        a.Cx = C; a.Cy = C;
-        a.xop.pstride = C; a.yop.pstride = C;
-        a.R = 3; a.S = 1; a.pad = 1;
-        a.tap_stride = (int64_t)C * C;
-        a.bf16x3 = true;
-        slab_need = std::max(slab_need, wgrad_slab_floats(a, IMPL_AUTO));
-        WgradArgs b;                                  // the transposed conv
-        b.N = n; b.H = h; b.W = w; b.Hx = 2 * h; b.Wx = 2 * w;
-        b.Cx = C; b.Cy = C;
-        b.xop.pstride = C; b.yop.pstride = C;
-        b.R = 2; b.S = 2; b.pad = 0;
-        b.tap_stride = (int64_t)C * C;
-        slab_need = std::max(slab_need, wgrad_slab_floats(b, IMPL_AUTO));
-    }
-    if (head_on_mfma()) {
-        WgradArgs c;                                  // the 1x1 head's weight gradient
-        c.N = n; c.H = out_scale * h; c.W = out_scale * w; c.Hx = c.H; c.Wx = c.W;
-        c.Cx = C; c.Cy = out_ch;
-        c.xop.pstride = C; c.yop.pstride = out_ch;
-        c.R = 1; c.S = 1; c.pad = 0;
-        c.tap_stride = (int64_t)C * out_ch;
-        c.bf16x3 = true;
-        slab_need = std::max(slab_need, wgrad_slab_floats(c, IMPL_AUTO));
-    }
+    const Shape s{n, h, w};
+    need_slab(wgrad_same(View{nullptr, C}, InXform{}, nullptr, s, 3, 1, C, C, nullptr));          // the 3x3 layers
+    // the transposed conv (sized without `upsample` too, as ever: ws_slab keeps its size)
+    UpConv up; up.cin = up.cout = C;
+    need_slab(convt_wgrad_args(upsample ? ups[0] : up, View{nullptr, C}, View{nullptr, C}, InXform{}, s));
+    if (head_on_mfma())                                   // the 1x1 head's weight gradient
+        need_slab(wgrad_same(View{nullptr, C}, InXform{}, nullptr, Shape{n, out_scale * h, out_scale * w}, 1, 0, C, out_ch, nullptr));
     bufs[head_wd].ensure(ctx, (size_t)out_ch * C + 16);
     bufs[head_w3].ensure(ctx, weights_x3_floats(1, out_ch, C) + 16);
     bufs[head_wd3].ensure(ctx, weights_x3_floats(1, C, out_ch) + 16);

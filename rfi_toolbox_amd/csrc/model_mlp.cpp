@@ -63,18 +63,7 @@ void BoxHeadModel::prepare_shape(int n, int h, int w) {
     size_t red_need = std::max({head_bwd_ws_floats((int64_t)M, feat, out_ch), channel_sum_ws_floats((int64_t)M, feat),
                                 sumsq_ws_doubles((int64_t)n_flat) * 2});
     bufs[ws_red].ensure(ctx, red_need + 16);
-    size_t slab_need = 0;
-    const Shape s = layout_of(n);
-    for (auto& c : convs) {
-        WgradArgs a;
-        a.N = s.N; a.H = s.H; a.W = s.W; a.Hx = s.H; a.Wx = s.W;
-        a.Cx = c.cin; a.Cy = c.cout;
-        a.xop.pstride = a.Cx; a.yop.pstride = a.Cy;
-        a.R = 1; a.S = 1; a.pad = 0;
-        a.tap_stride = (int64_t)a.Cx * a.Cy;
-        a.bf16x3 = true;
-        slab_need = std::max(slab_need, wgrad_slab_floats(a, IMPL_AUTO));
-    }
+    for (auto& c : convs) need_slab(wgrad_same(View{nullptr, c.cin}, InXform{}, nullptr, layout_of(n), 1, 0, c.cin, c.cout, nullptr));
     bufs[ws_slab].ensure(ctx, slab_need + 16);
     pN = n; pH = 1; pW = 1;
 }

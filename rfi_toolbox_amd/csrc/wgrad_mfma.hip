@@ -17,13 +17,6 @@
 
 namespace rfi {
 
-void launch_wgrad_direct(rfi_ctx* ctx, const WgradArgs& a);
-size_t wgrad_direct_slab_floats(const WgradArgs& a);
-// wgrad_split.hip: the 3 x bf16 arithmetic with the operands split once at staging time (3x3 layers)
-bool wgrad_split_eligible(const WgradArgs& a);
-size_t wgrad_split_slab_floats(const WgradArgs& a);
-void launch_wgrad_split(rfi_ctx* ctx, const WgradArgs& a);
-
 namespace {
 
 // 8 floats -> the three bf16 pieces of the 3 x bf16 arithmetic (bf16_mma.hpp): [0] = h, [1] = m, [2] = l
@@ -386,12 +379,6 @@ Plan select(rfi_ctx* ctx, const WgradArgs& a, int what, int cus) {
 #undef RFI_WG
 }
 
-bool wgrad_mfma_eligible(const WgradArgs& a) {
-    if (a.Cx % 4 || a.Cy % 4 || a.xop.pstride % 4 || a.yop.pstride % 4) return false;
-    if ((reinterpret_cast<uintptr_t>(a.xop.p) & 15) || (reinterpret_cast<uintptr_t>(a.yop.p) & 15)) return false;
-    return (a.R == 3 && a.S == 1 && a.pad == 1) || (a.R == 2 && a.S == 2 && a.pad == 0);
-}
-
 Plan dispatch(rfi_ctx* ctx, const WgradArgs& a, int what, int cus) {
     if (a.R == 3) {
         // channel tiles with fewer than 4 blocks split the tile's PIXELS over the waves: give them a
@@ -405,64 +392,17 @@ Plan dispatch(rfi_ctx* ctx, const WgradArgs& a, int what, int cus) {
 
 }  // namespace
 
-size_t wgrad_slab_floats(const WgradArgs& a, int impl) {
-    size_t need = wgrad_direct_slab_floats(a);
-    if ((impl == IMPL_PLANES_X3 || impl == IMPL_PLANES_BF16) && a.R == 3 && a.S == 1)
-        return std::max(need, pwgrad_slab_floats_f32(a));
-    if (impl == IMPL_MFMA_BF16 || impl == IMPL_MFMA_BF16X3) impl = IMPL_MFMA;
-    if (impl != IMPL_DIRECT && wgrad_split_eligible(a)) need = std::max(need, wgrad_split_slab_floats(a));
-    if (impl != IMPL_DIRECT) need = std::max(need, wgrad_ws_slab_floats(a));      // (the transposed conv's shape: its own plan)
-    if (impl != IMPL_DIRECT && wgrad_mfma_eligible(a)) {
-        const Plan p = dispatch(nullptr, a, SEL_PLAN, 256);
-        // plan with the largest CU count we may meet so the workspace always suffices
-        const size_t m = (size_t)p.nsplit * p.wp * p.slab_stride;
-        if (m > need) need = m;
-    }
-    return need;
+bool wgrad_mfma_eligible(const WgradArgs& a) {
+    if (a.Cx % 4 || a.Cy % 4 || a.xop.pstride % 4 || a.yop.pstride % 4) return false;
+    if ((reinterpret_cast<uintptr_t>(a.xop.p) & 15) || (reinterpret_cast<uintptr_t>(a.yop.p) & 15)) return false;
+    return (a.R == 3 && a.S == 1 && a.pad == 1) || (a.R == 2 && a.S == 2 && a.pad == 0);
 }
 
-void launch_wgrad(rfi_ctx* ctx, const WgradArgs& a_in, int impl) {
-    WgradArgs a = a_in;
-    if (impl == IMPL_PLANES_X3 || impl == IMPL_PLANES_BF16) {      // plane kernel through temporary plane copies
-        RFI_REQUIRE(a.R == 3 && a.S == 1, "wgrad: the plane kernel covers 3x3 stride-1 convolutions");
-        launch_pwgrad_from_f32(ctx, a, impl == IMPL_PLANES_X3 ? 3 : 1);
-        return;
-    }
-    if (impl == IMPL_MFMA_BF16) {
-        a.bf16 = true;
-        impl = IMPL_MFMA;
-    }
-    if (impl == IMPL_MFMA_BF16X3) {
-        a.bf16x3 = true;
-        impl = IMPL_MFMA;
-    }
-    RFI_REQUIRE(a.N > 0 && a.H > 0 && a.W > 0 && a.Cx > 0 && a.Cy > 0, "wgrad: empty shape");
-    RFI_REQUIRE((int64_t)a.N * a.Hx * a.Wx * a.xop.pstride < (int64_t)1 << 31 &&
-                    (int64_t)a.N * a.H * a.W * a.yop.pstride < (int64_t)1 << 31,
-                "wgrad: tensor too large for 32-bit element offsets");
-    const bool ok = wgrad_mfma_eligible(a) || ((a.bf16 || a.bf16x3) && wgrad_split_eligible(a));
-    if (impl == IMPL_MFMA) RFI_REQUIRE(ok, "wgrad: shape/alignment not eligible for the MFMA kernel");
-    if (impl == IMPL_DIRECT || !ok) {
-        launch_wgrad_direct(ctx, a);
-        return;
-    }
-    if (a.bf16x3 && wgrad_stem_eligible(a)) {
-        launch_wgrad_stem(ctx, a);    // Cx = 4: (tap, channel) packed into the GEMM's N (wgrad_stem.hip)
-        return;
-    }
-    if ((a.bf16x3 || a.bf16) && wgrad_ws_eligible(a) && (wgrad_split_eligible(a) || (a.R == 2 && a.S == 2))) {
-        launch_wgrad_ws(ctx, a);      // (its slab plan -- 256 workgroups -- fits inside wgrad_split's, which sized the workspace)
-        return;
-    }
-    // R = 2 / S = 1 and R = 1 (ResNet-style encoder) exist only in the split-at-staging kernel (P = 1: bf16 mode)
-    const bool only_split = (a.R == 2 && a.S == 1) || a.R == 1;
-    if (only_split) RFI_REQUIRE((a.bf16 || a.bf16x3) && wgrad_split_eligible(a),
-                                "wgrad: 2x2 stride-1 and 1x1 weight gradients need the bf16 or 3 x bf16 arithmetic and 4-channel alignment");
-    if ((a.bf16x3 || only_split) && wgrad_split_eligible(a)) {
-        launch_wgrad_split(ctx, a);
-        return;
-    }
-    dispatch(ctx, a, SEL_LAUNCH, 256);   // MI355X: 256 CUs (the plan fixes the slab workspace size)
+// planned for 256 CUs (the MI355X): the plan fixes the slab workspace size
+size_t wgrad_mfma_slab_floats(const WgradArgs& a) {
+    const Plan p = dispatch(nullptr, a, SEL_PLAN, 256);
+    return (size_t)p.nsplit * p.wp * p.slab_stride;
 }
+void launch_wgrad_mfma(rfi_ctx* ctx, const WgradArgs& a) { dispatch(ctx, a, SEL_LAUNCH, 256); }
 
 }  // namespace rfi

@@ -472,14 +472,16 @@ void launch_cfg(rfi_ctx* ctx, const WgradArgs& a) {
     launch_reduce_slabs(ctx, a.slab, p.nsplit, p.slab_stride, a.dw);
 }
 
+// plan_only != null (here and in select_t2): nothing is launched, the chosen configuration's slab plan is returned there
 template <int R>
-void select(rfi_ctx* ctx, const WgradArgs& a) {
+void select(rfi_ctx* ctx, const WgradArgs& a, Plan* plan_only) {
     const bool y2 = a.Cy > 32, x2 = a.Cx > 32;
     const bool p1 = a.bf16 && !a.bf16x3;
     // XM = 1 (compile-time transform) for the case that carries the U-Net: 3x3, Xop behind BatchNorm + ReLU, Yop plain
     const bool xm1 = R == 3 && a.xf_x.scale && a.xf_x.relu == 1 && a.xf_x.slope == 0.0f && !a.xf_y.scale;
 #define RFI_WW(BYB_, BXB_, TH_, TW_)                                                \
     do {                                                                            \
+        if (plan_only) { *plan_only = plan_cfg<R, BYB_, BXB_, TH_, TW_>(a); return; } \
         if constexpr (R == 3) {                                                     \
             if (xm1) {                                                              \
                 if (p1) launch_cfg<R, BYB_, BXB_, TH_, TW_, 1, 1>(ctx, a);          \
@@ -494,6 +496,7 @@ void select(rfi_ctx* ctx, const WgradArgs& a) {
     if constexpr (R == 1) {
         // one tap: producer-bound (header) -- eight producer waves where both operands have 64-channel tiles
         if (y2 && x2) {
+            if (plan_only) { *plan_only = plan_cfg<1, 2, 2, 8, 8>(a); return; }
             if (p1) launch_cfg<1, 2, 2, 8, 8, 1, 2, 1, 8>(ctx, a);
             else launch_cfg<1, 2, 2, 8, 8, 3, 2, 1, 8>(ctx, a);
             return;
@@ -526,6 +529,12 @@ void select_t2(rfi_ctx* ctx, const WgradArgs& a, Plan* plan_only) {
     RFI_WT(1, 1, 8, 8);
 #undef RFI_WT
 }
+void select_any(rfi_ctx* ctx, const WgradArgs& a, Plan* plan_only) {
+    if (a.R == 3) select<3>(ctx, a, plan_only);
+    else if (a.R == 2 && a.S == 2) select_t2(ctx, a, plan_only);
+    else if (a.R == 2) select<2>(ctx, a, plan_only);
+    else select<1>(ctx, a, plan_only);
+}
 
 }  // namespace
 
@@ -542,19 +551,14 @@ bool wgrad_ws_eligible(const WgradArgs& a) {
     if (a.S != 1) return false;
     return (a.R == 3 && a.pad == 1) || (a.R == 2 && a.pad == 1) || (a.R == 1 && a.pad == 0);
 }
-// slab workspace of the shapes no other kernel's plan covers (launch_wgrad sizes the others by wgrad_split's plan)
 size_t wgrad_ws_slab_floats(const WgradArgs& a) {
-    if (!(a.R == 2 && a.S == 2) || !wgrad_ws_eligible(a)) return 0;
     Plan p{0, 0};
-    select_t2(nullptr, a, &p);
+    select_any(nullptr, a, &p);
     return (size_t)p.nsplit * p.slab_stride;
 }
 void launch_wgrad_ws(rfi_ctx* ctx, const WgradArgs& a) {
     RFI_REQUIRE(wgrad_ws_eligible(a) && (a.bf16 || a.bf16x3), "wgrad_ws: shape or arithmetic not eligible");
-    if (a.R == 3) select<3>(ctx, a);
-    else if (a.R == 2 && a.S == 2) select_t2(ctx, a, nullptr);
-    else if (a.R == 2) select<2>(ctx, a);
-    else select<1>(ctx, a);
+    select_any(ctx, a, nullptr);
 }
 
 }  // namespace rfi

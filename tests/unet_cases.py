@@ -247,7 +247,7 @@ def ws_map_ok(h, w):                  # conv_ws_eligible: maps of at least 8 x 8
 
 
 def conv_fwd_path(L):
-    """kernel of a 3x3 forward conv in the default arithmetic: launch_conv's order of preference"""
+    """kernel of a 3x3 forward conv in the default arithmetic: choose_conv's order of preference (csrc/dispatch.cpp)"""
     if stem_eligible(L):
         return "conv_stem"
     if L["cin_p"] % 16 == 0 and ws_map_ok(L["h"], L["w"]):
@@ -267,7 +267,7 @@ def conv_dgrad_path(L):
 
 
 def conv_wgrad_path(L):
-    """... of its weight gradient (launch_wgrad).  The stem kernel also asks for a slab workspace of 64 x 9 x 4 x cout
+    """... of its weight gradient (choose_wgrad).  The stem kernel also asks for a slab workspace of 64 x 9 x 4 x cout
     floats; prepare_shape sizes the workspace by the largest split plan over all layers, which exceeds that for every
     case here (the second conv of level 1 alone: min(512, tiles) x 9 x 32 x 32)."""
     if stem_eligible(L):
