@@ -16,7 +16,8 @@ struct DevBuf {
 struct PlaneBuf {
     rfi_ctx* ctx = nullptr;
     bf16_t* p = nullptr;
-    size_t elems = 0;
+    size_t elems = 0;                 // allocated (the largest shape so far)
+    size_t used = 0;                  // of the shape in use: the kernels expect 64 zero bytes behind them
     int64_t pstride = 0;
     int nchunks = 0;
     void ensure(rfi_ctx* c, int64_t pixels, int C, int P);

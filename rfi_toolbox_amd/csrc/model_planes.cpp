@@ -26,19 +26,25 @@ void PlaneBuf::ensure(rfi_ctx* c, int64_t pixels, int C, int P) {
     const size_t need = plane_elems(pixels, C, P);
     nchunks = plane_chunks(C);
     pstride = (int64_t)nchunks * P * 16;
-    if (need <= elems && p) return;
+    if (need <= elems && p) {
+        // a smaller shape in the allocation of a larger one: the zero area the kernels look for lies behind the tensor of THIS
+        // shape (launch_pconv: x_zero = pixels * pstride * 2 bytes), where the larger shape left activations
+        if (need != used && need < elems) RFI_CHECK_HIP(hipMemsetAsync(p + need, 0, 64, c->stream));
+        used = need;
+        return;
+    }
     if (p) c->release(p);
     ctx = c;
     p = static_cast<bf16_t*>(c->alloc(need * 2 + 64));
     // zero once: channel padding is never written by the BatchNorm-backward producer, and the 64-byte tail is
     // where the LDS-DMA of out-of-image halo pixels points
     RFI_CHECK_HIP(hipMemsetAsync(p, 0, need * 2 + 64, c->stream));
-    elems = need;
+    elems = used = need;
 }
 void PlaneBuf::free() {
     if (p && ctx) ctx->release(p);
     p = nullptr;
-    elems = 0;
+    elems = used = 0;
 }
 
 }  // namespace rfi
