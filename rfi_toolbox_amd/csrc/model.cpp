@@ -44,11 +44,9 @@ rfi_model::~rfi_model() {
     ctx->activate();
     for (auto& b : bufs) b.free();
     if (ws_pool) ctx->release(ws_pool);
-    if (ws_descs) ctx->release(ws_descs);
     for (float* p : {params, grads, adam_m, adam_v, chan_pool, wd_pool, w3_pool, grad_acc})
         if (p) ctx->release(p);
-    if (relayout_descs) ctx->release(relayout_descs);
-    if (x3_descs) ctx->release(x3_descs);
+    for (BatchTable* t : {&ws, &relayout, &x3}) t->release(ctx);
     if (d_sums) ctx->release(d_sums);
     if (d_scalars) ctx->release(d_scalars);
     if (wd_ready) (void)hipEventDestroy(wd_ready);
@@ -59,8 +57,9 @@ UNetModel::~UNetModel() {
     if (!ctx) return;
     ctx->activate();
     for (auto& b : pl) b.free();
-    for (void* p : {(void*)wb_pool, wb_descs, (void*)dbias_pool, dbias_descs, (void*)rs_wpool, (void*)rs_cls_pool})
+    for (void* p : {(void*)wb_pool, (void*)dbias_pool, dbias_descs, (void*)rs_wpool, (void*)rs_cls_pool})
         if (p) ctx->release(p);
+    wb.release(ctx);
 }
 
 // ------------------------------------------------------------------------------------ build
@@ -114,9 +113,9 @@ void UNetModel::set_planes(int P) {
     RFI_CHECK_HIP(hipStreamSynchronize(ctx->side_stream));
     for (auto& b : pl) b.free();                  // tensors and filter copies of the other P
     if (wb_pool) { ctx->release(wb_pool); wb_pool = nullptr; }
-    if (wb_descs) { ctx->release(wb_descs); wb_descs = nullptr; }
+    wb.release(ctx);
     planesP = P;
-    wd_dirty = true;
+    stale |= WEIGHT_DERIVED;                      // (another data flow reads other copies: every one is rebuilt)
     pN = 0;                                       // (prepare() again: the two flows of the ResNet-encoder model own different tensors)
 }
 
@@ -262,142 +261,152 @@ void UNetModel::prepare_shape(int n, int h, int w) {
     pN = n; pH = h; pW = w;
 }
 
-// the main stream waits for the side stream's rebuild of the input-gradient-direction filter copies (refresh_dgrad_weights)
+// ------------------------------------------------------------------------------------ derived filter copies
+// the main stream waits for the side stream's half of a split rebuild
 void rfi_model::wait_wd() {
-    side_rebuild_wd();
     if (!wd_pending) return;
     RFI_CHECK_HIP(hipStreamWaitEvent(ctx->main_stream, wd_ready, 0));
     wd_pending = false;
 }
 
-// the side-stream half of the split rebuild: dgrad layout + its B-operand images.  Started by forward() AFTER the first
-// conv is enqueued (the stem is bound by its HBM writes: next to it the rebuild slowed it from 33 to 62 us; the convs that
-// follow are matrix-bound) -- or by whoever needs the copies first (wait_wd)
+// the side-stream half of the split rebuild, where sync_filters left it: dgrad layout + its B-operand images.  Called by the
+// forward pass AFTER the first conv is enqueued (the stem is bound by its HBM writes: next to it the rebuild slowed it
+// from 33 to 62 us; the convs that follow are matrix-bound)
 void rfi_model::side_rebuild_wd() {
-    if (!wd_side_todo) return;
-    wd_side_todo = false;
+    if (!(stale & INPUT_GRAD_HALF)) return;
     if (!wd_ready) RFI_CHECK_HIP(hipEventCreateWithFlags(&wd_ready, hipEventDisableTiming));
     // the side stream waits for everything on main so far (the optimiser step); no end(): wd_ready marks this work, and the
     // scope puts the context's stream back
     SideScope side(this);
-    launch_weight_to_dgrad_batched(ctx, static_cast<const RelayoutDesc*>(relayout_descs), relayout_n, params,
-                                   wd_pool, relayout_bytes, relayout_tiles);
-    if (planesP) refresh_model_weights(2);
-    else refresh_ws_weights(ws_need(), 2);
+    rebuild_dgrad();
+    refresh_ws_weights(Half::InputGrad);
+    refresh_model_weights(Half::InputGrad);
     RFI_CHECK_HIP(hipEventRecord(wd_ready, ctx->side_stream));
     wd_pending = true;
+    stale &= ~INPUT_GRAD_HALF;
 }
 
-void rfi_model::refresh_dgrad_weights() {
-    if (!wd_dirty && (!use_w3() || x3_fresh) && ws_P == ws_need()) return;
-    if (!relayout_descs) {          // one descriptor per conv-like layer, built once
+void rfi_model::sync_filters(Half needed) {
+    if (ws_P != ws_need()) stale |= WEIGHT_DERIVED;     // the images are another arithmetic's: its pool replaces them, every copy follows
+    unsigned due = stale & (use_w3() ? WEIGHT_DERIVED : WEIGHT_DERIVED & ~RECORDS);
+    if (!due) return;
+    // Split rebuild (wd_split_ok): the forward pass needs the forward-direction copies only, so the dgrad layout and its
+    // B-operand images are rebuilt on the SIDE stream (idle during the forward pass) under the first convs: their bits stay
+    // set for side_rebuild_wd, and backward() waits for them (wait_wd).  The split decides before anything is rebuilt
+    if (needed == Half::Forward && ctx->overlap && !ctx->profiling && ctx->stream == ctx->main_stream && wd_split_ok())
+        due &= ~INPUT_GRAD_HALF;
+    else
+        wait_wd();                    // (an earlier side-stream half may still be writing what is rebuilt here)
+    if (due & DGRAD) rebuild_dgrad();
+    if (due & (IMAGES_FWD | IMAGES_BWD)) refresh_ws_weights(half_of(due, IMAGES_FWD, IMAGES_BWD));
+    if (due & RECORDS) rebuild_records();
+    if (due & (MODEL_FWD | MODEL_BWD)) refresh_model_weights(half_of(due, MODEL_FWD, MODEL_BWD));
+    stale &= ~due;
+}
+
+void rfi_model::rebuild_dgrad() {
+    if (!relayout.descs) {
         std::vector<RelayoutDesc> h;
-        relayout_bytes = 0;
         for (auto& c : convs) {
             h.push_back({(int64_t)c.w_off, (int64_t)(c.wd - wd_pool), c.R * c.R, c.cout, c.cin_p, 1});
-            relayout_bytes += 8.0 * c.R * c.R * c.cout * c.cin_p;
+            relayout.bytes += 8.0 * c.R * c.R * c.cout * c.cin_p;
         }
         for (auto& u : ups) {
             h.push_back({(int64_t)u.w_off, (int64_t)(u.wd - wd_pool), 4, u.cout, u.cin, 0});
-            relayout_bytes += 8.0 * 4 * u.cout * u.cin;
+            relayout.bytes += 8.0 * 4 * u.cout * u.cin;
         }
-        relayout_n = (int)h.size();
-        relayout_tiles = relayout_assign_tiles(h.data(), relayout_n);
-        relayout_descs = ctx->upload_table(h.data(), h.size() * sizeof(RelayoutDesc));
+        relayout.n = (int)h.size();
+        relayout_tiles = relayout_assign_tiles(h.data(), relayout.n);
+        relayout.descs = ctx->upload_table(h.data(), h.size() * sizeof(RelayoutDesc));
     }
-    // Split rebuild (wd_split_ok): the forward pass needs the forward-direction copies only, so the dgrad layout and its
-    // B-operand images are rebuilt on the SIDE stream (idle during the forward pass) under the first convs; backward() waits
-    // for them (wait_wd)
-    const bool split = ctx->overlap && !ctx->profiling && ctx->stream == ctx->main_stream && wd_split_ok();
-    if (split) {
-        wd_side_todo = true;                      // (forward() starts it behind the first conv: side_rebuild_wd)
-    } else {
-        wait_wd();
-        launch_weight_to_dgrad_batched(ctx, static_cast<const RelayoutDesc*>(relayout_descs), relayout_n, params,
-                                       wd_pool, relayout_bytes, relayout_tiles);
+    launch_weight_to_dgrad_batched(ctx, static_cast<const RelayoutDesc*>(relayout.descs), relayout.n, params, wd_pool,
+                                   relayout.bytes, relayout_tiles);
+}
+
+// pre-split records of both layouts of the conv-like layers (the round-2 kernels read them as is)
+void rfi_model::rebuild_records() {
+    if (!w3_pool) {
+        size_t need = 0;
+        for (auto& c : convs) need += weights_x3_floats(c.R * c.R, c.cout, c.cin_p) + weights_x3_floats(c.R * c.R, c.cin_p, c.cout);
+        for (auto& u : ups) need += 2 * weights_x3_floats(4, u.cout, u.cin) + weights_x3_floats(4, u.cin, u.cout);
+        w3_pool = static_cast<float*>(ctx->alloc((need + 64) * sizeof(float)));
+        size_t o = 0;
+        for (auto& c : convs) {
+            c.w3 = w3_pool + o; o += weights_x3_floats(c.R * c.R, c.cout, c.cin_p);
+            c.wd3 = w3_pool + o; o += weights_x3_floats(c.R * c.R, c.cin_p, c.cout);
+        }
+        for (auto& u : ups) {
+            u.w3 = w3_pool + o; o += weights_x3_floats(4, u.cout, u.cin);
+            u.wd3 = w3_pool + o; o += weights_x3_floats(4, u.cin, u.cout);
+        }
     }
-    refresh_ws_weights(ws_need(), split ? 1 : 0);
-    if (use_w3()) {       // pre-split records of both layouts of the conv-like layers (the round-2 kernels read them as is)
-        if (!w3_pool) {
-            size_t need = 0;
-            for (auto& c : convs) need += weights_x3_floats(c.R * c.R, c.cout, c.cin_p) + weights_x3_floats(c.R * c.R, c.cin_p, c.cout);
-            for (auto& u : ups) need += 2 * weights_x3_floats(4, u.cout, u.cin) + weights_x3_floats(4, u.cin, u.cout);
-            w3_pool = static_cast<float*>(ctx->alloc((need + 64) * sizeof(float)));
-            size_t o = 0;
-            for (auto& c : convs) {
-                c.w3 = w3_pool + o; o += weights_x3_floats(c.R * c.R, c.cout, c.cin_p);
-                c.wd3 = w3_pool + o; o += weights_x3_floats(c.R * c.R, c.cin_p, c.cout);
-            }
-            for (auto& u : ups) {
-                u.w3 = w3_pool + o; o += weights_x3_floats(4, u.cout, u.cin);
-                u.wd3 = w3_pool + o; o += weights_x3_floats(4, u.cin, u.cout);
-            }
+    // layers whose filters the wave-specialised kernels read (ws_by_w) need no records: launch_conv drops
+    // ConvArgs::w3 for them, and a shape those kernels decline (maps under 8 x 8) gets a temporary split copy
+    const RecordKey key{ws_P, pH * 65536 + pW};
+    if (x3.descs && !(x3_key == key)) x3.release(ctx);
+    if (!x3.descs) {
+        x3_key = key;
+        std::vector<X3Desc> h;
+        const bool skip_ws = x3_skips_ws_layers && ws_P == 3;
+        x3_reads_wd = false;
+        x3_skipped.clear();
+        // a layer is left out only if the wave-specialised kernels cannot decline it at the prepared shape: its maps are at
+        // least 8 x 8 (conv_ws_eligible) -- a declined launch on a missing record would allocate a temporary copy and
+        // synchronise the stream inside launch_conv.  (pH == 0: nothing prepared yet, keep everything)
+        auto add = [&](const float* src, float* dst, int taps, int cout, int cin, int level = 0) {
+            const bool small_map = pH == 0 || (level > 0 && ((pH >> (level - 1)) < 8 || (pW >> (level - 1)) < 8));
+            if (skip_ws && ws_by_w.count(src) && !small_map) { x3_skipped.insert(src); return; }
+            if (src < params || src >= params + n_flat) x3_reads_wd = true;
+            h.push_back(X3Desc{src, dst, (int64_t)taps * cout, cin, (cin + 15) / 16});
+            x3.bytes += (double)taps * cout * cin * 4 + (double)weights_x3_floats(taps, cout, cin) * 4;
+        };
+        for (auto& c : convs) {
+            add(params + c.w_off, c.w3, c.R * c.R, c.cout, c.cin_p, c.level);
+            add(c.wd, c.wd3, c.R * c.R, c.cin_p, c.cout, c.level);
         }
-        // layers whose filters the wave-specialised kernels read (ws_by_w) need no records: launch_conv drops
-        // ConvArgs::w3 for them, and a shape those kernels decline (maps under 8 x 8) gets a temporary split copy
-        if (x3_descs && (x3_for_ws_P != ws_P || x3_for_shape != pH * 65536 + pW)) {
-            ctx->release(x3_descs);
-            x3_descs = nullptr;
+        for (auto& u : ups) {
+            add(params + u.w_off, u.w3, 4, u.cout, u.cin);
+            add(u.wd, u.wd3, 4, u.cin, u.cout);
         }
-        if (!x3_descs) {
-            x3_for_ws_P = ws_P;
-            x3_bytes = 0;
-            std::vector<X3Desc> h;
-            const bool skip_ws = x3_skips_ws_layers && ws_P == 3;
-            x3_reads_wd = false;
-            x3_skipped.clear();
-            // a layer is left out only if the wave-specialised kernels cannot decline it at the prepared shape: its maps are at
-            // least 8 x 8 (conv_ws_eligible) -- a declined launch on a missing record would allocate a temporary copy and
-            // synchronise the stream inside launch_conv.  (pH == 0: nothing prepared yet, keep everything)
-            auto add = [&](const float* src, float* dst, int taps, int cout, int cin, int level = 0) {
-                const bool small_map = pH == 0 || (level > 0 && ((pH >> (level - 1)) < 8 || (pW >> (level - 1)) < 8));
-                if (skip_ws && ws_by_w.count(src) && !small_map) { x3_skipped.insert(src); return; }
-                if (src < params || src >= params + n_flat) x3_reads_wd = true;
-                h.push_back(X3Desc{src, dst, (int64_t)taps * cout, cin, (cin + 15) / 16});
-                x3_bytes += (double)taps * cout * cin * 4 + (double)weights_x3_floats(taps, cout, cin) * 4;
-            };
-            for (auto& c : convs) {
-                add(params + c.w_off, c.w3, c.R * c.R, c.cout, c.cin_p, c.level);
-                add(c.wd, c.wd3, c.R * c.R, c.cin_p, c.cout, c.level);
-            }
-            for (auto& u : ups) {
-                add(params + u.w_off, u.w3, 4, u.cout, u.cin);
-                add(u.wd, u.wd3, 4, u.cin, u.cout);
-            }
-            x3_for_shape = pH * 65536 + pW;
-            x3_n = (int)h.size();
-            x3_descs = ctx->upload_table(h.data(), h.size() * sizeof(X3Desc));
-        }
-        if (x3_n) launch_weights_to_x3_batched(ctx, static_cast<const X3Desc*>(x3_descs), x3_n, x3_bytes);
-        x3_fresh = true;
+        x3.n = (int)h.size();
+        x3.descs = ctx->upload_table(h.data(), h.size() * sizeof(X3Desc));
     }
-    refresh_model_weights(split ? 1 : 0);
-    wd_dirty = false;
+    if (x3.n) launch_weights_to_x3_batched(ctx, static_cast<const X3Desc*>(x3.descs), x3.n, x3.bytes);
+}
+
+// 2 x 2 form of a stride-2 3x3 filter on the space-to-depth input, its dgrad layout and (3 x bf16 arithmetic) the records of both
+void rfi_model::refresh_s2d_forms(ConvBN& c) {
+    launch_w_s2d(ctx, params + c.w_off, c.cout, c.cin, c.ws2d, true);
+    launch_weight_to_dgrad(ctx, c.ws2d, 4, c.cout, 4 * c.cin, 1, c.wds2d);
+    if (use_w3()) {
+        launch_weights_to_x3(ctx, c.ws2d, 4, c.cout, 4 * c.cin, c.ws2d3);
+        launch_weights_to_x3(ctx, c.wds2d, 4, 4 * c.cin, c.cout, c.wds2d3);
+    }
 }
 
 // plain U-Net, float32 tensors: when the wave-specialised copies of both directions are in use (and the pre-split records
 // do not read the dgrad layouts).  The plane flows: the forward pass reads the forward-direction images only, nothing but
 // the input-gradient kernels reads the dgrad layouts -- unless pre-split records of them are in use
 bool UNetModel::wd_split_ok() const {
-    if (planesP) return wb_pool && wb_n_fwd > 0 && !use_w3() && training;
-    return !resnet_encoder && ws_need() != 0 && ws_pool && ws_P == ws_need() && ws_n_fwd > 0 &&
-           (!use_w3() || (x3_descs && !x3_reads_wd && x3_for_ws_P == ws_P));
+    if (planesP) return wb_pool && wb.n_fwd > 0 && !use_w3() && training;
+    return !resnet_encoder && ws_need() != 0 && ws_pool && ws_P == ws_need() && ws.n_fwd > 0 &&
+           (!use_w3() || (x3.descs && !x3_reads_wd && x3_key.ws_P == ws_P));
 }
 
-void UNetModel::refresh_model_weights(int which) {
-    if (planesP) refresh_plane_weights(which);                   // B-operand-order filters of the plane kernels
+void UNetModel::refresh_model_weights(Half half) {
+    if (planesP) refresh_plane_weights(half);                    // B-operand-order filters of the plane kernels
     else if (resnet_encoder) refresh_resnet_weights();           // 2x2 forms of the stride-2 filters
 }
 
 // filters of every 3x3 stride-1 layer in MFMA B-operand order with three planes (conv_ws.hip), both directions, rebuilt
 // with the other derived copies after each optimiser step by ONE batched launch.  Callers find them by the layer's
 // float32 filter pointer (set_filters -> ws_set looks up ConvArgs::w)
-void rfi_model::refresh_ws_weights(int P, int which) {
+void rfi_model::refresh_ws_weights(Half half) {
+    const int P = ws_need();
     if (P != ws_P) {                  // another arithmetic: its copies have another size
         if (ws_pool) { ctx->release(ws_pool); ws_pool = nullptr; }
-        if (ws_descs) { ctx->release(ws_descs); ws_descs = nullptr; }
+        ws.release(ctx);
         ws_by_w.clear();
-        ws_n = ws_n_fwd = 0;
         ws_P = P;
     }
     if (P == 0) return;
@@ -420,63 +429,42 @@ void rfi_model::refresh_ws_weights(int P, int which) {
         ws_pool = static_cast<bf16_t*>(ctx->alloc(need * 2));
         RFI_CHECK_HIP(hipMemsetAsync(ws_pool, 0, need * 2, ctx->stream));
         // forward-direction images first (sources in `params`), then the input-gradient direction (sources in wd_pool): the
-        // two halves can be rebuilt by separate launches (refresh_dgrad_weights puts the second on the side stream)
+        // two halves can be rebuilt by separate launches (a split rebuild puts the second on the side stream)
         std::vector<WBDesc> hd, hdg;
         size_t o = 0;
-        ws_bytes = ws_bytes_fwd = 0;
+        double bytes_bwd = 0;
+        // the image of `taps` filters [cout][cin] at `src`: the next region of the pool (+ its 32-element tail), one descriptor
+        auto image = [&](std::vector<WBDesc>& table, double& bytes, const float* src, int taps, int cout, int cin) {
+            bf16_t* dst = ws_pool + o;
+            const size_t e = wb_elems(taps, cout, cin, 0, P);
+            o += e + 32;
+            table.push_back(WBDesc{src, dst, taps, cout, cin, {cin, 0}, P});
+            ws_by_w[src] = dst;
+            bytes += 2.0 * e + 4.0 * taps * cout * cin;
+            return dst;
+        };
         for (ConvBN& c : convs) {
-            if (conv_f(c)) {
-                c.ws3f = ws_pool + o;
-                const size_t e = wb_elems(9, c.cout, c.cin_p, 0, P);
-                o += e + 32;
-                hd.push_back(WBDesc{params + c.w_off, c.ws3f, 9, c.cout, c.cin_p, {c.cin_p, 0}, P});
-                ws_by_w[params + c.w_off] = c.ws3f;
-                ws_bytes_fwd += 2.0 * e + 4.0 * 9 * c.cin_p * c.cout;
-            }
-            if (conv_d(c)) {
-                c.ws3d = ws_pool + o;
-                const size_t e = wb_elems(9, c.cin_p, c.cout, 0, P);
-                o += e + 32;
-                hdg.push_back(WBDesc{c.wd, c.ws3d, 9, c.cin_p, c.cout, {c.cout, 0}, P});
-                ws_by_w[c.wd] = c.ws3d;
-                ws_bytes += 2.0 * e + 4.0 * 9 * c.cin_p * c.cout;
-            }
+            if (conv_f(c)) c.ws3f = image(hd, ws.bytes_fwd, params + c.w_off, 9, c.cout, c.cin_p);
+            if (conv_d(c)) c.ws3d = image(hdg, bytes_bwd, c.wd, 9, c.cin_p, c.cout);
             if (one_ok(c)) {
-                const size_t ef = wb_elems(1, c.cout, c.cin_p, 0, P), ed = wb_elems(1, c.cin_p, c.cout, 0, P);
-                hd.push_back(WBDesc{params + c.w_off, ws_pool + o, 1, c.cout, c.cin_p, {c.cin_p, 0}, P});
-                ws_by_w[params + c.w_off] = ws_pool + o;
-                o += ef + 32;
-                hdg.push_back(WBDesc{c.wd, ws_pool + o, 1, c.cin_p, c.cout, {c.cout, 0}, P});
-                ws_by_w[c.wd] = ws_pool + o;
-                o += ed + 32;
-                ws_bytes_fwd += 2.0 * ef + 4.0 * c.cin_p * c.cout;
-                ws_bytes += 2.0 * ed + 4.0 * c.cin_p * c.cout;
+                image(hd, ws.bytes_fwd, params + c.w_off, 1, c.cout, c.cin_p);
+                image(hdg, bytes_bwd, c.wd, 1, c.cin_p, c.cout);
             }
         }
         // transposed convs (gemm_ws.hip): forward = ONE tap of 4 cout channels ([4][cout][cin] IS [4 cout][cin]); input
         // gradient = four taps of [cin][cout]
         for (UpConv& u : ups) {
             if (!up_ok(u)) continue;
-            const size_t ef = wb_elems(1, 4 * u.cout, u.cin, 0, P), ed = wb_elems(4, u.cin, u.cout, 0, P);
-            hd.push_back(WBDesc{params + u.w_off, ws_pool + o, 1, 4 * u.cout, u.cin, {u.cin, 0}, P});
-            ws_by_w[params + u.w_off] = ws_pool + o;
-            o += ef + 32;
-            hdg.push_back(WBDesc{u.wd, ws_pool + o, 4, u.cin, u.cout, {u.cout, 0}, P});
-            ws_by_w[u.wd] = ws_pool + o;
-            o += ed + 32;
-            ws_bytes_fwd += 2.0 * ef + 4.0 * 4 * u.cin * u.cout;
-            ws_bytes += 2.0 * ed + 4.0 * 4 * u.cin * u.cout;
+            image(hd, ws.bytes_fwd, params + u.w_off, 1, 4 * u.cout, u.cin);
+            image(hdg, bytes_bwd, u.wd, 4, u.cin, u.cout);
         }
-        ws_n_fwd = (int)hd.size();
-        ws_bytes += ws_bytes_fwd;
+        ws.n_fwd = (int)hd.size();
+        ws.bytes = ws.bytes_fwd + bytes_bwd;
         hd.insert(hd.end(), hdg.begin(), hdg.end());
-        ws_n = (int)hd.size();
-        ws_descs = ctx->upload_table(hd.data(), hd.size() * sizeof(WBDesc));
+        ws.n = (int)hd.size();
+        ws.descs = ctx->upload_table(hd.data(), hd.size() * sizeof(WBDesc));
     }
-    const WBDesc* descs = static_cast<const WBDesc*>(ws_descs);
-    if (which == 0 && ws_n) launch_weights_to_wb(ctx, descs, ws_n, ws_bytes);
-    if (which == 1 && ws_n_fwd) launch_weights_to_wb(ctx, descs, ws_n_fwd, ws_bytes_fwd);
-    if (which == 2 && ws_n > ws_n_fwd) launch_weights_to_wb(ctx, descs + ws_n_fwd, ws_n - ws_n_fwd, ws_bytes - ws_bytes_fwd);
+    ws.launch(ctx, half);
 }
 
 // ------------------------------------------------------------------------------------ shared launches
@@ -591,7 +579,8 @@ rfi::View rfi_model::network_input(const float* x_dev, int n, int h, int w) {
 
 void rfi_model::forward(const float* x_dev, int n, int h, int w, bool train_mode) {
     prepare(n, h, w);
-    refresh_dgrad_weights();          // derived filter copies (dgrad layout, 3 x bf16 records) follow the parameters
+    if (model_copies_every_pass) stale |= MODEL_FWD | MODEL_BWD;
+    sync_filters(Half::Forward);      // the derived filter copies follow the parameters
     forward_pass(x_dev, n, h, w, train_mode);
 }
 
@@ -829,14 +818,14 @@ void rfi_model::wgrad_on_side(const rfi::WgradArgs& wa, hipEvent_t after, bool a
 
 void rfi_model::backward(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w) {
     join_pending_side();
+    sync_filters(Half::Both);         // (the weights may have changed since the forward pass)
+    wait_wd();                        // the input-gradient-direction copies of a split rebuild come from the side stream
     backward_pass(x_dev, labels_dev, n, h, w);
 }
 
 void UNetModel::backward_pass(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w) {
     const int D = depth, IB = i_bott;
     const int64_t M1 = (int64_t)n * h * w;
-    refresh_dgrad_weights();
-    wait_wd();                        // (the input-gradient-direction filter copies were rebuilt on the side stream)
     if (planesP) return backward_planes(x_dev, labels_dev, n, h, w);
     side_bound = resnet_encoder ? 2 : 0;          // (the ResNet-style encoder double-buffers by block parity: bound 2)
     dbias_deferred = !resnet_encoder && dbias_pool && !ctx->exchange_active();
@@ -948,8 +937,7 @@ void rfi_model::apply(const rfi_hyper& hp, float grad_scale) {
     a.sumsq = d_sums + 4;
     a.norm_out = d_scalars + 1;
     launch_adam(ctx, a);
-    wd_dirty = true;
-    x3_fresh = false;
+    weights_changed();
 }
 
 // ------------------------------------------------------------------------------------ entry-point hooks

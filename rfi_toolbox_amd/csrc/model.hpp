@@ -1,6 +1,6 @@
 // The networks of the library (one class per network) on top of the HIP kernels (host orchestration).
 #pragma once
-#include "planes.hpp"
+#include "derived.hpp"
 
 namespace rfi {
 
@@ -156,10 +156,8 @@ struct rfi_model {
     float* chan_pool = nullptr;
     float* wd_pool = nullptr;
     float* w3_pool = nullptr;         // pre-split (3 x bf16) filter records, rebuilt with the dgrad layouts
-    rfi::bf16_t* ws_pool = nullptr;   // B-operand-order filters of the wave-specialised conv kernel (ConvBN::ws3f / ws3d)
-    void* ws_descs = nullptr;
-    int ws_n = 0;
-    double ws_bytes = 0;
+    rfi::bf16_t* ws_pool = nullptr;   // B-operand-order filters of the wave-specialised conv kernel (ConvBN::ws3f / ws3d) ...
+    rfi::BatchTable ws;               // ... and the table of their batched rebuild (refresh_ws_weights)
     std::unordered_map<const float*, const rfi::bf16_t*> ws_by_w;    // float32 filter pointer (ConvArgs::w) -> the same filters for conv_ws / gemm_ws
     int ws_P = 0;                     // planes of the copies in ws_pool: 3 (float32 by 3 x bf16), 1 (bf16 operands), 0 (none built)
     int ws_need() const { return planesP ? 0 : arith == Arith::X3 ? 3 : arith == Arith::BF16 ? 1 : 0; }
@@ -196,30 +194,36 @@ struct rfi_model {
     // record up to date, so a declined shape runs the round-2 kernel on valid records instead of a temporary copy (an
     // allocation + a stream synchronisation per launch)
     bool x3_skips_ws_layers = false;
-    int ws_n_fwd = 0;                 // the first ws_n_fwd descriptors build the forward-direction copies (sources in `params`)
-    double ws_bytes_fwd = 0;
-    void refresh_ws_weights(int P, int which = 0);      // which: 0 every copy, 1 the forward direction, 2 the input-gradient direction
-    // the input-gradient-direction copies (dgrad layout + their B-operand images) are rebuilt on the SIDE stream while the main
-    // stream runs the forward pass; the backward pass waits for wd_ready
+    int64_t adam_step = 0;
+
+    // ---- derived filter copies (derived.hpp; model.cpp): `stale` says which lag behind their sources.  Everything at
+    // construction; the events below set bits, sync_filters (with side_rebuild_wd) is the one place that clears them
+    unsigned stale = rfi::WEIGHT_DERIVED | rfi::FROZEN;
+    void weights_changed() { stale |= rfi::WEIGHT_DERIVED; }    // apply, init_params, load_entry of a parameter
+    void frozen_changed() { stale |= rfi::FROZEN; }             // load_entry of a per-channel entry
+    bool model_copies_every_pass = false;     // the backbone: its own copies are rebuilt by every forward pass
+    // rebuilds every stale copy the compute mode reads, row by row of the table: forward() and backward() call it.  A caller
+    // that needs the forward half only lets a model that allows it (wd_split_ok) leave INPUT_GRAD_HALF to the side stream
+    void sync_filters(rfi::Half needed);
+    rfi::BatchTable relayout;         // dgrad layouts: one descriptor per conv-like layer, built once
+    int64_t relayout_tiles = 0;
+    void rebuild_dgrad();
+    void refresh_ws_weights(rfi::Half half);
+    rfi::BatchTable x3;               // pre-split records: the list of the batched rebuild ...
+    rfi::RecordKey x3_key;            // ... and what it was built for
+    bool x3_reads_wd = false;         // the list reads dgrad-layout filters (which forbids the split)
+    std::unordered_set<const float*> x3_skipped;      // filters whose records are NOT kept up to date (ws_set clears ConvArgs::w3 for them)
+    void rebuild_records();
+    // U-Net family hooks: may INPUT_GRAD_HALF be rebuilt on the side stream, and the model's own derived filters
+    virtual bool wd_split_ok() const { return false; }
+    virtual void refresh_model_weights(rfi::Half half) {}
+    void refresh_s2d_forms(rfi::ConvBN& c);           // 2 x 2 form of a stride-2 3x3 filter, its dgrad layout, the records of both
+    // a split rebuild: the side stream rebuilds INPUT_GRAD_HALF while the main stream runs the forward pass (side_rebuild_wd,
+    // behind the first conv); wd_pending: enqueued there and not yet waited for (wait_wd: backward(), or the next rebuild)
     hipEvent_t wd_ready = nullptr;
     bool wd_pending = false;
-    bool wd_side_todo = false;        // the side half of a split rebuild has not been enqueued yet
     void side_rebuild_wd();
-    bool x3_reads_wd = false;         // the batched 3 x bf16 record rebuild reads dgrad-layout filters
     void wait_wd();
-    void* x3_descs = nullptr;         // device table of the batched rebuild
-    int x3_n = 0;
-    int x3_for_ws_P = -1;             // the ws_P the record list was built for (layers with ws copies are left out)
-    int x3_for_shape = -1;            // ... and the prepared H, W (a layer whose maps fall under 8 x 8 keeps its records)
-    std::unordered_set<const float*> x3_skipped;      // filters whose records are NOT kept up to date (ws_set clears ConvArgs::w3 for them)
-    double x3_bytes = 0;
-    int64_t adam_step = 0;
-    bool wd_dirty = true;
-    bool x3_fresh = false;            // the 3 x bf16 records match the current parameters
-    void* relayout_descs = nullptr;   // device table for the batched dgrad-layout rebuild
-    int relayout_n = 0;
-    int64_t relayout_tiles = 0;
-    double relayout_bytes = 0;
 
     // activations / workspaces for the prepared shape
     int pN = 0, pH = 0, pW = 0;
@@ -266,11 +270,6 @@ struct rfi_model {
     float* buf(int i) { return bufs[i].p; }
     int new_buf() { bufs.emplace_back(); return (int)bufs.size() - 1; }
     rfi::View network_input(const float* x_dev, int n, int h, int w);
-    void refresh_dgrad_weights();
-    // U-Net family hooks of refresh_dgrad_weights: may the input-gradient-direction copies be rebuilt on the side stream, and
-    // the model's own derived filters (which: as refresh_ws_weights)
-    virtual bool wd_split_ok() const { return false; }
-    virtual void refresh_model_weights(int which) {}
 
     // ---- launches on float32 tensors the networks share (model.cpp); algo_flops, stats and done stay the caller's
     // a stride-1 conv whose output grid is its input's (s): R x R taps, `pad`, filters w [tap][cout][cin], output [M][cout]
@@ -343,7 +342,7 @@ struct UNetModel : rfi_model {
     void set_compute_dtype(int dtype) override;
     void debug_tensor(const std::string& name, const std::string& base, int idx, bool to_host, const float*& src, size_t& n) override;
     bool wd_split_ok() const override;
-    void refresh_model_weights(int which) override;
+    void refresh_model_weights(rfi::Half half) override;
 
     int i_bott = 0;                   // index of the bottleneck's first conv in `convs` (decoder convs follow it)
     float act_slope = 0.0f;           // 0: ReLU; > 0: LeakyReLU(negative_slope) (UNetDifferentActivation)
@@ -424,14 +423,10 @@ struct UNetModel : rfi_model {
     std::vector<int> yD2, pUpIn, g16cat;
     int yB2 = -1, g16BottA = -1;
     rfi::bf16_t* wb_pool = nullptr;
-    void* wb_descs = nullptr;
-    int wb_n = 0;
-    double wb_bytes = 0;
+    rfi::BatchTable wb;               // (the forward-direction filter images first)
     void set_planes(int P);           // switches the data flow; frees plane tensors of another P
     void prepare_planes(int n, int h, int w);
-    int wb_n_fwd = 0;                 // descriptors of the forward-direction filter images (the table's first entries)
-    double wb_bytes_fwd = 0;
-    void refresh_plane_weights(int which = 0);       // 0 everything; 1 forward-direction images; 2 input-gradient direction (+ class tables)
+    void refresh_plane_weights(rfi::Half half);      // InputGrad: + the parity-class tables
     void forward_planes(const float* x_dev, int n, int h, int w, bool train_mode);
     void backward_planes(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w);
 };
@@ -469,7 +464,7 @@ struct ConvHeadModel : rfi_model {
 
 // ResNet-50-FPN backbone with frozen BatchNorm (model_backbone.cpp): feat = base width (64), out_ch = FPN channels
 struct BackboneModel : rfi_model {
-    BackboneModel(int in, int base_width, int fpn_ch) : rfi_model(in, fpn_ch, base_width, 0) {}
+    BackboneModel(int in, int base_width, int fpn_ch) : rfi_model(in, fpn_ch, base_width, 0) { model_copies_every_pass = true; }
     ~BackboneModel() override;
     void build() override;
     void prepare_shape(int n, int h, int w) override;
@@ -494,8 +489,8 @@ struct BackboneModel : rfi_model {
     float* bb_stem_w3 = nullptr;      // 3 x bf16 records of the K-packed stem filters (rebuilt with them every step)
     int bG[6] = {-1, -1, -1, -1, -1, -1};
     int bT[4][3] = {{-1, -1, -1}, {-1, -1, -1}, {-1, -1, -1}, {-1, -1, -1}};   // dY3 / dY2 / dY1 / dYd of a Bottleneck, by block index mod 3: what the side stream's weight gradients read
-    bool frozen_dirty = true;         // frozen BatchNorm buffers changed: scale / shift must be recomputed
-    void refresh_backbone();
+    // frozen BatchNorm scale / shift where FROZEN is set, then the 2 x 2 forms of the stride-2 filters
+    void refresh_model_weights(rfi::Half half) override;
 };
 
 // fully connected box head (model_mlp.cpp): depth FC + ReLU layers in_ch -> feat -> feat, head feat -> out_ch

@@ -108,7 +108,6 @@ void BackboneModel::build() {
             RFI_CHECK_HIP(hipMemcpyAsync(c.frozen_weight(), g.data(), g.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
             RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
         }
-    frozen_dirty = true;
 }
 
 namespace {
@@ -193,9 +192,10 @@ void BackboneModel::prepare_shape(int n, int h, int w) {
     pN = n; pH = h; pW = w;
 }
 
-// frozen BatchNorm coefficients and the derived filter copies the batched relayout does not cover
-void BackboneModel::refresh_backbone() {
-    if (frozen_dirty) {
+// frozen BatchNorm coefficients and the derived filter copies the batched relayout does not cover (both directions at
+// once: this model never splits its rebuild)
+void BackboneModel::refresh_model_weights(Half) {
+    if (stale & FROZEN) {
         for (auto& c : convs)
             if (c.has_bn) launch_bn_eval_coeffs(ctx, c.cout, c.frozen_weight(), c.frozen_bias(), c.running_mean(), c.running_var(), c.scale(), c.shift());
         for (auto& k : bb)
@@ -206,18 +206,10 @@ void BackboneModel::refresh_backbone() {
                     RFI_CHECK_HIP(hipMemcpyAsync(k.sh4 + r * k.width, c1.shift(), k.width * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
                 }
             }
-        frozen_dirty = false;
+        stale &= ~FROZEN;
     }
     for (auto& k : bb)
-        if (k.stride == 2) {
-            ConvBN& c = convs[k.c2];
-            launch_w_s2d(ctx, params + c.w_off, c.cout, c.cin, c.ws2d, true);
-            launch_weight_to_dgrad(ctx, c.ws2d, 4, c.cout, 4 * c.cin, 1, c.wds2d);
-            if (use_w3()) {
-                launch_weights_to_x3(ctx, c.ws2d, 4, c.cout, 4 * c.cin, c.ws2d3);
-                launch_weights_to_x3(ctx, c.wds2d, 4, 4 * c.cin, c.cout, c.wds2d3);
-            }
-        }
+        if (k.stride == 2) refresh_s2d_forms(convs[k.c2]);
 }
 
 namespace {
@@ -241,8 +233,6 @@ void affine_bwd(BackboneModel* m, const ConvBN& c, float* dA, const float* Y, in
 }  // namespace
 
 void BackboneModel::forward_pass(const float* x_dev, int n, int h, int w, bool) {
-    refresh_dgrad_weights();
-    refresh_backbone();
     {   // stem: 7x7 / 2 as a GEMM on its K-packed input (K = 49 C padded to a multiple of 16), then max-pool of the activated output
         ConvBN& c = convs[0];
         const int Kp = stem_kp();
@@ -300,7 +290,6 @@ void BackboneModel::forward_pass(const float* x_dev, int n, int h, int w, bool) 
 
 // dP2..dP6 sit in fdP[0..3] / fdP6 (rfi_backbone_backward copies them there)
 void BackboneModel::backward_pass(const float* x_dev, const uint8_t*, int n, int h, int w) {
-    refresh_dgrad_weights();
     side_bound = 2;                   // (measured 31.8 / 32.2 / 32.9 ms per step of the detector at bound 2 / bound 5 / no side stream)
     const int F = out_ch;
     int last[4], bi = -1;

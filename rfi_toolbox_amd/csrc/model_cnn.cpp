@@ -60,7 +60,6 @@ void Cnn3Model::prepare_shape(int n, int h, int w) {
 }
 
 void Cnn3Model::forward_pass(const float* x_dev, int n, int h, int w, bool) {
-    refresh_dgrad_weights();
     ConvBN& c1 = convs[0];
     ConvBN& c2 = convs[1];
     const Shape s{n, h, w};
@@ -81,7 +80,6 @@ void Cnn3Model::backward_pass(const float* x_dev, const uint8_t* labels_dev, int
     ConvBN& c2 = convs[1];
     const int64_t M = (int64_t)n * h * w;
     const Shape s{n, h, w};
-    refresh_dgrad_weights();
     if (loss_kind == 1) launch_focal_bwd(ctx, buf(logits), labels_dev, M, focal_alpha, focal_gamma, buf(dlogits));
     else launch_loss_bwd(ctx, buf(logits), labels_dev, M, d_sums, buf(dlogits));
     // head: dW, db and the gradient w.r.t. relu(Y2)

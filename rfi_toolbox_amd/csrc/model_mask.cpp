@@ -91,7 +91,6 @@ void ConvHeadModel::prepare_shape(int n, int h, int w) {
 }
 
 void ConvHeadModel::forward_pass(const float* x_dev, int n, int h, int w, bool) {
-    refresh_dgrad_weights();
     const int L = depth, C = in_ch;
     const int64_t M4 = (int64_t)out_scale * out_scale * n * h * w;
     for (int i = 0; i < L; ++i) {
@@ -122,7 +121,6 @@ void ConvHeadModel::backward_pass(const float* x_dev, const uint8_t* labels_dev,
     const int L = depth, C = in_ch;
     const int64_t M = (int64_t)n * h * w, M4 = (int64_t)out_scale * out_scale * M;
     const Shape s{n, h, w}, s4{n, out_scale * h, out_scale * w};
-    refresh_dgrad_weights();
     if (!ext_dlogits) {               // (rfi_model_backward_dlogits: the caller's loss kernel has filled dlogits)
         if (loss_kind == 1) launch_focal_bwd(ctx, buf(logits), labels_dev, M4 * out_ch, focal_alpha, focal_gamma, buf(dlogits));
         else launch_loss_bwd(ctx, buf(logits), labels_dev, M4 * out_ch, d_sums, buf(dlogits));

@@ -69,7 +69,6 @@ void BoxHeadModel::prepare_shape(int n, int h, int w) {
 }
 
 void BoxHeadModel::forward_pass(const float* x_dev, int n, int, int, bool) {
-    refresh_dgrad_weights();
     const int L = depth;
     const Shape s = layout_of(n);
     for (int i = 0; i < L; ++i) {
@@ -89,7 +88,6 @@ void BoxHeadModel::backward_pass(const float* x_dev, const uint8_t*, int n, int,
     const int L = depth;
     const Shape s = layout_of(n);
     const int64_t M = n;
-    refresh_dgrad_weights();
     const ConvBN& cl = convs[L - 1];
     launch_head_bwd(ctx, buf(fcY[L - 1]), M, feat, cl.scale(), cl.shift(), params + head_w_off, out_ch, buf(dlogits), buf(fcG[L - 1]),
                     buf(ws_red), grads + head_w_off, grads + head_b_off);

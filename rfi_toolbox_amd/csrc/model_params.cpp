@@ -260,8 +260,7 @@ void rfi_model::init_params(uint64_t seed) {
     RFI_CHECK_HIP(hipMemsetAsync(adam_m, 0, n_flat * sizeof(float), ctx->stream));
     RFI_CHECK_HIP(hipMemsetAsync(adam_v, 0, n_flat * sizeof(float), ctx->stream));
     adam_step = 0;
-    wd_dirty = true;
-    x3_fresh = false;
+    weights_changed();
 }
 
 void rfi_model::load_entry(const Entry& e, const void* host, size_t bytes) {
@@ -274,14 +273,13 @@ void rfi_model::load_entry(const Entry& e, const void* host, size_t bytes) {
     const float* src = static_cast<const float*>(host);
     if (float* dst = chan_slot(this, e)) {
         upload(this, dst, src, (size_t)convs[e.layer].cout);
-        if (auto* b = dynamic_cast<BackboneModel*>(this)) b->frozen_dirty = true;
+        frozen_changed();
         return;
     }
     std::vector<float> tmp;
     to_lib(this, e, src, tmp);
     upload(this, params + e.off, tmp.data(), tmp.size());
-    wd_dirty = true;
-    x3_fresh = false;
+    weights_changed();
 }
 
 void rfi_model::store_entry(const Entry& e, void* host, size_t bytes) {

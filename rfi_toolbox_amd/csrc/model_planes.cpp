@@ -183,7 +183,7 @@ void UNetModel::prepare_planes(int n, int h, int w) {
 
 // filters of every 3x3 layer in MFMA B-operand order, both directions, rebuilt with the dgrad layouts after each
 // optimiser step by ONE batched launch
-void UNetModel::refresh_plane_weights(int which) {
+void UNetModel::refresh_plane_weights(Half half) {
     const int P = planesP, IB = i_bott;
     auto two_seg = [&](size_t ci) { return (int)ci >= IB + 2 && (((int)ci - (IB + 2)) & 1) == 0; };      // decoder conv1: [up | skip]
     auto has_wBd = [&](const ConvBN& c) { return c.R == 3 && c.stride == 1; };      // (the other shapes' input gradients: class tables)
@@ -210,71 +210,50 @@ void UNetModel::refresh_plane_weights(int which) {
         if (cls_need && !rs_cls_pool) rs_cls_pool = static_cast<float*>(ctx->alloc(cls_need * sizeof(float)));
         std::vector<WBDesc> hd;
         size_t o = 0, co = 0;
-        wb_bytes = wb_bytes_fwd = 0;
+        // the image of `taps` filters [cout][cin] at `src`, its K in one or two segments: the next region of the pool (+ its
+        // 32-element tail) and one descriptor
+        auto image = [&](double& bytes, const float* src, int taps, int cout, int cin, int seg0, int seg1, int planes) {
+            bf16_t* dst = wb_pool + o;
+            const size_t e = wb_elems(taps, cout, seg0, seg1, planes);
+            o += e + 32;
+            hd.push_back(WBDesc{src, dst, taps, cout, cin, {seg0, seg1}, planes});
+            bytes += 2.0 * e + 4.0 * taps * cin * cout;
+            return dst;
+        };
         for (size_t ci = 0; ci < convs.size(); ++ci) {
             ConvBN& c = convs[ci];
             const bool two = two_seg(ci);
-            const int taps = c.R * c.R;
-            c.wBf = wb_pool + o;
-            const size_t ef = wb_elems(taps, c.cout, two ? c.cin / 2 : c.cin_p, two ? c.cin / 2 : 0, P);
-            o += ef + 32;
-            hd.push_back(WBDesc{params + c.w_off, c.wBf, taps, c.cout, c.cin_p, {two ? c.cin / 2 : c.cin_p, two ? c.cin / 2 : 0}, P});
-            wb_bytes_fwd += 2.0 * ef + 4.0 * taps * c.cin_p * c.cout;
+            c.wBf = image(wb.bytes_fwd, params + c.w_off, c.R * c.R, c.cout, c.cin_p, two ? c.cin / 2 : c.cin_p, two ? c.cin / 2 : 0, P);
         }
-        if (P == 1)
-            for (auto& u : ups) {                 // forward layout [4][cout][cin] = one 1x1 contraction with 4 cout channels
-                u.wBf = wb_pool + o;
-                const size_t ef = wb_elems(1, 4 * u.cout, u.cin, 0, 1);
-                o += ef + 32;
-                hd.push_back(WBDesc{params + u.w_off, u.wBf, 1, 4 * u.cout, u.cin, {u.cin, 0}, 1});
-                wb_bytes_fwd += 2.0 * ef + 16.0 * u.cin * u.cout;
-            }
-        wb_n_fwd = (int)hd.size();
-        wb_bytes = wb_bytes_fwd;
-        for (size_t ci = 0; ci < convs.size(); ++ci) {
-            ConvBN& c = convs[ci];
-            if (!has_wBd(c)) continue;
-            c.wBd = wb_pool + o;
-            const size_t ed = wb_elems(9, c.cin_p, c.cout, 0, P);
-            o += ed + 32;
-            hd.push_back(WBDesc{c.wd, c.wBd, 9, c.cin_p, c.cout, {c.cout, 0}, P});
-            wb_bytes += 2.0 * ed + 4.0 * 9 * c.cin_p * c.cout;
-        }
-        if (P == 1)
-            for (auto& u : ups) {                 // dgrad layout [4][cin][cout]
-                u.wBd = wb_pool + o;
-                const size_t ed = wb_elems(4, u.cin, u.cout, 0, 1);
-                o += ed + 32;
-                hd.push_back(WBDesc{u.wd, u.wBd, 4, u.cin, u.cout, {u.cout, 0}, 1});
-                wb_bytes += 2.0 * ed + 16.0 * u.cin * u.cout;
-            }
+        if (P == 1)                               // forward layout [4][cout][cin] = one 1x1 contraction with 4 cout channels
+            for (auto& u : ups) u.wBf = image(wb.bytes_fwd, params + u.w_off, 1, 4 * u.cout, u.cin, u.cin, 0, 1);
+        wb.n_fwd = (int)hd.size();
+        wb.bytes = wb.bytes_fwd;
+        for (ConvBN& c : convs)
+            if (has_wBd(c)) c.wBd = image(wb.bytes, c.wd, 9, c.cin_p, c.cout, c.cout, 0, P);
+        if (P == 1)                               // dgrad layout [4][cin][cout]
+            for (auto& u : ups) u.wBd = image(wb.bytes, u.wd, 4, u.cin, u.cout, u.cout, 0, 1);
         for (size_t bi = 0; bi < blocks.size(); ++bi) {
             const ResBlock& b = blocks[bi];
             if (b.stride != 2) continue;
             ResPlanes& r = rpb[bi];
             r.cls = rs_cls_pool + co;
             co += s2_class_floats(b.cout, b.cin);
-            for (int c = 0; c < 4; ++c) {
-                r.wBcls[c] = wb_pool + o;
-                const size_t e = wb_elems(4, b.cin, b.cout, c == 0 ? b.cout : 0, 1);
-                o += e + 32;
-                hd.push_back(WBDesc{r.cls + s2_class_offset(c, b.cout, b.cin), r.wBcls[c], 4, b.cin, c == 0 ? 2 * b.cout : b.cout,
-                                    {b.cout, c == 0 ? b.cout : 0}, 1});
-                wb_bytes += 2.0 * e + 16.0 * b.cin * b.cout * (c == 0 ? 2 : 1);
-            }
+            for (int c = 0; c < 4; ++c)           // (class 0: two K segments)
+                r.wBcls[c] = image(wb.bytes, r.cls + s2_class_offset(c, b.cout, b.cin), 4, b.cin, c == 0 ? 2 * b.cout : b.cout, b.cout,
+                                   c == 0 ? b.cout : 0, 1);
         }
-        wb_n = (int)hd.size();
-        wb_descs = ctx->upload_table(hd.data(), hd.size() * sizeof(WBDesc));
+        wb.n = (int)hd.size();
+        wb.descs = ctx->upload_table(hd.data(), hd.size() * sizeof(WBDesc));
     }
-    const WBDesc* descs = static_cast<const WBDesc*>(wb_descs);
-    if (which != 2) launch_weights_to_wb(ctx, descs, wb_n_fwd, wb_bytes_fwd);
-    if (which != 1) {
+    if (half != Half::InputGrad) wb.launch(ctx, Half::Forward);
+    if (half != Half::Forward) {      // (the class tables are sources of the table's second half: two launches also for Both)
         for (size_t bi = 0; bi < blocks.size(); ++bi) {
             const ResBlock& b = blocks[bi];
             if (b.stride == 2)
                 launch_w_s2_classes(ctx, params + convs[b.c1].w_off, params + convs[b.cd].w_off, b.cout, b.cin, rpb[bi].cls);
         }
-        if (wb_n > wb_n_fwd) launch_weights_to_wb(ctx, descs + wb_n_fwd, wb_n - wb_n_fwd, wb_bytes - wb_bytes_fwd);
+        wb.launch(ctx, Half::InputGrad);
     }
 }
 

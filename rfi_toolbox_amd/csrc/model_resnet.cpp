@@ -123,16 +123,8 @@ void UNetModel::prepare_resnet(int n, int h, int w) {
 // the 2x2 forms of the stride-2 filters (forward and input-gradient layouts); every other derived copy comes from
 // the batched relayout of model.cpp
 void UNetModel::refresh_resnet_weights() {
-    for (int ci = 0; ci < i_bott; ++ci) {
-        ConvBN& c = convs[ci];
-        if (c.stride != 2 || c.R != 3) continue;
-        launch_w_s2d(ctx, params + c.w_off, c.cout, c.cin, c.ws2d, true);
-        launch_weight_to_dgrad(ctx, c.ws2d, 4, c.cout, 4 * c.cin, 1, c.wds2d);
-        if (use_w3()) {
-            launch_weights_to_x3(ctx, c.ws2d, 4, c.cout, 4 * c.cin, c.ws2d3);
-            launch_weights_to_x3(ctx, c.wds2d, 4, 4 * c.cin, c.cout, c.wds2d3);
-        }
-    }
+    for (int ci = 0; ci < i_bott; ++ci)
+        if (convs[ci].stride == 2 && convs[ci].R == 3) refresh_s2d_forms(convs[ci]);
 }
 
 // -> the pooled output of layer 4 (input of the bottleneck); skip l is written into concat[l][..., C:2C]
