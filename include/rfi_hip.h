@@ -574,6 +574,37 @@ int rfi_norm_statistics(rfi_ctx* ctx, const void* const* chunks, const int64_t* 
 int rfi_norm_apply(rfi_ctx* ctx, const void* src_dev, int dtype, int src_layout, int n, int64_t pixels, double centre,
                    double scale, const double* params_dev, float* dst_dev, int dst_layout);
 
+/* ---- whole-observation prediction for 8-channel models: tiling, views, polarisation stacking and normalisation of
+ *      rfi_norm_apply in one pass, and the pipeline of rfi_model_predict_flags built on it.
+ *
+ *      rfi_norm_gather: planes (n_samples, 4, C, T), RFI_C128 or RFI_C64, in the order RR, RL, LR, LL; a table entry's
+ *      `plane` is the SAMPLE index and names all four of its planes, `view`, `row0`, `col0` are rfi_patch_src's and apply
+ *      to each of them alike.  out_nhwc (n, ps, ps, 8) float32 with the channels RR.re RR.im RL.re ... LL.im
+ *      (rfi_norm_apply's order).  Every output value is
+ *          scale == 0 ? 0.0f : (float)(((double)x - centre) / scale)
+ *      -- rfi_norm_apply's expression: fp64 on the exact source value, a real division, rounded once -- with
+ *      (centre, scale) the call's pair when params_host is NULL, else params_host[plane], one {centre, scale} array of
+ *      two doubles per sample (n_samples of them, contiguous).  A pixel past the view's edge is the visibility 0 + 0j sent through the same
+ *      expression: it is normalised like a sample of no signal, not written as a literal zero.  No atomics; the result
+ *      does not depend on the launch geometry.  planes, table_host and out_nhwc are host or device operands as in
+ *      rfi_preprocess_gather (the table and the pairs always host); buffers need only their element's alignment and the
+ *      table may name any origin.
+ *
+ *      rfi_model_predict_flags_pol: rfi_model_predict_flags for a model with 8 input channels, 1 output channel and an
+ *      output map the size of its input.  The unit of chunking, stitching and output is the sample (one baseline: 4
+ *      complex planes in, one C x T plane of flags out): flags and the optional prob are (n_samples, C, T).  The patches
+ *      are rfi_norm_gather's, with the same meaning of centre, scale and params_host (n_samples pairs); chunks, the
+ *      two-slot upload and download, the eval-mode forward at the full batch and the stitch are those of
+ *      rfi_model_predict_flags, and so are the workspace bound (counted with 4 complex planes per sample and 8-channel
+ *      image batches) and the error for a single sample that exceeds it. ---- */
+int rfi_norm_gather(rfi_ctx* ctx, const void* planes, int planes_mem, int dtype, int n_samples, int c, int t,
+                    const rfi_patch_src* table_host, int n, int ps, double centre, double scale,
+                    const double (*params_host)[2], float* out_nhwc, int out_mem);
+int rfi_model_predict_flags_pol(rfi_model* m, const void* planes, int planes_mem, int dtype, int n_samples, int c, int t,
+                                const rfi_tiling* tiling, int batch, int combine, float threshold, double centre,
+                                double scale, const double (*params_host)[2], uint8_t* flags, int flags_mem, float* prob,
+                                int prob_mem);
+
 /* ---- training augmentation (scripts/train_model.py:44-53,70-75, --augment): HorizontalFlip, VerticalFlip, Rotate and
  *      ShiftScaleRotate of a batch and its masks, as flips and ONE resampling through the composed affine transform.
  *      Distribution-level parity: the reference resamples once per transform with its library's own random stream.

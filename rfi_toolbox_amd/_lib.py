@@ -227,6 +227,9 @@ _PROTOS = {
     "rfi_norm_bracket": (_i, [_i64, C.c_double, _pi64, _pd]),
     "rfi_norm_statistics": (_i, [_vp, _pvp, _pi64, _i, _i, _i64, _i, C.POINTER(NormStats), _i]),
     "rfi_norm_apply": (_i, [_vp, _vp, _i, _i, _i, _i64, C.c_double, C.c_double, _vp, _vp, _i]),
+    "rfi_norm_gather": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, C.c_double, C.c_double, _vp, _vp, _i]),
+    "rfi_model_predict_flags_pol": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(Tiling), _i, _i, _f, C.c_double, C.c_double, _vp,
+                                         _vp, _i, _vp, _i]),
     "rfi_augment_params": (_i, [C.POINTER(AugmentConfig), C.c_uint64, _i, _i, _i, C.POINTER(C.c_int32), _pd]),
     "rfi_augment_batch": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, C.POINTER(AugmentConfig), C.c_uint64, _vp, _vp]),
     "rfi_sumthreshold_ladder": (_i, [C.POINTER(SumThresholdConfig), C.c_double, _i, _pd]),

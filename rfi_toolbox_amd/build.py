@@ -22,7 +22,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
 SOURCES = ["api.cpp", "api_ops.cpp", "api_flaggers.cpp", "api_components.cpp", "api_match.cpp", "model.cpp", "model_cnn.cpp", "model_planes.cpp", "model_resnet.cpp", "model_mask.cpp", "model_backbone.cpp", "model_mlp.cpp", "model_params.cpp", "dispatch.cpp", "elem_kernels.hip", "conv_direct.hip", "conv_mfma.hip",
-           "wgrad_mfma.hip", "preprocess.hip", "synth.hip", "order_stats.hip", "planes_elem.hip", "conv_planes.hip", "conv_ws.hip", "conv_stem.hip", "gemm_ws.hip", "wgrad_ws.hip", "wgrad_stem.hip", "wgrad_planes.hip", "wgrad_split.hip", "detect_kernels.hip", "detect_sample.hip", "detect_infer.hip", "rpn_kernels.hip", "resnet_kernels.hip", "flag_stats.hip", "rfi_sim.hip", "stitch.hip", "dataset_norm.hip", "augment.hip", "sumthreshold.hip", "casa_flaggers.hip", "threshold_sweep.hip", "components.hip", "instance_match.hip"]
+           "wgrad_mfma.hip", "preprocess.hip", "synth.hip", "order_stats.hip", "planes_elem.hip", "conv_planes.hip", "conv_ws.hip", "conv_stem.hip", "gemm_ws.hip", "wgrad_ws.hip", "wgrad_stem.hip", "wgrad_planes.hip", "wgrad_split.hip", "detect_kernels.hip", "detect_sample.hip", "detect_infer.hip", "rpn_kernels.hip", "resnet_kernels.hip", "flag_stats.hip", "rfi_sim.hip", "stitch.hip", "dataset_norm.hip", "augment.hip", "sumthreshold.hip", "casa_flaggers.hip", "threshold_sweep.hip", "components.hip", "instance_match.hip", "pol_gather.hip"]
 HEADERS = ["common.hpp", "kernels.hpp", "model.hpp", "derived.hpp", "planes.hpp", "bf16_mma.hpp", "philox.hpp", "ws_common.hpp", "detect_sort.hpp", "select_common.hpp", "launch_common.hpp", os.path.join(ROOT, "include", "rfi_hip.h")]
 
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
@@ -44,7 +44,7 @@ def _newer(target, deps):
 # float32 products in fp64, so they are built without the SLP vectoriser (which forms the packed ops); they are bound
 # by HBM, the packed forms bought nothing.  tools/scan_pk_f64_hazard.py checks the ISA of every source for the pair.
 NO_SLP = {"elem_kernels.hip", "planes_elem.hip", "resnet_kernels.hip", "rpn_kernels.hip", "detect_kernels.hip",
-          "preprocess.hip", "order_stats.hip", "synth.hip", "conv_direct.hip", "flag_stats.hip", "dataset_norm.hip", "augment.hip", "sumthreshold.hip", "casa_flaggers.hip", "instance_match.hip",
+          "preprocess.hip", "order_stats.hip", "synth.hip", "conv_direct.hip", "flag_stats.hip", "dataset_norm.hip", "augment.hip", "sumthreshold.hip", "casa_flaggers.hip", "instance_match.hip", "pol_gather.hip",
           # every other source that converts float32 to double (the statistics records of the conv epilogues, slab sums)
           "conv_planes.hip", "wgrad_planes.hip", "wgrad_split.hip", "wgrad_mfma.hip", "conv_mfma.hip",
           # conv_ws.hip: its producer waves run VALU next to the consumer waves' MFMAs, where a packed fp32 op costs

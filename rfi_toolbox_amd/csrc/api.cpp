@@ -957,13 +957,14 @@ int rfi_preprocess_patches(rfi_ctx* ctx, const void* patches, int patches_mem, i
 }
 
 namespace {
-void check_table(const rfi_patch_src* t, int n, int n_planes, int c, int tt, int ps) {
-    RFI_REQUIRE(n_planes > 0 && c > 0 && tt > 0 && ps > 0, "preprocess_gather: bad shape");
-    RFI_REQUIRE((int64_t)n_planes * c * tt < ((int64_t)1 << 40), "preprocess_gather: waterfall too large");
+void check_table(const rfi_patch_src* t, int n, int n_planes, int c, int tt, int ps, const char* who = "preprocess_gather") {
+    const std::string w(who);
+    RFI_REQUIRE(n_planes > 0 && c > 0 && tt > 0 && ps > 0, w + ": bad shape");
+    RFI_REQUIRE((int64_t)n_planes * c * tt < ((int64_t)1 << 40), w + ": waterfall too large");
     for (int i = 0; i < n; ++i) {
         const rfi_patch_src& e = t[i];
         RFI_REQUIRE(e.plane >= 0 && e.plane < n_planes && e.view >= 0 && e.view <= 3 && e.row0 >= 0 && e.col0 >= 0,
-                    "preprocess_gather: bad table entry " + std::to_string(i));
+                    w + ": bad table entry " + std::to_string(i));
     }
 }
 }  // namespace
@@ -1005,6 +1006,26 @@ int rfi_preprocess_gather(rfi_ctx* ctx, const void* planes, int planes_mem, int 
         void* mm = ctx->get_scratch((size_t)n * 4 * sizeof(unsigned long long));
         launch_preprocess(ctx, pl, dtype, n, ps, ps, static_cast<float*>(mm), dout, tb, c, t);
         if (out_labels) launch_gather_labels(ctx, fl, tb, c, t, n, ps, dlab);
+        sc.finish();
+    });
+}
+
+int rfi_norm_gather(rfi_ctx* ctx, const void* planes, int planes_mem, int dtype, int n_samples, int c, int t,
+                    const rfi_patch_src* table_host, int n, int ps, double centre, double scale,
+                    const double (*params_host)[2], float* out_nhwc, int out_mem) {
+    return guarded([&] {
+        RFI_REQUIRE(ctx && n >= 0 && planes && (n == 0 || (table_host && out_nhwc)), "norm_gather: null argument");
+        RFI_REQUIRE(dtype == RFI_C128 || dtype == RFI_C64, "norm_gather: planes must be complex128 or complex64");
+        if (n == 0) return;
+        check_table(table_host, n, n_samples, c, t, ps, "norm_gather");
+        RFI_REQUIRE((int64_t)n_samples * 4 * c * t < ((int64_t)1 << 40), "norm_gather: waterfall too large");
+        ctx->activate();
+        CallScope sc(ctx);
+        const void* pl = sc.in(planes, planes_mem, (size_t)n_samples * 4 * c * t * dtype_bytes(dtype));
+        const rfi_patch_src* tb = sc.in(table_host, RFI_HOST, (size_t)n);
+        const double* pr = sc.in(params_host ? params_host[0] : nullptr, RFI_HOST, (size_t)n_samples * 2);
+        float* dout = sc.out(out_nhwc, out_mem, (size_t)n * ps * ps * 8);
+        launch_pol_gather(ctx, pl, dtype, c, t, tb, n, ps, centre, scale, pr, dout);
         sc.finish();
     });
 }
@@ -1376,139 +1397,210 @@ int rfi_stitch_patches(rfi_ctx* ctx, const float* values, int values_mem, int ki
 // into the chunk's patch-output buffer, then one stitch.  Host input is uploaded on a second stream into two alternating
 // slots, the next chunk's upload next to the current chunk's compute; host outputs are staged the same way and copied
 // back on that stream while the next chunk computes.
+//
+// One driver serves both entry points.  Its unit is what one stitched C x T plane of flags comes from: a complex plane
+// (rfi_model_predict_flags) or a sample of 4 of them (rfi_model_predict_flags_pol); a PredictGather says how a batch of
+// patches becomes an image batch.
+namespace {
+struct PredictGather {
+    const char* who;           // the entry point, for messages
+    const char* unit;          // "plane" or "sample"
+    int in_ch;                 // channels of the image batch
+    int pols;                  // complex planes per unit
+    // private device workspace for image batches of nb patches out of n_units units, filled once by setup()
+    virtual size_t ws_bytes(int nb, int n_units) const = 0;
+    virtual void setup(rfi_ctx*, void*, int) {}
+    // patches tb[0 .. nv) of the chunk at `pl`, whose first unit is unit `first` of the call -> img (nv, ps, ps, in_ch)
+    virtual void run(rfi_ctx* ctx, const void* pl, int dtype, int first, int c, int t, const rfi_patch_src* tb, int nv, int ps,
+                     void* ws, float* img) const = 0;
+    virtual ~PredictGather() = default;
+};
+
+struct ChannelGather final : PredictGather {        // amplitude gradient, log-amplitude, phase (rfi_preprocess_gather's kernels)
+    ChannelGather() { who = "predict_flags"; unit = "plane"; in_ch = 3; pols = 1; }
+    size_t ws_bytes(int nb, int) const override { return (size_t)nb * 4 * sizeof(unsigned long long); }     // min/max words
+    void run(rfi_ctx* ctx, const void* pl, int dtype, int, int c, int t, const rfi_patch_src* tb, int nv, int ps, void* ws,
+             float* img) const override {
+        launch_preprocess(ctx, pl, dtype, nv, ps, ps, static_cast<float*>(ws), img, tb, c, t);
+    }
+};
+
+struct PolGather final : PredictGather {            // the four polarisations, normalised (rfi_norm_gather's kernel)
+    double centre, scale;
+    const double* params_host;                      // one pair per unit, or null
+    PolGather(double ce, double sc, const double* ph) : centre(ce), scale(sc), params_host(ph) {
+        who = "predict_flags_pol"; unit = "sample"; in_ch = 8; pols = 4;
+    }
+    size_t ws_bytes(int, int n_units) const override { return params_host ? (size_t)n_units * 2 * sizeof(double) : 0; }
+    void setup(rfi_ctx* ctx, void* ws, int n_units) override {
+        if (params_host)
+            RFI_CHECK_HIP(hipMemcpyAsync(ws, params_host, (size_t)n_units * 2 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    }
+    void run(rfi_ctx* ctx, const void* pl, int dtype, int first, int c, int t, const rfi_patch_src* tb, int nv, int ps, void* ws,
+             float* img) const override {
+        launch_pol_gather(ctx, pl, dtype, c, t, tb, nv, ps, centre, scale,
+                          params_host ? static_cast<const double*>(ws) + 2 * (size_t)first : nullptr, img);
+    }
+};
+
+void predict_flags_driver(rfi_model* m, PredictGather& g, const void* planes, int planes_mem, int dtype, int n_planes, int c,
+                          int t, const rfi_tiling* tiling, int batch, int combine, float threshold, uint8_t* flags,
+                          int flags_mem, float* prob, int prob_mem) {
+    const std::string who(g.who);
+    RFI_REQUIRE(m && planes && flags && tiling, who + ": null argument");
+    RFI_REQUIRE(dtype == RFI_C128 || dtype == RFI_C64,
+                who + ": planes must be complex128 or complex64 (real input: Preprocessor + rfi_stitch_patches)");
+    RFI_REQUIRE(n_planes >= 0 && c > 0 && t > 0 && batch > 0, who + ": bad shape or batch");
+    RFI_REQUIRE(m->in_ch == g.in_ch && m->out_ch == 1 && m->out_scale == 1,
+                who + ": needs a model with " + std::to_string(g.in_ch) +
+                    " input channels, 1 output channel and an output map the size of its input");
+    RFI_REQUIRE(combine == RFI_COMBINE_MEAN || combine == RFI_COMBINE_MAX, who + ": combine must be mean (0) or max (1)");
+    check_tiling(*tiling);
+    if (n_planes == 0) return;
+    rfi_ctx* ctx = m->ctx;
+    ctx->activate();
+    const int ps = tiling->ps;
+    const int64_t ppp = tiling_patches_per_plane(c, t, *tiling);
+    const size_t esz = dtype_bytes(dtype);
+    // plane_px: pixels of a stitched plane; plane_bytes: the input behind it
+    const size_t plane_px = (size_t)c * t, plane_bytes = plane_px * esz * g.pols, patch_px = (size_t)ps * ps;
+    const bool host_in = planes_mem == RFI_HOST, host_fl = flags_mem == RFI_HOST, host_pr = prob && prob_mem == RFI_HOST;
+    const size_t out_px_bytes = (host_fl ? 1 : 0) + (host_pr ? 4 : 0);
+    const size_t per_plane = (size_t)ppp * (patch_px * sizeof(float) + sizeof(rfi_patch_src)) +
+                             (host_in ? 2 * plane_bytes : 0) + 2 * plane_px * out_px_bytes;
+    RFI_REQUIRE(per_plane <= kPredictBudget,
+                who + ": one " + (g.pols > 1 ? std::to_string(g.pols) + " x " : std::string()) + std::to_string(c) + " x " +
+                    std::to_string(t) + " " + g.unit + " needs " +
+                    std::to_string(per_plane >> 20) + " MiB of workspace at this tiling (" + std::to_string(ppp) +
+                    " patches of " + std::to_string(ps) + "^2), over the budget of " +
+                    std::to_string(kPredictBudget >> 20) + " MiB; " + g.unit + "s are not split: use a larger stride, fewer views "
+                    "or smaller planes");
+    // planes per chunk: at least ~4 batches of patches, no more than the budget holds; among up to 4x that, the one
+    // whose last batch wastes the smallest share of slots
+    const int kmax = (int)std::min<size_t>((size_t)n_planes, kPredictBudget / per_plane);
+    const int k0 = (int)std::min<int64_t>(kmax, std::max<int64_t>(1, cdiv(4 * (int64_t)batch, ppp)));
+    int k = k0;
+    double best = 2.0;
+    for (int kk = k0; kk <= std::min(kmax, 4 * k0); ++kk) {
+        const int64_t np = (int64_t)kk * ppp, nbk = std::min<int64_t>(batch, np);
+        const double waste = (double)(cdiv(np, nbk) * nbk - np) / (double)np;
+        if (waste < best - 1e-12) { best = waste; k = kk; }
+    }
+    const int64_t chunk_patches = (int64_t)k * ppp;
+    const int nb = (int)std::min<int64_t>(batch, chunk_patches);
+    const int nchunks = (int)cdiv(n_planes, k);
+    const int kind = m->head_sigmoid ? RFI_VALUES_PROBS : RFI_VALUES_LOGITS;
+
+    // the chunk's patch table (plane indices local to the chunk; the same for every chunk, a prefix for the last)
+    std::vector<rfi_patch_src> table((size_t)chunk_patches);
+    {
+        const int nC = (int)(tiling_patches_per_plane(c, 1, rfi_tiling{ps, tiling->stride, tiling->edge, 1}));
+        const int nT = (int)(tiling_patches_per_plane(1, t, rfi_tiling{ps, tiling->stride, tiling->edge, 1}));
+        auto origin = [&](int i, int n, int L) {
+            return (tiling->edge == RFI_EDGE_SHIFT && i == n - 1 && L > ps) ? L - ps : i * tiling->stride;
+        };
+        size_t e = 0;
+        for (int p = 0; p < k; ++p)
+            for (int v = 0; v < tiling->views; ++v) {
+                const bool tr = v >= 2;
+                const int nr = tr ? nT : nC, nc = tr ? nC : nT, Hv = tr ? t : c, Wv = tr ? c : t;
+                for (int i = 0; i < nr; ++i)
+                    for (int j = 0; j < nc; ++j) table[e++] = rfi_patch_src{p, v, origin(i, nr, Hv), origin(j, nc, Wv)};
+            }
+    }
+
+    // one grow-only scratch region: [table | the gather's own | images | patch outputs | 2 plane slots | 2 output slots]
+    const size_t b_table = al(table.size() * sizeof(rfi_patch_src)), b_gws = al(g.ws_bytes(nb, n_planes));
+    const size_t b_img = al((size_t)nb * patch_px * g.in_ch * sizeof(float)), b_out = al((size_t)chunk_patches * patch_px * sizeof(float));
+    const size_t b_in = host_in ? al((size_t)k * plane_bytes) : 0;
+    const size_t b_fl = host_fl ? al((size_t)k * plane_px) : 0, b_pr = host_pr ? al((size_t)k * plane_px * sizeof(float)) : 0;
+    char* base = static_cast<char*>(ctx->get_scratch(b_table + b_gws + b_img + b_out + 2 * (b_in + b_fl + b_pr)));
+    auto* d_table = reinterpret_cast<rfi_patch_src*>(base);
+    void* d_gws = base + b_table;
+    float* d_img = reinterpret_cast<float*>(base + b_table + b_gws);
+    float* d_out = reinterpret_cast<float*>(base + b_table + b_gws + b_img);
+    char* slots = base + b_table + b_gws + b_img + b_out;
+    auto in_slot = [&](int s) { return slots + s * b_in; };
+    auto fl_slot = [&](int s) { return reinterpret_cast<uint8_t*>(slots + 2 * b_in + s * b_fl); };
+    auto pr_slot = [&](int s) { return reinterpret_cast<float*>(slots + 2 * (b_in + b_fl) + s * b_pr); };
+    RFI_CHECK_HIP(hipMemcpyAsync(d_table, table.data(), table.size() * sizeof(rfi_patch_src), hipMemcpyHostToDevice,
+                                 ctx->stream));
+    RFI_CHECK_HIP(hipMemsetAsync(d_img, 0, b_img, ctx->stream));
+    g.setup(ctx, d_gws, n_planes);
+
+    TmpStream cs;
+    TmpEvents ev(8);          // [0,1] upload done, [2,3] slot read by the gathers, [4,5] outputs ready, [6,7] outputs copied
+    Drain drain{ctx, cs.s};   // every exit (an exception included) leaves both streams idle
+    const char* src = static_cast<const char*>(planes);
+    auto planes_in = [&](int ci) { return std::min(k, n_planes - ci * k); };
+    auto upload = [&](int ci) {
+        const int s = ci & 1;
+        if (ci >= 2) RFI_CHECK_HIP(hipStreamWaitEvent(cs.s, ev.e[2 + s], 0));
+        OnStream on(ctx, cs.s);
+        ProfScope pf(ctx, FAM_PREPROCESS, 0, (double)planes_in(ci) * plane_bytes, "predict_upload");
+        RFI_CHECK_HIP(hipMemcpyAsync(in_slot(s), src + (size_t)ci * k * plane_bytes, (size_t)planes_in(ci) * plane_bytes,
+                                     hipMemcpyHostToDevice, cs.s));
+        RFI_CHECK_HIP(hipEventRecord(ev.e[s], cs.s));
+    };
+    auto download = [&](int ci) {
+        const int s = ci & 1;
+        const size_t px = (size_t)planes_in(ci) * plane_px, off = (size_t)ci * k * plane_px;
+        RFI_CHECK_HIP(hipStreamWaitEvent(cs.s, ev.e[4 + s], 0));
+        OnStream on(ctx, cs.s);
+        ProfScope pf(ctx, FAM_PREPROCESS, 0, (double)px * out_px_bytes, "predict_download");
+        if (host_fl) RFI_CHECK_HIP(hipMemcpyAsync(flags + off, fl_slot(s), px, hipMemcpyDeviceToHost, cs.s));
+        if (host_pr) RFI_CHECK_HIP(hipMemcpyAsync(prob + off, pr_slot(s), px * sizeof(float), hipMemcpyDeviceToHost, cs.s));
+        RFI_CHECK_HIP(hipEventRecord(ev.e[6 + s], cs.s));
+    };
+    auto compute = [&](int ci) {
+        const int s = ci & 1, np = planes_in(ci);
+        const int64_t npatch = (int64_t)np * ppp;
+        const void* pl = host_in ? static_cast<const void*>(in_slot(s)) : static_cast<const void*>(src + (size_t)ci * k * plane_bytes);
+        if (host_in) RFI_CHECK_HIP(hipStreamWaitEvent(ctx->stream, ev.e[s], 0));
+        if ((host_fl || host_pr) && ci >= 2) RFI_CHECK_HIP(hipStreamWaitEvent(ctx->stream, ev.e[6 + s], 0));
+        for (int64_t p0 = 0; p0 < npatch; p0 += nb) {
+            const int nv = (int)std::min<int64_t>(nb, npatch - p0);
+            g.run(ctx, pl, dtype, ci * k, c, t, d_table + p0, nv, ps, d_gws, d_img);
+            if (p0 + nb >= npatch) RFI_CHECK_HIP(hipEventRecord(ev.e[2 + s], ctx->stream));
+            m->forward(d_img, nb, ps, ps, false);
+            launch_copy_d2d(ctx, d_out + p0 * patch_px, m->buf(m->head_sigmoid ? m->probs : m->logits),
+                            (size_t)nv * patch_px * sizeof(float));
+        }
+        const size_t off = (size_t)ci * k * plane_px;
+        launch_stitch(ctx, d_out, kind, np, c, t, *tiling, combine, threshold, host_fl ? fl_slot(s) : flags + off,
+                      prob ? (host_pr ? pr_slot(s) : prob + off) : nullptr);
+        RFI_CHECK_HIP(hipEventRecord(ev.e[4 + s], ctx->stream));
+    };
+    if (host_in) upload(0);
+    for (int ci = 0; ci < nchunks; ++ci) {
+        compute(ci);
+        if (ci > 0 && (host_fl || host_pr)) download(ci - 1);
+        if (host_in && ci + 1 < nchunks) upload(ci + 1);
+    }
+    if (host_fl || host_pr) download(nchunks - 1);
+    RFI_CHECK_HIP(hipStreamSynchronize(cs.s));
+    RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+}
+}  // namespace
+
 int rfi_model_predict_flags(rfi_model* m, const void* planes, int planes_mem, int dtype, int n_planes, int c, int t,
                             const rfi_tiling* tiling, int batch, int combine, float threshold, uint8_t* flags,
                             int flags_mem, float* prob, int prob_mem) {
     return guarded([&] {
-        RFI_REQUIRE(m && planes && flags && tiling, "predict_flags: null argument");
-        RFI_REQUIRE(dtype == RFI_C128 || dtype == RFI_C64,
-                    "predict_flags: planes must be complex128 or complex64 (real input: Preprocessor + rfi_stitch_patches)");
-        RFI_REQUIRE(n_planes >= 0 && c > 0 && t > 0 && batch > 0, "predict_flags: bad shape or batch");
-        RFI_REQUIRE(m->in_ch == 3 && m->out_ch == 1 && m->out_scale == 1,
-                    "predict_flags: needs a model with 3 input channels, 1 output channel and an output map the size of its input");
-        RFI_REQUIRE(combine == RFI_COMBINE_MEAN || combine == RFI_COMBINE_MAX, "predict_flags: combine must be mean (0) or max (1)");
-        check_tiling(*tiling);
-        if (n_planes == 0) return;
-        rfi_ctx* ctx = m->ctx;
-        ctx->activate();
-        const int ps = tiling->ps;
-        const int64_t ppp = tiling_patches_per_plane(c, t, *tiling);
-        const size_t esz = dtype_bytes(dtype);
-        const size_t plane_px = (size_t)c * t, plane_bytes = plane_px * esz, patch_px = (size_t)ps * ps;
-        const bool host_in = planes_mem == RFI_HOST, host_fl = flags_mem == RFI_HOST, host_pr = prob && prob_mem == RFI_HOST;
-        const size_t out_px_bytes = (host_fl ? 1 : 0) + (host_pr ? 4 : 0);
-        const size_t per_plane = (size_t)ppp * (patch_px * sizeof(float) + sizeof(rfi_patch_src)) +
-                                 (host_in ? 2 * plane_bytes : 0) + 2 * plane_px * out_px_bytes;
-        RFI_REQUIRE(per_plane <= kPredictBudget,
-                    "predict_flags: one " + std::to_string(c) + " x " + std::to_string(t) + " plane needs " +
-                        std::to_string(per_plane >> 20) + " MiB of workspace at this tiling (" + std::to_string(ppp) +
-                        " patches of " + std::to_string(ps) + "^2), over the budget of " +
-                        std::to_string(kPredictBudget >> 20) + " MiB; planes are not split: use a larger stride, fewer views "
-                        "or smaller planes");
-        // planes per chunk: at least ~4 batches of patches, no more than the budget holds; among up to 4x that, the one
-        // whose last batch wastes the smallest share of slots
-        const int kmax = (int)std::min<size_t>((size_t)n_planes, kPredictBudget / per_plane);
-        const int k0 = (int)std::min<int64_t>(kmax, std::max<int64_t>(1, cdiv(4 * (int64_t)batch, ppp)));
-        int k = k0;
-        double best = 2.0;
-        for (int kk = k0; kk <= std::min(kmax, 4 * k0); ++kk) {
-            const int64_t np = (int64_t)kk * ppp, nbk = std::min<int64_t>(batch, np);
-            const double waste = (double)(cdiv(np, nbk) * nbk - np) / (double)np;
-            if (waste < best - 1e-12) { best = waste; k = kk; }
-        }
-        const int64_t chunk_patches = (int64_t)k * ppp;
-        const int nb = (int)std::min<int64_t>(batch, chunk_patches);
-        const int nchunks = (int)cdiv(n_planes, k);
-        const int kind = m->head_sigmoid ? RFI_VALUES_PROBS : RFI_VALUES_LOGITS;
+        ChannelGather g;
+        predict_flags_driver(m, g, planes, planes_mem, dtype, n_planes, c, t, tiling, batch, combine, threshold, flags, flags_mem,
+                             prob, prob_mem);
+    });
+}
 
-        // the chunk's patch table (plane indices local to the chunk; the same for every chunk, a prefix for the last)
-        std::vector<rfi_patch_src> table((size_t)chunk_patches);
-        {
-            const int nC = (int)(tiling_patches_per_plane(c, 1, rfi_tiling{ps, tiling->stride, tiling->edge, 1}));
-            const int nT = (int)(tiling_patches_per_plane(1, t, rfi_tiling{ps, tiling->stride, tiling->edge, 1}));
-            auto origin = [&](int i, int n, int L) {
-                return (tiling->edge == RFI_EDGE_SHIFT && i == n - 1 && L > ps) ? L - ps : i * tiling->stride;
-            };
-            size_t e = 0;
-            for (int p = 0; p < k; ++p)
-                for (int v = 0; v < tiling->views; ++v) {
-                    const bool tr = v >= 2;
-                    const int nr = tr ? nT : nC, nc = tr ? nC : nT, Hv = tr ? t : c, Wv = tr ? c : t;
-                    for (int i = 0; i < nr; ++i)
-                        for (int j = 0; j < nc; ++j) table[e++] = rfi_patch_src{p, v, origin(i, nr, Hv), origin(j, nc, Wv)};
-                }
-        }
-
-        // one grow-only scratch region: [table | min/max words | images | patch outputs | 2 plane slots | 2 output slots]
-        const size_t b_table = al(table.size() * sizeof(rfi_patch_src)), b_mm = al((size_t)nb * 4 * sizeof(unsigned long long));
-        const size_t b_img = al((size_t)nb * patch_px * 3 * sizeof(float)), b_out = al((size_t)chunk_patches * patch_px * sizeof(float));
-        const size_t b_in = host_in ? al((size_t)k * plane_bytes) : 0;
-        const size_t b_fl = host_fl ? al((size_t)k * plane_px) : 0, b_pr = host_pr ? al((size_t)k * plane_px * sizeof(float)) : 0;
-        char* base = static_cast<char*>(ctx->get_scratch(b_table + b_mm + b_img + b_out + 2 * (b_in + b_fl + b_pr)));
-        auto* d_table = reinterpret_cast<rfi_patch_src*>(base);
-        float* d_mm = reinterpret_cast<float*>(base + b_table);
-        float* d_img = reinterpret_cast<float*>(base + b_table + b_mm);
-        float* d_out = reinterpret_cast<float*>(base + b_table + b_mm + b_img);
-        char* slots = base + b_table + b_mm + b_img + b_out;
-        auto in_slot = [&](int s) { return slots + s * b_in; };
-        auto fl_slot = [&](int s) { return reinterpret_cast<uint8_t*>(slots + 2 * b_in + s * b_fl); };
-        auto pr_slot = [&](int s) { return reinterpret_cast<float*>(slots + 2 * (b_in + b_fl) + s * b_pr); };
-        RFI_CHECK_HIP(hipMemcpyAsync(d_table, table.data(), table.size() * sizeof(rfi_patch_src), hipMemcpyHostToDevice,
-                                     ctx->stream));
-        RFI_CHECK_HIP(hipMemsetAsync(d_img, 0, b_img, ctx->stream));
-
-        TmpStream cs;
-        TmpEvents ev(8);          // [0,1] upload done, [2,3] slot read by the gathers, [4,5] outputs ready, [6,7] outputs copied
-        Drain drain{ctx, cs.s};   // every exit (an exception included) leaves both streams idle
-        const char* src = static_cast<const char*>(planes);
-        auto planes_in = [&](int ci) { return std::min(k, n_planes - ci * k); };
-        auto upload = [&](int ci) {
-            const int s = ci & 1;
-            if (ci >= 2) RFI_CHECK_HIP(hipStreamWaitEvent(cs.s, ev.e[2 + s], 0));
-            OnStream on(ctx, cs.s);
-            ProfScope pf(ctx, FAM_PREPROCESS, 0, (double)planes_in(ci) * plane_bytes, "predict_upload");
-            RFI_CHECK_HIP(hipMemcpyAsync(in_slot(s), src + (size_t)ci * k * plane_bytes, (size_t)planes_in(ci) * plane_bytes,
-                                         hipMemcpyHostToDevice, cs.s));
-            RFI_CHECK_HIP(hipEventRecord(ev.e[s], cs.s));
-        };
-        auto download = [&](int ci) {
-            const int s = ci & 1;
-            const size_t px = (size_t)planes_in(ci) * plane_px, off = (size_t)ci * k * plane_px;
-            RFI_CHECK_HIP(hipStreamWaitEvent(cs.s, ev.e[4 + s], 0));
-            OnStream on(ctx, cs.s);
-            ProfScope pf(ctx, FAM_PREPROCESS, 0, (double)px * out_px_bytes, "predict_download");
-            if (host_fl) RFI_CHECK_HIP(hipMemcpyAsync(flags + off, fl_slot(s), px, hipMemcpyDeviceToHost, cs.s));
-            if (host_pr) RFI_CHECK_HIP(hipMemcpyAsync(prob + off, pr_slot(s), px * sizeof(float), hipMemcpyDeviceToHost, cs.s));
-            RFI_CHECK_HIP(hipEventRecord(ev.e[6 + s], cs.s));
-        };
-        auto compute = [&](int ci) {
-            const int s = ci & 1, np = planes_in(ci);
-            const int64_t npatch = (int64_t)np * ppp;
-            const void* pl = host_in ? static_cast<const void*>(in_slot(s)) : static_cast<const void*>(src + (size_t)ci * k * plane_bytes);
-            if (host_in) RFI_CHECK_HIP(hipStreamWaitEvent(ctx->stream, ev.e[s], 0));
-            if ((host_fl || host_pr) && ci >= 2) RFI_CHECK_HIP(hipStreamWaitEvent(ctx->stream, ev.e[6 + s], 0));
-            for (int64_t p0 = 0; p0 < npatch; p0 += nb) {
-                const int nv = (int)std::min<int64_t>(nb, npatch - p0);
-                launch_preprocess(ctx, pl, dtype, nv, ps, ps, d_mm, d_img, d_table + p0, c, t);
-                if (p0 + nb >= npatch) RFI_CHECK_HIP(hipEventRecord(ev.e[2 + s], ctx->stream));
-                m->forward(d_img, nb, ps, ps, false);
-                launch_copy_d2d(ctx, d_out + p0 * patch_px, m->buf(m->head_sigmoid ? m->probs : m->logits),
-                                (size_t)nv * patch_px * sizeof(float));
-            }
-            const size_t off = (size_t)ci * k * plane_px;
-            launch_stitch(ctx, d_out, kind, np, c, t, *tiling, combine, threshold, host_fl ? fl_slot(s) : flags + off,
-                          prob ? (host_pr ? pr_slot(s) : prob + off) : nullptr);
-            RFI_CHECK_HIP(hipEventRecord(ev.e[4 + s], ctx->stream));
-        };
-        if (host_in) upload(0);
-        for (int ci = 0; ci < nchunks; ++ci) {
-            compute(ci);
-            if (ci > 0 && (host_fl || host_pr)) download(ci - 1);
-            if (host_in && ci + 1 < nchunks) upload(ci + 1);
-        }
-        if (host_fl || host_pr) download(nchunks - 1);
-        RFI_CHECK_HIP(hipStreamSynchronize(cs.s));
-        RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+int rfi_model_predict_flags_pol(rfi_model* m, const void* planes, int planes_mem, int dtype, int n_samples, int c, int t,
+                                const rfi_tiling* tiling, int batch, int combine, float threshold, double centre,
+                                double scale, const double (*params_host)[2], uint8_t* flags, int flags_mem, float* prob,
+                                int prob_mem) {
+    return guarded([&] {
+        PolGather g(centre, scale, params_host ? params_host[0] : nullptr);
+        predict_flags_driver(m, g, planes, planes_mem, dtype, n_samples, c, t, tiling, batch, combine, threshold, flags, flags_mem,
+                             prob, prob_mem);
     });
 }
 

@@ -361,7 +361,7 @@ __global__ __launch_bounds__(kBlock) void ns_apply_kernel(const S* src, float* d
     }
     float o[8];
 #pragma unroll
-    for (int c = 0; c < 8; ++c) o[c] = scale == 0.0 ? 0.0f : (float)(((double)v[c] - centre) / scale);
+    for (int c = 0; c < 8; ++c) o[c] = norm_value(v[c], centre, scale);
     if constexpr (DNHWC) {
         Quad<float>* q = reinterpret_cast<Quad<float>*>(dst + gid * 8);
         q[0] = Quad<float>{{o[0], o[1], o[2], o[3]}};

@@ -389,6 +389,20 @@ void launch_norm_stats(rfi_ctx* ctx, const norm_chunk* chunks_dev, int n_chunks,
 // src_nhwc, (n, px, 8); dst (n, 8, px) or (n, px, 8)
 void launch_norm_apply(rfi_ctx* ctx, const void* src, int dtype, bool src_nhwc, int n, int64_t px, double centre, double scale,
                        const double* params_dev, float* dst, bool dst_nhwc);
+#if defined(__HIPCC__)
+// the normalised value of one source scalar, for every kernel that normalises (ns_apply_kernel, pol_gather_kernel): fp64
+// on the exact source value, a real division, one rounding; a pair with scale 0 stands for the all-zeros transform
+template <typename S>
+__device__ __forceinline__ float norm_value(S x, double centre, double scale) {
+    return scale == 0.0 ? 0.0f : (float)(((double)x - centre) / scale);
+}
+#endif
+// tiling, views, polarisation stacking and normalisation in one pass (pol_gather.hip; semantics in include/rfi_hip.h,
+// rfi_norm_gather): planes (n_samples, 4, C, T) RFI_C128 / RFI_C64 on the device, patch i is the ps x ps tile
+// table_dev[i] names of sample table_dev[i].plane -> out_nhwc (n, ps, ps, 8); params_dev: one (centre, scale) pair per
+// sample replacing the scalars
+void launch_pol_gather(rfi_ctx* ctx, const void* planes, int dtype, int C, int T, const rfi_patch_src* table_dev, int n, int ps,
+                       double centre, double scale, const double* params_dev, float* out_nhwc);
 // training augmentation (augment.hip): flips and one composed affine warp of x [n][h][w][c] float32 and y [n][h][w] bytes
 // into x_out / y_out (never in place); the transform of sample i is drawn in the kernel from (cfg, call, i).
 // augment_params_host evaluates the same draw on the host: gates [n][4], inv [n][6].  Semantics in include/rfi_hip.h.

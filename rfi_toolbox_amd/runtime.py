@@ -154,6 +154,19 @@ class DeviceArray:
         self.nbytes = int(np.prod(self.shape, dtype=np.int64)) * self.dtype.itemsize
         self.ptr = ctx.malloc(self.nbytes)
 
+    @classmethod
+    def borrow(cls, ctx: Context, ptr: int, shape, dtype, owner) -> "DeviceArray":
+        """A typed view of device memory that `owner` (kept referenced) holds: a slice of a DeviceArray or of a CUDA
+        tensor, for the functions that take a DeviceArray.  Never freed here."""
+        if owner is None:
+            raise ValueError("a borrowed view needs the object that owns the memory")
+        v = cls.__new__(cls)
+        v.ctx, v.shape, v.dtype = ctx, tuple(int(s) for s in shape), np.dtype(dtype)
+        v.nbytes = int(np.prod(v.shape, dtype=np.int64)) * v.dtype.itemsize
+        v.ptr, v._owner = None, owner              # (`ptr` is set last: __del__ frees what it finds without `_owner`)
+        v.ptr = int(ptr)
+        return v
+
     def numpy(self) -> np.ndarray:
         out = np.empty(self.shape, dtype=self.dtype)
         if self.nbytes:
@@ -172,7 +185,7 @@ class DeviceArray:
 
     def __del__(self):
         try:
-            if getattr(self, "ptr", None):
+            if getattr(self, "ptr", None) and getattr(self, "_owner", None) is None:
                 self.ctx.free(self.ptr)
                 self.ptr = None
         except Exception:
