@@ -866,6 +866,48 @@ int rfi_op_match_instances(rfi_ctx* ctx, const float* iou, const float* scores, 
                            const int32_t* gt_labels, const int32_t* gt_count, int n, int d, int g, const float* thresholds, int t,
                            int class_aware, int32_t* det_match, int32_t* gt_match);
 
+/* ---- instance stitch: the detections of the tiles of an observation -> one event per emitter of the whole plane
+ *      (csrc/instance_stitch.hip; rfi_toolbox_amd/inference.py stitch_instances, detect_observation).  The instance counterpart
+ *      of rfi_stitch_patches.  Not in the reference; tests/instance_stitch_ref.py restates every rule in NumPy and the results
+ *      are equal bit for bit.
+ *
+ *      Input: the detections of N = n_planes x patches_per_plane tiles in rfi_tiling order, in the layout of
+ *      MaskRCNN.detect(out="device"): boxes float32 [N][D][4] xyxy in tile coordinates, scores float32 [N][D], labels int32 [N][D],
+ *      counts int32 [N] (cut to 0 .. D), masks uint8 [N][D][ps][ps], any non-zero byte foreground; 1 <= D <= 256; slot j of
+ *      tile i is valid when j < counts[i], and nothing behind a count is read.
+ *
+ *      Geometry (what rfi_stitch_patches inverts): tile pixel (r, c) of a tile with origin (row0, col0) in view v is view
+ *      pixel (row0 + r, col0 + c), dropped when it lies past the view's edge (padding); the views are plane, plane[::-1, :],
+ *      plane.T, plane.T[::-1, :].  A tile's rectangle is the image of its non-padding pixels in plane coordinates.  A box maps
+ *      with the same transform in float32, one operation per step: add the origin as float (x += col0, y += row0); a mirrored
+ *      view (1, 3) makes y = (float)L - y with L the view's row count; a transposed view (2, 3) swaps x and y; x1 <= x2 and
+ *      y1 <= y2 are restored by swapping the pair; clip x to [0, T] and y to [0, C].
+ *
+ *      Members: a valid slot with score >= min_score whose mask has at least min_area (>= 1) non-zero pixels inside the plane.
+ *      Links: two members of one plane are linked when they come from different tiles, carry the same label (class_aware != 0
+ *      only), and either their tile rectangles intersect and the two masks share a plane pixel, or their tile rectangles are
+ *      disjoint and a pixel of one is adjacent to a pixel of the other (connectivity 8: Chebyshev distance 1; 4: Manhattan
+ *      distance 1).  Members of one tile are never linked.
+ *      Events: the connected components of the link graph.  id = the smallest member index i D + j; mask = OR of the members'
+ *      masks on the plane; box = min / min / max / max of the members' mapped boxes; score = the maximum member score; label =
+ *      the label of the member with the highest score, ties to the smaller member index (with class_aware the common label).
+ *      Output per plane: events by descending score, ties to the smaller id; the first max_events (1 .. 256 = E) are written:
+ *      out_boxes float32 [P][E][4], out_scores [P][E], out_labels int32 [P][E], out_counts int32 [P], out_masks uint8
+ *      [P][E][C][T] (0 / 1; NULL = not wanted), all zero behind out_counts.  rfi_mask uint8 [P][C][T] is the OR of ALL members'
+ *      masks, whether or not the cap cut their event: flags do not depend on max_events.
+ *
+ *      Known limit: the link test is boolean.  Two same-class emitters that touch across a seam merge, and with overlapping
+ *      tiles two same-class emitters that cross merge; the simulator's families put crossing lines in different classes, so
+ *      class_aware keeps those apart.
+ *
+ *      Limits: n_planes <= 65535, C T < 2^31, N D < 2^31, patches_per_plane x D <= 65536 (one sort segment per plane).
+ *      Device pointers aligned to their element size (masks aligned to 16 bytes with ps % 16 == 0 are read with 16-byte
+ *      loads); stream-ordered: nothing is synchronised, the workspace is the context's grow-only scratch. ---- */
+int rfi_stitch_instances(rfi_ctx* ctx, const float* boxes, const float* scores, const int32_t* labels, const int32_t* counts,
+                         const uint8_t* masks, int n_planes, int c, int t, const rfi_tiling* tiling, int d, int max_events, int min_area,
+                         float min_score, int class_aware, int connectivity, float* out_boxes, float* out_scores, int32_t* out_labels,
+                         int32_t* out_counts, uint8_t* rfi_mask, uint8_t* out_masks);
+
 /* ---- kernel-level entry points (device pointers only).  Used by the parity tests to
  *      check each HIP kernel against the oracle in isolation.  impl: 0 auto, 1 direct VALU,
  *      2 MFMA implicit GEMM in native float32 (v_mfma_f32_32x32x2_f32), 3 MFMA implicit GEMM with bfloat16

@@ -18,4 +18,6 @@ def __getattr__(name):
         return getattr(importlib.import_module(f"{__name__}.components"), name)
     if name in ("event_instances", "event_table", "EVENT_CLASSES"):
         return getattr(importlib.import_module(f"{__name__}.core"), name)
+    if name in ("stitch_instances", "detect_observation"):
+        return getattr(importlib.import_module(f"{__name__}.inference"), name)
     raise AttributeError(name)

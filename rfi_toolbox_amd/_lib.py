@@ -252,6 +252,8 @@ _PROTOS = {
     "rfi_op_mask_iou": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _vp, _vp]),
     "rfi_op_box_iou": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "rfi_op_match_instances": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
+    "rfi_stitch_instances": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.POINTER(Tiling), _i, _i, _i, _f, _i, _i,
+                                  _vp, _vp, _vp, _vp, _vp, _vp]),
     "rfi_op_conv3x3": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     "rfi_op_conv1x1": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     "rfi_op_conv_s2": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),

@@ -45,5 +45,18 @@ int rfi_op_match_instances(rfi_ctx* ctx, const float* iou, const float* scores, 
                                gt_match);
     });
 }
+int rfi_stitch_instances(rfi_ctx* ctx, const float* boxes, const float* scores, const int32_t* labels, const int32_t* counts,
+                         const uint8_t* masks, int n_planes, int c, int t, const rfi_tiling* tiling, int d, int max_events, int min_area,
+                         float min_score, int class_aware, int connectivity, float* out_boxes, float* out_scores, int32_t* out_labels,
+                         int32_t* out_counts, uint8_t* rfi_mask, uint8_t* out_masks) {
+    return guarded([&] {
+        RFI_REQUIRE(ctx && boxes && scores && labels && counts && masks && tiling && out_boxes && out_scores && out_labels && out_counts &&
+                        rfi_mask,
+                    "stitch_instances: null argument");
+        ctx->activate();
+        launch_stitch_instances(ctx, boxes, scores, labels, counts, masks, n_planes, c, t, *tiling, d, max_events, min_area, min_score,
+                                class_aware, connectivity, out_boxes, out_scores, out_labels, out_counts, rfi_mask, out_masks);
+    });
+}
 
 }  // extern "C"

@@ -22,6 +22,7 @@
 
 #include "kernels.hpp"
 #include "launch_common.hpp"
+#include "union_find.hpp"
 
 namespace rfi {
 namespace {
@@ -35,32 +36,8 @@ static_assert(kTilePx == kBlock * kPerThread, "a thread labels kPerThread pixels
 __device__ __forceinline__ bool nonzero(uint8_t v) { return v != 0; }
 __device__ __forceinline__ bool nonzero(float v) { return v != 0.0f; }      // (NaN is non-zero, as in NumPy)
 
-// ---- union-find.  A plain load (each one issued) serves LDS, which is coherent inside the workgroup, and global memory that
-// no running launch writes; the merging launch reads with agent-scope loads.
-struct PlainLoad {
-    __device__ __forceinline__ int operator()(const int* p) const { return *reinterpret_cast<const volatile int*>(p); }
-};
-struct AgentLoad {
-    __device__ __forceinline__ int operator()(const int* p) const { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-};
-template <class Load> __device__ __forceinline__ int find_root(const int* L, int a, Load ld) {
-    // terminates: a non-root's parent is smaller than itself, so `a` strictly decreases: at most H W steps
-    for (int p = ld(L + a); p != a; p = ld(L + a)) a = p;
-    return a;
-}
-template <class Load> __device__ __forceinline__ void unite(int* L, int a, int b, Load ld) {
-    // terminates: a pass that does not end the loop replaces the larger of (a, b) by the value atomicMin returned, which is
-    // smaller than it (somebody else hung that root lower in the meantime); a + b strictly decreases: at most 2 H W passes
-    for (;;) {
-        a = find_root(L, a, ld);
-        b = find_root(L, b, ld);
-        if (a == b) return;
-        if (a > b) { const int t = a; a = b; b = t; }
-        const int old = atomicMin(L + b, a);        // b was a root iff the word still held b
-        if (old == b) return;
-        b = old;
-    }
-}
+// (union-find: PlainLoad / AgentLoad, find_root, unite -- union_find.hpp; find_root takes at most H W steps here, unite at
+// most 2 H W passes)
 
 // ---- 1: label one tile in LDS.  grid (tiles of a plane, row-major; planes)
 template <typename T>

@@ -468,6 +468,12 @@ void launch_box_iou(rfi_ctx* ctx, const float* det_boxes, const int* det_count, 
 void launch_match_instances(rfi_ctx* ctx, const float* iou, const float* scores, const int* det_labels, const int* det_count,
                             const int* gt_labels, const int* gt_count, int n, int D, int G, const float* thresholds, int T, int class_aware,
                             int* det_match, int* gt_match);
+// instance stitch (instance_stitch.hip; semantics in include/rfi_hip.h, "instance stitch").  Device pointers; stream-ordered;
+// the workspace is the context's grow-only scratch.  out_masks may be null.
+void launch_stitch_instances(rfi_ctx* ctx, const float* boxes, const float* scores, const int* labels, const int* counts,
+                             const uint8_t* masks, int n_planes, int C, int T, const rfi_tiling& tiling, int D, int max_events,
+                             int min_area, float min_score, int class_aware, int connectivity, float* out_boxes, float* out_scores,
+                             int* out_labels, int* out_counts, uint8_t* rfi_mask, uint8_t* out_masks);
 // RFISimulator waterfalls (rfi_sim.hip): draws the event table into `events` (unless p.clean), then one gather per
 // pixel into `out` (layout RFI_SIM_*) and `mask`; sizes are checked by rfi_simulate_rfi
 void launch_rfi_sim(rfi_ctx* ctx, unsigned long long seed, unsigned first_sample, int n_samples,

@@ -31,7 +31,8 @@ from ._lib import (COMBINE_MAX, COMBINE_MEAN, COMPLEX_CODES, DEVICE, EDGE_PAD, E
                    VALUES_PROBS, Tiling, check, lib)
 from .runtime import DeviceArray, check_out, context_for, describe, is_torch, operand, result_buffer, torch
 
-__all__ = ["predict_flags", "tile_observation", "stitch_patches", "tiling_count", "check_tiling_args"]
+__all__ = ["predict_flags", "tile_observation", "stitch_patches", "tiling_count", "check_tiling_args", "stitch_instances",
+           "detect_observation"]
 
 _COMBINE = {"mean": COMBINE_MEAN, "max": COMBINE_MAX}
 _EDGE = {"pad": EDGE_PAD, "shift": EDGE_SHIFT}
@@ -321,3 +322,195 @@ def stitch_patches(values, channels, times, patch_size, stride=None, views=1, ed
                                      C.c_void_p(fp), omem, C.c_void_p(pp) if pp else None, omem))
     del o
     return (_as_bool(flags), prob) if return_probabilities else _as_bool(flags)
+
+
+# ---------------------------------------------------------------------------------------------- instances of a whole observation
+_STITCH_BYTES = 1 << 30               # tile masks plus outputs of one chunk of detect_observation (predict_flags' bound)
+_STITCH_MAX_SLOTS = 65536             # patches per plane x D: the ranking sorts one segment per plane
+
+
+def _check_stitch_args(max_events, min_area, min_score, connectivity, out):
+    if not isinstance(max_events, (int, np.integer)) or not 1 <= max_events <= 256:
+        raise ValueError(f"max_events must be an integer in 1 .. 256, got {max_events!r}")
+    if not isinstance(min_area, (int, np.integer)) or min_area < 1:
+        raise ValueError(f"min_area must be an integer of at least 1, got {min_area!r}")
+    if not isinstance(min_score, (int, float, np.integer, np.floating)) or not np.isfinite(min_score):
+        raise ValueError(f"min_score must be a finite number, got {min_score!r}")
+    if connectivity not in (4, 8):
+        raise ValueError(f"connectivity must be 4 or 8, got {connectivity!r}")
+    check_out(out)
+
+
+def _check_plane(channels, times, ps, s, views, edge, D):
+    """-> (C, T, patches per plane) of a stitch; ValueError for a plane the kernels do not take."""
+    if not isinstance(channels, (int, np.integer)) or not isinstance(times, (int, np.integer)) or channels <= 0 or times <= 0:
+        raise ValueError(f"channels and times must be positive integers, got {channels!r}, {times!r}")
+    Cn, Tn = int(channels), int(times)
+    if Cn * Tn >= 1 << 31:
+        raise ValueError(f"planes of fewer than 2^31 pixels, got {Cn} x {Tn}")
+    ppp = tiling_count(Cn, Tn, ps, s, views, edge)
+    if ppp * D > _STITCH_MAX_SLOTS:
+        raise ValueError(f"{ppp} patches per plane x {D} detection slots exceed {_STITCH_MAX_SLOTS}: use a larger stride, fewer "
+                         "views or a smaller max_det")
+    return Cn, Tn, ppp
+
+
+def _run_stitch(ctx, ptrs, n_planes, Cn, Tn, tiling, D, E, min_area, min_score, class_aware, connectivity, res, plane0=0):
+    """rfi_stitch_instances on device pointers `ptrs` (boxes, scores, labels, counts, masks) into the result dict `res`
+    from its plane `plane0` on."""
+    off = lambda k, per: C.c_void_p(res[k].ptr + plane0 * per * res[k].dtype.itemsize)  # noqa: E731
+    check(lib.rfi_stitch_instances(ctx.handle, *[C.c_void_p(p) for p in ptrs], n_planes, Cn, Tn, C.byref(tiling), D, E, int(min_area),
+                                   float(min_score), 1 if class_aware else 0, int(connectivity), off("boxes", E * 4), off("scores", E),
+                                   off("labels", E), off("counts", 1), off("rfi_mask", Cn * Tn),
+                                   off("masks", E * Cn * Tn) if "masks" in res else None))
+
+
+def _stitch_result(ctx, n_planes, E, Cn, Tn, instance_masks):
+    res = {"boxes": ctx.empty((n_planes, E, 4), np.float32), "scores": ctx.empty((n_planes, E), np.float32),
+           "labels": ctx.empty((n_planes, E), np.int32), "counts": ctx.empty((n_planes,), np.int32),
+           "rfi_mask": ctx.empty((n_planes, Cn, Tn), np.uint8)}
+    if instance_masks:
+        res["masks"] = ctx.empty((n_planes, E, Cn, Tn), np.uint8)
+    return res
+
+
+def _events_to_host(res, n_planes):
+    """The device dict of a stitch -> ``predict``'s list of dicts, one per plane."""
+    cnt, boxes, scores, labels = (res[k].numpy() for k in ("counts", "boxes", "scores", "labels"))
+    rfi = res["rfi_mask"].numpy().astype(bool)
+    masks = res["masks"].numpy() if "masks" in res else None
+    items = []
+    for i in range(n_planes):
+        k = int(cnt[i])
+        o = {"boxes": boxes[i, :k].copy(), "scores": scores[i, :k].copy(), "labels": labels[i, :k].astype(np.int64)}
+        if masks is not None:
+            o["masks"] = masks[i, :k].astype(bool)
+        o["rfi_mask"] = rfi[i]
+        items.append(o)
+    return items
+
+
+def stitch_instances(detections, channels, times, patch_size, stride=None, views=1, edge="pad", max_events=64, min_area=1,
+                     min_score=0.0, class_aware=True, connectivity=8, instance_masks=True, out="device"):
+    """Per-tile detections back to whole planes (``rfi_stitch_instances``): one event per emitter, the instance
+    counterpart of ``stitch_patches``, for tiles from any detector.
+
+    ``detections``: the dict of ``MaskRCNN.detect(out="device")`` over the ``N`` tiles of whole ``channels x times``
+    planes in ``rfi_tiling`` order (``DeviceArray``s, NumPy arrays or torch tensors; boxes ``(N, D, 4)`` xyxy in tile
+    coordinates, scores, labels, counts, masks ``(N, D, ps, ps)``), or the list of dicts of ``predict``, padded and
+    uploaded once.  The rules are pinned in include/rfi_hip.h ("instance stitch"): a slot with ``score >= min_score`` and
+    at least ``min_area`` mask pixels inside the plane is a member; members of different tiles (with ``class_aware``: of
+    one label) are linked when their masks share a pixel where the tiles overlap, or touch (``connectivity`` 8 or 4)
+    where the tiles only abut; an event is a connected set of members with the OR of their masks, the union of their
+    mapped boxes, their best score and its label.  The link test is boolean: two emitters of one class that touch across
+    a seam, or cross inside an overlap, merge.
+
+    ``out="device"``: a dict of ``DeviceArray``s in ``detect``'s layout, so ``match_instances`` and
+    ``DetectionScorer.update`` take it unchanged -- boxes ``(P, max_events, 4)``, scores, labels (int32), counts ``(P,)``,
+    rfi_mask ``(P, C, T)`` uint8 and, with ``instance_masks``, masks ``(P, max_events, C, T)`` uint8; events by
+    descending score, zero behind ``counts``.  ``rfi_mask`` is the OR of all members, whether or not ``max_events`` cut
+    their event: the flags do not depend on the cap.  ``out="host"``: ``predict``'s list of dicts, one per plane."""
+    from .evaluation.detection import _detections
+    ps, s = check_tiling_args(patch_size, stride, views, "mean", edge)
+    _check_stitch_args(max_events, min_area, min_score, connectivity, out)
+    side = _detections(detections)
+    if side.masks is None:
+        raise ValueError("stitch_instances needs the instance masks of the tiles (detect(instance_masks=True))")
+    if tuple(side.shape) != (ps, ps):
+        raise ValueError(f"the tile masks must be {ps} x {ps}, got {tuple(side.shape)}")
+    D = max(1, side.slots)
+    Cn, Tn, ppp = _check_plane(channels, times, ps, s, views, edge, D)
+    if side.n % ppp:
+        raise ValueError(f"{side.n} tiles are not a whole number of {Cn} x {Tn} planes of {ppp} patches each")
+    n_planes, E = side.n // ppp, int(max_events)
+    arrays = [side.boxes, side.scores, side.labels, side.count, side.masks]
+    if side.slots == 0:          # (lists without a detection: one empty slot per tile)
+        arrays = [np.zeros((side.n, 1, 4), np.float32), np.zeros((side.n, 1), np.float32), np.zeros((side.n, 1), np.int32),
+                  np.zeros((side.n,), np.int32), np.zeros((side.n, 1, ps, ps), np.uint8)]
+    ctx = context_for(None, *arrays)
+    res = _stitch_result(ctx, n_planes, E, Cn, Tn, instance_masks)
+    if n_planes:
+        ops = [operand(a, ctx, (dt,), "cast", to_device=True)
+               for a, dt in zip(arrays, (np.float32, np.float32, np.int32, np.int32, np.uint8))]
+        _run_stitch(ctx, [o.ptr for o in ops], n_planes, Cn, Tn, Tiling(ps, s, _EDGE[edge], views), D, E, min_area, min_score,
+                    class_aware, connectivity, res)
+        if out == "host" or any(o.keep is not a for o, a in zip(ops, arrays)):
+            ctx.synchronize()    # (uploaded copies are dropped on return)
+        del ops
+    return res if out == "device" else _events_to_host(res, n_planes)
+
+
+def detect_observation(detector, data, patch_size=128, stride=None, views=1, edge="pad", normalizer=None, batch_size=64,
+                       max_events=64, min_area=1, min_score=0.0, class_aware=True, connectivity=8, instance_masks=False,
+                       out="host"):
+    """The events of a whole observation from a ``MaskRCNN`` with 8 input channels: tile, detect, stitch.
+
+    ``data``: complex ``(B, 4, C, T)`` or ``(4, C, T)`` visibilities in the order RR, RL, LR, LL, as in ``predict_flags``;
+    ``normalizer`` has its three forms.  The observation is streamed through in chunks of whole baselines: the tiles
+    of a chunk are cut and normalised on the GPU (``tile_observation``'s gather), ``detector.detect`` runs on them in
+    batches of ``batch_size`` tiles, and one ``stitch_instances`` per chunk joins the pieces of every emitter (its
+    rules, arguments and boolean-link limit apply).  Returns one plane of events per baseline in ``stitch_instances``'
+    two forms.  ``rfi_mask`` does not depend on ``max_events``."""
+    from .models.mask_rcnn import MaskRCNN
+    ps, s = check_tiling_args(patch_size, stride, views, "mean", edge)
+    _check_stitch_args(max_events, min_area, min_score, connectivity, out)
+    if not isinstance(batch_size, (int, np.integer)) or batch_size <= 0:
+        raise ValueError(f"batch_size must be a positive integer, got {batch_size!r}")
+    if not isinstance(detector, MaskRCNN):
+        raise TypeError(f"detect_observation needs a rfi_toolbox_amd MaskRCNN, got {type(detector).__name__}")
+    if detector.backbone.in_channels != 8:
+        raise ValueError(f"detect_observation needs a detector with 8 input channels, got {detector.backbone.in_channels}: run "
+                         "a detector of another input on tiles of your own and join its detections with stitch_instances")
+    shape, dt = _complex_input(data, "detect_observation")
+    n, Cn, Tn = _pol_shape(shape)
+    form = _normalizer_form(normalizer)
+    bs, E, D = int(batch_size), int(max_events), int(detector.max_det)
+    detector._check_detect(bs, ps, ps)
+    Cn, Tn, ppp = _check_plane(Cn, Tn, ps, s, views, edge, D)
+    px = Cn * Tn
+    per_plane = ppp * D * (ps * ps + 24) + px * (1 + (E if instance_masks else 0)) + E * 24 + 4
+    if per_plane > _STITCH_BYTES:
+        raise ValueError(f"one {Cn} x {Tn} plane needs {per_plane} bytes of tile masks and outputs, more than {_STITCH_BYTES}: lower "
+                         "max_events, pass instance_masks=False, or use a larger stride or a smaller max_det")
+    chunk = max(1, min(n, _STITCH_BYTES // per_plane))
+    tiling = Tiling(ps, s, _EDGE[edge], views)
+    ctx = detector.backbone.ctx
+    full = out == "device"                       # the device result holds every plane; the host form is read back per chunk
+    res = _stitch_result(ctx, n if full else chunk, E, Cn, Tn, instance_masks)
+    items = []
+    if not n:
+        return res if full else items
+    o = operand(data, ctx, (dt,), "cast")
+    nt = chunk * ppp
+    tiles = {"boxes": ctx.empty((nt, D, 4), np.float32), "scores": ctx.empty((nt, D), np.float32),
+             "labels": ctx.empty((nt, D), np.int32), "counts": ctx.empty((nt,), np.int32), "masks": ctx.empty((nt, D, ps, ps), np.uint8)}
+    rows = {"boxes": D * 16, "scores": D * 4, "labels": D * 4, "counts": 4, "masks": D * ps * ps}
+    x = ctx.empty((bs, ps, ps, 8), np.float32)
+    for b0 in range(0, n, chunk):
+        b1 = min(n, b0 + chunk)
+        group = _group_on_device(o, ctx, b0, b1, (4, Cn, Tn))
+        pairs = None
+        if form[0] == "sample":
+            go = operand(group, ctx, (dt,))
+            pairs = np.concatenate([_sample_pairs(normalizer, _group_on_device(go, ctx, g0, g1, (4, Cn, Tn)))
+                                    for g0, g1 in _sample_groups(b1 - b0, 4 * px * dt.itemsize)])
+        centre, scale = (form[1], form[2]) if form[0] == "pair" else (0.0, 1.0)
+        table = _patch_table(b1 - b0, Cn, Tn, ps, s, views, edge)
+        for i0 in range(0, len(table), bs):
+            k = min(bs, len(table) - i0)
+            if k < bs:
+                x.zero_()                        # the last batch is padded with zero tiles; their slots are not copied
+            part = np.ascontiguousarray(table[i0:i0 + k])
+            check(lib.rfi_norm_gather(ctx.handle, C.c_void_p(group.ptr), DEVICE, COMPLEX_CODES[dt], b1 - b0, Cn, Tn,
+                                      part.ctypes.data_as(C.c_void_p), k, ps, centre, scale,
+                                      None if pairs is None else pairs.ctypes.data_as(C.c_void_p), C.c_void_p(x.ptr), DEVICE))
+            det = detector.detect(x, instance_masks=True, out="device")      # (valid until the next call: copied now)
+            for key, w in rows.items():
+                check(lib.rfi_op_copy_rows(ctx.handle, C.c_void_p(det[key].ptr), k * w, C.c_void_p(tiles[key].ptr + i0 * w), k * w, k * w, 1))
+        _run_stitch(ctx, [tiles[key].ptr for key in ("boxes", "scores", "labels", "counts", "masks")], b1 - b0, Cn, Tn, tiling, D, E,
+                    min_area, min_score, class_aware, connectivity, res, b0 if full else 0)
+        if not full:
+            items += _events_to_host(res, b1 - b0)
+        del group
+    del o
+    return res if full else items
