@@ -246,6 +246,15 @@ int rfi_model_algorithmic_flops(rfi_model* m, int n, int h, int w, double* fwd, 
  * "encY1.<l>" "encY2.<l>" "decY1.<l>" "decY2.<l>" "concat.<l>" "pool.<l>" "bottY1" "bottY2" "logits"
  * "dlogits" "gA.<l>" "gB.<l>" "dconcat.<l>" "dpool.<l>" "gBottA" "gBottB" (raw NHWC fp32), and
  * "chan.<conv index>" = [running_mean|running_var|mean|invstd|scale|shift|c1|c2] x Cout.
+ * Plain U-Net on a plane data flow ("bfloat16", "float32_planes"): a tensor the mode stores as
+ * bfloat16 comes back as the exact float32 values of its elements, dense NHWC, under the same name;
+ * gA / gB hold the ENCODER's gradients (the decoder phase's are overwritten within the pass).
+ * The plane tensors: "xin", "a1e.<l>" "skip.<l>" "pooled.<l>" "up.<l>" "a1d.<l>" "a1b" (activations
+ * as the contractions read them), "upin.<l>" (transposed convs on the plane kernels only), "upf.<l>"
+ * (the float32 transposed-conv output, where a conversion pass follows it), "dYa.<l>" "dYb.<l>"
+ * "dYaE.<l>" "dYbE.<l>" "dYbottA" "dYbottB" (BatchNorm-backward outputs of the decoder's / encoder's /
+ * bottleneck's second and first conv).  "<name>:pad" = the padding lanes of a bfloat16 / plane
+ * tensor, [pixels][16 * chunks - C] (empty when C % 16 == 0): zeros, if the pass is right.
  * ResNet-50-FPN backbone (conv indices in state_dict order of the conv weights): "conv.<i>" raw
  * output of conv i before its frozen BatchNorm, on its own output grid (0: the stem at H/2; FPN
  * inner / layer blocks: the lateral / the pyramid level), "pool" the pooled stem, "block.<b>" the

@@ -781,16 +781,20 @@ int rfi_model_debug_tensor(rfi_model* m, const char* name, float* host, size_t h
     return guarded([&] {
         m->ctx->activate();
         RFI_REQUIRE(name && m->pN > 0, "debug_tensor: no prepared shape");
-        std::string s(name), base = s;
+        std::string s(name);
+        const bool pad = s.size() > 4 && s.compare(s.size() - 4, 4, ":pad") == 0;      // "<name>:pad": the padding lanes of a plane tensor
+        std::string core = pad ? s.substr(0, s.size() - 4) : s, base = core;
         int idx = -1;
-        auto dot = s.find('.');
+        auto dot = core.find('.');
         if (dot != std::string::npos) {
-            base = s.substr(0, dot);
-            idx = std::stoi(s.substr(dot + 1));
+            base = core.substr(0, dot);
+            idx = std::stoi(core.substr(dot + 1));
         }
         const float* src = nullptr;
         size_t n = 0;
+        CallScope sc(m->ctx);                     // (float32 copies of bfloat16 tensors live until the copy to the host is done)
         const size_t M1 = (size_t)m->pN * m->pH * m->pW * m->out_scale * m->out_scale;     // pixels of the OUTPUT map
+        RFI_REQUIRE(!pad || (base != "logits" && base != "dlogits" && base != "chan"), "debug_tensor: this tensor has no padding lanes");
         if (base == "logits") { src = m->buf(m->logits); n = M1 * m->out_ch; }
         else if (base == "dlogits") { src = m->buf(m->dlogits); n = M1 * m->out_ch; }
         else if (base == "chan") {
@@ -798,10 +802,10 @@ int rfi_model_debug_tensor(rfi_model* m, const char* name, float* host, size_t h
             src = m->convs[idx].chan;
             n = (size_t)8 * m->convs[idx].cout;
         } else {
-            m->debug_tensor(s, base, idx, host != nullptr, src, n);     // (the U-Net's tensors)
+            m->debug_tensor(s, base, idx, host != nullptr, sc, src, n);     // (the U-Net's tensors)
         }
         if (n_floats) *n_floats = (int64_t)n;
-        if (host) {
+        if (host && n) {
             RFI_REQUIRE(host_floats >= n, "debug_tensor: host buffer too small");
             RFI_CHECK_HIP(hipMemcpyAsync(host, src, n * sizeof(float), hipMemcpyDeviceToHost, m->ctx->stream));
             RFI_CHECK_HIP(hipStreamSynchronize(m->ctx->stream));

@@ -951,13 +951,16 @@ void UNetModel::set_compute_dtype(int dtype) {
     else set_planes(dtype == 1 ? 1 : (dtype == 3 ? 3 : 0));
 }
 
-void rfi_model::debug_tensor(const std::string&, const std::string&, int, bool, const float*&, size_t&) {
+void rfi_model::debug_tensor(const std::string&, const std::string&, int, bool, CallScope&, const float*&, size_t&) {
     throw Error("debug_tensor: this model exposes only logits / dlogits / chan (the U-Net and the ResNet-50-FPN backbone expose their "
                 "own tensors, the ResNet-encoder U-Net its decoder's: see rfi_hip.h)");
 }
-void UNetModel::debug_tensor(const std::string& name, const std::string& base, int idx, bool to_host, const float*& src, size_t& n) {
+void UNetModel::debug_tensor(const std::string& name, const std::string& base, int idx, bool to_host, CallScope& sc, const float*& src,
+                             size_t& n) {
+    if (planesP && !resnet_encoder) return debug_tensor_planes(name, base, idx, to_host, sc, src, n);
+    RFI_REQUIRE(name.find(':') == std::string::npos, "debug_tensor: only the plain U-Net on a plane data flow has plane tensors");
     if (resnet_encoder && (base == "encY1" || base == "encY2" || base == "pool" || base == "dpool"))
-        return rfi_model::debug_tensor(name, base, idx, to_host, src, n);
+        return rfi_model::debug_tensor(name, base, idx, to_host, sc, src, n);
     RFI_REQUIRE(!(y16_flow && planesP == 1 && (base == "encY1" || base == "encY2" || base == "decY1" || base == "bottY1" ||
                                                (base == "decY2" && idx == 1))),
                 "debug_tensor: this conv output is stored as bfloat16 in the bfloat16 compute mode");

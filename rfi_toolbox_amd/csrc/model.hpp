@@ -250,8 +250,10 @@ struct rfi_model {
     void apply(const rfi_hyper& hp, float grad_scale);
     virtual void algorithmic_flops(int n, int h, int w, double& fwd, double& step) const = 0;   // 2*M*K*N per layer
     virtual void set_compute_dtype(int dtype);        // rfi_model_set_compute_dtype's codes
-    // rfi_model_debug_tensor for names other than logits / dlogits / chan: `n` floats at `src`
-    virtual void debug_tensor(const std::string& name, const std::string& base, int idx, bool to_host, const float*& src, size_t& n);
+    // rfi_model_debug_tensor for names other than logits / dlogits / chan: `n` floats at `src` (`name` with its ":pad" suffix,
+    // base and idx without; float32 copies of bfloat16 tensors are temporaries of the call: sc)
+    virtual void debug_tensor(const std::string& name, const std::string& base, int idx, bool to_host, rfi::CallScope& sc, const float*& src,
+                              size_t& n);
 
     // ---- the parameter table (model_params.cpp).  build() registers the layers in the order of the flat buffers, which
     // is also the state_dict's: each gets its align4'd flat slots, its regions of chan_pool / wd_pool and its entries
@@ -340,7 +342,8 @@ struct UNetModel : rfi_model {
     void backward_pass(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w) override;
     void algorithmic_flops(int n, int h, int w, double& fwd, double& step) const override;
     void set_compute_dtype(int dtype) override;
-    void debug_tensor(const std::string& name, const std::string& base, int idx, bool to_host, const float*& src, size_t& n) override;
+    void debug_tensor(const std::string& name, const std::string& base, int idx, bool to_host, rfi::CallScope& sc, const float*& src,
+                      size_t& n) override;
     bool wd_split_ok() const override;
     void refresh_model_weights(rfi::Half half) override;
 
@@ -429,6 +432,9 @@ struct UNetModel : rfi_model {
     void refresh_plane_weights(rfi::Half half);      // InputGrad: + the parity-class tables
     void forward_planes(const float* x_dev, int n, int h, int w, bool train_mode);
     void backward_planes(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w);
+    // debug_tensor of the plain U-Net on a plane data flow: bfloat16 and plane tensors as float32 values, "<name>:pad"
+    void debug_tensor_planes(const std::string& name, const std::string& base, int idx, bool to_host, rfi::CallScope& sc, const float*& src,
+                             size_t& n);
 };
 
 // 3-layer CNN (model_cnn.cpp)
@@ -471,7 +477,8 @@ struct BackboneModel : rfi_model {
     void forward_pass(const float* x_dev, int n, int h, int w, bool train_mode) override;
     void backward_pass(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w) override;
     void algorithmic_flops(int n, int h, int w, double& fwd, double& step) const override;
-    void debug_tensor(const std::string& name, const std::string& base, int idx, bool to_host, const float*& src, size_t& n) override;
+    void debug_tensor(const std::string& name, const std::string& base, int idx, bool to_host, rfi::CallScope& sc, const float*& src,
+                      size_t& n) override;
     struct BBlock {
         int stage = 0, stride = 1, cin = 0, width = 0, cout = 0, lvl_in = 2, lvl = 2;      // resolution H >> lvl
         int c1 = -1, c2 = -1, c3 = -1, cd = -1;                                           // convs indices (cd: projection shortcut)

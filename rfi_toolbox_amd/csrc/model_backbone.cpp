@@ -407,7 +407,7 @@ void BackboneModel::backward_pass(const float* x_dev, const uint8_t*, int n, int
 
 // conv.<i>: raw (pre-BatchNorm) output of convs[i] on its own output grid; pool: the pooled stem; block.<b>: output of
 // Bottleneck b; merged.<i> / dmerged.<i>: the top-down merged map of FPN level i and its gradient (after a backward pass)
-void BackboneModel::debug_tensor(const std::string& name, const std::string& base, int idx, bool, const float*& src, size_t& n) {
+void BackboneModel::debug_tensor(const std::string& name, const std::string& base, int idx, bool, CallScope&, const float*& src, size_t& n) {
     auto px = [&](int lvl) { return (size_t)pN * (pH >> lvl) * (pW >> lvl); };
     if (base == "conv") {
         RFI_REQUIRE(idx >= 0 && idx < (int)convs.size(), "debug_tensor: conv index out of range");

@@ -630,6 +630,88 @@ void UNetModel::backward_resnet_planes(int n, int h, int w) {
     }
 }
 
+// What the plain U-Net leaves in HBM after a pass on a plane data flow, as float32 values (parity debugging only: no pass calls
+// this).  A tensor the mode stores as bfloat16 or as planes is converted into a temporary of the call (exact: every bf16 value
+// is a float32 value; P = 3: the sum of the pieces); "<name>:pad" returns the lanes behind the C channels of the last
+// 16-channel chunk of every pixel, [pixels][16 chunks - C] (empty when C % 16 == 0), which every consumer expects to be zero.
+// Every name is a tensor of its own that the pass writes once, except gA.<l> / gB.<l>: the decoder phase and the encoder phase
+// of the backward pass share them, so they hold the ENCODER's gradients afterwards (the decoder's are gone: not exposed).
+void UNetModel::debug_tensor_planes(const std::string& name, const std::string& base, int idx, bool to_host, CallScope& sc, const float*& src,
+                                    size_t& n) {
+    const int D = depth, P = planesP;
+    const bool pad = name.find(":pad") != std::string::npos;
+    const bool leveled = name.find('.') != std::string::npos;
+    auto lvl = [&]() { RFI_REQUIRE(leveled && idx >= 1 && idx <= D, "debug_tensor: level out of range"); return idx; };
+    auto pix = [&](int l) { return (size_t)pN * (pH >> (l - 1)) * (pW >> (l - 1)); };       // pixels of level l (D + 1: the bottleneck)
+    auto chan = [&](int l) { return feat << (l - 1); };
+    // a float32 tensor of the model
+    auto f32 = [&](int bi, size_t M, int C) {
+        RFI_REQUIRE(!pad, "debug_tensor: this tensor is stored as float32 in this mode: it has no padding lanes");
+        RFI_REQUIRE(bi >= 0 && bufs[bi].p && bufs[bi].n >= M * C, "debug_tensor: this tensor does not exist in this mode");
+        src = buf(bi);
+        n = M * C;
+    };
+    // a plane tensor of P_ pieces (bfloat16 tensors: P_ = 1), C channels per pixel
+    auto planes = [&](int pi, size_t M, int C, int P_) {
+        RFI_REQUIRE(pi >= 0 && pi < (int)pl.size() && pl[pi].p, "debug_tensor: this tensor does not exist in this mode");
+        const PlaneBuf& b = pl[pi];
+        RFI_REQUIRE(b.nchunks == plane_chunks(C) && b.used >= plane_elems((int64_t)M, C, P_), "debug_tensor: plane tensor of another shape");
+        const int Cp = 16 * b.nchunks - C;
+        n = M * (size_t)(pad ? Cp : C);
+        if (!to_host || !n) return;
+        float* tmp = sc.temp<float>(n);
+        // (the padding lanes: the last chunk's lanes C % 16 .. 15 read as Cp channels of a tensor that starts there)
+        const bf16_t* in = pad ? b.p + (size_t)(b.nchunks - 1) * P_ * 16 + (C & 15) : b.p;
+        launch_planes_to_f32(ctx, in, b.pstride, (int64_t)M, pad ? Cp : C, P_, tmp, pad ? Cp : C);
+        src = tmp;
+    };
+    // a tensor that is bfloat16 (pl[hi]) when `half`, else float32 (bufs[fi])
+    auto either = [&](bool half, int hi, int fi, size_t M, int C) { if (half) planes(hi, M, C, 1); else f32(fi, M, C); };
+    const size_t Mb = pix(D + 1);
+    const int Cb = feat << D;
+    if (base == "xin") planes(pXin, pix(1), in_ch, P);
+    else if (base == "a1e") { const int l = lvl(); planes(pA1e[l], pix(l), chan(l), P); }
+    else if (base == "skip") { const int l = lvl(); planes(pSkip[l], pix(l), chan(l), P); }
+    else if (base == "pooled") { const int l = lvl(); planes(pPool[l], pix(l) / 4, chan(l), P); }
+    else if (base == "up") { const int l = lvl(); planes(pUp[l], pix(l), chan(l), P); }
+    else if (base == "a1d") { const int l = lvl(); planes(pA1d[l], pix(l), chan(l), P); }
+    else if (base == "a1b") planes(pA1b, Mb, Cb, P);
+    else if (base == "upin") {
+        RFI_REQUIRE(convt_planes, "debug_tensor: upin exists only with the transposed convs on the plane kernels");
+        const int l = lvl();
+        planes(pUpIn[l], pix(l) / 4, 2 * chan(l), 1);
+    }
+    else if (base == "dYa") { const int l = lvl(); planes(pdYa[l], pix(l), chan(l), P); }
+    else if (base == "dYb") { const int l = lvl(); planes(pdYb[l], pix(l), chan(l), P); }
+    else if (base == "dYaE") { const int l = lvl(); planes(pdYaE[l], pix(l), chan(l), P); }
+    else if (base == "dYbE") { const int l = lvl(); planes(pdYbE[l], pix(l), chan(l), P); }
+    else if (base == "dYbottA") planes(pdYbottA, Mb, Cb, P);
+    else if (base == "dYbottB") planes(pdYbottB, Mb, Cb, P);
+    else if (base == "encY1") { const int l = lvl(); either(y16_flow, y16_flow ? yE1[l] : -1, encY1[l], pix(l), chan(l)); }
+    else if (base == "encY2") { const int l = lvl(); either(y16_flow, y16_flow ? yE2[l] : -1, encY2[l], pix(l), chan(l)); }
+    else if (base == "decY1") { const int l = lvl(); either(y16_flow, y16_flow ? yD1[l] : -1, decY1[l], pix(l), chan(l)); }
+    else if (base == "decY2") {
+        const int l = lvl();
+        const bool half = l == 1 ? y16_flow : convt_planes;
+        either(half, half ? (l == 1 ? yD2top : yD2[l]) : -1, decY2[l], pix(l), chan(l));
+    }
+    else if (base == "bottY1") either(y16_flow, yB1, bottY1, Mb, Cb);
+    else if (base == "bottY2") either(convt_planes, yB2, bottY2, Mb, Cb);
+    else if (base == "gA") {                      // (l == 1 without the bf16 gradient flow: the head wrote it as float32)
+        const int l = lvl();
+        either(g16_flow, g16_flow ? g16A[l] : -1, gA[l], pix(l), chan(l));
+    }
+    else if (base == "gB") { const int l = lvl(); either(g16_flow, g16_flow ? g16B[l] : -1, gB[l], pix(l), chan(l)); }
+    else if (base == "dpool") { const int l = lvl(); either(g16_flow, g16_flow ? g16pool[l] : -1, dpool[l], pix(l) / 4, chan(l)); }
+    else if (base == "gBottA") either(convt_planes, g16BottA, gBottA, Mb, Cb);
+    else if (base == "gBottB") either(g16_flow, g16BottB, gBottB, Mb, Cb);
+    else if (base == "dconcat") { const int l = lvl(); either(convt_planes, convt_planes ? g16cat[l] : -1, dconcat[l], pix(l), 2 * chan(l)); }
+    else if (base == "concat") { const int l = lvl(); f32(concat[l], pix(l), 2 * chan(l)); }      // (tensors of the float32 path, where prepared)
+    else if (base == "pool") { const int l = lvl(); f32(pool[l], pix(l) / 4, chan(l)); }
+    else if (base == "upf") { const int l = lvl(); f32(upf[l], pix(l), chan(l)); }      // the float32 up-conv output (where act_split converts it)
+    else throw Error("debug_tensor: unknown tensor " + name);
+}
+
 void UNetModel::backward_planes(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w) {
     (void)x_dev;
     const int D = depth, IB = i_bott;

@@ -366,7 +366,14 @@ class HipSegmenter:
         return m, v, step.value
 
     def debug_tensor(self, name) -> np.ndarray:
-        """Flat copy of an internal activation/gradient buffer (see rfi_model_debug_tensor)."""
+        """Flat float32 copy of an internal activation/gradient tensor of the last pass (see rfi_model_debug_tensor).
+
+        On a plane data flow ("bfloat16", "float32_planes") the plain U-Net returns a tensor it stores as bfloat16 as the
+        exact float32 values of its elements (dense NHWC), the plane tensors under "xin", "a1e.<l>", "skip.<l>",
+        "pooled.<l>", "up.<l>", "a1d.<l>", "a1b", "upin.<l>", "upf.<l>", "dYa.<l>", "dYb.<l>", "dYaE.<l>", "dYbE.<l>",
+        "dYbottA", "dYbottB", and under "<name>:pad" the padding lanes of such a tensor ([pixels, 16 * chunks - C]; empty
+        when C % 16 == 0).  "gA.<l>" / "gB.<l>" hold the encoder's gradients: the decoder phase's are overwritten within
+        the backward pass and cannot be read."""
         n = C.c_int64()
         check(lib.rfi_model_debug_tensor(self._h, name.encode(), None, 0, C.byref(n)))
         out = np.empty(n.value, dtype=np.float32)
