@@ -398,6 +398,10 @@ enum { RFI_COMBINE_MEAN = 0, RFI_COMBINE_MAX = 1 };
 enum { RFI_VALUES_LOGITS = 0, RFI_VALUES_PROBS = 1 };
 /* host only: the number of patches one C x T plane is cut into */
 int rfi_tiling_count(int c, int t, const rfi_tiling* tiling, int64_t* patches_per_plane);
+/* host only: the patches of n_units planes of C x T (an axis of length 0 has the one origin 0) as table entries, in the patch
+ * order above with `plane` counting the units; writes n_units x patches_per_plane entries (none for n_units == 0), an error
+ * when `capacity` entries do not hold them */
+int rfi_tiling_table(int c, int t, const rfi_tiling* tiling, int n_units, rfi_patch_src* table_host, int64_t capacity);
 /* values: n_planes x patches_per_plane patches of ps x ps float32 in the order above; flags: n_planes x C x T uint8;
  * prob (optional, NULL = none): n_planes x C x T float32 combined values.  Returns when the outputs are in place. */
 int rfi_stitch_patches(rfi_ctx* ctx, const float* values, int values_mem, int kind, int n_planes, int c, int t,

@@ -218,6 +218,7 @@ _PROTOS = {
     "rfi_threshold_logits": (_i, [_vp, _vp, _i64, _f, _vp]),
     "rfi_threshold_sweep": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i64, _i64, _vp, _i, _vp]),
     "rfi_tiling_count": (_i, [_i, _i, C.POINTER(Tiling), _pi64]),
+    "rfi_tiling_table": (_i, [_i, _i, C.POINTER(Tiling), _i, _vp, _i64]),
     "rfi_stitch_patches": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(Tiling), _i, _f, _vp, _i, _vp, _i]),
     "rfi_model_predict_flags": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(Tiling), _i, _i, _f, _vp, _i, _vp, _i]),
     "rfi_simulate_rfi": (_i, [_vp, C.c_uint64, C.c_uint64, _i, C.POINTER(SimParams), _vp, _i, _vp, _vp, _vp, _vp]),

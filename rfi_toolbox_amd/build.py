@@ -23,7 +23,7 @@ ARCH = "gfx950"
 
 SOURCES = ["api.cpp", "api_ops.cpp", "api_flaggers.cpp", "api_components.cpp", "api_match.cpp", "model.cpp", "model_cnn.cpp", "model_planes.cpp", "model_resnet.cpp", "model_mask.cpp", "model_backbone.cpp", "model_mlp.cpp", "model_params.cpp", "dispatch.cpp", "elem_kernels.hip", "conv_direct.hip", "conv_mfma.hip",
            "wgrad_mfma.hip", "preprocess.hip", "synth.hip", "order_stats.hip", "planes_elem.hip", "conv_planes.hip", "conv_ws.hip", "conv_stem.hip", "gemm_ws.hip", "wgrad_ws.hip", "wgrad_stem.hip", "wgrad_planes.hip", "wgrad_split.hip", "detect_kernels.hip", "detect_sample.hip", "detect_infer.hip", "rpn_kernels.hip", "resnet_kernels.hip", "flag_stats.hip", "rfi_sim.hip", "stitch.hip", "dataset_norm.hip", "augment.hip", "sumthreshold.hip", "casa_flaggers.hip", "threshold_sweep.hip", "components.hip", "instance_match.hip", "pol_gather.hip", "instance_stitch.hip"]
-HEADERS = ["common.hpp", "kernels.hpp", "model.hpp", "derived.hpp", "planes.hpp", "bf16_mma.hpp", "philox.hpp", "ws_common.hpp", "detect_sort.hpp", "select_common.hpp", "launch_common.hpp", "union_find.hpp", os.path.join(ROOT, "include", "rfi_hip.h")]
+HEADERS = ["common.hpp", "kernels.hpp", "model.hpp", "derived.hpp", "planes.hpp", "bf16_mma.hpp", "philox.hpp", "ws_common.hpp", "detect_sort.hpp", "select_common.hpp", "launch_common.hpp", "union_find.hpp", "tiling.hpp", os.path.join(ROOT, "include", "rfi_hip.h")]
 
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
           "-ffp-contract=off"]

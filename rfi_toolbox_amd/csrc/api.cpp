@@ -6,6 +6,7 @@
 
 #include "launch_common.hpp"
 #include "model.hpp"
+#include "tiling.hpp"
 
 using namespace rfi;
 
@@ -1374,6 +1375,20 @@ int rfi_tiling_count(int c, int t, const rfi_tiling* tiling, int64_t* patches_pe
     });
 }
 
+int rfi_tiling_table(int c, int t, const rfi_tiling* tiling, int n_units, rfi_patch_src* table_host, int64_t capacity) {
+    return guarded([&] {
+        RFI_REQUIRE(tiling && (table_host || capacity <= 0), "tiling_table: null argument");
+        RFI_REQUIRE(c >= 0 && t >= 0 && n_units >= 0, "tiling_table: negative shape or unit count");
+        check_tiling(*tiling);
+        const TileGrid g = make_tile_grid(c, t, *tiling);
+        RFI_REQUIRE(capacity >= (int64_t)n_units * g.ppp,
+                    "tiling_table: the table has " + std::to_string((int64_t)n_units * g.ppp) + " entries, capacity is " +
+                        std::to_string(capacity));
+        const std::vector<rfi_patch_src> table = tile_table(g, n_units);
+        std::copy(table.begin(), table.end(), table_host);
+    });
+}
+
 int rfi_stitch_patches(rfi_ctx* ctx, const float* values, int values_mem, int kind, int n_planes, int c, int t,
                        const rfi_tiling* tiling, int combine, float threshold, uint8_t* flags, int flags_mem,
                        float* prob, int prob_mem) {
@@ -1496,22 +1511,7 @@ void predict_flags_driver(rfi_model* m, PredictGather& g, const void* planes, in
     const int kind = m->head_sigmoid ? RFI_VALUES_PROBS : RFI_VALUES_LOGITS;
 
     // the chunk's patch table (plane indices local to the chunk; the same for every chunk, a prefix for the last)
-    std::vector<rfi_patch_src> table((size_t)chunk_patches);
-    {
-        const int nC = (int)(tiling_patches_per_plane(c, 1, rfi_tiling{ps, tiling->stride, tiling->edge, 1}));
-        const int nT = (int)(tiling_patches_per_plane(1, t, rfi_tiling{ps, tiling->stride, tiling->edge, 1}));
-        auto origin = [&](int i, int n, int L) {
-            return (tiling->edge == RFI_EDGE_SHIFT && i == n - 1 && L > ps) ? L - ps : i * tiling->stride;
-        };
-        size_t e = 0;
-        for (int p = 0; p < k; ++p)
-            for (int v = 0; v < tiling->views; ++v) {
-                const bool tr = v >= 2;
-                const int nr = tr ? nT : nC, nc = tr ? nC : nT, Hv = tr ? t : c, Wv = tr ? c : t;
-                for (int i = 0; i < nr; ++i)
-                    for (int j = 0; j < nc; ++j) table[e++] = rfi_patch_src{p, v, origin(i, nr, Hv), origin(j, nc, Wv)};
-            }
-    }
+    const std::vector<rfi_patch_src> table = tile_table(make_tile_grid(c, t, *tiling), k);
 
     // one grow-only scratch region: [table | the gather's own | images | patch outputs | 2 plane slots | 2 output slots]
     const size_t b_table = al(table.size() * sizeof(rfi_patch_src)), b_gws = al(g.ws_bytes(nb, n_planes));

@@ -13,6 +13,7 @@
 //   6 emit     rank of every root; boxes, scores, labels and counts of the first max_events
 //   7 paste    gather form as in stitch.hip: a thread owns one plane pixel, visits every covering tile and its member slots
 //              (bounding box first, then the mask byte), ORs into rfi_mask and sets the pixel in the event's mask plane
+// The grid, the tile order of the host table and the walk over covering tiles are those of tiling.hpp.
 // The mask bytes dominate: N D ps^2 in (read once by 1; 7 reads the bytes inside member boxes only), P E C T out.
 #include <algorithm>
 #include <map>
@@ -21,6 +22,7 @@
 
 #include "kernels.hpp"
 #include "launch_common.hpp"
+#include "tiling.hpp"
 #include "union_find.hpp"
 
 namespace rfi {
@@ -36,16 +38,9 @@ struct TileDesc {          // one tile of a plane: its view and origin, and its 
 struct TilePair {          // tiles a < b of a plane; kind 0: the rectangles intersect, 1: they are disjoint and abut
     int a, b, kind, pad_;
 };
-struct Geo {
-    int C, T, ps, D;
-    int s, shift, views, nC, nT;
-    int ppp;
+struct Geo : TileGrid {    // (ppp x D <= 65536 here: the kernels index a plane's tiles and slots with int)
+    int D;
 };
-
-__host__ __device__ inline int axis_tiles(int L, int ps, int s) { return L <= ps ? 1 : (L - ps + s - 1) / s + 1; }
-__host__ __device__ inline int origin(int i, int n, int L, int ps, int s, int shift) {
-    return (shift && i == n - 1 && L > ps) ? L - ps : i * s;
-}
 
 // order-preserving integer images of a float (finite or infinite): signed for atomicMin / atomicMax, unsigned for sort keys
 __device__ __forceinline__ int ord_i(float f) {
@@ -61,11 +56,8 @@ __device__ __forceinline__ float ord_u_inv(unsigned u) { return __int_as_float((
 
 // offset of plane pixel (c, t) inside a tile, -1 when the tile does not hold it
 __device__ __forceinline__ int tile_offset(const TileDesc& d, const Geo& g, int c, int t) {
-    const bool tr = d.view >= 2;
-    const int Hv = tr ? g.T : g.C;
-    const int yy = tr ? t : c, x = tr ? c : t;
-    const int y = (d.view & 1) ? Hv - 1 - yy : yy;
-    const int r = y - d.row0, cc = x - d.col0;
+    const ViewPixel p = view_pixel(g, d.view, c, t);
+    const int r = p.y - d.row0, cc = p.x - d.col0;
     if ((unsigned)r >= (unsigned)g.ps || (unsigned)cc >= (unsigned)g.ps) return -1;
     return r * g.ps + cc;
 }
@@ -89,7 +81,8 @@ __global__ void __launch_bounds__(kBlock) member_kernel(const float* __restrict_
         }
         return;
     }
-    const TileDesc d = tiles[tile % g.ppp];
+    const int in_plane = tile % (int)g.ppp;
+    const TileDesc d = tiles[in_plane];
     const bool tr = d.view >= 2;
     const int Hv = tr ? g.T : g.C, Wv = tr ? g.C : g.T;
     const int rows = min(g.ps, Hv - d.row0), cols = min(g.ps, Wv - d.col0);       // the tile's non-padding part
@@ -178,7 +171,7 @@ __global__ void __launch_bounds__(kBlock) member_kernel(const float* __restrict_
     by1 = fminf(fmaxf(by1, 0.0f), fC);
     by2 = fminf(fmaxf(by2, 0.0f), fC);
     acc_box[m] = make_int4(ord_i(bx1), ord_i(by1), ord_i(bx2), ord_i(by2));
-    const unsigned local = (unsigned)((tile % g.ppp) * g.D + slot);
+    const unsigned local = (unsigned)(in_plane * g.D + slot);
     acc_key[m] = ((unsigned long long)ord_u(scores[m]) << 32) | (0xffffffffu - local);       // max: best score, then smallest index
 }
 
@@ -188,7 +181,8 @@ __global__ void __launch_bounds__(kBlock) link_kernel(const int* __restrict__ la
                                                       const TilePair* __restrict__ pairs, Geo g, int class_aware, int conn8,
                                                       const int4* __restrict__ mbox, int* parent) {
     const TilePair pr = pairs[blockIdx.x];
-    const int ta = blockIdx.y * g.ppp + pr.a, tb = blockIdx.y * g.ppp + pr.b;
+    const int ppp = (int)g.ppp;
+    const int ta = blockIdx.y * ppp + pr.a, tb = blockIdx.y * ppp + pr.b;
     const int ca = cut_count(counts, ta, g.D), cb = cut_count(counts, tb, g.D);
     if (ca == 0 || cb == 0) return;
     const TileDesc da = tiles[pr.a], db = tiles[pr.b];
@@ -318,39 +312,20 @@ __global__ void __launch_bounds__(256) paste_kernel(const int* __restrict__ coun
     if (t >= g.T || c >= g.C) return;
     const int64_t ps2 = (int64_t)g.ps * g.ps, px = (int64_t)g.C * g.T;
     uint8_t any = 0;
-    for (int v = 0; v < g.views; ++v) {
-        const bool tr = v >= 2;
-        const int Hv = tr ? g.T : g.C, Wv = tr ? g.C : g.T;
-        const int nr = tr ? g.nT : g.nC, nc = tr ? g.nC : g.nT;
-        const int yy = tr ? t : c, x = tr ? c : t;
-        const int y = (v & 1) ? Hv - 1 - yy : yy;
-        const int vbase = v * nr * nc;                         // (every view holds nC nT tiles)
-        const int i0 = y >= g.ps ? (y - g.ps) / g.s + 1 : 0;
-        const int j0 = x >= g.ps ? (x - g.ps) / g.s + 1 : 0;
-        for (int i = i0; i < nr; ++i) {
-            const int r0 = origin(i, nr, Hv, g.ps, g.s, g.shift);
-            if (r0 > y) break;
-            if (y >= r0 + g.ps) continue;
-            for (int j = j0; j < nc; ++j) {
-                const int q0 = origin(j, nc, Wv, g.ps, g.s, g.shift);
-                if (q0 > x) break;
-                if (x >= q0 + g.ps) continue;
-                const int64_t tile = plane * g.ppp + vbase + i * nc + j;
-                const int cnt = cut_count(counts, tile, g.D);
-                const int off = (y - r0) * g.ps + (x - q0);
-                for (int k = 0; k < cnt; ++k) {
-                    const int64_t m = tile * g.D + k;
-                    const int4 b = mbox[m];
-                    if (c < b.x || c > b.y || t < b.z || t > b.w || !masks[m * ps2 + off]) continue;
-                    any = 1;
-                    if (out_masks) {
-                        const int rk = rank_of[root[m]];
-                        if (rk < E) out_masks[(plane * E + rk) * px + (int64_t)c * g.T + t] = 1;
-                    }
-                }
+    for_each_covering_tile<int>(g, c, t, [&](int tile_in_plane, int off) {          // (ppp x D <= 65536, ps <= 32768)
+        const int64_t tile = plane * g.ppp + tile_in_plane;
+        const int cnt = cut_count(counts, tile, g.D);
+        for (int k = 0; k < cnt; ++k) {
+            const int64_t m = tile * g.D + k;
+            const int4 b = mbox[m];
+            if (c < b.x || c > b.y || t < b.z || t > b.w || !masks[m * ps2 + off]) continue;
+            any = 1;
+            if (out_masks) {
+                const int rk = rank_of[root[m]];
+                if (rk < E) out_masks[(plane * E + rk) * px + (int64_t)c * g.T + t] = 1;
             }
         }
-    }
+    });
     rfi_mask[plane * px + (int64_t)c * g.T + t] = any;
 }
 
@@ -367,28 +342,24 @@ const Tables& tables_for(int C, int T, const rfi_tiling& tl) {
     auto& slot = cache[std::make_tuple(C, T, tl.ps, tl.stride, tl.edge, tl.views)];
     if (slot) return *slot;
     auto tb = std::make_unique<Tables>();
-    const int ps = tl.ps, s = tl.stride, shift = tl.edge == RFI_EDGE_SHIFT ? 1 : 0;
-    const int nC = axis_tiles(C, ps, s), nT = axis_tiles(T, ps, s);
-    for (int v = 0; v < tl.views; ++v) {
-        const bool tr = v >= 2;
-        const int Hv = tr ? T : C, Wv = tr ? C : T, nr = tr ? nT : nC, nc = tr ? nC : nT;
-        for (int i = 0; i < nr; ++i)
-            for (int j = 0; j < nc; ++j) {
-                TileDesc d{};
-                d.view = v;
-                d.row0 = origin(i, nr, Hv, ps, s, shift);
-                d.col0 = origin(j, nc, Wv, ps, s, shift);
-                int y0 = d.row0, y1 = std::min(d.row0 + ps, Hv);
-                const int x0 = d.col0, x1 = std::min(d.col0 + ps, Wv);
-                if (v & 1) {
-                    const int a = Hv - y1, b = Hv - y0;
-                    y0 = a;
-                    y1 = b;
-                }
-                if (tr) { d.c0 = x0; d.c1 = x1; d.t0 = y0; d.t1 = y1; }
-                else { d.c0 = y0; d.c1 = y1; d.t0 = x0; d.t1 = x1; }
-                tb->tiles.push_back(d);
-            }
+    const TileGrid g = make_tile_grid(C, T, tl);
+    for (const rfi_patch_src& e : tile_table(g, 1)) {
+        const int v = e.view;
+        const ViewPixel vw = view_pixel(g, v, 0, 0);
+        TileDesc d{};
+        d.view = v;
+        d.row0 = e.row0;
+        d.col0 = e.col0;
+        int y0 = d.row0, y1 = std::min(d.row0 + g.ps, vw.Hv);
+        const int x0 = d.col0, x1 = std::min(d.col0 + g.ps, vw.Wv);
+        if (v & 1) {
+            const int a = vw.Hv - y1, b = vw.Hv - y0;
+            y0 = a;
+            y1 = b;
+        }
+        if (v >= 2) { d.c0 = x0; d.c1 = x1; d.t0 = y0; d.t1 = y1; }
+        else { d.c0 = y0; d.c1 = y1; d.t0 = x0; d.t1 = x1; }
+        tb->tiles.push_back(d);
     }
     const int n = (int)tb->tiles.size();
     for (int a = 0; a < n; ++a)
@@ -429,8 +400,7 @@ void launch_stitch_instances(rfi_ctx* ctx, const float* boxes, const float* scor
     RFI_REQUIRE(cdiv(C, 4) <= 65535, "stitch_instances: at most 262140 channels");
     const Tables& tb = tables_for(C, T, tl);
     const int stride = sort_stride(per_plane), E = max_events;
-    Geo g{C, T, tl.ps, D, tl.stride, tl.edge == RFI_EDGE_SHIFT ? 1 : 0, tl.views, axis_tiles(C, tl.ps, tl.stride),
-          axis_tiles(T, tl.ps, tl.stride), (int)ppp};
+    Geo g{make_tile_grid(C, T, tl), D};
 
     const size_t n_pairs = tb.pairs.size();
     const size_t bytes = al(tb.tiles.size() * sizeof(TileDesc)) + al(n_pairs * sizeof(TilePair)) + 2 * al(nd * sizeof(int4)) +

@@ -1,34 +1,21 @@
 // Inverse of the tiling of Preprocessor.create_dataset(inference_mode=True): per-patch model outputs -> one flag (and
-// optionally one combined probability) per waterfall pixel.  Gather form: a thread owns one output pixel, derives the
-// (view, tile row, tile column) triples that cover it from the grid arithmetic of rfi_tiling (include/rfi_hip.h) and
-// reads those patch pixels in a fixed order -- views ascending, then tile rows, then tile columns.  No atomics, no
+// optionally one combined probability) per waterfall pixel.  Gather form: a thread owns one output pixel and reads the
+// patch pixels of the tiles that cover it in the order of for_each_covering_tile (tiling.hpp, which holds the grid
+// arithmetic of rfi_tiling) -- views ascending, then tile rows, then tile columns.  No atomics, no
 // scatter: the result is bitwise reproducible.  Memory bound: 4 B read per covering tile, 1 (+4) B written per pixel.
 // Views 0/1 read along patch rows (coalesced); views 2/3 walk a patch column across a wavefront, so a block spans
 // 4 waterfall rows whose reads share those cache lines.
 #include <algorithm>
 
 #include "kernels.hpp"
+#include "tiling.hpp"
 
 namespace rfi {
 namespace {
 
-// tile origins along an axis of length L: n = 1 when L <= ps, else k + 1 with k = ceil((L - ps) / s); origin i = i * s,
-// except the last one under edge = shift, which is L - ps (no padded tile)
-__host__ __device__ inline int axis_tiles(int L, int ps, int s) { return L <= ps ? 1 : (L - ps + s - 1) / s + 1; }
-
-struct StitchGrid {
-    int C, T, ps, s, shift, views;
-    int nC, nT;                    // tiles along C and along T
-    int64_t ppp;                   // patches per plane
-};
-
-__device__ __forceinline__ int origin(int i, int n, int L, const StitchGrid& g) {
-    return (g.shift && i == n - 1 && L > g.ps) ? L - g.ps : i * g.s;
-}
-
 // kind 0: values are logits (sigmoid as threshold_kernel computes it), 1: probabilities as they are
 template <int KIND, int COMBINE>
-__global__ void __launch_bounds__(256) stitch_kernel(const float* __restrict__ vals, StitchGrid g, float thr,
+__global__ void __launch_bounds__(256) stitch_kernel(const float* __restrict__ vals, TileGrid g, float thr,
                                                      uint8_t* __restrict__ flags, float* __restrict__ prob) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int c = blockIdx.y * blockDim.y + threadIdx.y;
@@ -38,32 +25,13 @@ __global__ void __launch_bounds__(256) stitch_kernel(const float* __restrict__ v
     const float* pv = vals + (int64_t)plane * g.ppp * ps2;
     float acc = 0.0f;
     int cnt = 0;
-    for (int v = 0; v < g.views; ++v) {
-        const bool tr = v >= 2;
-        const int Hv = tr ? g.T : g.C, Wv = tr ? g.C : g.T;
-        const int nr = tr ? g.nT : g.nC, nc = tr ? g.nC : g.nT;
-        // waterfall pixel (c, t) in view coordinates (y, x); views: 0 plane, 1 plane[::-1,:], 2 plane.T, 3 plane.T[::-1,:]
-        const int yy = tr ? t : c, x = tr ? c : t;
-        const int y = (v & 1) ? Hv - 1 - yy : yy;
-        const int64_t vbase = (int64_t)v * nr * nc;
-        const int i0 = y >= g.ps ? (y - g.ps) / g.s + 1 : 0;
-        const int j0 = x >= g.ps ? (x - g.ps) / g.s + 1 : 0;
-        for (int i = i0; i < nr; ++i) {
-            const int r0 = origin(i, nr, Hv, g);
-            if (r0 > y) break;
-            if (y >= r0 + g.ps) continue;
-            for (int j = j0; j < nc; ++j) {
-                const int c0 = origin(j, nc, Wv, g);
-                if (c0 > x) break;
-                if (x >= c0 + g.ps) continue;
-                const float raw = pv[(vbase + (int64_t)i * nc + j) * ps2 + (int64_t)(y - r0) * g.ps + (x - c0)];
-                const float p = KIND == 0 ? 1.0f / (1.0f + expf(-raw)) : raw;
-                if (COMBINE == 0) acc += p;
-                else acc = (cnt == 0 || p > acc) ? p : acc;
-                ++cnt;
-            }
-        }
-    }
+    for_each_covering_tile<int64_t>(g, c, t, [&](int64_t tile, int64_t off) {
+        const float raw = pv[tile * ps2 + off];
+        const float p = KIND == 0 ? 1.0f / (1.0f + expf(-raw)) : raw;
+        if (COMBINE == 0) acc += p;
+        else acc = (cnt == 0 || p > acc) ? p : acc;
+        ++cnt;
+    });
     const float r = COMBINE == 0 ? acc / (float)cnt : acc;
     const int64_t o = ((int64_t)plane * g.C + c) * g.T + t;
     flags[o] = r > thr ? 1 : 0;
@@ -73,7 +41,7 @@ __global__ void __launch_bounds__(256) stitch_kernel(const float* __restrict__ v
 }  // namespace
 
 int64_t tiling_patches_per_plane(int C, int T, const rfi_tiling& tl) {
-    return (int64_t)tl.views * axis_tiles(C, tl.ps, tl.stride) * axis_tiles(T, tl.ps, tl.stride);
+    return make_tile_grid(C, T, tl).ppp;
 }
 
 void check_tiling(const rfi_tiling& tl) {
@@ -88,9 +56,7 @@ void launch_stitch(rfi_ctx* ctx, const float* values, int kind, int n_planes, in
     RFI_REQUIRE(kind == RFI_VALUES_LOGITS || kind == RFI_VALUES_PROBS, "stitch: kind must be logits (0) or probabilities (1)");
     RFI_REQUIRE(combine == RFI_COMBINE_MEAN || combine == RFI_COMBINE_MAX, "stitch: combine must be mean (0) or max (1)");
     if (n_planes == 0) return;
-    StitchGrid g{C, T, tl.ps, tl.stride, tl.edge == RFI_EDGE_SHIFT ? 1 : 0, tl.views, axis_tiles(C, tl.ps, tl.stride),
-                 axis_tiles(T, tl.ps, tl.stride), 0};
-    g.ppp = (int64_t)g.views * g.nC * g.nT;
+    const TileGrid g = make_tile_grid(C, T, tl);
     const double px = (double)n_planes * C * T;
     // bytes: every covering tile read once (about views x (ps / stride)^2 per pixel), flags and probabilities written
     const double cover = (double)g.views * ((double)tl.ps / tl.stride) * ((double)tl.ps / tl.stride);

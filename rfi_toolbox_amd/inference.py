@@ -31,8 +31,8 @@ from ._lib import (COMBINE_MAX, COMBINE_MEAN, COMPLEX_CODES, DEVICE, EDGE_PAD, E
                    VALUES_PROBS, Tiling, check, lib)
 from .runtime import DeviceArray, check_out, context_for, describe, is_torch, operand, result_buffer, torch
 
-__all__ = ["predict_flags", "tile_observation", "stitch_patches", "tiling_count", "check_tiling_args", "stitch_instances",
-           "detect_observation"]
+__all__ = ["predict_flags", "tile_observation", "stitch_patches", "tiling_count", "tiling_table", "check_tiling_args",
+           "stitch_instances", "detect_observation"]
 
 _COMBINE = {"mean": COMBINE_MEAN, "max": COMBINE_MAX}
 _EDGE = {"pad": EDGE_PAD, "shift": EDGE_SHIFT}
@@ -69,6 +69,18 @@ def tiling_count(channels, times, patch_size=128, stride=None, views=1, edge="pa
     n = C.c_int64()
     check(lib.rfi_tiling_count(int(channels), int(times), C.byref(Tiling(ps, s, _EDGE[edge], views)), C.byref(n)))
     return n.value
+
+
+def tiling_table(n_units, channels, times, patch_size, stride=None, views=1, edge="pad") -> np.ndarray:
+    """The (N, 4) int32 table (unit, view, row0, col0) of ``rfi_tiling``'s patch order for ``n_units`` planes of
+    channels x times (``rfi_tiling_table``; host only)."""
+    ps, s = check_tiling_args(patch_size, stride, views, "mean", edge)
+    tiling = Tiling(ps, s, _EDGE[edge], views)
+    Cn, Tn = int(channels), int(times)
+    ppp = tiling_count(max(Cn, 1), max(Tn, 1), ps, s, views, edge)       # (an empty axis has one origin, like an axis of 1)
+    table = np.empty((int(n_units) * ppp, 4), dtype=np.int32)
+    check(lib.rfi_tiling_table(Cn, Tn, C.byref(tiling), int(n_units), table.ctypes.data_as(C.c_void_p), len(table)))
+    return table
 
 
 def _complex_input(data, what):
@@ -243,23 +255,6 @@ def predict_flags(model, data, patch_size=128, stride=None, views=1, combine="me
     return (flags, prob) if return_probabilities else flags
 
 
-def _patch_table(n, Cn, Tn, ps, s, views, edge):
-    """The (N, 4) int32 table (unit, view, row0, col0) of rfi_tiling's patch order for n units of Cn x Tn."""
-    def origins(L):
-        if L <= ps:
-            return [0]
-        o = [i * s for i in range(-(-(L - ps) // s) + 1)]
-        if edge == "shift":
-            o[-1] = L - ps
-        return o
-    oc, ot = origins(Cn), origins(Tn)
-    per = [(v, r0, c0) for v in range(views) for r0 in (ot if v >= 2 else oc) for c0 in (oc if v >= 2 else ot)]
-    table = np.empty((n, len(per), 4), dtype=np.int32)
-    table[:, :, 0] = np.arange(n, dtype=np.int32)[:, None]
-    table[:, :, 1:] = np.asarray(per, dtype=np.int32).reshape(-1, 3)
-    return table.reshape(-1, 4)
-
-
 def tile_observation(data, patch_size, stride=None, views=1, edge="pad", normalizer=None, device=None):
     """The network input of every tile of an observation for an 8-channel model, for users who run their own model.
 
@@ -272,7 +267,7 @@ def tile_observation(data, patch_size, stride=None, views=1, edge="pad", normali
     n, Cn, Tn = _pol_shape(shape)
     form = _normalizer_form(normalizer)
     ctx = context_for(device, data)
-    table = _patch_table(n, Cn, Tn, ps, s, views, edge)
+    table = tiling_table(n, Cn, Tn, ps, s, views, edge)
     res = ctx.empty((len(table), ps, ps, 8), np.float32)
     if not len(table) or not Cn * Tn:
         return res
@@ -495,7 +490,7 @@ def detect_observation(detector, data, patch_size=128, stride=None, views=1, edg
             pairs = np.concatenate([_sample_pairs(normalizer, _group_on_device(go, ctx, g0, g1, (4, Cn, Tn)))
                                     for g0, g1 in _sample_groups(b1 - b0, 4 * px * dt.itemsize)])
         centre, scale = (form[1], form[2]) if form[0] == "pair" else (0.0, 1.0)
-        table = _patch_table(b1 - b0, Cn, Tn, ps, s, views, edge)
+        table = tiling_table(b1 - b0, Cn, Tn, ps, s, views, edge)
         for i0 in range(0, len(table), bs):
             k = min(bs, len(table) - i0)
             if k < bs:

@@ -26,6 +26,7 @@ import torch
 
 from .._lib import C128, DEVICE, F32, F64, HOST, VALUE_CODES, check, lib
 from ..datasets.batched_dataset import TorchDataset
+from ..inference import tiling_table
 from ..runtime import Context, ptr_mem
 
 
@@ -72,24 +73,9 @@ def _to_patches(wfs, ps):
 
 def _patch_table(n_planes, C, T, rot, ps):
     """One (plane, view, row0, col0) entry per patch, in the reference's order: plane-major, then
-    view (:413-446), then row-major tiles of the zero-padded view (:478-560)."""
-    views = (0,) if rot < 2 else ((0, 1) if rot < 4 else (0, 1, 2, 3))
-    whole = C <= ps and T <= ps          # small waterfalls are used whole, unpadded (:340-347)
-    rows = []
-    for plane in range(n_planes):
-        for v in views:
-            hv, wv = (T, C) if v >= 2 else (C, T)
-            if whole:
-                rows.append((plane, v, 0, 0))
-                continue
-            for r0 in range(0, max(hv, ps), ps):
-                if r0 >= hv and r0 > 0:
-                    break
-                for c0 in range(0, max(wv, ps), ps):
-                    if c0 >= wv and c0 > 0:
-                        break
-                    rows.append((plane, v, r0, c0))
-    return np.asarray(rows, dtype=np.int32).reshape(-1, 4)
+    view (:413-446), then row-major tiles of the zero-padded view (:478-560), a small waterfall whole (:340-347).
+    That is ``rfi_tiling``'s order at stride = patch size with a padded edge, so the library states it."""
+    return tiling_table(n_planes, C, T, ps, ps, 1 if rot < 2 else 2 if rot < 4 else 4, "pad")
 
 
 def select_patches(ctx, d_flags, n_planes, Cn, Tn, rot, ps, num_patches=None, inference_mode=False):

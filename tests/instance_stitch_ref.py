@@ -2,23 +2,12 @@
 pairs of members on whole-plane masks, float32 where the header says float32.  Shares no code with the kernels."""
 import numpy as np
 
-
-def origins(L, ps, s, edge):
-    if L <= ps:
-        return [0]
-    o = [i * s for i in range(-(-(L - ps) // s) + 1)]
-    if edge == "shift":
-        o[-1] = L - ps
-    return o
+import stitch_ref
 
 
 def tile_table(C, T, ps, s, views, edge):
-    """(view, row0, col0) of the tiles of one plane in rfi_tiling order."""
-    out = []
-    for v in range(views):
-        Hv, Wv = (T, C) if v >= 2 else (C, T)
-        out += [(v, r0, c0) for r0 in origins(Hv, ps, s, edge) for c0 in origins(Wv, ps, s, edge)]
-    return out
+    """(view, row0, col0) of the tiles of one plane in rfi_tiling order (stitch_ref holds the restatement)."""
+    return [(int(v), int(r0), int(c0)) for _, v, r0, c0 in stitch_ref.patch_table(1, C, T, ps, s, views, edge)]
 
 
 def view_of(plane, v):

@@ -46,6 +46,29 @@ def patch_table(n_planes, C, T, ps, stride=None, views=1, edge="pad"):
     return np.asarray(rows, dtype=np.int32).reshape(-1, 4)
 
 
+def reference_patch_table(n_planes, C, T, rot, ps):
+    """One (plane, view, row0, col0) entry per patch, in the reference's order: plane-major, then
+    view (:413-446), then row-major tiles of the zero-padded view (:478-560).  Written from the reference's
+    Preprocessor, not from the rules above: patch_table at stride == ps, edge "pad" must equal it."""
+    views = (0,) if rot < 2 else ((0, 1) if rot < 4 else (0, 1, 2, 3))
+    whole = C <= ps and T <= ps          # small waterfalls are used whole, unpadded (:340-347)
+    rows = []
+    for plane in range(n_planes):
+        for v in views:
+            hv, wv = (T, C) if v >= 2 else (C, T)
+            if whole:
+                rows.append((plane, v, 0, 0))
+                continue
+            for r0 in range(0, max(hv, ps), ps):
+                if r0 >= hv and r0 > 0:
+                    break
+                for c0 in range(0, max(wv, ps), ps):
+                    if c0 >= wv and c0 > 0:
+                        break
+                    rows.append((plane, v, r0, c0))
+    return np.asarray(rows, dtype=np.int32).reshape(-1, 4)
+
+
 def patches_per_plane(C, T, ps, stride=None, views=1, edge="pad"):
     stride = ps if stride is None else stride
     return len(VIEW_SETS[views]) * len(origins(C, ps, stride, edge)) * len(origins(T, ps, stride, edge))

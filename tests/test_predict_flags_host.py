@@ -1,5 +1,6 @@
 """CPU-only: the tiling rules of whole-observation prediction (tests/stitch_ref.py) against the reference's own
-tiling (Preprocessor's _patch_table), rfi_tiling_count, and the argument checks that need no model."""
+tiling (stitch_ref.reference_patch_table), rfi_tiling_count and rfi_tiling_table, and the argument checks that need no
+model."""
 import numpy as np
 import pytest
 
@@ -7,18 +8,54 @@ import stitch_ref as ref
 
 SHAPES = [(40, 40), (64, 64), (128, 64), (64, 128), (65, 64), (129, 257), (200, 333), (333, 200), (30, 100),
           (100, 30), (192, 128), (1, 64)]
-TILED = [s for s in SHAPES if max(s) > 64]          # (C, T <= ps: whole, unpadded waterfalls, not a tiling)
+BAD_TILINGS = [(64, 0, 0, 1), (64, 65, 0, 1), (64, 64, 2, 1), (64, 64, 0, 3), (0, 1, 0, 1)]
 
 
 @pytest.mark.parametrize("views", [1, 2, 4])
-@pytest.mark.parametrize("shape", TILED)
+@pytest.mark.parametrize("shape", SHAPES)          # (C, T <= ps: whole, unpadded waterfalls, one entry per view)
 def test_stride_ps_pad_equals_reference_patch_table(shape, views):
+    from rfi_toolbox_amd.inference import tiling_table
     from rfi_toolbox_amd.preprocessing.preprocessor import _patch_table
     C, T = shape
     ps = 64
     got = ref.patch_table(3, C, T, ps, ps, views, "pad")
-    want = _patch_table(3, C, T, views, ps)
+    want = ref.reference_patch_table(3, C, T, views, ps)
     assert np.array_equal(got, want)
+    assert np.array_equal(_patch_table(3, C, T, views, ps), want)          # the Preprocessor's table
+    lib = tiling_table(3, C, T, ps, ps, views, "pad")
+    assert lib.dtype == np.int32 and lib.flags.c_contiguous and np.array_equal(lib, want)
+
+
+@pytest.mark.parametrize("edge", ["pad", "shift"])
+@pytest.mark.parametrize("stride", [64, 48, 32, 1])
+@pytest.mark.parametrize("views", [1, 2, 4])
+@pytest.mark.parametrize("shape", SHAPES)
+def test_tiling_table_is_the_restatement(shape, views, stride, edge):
+    from rfi_toolbox_amd.inference import tiling_table
+    C, T = shape
+    for n_units in (1, 3):
+        got = tiling_table(n_units, C, T, 64, stride, views, edge)
+        assert got.dtype == np.int32 and got.flags.c_contiguous
+        assert np.array_equal(got, ref.patch_table(n_units, C, T, 64, stride, views, edge))
+    assert tiling_table(0, C, T, 64, stride, views, edge).shape == (0, 4)
+
+
+def test_tiling_table_rejects_small_capacity_and_bad_tilings():
+    from rfi_toolbox_amd import _lib
+    import ctypes as C
+    good = _lib.Tiling(64, 32, 0, 2)
+    n = C.c_int64()
+    assert _lib.lib.rfi_tiling_count(100, 130, C.byref(good), C.byref(n)) == 0
+    buf = np.full((3 * n.value + 1, 4), -7, dtype=np.int32)
+    ptr = buf.ctypes.data_as(C.c_void_p)
+    assert _lib.lib.rfi_tiling_table(100, 130, C.byref(good), 3, ptr, 3 * n.value - 1) != 0
+    assert _lib.lib.rfi_last_error() and np.all(buf == -7)                  # too small: an error, nothing written
+    assert _lib.lib.rfi_tiling_table(100, 130, C.byref(good), 3, ptr, 3 * n.value) == 0
+    assert np.array_equal(buf[:-1], ref.patch_table(3, 100, 130, 64, 32, 2, "pad")) and np.all(buf[-1] == -7)
+    assert _lib.lib.rfi_tiling_table(100, 130, C.byref(good), 0, None, 0) == 0
+    for t in BAD_TILINGS:
+        assert _lib.lib.rfi_tiling_table(100, 100, C.byref(_lib.Tiling(*t)), 1, ptr, len(buf)) != 0
+        assert _lib.lib.rfi_last_error()
 
 
 @pytest.mark.parametrize("edge", ["pad", "shift"])
@@ -67,9 +104,8 @@ def test_tiling_count_rejects_bad_tilings():
     from rfi_toolbox_amd import _lib
     import ctypes as C
     n = C.c_int64()
-    for t in (_lib.Tiling(64, 0, 0, 1), _lib.Tiling(64, 65, 0, 1), _lib.Tiling(64, 64, 2, 1), _lib.Tiling(64, 64, 0, 3),
-              _lib.Tiling(0, 1, 0, 1)):
-        assert _lib.lib.rfi_tiling_count(100, 100, C.byref(t), C.byref(n)) != 0
+    for t in BAD_TILINGS:
+        assert _lib.lib.rfi_tiling_count(100, 100, C.byref(_lib.Tiling(*t)), C.byref(n)) != 0
         assert _lib.lib.rfi_last_error()
 
 

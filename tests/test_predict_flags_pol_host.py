@@ -73,12 +73,12 @@ def test_tile_and_stitch_argument_errors_touch_no_device():
 
 
 def test_python_patch_table_is_the_restatement():
-    from rfi_toolbox_amd.inference import _patch_table
+    from rfi_toolbox_amd.inference import tiling_table
     for C, T in ((50, 77), (77, 50), (20, 70), (64, 64), (65, 63), (20, 20)):
         for stride in (32, 24, 16):
             for views in (1, 2, 4):
                 for edge in ("pad", "shift"):
-                    assert np.array_equal(_patch_table(3, C, T, 32, stride, views, edge),
+                    assert np.array_equal(tiling_table(3, C, T, 32, stride, views, edge),
                                           sref.patch_table(3, C, T, 32, stride, views, edge)), (C, T, stride, views, edge)
 
 

@@ -38,14 +38,11 @@ CASES = {"8x1024_s128_d20": (8, 1024, 128, 20), "8x1024_s96_d20": (8, 1024, 96, 
          "1x512_s128_d20": (1, 512, 128, 20)}
 
 
-def origins(L, s):
-    return [0] if L <= PS else [i * s for i in range(-(-(L - PS) // s) + 1)]
-
-
 def make(n, size, s, D, seed=0):
     """-> the tile detections of n planes of size x size (views 1, edge pad) and the (row0, col0) of a plane's tiles."""
+    from rfi_toolbox_amd.inference import tiling_table
     rng = np.random.default_rng(seed)
-    tiles = [(r0, c0) for r0 in origins(size, s) for c0 in origins(size, s)]
+    tiles = [(int(r0), int(c0)) for _, _, r0, c0 in tiling_table(1, size, size, PS, s)]
     N = n * len(tiles)
     det = {"boxes": np.zeros((N, D, 4), np.float32), "scores": np.zeros((N, D), np.float32), "labels": np.zeros((N, D), np.int32),
            "counts": np.zeros((N,), np.int32), "masks": np.zeros((N, D, PS, PS), np.uint8)}
