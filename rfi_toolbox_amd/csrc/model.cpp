@@ -153,9 +153,10 @@ void UNetModel::prepare_shape(int n, int h, int w) {
     const int D = depth;
     if (bufs.empty()) {
         auto mk = [&](std::vector<int>& v) { v.assign(D + 1, -1); for (int l = 1; l <= D; ++l) v[l] = new_buf(); };
-        mk(encY1); mk(encY2); mk(concat); mk(pool); mk(decY1); mk(decY2);
-        mk(gA); mk(gB); mk(dconcat); mk(dpool); mk(gAe); mk(gBe);
-        bottY1 = new_buf(); bottY2 = new_buf(); gBottA = new_buf(); gBottB = new_buf();
+        auto mkf = [&](std::vector<FlowTensor>& v) { v.assign(D + 1, FlowTensor()); for (int l = 1; l <= D; ++l) v[l].f32 = new_buf(); };
+        mkf(encY1); mkf(encY2); mk(concat); mk(pool); mkf(decY1); mkf(decY2);
+        mkf(gA); mkf(gB); mkf(dconcat); mkf(dpool); mk(gAe); mk(gBe);
+        for (FlowTensor* t : {&bottY1, &bottY2, &gBottA, &gBottB}) t->f32 = new_buf();
         logits = new_buf(); dlogits = new_buf(); probs = new_buf();
         x_stage = new_buf(); x_stage2 = new_buf(); x_pad = new_buf(); out_stage = new_buf();
         ws_red = new_buf(); ws_slab = new_buf(); lab_stage = new_buf();
@@ -165,20 +166,20 @@ void UNetModel::prepare_shape(int n, int h, int w) {
     for (int l = 1; l <= D; ++l) {
         const size_t M = (size_t)n * (h >> (l - 1)) * (w >> (l - 1));
         const size_t C = (size_t)feat << (l - 1);
-        for (int i : {decY1[l], decY2[l], gA[l], gB[l]}) bufs[i].ensure(ctx, M * C);
+        for (int i : {decY1[l].f32, decY2[l].f32, gA[l].f32, gB[l].f32}) bufs[i].ensure(ctx, M * C);
         if (!planesP && !resnet_encoder) for (int i : {gAe[l], gBe[l]}) bufs[i].ensure(ctx, M * C);   // (the encoder phase's own gradient tensors)
-        if (!resnet_encoder) for (int i : {encY1[l], encY2[l]}) bufs[i].ensure(ctx, M * C);     // (ResNet encoder: its own tensors, prepare_resnet)
+        if (!resnet_encoder) for (int i : {encY1[l].f32, encY2[l].f32}) bufs[i].ensure(ctx, M * C);     // (ResNet encoder: its own tensors, prepare_resnet)
         bufs[concat[l]].ensure(ctx, M * 2 * C);
-        bufs[dconcat[l]].ensure(ctx, M * 2 * C);
+        bufs[dconcat[l].f32].ensure(ctx, M * 2 * C);
         if (!resnet_encoder || l == D) {
             bufs[pool[l]].ensure(ctx, M / 4 * C);
-            bufs[dpool[l]].ensure(ctx, M / 4 * C);
+            bufs[dpool[l].f32].ensure(ctx, M / 4 * C);
         }
     }
     {
         const size_t M = (size_t)n * (h >> D) * (w >> D);
         const size_t C = (size_t)feat << D;
-        for (int i : {bottY1, bottY2, gBottA, gBottB}) bufs[i].ensure(ctx, M * C);
+        for (int i : {bottY1.f32, bottY2.f32, gBottA.f32, gBottB.f32}) bufs[i].ensure(ctx, M * C);
     }
     const size_t M1 = (size_t)n * h * w;
     bufs[logits].ensure(ctx, M1 * out_ch);
@@ -509,11 +510,15 @@ void rfi_model::conv_bn(ConvBN& c, View in, InXform xf, Shape s, const float* w,
         a.stats_max_records = (int)(bn_stats_ws_floats(c.cout) / ((size_t)c.cout * 4));
     }
     launch_conv(ctx, a);
-    const int64_t M = (int64_t)s.N * s.H * s.W;
+    bn_tail(c, Y, (int64_t)s.N * s.H * s.W, train, a.stats_records);
+}
+
+void rfi_model::bn_tail(ConvBN& c, const float* Y, int64_t M, bool train, int records) {
+    float* ws = buf(ws_red);
     if (train) {
-        if (a.stats_records == 0) launch_bn_stats(ctx, Y, M, c.cout, ws);   // direct-kernel fallback
+        if (records == 0) launch_bn_stats(ctx, Y, M, c.cout, ws);   // (a kernel without the statistics epilogue)
         launch_bn_finalize(ctx, ws, M, c.cout, params + c.g_off, params + c.be_off, c.running_mean(), c.running_var(),
-                           c.ema_repeats, c.mean(), c.invstd(), c.scale(), c.shift(), nullptr, a.stats_records);
+                           c.ema_repeats, c.mean(), c.invstd(), c.scale(), c.shift(), nullptr, records);
         c.nbt += c.ema_repeats;
     } else {
         launch_bn_eval_coeffs(ctx, c.cout, params + c.g_off, params + c.be_off, c.running_mean(), c.running_var(),
@@ -961,43 +966,45 @@ void UNetModel::debug_tensor(const std::string& name, const std::string& base, i
     RFI_REQUIRE(name.find(':') == std::string::npos, "debug_tensor: only the plain U-Net on a plane data flow has plane tensors");
     if (resnet_encoder && (base == "encY1" || base == "encY2" || base == "pool" || base == "dpool"))
         return rfi_model::debug_tensor(name, base, idx, to_host, sc, src, n);
-    RFI_REQUIRE(!(y16_flow && planesP == 1 && (base == "encY1" || base == "encY2" || base == "decY1" || base == "bottY1" ||
-                                               (base == "decY2" && idx == 1))),
-                "debug_tensor: this conv output is stored as bfloat16 in the bfloat16 compute mode");
-    RFI_REQUIRE(!(g16_flow && planesP == 1 && (base == "gB" || base == "dpool" || base == "gBottB" || base == "gA")),
-                "debug_tensor: this gradient tensor is stored as bfloat16 in the bfloat16 compute mode");
-    RFI_REQUIRE(!(convt_planes && planesP == 1 && (base == "decY2" || base == "bottY2" || base == "gBottA")),
-                "debug_tensor: with the transposed convs on the plane kernels this tensor is stored as bfloat16");
-    const int D = depth;
-    auto level = [&](const std::vector<int>& v, size_t chmul) {
-        RFI_REQUIRE(idx >= 1 && idx <= D, "debug_tensor: level out of range");
-        const size_t M = (size_t)pN * (pH >> (idx - 1)) * (pW >> (idx - 1));
-        src = buf(v[idx]);
-        n = M * ((size_t)feat << (idx - 1)) * chmul;
-    };
-    const size_t Mb = (size_t)pN * (pH >> D) * (pW >> D), Cb = (size_t)feat << D;
-    if (base == "encY1") level(encY1, 1);
-    else if (base == "encY2") level(encY2, 1);
-    else if (base == "decY1") level(decY1, 1);
-    else if (base == "decY2") level(decY2, 1);
-    else if (base == "gA") level(!planesP && !resnet_encoder ? gAe : gA, 1);     // (as left by the encoder phase)
-    else if (base == "gB") level(!planesP && !resnet_encoder ? gBe : gB, 1);
-    else if (base == "concat") level(concat, 2);
-    else if (base == "dconcat") {
-        level(dconcat, 2);
-        if (convt_planes && planesP == 1 && to_host) {      // stored as bfloat16: its values as float32 (tools/race_probe.py watches it)
-            const PlaneBuf& g = pl[g16cat[idx]];
-            launch_planes_to_f32(ctx, g.p, g.pstride, (int64_t)(n / ((size_t)2 * (feat << (idx - 1)))), 2 * (feat << (idx - 1)), 1,
-                                 buf(dconcat[idx]), 2 * (feat << (idx - 1)));
+    size_t M = 0;
+    int C = 0;
+    if (const FlowTensor* t = flow_named(base, idx, M, C)) {
+        // (`half` is prepare_planes's: it says nothing once the model has left the bfloat16 flow)
+        const bool b16 = planesP == 1 && t->half;
+        if (b16 && base == "dconcat") {           // its values as float32 (tools/race_probe.py watches it)
+            if (to_host) launch_planes_to_f32(ctx, pl[t->b16].p, pl[t->b16].pstride, (int64_t)M, C, 1, buf(*t), C);
+        } else {
+            RFI_REQUIRE(!b16, "debug_tensor: this tensor is stored as bfloat16 in the bfloat16 compute mode");
         }
+        // (the float32 path's encoder phase has gradient tensors of its own)
+        const bool enc_own = !planesP && !resnet_encoder && (base == "gA" || base == "gB");
+        src = enc_own ? buf((base == "gA" ? gAe : gBe)[idx]) : buf(*t);
+        n = M * C;
+        return;
     }
-    else if (base == "pool") { level(pool, 1); n /= 4; }
-    else if (base == "dpool") { level(dpool, 1); n /= 4; }
-    else if (base == "bottY1") { src = buf(bottY1); n = Mb * Cb; }
-    else if (base == "bottY2") { src = buf(bottY2); n = Mb * Cb; }
-    else if (base == "gBottA") { src = buf(gBottA); n = Mb * Cb; }
-    else if (base == "gBottB") { src = buf(gBottB); n = Mb * Cb; }
-    else throw Error("debug_tensor: unknown tensor " + name);
+    RFI_REQUIRE(base == "concat" || base == "pool", "debug_tensor: unknown tensor " + name);
+    RFI_REQUIRE(idx >= 1 && idx <= depth, "debug_tensor: level out of range");
+    const size_t Ml = (size_t)pN * (pH >> (idx - 1)) * (pW >> (idx - 1)), Cl = (size_t)feat << (idx - 1);
+    src = buf(base == "concat" ? concat[idx] : pool[idx]);
+    n = base == "concat" ? Ml * 2 * Cl : Ml / 4 * Cl;
+}
+
+const FlowTensor* UNetModel::flow_named(const std::string& base, int idx, size_t& M, int& C) const {
+    struct Row { const char* name; const std::vector<FlowTensor>* levels; const FlowTensor* bott; int pixdiv, chmul; };
+    const Row rows[] = {{"encY1", &encY1, nullptr, 1, 1}, {"encY2", &encY2, nullptr, 1, 1}, {"decY1", &decY1, nullptr, 1, 1},
+                        {"decY2", &decY2, nullptr, 1, 1}, {"gA", &gA, nullptr, 1, 1}, {"gB", &gB, nullptr, 1, 1},
+                        {"dpool", &dpool, nullptr, 4, 1}, {"dconcat", &dconcat, nullptr, 1, 2},
+                        {"bottY1", nullptr, &bottY1, 1, 1}, {"bottY2", nullptr, &bottY2, 1, 1},
+                        {"gBottA", nullptr, &gBottA, 1, 1}, {"gBottB", nullptr, &gBottB, 1, 1}};
+    for (const Row& r : rows) {
+        if (base != r.name) continue;
+        RFI_REQUIRE(!r.levels || (idx >= 1 && idx <= depth), "debug_tensor: level out of range");
+        const int l = r.levels ? idx : depth + 1;           // (the bottleneck: one level below the last)
+        M = (size_t)pN * (pH >> (l - 1)) * (pW >> (l - 1)) / r.pixdiv;
+        C = (feat << (l - 1)) * r.chmul;
+        return r.levels ? &(*r.levels)[l] : r.bott;
+    }
+    return nullptr;
 }
 
 void UNetModel::algorithmic_flops(int n, int h, int w, double& fwd, double& step) const {

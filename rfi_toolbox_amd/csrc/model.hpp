@@ -22,6 +22,30 @@ struct PlaneBuf {
     int nchunks = 0;
     void ensure(rfi_ctx* c, int64_t pixels, int C, int P);
     void free();
+    YRef ref() const { return YRef(p, pstride); }                       // as a bfloat16 [pixel][pstride] tensor (P = 1)
+    PlaneSeg seg() const { return PlaneSeg{p, pstride, nchunks}; }      // as a K-segment of a contraction
+};
+
+// One tensor of the U-Net's plane data flow (model_planes.cpp): a raw conv output or a gradient tensor that the mode stores
+// either as float32 (bufs[f32]) or as bfloat16 (pl[b16]).  UNetModel::prepare_planes decides `half`, nobody else; the passes
+// ask UNetModel::flow() for the storage in use
+struct FlowTensor {
+    int f32 = -1, b16 = -1;
+    bool half = false;
+};
+
+// a tensor resolved to its storage, which is what the launches take: a float32 pointer, or a bfloat16 one with its pixel
+// stride (neither: no tensor)
+struct FlowRef {
+    float* f = nullptr;
+    bf16_t* h = nullptr;
+    int64_t pstride = 0;
+    FlowRef() = default;
+    FlowRef(float* p) : f(p) {}
+    FlowRef(const PlaneBuf& b) : h(b.p), pstride(b.pstride) {}
+    FlowRef(bf16_t* p, int64_t ps) : h(p), pstride(ps) {}      // (a dense view of a scratch tensor)
+    explicit operator bool() const { return f || h; }
+    YRef ref() const { return h ? YRef(h, pstride) : YRef(f); }
 };
 
 // Conv3x3(pad 1)+bias -> BatchNorm2d -> ReLU
@@ -280,7 +304,10 @@ struct rfi_model {
     // its weight gradient from dy ([M][cout]) into dw [tap][cout][cin]
     rfi::WgradArgs wgrad_same(rfi::View x, rfi::InXform xf_x, const float* dy, rfi::Shape s, int R, int pad, int cin, int cout,
                               float* dw) const;
-    // conv_same into Y with the BatchNorm statistics of layer c from its epilogue + finalize (train), or its eval coefficients
+    // BatchNorm of layer c behind the conv that wrote its M output pixels.  Train: the batch statistics from the `records` the conv
+    // epilogue left in ws_red (none: a pass over the float32 output Y), finalize, running statistics; eval: the coefficients
+    void bn_tail(rfi::ConvBN& c, const float* Y, int64_t M, bool train, int records);
+    // conv_same into Y, then bn_tail
     void conv_bn(rfi::ConvBN& c, rfi::View in, rfi::InXform xf, rfi::Shape s, const float* w, const float* w3, int R, int pad,
                  int cin, float* Y, bool train, double flops);
     // ConvTranspose2d(k2, s2) over the input grid s: the forward launch but its output (y / y16: the caller's) ...
@@ -352,9 +379,14 @@ struct UNetModel : rfi_model {
     // BN-apply + activation of layer c as a load transform for its consumers (slope 0 = ReLU)
     rfi::InXform bn_xf(const rfi::ConvBN& c) const { return rfi::act_of(c, act_slope); }
     // convs: enc1.c1, enc1.c2, ..., encD.c2, bott.c1, bott.c2, decD.c1, decD.c2, ..., dec1.c2; ups: decD.up ... dec1.up
-    std::vector<int> encY1, encY2, concat, pool, decY1, decY2, gA, gB, dconcat, dpool;
+    // Raw conv outputs and gradient tensors, by level.  The float32 path reads their float32 storage, buf(t); on a plane data
+    // flow some are bfloat16 tensors instead: flow(t), below
+    std::vector<rfi::FlowTensor> encY1, encY2, decY1, decY2, gA, gB, dconcat, dpool;
+    rfi::FlowTensor bottY1, bottY2, gBottA, gBottB;
+    std::vector<int> concat, pool;
     std::vector<int> gAe, gBe;        // float32 U-Net path: the encoder phase's gradient tensors (gA / gB are the decoder's)
-    int bottY1 = -1, bottY2 = -1, gBottA = -1, gBottB = -1;
+    using rfi_model::buf;
+    float* buf(const rfi::FlowTensor& t) { return bufs[t.f32].p; }
     // conv-bias gradients of the float32 U-Net path: bn_bwd_apply leaves its per-block partial sums in a per-layer region of
     // dbias_pool; ONE batched launch at the end of the backward pass finishes them all (single-GPU steps: with a gradient
     // exchange the buckets need every gradient of a layer when the layer is done)
@@ -385,20 +417,20 @@ struct UNetModel : rfi_model {
 
     // ---- plane data flow (model_planes.cpp; planesP in the base)
     std::vector<rfi::PlaneBuf> pl;
-    std::vector<int> pA1e, pSkip, pPool, pUp, pA1d, pdYa, pdYb, pdYaE, pdYbE, upf;
+    std::vector<int> pA1e, pSkip, pPool, pUp, pA1d, pdYa, pdYb, pdYaE, pdYbE, pUpIn, upf;      // (upf: bufs indices)
     int pXin = -1, pA1b = -1, pdYbottA = -1, pdYbottB = -1;
-    // bf16 data flow (P = 1, feat % 4 == 0): raw conv outputs that only elementwise kernels read are stored as bfloat16
-    // (indices into pl; -1: float32 in bufs): both convs of every encoder, the first of the bottleneck and of every
-    // decoder, the last decoder's second.  The four tensors a transposed conv reads stay float32 tensors holding
-    // bf16-rounded values, so the arithmetic is uniform: every conv output of this mode is a bfloat16 value
+    // bf16 data flow (P = 1): three gates of the width decide which tensors are bfloat16 (prepare_planes holds the table).
+    // y16_flow (feat % 4 == 0): raw conv outputs that only elementwise kernels read -- both convs of every encoder, the first
+    // of the bottleneck and of every decoder, the last decoder's second.  The tensors a transposed conv reads stay float32
+    // tensors holding bf16-rounded values, so the arithmetic is uniform: every conv output of this mode is a bfloat16 value
     bool y16_flow = false;
-    std::vector<int> yE1, yE2, yD1;
-    int yB1 = -1, yD2top = -1;
-    // bf16 data flow: the gradient tensors the input-gradient convs write (dA of every first conv, the pooled gradients) are
-    // bfloat16 too when the level widths are multiples of 16
+    // g16_flow (level widths multiples of 16): the gradient tensors the input-gradient convs write (dA of every first conv, the
+    // pooled gradients), and dA of the second convs where an elementwise kernel produces it (head, max-pool backward)
     bool g16_flow = false;
-    std::vector<int> g16A, g16B, g16pool;       // g16A: dA of the second convs where an elementwise kernel produces it (head, max-pool backward)
-    int g16BottB = -1;
+    // gA.<l> has two storages in one pass: the decoder phase and the encoder phase share the tensor (gA: the encoder's rule)
+    std::vector<rfi::FlowTensor> gAdec;
+    // the storage of t in use
+    rfi::FlowRef flow(const rfi::FlowTensor& t) { return t.half ? rfi::FlowRef(pl[t.b16]) : rfi::FlowRef(buf(t)); }
     // ResNet-style encoder on the bf16 flow (feat % 16 == 0; model_planes.cpp): indices into pl.  Every block owns its
     // raw conv outputs, its activation planes and its dY planes (the side stream's weight gradients read them until side_join)
     struct ResPlanes {
@@ -414,17 +446,15 @@ struct UNetModel : rfi_model {
     void forward_resnet_planes(rfi::PlaneSeg& cur, int n, int h, int w, bool train_mode);
     void backward_resnet_planes(int n, int h, int w);
     // transposed convs on the plane kernels (bfloat16 flow, init_features % 32 == 0): the DoubleConv outputs they read are bfloat16
-    // (yB2, yD2[l]) and activated once into planes (pUpIn[l]: the forward operand AND the weight gradient's); the decoder's first
-    // conv writes its input gradient [up | skip] as bfloat16 (g16cat[l]) and the transposed conv's input gradient is bfloat16
-    // too (g16BottA, g16A[l + 1]), with the BatchNorm-backward sums of the layer below in its epilogue
+    // (bottY2, decY2[l]) and activated once into planes (pUpIn[l]: the forward operand AND the weight gradient's); the decoder's
+    // first conv writes its input gradient [up | skip] as bfloat16 (dconcat[l]) and the transposed conv's input gradient is
+    // bfloat16 too (gBottA, gA[l + 1]), with the BatchNorm-backward sums of the layer below in its epilogue
     bool convt_planes = false;
     // the skip half (channels C .. 2 C - 1) of the gradient decoder l's first conv sends into its [up | skip] input
     rfi::YRef skip_grad(int l, int C) {
-        if (convt_planes) return rfi::YRef(pl[g16cat[l]].p + C, pl[g16cat[l]].pstride);
-        return rfi::YRef(buf(dconcat[l]) + C, (int64_t)2 * C);
+        const rfi::FlowRef g = flow(dconcat[l]);
+        return g.h ? rfi::YRef(g.h + C, g.pstride) : rfi::YRef(g.f + C, (int64_t)2 * C);
     }
-    std::vector<int> yD2, pUpIn, g16cat;
-    int yB2 = -1, g16BottA = -1;
     rfi::bf16_t* wb_pool = nullptr;
     rfi::BatchTable wb;               // (the forward-direction filter images first)
     void set_planes(int P);           // switches the data flow; frees plane tensors of another P
@@ -432,6 +462,13 @@ struct UNetModel : rfi_model {
     void refresh_plane_weights(rfi::Half half);      // InputGrad: + the parity-class tables
     void forward_planes(const float* x_dev, int n, int h, int w, bool train_mode);
     void backward_planes(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w);
+    // weight-gradient launches of the plane kernel: of conv layer c over the output grid s (in: its input in nseg K-segments,
+    // dY: the gradient w.r.t. its raw output) and of transposed conv u over its input grid s (dUp: the gradient w.r.t. its
+    // output, in: its activated input).  prepare_planes sizes ws_slab from the same descriptors with null operands
+    rfi::PWgradArgs pwgrad_args(const rfi::ConvBN& c, const rfi::PlaneSeg* in, int nseg, rfi::PlaneSeg dY, rfi::Shape s);
+    rfi::PWgradArgs convt_pwgrad_args(const rfi::UpConv& u, rfi::PlaneSeg dUp, rfi::PlaneSeg in, rfi::Shape s);
+    // the flow tensor a debug name means (null: none of them) with its pixels and channels; a level out of range throws
+    const rfi::FlowTensor* flow_named(const std::string& base, int idx, size_t& M, int& C) const;
     // debug_tensor of the plain U-Net on a plane data flow: bfloat16 and plane tensors as float32 values, "<name>:pad"
     void debug_tensor_planes(const std::string& name, const std::string& base, int idx, bool to_host, rfi::CallScope& sc, const float*& src,
                              size_t& n);

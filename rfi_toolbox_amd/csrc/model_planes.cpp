@@ -50,80 +50,69 @@ void PlaneBuf::free() {
 }  // namespace rfi
 
 void UNetModel::prepare_planes(int n, int h, int w) {
-    const int P = planesP, D = depth, IB = i_bott;
+    const int P = planesP, D = depth;
     const bool rs = resnet_encoder;                    // ResNet-style encoder: its own tensors instead of the U-Net encoder's
+    auto one = [&]() { pl.emplace_back(); return (int)pl.size() - 1; };
     if (pl.empty()) {
-        auto mk = [&](std::vector<int>& v) { v.assign(D + 1, -1); for (int l = 1; l <= D; ++l) { pl.emplace_back(); v[l] = (int)pl.size() - 1; } };
-        mk(pA1e); mk(pSkip); mk(pPool); mk(pUp); mk(pA1d); mk(pdYa); mk(pdYb); mk(pdYaE); mk(pdYbE);
-        auto one = [&]() { pl.emplace_back(); return (int)pl.size() - 1; };
+        auto mk = [&](std::vector<int>& v) { v.assign(D + 1, -1); for (int l = 1; l <= D; ++l) v[l] = one(); };      // one per level
+        mk(pA1e); mk(pSkip); mk(pPool); mk(pUp); mk(pA1d); mk(pdYa); mk(pdYb); mk(pdYaE); mk(pdYbE); mk(pUpIn);
         pXin = one(); pA1b = one(); pdYbottA = one(); pdYbottB = one();
         upf.assign(D + 1, -1);
         for (int l = 1; l <= D; ++l) upf[l] = new_buf();
+        // the bfloat16 twins of the flow tensors (allocated below where the mode stores them)
+        for (auto* v : {&encY1, &encY2, &decY1, &decY2, &gA, &gB, &dconcat, &dpool})
+            for (int l = 1; l <= D; ++l) (*v)[l].b16 = one();
+        for (FlowTensor* t : {&bottY1, &bottY2, &gBottA, &gBottB}) t->b16 = one();
+        gAdec = gA;
     }
-    const int64_t M1 = (int64_t)n * h * w;
+    auto pixels = [&](int l) { return (int64_t)n * (h >> (l - 1)) * (w >> (l - 1)); };      // of level l (D + 1: the bottleneck)
+    const int64_t M1 = pixels(1), Mb = pixels(D + 1);
+    const int Cb = feat << D;
     pl[pXin].ensure(ctx, M1, in_ch, P);
     for (int l = 1; l <= D; ++l) {
-        const int64_t M = (int64_t)n * (h >> (l - 1)) * (w >> (l - 1));
+        const int64_t M = pixels(l);
         const int C = feat << (l - 1);
         for (int i : {pSkip[l], pUp[l], pA1d[l], pdYa[l], pdYb[l]}) pl[i].ensure(ctx, M, C, P);
         if (!rs) for (int i : {pA1e[l], pdYaE[l], pdYbE[l]}) pl[i].ensure(ctx, M, C, P);
         if (!rs || l == D) pl[pPool[l]].ensure(ctx, M / 4, C, P);
         bufs[upf[l]].ensure(ctx, (size_t)M * C);
     }
-    const int64_t Mb = (int64_t)n * (h >> D) * (w >> D);
-    for (int i : {pA1b, pdYbottA, pdYbottB}) pl[i].ensure(ctx, Mb, feat << D, P);
+    for (int i : {pA1b, pdYbottA, pdYbottB}) pl[i].ensure(ctx, Mb, Cb, P);
     y16_flow = P == 1 && feat % 4 == 0;
-    if (y16_flow) {
-        if (yB1 < 0) {
-            auto mk1 = [&](std::vector<int>& v) { v.assign(D + 1, -1); for (int l = 1; l <= D; ++l) { pl.emplace_back(); v[l] = (int)pl.size() - 1; } };
-            mk1(yE1); mk1(yE2); mk1(yD1);
-            pl.emplace_back(); yB1 = (int)pl.size() - 1;
-            pl.emplace_back(); yD2top = (int)pl.size() - 1;
-        }
-        for (int l = 1; l <= D; ++l) {
-            const int64_t M = (int64_t)n * (h >> (l - 1)) * (w >> (l - 1));
-            pl[yD1[l]].ensure(ctx, M, feat << (l - 1), 1);
-            if (!rs) for (int i : {yE1[l], yE2[l]}) pl[i].ensure(ctx, M, feat << (l - 1), 1);
-        }
-        pl[yB1].ensure(ctx, Mb, feat << D, 1);
-        pl[yD2top].ensure(ctx, M1, feat, 1);
-    }
     g16_flow = y16_flow && feat % 16 == 0;
-    if (g16_flow) {
-        if (g16BottB < 0) {
-            auto mk1 = [&](std::vector<int>& v) { v.assign(D + 1, -1); for (int l = 1; l <= D; ++l) { pl.emplace_back(); v[l] = (int)pl.size() - 1; } };
-            mk1(g16A); mk1(g16B); mk1(g16pool);
-            pl.emplace_back(); g16BottB = (int)pl.size() - 1;
-        }
-        for (int l = 1; l <= D; ++l) {
-            const int64_t M = (int64_t)n * (h >> (l - 1)) * (w >> (l - 1));
-            if (!rs || l == 1) pl[g16A[l]].ensure(ctx, M, feat << (l - 1), 1);
-            pl[g16B[l]].ensure(ctx, M, feat << (l - 1), 1);
-            if (!rs || l == D) pl[g16pool[l]].ensure(ctx, M / 4, feat << (l - 1), 1);
-        }
-        pl[g16BottB].ensure(ctx, Mb, feat << D, 1);
-    }
     convt_planes = g16_flow && feat % 32 == 0;
-    if (convt_planes) {
-        if (yB2 < 0) {
-            auto mk1 = [&](std::vector<int>& v) { v.assign(D + 1, -1); for (int l = 1; l <= D; ++l) { pl.emplace_back(); v[l] = (int)pl.size() - 1; } };
-            mk1(yD2); mk1(pUpIn); mk1(g16cat);
-            pl.emplace_back(); yB2 = (int)pl.size() - 1;
-            pl.emplace_back(); g16BottA = (int)pl.size() - 1;
-        }
-        for (int l = 1; l <= D; ++l) {
-            const int64_t M = (int64_t)n * (h >> (l - 1)) * (w >> (l - 1));
-            const int C = feat << (l - 1);
-            if (l > 1) { pl[yD2[l]].ensure(ctx, M, C, 1); pl[g16A[l]].ensure(ctx, M, C, 1); }
-            pl[pUpIn[l]].ensure(ctx, M / 4, 2 * C, 1);          // the input of decoder l's transposed conv: level l + 1, 2 C channels
-            pl[g16cat[l]].ensure(ctx, M, 2 * C, 1);
-        }
-        pl[yB2].ensure(ctx, Mb, feat << D, 1);
-        pl[g16BottA].ensure(ctx, Mb, feat << D, 1);
+    // ---- Where every flow tensor lives (DESIGN.md section 3 has the same table): t is a bfloat16 tensor iff `half`, and its
+    // bfloat16 storage is allocated here -- unless another owner has the tensor (own = false).  This block is the only place
+    // that reads the gates to choose a storage.  The float32 tensors of prepare_shape stay allocated either way
+    auto place = [&](FlowTensor& t, bool half, int64_t M, int C, bool own = true) {
+        t.half = half;
+        if (half && own) pl[t.b16].ensure(ctx, M, C, 1);
+    };
+    const bool y16 = y16_flow, g16 = g16_flow, ctp = convt_planes;
+    for (int l = 1; l <= D; ++l) {
+        const int64_t M = pixels(l);
+        const int C = feat << (l - 1);
+        place(encY1[l], y16, M, C, !rs);              // (the ResNet-style encoder owns its raw outputs: rpb)
+        place(encY2[l], y16, M, C, !rs);
+        place(decY1[l], y16, M, C);
+        place(decY2[l], l == 1 ? y16 : ctp, M, C);    // the head reads level 1, a transposed conv the others
+        place(gB[l], g16, M, C);
+        place(dpool[l], g16, M / 4, C, !rs || l == D);
+        place(dconcat[l], ctp, M, 2 * C);
+        // gA.<l> has two storages in one pass, on the same tensors.  Decoder phase: the head (one output channel) writes level 1,
+        // a transposed conv on the plane kernels the others.  Encoder phase: the max-pool backward writes it (the ResNet-style
+        // encoder has no such tensor; the head's bfloat16 gA.1 is allocated for it at any out_ch)
+        place(gAdec[l], l == 1 ? g16 && out_ch == 1 : ctp, M, C);
+        place(gA[l], g16, M, C, !rs || l == 1);
     }
+    place(bottY1, y16, Mb, Cb);
+    place(bottY2, ctp, Mb, Cb);                        // (read by the transposed conv: float32 for the round-1 kernel)
+    place(gBottA, ctp, Mb, Cb);
+    place(gBottB, g16, Mb, Cb);
+    if (convt_planes)                                  // the input of decoder l's transposed conv: level l + 1, 2 C channels
+        for (int l = 1; l <= D; ++l) pl[pUpIn[l]].ensure(ctx, pixels(l + 1), feat << l, 1);
     if (rs) {
         RFI_REQUIRE(P == 1 && y16_flow && g16_flow, "UNetResNet18 on the plane kernels: bfloat16 flow with init_features % 16 == 0 only");
-        auto one = [&]() { pl.emplace_back(); return (int)pl.size() - 1; };
         if (rpStemY < 0) {
             rpStemY = one(); rpA0 = one(); rpdY0 = one(); rp_dA1 = one(); rp_dX = one(); rp_dz[0] = one(); rp_dz[1] = one();
             if (rpb.empty()) rpb.assign(blocks.size(), ResPlanes());
@@ -145,40 +134,58 @@ void UNetModel::prepare_planes(int n, int h, int w) {
             if (b.stride == 2) for (int i : {r.Yd, r.dYd}) pl[i].ensure(ctx, M, b.cout, 1);
         }
     }
-    // weight-gradient slabs of the plane kernel
-    size_t slab_need = 0;
+    // weight-gradient slabs of the plane kernel: the largest need over the descriptors the backward pass will launch, from the
+    // same builders with null operands
+    auto none = [](int C) { return PlaneSeg{nullptr, 0, plane_chunks(C)}; };
+    size_t need = 0;
     for (size_t ci = 0; ci < convs.size(); ++ci) {
         const ConvBN& c = convs[ci];
-        const int lvl = c.level;
-        PWgradArgs a;
-        const bool two = (int)ci >= IB + 2 && (((int)ci - (IB + 2)) & 1) == 0;      // decoder conv1: [up | skip]
-        a.nseg = two ? 2 : 1;
-        a.seg_c[0] = two ? c.cin / 2 : c.cin;
-        a.seg_c[1] = two ? c.cin / 2 : 0;
-        a.xop[0].nchunks = plane_chunks(a.seg_c[0]);
-        a.xop[1].nchunks = two ? plane_chunks(a.seg_c[1]) : 0;
-        a.yop.nchunks = plane_chunks(c.cout);
-        a.Cy = c.cout;
-        a.N = n; a.H = h >> (lvl - 1); a.W = w >> (lvl - 1); a.Hx = a.H * c.stride; a.Wx = a.W * c.stride;
-        a.R = c.R; a.S = c.stride; a.pad = c.R == 3 ? 1 : 0;
-        if (c.stride == 2 || c.R != 3) a.P = 1;
-        a.tap_stride = (int64_t)c.cin_p * c.cout;
-        slab_need = std::max(slab_need, pwgrad_slab_floats(a));
+        const bool two = (int)ci >= i_bott + 2 && (((int)ci - (i_bott + 2)) & 1) == 0;      // decoder conv1: [up | skip]
+        const PlaneSeg in[2] = {none(two ? c.cin / 2 : c.cin), none(c.cin / 2)};
+        need = std::max(need, pwgrad_slab_floats(pwgrad_args(c, in, two ? 2 : 1, none(c.cout), Shape{n, h >> (c.level - 1), w >> (c.level - 1)})));
     }
     if (convt_planes)
-        for (int k = 0; k < D; ++k) {
-            const int l = D - k;
-            PWgradArgs a;
-            a.nseg = 1; a.seg_c[0] = ups[k].cout;
-            a.xop[0].nchunks = plane_chunks(ups[k].cout);
-            a.yop.nchunks = plane_chunks(ups[k].cin);
-            a.Cy = ups[k].cin; a.P = 1;
-            a.N = n; a.H = h >> l; a.W = w >> l; a.Hx = a.H * 2; a.Wx = a.W * 2;
-            a.R = 2; a.S = 2; a.pad = 0;
-            a.tap_stride = (int64_t)ups[k].cin * ups[k].cout;
-            slab_need = std::max(slab_need, pwgrad_slab_floats(a));
-        }
-    if (bufs[ws_slab].n < slab_need + 16) bufs[ws_slab].ensure(ctx, slab_need + 16);
+        for (int k = 0; k < D; ++k)               // (decoder level D - k: the grid of its input)
+            need = std::max(need, pwgrad_slab_floats(convt_pwgrad_args(ups[k], none(ups[k].cout), none(ups[k].cin), Shape{n, h >> (D - k), w >> (D - k)})));
+    if (bufs[ws_slab].n < need + 16) bufs[ws_slab].ensure(ctx, need + 16);
+}
+
+PWgradArgs UNetModel::pwgrad_args(const ConvBN& c, const PlaneSeg* in, int nseg, PlaneSeg dY, Shape s) {
+    PWgradArgs wa;
+    wa.xop[0] = in[0];
+    if (nseg > 1) wa.xop[1] = in[1];
+    wa.nseg = nseg;
+    wa.seg_c[0] = nseg > 1 ? c.cin / 2 : c.cin;
+    wa.seg_c[1] = nseg > 1 ? c.cin / 2 : 0;
+    wa.cx_layout = c.cin_p;
+    wa.yop = dY;
+    wa.Cy = c.cout;
+    wa.P = planesP;
+    wa.N = s.N; wa.H = s.H; wa.W = s.W; wa.Hx = s.H * c.stride; wa.Wx = s.W * c.stride;
+    wa.R = c.R; wa.S = c.stride; wa.pad = c.R == 3 ? 1 : 0;
+    wa.dw = grads + c.w_off;
+    wa.tap_stride = (int64_t)c.cin_p * c.cout;
+    wa.sy = c.cin_p; wa.sx = 1;
+    wa.algo_flops = 2.0 * s.N * s.H * s.W * (double)(c.R * c.R) * c.cin * c.cout;
+    wa.slab = buf(ws_slab);
+    wa.slab_floats = bufs[ws_slab].n;
+    return wa;
+}
+
+// dW[tap][cout][cin] = sum_pixels act(prev)[i, j, cin] * dUp[2 i + a, 2 j + b, cout]
+PWgradArgs UNetModel::convt_pwgrad_args(const UpConv& u, PlaneSeg dUp, PlaneSeg in, Shape s) {
+    PWgradArgs wa;
+    wa.xop[0] = dUp; wa.nseg = 1; wa.seg_c[0] = u.cout;
+    wa.yop = in; wa.Cy = u.cin; wa.P = 1;
+    wa.N = s.N; wa.H = s.H; wa.W = s.W; wa.Hx = 2 * s.H; wa.Wx = 2 * s.W;
+    wa.R = 2; wa.S = 2; wa.pad = 0;
+    wa.dw = grads + u.w_off;
+    wa.tap_stride = (int64_t)u.cin * u.cout;
+    wa.sy = 1; wa.sx = u.cin;
+    wa.algo_flops = 2.0 * s.N * s.H * s.W * 4.0 * u.cin * u.cout;
+    wa.slab = buf(ws_slab);
+    wa.slab_floats = bufs[ws_slab].n;
+    return wa;
 }
 
 // filters of every 3x3 layer in MFMA B-operand order, both directions, rebuilt with the dgrad layouts after each
@@ -259,18 +266,8 @@ void UNetModel::refresh_plane_weights(Half half) {
 
 namespace {
 
-PlaneSeg seg_of(const PlaneBuf& b) { return PlaneSeg{b.p, b.pstride, b.nchunks}; }
-
-// where a raw conv output lives: a float32 tensor (values rounded to bf16 when the bf16 flow is on) or a bfloat16 one
-struct YT {
-    float* f = nullptr;
-    const PlaneBuf* h = nullptr;
-    YRef ref() const { return h ? YRef(h->p, h->pstride) : YRef(f); }
-};
-
 // (s: the OUTPUT grid; a stride-2 layer reads an input of twice that size)
-void run_pconv_bn(UNetModel* m, ConvBN& c, const PlaneSeg* in, int nseg, Shape s, YT Yt, bool train) {
-    float* Y = Yt.f;
+void run_pconv_bn(UNetModel* m, ConvBN& c, const PlaneSeg* in, int nseg, Shape s, FlowRef Y, bool train) {
     PConvArgs a;
     a.x[0] = in[0];
     if (nseg > 1) a.x[1] = in[1];
@@ -280,38 +277,26 @@ void run_pconv_bn(UNetModel* m, ConvBN& c, const PlaneSeg* in, int nseg, Shape s
     a.Cout = c.cout;
     a.wB = c.wBf;
     a.bias = m->params + c.b_off;
-    if (Yt.h) { a.y16 = Yt.h->p; a.y_pstride = (int)Yt.h->pstride; }
-    else { a.y = Y; a.y_pstride = c.cout; a.round_y = m->y16_flow; }
+    if (Y.h) { a.y16 = Y.h; a.y_pstride = (int)Y.pstride; }
+    else { a.y = Y.f; a.y_pstride = c.cout; a.round_y = m->y16_flow; }      // (float32 holding bf16-rounded values in the bf16 flow)
     a.Hout = s.H; a.Wout = s.W;
     a.algo_flops = 2.0 * s.N * s.H * s.W * (double)(c.R * c.R) * c.cin * c.cout;
-    float* ws = m->buf(m->ws_red);
     if (train) {
-        a.stats = reinterpret_cast<double*>(ws);
+        a.stats = reinterpret_cast<double*>(m->buf(m->ws_red));
         a.stats_max_records = (int)(bn_stats_ws_floats(c.cout) / ((size_t)c.cout * 4));
     }
     launch_pconv(m->ctx, a);
-    const int64_t M = (int64_t)s.N * s.H * s.W;
-    if (train) {
-        RFI_REQUIRE(a.stats_records > 0 || !Yt.h, "plane conv: no statistics records for a bfloat16 output");
-        if (a.stats_records == 0) launch_bn_stats(m->ctx, Y, M, c.cout, ws);
-        launch_bn_finalize(m->ctx, ws, M, c.cout, m->params + c.g_off, m->params + c.be_off, c.running_mean(),
-                           c.running_var(), c.ema_repeats, c.mean(), c.invstd(), c.scale(), c.shift(), nullptr,
-                           a.stats_records);
-        c.nbt += c.ema_repeats;
-    } else {
-        launch_bn_eval_coeffs(m->ctx, c.cout, m->params + c.g_off, m->params + c.be_off, c.running_mean(),
-                              c.running_var(), c.scale(), c.shift());
-    }
+    RFI_REQUIRE(!train || a.stats_records > 0 || !Y.h, "plane conv: no statistics records for a bfloat16 output");
+    m->bn_tail(c, Y.f, (int64_t)s.N * s.H * s.W, train, a.stats_records);
 }
 
 // Conv3x3+BN+act twice: Y1 = conv(in) ; A1 = planes(act(BN(Y1))) ; Y2 = conv(A1)
-void double_conv(UNetModel* m, ConvBN& c1, ConvBN& c2, const PlaneSeg* in, int nseg, Shape s, YT Y1, PlaneBuf& A1,
-                 YT Y2, bool train) {
+void double_conv(UNetModel* m, ConvBN& c1, ConvBN& c2, const PlaneSeg* in, int nseg, Shape s, FlowRef Y1, PlaneBuf& A1,
+                 FlowRef Y2, bool train) {
     run_pconv_bn(m, c1, in, nseg, s, Y1, train);
     const int64_t M = (int64_t)s.N * s.H * s.W;
-    launch_act_split(m->ctx, View{Y1.f, c1.cout}, M, c1.cout, m->bn_xf(c1), m->planesP, A1.p, A1.pstride,
-                     Y1.h ? Y1.h->p : nullptr, Y1.h ? Y1.h->pstride : 0);
-    const PlaneSeg a1 = seg_of(A1);
+    launch_act_split(m->ctx, View{Y1.f, c1.cout}, M, c1.cout, m->bn_xf(c1), m->planesP, A1.p, A1.pstride, Y1.h, Y1.pstride);
+    const PlaneSeg a1 = A1.seg();
     run_pconv_bn(m, c2, &a1, 1, s, Y2, train);
 }
 
@@ -325,10 +310,9 @@ void UNetModel::forward_resnet_planes(PlaneSeg& cur, int n, int h, int w, bool t
     const int D = depth;
     {
         ConvBN& c = convs[0];
-        YT y; y.h = &pl[rpStemY];
-        run_pconv_bn(this, c, &cur, 1, Shape{n, h, w}, y, train);
-        launch_act_split(ctx, View{nullptr, c.cout}, (int64_t)n * h * w, c.cout, bn_xf(c), 1, pl[rpA0].p, pl[rpA0].pstride, pl[rpStemY].p,
-                         pl[rpStemY].pstride);
+        const PlaneBuf &Y = pl[rpStemY], &A0 = pl[rpA0];
+        run_pconv_bn(this, c, &cur, 1, Shape{n, h, w}, Y, train);
+        launch_act_split(ctx, View{nullptr, c.cout}, (int64_t)n * h * w, c.cout, bn_xf(c), 1, A0.p, A0.pstride, Y.p, Y.pstride);
         side_rebuild_wd();                        // (the input-gradient-direction filter images: side stream, under the forward pass)
     }
     const PlaneBuf* a_in = &pl[rpA0];
@@ -339,72 +323,64 @@ void UNetModel::forward_resnet_planes(PlaneSeg& cur, int n, int h, int w, bool t
         ConvBN& c2 = convs[b.c2];
         Shape s{n, h >> (b.level - 1), w >> (b.level - 1)};
         const int64_t M = (int64_t)s.N * s.H * s.W;
-        const PlaneSeg in = seg_of(*a_in);
-        YT y1, y2; y1.h = &pl[r.Y1]; y2.h = &pl[r.Y2];
-        run_pconv_bn(this, c1, &in, 1, s, y1, train);
-        if (b.stride == 2) { YT yd; yd.h = &pl[r.Yd]; run_pconv_bn(this, convs[b.cd], &in, 1, s, yd, train); }
-        launch_act_split(ctx, View{nullptr, c1.cout}, M, c1.cout, bn_xf(c1), 1, pl[r.A1].p, pl[r.A1].pstride, pl[r.Y1].p, pl[r.Y1].pstride);
-        const PlaneSeg a1 = seg_of(pl[r.A1]);
-        run_pconv_bn(this, c2, &a1, 1, s, y2, train);
+        const PlaneBuf &Y1 = pl[r.Y1], &Y2 = pl[r.Y2], &A1 = pl[r.A1], &A = pl[r.A];
+        const PlaneSeg in = a_in->seg();
+        run_pconv_bn(this, c1, &in, 1, s, Y1, train);
+        if (b.stride == 2) run_pconv_bn(this, convs[b.cd], &in, 1, s, pl[r.Yd], train);
+        launch_act_split(ctx, View{nullptr, c1.cout}, M, c1.cout, bn_xf(c1), 1, A1.p, A1.pstride, Y1.p, Y1.pstride);
+        const PlaneSeg a1 = A1.seg();
+        run_pconv_bn(this, c2, &a1, 1, s, Y2, train);
         if (b.stride == 2) {
             ConvBN& cd = convs[b.cd];
-            launch_bn_add_relu16(ctx, pl[r.Y2].p, pl[r.Y2].pstride, c2.scale(), c2.shift(), pl[r.Yd].p, pl[r.Yd].pstride, cd.scale(), cd.shift(),
-                                 M, b.cout, pl[r.A].p, pl[r.A].pstride);
+            const PlaneBuf& Yd = pl[r.Yd];
+            launch_bn_add_relu16(ctx, Y2.p, Y2.pstride, c2.scale(), c2.shift(), Yd.p, Yd.pstride, cd.scale(), cd.shift(), M, b.cout, A.p, A.pstride);
         } else {
-            launch_bn_add_relu16(ctx, pl[r.Y2].p, pl[r.Y2].pstride, c2.scale(), c2.shift(), a_in->p, a_in->pstride, nullptr, nullptr, M, b.cout,
-                                 pl[r.A].p, pl[r.A].pstride);
+            launch_bn_add_relu16(ctx, Y2.p, Y2.pstride, c2.scale(), c2.shift(), a_in->p, a_in->pstride, nullptr, nullptr, M, b.cout, A.p, A.pstride);
         }
-        a_in = &pl[r.A];
+        a_in = &A;
     }
     // MaxPool2d(2) of the last stage (identity "BatchNorm": scale 1, shift 0; the values are >= 0), + its copy as the skip
     const ResBlock& lb = blocks.back();
     launch_bn_relu_pool_planes(ctx, nullptr, n, h >> (D - 1), w >> (D - 1), lb.cout, rs_ones, rs_zeros, 0.0f, 1, pl[pSkip[D]].p,
                                pl[pSkip[D]].pstride, pl[pPool[D]].p, pl[pPool[D]].pstride, a_in->p, a_in->pstride);
-    cur = seg_of(pl[pPool[D]]);
+    cur = pl[pPool[D]].seg();
 }
 
 void UNetModel::forward_planes(const float* x_dev, int n, int h, int w, bool train_mode) {
     const int D = depth, P = planesP;
     prepare_planes(n, h, w);
     launch_act_split(ctx, View{x_dev, in_ch}, (int64_t)n * h * w, in_ch, InXform{}, P, pl[pXin].p, pl[pXin].pstride);
-    PlaneSeg cur = seg_of(pl[pXin]);
+    PlaneSeg cur = pl[pXin].seg();
     const int IB = i_bott;
-    // a raw conv output: the bfloat16 tensor pl[hi] when the bf16 flow is on (hi >= 0), else the float32 tensor bufs[fi]
-    auto yt = [&](int fi, int hi) { YT y; if (y16_flow && hi >= 0) y.h = &pl[hi]; else y.f = buf(fi); return y; };
     if (resnet_encoder) forward_resnet_planes(cur, n, h, w, train_mode);
     else for (int l = 1; l <= D; ++l) {
         Shape s{n, h >> (l - 1), w >> (l - 1)};
         ConvBN& c1 = convs[2 * (l - 1)];
         ConvBN& c2 = convs[2 * (l - 1) + 1];
-        const YT y2 = yt(encY2[l], y16_flow ? yE2[l] : -1);
-        double_conv(this, c1, c2, &cur, 1, s, yt(encY1[l], y16_flow ? yE1[l] : -1), pl[pA1e[l]], y2, train_mode);
+        const FlowRef y2 = flow(encY2[l]);
+        double_conv(this, c1, c2, &cur, 1, s, flow(encY1[l]), pl[pA1e[l]], y2, train_mode);
         if (l == 1) side_rebuild_wd();            // (the input-gradient-direction filter images: side stream, under the forward pass)
         launch_bn_relu_pool_planes(ctx, y2.f, s.N, s.H, s.W, c2.cout, c2.scale(), c2.shift(), act_slope, P,
-                                   pl[pSkip[l]].p, pl[pSkip[l]].pstride, pl[pPool[l]].p, pl[pPool[l]].pstride,
-                                   y2.h ? y2.h->p : nullptr, y2.h ? y2.h->pstride : 0);
-        cur = seg_of(pl[pPool[l]]);
+                                   pl[pSkip[l]].p, pl[pSkip[l]].pstride, pl[pPool[l]].p, pl[pPool[l]].pstride, y2.h, y2.pstride);
+        cur = pl[pPool[l]].seg();
     }
-    {
-        Shape s{n, h >> D, w >> D};
-        double_conv(this, convs[IB], convs[IB + 1], &cur, 1, s, yt(bottY1, y16_flow ? yB1 : -1), pl[pA1b],
-                    yt(bottY2, convt_planes ? yB2 : -1), train_mode);     // (read by the transposed conv: float32 tensor for the round-1 kernel)
-    }
-    const float* prevY = buf(bottY2);
-    const PlaneBuf* prevY16 = convt_planes ? &pl[yB2] : nullptr;
+    double_conv(this, convs[IB], convs[IB + 1], &cur, 1, Shape{n, h >> D, w >> D}, flow(bottY1), pl[pA1b], flow(bottY2), train_mode);
+    FlowRef prevY = flow(bottY2);                 // what the next transposed conv reads, with its BatchNorm
     ConvBN* prevBN = &convs[IB + 1];
     for (int l = D; l >= 1; --l) {
         const int k = D - l;
         UpConv& u = ups[k];
         Shape sin{n, h >> l, w >> l};
         Shape s{n, h >> (l - 1), w >> (l - 1)};
+        const PlaneBuf& up = pl[pUp[l]];
         if (convt_planes) {
             // ConvTranspose2d(k2, s2) on the plane kernels: the input activated once into planes, then ONE 1x1 contraction whose
             // 4 cout output channels are the four taps -- each lands on its own pixel of the 2 x 2 block (PConvArgs::zblocks)
             const int64_t Min = (int64_t)sin.N * sin.H * sin.W;
-            launch_act_split(ctx, View{nullptr, u.cin}, Min, u.cin, bn_xf(*prevBN), 1, pl[pUpIn[l]].p, pl[pUpIn[l]].pstride, prevY16->p,
-                             prevY16->pstride);
+            const PlaneBuf& upin = pl[pUpIn[l]];
+            launch_act_split(ctx, View{nullptr, u.cin}, Min, u.cin, bn_xf(*prevBN), 1, upin.p, upin.pstride, prevY.h, prevY.pstride);
             PConvArgs a;
-            a.x[0] = seg_of(pl[pUpIn[l]]);
+            a.x[0] = upin.seg();
             a.nseg = 1; a.P = 1;
             a.N = sin.N; a.H = sin.H; a.W = sin.W; a.Hin = sin.H; a.Win = sin.W;
             a.R = 1; a.S = 1; a.pad = 0;
@@ -412,64 +388,45 @@ void UNetModel::forward_planes(const float* x_dev, int n, int h, int w, bool tra
             a.zblocks = u.cout / 32;
             a.wB = u.wBf;
             a.bias = params + u.b_off;
-            a.y16 = pl[pUp[l]].p; a.y_pstride = (int)pl[pUp[l]].pstride;
+            a.y16 = up.p; a.y_pstride = (int)up.pstride;
             a.Hout = s.H; a.Wout = s.W; a.osy = 2; a.osx = 2;
             a.algo_flops = 2.0 * Min * 4.0 * u.cin * u.cout;
             launch_pconv(ctx, a);
-            ConvBN& c1 = convs[IB + 2 + 2 * k];
-            ConvBN& c2 = convs[IB + 2 + 2 * k + 1];
-            const PlaneSeg in2[2] = {seg_of(pl[pUp[l]]), seg_of(pl[pSkip[l]])};
-            double_conv(this, c1, c2, in2, 2, s, yt(decY1[l], yD1[l]), pl[pA1d[l]], yt(decY2[l], l == 1 ? yD2top : yD2[l]), train_mode);
-            prevY16 = l == 1 ? &pl[yD2top] : &pl[yD2[l]];
-            prevBN = &c2;
-            continue;
-        }
-        // ConvTranspose2d(k2,s2): the round-1 kernel, float32 tensors (with a plane flow on, ws_need() == 0: no wave-specialised
-        // copy exists for set_filters to find)
-        ConvArgs a = convt_args(u, View{prevY, u.cin}, bn_xf(*prevBN), sin);
-        // bf16 data flow with whole 16-channel chunks: the kernel writes the up-conv output as the bf16 operand of the
-        // decoder's first conv directly; otherwise float32 + one conversion pass (which also zero-fills chunk padding)
-        const bool direct = P == 1 && u.cout % 16 == 0 && conv_mfma_eligible(a) && pl[pUp[l]].pstride % 4 == 0;
-        if (direct) {
-            a.y16 = pl[pUp[l]].p;
-            a.y = MutView{nullptr, (int)pl[pUp[l]].pstride};
         } else {
-            a.y = MutView{buf(upf[l]), u.cout};
+            // ConvTranspose2d(k2,s2): the round-1 kernel, float32 tensors (with a plane flow on, ws_need() == 0: no wave-specialised
+            // copy exists for set_filters to find)
+            ConvArgs a = convt_args(u, View{prevY.f, u.cin}, bn_xf(*prevBN), sin);
+            // bf16 data flow with whole 16-channel chunks: the kernel writes the up-conv output as the bf16 operand of the
+            // decoder's first conv directly; otherwise float32 + one conversion pass (which also zero-fills chunk padding)
+            const bool direct = P == 1 && u.cout % 16 == 0 && conv_mfma_eligible(a) && up.pstride % 4 == 0;
+            if (direct) {
+                a.y16 = up.p;
+                a.y = MutView{nullptr, (int)up.pstride};
+            } else {
+                a.y = MutView{buf(upf[l]), u.cout};
+            }
+            launch_conv(ctx, a);
+            if (!direct)
+                launch_act_split(ctx, View{buf(upf[l]), u.cout}, (int64_t)s.N * s.H * s.W, u.cout, InXform{}, P, up.p, up.pstride);
         }
-        launch_conv(ctx, a);
-        const int64_t M = (int64_t)s.N * s.H * s.W;
-        if (!direct)
-            launch_act_split(ctx, View{buf(upf[l]), u.cout}, M, u.cout, InXform{}, P, pl[pUp[l]].p, pl[pUp[l]].pstride);
         ConvBN& c1 = convs[IB + 2 + 2 * k];
         ConvBN& c2 = convs[IB + 2 + 2 * k + 1];
-        const PlaneSeg in2[2] = {seg_of(pl[pUp[l]]), seg_of(pl[pSkip[l]])};      // cat([up, skip], dim=1) as two K-segments
-        // (decoder l's second output feeds the next transposed conv -- float32 tensor -- except the last: the head)
-        double_conv(this, c1, c2, in2, 2, s, yt(decY1[l], y16_flow ? yD1[l] : -1), pl[pA1d[l]],
-                    yt(decY2[l], y16_flow && l == 1 ? yD2top : -1), train_mode);
-        prevY = buf(decY2[l]);
+        const PlaneSeg in2[2] = {up.seg(), pl[pSkip[l]].seg()};      // cat([up, skip], dim=1) as two K-segments
+        double_conv(this, c1, c2, in2, 2, s, flow(decY1[l]), pl[pA1d[l]], flow(decY2[l]), train_mode);
+        prevY = flow(decY2[l]);                   // (float32 where the round-1 transposed conv reads it; the head reads either)
         prevBN = &c2;
     }
     const int64_t M1 = (int64_t)n * h * w;
-    launch_head_fwd(ctx, yt(decY2[1], y16_flow ? yD2top : -1).ref(), M1, feat, prevBN->scale(), prevBN->shift(),
-                    params + head_w_off, params + head_b_off, out_ch, buf(logits), act_slope);
+    launch_head_fwd(ctx, prevY.ref(), M1, feat, prevBN->scale(), prevBN->shift(), params + head_w_off, params + head_b_off, out_ch,
+                    buf(logits), act_slope);
     if (head_sigmoid) launch_sigmoid_fwd(ctx, buf(logits), M1 * out_ch, buf(probs));
 }
 
 namespace {
 
 // dA: gradient w.r.t. the ACTIVATED output of conv c (float32, left untouched).  Writes dW / db / dgamma / dbeta
-// and, if dx != null, the gradient w.r.t. the conv's input (float32 raw, `cin` channels per pixel).
-// a gradient tensor a conv kernel writes: float32 buffer, or (bf16 data flow) a dense bfloat16 [pixel][C] tensor
-struct GT {
-    float* f = nullptr;
-    PlaneBuf* h = nullptr;
-    GT(float* p) : f(p) {}
-    GT(std::nullptr_t) {}
-    GT(PlaneBuf& b) : h(&b) {}
-    explicit operator bool() const { return f || h; }
-    YRef ref() const { return h ? YRef(h->p, h->pstride) : YRef(f); }
-};
-
+// and, if dx is a tensor, the gradient w.r.t. the conv's input (raw, `cin` channels per pixel: a float32 buffer or, in the bf16
+// data flow, a dense bfloat16 [pixel][C] tensor).
 // `next` (with its raw bfloat16 output next_Y): the layer whose activated output dx is the gradient of -- its BatchNorm-
 // backward sums are then folded into the input-gradient conv's epilogue; returns the number of records left for it in
 // the workspace (0: none, the caller's next call runs bn_bwd_reduce).
@@ -478,7 +435,7 @@ struct GT {
 // encoder): s is the OUTPUT grid, `in` the input of stride times that size, dx must be null (the caller runs the input
 // gradient by parity classes).
 int backward_pconv_bn(UNetModel* m, ConvBN& c, YRef dA, YRef Y, const PlaneSeg* in, int nseg, Shape s,
-                      GT dx, PlaneBuf& dYp, int have_records = 0, ConvBN* next = nullptr, YRef next_Y = YRef((const float*)nullptr),
+                      FlowRef dx, PlaneBuf& dYp, int have_records = 0, ConvBN* next = nullptr, YRef next_Y = YRef((const float*)nullptr),
                       const float* slope_override = nullptr) {
     rfi_ctx* ctx = m->ctx;
     const int64_t M = (int64_t)s.N * s.H * s.W;
@@ -497,24 +454,7 @@ int backward_pconv_bn(UNetModel* m, ConvBN& c, YRef dA, YRef Y, const PlaneSeg* 
     launch_bn_bwd_apply(ctx, dA, Y, M, c.cout, c.scale(), c.shift(), c.mean(), c.invstd(),
                         m->params + c.g_off, c.c1(), c.c2(), defer ? m->dbias_pool + c.dbias_rec_off : ws,
                         c.has_bias ? m->grads + c.b_off : nullptr, slope, dYp.p, dYp.pstride, m->planesP, dy_done, !defer);
-    PWgradArgs wa;
-    wa.xop[0] = in[0];
-    if (nseg > 1) wa.xop[1] = in[1];
-    wa.nseg = nseg;
-    wa.seg_c[0] = nseg > 1 ? c.cin / 2 : c.cin;
-    wa.seg_c[1] = nseg > 1 ? c.cin / 2 : 0;
-    wa.cx_layout = c.cin_p;
-    wa.yop = PlaneSeg{dYp.p, dYp.pstride, dYp.nchunks};
-    wa.Cy = c.cout;
-    wa.P = m->planesP;
-    wa.N = s.N; wa.H = s.H; wa.W = s.W; wa.Hx = s.H * c.stride; wa.Wx = s.W * c.stride;
-    wa.R = c.R; wa.S = c.stride; wa.pad = c.R == 3 ? 1 : 0;
-    wa.dw = m->grads + c.w_off;
-    wa.tap_stride = (int64_t)c.cin_p * c.cout;
-    wa.sy = c.cin_p; wa.sx = 1;
-    wa.algo_flops = 2.0 * s.N * s.H * s.W * (double)(c.R * c.R) * c.cin * c.cout;
-    wa.slab = m->buf(m->ws_slab);
-    wa.slab_floats = m->bufs[m->ws_slab].n;
+    const PWgradArgs wa = m->pwgrad_args(c, in, nseg, dYp.seg(), s);
     {
         SideScope side(m, dy_done);
         launch_pwgrad(ctx, wa);
@@ -522,12 +462,12 @@ int backward_pconv_bn(UNetModel* m, ConvBN& c, YRef dA, YRef Y, const PlaneSeg* 
     }
     if (dx) {
         PConvArgs a;
-        a.x[0] = PlaneSeg{dYp.p, dYp.pstride, dYp.nchunks};
+        a.x[0] = dYp.seg();
         a.nseg = 1; a.P = m->planesP;
         a.N = s.N; a.H = s.H; a.W = s.W; a.Hin = s.H; a.Win = s.W;
         a.Cout = c.cin;                           // dx exists only for layers whose cin == cin_p
         a.wB = c.wBd;
-        if (dx.h) { a.y16 = dx.h->p; a.y_pstride = (int)dx.h->pstride; }
+        if (dx.h) { a.y16 = dx.h; a.y_pstride = (int)dx.pstride; }
         else { a.y = dx.f; a.y_pstride = c.cin; }
         a.Hout = s.H; a.Wout = s.W;
         a.algo_flops = 2.0 * s.N * s.H * s.W * 9.0 * c.cin * c.cout;
@@ -564,11 +504,10 @@ void UNetModel::backward_resnet_planes(int n, int h, int w) {
     {
         const ResBlock& lb = blocks.back();
         const PlaneBuf& A = pl[rpb.back().A];
-        launch_pool_bwd_merge(ctx, YRef(A.p, A.pstride), n, h >> (D - 1), w >> (D - 1), lb.cout, rs_ones, rs_zeros,
-                              skip_grad(D, lb.cout), YRef(pl[g16pool[D]].p, pl[g16pool[D]].pstride), nullptr, 0.0f, pl[rp_dX].p);
+        launch_pool_bwd_merge(ctx, A.ref(), n, h >> (D - 1), w >> (D - 1), lb.cout, rs_ones, rs_zeros, skip_grad(D, lb.cout),
+                              flow(dpool[D]).ref(), nullptr, 0.0f, pl[rp_dX].p);
     }
-    // (the scratch tensors rp_dA1 / rp_dX / rp_dz serve every level: dense [M][C] views of them)
-    auto view = [&](int idx, int C) { PlaneBuf v = pl[idx]; v.pstride = C; v.nchunks = C / 16; return v; };
+    // (the scratch tensors rp_dA1 / rp_dX / rp_dz serve every level: as dense [M][C] tensors)
     const bf16_t* g0 = pl[rp_dX].p;               // the terms of g (dense bfloat16 [M][C]) ...
     const bf16_t* g1 = nullptr;
     YRef g2((const float*)nullptr);               // ... and the decoder's skip gradient (a view), at stage boundaries
@@ -583,24 +522,21 @@ void UNetModel::backward_resnet_planes(int n, int h, int w) {
         PlaneBuf& dz = pl[rp_dz[bi & 1]];
         launch_relu_mask_sum16(ctx, g0, b.cout, g1, b.cout, g2, pl[r.A].p, pl[r.A].pstride, M, b.cout, dz.p, b.cout);
         const YRef dzr(dz.p, (int64_t)b.cout);
-        const PlaneSeg a1 = seg_of(pl[r.A1]);
-        PlaneBuf dA1v = view(rp_dA1, b.cout), dXv = view(rp_dX, b.cin);
-        const int rec1 = backward_pconv_bn(this, c2, dzr, YRef(pl[r.Y2].p, pl[r.Y2].pstride), &a1, 1, s, GT(dA1v), pl[r.dY2], 0, &c1,
-                                           YRef(pl[r.Y1].p, pl[r.Y1].pstride), &one);
-        const PlaneSeg in = seg_of(a_in);
-        const YRef dA1(pl[rp_dA1].p, (int64_t)b.cout);
+        const PlaneSeg a1 = pl[r.A1].seg();
+        const FlowRef dA1(pl[rp_dA1].p, b.cout), dX(pl[rp_dX].p, b.cin);
+        const int rec1 = backward_pconv_bn(this, c2, dzr, pl[r.Y2].ref(), &a1, 1, s, dA1, pl[r.dY2], 0, &c1, pl[r.Y1].ref(), &one);
+        const PlaneSeg in = a_in.seg();
         if (b.stride == 1) {
-            backward_pconv_bn(this, c1, dA1, YRef(pl[r.Y1].p, pl[r.Y1].pstride), &in, 1, s, GT(dXv), pl[r.dY1], rec1);
+            backward_pconv_bn(this, c1, dA1.ref(), pl[r.Y1].ref(), &in, 1, s, dX, pl[r.dY1], rec1);
             g0 = pl[rp_dX].p; g1 = dz.p; g2 = YRef((const float*)nullptr);
         } else {
             ConvBN& cd = convs[b.cd];
-            backward_pconv_bn(this, c1, dA1, YRef(pl[r.Y1].p, pl[r.Y1].pstride), &in, 1, s, GT(nullptr), pl[r.dY1], rec1);
-            backward_pconv_bn(this, cd, dzr, YRef(pl[r.Yd].p, pl[r.Yd].pstride), &in, 1, s, GT(nullptr), pl[r.dYd], 0, nullptr,
-                              YRef((const float*)nullptr), &one);
+            backward_pconv_bn(this, c1, dA1.ref(), pl[r.Y1].ref(), &in, 1, s, FlowRef(), pl[r.dY1], rec1);
+            backward_pconv_bn(this, cd, dzr, pl[r.Yd].ref(), &in, 1, s, FlowRef(), pl[r.dYd], 0, nullptr, YRef((const float*)nullptr), &one);
             for (int c = 0; c < 4; ++c) {
                 PConvArgs a;
-                a.x[0] = seg_of(pl[r.dY1]);
-                if (c == 0) a.x[1] = seg_of(pl[r.dYd]);
+                a.x[0] = pl[r.dY1].seg();
+                if (c == 0) a.x[1] = pl[r.dYd].seg();
                 a.nseg = c == 0 ? 2 : 1; a.P = 1;
                 a.N = s.N; a.H = s.H; a.W = s.W; a.Hin = s.H; a.Win = s.W;
                 a.R = 2; a.S = 1; a.pad = 0;
@@ -624,8 +560,8 @@ void UNetModel::backward_resnet_planes(int n, int h, int w) {
         const int64_t M = (int64_t)n * h * w;
         PlaneBuf& g = pl[rp_dz[1]];               // (block 0 used rp_dz[0])
         launch_relu_mask_sum16(ctx, g0, c.cout, g1, c.cout, YRef((const float*)nullptr), nullptr, 0, M, c.cout, g.p, c.cout);
-        const PlaneSeg in = seg_of(pl[pXin]);
-        backward_pconv_bn(this, c, YRef(g.p, (int64_t)c.cout), YRef(pl[rpStemY].p, pl[rpStemY].pstride), &in, 1, s, GT(nullptr), pl[rpdY0]);
+        const PlaneSeg in = pl[pXin].seg();
+        backward_pconv_bn(this, c, YRef(g.p, (int64_t)c.cout), pl[rpStemY].ref(), &in, 1, s, FlowRef(), pl[rpdY0]);
         bucket_ready(0, convs[blocks[0].c1].w_off);
     }
 }
@@ -640,10 +576,7 @@ void UNetModel::debug_tensor_planes(const std::string& name, const std::string& 
                                     size_t& n) {
     const int D = depth, P = planesP;
     const bool pad = name.find(":pad") != std::string::npos;
-    const bool leveled = name.find('.') != std::string::npos;
-    auto lvl = [&]() { RFI_REQUIRE(leveled && idx >= 1 && idx <= D, "debug_tensor: level out of range"); return idx; };
     auto pix = [&](int l) { return (size_t)pN * (pH >> (l - 1)) * (pW >> (l - 1)); };       // pixels of level l (D + 1: the bottleneck)
-    auto chan = [&](int l) { return feat << (l - 1); };
     // a float32 tensor of the model
     auto f32 = [&](int bi, size_t M, int C) {
         RFI_REQUIRE(!pad, "debug_tensor: this tensor is stored as float32 in this mode: it has no padding lanes");
@@ -665,51 +598,31 @@ void UNetModel::debug_tensor_planes(const std::string& name, const std::string& 
         launch_planes_to_f32(ctx, in, b.pstride, (int64_t)M, pad ? Cp : C, P_, tmp, pad ? Cp : C);
         src = tmp;
     };
-    // a tensor that is bfloat16 (pl[hi]) when `half`, else float32 (bufs[fi])
-    auto either = [&](bool half, int hi, int fi, size_t M, int C) { if (half) planes(hi, M, C, 1); else f32(fi, M, C); };
-    const size_t Mb = pix(D + 1);
-    const int Cb = feat << D;
-    if (base == "xin") planes(pXin, pix(1), in_ch, P);
-    else if (base == "a1e") { const int l = lvl(); planes(pA1e[l], pix(l), chan(l), P); }
-    else if (base == "skip") { const int l = lvl(); planes(pSkip[l], pix(l), chan(l), P); }
-    else if (base == "pooled") { const int l = lvl(); planes(pPool[l], pix(l) / 4, chan(l), P); }
-    else if (base == "up") { const int l = lvl(); planes(pUp[l], pix(l), chan(l), P); }
-    else if (base == "a1d") { const int l = lvl(); planes(pA1d[l], pix(l), chan(l), P); }
-    else if (base == "a1b") planes(pA1b, Mb, Cb, P);
-    else if (base == "upin") {
-        RFI_REQUIRE(convt_planes, "debug_tensor: upin exists only with the transposed convs on the plane kernels");
-        const int l = lvl();
-        planes(pUpIn[l], pix(l) / 4, 2 * chan(l), 1);
+    // the flow tensors: bfloat16 or float32, as the mode stores them
+    size_t M = 0;
+    int C = 0;
+    if (const FlowTensor* t = flow_named(base, idx, M, C)) return t->half ? planes(t->b16, M, C, 1) : f32(t->f32, M, C);
+    // the plane tensors (P pieces) and the float32 tensors that are no flow tensors: one per level l (the pixels of level
+    // l + down, feat << (l - 1 + wide) channels), or a single one (xin: the input's shape; the others: the bottleneck's)
+    struct Row { const char* name; const std::vector<int>* levels; int one; int P; int down, wide; };
+    const Row rows[] = {{"xin", nullptr, pXin, P, 0, 0},
+                        {"a1e", &pA1e, -1, P, 0, 0}, {"skip", &pSkip, -1, P, 0, 0}, {"pooled", &pPool, -1, P, 1, 0}, {"up", &pUp, -1, P, 0, 0},
+                        {"a1d", &pA1d, -1, P, 0, 0}, {"a1b", nullptr, pA1b, P, 0, 0}, {"upin", &pUpIn, -1, 1, 1, 1},
+                        {"dYa", &pdYa, -1, P, 0, 0}, {"dYb", &pdYb, -1, P, 0, 0}, {"dYaE", &pdYaE, -1, P, 0, 0}, {"dYbE", &pdYbE, -1, P, 0, 0},
+                        {"dYbottA", nullptr, pdYbottA, P, 0, 0}, {"dYbottB", nullptr, pdYbottB, P, 0, 0},
+                        // float32 (P = 0): tensors of the float32 path, where prepared; the float32 up-conv output (where act_split converts it)
+                        {"concat", &concat, -1, 0, 0, 1}, {"pool", &pool, -1, 0, 1, 0}, {"upf", &upf, -1, 0, 0, 0}};
+    for (const Row& r : rows) {
+        if (base != r.name) continue;
+        RFI_REQUIRE(base != "upin" || convt_planes, "debug_tensor: upin exists only with the transposed convs on the plane kernels");
+        RFI_REQUIRE(!r.levels || (idx >= 1 && idx <= D && (int)r.levels->size() > D), "debug_tensor: level out of range");
+        const int l = r.levels ? idx : D + 1;
+        const int i = r.levels ? (*r.levels)[l] : r.one;
+        const size_t Mr = base == "xin" ? pix(1) : pix(l + r.down);
+        const int Cr = base == "xin" ? in_ch : feat << (l - 1 + r.wide);
+        return r.P ? planes(i, Mr, Cr, r.P) : f32(i, Mr, Cr);
     }
-    else if (base == "dYa") { const int l = lvl(); planes(pdYa[l], pix(l), chan(l), P); }
-    else if (base == "dYb") { const int l = lvl(); planes(pdYb[l], pix(l), chan(l), P); }
-    else if (base == "dYaE") { const int l = lvl(); planes(pdYaE[l], pix(l), chan(l), P); }
-    else if (base == "dYbE") { const int l = lvl(); planes(pdYbE[l], pix(l), chan(l), P); }
-    else if (base == "dYbottA") planes(pdYbottA, Mb, Cb, P);
-    else if (base == "dYbottB") planes(pdYbottB, Mb, Cb, P);
-    else if (base == "encY1") { const int l = lvl(); either(y16_flow, y16_flow ? yE1[l] : -1, encY1[l], pix(l), chan(l)); }
-    else if (base == "encY2") { const int l = lvl(); either(y16_flow, y16_flow ? yE2[l] : -1, encY2[l], pix(l), chan(l)); }
-    else if (base == "decY1") { const int l = lvl(); either(y16_flow, y16_flow ? yD1[l] : -1, decY1[l], pix(l), chan(l)); }
-    else if (base == "decY2") {
-        const int l = lvl();
-        const bool half = l == 1 ? y16_flow : convt_planes;
-        either(half, half ? (l == 1 ? yD2top : yD2[l]) : -1, decY2[l], pix(l), chan(l));
-    }
-    else if (base == "bottY1") either(y16_flow, yB1, bottY1, Mb, Cb);
-    else if (base == "bottY2") either(convt_planes, yB2, bottY2, Mb, Cb);
-    else if (base == "gA") {                      // (l == 1 without the bf16 gradient flow: the head wrote it as float32)
-        const int l = lvl();
-        either(g16_flow, g16_flow ? g16A[l] : -1, gA[l], pix(l), chan(l));
-    }
-    else if (base == "gB") { const int l = lvl(); either(g16_flow, g16_flow ? g16B[l] : -1, gB[l], pix(l), chan(l)); }
-    else if (base == "dpool") { const int l = lvl(); either(g16_flow, g16_flow ? g16pool[l] : -1, dpool[l], pix(l) / 4, chan(l)); }
-    else if (base == "gBottA") either(convt_planes, g16BottA, gBottA, Mb, Cb);
-    else if (base == "gBottB") either(g16_flow, g16BottB, gBottB, Mb, Cb);
-    else if (base == "dconcat") { const int l = lvl(); either(convt_planes, convt_planes ? g16cat[l] : -1, dconcat[l], pix(l), 2 * chan(l)); }
-    else if (base == "concat") { const int l = lvl(); f32(concat[l], pix(l), 2 * chan(l)); }      // (tensors of the float32 path, where prepared)
-    else if (base == "pool") { const int l = lvl(); f32(pool[l], pix(l) / 4, chan(l)); }
-    else if (base == "upf") { const int l = lvl(); f32(upf[l], pix(l), chan(l)); }      // the float32 up-conv output (where act_split converts it)
-    else throw Error("debug_tensor: unknown tensor " + name);
+    throw Error("debug_tensor: unknown tensor " + name);
 }
 
 void UNetModel::backward_planes(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w) {
@@ -718,10 +631,6 @@ void UNetModel::backward_planes(const float* x_dev, const uint8_t* labels_dev, i
     // every layer owns its dY plane tensor and the other side-stream inputs (forward planes, dconcat, raw conv outputs)
     // are not rewritten before side_join(): the main stream never has to wait for a weight gradient inside the pass
     side_bound = 0;
-    // a raw conv output of the forward pass: bfloat16 tensor pl[hi] in the bf16 flow, else float32 bufs[fi]
-    auto yr = [&](int fi, int hi) { return (y16_flow && hi >= 0) ? YRef(pl[hi].p, pl[hi].pstride) : YRef(buf(fi)); };
-    // a gradient tensor an input-gradient conv writes: bfloat16 tensor pl[hi] in the bf16 flow, else float32 bufs[fi]
-    auto gt = [&](int fi, int hi) { return hi >= 0 ? GT(pl[hi]) : GT(buf(fi)); };
     const int64_t M1 = (int64_t)n * h * w;
     dbias_deferred = dbias_pool && !ctx->exchange_active();    // (bias gradients must be final before their bucket leaves)
     if (loss_kind == 1)
@@ -733,10 +642,11 @@ void UNetModel::backward_planes(const float* x_dev, const uint8_t* labels_dev, i
     {
         ConvBN& last = convs[IB + 2 + 2 * (D - 1) + 1];
         const bool hdefer = dbias_deferred && head_fin_deferred;
-        head_records = launch_head_bwd(ctx, yr(decY2[1], y16_flow ? yD2top : -1), M1, feat, last.scale(), last.shift(), params + head_w_off, out_ch,
+        // (the head always writes the float32 gA.1, and the bfloat16 one next to it where the decoder phase reads that)
+        head_records = launch_head_bwd(ctx, flow(decY2[1]).ref(), M1, feat, last.scale(), last.shift(), params + head_w_off, out_ch,
                                        buf(dlogits), buf(gA[1]), hdefer ? dbias_pool + head_rec_off : buf(ws_red) + bn_bwd_ws_floats(M1, feat),
                                        grads + head_w_off, grads + head_b_off, act_slope, last.mean(), last.invstd(), buf(ws_red),
-                                       g16_flow && out_ch == 1 ? pl[g16A[1]].p : nullptr, nullptr, !hdefer);
+                                       flow(gAdec[1]).h, nullptr, !hdefer);
     }
     int up_records = 0;                           // BatchNorm-backward records a transposed conv's input-gradient kernel left for the layer below
     for (int l = 1; l <= D; ++l) {                // decoders, shallow to deep
@@ -746,39 +656,26 @@ void UNetModel::backward_planes(const float* x_dev, const uint8_t* labels_dev, i
         ConvBN& c1 = convs[IB + 2 + 2 * k];
         ConvBN& c2 = convs[IB + 2 + 2 * k + 1];
         UpConv& u = ups[k];
-        const PlaneSeg a1 = seg_of(pl[pA1d[l]]);
+        const PlaneSeg a1 = pl[pA1d[l]].seg();
         // (with the transposed convs on the plane kernels the gradient arriving from decoder l - 1's is a bfloat16 tensor, the
         // BatchNorm-backward sums of c2 came out of that kernel's epilogue, and Y2 is a bfloat16 tensor)
-        const bool up16 = convt_planes && l > 1;
-        const int rec1 = backward_pconv_bn(this, c2, gt(gA[l], up16 || (g16_flow && out_ch == 1 && l == 1) ? g16A[l] : -1).ref(),
-                                           yr(decY2[l], y16_flow && l == 1 ? yD2top : (up16 ? yD2[l] : -1)), &a1, 1, s,
-                                           gt(gB[l], g16_flow ? g16B[l] : -1), pl[pdYa[l]], l == 1 ? head_records : up_records, &c1,
-                                           yr(decY1[l], y16_flow ? yD1[l] : -1));
-        const PlaneSeg in2[2] = {seg_of(pl[pUp[l]]), seg_of(pl[pSkip[l]])};
-        backward_pconv_bn(this, c1, gt(gB[l], g16_flow ? g16B[l] : -1).ref(), yr(decY1[l], y16_flow ? yD1[l] : -1), in2, 2, s,
-                          convt_planes ? GT(pl[g16cat[l]]) : GT(buf(dconcat[l])), pl[pdYb[l]], rec1);
+        const int rec1 = backward_pconv_bn(this, c2, flow(gAdec[l]).ref(), flow(decY2[l]).ref(), &a1, 1, s, flow(gB[l]), pl[pdYa[l]],
+                                           l == 1 ? head_records : up_records, &c1, flow(decY1[l]).ref());
+        const PlaneSeg in2[2] = {pl[pUp[l]].seg(), pl[pSkip[l]].seg()};
+        const FlowRef cat = flow(dconcat[l]);     // the gradient of [up | skip]
+        backward_pconv_bn(this, c1, flow(gB[l]).ref(), flow(decY1[l]).ref(), in2, 2, s, cat, pl[pdYb[l]], rec1);
         ConvBN& prevBN = (l == D) ? convs[IB + 1] : convs[IB + 2 + 2 * (k - 1) + 1];
+        // what the transposed conv read (with prevBN) and the gradient it sends there
+        const FlowRef prevY = flow(l == D ? bottY2 : decY2[l + 1]), dprev = flow(l == D ? gBottA : gAdec[l + 1]);
+        const bool udefer = dbias_deferred && u.cout % 4 == 0;
         if (convt_planes) {
             // ConvTranspose on the plane kernels: dUp = the first C channels of the bfloat16 [up | skip] gradient
-            const PlaneBuf& cat = pl[g16cat[l]];
-            const PlaneSeg dUp{cat.p, cat.pstride, plane_chunks(u.cout)};
-            const bool udefer = dbias_deferred && u.cout % 4 == 0;
-            launch_channel_sum(ctx, YRef(cat.p, cat.pstride), (int64_t)s.N * s.H * s.W, u.cout, udefer ? dbias_pool + u.dbias_rec_off : buf(ws_red),
+            const PlaneSeg dUp{cat.h, cat.pstride, plane_chunks(u.cout)};
+            launch_channel_sum(ctx, cat.ref(), (int64_t)s.N * s.H * s.W, u.cout, udefer ? dbias_pool + u.dbias_rec_off : buf(ws_red),
                                grads + u.b_off, !udefer);
-            PWgradArgs wa;                        // dW[tap][cout][cin] = sum_pixels act(prev)[i, j, cin] * dUp[2 i + a, 2 j + b, cout]
-            wa.xop[0] = dUp; wa.nseg = 1; wa.seg_c[0] = u.cout;
-            wa.yop = seg_of(pl[pUpIn[l]]); wa.Cy = u.cin; wa.P = 1;
-            wa.N = sin.N; wa.H = sin.H; wa.W = sin.W; wa.Hx = s.H; wa.Wx = s.W;
-            wa.R = 2; wa.S = 2; wa.pad = 0;
-            wa.dw = grads + u.w_off;
-            wa.tap_stride = (int64_t)u.cin * u.cout;
-            wa.sy = 1; wa.sx = u.cin;
-            wa.algo_flops = 2.0 * sin.N * sin.H * sin.W * 4.0 * u.cin * u.cout;
-            wa.slab = buf(ws_slab);
-            wa.slab_floats = bufs[ws_slab].n;
             {
                 SideScope side(this);
-                launch_pwgrad(ctx, wa);
+                launch_pwgrad(ctx, convt_pwgrad_args(u, dUp, pl[pUpIn[l]].seg(), sin));
                 side.end();
             }
             PConvArgs a;                          // the input gradient: a 2x2 stride-2 contraction of dUp, bfloat16 out, with the
@@ -787,43 +684,33 @@ void UNetModel::backward_planes(const float* x_dev, const uint8_t* labels_dev, i
             a.R = 2; a.S = 2; a.pad = 0;
             a.Cout = u.cin;
             a.wB = u.wBd;
-            PlaneBuf& dprev = (l == D) ? pl[g16BottA] : pl[g16A[l + 1]];
-            const PlaneBuf& prevY16 = (l == D) ? pl[yB2] : pl[yD2[l + 1]];
-            a.y16 = dprev.p; a.y_pstride = (int)dprev.pstride;
+            a.y16 = dprev.h; a.y_pstride = (int)dprev.pstride;
             a.Hout = sin.H; a.Wout = sin.W;
             a.algo_flops = 2.0 * sin.N * sin.H * sin.W * 4.0 * u.cin * u.cout;
-            float* ws = buf(ws_red);
-            a.stats = reinterpret_cast<double*>(ws);
+            a.stats = reinterpret_cast<double*>(buf(ws_red));
             a.stats_max_records = (int)(bn_stats_ws_floats(u.cin) / ((size_t)u.cin * 4));
-            a.bwd_y16 = prevY16.p;
-            a.bwd_yps = prevY16.pstride;
+            a.bwd_y16 = prevY.h;
+            a.bwd_yps = prevY.pstride;
             a.bwd_scale = prevBN.scale(); a.bwd_shift = prevBN.shift();
             a.bwd_mean = prevBN.mean(); a.bwd_invstd = prevBN.invstd();
             a.bwd_slope = act_slope;
             launch_pconv(ctx, a);
             up_records = a.stats_records;
-            bucket_ready(u.w_off, l == 1 ? n_flat : ups[k + 1].w_off);
-            continue;
-        }
-        // ConvTranspose: dUp = dconcat[..., 0:C]; the round-1 kernels on float32 tensors
-        const float* prevY = (l == D) ? buf(bottY2) : buf(decY2[l + 1]);
-        View dUp{buf(dconcat[l]), 2 * u.cout};
-        {
-            const bool udefer = dbias_deferred && u.cout % 4 == 0;
+        } else {
+            // ConvTranspose: dUp = dconcat[..., 0:C]; the round-1 kernels on float32 tensors
+            View dUp{cat.f, 2 * u.cout};
             launch_channel_sum(ctx, dUp, (int64_t)s.N * s.H * s.W, u.cout, udefer ? dbias_pool + u.dbias_rec_off : buf(ws_red), grads + u.b_off,
                                !udefer);
+            convt_backward(u, dUp, View{prevY.f, u.cin}, bn_xf(prevBN), sin, dprev.f);
         }
-        convt_backward(u, dUp, View{prevY, u.cin}, bn_xf(prevBN), sin, (l == D) ? buf(gBottA) : buf(gA[l + 1]));
         bucket_ready(u.w_off, l == 1 ? n_flat : ups[k + 1].w_off);      // decoder level l (+ head) is complete
     }
     {                                             // bottleneck
         Shape s{n, h >> D, w >> D};
-        const PlaneSeg a1 = seg_of(pl[pA1b]), p4 = seg_of(pl[pPool[D]]);
-        const int rec1 = backward_pconv_bn(this, convs[IB + 1], gt(gBottA, convt_planes ? g16BottA : -1).ref(), yr(bottY2, convt_planes ? yB2 : -1), &a1, 1,
-                                           s, gt(gBottB, g16_flow ? g16BottB : -1), pl[pdYbottA], convt_planes ? up_records : 0, &convs[IB],
-                                           yr(bottY1, y16_flow ? yB1 : -1));
-        backward_pconv_bn(this, convs[IB], gt(gBottB, g16_flow ? g16BottB : -1).ref(), yr(bottY1, y16_flow ? yB1 : -1), &p4, 1, s,
-                          gt(dpool[D], g16_flow ? g16pool[D] : -1), pl[pdYbottB], rec1);
+        const PlaneSeg a1 = pl[pA1b].seg(), p4 = pl[pPool[D]].seg();
+        const int rec1 = backward_pconv_bn(this, convs[IB + 1], flow(gBottA).ref(), flow(bottY2).ref(), &a1, 1, s, flow(gBottB), pl[pdYbottA],
+                                           up_records, &convs[IB], flow(bottY1).ref());
+        backward_pconv_bn(this, convs[IB], flow(gBottB).ref(), flow(bottY1).ref(), &p4, 1, s, flow(dpool[D]), pl[pdYbottB], rec1);
         bucket_ready(convs[IB].w_off, ups[0].w_off);
     }
     if (resnet_encoder) backward_resnet_planes(n, h, w);
@@ -831,21 +718,18 @@ void UNetModel::backward_planes(const float* x_dev, const uint8_t* labels_dev, i
         Shape s{n, h >> (l - 1), w >> (l - 1)};
         ConvBN& c1 = convs[2 * (l - 1)];
         ConvBN& c2 = convs[2 * (l - 1) + 1];
-        const YRef dskip = skip_grad(l, c2.cout);
-        const int have = launch_pool_bwd_merge_sums(ctx, yr(encY2[l], y16_flow ? yE2[l] : -1), s.N, s.H, s.W, c2.cout, c2.scale(), c2.shift(), c2.mean(),
-                                                    c2.invstd(), dskip, gt(dpool[l], g16_flow ? g16pool[l] : -1).ref(),
-                                                    buf(gA[l]), act_slope, buf(ws_red), g16_flow ? pl[g16A[l]].p : nullptr);
+        const YRef dskip = skip_grad(l, c2.cout), Y2 = flow(encY2[l]).ref(), Y1 = flow(encY1[l]).ref();
+        // (the max-pool backward always writes the float32 gA.l, and the bfloat16 one next to it where the mode reads that)
+        const FlowRef dA = flow(gA[l]);
+        const int have = launch_pool_bwd_merge_sums(ctx, Y2, s.N, s.H, s.W, c2.cout, c2.scale(), c2.shift(), c2.mean(), c2.invstd(), dskip,
+                                                    flow(dpool[l]).ref(), buf(gA[l]), act_slope, buf(ws_red), dA.h);
         if (!have)
-            launch_pool_bwd_merge(ctx, yr(encY2[l], y16_flow ? yE2[l] : -1), s.N, s.H, s.W, c2.cout, c2.scale(), c2.shift(),
-                                  dskip, gt(dpool[l], g16_flow ? g16pool[l] : -1).ref(), buf(gA[l]), act_slope,
-                                  g16_flow ? pl[g16A[l]].p : nullptr);
-        const PlaneSeg a1 = seg_of(pl[pA1e[l]]);
-        const int rec1 = backward_pconv_bn(this, c2, gt(gA[l], g16_flow ? g16A[l] : -1).ref(), yr(encY2[l], y16_flow ? yE2[l] : -1), &a1, 1, s, gt(gB[l], g16_flow ? g16B[l] : -1),
-                                           pl[pdYaE[l]], have, &c1, yr(encY1[l], y16_flow ? yE1[l] : -1));
-        const PlaneSeg in = seg_of(l == 1 ? pl[pXin] : pl[pPool[l - 1]]);
-        backward_pconv_bn(this, c1, gt(gB[l], g16_flow ? g16B[l] : -1).ref(), yr(encY1[l], y16_flow ? yE1[l] : -1), &in, 1, s,
-                          (l == 1) ? GT(nullptr) : gt(dpool[l - 1], g16_flow ? g16pool[l - 1] : -1),
-                          pl[pdYbE[l]], rec1);
+            launch_pool_bwd_merge(ctx, Y2, s.N, s.H, s.W, c2.cout, c2.scale(), c2.shift(), dskip, flow(dpool[l]).ref(), buf(gA[l]), act_slope,
+                                  dA.h);
+        const PlaneSeg a1 = pl[pA1e[l]].seg();
+        const int rec1 = backward_pconv_bn(this, c2, dA.ref(), Y2, &a1, 1, s, flow(gB[l]), pl[pdYaE[l]], have, &c1, Y1);
+        const PlaneSeg in = (l == 1 ? pl[pXin] : pl[pPool[l - 1]]).seg();
+        backward_pconv_bn(this, c1, flow(gB[l]).ref(), Y1, &in, 1, s, l == 1 ? FlowRef() : flow(dpool[l - 1]), pl[pdYbE[l]], rec1);
         bucket_ready(c1.w_off, convs[2 * l].w_off);
     }
     if (dbias_deferred)

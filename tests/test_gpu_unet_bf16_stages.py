@@ -5,13 +5,15 @@ test_bf16_stages[case]            one forward pass (padding lanes read), one for
                                   UNet.debug_tensor, the whole stage table checked; zero undecided masks / routes
 test_bf16_stages_after_reshape    one model at 1x48x80, 1x24x40, 1x48x80: the second and third runs are stage-checked
                                   (PlaneBuf::ensure's zero area and the padding lanes after a shape change)
-test_debug_tensor_names           what the debug path refuses: unknown names, levels out of range, :pad of a float32 tensor
+test_debug_tensor_names           what the debug path refuses: unknown names, levels out of range, :pad of a float32 tensor, and on
+                                  the ResNet-encoder U-Net every tensor the bfloat16 mode stores as bfloat16
 """
 import numpy as np
 import pytest
+import torch
 
 import unet_bf16_stages as S
-from rfi_toolbox_amd.models import UNet
+from rfi_toolbox_amd.models import UNet, UNetResNet18
 
 pytestmark = pytest.mark.gpu
 
@@ -85,3 +87,16 @@ def test_debug_tensor_names():
     m3.forward_backward(x, y)
     assert np.array_equal(m3.debug_tensor("xin").reshape(16, 24, 3), x.numpy()[0])       # (three pieces carry a float32 value exactly)
     assert not m3.debug_tensor("skip.1:pad").any() and m3.debug_tensor("skip.1").size == 16 * 24 * 20
+    # the ResNet-encoder U-Net exposes its decoder's float32 tensors only: what the bfloat16 mode stores as bfloat16 is refused
+    # (width 32: all three gates), and so are the tensors its own encoder replaces; dconcat is converted on a host read
+    g = torch.Generator().manual_seed(5)
+    xr = torch.randn(1, 32, 32, 3, generator=g)
+    yr = (torch.rand(1, 32, 32, generator=g) > 0.7).to(torch.uint8)
+    mr = UNetResNet18(3, 1, 32).train().set_compute_dtype("bfloat16")
+    mr.forward_backward(xr, yr)
+    for bad in ("decY1.1", "decY2.1", "decY2.2", "bottY1", "bottY2", "gB.1", "gBottA", "gBottB", "encY1.1", "pool.1"):
+        with pytest.raises(RuntimeError):
+            mr.debug_tensor(bad)
+    dcat = mr.debug_tensor("dconcat.1")
+    assert dcat.size == 32 * 32 * 64 and S.is_bf16(dcat).all() and dcat.any()
+    assert mr.debug_tensor("concat.1").size == 32 * 32 * 64
