@@ -496,8 +496,8 @@ const uint8_t* stage_labels(rfi_model* m, const uint8_t* y, int y_mem, int n, in
     if (y_mem == RFI_DEVICE) return y;
     uint8_t* st = reinterpret_cast<uint8_t*>(m->buf(m->lab_stage));
     const size_t bytes = (size_t)n * h * w * m->out_scale * m->out_scale;
-    // (the ResNet-50-FPN backbone prepares no label staging: its loss lives outside the model)
-    RFI_REQUIRE(bytes <= m->bufs[m->lab_stage].n * sizeof(float), "labels: this model takes no label map (its loss lives outside the model)");
+    // (the ResNet-50-FPN backbone prepares no label staging)
+    RFI_REQUIRE(m->dense_head, "labels: this model takes no label map (its loss lives outside the model)");
     RFI_CHECK_HIP(hipMemcpyAsync(st, y, bytes, hipMemcpyHostToDevice, m->ctx->stream));
     return st;
 }

@@ -104,6 +104,17 @@ void UNetModel::build() {
     }
     add_head("final_conv", feat);
     alloc_state();
+    make_slots();
+}
+
+void UNetModel::make_slots() {
+    const int D = depth;
+    auto mk = [&](std::vector<int>& v) { v.assign(D + 1, -1); for (int l = 1; l <= D; ++l) v[l] = new_buf(); };
+    auto mkf = [&](std::vector<FlowTensor>& v) { v.assign(D + 1, FlowTensor()); for (int l = 1; l <= D; ++l) v[l].f32 = new_buf(); };
+    mkf(encY1); mkf(encY2); mk(concat); mk(pool); mkf(decY1); mkf(decY2);
+    mkf(gA); mkf(gB); mkf(dconcat); mkf(dpool); mk(gAe); mk(gBe);
+    make_bufs({&bottY1.f32, &bottY2.f32, &gBottA.f32, &gBottB.f32});
+    make_plane_slots();
 }
 
 void UNetModel::set_planes(int P) {
@@ -116,7 +127,7 @@ void UNetModel::set_planes(int P) {
     wb.release(ctx);
     planesP = P;
     stale |= WEIGHT_DERIVED;                      // (another data flow reads other copies: every one is rebuilt)
-    pN = 0;                                       // (prepare() again: the two flows of the ResNet-encoder model own different tensors)
+    invalidate_shape();                           // (the flows own different tensors, and prepare_planes's table depends on the flow)
 }
 
 // ------------------------------------------------------------------------------------ prepare
@@ -139,7 +150,22 @@ void rfi_model::prepare(int n, int h, int w) {
         ctx->bucket_ev_used = 0;
         pend_lo = pend_hi = 0;
     }
+    if (n == pN && h == pH && w == pW) return;
+    ctx->activate();
     prepare_shape(n, h, w);
+    // what the entry points stage through, for M input pixels and Mout output pixels
+    const size_t M = (size_t)n * h * w, Mout = M * out_scale * out_scale;
+    const int cp = convs[0].cin_p;
+    for (int i : {x_stage, x_stage2}) bufs[i].ensure(ctx, M * in_ch);
+    bufs[x_pad].ensure(ctx, dense_head && cp != in_ch ? M * cp : 16);     // (network_input pads into it)
+    for (int i : {logits, dlogits, out_stage}) bufs[i].ensure(ctx, dense_head ? Mout * out_ch : 16);
+    bufs[lab_stage].ensure(ctx, dense_head ? (Mout + 3) / 4 + 4 : 16);
+    // the workspaces: the needs every model has (gradient norm, loss), on top of what prepare_shape declared
+    need_red(sumsq_ws_doubles(n_flat) * 2);
+    if (dense_head) need_red(loss_ws_doubles(Mout) * 2);
+    bufs[ws_red].ensure(ctx, red_need + 16);
+    bufs[ws_slab].ensure(ctx, slab_need + 16);
+    pN = n; pH = h; pW = w;
 }
 
 void UNetModel::prepare_shape(int n, int h, int w) {
@@ -148,21 +174,7 @@ void UNetModel::prepare_shape(int n, int h, int w) {
                 "forward: H and W must be multiples of 2^depth (" + std::to_string(div) +
                     "), as the reference's pool/up-conv/cat chain requires; got " +
                     std::to_string(h) + "x" + std::to_string(w));
-    if (n == pN && h == pH && w == pW && !bufs.empty()) return;     // (set_planes() clears pN: the table below depends on the flow)
-    ctx->activate();
     const int D = depth;
-    if (bufs.empty()) {
-        auto mk = [&](std::vector<int>& v) { v.assign(D + 1, -1); for (int l = 1; l <= D; ++l) v[l] = new_buf(); };
-        auto mkf = [&](std::vector<FlowTensor>& v) { v.assign(D + 1, FlowTensor()); for (int l = 1; l <= D; ++l) v[l].f32 = new_buf(); };
-        mkf(encY1); mkf(encY2); mk(concat); mk(pool); mkf(decY1); mkf(decY2);
-        mkf(gA); mkf(gB); mkf(dconcat); mkf(dpool); mk(gAe); mk(gBe);
-        for (FlowTensor* t : {&bottY1, &bottY2, &gBottA, &gBottB}) t->f32 = new_buf();
-        logits = new_buf(); dlogits = new_buf(); probs = new_buf();
-        x_stage = new_buf(); x_stage2 = new_buf(); x_pad = new_buf(); out_stage = new_buf();
-        ws_red = new_buf(); ws_slab = new_buf(); lab_stage = new_buf();
-    }
-    size_t red_need = 0;
-    auto upd_red = [&](size_t f) { if (f > red_need) red_need = f; };
     for (int l = 1; l <= D; ++l) {
         const size_t M = (size_t)n * (h >> (l - 1)) * (w >> (l - 1));
         const size_t C = (size_t)feat << (l - 1);
@@ -182,23 +194,13 @@ void UNetModel::prepare_shape(int n, int h, int w) {
         for (int i : {bottY1.f32, bottY2.f32, gBottA.f32, gBottB.f32}) bufs[i].ensure(ctx, M * C);
     }
     const size_t M1 = (size_t)n * h * w;
-    bufs[logits].ensure(ctx, M1 * out_ch);
-    bufs[dlogits].ensure(ctx, M1 * out_ch);
-    bufs[probs].ensure(ctx, M1 * out_ch);
-    bufs[x_stage].ensure(ctx, M1 * in_ch);
-    bufs[x_stage2].ensure(ctx, M1 * in_ch);
-    bufs[x_pad].ensure(ctx, M1 * convs[0].cin_p);
-    bufs[out_stage].ensure(ctx, M1 * out_ch);
-    bufs[lab_stage].ensure(ctx, (M1 + 3) / 4 + 4);
+    bufs[probs].ensure(ctx, M1 * out_ch);          // (set_head_sigmoid: this model only)
     // workspaces
     size_t cmax = (size_t)feat << depth;
-    upd_red(bn_stats_ws_floats((int)cmax));
-    upd_red(bn_bwd_ws_floats(M1, (int)cmax));
-    upd_red(head_bwd_ws_floats(M1, feat, out_ch) + bn_bwd_ws_floats(M1, feat));   // (+ the BN-backward records head_bwd leaves)
-    upd_red(channel_sum_ws_floats(M1, (int)cmax));
-    upd_red(loss_ws_doubles(M1) * 2);
-    upd_red(sumsq_ws_doubles(n_flat) * 2);
-    bufs[ws_red].ensure(ctx, red_need + 16);
+    need_red(bn_stats_ws_floats((int)cmax));
+    need_red(bn_bwd_ws_floats(M1, (int)cmax));
+    need_red(head_bwd_ws_floats(M1, feat, out_ch) + bn_bwd_ws_floats(M1, feat));   // (+ the BN-backward records head_bwd leaves)
+    need_red(channel_sum_ws_floats(M1, (int)cmax));
     // wgrad slabs: the largest need over all layers, from the descriptors the backward passes build (model_resnet.cpp: a
     // stride-2 3x3 conv runs as its 2x2 form on the space-to-depth input, the 1x1 projection on a channel slice of that input)
     for (const ConvBN& c : convs) {
@@ -209,7 +211,6 @@ void UNetModel::prepare_shape(int n, int h, int w) {
     }
     for (int k = 0; k < D; ++k)                    // decoder level D - k: dUp is the first half of its concat gradient
         need_slab(convt_wgrad_args(ups[k], View{nullptr, 2 * ups[k].cout}, View{nullptr, ups[k].cin}, InXform{}, Shape{n, h >> (D - k), w >> (D - k)}));
-    bufs[ws_slab].ensure(ctx, slab_need + 16);
     // per-layer regions for the partial sums of the conv-bias gradients + the table of the batched finisher
     // (the plane flows too: the plain U-Net's and the ResNet-encoder model's, whose encoder convs have no bias)
     if (!resnet_encoder || planesP) {
@@ -258,8 +259,8 @@ void UNetModel::prepare_shape(int n, int h, int w) {
         dbias_n = (int)hd.size();
         dbias_descs = ctx->upload_table(hd.data(), hd.size() * sizeof(FinishSumDesc));
     }
-    if (resnet_encoder && !planesP) prepare_resnet(n, h, w);
-    pN = n; pH = h; pW = w;
+    if (planesP) prepare_planes(n, h, w);
+    else if (resnet_encoder) prepare_resnet(n, h, w);
 }
 
 // ------------------------------------------------------------------------------------ derived filter copies
@@ -343,7 +344,7 @@ void rfi_model::rebuild_records() {
     }
     // layers whose filters the wave-specialised kernels read (ws_by_w) need no records: launch_conv drops
     // ConvArgs::w3 for them, and a shape those kernels decline (maps under 8 x 8) gets a temporary split copy
-    const RecordKey key{ws_P, pH * 65536 + pW};
+    const RecordKey key = record_key();
     if (x3.descs && !(x3_key == key)) x3.release(ctx);
     if (!x3.descs) {
         x3_key = key;
@@ -386,12 +387,13 @@ void rfi_model::refresh_s2d_forms(ConvBN& c) {
 }
 
 // plain U-Net, float32 tensors: when the wave-specialised copies of both directions are in use (and the pre-split records
-// do not read the dgrad layouts).  The plane flows: the forward pass reads the forward-direction images only, nothing but
+// do not read the dgrad layouts: the list in hand says so only while it is the prepared shape's -- on smaller maps the next
+// rebuild_records lists layers it left out, and would split stale dgrad layouts).  The plane flows: the forward pass reads the forward-direction images only, nothing but
 // the input-gradient kernels reads the dgrad layouts -- unless pre-split records of them are in use
 bool UNetModel::wd_split_ok() const {
     if (planesP) return wb_pool && wb.n_fwd > 0 && !use_w3() && training;
     return !resnet_encoder && ws_need() != 0 && ws_pool && ws_P == ws_need() && ws.n_fwd > 0 &&
-           (!use_w3() || (x3.descs && !x3_reads_wd && x3_key.ws_P == ws_P));
+           (!use_w3() || (x3.descs && !x3_reads_wd && x3_key == record_key()));
 }
 
 void UNetModel::refresh_model_weights(Half half) {
@@ -577,9 +579,8 @@ void rfi_model::convt_backward(const UpConv& u, View dup, View x, InXform xf, Sh
 // so the 3-channel stem runs on the same MFMA kernels as every other layer
 rfi::View rfi_model::network_input(const float* x_dev, int n, int h, int w) {
     const int cp = convs[0].cin_p;
-    if (cp == in_ch) return View{x_dev, in_ch};
-    launch_pad_channels(ctx, x_dev, (int64_t)n * h * w, in_ch, cp, buf(x_pad));
-    return View{buf(x_pad), cp};
+    if (cp != in_ch) launch_pad_channels(ctx, x_dev, (int64_t)n * h * w, in_ch, cp, buf(x_pad));
+    return padded_input(x_dev);
 }
 
 void rfi_model::forward(const float* x_dev, int n, int h, int w, bool train_mode) {
@@ -914,8 +915,7 @@ void UNetModel::backward_pass(const float* x_dev, const uint8_t* labels_dev, int
             launch_pool_bwd_merge(ctx, buf(encY2[l]), s.N, s.H, s.W, c2.cout, c2.scale(), c2.shift(),
                                   View{buf(dconcat[l]) + c2.cout, 2 * c2.cout}, buf(dpool[l]), buf(gA[l]), act_slope);
         backward_conv_bn(this, c2, buf(gA[l]), buf(encY2[l]), View{buf(encY1[l]), c1.cout}, bn_xf(c1), s, buf(gB[l]), have);
-        View in = (l == 1) ? (c1.cin_p == in_ch ? View{x_dev, in_ch} : View{buf(x_pad), c1.cin_p})
-                           : View{buf(pool[l - 1]), c1.cin};
+        View in = (l == 1) ? padded_input(x_dev) : View{buf(pool[l - 1]), c1.cin};
         backward_conv_bn(this, c1, buf(gB[l]), buf(encY1[l]), in, InXform{}, s,
                          (l == 1) ? nullptr : buf(dpool[l - 1]), 0);
         bucket_ready(c1.w_off, convs[l == D ? IB : 2 * l].w_off);       // convs[2 l] = first conv of the next level / the bottleneck

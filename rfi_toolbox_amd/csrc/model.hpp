@@ -165,7 +165,9 @@ struct rfi_model {
     int loss_kind = 0;                // 0: BCE-with-logits + dice (the reference's, train_model.py:120-128); 1: focal
     float focal_alpha = 0.25f, focal_gamma = 2.0f;
     bool head_sigmoid = false;        // UNetOverfit: forward returns sigmoid(logits); the loss sees that too
-    int probs = -1;                   // buffer index of sigmoid(logits) when head_sigmoid
+    // a per-pixel head of out_ch channels with the loss inside the model.  False (the backbone: out_ch is the FPN width): no
+    // logits, no label map, no loss workspace
+    bool dense_head = true;
 
     std::vector<rfi::ConvBN> convs;   // the network's conv-like layers in forward order
     std::vector<rfi::UpConv> ups;     // its transposed convs
@@ -209,10 +211,14 @@ struct rfi_model {
         wa.bf16 = arith == Arith::BF16;
         wa.bf16x3 = arith == Arith::X3;
     }
-    // prepare_shape: ws_slab (slab_need + 16 floats; grow-only, as the buffer) has to hold the slabs of weight gradient `wa` --
-    // the descriptor the backward pass will launch, from the same builder, with null data pointers
-    size_t slab_need = 0;
-    void need_slab(const rfi::WgradArgs& wa) { slab_need = std::max(slab_need, rfi::wgrad_slab_floats(wa, rfi::IMPL_AUTO)); }
+    // The two workspaces: prepare_shape declares what the passes need, prepare() sizes them (need + 16 floats; the needs are
+    // grow-only, as the buffers).  ws_red: the partial sums of a reduction, `floats` of them.  ws_slab: the slabs of weight
+    // gradient `wa` -- the descriptor the backward pass will launch, from the same builder, with null data pointers -- or of a
+    // plane weight gradient (pwgrad_slab_floats)
+    size_t red_need = 0, slab_need = 0;
+    void need_red(size_t floats) { red_need = std::max(red_need, floats); }
+    void need_slab(size_t floats) { slab_need = std::max(slab_need, floats); }
+    void need_slab(const rfi::WgradArgs& wa) { need_slab(rfi::wgrad_slab_floats(wa, rfi::IMPL_AUTO)); }
     // set by the plain U-Net: it keeps no pre-split (3 x bf16) filter records for the layers the wave-specialised kernels
     // cover, since at its shapes they never decline.  The other models (detector backbone on 4 x 4 maps, heads) keep every
     // record up to date, so a declined shape runs the round-2 kernel on valid records instead of a temporary copy (an
@@ -235,6 +241,7 @@ struct rfi_model {
     void refresh_ws_weights(rfi::Half half);
     rfi::BatchTable x3;               // pre-split records: the list of the batched rebuild ...
     rfi::RecordKey x3_key;            // ... and what it was built for
+    rfi::RecordKey record_key() const { return rfi::RecordKey{ws_P, pH * 65536 + pW}; }    // (what a list built now is for)
     bool x3_reads_wd = false;         // the list reads dgrad-layout filters (which forbids the split)
     std::unordered_set<const float*> x3_skipped;      // filters whose records are NOT kept up to date (ws_set clears ConvArgs::w3 for them)
     void rebuild_records();
@@ -249,22 +256,28 @@ struct rfi_model {
     void side_rebuild_wd();
     void wait_wd();
 
-    // activations / workspaces for the prepared shape
+    // activations / workspaces for the prepared shape (pN == 0: nothing prepared)
     int pN = 0, pH = 0, pW = 0;
+    void invalidate_shape() { pN = 0; }               // the next prepare() sizes everything again
     std::vector<rfi::DevBuf> bufs;
-    // indices into bufs
-    int logits = -1, dlogits = -1;
+    // indices into bufs.  What the entry points stage through and the workspaces: the constructor creates them, prepare() sizes
+    // them (probs, sigmoid(logits) when head_sigmoid: by the one model that can enable it)
+    int logits = -1, dlogits = -1, probs = -1;
     int x_stage = -1, x_stage2 = -1, x_pad = -1, out_stage = -1, ws_red = -1, ws_slab = -1, lab_stage = -1;
-    int gx = -1;                      // the gradient w.r.t. the input (the detector's heads; -1: the model computes none)
+    int gx = -1;                      // the gradient w.r.t. the input (the detector's heads own it; -1: the model computes none)
     bool ext_dlogits = false;         // backward from caller-provided dlogits (rfi_model_backward_dlogits)
     double* d_sums = nullptr;         // [0..3] loss sums, [4] grad sumsq
     float* d_scalars = nullptr;       // [0] loss, [1] grad norm
     float last_loss = 0, last_norm = 0;
 
-    rfi_model(int in, int out, int f, int d) : in_ch(in), out_ch(out), feat(f), depth(d) {}
+    rfi_model(int in, int out, int f, int d) : in_ch(in), out_ch(out), feat(f), depth(d) {
+        make_bufs({&logits, &dlogits, &probs, &x_stage, &x_stage2, &x_pad, &out_stage, &ws_red, &ws_slab, &lab_stage});
+    }
     virtual ~rfi_model();
-    virtual void build() = 0;                          // layers, parameter table, device state
-    void prepare(int n, int h, int w);                 // (rejoins the streams, then prepare_shape)
+    virtual void build() = 0;                          // layers, parameter table, device state, the slots of the network's own tensors
+    // rejoins the streams; for a shape other than the prepared one: prepare_shape, then the shared buffers and workspaces
+    void prepare(int n, int h, int w);
+    // rejects a shape the network cannot run, sizes the network's own tensors and declares its workspace needs
     virtual void prepare_shape(int n, int h, int w) = 0;
     void forward(const float* x_dev, int n, int h, int w, bool train_mode);    // (prepare + derived filters, then forward_pass)
     virtual void forward_pass(const float* x_dev, int n, int h, int w, bool train_mode) = 0;
@@ -295,7 +308,14 @@ struct rfi_model {
     void load_adam(const rfi::Entry& e, const void* host_m, const void* host_v, size_t bytes);
     float* buf(int i) { return bufs[i].p; }
     int new_buf() { bufs.emplace_back(); return (int)bufs.size() - 1; }
+    void make_bufs(std::initializer_list<int*> slots) { for (int* s : slots) *s = new_buf(); }     // build(): a network's own tensors
+    // what the first conv reads: the input with its channels zero-padded to convs[0].cin_p.  network_input pads (forward
+    // pass); padded_input is that view again for a backward pass, without a launch
     rfi::View network_input(const float* x_dev, int n, int h, int w);
+    rfi::View padded_input(const float* x_dev) const {
+        const int cp = convs[0].cin_p;
+        return cp == in_ch ? rfi::View{x_dev, in_ch} : rfi::View{bufs[x_pad].p, cp};
+    }
 
     // ---- launches on float32 tensors the networks share (model.cpp); algo_flops, stats and done stay the caller's
     // a stride-1 conv whose output grid is its input's (s): R x R taps, `pad`, filters w [tap][cout][cin], output [M][cout]
@@ -458,13 +478,15 @@ struct UNetModel : rfi_model {
     rfi::bf16_t* wb_pool = nullptr;
     rfi::BatchTable wb;               // (the forward-direction filter images first)
     void set_planes(int P);           // switches the data flow; frees plane tensors of another P
-    void prepare_planes(int n, int h, int w);
+    void make_slots();                // (end of build()) the float32 tensors' slots, then make_plane_slots
+    void make_plane_slots();          // every plane tensor's slot, for either flow: they depend on depth and blocks only
+    void prepare_planes(int n, int h, int w);        // (prepare_shape, on a plane data flow)
     void refresh_plane_weights(rfi::Half half);      // InputGrad: + the parity-class tables
     void forward_planes(const float* x_dev, int n, int h, int w, bool train_mode);
     void backward_planes(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w);
     // weight-gradient launches of the plane kernel: of conv layer c over the output grid s (in: its input in nseg K-segments,
     // dY: the gradient w.r.t. its raw output) and of transposed conv u over its input grid s (dUp: the gradient w.r.t. its
-    // output, in: its activated input).  prepare_planes sizes ws_slab from the same descriptors with null operands
+    // output, in: its activated input).  prepare_planes declares ws_slab's need from the same descriptors with null operands
     rfi::PWgradArgs pwgrad_args(const rfi::ConvBN& c, const rfi::PlaneSeg* in, int nseg, rfi::PlaneSeg dY, rfi::Shape s);
     rfi::PWgradArgs convt_pwgrad_args(const rfi::UpConv& u, rfi::PlaneSeg dUp, rfi::PlaneSeg in, rfi::Shape s);
     // the flow tensor a debug name means (null: none of them) with its pixels and channels; a level out of range throws
@@ -490,7 +512,7 @@ struct Cnn3Model : rfi_model {
 // head (the same stack without the transposed conv)
 struct ConvHeadModel : rfi_model {
     const bool upsample;
-    ConvHeadModel(int in, int layers, int out, bool up) : rfi_model(in, out, in, layers), upsample(up) { gx = new_buf(); }
+    ConvHeadModel(int in, int layers, int out, bool up) : rfi_model(in, out, in, layers), upsample(up) {}
     void build() override;
     void prepare_shape(int n, int h, int w) override;
     void forward_pass(const float* x_dev, int n, int h, int w, bool train_mode) override;
@@ -507,7 +529,10 @@ struct ConvHeadModel : rfi_model {
 
 // ResNet-50-FPN backbone with frozen BatchNorm (model_backbone.cpp): feat = base width (64), out_ch = FPN channels
 struct BackboneModel : rfi_model {
-    BackboneModel(int in, int base_width, int fpn_ch) : rfi_model(in, fpn_ch, base_width, 0) { model_copies_every_pass = true; }
+    BackboneModel(int in, int base_width, int fpn_ch) : rfi_model(in, fpn_ch, base_width, 0) {
+        model_copies_every_pass = true;
+        dense_head = false;
+    }
     ~BackboneModel() override;
     void build() override;
     void prepare_shape(int n, int h, int w) override;
@@ -539,7 +564,7 @@ struct BackboneModel : rfi_model {
 
 // fully connected box head (model_mlp.cpp): depth FC + ReLU layers in_ch -> feat -> feat, head feat -> out_ch
 struct BoxHeadModel : rfi_model {
-    BoxHeadModel(int in, int hidden, int layers, int out) : rfi_model(in, out, hidden, layers) { gx = new_buf(); }
+    BoxHeadModel(int in, int hidden, int layers, int out) : rfi_model(in, out, hidden, layers) {}
     void build() override;
     void prepare_shape(int n, int h, int w) override;
     void forward_pass(const float* x_dev, int n, int h, int w, bool train_mode) override;

@@ -69,6 +69,14 @@ void BackboneModel::build() {
         fpn_layer[i] = add("fpn.layer_blocks." + std::to_string(i) + ".0", "", F, F, 3, 1, i + 2, false, true);
     head_w_off = head_b_off = n_flat;     // (no head)
     alloc_state();
+    make_bufs({&bY0, &bP0, &bArg, &fP6, &fdP6, &bdW, &bS, &bCol, &bWp});
+    for (auto& k : bb) {
+        make_bufs({&k.Y1, &k.Y2, &k.Y3, &k.A});
+        if (k.cd >= 0) make_bufs({&k.Yd});
+        if (k.stride == 2) make_bufs({&k.xs1, &k.xsA});
+    }
+    for (int i = 0; i < 4; ++i) make_bufs({&fL[i], &fM[i], &fP[i], &fdM[i], &fdP[i], &bT[i][0], &bT[i][1], &bT[i][2]});
+    for (int& g : bG) make_bufs({&g});
 
     // 2x2 forms of the stride-2 3x3 filters, 4x tiled affine coefficients of their inputs, identity vectors
     const size_t cmax = (size_t)32 * w0;
@@ -121,24 +129,7 @@ Shape flat_1x1(Shape s, int R) {
 
 void BackboneModel::prepare_shape(int n, int h, int w) {
     RFI_REQUIRE(h % 64 == 0 && w % 64 == 0, "ResNet50FPN: H and W must be multiples of 64");
-    if (n == pN && h == pH && w == pW && !bufs.empty()) return;
-    ctx->activate();
     const int F = out_ch;
-    if (bufs.empty()) {
-        bY0 = new_buf(); bP0 = new_buf(); bArg = new_buf();
-        for (auto& k : bb) {
-            k.Y1 = new_buf(); k.Y2 = new_buf(); k.Y3 = new_buf(); k.A = new_buf();
-            if (k.cd >= 0) k.Yd = new_buf();
-            if (k.stride == 2) { k.xs1 = new_buf(); k.xsA = new_buf(); }
-        }
-        for (int i = 0; i < 4; ++i) { fL[i] = new_buf(); fM[i] = new_buf(); fP[i] = new_buf(); fdM[i] = new_buf(); fdP[i] = new_buf(); }
-        fP6 = new_buf(); fdP6 = new_buf();
-        for (int i = 0; i < 6; ++i) bG[i] = new_buf();
-        for (int r = 0; r < 4; ++r) for (int p = 0; p < 3; ++p) bT[r][p] = new_buf();
-        bdW = new_buf(); bS = new_buf(); bCol = new_buf(); bWp = new_buf();
-        x_stage = new_buf(); x_stage2 = new_buf(); x_pad = new_buf(); out_stage = new_buf();
-        ws_red = new_buf(); ws_slab = new_buf(); lab_stage = new_buf(); logits = new_buf(); dlogits = new_buf();
-    }
     auto px = [&](int lvl) { return (size_t)n * (h >> lvl) * (w >> lvl); };
     bufs[bY0].ensure(ctx, px(1) * feat);
     bufs[bP0].ensure(ctx, px(2) * feat);
@@ -170,13 +161,9 @@ void BackboneModel::prepare_shape(int n, int h, int w) {
     bufs[bCol].ensure(ctx, px(1) * stem_kp());
     bufs[bWp].ensure(ctx, (size_t)feat * stem_kp() + 16);
     bufs[bdW].ensure(ctx, wmax + 16);
-    bufs[x_stage].ensure(ctx, (size_t)n * h * w * in_ch);
-    bufs[x_stage2].ensure(ctx, (size_t)n * h * w * in_ch);
-    for (int b : {x_pad, out_stage, lab_stage, logits, dlogits}) bufs[b].ensure(ctx, 16);
-    size_t red_need = sumsq_ws_doubles((int64_t)n_flat) * 2;
     const int cmax = 32 * feat;
-    red_need = std::max({red_need, bn_bwd_ws_floats((int64_t)px(1), cmax), channel_sum_ws_floats((int64_t)px(2), std::max(cmax, F))});
-    bufs[ws_red].ensure(ctx, red_need + 16);
+    need_red(bn_bwd_ws_floats((int64_t)px(1), cmax));
+    need_red(channel_sum_ws_floats((int64_t)px(2), std::max(cmax, F)));
     for (auto& c : convs) {
         // in the form backward_pass launches it: a stride-2 3x3 conv as 2x2 on its space-to-depth input (of which a stride-2
         // 1x1 projection reads a channel slice), the stem K-packed as a 1x1 conv
@@ -188,8 +175,6 @@ void BackboneModel::prepare_shape(int n, int h, int w) {
         for (const Shape& l : {s, flat_1x1(s, R)})      // (a small 1x1 map in both layouts, as ever: ws_slab keeps its size)
             need_slab(wgrad_same(x, InXform{}, nullptr, l, R, pad, cx, c.cout, nullptr));
     }
-    bufs[ws_slab].ensure(ctx, slab_need + 16);
-    pN = n; pH = h; pW = w;
 }
 
 // frozen BatchNorm coefficients and the derived filter copies the batched relayout does not cover (both directions at

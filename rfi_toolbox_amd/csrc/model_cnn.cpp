@@ -27,36 +27,15 @@ void Cnn3Model::build() {
     }
     add_head("decoder.0", feat);
     alloc_state();
+    make_bufs({&cY1, &cY2, &cG1, &cG2});
 }
 
 void Cnn3Model::prepare_shape(int n, int h, int w) {
-    if (n == pN && h == pH && w == pW && !bufs.empty()) return;
-    ctx->activate();
-    if (bufs.empty()) {
-        cY1 = new_buf(); cY2 = new_buf(); cG1 = new_buf(); cG2 = new_buf();
-        logits = new_buf(); dlogits = new_buf();
-        x_stage = new_buf(); x_stage2 = new_buf(); x_pad = new_buf(); out_stage = new_buf();
-        ws_red = new_buf(); ws_slab = new_buf(); lab_stage = new_buf();
-    }
     const size_t M1 = (size_t)n * h * w;
     for (int i : {cY1, cY2, cG1, cG2}) bufs[i].ensure(ctx, M1 * feat);
-    bufs[logits].ensure(ctx, M1 * out_ch);
-    bufs[dlogits].ensure(ctx, M1 * out_ch);
-    bufs[x_stage].ensure(ctx, M1 * in_ch);
-    bufs[x_stage2].ensure(ctx, M1 * in_ch);
-    bufs[x_pad].ensure(ctx, M1 * convs[0].cin_p);
-    bufs[out_stage].ensure(ctx, M1 * out_ch);
-    bufs[lab_stage].ensure(ctx, (M1 + 3) / 4 + 4);
-    size_t red_need = 0;
-    auto upd = [&](size_t f) { red_need = std::max(red_need, f); };
-    upd(head_bwd_ws_floats((int64_t)M1, feat, out_ch));
-    upd(channel_sum_ws_floats((int64_t)M1, feat));
-    upd(loss_ws_doubles((int64_t)M1) * 2);
-    upd(sumsq_ws_doubles((int64_t)n_flat) * 2);
-    bufs[ws_red].ensure(ctx, red_need + 16);
+    need_red(head_bwd_ws_floats((int64_t)M1, feat, out_ch));
+    need_red(channel_sum_ws_floats((int64_t)M1, feat));
     for (auto& c : convs) need_slab(wgrad_same(View{nullptr, c.cin_p}, InXform{}, nullptr, Shape{n, h, w}, 3, 1, c.cin_p, c.cout, nullptr));
-    bufs[ws_slab].ensure(ctx, slab_need + 16);
-    pN = n; pH = h; pW = w;
 }
 
 void Cnn3Model::forward_pass(const float* x_dev, int n, int h, int w, bool) {
@@ -98,8 +77,7 @@ void Cnn3Model::backward_pass(const float* x_dev, const uint8_t* labels_dev, int
         }
     };
     conv_backward(c2, buf(cG2), buf(cY2), View{buf(cY1), c1.cout}, act_of(c1), buf(cG1));
-    View x = c1.cin_p == in_ch ? View{x_dev, in_ch} : View{buf(x_pad), c1.cin_p};
-    conv_backward(c1, buf(cG1), buf(cY1), x, InXform{}, nullptr);
+    conv_backward(c1, buf(cG1), buf(cY1), padded_input(x_dev), InXform{}, nullptr);
     side_join();
     bucket_ready(0, n_flat);                  // three layers: one bucket
 }

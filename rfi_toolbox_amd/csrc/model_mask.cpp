@@ -43,39 +43,20 @@ void ConvHeadModel::build() {
     if (up) add_up("conv5_mask", C, C);
     add_head(up ? "mask_fcn_logits" : "head", C);
     alloc_state();
+    mkY.assign(L, -1); mkG.assign(L, -1);
+    for (int i = 0; i < L; ++i) make_bufs({&mkY[i], &mkG[i]});
+    make_bufs({&mkU, &mkGU, &gx, &head_wd, &head_w3, &head_wd3});
 }
 
 void ConvHeadModel::prepare_shape(int n, int h, int w) {
-    if (n == pN && h == pH && w == pW && !bufs.empty()) return;
-    ctx->activate();
     const int L = depth, C = in_ch;
-    if (mkY.empty()) {
-        mkY.assign(L, -1); mkG.assign(L, -1);
-        for (int i = 0; i < L; ++i) { mkY[i] = new_buf(); mkG[i] = new_buf(); }
-        mkU = new_buf(); mkGU = new_buf();
-        logits = new_buf(); dlogits = new_buf(); head_wd = new_buf(); head_w3 = new_buf(); head_wd3 = new_buf();
-        x_stage = new_buf(); x_stage2 = new_buf(); x_pad = new_buf(); out_stage = new_buf();
-        ws_red = new_buf(); ws_slab = new_buf(); lab_stage = new_buf();
-    }
     const size_t M = (size_t)n * h * w, M4 = (size_t)out_scale * out_scale * M;
     for (int i = 0; i < L; ++i) { bufs[mkY[i]].ensure(ctx, M * C); bufs[mkG[i]].ensure(ctx, M * C); }
     bufs[mkU].ensure(ctx, upsample ? M4 * C : 16);
     bufs[mkGU].ensure(ctx, upsample ? M4 * C : 16);
     bufs[gx].ensure(ctx, M * C);
-    bufs[logits].ensure(ctx, M4 * out_ch);
-    bufs[dlogits].ensure(ctx, M4 * out_ch);
-    bufs[x_stage].ensure(ctx, M * C);
-    bufs[x_stage2].ensure(ctx, M * C);
-    bufs[x_pad].ensure(ctx, 16);
-    bufs[out_stage].ensure(ctx, M4 * out_ch);
-    bufs[lab_stage].ensure(ctx, (M4 + 3) / 4 + 4);
-    size_t red_need = 0;
-    auto upd = [&](size_t f) { red_need = std::max(red_need, f); };
-    upd(head_bwd_ws_floats((int64_t)M4, C, out_ch));
-    upd(channel_sum_ws_floats((int64_t)M4, C));
-    upd(loss_ws_doubles((int64_t)M4) * 2);
-    upd(sumsq_ws_doubles((int64_t)n_flat) * 2);
-    bufs[ws_red].ensure(ctx, red_need + 16);
+    need_red(head_bwd_ws_floats((int64_t)M4, C, out_ch));
+    need_red(channel_sum_ws_floats((int64_t)M4, C));
     const Shape s{n, h, w};
     need_slab(wgrad_same(View{nullptr, C}, InXform{}, nullptr, s, 3, 1, C, C, nullptr));          // the 3x3 layers
     // the transposed conv (sized without `upsample` too, as ever: ws_slab keeps its size)
@@ -86,8 +67,6 @@ void ConvHeadModel::prepare_shape(int n, int h, int w) {
     bufs[head_wd].ensure(ctx, (size_t)out_ch * C + 16);
     bufs[head_w3].ensure(ctx, weights_x3_floats(1, out_ch, C) + 16);
     bufs[head_wd3].ensure(ctx, weights_x3_floats(1, C, out_ch) + 16);
-    bufs[ws_slab].ensure(ctx, slab_need + 16);
-    pN = n; pH = h; pW = w;
 }
 
 void ConvHeadModel::forward_pass(const float* x_dev, int n, int h, int w, bool) {

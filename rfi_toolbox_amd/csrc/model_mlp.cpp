@@ -31,6 +31,9 @@ void BoxHeadModel::build() {
     }
     add_head("head", feat);
     alloc_state();
+    fcY.assign(L, -1); fcG.assign(L, -1);
+    for (int i = 0; i < L; ++i) make_bufs({&fcY[i], &fcG[i]});
+    make_bufs({&gx});
 }
 
 namespace {
@@ -40,32 +43,14 @@ Shape layout_of(int rows) { return rows % 32 == 0 ? Shape{1, rows / 32, 32} : Sh
 
 void BoxHeadModel::prepare_shape(int n, int h, int w) {
     RFI_REQUIRE(h == 1 && w == 1, "BoxHead: the input is [R, in_features] (n = R, h = w = 1)");
-    if (n == pN && !bufs.empty()) return;
-    ctx->activate();
-    const int L = depth;
-    if (fcY.empty()) {
-        fcY.assign(L, -1); fcG.assign(L, -1);
-        for (int i = 0; i < L; ++i) { fcY[i] = new_buf(); fcG[i] = new_buf(); }
-        logits = new_buf(); dlogits = new_buf();
-        x_stage = new_buf(); x_stage2 = new_buf(); x_pad = new_buf(); out_stage = new_buf();
-        ws_red = new_buf(); ws_slab = new_buf(); lab_stage = new_buf();
-    }
     const size_t M = (size_t)n;
-    for (int i = 0; i < L; ++i) { bufs[fcY[i]].ensure(ctx, M * feat); bufs[fcG[i]].ensure(ctx, M * feat); }
+    for (int i = 0; i < depth; ++i) { bufs[fcY[i]].ensure(ctx, M * feat); bufs[fcG[i]].ensure(ctx, M * feat); }
     bufs[gx].ensure(ctx, M * in_ch);
-    bufs[logits].ensure(ctx, M * out_ch);
-    bufs[dlogits].ensure(ctx, M * out_ch);
-    bufs[x_stage].ensure(ctx, M * in_ch);
-    bufs[x_stage2].ensure(ctx, M * in_ch);
-    bufs[x_pad].ensure(ctx, 16);
-    bufs[out_stage].ensure(ctx, M * out_ch);
-    bufs[lab_stage].ensure(ctx, (M + 3) / 4 + 4);
-    size_t red_need = std::max({head_bwd_ws_floats((int64_t)M, feat, out_ch), channel_sum_ws_floats((int64_t)M, feat),
-                                sumsq_ws_doubles((int64_t)n_flat) * 2});
-    bufs[ws_red].ensure(ctx, red_need + 16);
+    // (prepare() adds the loss partials of a dense head, which this one never uses: 8208 floats, under the head's
+    // 2048 (feat + 1) out_ch at any width)
+    need_red(head_bwd_ws_floats((int64_t)M, feat, out_ch));
+    need_red(channel_sum_ws_floats((int64_t)M, feat));
     for (auto& c : convs) need_slab(wgrad_same(View{nullptr, c.cin}, InXform{}, nullptr, layout_of(n), 1, 0, c.cin, c.cout, nullptr));
-    bufs[ws_slab].ensure(ctx, slab_need + 16);
-    pN = n; pH = 1; pW = 1;
 }
 
 void BoxHeadModel::forward_pass(const float* x_dev, int n, int, int, bool) {

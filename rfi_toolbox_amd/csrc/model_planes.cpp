@@ -49,22 +49,35 @@ void PlaneBuf::free() {
 
 }  // namespace rfi
 
+void UNetModel::make_plane_slots() {
+    const int D = depth;
+    auto one = [&]() { pl.emplace_back(); return (int)pl.size() - 1; };
+    auto mk = [&](std::vector<int>& v) { v.assign(D + 1, -1); for (int l = 1; l <= D; ++l) v[l] = one(); };      // one per level
+    mk(pA1e); mk(pSkip); mk(pPool); mk(pUp); mk(pA1d); mk(pdYa); mk(pdYb); mk(pdYaE); mk(pdYbE); mk(pUpIn);
+    pXin = one(); pA1b = one(); pdYbottA = one(); pdYbottB = one();
+    upf.assign(D + 1, -1);
+    for (int l = 1; l <= D; ++l) upf[l] = new_buf();
+    // the bfloat16 twins of the flow tensors (prepare_planes allocates them where the mode stores them)
+    for (auto* v : {&encY1, &encY2, &decY1, &decY2, &gA, &gB, &dconcat, &dpool})
+        for (int l = 1; l <= D; ++l) (*v)[l].b16 = one();
+    for (FlowTensor* t : {&bottY1, &bottY2, &gBottA, &gBottB}) t->b16 = one();
+    gAdec = gA;
+    if (!resnet_encoder) return;
+    rpStemY = one(); rpA0 = one(); rpdY0 = one(); rp_dA1 = one(); rp_dX = one(); rp_dz[0] = one(); rp_dz[1] = one();
+    rpb.assign(blocks.size(), ResPlanes());
+    for (size_t bi = 0; bi < blocks.size(); ++bi) {
+        ResPlanes& r = rpb[bi];
+        const ResBlock& b = blocks[bi];
+        r.Y1 = one(); r.Y2 = one(); r.A1 = one(); r.dY1 = one(); r.dY2 = one();
+        // a stage's output is the decoder's skip tensor; the last stage's is pooled (and copied there) by one kernel
+        r.A = ((bi & 1) && b.level < D) ? pSkip[b.level] : one();
+        if (b.stride == 2) { r.Yd = one(); r.dYd = one(); }
+    }
+}
+
 void UNetModel::prepare_planes(int n, int h, int w) {
     const int P = planesP, D = depth;
     const bool rs = resnet_encoder;                    // ResNet-style encoder: its own tensors instead of the U-Net encoder's
-    auto one = [&]() { pl.emplace_back(); return (int)pl.size() - 1; };
-    if (pl.empty()) {
-        auto mk = [&](std::vector<int>& v) { v.assign(D + 1, -1); for (int l = 1; l <= D; ++l) v[l] = one(); };      // one per level
-        mk(pA1e); mk(pSkip); mk(pPool); mk(pUp); mk(pA1d); mk(pdYa); mk(pdYb); mk(pdYaE); mk(pdYbE); mk(pUpIn);
-        pXin = one(); pA1b = one(); pdYbottA = one(); pdYbottB = one();
-        upf.assign(D + 1, -1);
-        for (int l = 1; l <= D; ++l) upf[l] = new_buf();
-        // the bfloat16 twins of the flow tensors (allocated below where the mode stores them)
-        for (auto* v : {&encY1, &encY2, &decY1, &decY2, &gA, &gB, &dconcat, &dpool})
-            for (int l = 1; l <= D; ++l) (*v)[l].b16 = one();
-        for (FlowTensor* t : {&bottY1, &bottY2, &gBottA, &gBottB}) t->b16 = one();
-        gAdec = gA;
-    }
     auto pixels = [&](int l) { return (int64_t)n * (h >> (l - 1)) * (w >> (l - 1)); };      // of level l (D + 1: the bottleneck)
     const int64_t M1 = pixels(1), Mb = pixels(D + 1);
     const int Cb = feat << D;
@@ -113,18 +126,6 @@ void UNetModel::prepare_planes(int n, int h, int w) {
         for (int l = 1; l <= D; ++l) pl[pUpIn[l]].ensure(ctx, pixels(l + 1), feat << l, 1);
     if (rs) {
         RFI_REQUIRE(P == 1 && y16_flow && g16_flow, "UNetResNet18 on the plane kernels: bfloat16 flow with init_features % 16 == 0 only");
-        if (rpStemY < 0) {
-            rpStemY = one(); rpA0 = one(); rpdY0 = one(); rp_dA1 = one(); rp_dX = one(); rp_dz[0] = one(); rp_dz[1] = one();
-            if (rpb.empty()) rpb.assign(blocks.size(), ResPlanes());
-            for (size_t bi = 0; bi < blocks.size(); ++bi) {
-                ResPlanes& r = rpb[bi];
-                const ResBlock& b = blocks[bi];
-                r.Y1 = one(); r.Y2 = one(); r.A1 = one(); r.dY1 = one(); r.dY2 = one();
-                // a stage's output is the decoder's skip tensor; the last stage's is pooled (and copied there) by one kernel
-                r.A = ((bi & 1) && b.level < D) ? pSkip[b.level] : one();
-                if (b.stride == 2) { r.Yd = one(); r.dYd = one(); }
-            }
-        }
         for (int i : {rpStemY, rpA0, rpdY0, rp_dA1, rp_dX, rp_dz[0], rp_dz[1]}) pl[i].ensure(ctx, M1, feat, 1);   // (M C halves per level)
         for (size_t bi = 0; bi < blocks.size(); ++bi) {
             const ResBlock& b = blocks[bi];
@@ -134,20 +135,18 @@ void UNetModel::prepare_planes(int n, int h, int w) {
             if (b.stride == 2) for (int i : {r.Yd, r.dYd}) pl[i].ensure(ctx, M, b.cout, 1);
         }
     }
-    // weight-gradient slabs of the plane kernel: the largest need over the descriptors the backward pass will launch, from the
-    // same builders with null operands
+    // weight-gradient slabs of the plane kernel: the descriptors the backward pass will launch, from the same builders with null
+    // operands (the plan comes from the shape alone: the workspace the builders point at need not exist yet)
     auto none = [](int C) { return PlaneSeg{nullptr, 0, plane_chunks(C)}; };
-    size_t need = 0;
     for (size_t ci = 0; ci < convs.size(); ++ci) {
         const ConvBN& c = convs[ci];
         const bool two = (int)ci >= i_bott + 2 && (((int)ci - (i_bott + 2)) & 1) == 0;      // decoder conv1: [up | skip]
         const PlaneSeg in[2] = {none(two ? c.cin / 2 : c.cin), none(c.cin / 2)};
-        need = std::max(need, pwgrad_slab_floats(pwgrad_args(c, in, two ? 2 : 1, none(c.cout), Shape{n, h >> (c.level - 1), w >> (c.level - 1)})));
+        need_slab(pwgrad_slab_floats(pwgrad_args(c, in, two ? 2 : 1, none(c.cout), Shape{n, h >> (c.level - 1), w >> (c.level - 1)})));
     }
     if (convt_planes)
         for (int k = 0; k < D; ++k)               // (decoder level D - k: the grid of its input)
-            need = std::max(need, pwgrad_slab_floats(convt_pwgrad_args(ups[k], none(ups[k].cout), none(ups[k].cin), Shape{n, h >> (D - k), w >> (D - k)})));
-    if (bufs[ws_slab].n < need + 16) bufs[ws_slab].ensure(ctx, need + 16);
+            need_slab(pwgrad_slab_floats(convt_pwgrad_args(ups[k], none(ups[k].cout), none(ups[k].cin), Shape{n, h >> (D - k), w >> (D - k)})));
 }
 
 PWgradArgs UNetModel::pwgrad_args(const ConvBN& c, const PlaneSeg* in, int nseg, PlaneSeg dY, Shape s) {
@@ -194,7 +193,6 @@ void UNetModel::refresh_plane_weights(Half half) {
     const int P = planesP, IB = i_bott;
     auto two_seg = [&](size_t ci) { return (int)ci >= IB + 2 && (((int)ci - (IB + 2)) & 1) == 0; };      // decoder conv1: [up | skip]
     auto has_wBd = [&](const ConvBN& c) { return c.R == 3 && c.stride == 1; };      // (the other shapes' input gradients: class tables)
-    if (resnet_encoder && rpb.empty()) rpb.assign(blocks.size(), ResPlanes());
     if (!wb_pool) {
         // the table: every forward-direction image first (what the forward pass reads), then the input-gradient direction
         // (dgrad layouts, parity-class tables) -- the second half can be rebuilt on the side stream under the forward pass
@@ -348,7 +346,6 @@ void UNetModel::forward_resnet_planes(PlaneSeg& cur, int n, int h, int w, bool t
 
 void UNetModel::forward_planes(const float* x_dev, int n, int h, int w, bool train_mode) {
     const int D = depth, P = planesP;
-    prepare_planes(n, h, w);
     launch_act_split(ctx, View{x_dev, in_ch}, (int64_t)n * h * w, in_ch, InXform{}, P, pl[pXin].p, pl[pXin].pstride);
     PlaneSeg cur = pl[pXin].seg();
     const int IB = i_bott;

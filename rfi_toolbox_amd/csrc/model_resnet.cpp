@@ -66,6 +66,12 @@ void UNetModel::build_resnet() {
     }
     add_head("final_conv", feat);
     alloc_state();
+    make_slots();
+    make_bufs({&rs_stemY, &rs_a0, &rs_g0, &rs_g1, &rs_dX, &rs_dS, &rs_dW, &rs_dzd, &rs_dz[0], &rs_dz[1], &rs_dA1[0], &rs_dA1[1]});
+    for (auto& b : blocks) {
+        make_bufs({&b.Y1, &b.Y2, &b.A});
+        if (b.stride == 2) make_bufs({&b.Yd, &b.xs});
+    }
 
     // derived filters of the stride-2 convs (2x2 form + its dgrad layout) and identity scale / shift vectors
     size_t wneed = 0;
@@ -93,15 +99,6 @@ void UNetModel::build_resnet() {
 }
 
 void UNetModel::prepare_resnet(int n, int h, int w) {
-    if (rs_stemY < 0) {
-        rs_stemY = new_buf(); rs_a0 = new_buf(); rs_g0 = new_buf(); rs_g1 = new_buf();
-        rs_dX = new_buf(); rs_dS = new_buf(); rs_dW = new_buf(); rs_dzd = new_buf();
-        for (int i = 0; i < 2; ++i) { rs_dz[i] = new_buf(); rs_dA1[i] = new_buf(); }
-        for (auto& b : blocks) {
-            b.Y1 = new_buf(); b.Y2 = new_buf(); b.A = new_buf();
-            if (b.stride == 2) { b.Yd = new_buf(); b.xs = new_buf(); }
-        }
-    }
     const size_t M1 = (size_t)n * h * w;
     bufs[rs_stemY].ensure(ctx, M1 * feat);
     bufs[rs_a0].ensure(ctx, M1 * feat);
@@ -265,8 +262,7 @@ void UNetModel::backward_resnet_encoder(const float* x_dev, int n, int h, int w)
                              grads + c.g_off, grads + c.be_off, act_slope);
         launch_bn_bwd_apply(ctx, gout, buf(rs_stemY), M, c.cout, c.scale(), c.shift(), c.mean(), c.invstd(), params + c.g_off,
                             c.c1(), c.c2(), ws, nullptr, act_slope);
-        View in = c.cin_p == in_ch ? View{x_dev, in_ch} : View{buf(x_pad), c.cin_p};
-        wgrad(in, InXform{}, gout, c.cout, c.cin_p, s, 3, 1, grads + c.w_off, 2.0 * M * 9.0 * c.cin * c.cout);
+        wgrad(padded_input(x_dev), InXform{}, gout, c.cout, c.cin_p, s, 3, 1, grads + c.w_off, 2.0 * M * 9.0 * c.cin * c.cout);
         bucket_ready(0, convs[blocks[0].c1].w_off);
     }
 }

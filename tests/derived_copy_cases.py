@@ -41,13 +41,13 @@ ARCHS = (
     # depth 2 instead of the default 4: 0.5 M parameters instead of 7.8 M.  Every compared step moves the whole state and both Adam
     # moments across the host boundary four times; at depth 4 this one row took half the file's time.  The stem kernels (4 -> 32)
     # and the transposed convs on the plane kernels (widths in whole 32-channel blocks) are reached at either depth
-    Arch("unet_in4_f32", "UNet", (4, 1, 32), {"depth": 2}, "seg", ((2, 32, 32),), "decoder2.conv.conv.0.weight", None, ALL),
-    Arch("unet_f6", "UNet", (3, 1, 6), {}, "seg", ((2, 32, 32),), "decoder3.conv.conv.0.weight", None, ALL),
-    Arch("resnet18_f16", "UNetResNet18", (3, 1, 16), {}, "seg", ((2, 64, 64),), "decoder3.conv.conv.0.weight", None, ALL),
-    Arch("cnn_w64", "SimpleCNN", (3, 1, 64), {}, "seg", ((2, 32, 32),), "encoder.2.weight", None, ALL),
-    Arch("mask_head", "MaskHead", (16, 1, 4), {}, "mask", ((6, 14, 14),), "mask_fcn3.weight", None, ALL),
-    Arch("rpn_head", "RPNHead", (16, 4), {}, "rpn", (((2, 16, 16), (2, 8, 8)),), "head.weight", None, ALL),
-    Arch("box_head", "BoxHead", (16, 7, 64, 2), {}, "box", ((96,),), "fc7.weight", None, ALL),
+    Arch("unet_in4_f32", "UNet", (4, 1, 32), {"depth": 2}, "seg", ((2, 32, 32), (1, 16, 48)), "decoder2.conv.conv.0.weight", None, ALL),
+    Arch("unet_f6", "UNet", (3, 1, 6), {}, "seg", ((2, 32, 32), (1, 16, 48)), "decoder3.conv.conv.0.weight", None, ALL),
+    Arch("resnet18_f16", "UNetResNet18", (3, 1, 16), {}, "seg", ((2, 64, 64), (1, 32, 32)), "decoder3.conv.conv.0.weight", None, ALL),
+    Arch("cnn_w64", "SimpleCNN", (3, 1, 64), {}, "seg", ((2, 32, 32), (1, 16, 48)), "encoder.2.weight", None, ALL),
+    Arch("mask_head", "MaskHead", (16, 1, 4), {}, "mask", ((6, 14, 14), (10, 14, 14)), "mask_fcn3.weight", None, ALL),
+    Arch("rpn_head", "RPNHead", (16, 4), {}, "rpn", (((2, 16, 16), (2, 8, 8)), ((1, 32, 32), (1, 16, 16))), "head.weight", None, ALL),
+    Arch("box_head", "BoxHead", (16, 7, 64, 2), {}, "box", ((96,), (50,)), "fc7.weight", None, ALL),
     Arch("backbone", "ResNet50FPN", (3, 8, 16), {}, "backbone", ((2, 64, 64), (1, 128, 64)), "body.layer3.0.conv2.weight",
          "body.layer2.0.bn1.running_var", ALL),
     # every map of a depth-4 U-Net at 128 x 128 is at least 8 x 8: no 3 x bf16 record reads a dgrad layout, so the default

@@ -58,8 +58,13 @@ def test_issue_rows_run_every_event():
         ("MaskHead", (16, 1, 4)), ("RPNHead", (16, 4)), ("BoxHead", (16, 7, 64, 2)), ("ResNet50FPN", (3, 8, 16))}
     assert full["unet_f16"].shapes == ((2, 64, 64), (1, 16, 16))
     assert full["backbone"].shapes == ((2, 64, 64), (1, 128, 64))
-    assert full["rpn_head"].shapes == (((2, 16, 16), (2, 8, 8)),)
+    assert full["rpn_head"].shapes == (((2, 16, 16), (2, 8, 8)), ((1, 32, 32), (1, 16, 16)))
+    # every class with a prepare_shape of its own goes through the shape round trip: a second shape that changes every buffer's size
+    assert {a.id: a.shapes[1] for a in full.values() if a.id not in ("unet_f16", "backbone", "rpn_head")} == {
+        "unet_in4_f32": (1, 16, 48), "unet_f6": (1, 16, 48), "resnet18_f16": (1, 32, 32), "cnn_w64": (1, 16, 48),
+        "mask_head": (10, 14, 14), "box_head": (50,)}
     for a in full.values():
+        assert len(a.shapes) == 2, a.id
         want = set(D.EVENTS) - (set() if len(a.shapes) > 1 else {"shape_round_trip"})
         assert set(D.scripts(a)) == want, a.id
     for a in D.ARCHS:

@@ -32,6 +32,13 @@ What the scripts found when they were written (both fixed with them):
     (hipMemcpyAsync refused it with "invalid argument", which then surfaced at the next launch of the next model); the
     label staging now checks its size and raises the error listed above.
 No derived filter copy was found stale: every event x mode x network was byte-equal to its twin after these two fixes.
+
+What the shape round trip of the other rows found (fixed with them):
+  * shape_round_trip, op 5 ("fb" at 1x16x48 after a step at 2x32x32), unet_in4_f32, float32: the 20 gradients below the
+    bottleneck's second conv differed from the twin -- a stale copy.  At 32x32 no 3 x bf16 record of this model reads a dgrad
+    layout, so the forward pass left the dgrad layouts to the side stream; at 16x48 the bottleneck's maps are under 8 x 8, the
+    record list of the new shape splits its dgrad layouts, and it did so before they were rebuilt.  UNetModel::wd_split_ok now
+    splits the rebuild only while the record list is the prepared shape's.
 """
 import numpy as np
 import pytest
