@@ -166,8 +166,20 @@ int rfi_model_set_head_sigmoid(rfi_model* m, int enabled);
 /* training loss: 0 = mean BCE-with-logits + dice, the reference's (scripts/train_model.py:120-128,146; default);
  * 1 = sigmoid focal loss, mean over elements (NOT in the reference; builder-defined as
  * Lin et al. 2017 / torchvision.ops.sigmoid_focal_loss: alpha_t (1 - p_t)^gamma BCEwithLogits; alpha < 0
- * disables the alpha weighting). */
+ * disables the alpha weighting);
+ * 2 = the same BCE mean + (1/K) sum_k [1 - (2 I_k + 1) / (P_k + T_k + 1)], the dice term of every output channel k on its
+ * own (I_k = sum p t, P_k = sum p, T_k = sum t over the batch's pixels of channel k); class-bit labels only.  With one
+ * channel it is kind 0.  d/dx_{i,k} = (p - t) / (n h w K) + (1/K) p (1 - p) ((2 I_k + 1) / D_k^2 - 2 t / D_k), D_k = P_k + T_k + 1.
+ * With class-bit labels kind 0 is the reference's code on the K-channel tensor (BCE mean over all n h w K elements + ONE
+ * dice term over all of them) and kind 1 the focal mean over all of them. */
 int rfi_model_set_loss(rfi_model* m, int kind, float alpha, float gamma);
+/* what a label byte means.  RFI_LABELS_MAP (default): non-zero == RFI; the loss and the evaluation need one output channel.
+ * RFI_LABELS_CLASS_BITS: the target of output channel k is (label >> k) & 1, 1 <= out_channels <= 8, bits at and above
+ * out_channels are ignored; the label tensors keep their shape (n x h x w uint8).  U-Net models without a sigmoid head and
+ * without the ResNet encoder only.  The K-channel loss sums are taken in one pass (four double sums per class, per-block
+ * partials in a fixed order, float32 final combination): bitwise reproducible. */
+enum { RFI_LABELS_MAP = 0, RFI_LABELS_CLASS_BITS = 1 };
+int rfi_model_set_label_mode(rfi_model* m, int mode);
 /* deterministic init with torch's default distributions (kaiming-uniform(a=sqrt5) conv
  * weights/biases, BN gamma=1 beta=0, running stats 0/1) from a 64-bit seed */
 int rfi_model_init(rfi_model* m, uint64_t seed);
@@ -269,6 +281,10 @@ int rfi_model_debug_tensor(rfi_model* m, const char* name, float* host, size_t h
 int rfi_model_eval_batch(rfi_model* m, const float* x_nhwc, int x_mem, const uint8_t* labels,
                          int labels_mem, int n, int h, int w, float threshold, int64_t* tp,
                          int64_t* fp, int64_t* fn);
+/* the same for a model with class-bit labels: one forward pass, then one kernel that thresholds sigmoid(logit) of every
+ * channel and counts against the channel's label bit.  counts: out_channels x 3 on the host, (tp, fp, fn) per channel */
+int rfi_model_eval_batch_classes(rfi_model* m, const float* x_nhwc, int x_mem, const uint8_t* labels, int labels_mem, int n,
+                                 int h, int w, float threshold, int64_t* counts);
 /* rfi_model_eval_batch for n_thresholds cuts from ONE forward pass: forward in the current mode, then
  * rfi_threshold_sweep's kernel with kind LOGITS on what eval_batch thresholds (logits, or the probabilities of a
  * sigmoid-head model: sigmoid of the model's output, as evaluate_model.py:44 does), one group.  counts: K x 3. */
@@ -407,6 +423,12 @@ int rfi_tiling_table(int c, int t, const rfi_tiling* tiling, int n_units, rfi_pa
 int rfi_stitch_patches(rfi_ctx* ctx, const float* values, int values_mem, int kind, int n_planes, int c, int t,
                        const rfi_tiling* tiling, int combine, float threshold, uint8_t* flags, int flags_mem,
                        float* prob, int prob_mem);
+/* the same for patches of n_classes channel-last values (n_planes x patches_per_plane x ps x ps x n_classes): class k is
+ * stitched on its own into plane `plane * n_classes + k` of flags / prob (n_planes x n_classes x C x T).  n_classes == 1 is
+ * rfi_stitch_patches */
+int rfi_stitch_patches_classes(rfi_ctx* ctx, const float* values, int values_mem, int kind, int n_planes, int n_classes, int c,
+                               int t, const rfi_tiling* tiling, int combine, float threshold, uint8_t* flags, int flags_mem,
+                               float* prob, int prob_mem);
 /* the whole pipeline on a model with 3 input channels and 1 output channel: planes (n_planes x C x T, RFI_C128 or
  * RFI_C64, host or device) are streamed through in chunks of whole planes -- upload, gather + channel extraction
  * (rfi_preprocess_gather's kernels), EVAL-mode forward in sub-batches of `batch` patches (BatchNorm on the running
@@ -547,6 +569,13 @@ int rfi_sim_event_table(rfi_ctx* ctx, uint64_t seed, uint64_t first_sample, int 
 int rfi_sim_instances(rfi_ctx* ctx, uint64_t seed, uint64_t first_sample, int n_samples, const rfi_sim_params* params,
                       const double* power_range_dev, const rfi_sim_event* events_dev, const int32_t* component, const int32_t* count,
                       const int32_t* base, int max_instances, int class_mode, int32_t* labels, uint8_t* masks);
+/* per-family segmentation targets of the same batch (rfi_toolbox_amd.core.family_masks), class-bit labels for
+ * rfi_model_set_label_mode: bits uint8 [n_samples][T][F], bit cat - 1 set where an event of category cat (1 broadband, 2
+ * narrowband, 3 burst, 4 linear sweep, 5 quadratic sweep) flags the pixel -- the OR by category of the instance masks of
+ * every event, without forming them.  bits != 0 is mask_dev; gibbs_ringing changes nothing.  A gather over all event slots,
+ * 16 bytes stored at a time; sizes and guarantees as above. */
+int rfi_sim_family_bits(rfi_ctx* ctx, uint64_t seed, uint64_t first_sample, int n_samples, const rfi_sim_params* params,
+                        const double* power_range_dev, const rfi_sim_event* events_dev, uint8_t* bits);
 
 /* ---- input normalisation of 8-channel data (datasets/rfi_mask_dataset.py:99-156, scripts/normalize_rfi_data.py).
  *
@@ -609,7 +638,10 @@ int rfi_norm_apply(rfi_ctx* ctx, const void* src_dev, int dtype, int src_layout,
  *      are rfi_norm_gather's, with the same meaning of centre, scale and params_host (n_samples pairs); chunks, the
  *      two-slot upload and download, the eval-mode forward at the full batch and the stitch are those of
  *      rfi_model_predict_flags, and so are the workspace bound (counted with 4 complex planes per sample and 8-channel
- *      image batches) and the error for a single sample that exceeds it. ---- */
+ *      image batches) and the error for a single sample that exceeds it.  A model with class-bit labels
+ *      (rfi_model_set_label_mode) and K = 2 .. 8 output channels, a per-family flagger, is taken too: every channel is stitched on its own, as
+ *      rfi_stitch_patches_classes does, flags and prob are (n_samples, K, C, T), and the workspace bound counts K values
+ *      per patch pixel. ---- */
 int rfi_norm_gather(rfi_ctx* ctx, const void* planes, int planes_mem, int dtype, int n_samples, int c, int t,
                     const rfi_patch_src* table_host, int n, int ps, double centre, double scale,
                     const double (*params_host)[2], float* out_nhwc, int out_mem);

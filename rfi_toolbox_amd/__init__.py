@@ -12,12 +12,14 @@ __version__ = "0.1.0"
 def __getattr__(name):
     import importlib
     if name in ("models", "evaluation", "preprocessing", "datasets", "training", "distributed", "runtime",
-                "data_generation", "core", "inference", "flagging", "components"):
+                "data_generation", "core", "inference", "flagging", "components", "class_labels"):
         return importlib.import_module(f"{__name__}.{name}")
     if name in ("label_components", "component_table", "remove_small_components", "instances_from_masks", "InstanceTargets"):
         return getattr(importlib.import_module(f"{__name__}.components"), name)
-    if name in ("event_instances", "event_table", "EVENT_CLASSES"):
+    if name in ("event_instances", "event_table", "family_masks", "EVENT_CLASSES"):
         return getattr(importlib.import_module(f"{__name__}.core"), name)
+    if name in ("pack_class_masks", "unpack_class_bits"):
+        return getattr(importlib.import_module(f"{__name__}.class_labels"), name)
     if name in ("stitch_instances", "detect_observation"):
         return getattr(importlib.import_module(f"{__name__}.inference"), name)
     raise AttributeError(name)

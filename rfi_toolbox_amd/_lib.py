@@ -142,6 +142,7 @@ _PROTOS = {
     "rfi_model_set_compute_dtype": (_i, [_vp, _i]),
     "rfi_model_set_head_sigmoid": (_i, [_vp, _i]),
     "rfi_model_set_loss": (_i, [_vp, _i, _f, _f]),
+    "rfi_model_set_label_mode": (_i, [_vp, _i]),
     "rfi_model_destroy": (_i, [_vp]),
     "rfi_model_init": (_i, [_vp, C.c_uint64]),
     "rfi_model_entry_count": (_i, [_vp, _pi]),
@@ -165,6 +166,7 @@ _PROTOS = {
     "rfi_model_load_adam": (_i, [_vp, _cp, _vp, _vp, _sz]),
     "rfi_model_set_adam_step": (_i, [_vp, _i64]),
     "rfi_model_eval_batch": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _f, _pi64, _pi64, _pi64]),
+    "rfi_model_eval_batch_classes": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _f, _vp]),
     "rfi_model_eval_sweep": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "rfi_model_algorithmic_flops": (_i, [_vp, _i, _i, _i, _pd, _pd]),
     "rfi_model_debug_tensor": (_i, [_vp, _cp, _vp, _sz, _pi64]),
@@ -220,10 +222,12 @@ _PROTOS = {
     "rfi_tiling_count": (_i, [_i, _i, C.POINTER(Tiling), _pi64]),
     "rfi_tiling_table": (_i, [_i, _i, C.POINTER(Tiling), _i, _vp, _i64]),
     "rfi_stitch_patches": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(Tiling), _i, _f, _vp, _i, _vp, _i]),
+    "rfi_stitch_patches_classes": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(Tiling), _i, _f, _vp, _i, _vp, _i]),
     "rfi_model_predict_flags": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(Tiling), _i, _i, _f, _vp, _i, _vp, _i]),
     "rfi_simulate_rfi": (_i, [_vp, C.c_uint64, C.c_uint64, _i, C.POINTER(SimParams), _vp, _i, _vp, _vp, _vp, _vp]),
     "rfi_sim_event_table": (_i, [_vp, C.c_uint64, C.c_uint64, _i, C.POINTER(SimParams), _vp, _vp, _vp, _vp]),
     "rfi_sim_instances": (_i, [_vp, C.c_uint64, C.c_uint64, _i, C.POINTER(SimParams), _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "rfi_sim_family_bits": (_i, [_vp, C.c_uint64, C.c_uint64, _i, C.POINTER(SimParams), _vp, _vp, _vp]),
     "rfi_flag_statistics": (_i, [_vp, _vp, _i, _i, _i64, _vp, _i, _i, _i, C.POINTER(FlagStats), C.POINTER(FlagStats)]),
     "rfi_norm_bracket": (_i, [_i64, C.c_double, _pi64, _pd]),
     "rfi_norm_statistics": (_i, [_vp, _pvp, _pi64, _i, _i, _i64, _i, C.POINTER(NormStats), _i]),

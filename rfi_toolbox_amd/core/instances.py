@@ -65,6 +65,24 @@ def event_table(batch):
     return _table(batch, n, S)
 
 
+def family_masks(batch):
+    """Per-family segmentation targets straight from the generator -> ``DeviceArray`` (n, T, F) uint8 on the batch's GPU:
+    bit ``c - 1`` is set where an event of ``EVENT_CLASSES[c]`` (c = 1 .. 5) flags the pixel.  These are class-bit labels
+    for ``UNet(8, 5, ...).set_targets("class_bits")``; ``bits != 0`` is ``batch.mask``, a pixel several families flag
+    carries all their bits, and ``gibbs_ringing`` changes nothing.  One kernel (``rfi_sim_family_bits``): no instance
+    mask is formed.  A clean batch has no events and gives zeros (a fill), an empty one nothing at all."""
+    n, T, F, _ = _origin(batch)
+    ctx = batch.mask.ctx
+    bits = ctx.empty((n, T, F), np.uint8)
+    if batch.events is None or n == 0:
+        if n:
+            bits.zero_()
+        return bits
+    from .._lib import check, lib
+    check(lib.rfi_sim_family_bits(*_sim_args(batch), C.c_void_p(bits.ptr)))
+    return bits
+
+
 def event_instances(batch, min_area=1, min_side=1, max_instances=64, classes="family", instance_masks=True):
     """Instance targets for the detector straight from the generator: every event of ``batch`` that flags at least
     ``min_area`` pixels and whose box has both sides >= ``min_side`` is one instance; at most ``max_instances`` (1 .. 256)

@@ -457,16 +457,34 @@ int rfi_model_set_compute_dtype(rfi_model* m, int dtype) {
 }
 int rfi_model_set_loss(rfi_model* m, int kind, float alpha, float gamma) {
     return guarded([&] {
-        RFI_REQUIRE(kind == 0 || kind == 1, "set_loss: 0 (BCE-with-logits + dice) or 1 (sigmoid focal loss)");
-        RFI_REQUIRE(kind == 0 || (gamma >= 0.0f && alpha <= 1.0f), "set_loss: focal needs gamma >= 0 and alpha <= 1");
+        RFI_REQUIRE(kind >= 0 && kind <= 2,
+                    "set_loss: 0 (BCE-with-logits + dice), 1 (sigmoid focal loss) or 2 (BCE-with-logits + per-class dice)");
+        RFI_REQUIRE(kind != 1 || (gamma >= 0.0f && alpha <= 1.0f), "set_loss: focal needs gamma >= 0 and alpha <= 1");
+        RFI_REQUIRE(kind != 2 || m->label_mode == RFI_LABELS_CLASS_BITS,
+                    "set_loss: the per-class dice term needs class-bit labels (rfi_model_set_label_mode first)");
         m->loss_kind = kind;
         m->focal_alpha = alpha;
         m->focal_gamma = gamma;
     });
 }
+int rfi_model_set_label_mode(rfi_model* m, int mode) {
+    return guarded([&] {
+        RFI_REQUIRE(mode == RFI_LABELS_MAP || mode == RFI_LABELS_CLASS_BITS, "set_label_mode: RFI_LABELS_MAP or RFI_LABELS_CLASS_BITS");
+        if (mode == RFI_LABELS_CLASS_BITS) {
+            RFI_REQUIRE(plain_unet(m) && !m->head_sigmoid,
+                        "set_label_mode: class-bit labels are for UNet, UNetBigger and UNetDifferentActivation (not the sigmoid-head, "
+                        "ResNet-encoder or SimpleCNN models)");
+            RFI_REQUIRE(m->out_ch >= 1 && m->out_ch <= 8, "set_label_mode: class-bit labels need 1 <= out_channels <= 8");
+        } else if (m->loss_kind == 2) {
+            m->loss_kind = 0;         // (the per-class dice term of one class is the reference's loss)
+        }
+        m->label_mode = mode;
+    });
+}
 int rfi_model_set_head_sigmoid(rfi_model* m, int enabled) {
     return guarded([&] {
         RFI_REQUIRE(plain_unet(m), "set_head_sigmoid: U-Net models only");
+        RFI_REQUIRE(!enabled || m->label_mode == RFI_LABELS_MAP, "set_head_sigmoid: not with class-bit labels");
         m->head_sigmoid = enabled != 0;
     });
 }
@@ -709,6 +727,7 @@ int rfi_model_eval_batch(rfi_model* m, const float* x, int x_mem, const uint8_t*
                          int h, int w, float threshold, int64_t* tp, int64_t* fp, int64_t* fn) {
     return guarded([&] {
         RFI_REQUIRE(m->out_ch == 1, "eval_batch: defined for out_channels == 1");
+        RFI_REQUIRE(m->label_mode == RFI_LABELS_MAP, "eval_batch: class-bit labels are counted by rfi_model_eval_batch_classes");
         m->ctx->activate();
         m->prepare(n, h, w);
         const float* xd = stage_input(m, x, x_mem, n, h, w, false);
@@ -727,10 +746,30 @@ int rfi_model_eval_batch(rfi_model* m, const float* x, int x_mem, const uint8_t*
     });
 }
 
+int rfi_model_eval_batch_classes(rfi_model* m, const float* x, int x_mem, const uint8_t* labels, int labels_mem, int n, int h,
+                                 int w, float threshold, int64_t* counts) {
+    return guarded([&] {
+        RFI_REQUIRE(m->label_mode == RFI_LABELS_CLASS_BITS, "eval_batch_classes: the model's labels are not class bits");
+        RFI_REQUIRE(counts, "eval_batch_classes: null argument");
+        m->ctx->activate();
+        m->prepare(n, h, w);
+        const float* xd = stage_input(m, x, x_mem, n, h, w, false);
+        const uint8_t* yd = stage_labels(m, labels, labels_mem, n, h, w);
+        m->forward(xd, n, h, w, m->training);
+        const int K = m->out_ch;
+        CallScope sc(m->ctx);
+        auto* ws = sc.temp<unsigned long long>(class_confusion_ws_words(K));
+        static_assert(sizeof(unsigned long long) == sizeof(int64_t), "counts are copied as they are");
+        auto* out = reinterpret_cast<unsigned long long*>(sc.out(counts, RFI_HOST, (size_t)K * 3));
+        launch_class_confusion(m->ctx, m->buf(m->logits), yd, (int64_t)n * h * w, K, threshold, ws, out);
+        sc.finish();
+    });
+}
+
 int rfi_model_eval_sweep(rfi_model* m, const float* x, int x_mem, const uint8_t* labels, int labels_mem, int n, int h,
                          int w, const float* thresholds_host, int n_thresholds, int64_t* counts_host) {
     return guarded([&] {
-        RFI_REQUIRE(m->out_ch == 1, "eval_sweep: defined for out_channels == 1");
+        RFI_REQUIRE(m->out_ch == 1 && m->label_mode == RFI_LABELS_MAP, "eval_sweep: defined for out_channels == 1 and label maps");
         RFI_REQUIRE(thresholds_host && counts_host, "eval_sweep: null argument");
         check_sweep_thresholds(thresholds_host, n_thresholds);
         m->ctx->activate();
@@ -1262,6 +1301,17 @@ int rfi_sim_instances(rfi_ctx* ctx, uint64_t seed, uint64_t first_sample, int n_
                                  base, max_instances, class_mode, labels, masks);
     });
 }
+int rfi_sim_family_bits(rfi_ctx* ctx, uint64_t seed, uint64_t first_sample, int n_samples, const rfi_sim_params* params,
+                        const double* power_range_dev, const rfi_sim_event* events_dev, uint8_t* bits) {
+    return guarded([&] {
+        RFI_REQUIRE(ctx && params, "sim_family_bits: null argument");
+        require_sim_events_batch("sim_family_bits", *params, first_sample, n_samples);
+        RFI_REQUIRE(power_range_dev && events_dev && bits, "sim_family_bits: null buffer");
+        if (n_samples == 0) return;
+        ctx->activate();
+        launch_rfi_sim_family_bits(ctx, seed, (unsigned)first_sample, n_samples, *params, power_range_dev, events_dev, bits);
+    });
+}
 namespace {
 void norm_bracket(int64_t count, double q, int64_t* ranks, double* frac) {
     const double v = q * (double)(count - 1), f = std::floor(v);
@@ -1392,19 +1442,25 @@ int rfi_tiling_table(int c, int t, const rfi_tiling* tiling, int n_units, rfi_pa
 int rfi_stitch_patches(rfi_ctx* ctx, const float* values, int values_mem, int kind, int n_planes, int c, int t,
                        const rfi_tiling* tiling, int combine, float threshold, uint8_t* flags, int flags_mem,
                        float* prob, int prob_mem) {
+    return rfi_stitch_patches_classes(ctx, values, values_mem, kind, n_planes, 1, c, t, tiling, combine, threshold, flags, flags_mem,
+                                      prob, prob_mem);
+}
+int rfi_stitch_patches_classes(rfi_ctx* ctx, const float* values, int values_mem, int kind, int n_planes, int n_classes, int c,
+                               int t, const rfi_tiling* tiling, int combine, float threshold, uint8_t* flags, int flags_mem,
+                               float* prob, int prob_mem) {
     return guarded([&] {
         RFI_REQUIRE(ctx && values && flags && tiling, "stitch_patches: null argument");
-        RFI_REQUIRE(n_planes >= 0 && c > 0 && t > 0, "stitch_patches: bad shape");
+        RFI_REQUIRE(n_planes >= 0 && n_classes > 0 && c > 0 && t > 0, "stitch_patches: bad shape");
         check_tiling(*tiling);
         if (n_planes == 0) return;
         ctx->activate();
         const int64_t ppp = tiling_patches_per_plane(c, t, *tiling);
-        const size_t px = (size_t)n_planes * c * t;
+        const size_t px = (size_t)n_planes * n_classes * c * t;
         CallScope sc(ctx);
-        const float* v = sc.in(values, values_mem, (size_t)n_planes * ppp * tiling->ps * tiling->ps);
+        const float* v = sc.in(values, values_mem, (size_t)n_planes * ppp * tiling->ps * tiling->ps * n_classes);
         uint8_t* df = sc.out(flags, flags_mem, px);
         float* dp = sc.out(prob, prob_mem, px);
-        launch_stitch(ctx, v, kind, n_planes, c, t, *tiling, combine, threshold, df, dp);
+        launch_stitch(ctx, v, kind, n_planes, c, t, *tiling, combine, threshold, df, dp, n_classes);
         sc.finish();
         RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));     // (with device pointers only too)
     });
@@ -1426,6 +1482,7 @@ struct PredictGather {
     const char* unit;          // "plane" or "sample"
     int in_ch;                 // channels of the image batch
     int pols;                  // complex planes per unit
+    int max_out = 1;           // output channels a model may have: each is stitched into a plane of its own
     // private device workspace for image batches of nb patches out of n_units units, filled once by setup()
     virtual size_t ws_bytes(int nb, int n_units) const = 0;
     virtual void setup(rfi_ctx*, void*, int) {}
@@ -1448,7 +1505,7 @@ struct PolGather final : PredictGather {            // the four polarisations, n
     double centre, scale;
     const double* params_host;                      // one pair per unit, or null
     PolGather(double ce, double sc, const double* ph) : centre(ce), scale(sc), params_host(ph) {
-        who = "predict_flags_pol"; unit = "sample"; in_ch = 8; pols = 4;
+        who = "predict_flags_pol"; unit = "sample"; in_ch = 8; pols = 4; max_out = 8;
     }
     size_t ws_bytes(int, int n_units) const override { return params_host ? (size_t)n_units * 2 * sizeof(double) : 0; }
     void setup(rfi_ctx* ctx, void* ws, int n_units) override {
@@ -1470,9 +1527,12 @@ void predict_flags_driver(rfi_model* m, PredictGather& g, const void* planes, in
     RFI_REQUIRE(dtype == RFI_C128 || dtype == RFI_C64,
                 who + ": planes must be complex128 or complex64 (real input: Preprocessor + rfi_stitch_patches)");
     RFI_REQUIRE(n_planes >= 0 && c > 0 && t > 0 && batch > 0, who + ": bad shape or batch");
-    RFI_REQUIRE(m->in_ch == g.in_ch && m->out_ch == 1 && m->out_scale == 1,
-                who + ": needs a model with " + std::to_string(g.in_ch) +
-                    " input channels, 1 output channel and an output map the size of its input");
+    // (several output channels: those of a model with class-bit labels, each a class of its own)
+    const bool by_class = g.max_out > 1 && m->label_mode == RFI_LABELS_CLASS_BITS;
+    RFI_REQUIRE(m->in_ch == g.in_ch && m->out_ch >= 1 && m->out_ch <= (by_class ? g.max_out : 1) && m->out_scale == 1,
+                who + ": needs a model with " + std::to_string(g.in_ch) + " input channels, 1 output channel" +
+                    (g.max_out > 1 ? " (class-bit labels: up to " + std::to_string(g.max_out) + ")" : std::string()) +
+                    " and an output map the size of its input");
     RFI_REQUIRE(combine == RFI_COMBINE_MEAN || combine == RFI_COMBINE_MAX, who + ": combine must be mean (0) or max (1)");
     check_tiling(*tiling);
     if (n_planes == 0) return;
@@ -1482,11 +1542,13 @@ void predict_flags_driver(rfi_model* m, PredictGather& g, const void* planes, in
     const int64_t ppp = tiling_patches_per_plane(c, t, *tiling);
     const size_t esz = dtype_bytes(dtype);
     // plane_px: pixels of a stitched plane; plane_bytes: the input behind it
-    const size_t plane_px = (size_t)c * t, plane_bytes = plane_px * esz * g.pols, patch_px = (size_t)ps * ps;
+    // K output channels: patch outputs are channel-last and every unit has K stitched planes (K = 1: the plane itself)
+    const size_t K = (size_t)m->out_ch;
+    const size_t plane_px = (size_t)c * t, plane_bytes = plane_px * esz * g.pols, patch_px = (size_t)ps * ps, out_px = plane_px * K;
     const bool host_in = planes_mem == RFI_HOST, host_fl = flags_mem == RFI_HOST, host_pr = prob && prob_mem == RFI_HOST;
     const size_t out_px_bytes = (host_fl ? 1 : 0) + (host_pr ? 4 : 0);
-    const size_t per_plane = (size_t)ppp * (patch_px * sizeof(float) + sizeof(rfi_patch_src)) +
-                             (host_in ? 2 * plane_bytes : 0) + 2 * plane_px * out_px_bytes;
+    const size_t per_plane = (size_t)ppp * (patch_px * K * sizeof(float) + sizeof(rfi_patch_src)) +
+                             (host_in ? 2 * plane_bytes : 0) + 2 * out_px * out_px_bytes;
     RFI_REQUIRE(per_plane <= kPredictBudget,
                 who + ": one " + (g.pols > 1 ? std::to_string(g.pols) + " x " : std::string()) + std::to_string(c) + " x " +
                     std::to_string(t) + " " + g.unit + " needs " +
@@ -1515,9 +1577,9 @@ void predict_flags_driver(rfi_model* m, PredictGather& g, const void* planes, in
 
     // one grow-only scratch region: [table | the gather's own | images | patch outputs | 2 plane slots | 2 output slots]
     const size_t b_table = al(table.size() * sizeof(rfi_patch_src)), b_gws = al(g.ws_bytes(nb, n_planes));
-    const size_t b_img = al((size_t)nb * patch_px * g.in_ch * sizeof(float)), b_out = al((size_t)chunk_patches * patch_px * sizeof(float));
+    const size_t b_img = al((size_t)nb * patch_px * g.in_ch * sizeof(float)), b_out = al((size_t)chunk_patches * patch_px * K * sizeof(float));
     const size_t b_in = host_in ? al((size_t)k * plane_bytes) : 0;
-    const size_t b_fl = host_fl ? al((size_t)k * plane_px) : 0, b_pr = host_pr ? al((size_t)k * plane_px * sizeof(float)) : 0;
+    const size_t b_fl = host_fl ? al((size_t)k * out_px) : 0, b_pr = host_pr ? al((size_t)k * out_px * sizeof(float)) : 0;
     char* base = static_cast<char*>(ctx->get_scratch(b_table + b_gws + b_img + b_out + 2 * (b_in + b_fl + b_pr)));
     auto* d_table = reinterpret_cast<rfi_patch_src*>(base);
     void* d_gws = base + b_table;
@@ -1548,7 +1610,7 @@ void predict_flags_driver(rfi_model* m, PredictGather& g, const void* planes, in
     };
     auto download = [&](int ci) {
         const int s = ci & 1;
-        const size_t px = (size_t)planes_in(ci) * plane_px, off = (size_t)ci * k * plane_px;
+        const size_t px = (size_t)planes_in(ci) * out_px, off = (size_t)ci * k * out_px;
         RFI_CHECK_HIP(hipStreamWaitEvent(cs.s, ev.e[4 + s], 0));
         OnStream on(ctx, cs.s);
         ProfScope pf(ctx, FAM_PREPROCESS, 0, (double)px * out_px_bytes, "predict_download");
@@ -1567,12 +1629,12 @@ void predict_flags_driver(rfi_model* m, PredictGather& g, const void* planes, in
             g.run(ctx, pl, dtype, ci * k, c, t, d_table + p0, nv, ps, d_gws, d_img);
             if (p0 + nb >= npatch) RFI_CHECK_HIP(hipEventRecord(ev.e[2 + s], ctx->stream));
             m->forward(d_img, nb, ps, ps, false);
-            launch_copy_d2d(ctx, d_out + p0 * patch_px, m->buf(m->head_sigmoid ? m->probs : m->logits),
-                            (size_t)nv * patch_px * sizeof(float));
+            launch_copy_d2d(ctx, d_out + p0 * patch_px * K, m->buf(m->head_sigmoid ? m->probs : m->logits),
+                            (size_t)nv * patch_px * K * sizeof(float));
         }
-        const size_t off = (size_t)ci * k * plane_px;
+        const size_t off = (size_t)ci * k * out_px;
         launch_stitch(ctx, d_out, kind, np, c, t, *tiling, combine, threshold, host_fl ? fl_slot(s) : flags + off,
-                      prob ? (host_pr ? pr_slot(s) : prob + off) : nullptr);
+                      prob ? (host_pr ? pr_slot(s) : prob + off) : nullptr, (int)K);
         RFI_CHECK_HIP(hipEventRecord(ev.e[4 + s], ctx->stream));
     };
     if (host_in) upload(0);

@@ -993,34 +993,185 @@ __global__ void focal_finish_kernel(const double* __restrict__ partial, int bloc
         loss_out[0] = (float)(t / count);
     }
 }
-// d FL / d x (closed form), times 1/N
+// d FL / d x of one element (closed form)
+__device__ __forceinline__ double focal_grad(float x, bool pos, float alpha, float gamma) {
+    // p and q = 1 - p from one exp, neither by subtraction from 1: with q = 1.0f - p the term gamma q softplus(x) of a
+    // background pixel is off by gamma x 2^-24 (q is 0 from x = 17 on, where the term is still 6e-7 at gamma = 0.5).
+    // The three library calls stay float32; the few products and sums around them are formed in double and rounded
+    // once, which keeps a pixel within about 2 x 2^-24 of the largest gradient
+    const float e = expf(-fabsf(x));
+    const double l1p = (double)log1pf(e);
+    const double big = 1.0 / (1.0 + (double)e), small = (double)e * big;      // sigmoid(|x|), sigmoid(-|x|)
+    const double p = x >= 0.0f ? big : small, q = x >= 0.0f ? small : big;
+    // log p and log(1-p) without cancellation: -softplus(-x), -softplus(x)
+    const double sp_neg = (double)fmaxf(-x, 0.0f) + l1p;     // softplus(-x) = -log p
+    const double sp_pos = (double)fmaxf(x, 0.0f) + l1p;      // softplus(x)  = -log(1-p)
+    if (pos) {       // FL = -a (1-p)^g log p
+        const double a = alpha >= 0.0f ? alpha : 1.0f;
+        return a * (double)powf((float)q, gamma) * ((double)gamma * p * (-sp_neg) - q);
+    }
+    // FL = -(1-a) p^g log(1-p)
+    const double a = alpha >= 0.0f ? 1.0 - (double)alpha : 1.0;
+    return a * (double)powf((float)p, gamma) * (p + (double)gamma * q * sp_pos);
+}
+// times 1/N
 __global__ void focal_bwd_kernel(const float* __restrict__ logits, const uint8_t* __restrict__ labels, int64_t count,
                                  float alpha, float gamma, float* __restrict__ dlogits) {
     const double n = (double)count;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) {
-        const float x = logits[i];
-        const bool pos = labels[i] != 0;
-        // p and q = 1 - p from one exp, neither by subtraction from 1: with q = 1.0f - p the term gamma q softplus(x) of a
-        // background pixel is off by gamma x 2^-24 (q is 0 from x = 17 on, where the term is still 6e-7 at gamma = 0.5).
-        // The three library calls stay float32; the few products and sums around them are formed in double and rounded
-        // once, which keeps a pixel within about 2 x 2^-24 of the largest gradient
-        const float e = expf(-fabsf(x));
-        const double l1p = (double)log1pf(e);
-        const double big = 1.0 / (1.0 + (double)e), small = (double)e * big;      // sigmoid(|x|), sigmoid(-|x|)
-        const double p = x >= 0.0f ? big : small, q = x >= 0.0f ? small : big;
-        // log p and log(1-p) without cancellation: -softplus(-x), -softplus(x)
-        const double sp_neg = (double)fmaxf(-x, 0.0f) + l1p;     // softplus(-x) = -log p
-        const double sp_pos = (double)fmaxf(x, 0.0f) + l1p;      // softplus(x)  = -log(1-p)
-        double g;
-        if (pos) {       // FL = -a (1-p)^g log p
-            const double a = alpha >= 0.0f ? alpha : 1.0f;
-            g = a * (double)powf((float)q, gamma) * ((double)gamma * p * (-sp_neg) - q);
-        } else {         // FL = -(1-a) p^g log(1-p)
-            const double a = alpha >= 0.0f ? 1.0 - (double)alpha : 1.0;
-            g = a * (double)powf((float)p, gamma) * (p + (double)gamma * q * sp_pos);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x)
+        dlogits[i] = (float)(focal_grad(logits[i], labels[i] != 0, alpha, gamma) / n);
+}
+
+// ---- class-bit labels (include/rfi_hip.h, RFI_LABELS_CLASS_BITS): logits [pixels][K] channel-last, K <= kMaxClasses, one
+// label byte per pixel whose bit k is the target of channel k.  A block works with A = (kBlock / K) * K threads, so the
+// element a thread visits (block * A + tid + trip * grid * A) keeps the class tid % K on every trip: four double sums
+// per thread serve all classes.  kind: 0 pooled BCE + dice, 1 focal, 2 BCE + mean per-class dice
+constexpr int kMaxClasses = 8;
+
+__global__ __launch_bounds__(kBlock) void class_loss_reduce_kernel(const float* __restrict__ logits, const uint8_t* __restrict__ labels,
+                                                                   int64_t count, int K, int kind, float alpha, float gamma,
+                                                                   double* __restrict__ partial) {
+    __shared__ double red[4][kBlock];
+    const int A = (kBlock / K) * K, k = threadIdx.x % K;
+    double s[4] = {0, 0, 0, 0};
+    if ((int)threadIdx.x < A) {
+        for (int64_t i = (int64_t)blockIdx.x * A + threadIdx.x; i < count; i += (int64_t)gridDim.x * A) {
+            const float x = logits[i];
+            const float t = (float)((labels[i / K] >> k) & 1);
+            if (kind == 1) {
+                s[0] += (double)focal_elem(x, t, alpha, gamma);
+                continue;
+            }
+            const float bce = fmaxf(x, 0.0f) - x * t + log1pf(expf(-fabsf(x)));
+            const float p = sigmoidf_(x);
+            s[0] += (double)bce;
+            s[1] += (double)(p * t);
+            s[2] += (double)p;
+            s[3] += (double)t;
         }
-        dlogits[i] = (float)(g / n);
     }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) red[q][threadIdx.x] = s[q];
+    __syncthreads();
+    // thread (q, class): the threads of that class, in thread order
+    if ((int)threadIdx.x < 4 * K) {
+        const int q = threadIdx.x / K, c = threadIdx.x % K;
+        double v = 0;
+        for (int j = c; j < A; j += K) v += red[q][j];
+        partial[(int64_t)blockIdx.x * 4 * K + threadIdx.x] = v;
+    }
+}
+
+// sums: 4 x kMaxClasses doubles, [q * kMaxClasses + class]
+__global__ __launch_bounds__(kBlock) void class_loss_finish_kernel(const double* __restrict__ partial, int blocks, double count, int K,
+                                                                   int kind, double* __restrict__ sums, float* __restrict__ loss_out) {
+    constexpr int G = kBlock / (4 * kMaxClasses);         // block lanes per sum
+    __shared__ double red[G][4 * kMaxClasses];
+    const int o = threadIdx.x % (4 * kMaxClasses), g = threadIdx.x / (4 * kMaxClasses);
+    double v = 0;
+    if (o < 4 * K)
+        for (int b = g; b < blocks; b += G) v += partial[(int64_t)b * 4 * K + o];
+    red[g][o] = v;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double t[4][kMaxClasses], all[4] = {0, 0, 0, 0};
+    for (int q = 0; q < 4; ++q)
+        for (int c = 0; c < K; ++c) {
+            double a = 0;
+            for (int j = 0; j < G; ++j) a += red[j][q * K + c];
+            t[q][c] = a;
+            all[q] += a;
+            sums[q * kMaxClasses + c] = a;
+        }
+    if (kind == 1) {
+        loss_out[0] = (float)(all[0] / count);
+        return;
+    }
+    // float32 arithmetic for the final combination, as loss_finish_kernel
+    const float bce = (float)(all[0] / count);
+    float dice;
+    if (kind == 0) {
+        const float inter = (float)all[1], sp = (float)all[2], st = (float)all[3];
+        dice = 1.0f - (2.0f * inter + 1.0f) / (sp + st + 1.0f);
+    } else {
+        dice = 0.0f;
+        for (int c = 0; c < K; ++c) {
+            const float inter = (float)t[1][c], sp = (float)t[2][c], st = (float)t[3][c];
+            dice += 1.0f - (2.0f * inter + 1.0f) / (sp + st + 1.0f);
+        }
+        dice /= (float)K;
+    }
+    loss_out[0] = bce + dice;
+}
+
+__global__ __launch_bounds__(kBlock) void class_loss_bwd_kernel(const float* __restrict__ logits, const uint8_t* __restrict__ labels,
+                                                                int64_t count, int K, int kind, float alpha, float gamma,
+                                                                const double* __restrict__ sums, float* __restrict__ dlogits) {
+    const int A = (kBlock / K) * K, k = threadIdx.x % K;
+    if ((int)threadIdx.x >= A) return;
+    if (kind == 1) {
+        const double n = (double)count;
+        for (int64_t i = (int64_t)blockIdx.x * A + threadIdx.x; i < count; i += (int64_t)gridDim.x * A)
+            dlogits[i] = (float)(focal_grad(logits[i], (labels[i / K] >> k) & 1, alpha, gamma) / n);
+        return;
+    }
+    // the dice term this thread's class belongs to: the pooled one (sums over the classes, in class order) or its own
+    double s3[3];
+    for (int q = 1; q < 4; ++q) {
+        double a = 0;
+        if (kind == 0) for (int c = 0; c < K; ++c) a += sums[q * kMaxClasses + c];
+        else a = sums[q * kMaxClasses + k];
+        s3[q - 1] = a;
+    }
+    const float inter = (float)s3[0], sp = (float)s3[1], st = (float)s3[2];
+    const float D = sp + st + 1.0f;
+    const float num = 2.0f * inter + 1.0f;
+    const float invD2 = 1.0f / (D * D);
+    const float invN = (float)(1.0 / (double)count);
+    const float wdice = kind == 0 ? 1.0f : 1.0f / (float)K;
+    for (int64_t i = (int64_t)blockIdx.x * A + threadIdx.x; i < count; i += (int64_t)gridDim.x * A) {
+        const float x = logits[i];
+        const float t = (float)((labels[i / K] >> k) & 1);
+        const float p = sigmoidf_(x);
+        // d dice / d p_i = -(2 t D - num) / D^2, as loss_bwd_kernel
+        const float ddice = -(2.0f * t * D - num) * invD2 * wdice;
+        dlogits[i] = (p - t) * invN + ddice * p * (1.0f - p);
+    }
+}
+
+// (tp, fp, fn) per class of sigmoid(logit) > thr against the class bits: exact integers.  partial: blocks x 3 x K
+__global__ __launch_bounds__(kBlock) void class_confusion_kernel(const float* __restrict__ logits, const uint8_t* __restrict__ labels,
+                                                                 int64_t count, int K, float thr, unsigned long long* __restrict__ partial) {
+    __shared__ unsigned red[3][kBlock];
+    const int A = (kBlock / K) * K, k = threadIdx.x % K;
+    unsigned s[3] = {0, 0, 0};
+    if ((int)threadIdx.x < A) {
+        for (int64_t i = (int64_t)blockIdx.x * A + threadIdx.x; i < count; i += (int64_t)gridDim.x * A) {
+            const bool p = (1.0f / (1.0f + expf(-logits[i]))) > thr;      // (threshold_kernel's expression)
+            const bool t = (labels[i / K] >> k) & 1;
+            s[0] += (p && t);
+            s[1] += (p && !t);
+            s[2] += (!p && t);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 3; ++q) red[q][threadIdx.x] = s[q];
+    __syncthreads();
+    if ((int)threadIdx.x < 3 * K) {
+        const int q = threadIdx.x / K, c = threadIdx.x % K;
+        unsigned long long v = 0;
+        for (int j = c; j < A; j += K) v += red[q][j];
+        partial[(int64_t)blockIdx.x * 3 * K + threadIdx.x] = v;
+    }
+}
+// counts: K x 3, [class][tp, fp, fn]
+__global__ void class_confusion_finish_kernel(const unsigned long long* __restrict__ partial, int blocks, int K,
+                                              unsigned long long* __restrict__ counts) {
+    const int o = threadIdx.x;
+    if (o >= 3 * K) return;
+    unsigned long long v = 0;
+    for (int b = 0; b < blocks; ++b) v += partial[(int64_t)b * 3 * K + o];
+    counts[(o % K) * 3 + o / K] = v;
 }
 
 // UNetOverfit's head (models/unet.py:196): the model RETURNS sigmoid(logits), and train_model.py:120 still
@@ -1097,7 +1248,8 @@ __global__ __launch_bounds__(256) void head_bwd_vec_kernel(const void* __restric
                                                            int store_da) {
     // store_da == 0 (Cout == 1, bn_records != null): da is not written -- bn_bwd_apply's head form recomputes d * w from
     // the logit gradients (1 float per pixel) instead of reading C floats per pixel back
-    // da16 != null (Cout == 1): da is stored as bfloat16 there and the BatchNorm-backward sums are those of the stored values
+    // da16 != null: da is stored as bfloat16 there (Cout > 1: the float32 da holds the running sum over the outputs and the
+    // last output's pass rounds it) and the BatchNorm-backward sums (Cout == 1) are those of the stored values
     // bn_records != null (Cout == 1): also the BatchNorm-backward sums of the layer below (sum dz, sum dz * xhat with
     // dz = da * act'), one fp64 record per row block -- bn_bwd_reduce's pass over da and y disappears
     __shared__ double red[4 * kBlock];
@@ -1142,7 +1294,7 @@ __global__ __launch_bounds__(256) void head_bwd_vec_kernel(const void* __restric
                     sw[v] += (double)d * (double)a;
                     g[v] = o == 0 ? d * wv[v] : g[v] + d * wv[v];
                 }
-                if (da16) round_store_bf16x4(da16 + r * C + c, g);
+                if (da16 && o == Cout - 1) round_store_bf16x4(da16 + r * C + c, g);
                 else if (store_da) stv<4>(da + r * C + c, g);
                 if (bn_records) {
 #pragma unroll
@@ -1770,6 +1922,56 @@ void launch_loss_bwd(rfi_ctx* ctx, const float* logits, const uint8_t* labels, i
     check_launch("loss_bwd");
 }
 
+// class-bit labels: count = pixels * K elements
+static int class_grid(int64_t count, int K, int cap) {
+    int64_t b = cdiv(count, (int64_t)(kBlock / K) * K);
+    return (int)std::max<int64_t>(1, std::min<int64_t>(b, cap));
+}
+static void check_classes(int K) {
+    RFI_REQUIRE(K >= 1 && K <= kMaxClasses, "class-bit labels: 1 <= out_channels <= 8 (one bit of the label byte per channel)");
+}
+size_t class_loss_ws_doubles(int K) { return (size_t)4 * std::min(std::max(K, 1), kMaxClasses) * 1024 + 8; }
+void launch_class_loss_reduce(rfi_ctx* ctx, const float* logits, const uint8_t* labels, int64_t pixels, int K, int kind,
+                              float alpha, float gamma, double* partial_ws, double* sums, float* loss_out) {
+    check_classes(K);
+    const int64_t count = pixels * K;
+    const int blocks = class_grid(count, K, 1024);
+    {
+        ProfScope ps(ctx, FAM_ELEMWISE, 0, (double)count * 4 + (double)pixels);
+        hipLaunchKernelGGL(class_loss_reduce_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, logits, labels, count, K, kind,
+                           alpha, gamma, partial_ws);
+        check_launch("class_loss_reduce");
+    }
+    {
+        ProfScope ps(ctx, FAM_ELEMWISE);
+        hipLaunchKernelGGL(class_loss_finish_kernel, dim3(1), dim3(kBlock), 0, ctx->stream, partial_ws, blocks, (double)count, K,
+                           kind, sums, loss_out);
+        check_launch("class_loss_finish");
+    }
+}
+void launch_class_loss_bwd(rfi_ctx* ctx, const float* logits, const uint8_t* labels, int64_t pixels, int K, int kind, float alpha,
+                           float gamma, const double* sums, float* dlogits) {
+    check_classes(K);
+    const int64_t count = pixels * K;
+    ProfScope ps(ctx, FAM_ELEMWISE, 0, (double)count * 8 + (double)pixels);
+    hipLaunchKernelGGL(class_loss_bwd_kernel, dim3(class_grid(count, K, 256 * 16)), dim3(kBlock), 0, ctx->stream, logits, labels,
+                       count, K, kind, alpha, gamma, sums, dlogits);
+    check_launch("class_loss_bwd");
+}
+size_t class_confusion_ws_words(int K) { return (size_t)3 * K * 1024; }
+void launch_class_confusion(rfi_ctx* ctx, const float* logits, const uint8_t* labels, int64_t pixels, int K, float threshold,
+                            unsigned long long* partial_ws, unsigned long long* counts) {
+    check_classes(K);
+    const int64_t count = pixels * K;
+    const int blocks = class_grid(count, K, 1024);
+    ProfScope ps(ctx, FAM_METRICS, 0, (double)count * 4 + (double)pixels);
+    hipLaunchKernelGGL(class_confusion_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, logits, labels, count, K, threshold,
+                       partial_ws);
+    check_launch("class_confusion");
+    hipLaunchKernelGGL(class_confusion_finish_kernel, dim3(1), dim3(64), 0, ctx->stream, partial_ws, blocks, K, counts);
+    check_launch("class_confusion_finish");
+}
+
 void launch_sigmoid_fwd(rfi_ctx* ctx, const float* z, int64_t n, float* x) {
     ProfScope ps(ctx, FAM_ELEMWISE, 0, (double)n * 8);
     hipLaunchKernelGGL(sigmoid_fwd_kernel, dim3(grid_for(n)), dim3(kBlock), 0, ctx->stream, z, n, x);
@@ -1799,7 +2001,7 @@ int launch_head_bwd(rfi_ctx* ctx, YRef yr, int64_t M, int C, const float* scale,
     RFI_REQUIRE(vec || !yr.bf16, "head_bwd: a bfloat16 input needs C % 4 == 0");
     // finish = false leaves the records for a batched finisher whose table was filled with the VECTOR kernel's record geometry
     RFI_REQUIRE(finish || vec, "head_bwd: deferred finishing needs the vector path (C % 4 == 0, 16-byte aligned tensors)");
-    RFI_REQUIRE(!da16 || (vec && Cout == 1 && !(reinterpret_cast<uintptr_t>(da16) & 7)), "head_bwd: a bfloat16 gradient tensor needs C % 4 == 0 and one output channel");
+    RFI_REQUIRE(!da16 || (vec && !(reinterpret_cast<uintptr_t>(da16) & 7)), "head_bwd: a bfloat16 gradient tensor needs C % 4 == 0");
     const float* y = static_cast<const float*>(yr.p);
     ChanGeom g = geom_rows(M, C, vec);     // scalar kernel: one channel per lane; vector kernel: four
     {

@@ -256,6 +256,19 @@ void launch_focal_reduce(rfi_ctx* ctx, const float* logits, const uint8_t* label
                          float gamma, double* partial_ws, float* loss_out);
 void launch_focal_bwd(rfi_ctx* ctx, const float* logits, const uint8_t* labels, int64_t count, float alpha,
                       float gamma, float* dlogits);
+// class-bit labels (RFI_LABELS_CLASS_BITS): logits [pixels][K] channel-last, K <= 8, labels one byte per pixel whose bit k is the
+// target of channel k.  kind: 0 BCE mean + one dice term over all elements (the reference's code on the K-channel tensor), 1
+// focal, 2 BCE mean + the mean of the K per-class dice terms.  sums: 4 x 8 doubles, [q * 8 + class] with q as launch_loss_reduce;
+// partial_ws: class_loss_ws_doubles(K) doubles.  Two-stage in a fixed order: bitwise reproducible
+size_t class_loss_ws_doubles(int K);
+void launch_class_loss_reduce(rfi_ctx* ctx, const float* logits, const uint8_t* labels, int64_t pixels, int K, int kind,
+                              float alpha, float gamma, double* partial_ws, double* sums, float* loss_out);
+void launch_class_loss_bwd(rfi_ctx* ctx, const float* logits, const uint8_t* labels, int64_t pixels, int K, int kind, float alpha,
+                           float gamma, const double* sums, float* dlogits);
+// counts[class][tp, fp, fn] of sigmoid(logit) > threshold against the class bits; partial_ws: class_confusion_ws_words(K) words
+size_t class_confusion_ws_words(int K);
+void launch_class_confusion(rfi_ctx* ctx, const float* logits, const uint8_t* labels, int64_t pixels, int K, float threshold,
+                            unsigned long long* partial_ws, unsigned long long* counts);
 // head backward: da[m,c] = sum_o dlogits[m,o]*w[o][c] (NOT yet relu-masked: bn_bwd does that);
 // dw[o][c] = sum_m dlogits[m,o]*act[m,c]; db[o] = sum_m dlogits[m,o]
 // bn_records_ws != null (+ the layer's batch mean / invstd): where the shape allows (Cout == 1, C % 4 == 0) the same pass
@@ -363,11 +376,12 @@ void launch_threshold_sweep(rfi_ctx* ctx, const float* scores, int kind, const v
 void check_sweep_thresholds(const float* thr_host, int K);       // 1 .. 1024 finite, strictly increasing, or throws
 void threshold_sweep_counts(const unsigned long long* hist, int64_t n_groups, int K, int64_t* counts);
 // inverse of the inference tiling (stitch.hip): patch values (n_planes x tiling_patches_per_plane x ps x ps) -> flags
-// (and prob when non-null), n_planes x C x T; semantics in include/rfi_hip.h (rfi_stitch_patches)
+// (and prob when non-null), n_planes x C x T; semantics in include/rfi_hip.h (rfi_stitch_patches); n_classes > 1: values are
+// channel-last (... x ps x ps x n_classes) and the outputs n_planes x n_classes x C x T (rfi_stitch_patches_classes)
 int64_t tiling_patches_per_plane(int C, int T, const rfi_tiling& tiling);
 void check_tiling(const rfi_tiling& tiling);
 void launch_stitch(rfi_ctx* ctx, const float* values, int kind, int n_planes, int C, int T, const rfi_tiling& tiling,
-                   int combine, float threshold, uint8_t* flags, float* prob);
+                   int combine, float threshold, uint8_t* flags, float* prob, int n_classes = 1);
 // whole-array flagging statistics (flag_stats.hip): src is `n` elements of dtype RFI_C128/C64/F64/F32 on the device,
 // flags n bytes (non-zero == flagged) or nullptr; views bit 0 all elements, bit 1 unflagged elements; ws holds
 // flag_stats_ws_bytes(); mag holds n input-precision floats (complex input only); out_dev[2] receives the views
@@ -486,6 +500,9 @@ void launch_rfi_sim_event_table(rfi_ctx* ctx, unsigned long long seed, unsigned 
 void launch_rfi_sim_instances(rfi_ctx* ctx, unsigned long long seed, unsigned first_sample, int n_samples, const rfi_sim_params& p,
                               const double* power_dev, const rfi_sim_event* events, const int* component, const int* count,
                               const int* base, int max_instances, int class_mode, int* labels, uint8_t* masks);
+// bits: n_samples x T x F bytes, bit cat - 1 = an event of category cat (1 .. 5) flags the pixel
+void launch_rfi_sim_family_bits(rfi_ctx* ctx, unsigned long long seed, unsigned first_sample, int n_samples, const rfi_sim_params& p,
+                                const double* power_dev, const rfi_sim_event* events, uint8_t* bits);
 
 // x[i] *= f  (the emulated gradient exchange of the single-GPU tests, rfi_comm_emulate)
 void launch_scale_inplace(rfi_ctx* ctx, float* x, int64_t n, float f);

@@ -162,7 +162,7 @@ void rfi_model::prepare(int n, int h, int w) {
     bufs[lab_stage].ensure(ctx, dense_head ? (Mout + 3) / 4 + 4 : 16);
     // the workspaces: the needs every model has (gradient norm, loss), on top of what prepare_shape declared
     need_red(sumsq_ws_doubles(n_flat) * 2);
-    if (dense_head) need_red(loss_ws_doubles(Mout) * 2);
+    if (dense_head) need_red(std::max(loss_ws_doubles(Mout), class_loss_ws_doubles(out_ch)) * 2);
     bufs[ws_red].ensure(ctx, red_need + 16);
     bufs[ws_slab].ensure(ctx, slab_need + 16);
     pN = n; pH = h; pW = w;
@@ -643,8 +643,13 @@ void UNetModel::forward_pass(const float* x_dev, int n, int h, int w, bool train
 }
 
 void rfi_model::loss_forward(const uint8_t* labels_dev, int n, int h, int w) {
-    RFI_REQUIRE(out_ch == 1, "loss: the reference's BCE+dice step is defined for out_channels == 1");
     const int64_t cnt = (int64_t)n * h * w * out_scale * out_scale;
+    if (label_mode == RFI_LABELS_CLASS_BITS) {
+        launch_class_loss_reduce(ctx, buf(logits), labels_dev, cnt, out_ch, loss_kind, focal_alpha, focal_gamma,
+                                 reinterpret_cast<double*>(buf(ws_red)), class_sums(), d_scalars);
+        return;
+    }
+    RFI_REQUIRE(out_ch == 1, "loss: the reference's BCE+dice step is defined for out_channels == 1");
     // UNetOverfit: BCE-with-logits + dice are applied to the model OUTPUT, i.e. to sigmoid(logits)
     if (loss_kind == 1) {
         launch_focal_reduce(ctx, buf(head_sigmoid ? probs : logits), labels_dev, cnt, focal_alpha, focal_gamma,
@@ -653,6 +658,17 @@ void rfi_model::loss_forward(const uint8_t* labels_dev, int n, int h, int w) {
     }
     launch_loss_reduce(ctx, buf(head_sigmoid ? probs : logits), labels_dev, cnt,
                        reinterpret_cast<double*>(buf(ws_red)), d_sums, d_scalars);
+}
+
+void rfi_model::loss_backward(const uint8_t* labels_dev, int64_t pixels) {
+    if (label_mode == RFI_LABELS_CLASS_BITS)
+        return launch_class_loss_bwd(ctx, buf(logits), labels_dev, pixels, out_ch, loss_kind, focal_alpha, focal_gamma, class_sums(),
+                                     buf(dlogits));
+    if (loss_kind == 1)
+        launch_focal_bwd(ctx, buf(head_sigmoid ? probs : logits), labels_dev, pixels, focal_alpha, focal_gamma, buf(dlogits));
+    else
+        launch_loss_bwd(ctx, buf(head_sigmoid ? probs : logits), labels_dev, pixels, d_sums, buf(dlogits));
+    if (head_sigmoid) launch_sigmoid_bwd(ctx, buf(probs), pixels * out_ch, buf(dlogits));
 }
 
 // ------------------------------------------------------------------------------------ backward
@@ -836,11 +852,7 @@ void UNetModel::backward_pass(const float* x_dev, const uint8_t* labels_dev, int
     side_bound = resnet_encoder ? 2 : 0;          // (the ResNet-style encoder double-buffers by block parity: bound 2)
     dbias_deferred = !resnet_encoder && dbias_pool && !ctx->exchange_active();
     // loss -> dlogits -> head
-    if (loss_kind == 1)
-        launch_focal_bwd(ctx, buf(head_sigmoid ? probs : logits), labels_dev, M1, focal_alpha, focal_gamma, buf(dlogits));
-    else
-        launch_loss_bwd(ctx, buf(head_sigmoid ? probs : logits), labels_dev, M1, d_sums, buf(dlogits));
-    if (head_sigmoid) launch_sigmoid_bwd(ctx, buf(probs), M1 * out_ch, buf(dlogits));
+    loss_backward(labels_dev, M1);
     int head_records = 0;
     // a one-channel head sends d[pixel] * w[channel] down: where its BatchNorm-backward sums come out of launch_head_bwd's own
     // pass the gradient tensor is never written -- bn_bwd_apply recomputes it from the logit gradients (268 MB of HBM traffic

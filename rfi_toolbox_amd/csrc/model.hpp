@@ -162,7 +162,12 @@ struct rfi_model {
     // plane data flow (model_planes.cpp; set by the U-Net family only): 0 off (round-1 kernels on float32 tensors), 1 bf16
     // activations (the bfloat16 compute mode), 3 float32 as three bf16 pieces
     int planesP = 0;
-    int loss_kind = 0;                // 0: BCE-with-logits + dice (the reference's, train_model.py:120-128); 1: focal
+    // 0: BCE-with-logits + dice (the reference's, train_model.py:120-128); 1: focal; 2: BCE + the mean of the per-class dice
+    // terms (class-bit labels; with one class it is kind 0)
+    int loss_kind = 0;
+    // what a label byte means (rfi_model_set_label_mode): RFI_LABELS_MAP non-zero == RFI, one output channel; RFI_LABELS_CLASS_BITS
+    // bit k is the target of output channel k (the plain U-Net without the sigmoid head)
+    int label_mode = 0;
     float focal_alpha = 0.25f, focal_gamma = 2.0f;
     bool head_sigmoid = false;        // UNetOverfit: forward returns sigmoid(logits); the loss sees that too
     // a per-pixel head of out_ch channels with the loss inside the model.  False (the backbone: out_ch is the FPN width): no
@@ -266,7 +271,9 @@ struct rfi_model {
     int x_stage = -1, x_stage2 = -1, x_pad = -1, out_stage = -1, ws_red = -1, ws_slab = -1, lab_stage = -1;
     int gx = -1;                      // the gradient w.r.t. the input (the detector's heads own it; -1: the model computes none)
     bool ext_dlogits = false;         // backward from caller-provided dlogits (rfi_model_backward_dlogits)
-    double* d_sums = nullptr;         // [0..3] loss sums, [4] grad sumsq
+    double* d_sums = nullptr;         // [0..3] loss sums, [4] grad sumsq, [5..7] eval_batch's counts, [8..39] class-bit loss sums (4 x 8)
+    static constexpr int kSumsDoubles = 40;
+    double* class_sums() const { return d_sums + 8; }
     float* d_scalars = nullptr;       // [0] loss, [1] grad norm
     float last_loss = 0, last_norm = 0;
 
@@ -282,6 +289,7 @@ struct rfi_model {
     void forward(const float* x_dev, int n, int h, int w, bool train_mode);    // (prepare + derived filters, then forward_pass)
     virtual void forward_pass(const float* x_dev, int n, int h, int w, bool train_mode) = 0;
     void loss_forward(const uint8_t* labels_dev, int n, int h, int w);
+    void loss_backward(const uint8_t* labels_dev, int64_t pixels);      // logits + the loss sums -> dlogits (U-Net family)
     void backward(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w);    // (then backward_pass)
     virtual void backward_pass(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w) = 0;
     void apply(const rfi_hyper& hp, float grad_scale);

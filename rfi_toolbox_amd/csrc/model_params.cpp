@@ -185,11 +185,11 @@ void rfi_model::alloc_state() {
     adam_v = static_cast<float*>(ctx->alloc(bytes));
     chan_pool = static_cast<float*>(ctx->alloc(chan_floats * sizeof(float)));
     wd_pool = static_cast<float*>(ctx->alloc(wd_floats * sizeof(float)));
-    d_sums = static_cast<double*>(ctx->alloc(8 * sizeof(double)));
+    d_sums = static_cast<double*>(ctx->alloc(kSumsDoubles * sizeof(double)));
     d_scalars = static_cast<float*>(ctx->alloc(8 * sizeof(float)));
     for (float* p : {params, grads, adam_m, adam_v}) RFI_CHECK_HIP(hipMemsetAsync(p, 0, bytes, ctx->stream));
     RFI_CHECK_HIP(hipMemsetAsync(chan_pool, 0, chan_floats * sizeof(float), ctx->stream));
-    RFI_CHECK_HIP(hipMemsetAsync(d_sums, 0, 8 * sizeof(double), ctx->stream));
+    RFI_CHECK_HIP(hipMemsetAsync(d_sums, 0, kSumsDoubles * sizeof(double), ctx->stream));
     RFI_CHECK_HIP(hipMemsetAsync(d_scalars, 0, 8 * sizeof(float), ctx->stream));
     for (auto& c : convs) {
         c.chan = chan_pool + c.chan_off;

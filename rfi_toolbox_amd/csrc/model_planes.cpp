@@ -630,11 +630,7 @@ void UNetModel::backward_planes(const float* x_dev, const uint8_t* labels_dev, i
     side_bound = 0;
     const int64_t M1 = (int64_t)n * h * w;
     dbias_deferred = dbias_pool && !ctx->exchange_active();    // (bias gradients must be final before their bucket leaves)
-    if (loss_kind == 1)
-        launch_focal_bwd(ctx, buf(head_sigmoid ? probs : logits), labels_dev, M1, focal_alpha, focal_gamma, buf(dlogits));
-    else
-        launch_loss_bwd(ctx, buf(head_sigmoid ? probs : logits), labels_dev, M1, d_sums, buf(dlogits));
-    if (head_sigmoid) launch_sigmoid_bwd(ctx, buf(probs), M1 * out_ch, buf(dlogits));
+    loss_backward(labels_dev, M1);
     int head_records = 0;
     {
         ConvBN& last = convs[IB + 2 + 2 * (D - 1) + 1];

@@ -570,6 +570,50 @@ __global__ __launch_bounds__(256) void rfisim_instance_masks_kernel(SimDev d, co
     }
 }
 
+// bits[i] = one byte per pixel of sample i, bit cat - 1 set where an event of category cat (1 broadband .. 5 quadratic
+// sweep) flags it: the OR by family of the instance masks, without the masks.  The same gather as above -- a thread owns one
+// 16-byte-aligned range of the sample's plane and stores it once -- over every event slot of the sample: event_row_bits
+// evaluates a draw only inside a broadband chunk and on the one column / row / point of a line event, so the slots that do
+// not touch the range cost a few integer comparisons each.  blockIdx: sample x blocks_per_plane + block of the plane.
+__global__ __launch_bounds__(256) void rfisim_family_bits_kernel(SimDev d, int blocks_per_plane, uint8_t* __restrict__ out) {
+    const int i = (int)(blockIdx.x / blocks_per_plane);
+    const int64_t HW = (int64_t)d.T * d.F;
+    uint8_t* plane = out + (int64_t)i * HW;
+    const int head = (int)(reinterpret_cast<uintptr_t>(plane) & (kRun - 1));
+    const int64_t c = (int64_t)(blockIdx.x % blocks_per_plane) * 256 + threadIdx.x;
+    const int64_t r0 = c * kRun - head;                  // the range [r0, r0 + kRun) in the plane's pixel indices
+    const int64_t p0 = max(r0, (int64_t)0), p1 = min(r0 + kRun, HW);
+    if (p0 >= p1) return;
+    const unsigned sample = d.first + (unsigned)i;
+    const int t0 = (int)(p0 / d.F), f0 = (int)(p0 - (int64_t)t0 * d.F);
+    unsigned w[4] = {0, 0, 0, 0};                        // byte b of the range = byte b % 4 of w[b / 4]
+    for (int slot = 1; slot < d.slots; ++slot) {
+        rfi_sim_event e;
+        int cat = S_HEADER, k = 0;
+        if (!live_event(d, i, slot, e, cat, k)) continue;
+        unsigned bits = 0;                               // bit b = pixel r0 + b
+        int t = t0, f = f0;
+        for (int64_t p = p0; p < p1; ++t, f = 0) {
+            const int fb = (int)min((int64_t)d.F, f + (p1 - p));
+            bits |= event_row_bits(d, e, cat, k, t, f, fb, sample) << (int)(p - r0);
+            p += fb - f;
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const unsigned nib = (bits >> (4 * q)) & 15u;
+            w[q] |= ((nib & 1u) | (nib & 2u) << 7 | (nib & 4u) << 14 | (nib & 8u) << 21) << (cat - 1);
+        }
+    }
+    if (p1 - p0 == kRun) {
+        *reinterpret_cast<uint4*>(plane + r0) = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {
+        for (int64_t p = p0; p < p1; ++p) {
+            const int b = (int)(p - r0);
+            plane[p] = (uint8_t)(w[b >> 2] >> (8 * (b & 3)));
+        }
+    }
+}
+
 SimDev sim_dev(unsigned long long seed, unsigned first_sample, int n_samples, const rfi_sim_params& p, const double* power_dev,
                rfi_sim_event* events) {
     SimDev d{};
@@ -648,6 +692,18 @@ void launch_rfi_sim_instances(rfi_ctx* ctx, unsigned long long seed, unsigned fi
     hipLaunchKernelGGL(rfisim_instance_masks_kernel, dim3((unsigned)(slots * per_plane)), dim3(256), 0, ctx->stream, d, component, count,
                        base, max_instances, (int)per_plane, masks);
     check_launch("rfisim_instance_masks");
+}
+
+void launch_rfi_sim_family_bits(rfi_ctx* ctx, unsigned long long seed, unsigned first_sample, int n_samples, const rfi_sim_params& p,
+                                const double* power_dev, const rfi_sim_event* events, uint8_t* bits) {
+    const SimDev d = sim_dev(seed, first_sample, n_samples, p, power_dev, const_cast<rfi_sim_event*>(events));   // (read only here)
+    const int64_t HW = (int64_t)d.T * d.F;
+    const int64_t per_plane = cdiv(HW / kRun + 2, 256);          // ranges of a plane: at most HW / 16 whole ones and two cut ones
+    RFI_REQUIRE(n_samples * per_plane < ((int64_t)1 << 31), "sim_family_bits: batch too large for one launch");
+    ProfScope ps(ctx, FAM_PREPROCESS, 0, (double)n_samples * HW);
+    hipLaunchKernelGGL(rfisim_family_bits_kernel, dim3((unsigned)(n_samples * per_plane)), dim3(256), 0, ctx->stream, d, (int)per_plane,
+                       bits);
+    check_launch("rfisim_family_bits");
 }
 
 }  // namespace rfi

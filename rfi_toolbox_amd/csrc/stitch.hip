@@ -14,19 +14,20 @@ namespace rfi {
 namespace {
 
 // kind 0: values are logits (sigmoid as threshold_kernel computes it), 1: probabilities as they are
+// K classes, channel-last in a patch pixel: grid.z counts (plane, class) pairs, which is also the output plane
 template <int KIND, int COMBINE>
-__global__ void __launch_bounds__(256) stitch_kernel(const float* __restrict__ vals, TileGrid g, float thr,
+__global__ void __launch_bounds__(256) stitch_kernel(const float* __restrict__ vals, TileGrid g, int K, float thr,
                                                      uint8_t* __restrict__ flags, float* __restrict__ prob) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int c = blockIdx.y * blockDim.y + threadIdx.y;
     const int plane = blockIdx.z;
     if (t >= g.T || c >= g.C) return;
-    const int64_t ps2 = (int64_t)g.ps * g.ps;
-    const float* pv = vals + (int64_t)plane * g.ppp * ps2;
+    const int64_t ps2 = (int64_t)g.ps * g.ps * K;
+    const float* pv = vals + (int64_t)(plane / K) * g.ppp * ps2 + plane % K;
     float acc = 0.0f;
     int cnt = 0;
     for_each_covering_tile<int64_t>(g, c, t, [&](int64_t tile, int64_t off) {
-        const float raw = pv[tile * ps2 + off];
+        const float raw = pv[tile * ps2 + off * K];
         const float p = KIND == 0 ? 1.0f / (1.0f + expf(-raw)) : raw;
         if (COMBINE == 0) acc += p;
         else acc = (cnt == 0 || p > acc) ? p : acc;
@@ -52,24 +53,26 @@ void check_tiling(const rfi_tiling& tl) {
 }
 
 void launch_stitch(rfi_ctx* ctx, const float* values, int kind, int n_planes, int C, int T, const rfi_tiling& tl,
-                   int combine, float threshold, uint8_t* flags, float* prob) {
+                   int combine, float threshold, uint8_t* flags, float* prob, int n_classes) {
+    RFI_REQUIRE(n_classes >= 1 && n_classes <= 65535, "stitch: 1 to 65535 classes");
     RFI_REQUIRE(kind == RFI_VALUES_LOGITS || kind == RFI_VALUES_PROBS, "stitch: kind must be logits (0) or probabilities (1)");
     RFI_REQUIRE(combine == RFI_COMBINE_MEAN || combine == RFI_COMBINE_MAX, "stitch: combine must be mean (0) or max (1)");
     if (n_planes == 0) return;
     const TileGrid g = make_tile_grid(C, T, tl);
-    const double px = (double)n_planes * C * T;
+    const double px = (double)n_planes * n_classes * C * T;
     // bytes: every covering tile read once (about views x (ps / stride)^2 per pixel), flags and probabilities written
     const double cover = (double)g.views * ((double)tl.ps / tl.stride) * ((double)tl.ps / tl.stride);
     ProfScope ps_(ctx, FAM_METRICS, 0, px * (4 * cover + 1 + (prob ? 4 : 0)), "stitch");
     RFI_REQUIRE(cdiv(C, 4) <= 65535, "stitch: at most 262140 channels");
     const dim3 block(64, 4);
-    for (int p0 = 0; p0 < n_planes; p0 += 65535) {           // grid.z: at most 65535 planes per launch
-        const int np = std::min(65535, n_planes - p0);
-        const dim3 grid((unsigned)cdiv(T, 64), (unsigned)cdiv(C, 4), (unsigned)np);
-        const float* v = values + (int64_t)p0 * g.ppp * tl.ps * tl.ps;
-        uint8_t* f = flags + (int64_t)p0 * C * T;
-        float* pr = prob ? prob + (int64_t)p0 * C * T : nullptr;
-#define RFI_STITCH(K, M) hipLaunchKernelGGL((stitch_kernel<K, M>), grid, block, 0, ctx->stream, v, g, threshold, f, pr)
+    const int step = 65535 / n_classes;                      // grid.z: at most 65535 (plane, class) pairs per launch
+    for (int p0 = 0; p0 < n_planes; p0 += step) {
+        const int np = std::min(step, n_planes - p0);
+        const dim3 grid((unsigned)cdiv(T, 64), (unsigned)cdiv(C, 4), (unsigned)(np * n_classes));
+        const float* v = values + (int64_t)p0 * g.ppp * tl.ps * tl.ps * n_classes;
+        uint8_t* f = flags + (int64_t)p0 * n_classes * C * T;
+        float* pr = prob ? prob + (int64_t)p0 * n_classes * C * T : nullptr;
+#define RFI_STITCH(K, M) hipLaunchKernelGGL((stitch_kernel<K, M>), grid, block, 0, ctx->stream, v, g, n_classes, threshold, f, pr)
         if (kind == 0) {
             if (combine == 0) RFI_STITCH(0, 0);
             else RFI_STITCH(0, 1);

@@ -184,6 +184,9 @@ def predict_flags(model, data, patch_size=128, stride=None, views=1, combine="me
       own whole ``8 C T`` scalars (never per tile; a stored fit is ignored).  One flag per baseline pixel comes out:
       with ``broadcast_pols`` it is repeated over the four polarisations (``data``'s shape, what ``MSLoader.save_flags``
       takes), without it the flags are ``(B, C, T)`` / ``(C, T)``.  The probabilities are always per baseline.
+      A model with class-bit targets (``set_targets("class_bits")``) and K = 2 .. 8 output channels gives flags
+      ``(B, K, C, T)`` / ``(K, C, T)``, one plane per class from the same tiling, combine rule and scalar ``threshold``,
+      and probabilities of that shape; ``broadcast_pols`` does not apply to it and raises when passed as False.
 
     Tiling works on the last two axes as they are: a model trained on the simulator's ``(T, F)`` planes must be given
     observation planes in that orientation (``views=4`` covers both).  Results are NumPy arrays (for NumPy or CPU-tensor
@@ -201,10 +204,15 @@ def predict_flags(model, data, patch_size=128, stride=None, views=1, combine="me
         raise ValueError(f"data must be (B, P, C, T) or (P, C, T), got shape {shape}")
     if not isinstance(model, HipSegmenter):
         raise TypeError(f"predict_flags needs a rfi_toolbox_amd segmentation model, got {type(model).__name__}")
-    if model.in_channels not in (3, 8) or model.out_channels != 1 or model._out_scale != 1:
-        raise ValueError(f"predict_flags needs a model with 3 or 8 input channels and 1 output channel the size of its "
-                         f"input, got {type(model).__name__} with {model.in_channels} -> {model.out_channels}")
     pol = model.in_channels == 8
+    K = model.out_channels
+    by_class = pol and getattr(model, "targets", "map") == "class_bits"       # its channels are classes of their own
+    if model.in_channels not in (3, 8) or not 1 <= K <= (8 if by_class else 1) or model._out_scale != 1:
+        raise ValueError(f"predict_flags needs a model with 3 or 8 input channels and 1 output channel the size of its input, or "
+                         f"with 8 input channels, class-bit targets and up to 8 output channels, got {type(model).__name__} "
+                         f"with {model.in_channels} -> {K} and {getattr(model, 'targets', 'map')!r} targets")
+    if K > 1 and not broadcast_pols:
+        raise ValueError("broadcast_pols does not apply to a model with several output channels: its flags are (B, K, C, T)")
     if not pol and (normalizer is not None or not broadcast_pols):
         raise ValueError("normalizer and broadcast_pols=False belong to models with 8 input channels; a model with 3 "
                          "input channels normalises every patch itself and flags every plane")
@@ -230,15 +238,16 @@ def predict_flags(model, data, patch_size=128, stride=None, views=1, combine="me
     form = _normalizer_form(normalizer)
     ctx = model.ctx
     o = operand(data, ctx, (dt,), "cast")
-    base = shape[:-3] + (Cn, Tn)
+    base = shape[:-3] + ((Cn, Tn) if K == 1 else (K, Cn, Tn))
     flags, fp, omem = _flag_buffer(ctx, base, out, data)
     prob, pp, _ = result_buffer(ctx, base, np.float32, out, data) if return_probabilities else (None, None, None)
     px = Cn * Tn
+    opx = K * px                # output elements per sample
 
     def run(ptr, mem, b0, b1, centre, scale, pairs):
         check(lib.rfi_model_predict_flags_pol(model._h, C.c_void_p(ptr), mem, COMPLEX_CODES[dt], b1 - b0, Cn, Tn, C.byref(tiling),
                                               *args, centre, scale, None if pairs is None else pairs.ctypes.data_as(C.c_void_p),
-                                              C.c_void_p(fp + b0 * px), omem, C.c_void_p(pp + 4 * b0 * px) if pp else None, omem))
+                                              C.c_void_p(fp + b0 * opx), omem, C.c_void_p(pp + 4 * b0 * opx) if pp else None, omem))
 
     if n and px:
         if form[0] == "pair":
@@ -250,7 +259,7 @@ def predict_flags(model, data, patch_size=128, stride=None, views=1, combine="me
                 del group
     del o
     flags = _as_bool(flags)
-    if broadcast_pols:
+    if broadcast_pols and K == 1:
         flags = _broadcast_pols(ctx, flags, shape)
     return (flags, prob) if return_probabilities else flags
 
@@ -292,13 +301,19 @@ def stitch_patches(values, channels, times, patch_size, stride=None, views=1, ed
     ``values``: float32 ``(N, ps, ps)``, ``(N, ps, ps, 1)`` or ``(N, 1, ps, ps)`` in ``rfi_tiling`` order, logits (read
     as ``sigmoid``) or, with ``logits=False``, probabilities; ``N`` must be a whole number of ``channels x times``
     planes.  Returns bool flags ``(planes, channels, times)`` and, with ``return_probabilities``, the float32 combined
-    values: ``DeviceArray``s for a ``DeviceArray``, CUDA tensors for a CUDA tensor, else NumPy arrays."""
+    values: ``DeviceArray``s for a ``DeviceArray``, CUDA tensors for a CUDA tensor, else NumPy arrays.
+
+    ``values`` of ``(N, ps, ps, K)`` with K > 1 -- the channel-last output of a K-class model -- are stitched class by
+    class: flags ``(planes, K, channels, times)``, and the probabilities likewise."""
     ps, s = check_tiling_args(patch_size, stride, views, combine, edge)
     shape = tuple(int(v) for v in describe(values)[0])
+    K = None
     if len(shape) == 4 and (shape[-1] == 1 or shape[1] == 1):
         shape = shape[:3] if shape[-1] == 1 else (shape[0],) + shape[2:]
+    elif len(shape) == 4 and shape[1:3] == (ps, ps):
+        shape, K = shape[:3], shape[3]
     if len(shape) != 3 or shape[1:] != (ps, ps):
-        raise ValueError(f"values must be (N, {ps}, {ps}), (N, {ps}, {ps}, 1) or (N, 1, {ps}, {ps}), got {describe(values)[0]}")
+        raise ValueError(f"values must be (N, {ps}, {ps}), (N, {ps}, {ps}, K) or (N, 1, {ps}, {ps}), got {describe(values)[0]}")
     Cn, Tn = int(channels), int(times)
     if Cn <= 0 or Tn <= 0:
         raise ValueError(f"channels and times must be positive, got {channels!r}, {times!r}")
@@ -309,12 +324,14 @@ def stitch_patches(values, channels, times, patch_size, stride=None, views=1, ed
     ctx = context_for(None, values)
     o = operand(values, ctx, (np.float32,), "cast")
     out = "device" if isinstance(values, DeviceArray) else "host"
-    flags, fp, omem = _flag_buffer(ctx, (n_planes, Cn, Tn), out, values)
-    prob, pp, _ = result_buffer(ctx, (n_planes, Cn, Tn), np.float32, out, values) if return_probabilities else (None, None, None)
+    oshape = (n_planes, Cn, Tn) if K is None else (n_planes, K, Cn, Tn)
+    flags, fp, omem = _flag_buffer(ctx, oshape, out, values)
+    prob, pp, _ = result_buffer(ctx, oshape, np.float32, out, values) if return_probabilities else (None, None, None)
     if n_planes:
-        check(lib.rfi_stitch_patches(ctx.handle, C.c_void_p(o.ptr), o.mem, VALUES_LOGITS if logits else VALUES_PROBS, n_planes,
-                                     Cn, Tn, C.byref(Tiling(ps, s, _EDGE[edge], views)), _COMBINE[combine], float(threshold),
-                                     C.c_void_p(fp), omem, C.c_void_p(pp) if pp else None, omem))
+        check(lib.rfi_stitch_patches_classes(ctx.handle, C.c_void_p(o.ptr), o.mem, VALUES_LOGITS if logits else VALUES_PROBS,
+                                             n_planes, K or 1, Cn, Tn, C.byref(Tiling(ps, s, _EDGE[edge], views)),
+                                             _COMBINE[combine], float(threshold), C.c_void_p(fp), omem,
+                                             C.c_void_p(pp) if pp else None, omem))
     del o
     return (_as_bool(flags), prob) if return_probabilities else _as_bool(flags)
 

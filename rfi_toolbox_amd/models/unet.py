@@ -120,6 +120,8 @@ class HipSegmenter:
         self.load_state_dict(old_state)
         self._init = None
         check(lib.rfi_model_set_training(self._h, 1 if self.training else 0))
+        if self.targets != "map":
+            self.set_targets(self.targets)
 
     def _release(self):
         if self._h is not None:
@@ -179,11 +181,31 @@ class HipSegmenter:
 
     def set_loss(self, kind="bce_dice", alpha=0.25, gamma=2.0):
         """``"bce_dice"``: the reference's BCE-with-logits + dice (train_model.py:120-128, default);
-        ``"focal"``: sigmoid focal loss, mean over elements (not in the reference; Lin et al. 2017)."""
-        code = {"bce_dice": 0, "focal": 1}.get(kind)
+        ``"focal"``: sigmoid focal loss, mean over elements (not in the reference; Lin et al. 2017);
+        ``"bce_class_dice"`` (class-bit targets only): the same BCE mean plus the mean of the dice terms of the K output
+        channels, each over its own channel of the batch, so that a family of a few dozen pixels weighs as much as one
+        that covers half the plane.  With class-bit targets ``"bce_dice"`` is the reference's code on the K-channel
+        tensor: the BCE mean and ONE dice term over all ``n h w K`` elements."""
+        code = {"bce_dice": 0, "focal": 1, "bce_class_dice": 2}.get(kind)
         if code is None:
-            raise ValueError(f"loss must be 'bce_dice' or 'focal', got {kind!r}")
+            raise ValueError(f"loss must be 'bce_dice', 'focal' or 'bce_class_dice', got {kind!r}")
         check(lib.rfi_model_set_loss(self._h, code, float(alpha), float(gamma)))
+        return self
+
+    targets = "map"
+
+    def set_targets(self, kind="map"):
+        """What a label byte means.  ``"map"`` (default): non-zero is RFI, for a model with one output channel.
+        ``"class_bits"``: the target of output channel k is ``(label >> k) & 1`` (``pack_class_masks`` builds such
+        labels, ``core.family_masks`` makes them for a simulated batch), for 1 to 8 output channels; bits at and above
+        ``out_channels`` are ignored.  Labels stay ``(n, h, w)`` uint8 everywhere.  ``train_step``, ``loss`` and
+        ``forward_backward`` then apply the K-channel loss of ``set_loss``, and ``eval_batch`` counts per class.
+        ``UNet``, ``UNetBigger`` and ``UNetDifferentActivation`` only."""
+        code = {"map": 0, "class_bits": 1}.get(kind)
+        if code is None:
+            raise ValueError(f"targets must be 'map' or 'class_bits', got {kind!r}")
+        check(lib.rfi_model_set_label_mode(self._h, code))
+        self.targets = kind
         return self
 
     # ---- mode
@@ -415,8 +437,15 @@ class HipSegmenter:
         self.set_adam_step(step)
 
     def eval_batch(self, data, mask, threshold=0.5):
-        """(tp, fp, fn) of one batch: forward, sigmoid > threshold, counts -- all on the GPU."""
+        """(tp, fp, fn) of one batch: forward, sigmoid > threshold, counts -- all on the GPU.  With class-bit targets:
+        int64 ``(out_channels, 3)``, the three counts of every class."""
         n, h, w, xp, xm, yp, ym, keep = self._xy(data, mask, True)
+        if self.targets == "class_bits":
+            counts = np.empty((self.out_channels, 3), np.int64)
+            check(lib.rfi_model_eval_batch_classes(self._h, C.c_void_p(xp), xm, C.c_void_p(yp), ym, n, h, w, float(threshold),
+                                                   counts.ctypes.data_as(C.c_void_p)))
+            del keep
+            return counts
         tp, fp, fn = C.c_int64(), C.c_int64(), C.c_int64()
         check(lib.rfi_model_eval_batch(self._h, C.c_void_p(xp), xm, C.c_void_p(yp), ym, n, h, w, float(threshold),
                                        C.byref(tp), C.byref(fp), C.byref(fn)))

@@ -41,22 +41,41 @@ def _batches(n, batch_size, order=None):
         yield idx[i:i + batch_size]
 
 
-def evaluate_rfi_model(model, dataset, batch_size=4, threshold=0.5):
-    """dict of mean per-batch iou / precision / recall / f1 / dice (evaluate_model.py:54-56)."""
+_METRICS = {"iou": _iou, "precision": _precision, "recall": _recall, "f1": _f1, "dice": _dice}
+
+
+def evaluate_rfi_model(model, dataset, batch_size=4, threshold=0.5, class_names=None):
+    """dict of mean per-batch iou / precision / recall / f1 / dice (evaluate_model.py:54-56).
+
+    A model with class-bit targets (``set_targets("class_bits")``) gives the same five metrics per class, each the mean
+    of its per-batch values under the same rules: ``{"per_class": [{"name": ..., "iou": ..., ...}, ...], "macro": {...}}``
+    with ``macro`` the mean over the classes; ``class_names`` (one per output channel) names the entries, else they
+    are ``"class0"`` ..."""
     images, labels = _pair(dataset)
+    by_class = getattr(model, "targets", "map") == "class_bits"
+    if class_names is not None:
+        if not by_class:
+            raise ValueError("class_names belongs to a model with class-bit targets")
+        class_names = [str(v) for v in class_names]
+        if len(class_names) != model.out_channels:
+            raise ValueError(f"class_names must name the {model.out_channels} output channels, got {len(class_names)}")
     was_training = model.training
     model.eval()
-    per_batch = []
+    per_batch = []                    # one row of counts per class and batch
     try:
         for sel in _batches(len(images), batch_size):
-            c = model.eval_batch(images[sel], labels[sel], threshold)
-            per_batch.append({"iou": _iou(*c), "precision": _precision(*c), "recall": _recall(*c),
-                              "f1": _f1(*c), "dice": _dice(*c)})
+            c = np.asarray(model.eval_batch(images[sel], labels[sel], threshold), np.int64).reshape(-1, 3)
+            per_batch.append([{k: f(*(int(v) for v in row)) for k, f in _METRICS.items()} for row in c])
     finally:
         model.train(was_training)
     if not per_batch:
         raise ValueError("empty dataset")
-    return {k: float(np.mean([m[k] for m in per_batch])) for k in per_batch[0]}
+    classes = [{k: float(np.mean([b[j][k] for b in per_batch])) for k in _METRICS} for j in range(len(per_batch[0]))]
+    if not by_class:
+        return classes[0]
+    names = class_names or [f"class{j}" for j in range(len(classes))]
+    return {"per_class": [dict(name=nm, **m) for nm, m in zip(names, classes)],
+            "macro": {k: float(np.mean([m[k] for m in classes])) for k in _METRICS}}
 
 
 def sweep_rfi_model(model, dataset, batch_size=4, thresholds=None):
