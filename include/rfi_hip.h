@@ -267,6 +267,18 @@ int rfi_model_algorithmic_flops(rfi_model* m, int n, int h, int w, double* fwd, 
  * "dYaE.<l>" "dYbE.<l>" "dYbottA" "dYbottB" (BatchNorm-backward outputs of the decoder's / encoder's /
  * bottleneck's second and first conv).  "<name>:pad" = the padding lanes of a bfloat16 / plane
  * tensor, [pixels][16 * chunks - C] (empty when C % 16 == 0): zeros, if the pass is right.
+ * ResNet-encoder U-Net on the bfloat16 data flow (init_features % 16 == 0): its encoder's bfloat16
+ * tensors as float32 values, each with the element count of its last writer: "xin" ("xin:pad"),
+ * "stemY" "a0" "dY0" (the stem's raw output, activation, BatchNorm-backward output); per block
+ * b = 0..7 "rY1.<b>" "rY2.<b>" (raw outputs of conv1 / conv2), "rA1.<b>" (act(BN1(Y1))), "rA.<b>"
+ * (the block output; odd b below the last level: the decoder's skip tensor itself), "rdY1.<b>"
+ * "rdY2.<b>" (BatchNorm-backward outputs); on the stride-2 blocks 2, 4, 6 also "rYd.<b>" "rdYd.<b>"
+ * (the 1x1 projection); "rskip" (the last stage's output as the decoder's skip), "rpool" (its 2x2
+ * max), "rdpool" (the gradient w.r.t. rpool); and the scratch every block reuses, which holds its
+ * last writer's values, [n h w][init_features]: "rdz.0" (block 0's dz), "rdz.1" (the stem's
+ * g = dX + dz of block 0), "rdA1" (block 0's conv2 input gradient), "rdX" (block 0's conv1 input
+ * gradient).  A block index out of range, "rYd" / "rdYd" on a stride-1 block and every one of
+ * these names on a model that is not on this flow are errors.
  * ResNet-50-FPN backbone (conv indices in state_dict order of the conv weights): "conv.<i>" raw
  * output of conv i before its frozen BatchNorm, on its own output grid (0: the stem at H/2; FPN
  * inner / layer blocks: the lateral / the pyramid level), "pool" the pooled stem, "block.<b>" the

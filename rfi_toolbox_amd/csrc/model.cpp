@@ -970,11 +970,12 @@ void UNetModel::set_compute_dtype(int dtype) {
 
 void rfi_model::debug_tensor(const std::string&, const std::string&, int, bool, CallScope&, const float*&, size_t&) {
     throw Error("debug_tensor: this model exposes only logits / dlogits / chan (the U-Net and the ResNet-50-FPN backbone expose their "
-                "own tensors, the ResNet-encoder U-Net its decoder's: see rfi_hip.h)");
+                "own tensors, the ResNet-encoder U-Net its decoder's and, on the bfloat16 flow, its encoder's: see rfi_hip.h)");
 }
 void UNetModel::debug_tensor(const std::string& name, const std::string& base, int idx, bool to_host, CallScope& sc, const float*& src,
                              size_t& n) {
     if (planesP && !resnet_encoder) return debug_tensor_planes(name, base, idx, to_host, sc, src, n);
+    if (resnet_planes() && debug_tensor_resnet_planes(name, base, idx, to_host, sc, src, n)) return;      // (its encoder's bfloat16 tensors)
     RFI_REQUIRE(name.find(':') == std::string::npos, "debug_tensor: only the plain U-Net on a plane data flow has plane tensors");
     if (resnet_encoder && (base == "encY1" || base == "encY2" || base == "pool" || base == "dpool"))
         return rfi_model::debug_tensor(name, base, idx, to_host, sc, src, n);

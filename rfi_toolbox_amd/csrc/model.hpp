@@ -502,6 +502,11 @@ struct UNetModel : rfi_model {
     // debug_tensor of the plain U-Net on a plane data flow: bfloat16 and plane tensors as float32 values, "<name>:pad"
     void debug_tensor_planes(const std::string& name, const std::string& base, int idx, bool to_host, rfi::CallScope& sc, const float*& src,
                              size_t& n);
+    // ... its conversion of ONE plane tensor (pl[pi]: M pixels, C channels, P_ pieces; pad: the padding lanes instead) ...
+    void debug_plane_values(int pi, size_t M, int C, int P_, bool pad, bool to_host, rfi::CallScope& sc, const float*& src, size_t& n);
+    // ... and the tensors of the ResNet-style encoder on the bf16 flow (false: `base` is none of them)
+    bool debug_tensor_resnet_planes(const std::string& name, const std::string& base, int idx, bool to_host, rfi::CallScope& sc,
+                                    const float*& src, size_t& n);
 };
 
 // 3-layer CNN (model_cnn.cpp)

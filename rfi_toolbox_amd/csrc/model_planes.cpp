@@ -563,6 +563,66 @@ void UNetModel::backward_resnet_planes(int n, int h, int w) {
     }
 }
 
+void UNetModel::debug_plane_values(int pi, size_t M, int C, int P_, bool pad, bool to_host, CallScope& sc, const float*& src, size_t& n) {
+    RFI_REQUIRE(pi >= 0 && pi < (int)pl.size() && pl[pi].p, "debug_tensor: this tensor does not exist in this mode");
+    const PlaneBuf& b = pl[pi];
+    RFI_REQUIRE(b.nchunks == plane_chunks(C) && b.used >= plane_elems((int64_t)M, C, P_), "debug_tensor: plane tensor of another shape");
+    const int Cp = 16 * b.nchunks - C;
+    n = M * (size_t)(pad ? Cp : C);
+    if (!to_host || !n) return;
+    float* tmp = sc.temp<float>(n);
+    // (the padding lanes: the last chunk's lanes C % 16 .. 15 read as Cp channels of a tensor that starts there)
+    const bf16_t* in = pad ? b.p + (size_t)(b.nchunks - 1) * P_ * 16 + (C & 15) : b.p;
+    launch_planes_to_f32(ctx, in, b.pstride, (int64_t)M, pad ? Cp : C, P_, tmp, pad ? Cp : C);
+    src = tmp;
+}
+
+// What the ResNet-style encoder leaves behind after a pass on the bf16 flow (forward_resnet_planes / backward_resnet_planes), as
+// float32 values: every tensor is bfloat16, [pixels of its level][channels].  Reported with the element count of its LAST writer:
+//   xin                       the input as the stem reads it (":pad": its padding lanes)
+//   stemY, a0, dY0            the stem's raw output, its activation (block 0's input), the gradient w.r.t. the raw output
+//   rY1.<b> rY2.<b> rYd.<b>   raw outputs of block b's conv1 / conv2 / projection (b = 0..7; rYd on the stride-2 blocks 2, 4, 6)
+//   rA1.<b>, rA.<b>           act(BN1(Y1)) and the block's output (odd b below the last level: the decoder's skip tensor itself)
+//   rdY1.<b> rdY2.<b> rdYd.<b>  the BatchNorm-backward outputs of the three layers
+//   rskip, rpool              the last stage's output as the decoder's skip (a copy of rA.7) and its 2x2 max
+//   rdpool                    the gradient w.r.t. rpool (the bottleneck's input gradient)
+//   rdz.0, rdz.1, rdA1, rdX   scratch every block reuses; the last writers run at level 1, [n h w][feat]:
+//                             rdz.0 = block 0's dz (blocks 6, 4, 2 wrote it before), rdz.1 = the stem's g = dX_0 + dz_0 (blocks 7, 5,
+//                             3, 1 wrote their dz there before), rdA1 = block 0's dA1 (conv2's input gradient), rdX = block 0's dX
+//                             (conv1's input gradient; before: the pool backward's merge and every block's dX / class launches)
+bool UNetModel::debug_tensor_resnet_planes(const std::string& name, const std::string& base, int idx, bool to_host, CallScope& sc,
+                                           const float*& src, size_t& n) {
+    const int D = depth;
+    const bool pad = name.find(":pad") != std::string::npos;
+    auto pix = [&](int l) { return (size_t)pN * (pH >> (l - 1)) * (pW >> (l - 1)); };
+    auto serve = [&](int pi, size_t M, int C) { debug_plane_values(pi, M, C, 1, pad, to_host, sc, src, n); return true; };
+    struct One { const char* name; int pi; size_t M; int C; };
+    const One ones[] = {{"xin", pXin, pix(1), in_ch}, {"stemY", rpStemY, pix(1), feat}, {"a0", rpA0, pix(1), feat}, {"dY0", rpdY0, pix(1), feat},
+                        {"rdA1", rp_dA1, pix(1), feat}, {"rdX", rp_dX, pix(1), feat},
+                        {"rskip", pSkip[D], pix(D), feat << (D - 1)}, {"rpool", pPool[D], pix(D) / 4, feat << (D - 1)},
+                        {"rdpool", dpool[D].b16, pix(D) / 4, feat << (D - 1)}};
+    for (const One& o : ones)
+        if (base == o.name) {
+            RFI_REQUIRE(idx == -1, "debug_tensor: " + base + " is one tensor: no index");
+            return serve(o.pi, o.M, o.C);
+        }
+    if (base == "rdz") {
+        RFI_REQUIRE(idx == 0 || idx == 1, "debug_tensor: rdz.0 or rdz.1");
+        return serve(rp_dz[idx], pix(1), feat);
+    }
+    struct PerBlock { const char* name; int ResPlanes::*slot; };
+    const PerBlock per[] = {{"rY1", &ResPlanes::Y1}, {"rY2", &ResPlanes::Y2}, {"rYd", &ResPlanes::Yd}, {"rA1", &ResPlanes::A1}, {"rA", &ResPlanes::A},
+                            {"rdY1", &ResPlanes::dY1}, {"rdY2", &ResPlanes::dY2}, {"rdYd", &ResPlanes::dYd}};
+    for (const PerBlock& p : per)
+        if (base == p.name) {
+            RFI_REQUIRE(idx >= 0 && idx < (int)blocks.size(), "debug_tensor: block index out of range");
+            const int pi = rpb[idx].*(p.slot);
+            RFI_REQUIRE(pi >= 0, "debug_tensor: only a stride-2 block has a projection");
+            return serve(pi, pix(blocks[idx].level), blocks[idx].cout);
+        }
+    return false;
+}
+
 // What the plain U-Net leaves in HBM after a pass on a plane data flow, as float32 values (parity debugging only: no pass calls
 // this).  A tensor the mode stores as bfloat16 or as planes is converted into a temporary of the call (exact: every bf16 value
 // is a float32 value; P = 3: the sum of the pieces); "<name>:pad" returns the lanes behind the C channels of the last
@@ -582,19 +642,7 @@ void UNetModel::debug_tensor_planes(const std::string& name, const std::string& 
         n = M * C;
     };
     // a plane tensor of P_ pieces (bfloat16 tensors: P_ = 1), C channels per pixel
-    auto planes = [&](int pi, size_t M, int C, int P_) {
-        RFI_REQUIRE(pi >= 0 && pi < (int)pl.size() && pl[pi].p, "debug_tensor: this tensor does not exist in this mode");
-        const PlaneBuf& b = pl[pi];
-        RFI_REQUIRE(b.nchunks == plane_chunks(C) && b.used >= plane_elems((int64_t)M, C, P_), "debug_tensor: plane tensor of another shape");
-        const int Cp = 16 * b.nchunks - C;
-        n = M * (size_t)(pad ? Cp : C);
-        if (!to_host || !n) return;
-        float* tmp = sc.temp<float>(n);
-        // (the padding lanes: the last chunk's lanes C % 16 .. 15 read as Cp channels of a tensor that starts there)
-        const bf16_t* in = pad ? b.p + (size_t)(b.nchunks - 1) * P_ * 16 + (C & 15) : b.p;
-        launch_planes_to_f32(ctx, in, b.pstride, (int64_t)M, pad ? Cp : C, P_, tmp, pad ? Cp : C);
-        src = tmp;
-    };
+    auto planes = [&](int pi, size_t M, int C, int P_) { debug_plane_values(pi, M, C, P_, pad, to_host, sc, src, n); };
     // the flow tensors: bfloat16 or float32, as the mode stores them
     size_t M = 0;
     int C = 0;

@@ -395,7 +395,14 @@ class HipSegmenter:
         "pooled.<l>", "up.<l>", "a1d.<l>", "a1b", "upin.<l>", "upf.<l>", "dYa.<l>", "dYb.<l>", "dYaE.<l>", "dYbE.<l>",
         "dYbottA", "dYbottB", and under "<name>:pad" the padding lanes of such a tensor ([pixels, 16 * chunks - C]; empty
         when C % 16 == 0).  "gA.<l>" / "gB.<l>" hold the encoder's gradients: the decoder phase's are overwritten within
-        the backward pass and cannot be read."""
+        the backward pass and cannot be read.
+
+        UNetResNet18 on the bfloat16 data flow (init_features % 16 == 0) returns its encoder's bfloat16 tensors the same
+        way: "xin" ("xin:pad"), "stemY", "a0", "dY0"; per block b = 0..7 "rY1.<b>", "rY2.<b>", "rA1.<b>", "rA.<b>",
+        "rdY1.<b>", "rdY2.<b>", and on the stride-2 blocks 2, 4, 6 "rYd.<b>", "rdYd.<b>"; "rskip", "rpool", "rdpool"; and
+        the scratch all blocks share, with its last writer's values ([n, h, w, init_features]): "rdz.0" (block 0's dz),
+        "rdz.1" (the stem's g = dX + dz of block 0), "rdA1", "rdX" (block 0's conv2 / conv1 input gradients).  Block
+        indices out of range, "rYd" on a stride-1 block, and these names in any other mode or model raise."""
         n = C.c_int64()
         check(lib.rfi_model_debug_tensor(self._h, name.encode(), None, 0, C.byref(n)))
         out = np.empty(n.value, dtype=np.float32)

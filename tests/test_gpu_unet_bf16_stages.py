@@ -87,7 +87,8 @@ def test_debug_tensor_names():
     m3.forward_backward(x, y)
     assert np.array_equal(m3.debug_tensor("xin").reshape(16, 24, 3), x.numpy()[0])       # (three pieces carry a float32 value exactly)
     assert not m3.debug_tensor("skip.1:pad").any() and m3.debug_tensor("skip.1").size == 16 * 24 * 20
-    # the ResNet-encoder U-Net exposes its decoder's float32 tensors only: what the bfloat16 mode stores as bfloat16 is refused
+    # the ResNet-encoder U-Net exposes its decoder's float32 tensors under these names (its encoder's bfloat16 tensors have names
+    # of their own: test_gpu_resnet_bf16_stages.py): what the bfloat16 mode stores as bfloat16 is refused
     # (width 32: all three gates), and so are the tensors its own encoder replaces; dconcat is converted on a host read
     g = torch.Generator().manual_seed(5)
     xr = torch.randn(1, 32, 32, 3, generator=g)

@@ -333,10 +333,10 @@ def dgrad3x3_stage(dy, w):
     return _n(F.conv_transpose2d(dt, wt, padding=1)), _n(F.conv_transpose2d(dt.abs(), wt.abs(), padding=1))
 
 
-def wgrad3x3_stage(x, dy, wshape):
+def wgrad_stage(x, dy, wshape, stride=1, padding=1):
     xt, dt = _t(x), _t(dy)
-    return (torch.nn.grad.conv2d_weight(xt, wshape, dt, padding=1).numpy(),
-            torch.nn.grad.conv2d_weight(xt.abs(), wshape, dt.abs(), padding=1).numpy())
+    return (torch.nn.grad.conv2d_weight(xt, wshape, dt, stride=stride, padding=padding).numpy(),
+            torch.nn.grad.conv2d_weight(xt.abs(), wshape, dt.abs(), stride=stride, padding=padding).numpy())
 
 
 def convt_stage(a, w, b, gap=None):
@@ -455,29 +455,25 @@ def split_chan(v, C):
 
 # ------------------------------------------------------------------------------------------------------------ the checker
 class Finding(namedtuple("Finding", "stage klass tensor ratio limit ok detail")):
-    def line(self, case_id):
-        return "UNETBF16 %s %s %.3g %s" % (case_id, self.klass, self.ratio, self.tensor)
+    def line(self, case_id, tag="UNETBF16"):
+        return "%s %s %s %.3g %s" % (tag, case_id, self.klass, self.ratio, self.tensor)
 
 
-class Checker:
-    """Runs the stage table of one case over a tensor dictionary T (device or stand-in):
-       T[name]            NHWC float32 arrays under the debug_tensor names, "logits", "dlogits", "x"
-       T["chan"][i]       split_chan(chan.<i>)
-       T["grad"][name]    the gradients in the reference's layout
-       T["pad_fwd"] / T["pad_bwd"][name]   the padding lanes after the forward / the backward pass
-    ``state``: the parameters.  findings: one Finding per (stage, output)."""
+# a conv + BatchNorm layer as bn_backward_layer needs it: its place in `convs`, the names of its parameters (b: None without a
+# conv bias), stride and padding of the conv
+Layer = namedtuple("Layer", "i w b gamma beta stride pad")
 
-    def __init__(self, case, state, T):
-        self.c, self.T = case._replace(slope=float(np.float32(case.slope))), T      # (the slope as the device's float holds it)
-        self.st = {k: v.numpy() if hasattr(v, "numpy") else np.asarray(v) for k, v in state.items()}
-        self.g = gates(case)
+
+class Criteria:
+    """The criteria of the module docstring and the report / failure machinery, shared by the stage checkers of both encoders
+    (tests/resnet_bf16_stages.py has the other): one Finding per (stage, output)."""
+    TAG = "UNETBF16"
+
+    def __init__(self):
         self.findings = []
         self.undecided = 0                # ReLU masks and pooling routes float32 cannot be trusted to decide
-        self.operand_undecided = 0        # elements of an operand rounded in registers next to a bf16 boundary (they widen bounds)
         self.tie_windows = 0
-        self.rows = []
 
-    # -- criteria
     def _add(self, stage, klass, tensor, ratio, limit, detail=""):
         ok = bool(np.isfinite(ratio)) and ratio <= limit
         self.findings.append(Finding(stage, klass, tensor, float(ratio), float(limit), ok, detail))
@@ -512,6 +508,13 @@ class Checker:
             detail = "worst at %s: got %r, want %r, S %r (%d elements over)" % (i, got[i], e[i], S[i], int((r > k).sum()))
         self._add(stage, klass, tensor, worst, k, detail)
 
+    def stats(self, stage, i, ch, Y):
+        """chan.<i>'s mean / invstd against those of the STORED values Y (conv_planes.hip: rounded first, then summed)."""
+        mean, invstd, mabs = stats_stage(Y)
+        self.close(stage + ":stats", "stats", "chan.%d.mean" % i, ch["mean"], mean, mabs)
+        self._add(stage + ":stats", "stats", "chan.%d.invstd" % i, float(np.abs(ch["invstd"] / invstd - 1).max()) / INVSTD_RTOL * K_CONTRACTION,
+                  K_CONTRACTION)
+
     # -- access
     def chan(self, i):
         return self.T["chan"][i]
@@ -527,6 +530,90 @@ class Checker:
         self.undecided += und
         return m
 
+    def bn_backward_layer(self, stage, L, dA, Y_name, x, dY_name, dA_bound=None, slope=None):
+        """BatchNorm backward of layer L (a Layer record) + its conv's weight and bias gradients.  dA: the stored gradient w.r.t.
+        the activated output (exact), or with dA_bound the float64 oracle of a gradient that cannot be read (composite row).
+        slope: the activation slope of the layer's output (default: the model's; 1: no activation of its own -- no mask to decide)."""
+        c, T = self.c, self.T
+        slope = c.slope if slope is None else slope
+        ch, Y = self.chan(L.i), np.asarray(T[Y_name], np.float64)
+        gamma = self.param(L.gamma)
+        mask = self._mask(T[Y_name], ch) if slope != 1 else np.ones(Y.shape, bool)
+        f = np.where(mask, 1.0, slope)
+        dz = np.asarray(dA, np.float64) * f
+        xh = (Y - ch["mean"].astype(np.float64)) * ch["invstd"].astype(np.float64)
+        M = Y.size // Y.shape[-1]
+        ax = (0, 1, 2)
+        b = np.zeros_like(dz) if dA_bound is None else np.asarray(dA_bound, np.float64) * f
+        s1, s2, S1, S2 = dz.sum(ax), (dz * xh).sum(ax), np.abs(dz).sum(ax), np.abs(dz * xh).sum(ax)
+        w1, w2 = b.sum(ax), (b * np.abs(xh)).sum(ax)
+        st = stage + ":sums"
+        self.close(st, "sums", "chan.%d.c1" % L.i, ch["c1"], s1 / M, S1 / M, extra=w1 / M)
+        self.close(st, "sums", "chan.%d.c2" % L.i, ch["c2"], s2 / M, S2 / M, extra=w2 / M)
+        self.close(st, "sums", L.beta, self.grad(L.beta), s1, S1, extra=w1)
+        self.close(st, "sums", L.gamma, self.grad(L.gamma), s2, S2, extra=w2)
+        dY = T[dY_name]
+        if dA_bound is None:
+            o = bn_apply32(dA, T[Y_name], ch, gamma, slope)
+            self.exact(stage + ":apply", dY_name, dY, rne(o))
+            o64 = o.astype(np.float64)
+            if L.b:
+                self.close(stage + ":apply", "sums", L.b, self.grad(L.b), o64.sum(ax), np.abs(o64).sum(ax))
+        else:
+            gi = gamma.astype(np.float64) * ch["invstd"].astype(np.float64)
+            c1, c2 = ch["c1"].astype(np.float64), ch["c2"].astype(np.float64)
+            o = gi * (dz - c1 - xh * c2)
+            So = np.abs(gi) * (np.abs(dz) + np.abs(c1) + np.abs(xh * c2))
+            wide = np.abs(gi) * b
+            # (its own rounding: a handful of float32 operations, k = 4 of S, then one rounding to bf16)
+            self.close(stage + ":apply(composite)", "conv16", dY_name, dY, o, So, half_ulp=True, extra=wide, k=K_ELEM)
+            if L.b:
+                self.close(stage + ":apply(composite)", "sums", L.b, self.grad(L.b), o.sum(ax),
+                           np.abs(o).sum(ax) + So.sum(ax) * K_ELEM / K_CONTRACTION,
+                           extra=wide.sum(ax))
+        e, S = wgrad_stage(x, dY, self.param(L.w).shape, L.stride, L.pad)
+        self.close(stage + ":wgrad", "f32", L.w, self.grad(L.w), e, S)
+
+    def padding(self):
+        for when in ("pad_fwd", "pad_bwd"):
+            for name, v in self.T.get(when, {}).items():
+                nz = int(np.count_nonzero(np.nan_to_num(np.asarray(v), nan=1.0)))
+                self._add("%s" % when, "pad", name + ":pad", float(nz), 0.0, "%d non-zero padding lanes" % nz if nz else "")
+
+    # -- reporting
+    def failures(self):
+        return [f for f in self.findings if not f.ok]
+
+    def failed_stages(self):
+        return sorted({f.stage.split(":")[0] for f in self.failures()})
+
+    def worst_per_class(self):
+        out = OrderedDict()
+        for f in self.findings:
+            if f.klass not in out or f.ratio > out[f.klass].ratio:
+                out[f.klass] = f
+        return out
+
+    def report(self):
+        return [f.line(self.c.id, self.TAG) for f in self.worst_per_class().values()]
+
+
+class Checker(Criteria):
+    """Runs the stage table of one case over a tensor dictionary T (device or stand-in):
+       T[name]            NHWC float32 arrays under the debug_tensor names, "logits", "dlogits", "x"
+       T["chan"][i]       split_chan(chan.<i>)
+       T["grad"][name]    the gradients in the reference's layout
+       T["pad_fwd"] / T["pad_bwd"][name]   the padding lanes after the forward / the backward pass
+    ``state``: the parameters.  findings: one Finding per (stage, output)."""
+
+    def __init__(self, case, state, T):
+        self.c, self.T = case._replace(slope=float(np.float32(case.slope))), T      # (the slope as the device's float holds it)
+        self.st = {k: v.numpy() if hasattr(v, "numpy") else np.asarray(v) for k, v in state.items()}
+        self.g = gates(case)
+        super().__init__()
+        self.operand_undecided = 0        # elements of an operand rounded in registers next to a bf16 boundary (they widen bounds)
+        self.rows = []
+
     # -- stages
     def conv_bn(self, stage, block, which, segs, out_name):
         """conv3x3 + bias of [segs] -> out_name, its BatchNorm statistics and coefficients."""
@@ -541,10 +628,7 @@ class Checker:
         else:
             self.close(stage, "f32", out_name, Y, e, S)
         ch = self.chan(i)
-        mean, invstd, mabs = stats_stage(Y)                     # of the STORED values (conv_planes.hip: rounded first, then summed)
-        self.close(stage + ":stats", "stats", "chan.%d.mean" % i, ch["mean"], mean, mabs)
-        self._add(stage + ":stats", "stats", "chan.%d.invstd" % i, float(np.abs(ch["invstd"] / invstd - 1).max()) / INVSTD_RTOL * K_CONTRACTION,
-                  K_CONTRACTION)
+        self.stats(stage, i, ch, Y)
         sc, sh = bn_coeffs32(self.param("%s.%d.weight" % (p, bi)), self.param("%s.%d.bias" % (p, bi)), ch["mean"], ch["invstd"])
         self.exact(stage + ":coeffs", "chan.%d.scale" % i, ch["scale"], sc)
         self.exact(stage + ":coeffs", "chan.%d.shift" % i, ch["shift"], sh)
@@ -609,48 +693,11 @@ class Checker:
         self.close("head_fwd", "f32", "logits", T["logits"], e, S)
 
     def bn_backward(self, stage, block, which, dA, Y_name, x_segs, dY_name, dA_bound=None):
-        """BatchNorm backward of convs[i] + its conv's weight and bias gradients.  dA: the stored gradient w.r.t. the activated
-        output (exact), or with dA_bound the float64 oracle of a gradient that cannot be read (composite row)."""
-        c, T = self.c, self.T
-        i = conv_index(c, block, which)
-        p, ci, bi = conv_prefix(c, i)
-        ch, Y = self.chan(i), np.asarray(T[Y_name], np.float64)
-        gamma = self.param("%s.%d.weight" % (p, bi))
-        mask = self._mask(T[Y_name], ch)
-        f = np.where(mask, 1.0, c.slope)
-        dz = np.asarray(dA, np.float64) * f
-        xh = (Y - ch["mean"].astype(np.float64)) * ch["invstd"].astype(np.float64)
-        M = Y.size // Y.shape[-1]
-        ax = (0, 1, 2)
-        b = np.zeros_like(dz) if dA_bound is None else np.asarray(dA_bound, np.float64) * f
-        s1, s2, S1, S2 = dz.sum(ax), (dz * xh).sum(ax), np.abs(dz).sum(ax), np.abs(dz * xh).sum(ax)
-        w1, w2 = b.sum(ax), (b * np.abs(xh)).sum(ax)
-        st = stage + ":sums"
-        self.close(st, "sums", "chan.%d.c1" % i, ch["c1"], s1 / M, S1 / M, extra=w1 / M)
-        self.close(st, "sums", "chan.%d.c2" % i, ch["c2"], s2 / M, S2 / M, extra=w2 / M)
-        self.close(st, "sums", "%s.%d.bias" % (p, bi), self.grad("%s.%d.bias" % (p, bi)), s1, S1, extra=w1)
-        self.close(st, "sums", "%s.%d.weight" % (p, bi), self.grad("%s.%d.weight" % (p, bi)), s2, S2, extra=w2)
-        dY = T[dY_name]
-        if dA_bound is None:
-            o = bn_apply32(dA, T[Y_name], ch, gamma, c.slope)
-            self.exact(stage + ":apply", dY_name, dY, rne(o))
-            o64 = o.astype(np.float64)
-            self.close(stage + ":apply", "sums", "%s.%d.bias" % (p, ci), self.grad("%s.%d.bias" % (p, ci)), o64.sum(ax), np.abs(o64).sum(ax))
-        else:
-            gi = gamma.astype(np.float64) * ch["invstd"].astype(np.float64)
-            c1, c2 = ch["c1"].astype(np.float64), ch["c2"].astype(np.float64)
-            o = gi * (dz - c1 - xh * c2)
-            So = np.abs(gi) * (np.abs(dz) + np.abs(c1) + np.abs(xh * c2))
-            wide = np.abs(gi) * b
-            # (its own rounding: a handful of float32 operations, k = 4 of S, then one rounding to bf16)
-            self.close(stage + ":apply(composite)", "conv16", dY_name, dY, o, So, half_ulp=True, extra=wide, k=K_ELEM)
-            self.close(stage + ":apply(composite)", "sums", "%s.%d.bias" % (p, ci), self.grad("%s.%d.bias" % (p, ci)), o.sum(ax),
-                       np.abs(o).sum(ax) + So.sum(ax) * K_ELEM / K_CONTRACTION,
-                       extra=wide.sum(ax))
-        x = np.concatenate([T[s] for s in x_segs], -1)
-        wn = "%s.%d.weight" % (p, ci)
-        e, S = wgrad3x3_stage(x, dY, self.param(wn).shape)
-        self.close(stage + ":wgrad", "f32", wn, self.grad(wn), e, S)
+        """BatchNorm backward of convs[i] + its conv's weight and bias gradients (Criteria.bn_backward_layer)."""
+        i = conv_index(self.c, block, which)
+        p, ci, bi = conv_prefix(self.c, i)
+        L = Layer(i, "%s.%d.weight" % (p, ci), "%s.%d.bias" % (p, ci), "%s.%d.weight" % (p, bi), "%s.%d.bias" % (p, bi), 1, 1)
+        self.bn_backward_layer(stage, L, dA, Y_name, np.concatenate([self.T[s] for s in x_segs], -1), dY_name, dA_bound)
 
     def dgrad(self, stage, block, which, dY_name, out_name, half):
         """Input gradient of convs[i] from its stored dY: -> (e, bound) and, if out_name is readable, its check."""
@@ -738,34 +785,11 @@ class Checker:
             if l > 1:
                 self.dgrad("enc%d.dgrad1" % l, b, 0, dYb, "dpool.%d" % (l - 1), g["g16"])
 
-    def padding(self):
-        for when in ("pad_fwd", "pad_bwd"):
-            for name, v in self.T.get(when, {}).items():
-                nz = int(np.count_nonzero(np.nan_to_num(np.asarray(v), nan=1.0)))
-                self._add("%s" % when, "pad", name + ":pad", float(nz), 0.0, "%d non-zero padding lanes" % nz if nz else "")
-
     def run(self):
         self.forward()
         self.backward()
         self.padding()
         return self
-
-    # -- reporting
-    def failures(self):
-        return [f for f in self.findings if not f.ok]
-
-    def failed_stages(self):
-        return sorted({f.stage.split(":")[0] for f in self.failures()})
-
-    def worst_per_class(self):
-        out = OrderedDict()
-        for f in self.findings:
-            if f.klass not in out or f.ratio > out[f.klass].ratio:
-                out[f.klass] = f
-        return out
-
-    def report(self):
-        return [f.line(self.c.id) for f in self.worst_per_class().values()]
 
 
 def stage_table(c):
@@ -876,7 +900,17 @@ class StandIn:
         self.st = {k: v.numpy() if hasattr(v, "numpy") else np.asarray(v) for k, v in state.items()}
         self.x, self.y = np.asarray(x, np.float32), np.asarray(y)
         self.mut = mutate or {}
-        self.T = {"x": self.x, "chan": [None] * (4 * case.depth + 2), "grad": {}, "pad_fwd": OrderedDict(), "pad_bwd": OrderedDict()}
+        self.T = {"x": self.x, "chan": [None] * self.n_convs(), "grad": {}, "pad_fwd": OrderedDict(), "pad_bwd": OrderedDict()}
+
+    # the layers' places in the device's `convs` (the ResNet-encoder stand-in of tests/resnet_bf16_stages.py has other ones)
+    def n_convs(self):
+        return 4 * self.c.depth + 2
+
+    def ci(self, block, which):
+        return conv_index(self.c, block, which)
+
+    def cp(self, i):
+        return conv_prefix(self.c, i)
 
     # float32 contractions on bf16-rounded operands
     @staticmethod
@@ -901,8 +935,8 @@ class StandIn:
 
     def conv_bn(self, block, which, segs, out_name):
         c, T = self.c, self.T
-        i = conv_index(c, block, which)
-        p, ci, bi = conv_prefix(c, i)
+        i = self.ci(block, which)
+        p, ci, bi = self.cp(i)
         x = np.concatenate([T[s] for s in segs], -1)
         acc = self._n32(F.conv2d(self._t32(x), self._wb("%s.%d.weight" % (p, ci)), torch.from_numpy(self.st["%s.%d.bias" % (p, ci)]), padding=1))
         Y = self.store16(out_name, acc) if self.g["y16"] else acc
@@ -924,14 +958,19 @@ class StandIn:
     def double_conv(self, block, segs):
         Y1, A1, Y2, _, _ = block_names(block)
         self.conv_bn(block, 0, segs, Y1)
-        self.act(Y1, conv_index(self.c, block, 0), A1)
+        self.act(Y1, self.ci(block, 0), A1)
         self.conv_bn(block, 1, [A1], Y2)
-        return Y2, conv_index(self.c, block, 1)
+        return Y2, self.ci(block, 1)
 
     def forward(self):
         c, T, g, D = self.c, self.T, self.g, self.c.depth
         T["xin"] = self.hook("out:xin", self.store16("xin", self.x))
-        cur = "xin"
+        self.forward_decoder(self.forward_encoder("xin"))
+        self.record_pads("pad_fwd", forward_only=True)
+
+    def forward_encoder(self, cur):
+        """-> the name of the bottleneck's input; leaves skip.<l>."""
+        c, T, D = self.c, self.T, self.c.depth
         for l in range(1, D + 1):
             Y2, i2 = self.double_conv(("enc", l), [cur])
             ch = T["chan"][i2]
@@ -940,6 +979,10 @@ class StandIn:
             T["skip.%d" % l] = self.hook("out:skip.%d" % l, rne(a))
             T["pooled.%d" % l] = self.hook("out:pooled.%d" % l, rne(a.reshape(N, H // 2, 2, W // 2, 2, C).max((2, 4))))
             cur = "pooled.%d" % l
+        return cur
+
+    def forward_decoder(self, cur):
+        c, T, g, D = self.c, self.T, self.g, self.c.depth
         prevY, prevI = self.double_conv(("bott",), [cur])
         for l in range(D, 0, -1):
             ch = T["chan"][prevI]
@@ -958,7 +1001,6 @@ class StandIn:
         a, _ = act32(T[prevY], ch["scale"], ch["shift"], c.slope)
         w = self.st["final_conv.weight"].reshape(-1)
         T["logits"] = ((a * w).sum(-1, keepdims=True, dtype=np.float32) + self.st["final_conv.bias"][0]).astype(np.float32)
-        self.record_pads("pad_fwd", forward_only=True)
 
     def record_pads(self, when, forward_only=False):
         for name, C in plane_names(self.c).items():
@@ -978,8 +1020,8 @@ class StandIn:
 
     def bn_backward(self, block, which, dA, Y_name, x_segs, dY_name):
         c, T = self.c, self.T
-        i = conv_index(c, block, which)
-        p, ci, bi = conv_prefix(c, i)
+        i = self.ci(block, which)
+        p, ci, bi = self.cp(i)
         ch, Y = T["chan"][i], T[Y_name]
         z = f32(Y) * ch["scale"] + ch["shift"]
         dz = np.where(z > 0, f32(dA), f32(dA) * np.float32(c.slope)).astype(np.float64)
@@ -998,16 +1040,22 @@ class StandIn:
         T["grad"][wn] = torch.nn.grad.conv2d_weight(self._t32(x), self.st[wn].shape, self._t32(T[dY_name]), padding=1).numpy()
 
     def dgrad(self, block, which, dY_name, out_name, half):
-        p, ci, _ = conv_prefix(self.c, conv_index(self.c, block, which))
+        p, ci, _ = self.cp(self.ci(block, which))
         acc = self._n32(F.conv_transpose2d(self._t32(self.T[dY_name]), self._wb("%s.%d.weight" % (p, ci)), padding=1))
         out = self.store16(out_name, acc) if half else acc
         return self.hook("out:" + out_name, out)
 
     def backward(self):
-        c, T, g, D = self.c, self.T, self.g, self.c.depth
         self.loss_turnaround()
+        self.backward_decoder("pooled.%d" % self.c.depth)
+        self.backward_encoder()
+        self.record_pads("pad_bwd")
+
+    def backward_decoder(self, bott_in):
+        """Head, decoders, bottleneck -> dconcat.<l>, dpool.<depth>."""
+        c, T, g, D = self.c, self.T, self.g, self.c.depth
         d = T["dlogits"]
-        ch = T["chan"][conv_index(c, ("dec", 1), 1)]
+        ch = T["chan"][self.ci(("dec", 1), 1)]
         a, _ = act32(T["decY2.1"], ch["scale"], ch["shift"], c.slope)
         T["grad"]["final_conv.weight"] = (d.astype(np.float64) * a).sum((0, 1, 2)).astype(np.float32).reshape(self.st["final_conv.weight"].shape)
         T["grad"]["final_conv.bias"] = np.array([d.astype(np.float64).sum()], np.float32)
@@ -1024,7 +1072,7 @@ class StandIn:
             dUp = T["dconcat.%d" % l][..., :C]
             T["grad"]["decoder%d.up.bias" % l] = dUp.astype(np.float64).sum((0, 1, 2)).astype(np.float32)
             prev_block = ("bott",) if l == D else ("dec", l + 1)
-            prevY, prevI = block_names(prev_block)[2], conv_index(c, prev_block, 1)
+            prevY, prevI = block_names(prev_block)[2], self.ci(prev_block, 1)
             if g["ctp"]:
                 aop = T["upin.%d" % l]
             else:
@@ -1042,13 +1090,16 @@ class StandIn:
         Y1, A1, Y2, dYa, dYb = block_names(b)
         self.bn_backward(b, 1, T["gBottA"], Y2, [A1], dYa)
         T["gBottB"] = self.dgrad(b, 1, dYa, "gBottB", g["g16"])
-        self.bn_backward(b, 0, T["gBottB"], Y1, ["pooled.%d" % D], dYb)
+        self.bn_backward(b, 0, T["gBottB"], Y1, [bott_in], dYb)
         T["dpool.%d" % D] = self.dgrad(b, 0, dYb, "dpool.%d" % D, g["g16"])
+
+    def backward_encoder(self):
+        c, T, g, D = self.c, self.T, self.g, self.c.depth
         for l in range(D, 0, -1):
             b = ("enc", l)
             Y1, A1, Y2, dYa, dYb = block_names(b)
             C = c.feat << (l - 1)
-            ch = T["chan"][conv_index(c, b, 1)]
+            ch = T["chan"][self.ci(b, 1)]
             a, _ = act32(T[Y2], ch["scale"], ch["shift"], c.slope)
             N, H, W, _ = a.shape
             aw = a.reshape(N, H // 2, 2, W // 2, 2, C).transpose(0, 1, 3, 5, 2, 4).reshape(N, H // 2, W // 2, C, 4)
@@ -1060,7 +1111,6 @@ class StandIn:
             self.bn_backward(b, 0, T["gB.%d" % l], Y1, ["xin" if l == 1 else "pooled.%d" % (l - 1)], dYb)
             if l > 1:
                 T["dpool.%d" % (l - 1)] = self.dgrad(b, 0, dYb, "dpool.%d" % (l - 1), g["g16"])
-        self.record_pads("pad_bwd")
 
     def run(self):
         self.forward()
