@@ -662,6 +662,68 @@ int rfi_model_predict_flags_pol(rfi_model* m, const void* planes, int planes_mem
                                 double scale, const double (*params_host)[2], uint8_t* flags, int flags_mem, float* prob,
                                 int prob_mem);
 
+/* ---- validity-aware 8-channel input: prior flags and non-finite samples carried through the normalisation, the
+ *      gather and the prediction of 8-channel models.  With no flags and finite data the entry points above are the
+ *      ones to call, and nothing of theirs changes; these are separate kernels beside them.
+ *
+ *      Invalid visibility.  A visibility (one polarisation of one pixel) is INVALID when its prior flag is non-zero, or
+ *      its real part is non-finite, or its imaginary part is non-finite.  For real 8-channel input, polarisation p of a
+ *      pixel is invalid when its flag is set or channel 2 p or 2 p + 1 is non-finite.  Prior flags are bytes (non-zero
+ *      == flagged), RFI_VALID_FLAGS_POL: (n, 4, T, F), one per visibility, or RFI_VALID_FLAGS_BASELINE: (n, T, F), one
+ *      per pixel, applying to all four polarisations.  A NULL flags pointer means no prior flag: non-finite values only.
+ *
+ *      rfi_valid_map: the invalid map of device data in any of rfi_norm_apply's six source forms: map_dev (n, 4, pixels)
+ *      bytes, 1 == invalid, and counts[n] (host or device by counts_mem, or NULL), the invalid visibilities per sample.
+ *      One read of the data, one byte written per visibility; integer atomics only.  Stream-ordered; synchronises only
+ *      to hand host counts back.
+ *
+ *      rfi_valid_statistics: rfi_norm_statistics over the VALID scalars only (both scalars of a valid visibility,
+ *      neither of an invalid one).  Chunk i has the invalid map maps[i] (device, as rfi_valid_map writes it), the form
+ *      forms[i] of its scalars -- RFI_VALID_SRC_COMPLEX: interleaved (n, 4, pixels) pairs; RFI_VALID_SRC_PLANAR:
+ *      (n, 8, pixels); RFI_VALID_SRC_NHWC: (n, pixels, 8) -- and pixels[i]; counts[i] is a multiple of 8 pixels[i].
+ *      Segment and dataset modes as rfi_norm_statistics.  Per population: count is the number of valid scalars; min, max
+ *      and the six order statistics are exact over them, the brackets formed from the population's OWN valid count by
+ *      rfi_norm_bracket's fp64 rule, evaluated on the device (v = q (count - 1), ranks floor(v) and min(floor(v) + 1,
+ *      count - 1)); mean and population variance are two-pass fp64 sums over the same fixed 8192-scalar index tiles, an
+ *      invalid scalar contributing nothing, divided by count: bitwise reproducible and independent of chunking and launch
+ *      geometry.  When no scalar is invalid the whole record is bit-identical to rfi_norm_statistics'.  A population
+ *      with no valid scalar has count 0 and NaN in every other statistic.  nonfinite counts the non-finite scalars among
+ *      those the map calls valid (0 for a map from rfi_valid_map).  No floating-point atomics.  Synchronises.
+ *
+ *      rfi_valid_apply: rfi_norm_apply where both channels of an invalid visibility (map_dev, (n, 4, pixels)) are
+ *      written as `fill`, a float32 in normalised units; a valid scalar gets rfi_norm_apply's expression unchanged.  In
+ *      place under rfi_norm_apply's rule; the map must not overlap the destination.  Stream-ordered.
+ *
+ *      rfi_valid_gather: rfi_norm_gather with optional prior flags (n_samples, 4, C, T) or (n_samples, C, T), host or
+ *      device like `planes`, and `fill`.  Validity is decided inline from the loaded value and its flag byte; a pixel
+ *      past the view's edge stays the normalised value of 0 + 0j and counts as valid.
+ *
+ *      rfi_model_predict_flags_valid: rfi_model_predict_flags_pol with prior flags `prior` (streamed through the same
+ *      two-slot chunk upload as the planes when host memory) and `fill`: the network sees rfi_valid_gather's tiles, and
+ *      flags / prob are the model's on that input.  merged (optional, (n_samples, 4, C, T) bytes, host or device; 1
+ *      output channel only): merged[b][p] = flags[b] | invalid[b][p], one pass after each chunk's stitch, so a non-finite
+ *      or prior-flagged visibility comes back flagged.  The workspace bound counts the prior flag bytes and the merged
+ *      output next to rfi_model_predict_flags_pol's.  The (centre, scale) pairs are the caller's: for per-sample
+ *      normalisation take them from rfi_valid_statistics. ---- */
+enum { RFI_VALID_FLAGS_POL = 0, RFI_VALID_FLAGS_BASELINE = 1 };
+enum { RFI_VALID_SRC_COMPLEX = 0, RFI_VALID_SRC_PLANAR = 1, RFI_VALID_SRC_NHWC = 2 };
+int rfi_valid_map(rfi_ctx* ctx, const void* src_dev, int dtype, int src_layout, int n, int64_t pixels, const uint8_t* flags_dev,
+                  int flags_form, uint8_t* map_dev, int64_t* counts, int counts_mem);
+int rfi_valid_statistics(rfi_ctx* ctx, const void* const* chunks, const int64_t* counts, const uint8_t* const* maps,
+                         const int* forms, const int64_t* pixels, int n_chunks, int dtype, int64_t segment, int quantiles,
+                         rfi_norm_stats* out, int n_out);
+int rfi_valid_apply(rfi_ctx* ctx, const void* src_dev, int dtype, int src_layout, int n, int64_t pixels, double centre,
+                    double scale, const double* params_dev, const uint8_t* map_dev, float fill, float* dst_dev, int dst_layout);
+int rfi_valid_gather(rfi_ctx* ctx, const void* planes, int planes_mem, int dtype, int n_samples, int c, int t,
+                     const rfi_patch_src* table_host, int n, int ps, double centre, double scale,
+                     const double (*params_host)[2], const uint8_t* flags, int flags_mem, int flags_form, float fill,
+                     float* out_nhwc, int out_mem);
+int rfi_model_predict_flags_valid(rfi_model* m, const void* planes, int planes_mem, int dtype, int n_samples, int c, int t,
+                                  const rfi_tiling* tiling, int batch, int combine, float threshold, double centre,
+                                  double scale, const double (*params_host)[2], const uint8_t* prior, int prior_mem,
+                                  int prior_form, float fill, uint8_t* flags, int flags_mem, float* prob, int prob_mem,
+                                  uint8_t* merged, int merged_mem);
+
 /* ---- training augmentation (scripts/train_model.py:44-53,70-75, --augment): HorizontalFlip, VerticalFlip, Rotate and
  *      ShiftScaleRotate of a batch and its masks, as flips and ONE resampling through the composed affine transform.
  *      Distribution-level parity: the reference resamples once per transform with its library's own random stream.

@@ -34,6 +34,8 @@ class FlagStats(C.Structure):
 
 SIM_C128, SIM_C64, SIM_NCHW, SIM_NHWC = 0, 1, 2, 3
 NORM_NCHW, NORM_NHWC = 0, 1
+VALID_FLAGS_POL, VALID_FLAGS_BASELINE = 0, 1
+VALID_SRC_COMPLEX, VALID_SRC_PLANAR, VALID_SRC_NHWC = 0, 1, 2
 
 
 class NormStats(C.Structure):
@@ -235,6 +237,12 @@ _PROTOS = {
     "rfi_norm_gather": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, C.c_double, C.c_double, _vp, _vp, _i]),
     "rfi_model_predict_flags_pol": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(Tiling), _i, _i, _f, C.c_double, C.c_double, _vp,
                                          _vp, _i, _vp, _i]),
+    "rfi_valid_map": (_i, [_vp, _vp, _i, _i, _i, _i64, _vp, _i, _vp, _vp, _i]),
+    "rfi_valid_statistics": (_i, [_vp, _pvp, _pi64, _pvp, _pi, _pi64, _i, _i, _i64, _i, C.POINTER(NormStats), _i]),
+    "rfi_valid_apply": (_i, [_vp, _vp, _i, _i, _i, _i64, C.c_double, C.c_double, _vp, _vp, _f, _vp, _i]),
+    "rfi_valid_gather": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, C.c_double, C.c_double, _vp, _vp, _i, _i, _f, _vp, _i]),
+    "rfi_model_predict_flags_valid": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(Tiling), _i, _i, _f, C.c_double, C.c_double, _vp,
+                                           _vp, _i, _i, _f, _vp, _i, _vp, _i, _vp, _i]),
     "rfi_augment_params": (_i, [C.POINTER(AugmentConfig), C.c_uint64, _i, _i, _i, C.POINTER(C.c_int32), _pd]),
     "rfi_augment_batch": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, C.POINTER(AugmentConfig), C.c_uint64, _vp, _vp]),
     "rfi_sumthreshold_ladder": (_i, [C.POINTER(SumThresholdConfig), C.c_double, _i, _pd]),

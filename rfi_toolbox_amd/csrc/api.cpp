@@ -1074,6 +1074,31 @@ int rfi_norm_gather(rfi_ctx* ctx, const void* planes, int planes_mem, int dtype,
     });
 }
 
+int rfi_valid_gather(rfi_ctx* ctx, const void* planes, int planes_mem, int dtype, int n_samples, int c, int t,
+                     const rfi_patch_src* table_host, int n, int ps, double centre, double scale,
+                     const double (*params_host)[2], const uint8_t* flags, int flags_mem, int flags_form, float fill,
+                     float* out_nhwc, int out_mem) {
+    return guarded([&] {
+        RFI_REQUIRE(ctx && n >= 0 && planes && (n == 0 || (table_host && out_nhwc)), "valid_gather: null argument");
+        RFI_REQUIRE(dtype == RFI_C128 || dtype == RFI_C64, "valid_gather: planes must be complex128 or complex64");
+        RFI_REQUIRE(flags_form == RFI_VALID_FLAGS_POL || flags_form == RFI_VALID_FLAGS_BASELINE, "valid_gather: bad flags form");
+        if (n == 0) return;
+        check_table(table_host, n, n_samples, c, t, ps, "valid_gather");
+        RFI_REQUIRE((int64_t)n_samples * 4 * c * t < ((int64_t)1 << 40), "valid_gather: waterfall too large");
+        ctx->activate();
+        const size_t px = (size_t)n_samples * c * t;
+        const bool per_baseline = flags_form == RFI_VALID_FLAGS_BASELINE;
+        CallScope sc(ctx);
+        const void* pl = sc.in(planes, planes_mem, px * 4 * dtype_bytes(dtype));
+        const uint8_t* fl = sc.in(flags, flags_mem, px * (per_baseline ? 1 : 4));
+        const rfi_patch_src* tb = sc.in(table_host, RFI_HOST, (size_t)n);
+        const double* pr = sc.in(params_host ? params_host[0] : nullptr, RFI_HOST, (size_t)n_samples * 2);
+        float* dout = sc.out(out_nhwc, out_mem, (size_t)n * ps * ps * 8);
+        launch_pol_gather_valid(ctx, pl, dtype, c, t, tb, n, ps, centre, scale, pr, fl, per_baseline, fill, dout);
+        sc.finish();
+    });
+}
+
 namespace {
 // med / mad of every patch of w (n x per doubles) over its non-NaN values -> d_med, d_mad
 void median_and_mad(rfi_ctx* ctx, const double* w, int n, int per, bool finite_only, double* d_med, double* d_mad,
@@ -1388,6 +1413,99 @@ int rfi_norm_apply(rfi_ctx* ctx, const void* src_dev, int dtype, int src_layout,
                           dst_layout == RFI_NORM_NHWC);
     });
 }
+// ---- validity-aware 8-channel input (include/rfi_hip.h): the three entry points above with an invalid map
+namespace {
+// the argument checks rfi_norm_apply makes on a source, for `who`
+void check_valid_source(const char* who, rfi_ctx* ctx, int dtype, int src_layout, int n, int64_t pixels) {
+    const std::string w(who);
+    RFI_REQUIRE(ctx, w + ": null context");
+    RFI_REQUIRE(dtype >= RFI_C128 && dtype <= RFI_F32, w + ": dtype must be complex128, complex64, float64 or float32");
+    RFI_REQUIRE(src_layout == RFI_NORM_NCHW || src_layout == RFI_NORM_NHWC, w + ": bad source layout");
+    const bool cplx = dtype == RFI_C128 || dtype == RFI_C64;
+    RFI_REQUIRE(!cplx || src_layout == RFI_NORM_NCHW, w + ": complex input is (n, 4, T, F)");
+    RFI_REQUIRE(n >= 0 && pixels >= 1 && (double)n * (double)pixels < 549755813888.0, w + ": bad sizes");
+}
+}  // namespace
+int rfi_valid_map(rfi_ctx* ctx, const void* src_dev, int dtype, int src_layout, int n, int64_t pixels, const uint8_t* flags_dev,
+                  int flags_form, uint8_t* map_dev, int64_t* counts, int counts_mem) {
+    return guarded([&] {
+        check_valid_source("valid_map", ctx, dtype, src_layout, n, pixels);
+        RFI_REQUIRE(flags_form == RFI_VALID_FLAGS_POL || flags_form == RFI_VALID_FLAGS_BASELINE, "valid_map: bad flags form");
+        if (n == 0) return;
+        RFI_REQUIRE(src_dev && map_dev, "valid_map: null buffer");
+        RFI_REQUIRE(reinterpret_cast<uintptr_t>(src_dev) % 16 == 0, "valid_map: the source must be 16-byte aligned");
+        RFI_REQUIRE(cdiv(pixels, 256) <= 0x7fffffff, "valid_map: sample too large for one launch");
+        ctx->activate();
+        CallScope sc(ctx);
+        int64_t* dc = counts ? sc.out(counts, counts_mem, (size_t)n) : sc.temp<int64_t>((size_t)n);
+        launch_valid_map(ctx, src_dev, dtype, src_layout == RFI_NORM_NHWC, flags_dev, flags_form == RFI_VALID_FLAGS_BASELINE, n, pixels,
+                         map_dev, dc);
+        sc.finish();
+    });
+}
+int rfi_valid_statistics(rfi_ctx* ctx, const void* const* chunks, const int64_t* counts, const uint8_t* const* maps,
+                         const int* forms, const int64_t* pixels, int n_chunks, int dtype, int64_t segment, int quantiles,
+                         rfi_norm_stats* out, int n_out) {
+    return guarded([&] {
+        RFI_REQUIRE(ctx && chunks && counts && maps && forms && pixels && out, "valid_statistics: null argument");
+        RFI_REQUIRE(dtype == RFI_F64 || dtype == RFI_F32, "valid_statistics: dtype must be float64 or float32 (pass complex data as its real scalars)");
+        RFI_REQUIRE(n_chunks >= 1 && n_chunks <= 65536, "valid_statistics: needs 1 to 65536 chunks");
+        RFI_REQUIRE(segment >= 0, "valid_statistics: negative segment");
+        RFI_REQUIRE(segment == 0 || n_chunks == 1, "valid_statistics: the per-sample mode takes one chunk");
+        const size_t esz = dtype == RFI_F32 ? 4 : 8;
+        std::vector<norm_chunk> table((size_t)n_chunks + 1);
+        std::vector<valid_chunk> vtable((size_t)n_chunks);
+        int64_t total = 0;
+        for (int i = 0; i < n_chunks; ++i) {
+            RFI_REQUIRE(counts[i] >= 0 && (counts[i] == 0 || (chunks[i] && maps[i])), "valid_statistics: bad chunk");
+            RFI_REQUIRE(reinterpret_cast<uintptr_t>(chunks[i]) % esz == 0, "valid_statistics: misaligned chunk");
+            RFI_REQUIRE(forms[i] == RFI_VALID_SRC_COMPLEX || forms[i] == RFI_VALID_SRC_PLANAR || forms[i] == RFI_VALID_SRC_NHWC,
+                        "valid_statistics: bad source form");
+            RFI_REQUIRE(pixels[i] >= 1 && counts[i] % (8 * pixels[i]) == 0,
+                        "valid_statistics: a chunk must be whole samples of 8 x pixels scalars");
+            table[i] = norm_chunk{chunks[i], total};
+            vtable[i] = valid_chunk{maps[i], pixels[i], forms[i], 0};
+            total += counts[i];
+        }
+        table[n_chunks] = norm_chunk{nullptr, total};
+        RFI_REQUIRE(total >= 1, "valid_statistics: no data");
+        const int64_t seg = segment ? segment : total;
+        RFI_REQUIRE(total % seg == 0, "valid_statistics: the chunk is not a whole number of segments");
+        const int64_t pops = total / seg;
+        RFI_REQUIRE(pops <= 4096, "valid_statistics: at most 4096 populations per call");
+        RFI_REQUIRE(n_out == pops, "valid_statistics: n_out must be the number of populations");
+        ctx->activate();
+        CallScope sc(ctx);
+        const norm_chunk* tb = sc.in(table.data(), RFI_HOST, table.size());
+        const valid_chunk* vb = sc.in(vtable.data(), RFI_HOST, vtable.size());
+        void* ws = sc.temp<void>(valid_stats_ws_bytes((int)pops, seg));
+        rfi_norm_stats* dout = sc.out(out, RFI_HOST, (size_t)pops);
+        launch_valid_stats(ctx, tb, vb, n_chunks, dtype == RFI_F32, seg, (int)pops, quantiles != 0, ws, dout);
+        sc.finish();
+    });
+}
+int rfi_valid_apply(rfi_ctx* ctx, const void* src_dev, int dtype, int src_layout, int n, int64_t pixels, double centre,
+                    double scale, const double* params_dev, const uint8_t* map_dev, float fill, float* dst_dev, int dst_layout) {
+    return guarded([&] {
+        check_valid_source("valid_apply", ctx, dtype, src_layout, n, pixels);
+        RFI_REQUIRE(dst_layout == RFI_NORM_NCHW || dst_layout == RFI_NORM_NHWC, "valid_apply: bad destination layout");
+        if (n == 0) return;
+        RFI_REQUIRE(src_dev && dst_dev && map_dev, "valid_apply: null buffer");
+        RFI_REQUIRE(reinterpret_cast<uintptr_t>(src_dev) % 16 == 0 && reinterpret_cast<uintptr_t>(dst_dev) % 16 == 0,
+                    "valid_apply: buffers must be 16-byte aligned");
+        const size_t sbytes = (size_t)n * (size_t)pixels * 8 * (dtype == RFI_C64 || dtype == RFI_F32 ? 4 : 8);
+        const size_t dbytes = (size_t)n * (size_t)pixels * 8 * 4, mbytes = (size_t)n * (size_t)pixels * 4;
+        const char *s0 = static_cast<const char*>(src_dev), *d0 = reinterpret_cast<const char*>(dst_dev);
+        const char* m0 = reinterpret_cast<const char*>(map_dev);
+        const bool same = s0 == d0 && dtype == RFI_F32 && src_layout == dst_layout;
+        RFI_REQUIRE(same || s0 + sbytes <= d0 || d0 + dbytes <= s0,
+                    "valid_apply: source and destination overlap (in place needs the same dtype and layout)");
+        RFI_REQUIRE(m0 + mbytes <= d0 || d0 + dbytes <= m0, "valid_apply: the invalid map overlaps the destination");
+        ctx->activate();
+        launch_valid_apply(ctx, src_dev, dtype, src_layout == RFI_NORM_NHWC, map_dev, fill, n, pixels, centre, scale, params_dev,
+                           dst_dev, dst_layout == RFI_NORM_NHWC);
+    });
+}
 int rfi_threshold_logits(rfi_ctx* ctx, const float* logits_dev, int64_t count, float threshold,
                          uint8_t* mask_dev) {
     return guarded([&] {
@@ -1483,12 +1601,24 @@ struct PredictGather {
     int in_ch;                 // channels of the image batch
     int pols;                  // complex planes per unit
     int max_out = 1;           // output channels a model may have: each is stitched into a plane of its own
+    // optional second input streamed next to the planes (prior flags; aux_unit bytes per unit) and optional second
+    // output written after the stitch (merged_unit bytes per unit); both null for the entry points without them
+    const uint8_t* aux = nullptr;
+    int aux_mem = RFI_HOST;
+    size_t aux_unit = 0;
+    uint8_t* merged = nullptr;
+    int merged_mem = RFI_HOST;
+    size_t merged_unit = 0;
     // private device workspace for image batches of nb patches out of n_units units, filled once by setup()
     virtual size_t ws_bytes(int nb, int n_units) const = 0;
     virtual void setup(rfi_ctx*, void*, int) {}
     // patches tb[0 .. nv) of the chunk at `pl`, whose first unit is unit `first` of the call -> img (nv, ps, ps, in_ch)
     virtual void run(rfi_ctx* ctx, const void* pl, int dtype, int first, int c, int t, const rfi_patch_src* tb, int nv, int ps,
                      void* ws, float* img) const = 0;
+    // the chunk's part of `aux` on the device, before the chunk's first run()
+    virtual void bind(const uint8_t*) {}
+    // after the stitch of a chunk of np units at `pl`: its stitched flags -> its part of `merged`, both on the device
+    virtual void merge(rfi_ctx*, const void*, int, int, int, int, const uint8_t*, uint8_t*) const {}
     virtual ~PredictGather() = default;
 };
 
@@ -1519,6 +1649,31 @@ struct PolGather final : PredictGather {            // the four polarisations, n
     }
 };
 
+struct ValidGather final : PredictGather {          // PolGather with prior flags and non-finite values (rfi_valid_gather's kernel)
+    double centre, scale;
+    const double* params_host;
+    bool per_baseline;
+    float fill;
+    const uint8_t* cur = nullptr;                   // the current chunk's prior flags on the device
+    ValidGather(double ce, double sc, const double* ph, bool pb, float fi) : centre(ce), scale(sc), params_host(ph), per_baseline(pb), fill(fi) {
+        who = "predict_flags_valid"; unit = "sample"; in_ch = 8; pols = 4; max_out = 8;
+    }
+    size_t ws_bytes(int, int n_units) const override { return params_host ? (size_t)n_units * 2 * sizeof(double) : 0; }
+    void setup(rfi_ctx* ctx, void* ws, int n_units) override {
+        if (params_host)
+            RFI_CHECK_HIP(hipMemcpyAsync(ws, params_host, (size_t)n_units * 2 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    }
+    void bind(const uint8_t* chunk_flags) override { cur = chunk_flags; }
+    void run(rfi_ctx* ctx, const void* pl, int dtype, int first, int c, int t, const rfi_patch_src* tb, int nv, int ps, void* ws,
+             float* img) const override {
+        launch_pol_gather_valid(ctx, pl, dtype, c, t, tb, nv, ps, centre, scale,
+                                params_host ? static_cast<const double*>(ws) + 2 * (size_t)first : nullptr, cur, per_baseline, fill, img);
+    }
+    void merge(rfi_ctx* ctx, const void* pl, int dtype, int np, int c, int t, const uint8_t* stitched, uint8_t* out) const override {
+        launch_valid_merge(ctx, pl, dtype, np, (int64_t)c * t, cur, per_baseline, stitched, out);
+    }
+};
+
 void predict_flags_driver(rfi_model* m, PredictGather& g, const void* planes, int planes_mem, int dtype, int n_planes, int c,
                           int t, const rfi_tiling* tiling, int batch, int combine, float threshold, uint8_t* flags,
                           int flags_mem, float* prob, int prob_mem) {
@@ -1546,9 +1701,13 @@ void predict_flags_driver(rfi_model* m, PredictGather& g, const void* planes, in
     const size_t K = (size_t)m->out_ch;
     const size_t plane_px = (size_t)c * t, plane_bytes = plane_px * esz * g.pols, patch_px = (size_t)ps * ps, out_px = plane_px * K;
     const bool host_in = planes_mem == RFI_HOST, host_fl = flags_mem == RFI_HOST, host_pr = prob && prob_mem == RFI_HOST;
+    const bool host_ax = g.aux && g.aux_mem == RFI_HOST, host_mg = g.merged && g.merged_mem == RFI_HOST;
+    const bool host_out = host_fl || host_pr || host_mg;
+    RFI_REQUIRE(!g.merged || K == 1, who + ": merged flags need a model with 1 output channel");
     const size_t out_px_bytes = (host_fl ? 1 : 0) + (host_pr ? 4 : 0);
     const size_t per_plane = (size_t)ppp * (patch_px * K * sizeof(float) + sizeof(rfi_patch_src)) +
-                             (host_in ? 2 * plane_bytes : 0) + 2 * out_px * out_px_bytes;
+                             (host_in ? 2 * plane_bytes : 0) + 2 * out_px * out_px_bytes +
+                             (host_ax ? 2 * g.aux_unit : 0) + (host_mg ? 2 * g.merged_unit : 0);
     RFI_REQUIRE(per_plane <= kPredictBudget,
                 who + ": one " + (g.pols > 1 ? std::to_string(g.pols) + " x " : std::string()) + std::to_string(c) + " x " +
                     std::to_string(t) + " " + g.unit + " needs " +
@@ -1575,12 +1734,14 @@ void predict_flags_driver(rfi_model* m, PredictGather& g, const void* planes, in
     // the chunk's patch table (plane indices local to the chunk; the same for every chunk, a prefix for the last)
     const std::vector<rfi_patch_src> table = tile_table(make_tile_grid(c, t, *tiling), k);
 
-    // one grow-only scratch region: [table | the gather's own | images | patch outputs | 2 plane slots | 2 output slots]
+    // one grow-only scratch region: [table | the gather's own | images | patch outputs | 2 plane slots | 2 output slots |
+    // 2 slots of the second input | 2 slots of the second output]
     const size_t b_table = al(table.size() * sizeof(rfi_patch_src)), b_gws = al(g.ws_bytes(nb, n_planes));
     const size_t b_img = al((size_t)nb * patch_px * g.in_ch * sizeof(float)), b_out = al((size_t)chunk_patches * patch_px * K * sizeof(float));
     const size_t b_in = host_in ? al((size_t)k * plane_bytes) : 0;
     const size_t b_fl = host_fl ? al((size_t)k * out_px) : 0, b_pr = host_pr ? al((size_t)k * out_px * sizeof(float)) : 0;
-    char* base = static_cast<char*>(ctx->get_scratch(b_table + b_gws + b_img + b_out + 2 * (b_in + b_fl + b_pr)));
+    const size_t b_ax = host_ax ? al((size_t)k * g.aux_unit) : 0, b_mg = host_mg ? al((size_t)k * g.merged_unit) : 0;
+    char* base = static_cast<char*>(ctx->get_scratch(b_table + b_gws + b_img + b_out + 2 * (b_in + b_fl + b_pr + b_ax + b_mg)));
     auto* d_table = reinterpret_cast<rfi_patch_src*>(base);
     void* d_gws = base + b_table;
     float* d_img = reinterpret_cast<float*>(base + b_table + b_gws);
@@ -1589,6 +1750,8 @@ void predict_flags_driver(rfi_model* m, PredictGather& g, const void* planes, in
     auto in_slot = [&](int s) { return slots + s * b_in; };
     auto fl_slot = [&](int s) { return reinterpret_cast<uint8_t*>(slots + 2 * b_in + s * b_fl); };
     auto pr_slot = [&](int s) { return reinterpret_cast<float*>(slots + 2 * (b_in + b_fl) + s * b_pr); };
+    auto ax_slot = [&](int s) { return reinterpret_cast<uint8_t*>(slots + 2 * (b_in + b_fl + b_pr) + s * b_ax); };
+    auto mg_slot = [&](int s) { return reinterpret_cast<uint8_t*>(slots + 2 * (b_in + b_fl + b_pr + b_ax) + s * b_mg); };
     RFI_CHECK_HIP(hipMemcpyAsync(d_table, table.data(), table.size() * sizeof(rfi_patch_src), hipMemcpyHostToDevice,
                                  ctx->stream));
     RFI_CHECK_HIP(hipMemsetAsync(d_img, 0, b_img, ctx->stream));
@@ -1603,9 +1766,13 @@ void predict_flags_driver(rfi_model* m, PredictGather& g, const void* planes, in
         const int s = ci & 1;
         if (ci >= 2) RFI_CHECK_HIP(hipStreamWaitEvent(cs.s, ev.e[2 + s], 0));
         OnStream on(ctx, cs.s);
-        ProfScope pf(ctx, FAM_PREPROCESS, 0, (double)planes_in(ci) * plane_bytes, "predict_upload");
-        RFI_CHECK_HIP(hipMemcpyAsync(in_slot(s), src + (size_t)ci * k * plane_bytes, (size_t)planes_in(ci) * plane_bytes,
-                                     hipMemcpyHostToDevice, cs.s));
+        ProfScope pf(ctx, FAM_PREPROCESS, 0, (double)planes_in(ci) * ((host_in ? plane_bytes : 0) + (host_ax ? g.aux_unit : 0)), "predict_upload");
+        if (host_in)
+            RFI_CHECK_HIP(hipMemcpyAsync(in_slot(s), src + (size_t)ci * k * plane_bytes, (size_t)planes_in(ci) * plane_bytes,
+                                         hipMemcpyHostToDevice, cs.s));
+        if (host_ax)
+            RFI_CHECK_HIP(hipMemcpyAsync(ax_slot(s), g.aux + (size_t)ci * k * g.aux_unit, (size_t)planes_in(ci) * g.aux_unit,
+                                         hipMemcpyHostToDevice, cs.s));
         RFI_CHECK_HIP(hipEventRecord(ev.e[s], cs.s));
     };
     auto download = [&](int ci) {
@@ -1613,21 +1780,25 @@ void predict_flags_driver(rfi_model* m, PredictGather& g, const void* planes, in
         const size_t px = (size_t)planes_in(ci) * out_px, off = (size_t)ci * k * out_px;
         RFI_CHECK_HIP(hipStreamWaitEvent(cs.s, ev.e[4 + s], 0));
         OnStream on(ctx, cs.s);
-        ProfScope pf(ctx, FAM_PREPROCESS, 0, (double)px * out_px_bytes, "predict_download");
+        ProfScope pf(ctx, FAM_PREPROCESS, 0, (double)px * out_px_bytes + (host_mg ? (double)planes_in(ci) * g.merged_unit : 0.0), "predict_download");
         if (host_fl) RFI_CHECK_HIP(hipMemcpyAsync(flags + off, fl_slot(s), px, hipMemcpyDeviceToHost, cs.s));
         if (host_pr) RFI_CHECK_HIP(hipMemcpyAsync(prob + off, pr_slot(s), px * sizeof(float), hipMemcpyDeviceToHost, cs.s));
+        if (host_mg)
+            RFI_CHECK_HIP(hipMemcpyAsync(g.merged + (size_t)ci * k * g.merged_unit, mg_slot(s), (size_t)planes_in(ci) * g.merged_unit,
+                                         hipMemcpyDeviceToHost, cs.s));
         RFI_CHECK_HIP(hipEventRecord(ev.e[6 + s], cs.s));
     };
     auto compute = [&](int ci) {
         const int s = ci & 1, np = planes_in(ci);
         const int64_t npatch = (int64_t)np * ppp;
         const void* pl = host_in ? static_cast<const void*>(in_slot(s)) : static_cast<const void*>(src + (size_t)ci * k * plane_bytes);
-        if (host_in) RFI_CHECK_HIP(hipStreamWaitEvent(ctx->stream, ev.e[s], 0));
-        if ((host_fl || host_pr) && ci >= 2) RFI_CHECK_HIP(hipStreamWaitEvent(ctx->stream, ev.e[6 + s], 0));
+        if (host_in || host_ax) RFI_CHECK_HIP(hipStreamWaitEvent(ctx->stream, ev.e[s], 0));
+        if (host_out && ci >= 2) RFI_CHECK_HIP(hipStreamWaitEvent(ctx->stream, ev.e[6 + s], 0));
+        if (g.aux) g.bind(host_ax ? ax_slot(s) : g.aux + (size_t)ci * k * g.aux_unit);
         for (int64_t p0 = 0; p0 < npatch; p0 += nb) {
             const int nv = (int)std::min<int64_t>(nb, npatch - p0);
             g.run(ctx, pl, dtype, ci * k, c, t, d_table + p0, nv, ps, d_gws, d_img);
-            if (p0 + nb >= npatch) RFI_CHECK_HIP(hipEventRecord(ev.e[2 + s], ctx->stream));
+            if (p0 + nb >= npatch && !g.merged) RFI_CHECK_HIP(hipEventRecord(ev.e[2 + s], ctx->stream));
             m->forward(d_img, nb, ps, ps, false);
             launch_copy_d2d(ctx, d_out + p0 * patch_px * K, m->buf(m->head_sigmoid ? m->probs : m->logits),
                             (size_t)nv * patch_px * K * sizeof(float));
@@ -1635,15 +1806,20 @@ void predict_flags_driver(rfi_model* m, PredictGather& g, const void* planes, in
         const size_t off = (size_t)ci * k * out_px;
         launch_stitch(ctx, d_out, kind, np, c, t, *tiling, combine, threshold, host_fl ? fl_slot(s) : flags + off,
                       prob ? (host_pr ? pr_slot(s) : prob + off) : nullptr, (int)K);
+        if (g.merged) {                       // (the merge reads the chunk's planes and prior flags once more: the slot is free after it)
+            g.merge(ctx, pl, dtype, np, c, t, host_fl ? fl_slot(s) : flags + off,
+                    host_mg ? mg_slot(s) : g.merged + (size_t)ci * k * g.merged_unit);
+            RFI_CHECK_HIP(hipEventRecord(ev.e[2 + s], ctx->stream));
+        }
         RFI_CHECK_HIP(hipEventRecord(ev.e[4 + s], ctx->stream));
     };
-    if (host_in) upload(0);
+    if (host_in || host_ax) upload(0);
     for (int ci = 0; ci < nchunks; ++ci) {
         compute(ci);
-        if (ci > 0 && (host_fl || host_pr)) download(ci - 1);
-        if (host_in && ci + 1 < nchunks) upload(ci + 1);
+        if (ci > 0 && host_out) download(ci - 1);
+        if ((host_in || host_ax) && ci + 1 < nchunks) upload(ci + 1);
     }
-    if (host_fl || host_pr) download(nchunks - 1);
+    if (host_out) download(nchunks - 1);
     RFI_CHECK_HIP(hipStreamSynchronize(cs.s));
     RFI_CHECK_HIP(hipStreamSynchronize(ctx->stream));
 }
@@ -1665,6 +1841,23 @@ int rfi_model_predict_flags_pol(rfi_model* m, const void* planes, int planes_mem
                                 int prob_mem) {
     return guarded([&] {
         PolGather g(centre, scale, params_host ? params_host[0] : nullptr);
+        predict_flags_driver(m, g, planes, planes_mem, dtype, n_samples, c, t, tiling, batch, combine, threshold, flags, flags_mem,
+                             prob, prob_mem);
+    });
+}
+
+int rfi_model_predict_flags_valid(rfi_model* m, const void* planes, int planes_mem, int dtype, int n_samples, int c, int t,
+                                  const rfi_tiling* tiling, int batch, int combine, float threshold, double centre,
+                                  double scale, const double (*params_host)[2], const uint8_t* prior, int prior_mem,
+                                  int prior_form, float fill, uint8_t* flags, int flags_mem, float* prob, int prob_mem,
+                                  uint8_t* merged, int merged_mem) {
+    return guarded([&] {
+        RFI_REQUIRE(prior_form == RFI_VALID_FLAGS_POL || prior_form == RFI_VALID_FLAGS_BASELINE, "predict_flags_valid: bad flags form");
+        const bool per_baseline = prior_form == RFI_VALID_FLAGS_BASELINE;
+        ValidGather g(centre, scale, params_host ? params_host[0] : nullptr, per_baseline, fill);
+        const size_t px = c > 0 && t > 0 ? (size_t)c * t : 0;
+        g.aux = prior; g.aux_mem = prior_mem; g.aux_unit = px * (per_baseline ? 1 : 4);
+        g.merged = merged; g.merged_mem = merged_mem; g.merged_unit = px * 4;
         predict_flags_driver(m, g, planes, planes_mem, dtype, n_samples, c, t, tiling, batch, combine, threshold, flags, flags_mem,
                              prob, prob_mem);
     });

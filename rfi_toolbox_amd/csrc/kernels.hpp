@@ -403,6 +403,22 @@ void launch_norm_stats(rfi_ctx* ctx, const norm_chunk* chunks_dev, int n_chunks,
 // src_nhwc, (n, px, 8); dst (n, 8, px) or (n, px, 8)
 void launch_norm_apply(rfi_ctx* ctx, const void* src, int dtype, bool src_nhwc, int n, int64_t px, double centre, double scale,
                        const double* params_dev, float* dst, bool dst_nhwc);
+// validity-aware counterparts (dataset_norm.hip; semantics in include/rfi_hip.h, "validity-aware 8-channel input").
+// An invalid map holds one byte per visibility, (n, 4, px), non-zero == invalid.  valid_dev[i] says where the bytes of
+// chunk i's scalars are: its map, its pixels per plane and the form of its scalars (complex pairs, 8 planes, or 8
+// contiguous channels per pixel).  launch_valid_stats is launch_norm_stats over the valid scalars, with the ranks
+// formed on the device from every population's own valid count; ws holds valid_stats_ws_bytes(pops, seg).
+struct valid_chunk { const uint8_t* map; int64_t px; int form; int pad_; };
+size_t valid_stats_ws_bytes(int pops, int64_t seg);
+void launch_valid_stats(rfi_ctx* ctx, const norm_chunk* chunks_dev, const valid_chunk* valid_dev, int n_chunks, bool f32, int64_t seg,
+                        int pops, bool quantiles, void* ws, rfi_norm_stats* out_dev);
+// map (n, 4, px) and counts_dev[n] (invalid visibilities per sample) from the data and optional prior flags: (n, 4, px),
+// or (n, px) with per_baseline, or null (non-finite values only); counts_dev is zeroed here
+void launch_valid_map(rfi_ctx* ctx, const void* src, int dtype, bool src_nhwc, const uint8_t* flags, bool per_baseline, int n,
+                      int64_t px, uint8_t* map, int64_t* counts_dev);
+// launch_norm_apply with both channels of an invalid visibility written as `fill`
+void launch_valid_apply(rfi_ctx* ctx, const void* src, int dtype, bool src_nhwc, const uint8_t* map, float fill, int n, int64_t px,
+                        double centre, double scale, const double* params_dev, float* dst, bool dst_nhwc);
 #if defined(__HIPCC__)
 // the normalised value of one source scalar, for every kernel that normalises (ns_apply_kernel, pol_gather_kernel): fp64
 // on the exact source value, a real division, one rounding; a pair with scale 0 stands for the all-zeros transform
@@ -417,6 +433,14 @@ __device__ __forceinline__ float norm_value(S x, double centre, double scale) {
 // sample replacing the scalars
 void launch_pol_gather(rfi_ctx* ctx, const void* planes, int dtype, int C, int T, const rfi_patch_src* table_dev, int n, int ps,
                        double centre, double scale, const double* params_dev, float* out_nhwc);
+// launch_pol_gather with validity decided inline (rfi_valid_gather): flags_dev (n_samples, 4, C, T) bytes, or
+// (n_samples, C, T) with per_baseline, or null; both channels of an invalid visibility are `fill`
+void launch_pol_gather_valid(rfi_ctx* ctx, const void* planes, int dtype, int C, int T, const rfi_patch_src* table_dev, int n, int ps,
+                             double centre, double scale, const double* params_dev, const uint8_t* flags_dev, bool per_baseline,
+                             float fill, float* out_nhwc);
+// merged (n_samples, 4, C, T) = model_flags (n_samples, C, T) | invalid, the invalid visibilities decided as above
+void launch_valid_merge(rfi_ctx* ctx, const void* planes, int dtype, int n_samples, int64_t px, const uint8_t* flags_dev,
+                        bool per_baseline, const uint8_t* model_flags, uint8_t* merged);
 // training augmentation (augment.hip): flips and one composed affine warp of x [n][h][w][c] float32 and y [n][h][w] bytes
 // into x_out / y_out (never in place); the transform of sample i is drawn in the kernel from (cfg, call, i).
 // augment_params_host evaluates the same draw on the host: gates [n][4], inv [n][6].  Semantics in include/rfi_hip.h.

@@ -27,7 +27,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (COMBINE_MAX, COMBINE_MEAN, COMPLEX_CODES, DEVICE, EDGE_PAD, EDGE_SHIFT, VALUES_LOGITS,
+from ._lib import (COMBINE_MAX, COMBINE_MEAN, COMPLEX_CODES, DEVICE, EDGE_PAD, EDGE_SHIFT, VALID_FLAGS_BASELINE, VALID_FLAGS_POL, VALUES_LOGITS,
                    VALUES_PROBS, Tiling, check, lib)
 from .runtime import DeviceArray, check_out, context_for, describe, is_torch, operand, result_buffer, torch
 
@@ -135,12 +135,33 @@ def _group_on_device(o, ctx, b0, b1, sample_shape):
     return ctx.to_device(o.keep.reshape((-1,) + tuple(sample_shape))[b0:b1])
 
 
-def _sample_pairs(normalizer, group):
+def _sample_pairs(normalizer, group, flags=None):
     """(len(group), 2) float64 (centre, scale) of every baseline of the DeviceArray `group` by its own statistics: what
-    ``Normalizer(method, "sample").fit(group)`` keeps.  Raises ValueError on non-finite input."""
+    ``Normalizer(method, "sample").fit(group, flags=flags)`` keeps.  Without `flags` it raises ValueError on non-finite
+    input; with them (the group's prior flags or "nonfinite") the invalid visibilities are left out."""
     from .preprocessing.normalization import sample_parameters
-    stats = normalizer.statistics(group, quantiles=normalizer.method == "robust_scale")
+    stats = normalizer.statistics(group, quantiles=normalizer.method == "robust_scale", flags=flags)
     return np.ascontiguousarray([sample_parameters(normalizer.method, st) for st in stats], dtype=np.float64).reshape(-1, 2)
+
+
+def _prior_flags(flags, shape, n, Cn, Tn):
+    """-> (form, array or None) of the `flags` argument of an 8-channel call on data of `shape`: VALID_FLAGS_POL for
+    flags of the data's shape, VALID_FLAGS_BASELINE for flags without the polarisation axis, (0, None) for "nonfinite".
+    ValueError / TypeError otherwise; no device is touched."""
+    if isinstance(flags, str):
+        if flags != "nonfinite":
+            raise ValueError(f"flags must be an array of prior flags or the string 'nonfinite', got {flags!r}")
+        return VALID_FLAGS_POL, None
+    got, fdt = describe(flags)[:2]
+    got = tuple(int(v) for v in got)
+    if fdt is None or fdt not in (np.dtype(np.uint8), np.dtype(np.bool_)):
+        raise TypeError(f"flags must be uint8 or bool, not {fdt}")
+    if got == tuple(shape):
+        return VALID_FLAGS_POL, flags
+    if got == tuple(shape[:-3]) + (Cn, Tn):
+        return VALID_FLAGS_BASELINE, flags
+    raise ValueError(f"flags must have the data's shape {tuple(shape)} (per polarisation) or {tuple(shape[:-3]) + (Cn, Tn)} (per "
+                     f"baseline), got shape {got}")
 
 
 def _as_bool(flags):
@@ -167,7 +188,7 @@ def _broadcast_pols(ctx, flags, shape):
 
 
 def predict_flags(model, data, patch_size=128, stride=None, views=1, combine="mean", threshold=0.5, batch_size=64,
-                  edge="pad", return_probabilities=False, normalizer=None, broadcast_pols=True, out="host"):
+                  edge="pad", return_probabilities=False, normalizer=None, broadcast_pols=True, out="host", flags=None, fill=0.0):
     """Flags of a whole observation from a segmentation model.
 
     ``data``: complex64 / complex128 visibilities, a NumPy array, a torch tensor (a CUDA tensor stays on the device) or
@@ -187,6 +208,16 @@ def predict_flags(model, data, patch_size=128, stride=None, views=1, combine="me
       A model with class-bit targets (``set_targets("class_bits")``) and K = 2 .. 8 output channels gives flags
       ``(B, K, C, T)`` / ``(K, C, T)``, one plane per class from the same tiling, combine rule and scalar ``threshold``,
       and probabilities of that shape; ``broadcast_pols`` does not apply to it and raises when passed as False.
+
+    ``flags`` (8 input channels only): the observation's prior flags, uint8 or bool, of ``data``'s shape (per
+    polarisation) or without the polarisation axis (per baseline: all four), e.g. ``MSLoader.load_flags()``; or the string
+    ``"nonfinite"``.  A visibility is then invalid when its prior flag is set or its real or imaginary part is
+    non-finite: it is left out of a sample-scope normalizer's statistics (``rfi_valid_statistics``) and enters the network
+    as ``fill`` (float32, normalised units).  The probabilities are the model's on that input.  With ``broadcast_pols``
+    and one output channel the returned flags are ``model_flags[b] | invalid[b, p]``: a prior-flagged or non-finite
+    visibility comes back flagged.  With ``broadcast_pols=False``, or a class-bit model with K > 1, the returned flags
+    are the model's alone.  With ``flags=None`` nothing changes: non-finite input raises ``ValueError`` with a
+    sample-scope normalizer and spreads through the network's receptive field otherwise.
 
     Tiling works on the last two axes as they are: a model trained on the simulator's ``(T, F)`` planes must be given
     observation planes in that orientation (``views=4`` covers both).  Results are NumPy arrays (for NumPy or CPU-tensor
@@ -216,6 +247,8 @@ def predict_flags(model, data, patch_size=128, stride=None, views=1, combine="me
     if not pol and (normalizer is not None or not broadcast_pols):
         raise ValueError("normalizer and broadcast_pols=False belong to models with 8 input channels; a model with 3 "
                          "input channels normalises every patch itself and flags every plane")
+    if not pol and flags is not None:
+        raise ValueError("flags belong to models with 8 input channels; a model with 3 input channels takes no prior flags")
     f = _downsampling(model)
     if ps % f:
         raise ValueError(f"patch_size {ps} is not a multiple of {f}, the downsampling factor of {type(model).__name__}")
@@ -236,6 +269,8 @@ def predict_flags(model, data, patch_size=128, stride=None, views=1, combine="me
 
     n, Cn, Tn = _pol_shape(shape)
     form = _normalizer_form(normalizer)
+    valid = flags is not None
+    fform, prior = _prior_flags(flags, shape, n, Cn, Tn) if valid else (0, None)
     ctx = model.ctx
     o = operand(data, ctx, (dt,), "cast")
     base = shape[:-3] + ((Cn, Tn) if K == 1 else (K, Cn, Tn))
@@ -248,6 +283,35 @@ def predict_flags(model, data, patch_size=128, stride=None, views=1, combine="me
         check(lib.rfi_model_predict_flags_pol(model._h, C.c_void_p(ptr), mem, COMPLEX_CODES[dt], b1 - b0, Cn, Tn, C.byref(tiling),
                                               *args, centre, scale, None if pairs is None else pairs.ctypes.data_as(C.c_void_p),
                                               C.c_void_p(fp + b0 * opx), omem, C.c_void_p(pp + 4 * b0 * opx) if pp else None, omem))
+
+    if valid:                   # the validity-aware pipeline: prior flags and non-finite values (rfi_model_predict_flags_valid)
+        fo = None if prior is None else operand(prior, ctx, (np.uint8,))
+        fshape = (Cn, Tn) if fform == VALID_FLAGS_BASELINE else (4, Cn, Tn)
+        fpx = px if fform == VALID_FLAGS_BASELINE else 4 * px
+        merge = broadcast_pols and K == 1
+        merged, mp, _ = _flag_buffer(ctx, shape, out, data) if merge else (None, None, None)
+        fill = float(np.float32(fill))
+
+        def run_valid(ptr, mem, fptr, fmem, b0, b1, centre, scale, pairs):
+            check(lib.rfi_model_predict_flags_valid(
+                model._h, C.c_void_p(ptr), mem, COMPLEX_CODES[dt], b1 - b0, Cn, Tn, C.byref(tiling), *args, centre, scale,
+                None if pairs is None else pairs.ctypes.data_as(C.c_void_p), C.c_void_p(fptr) if fptr else None, fmem, fform, fill,
+                C.c_void_p(fp + b0 * opx), omem, C.c_void_p(pp + 4 * b0 * opx) if pp else None, omem,
+                C.c_void_p(mp + 4 * b0 * px) if merge else None, omem))
+
+        if n and px:
+            if form[0] == "pair":
+                run_valid(o.ptr, o.mem, fo.ptr if fo else None, fo.mem if fo else DEVICE, 0, n, form[1], form[2], None)
+            else:
+                for b0, b1 in _sample_groups(n, 4 * px * dt.itemsize):
+                    group = _group_on_device(o, ctx, b0, b1, (4, Cn, Tn))
+                    gflags = None if fo is None else _group_on_device(fo, ctx, b0, b1, fshape)
+                    pairs = _sample_pairs(normalizer, group, "nonfinite" if gflags is None else gflags)
+                    run_valid(group.ptr, DEVICE, gflags.ptr if gflags is not None else None, DEVICE, b0, b1, 0.0, 1.0, pairs)
+                    del group, gflags
+        del o, fo
+        flags = _as_bool(merged if merge else flags)
+        return (flags, prob) if return_probabilities else flags
 
     if n and px:
         if form[0] == "pair":
@@ -264,32 +328,48 @@ def predict_flags(model, data, patch_size=128, stride=None, views=1, combine="me
     return (flags, prob) if return_probabilities else flags
 
 
-def tile_observation(data, patch_size, stride=None, views=1, edge="pad", normalizer=None, device=None):
+def tile_observation(data, patch_size, stride=None, views=1, edge="pad", normalizer=None, device=None, flags=None, fill=0.0):
     """The network input of every tile of an observation for an 8-channel model, for users who run their own model.
 
     ``data``: complex ``(B, 4, C, T)`` or ``(4, C, T)`` (NumPy, torch or ``DeviceArray``).  Returns a ``DeviceArray``
     ``(N, ps, ps, 8)`` float32, NHWC, channels RR.re, RR.im, RL.re, ... LL.im, the tiles in ``rfi_tiling`` order
     (baseline, view, tile row, tile column); ``normalizer`` as in ``predict_flags``; a pixel past a view's edge holds
-    the normalised value of a zero visibility.  ``stitch_patches`` puts the outputs of these tiles back together."""
+    the normalised value of a zero visibility.  ``stitch_patches`` puts the outputs of these tiles back together.
+
+    ``flags`` and ``fill`` as in ``predict_flags``: invalid visibilities (prior flag set, or a non-finite part) are left
+    out of a sample-scope normalizer's statistics and written as ``fill`` (``rfi_valid_gather``); the pixels past a
+    view's edge stay what they are and count as valid."""
     ps, s = check_tiling_args(patch_size, stride, views, "mean", edge)
     shape, dt = _complex_input(data, "tile_observation")
     n, Cn, Tn = _pol_shape(shape)
     form = _normalizer_form(normalizer)
+    fform, prior = _prior_flags(flags, shape, n, Cn, Tn) if flags is not None else (0, None)
     ctx = context_for(device, data)
     table = tiling_table(n, Cn, Tn, ps, s, views, edge)
     res = ctx.empty((len(table), ps, ps, 8), np.float32)
     if not len(table) or not Cn * Tn:
         return res
     o = operand(data, ctx, (dt,), "cast", to_device=True)
+    fo = None if prior is None else operand(prior, ctx, (np.uint8,), to_device=True)
+    fshape = (Cn, Tn) if fform == VALID_FLAGS_BASELINE else (4, Cn, Tn)
     pairs = None
     if form[0] == "sample":
-        pairs = np.concatenate([_sample_pairs(normalizer, _group_on_device(o, ctx, b0, b1, (4, Cn, Tn)))
+        pairs = np.concatenate([_sample_pairs(normalizer, _group_on_device(o, ctx, b0, b1, (4, Cn, Tn)),
+                                              None if flags is None else
+                                              ("nonfinite" if fo is None else _group_on_device(fo, ctx, b0, b1, fshape)))
                                 for b0, b1 in _sample_groups(n, 4 * Cn * Tn * dt.itemsize)])
     centre, scale = (form[1], form[2]) if form[0] == "pair" else (0.0, 1.0)
-    check(lib.rfi_norm_gather(ctx.handle, C.c_void_p(o.ptr), DEVICE, COMPLEX_CODES[dt], n, Cn, Tn,
-                              table.ctypes.data_as(C.c_void_p), len(table), ps, centre, scale,
-                              None if pairs is None else pairs.ctypes.data_as(C.c_void_p), C.c_void_p(res.ptr), DEVICE))
-    del o
+    if flags is None:
+        check(lib.rfi_norm_gather(ctx.handle, C.c_void_p(o.ptr), DEVICE, COMPLEX_CODES[dt], n, Cn, Tn,
+                                  table.ctypes.data_as(C.c_void_p), len(table), ps, centre, scale,
+                                  None if pairs is None else pairs.ctypes.data_as(C.c_void_p), C.c_void_p(res.ptr), DEVICE))
+    else:
+        check(lib.rfi_valid_gather(ctx.handle, C.c_void_p(o.ptr), DEVICE, COMPLEX_CODES[dt], n, Cn, Tn,
+                                   table.ctypes.data_as(C.c_void_p), len(table), ps, centre, scale,
+                                   None if pairs is None else pairs.ctypes.data_as(C.c_void_p),
+                                   None if fo is None else C.c_void_p(fo.ptr), DEVICE, fform, float(np.float32(fill)),
+                                   C.c_void_p(res.ptr), DEVICE))
+    del o, fo
     return res
 
 

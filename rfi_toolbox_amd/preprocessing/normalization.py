@@ -21,8 +21,22 @@ Accepted inputs: planar ``(n, 8, T, F)`` or channel-last ``(n, T, F, 8)`` float6
 complex64 ``(n, 4, T, F)`` in the order RR, RL, LR, LL (channels RR.re, RR.im, ... as ``save_example_pair_npy``).
 For float32 / complex64 input the arithmetic is fp64 on the values widened to fp64, not NumPy's float32 arithmetic.
 
-Deviation: input holding a NaN or an infinity raises ``ValueError`` in ``fit`` (scikit-learn skips NaN; the
-reference's data never has one).
+Prior flags and non-finite samples.  ``statistics``, ``fit``, ``transform``, ``fit_transform`` and ``normalize_array``
+take ``flags``: prior flags of the visibilities, uint8 or bool (NumPy, torch or ``DeviceArray``), per polarisation
+``(n, 4, T, F)`` or per baseline ``(n, T, F)`` (all four polarisations of a pixel); for a list of chunks a list of the
+same length; or the string ``"nonfinite"``: no prior flags.  A visibility is then INVALID when its flag is set or its
+real or imaginary part (channels ``2p``, ``2p + 1`` of real input) is non-finite.  The statistics are those of the
+valid scalars alone (``rfi_valid_statistics``: ``count`` is the valid count, and the quantile brackets come from it); a
+population without a valid scalar has ``count`` 0, NaN statistics and the pair ``(0.0, 0.0)``, the all-zeros transform.
+``transform`` writes ``fill`` (float32, normalised units, default 0.0) into both channels of an invalid visibility and
+today's expression everywhere else (``rfi_valid_apply``).  What ``transform`` calls invalid is decided from the array it
+is given, so ``fit`` and ``transform`` may see different flags.
+
+Deviation: with ``flags=None`` input holding a NaN or an infinity raises ``ValueError`` in ``fit``, as before
+(scikit-learn skips NaN; the reference's simulated data never has one).  Measured data does: pass its ``FLAG`` column,
+or ``flags="nonfinite"``.  Out of scope here: an ignore mask in the training loss (training on real data feeds ``fill``
+inputs with the prior flags as labels, as the reference does), ``detect_observation``, the 3-channel ``Preprocessor``
+path and ``RFIMaskDataset``, none of which takes ``flags``.
 """
 from __future__ import annotations
 
@@ -64,6 +78,43 @@ def _describe(x, layout=None):
     return shape[0], tf[0] * tf[1], layout, tf
 
 
+def _flags_form(flags, n, tf, what="flags"):
+    """-> VALID_FLAGS_POL / VALID_FLAGS_BASELINE of prior flags for `n` samples of planes `tf`, or None for
+    ``"nonfinite"``; ValueError / TypeError otherwise (host only: no device is touched)."""
+    from .._lib import VALID_FLAGS_BASELINE, VALID_FLAGS_POL
+    from ..runtime import describe
+    if isinstance(flags, str):
+        if flags != "nonfinite":
+            raise ValueError(f"{what} must be an array of prior flags or the string 'nonfinite', got {flags!r}")
+        return None
+    shape, dt = describe(flags)[:2]
+    shape = tuple(int(v) for v in shape)
+    if dt is None or dt not in (np.dtype(np.uint8), np.dtype(np.bool_)):
+        raise TypeError(f"{what} must be uint8 or bool, not {dt}")
+    tf = tuple(int(v) for v in tf)
+    if shape == (n, 4) + tf:
+        return VALID_FLAGS_POL
+    if shape == (n,) + tf:
+        return VALID_FLAGS_BASELINE
+    raise ValueError(f"{what} must be per polarisation {(n, 4) + tf} or per baseline {(n,) + tf}, got shape {shape}")
+
+
+def _invalid_map(ctx, src, desc, flags, form):
+    """The (n, 4, pixels) uint8 invalid map (``rfi_valid_map``) of the device operand `src` described by `desc`; `flags`:
+    prior flags in `form`, or None."""
+    from .._lib import NORM_NCHW, NORM_NHWC, VALUE_CODES, check, lib
+    from ..runtime import operand
+    n, px, lay = desc[0], desc[1], desc[2]
+    vmap = ctx.empty((n, 4, px), np.uint8)
+    if n and px:
+        fo = None if form is None else operand(flags, ctx, (np.uint8,), to_device=True)
+        check(lib.rfi_valid_map(ctx.handle, C.c_void_p(src.ptr), VALUE_CODES[src.dtype], NORM_NHWC if lay == "nhwc" else NORM_NCHW,
+                                n, px, None if fo is None else C.c_void_p(fo.ptr), form or 0, C.c_void_p(vmap.ptr), None, 0))
+        if fo is not None and fo.keep is not flags:
+            ctx.synchronize()                           # (an uploaded copy of the flags goes with this frame)
+    return vmap
+
+
 def _lerp(a, b, t):
     """NumPy's _lerp for scalars."""
     d = b - a
@@ -89,6 +140,10 @@ def quantiles_from_brackets(count, q):
 def dataset_parameters(method, st):
     """RFIMaskDataset's attributes and the (centre, scale) pair of `method` from one population's statistics `st`
     (a dict with count, min, max, mean, var, q).  scale 0.0 stands for the all-zeros transform."""
+    if st["count"] == 0:                                # (no valid scalar: NaN statistics, the all-zeros transform)
+        nan = float("nan")
+        return {"global_min": nan, "global_max": nan, "mean": nan, "std": nan, "robust_median": nan if method == "robust_scale" else None,
+                "robust_iqr": nan if method == "robust_scale" else None}, (0.0, 0.0)
     attrs = {"global_min": st["min"], "global_max": st["max"], "mean": st["mean"], "std": math.sqrt(st["var"]) + 1e-8,
              "robust_median": None, "robust_iqr": None}
     if method == "robust_scale":
@@ -106,7 +161,9 @@ def dataset_parameters(method, st):
 
 def sample_parameters(method, st):
     """normalize_array's (centre, scale) for one sample from its statistics (scikit-learn 1.7's constant-feature rules)."""
-    n = st["count"]
+    n = st["count"]                                     # (with prior flags: the number of valid scalars)
+    if n == 0:
+        return 0.0, 0.0
     if method == "global_min_max":
         return (st["min"], st["max"] - st["min"]) if st["max"] > st["min"] else (0.0, 0.0)
     if method == "standardize":
@@ -143,10 +200,12 @@ class Normalizer:
     def _as_list(x):
         return list(x) if isinstance(x, (list, tuple)) else [x]
 
-    def statistics(self, x_or_list, layout=None, quantiles=True):
+    def statistics(self, x_or_list, layout=None, quantiles=True, flags=None):
         """The raw per-population statistics (list of dicts) of what ``fit`` would see; raises on non-finite input.
-        quantiles=False skips the order statistics (``q`` is NaN): 2 reads of the data instead of 6."""
-        from .._lib import F32, F64, NormStats, check, lib
+        quantiles=False skips the order statistics (``q`` is NaN): 2 reads of the data instead of 6.
+        flags: prior flags (one array, or a list like `x_or_list`) or "nonfinite": the statistics of the valid scalars
+        (module docstring); non-finite input is then skipped, not refused."""
+        from .._lib import F32, F64, VALID_SRC_COMPLEX, VALID_SRC_NHWC, VALID_SRC_PLANAR, NormStats, check, lib
         from ..runtime import DeviceArray, context_for, operand
         xs = [x if isinstance(x, DeviceArray) else np.asarray(x) for x in self._as_list(x_or_list)]
         if not xs:
@@ -160,6 +219,12 @@ class Normalizer:
         if sum(d[0] for d in desc) == 0:
             raise ValueError("fit needs at least one sample")
         scalar = scalars.pop()
+        forms = None
+        if flags is not None:
+            fl = list(flags) if isinstance(flags, (list, tuple)) else [flags] * (len(xs) if isinstance(flags, str) else 1)
+            if len(fl) != len(xs):
+                raise ValueError(f"flags must match the data: {len(xs)} chunk(s) of data, {len(fl)} of flags")
+            forms = [_flags_form(f, d[0], d[3], f"flags[{i}]" if len(fl) > 1 else "flags") for i, (f, d) in enumerate(zip(fl, desc))]
         ctx = context_for(self.device, *xs)
         devs = [operand(x, ctx, tuple(_SCALAR), to_device=True) for x in xs]      # kept alive until the call returns
         counts = [d[0] * d[1] * 8 for d in desc]
@@ -169,8 +234,18 @@ class Normalizer:
         segment = desc[0][1] * 8 if self.scope == "sample" else 0
         pops = desc[0][0] if self.scope == "sample" else 1
         out = (NormStats * pops)()
-        check(lib.rfi_norm_statistics(ctx.handle, ptrs, cnts, n, F32 if scalar == np.float32 else F64, segment,
-                                      1 if quantiles else 0, out, pops))
+        if forms is None:
+            check(lib.rfi_norm_statistics(ctx.handle, ptrs, cnts, n, F32 if scalar == np.float32 else F64, segment,
+                                          1 if quantiles else 0, out, pops))
+        else:
+            maps = [_invalid_map(ctx, s, d, f, form) for s, d, f, form in zip(devs, desc, fl, forms)]
+            mptrs = (C.c_void_p * n)(*[m.ptr for m in maps])
+            kinds = (C.c_int * n)(*[VALID_SRC_COMPLEX if np.dtype(x.dtype).kind == "c" else
+                                    (VALID_SRC_NHWC if d[2] == "nhwc" else VALID_SRC_PLANAR) for x, d in zip(xs, desc)])
+            pixels = (C.c_int64 * n)(*[max(1, d[1]) for d in desc])
+            check(lib.rfi_valid_statistics(ctx.handle, ptrs, cnts, mptrs, kinds, pixels, n, F32 if scalar == np.float32 else F64,
+                                           segment, 1 if quantiles else 0, out, pops))
+            del maps
         del devs
         bad = sum(int(r.nonfinite) for r in out)
         if bad:
@@ -179,8 +254,8 @@ class Normalizer:
                  "q": tuple((float(r.q[j][0]), float(r.q[j][1])) for j in range(3))} for r in out]
 
     # ---- the surface
-    def fit(self, x_or_list, layout=None):
-        stats = self.statistics(x_or_list, layout, quantiles=self.method == "robust_scale")
+    def fit(self, x_or_list, layout=None, flags=None):
+        stats = self.statistics(x_or_list, layout, quantiles=self.method == "robust_scale", flags=flags)
         if self.scope == "dataset":
             attrs, pair = dataset_parameters(self.method, stats[0])
             for k, v in attrs.items():
@@ -193,9 +268,11 @@ class Normalizer:
         self._params_dev = None
         return self
 
-    def transform(self, x, out="nhwc", layout=None):
+    def transform(self, x, out="nhwc", layout=None, flags=None, fill=0.0):
         """float32 (n, T, F, 8) for out="nhwc", (n, 8, T, F) for out="nchw": DeviceArray for DeviceArray input (stream-
-        ordered, nothing synchronised), NumPy for NumPy input."""
+        ordered, nothing synchronised), NumPy for NumPy input.  flags (prior flags or "nonfinite") and fill: both
+        channels of an invalid visibility are written as float32 `fill` (module docstring); the call then synchronises,
+        since the invalid map it builds is its own."""
         from .._lib import NORM_NCHW, NORM_NHWC, VALUE_CODES, check, lib
         from ..runtime import DeviceArray, context_for, operand
         if out not in ("nhwc", "nchw"):
@@ -207,6 +284,10 @@ class Normalizer:
             raise RuntimeError("transform before fit (or load_state_dict)")
         if self.scope == "sample" and len(self.centres) != n:
             raise ValueError(f"fitted on {len(self.centres)} samples, asked to transform {n}")
+        form = None
+        if flags is not None:
+            form = _flags_form(flags, n, (T, F))
+            fill = float(np.float32(fill))
         on_device = isinstance(x, DeviceArray)
         ctx = context_for(self.device, x)
         src = operand(x, ctx, tuple(_SCALAR), to_device=True)
@@ -216,17 +297,25 @@ class Normalizer:
             if self._params_dev is None or self._params_dev.ctx is not ctx:
                 self._params_dev = ctx.to_device(np.stack([self.centres, self.scales], axis=1).astype(np.float64))
             params = C.c_void_p(self._params_dev.ptr)
-        check(lib.rfi_norm_apply(ctx.handle, C.c_void_p(src.ptr), VALUE_CODES[src.dtype], NORM_NHWC if lay == "nhwc" else NORM_NCHW, n, px,
-                                 self.centres[0], self.scales[0], params, C.c_void_p(dst.ptr),
-                                 NORM_NHWC if out == "nhwc" else NORM_NCHW))
+        if flags is None:
+            check(lib.rfi_norm_apply(ctx.handle, C.c_void_p(src.ptr), VALUE_CODES[src.dtype], NORM_NHWC if lay == "nhwc" else NORM_NCHW, n, px,
+                                     self.centres[0], self.scales[0], params, C.c_void_p(dst.ptr),
+                                     NORM_NHWC if out == "nhwc" else NORM_NCHW))
+        elif n and px:
+            vmap = _invalid_map(ctx, src, (n, px, lay), flags, form)
+            check(lib.rfi_valid_apply(ctx.handle, C.c_void_p(src.ptr), VALUE_CODES[src.dtype], NORM_NHWC if lay == "nhwc" else NORM_NCHW,
+                                      n, px, self.centres[0], self.scales[0], params, C.c_void_p(vmap.ptr), fill, C.c_void_p(dst.ptr),
+                                      NORM_NHWC if out == "nhwc" else NORM_NCHW))
+            if on_device:
+                ctx.synchronize()                       # (the map is this call's own: it must outlive the kernel that reads it)
         if on_device:
             return dst
         return dst.numpy()                              # (the copy waits for the stream, so `src` may go now)
 
-    def fit_transform(self, x, out="nhwc", layout=None):
+    def fit_transform(self, x, out="nhwc", layout=None, flags=None, fill=0.0):
         if self.scope == "dataset" and isinstance(x, (list, tuple)):
             raise ValueError("fit_transform takes one array; fit a list, then transform each chunk")
-        return self.fit(x, layout).transform(x, out, layout)
+        return self.fit(x, layout, flags).transform(x, out, layout, flags, fill)
 
     def state_dict(self):
         """Plain Python floats and strings (fit for a checkpoint's ``args``)."""
@@ -250,12 +339,20 @@ class Normalizer:
         return self
 
 
-def normalize_array(data, method="standardize", device=None):
+def normalize_array(data, method="standardize", device=None, flags=None, fill=0.0):
     """``scripts/normalize_rfi_data.py::normalize_array`` for one (8, T, F) array, computed on the GPU.  Returns
-    float32: what the reference's training loop sees after ``torch.tensor(..., dtype=torch.float32)``."""
+    float32: what the reference's training loop sees after ``torch.tensor(..., dtype=torch.float32)``.
+    flags: prior flags (4, T, F) or (T, F), or "nonfinite"; invalid visibilities are left out of the statistics and
+    come back as `fill` (module docstring)."""
     if method not in METHODS:
         raise ValueError(f"Unsupported normalization method: {method}")
     data = np.asarray(data)
     if data.ndim != 3 or data.shape[0] != 8:
         raise ValueError(f"data must be (8, T, F), got shape {data.shape}")
-    return Normalizer(method, scope="sample", device=device).fit_transform(data[None], out="nchw", layout="nchw")[0]
+    if flags is not None and not isinstance(flags, str):
+        flags = np.asarray(flags)
+        if flags.shape not in ((4,) + data.shape[1:], data.shape[1:]):
+            raise ValueError(f"flags must be {(4,) + data.shape[1:]} or {data.shape[1:]}, got shape {flags.shape}")
+        flags = flags[None]
+    return Normalizer(method, scope="sample", device=device).fit_transform(data[None], out="nchw", layout="nchw", flags=flags,
+                                                                           fill=fill)[0]
