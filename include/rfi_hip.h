@@ -173,6 +173,32 @@ int rfi_model_set_head_sigmoid(rfi_model* m, int enabled);
  * With class-bit labels kind 0 is the reference's code on the K-channel tensor (BCE mean over all n h w K elements + ONE
  * dice term over all of them) and kind 1 the focal mean over all of them. */
 int rfi_model_set_loss(rfi_model* m, int kind, float alpha, float gamma);
+/* An ignore bit in the label byte and per-channel positive weights, two weights on the terms of the sums above.  Both are
+ * per-model switches, off by default, for the models class-bit labels support (the plain U-Net without a sigmoid head);
+ * the other models refuse them.  While neither is set every path and launch is the one described above.
+ *   rfi_model_set_ignore(m, 1): a pixel whose label has bit 7 (RFI_LABEL_IGNORE) set is IGNORED.  Label maps: the target of a
+ *     pixel that is not ignored is (label & 0x7F) != 0, so a bool or 0/1 mask means what it meant.  Class-bit labels: the
+ *     pixel is ignored for all channels, which needs out_channels <= 7.  With the switch off bit 7 is what it was: RFI in
+ *     a map, channel 7's target (or nothing) in class bits.  rfi_model_eval_batch / _eval_batch_classes then count over
+ *     the pixels that are not ignored; rfi_model_eval_sweep refuses (its pooled count is the size of the label array).
+ *   rfi_model_set_pos_weight(m, w, k): k == out_channels weights, each finite and >= 0, checked before anything is
+ *     launched; NULL or k == 0 clears them.  For loss kinds 0 and 2; with focal (which has alpha) either call order fails.
+ * With v_i = 1 where pixel i is not ignored (else 0), pi_k the weight of channel k (1 when unset), N_v = K sum_i v_i and
+ * p = sigmoid(x):
+ *   BCE  = sum v [pi t softplus(-x) + (1 - t) softplus(x)] / N_v  (torch's BCEWithLogitsLoss(pos_weight = pi) over the
+ *          valid elements; 0 when N_v = 0);
+ *   dice sums I = sum v p t, P = sum v p, T = sum v t, pooled (kind 0) or per channel (kind 2); the dice terms and their
+ *          1/K mean are formed from them as above.  The weights do not enter the dice term;
+ *   focal = the mean of the focal element over the valid elements, 0 when there are none;
+ *   dlogits: at a valid element v (t ? -pi (1 - p) : p) / N_v plus the dice derivative from the masked sums; at an
+ *          ignored element every bit is +0.0.  A batch whose pixels are all ignored gives the loss 0.0f and a zero
+ *          gradient, nothing non-finite.
+ * Reductions: five double sums per class (the four above and the valid count, whole numbers and therefore exact), per
+ * block in a fixed order, float32 final combination, bitwise reproducible; with nothing ignored and unit weights the sums
+ * are those of the class-bit kernels bit for bit.  N_v stays on the device: rfi_train_step_async reads nothing back. */
+#define RFI_LABEL_IGNORE 0x80
+int rfi_model_set_ignore(rfi_model* m, int enabled);
+int rfi_model_set_pos_weight(rfi_model* m, const float* weights_host, int k);
 /* what a label byte means.  RFI_LABELS_MAP (default): non-zero == RFI; the loss and the evaluation need one output channel.
  * RFI_LABELS_CLASS_BITS: the target of output channel k is (label >> k) & 1, 1 <= out_channels <= 8, bits at and above
  * out_channels are ignored; the label tensors keep their shape (n x h x w uint8).  U-Net models without a sigmoid head and
@@ -225,7 +251,9 @@ typedef struct rfi_hyper {   /* doubles: the reference's hyper-parameters are py
  * rfi_train_step and rfi_train_step_async all-reduce(sum) the flat gradient buffer over the ranks before
  * clipping and apply the MEAN gradient (grad_scale = 1/world), so every rank makes the identical update.
  * BatchNorm batch statistics, running buffers and the dice term stay LOCAL to each rank's batch (torch DDP
- * broadcasts rank 0's buffers every step; here they are only taken from rank 0 at checkpoint time). */
+ * broadcasts rank 0's buffers every step; here they are only taken from rank 0 at checkpoint time).
+ * With the ignore bit on (rfi_model_set_ignore) each rank also divides by its OWN valid count N_v: the ranks' losses are
+ * means over their own valid elements, and the update is the mean of those gradients. */
 int rfi_train_step(rfi_model* m, const float* x_nhwc, int x_mem, const uint8_t* labels,
                    int labels_mem, int n, int h, int w, const rfi_hyper* hp, float* loss_out);
 /* same step split in two so a data-parallel caller can all-reduce the gradients in between */
@@ -723,6 +751,19 @@ int rfi_model_predict_flags_valid(rfi_model* m, const void* planes, int planes_m
                                   double scale, const double (*params_host)[2], const uint8_t* prior, int prior_mem,
                                   int prior_form, float fill, uint8_t* flags, int flags_mem, float* prob, int prob_mem,
                                   uint8_t* merged, int merged_mem);
+/* The label planes of an observation cut into the tiles rfi_norm_gather / rfi_valid_gather cut the data into, for training
+ * with the ignore bit (rfi_model_set_ignore).  labels (n_samples, C, T) bytes, one plane per sample (a map or class bits);
+ * invalid: NULL, or the invalid map (n_samples, 4, C, T) as rfi_valid_map writes it (RFI_VALID_FLAGS_POL) or one byte per
+ * pixel (n_samples, C, T) (RFI_VALID_FLAGS_BASELINE), non-zero == invalid.  table_host: n_tiles entries of rfi_tiling_table,
+ * so the tile order is that of the data tiles by construction.  out (n_tiles, ps, ps) bytes: label | RFI_LABEL_IGNORE where
+ * the pixel is invalid -- under the POL form where any (RFI_LABEL_INVALID_ANY) or all (RFI_LABEL_INVALID_ALL) of its four
+ * polarisations are -- the label elsewhere, and pad_value (0 .. 255; RFI_LABEL_IGNORE keeps the padding of edge tiles out
+ * of the loss) past a view's edge.  One launch per 65535 tiles, no synchronisation when everything is device-resident;
+ * n_tiles == 0 is a no-op. */
+enum { RFI_LABEL_INVALID_ANY = 0, RFI_LABEL_INVALID_ALL = 1 };
+int rfi_label_gather(rfi_ctx* ctx, const uint8_t* labels, int labels_mem, int n_samples, int c, int t, const uint8_t* invalid,
+                     int invalid_mem, int invalid_form, int rule, const rfi_patch_src* table_host, int n_tiles, int ps,
+                     int pad_value, uint8_t* out, int out_mem);
 
 /* ---- training augmentation (scripts/train_model.py:44-53,70-75, --augment): HorizontalFlip, VerticalFlip, Rotate and
  *      ShiftScaleRotate of a batch and its masks, as flips and ONE resampling through the composed affine transform.

@@ -145,6 +145,8 @@ _PROTOS = {
     "rfi_model_set_head_sigmoid": (_i, [_vp, _i]),
     "rfi_model_set_loss": (_i, [_vp, _i, _f, _f]),
     "rfi_model_set_label_mode": (_i, [_vp, _i]),
+    "rfi_model_set_ignore": (_i, [_vp, _i]),
+    "rfi_model_set_pos_weight": (_i, [_vp, _pf, _i]),
     "rfi_model_destroy": (_i, [_vp]),
     "rfi_model_init": (_i, [_vp, C.c_uint64]),
     "rfi_model_entry_count": (_i, [_vp, _pi]),
@@ -240,6 +242,7 @@ _PROTOS = {
     "rfi_valid_map": (_i, [_vp, _vp, _i, _i, _i, _i64, _vp, _i, _vp, _vp, _i]),
     "rfi_valid_statistics": (_i, [_vp, _pvp, _pi64, _pvp, _pi, _pi64, _i, _i, _i64, _i, C.POINTER(NormStats), _i]),
     "rfi_valid_apply": (_i, [_vp, _vp, _i, _i, _i, _i64, C.c_double, C.c_double, _vp, _vp, _f, _vp, _i]),
+    "rfi_label_gather": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _i]),
     "rfi_valid_gather": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, C.c_double, C.c_double, _vp, _vp, _i, _i, _f, _vp, _i]),
     "rfi_model_predict_flags_valid": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.POINTER(Tiling), _i, _i, _f, C.c_double, C.c_double, _vp,
                                            _vp, _i, _i, _f, _vp, _i, _vp, _i, _vp, _i]),

@@ -48,3 +48,29 @@ def unpack_class_bits(bits, num_classes, channel_axis=-3):
         raise ValueError(f"channel_axis must be -3 or -1, got {channel_axis!r}")
     out = ((b.astype(np.uint8)[..., None] >> np.arange(K, dtype=np.uint8)) & 1).astype(np.bool_)
     return out if channel_axis == -1 else np.moveaxis(out, -1, -3)
+
+
+# ---- the ignore bit (``model.set_ignore(True)``, RFI_LABEL_IGNORE in include/rfi_hip.h): bit 7 of the label byte takes the
+# pixel out of the loss and out of the evaluation counts.  It rides in the byte, so everything that carries labels carries it
+IGNORE = 0x80
+
+
+def with_ignore(labels, ignore):
+    """``labels`` (uint8 or bool, a map or class bits of at most 7 classes) with bit 7 set where ``ignore`` is non-zero.
+    The low seven bits stay as they are: ``split_ignore`` gives both back."""
+    b = np.asarray(labels)
+    if b.dtype != np.uint8 and b.dtype != np.bool_:
+        raise ValueError(f"labels must be uint8 or bool, got {b.dtype}")
+    b = b.astype(np.uint8)
+    if (b & IGNORE).any():
+        raise ValueError("labels already use bit 7: the ignore bit needs labels below 0x80 (at most 7 classes)")
+    ig = np.broadcast_to(np.asarray(ignore) != 0, b.shape)
+    return b | (ig.astype(np.uint8) << 7).astype(np.uint8)
+
+
+def split_ignore(labels):
+    """``(labels & 0x7F, ignored)``: the label bytes without bit 7 and the bool mask of the pixels that had it"""
+    b = np.asarray(labels)
+    if b.dtype != np.uint8:
+        raise ValueError(f"labels must be uint8, got {b.dtype}")
+    return b & np.uint8(0x7F), (b & np.uint8(IGNORE)) != 0

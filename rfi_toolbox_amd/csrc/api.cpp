@@ -462,9 +462,45 @@ int rfi_model_set_loss(rfi_model* m, int kind, float alpha, float gamma) {
         RFI_REQUIRE(kind != 1 || (gamma >= 0.0f && alpha <= 1.0f), "set_loss: focal needs gamma >= 0 and alpha <= 1");
         RFI_REQUIRE(kind != 2 || m->label_mode == RFI_LABELS_CLASS_BITS,
                     "set_loss: the per-class dice term needs class-bit labels (rfi_model_set_label_mode first)");
+        RFI_REQUIRE(kind != 1 || !m->weights_on,
+                    "set_loss: the focal loss takes no positive weights (it has alpha); clear them with rfi_model_set_pos_weight(m, NULL, 0) first");
         m->loss_kind = kind;
         m->focal_alpha = alpha;
         m->focal_gamma = gamma;
+    });
+}
+namespace {
+void require_masked_scope(rfi_model* m, const char* what) {
+    RFI_REQUIRE(plain_unet(m) && !m->head_sigmoid && m->dense_head,
+                std::string(what) + ": the ignore bit and positive weights are for UNet, UNetBigger and UNetDifferentActivation (not the "
+                                    "sigmoid-head, ResNet-encoder, SimpleCNN or detector models)");
+}
+}  // namespace
+int rfi_model_set_ignore(rfi_model* m, int enabled) {
+    return guarded([&] {
+        if (enabled) {
+            require_masked_scope(m, "set_ignore");
+            RFI_REQUIRE(m->label_mode != RFI_LABELS_CLASS_BITS || m->out_ch <= 7,
+                        "set_ignore: bit 7 of a class-bit label is the target of channel 7; the ignore bit needs out_channels <= 7");
+        }
+        m->ignore_on = enabled != 0;
+    });
+}
+int rfi_model_set_pos_weight(rfi_model* m, const float* weights_host, int k) {
+    return guarded([&] {
+        if (!weights_host || k == 0) {
+            m->weights_on = false;
+            for (float& w : m->pos_weight) w = 1.0f;
+            return;
+        }
+        require_masked_scope(m, "set_pos_weight");
+        RFI_REQUIRE(k == m->out_ch, "set_pos_weight: " + std::to_string(k) + " weights for " + std::to_string(m->out_ch) + " output channels");
+        RFI_REQUIRE(k <= 8, "set_pos_weight: at most 8 output channels");
+        for (int c = 0; c < k; ++c)
+            RFI_REQUIRE(std::isfinite(weights_host[c]) && weights_host[c] >= 0.0f, "set_pos_weight: every weight must be finite and >= 0");
+        RFI_REQUIRE(m->loss_kind != 1, "set_pos_weight: the focal loss takes no positive weights (it has alpha)");
+        for (int c = 0; c < 8; ++c) m->pos_weight[c] = c < k ? weights_host[c] : 1.0f;
+        m->weights_on = true;
     });
 }
 int rfi_model_set_label_mode(rfi_model* m, int mode) {
@@ -475,6 +511,8 @@ int rfi_model_set_label_mode(rfi_model* m, int mode) {
                         "set_label_mode: class-bit labels are for UNet, UNetBigger and UNetDifferentActivation (not the sigmoid-head, "
                         "ResNet-encoder or SimpleCNN models)");
             RFI_REQUIRE(m->out_ch >= 1 && m->out_ch <= 8, "set_label_mode: class-bit labels need 1 <= out_channels <= 8");
+            RFI_REQUIRE(!m->ignore_on || m->out_ch <= 7,
+                        "set_label_mode: the ignore bit (rfi_model_set_ignore) is bit 7; class-bit labels then need out_channels <= 7");
         } else if (m->loss_kind == 2) {
             m->loss_kind = 0;         // (the per-class dice term of one class is the reference's loss)
         }
@@ -485,6 +523,7 @@ int rfi_model_set_head_sigmoid(rfi_model* m, int enabled) {
     return guarded([&] {
         RFI_REQUIRE(plain_unet(m), "set_head_sigmoid: U-Net models only");
         RFI_REQUIRE(!enabled || m->label_mode == RFI_LABELS_MAP, "set_head_sigmoid: not with class-bit labels");
+        RFI_REQUIRE(!enabled || !m->masked_loss(), "set_head_sigmoid: not with the ignore bit or positive weights");
         m->head_sigmoid = enabled != 0;
     });
 }
@@ -734,6 +773,15 @@ int rfi_model_eval_batch(rfi_model* m, const float* x, int x_mem, const uint8_t*
         const uint8_t* yd = stage_labels(m, labels, labels_mem, n, h, w);
         m->forward(xd, n, h, w, m->training);
         const int64_t cnt = (int64_t)n * h * w * m->out_scale * m->out_scale;
+        if (m->ignore_on) {           // the counts over the pixels whose label has bit 7 clear
+            CallScope sc(m->ctx);
+            auto* ws = sc.temp<unsigned long long>(class_confusion_ws_words(1));
+            unsigned long long h3[3];
+            launch_masked_confusion(m->ctx, m->buf(m->logits), yd, cnt, 1, threshold, true, true, ws, sc.out(h3, RFI_HOST, 3));
+            sc.finish();
+            *tp = (int64_t)h3[0]; *fp = (int64_t)h3[1]; *fn = (int64_t)h3[2];
+            return;
+        }
         uint8_t* mask = reinterpret_cast<uint8_t*>(m->buf(m->out_stage));      // cnt bytes fit (cnt floats)
         // evaluate_model.py:44-47 thresholds sigmoid(model output), whatever the model returns
         launch_threshold(m->ctx, m->buf(m->head_sigmoid ? m->probs : m->logits), cnt, threshold, mask);
@@ -761,7 +809,8 @@ int rfi_model_eval_batch_classes(rfi_model* m, const float* x, int x_mem, const 
         auto* ws = sc.temp<unsigned long long>(class_confusion_ws_words(K));
         static_assert(sizeof(unsigned long long) == sizeof(int64_t), "counts are copied as they are");
         auto* out = reinterpret_cast<unsigned long long*>(sc.out(counts, RFI_HOST, (size_t)K * 3));
-        launch_class_confusion(m->ctx, m->buf(m->logits), yd, (int64_t)n * h * w, K, threshold, ws, out);
+        if (m->ignore_on) launch_masked_confusion(m->ctx, m->buf(m->logits), yd, (int64_t)n * h * w, K, threshold, false, true, ws, out);
+        else launch_class_confusion(m->ctx, m->buf(m->logits), yd, (int64_t)n * h * w, K, threshold, ws, out);
         sc.finish();
     });
 }
@@ -770,6 +819,9 @@ int rfi_model_eval_sweep(rfi_model* m, const float* x, int x_mem, const uint8_t*
                          int w, const float* thresholds_host, int n_thresholds, int64_t* counts_host) {
     return guarded([&] {
         RFI_REQUIRE(m->out_ch == 1 && m->label_mode == RFI_LABELS_MAP, "eval_sweep: defined for out_channels == 1 and label maps");
+        RFI_REQUIRE(!m->ignore_on,
+                    "eval_sweep: not while the ignore bit is on (the sweep pools every pixel); sweep the valid pixels with "
+                    "rfi_threshold_sweep on prob[valid], truth[valid]");
         RFI_REQUIRE(thresholds_host && counts_host, "eval_sweep: null argument");
         check_sweep_thresholds(thresholds_host, n_thresholds);
         m->ctx->activate();
@@ -1095,6 +1147,30 @@ int rfi_valid_gather(rfi_ctx* ctx, const void* planes, int planes_mem, int dtype
         const double* pr = sc.in(params_host ? params_host[0] : nullptr, RFI_HOST, (size_t)n_samples * 2);
         float* dout = sc.out(out_nhwc, out_mem, (size_t)n * ps * ps * 8);
         launch_pol_gather_valid(ctx, pl, dtype, c, t, tb, n, ps, centre, scale, pr, fl, per_baseline, fill, dout);
+        sc.finish();
+    });
+}
+
+int rfi_label_gather(rfi_ctx* ctx, const uint8_t* labels, int labels_mem, int n_samples, int c, int t, const uint8_t* invalid,
+                     int invalid_mem, int invalid_form, int rule, const rfi_patch_src* table_host, int n_tiles, int ps,
+                     int pad_value, uint8_t* out, int out_mem) {
+    return guarded([&] {
+        RFI_REQUIRE(ctx && n_tiles >= 0 && labels && (n_tiles == 0 || (table_host && out)), "label_gather: null argument");
+        RFI_REQUIRE(invalid_form == RFI_VALID_FLAGS_POL || invalid_form == RFI_VALID_FLAGS_BASELINE, "label_gather: bad invalid form");
+        RFI_REQUIRE(rule == RFI_LABEL_INVALID_ANY || rule == RFI_LABEL_INVALID_ALL, "label_gather: rule must be any (0) or all (1)");
+        RFI_REQUIRE(pad_value >= 0 && pad_value <= 255, "label_gather: pad_value must be a byte");
+        if (n_tiles == 0) return;
+        check_table(table_host, n_tiles, n_samples, c, t, ps, "label_gather");
+        RFI_REQUIRE((int64_t)n_samples * 4 * c * t < ((int64_t)1 << 40), "label_gather: waterfall too large");
+        ctx->activate();
+        const size_t px = (size_t)n_samples * c * t;
+        const bool per_baseline = invalid_form == RFI_VALID_FLAGS_BASELINE;
+        CallScope sc(ctx);
+        const uint8_t* lb = sc.in(labels, labels_mem, px);
+        const uint8_t* iv = sc.in(invalid, invalid_mem, px * (per_baseline ? 1 : 4));
+        const rfi_patch_src* tb = sc.in(table_host, RFI_HOST, (size_t)n_tiles);
+        uint8_t* dout = sc.out(out, out_mem, (size_t)n_tiles * ps * ps);
+        launch_label_gather(ctx, lb, c, t, iv, per_baseline, rule == RFI_LABEL_INVALID_ALL, tb, n_tiles, ps, pad_value, dout);
         sc.finish();
     });
 }

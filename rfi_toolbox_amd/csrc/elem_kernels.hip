@@ -1139,6 +1139,194 @@ __global__ __launch_bounds__(kBlock) void class_loss_bwd_kernel(const float* __r
     }
 }
 
+// ---- the same losses with an ignore bit and per-channel positive weights (include/rfi_hip.h, rfi_model_set_ignore /
+// rfi_model_set_pos_weight).  One family for both label modes: `map` makes the target of the one channel "any of the
+// low bits", else bit k; `ignore` makes bit 7 (RFI_LABEL_IGNORE) take the pixel out of every sum and out of dlogits.
+// Elements go to threads and partial sums are combined exactly as in class_loss_*: a valid element adds the float32
+// terms those kernels add, times its weight, so with nothing ignored and unit weights every sum is theirs bit for bit.
+// A fifth sum counts the valid elements (whole numbers in double: exact); the finish leaves it at sums[4 * kMaxClasses]
+// for the backward kernel, so N_v never visits the host
+struct PosWeights { float w[kMaxClasses]; };
+
+__device__ __forceinline__ float pos_weight_of(const PosWeights& pw, int k) {
+    float w = pw.w[0];
+#pragma unroll
+    for (int c = 1; c < kMaxClasses; ++c) w = c == k ? pw.w[c] : w;       // (selects, no indexed read of the arguments)
+    return w;
+}
+__device__ __forceinline__ bool label_ignored(uint8_t b, int ignore) { return ignore && (b & 0x80); }
+__device__ __forceinline__ bool label_target(uint8_t b, int k, int map, int ignore) {
+    const unsigned v = ignore ? (b & 0x7Fu) : b;
+    return map ? v != 0 : (v >> k) & 1;
+}
+
+__global__ __launch_bounds__(kBlock) void masked_loss_reduce_kernel(const float* __restrict__ logits, const uint8_t* __restrict__ labels,
+                                                                    int64_t count, int K, int kind, float alpha, float gamma, int map,
+                                                                    int ignore, PosWeights pw, double* __restrict__ partial) {
+    __shared__ double red[5][kBlock];
+    const int A = (kBlock / K) * K, k = threadIdx.x % K;
+    const float wk = pos_weight_of(pw, k);
+    double s[5] = {0, 0, 0, 0, 0};
+    if ((int)threadIdx.x < A) {
+        for (int64_t i = (int64_t)blockIdx.x * A + threadIdx.x; i < count; i += (int64_t)gridDim.x * A) {
+            const uint8_t b = labels[i / K];
+            if (label_ignored(b, ignore)) continue;
+            const float x = logits[i];
+            const bool pos = label_target(b, k, map, ignore);
+            const float t = pos ? 1.0f : 0.0f;
+            s[4] += 1.0;
+            if (kind == 1) {
+                s[0] += (double)focal_elem(x, t, alpha, gamma);
+                continue;
+            }
+            // t = 1: softplus(-x), t = 0: softplus(x), in the expression of class_loss_reduce_kernel
+            const float bce = fmaxf(x, 0.0f) - x * t + log1pf(expf(-fabsf(x)));
+            const float p = sigmoidf_(x);
+            s[0] += (double)(pos ? wk * bce : bce);
+            s[1] += (double)(p * t);
+            s[2] += (double)p;
+            s[3] += (double)t;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 5; ++q) red[q][threadIdx.x] = s[q];
+    __syncthreads();
+    if ((int)threadIdx.x < 5 * K) {
+        const int q = threadIdx.x / K, c = threadIdx.x % K;
+        double v = 0;
+        for (int j = c; j < A; j += K) v += red[q][j];
+        partial[(int64_t)blockIdx.x * 5 * K + threadIdx.x] = v;
+    }
+}
+
+// sums: 4 x kMaxClasses doubles as class_loss_finish_kernel, then the valid element count N_v
+__global__ __launch_bounds__(kBlock) void masked_loss_finish_kernel(const double* __restrict__ partial, int blocks, int K, int kind,
+                                                                    double* __restrict__ sums, float* __restrict__ loss_out) {
+    constexpr int G = kBlock / (4 * kMaxClasses);
+    __shared__ double red[G][4 * kMaxClasses];
+    __shared__ double cnt[kBlock];
+    const int o = threadIdx.x % (4 * kMaxClasses), g = threadIdx.x / (4 * kMaxClasses);
+    double v = 0;
+    if (o < 4 * K)
+        for (int b = g; b < blocks; b += G) v += partial[(int64_t)b * 5 * K + o];
+    red[g][o] = v;
+    double nv = 0;      // (whole numbers: any order gives the same sum)
+    for (int b = threadIdx.x; b < blocks; b += kBlock)
+        for (int c = 0; c < K; ++c) nv += partial[(int64_t)b * 5 * K + 4 * K + c];
+    cnt[threadIdx.x] = nv;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double t[4][kMaxClasses], all[4] = {0, 0, 0, 0};
+    for (int q = 0; q < 4; ++q)
+        for (int c = 0; c < K; ++c) {
+            double a = 0;
+            for (int j = 0; j < G; ++j) a += red[j][q * K + c];
+            t[q][c] = a;
+            all[q] += a;
+            sums[q * kMaxClasses + c] = a;
+        }
+    double count = 0;
+    for (int j = 0; j < kBlock; ++j) count += cnt[j];
+    sums[4 * kMaxClasses] = count;
+    if (count == 0.0) {         // every pixel ignored: the loss is 0, and the backward kernel writes zeros
+        loss_out[0] = 0.0f;
+        return;
+    }
+    if (kind == 1) {
+        loss_out[0] = (float)(all[0] / count);
+        return;
+    }
+    const float bce = (float)(all[0] / count);
+    float dice;
+    if (kind == 0) {
+        const float inter = (float)all[1], sp = (float)all[2], st = (float)all[3];
+        dice = 1.0f - (2.0f * inter + 1.0f) / (sp + st + 1.0f);
+    } else {
+        dice = 0.0f;
+        for (int c = 0; c < K; ++c) {
+            const float inter = (float)t[1][c], sp = (float)t[2][c], st = (float)t[3][c];
+            dice += 1.0f - (2.0f * inter + 1.0f) / (sp + st + 1.0f);
+        }
+        dice /= (float)K;
+    }
+    loss_out[0] = bce + dice;
+}
+
+__global__ __launch_bounds__(kBlock) void masked_loss_bwd_kernel(const float* __restrict__ logits, const uint8_t* __restrict__ labels,
+                                                                 int64_t count, int K, int kind, float alpha, float gamma, int map,
+                                                                 int ignore, PosWeights pw, const double* __restrict__ sums,
+                                                                 float* __restrict__ dlogits) {
+    const int A = (kBlock / K) * K, k = threadIdx.x % K;
+    if ((int)threadIdx.x >= A) return;
+    const double n = sums[4 * kMaxClasses];         // N_v; 0: every element below is ignored and none divides by it
+    if (kind == 1) {
+        for (int64_t i = (int64_t)blockIdx.x * A + threadIdx.x; i < count; i += (int64_t)gridDim.x * A) {
+            const uint8_t b = labels[i / K];
+            dlogits[i] = label_ignored(b, ignore) ? 0.0f
+                                                  : (float)(focal_grad(logits[i], label_target(b, k, map, ignore), alpha, gamma) / n);
+        }
+        return;
+    }
+    const float wk = pos_weight_of(pw, k);
+    double s3[3];
+    for (int q = 1; q < 4; ++q) {
+        double a = 0;
+        if (kind == 0) for (int c = 0; c < K; ++c) a += sums[q * kMaxClasses + c];
+        else a = sums[q * kMaxClasses + k];
+        s3[q - 1] = a;
+    }
+    const float inter = (float)s3[0], sp = (float)s3[1], st = (float)s3[2];
+    const float D = sp + st + 1.0f;
+    const float num = 2.0f * inter + 1.0f;
+    const float invD2 = 1.0f / (D * D);
+    const float invN = (float)(1.0 / n);
+    const float wdice = kind == 0 ? 1.0f : 1.0f / (float)K;
+    for (int64_t i = (int64_t)blockIdx.x * A + threadIdx.x; i < count; i += (int64_t)gridDim.x * A) {
+        const uint8_t b = labels[i / K];
+        if (label_ignored(b, ignore)) {
+            dlogits[i] = 0.0f;
+            continue;
+        }
+        const float x = logits[i];
+        const bool pos = label_target(b, k, map, ignore);
+        const float t = pos ? 1.0f : 0.0f;
+        const float p = sigmoidf_(x);
+        const float ddice = -(2.0f * t * D - num) * invD2 * wdice;
+        // t ? -pi (1 - p) : p, with p - t as class_loss_bwd_kernel forms it
+        const float g = pos ? wk * (p - t) : p - t;
+        dlogits[i] = g * invN + ddice * p * (1.0f - p);
+    }
+}
+
+// class_confusion_kernel with the same two switches: an ignored pixel enters none of the three counts
+__global__ __launch_bounds__(kBlock) void masked_confusion_kernel(const float* __restrict__ logits, const uint8_t* __restrict__ labels,
+                                                                  int64_t count, int K, float thr, int map, int ignore,
+                                                                  unsigned long long* __restrict__ partial) {
+    __shared__ unsigned red[3][kBlock];
+    const int A = (kBlock / K) * K, k = threadIdx.x % K;
+    unsigned s[3] = {0, 0, 0};
+    if ((int)threadIdx.x < A) {
+        for (int64_t i = (int64_t)blockIdx.x * A + threadIdx.x; i < count; i += (int64_t)gridDim.x * A) {
+            const uint8_t b = labels[i / K];
+            if (label_ignored(b, ignore)) continue;
+            const bool p = (1.0f / (1.0f + expf(-logits[i]))) > thr;      // (threshold_kernel's expression)
+            const bool t = label_target(b, k, map, ignore);
+            s[0] += (p && t);
+            s[1] += (p && !t);
+            s[2] += (!p && t);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 3; ++q) red[q][threadIdx.x] = s[q];
+    __syncthreads();
+    if ((int)threadIdx.x < 3 * K) {
+        const int q = threadIdx.x / K, c = threadIdx.x % K;
+        unsigned long long v = 0;
+        for (int j = c; j < A; j += K) v += red[q][j];
+        partial[(int64_t)blockIdx.x * 3 * K + threadIdx.x] = v;
+    }
+}
+
 // (tp, fp, fn) per class of sigmoid(logit) > thr against the class bits: exact integers.  partial: blocks x 3 x K
 __global__ __launch_bounds__(kBlock) void class_confusion_kernel(const float* __restrict__ logits, const uint8_t* __restrict__ labels,
                                                                  int64_t count, int K, float thr, unsigned long long* __restrict__ partial) {
@@ -1957,6 +2145,55 @@ void launch_class_loss_bwd(rfi_ctx* ctx, const float* logits, const uint8_t* lab
     hipLaunchKernelGGL(class_loss_bwd_kernel, dim3(class_grid(count, K, 256 * 16)), dim3(kBlock), 0, ctx->stream, logits, labels,
                        count, K, kind, alpha, gamma, sums, dlogits);
     check_launch("class_loss_bwd");
+}
+static PosWeights pos_weights(const float* weights, int K) {
+    PosWeights pw;
+    for (int c = 0; c < kMaxClasses; ++c) pw.w[c] = weights && c < K ? weights[c] : 1.0f;
+    return pw;
+}
+size_t masked_loss_ws_doubles(int K) { return (size_t)5 * std::min(std::max(K, 1), kMaxClasses) * 1024 + 8; }
+void launch_masked_loss_reduce(rfi_ctx* ctx, const float* logits, const uint8_t* labels, int64_t pixels, int K, int kind,
+                               float alpha, float gamma, bool map, bool ignore, const float* weights_host, double* partial_ws,
+                               double* sums, float* loss_out) {
+    check_classes(K);
+    RFI_REQUIRE(!map || K == 1, "masked loss: a label map has one output channel");
+    const int64_t count = pixels * K;
+    const int blocks = class_grid(count, K, 1024);
+    {
+        ProfScope ps(ctx, FAM_ELEMWISE, 0, (double)count * 4 + (double)pixels, "masked_loss_reduce");
+        hipLaunchKernelGGL(masked_loss_reduce_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, logits, labels, count, K, kind,
+                           alpha, gamma, (int)map, (int)ignore, pos_weights(weights_host, K), partial_ws);
+        check_launch("masked_loss_reduce");
+    }
+    {
+        ProfScope ps(ctx, FAM_ELEMWISE, 0, 0, "masked_loss_finish");
+        hipLaunchKernelGGL(masked_loss_finish_kernel, dim3(1), dim3(kBlock), 0, ctx->stream, partial_ws, blocks, K, kind, sums,
+                           loss_out);
+        check_launch("masked_loss_finish");
+    }
+}
+void launch_masked_loss_bwd(rfi_ctx* ctx, const float* logits, const uint8_t* labels, int64_t pixels, int K, int kind, float alpha,
+                            float gamma, bool map, bool ignore, const float* weights_host, const double* sums, float* dlogits) {
+    check_classes(K);
+    RFI_REQUIRE(!map || K == 1, "masked loss: a label map has one output channel");
+    const int64_t count = pixels * K;
+    ProfScope ps(ctx, FAM_ELEMWISE, 0, (double)count * 8 + (double)pixels, "masked_loss_bwd");
+    hipLaunchKernelGGL(masked_loss_bwd_kernel, dim3(class_grid(count, K, 256 * 16)), dim3(kBlock), 0, ctx->stream, logits, labels,
+                       count, K, kind, alpha, gamma, (int)map, (int)ignore, pos_weights(weights_host, K), sums, dlogits);
+    check_launch("masked_loss_bwd");
+}
+void launch_masked_confusion(rfi_ctx* ctx, const float* logits, const uint8_t* labels, int64_t pixels, int K, float threshold,
+                             bool map, bool ignore, unsigned long long* partial_ws, unsigned long long* counts) {
+    check_classes(K);
+    RFI_REQUIRE(!map || K == 1, "masked counts: a label map has one output channel");
+    const int64_t count = pixels * K;
+    const int blocks = class_grid(count, K, 1024);
+    ProfScope ps(ctx, FAM_METRICS, 0, (double)count * 4 + (double)pixels, "masked_confusion");
+    hipLaunchKernelGGL(masked_confusion_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, logits, labels, count, K, threshold,
+                       (int)map, (int)ignore, partial_ws);
+    check_launch("masked_confusion");
+    hipLaunchKernelGGL(class_confusion_finish_kernel, dim3(1), dim3(64), 0, ctx->stream, partial_ws, blocks, K, counts);
+    check_launch("class_confusion_finish");
 }
 size_t class_confusion_ws_words(int K) { return (size_t)3 * K * 1024; }
 void launch_class_confusion(rfi_ctx* ctx, const float* logits, const uint8_t* labels, int64_t pixels, int K, float threshold,

@@ -269,6 +269,20 @@ void launch_class_loss_bwd(rfi_ctx* ctx, const float* logits, const uint8_t* lab
 size_t class_confusion_ws_words(int K);
 void launch_class_confusion(rfi_ctx* ctx, const float* logits, const uint8_t* labels, int64_t pixels, int K, float threshold,
                             unsigned long long* partial_ws, unsigned long long* counts);
+// The three losses with the ignore bit and per-channel positive weights (rfi_hip.h, rfi_model_set_ignore / _set_pos_weight),
+// for both label modes: map = one channel whose target is "any of the label's bits", else class bits; ignore = bit 7 of the
+// byte takes the pixel out of every sum, dlogits there is +0.  weights_host: K floats or null (all 1), passed as kernel
+// arguments.  sums: 4 x 8 doubles as above + the valid element count at [32] (it stays on the device); partial_ws:
+// masked_loss_ws_doubles(K) doubles.  The same element order and combination as the class_loss kernels
+size_t masked_loss_ws_doubles(int K);
+void launch_masked_loss_reduce(rfi_ctx* ctx, const float* logits, const uint8_t* labels, int64_t pixels, int K, int kind,
+                               float alpha, float gamma, bool map, bool ignore, const float* weights_host, double* partial_ws,
+                               double* sums, float* loss_out);
+void launch_masked_loss_bwd(rfi_ctx* ctx, const float* logits, const uint8_t* labels, int64_t pixels, int K, int kind, float alpha,
+                            float gamma, bool map, bool ignore, const float* weights_host, const double* sums, float* dlogits);
+// launch_class_confusion over the pixels that are not ignored, for either label mode
+void launch_masked_confusion(rfi_ctx* ctx, const float* logits, const uint8_t* labels, int64_t pixels, int K, float threshold,
+                             bool map, bool ignore, unsigned long long* partial_ws, unsigned long long* counts);
 // head backward: da[m,c] = sum_o dlogits[m,o]*w[o][c] (NOT yet relu-masked: bn_bwd does that);
 // dw[o][c] = sum_m dlogits[m,o]*act[m,c]; db[o] = sum_m dlogits[m,o]
 // bn_records_ws != null (+ the layer's batch mean / invstd): where the shape allows (Cout == 1, C % 4 == 0) the same pass
@@ -441,6 +455,10 @@ void launch_pol_gather_valid(rfi_ctx* ctx, const void* planes, int dtype, int C,
 // merged (n_samples, 4, C, T) = model_flags (n_samples, C, T) | invalid, the invalid visibilities decided as above
 void launch_valid_merge(rfi_ctx* ctx, const void* planes, int dtype, int n_samples, int64_t px, const uint8_t* flags_dev,
                         bool per_baseline, const uint8_t* model_flags, uint8_t* merged);
+// rfi_label_gather (pol_gather.hip): labels_dev (n_samples, C, T) bytes -> out (n, ps, ps) bytes by the same table, | 0x80 where
+// invalid_dev ((n_samples, 4, C, T), or (n_samples, C, T) when per_baseline; may be null) marks any / all of the polarisations
+void launch_label_gather(rfi_ctx* ctx, const uint8_t* labels_dev, int C, int T, const uint8_t* invalid_dev, bool per_baseline,
+                         bool all_rule, const rfi_patch_src* table_dev, int n, int ps, int pad_value, uint8_t* out);
 // training augmentation (augment.hip): flips and one composed affine warp of x [n][h][w][c] float32 and y [n][h][w] bytes
 // into x_out / y_out (never in place); the transform of sample i is drawn in the kernel from (cfg, call, i).
 // augment_params_host evaluates the same draw on the host: gates [n][4], inv [n][6].  Semantics in include/rfi_hip.h.

@@ -162,7 +162,7 @@ void rfi_model::prepare(int n, int h, int w) {
     bufs[lab_stage].ensure(ctx, dense_head ? (Mout + 3) / 4 + 4 : 16);
     // the workspaces: the needs every model has (gradient norm, loss), on top of what prepare_shape declared
     need_red(sumsq_ws_doubles(n_flat) * 2);
-    if (dense_head) need_red(std::max(loss_ws_doubles(Mout), class_loss_ws_doubles(out_ch)) * 2);
+    if (dense_head) need_red(std::max({loss_ws_doubles(Mout), class_loss_ws_doubles(out_ch), masked_loss_ws_doubles(out_ch)}) * 2);
     bufs[ws_red].ensure(ctx, red_need + 16);
     bufs[ws_slab].ensure(ctx, slab_need + 16);
     pN = n; pH = h; pW = w;
@@ -644,6 +644,13 @@ void UNetModel::forward_pass(const float* x_dev, int n, int h, int w, bool train
 
 void rfi_model::loss_forward(const uint8_t* labels_dev, int n, int h, int w) {
     const int64_t cnt = (int64_t)n * h * w * out_scale * out_scale;
+    if (masked_loss()) {          // (the setters admit the plain U-Net without the sigmoid head only)
+        RFI_REQUIRE(label_mode != RFI_LABELS_MAP || out_ch == 1, "loss: the reference's BCE+dice step is defined for out_channels == 1");
+        launch_masked_loss_reduce(ctx, buf(logits), labels_dev, cnt, out_ch, loss_kind, focal_alpha, focal_gamma,
+                                  label_mode == RFI_LABELS_MAP, ignore_on, weights_on ? pos_weight : nullptr,
+                                  reinterpret_cast<double*>(buf(ws_red)), class_sums(), d_scalars);
+        return;
+    }
     if (label_mode == RFI_LABELS_CLASS_BITS) {
         launch_class_loss_reduce(ctx, buf(logits), labels_dev, cnt, out_ch, loss_kind, focal_alpha, focal_gamma,
                                  reinterpret_cast<double*>(buf(ws_red)), class_sums(), d_scalars);
@@ -661,6 +668,10 @@ void rfi_model::loss_forward(const uint8_t* labels_dev, int n, int h, int w) {
 }
 
 void rfi_model::loss_backward(const uint8_t* labels_dev, int64_t pixels) {
+    if (masked_loss())
+        return launch_masked_loss_bwd(ctx, buf(logits), labels_dev, pixels, out_ch, loss_kind, focal_alpha, focal_gamma,
+                                      label_mode == RFI_LABELS_MAP, ignore_on, weights_on ? pos_weight : nullptr, class_sums(),
+                                      buf(dlogits));
     if (label_mode == RFI_LABELS_CLASS_BITS)
         return launch_class_loss_bwd(ctx, buf(logits), labels_dev, pixels, out_ch, loss_kind, focal_alpha, focal_gamma, class_sums(),
                                      buf(dlogits));

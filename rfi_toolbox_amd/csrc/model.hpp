@@ -169,6 +169,11 @@ struct rfi_model {
     // bit k is the target of output channel k (the plain U-Net without the sigmoid head)
     int label_mode = 0;
     float focal_alpha = 0.25f, focal_gamma = 2.0f;
+    // rfi_model_set_ignore / rfi_model_set_pos_weight: bit 7 of a label byte takes the pixel out of the loss and the counts;
+    // pos_weight[k] multiplies the positive BCE term of channel k.  Either one routes the loss through the masked kernels
+    bool ignore_on = false, weights_on = false;
+    float pos_weight[8] = {1, 1, 1, 1, 1, 1, 1, 1};
+    bool masked_loss() const { return ignore_on || weights_on; }
     bool head_sigmoid = false;        // UNetOverfit: forward returns sigmoid(logits); the loss sees that too
     // a per-pixel head of out_ch channels with the loss inside the model.  False (the backbone: out_ch is the FPN width): no
     // logits, no label map, no loss workspace
@@ -271,8 +276,8 @@ struct rfi_model {
     int x_stage = -1, x_stage2 = -1, x_pad = -1, out_stage = -1, ws_red = -1, ws_slab = -1, lab_stage = -1;
     int gx = -1;                      // the gradient w.r.t. the input (the detector's heads own it; -1: the model computes none)
     bool ext_dlogits = false;         // backward from caller-provided dlogits (rfi_model_backward_dlogits)
-    double* d_sums = nullptr;         // [0..3] loss sums, [4] grad sumsq, [5..7] eval_batch's counts, [8..39] class-bit loss sums (4 x 8)
-    static constexpr int kSumsDoubles = 40;
+    double* d_sums = nullptr;         // [0..3] loss sums, [4] grad sumsq, [5..7] eval_batch's counts, [8..39] class-bit loss sums (4 x 8), [40] the masked loss's valid element count
+    static constexpr int kSumsDoubles = 48;
     double* class_sums() const { return d_sums + 8; }
     float* d_scalars = nullptr;       // [0] loss, [1] grad norm
     float last_loss = 0, last_norm = 0;

@@ -199,7 +199,92 @@ __global__ __launch_bounds__(kBlock) void valid_merge_kernel(const S* __restrict
     merged[gid] = (model[b * px + i] != 0 || inv) ? 1 : 0;
 }
 
+// ---- label tiles (include/rfi_hip.h, rfi_label_gather): the label plane of every sample cut into the tiles of the same
+// table, one byte per pixel.  out = label | 0x80 where the pixel is invalid -- any (or, all_rule, all) of the npol invalid
+// bytes ipol apart -- and `pad` past the view's edge.  Same tile walk as pol_gather_kernel: the transposed views read with
+// the lanes along T, stage the bytes in LDS (one word each, rows 33 words apart) and store with the lanes along the patch
+// row.  2 to 5 bytes in and one out per pixel
+__device__ __forceinline__ unsigned label_byte(const uint8_t* lab, const uint8_t* inv, int64_t at, int npol, int64_t ipol, bool all_rule) {
+    unsigned b = lab[at];
+    if (inv) {
+        bool any = false, all = true;
+        for (int p = 0; p < npol; ++p) {
+            const bool f = inv[p * ipol + at] != 0;
+            any |= f;
+            all &= f;
+        }
+        if (all_rule ? all : any) b |= 0x80u;
+    }
+    return b;
+}
+
+__global__ __launch_bounds__(kBlock) void label_gather_kernel(const uint8_t* __restrict__ labels, const uint8_t* __restrict__ invalid,
+                                                              int64_t isample, int64_t ipol, int npol, int all_rule,
+                                                              const rfi_patch_src* __restrict__ table, int C, int T, int ps, int tiles,
+                                                              unsigned pad, uint8_t* __restrict__ out) {
+    __shared__ unsigned s_t[kTile][kPitch];                       // [patch column][patch row]
+    const int patch = blockIdx.y;
+    const rfi_patch_src e = table[patch];
+    const int y0 = (int)(blockIdx.x / tiles) * kTile, x0 = (int)(blockIdx.x % tiles) * kTile;
+    const bool tr = e.view >= 2, flip = (e.view & 1) != 0;
+    const int Hv = tr ? T : C, Wv = tr ? C : T;
+    const int64_t px = (int64_t)C * T;
+    const uint8_t* lab = labels + (int64_t)e.plane * px;
+    const uint8_t* inv = invalid ? invalid + (int64_t)e.plane * isample : nullptr;
+    uint8_t* o = out + (int64_t)patch * ps * ps;
+    const int l = threadIdx.x % kTile, g = threadIdx.x / kTile;
+    if (!tr) {                                                    // view[a][b] = plane[a or C-1-a][b]
+        const int x = x0 + l, vx = e.col0 + x;
+#pragma unroll
+        for (int i = 0; i < kTile / kRows; ++i) {
+            const int y = y0 + g + kRows * i, vy = e.row0 + y;
+            if (x >= ps || y >= ps) continue;
+            const bool inside = vy < Hv && vx < Wv;
+            const int sy = flip ? Hv - 1 - vy : vy;
+            o[(int64_t)y * ps + x] = (uint8_t)(inside ? label_byte(lab, inv, (int64_t)sy * T + vx, npol, ipol, all_rule != 0) : pad);
+        }
+        return;
+    }
+    {                                                             // view[a][b] = plane[b][a or T-1-a]
+        const int y = y0 + l, vy = e.row0 + y;
+        const int sx = flip ? Hv - 1 - vy : vy;
+#pragma unroll
+        for (int i = 0; i < kTile / kRows; ++i) {
+            const int xl = g + kRows * i, x = x0 + xl, vx = e.col0 + x;
+            if (x >= ps || y >= ps) continue;
+            const bool inside = vy < Hv && vx < Wv;
+            s_t[xl][l] = inside ? label_byte(lab, inv, (int64_t)vx * T + sx, npol, ipol, all_rule != 0) : pad;
+        }
+    }
+    __syncthreads();
+    const int x = x0 + l;
+#pragma unroll
+    for (int i = 0; i < kTile / kRows; ++i) {
+        const int yl = g + kRows * i, y = y0 + yl;
+        if (x >= ps || y >= ps) continue;
+        o[(int64_t)y * ps + x] = (uint8_t)s_t[l][yl];
+    }
+}
+
 }  // namespace
+
+void launch_label_gather(rfi_ctx* ctx, const uint8_t* labels_dev, int C, int T, const uint8_t* invalid_dev, bool per_baseline,
+                         bool all_rule, const rfi_patch_src* table_dev, int n, int ps, int pad_value, uint8_t* out) {
+    RFI_REQUIRE(C > 0 && T > 0 && ps > 0 && n >= 0, "label_gather: bad shape");
+    if (n == 0) return;
+    const size_t per = (size_t)ps * ps;
+    const int64_t px = (int64_t)C * T, isample = per_baseline ? px : 4 * px, ipol = per_baseline ? 0 : px;
+    ProfScope pf(ctx, FAM_PREPROCESS, 0, (double)n * per * (2 + (invalid_dev ? (per_baseline ? 1 : 4) : 0)), "label_gather");
+    const int tiles = (int)cdiv(ps, kTile);
+    RFI_REQUIRE((int64_t)tiles * tiles <= 0x7fffffff, "label_gather: patch too large for one launch");
+    for (int n0 = 0; n0 < n; n0 += kMaxGridY) {
+        const dim3 grid((unsigned)(tiles * tiles), (unsigned)std::min(n - n0, kMaxGridY));
+        hipLaunchKernelGGL(label_gather_kernel, grid, dim3(kBlock), 0, ctx->stream, labels_dev, invalid_dev, isample, ipol,
+                           per_baseline ? 1 : 4, (int)all_rule, table_dev + n0, C, T, ps, tiles, (unsigned)(pad_value & 0xFF),
+                           out + (size_t)n0 * per);
+        check_launch("label_gather");
+    }
+}
 
 void launch_pol_gather_valid(rfi_ctx* ctx, const void* planes, int dtype, int C, int T, const rfi_patch_src* table_dev, int n, int ps,
                              double centre, double scale, const double* params_dev, const uint8_t* flags_dev, bool per_baseline,

@@ -31,7 +31,7 @@ from ._lib import (COMBINE_MAX, COMBINE_MEAN, COMPLEX_CODES, DEVICE, EDGE_PAD, E
                    VALUES_PROBS, Tiling, check, lib)
 from .runtime import DeviceArray, check_out, context_for, describe, is_torch, operand, result_buffer, torch
 
-__all__ = ["predict_flags", "tile_observation", "stitch_patches", "tiling_count", "tiling_table", "check_tiling_args",
+__all__ = ["predict_flags", "tile_observation", "tile_labels", "stitch_patches", "tiling_count", "tiling_table", "check_tiling_args",
            "stitch_instances", "detect_observation"]
 
 _COMBINE = {"mean": COMBINE_MEAN, "max": COMBINE_MAX}
@@ -370,6 +370,56 @@ def tile_observation(data, patch_size, stride=None, views=1, edge="pad", normali
                                    None if fo is None else C.c_void_p(fo.ptr), DEVICE, fform, float(np.float32(fill)),
                                    C.c_void_p(res.ptr), DEVICE))
     del o, fo
+    return res
+
+
+def tile_labels(labels, patch_size, stride=None, views=1, edge="pad", invalid=None, invalid_rule="any", pad="ignore", device=None):
+    """The label planes of an observation cut into the tiles ``tile_observation`` cuts the data into, for training with
+    ``model.set_ignore(True)`` (``rfi_label_gather``).
+
+    ``labels``: ``(B, C, T)`` or ``(C, T)`` uint8 or bool (NumPy, torch or ``DeviceArray``), a map or class bits, one
+    plane per baseline.  ``invalid``: None, or non-zero where a visibility is invalid, per polarisation ``(B, 4, C, T)`` --
+    ``preprocessing.invalid_map(data, flags)`` -- or per baseline ``(B, C, T)``; such a pixel's byte gets bit 7
+    (``class_labels.IGNORE``).  ``invalid_rule``: a pixel is invalid when ``"any"`` or ``"all"`` of its four polarisations
+    are.  ``pad``: what a pixel past a view's edge holds (``edge="pad"``): ``"ignore"`` 0x80, ``"zero"`` 0.  Returns a
+    ``DeviceArray`` ``(N, ps, ps)`` uint8 in ``rfi_tiling`` order: row i is the label of ``tile_observation``'s row i."""
+    ps, s = check_tiling_args(patch_size, stride, views, "mean", edge)
+    if invalid_rule not in ("any", "all"):
+        raise ValueError(f"invalid_rule must be 'any' or 'all', got {invalid_rule!r}")
+    if pad not in ("ignore", "zero"):
+        raise ValueError(f"pad must be 'ignore' or 'zero', got {pad!r}")
+    shape, dt = describe(labels)[:2]
+    shape = tuple(int(v) for v in shape)
+    if dt is None or dt not in (np.dtype(np.uint8), np.dtype(np.bool_)):
+        raise TypeError(f"labels must be uint8 or bool, not {dt}")
+    if len(shape) not in (2, 3):
+        raise ValueError(f"labels must be (B, C, T) or (C, T), got shape {shape}")
+    n, Cn, Tn = (shape[0] if len(shape) == 3 else 1), shape[-2], shape[-1]
+    form = VALID_FLAGS_POL
+    if invalid is not None:
+        got, idt = describe(invalid)[:2]
+        got = tuple(int(v) for v in got)
+        if idt is None or idt not in (np.dtype(np.uint8), np.dtype(np.bool_)):
+            raise TypeError(f"invalid must be uint8 or bool, not {idt}")
+        if got in ((n, 4, Cn, Tn), (n, 4, Cn * Tn)) or (len(shape) == 2 and got == (4, Cn, Tn)):
+            form = VALID_FLAGS_POL
+        elif got == shape or got == (n, Cn, Tn):
+            form = VALID_FLAGS_BASELINE
+        else:
+            raise ValueError(f"invalid must be per polarisation {(n, 4, Cn, Tn)} or per baseline {(n, Cn, Tn)}, got shape {got}")
+    ctx = context_for(device, labels, invalid)
+    table = tiling_table(n, Cn, Tn, ps, s, views, edge)
+    res = ctx.empty((len(table), ps, ps), np.uint8)
+    if not len(table) or not Cn * Tn:
+        return res
+    o = operand(labels, ctx, (np.uint8,), to_device=True)
+    io = None if invalid is None else operand(invalid, ctx, (np.uint8,), to_device=True)
+    check(lib.rfi_label_gather(ctx.handle, C.c_void_p(o.ptr), DEVICE, n, Cn, Tn, None if io is None else C.c_void_p(io.ptr), DEVICE,
+                               form, 1 if invalid_rule == "all" else 0, table.ctypes.data_as(C.c_void_p), len(table), ps,
+                               0x80 if pad == "ignore" else 0, C.c_void_p(res.ptr), DEVICE))
+    if any(is_torch(k.keep) or k.keep is not x for k, x in ((o, labels), (io, invalid)) if k is not None):
+        ctx.synchronize()                 # (an uploaded or converted copy goes with this frame)
+    del o, io
     return res
 
 

@@ -122,6 +122,10 @@ class HipSegmenter:
         check(lib.rfi_model_set_training(self._h, 1 if self.training else 0))
         if self.targets != "map":
             self.set_targets(self.targets)
+        if self.ignore:
+            self.set_ignore(True)
+        if self.pos_weight is not None:
+            self.set_pos_weight(self.pos_weight)
 
     def _release(self):
         if self._h is not None:
@@ -206,6 +210,37 @@ class HipSegmenter:
             raise ValueError(f"targets must be 'map' or 'class_bits', got {kind!r}")
         check(lib.rfi_model_set_label_mode(self._h, code))
         self.targets = kind
+        return self
+
+    ignore = False           # plain values: a caller can keep them in a checkpoint's ``args``
+    pos_weight = None
+
+    def set_ignore(self, enabled=True):
+        """With the switch on, a pixel whose label byte has bit 7 (``class_labels.IGNORE``) set takes no part in
+        ``train_step``, ``loss``, ``forward_backward``, ``train_step_async`` or ``eval_batch``: it enters no sum of the loss,
+        its ``dlogits`` are +0.0 and it is in none of the counts.  The loss is the mean over the pixels that are left (0 when
+        there are none).  Map targets: the target of a pixel that is not ignored is ``(label & 0x7F) != 0``.  Class-bit
+        targets: the pixel is ignored for all channels, which needs ``out_channels <= 7``.  Off (the default): bit 7 means
+        what it always did.  ``eval_sweep`` raises while the switch is on.  ``UNet``, ``UNetBigger`` and
+        ``UNetDifferentActivation`` only."""
+        check(lib.rfi_model_set_ignore(self._h, 1 if enabled else 0))
+        self.ignore = bool(enabled)
+        return self
+
+    def set_pos_weight(self, weights=None):
+        """Weights of the positive BCE term per output channel, as ``torch.nn.BCEWithLogitsLoss(pos_weight=)``: a sequence of
+        ``out_channels`` floats, one float for all channels, or ``None`` to clear them.  Each finite and >= 0.  They apply
+        with ``"bce_dice"`` and ``"bce_class_dice"`` (not to the dice term); ``"focal"`` has ``alpha`` and refuses them."""
+        if weights is None:
+            check(lib.rfi_model_set_pos_weight(self._h, None, 0))
+            self.pos_weight = None
+            return self
+        w = np.asarray(weights, dtype=np.float32)
+        if w.ndim == 0:
+            w = np.full(self.out_channels, w, np.float32)
+        w = np.ascontiguousarray(w.reshape(-1))
+        check(lib.rfi_model_set_pos_weight(self._h, w.ctypes.data_as(C.POINTER(C.c_float)), int(w.size)))
+        self.pos_weight = [float(v) for v in w]
         return self
 
     # ---- mode
@@ -461,7 +496,9 @@ class HipSegmenter:
 
     def eval_sweep(self, data, mask, thresholds):
         """int64 (K, 3): ``eval_batch(data, mask, t)`` for every ``t`` of ``thresholds`` from ONE forward pass (more than
-        1024 distinct thresholds: one pass per 1024).  Rows follow the caller's order, duplicates included."""
+        1024 distinct thresholds: one pass per 1024).  Rows follow the caller's order, duplicates included.  Raises while
+        ``set_ignore`` is on (the sweep's pooled count is the size of the label array): sweep the valid pixels with
+        ``evaluation.threshold_sweep(prob[valid], truth[valid])``."""
         from ..evaluation.sweep import MAX_THRESHOLDS, prepare_thresholds
         thr, uniq, inverse = prepare_thresholds(thresholds)
         n, h, w, xp, xm, yp, ym, keep = self._xy(data, mask, True)

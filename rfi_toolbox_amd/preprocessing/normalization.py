@@ -34,9 +34,9 @@ is given, so ``fit`` and ``transform`` may see different flags.
 
 Deviation: with ``flags=None`` input holding a NaN or an infinity raises ``ValueError`` in ``fit``, as before
 (scikit-learn skips NaN; the reference's simulated data never has one).  Measured data does: pass its ``FLAG`` column,
-or ``flags="nonfinite"``.  Out of scope here: an ignore mask in the training loss (training on real data feeds ``fill``
-inputs with the prior flags as labels, as the reference does), ``detect_observation``, the 3-channel ``Preprocessor``
-path and ``RFIMaskDataset``, none of which takes ``flags``.
+or ``flags="nonfinite"``.  ``invalid_map`` hands the same decision out as bytes, for ``inference.tile_labels`` to put
+into the label tiles as the ignore bit of ``model.set_ignore(True)``.  Out of scope here: ``detect_observation``, the
+3-channel ``Preprocessor`` path and ``RFIMaskDataset``, none of which takes ``flags``.
 """
 from __future__ import annotations
 
@@ -45,7 +45,7 @@ import math
 
 import numpy as np
 
-__all__ = ["Normalizer", "normalize_array", "METHODS"]
+__all__ = ["Normalizer", "normalize_array", "invalid_map", "METHODS"]
 
 METHODS = ("global_min_max", "standardize", "robust_scale", None)
 _EPS = float(np.finfo(np.float64).eps)
@@ -112,6 +112,25 @@ def _invalid_map(ctx, src, desc, flags, form):
                                 n, px, None if fo is None else C.c_void_p(fo.ptr), form or 0, C.c_void_p(vmap.ptr), None, 0))
         if fo is not None and fo.keep is not flags:
             ctx.synchronize()                           # (an uploaded copy of the flags goes with this frame)
+    return vmap
+
+
+def invalid_map(data, flags=None, layout=None, device=None):
+    """``DeviceArray`` ``(n, 4, T, F)`` uint8, 1 where a visibility of `data` is invalid: its prior flag is set or its real or
+    imaginary part is non-finite (``rfi_valid_map``, what ``transform(flags=)`` and ``tile_observation(flags=)`` decide
+    internally).  `data`: any input this module accepts (NumPy or ``DeviceArray``); `flags`: prior flags per
+    polarisation or per baseline, None or ``"nonfinite"``: none.  ``inference.tile_labels(invalid=)`` takes the result."""
+    from ..runtime import DeviceArray, context_for, operand
+    if not isinstance(data, DeviceArray):
+        data = np.asarray(data)
+    n, px, lay, (T, F) = _describe(data, layout)
+    form = None if flags is None else _flags_form(flags, n, (T, F))
+    ctx = context_for(device, data, flags)
+    src = operand(data, ctx, tuple(_SCALAR), to_device=True)
+    vmap = _invalid_map(ctx, src, (n, px, lay), flags if form is not None else None, form)
+    if src.keep is not data:
+        ctx.synchronize()                               # (an uploaded copy of the data goes with this frame)
+    vmap.shape = (n, 4, T, F)                           # (the same bytes: pixels = T F)
     return vmap
 
 

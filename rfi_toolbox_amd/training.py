@@ -83,7 +83,9 @@ def sweep_rfi_model(model, dataset, batch_size=4, thresholds=None):
     (float32, the caller's order; None: 0.01 ... 0.99), ``mean_per_batch`` metric -> (K,) under the reference's rule
     (the mean of the per-batch metrics, evaluate_model.py:54-56 -- at a threshold of the sweep it equals
     ``evaluate_rfi_model(..., threshold=t)``), ``pooled`` the ``ThresholdSweep`` of all batches' counts together,
-    ``best`` metric -> (threshold, value) under the per-batch rule, ties to the lowest threshold."""
+    ``best`` metric -> (threshold, value) under the per-batch rule, ties to the lowest threshold.  Raises while the model's
+    ignore switch is on (``set_ignore``), as ``eval_sweep`` does: the pooled count is the size of the label array.  Sweep the
+    valid pixels with ``evaluation.threshold_sweep(prob[valid], truth[valid])`` instead."""
     from .evaluation.sweep import prepare_thresholds, sweep_from_counts
     thr = prepare_thresholds(thresholds)[0]
     images, labels = _pair(dataset)
