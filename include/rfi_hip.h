@@ -581,6 +581,40 @@ int rfi_simulate_rfi(rfi_ctx* ctx, uint64_t seed, uint64_t first_sample, int n_s
                      const double* power_range_dev, int out_layout, void* out_dev, uint8_t* mask_dev,
                      rfi_sim_event* events_dev, double* baseline_frac_dev);
 
+/*      rfi_sim_inject: the events of rfi_simulate_rfi ADDED to visibilities that already exist (RFISimulator.inject), so that
+ *      a measured background gets an exact truth.  The event table and every per-pixel draw are those of rfi_simulate_rfi
+ *      for the same (seed, first_sample + s); stream 8 (the noise) is not drawn.  params->clean must be 0.
+ *
+ *      data_dev / out_dev: (n, 4, R, S) complex128 (layout RFI_SIM_C128) or complex64 (RFI_SIM_C64), RR, RL, LR, LL; out_dev
+ *      may be data_dev.  rows RFI_INJECT_ROWS_TIME: the planes are (T, F), simulator pixel (t, f) is element [t][f];
+ *      RFI_INJECT_ROWS_CHANNEL: they are (F, T) and pixel (t, f) is element [f][t].  mask_dev (n, R, S) uint8 is laid out
+ *      like the planes.  sigma_dev: n doubles, the noise scale of each sample's data (finite and positive: the caller checks).
+ *      flags_dev: NULL, or uint8 prior flags (n, 4, R, S) (flag_pols 4) or (n, R, S) (flag_pols 1: all four polarisations).
+ *
+ *      Per pixel, in fp64 (complex64 is widened): rr = RR and ll = LL as loaded, S = 0.  Every contribution v that
+ *      rfi_simulate_rfi adds to RR / LL is added in its order as c = (sigma v.re, sigma v.im), each product rounded once
+ *      and then added (no fused multiply-add): rr += c, ll += c (the quadratic sweeps: rr only), and S += c whenever rr
+ *      gets c.  With gibbs_ringing v is the convolved / spread value.  With sigma = 1.0 this is rfi_simulate_rfi's arithmetic
+ *      on its noise.  Cross hands, with the factors frl, flr of draw (t F + f, 0, 14):
+ *        RFI_INJECT_CROSS_INJECTED   rl = RL + frl S, lr = LR + flr S             (only where something was added to RR)
+ *        RFI_INJECT_CROSS_REFERENCE  rl = RL + frl rr, lr = LR + flr rr           (the reference's rule on the whole RR)
+ *      A visibility to which nothing was added, and a visibility whose flag is set, is stored exactly as loaded, bit for bit
+ *      (tracked with a flag, not left to x + 0); S does not depend on RR's flag.  Every other one is the fp64 value rounded
+ *      once to the data's type.  The mask is rfi_simulate_rfi's: decided in noise units, before sigma, whatever the flags.
+ *      events_dev, baseline_frac_dev: as rfi_simulate_rfi fills them.  Sizes: those of rfi_simulate_rfi with clean == 0.
+ *      Device pointers only; stream-ordered on the context's stream; no atomics, nothing allocates or synchronises;
+ *      results do not depend on the launch geometry.
+ *
+ *      rfi_sim_transpose_planes: dst[i][c][r] = src[i][r][c] for n byte planes of rows x cols (device, dst != src), the
+ *      orientation change of rfi_sim_family_bits' output for a RFI_INJECT_ROWS_CHANNEL batch.  Stream-ordered. */
+enum { RFI_INJECT_ROWS_TIME = 0, RFI_INJECT_ROWS_CHANNEL = 1 };
+enum { RFI_INJECT_CROSS_INJECTED = 0, RFI_INJECT_CROSS_REFERENCE = 1 };
+int rfi_sim_inject(rfi_ctx* ctx, uint64_t seed, uint64_t first_sample, int n_samples, const rfi_sim_params* params,
+                   const double* power_range_dev, int layout, int rows, int cross_hand, const void* data_dev,
+                   const uint8_t* flags_dev, int flag_pols, const double* sigma_dev, void* out_dev, uint8_t* mask_dev,
+                   rfi_sim_event* events_dev, double* baseline_frac_dev);
+int rfi_sim_transpose_planes(rfi_ctx* ctx, const uint8_t* src_dev, int64_t n, int rows, int cols, uint8_t* dst_dev);
+
 /*      Per-emitter targets of a generated batch (rfi_toolbox_amd.core.event_instances): one event is one instance.
  *      Both calls take the (seed, first_sample, n_samples, params, power_range_dev, events_dev) of the rfi_simulate_rfi call
  *      that made the batch (sample s draws with c3 = first_sample + s) and recompute, with the pixel kernel's own device

@@ -232,6 +232,9 @@ _PROTOS = {
     "rfi_sim_event_table": (_i, [_vp, C.c_uint64, C.c_uint64, _i, C.POINTER(SimParams), _vp, _vp, _vp, _vp]),
     "rfi_sim_instances": (_i, [_vp, C.c_uint64, C.c_uint64, _i, C.POINTER(SimParams), _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "rfi_sim_family_bits": (_i, [_vp, C.c_uint64, C.c_uint64, _i, C.POINTER(SimParams), _vp, _vp, _vp]),
+    "rfi_sim_inject": (_i, [_vp, C.c_uint64, C.c_uint64, _i, C.POINTER(SimParams), _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp,
+                            _vp]),
+    "rfi_sim_transpose_planes": (_i, [_vp, _vp, _i64, _i, _i, _vp]),
     "rfi_flag_statistics": (_i, [_vp, _vp, _i, _i, _i64, _vp, _i, _i, _i, C.POINTER(FlagStats), C.POINTER(FlagStats)]),
     "rfi_norm_bracket": (_i, [_i64, C.c_double, _pi64, _pd]),
     "rfi_norm_statistics": (_i, [_vp, _pvp, _pi64, _i, _i, _i64, _i, C.POINTER(NormStats), _i]),

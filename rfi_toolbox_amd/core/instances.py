@@ -36,6 +36,13 @@ def _origin(batch):
     return int(batch.mask.shape[0]), o.T, o.F, event_slots(o.T, o.F) - 1
 
 
+def _time_rows(batch, who):
+    if batch.rows != "time":
+        raise ValueError(f"{who} describes events in the simulator's (time, channel) orientation -- boxes are (channel, time, channel, "
+                         f"time) and masks (T, F) -- but this batch was injected with rows={batch.rows!r}, whose planes are "
+                         "(channel, time): inject with rows='time' for instance targets (family_masks works on both)")
+
+
 def _sim_args(batch):
     o = batch.origin
     return (batch.mask.ctx.handle, o.seed, o.first_sample, int(batch.mask.shape[0]), C.byref(o.params), C.c_void_p(o.power.ptr),
@@ -56,6 +63,7 @@ def event_table(batch):
     inclusive over them, x the channel and y the time row, (0, 0, 0, 0) for an event that flags nothing (an unused third
     broadband slot among them).  A clean batch has no events: S columns of zeros."""
     n, T, F, S = _origin(batch)
+    _time_rows(batch, "event_table")
     ctx = batch.mask.ctx
     if batch.events is None or n == 0:
         area, box = ctx.empty((n, S), np.int32), ctx.empty((n, S, 4), np.int32)
@@ -70,16 +78,23 @@ def family_masks(batch):
     bit ``c - 1`` is set where an event of ``EVENT_CLASSES[c]`` (c = 1 .. 5) flags the pixel.  These are class-bit labels
     for ``UNet(8, 5, ...).set_targets("class_bits")``; ``bits != 0`` is ``batch.mask``, a pixel several families flag
     carries all their bits, and ``gibbs_ringing`` changes nothing.  One kernel (``rfi_sim_family_bits``): no instance
-    mask is formed.  A clean batch has no events and gives zeros (a fill), an empty one nothing at all."""
+    mask is formed.  A clean batch has no events and gives zeros (a fill), an empty one nothing at all.  A batch of
+    ``inject(rows="channel")`` gives (n, F, T), the orientation of its mask: the same kernel, then a byte-plane transpose."""
     n, T, F, _ = _origin(batch)
     ctx = batch.mask.ctx
-    bits = ctx.empty((n, T, F), np.uint8)
     if batch.events is None or n == 0:
+        bits = ctx.empty((n, T, F) if batch.rows == "time" else (n, F, T), np.uint8)
         if n:
             bits.zero_()
         return bits
+    bits = ctx.empty((n, T, F), np.uint8)
     from .._lib import check, lib
     check(lib.rfi_sim_family_bits(*_sim_args(batch), C.c_void_p(bits.ptr)))
+    if batch.rows == "channel":                             # the kernel writes (T, F): turn the byte planes into the batch's (F, T)
+        turned = ctx.empty((n, F, T), np.uint8)
+        check(lib.rfi_sim_transpose_planes(ctx.handle, C.c_void_p(bits.ptr), n, T, F, C.c_void_p(turned.ptr)))
+        ctx.synchronize()                                   # (`bits` goes with this frame)
+        return turned
     return bits
 
 
@@ -101,6 +116,7 @@ def event_instances(batch, min_area=1, min_side=1, max_instances=64, classes="fa
     if not isinstance(classes, str) or classes not in _CLASS_MODES:
         raise ValueError(f"classes must be 'family' or 'single', got {classes!r}")
     n, T, F, S = _origin(batch)
+    _time_rows(batch, "event_instances")
     G = int(max_instances)
     num_classes = len(EVENT_CLASSES) if classes == "family" else 2
     if n == 0 or batch.events is None:                      # nothing to select from (a clean batch has no events): no device call

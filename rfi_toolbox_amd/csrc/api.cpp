@@ -1413,6 +1413,36 @@ int rfi_sim_family_bits(rfi_ctx* ctx, uint64_t seed, uint64_t first_sample, int 
         launch_rfi_sim_family_bits(ctx, seed, (unsigned)first_sample, n_samples, *params, power_range_dev, events_dev, bits);
     });
 }
+int rfi_sim_inject(rfi_ctx* ctx, uint64_t seed, uint64_t first_sample, int n_samples, const rfi_sim_params* params,
+                   const double* power_range_dev, int layout, int rows, int cross_hand, const void* data_dev,
+                   const uint8_t* flags_dev, int flag_pols, const double* sigma_dev, void* out_dev, uint8_t* mask_dev,
+                   rfi_sim_event* events_dev, double* baseline_frac_dev) {
+    return guarded([&] {
+        RFI_REQUIRE(ctx && params, "sim_inject: null argument");
+        require_sim_events_batch("sim_inject", *params, first_sample, n_samples);
+        RFI_REQUIRE(layout == RFI_SIM_C128 || layout == RFI_SIM_C64, "sim_inject: the planes are complex128 or complex64");
+        RFI_REQUIRE(rows == RFI_INJECT_ROWS_TIME || rows == RFI_INJECT_ROWS_CHANNEL, "sim_inject: bad rows");
+        RFI_REQUIRE(cross_hand == RFI_INJECT_CROSS_INJECTED || cross_hand == RFI_INJECT_CROSS_REFERENCE, "sim_inject: bad cross_hand");
+        RFI_REQUIRE(!flags_dev || flag_pols == 1 || flag_pols == 4, "sim_inject: flag_pols must be 1 or 4");
+        RFI_REQUIRE(rfi_sim_inject_blocks(n_samples, params->time_bins, params->freq_bins, params->gibbs_ringing, rows) < ((int64_t)1 << 31),
+                    "sim_inject: batch too large for one launch");
+        RFI_REQUIRE(power_range_dev && data_dev && sigma_dev && out_dev && mask_dev && events_dev, "sim_inject: null buffer");
+        if (n_samples == 0) return;
+        ctx->activate();
+        launch_rfi_sim_inject(ctx, seed, (unsigned)first_sample, n_samples, *params, power_range_dev, layout, rows, cross_hand, data_dev,
+                              flags_dev, flag_pols, sigma_dev, out_dev, mask_dev, events_dev, baseline_frac_dev);
+    });
+}
+int rfi_sim_transpose_planes(rfi_ctx* ctx, const uint8_t* src_dev, int64_t n, int rows, int cols, uint8_t* dst_dev) {
+    return guarded([&] {
+        RFI_REQUIRE(ctx, "sim_transpose_planes: null argument");
+        RFI_REQUIRE(n >= 0 && rows >= 1 && cols >= 1, "sim_transpose_planes: bad sizes");
+        RFI_REQUIRE(src_dev && dst_dev && src_dev != dst_dev, "sim_transpose_planes: null buffer, or dst is src");
+        if (n == 0) return;
+        ctx->activate();
+        launch_rfi_sim_transpose_bytes(ctx, src_dev, n, rows, cols, dst_dev);
+    });
+}
 namespace {
 void norm_bracket(int64_t count, double q, int64_t* ranks, double* frac) {
     const double v = q * (double)(count - 1), f = std::floor(v);

@@ -535,6 +535,15 @@ void launch_stitch_instances(rfi_ctx* ctx, const float* boxes, const float* scor
 void launch_rfi_sim(rfi_ctx* ctx, unsigned long long seed, unsigned first_sample, int n_samples,
                     const rfi_sim_params& p, const double* power_dev, int layout, void* out, uint8_t* mask,
                     rfi_sim_event* events, double* baseline_out);
+// rfi_sim_inject (rfi_sim.hip): the event table of (seed, first_sample + s) drawn into `events`, then one gather per pixel
+// that adds the events, scaled by sigma[s], to the visibilities of `data` into `out` (layout RFI_SIM_C128 / RFI_SIM_C64; may
+// be `data`) and writes `mask`; rfi_sim_inject_blocks: the workgroups of that launch.  Sizes are checked by rfi_sim_inject
+int64_t rfi_sim_inject_blocks(int n_samples, int T, int F, int ringing, int rows);
+void launch_rfi_sim_inject(rfi_ctx* ctx, unsigned long long seed, unsigned first_sample, int n_samples, const rfi_sim_params& p,
+                           const double* power_dev, int layout, int rows, int cross_hand, const void* data, const uint8_t* flags,
+                           int flag_pols, const double* sigma, void* out, uint8_t* mask, rfi_sim_event* events, double* baseline_out);
+// dst[i][c][r] = src[i][r][c] over n byte planes of rows x cols (family_masks of a rows="channel" batch)
+void launch_rfi_sim_transpose_bytes(rfi_ctx* ctx, const uint8_t* src, int64_t n, int rows, int cols, uint8_t* dst);
 // per-event targets recomputed from the event table (rfi_sim.hip; include/rfi_hip.h, "per-emitter targets"): area and box of
 // every event slot; classes and instance masks of the slots rfi_op_instances_select kept.  Sizes are checked by the callers
 void launch_rfi_sim_event_table(rfi_ctx* ctx, unsigned long long seed, unsigned first_sample, int n_samples, const rfi_sim_params& p,

@@ -16,6 +16,10 @@
 // sums its 17 taps from there.  Narrowband / burst lines are one value per (event, row) or (event, column) and
 // are evaluated by the lanes that need them.
 //
+// The gather itself is the device function gather_events, which rfisim_inject_kernel (rfi_sim_inject: the same events added
+// to visibilities that already exist, at the data's noise scale) calls too, with another sink and, for (channel, time)
+// planes, another tile.
+//
 // Per-emitter targets (below the pixel kernel): rfisim_event_table_kernel and rfisim_instance_masks_kernel recompute the
 // pixels each event ALONE flags from the event table, through the device functions the pixel kernel decides its mask
 // with -- one event is one instance of the detector's ground truth (include/rfi_hip.h, "per-emitter targets").
@@ -208,6 +212,131 @@ __device__ __forceinline__ void add(double2& acc, double2 v) {
     acc.y = acc.y + v.y;
 }
 
+// The event gather of one pixel (t, f) of sample s, shared by the generating kernel and the injecting one: every
+// contribution in the reference's order -- broadband chunks, narrowband channels, burst rows, linear sweeps to
+// sink.par (RR and LL), then the quadratic sweeps to sink.rr_only -- and the truth mask as the return value.  The
+// workgroup's kChunk lanes tile TT rows x TF columns whose first pixel is (t0, f0); lane (lt, lf) of the tile owns
+// (t, f) = (t0 + lt, f0 + lf) and `active` says that pixel exists.  Only the ringing broadband stage knows the tile:
+// it stages each chunk's fields for the tile's rows with an 8-column halo in LDS.  Every lane of the workgroup must
+// call this (a barrier and readlane broadcasts inside), and no draw depends on the tile shape.
+template <bool RING, int TT, int TF, class Sink>
+__device__ __forceinline__ bool gather_events(const SimDev& d, int s, unsigned sample, int t0, int f0, int lt, int lf, bool active,
+                                              Sink& sink) {
+    static_assert(TT * TF == kChunk, "a tile is one workgroup");
+    constexpr int W = TF + 2 * kHalo;
+    const int T = d.T, F = d.F, t = t0 + lt, f = f0 + lf;
+    const rfi_sim_event* __restrict__ E = d.ev + (int64_t)s * d.slots;
+    const int nbb = E[0].i0;
+    const double floor = d.floor;
+    bool m = false;
+    // broadband chunks, in event order (:162-176)
+    if (RING) {
+        __shared__ double2 seg[3][TT][W];
+        for (int b = 0; b < nbb; ++b) {
+            const rfi_sim_event e = E[1 + b];
+            const int lo = max(e.i0, f0 - kHalo), hi = min(e.i0 + e.i1, f0 + TF + kHalo);
+            for (int idx = (int)threadIdx.x; idx < TT * W; idx += kChunk) {
+                const int r = idx / W, w = idx - r * W, c = f0 - kHalo + w;
+                if (c >= lo && c < hi && t0 + r < T) seg[b][r][w] = broadband_field(d, e, b, t0 + r, c, sample);
+            }
+        }
+        __syncthreads();
+        for (int b = 0; b < nbb; ++b) {
+            const int c0 = E[1 + b].i0, c1 = c0 + E[1 + b].i1;
+            if (active && f >= c0 && f < c1) {
+                const double2 own = seg[b][lt][lf + kHalo];
+                m = m || detectable(own, floor);
+                // np.convolve(row, k, 'same'): out[f] = sum_c row[c] k[f - c + 8], zeros outside the chunk
+                double2 acc = make_double2(0.0, 0.0);
+                const int lo = max(c0, f - kHalo), hi = min(c1 - 1, f + kHalo);
+                for (int c = lo; c <= hi; ++c) {
+                    const double2 v = seg[b][lt][c - f0 + kHalo];
+                    const double k = d.gk[f - c + kHalo];
+                    acc.x = acc.x + v.x * k;
+                    acc.y = acc.y + v.y * k;
+                }
+                sink.par(acc);
+            }
+        }
+    } else {
+        for (int b = 0; b < nbb; ++b) {
+            const rfi_sim_event e = E[1 + b];
+            if (active && f >= e.i0 && f < e.i0 + e.i1) {
+                const double2 v = broadband_field(d, e, b, t, f, sample);
+                m = m || detectable(v, floor);
+                sink.par(v);
+            }
+        }
+    }
+    // narrowband channels (:178-188): the line value at row t, deposited on its channel or spread +-8 channels
+    // (the channels / rows are fetched 64 at a time, one per lane, and broadcast with readlane: a dependent
+    // scalar load per event would put one memory latency per event on every wave)
+    const int lane = (int)(threadIdx.x & 63);
+    for (int base = 0; base < d.NN; base += 64) {
+        const int mine = base + lane < d.NN ? E[4 + base + lane].i0 : 0;
+        const int cnt = min(64, d.NN - base);
+        for (int j = 0; j < cnt; ++j) {
+            const int k = base + j;
+            const int df = f - __builtin_amdgcn_readlane(mine, j);
+            if (active && (RING ? (df >= -kHalo && df <= kHalo) : df == 0)) {
+                const rfi_sim_event e = E[4 + k];
+                const double2 v = narrowband_field(d, e, k, t, sample);
+                if (df == 0) m = m || detectable(v, floor);
+                sink.par(RING ? make_double2(v.x * d.gk[df + kHalo], v.y * d.gk[df + kHalo]) : v);
+            }
+        }
+    }
+    // burst rows (:190-199)
+    for (int base = 0; base < d.NB; base += 64) {
+        const int mine = base + lane < d.NB ? E[4 + d.NN + base + lane].i0 : 0;
+        const int cnt = min(64, d.NB - base);
+        for (int j = 0; j < cnt; ++j) {
+            const int k = base + j;
+            const int dt = t - __builtin_amdgcn_readlane(mine, j);
+            if (active && (RING ? (dt >= -kHalo && dt <= kHalo) : dt == 0)) {
+                const rfi_sim_event e = E[4 + d.NN + k];
+                const double2 v = burst_field(d, e, k, f, sample);
+                if (dt == 0) m = m || detectable(v, floor);
+                sink.par(RING ? make_double2(d.gk[dt + kHalo] * v.x, d.gk[dt + kHalo] * v.y) : v);
+            }
+        }
+    }
+    // linear sweeps (:201-214): point i = t - start_t, channel int(start_f + slope i) % F
+    for (int k = 0; k < 5; ++k) {
+        const rfi_sim_event e = E[4 + d.NN + d.NB + k];
+        const int i = sweep_point(e, t, T);
+        if (active && i < T / 2) {
+            const int fi = linear_channel(e, i, F);
+            if (f == fi) {
+                const double amp = sweep_amp(d, i, k, S_LINEAR_PT, sample);
+                sink.par(field(amp, phase(e, t, fi)));
+                m = m || amp > floor;
+            }
+        }
+    }
+    // quadratic sweeps, RR only (:216-228): channel (start_f + (direction t^2) // 100) % F, floor division
+    for (int k = 0; k < 5; ++k) {
+        const rfi_sim_event e = E[9 + d.NN + d.NB + k];
+        const int tt = sweep_point(e, t, T);
+        if (active && tt < T / 4) {
+            const int fi = quadratic_channel(e, tt, F);
+            if (f == fi) {
+                const double amp = sweep_amp(d, tt, k, S_QUAD_PT, sample);
+                sink.rr_only(field(amp, phase(e, t, fi)));
+                m = m || amp > floor;
+            }
+        }
+    }
+    return m;
+}
+
+// the generating kernel's sums: RR and LL start as their noise
+struct GenSink {
+    double2 rr, ll;
+    __device__ __forceinline__ void par(double2 v) { add(rr, v); add(ll, v); }
+    __device__ __forceinline__ void rr_only(double2 v) { add(rr, v); }
+};
+
 template <bool RING>
 __global__ __launch_bounds__(kChunk) void rfisim_pixels_kernel(SimDev d) {
     const int nchunk = (d.F + kChunk - 1) / kChunk;
@@ -220,132 +349,28 @@ __global__ __launch_bounds__(kChunk) void rfisim_pixels_kernel(SimDev d) {
     const unsigned sample = d.first + (unsigned)s;
     const unsigned pix = (unsigned)t * (unsigned)F + (unsigned)(active ? f : 0);
 
-    double2 rr, rl, lr, ll;
+    GenSink g;
+    double2 rl, lr;
     {
         const U4 a = draw(d, pix, 0, S_NOISE, sample), b = draw(d, pix, 1, S_NOISE, sample);
-        normal2(a.x, a.y, rr.x, rr.y);
+        normal2(a.x, a.y, g.rr.x, g.rr.y);
         normal2(a.z, a.w, rl.x, rl.y);
         normal2(b.x, b.y, lr.x, lr.y);
-        normal2(b.z, b.w, ll.x, ll.y);
+        normal2(b.z, b.w, g.ll.x, g.ll.y);
     }
     bool m = false;
     if (!d.clean) {
-        const rfi_sim_event* __restrict__ E = d.ev + (int64_t)s * d.slots;
-        const int nbb = E[0].i0;
-        const double floor = d.floor;
-        // broadband chunks, in event order (:162-176)
-        if (RING) {
-            __shared__ double2 seg[3][kChunk + 2 * kHalo];
-            for (int b = 0; b < nbb; ++b) {
-                const rfi_sim_event e = E[1 + b];
-                const int lo = max(e.i0, f0 - kHalo), hi = min(e.i0 + e.i1, f0 + kChunk + kHalo);
-                for (int c = lo + (int)threadIdx.x; c < hi; c += kChunk)
-                    seg[b][c - (f0 - kHalo)] = broadband_field(d, e, b, t, c, sample);
-            }
-            __syncthreads();
-            for (int b = 0; b < nbb; ++b) {
-                const int c0 = E[1 + b].i0, c1 = c0 + E[1 + b].i1;
-                if (active && f >= c0 && f < c1) {
-                    const double2 own = seg[b][f - f0 + kHalo];
-                    m = m || detectable(own, floor);
-                    // np.convolve(row, k, 'same'): out[f] = sum_c row[c] k[f - c + 8], zeros outside the chunk
-                    double2 acc = make_double2(0.0, 0.0);
-                    const int lo = max(c0, f - kHalo), hi = min(c1 - 1, f + kHalo);
-                    for (int c = lo; c <= hi; ++c) {
-                        const double2 v = seg[b][c - f0 + kHalo];
-                        const double k = d.gk[f - c + kHalo];
-                        acc.x = acc.x + v.x * k;
-                        acc.y = acc.y + v.y * k;
-                    }
-                    add(rr, acc);
-                    add(ll, acc);
-                }
-            }
-        } else {
-            for (int b = 0; b < nbb; ++b) {
-                const rfi_sim_event e = E[1 + b];
-                if (active && f >= e.i0 && f < e.i0 + e.i1) {
-                    const double2 v = broadband_field(d, e, b, t, f, sample);
-                    m = m || detectable(v, floor);
-                    add(rr, v);
-                    add(ll, v);
-                }
-            }
-        }
-        // narrowband channels (:178-188): the line value at row t, deposited on its channel or spread +-8 channels
-        // (the channels / rows are fetched 64 at a time, one per lane, and broadcast with readlane: a dependent
-        // scalar load per event would put one memory latency per event on every wave)
-        const int lane = (int)(threadIdx.x & 63);
-        for (int base = 0; base < d.NN; base += 64) {
-            const int mine = base + lane < d.NN ? E[4 + base + lane].i0 : 0;
-            const int cnt = min(64, d.NN - base);
-            for (int j = 0; j < cnt; ++j) {
-                const int k = base + j;
-                const int df = f - __builtin_amdgcn_readlane(mine, j);
-                if (active && (RING ? (df >= -kHalo && df <= kHalo) : df == 0)) {
-                    const rfi_sim_event e = E[4 + k];
-                    const double2 v = narrowband_field(d, e, k, t, sample);
-                    if (df == 0) m = m || detectable(v, floor);
-                    const double2 c = RING ? make_double2(v.x * d.gk[df + kHalo], v.y * d.gk[df + kHalo]) : v;
-                    add(rr, c);
-                    add(ll, c);
-                }
-            }
-        }
-        // burst rows (:190-199)
-        for (int base = 0; base < d.NB; base += 64) {
-            const int mine = base + lane < d.NB ? E[4 + d.NN + base + lane].i0 : 0;
-            const int cnt = min(64, d.NB - base);
-            for (int j = 0; j < cnt; ++j) {
-                const int k = base + j;
-                const int dt = t - __builtin_amdgcn_readlane(mine, j);
-                if (active && (RING ? (dt >= -kHalo && dt <= kHalo) : dt == 0)) {
-                    const rfi_sim_event e = E[4 + d.NN + k];
-                    const double2 v = burst_field(d, e, k, f, sample);
-                    if (dt == 0) m = m || detectable(v, floor);
-                    const double2 c = RING ? make_double2(d.gk[dt + kHalo] * v.x, d.gk[dt + kHalo] * v.y) : v;
-                    add(rr, c);
-                    add(ll, c);
-                }
-            }
-        }
-        // linear sweeps (:201-214): point i = t - start_t, channel int(start_f + slope i) % F
-        for (int k = 0; k < 5; ++k) {
-            const rfi_sim_event e = E[4 + d.NN + d.NB + k];
-            const int i = sweep_point(e, t, T);
-            if (i < T / 2) {
-                const int fi = linear_channel(e, i, F);
-                if (active && f == fi) {
-                    const double amp = sweep_amp(d, i, k, S_LINEAR_PT, sample);
-                    const double2 v = field(amp, phase(e, t, fi));
-                    add(rr, v);
-                    add(ll, v);
-                    m = m || amp > floor;
-                }
-            }
-        }
-        // quadratic sweeps, RR only (:216-228): channel (start_f + (direction t^2) // 100) % F, floor division
-        for (int k = 0; k < 5; ++k) {
-            const rfi_sim_event e = E[9 + d.NN + d.NB + k];
-            const int tt = sweep_point(e, t, T);
-            if (tt < T / 4) {
-                const int fi = quadratic_channel(e, tt, F);
-                if (active && f == fi) {
-                    const double amp = sweep_amp(d, tt, k, S_QUAD_PT, sample);
-                    add(rr, field(amp, phase(e, t, fi)));
-                    m = m || amp > floor;
-                }
-            }
-        }
+        m = gather_events<RING, 1, kChunk>(d, s, sample, t, f0, 0, (int)threadIdx.x, active, g);
         // cross hands (:231-235)
         const U4 x = draw(d, pix, 0, S_CROSS, sample);
         const double frl = u53(x.x, x.y), flr = u53(x.z, x.w);
-        rl.x = rl.x + frl * rr.x;
-        rl.y = rl.y + frl * rr.y;
-        lr.x = lr.x + flr * rr.x;
-        lr.y = lr.y + flr * rr.y;
+        rl.x = rl.x + frl * g.rr.x;
+        rl.y = rl.y + frl * g.rr.y;
+        lr.x = lr.x + flr * g.rr.x;
+        lr.y = lr.y + flr * g.rr.y;
     }
     if (!active) return;
+    const double2 rr = g.rr, ll = g.ll;
     const int64_t plane = (int64_t)T * F, px = (int64_t)t * F + f;
     d.mask[(int64_t)s * plane + px] = m ? 1 : 0;
     switch (d.layout) {
@@ -375,6 +400,139 @@ __global__ __launch_bounds__(kChunk) void rfisim_pixels_kernel(SimDev d) {
         break;
     }
     }
+}
+
+// ---------------------------------------------------------------- injection into planes the simulator did not make
+// rfi_sim_inject (include/rfi_hip.h): the same event table, the same gather and the same draws as above for (seed,
+// first + s), added at the data's own noise scale sigma[s] to visibilities loaded from `data`; stream 8 (noise) is never
+// drawn.  The planes are (T, F) (`CH` false: a workgroup is 256 channels of one row, as above) or (F, T) (`CH` true:
+// simulator pixel (t, f) is element [f, t]).  There neighbouring lanes own neighbouring TIMES, so that a wave still reads
+// and writes whole cache lines of every plane: 256 times of one channel without ringing, and with it a 16 x 16 tile whose
+// 16 rows share one LDS stage of the +-8-channel broadband neighbourhood (each field value is then computed twice per tile,
+// not 17 times; 16 complex128 are 256 contiguous bytes, 16 complex64 one 128-byte line).
+struct InjDev {
+    const void* data;                // (n, 4, R, S) complex128 / complex64; may be SimDev::out (in place)
+    const uint8_t* flags;            // NULL, (n, 4, R, S) or (n, R, S): nonzero = stored as loaded
+    const double* sigma;             // (n,)
+    int flag_pols, cross, c64;
+};
+
+// the injecting kernel's sums: RR and LL start as loaded, S (RR's contributions alone) at zero; c = (sigma v.re, sigma v.im),
+// each product rounded once and then added; t_rr / t_ll: something was added (x + 0 is not relied on to leave x alone)
+struct InjectSink {
+    double sigma;
+    double2 rr, ll, S;
+    bool t_rr, t_ll;
+    __device__ __forceinline__ void par(double2 v) {
+        const double2 c = make_double2(sigma * v.x, sigma * v.y);
+        add(rr, c); add(ll, c); add(S, c);
+        t_rr = true; t_ll = true;
+    }
+    __device__ __forceinline__ void rr_only(double2 v) {
+        const double2 c = make_double2(sigma * v.x, sigma * v.y);
+        add(rr, c); add(S, c);
+        t_rr = true;
+    }
+};
+
+__device__ __forceinline__ double2 widen(double2 z) { return z; }
+__device__ __forceinline__ double2 widen(float2 z) { return make_double2((double)z.x, (double)z.y); }
+__device__ __forceinline__ void narrow(double2 v, double2& z) { z = v; }
+__device__ __forceinline__ void narrow(double2 v, float2& z) { z = make_float2((float)v.x, (float)v.y); }
+
+// Z: the planes' element, double2 or float2.  Only RR and LL are loaded before the gather and only as loaded (their raw
+// values are what an untouched or flagged visibility is stored from: bit for bit, NaN payloads included); RL, LR and the
+// flags are loaded after it, so that the gather's loops run with few registers held across them.
+template <bool RING, bool CH, class Z>
+__global__ __launch_bounds__(kChunk) void rfisim_inject_kernel(SimDev d, InjDev q) {
+    constexpr int TT = CH ? (RING ? 16 : kChunk) : 1, TF = kChunk / TT;
+    const int T = d.T, F = d.F;
+    const int nf = (F + TF - 1) / TF, nt = (T + TT - 1) / TT;
+    const int64_t bid = blockIdx.x;
+    const int cf = (int)(bid % nf);
+    const int64_t rest = bid / nf;
+    const int ct = (int)(rest % nt), s = (int)(rest / nt);
+    const int tid = (int)threadIdx.x;
+    const int lt = CH ? tid % TT : 0, lf = CH ? tid / TT : tid;          // the lane index runs along the planes' last axis
+    const int t0 = ct * TT, f0 = cf * TF, t = t0 + lt, f = f0 + lf;
+    const bool active = t < T && f < F;
+    const unsigned sample = d.first + (unsigned)s;
+    const unsigned pix = active ? (unsigned)t * (unsigned)F + (unsigned)f : 0u;
+    const int64_t plane = (int64_t)T * F, px = active ? (CH ? (int64_t)f * T + t : (int64_t)t * F + f) : 0;
+    const int64_t at = (int64_t)s * 4 * plane + px;
+    const Z* in = reinterpret_cast<const Z*>(q.data);                    // (may be `out`: a thread reads a visibility, then writes it)
+    Z* out = reinterpret_cast<Z*>(d.out);
+
+    Z raw_rr{}, raw_ll{};
+    if (active) {
+        raw_rr = in[at];
+        raw_ll = in[at + 3 * plane];
+    }
+    InjectSink g;
+    g.sigma = q.sigma[s];
+    g.rr = widen(raw_rr);
+    g.ll = widen(raw_ll);
+    g.S = make_double2(0.0, 0.0);
+    g.t_rr = false;
+    g.t_ll = false;
+    const bool m = gather_events<RING, TT, TF>(d, s, sample, t0, f0, lt, lf, active, g);
+    if (!active) return;
+    const Z raw_rl = in[at + plane], raw_lr = in[at + 2 * plane];
+    bool keep[4] = {false, false, false, false};
+    if (q.flags) {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) keep[p] = (q.flag_pols == 4 ? q.flags[at + p * plane] : q.flags[(int64_t)s * plane + px]) != 0;
+    }
+    // cross hands: the factors of the generating kernel's draw
+    const U4 x = draw(d, pix, 0, S_CROSS, sample);
+    const double frl = u53(x.x, x.y), flr = u53(x.z, x.w);
+    double2 rl = widen(raw_rl), lr = widen(raw_lr);
+    bool t_x;
+    if (q.cross == RFI_INJECT_CROSS_REFERENCE) {                        // factor * the whole RR (:233-235)
+        rl.x = rl.x + frl * g.rr.x;
+        rl.y = rl.y + frl * g.rr.y;
+        lr.x = lr.x + flr * g.rr.x;
+        lr.y = lr.y + flr * g.rr.y;
+        t_x = true;
+    } else {                                                            // factor * what was injected into RR
+        t_x = g.t_rr;
+        if (t_x) {
+            rl.x = rl.x + frl * g.S.x;
+            rl.y = rl.y + frl * g.S.y;
+            lr.x = lr.x + flr * g.S.x;
+            lr.y = lr.y + flr * g.S.y;
+        }
+    }
+    d.mask[(int64_t)s * plane + px] = m ? 1 : 0;
+    Z z;
+    narrow(g.rr, z);
+    out[at] = keep[0] || !g.t_rr ? raw_rr : z;
+    narrow(rl, z);
+    out[at + plane] = keep[1] || !t_x ? raw_rl : z;
+    narrow(lr, z);
+    out[at + 2 * plane] = keep[2] || !t_x ? raw_lr : z;
+    narrow(g.ll, z);
+    out[at + 3 * plane] = keep[3] || !g.t_ll ? raw_ll : z;
+}
+
+// dst[i][c][r] = src[i][r][c] for n byte planes of R rows x C columns, through a 64 x 64 LDS tile so that both the reads
+// and the writes of a wave are 64 consecutive bytes (family_masks of a rows="channel" batch)
+constexpr int kTr = 64;
+__global__ __launch_bounds__(256) void rfisim_transpose_bytes_kernel(const uint8_t* __restrict__ src, int R, int Cc, int tiles_r,
+                                                                     int tiles_c, uint8_t* __restrict__ dst) {
+    __shared__ uint8_t tile[kTr][kTr + 1];
+    const int64_t bid = blockIdx.x;
+    const int tc = (int)(bid % tiles_c);
+    const int64_t rest = bid / tiles_c;
+    const int tr = (int)(rest % tiles_r);
+    const int64_t i = rest / tiles_r, plane = (int64_t)R * Cc;
+    const int x = (int)(threadIdx.x & 63), y = (int)(threadIdx.x >> 6);
+    const int r0 = tr * kTr, c0 = tc * kTr;
+    for (int r = y; r < kTr; r += 4)
+        if (r0 + r < R && c0 + x < Cc) tile[r][x] = src[i * plane + (int64_t)(r0 + r) * Cc + c0 + x];
+    __syncthreads();
+    for (int c = y; c < kTr; c += 4)
+        if (c0 + c < Cc && r0 + x < R) dst[i * plane + (int64_t)(c0 + c) * R + r0 + x] = tile[x][c];
 }
 
 // ---------------------------------------------------------------- per-event targets: table, classes, instance masks
@@ -664,6 +822,55 @@ void launch_rfi_sim(rfi_ctx* ctx, unsigned long long seed, unsigned first_sample
     else
         hipLaunchKernelGGL(rfisim_pixels_kernel<false>, dim3((unsigned)blocks), dim3(kChunk), 0, ctx->stream, d);
     check_launch("rfisim_pixels");
+}
+
+int64_t rfi_sim_inject_blocks(int n_samples, int T, int F, int ringing, int rows) {
+    const int TT = rows == RFI_INJECT_ROWS_CHANNEL ? (ringing ? 16 : kChunk) : 1, TF = kChunk / TT;
+    return (int64_t)n_samples * cdiv(T, TT) * cdiv(F, TF);
+}
+
+void launch_rfi_sim_inject(rfi_ctx* ctx, unsigned long long seed, unsigned first_sample, int n_samples, const rfi_sim_params& p,
+                           const double* power_dev, int layout, int rows, int cross_hand, const void* data, const uint8_t* flags,
+                           int flag_pols, const double* sigma, void* out, uint8_t* mask, rfi_sim_event* events, double* baseline_out) {
+    SimDev d = sim_dev(seed, first_sample, n_samples, p, power_dev, events);
+    d.clean = 0;
+    d.layout = layout;
+    d.bl_out = baseline_out;
+    d.out = out;
+    d.mask = mask;
+    InjDev q{};
+    q.data = data;
+    q.flags = flags;
+    q.sigma = sigma;
+    q.flag_pols = flag_pols;
+    q.cross = cross_hand;
+    q.c64 = layout == RFI_SIM_C64 ? 1 : 0;
+    const int64_t px = (int64_t)n_samples * d.T * d.F;
+    ProfScope ps(ctx, FAM_PREPROCESS, 0, (double)px * ((q.c64 ? 64 : 128) + 1 + (flags ? flag_pols : 0)));
+    const int64_t nt = (int64_t)n_samples * d.slots;
+    hipLaunchKernelGGL(rfisim_events_kernel, dim3((unsigned)cdiv(nt, 256)), dim3(256), 0, ctx->stream, d);
+    check_launch("rfisim_events");
+    const bool ring = p.gibbs_ringing != 0, ch = rows == RFI_INJECT_ROWS_CHANNEL;
+    const dim3 grid((unsigned)rfi_sim_inject_blocks(n_samples, d.T, d.F, ring, rows)), block(kChunk);
+    auto launch = [&](auto z) {
+        using Z = decltype(z);
+        if (ring && ch) hipLaunchKernelGGL((rfisim_inject_kernel<true, true, Z>), grid, block, 0, ctx->stream, d, q);
+        else if (ring) hipLaunchKernelGGL((rfisim_inject_kernel<true, false, Z>), grid, block, 0, ctx->stream, d, q);
+        else if (ch) hipLaunchKernelGGL((rfisim_inject_kernel<false, true, Z>), grid, block, 0, ctx->stream, d, q);
+        else hipLaunchKernelGGL((rfisim_inject_kernel<false, false, Z>), grid, block, 0, ctx->stream, d, q);
+    };
+    if (q.c64) launch(float2{});
+    else launch(double2{});
+    check_launch("rfisim_inject");
+}
+
+void launch_rfi_sim_transpose_bytes(rfi_ctx* ctx, const uint8_t* src, int64_t n, int rows, int cols, uint8_t* dst) {
+    const int64_t tr = cdiv(rows, kTr), tc = cdiv(cols, kTr);
+    RFI_REQUIRE(n * tr * tc < ((int64_t)1 << 31), "sim_transpose_planes: batch too large for one launch");
+    ProfScope ps(ctx, FAM_PREPROCESS, 0, 2.0 * (double)n * rows * cols);
+    hipLaunchKernelGGL(rfisim_transpose_bytes_kernel, dim3((unsigned)(n * tr * tc)), dim3(256), 0, ctx->stream, src, rows, cols, (int)tr,
+                       (int)tc, dst);
+    check_launch("rfisim_transpose_bytes");
 }
 
 void launch_rfi_sim_event_table(rfi_ctx* ctx, unsigned long long seed, unsigned first_sample, int n_samples, const rfi_sim_params& p,

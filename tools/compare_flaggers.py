@@ -4,6 +4,7 @@ toolbox exists for ("established statistical methods (TFCROP, RFLAG, AOFlagger)"
 
     python tools/compare_flaggers.py [--source simulator|synthetic] [--samples 8] [--size 256] [--seed 0] [--ntime N]
                                      [--checkpoint unet.pt --width 16 [--sweep]]
+                                     [--background FILE.npy [--background-flags FILE.npy]]
 
 Planes come from ``RFISimulator.generate_batch`` (default) or from ``oracle/synth_ref.generate`` with a fixed event list on
 96 x 160 planes.  Every flagger runs on the device: ``sumthreshold_flags``, ``tfcrop_flags`` and ``rflag_flags``,
@@ -11,7 +12,14 @@ the last two also followed by ``extend_flags`` as CASA users run them, and with 
 ``UNet(3, 1, --width)``.  One table: ``evaluate_segmentation`` against the truth mask and ``compute_ffi`` per flagger.
 ``--sweep`` adds the row ``unet@best-f1``: the same model cut where its f1 is highest instead of at 0.5, the cut found by
 one ``threshold_sweep`` over the probabilities ``predict_flags`` leaves on the device.  That cut is chosen on the very
-planes it is scored on, so the row is the model's ceiling on these planes, not a held-out figure."""
+planes it is scored on, so the row is the model's ceiling on these planes, not a held-out figure.
+
+``--background FILE.npy``: complex ``(B, 4, C, T)`` visibilities of an observation (``MSLoader``'s orientation).  The simulator's
+emitters are added on top at the data's own noise scale (``RFISimulator(T, C).inject(rows="channel")``, ``scale="iqr"``) and
+the table is scored against the injection truth.  ``--background-flags FILE.npy``: the observation's prior flags, ``(B, 4, C, T)``
+or ``(B, C, T)``; flagged and non-finite visibilities are left as they are, reach the flaggers as zeros and are excluded from
+every score.  RFI the background already holds is NOT in the truth: unless the prior flags mark it, a flagger that finds it
+is charged a false positive."""
 import argparse
 import os
 import sys
@@ -35,10 +43,33 @@ def parse(argv=None):
     ap.add_argument("--width", type=int, default=16)
     ap.add_argument("--patch-size", type=int, default=128)
     ap.add_argument("--sweep", action="store_true", help="with --checkpoint: add the model at its best-f1 threshold on these planes")
+    ap.add_argument("--background", default=None, help="complex (B, 4, C, T) .npy: inject the simulator's emitters into these planes")
+    ap.add_argument("--background-flags", default=None, help="prior flags of --background, (B, 4, C, T) or (B, C, T) .npy")
     args = ap.parse_args(argv)
     if args.sweep and not args.checkpoint:
         ap.error("--sweep needs --checkpoint")
+    if args.background_flags and not args.background:
+        ap.error("--background-flags needs --background")
     return args
+
+
+def injected_background(args):
+    """-> (data, truth, valid): --background with the simulator's emitters injected (invalid visibilities zeroed for the
+    flaggers), the injection truth per plane, and which visibilities were valid on input (bool, the ones that are scored)."""
+    from rfi_toolbox_amd.core.simulator import RFISimulator
+    from rfi_toolbox_amd.preprocessing.normalization import invalid_map
+    bg = np.load(args.background)
+    if bg.ndim != 4 or bg.shape[1] != 4 or bg.dtype.kind != "c":
+        raise SystemExit(f"--background must hold complex (B, 4, C, T), got {bg.dtype} {bg.shape}")
+    bg = bg.astype(np.complex64, copy=False)
+    flags = None if args.background_flags is None else np.load(args.background_flags).astype(np.uint8)
+    valid = invalid_map(bg, flags).numpy() == 0
+    B, _, C, T = bg.shape
+    batch = RFISimulator(T, C, seed=args.seed).inject(bg, flags, scale="iqr", rows="channel")
+    data = np.where(valid, batch.data.numpy(), 0).astype(np.complex64)
+    print(f"injected into {B} x 4 planes of {C} channels x {T} times; noise scale per sample: "
+          + " ".join(f"{v:.4g}" for v in batch.noise_scale) + f"; {100 * (1 - valid.mean()):.2f} % invalid on input (not scored)")
+    return data, np.ascontiguousarray(np.repeat(batch.mask.numpy()[:, None], 4, axis=1)), valid
 
 
 def planes_and_truth(args):
@@ -91,12 +122,21 @@ def main(argv=None):
     args = parse(argv)
     from rfi_toolbox_amd.evaluation.metrics import evaluate_segmentation
     from rfi_toolbox_amd.evaluation.statistics import compute_ffi
-    data, truth = planes_and_truth(args)
+    valid = None
+    if args.background:
+        data, truth, valid = injected_background(args)
+    else:
+        data, truth = planes_and_truth(args)
     rows, chosen = [], {}
     for name, run in flaggers(args, truth, chosen):
         flags = run(data)
-        seg = evaluate_segmentation(flags, truth)
-        ffi = compute_ffi(data, flags)
+        if valid is None:
+            seg = evaluate_segmentation(flags, truth)
+            ffi = compute_ffi(data, flags)
+        else:                                                           # only what was valid on input is scored
+            host = np.asarray(flags.numpy() if hasattr(flags, "numpy") else flags).reshape(truth.shape)
+            seg = evaluate_segmentation(host[valid], truth[valid])
+            ffi = compute_ffi(data[valid], host[valid])
         rows.append((name, seg, ffi))
     print(f"{'flagger':<15}{'iou':>8}{'precision':>11}{'recall':>8}{'f1':>8}{'ffi':>8}{'flagged':>9}")
     for name, seg, ffi in rows:
