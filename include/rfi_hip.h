@@ -1139,7 +1139,10 @@ int rfi_op_convt2x2_wgrad(rfi_ctx* ctx, int impl, const float* x, const float* d
  * algorithms: RoIAlign (He et al. 2017; the sampling rules of the public torchvision.ops.roi_align: rois =
  * r x (batch index, x1, y1, x2, y2), bilinear samples, sampling_ratio <= 0 -> ceil(roi extent / bins), `aligned`
  * shifts by half a pixel) over an NHWC float32 feature map, out [r][ph][pw][c]; and the FPN top-down merge (Lin et
- * al. 2017): out = lateral + nearest-neighbour 2x upsampling of top [n][ceil(h/2)][ceil(w/2)][c].  Device pointers. */
+ * al. 2017): out = lateral + nearest-neighbour 2x upsampling of top [n][ceil(h/2)][ceil(w/2)][c].  Device pointers.
+ * RoIs with x2 >= x1 and y2 >= y1 only: a RoI of zero width or height is sampled on its edge (`aligned`; otherwise its extent
+ * is raised to one pixel) and roi_align_backward is the adjoint of that; inverted boxes (x2 < x1 or y2 < y1) are outside the
+ * contract of the forward and the backward pass alike. */
 int rfi_op_roi_align(rfi_ctx* ctx, const float* x, int n, int h, int w, int c, const float* rois, int r,
                      float spatial_scale, int ph, int pw, int sampling_ratio, int aligned, float* out);
 /* roi_align_backward: the gradient w.r.t. the feature map, by gather.  Contract: the RoIs are sorted by batch index
@@ -1173,7 +1176,9 @@ int rfi_op_nms(rfi_ctx* ctx, const float* boxes_sorted, int n, float iou_thresho
  *   deltas of the positives, zeros elsewhere.  Anchors shared by the images (anchor_stride 0: [n][4]) or per image
  *   (anchor_stride = n: [images][n][4] with anchor_count[b] valid rows -- the proposals of the RoI stage; null: all n);
  *   gt_boxes [images][gt_max][4] (gt_max >= 1) with gt_count[b] valid rows; labels / matched [images][n], targets
- *   [images][n][4].  A row beyond anchor_count[b] gets label -2.  best_ws: a workspace of images x gt_max floats on the
+ *   [images][n][4].  A row beyond anchor_count[b] gets label -2.  A zero-area anchor and a zero-area ground truth have no IoU
+ *   (union 0): the pair never matches, so an anchor with nothing but such pairs gets label 0, matched -1 and zero targets, and
+ *   such a ground truth makes no low-quality match.  best_ws: a workspace of images x gt_max floats on the
  *   device that the caller keeps until the stream has passed.  Does not allocate or synchronise.
  * nms_batched: `sets` independent sets of at most k <= 256 boxes, each sorted by descending score ([sets][k][4], count[s]
  *   valid rows) -> keep uint8 [sets][k] (1 kept, 0 suppressed or beyond count). */

@@ -189,11 +189,15 @@ def anchor_match(anchors, gt, hi=0.7, lo=0.3, allow_low_quality=True):
     inter = (iw * ih).astype(f)
     area_g = ((g[:, 2] - g[:, 0]) * (g[:, 3] - g[:, 1])).astype(f)
     area_a = ((a[:, 2] - a[:, 0]) * (a[:, 3] - a[:, 1])).astype(f)
-    iou = (inter / ((area_g[:, None] + area_a[None, :]).astype(f) - inter).astype(f)).astype(f)        # (g, n)
+    with np.errstate(invalid="ignore"):
+        iou = (inter / ((area_g[:, None] + area_a[None, :]).astype(f) - inter).astype(f)).astype(f)    # (g, n)
+    # two zero-area boxes have a union of 0 and no IoU (0 / 0): such a pair never matches, as on the device, where a NaN fails
+    # `v > mv` (mv starts at -1) and fmaxf skips it -- the anchor is labelled 0 unless another ground truth reaches it
+    iou = np.where(np.isnan(iou), f(-1), iou)
     mv, mi = iou.max(0), iou.argmax(0)
     lab = np.where(mv >= f(hi), 1, np.where(mv < f(lo), 0, -1)).astype(np.int8)
     if allow_low_quality:
-        best = iou.max(1)
+        best = np.maximum(iou.max(1), f(0))
         lq = ((iou == best[:, None]) & (iou > 0)).any(0)
         lab[lq] = 1
     matched = np.where(lab == 1, mi, -1).astype(np.int32)

@@ -174,13 +174,21 @@ __global__ __launch_bounds__(256) void roi_align_bwd_gather_kernel(const float* 
                 const RoiGeom g = sg[k];
                 // bins whose samples can touch this pixel (conservative; the exact test is in bin_weight).  A border pixel also
                 // collects the samples clamped onto it from outside the map: it scans to the RoI's end on that side
-                int by0 = (int)floorf(((float)py - 1.0f - g.y1) / g.bh) - 1, by1 = (int)ceilf(((float)py + 1.0f - g.y1) / g.bh) + 1;
-                int bx0 = (int)floorf(((float)px - 1.0f - g.x1) / g.bw) - 1, bx1 = (int)ceilf(((float)px + 1.0f - g.x1) / g.bw) + 1;
-                if (py == 0) by0 = 0;
-                if (py == H - 1) by1 = PH - 1;
-                if (px == 0) bx0 = 0;
-                if (px == W - 1) bx1 = PW - 1;
-                by0 = max(by0, 0); by1 = min(by1, PH - 1); bx0 = max(bx0, 0); bx1 = min(bx1, PW - 1);
+                // A bin size that is not positive and finite (aligned RoIs of zero width or height: every bin's samples sit on
+                // the RoI's edge) has no such range -- the quotient is +-inf or NaN: every bin of that axis is scanned instead
+                int by0 = 0, by1 = PH - 1, bx0 = 0, bx1 = PW - 1;
+                if (g.bh > 0.0f && g.bh < INFINITY) {
+                    by0 = (int)floorf(((float)py - 1.0f - g.y1) / g.bh) - 1; by1 = (int)ceilf(((float)py + 1.0f - g.y1) / g.bh) + 1;
+                    if (py == 0) by0 = 0;
+                    if (py == H - 1) by1 = PH - 1;
+                    by0 = max(by0, 0); by1 = min(by1, PH - 1);
+                }
+                if (g.bw > 0.0f && g.bw < INFINITY) {
+                    bx0 = (int)floorf(((float)px - 1.0f - g.x1) / g.bw) - 1; bx1 = (int)ceilf(((float)px + 1.0f - g.x1) / g.bw) + 1;
+                    if (px == 0) bx0 = 0;
+                    if (px == W - 1) bx1 = PW - 1;
+                    bx0 = max(bx0, 0); bx1 = min(bx1, PW - 1);
+                }
                 const float inv = 1.0f / (float)(g.gh * g.gw > 0 ? g.gh * g.gw : 1);
                 const float* dr = dout + ((int64_t)(r0 + k) * PH * PW) * C + c;
                 for (int by = by0; by <= by1; ++by) {

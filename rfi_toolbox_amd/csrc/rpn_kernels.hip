@@ -139,8 +139,8 @@ __global__ __launch_bounds__(kB) void fastrcnn_loss_kernel(const float* __restri
         for (int j = 1; j < K1; ++j) mx = fmaxf(mx, x[j]);
         float se = 0.0f;
         for (int j = 0; j < K1; ++j) se += expf(x[j] - mx);
-        const float lse = mx + logf(se);
-        s_cls += (double)(lse - x[lab]);
+        const float lg = logf(se), lse = mx + lg;
+        s_cls += (double)((mx - x[lab]) + lg);       // (not lse - x[lab]: lse carries half a float32 step of |mx|, up to 64 x 2^-24 at logits of 80)
         for (int j = 0; j < K1; ++j) g[j] = (expf(x[j] - lse) - (j == lab ? 1.0f : 0.0f)) * inv_R;
         for (int j = 0; j < 4 * K1; ++j) g[K1 + j] = 0.0f;
         if (lab > 0) {
@@ -198,7 +198,9 @@ __global__ __launch_bounds__(kB) void gt_best_iou_batched_kernel(const float* __
 // per anchor: matched ground truth = first argmax of the IoU; label 1 (IoU >= hi, or -- low-quality rule -- the anchor
 // attains some ground truth's best IoU), 0 (IoU < lo), -1 (between); matched index kept for labels 1 only (else -1);
 // regression targets of the positives: encode(gt[matched], anchor) with weights 1, zeros elsewhere.  An entry beyond
-// acount[b] gets label -2 (not a box), matched -1, zero targets
+// acount[b] gets label -2 (not a box), matched -1, zero targets.  Two zero-area boxes have a union of 0 and no IoU (0 / 0 = NaN):
+// the pair never matches -- NaN fails `v > mv`, `v == best` and `v > 0`, and fmaxf in gt_best_iou skips it -- so an anchor whose
+// every IoU is NaN keeps mv = -1: label 0, matched -1, zero targets (oracle/detection_ref.anchor_match follows this rule)
 __global__ __launch_bounds__(kB) void anchor_match_batched_kernel(const float* __restrict__ anchors, int64_t n, int64_t astride,
                                                                  const int* __restrict__ acount, const float* __restrict__ gt, int Gmax,
                                                                  const int* __restrict__ gcount, const float* __restrict__ best, float hi,
