@@ -312,6 +312,12 @@ int rfi_model_algorithmic_flops(rfi_model* m, int n, int h, int w, double* fwd, 
  * inner / layer blocks: the lateral / the pyramid level), "pool" the pooled stem, "block.<b>" the
  * output of Bottleneck b (0..15), "merged.<i>" the top-down merged map of FPN level i (0..3),
  * "dmerged.<i>" its gradient (valid after a backward pass); all NHWC fp32.
+ * Mask head, RPN head and box head (read-only views of buffers the passes keep anyway, fp32):
+ * "y.<i>" the raw output (before ReLU) of 3x3 / FC layer i = 0..layers-1, [n h w][C] or
+ * [R][hidden]; "dy.<i>" its gradient dY_i as a backward pass leaves it (after the ReLU mask);
+ * "u" / "du" the same two of the transposed conv, [n 2h 2w][C] (the mask head only); "dx" the
+ * gradient w.r.t. the input.  A layer index out of range, "u" / "du" on the RPN or box head and
+ * every one of these names on another model are errors.
  * host == NULL only reports the element count. */
 int rfi_model_debug_tensor(rfi_model* m, const char* name, float* host, size_t host_floats,
                            int64_t* n_floats);

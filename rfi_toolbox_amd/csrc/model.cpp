@@ -981,7 +981,8 @@ void UNetModel::set_compute_dtype(int dtype) {
 
 void rfi_model::debug_tensor(const std::string&, const std::string&, int, bool, CallScope&, const float*&, size_t&) {
     throw Error("debug_tensor: this model exposes only logits / dlogits / chan (the U-Net and the ResNet-50-FPN backbone expose their "
-                "own tensors, the ResNet-encoder U-Net its decoder's and, on the bfloat16 flow, its encoder's: see rfi_hip.h)");
+                "own tensors, the ResNet-encoder U-Net its decoder's and, on the bfloat16 flow, its encoder's, the detector heads their "
+                "layer outputs and gradients: see rfi_hip.h)");
 }
 void UNetModel::debug_tensor(const std::string& name, const std::string& base, int idx, bool to_host, CallScope& sc, const float*& src,
                              size_t& n) {

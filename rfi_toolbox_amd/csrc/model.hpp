@@ -536,6 +536,8 @@ struct ConvHeadModel : rfi_model {
     void forward_pass(const float* x_dev, int n, int h, int w, bool train_mode) override;
     void backward_pass(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w) override;
     void algorithmic_flops(int n, int h, int w, double& fwd, double& step) const override;
+    void debug_tensor(const std::string& name, const std::string& base, int idx, bool to_host, rfi::CallScope& sc, const float*& src,
+                      size_t& n) override;
     std::vector<int> mkY, mkG;
     int mkU = -1, mkGU = -1, head_wd = -1, head_w3 = -1, head_wd3 = -1;
     // the 1x1 head as a GEMM on the matrix cores (conv kernels forward / input gradient, weight-gradient kernel) instead of the
@@ -588,5 +590,7 @@ struct BoxHeadModel : rfi_model {
     void forward_pass(const float* x_dev, int n, int h, int w, bool train_mode) override;
     void backward_pass(const float* x_dev, const uint8_t* labels_dev, int n, int h, int w) override;
     void algorithmic_flops(int n, int h, int w, double& fwd, double& step) const override;
+    void debug_tensor(const std::string& name, const std::string& base, int idx, bool to_host, rfi::CallScope& sc, const float*& src,
+                      size_t& n) override;
     std::vector<int> fcY, fcG;        // raw outputs of the FC layers and their gradients
 };

@@ -144,3 +144,24 @@ void ConvHeadModel::algorithmic_flops(int n, int h, int w, double& fwd, double& 
     fwd = depth * 2.0 * M * 9.0 * C * C + (upsample ? 2.0 * M * 4.0 * C * C : 0.0) + 2.0 * s2 * M * C * out_ch;
     step = 3.0 * fwd;                 // the input gradient is computed too (it feeds the RoIAlign adjoint)
 }
+
+// y.<i> / dy.<i>: raw output of 3x3 layer i and, after a backward pass, its gradient dY_i; u / du: the same of the transposed
+// conv (the mask head only); dx: the input gradient.  Read-only views of the buffers the passes keep anyway
+void ConvHeadModel::debug_tensor(const std::string& name, const std::string& base, int idx, bool, CallScope&, const float*& src, size_t& n) {
+    const size_t M = (size_t)pN * pH * pW;
+    RFI_REQUIRE(name.find(':') == std::string::npos, "debug_tensor: the heads' tensors are float32: no padding lanes");
+    if (base == "y" || base == "dy") {
+        RFI_REQUIRE(idx >= 0 && idx < depth, "debug_tensor: layer index out of range");
+        src = buf(base == "y" ? mkY[idx] : mkG[idx]);
+        n = M * in_ch;
+    } else if (name == "u" || name == "du") {
+        RFI_REQUIRE(upsample, "debug_tensor: only the mask head has the transposed conv");
+        src = buf(name == "u" ? mkU : mkGU);
+        n = (size_t)out_scale * out_scale * M * in_ch;
+    } else if (name == "dx") {
+        src = buf(gx);
+        n = M * in_ch;
+    } else {
+        throw Error("debug_tensor: unknown tensor " + name);
+    }
+}

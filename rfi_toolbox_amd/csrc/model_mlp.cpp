@@ -99,3 +99,18 @@ void BoxHeadModel::algorithmic_flops(int n, int, int, double& fwd, double& step)
     fwd = f;
     step = 3.0 * f;
 }
+
+// y.<i> / dy.<i>: raw output of FC layer i and, after a backward pass, its gradient dY_i; dx: the input gradient
+void BoxHeadModel::debug_tensor(const std::string& name, const std::string& base, int idx, bool, CallScope&, const float*& src, size_t& n) {
+    RFI_REQUIRE(name.find(':') == std::string::npos, "debug_tensor: the heads' tensors are float32: no padding lanes");
+    if (base == "y" || base == "dy") {
+        RFI_REQUIRE(idx >= 0 && idx < depth, "debug_tensor: layer index out of range");
+        src = buf(base == "y" ? fcY[idx] : fcG[idx]);
+        n = (size_t)pN * feat;
+    } else if (name == "dx") {
+        src = buf(gx);
+        n = (size_t)pN * in_ch;
+    } else {
+        throw Error("debug_tensor: unknown tensor " + name);
+    }
+}
